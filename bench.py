@@ -99,6 +99,33 @@ class ClockSampler:
         return out or None
 
 
+DUMP_ENTRIES = 2_000_000        # node counts written per --dump-outputs (float64 values + float64 node ids: 32 MB)
+DUMP_SLICES = 4096
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, node_counts):
+    """--dump-outputs: the uint32 node-count vector of the timed steps, as float64 .npy files (exact for these integers),
+    so that two builds run with the same arguments can be compared output for output:
+      node_counts.npy         the counts of the nodes in node_counts_ids.npy
+      node_counts_ids.npy     every node id when there are at most DUMP_ENTRIES of them, else a fixed seeded sample of
+                              DUMP_ENTRIES ids in increasing order (the same for every run with the same index)
+      node_counts_slices.npy  the sums of DUMP_SLICES equal slices of the WHOLE vector: a difference outside the sample
+                              still shows"""
+    os.makedirs(out_dir, exist_ok=True)
+    n = node_counts.shape[0]
+    if n <= DUMP_ENTRIES:
+        ids = np.arange(n, dtype=np.int64)
+    else:
+        ids = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ENTRIES, replace=False))
+    starts = np.unique(np.linspace(0, n, DUMP_SLICES, endpoint=False).astype(np.int64))
+    slices = np.add.reduceat(node_counts, starts, dtype=np.int64) if n else np.zeros(0, np.int64)
+    np.save(os.path.join(out_dir, "node_counts.npy"), node_counts[ids].astype(np.float64))
+    np.save(os.path.join(out_dir, "node_counts_ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(out_dir, "node_counts_slices.npy"), slices.astype(np.float64))
+    log("dumped %d of %d node counts and %d slice sums to %s" % (len(ids), n, len(slices), out_dir))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -155,7 +182,12 @@ def main():
                          "Default (weak): every rank maps --steps batches of --reads reads.")
     ap.add_argument("--max-freq", type=int, default=1000,
                     help="max_index_lookup_frequency (-1 filters every hit: timing ablation without atomics)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the node-count vector they produced (what the caller of the path "
+                         "receives) to DIR as float64 .npy files, <= 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.index_kmers is None:
         args.index_kmers = {1: 10_000_000, 2: 100_000_000}[args.config]
     if args.reads is None:
@@ -306,13 +338,13 @@ def main():
         sizes = [R] * args.steps
     my_kmers = sum(sizes) * max(L - k + 1, 0)
 
-    def step(i):
+    def step(i, n):
         b = batches[i & 1]
-        if sizes[i] != R:
+        if n != R:
             if offs is not None:
-                dev.map_reads(b[:sizes[i] * L], offs[:sizes[i] + 1], k, args.max_freq)
+                dev.map_reads(b[:n * L], offs[:n + 1], k, args.max_freq)
             else:
-                dev.map_reads_uniform(b[:sizes[i] * L], sizes[i], L, k, args.max_freq)
+                dev.map_reads_uniform(b[:n * L], n, L, k, args.max_freq)
             return
         if fastq_batches is not None:
             used, n_rec = dev.map_records(fastq_batches[i & 1], fmt=kmm_lib.FORMAT_FASTQ, k=k,
@@ -367,8 +399,8 @@ def main():
             reduce_node_counts(h, dst=0)
             t.copy_(h)
 
-    for i in range(args.warmup):
-        step(i)
+    for i in range(args.warmup):                    # full batches: --warmup may exceed the number of timed steps
+        step(i, R)
     if world > 1:                                   # warm the communicator the timed reduce will use (the first collective
         reduce_counts(counts)                       # of an RCCL communicator sets up its channels); counts are zeroed below
     fence()
@@ -380,7 +412,7 @@ def main():
     clocks.start()
     t0 = time.perf_counter()
     for i in range(len(sizes)):
-        step(i)
+        step(i, sizes[i])
     dev.synchronize()
     t_map = time.perf_counter()
     clocks.stop()
@@ -431,6 +463,8 @@ def main():
             dev.get_node_counts(out=landing)
             t_ = (time.perf_counter() - td2) * 1e3
             final_d2h_pageable_ms = t_ if final_d2h_pageable_ms is None else min(final_d2h_pageable_ms, t_)
+        if args.dump_outputs:           # the legs below zero the counts: this is the timed steps' own result
+            dump_outputs(args.dump_outputs, landing)
         del landing
     hits = int(counts.to(torch.int64).bitwise_and(0xFFFFFFFF).sum().item()) if rank == 0 else 0
     hbm_free, hbm_total = torch.cuda.mem_get_info(dev_t)

@@ -39,8 +39,12 @@ static std::string gz(const std::string &in, int level, bool bgzf_extra)
 
 static int check(const char *what, const std::string &file, const std::string &expect, int threads)
 {
-    const char *path = "/tmp/kmm_io_tsan.gz";
+    const char *path = "kmm_io_tsan.gz";     // in the working directory: the test runs this in its own tmp_path
     FILE *f = fopen(path, "wb");
+    if (!f) {
+        fprintf(stderr, "%s: cannot write %s\n", what, path);
+        return 1;
+    }
     fwrite(file.data(), 1, file.size(), f);
     fclose(f);
     kmm_io_t *h = kmm_io_open(path, threads);

@@ -164,6 +164,38 @@ def test_bench_line_has_what_the_contract_names():
     assert j["config"]["final_d2h_ms"] > 0 and "numa_node" in j["config"]["numa_binding"]
 
 
+def test_bench_dumps_what_its_timed_steps_computed(tmp_path, oracle):
+    """`bench.py --dump-outputs DIR`: the node counts of the timed steps as float64 .npy files within 64 MB, the same for
+    two runs with the same arguments.  One timed step (a --warmup larger than --steps included) maps batch 0 exactly
+    once, so the dump is the oracle's count vector of those reads."""
+    import torch
+    from kmer_mapper_amd import synthetic as syn
+    args = ["--steps", "1", "--warmup", "2", "--index-kmers", "2000000", "--reads", "600000", "--no-cpu-baseline",
+            "--no-h2d-leg", "--no-records-host-leg"]
+    dumps = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        j = _bench_line(args + ["--dump-outputs", str(out)])
+        assert j["steps"] == 1 and j["config"]["batches_this_rank"] == 1
+        files = sorted(os.listdir(out))
+        assert files == ["node_counts.npy", "node_counts_ids.npy", "node_counts_slices.npy"], files
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        d = {f[:-4]: np.load(out / f) for f in files}
+        assert all(v.dtype == np.float64 for v in d.values())
+        assert abs(d["node_counts_slices"].sum() / (600000 * 120) - j["config"]["hit_rate"]) <= 1e-4
+        dumps.append(d)
+    for key in dumps[0]:
+        assert np.array_equal(dumps[0][key], dumps[1][key]), key
+    index, genome = syn.make_index(2000000, seed=1)          # bench.py's index and batch 0 (numpy builder: same arrays)
+    mx = index.max_node_id()
+    reads = syn.make_reads_torch(torch.from_numpy(syn.ACGT[genome]).to("cuda:0"), 600000, 150, seed=1000).cpu().numpy()
+    expect, _ = oracle.map_reads(index, mx, reads, np.arange(600001, dtype=np.int64) * 150, 31, n_threads=8)
+    d = dumps[0]
+    assert np.array_equal(d["node_counts_ids"], np.arange(mx + 1))     # 2 M nodes: the whole vector
+    assert np.array_equal(d["node_counts"], expect.astype(np.float64))
+    assert d["node_counts_slices"].sum() == expect.sum(dtype=np.int64) > 0
+
+
 def test_bench_line_of_two_ranks_carries_the_strong_and_the_staged_leg():
     """The driver's N > 1 invocation (`torch.distributed.run ... bench.py --gpus N --steps K --warmup W`) rehearsed with
     two ranks on this box's one GPU, the reduce over gloo: weak `value` over both ranks, the configs[3] `strong` leg
