@@ -208,7 +208,7 @@ int kmm_map_records(kmm_index_t *idx, const uint8_t *raw, int64_t n_bytes, int f
  * back with the rest and the same flag).
  * format: KMM_FORMAT_FASTQ or KMM_FORMAT_FASTA2.  A corrupt member (header, Huffman code, distance, ISIZE, CRC32) makes the
  * call fail with KMM_ERR_MALFORMED before anything of the chunk is mapped.  A plain gzip file (no member sizes: `gzip`, not
- * `bgzip`) is refused the same way — inflate it on the host (libkmm_io).  *n_records: reads mapped by this call.
+ * `bgzip`) is refused the same way — kmm_map_gzip below inflates those on the GPU.  *n_records: reads mapped by this call.
  */
 #define KMM_FORMAT_NEW_STREAM 0x400
 /* Optional, before a kmm_map_bgzf call whose chunk is followed in the caller's memory by more of the file (a file mapping):
@@ -218,6 +218,29 @@ int kmm_map_records(kmm_index_t *idx, const uint8_t *raw, int64_t n_bytes, int f
  * the next call does not keep to costs nothing but the copy.  "bgzf_prestaged_calls" (read-only) counts the hints used. */
 int kmm_map_bgzf_hint_next(kmm_index_t *idx, const uint8_t *comp_next, int64_t n_next);
 int kmm_map_bgzf(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int format, int k, int max_index_lookup_frequency,
+                 int also_revcomp, const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
+
+/*
+ * kmm_map_gzip — reads from a PLAIN gzip-compressed FASTQ / two-line FASTA file (what `gzip reads.fq` writes: one deflate
+ * stream, or several members back to back, any header flags), INFLATED ON THE GPU and mapped like kmm_map_bgzf's output.
+ * The deflate stream is cut at speculative block starts (one every ~32 KiB of compressed bytes), one GPU lane decodes each
+ * piece with markers for its unknown 32 KiB of history, a start is kept only where the piece before it ended exactly
+ * there, and the history is resolved afterwards (csrc/kmm_gpu_gunzip.hpp).  The same stream-per-handle contract
+ * as kmm_map_bgzf: format KMM_FORMAT_FASTQ / KMM_FORMAT_FASTA2, OR KMM_FORMAT_NEW_STREAM for a file's first window and
+ * KMM_FORMAT_LAST_CHUNK for its last; comp lies in HOST memory (a file mapping will do) and reaches HBM through the handle's
+ * staging ring; the inflated bytes behind the last complete record are carried to the next call.
+ * comp may be ANY prefix of the rest of the file (at most 2 GiB of it are looked at): the call maps everything up to the
+ * last deflate block boundary it could verify (at most 3.5 GiB of inflated bytes; a call stopped by that limit ignores
+ * KMM_FORMAT_LAST_CHUNK) and returns that point's byte in *consumed_comp — the caller continues there (the bit offset inside
+ * that byte, the last 32 KiB of output and the member's running CRC32 / ISIZE stay in the handle).  A window too short to
+ * hold a whole block consumes nothing: bring a longer one.  KMM_ERR_MALFORMED, with nothing of the window mapped: a bad
+ * header, Huffman code or distance, a distance before the start of the member, a CRC32 or ISIZE mismatch, a file that ends
+ * inside a member (or inside a record) on KMM_FORMAT_LAST_CHUNK, bytes behind a member that are neither zeros nor a member.
+ * Counters: "gzip_calls", "gzip_members", "gzip_chunks", "gzip_false_starts", "gzip_continuations", "gzip_inflated_bytes"
+ * (see kmm_set_param).  The handle keeps the device memory of its symbol slots while a stream lasts and releases it at the
+ * end of the stream (a KMM_FORMAT_LAST_CHUNK call that used the whole file, or an error).
+ */
+int kmm_map_gzip(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int format, int k, int max_index_lookup_frequency,
                  int also_revcomp, const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
 
 /*
@@ -359,6 +382,12 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      bytes of its last member (the rest starts the next rank's first record); each is used once
  *                      (tail: -1 = all, the default).  The boundaries are the caller's business
  *                      (kmer_mapper_amd/bgzf_ranges.py: record-structure resynchronisation on the members around a boundary)
+ *   "debug_gzip_chunk_kb" test hook of kmm_map_gzip: spacing of the chunk search in KiB (0 = the default, 32; a test file of a
+ *                      few MB then has hundreds of chunks).  Read-only: "gzip_calls", "gzip_members" (members whose CRC32 and
+ *                      ISIZE were checked), "gzip_chunks" (speculative starts decoded, every call's first chunk included),
+ *                      "gzip_false_starts" (starts rejected by the predecessor check), "gzip_continuations" (lanes re-run past
+ *                      a rejected start or a full output slot), "gzip_inflated_bytes" (inflated so far: a caller's ratio for
+ *                      sizing its next window)
  *   "comm_overlap_slices" kmm_comm_reduce_counts: node ranges whose flush (per-entry hits -> node counts) runs under the
  *                      previous range's RCCL reduce on a second stream (default 8; 1 = flush, then one reduce).  A
  *                      parameter of the JOB: every rank must use the same value — it alone (with the vector's length)

@@ -212,6 +212,13 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     # (Decided BEFORE a chunker is made: the prefetching one starts a reader thread and page-locks two batch buffers — making
     # and freeing those cost this route 100 ms of its map phase until it was noticed.)
     gpu_inflate = (not seekable and fmt in ("fastq", "fasta") and not os.environ.get("KMM_CLI_NO_GPU_INFLATE") and _is_bgzf(path))
+    # plain gzip (`gzip reads.fq`: one deflate stream, no member sizes), one rank: the stream is inflated on the GPU too
+    # (kmm_map_gzip: speculative block starts, one lane per ~32 KiB of compressed bytes).  Opt-in (KMM_CLI_GPU_GUNZIP=1)
+    # until it beats the host inflater's route on the same box (profiles/gzip_gpu/).
+    gpu_gunzip = (not gpu_inflate and world_size == 1 and not seekable and fmt in ("fastq", "fasta")
+                  and os.environ.get("KMM_CLI_GPU_GUNZIP", "") not in ("", "0")
+                  and not os.environ.get("KMM_CLI_NO_GPU_INFLATE") and _is_gzip(path))
+    gpu_inflate = gpu_inflate or gpu_gunzip
     if early is not None and use_mmap and not gpu_inflate:
         chunker = early
         chunker.chunk_size = batch_bytes
@@ -239,6 +246,11 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "fasta_ml": _lib.FORMAT_FASTA}[fmt]
     t_start = time.perf_counter()
     n_reads = n_bytes = 0
+    if gpu_gunzip:
+        if helper.ident is not None:
+            helper.join()
+        return _map_gzip_file(dev, path, kfmt, k, max_index_lookup_frequency, map_reverse_complements, before_fetch, t_start,
+                              counts_out=prepared.get("counts"))
     if gpu_inflate:
         if helper.ident is not None:
             helper.join()
@@ -314,6 +326,83 @@ def _is_bgzf(path):
     except OSError:
         return False
     return len(h) == 18 and h[:4] == b"\x1f\x8b\x08\x04" and h[12:14] == b"BC" and h[14:16] == b"\x02\x00"
+
+
+def _is_gzip(path):
+    """Does the file start with a gzip member header (RFC 1952: 1f 8b, deflate)?"""
+    try:
+        with open(path, "rb") as f:
+            h = f.read(3)
+    except OSError:
+        return False
+    return h == b"\x1f\x8b\x08"
+
+
+_GZIP_CALL_INFLATED = 3 << 30      # inflated bytes a kmm_map_gzip window is sized for (a call takes at most 3.5 GiB)
+
+
+def _map_gzip_file(dev, path, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None):
+    """`kmer_mapper map -f reads.fq.gz` for PLAIN gzip files with the GPU inflater: windows of the file mapping ->
+    kmm_map_gzip, each call going on where the one before could verify a deflate block boundary."""
+    import mmap
+    n_reads = size = 0
+    logging.info("Route: gzip stream inflated on the GPU (kmm_map_gzip)")
+    try:
+        with open(path, "rb") as f:
+            size = os.fstat(f.fileno()).st_size
+            mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+            try:
+                if hasattr(mm, "madvise") and hasattr(mmap, "MADV_SEQUENTIAL"):
+                    mm.madvise(mmap.MADV_SEQUENTIAL)
+                whole = np.frombuffer(mm, dtype=np.uint8)
+                # windows of ~3 GiB INFLATED: the first from a typical FASTQ ratio, every later one from the ratio of what
+                # the calls before inflated (the trailer's ISIZE is the size mod 2^32: no guide for the large files)
+                inflated0 = dev.get_param("gzip_inflated_bytes")
+                window = int(_GZIP_CALL_INFLATED / 4.5)
+                pos = 0
+                t_calls = time.perf_counter()
+                while pos < size:
+                    end = min(pos + window, size)
+                    if size - end < window // 4:         # (no short tail call: a call's time is its slowest lane's)
+                        end = size
+                    used, n_rec = dev.map_gzip(whole[pos:end], fmt=kfmt, k=k, max_index_lookup_frequency=max_freq,
+                                               also_revcomp=revcomp, first=pos == 0, last=end == size)
+                    n_reads += n_rec
+                    if used == 0:
+                        if end == size:
+                            raise ValueError("trailing bytes of %s are no complete gzip member" % path)
+                        window *= 2                      # no whole deflate block in the window: a longer one
+                        continue
+                    pos += used
+                    ratio = max((dev.get_param("gzip_inflated_bytes") - inflated0) / pos, 1.0)
+                    window = min(max(int(_GZIP_CALL_INFLATED / ratio), 1 << 20), 2 << 30)
+                del whole
+            finally:
+                try:
+                    mm.close()
+                except BufferError:
+                    pass
+        n_lookups, n_hits = dev.get_stats()
+        n_members, n_chunks = dev.get_param("gzip_members"), dev.get_param("gzip_chunks")
+        n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
+        if before_fetch is not None:
+            before_fetch(dev)
+        t_fetch = time.perf_counter()
+        node_counts = dev.get_node_counts(out=counts_out)
+        logging.info("%.0f ms in kmm_map_gzip, %.0f ms more until the node counts were on the host",
+                     (t_fetch - t_calls) * 1e3, (time.perf_counter() - t_fetch) * 1e3)
+    finally:
+        dt = time.perf_counter() - t_start
+        dev.close()
+    logging.info("Time spent only on hashing and counting hashes: %.5f" % dt)
+    logging.info("Mapped %d reads from %d compressed bytes (%.1f MB/s compressed; gzip stream inflated on the GPU: %d members, "
+                 "%d chunks): %d k-mer lookups (%.1f M/s), %d index hits"
+                 % (n_reads, size, size / max(dt, 1e-9) / 1e6, n_members, n_chunks, n_lookups, n_lookups / max(dt, 1e-9) / 1e6,
+                    n_hits))
+    logging.info("path_taken: %s (%d batches on the radix path, %d on the direct path; 0 batches packed to 2 bits per base by "
+                 "the host threads)" % ("radix" if n_radix and not n_direct else "direct" if n_direct and not n_radix else "mixed",
+                                        n_radix, n_direct))
+    return node_counts
 
 
 _BGZF_CALL_INFLATED = 3150 << 20   # inflated bytes per kmm_map_bgzf call: under what a call takes (3.5 GiB; 3.25 GiB for a window staged ahead)

@@ -159,6 +159,7 @@ constexpr unsigned long long NO_BAD = ~0ull;
 #include "kmm_comm.hpp"
 #include "kmm_hostpack.hpp"
 #include "kmm_gpu_inflate.hpp"
+#include "kmm_gpu_gunzip.hpp"
 
 // Page-locked buffers are expensive to make (hipHostMalloc: ~50 ms per GB) and cheap to keep: the ones a handle gives up go
 // to a process-wide shelf (at most 8 GiB), and kmm_host_reserve puts buffers there ahead of time — from another thread,
@@ -299,6 +300,17 @@ struct kmm_index {
     int64_t bgzf_head_skip = 0;  // "bgzf_head_skip": inflated bytes of the next NEW_STREAM call's first member that belong to someone else
     int64_t bgzf_tail_stop = -1; // "bgzf_tail_stop": >= 0: of the next LAST_CHUNK call's last member only this many inflated bytes are taken
     int64_t bgzf_calls = 0, bgzf_members = 0;
+    // kmm_map_gzip: a plain gzip stream inflated on the GPU (kmm_gpu_gunzip.hpp).  The symbol slots come from an arena of
+    // large blocks kept from call to call (a bump pointer per call); the stream's state (bit offset, mode, history length,
+    // CRC register and length of the member in progress) and its last 32 KiB of output (gz_window) carry over.
+    DevBuf gz_comp, gz_raw, gz_carry, gz_window, gz_tabs, gz_meta, gz_res, gz_win, gz_gmaps, gz_gwin, gz_err;
+    std::vector<DevBuf> gz_arena; // (kept while a stream lasts, released when it ends: ~2.5 bytes per inflated byte of a call
+                                  // plus 64 KiB per chunk — 10 GB for a call of 3.3 GB)
+    kmm_gunzip::StreamState gz_state;
+    int64_t gz_carry_len = 0;
+    double gz_ratio = 4.0;        // inflated / compressed bytes of the stream so far (the slots' size)
+    int64_t gzip_calls = 0, gzip_members = 0, gzip_chunks = 0, gzip_false_starts = 0, gzip_continuations = 0, gzip_inflated = 0;
+    int dbg_gzip_chunk_kb = 0;    // test hook ("debug_gzip_chunk_kb"): spacing of the chunk search, KiB (0: 32)
     int dbg_bgzf_slot_kb = 0;     // test hook ("debug_bgzf_ring_slot_kb"): slot size of kmm_map_bgzf's staging ring (a power of two, >= 4)
     int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
@@ -1123,6 +1135,11 @@ void kmm_index_destroy(kmm_index_t *ix)
     release(ix->bgzf_crc);
     release(ix->bgzf_err);
     release(ix->bgzf_carry);
+    for (DevBuf *b : {&ix->gz_comp, &ix->gz_raw, &ix->gz_carry, &ix->gz_window, &ix->gz_tabs, &ix->gz_meta, &ix->gz_res, &ix->gz_win,
+                      &ix->gz_gmaps, &ix->gz_gwin, &ix->gz_err})
+        release(*b);
+    for (DevBuf &b : ix->gz_arena)
+        release(b);
     ix->pack_pool.reset();
     g_shelf.give(ix->pack_pinned, ix->pack_pinned_bytes);
     for (uint8_t *&slot : ix->ring) {
@@ -2880,7 +2897,7 @@ int kmm_map_packed(kmm_index_t *ix, const uint32_t *codes, int64_t n_bases, int6
 // over from the chunk before) and walks the member chain of comp[0, n_comp) behind the copying threads.  cap: inflated bytes
 // the chain may hold.  all: n_comp is where the chunk ends (an incomplete last member ends the chain).
 static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre, int64_t n_comp, uint8_t *d_comp, unsigned long long out_cap,
-                               BgzfStaged &st)
+                               BgzfStaged &st, bool walk = true)
 {
     auto ms_since = [](std::chrono::steady_clock::time_point a) {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
@@ -2897,6 +2914,8 @@ static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre
     chain_err = 0;
     // walks the chain through comp[0, limit); all = the limit is the end of the chunk
     auto scan_upto = [&](uint64_t limit, bool all) {
+        if (!walk) // (kmm_map_gzip: the ring only — a plain gzip stream has no member chain to walk)
+            return;
         while (!chain_end && p + 18 <= limit) {
             const uint32_t ms = kmm_gz::bgzf_member_size(comp + p, limit - p);
             if (!ms) {
@@ -3267,6 +3286,340 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     ix->bgzf_carry_len = tail;
     HIPCHK(hipEventRecord(ix->bgzf_done[cur], ix->stream));
     ix->bgzf_used[cur] = true;
+    return KMM_OK;
+}
+
+// ---- kmm_map_gzip: a plain gzip stream inflated on the GPU (kmm_gpu_gunzip.hpp; the orchestration there, run_call, is shared
+// with the CPU tests).  The backend: buffers of the handle, kernels on its stream, a bump allocator over gz_arena for the slots.
+struct GzGpuBackend {
+    kmm_index_t *ix;
+    double ratio = 4.0;
+    const uint8_t *d_in = nullptr;
+    uint32_t n_pad = 0;
+    uint64_t n = 0;
+    uint8_t *d_out = nullptr; // where the call's inflated bytes go
+    size_t blk = 0, used = 0; // arena block in use, bytes used in it
+    int rc = KMM_OK;
+    uint32_t n_chunks = 0;
+    double ms_find = 0, ms_decode = 0, ms_windows = 0, ms_resolve = 0, ms_crc = 0;
+    int launches = 0;
+
+    bool hip(hipError_t e, const char *what)
+    {
+        if (e == hipSuccess)
+            return true;
+        rc = fail(KMM_ERR_HIP, "kmm_map_gzip: %s: %s", what, hipGetErrorString(e));
+        return false;
+    }
+    bool sync() { return hip(hipStreamSynchronize(ix->stream), "hipStreamSynchronize"); }
+    bool upload(DevBuf &b, const void *p, size_t bytes)
+    {
+        if ((rc = ensure(b, bytes + 64)) != KMM_OK)
+            return false;
+        return hip(hipMemcpyAsync(b.p, p, bytes, hipMemcpyHostToDevice, ix->stream), "upload");
+    }
+    uint16_t *alloc_syms(size_t k)
+    {
+        const size_t bytes = (k * 2 + 255) & ~(size_t)255, BLOCK = (size_t)1 << 30;
+        while (blk < ix->gz_arena.size() && used + bytes > ix->gz_arena[blk].cap) {
+            ++blk;
+            used = 0;
+        }
+        if (blk == ix->gz_arena.size()) {
+            ix->gz_arena.emplace_back();
+            if ((rc = ensure(ix->gz_arena.back(), bytes > BLOCK ? bytes : BLOCK)) != KMM_OK) {
+                ix->gz_arena.pop_back();
+                return nullptr;
+            }
+            used = 0;
+        }
+        uint16_t *p = (uint16_t *)((uint8_t *)ix->gz_arena[blk].p + used);
+        used += bytes;
+        return p;
+    }
+    bool tabs(uint32_t threads)
+    {
+        return (rc = ensure(ix->gz_tabs, (size_t)threads * kmm_gz::SEC_WORDS * 2)) == KMM_OK;
+    }
+    bool find(const uint8_t *, uint64_t, uint64_t S8, uint32_t c0, uint32_t n_cand, uint64_t *starts)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint32_t grid = n_cand < 1024u ? n_cand : 1024u;
+        if (!tabs(grid * 64u) || (rc = ensure(ix->gz_res, (size_t)n_cand * 8 + 64)) != KMM_OK)
+            return false;
+        hipLaunchKernelGGL(kmm_gunzip::k_gz_find, dim3(grid), dim3(64), 0, ix->stream, d_in, n_pad, n, S8, c0, n_cand, (uint16_t *)ix->gz_tabs.p,
+                           (unsigned long long *)ix->gz_res.p);
+        ++launches;
+        if (!hip(hipGetLastError(), "k_gz_find") ||
+            !hip(hipMemcpyAsync(starts, ix->gz_res.p, (size_t)n_cand * 8, hipMemcpyDeviceToHost, ix->stream), "starts") || !sync())
+            return false;
+        ms_find += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    }
+    bool decode(const kmm_gunzip::Work *w, kmm_gunzip::Result *r, size_t k)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        const uint32_t threads = (uint32_t)((k < 65536 ? k : 65536) + 63) / 64u * 64u;
+        if (!tabs(threads) || !upload(ix->gz_meta, w, k * sizeof *w) || (rc = ensure(ix->gz_res, k * sizeof(kmm_gunzip::Result) + 64)) != KMM_OK)
+            return false;
+        hipLaunchKernelGGL(kmm_gunzip::k_gz_decode, dim3(threads / 64u), dim3(64), 0, ix->stream, d_in, n_pad, n,
+                           (const kmm_gunzip::Work *)ix->gz_meta.p, (kmm_gunzip::Result *)ix->gz_res.p, (uint32_t)k, (uint16_t *)ix->gz_tabs.p);
+        ++launches;
+        if (!hip(hipGetLastError(), "k_gz_decode") ||
+            !hip(hipMemcpyAsync(r, ix->gz_res.p, k * sizeof(kmm_gunzip::Result), hipMemcpyDeviceToHost, ix->stream), "results") || !sync())
+            return false;
+        ms_decode += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    }
+    bool windows(const kmm_gunzip::MapRef *maps, uint32_t nc, uint32_t G)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        using kmm_gunzip::WIN;
+        const uint32_t n_groups = (nc + G - 1) / G;
+        n_chunks = nc;
+        if (!upload(ix->gz_meta, maps, nc * sizeof *maps) || (rc = ensure(ix->gz_gmaps, (size_t)n_groups * WIN * 2)) != KMM_OK ||
+            (rc = ensure(ix->gz_gwin, (size_t)n_groups * WIN)) != KMM_OK || (rc = ensure(ix->gz_win, (size_t)nc * WIN)) != KMM_OK)
+            return false;
+        const kmm_gunzip::MapRef *d_maps = (const kmm_gunzip::MapRef *)ix->gz_meta.p;
+        hipLaunchKernelGGL(kmm_gunzip::k_gz_compose, dim3(n_groups), dim3(kmm_gunzip::WT), 0, ix->stream, d_maps, nc, G, (uint16_t *)ix->gz_gmaps.p);
+        hipLaunchKernelGGL(kmm_gunzip::k_gz_chain, dim3(1), dim3(kmm_gunzip::WT), 0, ix->stream, (const uint16_t *)ix->gz_gmaps.p, n_groups,
+                           (const uint8_t *)ix->gz_window.p, (uint8_t *)ix->gz_gwin.p);
+        hipLaunchKernelGGL(kmm_gunzip::k_gz_fix, dim3(n_groups), dim3(kmm_gunzip::WT), 0, ix->stream, d_maps, nc, G, (const uint8_t *)ix->gz_gwin.p,
+                           (uint8_t *)ix->gz_win.p, (uint8_t *)ix->gz_window.p);
+        launches += 3;
+        if (!hip(hipGetLastError(), "window kernels") || !sync())
+            return false;
+        ms_windows += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    }
+    bool resolve(const kmm_gunzip::PieceRef *p, size_t k, uint64_t *bad)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        *bad = 0;
+        if (!k)
+            return true;
+        if (!upload(ix->gz_meta, p, k * sizeof *p) || (rc = ensure(ix->gz_err, 64)) != KMM_OK ||
+            !hip(hipMemsetAsync(ix->gz_err.p, 0, 4, ix->stream), "memset"))
+            return false;
+        const uint32_t grid = k < 65535 ? (uint32_t)k : 65535u;
+        hipLaunchKernelGGL(kmm_gunzip::k_gz_resolve, dim3(grid), dim3(256), 0, ix->stream, (const kmm_gunzip::PieceRef *)ix->gz_meta.p, (uint32_t)k,
+                           (const uint8_t *)ix->gz_win.p, d_out, (unsigned int *)ix->gz_err.p);
+        ++launches;
+        unsigned int e = 0;
+        if (!hip(hipGetLastError(), "k_gz_resolve") || !hip(hipMemcpyAsync(&e, ix->gz_err.p, 4, hipMemcpyDeviceToHost, ix->stream), "err") ||
+            !sync())
+            return false;
+        *bad = e;
+        ms_resolve += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    }
+    bool crc(const kmm_gunzip::Part *p, size_t k, uint32_t *regs)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!upload(ix->gz_meta, p, k * sizeof *p) || (rc = ensure(ix->gz_res, k * 4 + 64)) != KMM_OK)
+            return false;
+        hipLaunchKernelGGL(kmm_gunzip::k_gz_crc, dim3((uint32_t)((k + 255) / 256)), dim3(256), 0, ix->stream, (const uint8_t *)d_out,
+                           (const kmm_gunzip::Part *)ix->gz_meta.p, (uint32_t)k, (const uint32_t *)ix->bgzf_crc.p, (uint32_t *)ix->gz_res.p);
+        ++launches;
+        if (!hip(hipGetLastError(), "k_gz_crc") || !hip(hipMemcpyAsync(regs, ix->gz_res.p, k * 4, hipMemcpyDeviceToHost, ix->stream), "regs") ||
+            !sync())
+            return false;
+        ms_crc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return true;
+    }
+};
+
+static int map_gzip_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
+                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
+
+int kmm_map_gzip(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
+                 const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
+{
+    return guarded("kmm_map_gzip", [&] { return map_gzip_entry(ix, comp, n_comp, format, k, max_freq, also_revcomp, lut, consumed_comp, n_records); });
+}
+
+static int map_gzip_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
+                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
+{
+    if (!ix)
+        return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(check_k(k));
+    bool last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
+    const bool new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
+    const int fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
+    if (fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_map_gzip: format must be KMM_FORMAT_FASTQ (4) or KMM_FORMAT_FASTA2 (2)");
+    if (n_comp < 0 || (n_comp > 0 && !comp))
+        return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
+    if (consumed_comp)
+        *consumed_comp = 0;
+    if (n_records)
+        *n_records = 0;
+    if (n_comp > 0 && is_device_ptr(comp))
+        return fail(KMM_ERR_INVALID_ARG, "kmm_map_gzip takes the compressed bytes from host memory");
+    HIPCHK(hipSetDevice(ix->device));
+    static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
+    const auto t_0 = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point a) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+    };
+    constexpr int64_t MAX_WINDOW = (int64_t)1 << 31;   // compressed bytes one call looks at (the lanes' byte positions are 32-bit)
+    constexpr unsigned long long CALL_CAP = 7ull << 29; // 3.5 GiB of inflated bytes per call, as kmm_map_bgzf
+    bool window_cut = false;
+    if (n_comp > MAX_WINDOW) {
+        n_comp = MAX_WINDOW;
+        window_cut = true;
+    }
+    if (new_stream) {
+        ix->gz_carry_len = 0;
+        ix->gz_state = kmm_gunzip::StreamState();
+        ix->gz_ratio = 4.0;
+    }
+    KMMCHK(ensure(ix->gz_window, kmm_gunzip::WIN));
+    if (new_stream)
+        HIPCHK(hipMemsetAsync(ix->gz_window.p, 0, kmm_gunzip::WIN, ix->stream));
+    if (!ix->bgzf_crc.p) { // the CRC32 tables (slicing by 8), once per handle (shared with kmm_map_bgzf)
+        std::vector<uint32_t> t(kmm_gz::CRC_TABLE_WORDS);
+        for (int kk = 0; kk < 8; ++kk)
+            for (uint32_t bb = 0; bb < 256u; ++bb)
+                t[(size_t)kk * 256 + bb] = kmm_gz::crc_table_entry(kk, bb);
+        for (int kk = 0; kk < kmm_gz::CRC_SHIFT_WORDS; ++kk)
+            t[8 * 256 + kk] = kmm_gz::crc_shift_table_entry(kk);
+        KMMCHK(ensure(ix->bgzf_crc, t.size() * 4));
+        HIPCHK(hipMemcpy(ix->bgzf_crc.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    }
+    // the compressed bytes reach HBM through the page-locked staging ring of kmm_map_bgzf (no member chain to walk)
+    const uint32_t n_pad = (uint32_t)(n_comp < 16 ? 16 : n_comp) + 64u;
+    KMMCHK(ensure(ix->gz_comp, n_pad));
+    HIPCHK(hipStreamSynchronize(ix->stream)); // (the kernels of the call before have let go of gz_comp)
+    uint8_t *d_comp = (uint8_t *)ix->gz_comp.p;
+    HIPCHK(hipMemsetAsync(d_comp + n_comp, 0, n_pad - (uint32_t)n_comp, ix->copy_stream));
+    if (n_comp > 0) {
+        BgzfStaged st;
+        KMMCHK(bgzf_stage_and_scan(ix, comp, 0, n_comp, d_comp, 0, st, false));
+        if (!st.staged)
+            HIPCHK(hipMemcpyAsync(d_comp, comp, (size_t)n_comp, hipMemcpyHostToDevice, ix->copy_stream));
+    }
+    KMMCHK(stage_copies_done(ix));
+    HIPCHK(hipStreamSynchronize(ix->copy_stream));
+    const double ms_stage = ms_since(t_0);
+    // inflate
+    GzGpuBackend be;
+    be.ix = ix;
+    be.ratio = ix->gz_ratio;
+    be.d_in = d_comp;
+    be.n_pad = n_pad;
+    be.n = (uint64_t)n_comp;
+    const int64_t carry = ix->gz_carry_len;
+    // the output: the call inflates into gz_raw behind the carried bytes; its size is known once the chunks stand, so the
+    // buffer is made large enough for the window at the stream's ratio and grown (before any byte lands) if it must be
+    const uint64_t S = ix->dbg_gzip_chunk_kb > 0 ? (uint64_t)ix->dbg_gzip_chunk_kb << 10 : (uint64_t)32 << 10;
+    kmm_gunzip::StreamState state = ix->gz_state;
+    kmm_gunzip::CallOut co;
+    kmm_gunzip::CallStats cs;
+    struct RawBackend : GzGpuBackend {
+        int64_t carry = 0;
+        bool resolve(const kmm_gunzip::PieceRef *p, size_t k, uint64_t *bad)
+        {
+            uint64_t need = 0;
+            for (size_t i = 0; i < k; ++i)
+                need = p[i].off + p[i].n > need ? p[i].off + p[i].n : need;
+            DevBuf &raw = ix->gz_raw;
+            if (raw.cap < (size_t)carry + need + 4096) { // (the carried bytes move along)
+                DevBuf nb;
+                if ((rc = ensure(nb, (size_t)carry + need + need / 8 + 4096)) != KMM_OK)
+                    return false;
+                if (carry > 0 && !hip(hipMemcpyAsync(nb.p, ix->gz_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream), "carry"))
+                    return false;
+                if (!sync())
+                    return false;
+                release(raw);
+                raw = nb;
+            } else if (carry > 0 && !hip(hipMemcpyAsync(raw.p, ix->gz_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream), "carry")) {
+                return false;
+            }
+            d_out = (uint8_t *)raw.p + carry;
+            return GzGpuBackend::resolve(p, k, bad);
+        }
+    } rb;
+    static_cast<GzGpuBackend &>(rb) = be;
+    rb.carry = carry;
+    if (carry == 0 && ix->gz_raw.p == nullptr)
+        KMMCHK(ensure(ix->gz_raw, 4096));
+    const int rr = kmm_gunzip::run_call(rb, comp, (uint64_t)n_comp, last_chunk && !window_cut, S, CALL_CAP - (unsigned long long)carry, state, co, cs);
+    if (rr != 0)
+        return rb.rc != KMM_OK ? rb.rc : fail(KMM_ERR_INTERNAL, "kmm_map_gzip: backend failure");
+    ix->gzip_calls++;
+    ix->gzip_chunks += (int64_t)cs.chunks;
+    ix->gzip_false_starts += (int64_t)cs.false_starts;
+    ix->gzip_continuations += (int64_t)cs.continuations;
+    auto release_arena = [&] { // the stream has ended (or cannot go on): its symbol slots go back to the device
+        for (DevBuf &b : ix->gz_arena)
+            release(b);
+        ix->gz_arena.clear();
+    };
+    if (co.err) {
+        static const char *why[] = {"", "header", "reserved block type", "stored block", "code lengths", "Huffman code", "invalid symbol",
+                                    "distance too far back", "more data than a block can hold", "compressed data ended early",
+                                    "ISIZE mismatch", "CRC32 mismatch"};
+        ix->gz_carry_len = 0;
+        release_arena();
+        return fail(KMM_ERR_MALFORMED, "kmm_map_gzip: corrupt gzip stream near compressed byte %llu of the chunk: %s",
+                    (unsigned long long)co.err_at, co.err < 12 ? why[co.err] : "?");
+    }
+    if (co.hit_cap || window_cut)
+        last_chunk = false; // (the call stops at its own size limit: the caller continues with the same flags)
+    ix->gzip_members += (int64_t)cs.members;
+    ix->gzip_inflated += (int64_t)co.n_out;
+    ix->gz_state = state;
+    if (co.consumed > 0 && co.n_out > 0) {
+        const double r = (double)co.n_out / (double)co.consumed;
+        ix->gz_ratio = r < 1.0 ? 1.0 : r > 1032.0 ? 1032.0 : r;
+    }
+    if (consumed_comp)
+        *consumed_comp = (int64_t)co.consumed;
+    const double ms_inflate = ms_since(t_0) - ms_stage;
+    uint8_t *d_raw = (uint8_t *)ix->gz_raw.p;
+    int64_t n_raw = carry + (int64_t)co.n_out;
+    if (n_raw == 0) {
+        if (last_chunk)
+            release_arena();
+        return KMM_OK;
+    }
+    uint8_t last_byte = 10;
+    if (last_chunk) {
+        HIPCHK(hipMemcpyAsync(&last_byte, d_raw + n_raw - 1, 1, hipMemcpyDeviceToHost, ix->stream));
+        HIPCHK(hipStreamSynchronize(ix->stream));
+        if (last_byte != 10) { // a last line without its newline gets one (as the file readers do)
+            if (ix->gz_raw.cap < (size_t)n_raw + 1)
+                return fail(KMM_ERR_INTERNAL, "kmm_map_gzip: no room for the final newline");
+            HIPCHK(hipMemsetAsync(d_raw + n_raw, 10, 1, ix->stream));
+            ++n_raw;
+        }
+    }
+    int64_t used = 0, recs = 0;
+    KMMCHK(kmm_map_records(ix, d_raw, n_raw, fmt, k, max_freq, also_revcomp, lut, &used, &recs));
+    if (n_records)
+        *n_records = recs;
+    if (verbose)
+        fprintf(stderr, "libkmm: kmm_map_gzip: %lld -> %llu bytes, %llu chunks (%llu false starts, %llu continuations), %d launches: staging %.2f ms, "
+                "inflate %.2f ms (find %.2f, decode %.2f, windows %.2f, resolve %.2f, crc %.2f), records %.2f ms\n",
+                (long long)co.consumed, (unsigned long long)co.n_out, (unsigned long long)cs.chunks, (unsigned long long)cs.false_starts,
+                (unsigned long long)cs.continuations, rb.launches, ms_stage, ms_inflate, rb.ms_find, rb.ms_decode, rb.ms_windows, rb.ms_resolve,
+                rb.ms_crc, ms_since(t_0) - ms_stage - ms_inflate);
+    const int64_t tail = n_raw - used;
+    if (last_chunk && tail > 0) {
+        ix->gz_carry_len = 0;
+        return fail(KMM_ERR_MALFORMED, "kmm_map_gzip: the stream ends with %lld bytes that form no complete record", (long long)tail);
+    }
+    if (tail > 0) {
+        KMMCHK(ensure(ix->gz_carry, (size_t)tail + 64)); // (may free and reallocate: a device-wide sync, rare)
+        HIPCHK(hipMemcpyAsync(ix->gz_carry.p, d_raw + used, (size_t)tail, hipMemcpyDeviceToDevice, ix->stream));
+    }
+    ix->gz_carry_len = tail;
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    if (last_chunk)
+        release_arena();
     return KMM_OK;
 }
 
@@ -3751,6 +4104,11 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value != 0 && (value < 4 || value > (1 << 20) || (value & (value - 1))))
             return fail(KMM_ERR_INVALID_ARG, "debug_ring_slot_kb: 0 or a power of two in [4, 2^20]");
         ix->dbg_bgzf_slot_kb = (int)value;
+    } else if (!strcmp(name, "debug_gzip_chunk_kb")) {
+        // test hook of kmm_map_gzip: spacing of the chunk search in KiB (0 = the default, 32) — a few MB then make hundreds of chunks
+        if (value < 0 || value > (1 << 20))
+            return fail(KMM_ERR_INVALID_ARG, "debug_gzip_chunk_kb outside [0, 2^20]");
+        ix->dbg_gzip_chunk_kb = (int)value;
     } else if (!strcmp(name, "debug_rx_buffer_limit")) {
         // test hook of the out-of-memory route of launch_rx (the call takes more sub-batches until the buffers fit)
         ix->dbg_rx_buf_limit = value;
@@ -3793,6 +4151,20 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->host_packed_record_calls;
     else if (!strcmp(name, "bgzf_prestaged_calls")) // kmm_map_bgzf calls that staged the chunk behind them under their own kernel
         *value = ix->bgzf_prestaged_calls;
+    else if (!strcmp(name, "gzip_calls")) // kmm_map_gzip calls
+        *value = ix->gzip_calls;
+    else if (!strcmp(name, "gzip_members")) // gzip members whose CRC32 / ISIZE kmm_map_gzip checked
+        *value = ix->gzip_members;
+    else if (!strcmp(name, "gzip_chunks")) // speculative starts decoded by kmm_map_gzip (the first chunk of every call included)
+        *value = ix->gzip_chunks;
+    else if (!strcmp(name, "gzip_false_starts")) // starts rejected by the predecessor check
+        *value = ix->gzip_false_starts;
+    else if (!strcmp(name, "gzip_continuations")) // lanes re-run past a rejected start or a full output slot
+        *value = ix->gzip_continuations;
+    else if (!strcmp(name, "gzip_inflated_bytes")) // bytes kmm_map_gzip inflated (callers size their next window from it)
+        *value = ix->gzip_inflated;
+    else if (!strcmp(name, "debug_gzip_chunk_kb"))
+        *value = ix->dbg_gzip_chunk_kb;
     else if (!strcmp(name, "bgzf_members")) // BGZF members inflated on the GPU by kmm_map_bgzf
         *value = ix->bgzf_members;
     else if (!strcmp(name, "bgzf_carry_bytes")) // inflated bytes behind the last complete record, waiting for the next call

@@ -235,6 +235,23 @@ class DeviceIndex:
                                            int(bool(also_revcomp)), t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
         return used.value, n_rec.value
 
+    def map_gzip(self, comp, n_bytes=None, fmt=_lib.FORMAT_FASTQ, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
+                 lut=None, first=False, last=False):
+        """Map a window of a PLAIN gzip-compressed FASTQ (fmt=4) / two-line FASTA (fmt=2) file, inflated on the GPU
+        (kmm_map_gzip).  `comp` is any prefix of the rest of the file; returns (compressed bytes used, records mapped):
+        continue at comp[used:].  first / last mark the file's first / last window (per call: nothing is kept for later)."""
+        b = _Arg(comp, np.uint8, "comp")
+        t = _Arg(lut, np.uint8, "lut")
+        n = b.n if n_bytes is None else int(n_bytes)
+        if n > b.n:
+            raise ValueError("n_bytes exceeds the buffer")
+        used = ctypes.c_int64(0)
+        n_rec = ctypes.c_int64(0)
+        flags = (_lib.FORMAT_NEW_STREAM if first else 0) | (_lib.FORMAT_LAST_CHUNK if last else 0)
+        _lib.check(_lib.lib().kmm_map_gzip(self._h, b.ptr, n, int(fmt) | flags, int(k), int(max_index_lookup_frequency),
+                                           int(bool(also_revcomp)), t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
+        return used.value, n_rec.value
+
     def map_packed(self, codes, n_bases, n_reads, read_len=0, read_starts=None, k=31, max_index_lookup_frequency=1000,
                    also_revcomp=False):
         """Reads held as 2-bit codes (uint32 words, 16 codes per word, first base lowest): kmm_map_packed.  read_len > 0:
