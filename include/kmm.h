@@ -244,6 +244,31 @@ int kmm_map_gzip(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int form
                  int also_revcomp, const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
 
 /*
+ * kmm_map_bam — reads from a BAM file (SAM/BAM specification 4.2; aligned or unaligned), INFLATED AND DECODED ON THE GPU:
+ * replaces `bnp.open(args.reads)` on a .bam + the map of `chunk.sequence` (command_line_interface.py:102,109; bionumpy >= 0.2.7,
+ * pinned by setup.py, opens .bam through its BAM buffer and yields every record's SEQ [UPSTREAM-UNVERIFIED: bionumpy is not
+ * vendored here]).  The same stream-per-handle contract as kmm_map_bgzf: comp lies in HOST memory and starts at a member
+ * boundary; flags = KMM_FORMAT_NEW_STREAM for a file's first window, KMM_FORMAT_LAST_CHUNK for its last (no format value);
+ * the call uses whole members up to 3.5 GiB of inflated bytes and returns *consumed_comp; the inflated bytes behind its last
+ * complete record are carried to the next call; kmm_map_bgzf_hint_next prestages BAM windows too.  On KMM_FORMAT_NEW_STREAM
+ * the header is checked (magic "BAM\1") and skipped (l_text, text, n_ref, the references; it may span many members — a first
+ * window that ends inside it consumes nothing and maps nothing: bring a longer one); n_ref stays in the handle.  Record
+ * starts are found speculatively per 16 KiB tile and verified by a link pass (csrc/kmm_bam.hpp); each record's
+ * SEQ, AS STORED (reverse-strand records are not flipped, as bionumpy does not flip them), goes through the same 256-byte
+ * lookup table as every other entry point (lut NULL: ACGT -> 0123, N -> A, command_line_interface.py:41): "=" and the IUPAC
+ * codes are KMM_ERR_INVALID_BASE at the next synchronising call, exactly as the same letter in a FASTQ.  A record with
+ * l_seq = 0 is a read without k-mers; no k-mer spans two records.  Refused with KMM_ERR_MALFORMED, with nothing of the call
+ * mapped: a bad magic, a header that overruns its lengths, a record whose fields do not fit its block_size (or whose refID /
+ * next_refID lie outside [-1, n_ref), or whose read_name is not NUL-terminated), a corrupt member, a file that ends inside a
+ * member or a record on KMM_FORMAT_LAST_CHUNK.  The handle then takes a new stream.  Extension (default off):
+ * "bam_exclude_flags" drops records with flag & mask (samtools view -F).  *n_records: records mapped by this call.
+ * Counters (kmm_get_param): "bam_calls", "bam_records", "bam_records_excluded", "bam_header_bytes", "bam_false_starts",
+ * "bam_continuations".  SAM text and CRAM are not read.
+ */
+int kmm_map_bam(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int flags, int k, int max_index_lookup_frequency,
+                int also_revcomp, const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
+
+/*
  * kmm_map_packed — reads the caller already holds as 2-BIT CODES (its own encoder, a .2bit-style store, the output of a
  * host-side packer): the same mapping as kmm_map_reads without the byte -> code step, and a quarter of the bytes over
  * PCIe.  This is the form the library's own host packer produces when kmm_map_reads* / kmm_map_records are handed host
@@ -388,6 +413,13 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      "gzip_false_starts" (starts rejected by the predecessor check), "gzip_continuations" (lanes re-run past
  *                      a rejected start or a full output slot), "gzip_inflated_bytes" (inflated so far: a caller's ratio for
  *                      sizing its next window)
+ *   "bam_exclude_flags" kmm_map_bam: records whose FLAG has any of these bits are not mapped (0 = the default: every record,
+ *                      as the reference; 0x900 = no secondary and supplementary alignments).  Read-only: "bam_calls",
+ *                      "bam_records" (mapped), "bam_records_excluded", "bam_header_bytes", "bam_false_starts" (speculative
+ *                      starts the link check rejected), "bam_continuations" (tiles walked again from the exit before them)
+ *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the
+ *                      default, 3.5 GiB) — a small file then reaches the cap.  Read-only "flat_uniform_batches": flat reads
+ *                      of one length that took the uniform / packed front ends of the radix path
  *   "comm_overlap_slices" kmm_comm_reduce_counts: node ranges whose flush (per-entry hits -> node counts) runs under the
  *                      previous range's RCCL reduce on a second stream (default 8; 1 = flush, then one reduce).  A
  *                      parameter of the JOB: every rank must use the same value — it alone (with the vector's length)

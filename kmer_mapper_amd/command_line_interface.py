@@ -122,9 +122,12 @@ def map_gpu(index, chunks, k, hash_map_size=0, map_reverse_complements=False,
 
 
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
-                max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16):
+                max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
+                exclude_flags=0):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
-    (kmm_map_records): the host only reads (and for .gz inflates) raw bytes."""
+    (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
+    on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags")."""
+    _check_bam_route(fmt, world_size, exclude_flags)
     t_index = time.perf_counter()
     # page-locked memory is slow to make (~50 ms per GB): the staging buffers of the host packer are made by a helper thread
     # WHILE the index is uploaded and repacked, not inside the map phase.  (The count vector needs none: kmm_get_node_counts
@@ -219,6 +222,10 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                   and os.environ.get("KMM_CLI_GPU_GUNZIP", "") not in ("", "0")
                   and not os.environ.get("KMM_CLI_NO_GPU_INFLATE") and _is_gzip(path))
     gpu_inflate = gpu_inflate or gpu_gunzip
+    # BAM (told by its content, reads_io.sniff_format): its BGZF members go to the GPU like a .fq.gz's, the records are found
+    # and their SEQ decoded there (kmm_map_bam)
+    bam = fmt == "bam"
+    gpu_inflate = gpu_inflate or bam
     if early is not None and use_mmap and not gpu_inflate:
         chunker = early
         chunker.chunk_size = batch_bytes
@@ -243,9 +250,14 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             logging.debug("packer threads stay on the GPU's node: %s", exc)
     owns = (lambda i: True) if (world_size == 1 or seekable) else (lambda i: chunk_owner(i, world_size) == rank)
     # FASTQ and two-line FASTA are parsed as they are; FASTA with wrapped sequence lines is unwrapped on the GPU first
-    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "fasta_ml": _lib.FORMAT_FASTA}[fmt]
+    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "fasta_ml": _lib.FORMAT_FASTA, "bam": 0}[fmt]
     t_start = time.perf_counter()
     n_reads = n_bytes = 0
+    if bam:
+        if helper.ident is not None:
+            helper.join()
+        return _map_bam_file(dev, path, k, max_index_lookup_frequency, map_reverse_complements, before_fetch, t_start,
+                             counts_out=prepared.get("counts"), exclude_flags=exclude_flags)
     if gpu_gunzip:
         if helper.ident is not None:
             helper.join()
@@ -485,6 +497,80 @@ def _map_bgzf_file(dev, path, kfmt, k, max_freq, revcomp, before_fetch, t_start,
     return node_counts
 
 
+def _check_bam_route(fmt, world_size, exclude_flags):
+    """What the BAM route does not do (yet): several ranks on one file; and the flag filter is BAM's alone."""
+    if fmt == "bam" and world_size > 1:
+        raise ValueError("BAM input is mapped by one rank: sharding a BAM file over %d ranks needs the ranks to resynchronise "
+                         "to its records, which is not implemented (run without torchrun, WORLD_SIZE=1)" % world_size)
+    if exclude_flags and fmt != "bam":
+        raise ValueError("--exclude-flags applies to BAM input only (the reads are %s)" % fmt)
+
+
+def _map_bam_file(dev, path, k, max_freq, revcomp, before_fetch, t_start, comp_batch=None, counts_out=None, exclude_flags=0):
+    """`kmer_mapper map -f reads.bam`: compressed windows of the file mapping -> kmm_map_bam (members inflated, records found and
+    their SEQ decoded on the GPU; the handle carries the bytes behind a window's last complete record to the next one).  Windows
+    as _map_bgzf_file: as few as the inflated size a call takes allows, each one announced to the call before it."""
+    import mmap
+    from . import bgzf_ranges as _br
+    n_reads = size = 0
+    dev.set_param("bam_exclude_flags", int(exclude_flags))
+    try:
+        with open(path, "rb") as f:
+            size = os.fstat(f.fileno()).st_size
+            mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+            try:
+                if hasattr(mm, "madvise") and hasattr(mmap, "MADV_SEQUENTIAL"):
+                    mm.madvise(mmap.MADV_SEQUENTIAL)
+                whole = np.frombuffer(mm, dtype=np.uint8)
+                per_call = int(_BGZF_CALL_INFLATED / max(1.0, _br.inflation_ratio(mm, 0, size)))
+                n_calls = max(1, -(-size // per_call))
+                pos, window = 0, int(comp_batch) if comp_batch else size // n_calls + (1 << 16)
+                t_calls = time.perf_counter()
+                end = min(window, size)
+                while pos < size:
+                    nxt = min(end + window, size)
+                    used, n_rec = dev.map_bam(whole[pos:end], first=pos == 0, last=end == size, k=k, max_index_lookup_frequency=max_freq,
+                                              also_revcomp=revcomp, next_chunk=whole[end:nxt] if nxt > end else None)
+                    if used == 0 and end == size:
+                        raise ValueError("%s: the BAM header or the trailing bytes are no complete BGZF member" % path)
+                    if used == 0 and pos == 0 and end < size:   # a header longer than the window: a longer one
+                        end = nxt
+                        continue
+                    pos += used
+                    n_reads += n_rec
+                    if pos < end and end == size:
+                        continue
+                    end = nxt
+                del whole
+            finally:
+                try:
+                    mm.close()
+                except BufferError:
+                    pass
+        n_lookups, n_hits = dev.get_stats()
+        n_members = dev.get_param("bgzf_members")
+        n_excl, n_false = dev.get_param("bam_records_excluded"), dev.get_param("bam_false_starts")
+        n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
+        if before_fetch is not None:
+            before_fetch(dev)
+        t_fetch = time.perf_counter()
+        node_counts = dev.get_node_counts(out=counts_out)
+        logging.info("%.0f ms in kmm_map_bam, %.0f ms more until the node counts were on the host",
+                     (t_fetch - t_calls) * 1e3, (time.perf_counter() - t_fetch) * 1e3)
+    finally:
+        dt = time.perf_counter() - t_start
+        dev.close()
+    logging.info("Time spent only on hashing and counting hashes: %.5f" % dt)
+    logging.info("Mapped %d BAM records from %d compressed bytes (%.1f MB/s compressed; %d BGZF members inflated and the records "
+                 "decoded on the GPU; %d records excluded by flag, %d false record starts): %d k-mer lookups (%.1f M/s), %d index "
+                 "hits" % (n_reads, size, size / max(dt, 1e-9) / 1e6, n_members, n_excl, n_false, n_lookups,
+                           n_lookups / max(dt, 1e-9) / 1e6, n_hits))
+    logging.info("path_taken: %s (%d batches on the radix path, %d on the direct path; 0 batches packed to 2 bits per base by "
+                 "the host threads)" % ("radix" if n_radix and not n_direct else "direct" if n_direct and not n_radix else "mixed",
+                                        n_radix, n_direct))
+    return node_counts
+
+
 def map_bnp(args):
     if args.debug:
         logging.info("Will print debug log")
@@ -535,12 +621,16 @@ def map_bnp(args):
     logging.info("Rank %d: host side bound to its GPU's NUMA node: %s", rank, bind_to_gpu_numa_node(device))
     revcomp = bool(getattr(args, "map_reverse_complements", False))
     fmt, two_line = sniff_format(args.reads)
+    exclude_flags = int(getattr(args, "exclude_flags", 0) or 0)
+    _check_bam_route(fmt, world, exclude_flags)
+    if fmt == "bam" and getattr(args, "host_parser", False):
+        raise ValueError("--host-parser does not read BAM: its records are decoded on the GPU (drop --host-parser)")
     if not getattr(args, "host_parser", False):
         if fmt == "fasta" and not two_line:
             fmt = "fasta_ml"           # wrapped sequence lines: unwrapped on the GPU (KMM_FORMAT_FASTA)
         node_counts = map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, revcomp, max_freq,
                                   device=device, rank=rank, world_size=world, before_fetch=before_fetch,
-                                  n_threads=args.n_threads)
+                                  n_threads=args.n_threads, exclude_flags=exclude_flags)
     else:
         logging.info("Using the host FASTA/FASTQ parser")
         seekable = not str(args.reads).endswith(".gz")
@@ -587,7 +677,7 @@ def run_argument_parser(args):
     subparser = subparsers.add_parser("map", help="Map reads to a kmer index")
     subparser.add_argument("-i", "--kmer-index", required=False)
     subparser.add_argument("-b", "--index-bundle", required=False)
-    subparser.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz, or fq.gz format")
+    subparser.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz, fq.gz or BAM format")
     subparser.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
     subparser.add_argument("-t", "--n-threads", required=False, default=16, type=int,
                            help="Host threads that read / inflate the reads and pack them to 2 bits per base before they "
@@ -611,6 +701,9 @@ def run_argument_parser(args):
                            help="Extension: parse records on the host instead of on the GPU (kmm_map_records; wrapped FASTA is "
                                 "unwrapped on the GPU too).")
     subparser.add_argument("--device", default=0, type=int, help="Extension: GPU ordinal (single process).")
+    subparser.add_argument("--exclude-flags", default=0, type=lambda v: int(v, 0),
+                           help="Extension, BAM input only: leave out records whose FLAG has any of these bits (samtools view -F; "
+                                "e.g. 0x900 = secondary and supplementary alignments). Default 0: every record, as the reference.")
     subparser.set_defaults(func=map_bnp)
 
     if len(args) == 0:

@@ -160,6 +160,7 @@ constexpr unsigned long long NO_BAD = ~0ull;
 #include "kmm_hostpack.hpp"
 #include "kmm_gpu_inflate.hpp"
 #include "kmm_gpu_gunzip.hpp"
+#include "kmm_bam.hpp"
 
 // Page-locked buffers are expensive to make (hipHostMalloc: ~50 ms per GB) and cheap to keep: the ones a handle gives up go
 // to a process-wide shelf (at most 8 GiB), and kmm_host_reserve puts buffers there ahead of time — from another thread,
@@ -311,6 +312,17 @@ struct kmm_index {
     double gz_ratio = 4.0;        // inflated / compressed bytes of the stream so far (the slots' size)
     int64_t gzip_calls = 0, gzip_members = 0, gzip_chunks = 0, gzip_false_starts = 0, gzip_continuations = 0, gzip_inflated = 0;
     int dbg_gzip_chunk_kb = 0;    // test hook ("debug_gzip_chunk_kb"): spacing of the chunk search, KiB (0: 32)
+    // kmm_map_bam: the BGZF members of a BAM file inflated as for kmm_map_bgzf, the records found and decoded on the GPU
+    // (kmm_bam.hpp): the tiles' claims (two buffers: the link passes read one and write the other), the control words, the
+    // tiles' output offsets and the two-line FASTA the records become.  The stream's reference count (from its header)
+    // validates refID / next_refID of every record.
+    DevBuf bam_tiles[2], bam_bad, bam_base, bam_ctl, bam_out;
+    int32_t bam_n_ref = -1;       // -1: no BAM stream started on this handle
+    uint32_t bam_excl = 0;        // "bam_exclude_flags": records with flag & mask are not mapped (samtools view -F)
+    int64_t bam_calls = 0, bam_records = 0, bam_excluded = 0, bam_header_bytes = 0, bam_false_starts = 0, bam_continuations = 0;
+    int64_t dbg_bgzf_call_cap_kb = 0; // test hook ("debug_bgzf_call_cap_kb"): inflated bytes a kmm_map_bgzf / kmm_map_bam call
+                                      // takes at most, KiB (0: 3.5 GiB)
+    int64_t flat_uniform_batches = 0; // flat reads mapped by the uniform / packed front ends of the radix path (rec_launch_flat)
     int dbg_bgzf_slot_kb = 0;     // test hook ("debug_bgzf_ring_slot_kb"): slot size of kmm_map_bgzf's staging ring (a power of two, >= 4)
     int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
@@ -1135,6 +1147,8 @@ void kmm_index_destroy(kmm_index_t *ix)
     release(ix->bgzf_crc);
     release(ix->bgzf_err);
     release(ix->bgzf_carry);
+    for (DevBuf *b : {&ix->bam_tiles[0], &ix->bam_tiles[1], &ix->bam_bad, &ix->bam_base, &ix->bam_ctl, &ix->bam_out})
+        release(*b);
     for (DevBuf *b : {&ix->gz_comp, &ix->gz_raw, &ix->gz_carry, &ix->gz_window, &ix->gz_tabs, &ix->gz_meta, &ix->gz_res, &ix->gz_win,
                       &ix->gz_gmaps, &ix->gz_gwin, &ix->gz_err})
         release(*b);
@@ -2561,6 +2575,7 @@ static int rec_launch_flat(kmm_index_t *ix, const uint32_t *flat, int64_t total,
     KMMCHK(stage_copies_done(ix));
     if (uniform_len >= 16 && uniform_len * n_reads == total) {
         set_uniform_geometry(ix, rv, uniform_len, k);
+        ix->flat_uniform_batches++;
         if (rv.pk_rpt)
             return launch_rx<MODE_PACKED>(ix, rv, nullptr, 0, k, max_freq, also_revcomp ? 1 : 0);
         return launch_rx<MODE_UNIFORM>(ix, rv, nullptr, 0, k, max_freq, also_revcomp ? 1 : 0);
@@ -2912,6 +2927,8 @@ static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre
     int &chain_err = st.chain_err;
     uint32_t &bad_isize = st.bad_isize, &bad_ms = st.bad_ms;
     chain_err = 0;
+    bad_isize = bad_ms = 0;
+    st.hit_cap = false; // (st may be the handle's prestaged chunk of an earlier call: nothing of that call's chain holds here)
     // walks the chain through comp[0, limit); all = the limit is the end of the chunk
     auto scan_upto = [&](uint64_t limit, bool all) {
         if (!walk) // (kmm_map_gzip: the ring only — a plain gzip stream has no member chain to walk)
@@ -3057,7 +3074,7 @@ int kmm_map_bgzf_hint_next(kmm_index_t *ix, const uint8_t *comp_next, int64_t n_
 }
 
 static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
-                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
+                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records, bool bam = false);
 
 int kmm_map_bgzf(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
                  const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
@@ -3065,17 +3082,24 @@ int kmm_map_bgzf(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int forma
     return guarded("kmm_map_bgzf", [&] { return map_bgzf_entry(ix, comp, n_comp, format, k, max_freq, also_revcomp, lut, consumed_comp, n_records); });
 }
 
+static int bam_map_inflated(kmm_index_t *ix, uint8_t *d_raw, int64_t n_raw, bool new_stream, bool last_chunk, int k, int max_freq,
+                            int also_revcomp, const uint8_t *lut, int64_t *used, int64_t *n_records, bool *short_header);
+
+// bam: the members hold a BAM stream (kmm_map_bam) — the same staging, member chain, inflate and CRC kernels and carry; the
+// inflated bytes then go through bam_map_inflated instead of the text record parser.
 static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
-                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
+                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records, bool bam)
 {
     if (!ix)
         return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
     KMMCHK(check_k(k));
+    const char *who = bam ? "kmm_map_bam" : "kmm_map_bgzf";
     bool last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
     const bool new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
     const int fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
-    if (fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2)
-        return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf: format must be KMM_FORMAT_FASTQ (4) or KMM_FORMAT_FASTA2 (2)");
+    if (bam ? fmt != 0 : fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2)
+        return fail(KMM_ERR_INVALID_ARG, bam ? "kmm_map_bam: flags take KMM_FORMAT_NEW_STREAM and KMM_FORMAT_LAST_CHUNK only"
+                                             : "kmm_map_bgzf: format must be KMM_FORMAT_FASTQ (4) or KMM_FORMAT_FASTA2 (2)");
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
     if (consumed_comp)
@@ -3083,7 +3107,7 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     if (n_records)
         *n_records = 0;
     if (n_comp > 0 && is_device_ptr(comp))
-        return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf takes the compressed bytes from host memory (the member chain is read there)");
+        return fail(KMM_ERR_INVALID_ARG, "%s takes the compressed bytes from host memory (the member chain is read there)", who);
     HIPCHK(hipSetDevice(ix->device));
     if (new_stream)
         ix->bgzf_carry_len = 0;
@@ -3103,7 +3127,9 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     if (!ix->bgzf_done[cur])
         HIPCHK(hipEventCreateWithFlags(&ix->bgzf_done[cur], hipEventDisableTiming));
     const int64_t carry = ix->bgzf_carry_len;
-    constexpr unsigned long long CALL_CAP = 7ull << 29, PRE_CARRY = 256ull << 20; // 3.5 GiB per call; what a prestaged chain leaves for a carry
+    // 3.5 GiB per call; what a prestaged chain leaves for a carry ("debug_bgzf_call_cap_kb": a small file reaches the cap)
+    const unsigned long long CALL_CAP = ix->dbg_bgzf_call_cap_kb > 0 ? (unsigned long long)ix->dbg_bgzf_call_cap_kb << 10 : 7ull << 29,
+                             PRE_CARRY = ix->dbg_bgzf_call_cap_kb > 0 ? CALL_CAP / 4 : 256ull << 20;
     BgzfStaged st;
     bool from_pre = false;
     if (ix->bgzf_pre_valid && ix->bgzf_pre_from == comp && ix->bgzf_pre_n == n_comp && ix->bgzf_pre_buf == cur &&
@@ -3128,10 +3154,10 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     if (st.chain_err) {
         (void)hipStreamSynchronize(ix->copy_stream); // (the page-locked ring is free again)
         if (st.chain_err == 1)
-            return fail(KMM_ERR_MALFORMED, "kmm_map_bgzf: no BGZF member at compressed byte %llu of the chunk (a gzip file that bgzip did "
-                        "not write has no member sizes in its headers: inflate it on the host)", (unsigned long long)p);
-        return fail(KMM_ERR_MALFORMED, "kmm_map_bgzf: member at compressed byte %llu claims %u inflated bytes for %u compressed ones",
-                    (unsigned long long)p, st.bad_isize, st.bad_ms);
+            return fail(KMM_ERR_MALFORMED, "%s: no BGZF member at compressed byte %llu of the chunk (a gzip file that bgzip did "
+                        "not write has no member sizes in its headers: inflate it on the host)", who, (unsigned long long)p);
+        return fail(KMM_ERR_MALFORMED, "%s: member at compressed byte %llu claims %u inflated bytes for %u compressed ones",
+                    who, (unsigned long long)p, st.bad_isize, st.bad_ms);
     }
     std::vector<unsigned long long> &m_off = st.m_off, &o_off = st.o_rel;
     for (unsigned long long &o : o_off) // (the inflated bytes carried over from the call before lie in front)
@@ -3142,7 +3168,7 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
         *consumed_comp = n_used;
     if (last_chunk && n_used != n_comp) {
         (void)hipStreamSynchronize(ix->copy_stream);
-        return fail(KMM_ERR_MALFORMED, "kmm_map_bgzf: the file ends inside a BGZF member (%lld bytes behind the last whole member)",
+        return fail(KMM_ERR_MALFORMED, "%s: the file ends inside a BGZF member (%lld bytes behind the last whole member)", who,
                     (long long)(n_comp - n_used));
     }
     if (n_members == 0 && !(last_chunk && carry > 0)) {
@@ -3224,11 +3250,11 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     // that belongs to the rank before it — "bgzf_head_skip" bytes of the stream's first member are passed over — and its last
     // member holds the start of the next rank's first record — only "bgzf_tail_stop" bytes of the last member are taken.
     int64_t head = 0, n_raw = n_total;
-    if (new_stream) {
+    if (new_stream && !bam) {
         head = ix->bgzf_head_skip;
         ix->bgzf_head_skip = 0;
     }
-    if (last_chunk && ix->bgzf_tail_stop >= 0) {
+    if (last_chunk && ix->bgzf_tail_stop >= 0 && !bam) {
         if (n_members == 0 || (unsigned long long)ix->bgzf_tail_stop > o_off[n_members] - o_off[n_members - 1]) {
             (void)hipStreamSynchronize(ix->stream);
             return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf: bgzf_tail_stop %lld lies beyond the last member's %llu bytes",
@@ -3256,28 +3282,40 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
                                     "distance too far back", "more data than ISIZE", "compressed data ended early", "less data than ISIZE",
                                     "CRC32 mismatch"};
         ix->bgzf_carry_len = 0;
-        return fail(KMM_ERR_MALFORMED, "kmm_map_bgzf: %u corrupt BGZF member(s); the first starts at compressed byte %llu of the chunk: %s",
-                    err[0], err[1] < n_members ? m_off[err[1]] : 0ull, err[2] < 12 ? why[err[2]] : "?");
+        return fail(KMM_ERR_MALFORMED, "%s: %u corrupt BGZF member(s); the first starts at compressed byte %llu of the chunk: %s",
+                    who, err[0], err[1] < n_members ? m_off[err[1]] : 0ull, err[2] < 12 ? why[err[2]] : "?");
     }
-    if (last_chunk && n_raw > head && last_byte != 10) { // a last line without its newline gets one (as the file readers do)
+    if (!bam && last_chunk && n_raw > head && last_byte != 10) { // a last line without its newline gets one (as the file readers do)
         HIPCHK(hipMemsetAsync(d_raw + n_raw, 10, 1, ix->stream));
         ++n_raw;
     }
     int64_t used = 0, recs = 0;
-    if (n_raw > head)
+    if (bam) {
+        bool short_header = false;
+        const int rc = bam_map_inflated(ix, d_raw, n_raw, new_stream, last_chunk, k, max_freq, also_revcomp, lut, &used, &recs, &short_header);
+        if (rc != KMM_OK || short_header) { // (an error, or a first window that ends inside the header: nothing used, nothing kept)
+            ix->bgzf_carry_len = 0;
+            ix->bgzf_pre_valid = false;
+            if (consumed_comp)
+                *consumed_comp = 0;
+            HIPCHK(hipEventRecord(ix->bgzf_done[cur], ix->stream));
+            ix->bgzf_used[cur] = true;
+            return rc;
+        }
+    } else if (n_raw > head)
         KMMCHK(kmm_map_records(ix, d_raw + head, n_raw - head, fmt, k, max_freq, also_revcomp, lut, &used, &recs));
     used += head;
     if (n_records)
         *n_records = recs;
     if (verbose)
-        fprintf(stderr, "libkmm: kmm_map_bgzf: %u members, %lld -> %lld bytes: member scan %.2f ms, buffers + staging + copy %.2f ms%s, "
-                "copy tail + inflate kernel%s %.2f ms, records %.2f ms\n", n_members, (long long)n_used, (long long)n_total, ms_scan, ms_stage,
+        fprintf(stderr, "libkmm: %s: %u members, %lld -> %lld bytes: member scan %.2f ms, buffers + staging + copy %.2f ms%s, "
+                "copy tail + inflate kernel%s %.2f ms, records %.2f ms\n", who, n_members, (long long)n_used, (long long)n_total, ms_scan, ms_stage,
                 from_pre ? " (staged and walked under the call before)" : "", ix->bgzf_pre_valid ? " + the next chunk's staging" : "",
                 ms_inflate, ms_since(t_0) - ms_scan - ms_stage - ms_inflate);
     const int64_t tail = n_raw - used;
     if (last_chunk && tail > 0) {
         ix->bgzf_carry_len = 0;
-        return fail(KMM_ERR_MALFORMED, "kmm_map_bgzf: the stream ends with %lld bytes that form no complete record", (long long)tail);
+        return fail(KMM_ERR_MALFORMED, "%s: the stream ends with %lld bytes that form no complete record", who, (long long)tail);
     }
     if (tail > 0) {
         KMMCHK(ensure(ix->bgzf_carry, (size_t)tail + 64)); // (may free and reallocate: a device-wide sync, rare)
@@ -3287,6 +3325,151 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     HIPCHK(hipEventRecord(ix->bgzf_done[cur], ix->stream));
     ix->bgzf_used[cur] = true;
     return KMM_OK;
+}
+
+// ---- kmm_map_bam: BAM records found and decoded on the GPU (kmm_bam.hpp; the orchestration there, run_call, is shared with the
+// CPU tests).  The backend: the handle's bam_* buffers, kernels on its stream.
+struct BamGpuBackend {
+    kmm_index_t *ix;
+    const uint8_t *d;
+    uint64_t n;
+    int32_t n_ref;
+    uint32_t excl;
+    int cur = 0;
+
+    kmm_bam::Tile *tiles(int i) { return (kmm_bam::Tile *)ix->bam_tiles[i].p; }
+    kmm_bam::Ctl *ctl() { return (kmm_bam::Ctl *)ix->bam_ctl.p; }
+    dim3 wave_grid(uint64_t n_tiles) { return dim3((unsigned)grid_for(ix, (int64_t)((n_tiles + 3) / 4), 16)); } // 4 waves per block
+    dim3 lane_grid(uint64_t n_tiles) { return dim3((unsigned)grid_for(ix, (int64_t)((n_tiles + 255) / 256), 16)); }
+
+    int spec(uint64_t n_tiles, uint64_t start0)
+    {
+        for (DevBuf &b : ix->bam_tiles)
+            KMMCHK(ensure(b, (size_t)n_tiles * sizeof(kmm_bam::Tile) + 64));
+        KMMCHK(ensure(ix->bam_bad, (size_t)n_tiles + 64));
+        KMMCHK(ensure(ix->bam_base, (size_t)n_tiles * 8 + 64));
+        KMMCHK(ensure(ix->bam_ctl, 256));
+        cur = 0;
+        HIPCHK(hipMemsetAsync(ctl(), 0, sizeof(kmm_bam::Ctl), ix->stream));
+        HIPCHK(hipMemsetAsync(&ctl()->err_pos, 0xFF, 8, ix->stream)); // (no error)
+        hipLaunchKernelGGL(kmm_bam::k_bam_spec, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl, tiles(0));
+        HIPCHK(hipGetLastError());
+        return KMM_OK;
+    }
+    int check(uint64_t n_tiles, uint64_t start0, kmm_bam::Ctl &h)
+    {
+        HIPCHK(hipMemsetAsync(&ctl()->n_bad, 0, 8, ix->stream));
+        HIPCHK(hipMemsetAsync(&ctl()->first_bad, 0xFF, 8, ix->stream));
+        hipLaunchKernelGGL(kmm_bam::k_bam_check, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref,
+                           (const kmm_bam::Tile *)tiles(cur), (uint8_t *)ix->bam_bad.p, ctl());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&h, ctl(), sizeof h, hipMemcpyDeviceToHost, ix->stream));
+        HIPCHK(hipStreamSynchronize(ix->stream));
+        return KMM_OK;
+    }
+    int fix(uint64_t n_tiles, uint64_t start0)
+    {
+        hipLaunchKernelGGL(kmm_bam::k_bam_fix, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl,
+                           (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
+        HIPCHK(hipGetLastError());
+        cur ^= 1;
+        return KMM_OK;
+    }
+    int totals(uint64_t n_tiles, uint64_t start0, kmm_bam::Totals &h)
+    {
+        kmm_bam::Totals *d_tot = (kmm_bam::Totals *)((uint8_t *)ix->bam_ctl.p + 128);
+        hipLaunchKernelGGL(kmm_bam::k_bam_totals, dim3(1), dim3(1024), 0, ix->stream, (const kmm_bam::Tile *)tiles(cur), n_tiles, start0,
+                           (unsigned long long *)ix->bam_base.p, d_tot);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&h, d_tot, sizeof h, hipMemcpyDeviceToHost, ix->stream));
+        HIPCHK(hipStreamSynchronize(ix->stream));
+        return KMM_OK;
+    }
+    int decode(uint64_t n_tiles, uint8_t *out)
+    {
+        hipLaunchKernelGGL(kmm_bam::k_bam_decode, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
+                           (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out);
+        HIPCHK(hipGetLastError());
+        return KMM_OK;
+    }
+};
+
+// The inflated bytes of a kmm_map_bam call (d_raw[0, n_raw): the carry of the call before in front): the header on a stream's
+// first call, then the records up to the last complete one (*used), decoded into two-line FASTA in HBM and mapped by
+// kmm_map_records.  *short_header: a first window that ends inside the header (nothing is used).
+static int bam_map_inflated(kmm_index_t *ix, uint8_t *d_raw, int64_t n_raw, bool new_stream, bool last_chunk, int k, int max_freq,
+                            int also_revcomp, const uint8_t *lut, int64_t *used, int64_t *n_records, bool *short_header)
+{
+    *used = 0;
+    *n_records = 0;
+    *short_header = false;
+    uint64_t start0 = 0;
+    if (new_stream) {
+        // the header (magic, l_text, text, n_ref, the references) is read back in growing prefixes: its length is only known by
+        // walking it, and it is read once per stream
+        ix->bam_n_ref = -1;
+        std::vector<uint8_t> h;
+        uint64_t want = n_raw < (1 << 16) ? (uint64_t)n_raw : 1u << 16, hdr_end = 0;
+        int32_t n_ref = 0;
+        for (;;) {
+            h.resize(want);
+            if (want)
+                HIPCHK(hipMemcpyAsync(h.data(), d_raw, want, hipMemcpyDeviceToHost, ix->stream));
+            HIPCHK(hipStreamSynchronize(ix->stream));
+            const int r = kmm_bam::parse_header(h.data(), want, &hdr_end, &n_ref);
+            if (r < 0)
+                return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the stream does not start with a BAM header (magic \"BAM\\1\", lengths)");
+            if (r == 0)
+                break;
+            if (want == (uint64_t)n_raw) {
+                if (last_chunk)
+                    return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside the BAM header (%lld bytes)", (long long)n_raw);
+                *short_header = true;
+                return KMM_OK;
+            }
+            want = want * 4 < (uint64_t)n_raw ? want * 4 : (uint64_t)n_raw;
+        }
+        ix->bam_n_ref = n_ref;
+        ix->bam_header_bytes += (int64_t)hdr_end;
+        start0 = hdr_end;
+    } else if (ix->bam_n_ref < 0) {
+        return fail(KMM_ERR_INVALID_ARG, "kmm_map_bam: no BAM stream was started on this handle (KMM_FORMAT_NEW_STREAM)");
+    }
+    BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl};
+    kmm_bam::CallOut co;
+    KMMCHK(kmm_bam::run_call(be, (uint64_t)n_raw, start0, co));
+    ix->bam_false_starts += (int64_t)co.false_starts;
+    ix->bam_continuations += (int64_t)co.continuations;
+    if (co.err_pos != kmm_bam::NONE)
+        return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the record at inflated byte %llu of the call does not fit its block_size (or its "
+                    "refID / next_refID / read_name are not a record's)", co.err_pos);
+    if (last_chunk && co.consumed != (uint64_t)n_raw)
+        return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside a record (%lld bytes behind the last complete one)",
+                    (long long)(n_raw - (int64_t)co.consumed));
+    ix->bam_calls++;
+    ix->bam_records += (int64_t)co.recs;
+    ix->bam_excluded += (int64_t)co.excluded;
+    *used = (int64_t)co.consumed;
+    if (co.recs == 0)
+        return KMM_OK;
+    KMMCHK(ensure(ix->bam_out, (size_t)co.out_bytes + 64));
+    KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p));
+    int64_t taken = 0, recs = 0;
+    KMMCHK(kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, KMM_FORMAT_FASTA2, k, max_freq, also_revcomp, lut,
+                           &taken, &recs));
+    if (taken != (int64_t)co.out_bytes || recs != (int64_t)co.recs)
+        return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %llu decoded bytes, %lld of %llu records mapped", (long long)taken,
+                    co.out_bytes, (long long)recs, co.recs);
+    *n_records = recs;
+    return KMM_OK;
+}
+
+int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags, int k, int max_freq, int also_revcomp,
+                const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
+{
+    return guarded("kmm_map_bam", [&] {
+        return map_bgzf_entry(ix, comp, n_comp, flags, k, max_freq, also_revcomp, lut, consumed_comp, n_records, true);
+    });
 }
 
 // ---- kmm_map_gzip: a plain gzip stream inflated on the GPU (kmm_gpu_gunzip.hpp; the orchestration there, run_call, is shared
@@ -4104,6 +4287,15 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value != 0 && (value < 4 || value > (1 << 20) || (value & (value - 1))))
             return fail(KMM_ERR_INVALID_ARG, "debug_ring_slot_kb: 0 or a power of two in [4, 2^20]");
         ix->dbg_bgzf_slot_kb = (int)value;
+    } else if (!strcmp(name, "bam_exclude_flags")) {
+        if (value < 0 || value > 0xFFFF)
+            return fail(KMM_ERR_INVALID_ARG, "bam_exclude_flags outside [0, 0xFFFF]");
+        ix->bam_excl = (uint32_t)value;
+    } else if (!strcmp(name, "debug_bgzf_call_cap_kb")) {
+        // test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, KiB (0 = the default, 3.5 GiB)
+        if (value < 0 || value > (7ll << 19))
+            return fail(KMM_ERR_INVALID_ARG, "debug_bgzf_call_cap_kb outside [0, 3.5 GiB / 1 KiB]");
+        ix->dbg_bgzf_call_cap_kb = value;
     } else if (!strcmp(name, "debug_gzip_chunk_kb")) {
         // test hook of kmm_map_gzip: spacing of the chunk search in KiB (0 = the default, 32) — a few MB then make hundreds of chunks
         if (value < 0 || value > (1 << 20))
@@ -4165,6 +4357,24 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->gzip_inflated;
     else if (!strcmp(name, "debug_gzip_chunk_kb"))
         *value = ix->dbg_gzip_chunk_kb;
+    else if (!strcmp(name, "bam_calls")) // kmm_map_bam calls that mapped their records (a window inside the header not counted)
+        *value = ix->bam_calls;
+    else if (!strcmp(name, "bam_records")) // BAM records mapped
+        *value = ix->bam_records;
+    else if (!strcmp(name, "bam_records_excluded")) // BAM records left out by "bam_exclude_flags"
+        *value = ix->bam_excluded;
+    else if (!strcmp(name, "bam_header_bytes")) // inflated bytes of the BAM headers read
+        *value = ix->bam_header_bytes;
+    else if (!strcmp(name, "bam_false_starts")) // speculative record starts found wrong by the link check
+        *value = ix->bam_false_starts;
+    else if (!strcmp(name, "bam_continuations")) // tiles walked again from the exit before them
+        *value = ix->bam_continuations;
+    else if (!strcmp(name, "bam_exclude_flags"))
+        *value = ix->bam_excl;
+    else if (!strcmp(name, "debug_bgzf_call_cap_kb"))
+        *value = ix->dbg_bgzf_call_cap_kb;
+    else if (!strcmp(name, "flat_uniform_batches")) // flat reads of one length mapped by the uniform / packed front ends
+        *value = ix->flat_uniform_batches;
     else if (!strcmp(name, "bgzf_members")) // BGZF members inflated on the GPU by kmm_map_bgzf
         *value = ix->bgzf_members;
     else if (!strcmp(name, "bgzf_carry_bytes")) // inflated bytes behind the last complete record, waiting for the next call

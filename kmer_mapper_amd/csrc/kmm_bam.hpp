@@ -1,0 +1,570 @@
+// kmm_bam.hpp — part of libkmm: BAM records (SAM/BAM specification 4.2) found and decoded ON THE GPU (kmm_map_bam; included by
+// kmm.hip, compiled by itself with g++ in tests/test_bam_walk_on_the_cpu.py, where the very same orchestration runs on the CPU).
+//
+// A BAM file is a BGZF stream (kmm_gpu_inflate.hpp inflates it) holding a header and then records, each one prefixed by its
+// length: where a record starts is known only by walking the chain from the first one — a serial chain.  It is cut the way
+// kmm_gpu_gunzip.hpp cuts a deflate stream:
+//   1. spec     the inflated bytes are cut into tiles of TILE bytes; one wavefront per tile tests 64 byte positions at a time
+//               for a plausible record start (fields consistent with block_size, the name NUL-terminated, -1 <= refID,
+//               next_refID < n_ref, and CHAIN such records in a row) and one lane walks the chain from the first one to the
+//               first start at or past the tile's end: the tile's claim (entry, exit, records).  Tile 0 starts where it is
+//               known to (behind the header, or at the bytes carried over from the call before).  A tile with no plausible
+//               start claims to lie inside one record (long reads) — the exit passes through it;
+//   2. link     a tile's claim stands iff it agrees with the exit of the tiles before it (check); the claims that do not are
+//               walked again from that exit (fix) — follow-up launches until every claim agrees.  A fix from an exit that is
+//               itself verified (the first disagreeing tile) is exact: a malformed record met there is an error of the file;
+//   3. totals   records, excluded records (the flag filter), the output offset of every tile (an exclusive scan), the exit;
+//   4. decode   one wavefront per tile walks its records again and writes every kept record as two-line FASTA (">\n" SEQ
+//               "\n": the 4-bit codes =ACMGRSVTWYHKDBN as letters), 64 lanes over a record's bases.  The library maps that with
+//               kmm_map_records: the LUT, the invalid-base rule, the radix / direct choice and the uniform-length path are
+//               the ones every other input takes.
+// Exactness never depends on the plausibility test: a wrong guess only costs a fix.  Every read is bounds-checked against n.
+#pragma once
+
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define KMM_BAM_HD __host__ __device__ __forceinline__
+#else
+#define KMM_BAM_HD inline
+#endif
+
+namespace kmm_bam {
+
+constexpr uint64_t NONE = ~0ull;        // claim: no record starts in the tile (the exit of the tiles before passes through)
+constexpr uint64_t INVALID = ~0ull - 1; // claim: the walk from the tile's start met a malformed record (never agrees)
+constexpr uint32_t TILE = 16384;
+constexpr int CHAIN = 4;
+enum Rec { REC_OK = 0, REC_SHORT = 1, REC_BAD = 2 };
+
+// One tile's claim: records starting in [entry, exit) (entry NONE / INVALID: see above); bytes = its kept records' output.
+struct Tile {
+    uint64_t entry, exit;
+    uint32_t recs, excluded, bytes, spec; // spec: the claim comes from the speculative pass
+};
+
+// Host <-> device control words of the link passes (one struct, read back after every check).
+struct Ctl {
+    unsigned long long n_bad;        // claims that disagree, this pass
+    unsigned long long first_bad;    // the first of them (its predecessors are verified)
+    unsigned long long err_pos;      // a malformed record met from a verified start (NONE: none)
+    unsigned long long false_starts; // speculative starts found to be wrong
+};
+
+struct Totals {
+    unsigned long long recs, excluded, out_bytes, exit;
+};
+
+KMM_BAM_HD uint32_t rd32(const uint8_t *p)
+{
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+KMM_BAM_HD uint32_t rd16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+
+struct RecHead {
+    uint32_t bs, l_name, n_cigar, flag, l_seq;
+};
+
+// The record at d[p]: REC_OK (h filled), REC_SHORT (it does not end inside d[0, n)), REC_BAD (its fields cannot be a record's).
+KMM_BAM_HD int record_at(const uint8_t *d, uint64_t n, uint64_t p, int32_t n_ref, RecHead &h)
+{
+    if (p > n || n - p < 4) // (overflow-safe: p may be any claim)
+        return REC_SHORT;
+    const uint32_t bs = rd32(d + p);
+    if (bs < 32u || bs >= 0x80000000u)
+        return REC_BAD;
+    if (n - p - 4 < bs)
+        return REC_SHORT;
+    const int32_t ref = (int32_t)rd32(d + p + 4), next_ref = (int32_t)rd32(d + p + 24);
+    const uint32_t l_name = d[p + 12], n_cigar = rd16(d + p + 16), flag = rd16(d + p + 18), l_seq = rd32(d + p + 20);
+    if (ref < -1 || ref >= n_ref || next_ref < -1 || next_ref >= n_ref || l_name == 0 || l_seq >= 0x80000000u)
+        return REC_BAD;
+    if (32ull + l_name + 4ull * n_cigar + (l_seq + 1ull) / 2 + l_seq > (uint64_t)bs)
+        return REC_BAD;
+    if (d[p + 35 + l_name] != 0) // (read_name[l_read_name - 1]; inside the record: 32 + l_name <= bs)
+        return REC_BAD;
+    h.bs = bs;
+    h.l_name = l_name;
+    h.n_cigar = n_cigar;
+    h.flag = flag;
+    h.l_seq = l_seq;
+    return REC_OK;
+}
+
+KMM_BAM_HD uint64_t seq_offset(const RecHead &h) { return 36ull + h.l_name + 4ull * h.n_cigar; }
+
+// Could a record start at d[c]?  It is whole and consistent, and so are the CHAIN - 1 behind it (or the data ends there).
+KMM_BAM_HD bool plausible(const uint8_t *d, uint64_t n, uint64_t c, int32_t n_ref)
+{
+    uint64_t p = c;
+    for (int i = 0; i < CHAIN; ++i) {
+        RecHead h;
+        const int r = record_at(d, n, p, n_ref, h);
+        if (r == REC_BAD)
+            return false;
+        if (r == REC_SHORT)
+            return i > 0;
+        p += 4ull + h.bs;
+    }
+    return true;
+}
+
+struct Walk {
+    uint64_t exit;
+    uint32_t recs, excluded, bytes;
+    bool bad;
+};
+
+// The chain from p (a record start) to the first start at or past te; it stops early at a record that does not end inside
+// d[0, n) (exit = its start) or at a malformed one (bad, exit = its start).
+KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int32_t n_ref, uint32_t excl, Walk &w)
+{
+    w.recs = w.excluded = w.bytes = 0;
+    w.bad = false;
+    while (p < te) {
+        RecHead h;
+        const int r = record_at(d, n, p, n_ref, h);
+        if (r == REC_SHORT)
+            break;
+        if (r == REC_BAD) {
+            w.bad = true;
+            break;
+        }
+        if (h.flag & excl)
+            ++w.excluded;
+        else {
+            ++w.recs;
+            w.bytes += h.l_seq + 3u;
+        }
+        p += 4ull + h.bs;
+    }
+    w.exit = p;
+}
+
+KMM_BAM_HD uint64_t tile_end(uint64_t t, uint64_t n) { return (t + 1) * TILE < n ? (t + 1) * TILE : n; }
+
+// The claim of tile t once its start is known (entry = a record start) or guessed.
+KMM_BAM_HD void claim_from(const uint8_t *d, uint64_t n, uint64_t t, uint64_t entry, int32_t n_ref, uint32_t excl, uint32_t spec,
+                           Tile &o)
+{
+    o.spec = spec;
+    if (entry == NONE) {
+        o.entry = o.exit = NONE;
+        o.recs = o.excluded = o.bytes = 0;
+        return;
+    }
+    Walk w;
+    walk(d, n, entry, tile_end(t, n), n_ref, excl, w);
+    o.entry = w.bad ? INVALID : entry;
+    o.exit = w.bad ? INVALID : w.exit;
+    o.recs = w.recs;
+    o.excluded = w.excluded;
+    o.bytes = w.bytes;
+}
+
+// The exit of the tiles before t, as the claims `in` say (start0 in front of tile 0).
+KMM_BAM_HD uint64_t prev_exit(const Tile *in, uint64_t t, uint64_t start0)
+{
+    while (t > 0) {
+        --t;
+        if (in[t].entry != NONE)
+            return in[t].exit;
+    }
+    return start0;
+}
+
+// Does tile t's claim agree with the exit `prev` of the tiles before it?
+KMM_BAM_HD bool agrees(const uint8_t *d, uint64_t n, uint64_t t, const Tile &c, uint64_t prev, int32_t n_ref)
+{
+    if (c.entry != NONE)
+        return c.entry == prev;
+    if (prev >= tile_end(t, n))
+        return true;
+    RecHead h;
+    return record_at(d, n, prev, n_ref, h) == REC_SHORT; // (the data end inside the record that starts at prev)
+}
+
+// ---- the per-tile steps, shared by the kernels and the CPU backend ----
+
+// spec, one tile (scalar form: the kernel tests 64 positions at a time, with the same `plausible`)
+inline void spec_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, uint64_t start0, int32_t n_ref, uint32_t excl, Tile &o)
+{
+    uint64_t entry = NONE;
+    if (t == 0)
+        entry = start0;
+    else
+        for (uint64_t c = t * TILE, e = tile_end(t, n); c < e && entry == NONE; ++c)
+            if (plausible(d, n, c, n_ref))
+                entry = c;
+    claim_from(d, n, t, entry, n_ref, excl, 1u, o);
+}
+
+// fix, one tile: its claim is walked again from the exit before it.  verified: that exit is exact (t is the first tile
+// that disagrees), so a malformed record met on the way is an error of the file (returns its position, else NONE).
+KMM_BAM_HD uint64_t fix_tile(const uint8_t *d, uint64_t n, uint64_t t, uint64_t prev, bool verified, int32_t n_ref, uint32_t excl,
+                             Tile &o)
+{
+    Walk w;
+    walk(d, n, prev, tile_end(t, n), n_ref, excl, w);
+    o.spec = 0;
+    o.recs = w.recs;
+    o.excluded = w.excluded;
+    o.bytes = w.bytes;
+    if (w.bad) {
+        o.entry = o.exit = INVALID;
+        return verified ? w.exit : NONE;
+    }
+    o.entry = prev;
+    o.exit = w.exit;
+    return NONE;
+}
+
+// "=ACMGRSVTWYHKDBN": the letters of the 4-bit base codes (SAM/BAM specification 4.2.3)
+KMM_BAM_HD uint8_t base_letter(uint32_t code)
+{
+    return (uint8_t)"=ACMGRSVTWYHKDBN"[code & 15u];
+}
+
+// decode, one record's output (lane `lane` of `lanes`): ">\n" + letters + "\n" at out[o]
+KMM_BAM_HD void decode_record(const uint8_t *rec, const RecHead &h, uint8_t *out, uint32_t lane, uint32_t lanes)
+{
+    const uint8_t *seq = rec + seq_offset(h);
+    const uint32_t n_bytes = (h.l_seq + 1u) / 2u;
+    if (lane == 0) {
+        out[0] = '>';
+        out[1] = '\n';
+        out[2 + h.l_seq] = '\n';
+    }
+    for (uint32_t j = lane; j < n_bytes; j += lanes) {
+        const uint32_t b = seq[j];
+        out[2 + 2 * j] = base_letter(b >> 4);
+        if (2 * j + 1 < h.l_seq)
+            out[3 + 2 * j] = base_letter(b);
+    }
+}
+
+// ---- the header (host side: the library reads it back once per stream) ----
+
+// d[0, n) = the stream's first inflated bytes.  0: the header ends at *hdr_end and names *n_ref references; 1: it goes on
+// behind n; -1: it is no BAM header (magic, or a length no header can have).
+inline int parse_header(const uint8_t *d, uint64_t n, uint64_t *hdr_end, int32_t *n_ref)
+{
+    static const uint8_t magic[4] = {'B', 'A', 'M', 1};
+    if (memcmp(d, magic, n < 4 ? (size_t)n : 4) != 0)
+        return -1;
+    if (n < 8)
+        return 1;
+    const uint32_t l_text = rd32(d + 4);
+    if (l_text >= 0x80000000u)
+        return -1;
+    uint64_t p = 8ull + l_text;
+    if (p + 4 > n)
+        return 1;
+    const uint32_t nr = rd32(d + p);
+    if (nr >= 0x80000000u)
+        return -1;
+    p += 4;
+    for (uint32_t i = 0; i < nr; ++i) {
+        if (p + 4 > n)
+            return 1;
+        const uint32_t l_name = rd32(d + p);
+        if (l_name == 0 || l_name >= 0x80000000u)
+            return -1;
+        p += 4ull + l_name + 4ull;
+        if (p > n)
+            return 1;
+    }
+    *hdr_end = p;
+    *n_ref = (int32_t)nr;
+    return 0;
+}
+
+// ---- the orchestration, written once against a backend (GPU: kmm.hip; CPU: CpuBackend below) ----
+//   be.spec(n_tiles, start0)                 the speculative claims into the current buffer
+//   be.check(n_tiles, start0, Ctl &)         counts the claims that disagree (synchronises: the control words come back)
+//   be.fix(n_tiles, start0)                  the disagreeing claims walked again, into the other buffer; swaps the buffers
+//   be.totals(n_tiles, start0, Totals &)     output offsets of the tiles + totals (synchronises)
+struct CallOut {
+    uint64_t consumed = 0;           // where the last complete record ends (the bytes behind it are carried over)
+    uint64_t recs = 0, excluded = 0, out_bytes = 0;
+    uint64_t false_starts = 0, continuations = 0;
+    uint64_t err_pos = NONE;         // a malformed record (nothing of the call may be mapped)
+};
+
+template <class B>
+int run_call(B &be, uint64_t n, uint64_t start0, CallOut &co)
+{
+    co = CallOut();
+    if (start0 >= n) {
+        co.consumed = start0 < n ? start0 : n;
+        return 0;
+    }
+    const uint64_t n_tiles = (n + TILE - 1) / TILE;
+    int rc = be.spec(n_tiles, start0);
+    for (int pass = 0; rc == 0; ++pass) {
+        Ctl c;
+        if ((rc = be.check(n_tiles, start0, c)) != 0)
+            break;
+        co.false_starts = c.false_starts;
+        if (c.err_pos != NONE) {
+            co.err_pos = c.err_pos;
+            return 0;
+        }
+        if (c.n_bad == 0)
+            break;
+        co.continuations += c.n_bad;
+        rc = be.fix(n_tiles, start0);
+    }
+    if (rc != 0)
+        return rc;
+    Totals t;
+    if ((rc = be.totals(n_tiles, start0, t)) != 0)
+        return rc;
+    co.recs = t.recs;
+    co.excluded = t.excluded;
+    co.out_bytes = t.out_bytes;
+    co.consumed = t.exit;
+    return 0;
+}
+
+// The CPU backend (the tests): the same per-tile steps in loops; decode() writes the two-line FASTA of the call.
+struct CpuBackend {
+    const uint8_t *d = nullptr;
+    uint64_t n = 0;
+    int32_t n_ref = 0;
+    uint32_t excl = 0;
+    std::vector<Tile> cur, nxt;
+    std::vector<uint64_t> base;
+    uint64_t false_starts = 0;
+
+    int spec(uint64_t n_tiles, uint64_t start0)
+    {
+        cur.assign(n_tiles, Tile());
+        nxt.assign(n_tiles, Tile());
+        false_starts = 0;
+        first_bad = err_pos = NONE;
+        for (uint64_t t = 0; t < n_tiles; ++t)
+            spec_tile_scalar(d, n, t, start0, n_ref, excl, cur[t]);
+        return 0;
+    }
+    uint64_t first_bad = NONE, err_pos = NONE;
+    int check(uint64_t n_tiles, uint64_t start0, Ctl &c)
+    {
+        c.n_bad = 0;
+        c.first_bad = NONE;
+        c.err_pos = err_pos;
+        for (uint64_t t = 0; t < n_tiles; ++t)
+            if (!agrees(d, n, t, cur[t], prev_exit(cur.data(), t, start0), n_ref)) {
+                ++c.n_bad;
+                if (c.first_bad == NONE)
+                    c.first_bad = t;
+            }
+        first_bad = c.first_bad;
+        c.false_starts = false_starts;
+        return 0;
+    }
+    int fix(uint64_t n_tiles, uint64_t start0)
+    {
+        for (uint64_t t = 0; t < n_tiles; ++t) {
+            const uint64_t prev = prev_exit(cur.data(), t, start0);
+            if (agrees(d, n, t, cur[t], prev, n_ref)) {
+                nxt[t] = cur[t];
+                continue;
+            }
+            if (cur[t].spec && cur[t].entry != NONE)
+                ++false_starts;
+            const uint64_t e = fix_tile(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t]);
+            if (e != NONE && (err_pos == NONE || e < err_pos))
+                err_pos = e;
+        }
+        cur.swap(nxt);
+        return 0;
+    }
+    int totals(uint64_t n_tiles, uint64_t start0, Totals &o)
+    {
+        o.recs = o.excluded = o.out_bytes = 0;
+        base.assign(n_tiles, 0);
+        for (uint64_t t = 0; t < n_tiles; ++t) {
+            base[t] = o.out_bytes;
+            o.recs += cur[t].recs;
+            o.excluded += cur[t].excluded;
+            o.out_bytes += cur[t].bytes;
+        }
+        o.exit = prev_exit(cur.data(), n_tiles, start0);
+        return 0;
+    }
+    void decode(uint8_t *out)
+    {
+        for (uint64_t t = 0; t < cur.size(); ++t) {
+            const Tile &c = cur[t];
+            if (c.entry == NONE || c.recs == 0)
+                continue;
+            uint64_t p = c.entry, o = base[t];
+            while (p < c.exit) {
+                RecHead h;
+                if (record_at(d, n, p, n_ref, h) != REC_OK)
+                    break;
+                if (!(h.flag & excl)) {
+                    decode_record(d + p, h, out + o, 0, 1);
+                    o += h.l_seq + 3ull;
+                }
+                p += 4ull + h.bs;
+            }
+        }
+    }
+};
+
+#if defined(__HIPCC__)
+// spec: one wavefront per tile (grid-stride); lanes test 64 consecutive positions, the lowest plausible one is the start;
+// lane 0 walks the chain from it.
+__global__ void __launch_bounds__(256) k_bam_spec(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                  int32_t n_ref, uint32_t excl, Tile *__restrict__ out)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        uint64_t entry = NONE;
+        if (t == 0)
+            entry = start0;
+        else
+            for (uint64_t c0 = t * TILE, e = tile_end(t, n); c0 < e && entry == NONE; c0 += 64u) {
+                const uint64_t c = c0 + lane;
+                const unsigned long long m = __ballot(c < e && plausible(d, n, c, n_ref));
+                if (m)
+                    entry = c0 + (uint64_t)(__ffsll((long long)m) - 1);
+            }
+        if (lane == 0) {
+            Walk w;
+            if (entry != NONE)
+                walk(d, n, entry, tile_end(t, n), n_ref, excl, w);
+            const bool none = entry == NONE, bad = !none && w.bad;
+            out[t].entry = bad ? INVALID : entry;
+            out[t].exit = none ? NONE : bad ? INVALID : w.exit;
+            out[t].recs = none ? 0u : w.recs;
+            out[t].excluded = none ? 0u : w.excluded;
+            out[t].bytes = none ? 0u : w.bytes;
+            out[t].spec = 1u;
+        }
+    }
+}
+
+// check: one lane per tile; bad[t] = its claim disagrees with the exit before it
+__global__ void __launch_bounds__(256) k_bam_check(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                   int32_t n_ref, const Tile *__restrict__ in, uint8_t *__restrict__ bad,
+                                                   Ctl *__restrict__ ctl)
+{
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tiles; t += (uint64_t)gridDim.x * blockDim.x) {
+        const bool b = !agrees(d, n, t, in[t], prev_exit(in, t, start0), n_ref);
+        bad[t] = b ? 1 : 0;
+        if (b) {
+            atomicAdd(&ctl->n_bad, 1ull);
+            atomicMin(&ctl->first_bad, (unsigned long long)t);
+        }
+    }
+}
+
+// fix: one lane per tile; claims that agree are copied, the others walked again from the exit before them
+__global__ void __launch_bounds__(256) k_bam_fix(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                 int32_t n_ref, uint32_t excl, const Tile *__restrict__ in, const uint8_t *__restrict__ bad,
+                                                 Tile *__restrict__ out, Ctl *__restrict__ ctl)
+{
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tiles; t += (uint64_t)gridDim.x * blockDim.x) {
+        const Tile c = in[t];
+        if (!bad[t]) {
+            out[t] = c;
+            continue;
+        }
+        if (c.spec && c.entry != NONE)
+            atomicAdd(&ctl->false_starts, 1ull);
+        Tile o;
+        const uint64_t e = fix_tile(d, n, t, prev_exit(in, t, start0), t == ctl->first_bad, n_ref, excl, o);
+        out[t] = o;
+        if (e != NONE)
+            atomicMin(&ctl->err_pos, (unsigned long long)e);
+    }
+}
+
+// totals: one workgroup of 1024 threads, each over a run of consecutive tiles: the exclusive scan of the tiles' output bytes
+// (base), the sums, the exit of the last tile
+__global__ void __launch_bounds__(1024) k_bam_totals(const Tile *__restrict__ in, uint64_t n_tiles, uint64_t start0,
+                                                     unsigned long long *__restrict__ base, Totals *__restrict__ tot)
+{
+    __shared__ unsigned long long s[1024];
+    const uint32_t i = threadIdx.x;
+    const uint64_t per = (n_tiles + 1023) / 1024, t0 = (uint64_t)i * per < n_tiles ? (uint64_t)i * per : n_tiles,
+                   t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
+    unsigned long long sum = 0, recs = 0, excl = 0;
+    for (uint64_t t = t0; t < t1; ++t) {
+        sum += in[t].bytes;
+        recs += in[t].recs;
+        excl += in[t].excluded;
+    }
+    s[i] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024; off <<= 1) { // inclusive scan (Hillis-Steele)
+        const unsigned long long v = i >= off ? s[i - off] : 0ull;
+        __syncthreads();
+        s[i] += v;
+        __syncthreads();
+    }
+    unsigned long long b = s[i] - sum;
+    for (uint64_t t = t0; t < t1; ++t) {
+        base[t] = b;
+        b += in[t].bytes;
+    }
+    if (i == 1023)
+        tot->out_bytes = s[1023];
+    __syncthreads();
+    s[i] = recs;
+    __syncthreads();
+    for (uint32_t h = 512; h > 0; h >>= 1) {
+        if (i < h)
+            s[i] += s[i + h];
+        __syncthreads();
+    }
+    if (i == 0)
+        tot->recs = s[0];
+    __syncthreads();
+    s[i] = excl;
+    __syncthreads();
+    for (uint32_t h = 512; h > 0; h >>= 1) {
+        if (i < h)
+            s[i] += s[i + h];
+        __syncthreads();
+    }
+    if (i == 0) {
+        tot->excluded = s[0];
+        tot->exit = prev_exit(in, n_tiles, start0);
+    }
+}
+
+// decode: one wavefront per tile (grid-stride); its records in order, 64 lanes over every kept record's bases
+__global__ void __launch_bounds__(256) k_bam_decode(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                    uint32_t excl, const Tile *__restrict__ in, const unsigned long long *__restrict__ base,
+                                                    uint8_t *__restrict__ out)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        const Tile c = in[t];
+        if (c.entry == NONE || c.recs == 0)
+            continue;
+        uint64_t p = c.entry, o = base[t];
+        while (p < c.exit) {
+            RecHead h;
+            if (record_at(d, n, p, n_ref, h) != REC_OK) // (cannot happen on a verified chain; bounds all the same)
+                break;
+            if (!(h.flag & excl)) {
+                decode_record(d + p, h, out + o, lane, 64u);
+                o += h.l_seq + 3ull;
+            }
+            p += 4ull + h.bs;
+        }
+    }
+}
+#endif
+
+} // namespace kmm_bam

@@ -252,6 +252,28 @@ class DeviceIndex:
                                            int(bool(also_revcomp)), t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
         return used.value, n_rec.value
 
+    def map_bam(self, comp, first, last, next_chunk=None, n_bytes=None, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
+                lut=None):
+        """Map a window of a BAM file (kmm_map_bam): BGZF members inflated, records found and their SEQ decoded on the GPU.
+        `comp` starts at a member boundary; returns (compressed bytes used, records mapped): continue at comp[used:].  first /
+        last mark the file's first / last window (the header is read on the first; a first window that ends inside the header
+        uses nothing: bring a longer one).  next_chunk: the bytes that follow `comp` in the caller's memory, staged under this
+        window's inflate kernel (as map_bgzf)."""
+        if next_chunk is not None and len(next_chunk):
+            nx = _Arg(next_chunk, np.uint8, "next_chunk")
+            _lib.check(_lib.lib().kmm_map_bgzf_hint_next(self._h, nx.ptr, nx.n))
+        b = _Arg(comp, np.uint8, "comp")
+        t = _Arg(lut, np.uint8, "lut")
+        n = b.n if n_bytes is None else int(n_bytes)
+        if n > b.n:
+            raise ValueError("n_bytes exceeds the buffer")
+        used = ctypes.c_int64(0)
+        n_rec = ctypes.c_int64(0)
+        flags = (_lib.FORMAT_NEW_STREAM if first else 0) | (_lib.FORMAT_LAST_CHUNK if last else 0)
+        _lib.check(_lib.lib().kmm_map_bam(self._h, b.ptr, n, flags, int(k), int(max_index_lookup_frequency), int(bool(also_revcomp)),
+                                          t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
+        return used.value, n_rec.value
+
     def map_packed(self, codes, n_bases, n_reads, read_len=0, read_starts=None, k=31, max_index_lookup_frequency=1000,
                    also_revcomp=False):
         """Reads held as 2-bit codes (uint32 words, 16 codes per word, first base lowest): kmm_map_packed.  read_len > 0:

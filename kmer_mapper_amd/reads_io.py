@@ -222,6 +222,89 @@ def write_fastq(path, batch, gz=False):
             f.write(b"@r%d\n" % i + seq + b"\n+\n" + b"I" * len(seq) + b"\n")
 
 
+_BAM_NIBBLE = {c: i for i, c in enumerate(b"=ACMGRSVTWYHKDBN")}
+
+
+def bam_record(seq, name=b"r", flag=4, ref_id=-1, pos=-1, cigar=(), qual=None, aux=b"", next_ref_id=-1, next_pos=-1, tlen=0,
+               mapq=255):
+    """One BAM alignment record (SAM/BAM specification 4.2), block_size included: SEQ packed two bases per byte (high nibble
+    first) from the letters =ACMGRSVTWYHKDBN (BAM has no lower case: a soft-masked base is stored as its upper-case code);
+    qual None = 0xFF bytes (absent); cigar = uint32 operations."""
+    import struct
+    seq = bytes(seq).upper()
+    name = bytes(name) + b"\0"
+    codes = [_BAM_NIBBLE[c] for c in seq] + [0]
+    packed = bytes((codes[i] << 4) | codes[i + 1] for i in range(0, len(seq), 2))
+    qual = b"\xff" * len(seq) if qual is None else bytes(qual)
+    body = (struct.pack("<iiBBHHHiiii", ref_id, pos, len(name), mapq, 4680, len(cigar), flag, len(seq), next_ref_id, next_pos, tlen)
+            + name + struct.pack("<%dI" % len(cigar), *cigar) + packed + qual + bytes(aux))
+    return struct.pack("<I", len(body)) + body
+
+
+def bam_header(refs=(), text=b""):
+    """The BAM header: magic, l_text + text, n_ref + the references (name, length)."""
+    import struct
+    out = [b"BAM\1", struct.pack("<I", len(text)), bytes(text), struct.pack("<I", len(refs))]
+    for name, length in refs:
+        nm = bytes(name) + b"\0"
+        out.append(struct.pack("<I", len(nm)) + nm + struct.pack("<I", int(length)))
+    return b"".join(out)
+
+
+def bgzf_members(data, block=0xFF00, level=6):
+    """`data` as BGZF members of at most `block` inflated bytes (no EOF member)."""
+    import struct
+    import zlib
+    out = []
+    for p in range(0, len(data), block):
+        chunk = bytes(data[p:p + block])
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        payload = c.compress(chunk) + c.flush()
+        bsize = 18 + len(payload) + 8 - 1
+        assert bsize < 65536
+        out.append(b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + struct.pack("<H", bsize) + payload +
+                   struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
+    return b"".join(out)
+
+
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def write_bam(path, batch, names=None, flags=None, refs=(), text=b"@HD\tVN:1.6\tSO:unsorted\n", level=6, block=0xFF00):
+    """Write the reads of `batch` as an unaligned BAM file (for tools and tests): every read one record (name r<i> unless
+    `names`, FLAG 4 unless `flags`, quality 'I').  The header goes in members of its own, the records in members of at most
+    `block` inflated bytes, and the file ends with the empty EOF member, as htslib writes it."""
+    recs = []
+    for i in range(len(batch)):
+        seq = batch.bases[batch.offsets[i]:batch.offsets[i + 1]].tobytes()
+        recs.append(bam_record(seq, names[i] if names is not None else b"r%d" % i, int(flags[i]) if flags is not None else 4,
+                               qual=b"\x28" * len(seq)))
+    with open(path, "wb") as f:
+        f.write(bgzf_members(bam_header(refs, text), block, level))
+        f.write(bgzf_members(b"".join(recs), block, level))
+        f.write(BGZF_EOF)
+
+
+def is_bam(path):
+    """Is the file BGZF whose first inflated bytes are the BAM magic "BAM\\1" (whatever its name)?"""
+    import zlib
+    try:
+        with open(path, "rb") as f:
+            h = f.read(1 << 16)
+    except OSError:
+        return False
+    if len(h) < 18 or h[:4] != b"\x1f\x8b\x08\x04" or h[12:14] != b"BC" or h[14:16] != b"\x02\x00":
+        return False
+    try:
+        d = zlib.decompressobj(-15)
+        head = d.decompress(h[18:], 4)
+        while len(head) < 4 and not d.eof and d.unconsumed_tail:
+            head += d.decompress(d.unconsumed_tail, 4 - len(head))
+    except zlib.error:
+        return False
+    return head[:4] == b"BAM\1"
+
+
 # ------------------------------------------------------------------------------------------------
 # Byte-range sharding of a read file over ranks (multi-GPU file input).  The reference hands each chunk to one
 # worker (command_line_interface.py:109-111); here rank g owns the records that START inside
@@ -350,8 +433,11 @@ def records_cut(buf, fmt, at_eof=False):
 # Raw-chunk reader for the GPU record parser (kmm_map_records): the host only moves bytes.
 # ------------------------------------------------------------------------------------------------
 def sniff_format(path, probe_bytes=1 << 16):
-    """Returns ("fastq" | "fasta", gpu_parsable).  Two-line FASTA and 4-line FASTQ can be parsed on
-    the GPU; FASTA whose sequences are wrapped over several lines needs the host parser."""
+    """Returns ("fastq" | "fasta" | "bam", gpu_parsable).  Two-line FASTA and 4-line FASTQ can be parsed on
+    the GPU; FASTA whose sequences are wrapped over several lines needs the host parser.  BAM is told by its content (a BGZF
+    member whose inflated bytes start with "BAM\\1"), whatever the file is called; its records are decoded on the GPU."""
+    if is_bam(path):
+        return "bam", True
     with _open(path) as f:
         head = f.read(probe_bytes)
     if not head:
