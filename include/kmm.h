@@ -185,6 +185,22 @@ int kmm_map_reads_uniform(kmm_index_t *idx, const uint8_t *bases, int64_t n_read
  * `format` (the chunk ends the file: everything is consumed). */
 #define KMM_FORMAT_FASTA 1
 #define KMM_FORMAT_LAST_CHUNK 0x100
+/* SAM text (SAM/BAM specification 1.4; what `samtools view`, aligners and simulators write; `bnp.open` reads it and the
+ * reference maps chunk.sequence, command_line_interface.py:102,109).  Also a format of kmm_map_bgzf (BGZF .sam.gz, as htslib
+ * writes it) and kmm_map_gzip.  The chunk's lines are parsed on the GPU (csrc/kmm_sam.hpp) into two-line FASTA
+ * in HBM, which is then mapped like any other:
+ *   - a line whose first byte is '@' is a header line, skipped wherever it appears (concatenated files), counted in
+ *     "sam_header_lines";
+ *   - every other line is one record with at least 11 TAB-separated fields; field 10 (SEQ) is mapped AS STORED (reverse-
+ *     strand records are not flipped, as in kmm_map_bam) through the same lookup table as every other entry point (lut
+ *     NULL: ACGT -> 0123, N -> A): "=" and the IUPAC codes are KMM_ERR_INVALID_BASE at the next synchronising call; optional
+ *     fields behind QUAL are ignored.  SEQ "*" is a read without k-mers that counts in *n_records (as l_seq = 0 in BAM);
+ *   - "bam_exclude_flags" (kmm_set_param) leaves out records with FLAG & mask;
+ *   - *consumed = the byte after the chunk's last '\n' (a record never spans a newline); '\r' before '\n' is tolerated;
+ *   - refused with KMM_ERR_MALFORMED, nothing of the call mapped, the message naming the first bad line's byte offset: a
+ *     record line with fewer than 10 TABs, a FLAG that is no decimal integer in [0, 65535], an empty line.
+ * Counters (kmm_get_param): "sam_calls", "sam_records", "sam_records_excluded", "sam_header_lines". */
+#define KMM_FORMAT_SAM 8
 int kmm_map_records(kmm_index_t *idx, const uint8_t *raw, int64_t n_bytes, int format, int k,
                     int max_index_lookup_frequency, int also_revcomp, const uint8_t *lut,
                     int64_t *consumed, int64_t *n_records);
@@ -206,7 +222,7 @@ int kmm_map_records(kmm_index_t *idx, const uint8_t *raw, int64_t n_bytes, int f
  * last: a final line without newline gets one, and bytes that then still form no record — or compressed bytes behind the
  * last whole member — are KMM_ERR_MALFORMED; a call that stops at its own size limit ignores the flag: the caller comes
  * back with the rest and the same flag).
- * format: KMM_FORMAT_FASTQ or KMM_FORMAT_FASTA2.  A corrupt member (header, Huffman code, distance, ISIZE, CRC32) makes the
+ * format: KMM_FORMAT_FASTQ, KMM_FORMAT_FASTA2 or KMM_FORMAT_SAM.  A corrupt member (header, Huffman code, distance, ISIZE, CRC32) makes the
  * call fail with KMM_ERR_MALFORMED before anything of the chunk is mapped.  A plain gzip file (no member sizes: `gzip`, not
  * `bgzip`) is refused the same way — kmm_map_gzip below inflates those on the GPU.  *n_records: reads mapped by this call.
  */
@@ -226,7 +242,7 @@ int kmm_map_bgzf(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int form
  * The deflate stream is cut at speculative block starts (one every ~32 KiB of compressed bytes), one GPU lane decodes each
  * piece with markers for its unknown 32 KiB of history, a start is kept only where the piece before it ended exactly
  * there, and the history is resolved afterwards (csrc/kmm_gpu_gunzip.hpp).  The same stream-per-handle contract
- * as kmm_map_bgzf: format KMM_FORMAT_FASTQ / KMM_FORMAT_FASTA2, OR KMM_FORMAT_NEW_STREAM for a file's first window and
+ * as kmm_map_bgzf: format KMM_FORMAT_FASTQ / KMM_FORMAT_FASTA2 / KMM_FORMAT_SAM, OR KMM_FORMAT_NEW_STREAM for a file's first window and
  * KMM_FORMAT_LAST_CHUNK for its last; comp lies in HOST memory (a file mapping will do) and reaches HBM through the handle's
  * staging ring; the inflated bytes behind the last complete record are carried to the next call.
  * comp may be ANY prefix of the rest of the file (at most 2 GiB of it are looked at): the call maps everything up to the
@@ -263,7 +279,7 @@ int kmm_map_gzip(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int form
  * member or a record on KMM_FORMAT_LAST_CHUNK.  The handle then takes a new stream.  Extension (default off):
  * "bam_exclude_flags" drops records with flag & mask (samtools view -F).  *n_records: records mapped by this call.
  * Counters (kmm_get_param): "bam_calls", "bam_records", "bam_records_excluded", "bam_header_bytes", "bam_false_starts",
- * "bam_continuations".  SAM text and CRAM are not read.
+ * "bam_continuations".  SAM text is read by kmm_map_bgzf / kmm_map_gzip / kmm_map_records (KMM_FORMAT_SAM); CRAM is not read.
  */
 int kmm_map_bam(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int flags, int k, int max_index_lookup_frequency,
                 int also_revcomp, const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
@@ -413,8 +429,8 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      "gzip_false_starts" (starts rejected by the predecessor check), "gzip_continuations" (lanes re-run past
  *                      a rejected start or a full output slot), "gzip_inflated_bytes" (inflated so far: a caller's ratio for
  *                      sizing its next window)
- *   "bam_exclude_flags" kmm_map_bam: records whose FLAG has any of these bits are not mapped (0 = the default: every record,
- *                      as the reference; 0x900 = no secondary and supplementary alignments).  Read-only: "bam_calls",
+ *   "bam_exclude_flags" kmm_map_bam and KMM_FORMAT_SAM: records whose FLAG has any of these bits are not mapped (0 = the
+ *                      default: every record, as the reference; 0x900 = no secondary and supplementary alignments).  Read-only: "bam_calls",
  *                      "bam_records" (mapped), "bam_records_excluded", "bam_header_bytes", "bam_false_starts" (speculative
  *                      starts the link check rejected), "bam_continuations" (tiles walked again from the exit before them)
  *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the

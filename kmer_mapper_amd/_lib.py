@@ -23,6 +23,7 @@ KMM_ERR_MALFORMED = -6
 KMM_ERR_INTERNAL = -7
 FORMAT_FASTA2, FORMAT_FASTQ = 2, 4
 FORMAT_FASTA, FORMAT_LAST_CHUNK, FORMAT_NEW_STREAM = 1, 0x100, 0x400      # multi-line FASTA (unwrapped on the GPU); flag: the chunk ends the file
+FORMAT_SAM = 8                  # SAM text: the SEQ column extracted on the GPU (kmm_map_records / kmm_map_bgzf / kmm_map_gzip)
 
 # kernel ids of kmm_get_timing (include/kmm.h)
 (KERNEL_MAP_READS, KERNEL_MAP_KMERS, KERNEL_RX_P1, KERNEL_RX_SCAN, KERNEL_RX_P2, KERNEL_RX_P3,

@@ -131,7 +131,7 @@ def _record_start_at_or_after(buf, m, prev, fmt):
             data = np.concatenate([data, np.array([_NL], dtype=np.uint8)])
         starts = (np.flatnonzero(data == _NL) + 1).astype(np.int64)
         for i in range(len(starts) - 1):
-            r = _is_record_start(data, starts, i, "fastq" if fmt == "fastq" else "fasta", at_eof)
+            r = _is_record_start(data, starts, i, fmt if fmt in ("fastq", "sam") else "fasta", at_eof)
             if r is None:
                 break
             if r:

@@ -126,7 +126,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 exclude_flags=0):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
-    on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags")."""
+    on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
+    extracted on the GPU (KMM_FORMAT_SAM on the routes of a FASTQ; exclude_flags filters it too)."""
     _check_bam_route(fmt, world_size, exclude_flags)
     t_index = time.perf_counter()
     # page-locked memory is slow to make (~50 ms per GB): the staging buffers of the host packer are made by a helper thread
@@ -214,11 +215,12 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     # of the compressed bytes, resynchronised to the records at both ends (bgzf_ranges.py).
     # (Decided BEFORE a chunker is made: the prefetching one starts a reader thread and page-locks two batch buffers — making
     # and freeing those cost this route 100 ms of its map phase until it was noticed.)
-    gpu_inflate = (not seekable and fmt in ("fastq", "fasta") and not os.environ.get("KMM_CLI_NO_GPU_INFLATE") and _is_bgzf(path))
+    gpu_inflate = (not seekable and fmt in ("fastq", "fasta", "sam") and not os.environ.get("KMM_CLI_NO_GPU_INFLATE")
+                   and _is_bgzf(path))
     # plain gzip (`gzip reads.fq`: one deflate stream, no member sizes), one rank: the stream is inflated on the GPU too
     # (kmm_map_gzip: speculative block starts, one lane per ~32 KiB of compressed bytes).  Opt-in (KMM_CLI_GPU_GUNZIP=1)
     # until it beats the host inflater's route on the same box (profiles/gzip_gpu/).
-    gpu_gunzip = (not gpu_inflate and world_size == 1 and not seekable and fmt in ("fastq", "fasta")
+    gpu_gunzip = (not gpu_inflate and world_size == 1 and not seekable and fmt in ("fastq", "fasta", "sam")
                   and os.environ.get("KMM_CLI_GPU_GUNZIP", "") not in ("", "0")
                   and not os.environ.get("KMM_CLI_NO_GPU_INFLATE") and _is_gzip(path))
     gpu_inflate = gpu_inflate or gpu_gunzip
@@ -250,7 +252,9 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             logging.debug("packer threads stay on the GPU's node: %s", exc)
     owns = (lambda i: True) if (world_size == 1 or seekable) else (lambda i: chunk_owner(i, world_size) == rank)
     # FASTQ and two-line FASTA are parsed as they are; FASTA with wrapped sequence lines is unwrapped on the GPU first
-    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "fasta_ml": _lib.FORMAT_FASTA, "bam": 0}[fmt]
+    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "fasta_ml": _lib.FORMAT_FASTA, "bam": 0, "sam": _lib.FORMAT_SAM}[fmt]
+    if fmt == "sam":                 # SAM: lines parsed on the GPU, the SEQ column written as two-line FASTA there
+        dev.set_param("bam_exclude_flags", int(exclude_flags))
     t_start = time.perf_counter()
     n_reads = n_bytes = 0
     if bam:
@@ -498,12 +502,12 @@ def _map_bgzf_file(dev, path, kfmt, k, max_freq, revcomp, before_fetch, t_start,
 
 
 def _check_bam_route(fmt, world_size, exclude_flags):
-    """What the BAM route does not do (yet): several ranks on one file; and the flag filter is BAM's alone."""
+    """What the BAM route does not do (yet): several ranks on one file; and the flag filter is for SAM and BAM alone."""
     if fmt == "bam" and world_size > 1:
         raise ValueError("BAM input is mapped by one rank: sharding a BAM file over %d ranks needs the ranks to resynchronise "
                          "to its records, which is not implemented (run without torchrun, WORLD_SIZE=1)" % world_size)
-    if exclude_flags and fmt != "bam":
-        raise ValueError("--exclude-flags applies to BAM input only (the reads are %s)" % fmt)
+    if exclude_flags and fmt not in ("bam", "sam"):
+        raise ValueError("--exclude-flags applies to SAM and BAM input only (the reads are %s)" % fmt)
 
 
 def _map_bam_file(dev, path, k, max_freq, revcomp, before_fetch, t_start, comp_batch=None, counts_out=None, exclude_flags=0):
@@ -625,6 +629,8 @@ def map_bnp(args):
     _check_bam_route(fmt, world, exclude_flags)
     if fmt == "bam" and getattr(args, "host_parser", False):
         raise ValueError("--host-parser does not read BAM: its records are decoded on the GPU (drop --host-parser)")
+    if fmt == "sam" and getattr(args, "host_parser", False):
+        raise ValueError("--host-parser does not read SAM: its SEQ column is extracted on the GPU (drop --host-parser)")
     if not getattr(args, "host_parser", False):
         if fmt == "fasta" and not two_line:
             fmt = "fasta_ml"           # wrapped sequence lines: unwrapped on the GPU (KMM_FORMAT_FASTA)
@@ -677,7 +683,7 @@ def run_argument_parser(args):
     subparser = subparsers.add_parser("map", help="Map reads to a kmer index")
     subparser.add_argument("-i", "--kmer-index", required=False)
     subparser.add_argument("-b", "--index-bundle", required=False)
-    subparser.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz, fq.gz or BAM format")
+    subparser.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz, fq.gz, SAM (.sam, .sam.gz) or BAM format")
     subparser.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
     subparser.add_argument("-t", "--n-threads", required=False, default=16, type=int,
                            help="Host threads that read / inflate the reads and pack them to 2 bits per base before they "
@@ -702,7 +708,7 @@ def run_argument_parser(args):
                                 "unwrapped on the GPU too).")
     subparser.add_argument("--device", default=0, type=int, help="Extension: GPU ordinal (single process).")
     subparser.add_argument("--exclude-flags", default=0, type=lambda v: int(v, 0),
-                           help="Extension, BAM input only: leave out records whose FLAG has any of these bits (samtools view -F; "
+                           help="Extension, SAM and BAM input only: leave out records whose FLAG has any of these bits (samtools view -F; "
                                 "e.g. 0x900 = secondary and supplementary alignments). Default 0: every record, as the reference.")
     subparser.set_defaults(func=map_bnp)
 

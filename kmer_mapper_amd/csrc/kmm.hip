@@ -161,6 +161,7 @@ constexpr unsigned long long NO_BAD = ~0ull;
 #include "kmm_gpu_inflate.hpp"
 #include "kmm_gpu_gunzip.hpp"
 #include "kmm_bam.hpp"
+#include "kmm_sam.hpp"
 
 // Page-locked buffers are expensive to make (hipHostMalloc: ~50 ms per GB) and cheap to keep: the ones a handle gives up go
 // to a process-wide shelf (at most 8 GiB), and kmm_host_reserve puts buffers there ahead of time — from another thread,
@@ -323,6 +324,9 @@ struct kmm_index {
     int64_t dbg_bgzf_call_cap_kb = 0; // test hook ("debug_bgzf_call_cap_kb"): inflated bytes a kmm_map_bgzf / kmm_map_bam call
                                       // takes at most, KiB (0: 3.5 GiB)
     int64_t flat_uniform_batches = 0; // flat reads mapped by the uniform / packed front ends of the radix path (rec_launch_flat)
+    // KMM_FORMAT_SAM (kmm_sam.hpp): the tiles' line counts, their output offsets, the totals; the filter is bam_excl
+    DevBuf sam_tiles, sam_base, sam_ctl;
+    int64_t sam_calls = 0, sam_records = 0, sam_excluded = 0, sam_header_lines = 0;
     int dbg_bgzf_slot_kb = 0;     // test hook ("debug_bgzf_ring_slot_kb"): slot size of kmm_map_bgzf's staging ring (a power of two, >= 4)
     int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
@@ -1148,6 +1152,8 @@ void kmm_index_destroy(kmm_index_t *ix)
     release(ix->bgzf_err);
     release(ix->bgzf_carry);
     for (DevBuf *b : {&ix->bam_tiles[0], &ix->bam_tiles[1], &ix->bam_bad, &ix->bam_base, &ix->bam_ctl, &ix->bam_out})
+        release(*b);
+    for (DevBuf *b : {&ix->sam_tiles, &ix->sam_base, &ix->sam_ctl})
         release(*b);
     for (DevBuf *b : {&ix->gz_comp, &ix->gz_raw, &ix->gz_carry, &ix->gz_window, &ix->gz_tabs, &ix->gz_meta, &ix->gz_res, &ix->gz_win,
                       &ix->gz_gmaps, &ix->gz_gwin, &ix->gz_err})
@@ -2798,6 +2804,69 @@ static int map_multiline_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_by
     return rc != KMM_OK ? rc : rel;
 }
 
+// One piece of a SAM chunk (kmm_sam.hpp): its lines counted and checked on the device, the SEQ of every kept record written as
+// two-line FASTA into the stage's second buffer, which map_records_piece then maps.  Only complete lines are taken (*consumed:
+// the byte after the piece's last newline).  dry: the count and the checks only (a chunk of several pieces is checked whole
+// before any of it is mapped).  at: the piece's offset in the caller's chunk (for the error message).
+static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int64_t at, bool dry, int k, int max_freq,
+                         int also_revcomp, const uint8_t *lut, int64_t *consumed, int64_t *n_records)
+{
+    *consumed = 0;
+    *n_records = 0;
+    Stage &s = next_stage(ix);
+    KMMCHK(stage_acquire(ix, s));
+    bool staged = false;
+    const uint8_t *d_raw = nullptr;
+    KMMCHK(stage_in<uint8_t>(ix, s.bases, raw, (size_t)n_bytes, &d_raw, &staged));
+    const uint64_t n_tiles = ((uint64_t)n_bytes + kmm_sam::TILE - 1) / kmm_sam::TILE;
+    KMMCHK(ensure(ix->sam_tiles, (size_t)n_tiles * sizeof(kmm_sam::Tile) + 64));
+    KMMCHK(ensure(ix->sam_base, (size_t)n_tiles * 8 + 64));
+    KMMCHK(ensure(ix->sam_ctl, 256));
+    if (!dry)
+        KMMCHK(ensure(s.kmers, (size_t)n_bytes + 16)); // (a record's output is never longer than its line)
+    kmm_sam::Tile *tiles = (kmm_sam::Tile *)ix->sam_tiles.p;
+    unsigned long long *base = (unsigned long long *)ix->sam_base.p;
+    kmm_sam::Totals *d_tot = (kmm_sam::Totals *)ix->sam_ctl.p;
+    uint8_t *out = (uint8_t *)s.kmers.p;
+    const uint32_t excl = ix->bam_excl;
+    KMMCHK(stage_copies_done(ix));
+    hipStream_t cs = ix->stream; // (kernels run on the handle's stream only: see rec_compact_piece)
+    const dim3 gw((unsigned)grid_for(ix, (int64_t)((n_tiles + 3) / 4), 16)); // one wavefront per tile, 4 per block, grid-stride
+    hipLaunchKernelGGL(kmm_sam::k_sam_count, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl, tiles);
+    hipLaunchKernelGGL(kmm_sam::k_sam_totals, dim3(1), dim3(1024), 0, cs, (const kmm_sam::Tile *)tiles, n_tiles, base, d_tot);
+    HIPCHK(hipGetLastError());
+    kmm_sam::Totals h;
+    HIPCHK(hipMemcpyAsync(&h, d_tot, sizeof h, hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipStreamSynchronize(cs)); // (the borrowed host buffer is free from here on)
+    if (h.err != kmm_sam::NONE) {
+        static const char *why[4] = {"?", "fewer than 11 TAB-separated fields", "FLAG is not a decimal integer in [0, 65535]",
+                                     "an empty line"};
+        (void)stage_release(ix, s, false);
+        return fail(KMM_ERR_MALFORMED, "kmm_map_records: SAM line at byte %llu of the chunk: %s (nothing of the call is mapped)",
+                    (unsigned long long)at + (h.err >> 2), why[h.err & 3]);
+    }
+    *consumed = (int64_t)h.consumed;
+    int rc = KMM_OK;
+    if (!dry) {
+        ix->sam_records += (int64_t)h.recs;
+        ix->sam_excluded += (int64_t)h.excluded;
+        ix->sam_header_lines += (int64_t)h.headers;
+        if (h.recs > 0) {
+            hipLaunchKernelGGL(kmm_sam::k_sam_write, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
+                               (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out);
+            HIPCHK(hipGetLastError());
+            // the records as two-line FASTA, from HBM, through the two-line parser (its kernels wait for the copy stream)
+            int64_t used = 0;
+            rc = map_records_piece(ix, out, (int64_t)h.out_bytes, KMM_FORMAT_FASTA2, k, max_freq, also_revcomp, lut, &used, n_records);
+            if (rc == KMM_OK && (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs))
+                rc = fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %llu written bytes, %lld of %llu records mapped", (long long)used,
+                          h.out_bytes, (long long)*n_records, h.recs);
+        }
+    }
+    const int rel = stage_release(ix, s, false); // (after the inner call's kernels: they read this stage's buffer)
+    return rc != KMM_OK ? rc : rel;
+}
+
 static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int format, int k, int max_freq, int also_revcomp,
                              const uint8_t *lut, int64_t *consumed, int64_t *n_records);
 
@@ -2816,8 +2885,9 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     KMMCHK(check_k(k));
     const bool last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
     format &= ~KMM_FORMAT_LAST_CHUNK;
-    if (format != KMM_FORMAT_FASTQ && format != KMM_FORMAT_FASTA2 && format != KMM_FORMAT_FASTA)
-        return fail(KMM_ERR_INVALID_ARG, "format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2) or KMM_FORMAT_FASTA (1)");
+    if (format != KMM_FORMAT_FASTQ && format != KMM_FORMAT_FASTA2 && format != KMM_FORMAT_FASTA && format != KMM_FORMAT_SAM)
+        return fail(KMM_ERR_INVALID_ARG, "format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2), KMM_FORMAT_FASTA (1) or "
+                    "KMM_FORMAT_SAM (8)");
     if (n_bytes < 0)
         return fail(KMM_ERR_INVALID_ARG, "n_bytes negative");
     if (consumed)
@@ -2831,7 +2901,9 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     HIPCHK(hipSetDevice(ix->device));
     // chunks beyond 2^30 bytes are mapped piece by piece: every piece starts where the previous one's last complete
     // record ended, so the pieces cut the chunk exactly as one census over all of it would
-    if (format != KMM_FORMAT_FASTA && records_take_radix(ix, n_bytes, format)) {
+    // (multi-line FASTA and SAM are turned into two-line FASTA on the device first: never the host packer, whose parser knows
+    // FASTQ and two-line FASTA only)
+    if (format != KMM_FORMAT_FASTA && format != KMM_FORMAT_SAM && records_take_radix(ix, n_bytes, format)) {
         // raw bytes in host memory: the host threads pack the sequence lines to 2 bits per base before they cross PCIe
         if (ix->host_pack_threads > 0 && !lut && !ix->dbg_rec_skip && !ix->dbg_rec_copy_stream && !is_device_ptr(raw)) {
             bool done = false;
@@ -2843,10 +2915,24 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     }
     const int64_t piece_max = (int64_t)1 << 30;
     int64_t off = 0, recs = 0;
+    if (format == KMM_FORMAT_SAM && n_bytes > piece_max) {
+        // a SAM chunk of several pieces is checked whole first: a malformed line in a later piece maps nothing of the call
+        while (off < n_bytes) {
+            const int64_t len = n_bytes - off < piece_max ? n_bytes - off : piece_max;
+            int64_t used = 0, nr = 0;
+            KMMCHK(map_sam_piece(ix, raw + off, len, off, true, k, max_freq, also_revcomp, lut, &used, &nr));
+            off += used;
+            if (used == 0 || len < piece_max)
+                break;
+        }
+        off = 0;
+    }
     while (off < n_bytes) {
         const int64_t len = n_bytes - off < piece_max ? n_bytes - off : piece_max;
         int64_t used = 0, nr = 0;
-        if (format == KMM_FORMAT_FASTA)
+        if (format == KMM_FORMAT_SAM)
+            KMMCHK(map_sam_piece(ix, raw + off, len, off, false, k, max_freq, also_revcomp, lut, &used, &nr));
+        else if (format == KMM_FORMAT_FASTA)
             KMMCHK(map_multiline_piece(ix, raw + off, len, last_chunk && off + len == n_bytes, k, max_freq, also_revcomp, lut,
                                        &used, &nr));
         else
@@ -2856,6 +2942,8 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         if (used == 0 || len < piece_max)
             break; // no complete record left in reach / the last piece
     }
+    if (format == KMM_FORMAT_SAM)
+        ix->sam_calls++;
     if (consumed)
         *consumed = off;
     if (n_records)
@@ -3097,9 +3185,10 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     bool last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
     const bool new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
     const int fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
-    if (bam ? fmt != 0 : fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2)
+    if (bam ? fmt != 0 : fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2 && fmt != KMM_FORMAT_SAM)
         return fail(KMM_ERR_INVALID_ARG, bam ? "kmm_map_bam: flags take KMM_FORMAT_NEW_STREAM and KMM_FORMAT_LAST_CHUNK only"
-                                             : "kmm_map_bgzf: format must be KMM_FORMAT_FASTQ (4) or KMM_FORMAT_FASTA2 (2)");
+                                             : "kmm_map_bgzf: format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2) or "
+                                               "KMM_FORMAT_SAM (8)");
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
     if (consumed_comp)
@@ -3630,8 +3719,8 @@ static int map_gzip_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     bool last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
     const bool new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
     const int fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
-    if (fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2)
-        return fail(KMM_ERR_INVALID_ARG, "kmm_map_gzip: format must be KMM_FORMAT_FASTQ (4) or KMM_FORMAT_FASTA2 (2)");
+    if (fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2 && fmt != KMM_FORMAT_SAM)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_map_gzip: format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2) or KMM_FORMAT_SAM (8)");
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
     if (consumed_comp)
@@ -4371,6 +4460,14 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->bam_continuations;
     else if (!strcmp(name, "bam_exclude_flags"))
         *value = ix->bam_excl;
+    else if (!strcmp(name, "sam_calls")) // kmm_map_records calls (direct, or on the inflated bytes of kmm_map_bgzf / _gzip) on SAM
+        *value = ix->sam_calls;
+    else if (!strcmp(name, "sam_records")) // SAM records mapped
+        *value = ix->sam_records;
+    else if (!strcmp(name, "sam_records_excluded")) // SAM records left out by "bam_exclude_flags"
+        *value = ix->sam_excluded;
+    else if (!strcmp(name, "sam_header_lines")) // SAM lines starting with '@', skipped
+        *value = ix->sam_header_lines;
     else if (!strcmp(name, "debug_bgzf_call_cap_kb"))
         *value = ix->dbg_bgzf_call_cap_kb;
     else if (!strcmp(name, "flat_uniform_batches")) // flat reads of one length mapped by the uniform / packed front ends

@@ -1,0 +1,444 @@
+// kmm_sam.hpp — part of libkmm: SAM text records (SAM/BAM specification 1.4) turned into two-line FASTA ON THE GPU
+// (KMM_FORMAT_SAM; included by kmm.hip, compiled by itself with g++ in tests/test_sam_on_the_cpu.py, where the same per-line
+// steps run on the CPU).
+//
+// The QNAME grammar [!-?A-~]{1,254} cannot start with '@', so every line of a SAM stream is either a header line (first byte
+// '@') or one whole record: every newline is an exact record boundary.  A chunk in HBM (at most 2^30 bytes: one piece of
+// kmm_map_records) is cut into tiles of TILE bytes; the tile in which a line STARTS owns it, however long it is:
+//   1. count   one wavefront per tile finds its first line start (the first newline at or after the tile's start), then
+//              walks its lines: per line, 64 lanes read 16 bytes each per step (a 1 KiB window, aligned 16-byte loads) and
+//              find the newline and TABs 1, 2, 9 and 10 with ballots and a lane prefix sum.  From those: header / record,
+//              FLAG, the SEQ range, the flag filter, the output length; the first malformed line of the tile;
+//   2. totals  the tiles' output offsets (an exclusive scan), records, exclusions, header lines, the end of the last complete
+//              line (= *consumed) and the first error;
+//   3. write   the same walk again, every kept record written as ">\n" SEQ "\n" (SEQ "*": an empty line), 64 lanes per SEQ.
+// kmm_map_records then maps that text as two-line FASTA: the LUT, the invalid-base rule and the radix / direct choice are the
+// ones every other input takes.  Every read is bounds-checked against n.
+#pragma once
+
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define KMM_SAM_HD __host__ __device__ __forceinline__
+#else
+#define KMM_SAM_HD inline
+#endif
+
+namespace kmm_sam {
+
+constexpr uint64_t NONE = ~0ull;
+constexpr uint32_t TILE = 1024;       // bytes per tile (the lines that start in it are its own)
+constexpr uint32_t WIN = 1024;        // bytes one wavefront reads per step of a line: 64 lanes x 16 bytes
+enum Err : uint32_t { ERR_FIELDS = 1, ERR_FLAG = 2, ERR_EMPTY = 3 }; // an error word = line start << 2 | code
+enum Kind : uint32_t { K_KEPT = 0, K_EXCLUDED = 1, K_HEADER = 2, K_BAD = 3 };
+
+// One tile's lines: records kept / excluded, header lines, output bytes, the end of its last complete line (0: none), the
+// first malformed line (NONE: none).
+struct Tile {
+    uint32_t recs, excluded, headers, bytes;
+    uint64_t last_end, err;
+};
+
+struct Totals {
+    unsigned long long recs, excluded, headers, out_bytes, consumed, err;
+};
+
+// Where a line's fields lie: its newline (NONE: no newline before n), TABs 1, 2, 9 and 10 (NONE: the line has fewer)
+struct Line {
+    uint64_t end;
+    uint64_t tab[4];
+};
+KMM_SAM_HD uint32_t want_tab(int w) { return w < 2 ? (uint32_t)w + 1u : (uint32_t)w + 7u; } // 1, 2, 9, 10
+
+struct LineInfo {
+    uint32_t kind, err;
+    uint64_t seq, seq_len; // SEQ of a record ("*": length 0)
+};
+
+// TAB / newline masks of one lane's 16 bytes d[a + 16 lane, +16), restricted to [s, n).  d + a is 16-byte aligned; on the
+// device a block wholly inside [0, n) is one 16-byte load, anything else (the chunk's ends) is read byte by byte.
+KMM_SAM_HD void lane_masks(const uint8_t *d, uint64_t n, uint64_t s, int64_t a, uint32_t lane, uint32_t &tab, uint32_t &nl)
+{
+    const int64_t p = a + 16 * (int64_t)lane;
+    tab = nl = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (p >= 0 && p + 16 <= (int64_t)n) {
+        typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+        const v4 x = *reinterpret_cast<const v4 *>(d + p);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t c = (x[i] >> (8 * b)) & 255u;
+                tab |= (c == 9u ? 1u : 0u) << (4 * i + b);
+                nl |= (c == 10u ? 1u : 0u) << (4 * i + b);
+            }
+        const int64_t lo = (int64_t)s - p; // bytes of the block before s
+        if (lo > 0) {
+            const uint32_t keep = lo >= 16 ? 0u : ~((1u << lo) - 1u);
+            tab &= keep;
+            nl &= keep;
+        }
+        return;
+    }
+#endif
+    for (int i = 0; i < 16; ++i) {
+        const int64_t q = p + i;
+        if (q < (int64_t)s || q < 0 || q >= (int64_t)n)
+            continue;
+        const uint32_t c = d[q];
+        tab |= (c == 9u ? 1u : 0u) << i;
+        nl |= (c == 10u ? 1u : 0u) << i;
+    }
+}
+
+// position (0..15) of the k-th (1-based) set bit of m; m has at least k set bits
+KMM_SAM_HD uint32_t nth_bit(uint32_t m, uint32_t k)
+{
+    for (uint32_t i = 1; i < k; ++i)
+        m &= m - 1u;
+    uint32_t b = 0;
+    while (!((m >> b) & 1u))
+        ++b;
+    return b;
+}
+
+// The first window of a line that starts at s: its start is s rounded down to the 16-byte alignment of the address d + s.
+KMM_SAM_HD int64_t first_window(const uint8_t *d, uint64_t s)
+{
+    return (int64_t)s - (int64_t)(((uintptr_t)d + s) & 15u);
+}
+
+// What the line [s, L.end) is.  L.end != NONE.
+KMM_SAM_HD void classify(const uint8_t *d, uint64_t s, const Line &L, uint32_t excl, LineInfo &o)
+{
+    o.kind = K_BAD;
+    o.err = 0;
+    o.seq = o.seq_len = 0;
+    const uint64_t e = L.end;
+    if (e == s || (e == s + 1 && d[s] == 13u)) {
+        o.err = ERR_EMPTY;
+        return;
+    }
+    if (d[s] == (uint8_t)'@') {
+        o.kind = K_HEADER;
+        return;
+    }
+    if (L.tab[3] == NONE) { // (fewer than 10 TABs before the newline)
+        o.err = ERR_FIELDS;
+        return;
+    }
+    const uint64_t f0 = L.tab[0] + 1, f1 = L.tab[1];
+    uint32_t flag = 0;
+    bool ok = f1 > f0;
+    for (uint64_t q = f0; q < f1 && ok; ++q) {
+        const uint32_t c = d[q];
+        ok = c >= (uint32_t)'0' && c <= (uint32_t)'9';
+        flag = flag * 10u + (c - (uint32_t)'0');
+        ok = ok && flag <= 0xFFFFu;
+    }
+    if (!ok) {
+        o.err = ERR_FLAG;
+        return;
+    }
+    o.seq = L.tab[2] + 1;
+    o.seq_len = L.tab[3] - o.seq;
+    if (o.seq_len == 1 && d[o.seq] == (uint8_t)'*')
+        o.seq_len = 0;
+    o.kind = (flag & excl) ? K_EXCLUDED : K_KEPT;
+}
+
+// One kept record's output (lane `lane` of `lanes`): ">\n" + SEQ + "\n" at out[0]
+KMM_SAM_HD void emit(const uint8_t *d, const LineInfo &li, uint8_t *out, uint32_t lane, uint32_t lanes)
+{
+    if (lane == 0) {
+        out[0] = '>';
+        out[1] = '\n';
+        out[2 + li.seq_len] = '\n';
+    }
+    for (uint64_t j = lane; j < li.seq_len; j += lanes)
+        out[2 + j] = d[li.seq + j];
+}
+
+// The line that starts at s, scanned window by window as the wavefront does, one lane after the other (the CPU form of
+// scan_line_wave below: the same masks, the same prefix over the lanes).  tabs: false = the newline only; windows that start
+// at or past `stop` are not read (L.end NONE).
+inline void scan_line_lanes(const uint8_t *d, uint64_t n, uint64_t s, bool tabs, uint64_t stop, Line &L)
+{
+    L.end = NONE;
+    for (int w = 0; w < 4; ++w)
+        L.tab[w] = NONE;
+    uint32_t seen = 0; // TABs of the line before the window
+    for (int64_t a = first_window(d, s); a < (int64_t)n && a < (int64_t)stop; a += WIN) {
+        for (uint32_t lane = 0; lane < 64; ++lane) {
+            uint32_t tm, nm;
+            lane_masks(d, n, s, a, lane, tm, nm);
+            if (nm)
+                tm &= (nm & (0u - nm)) - 1u; // (TABs behind the newline are another line's)
+            const uint32_t cnt = tabs ? (uint32_t)__builtin_popcount(tm) : 0u;
+            for (int w = 0; w < 4 && tabs; ++w) {
+                const uint32_t k = want_tab(w);
+                if (L.tab[w] == NONE && seen < k && k <= seen + cnt)
+                    L.tab[w] = (uint64_t)(a + 16 * (int64_t)lane + nth_bit(tm, k - seen));
+            }
+            seen += cnt;
+            if (nm) {
+                L.end = (uint64_t)(a + 16 * (int64_t)lane + __builtin_ctz(nm));
+                return;
+            }
+        }
+    }
+}
+
+KMM_SAM_HD uint64_t tile_end(uint64_t t, uint64_t n) { return (t + 1) * TILE < n ? (t + 1) * TILE : n; }
+
+// The walk over tile t's lines, written once against a scanner (scan(s, tabs, stop, Line &)) and a sink for the kept records
+// (sink(LineInfo, offset of its output inside the tile's)).  The tile's first line starts at its first byte when the byte
+// before is a newline (or the tile is the first), else behind the first newline inside the tile — looked for inside the tile
+// only, so that a long line costs its own tiles one window each.
+template <class Scan, class Sink>
+KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t excl, Scan &scan, Sink &sink, Tile &o)
+{
+    o.recs = o.excluded = o.headers = o.bytes = 0;
+    o.last_end = 0;
+    o.err = NONE;
+    const uint64_t ts = t * TILE, te = tile_end(t, n);
+    uint64_t s = ts;
+    Line L;
+    if (ts > 0 && d[ts - 1] != 10u) {
+        scan(ts, false, te, L); // (the line in progress at the tile's start belongs to a tile before)
+        if (L.end == NONE)
+            return;
+        s = L.end + 1;
+    }
+    while (s < te) {
+        scan(s, true, n, L);
+        if (L.end == NONE)
+            return; // (no newline before the chunk ends: the line waits for the next call)
+        LineInfo li;
+        classify(d, s, L, excl, li);
+        if (li.kind == K_BAD) {
+            o.err = s << 2 | li.err;
+            return;
+        }
+        if (li.kind == K_HEADER)
+            ++o.headers;
+        else if (li.kind == K_EXCLUDED)
+            ++o.excluded;
+        else {
+            sink(li, o.bytes);
+            ++o.recs;
+            o.bytes += (uint32_t)li.seq_len + 3u;
+        }
+        o.last_end = L.end + 1;
+        s = L.end + 1;
+    }
+}
+
+// ---- the CPU form (the tests): the same walk, the lanes one after the other ----
+struct CpuScan {
+    const uint8_t *d;
+    uint64_t n;
+    void operator()(uint64_t s, bool tabs, uint64_t stop, Line &L) { scan_line_lanes(d, n, s, tabs, stop, L); }
+};
+struct CpuSink {
+    const uint8_t *d;
+    uint8_t *out; // null: the count pass
+    void operator()(const LineInfo &li, uint32_t at)
+    {
+        if (out)
+            emit(d, li, out + at, 0, 1);
+    }
+};
+
+// One chunk on the CPU: the count pass, the totals, the write pass (out: at least tot.out_bytes; null = count only).
+inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out, Totals &tot)
+{
+    tot = Totals{0, 0, 0, 0, 0, NONE};
+    const uint64_t n_tiles = (n + TILE - 1) / TILE;
+    std::vector<uint64_t> base(n_tiles);
+    CpuScan sc{d, n};
+    CpuSink count{d, nullptr};
+    for (uint64_t t = 0; t < n_tiles; ++t) {
+        Tile o;
+        walk_tile(d, n, t, excl, sc, count, o);
+        base[t] = tot.out_bytes;
+        tot.recs += o.recs;
+        tot.excluded += o.excluded;
+        tot.headers += o.headers;
+        tot.out_bytes += o.bytes;
+        if (o.last_end > tot.consumed)
+            tot.consumed = o.last_end;
+        if (o.err < tot.err)
+            tot.err = o.err;
+    }
+    if (!out || tot.err != NONE)
+        return;
+    for (uint64_t t = 0; t < n_tiles; ++t) {
+        CpuSink write{d, out + base[t]};
+        Tile o;
+        walk_tile(d, n, t, excl, sc, write, o);
+    }
+}
+
+#if defined(__HIPCC__)
+// The line that starts at s, one wavefront: 64 lanes x 16 bytes per window; the newline is the first lane (ballot) with one,
+// TAB k lies in the lane whose prefix of TAB counts passes k.  Wave-uniform result.
+__device__ __forceinline__ void scan_line_wave(const uint8_t *__restrict__ d, uint64_t n, uint64_t s, bool tabs, uint64_t stop, Line &L)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    L.end = NONE;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+        L.tab[w] = NONE;
+    uint32_t seen = 0;
+    for (int64_t a = first_window(d, s); a < (int64_t)n && a < (int64_t)stop; a += WIN) {
+        uint32_t tm, nm;
+        lane_masks(d, n, s, a, lane, tm, nm);
+        const unsigned long long nb = __ballot(nm != 0);
+        const uint32_t cut = nb ? (uint32_t)__ffsll((long long)nb) - 1u : 64u;
+        if (lane == cut)
+            tm &= (nm & (0u - nm)) - 1u;
+        else if (lane > cut)
+            tm = 0;
+        if (tabs && L.tab[3] == NONE) {
+            const uint32_t cnt = (uint32_t)__popc(tm);
+            uint32_t incl = cnt;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t v = __shfl_up(incl, o);
+                if ((int)lane >= o)
+                    incl += v;
+            }
+            const uint32_t before = seen + incl - cnt;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t k = want_tab(w);
+                const bool mine = L.tab[w] == NONE && before < k && k <= before + cnt;
+                const unsigned long long m = __ballot(mine);
+                if (m) {
+                    const int src = __ffsll((long long)m) - 1;
+                    const uint32_t bit = __shfl(mine ? nth_bit(tm, k - before) : 0u, src);
+                    L.tab[w] = (uint64_t)(a + 16 * (int64_t)src + bit);
+                }
+            }
+            seen += __shfl(incl, 63);
+        }
+        if (nb) {
+            const uint32_t bit = (uint32_t)__shfl((int)(nm ? __builtin_ctz(nm) : 0), (int)cut);
+            L.end = (uint64_t)(a + 16 * (int64_t)cut + bit);
+            return;
+        }
+    }
+}
+
+struct WaveScan {
+    const uint8_t *d;
+    uint64_t n;
+    __device__ void operator()(uint64_t s, bool tabs, uint64_t stop, Line &L) { scan_line_wave(d, n, s, tabs, stop, L); }
+};
+struct NoSink {
+    __device__ void operator()(const LineInfo &, uint32_t) {}
+};
+struct WaveSink {
+    const uint8_t *d;
+    uint8_t *out;
+    __device__ void operator()(const LineInfo &li, uint32_t at) { emit(d, li, out + at, threadIdx.x & 63u, 64u); }
+};
+
+// count: one wavefront per tile (grid-stride)
+__global__ void __launch_bounds__(256) k_sam_count(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint32_t excl,
+                                                   Tile *__restrict__ tiles)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    WaveScan sc{d, n};
+    NoSink none;
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        Tile o;
+        walk_tile(d, n, t, excl, sc, none, o);
+        if ((threadIdx.x & 63u) == 0)
+            tiles[t] = o;
+    }
+}
+
+// totals: one workgroup of 1024 threads, each over a run of consecutive tiles: the exclusive scan of the tiles' output bytes
+// (base) and the sums / extremes
+__global__ void __launch_bounds__(1024) k_sam_totals(const Tile *__restrict__ in, uint64_t n_tiles, unsigned long long *__restrict__ base,
+                                                     Totals *__restrict__ tot)
+{
+    __shared__ unsigned long long s[1024];
+    const uint32_t i = threadIdx.x;
+    const uint64_t per = (n_tiles + 1023) / 1024, t0 = (uint64_t)i * per < n_tiles ? (uint64_t)i * per : n_tiles,
+                   t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
+    unsigned long long v[6] = {0, 0, 0, 0, 0, NONE}; // out bytes, recs, excluded, headers, consumed (max), err (min)
+    for (uint64_t t = t0; t < t1; ++t) {
+        const Tile c = in[t];
+        v[0] += c.bytes;
+        v[1] += c.recs;
+        v[2] += c.excluded;
+        v[3] += c.headers;
+        v[4] = c.last_end > v[4] ? c.last_end : v[4];
+        v[5] = c.err < v[5] ? c.err : v[5];
+    }
+    s[i] = v[0];
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024; off <<= 1) { // inclusive scan (Hillis-Steele)
+        const unsigned long long x = i >= off ? s[i - off] : 0ull;
+        __syncthreads();
+        s[i] += x;
+        __syncthreads();
+    }
+    unsigned long long b = s[i] - v[0];
+    for (uint64_t t = t0; t < t1; ++t) {
+        base[t] = b;
+        b += in[t].bytes;
+    }
+    if (i == 1023)
+        tot->out_bytes = s[1023];
+#pragma unroll
+    for (int f = 1; f < 6; ++f) {
+        __syncthreads();
+        s[i] = v[f];
+        __syncthreads();
+        for (uint32_t h = 512; h > 0; h >>= 1) {
+            if (i < h) {
+                const unsigned long long x = s[i + h];
+                s[i] = f == 4 ? (x > s[i] ? x : s[i]) : f == 5 ? (x < s[i] ? x : s[i]) : s[i] + x;
+            }
+            __syncthreads();
+        }
+        if (i == 0) {
+            if (f == 1)
+                tot->recs = s[0];
+            else if (f == 2)
+                tot->excluded = s[0];
+            else if (f == 3)
+                tot->headers = s[0];
+            else if (f == 4)
+                tot->consumed = s[0];
+            else
+                tot->err = s[0];
+        }
+    }
+}
+
+// write: one wavefront per tile (grid-stride), the same walk; every kept record at base[t] + its offset in the tile
+__global__ void __launch_bounds__(256) k_sam_write(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint32_t excl,
+                                                   const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                   uint8_t *__restrict__ out)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    WaveScan sc{d, n};
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        if (tiles[t].recs == 0)
+            continue;
+        WaveSink sink{d, out + base[t]};
+        Tile o;
+        walk_tile(d, n, t, excl, sc, sink, o);
+    }
+}
+#endif
+
+} // namespace kmm_sam

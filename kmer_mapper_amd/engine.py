@@ -192,7 +192,8 @@ class DeviceIndex:
 
     def map_records(self, raw, n_bytes=None, fmt=_lib.FORMAT_FASTQ, k=31, max_index_lookup_frequency=1000,
                     also_revcomp=False, lut=None):
-        """Map a raw FASTQ (fmt=4) / two-line FASTA (fmt=2) chunk parsed on the GPU.
+        """Map a raw FASTQ (fmt=4) / two-line FASTA (fmt=2) / SAM (fmt=8; "bam_exclude_flags" filters it) chunk parsed on
+        the GPU.
         Returns (consumed_bytes, n_records); the caller carries raw[consumed:] to the next chunk."""
         b = _Arg(raw, np.uint8, "raw")
         t = _Arg(lut, np.uint8, "lut")
@@ -208,7 +209,8 @@ class DeviceIndex:
 
     def map_bgzf(self, comp, n_bytes=None, fmt=_lib.FORMAT_FASTQ, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
                  lut=None, first=False, last=False, head_skip=0, tail_stop=None, next_chunk=None):
-        """Map a chunk of a BGZF-compressed FASTQ (fmt=4) / two-line FASTA (fmt=2) file, inflated on the GPU (kmm_map_bgzf).
+        """Map a chunk of a BGZF-compressed FASTQ (fmt=4) / two-line FASTA (fmt=2) / SAM (fmt=8) file, inflated on the GPU
+        (kmm_map_bgzf).
         `comp` starts at a member boundary; returns (compressed bytes used, records mapped): continue at comp[used:].  The
         handle carries the inflated bytes behind the last complete record to the next call; first / last mark the file's
         first / last chunk.  A rank's share of a file (bgzf_ranges.rank_member_range): head_skip = inflated bytes of the
@@ -237,7 +239,7 @@ class DeviceIndex:
 
     def map_gzip(self, comp, n_bytes=None, fmt=_lib.FORMAT_FASTQ, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
                  lut=None, first=False, last=False):
-        """Map a window of a PLAIN gzip-compressed FASTQ (fmt=4) / two-line FASTA (fmt=2) file, inflated on the GPU
+        """Map a window of a PLAIN gzip-compressed FASTQ (fmt=4) / two-line FASTA (fmt=2) / SAM (fmt=8) file, inflated on the GPU
         (kmm_map_gzip).  `comp` is any prefix of the rest of the file; returns (compressed bytes used, records mapped):
         continue at comp[used:].  first / last mark the file's first / last window (per call: nothing is kept for later)."""
         b = _Arg(comp, np.uint8, "comp")

@@ -9,6 +9,7 @@ scan, header/sequence line masks); no per-read Python loop.
 """
 import gzip
 import queue
+import re
 import threading
 
 import numpy as np
@@ -285,6 +286,55 @@ def write_bam(path, batch, names=None, flags=None, refs=(), text=b"@HD\tVN:1.6\t
         f.write(BGZF_EOF)
 
 
+def sam_text(batch, names=None, flags=None, header=b"@HD\tVN:1.6\tSO:unsorted\n"):
+    """The reads of `batch` as SAM text (SAM/BAM specification 1.4): `header` (header lines, each ending in a newline), then one
+    unaligned record per read: QNAME r<i> unless `names`, FLAG 4 unless `flags`, SEQ (an empty read: "*"), QUAL 'I'."""
+    out = [bytes(header)]
+    for i in range(len(batch)):
+        seq = batch.bases[batch.offsets[i]:batch.offsets[i + 1]].tobytes()
+        name = names[i] if names is not None else b"r%d" % i
+        flag = int(flags[i]) if flags is not None else 4
+        out.append(b"%s\t%d\t*\t0\t0\t*\t*\t0\t0\t%s\t%s\n" % (name, flag, seq or b"*", b"I" * len(seq) if seq else b"*"))
+    return b"".join(out)
+
+
+def write_sam(path, batch, names=None, flags=None, header=b"@HD\tVN:1.6\tSO:unsorted\n", bgzf=False, gz=False, level=6,
+              block=0xFF00):
+    """Write the reads of `batch` as a SAM file (sam_text; for tools and tests): plain, BGZF (bgzf=True: members of at most
+    `block` inflated bytes and the EOF member, as htslib writes .sam.gz) or plain gzip (gz=True)."""
+    data = sam_text(batch, names, flags, header)
+    with open(path, "wb") as f:
+        if bgzf:
+            f.write(bgzf_members(data, block, level) + BGZF_EOF)
+        elif gz:
+            f.write(gzip.compress(data, level))
+        else:
+            f.write(data)
+
+
+_SAM_HEADER = re.compile(rb"@(HD|SQ|RG|PG|CO)\t")
+
+
+def _sam_record_line(line):
+    """Does the line have at least 11 TAB-separated fields with a decimal FLAG in [0, 65535] (a SAM record)?"""
+    f = line.split(b"\t", 11)
+    return len(f) >= 11 and f[1].isdigit() and int(f[1]) <= 0xFFFF
+
+
+def _looks_like_sam(head):
+    """SAM text by content (the first bytes of the inflated file): a first line that is a SAM header line (@HD, @SQ, @RG, @PG,
+    @CO and a TAB) whose first non-'@' line in the probe, if any, is a record; or a first line that is a record (it cannot start
+    with '@' or '>').  A FASTQ whose header reads "@HD\t..." stays FASTQ: its sequence line is no record."""
+    lines = head.split(b"\n")
+    if _SAM_HEADER.match(lines[0]):
+        complete = lines[1:-1] if len(lines) > 1 else []
+        for ln in complete:
+            if ln[:1] != b"@":
+                return _sam_record_line(ln)
+        return True
+    return head[:1] not in (b"@", b">") and _sam_record_line(lines[0])
+
+
 def is_bam(path):
     """Is the file BGZF whose first inflated bytes are the BAM magic "BAM\\1" (whatever its name)?"""
     import zlib
@@ -318,6 +368,8 @@ def _is_record_start(buf, starts, i, fmt, at_eof):
     n_lines = len(starts) - 1                      # complete lines in buf
     if i >= n_lines:
         return None if not at_eof else False
+    if fmt == "sam":                               # SAM: every line is a header line or one whole record
+        return True
     if fmt != "fastq":                             # FASTA: '>' never starts a sequence line
         return bool(buf[starts[i]] == ord(">"))
     if buf[starts[i]] != ord("@"):
@@ -393,6 +445,8 @@ def last_record_start(buf, fmt):
         else:
             n_lines = len(starts) - 1
         view = starts[:n_lines + 1]
+        if fmt == "sam":
+            return int(view[-1]) if n_lines > 0 else 0
         if fmt != "fastq":
             cand = starts[(starts > 0) & (starts < n)]          # an unfinished header line is a record start too
             cand = cand[buf[cand] == ord(">")]
@@ -423,8 +477,10 @@ def records_cut(buf, fmt, at_eof=False):
         starts = nl[nl + 1 < buf.shape[0]] + 1
         hdr = starts[buf[starts] == ord(">")]
         return int(hdr[-1]) if hdr.shape[0] else 0
-    period = 4 if fmt == "fastq" else 2
     nl = np.flatnonzero(buf == _NL)
+    if fmt == "sam":               # SAM: every newline ends a record (or a header line) — the GPU's *consumed
+        return int(nl[-1]) + 1 if nl.shape[0] else 0
+    period = 4 if fmt == "fastq" else 2
     whole = (nl.shape[0] // period) * period
     return int(nl[whole - 1]) + 1 if whole else 0
 
@@ -433,15 +489,19 @@ def records_cut(buf, fmt, at_eof=False):
 # Raw-chunk reader for the GPU record parser (kmm_map_records): the host only moves bytes.
 # ------------------------------------------------------------------------------------------------
 def sniff_format(path, probe_bytes=1 << 16):
-    """Returns ("fastq" | "fasta" | "bam", gpu_parsable).  Two-line FASTA and 4-line FASTQ can be parsed on
+    """Returns ("fastq" | "fasta" | "bam" | "sam", gpu_parsable).  Two-line FASTA and 4-line FASTQ can be parsed on
     the GPU; FASTA whose sequences are wrapped over several lines needs the host parser.  BAM is told by its content (a BGZF
-    member whose inflated bytes start with "BAM\\1"), whatever the file is called; its records are decoded on the GPU."""
+    member whose inflated bytes start with "BAM\\1"), whatever the file is called; its records are decoded on the GPU.  SAM
+    text (plain, BGZF or gzip) is told by its content too (_looks_like_sam), not by its name; its SEQ column is extracted on
+    the GPU."""
     if is_bam(path):
         return "bam", True
     with _open(path) as f:
         head = f.read(probe_bytes)
     if not head:
         return "fasta", True
+    if _looks_like_sam(bytes(head)):
+        return "sam", True
     fmt = _detect_format(head[0], path)
     if fmt == "fastq":
         return fmt, True
