@@ -253,25 +253,17 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     owns = (lambda i: True) if (world_size == 1 or seekable) else (lambda i: chunk_owner(i, world_size) == rank)
     # FASTQ and two-line FASTA are parsed as they are; FASTA with wrapped sequence lines is unwrapped on the GPU first
     kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "fasta_ml": _lib.FORMAT_FASTA, "bam": 0, "sam": _lib.FORMAT_SAM}[fmt]
-    if fmt == "sam":                 # SAM: lines parsed on the GPU, the SEQ column written as two-line FASTA there
+    # SAM: lines parsed on the GPU, the SEQ column written as two-line FASTA there; BAM: records decoded there
+    if fmt in ("sam", "bam"):
         dev.set_param("bam_exclude_flags", int(exclude_flags))
     t_start = time.perf_counter()
     n_reads = n_bytes = 0
-    if bam:
-        if helper.ident is not None:
-            helper.join()
-        return _map_bam_file(dev, path, k, max_index_lookup_frequency, map_reverse_complements, before_fetch, t_start,
-                             counts_out=prepared.get("counts"), exclude_flags=exclude_flags)
-    if gpu_gunzip:
-        if helper.ident is not None:
-            helper.join()
-        return _map_gzip_file(dev, path, kfmt, k, max_index_lookup_frequency, map_reverse_complements, before_fetch, t_start,
-                              counts_out=prepared.get("counts"))
     if gpu_inflate:
         if helper.ident is not None:
             helper.join()
-        return _map_bgzf_file(dev, path, kfmt, k, max_index_lookup_frequency, map_reverse_complements, before_fetch, t_start,
-                              counts_out=prepared.get("counts"), rank=rank, world_size=world_size, fmt=fmt)
+        return _map_compressed_file(dev, path, "bam" if bam else "gzip" if gpu_gunzip else "bgzf", kfmt, k, max_index_lookup_frequency,
+                                    map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
+                                    world_size=world_size, fmt=fmt)
     try:
         i = 0
         while True:
@@ -327,11 +319,15 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     logging.info("Mapped %d reads from %d bytes (%.1f MB/s, GPU record parser): %d k-mer lookups "
                  "(%.1f M/s), %d index hits" % (n_reads, n_bytes, n_bytes / max(dt, 1e-9) / 1e6, n_lookups,
                                                   n_lookups / max(dt, 1e-9) / 1e6, n_hits))
+    _log_path_taken(n_radix, n_direct, n_host_packed)
+    return node_counts
+
+
+def _log_path_taken(n_radix, n_direct, n_host_packed=0):
     logging.info("path_taken: %s (%d batches on the radix path, %d on the direct path; %d batches packed to 2 bits per base "
                  "by the host threads)"
                  % ("radix" if n_radix and not n_direct else "direct" if n_direct and not n_radix else "mixed", n_radix, n_direct,
                     n_host_packed))
-    return node_counts
 
 
 def _is_bgzf(path):
@@ -355,90 +351,44 @@ def _is_gzip(path):
 
 
 _GZIP_CALL_INFLATED = 3 << 30      # inflated bytes a kmm_map_gzip window is sized for (a call takes at most 3.5 GiB)
-
-
-def _map_gzip_file(dev, path, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None):
-    """`kmer_mapper map -f reads.fq.gz` for PLAIN gzip files with the GPU inflater: windows of the file mapping ->
-    kmm_map_gzip, each call going on where the one before could verify a deflate block boundary."""
-    import mmap
-    n_reads = size = 0
-    logging.info("Route: gzip stream inflated on the GPU (kmm_map_gzip)")
-    try:
-        with open(path, "rb") as f:
-            size = os.fstat(f.fileno()).st_size
-            mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
-            try:
-                if hasattr(mm, "madvise") and hasattr(mmap, "MADV_SEQUENTIAL"):
-                    mm.madvise(mmap.MADV_SEQUENTIAL)
-                whole = np.frombuffer(mm, dtype=np.uint8)
-                # windows of ~3 GiB INFLATED: the first from a typical FASTQ ratio, every later one from the ratio of what
-                # the calls before inflated (the trailer's ISIZE is the size mod 2^32: no guide for the large files)
-                inflated0 = dev.get_param("gzip_inflated_bytes")
-                window = int(_GZIP_CALL_INFLATED / 4.5)
-                pos = 0
-                t_calls = time.perf_counter()
-                while pos < size:
-                    end = min(pos + window, size)
-                    if size - end < window // 4:         # (no short tail call: a call's time is its slowest lane's)
-                        end = size
-                    used, n_rec = dev.map_gzip(whole[pos:end], fmt=kfmt, k=k, max_index_lookup_frequency=max_freq,
-                                               also_revcomp=revcomp, first=pos == 0, last=end == size)
-                    n_reads += n_rec
-                    if used == 0:
-                        if end == size:
-                            raise ValueError("trailing bytes of %s are no complete gzip member" % path)
-                        window *= 2                      # no whole deflate block in the window: a longer one
-                        continue
-                    pos += used
-                    ratio = max((dev.get_param("gzip_inflated_bytes") - inflated0) / pos, 1.0)
-                    window = min(max(int(_GZIP_CALL_INFLATED / ratio), 1 << 20), 2 << 30)
-                del whole
-            finally:
-                try:
-                    mm.close()
-                except BufferError:
-                    pass
-        n_lookups, n_hits = dev.get_stats()
-        n_members, n_chunks = dev.get_param("gzip_members"), dev.get_param("gzip_chunks")
-        n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
-        if before_fetch is not None:
-            before_fetch(dev)
-        t_fetch = time.perf_counter()
-        node_counts = dev.get_node_counts(out=counts_out)
-        logging.info("%.0f ms in kmm_map_gzip, %.0f ms more until the node counts were on the host",
-                     (t_fetch - t_calls) * 1e3, (time.perf_counter() - t_fetch) * 1e3)
-    finally:
-        dt = time.perf_counter() - t_start
-        dev.close()
-    logging.info("Time spent only on hashing and counting hashes: %.5f" % dt)
-    logging.info("Mapped %d reads from %d compressed bytes (%.1f MB/s compressed; gzip stream inflated on the GPU: %d members, "
-                 "%d chunks): %d k-mer lookups (%.1f M/s), %d index hits"
-                 % (n_reads, size, size / max(dt, 1e-9) / 1e6, n_members, n_chunks, n_lookups, n_lookups / max(dt, 1e-9) / 1e6,
-                    n_hits))
-    logging.info("path_taken: %s (%d batches on the radix path, %d on the direct path; 0 batches packed to 2 bits per base by "
-                 "the host threads)" % ("radix" if n_radix and not n_direct else "direct" if n_direct and not n_radix else "mixed",
-                                        n_radix, n_direct))
-    return node_counts
-
-
 _BGZF_CALL_INFLATED = 3150 << 20   # inflated bytes per kmm_map_bgzf call: under what a call takes (3.5 GiB; 3.25 GiB for a window staged ahead)
 
+# per route: the counters its summary line reports, and that line
+_COMPRESSED_ROUTES = {
+    "gzip": (("gzip_members", "gzip_chunks"),
+             "Mapped %d reads from %d compressed bytes (%.1f MB/s compressed; gzip stream inflated on the GPU: %d members, "
+             "%d chunks): %d k-mer lookups (%.1f M/s), %d index hits"),
+    "bgzf": (("bgzf_members",),
+             "Mapped %d reads from %d compressed bytes (%.1f MB/s compressed; %d BGZF members inflated on the GPU): %d k-mer "
+             "lookups (%.1f M/s), %d index hits"),
+    "bam": (("bgzf_members", "bam_records_excluded", "bam_false_starts"),
+            "Mapped %d BAM records from %d compressed bytes (%.1f MB/s compressed; %d BGZF members inflated and the records "
+            "decoded on the GPU; %d records excluded by flag, %d false record starts): %d k-mer lookups (%.1f M/s), %d index "
+            "hits"),
+}
 
-def _map_bgzf_file(dev, path, kfmt, k, max_freq, revcomp, before_fetch, t_start, comp_batch=None, counts_out=None, rank=0,
-                   world_size=1, fmt="fastq"):
-    """`kmer_mapper map -f reads.fq.gz` for BGZF files: compressed chunks of the file mapping -> kmm_map_bgzf (members inflated
-    and records parsed on the GPU; the handle carries the bytes behind a chunk's last complete record to the next chunk).
-    Several ranks: each maps its member range (bgzf_ranges.rank_member_range), the first member's head and the last member's
-    tail trimmed to the record boundaries the ranks agree on."""
+
+def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None, rank=0,
+                         world_size=1, fmt="fastq"):
+    """`kmer_mapper map -f reads.fq.gz | reads.bam` with the GPU inflater: windows of the file mapping -> kmm_map_<route>.
+
+    route "gzip" (PLAIN gzip, kmm_map_gzip): each call goes on where the one before could verify a deflate block boundary.
+    route "bgzf" / "bam" (kmm_map_bgzf / kmm_map_bam): each window starts at a member boundary; members are inflated and the
+    records parsed (BAM: found and their SEQ decoded) on the GPU, and the handle carries the bytes behind a window's last
+    complete record to the next one.  BGZF with several ranks: each maps its member range (bgzf_ranges.rank_member_range),
+    the first member's head and the last member's tail trimmed to the record boundaries the ranks agree on."""
     import mmap
+    counters, summary = _COMPRESSED_ROUTES[route]
     n_reads = lo = size = 0
+    if route == "gzip":
+        logging.info("Route: gzip stream inflated on the GPU (kmm_map_gzip)")
     try:
         with open(path, "rb") as f:
             file_size = os.fstat(f.fileno()).st_size
             mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
             try:
                 lo, size, head_skip, tail_stop = 0, file_size, 0, None
-                if world_size > 1:
+                if world_size > 1:                       # (BGZF text alone: gzip and BAM are mapped by one rank)
                     from . import bgzf_ranges
                     lo, s0, hi, s1 = bgzf_ranges.rank_member_range(mm, fmt, rank, world_size)
                     size = bgzf_ranges.member_end(mm, hi) if s1 > 0 else hi
@@ -449,30 +399,61 @@ def _map_bgzf_file(dev, path, kfmt, k, max_freq, revcomp, before_fetch, t_start,
                 if hasattr(mm, "madvise") and hasattr(mmap, "MADV_SEQUENTIAL"):
                     mm.madvise(mmap.MADV_SEQUENTIAL)
                 whole = np.frombuffer(mm, dtype=np.uint8)
-                # equal windows, none small: one GPU thread inflates one member, a call's time is one member's (~tens of
-                # milliseconds) whatever its size — so as FEW calls as their inflated size allows: the compressed bytes of a
-                # call follow from the file's own ratio (its first members' ISIZE against their sizes; FASTQ with binned
-                # qualities 3.3, with forty quality values 2.1 — one call instead of two for 1.5 GB of it)
-                from . import bgzf_ranges as _br
-                per_call = int(_BGZF_CALL_INFLATED / max(1.0, _br.inflation_ratio(mm, lo, size)))
-                n_calls = max(1, -(-(size - lo) // per_call))
-                pos, window = lo, int(comp_batch) if comp_batch else (size - lo) // n_calls + (1 << 16)
-                t_calls = time.perf_counter()
-                end = min(lo + window, size)             # windows END at fixed places; a window starts where the one before
-                while pos < size:                        # it ran out of whole members (at most 64 KiB in front of that end)
-                    nxt = min(end + window, size)
-                    used, n_rec = dev.map_bgzf(whole[pos:end], fmt=kfmt, k=k, max_index_lookup_frequency=max_freq,
-                                               also_revcomp=revcomp, first=pos == lo, last=end == size,
-                                               head_skip=head_skip if pos == lo else 0,
-                                               tail_stop=tail_stop if end == size else None,
-                                               next_chunk=whole[end:nxt] if nxt > end else None)
-                    if used == 0 and end == size:
-                        raise ValueError("trailing bytes of %s are no complete BGZF member" % path)
-                    pos += used
-                    n_reads += n_rec
-                    if pos < end and end == size:        # the last window held more than one call takes: go on
-                        continue
-                    end = nxt
+                if route == "gzip":
+                    # windows of ~3 GiB INFLATED: the first from a typical FASTQ ratio, every later one from the ratio of what
+                    # the calls before inflated (the trailer's ISIZE is the size mod 2^32: no guide for the large files)
+                    inflated0 = dev.get_param("gzip_inflated_bytes")
+                    window = int(_GZIP_CALL_INFLATED / 4.5)
+                    pos = 0
+                    t_calls = time.perf_counter()
+                    while pos < size:
+                        end = min(pos + window, size)
+                        if size - end < window // 4:     # (no short tail call: a call's time is its slowest lane's)
+                            end = size
+                        used, n_rec = dev.map_gzip(whole[pos:end], fmt=kfmt, k=k, max_index_lookup_frequency=max_freq,
+                                                   also_revcomp=revcomp, first=pos == 0, last=end == size)
+                        n_reads += n_rec
+                        if used == 0:
+                            if end == size:
+                                raise ValueError("trailing bytes of %s are no complete gzip member" % path)
+                            window *= 2                  # no whole deflate block in the window: a longer one
+                            continue
+                        pos += used
+                        ratio = max((dev.get_param("gzip_inflated_bytes") - inflated0) / pos, 1.0)
+                        window = min(max(int(_GZIP_CALL_INFLATED / ratio), 1 << 20), 2 << 30)
+                else:
+                    # equal windows, none small: one GPU thread inflates one member, a call's time is one member's (~tens of
+                    # milliseconds) whatever its size — so as FEW calls as their inflated size allows: the compressed bytes of
+                    # a call follow from the file's own ratio (its first members' ISIZE against their sizes; FASTQ with binned
+                    # qualities 3.3, with forty quality values 2.1 — one call instead of two for 1.5 GB of it)
+                    from . import bgzf_ranges as _br
+                    per_call = int(_BGZF_CALL_INFLATED / max(1.0, _br.inflation_ratio(mm, lo, size)))
+                    n_calls = max(1, -(-(size - lo) // per_call))
+                    pos, window = lo, (size - lo) // n_calls + (1 << 16)
+                    t_calls = time.perf_counter()
+                    end = min(lo + window, size)         # windows END at fixed places; a window starts where the one before
+                    while pos < size:                    # it ran out of whole members (at most 64 KiB in front of that end)
+                        nxt = min(end + window, size)
+                        # each window is announced to the call before it (next_chunk: staged under that call's inflate kernel)
+                        common = dict(first=pos == lo, last=end == size, k=k, max_index_lookup_frequency=max_freq,
+                                      also_revcomp=revcomp, next_chunk=whole[end:nxt] if nxt > end else None)
+                        if route == "bam":
+                            used, n_rec = dev.map_bam(whole[pos:end], **common)
+                            if used == 0 and end == size:
+                                raise ValueError("%s: the BAM header or the trailing bytes are no complete BGZF member" % path)
+                            if used == 0 and pos == lo:  # a header longer than the window: a longer one
+                                end = nxt
+                                continue
+                        else:
+                            used, n_rec = dev.map_bgzf(whole[pos:end], fmt=kfmt, head_skip=head_skip if pos == lo else 0,
+                                                       tail_stop=tail_stop if end == size else None, **common)
+                            if used == 0 and end == size:
+                                raise ValueError("trailing bytes of %s are no complete BGZF member" % path)
+                        pos += used
+                        n_reads += n_rec
+                        if pos < end and end == size:    # the last window held more than one call takes: go on
+                            continue
+                        end = nxt
                 del whole
             finally:
                 try:
@@ -480,24 +461,21 @@ def _map_bgzf_file(dev, path, kfmt, k, max_freq, revcomp, before_fetch, t_start,
                 except BufferError:
                     pass
         n_lookups, n_hits = dev.get_stats()
-        n_members = dev.get_param("bgzf_members")
+        counts = [dev.get_param(c) for c in counters]
         n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
         if before_fetch is not None:
             before_fetch(dev)
         t_fetch = time.perf_counter()
         node_counts = dev.get_node_counts(out=counts_out)
-        logging.info("%.0f ms in kmm_map_bgzf, %.0f ms more until the node counts were on the host",
-                     (t_fetch - t_calls) * 1e3, (time.perf_counter() - t_fetch) * 1e3)
+        logging.info("%.0f ms in kmm_map_%s, %.0f ms more until the node counts were on the host",
+                     (t_fetch - t_calls) * 1e3, route, (time.perf_counter() - t_fetch) * 1e3)
     finally:
         dt = time.perf_counter() - t_start
         dev.close()
     logging.info("Time spent only on hashing and counting hashes: %.5f" % dt)
-    logging.info("Mapped %d reads from %d compressed bytes (%.1f MB/s compressed; %d BGZF members inflated on the GPU): %d k-mer "
-                 "lookups (%.1f M/s), %d index hits" % (n_reads, size - lo, (size - lo) / max(dt, 1e-9) / 1e6, n_members, n_lookups,
-                                                          n_lookups / max(dt, 1e-9) / 1e6, n_hits))
-    logging.info("path_taken: %s (%d batches on the radix path, %d on the direct path; 0 batches packed to 2 bits per base by "
-                 "the host threads)" % ("radix" if n_radix and not n_direct else "direct" if n_direct and not n_radix else "mixed",
-                                        n_radix, n_direct))
+    logging.info(summary % (n_reads, size - lo, (size - lo) / max(dt, 1e-9) / 1e6, *counts, n_lookups,
+                            n_lookups / max(dt, 1e-9) / 1e6, n_hits))
+    _log_path_taken(n_radix, n_direct)
     return node_counts
 
 
@@ -508,71 +486,6 @@ def _check_bam_route(fmt, world_size, exclude_flags):
                          "to its records, which is not implemented (run without torchrun, WORLD_SIZE=1)" % world_size)
     if exclude_flags and fmt not in ("bam", "sam"):
         raise ValueError("--exclude-flags applies to SAM and BAM input only (the reads are %s)" % fmt)
-
-
-def _map_bam_file(dev, path, k, max_freq, revcomp, before_fetch, t_start, comp_batch=None, counts_out=None, exclude_flags=0):
-    """`kmer_mapper map -f reads.bam`: compressed windows of the file mapping -> kmm_map_bam (members inflated, records found and
-    their SEQ decoded on the GPU; the handle carries the bytes behind a window's last complete record to the next one).  Windows
-    as _map_bgzf_file: as few as the inflated size a call takes allows, each one announced to the call before it."""
-    import mmap
-    from . import bgzf_ranges as _br
-    n_reads = size = 0
-    dev.set_param("bam_exclude_flags", int(exclude_flags))
-    try:
-        with open(path, "rb") as f:
-            size = os.fstat(f.fileno()).st_size
-            mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
-            try:
-                if hasattr(mm, "madvise") and hasattr(mmap, "MADV_SEQUENTIAL"):
-                    mm.madvise(mmap.MADV_SEQUENTIAL)
-                whole = np.frombuffer(mm, dtype=np.uint8)
-                per_call = int(_BGZF_CALL_INFLATED / max(1.0, _br.inflation_ratio(mm, 0, size)))
-                n_calls = max(1, -(-size // per_call))
-                pos, window = 0, int(comp_batch) if comp_batch else size // n_calls + (1 << 16)
-                t_calls = time.perf_counter()
-                end = min(window, size)
-                while pos < size:
-                    nxt = min(end + window, size)
-                    used, n_rec = dev.map_bam(whole[pos:end], first=pos == 0, last=end == size, k=k, max_index_lookup_frequency=max_freq,
-                                              also_revcomp=revcomp, next_chunk=whole[end:nxt] if nxt > end else None)
-                    if used == 0 and end == size:
-                        raise ValueError("%s: the BAM header or the trailing bytes are no complete BGZF member" % path)
-                    if used == 0 and pos == 0 and end < size:   # a header longer than the window: a longer one
-                        end = nxt
-                        continue
-                    pos += used
-                    n_reads += n_rec
-                    if pos < end and end == size:
-                        continue
-                    end = nxt
-                del whole
-            finally:
-                try:
-                    mm.close()
-                except BufferError:
-                    pass
-        n_lookups, n_hits = dev.get_stats()
-        n_members = dev.get_param("bgzf_members")
-        n_excl, n_false = dev.get_param("bam_records_excluded"), dev.get_param("bam_false_starts")
-        n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
-        if before_fetch is not None:
-            before_fetch(dev)
-        t_fetch = time.perf_counter()
-        node_counts = dev.get_node_counts(out=counts_out)
-        logging.info("%.0f ms in kmm_map_bam, %.0f ms more until the node counts were on the host",
-                     (t_fetch - t_calls) * 1e3, (time.perf_counter() - t_fetch) * 1e3)
-    finally:
-        dt = time.perf_counter() - t_start
-        dev.close()
-    logging.info("Time spent only on hashing and counting hashes: %.5f" % dt)
-    logging.info("Mapped %d BAM records from %d compressed bytes (%.1f MB/s compressed; %d BGZF members inflated and the records "
-                 "decoded on the GPU; %d records excluded by flag, %d false record starts): %d k-mer lookups (%.1f M/s), %d index "
-                 "hits" % (n_reads, size, size / max(dt, 1e-9) / 1e6, n_members, n_excl, n_false, n_lookups,
-                           n_lookups / max(dt, 1e-9) / 1e6, n_hits))
-    logging.info("path_taken: %s (%d batches on the radix path, %d on the direct path; 0 batches packed to 2 bits per base by "
-                 "the host threads)" % ("radix" if n_radix and not n_direct else "direct" if n_direct and not n_radix else "mixed",
-                                        n_radix, n_direct))
-    return node_counts
 
 
 def map_bnp(args):

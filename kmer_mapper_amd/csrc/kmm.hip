@@ -59,6 +59,11 @@ static int guarded(const char *what, F body)
     }
 }
 
+static double ms_since(std::chrono::steady_clock::time_point a)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+}
+
 #define HIPCHK(expr)                                                                               \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -692,9 +697,6 @@ int launch_rx(kmm_index *ix, const ReadsView &rv, const uint64_t *kmers_in, int6
     int64_t n_sub = 1, max_src = 0;
     static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
     const auto t_0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
     if (ix->rx_sub_cap_eff > 0 && ++ix->rx_sub_cap_eff_age >= 16)
         ix->rx_sub_cap_eff = 0;
     int64_t cap = ix->rx_sub_cap_eff > 0 && ix->rx_sub_cap_eff < ix->rx_sub_cap ? ix->rx_sub_cap_eff : ix->rx_sub_cap;
@@ -2154,9 +2156,6 @@ static int map_reads_host_packed(kmm_index_t *ix, const uint8_t *bases, const in
         return KMM_OK; // (no threads / no page-locked memory to be had: the ordinary route)
     static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
     const auto t_0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
     Stage &s = next_stage(ix);
     KMMCHK(stage_acquire(ix, s));
     KMMCHK(ensure(s.kmers, code_bytes));
@@ -2309,9 +2308,6 @@ static int map_records_host_packed(kmm_index_t *ix, const uint8_t *raw, int64_t 
     const size_t code_bytes = (n / 4 + 1024 + 63) & ~(size_t)63, bits_bytes = (n / 8 + 256 + 63) & ~(size_t)63;
     static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
     const auto t_0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
     if (!ensure_pack_pool(ix) || !ensure_pinned(ix->pack_pinned, ix->pack_pinned_bytes, code_bytes) ||
         !ensure_pinned(ix->pack_bits_pinned, ix->pack_bits_pinned_bytes, bits_bytes))
         return KMM_OK;
@@ -2619,9 +2615,6 @@ static int map_records_radix_call(kmm_index_t *ix, const uint8_t *raw, int64_t n
 {
     static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
     const auto t_0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
     Stage &s = next_stage(ix);
     KMMCHK(stage_acquire(ix, s));
     const double ms_acquire = ms_since(t_0);
@@ -3002,16 +2995,12 @@ int kmm_map_packed(kmm_index_t *ix, const uint32_t *codes, int64_t n_bases, int6
 static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre, int64_t n_comp, uint8_t *d_comp, unsigned long long out_cap,
                                BgzfStaged &st, bool walk = true)
 {
-    auto ms_since = [](std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
     std::vector<unsigned long long> &m_off = st.m_off, &o_off = st.o_rel;
     m_off.assign(1, 0ull);
-    o_off.assign(1, 0ull);
-    const int64_t carry = 0; // (offsets relative to the chunk: the caller adds what it carries over)
+    o_off.assign(1, 0ull); // (offsets relative to the chunk: the caller adds what it carries over)
     uint64_t &p = st.p;
     p = 0;
-    bool chain_end = false, last_chunk = false;
+    bool chain_end = false;
     int &chain_err = st.chain_err;
     uint32_t &bad_isize = st.bad_isize, &bad_ms = st.bad_ms;
     chain_err = 0;
@@ -3047,7 +3036,7 @@ static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre
                 chain_end = true;
                 return;
             }
-            if (o_off.back() - (unsigned long long)carry + isize > out_cap && m_off.size() > 1) {
+            if (o_off.back() + isize > out_cap && m_off.size() > 1) {
                 st.hit_cap = true; // (the call stops at its own size limit: the caller continues with the same flags)
                 chain_end = true;
                 return;
@@ -3059,7 +3048,6 @@ static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre
         if (all)
             chain_end = true;
     };
-    (void)last_chunk;
     bool &staged = st.staged;
     double &ms_scan_inside = st.ms_scan_inside;
     staged = false;
@@ -3161,57 +3149,127 @@ int kmm_map_bgzf_hint_next(kmm_index_t *ix, const uint8_t *comp_next, int64_t n_
     return KMM_OK;
 }
 
-static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
-                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records, bool bam = false);
+// ---- Compressed read streams (kmm_map_bgzf, kmm_map_gzip, kmm_map_bam): one stream per handle, started by KMM_FORMAT_NEW_STREAM
+// and ended by KMM_FORMAT_LAST_CHUNK; the inflated bytes behind a call's last complete record are carried to the next call.
+struct StreamCall {
+    const char *who;
+    int k, max_freq, also_revcomp;
+    const uint8_t *lut;
+    int64_t *consumed_comp, *n_records;
+    int fmt = 0; // the format without the stream flags (stream_call_start)
+    bool new_stream = false, last_chunk = false;
+};
 
-int kmm_map_bgzf(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
-                 const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
-{
-    return guarded("kmm_map_bgzf", [&] { return map_bgzf_entry(ix, comp, n_comp, format, k, max_freq, also_revcomp, lut, consumed_comp, n_records); });
-}
-
-static int bam_map_inflated(kmm_index_t *ix, uint8_t *d_raw, int64_t n_raw, bool new_stream, bool last_chunk, int k, int max_freq,
-                            int also_revcomp, const uint8_t *lut, int64_t *used, int64_t *n_records, bool *short_header);
-
-// bam: the members hold a BAM stream (kmm_map_bam) — the same staging, member chain, inflate and CRC kernels and carry; the
-// inflated bytes then go through bam_map_inflated instead of the text record parser.
-static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
-                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records, bool bam)
+// text: FASTQ, two-line FASTA or SAM (else BAM: the flags alone); chain: a BGZF member chain is walked in the caller's bytes
+static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp, int64_t n_comp, int format, bool text, bool chain)
 {
     if (!ix)
         return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
-    KMMCHK(check_k(k));
-    const char *who = bam ? "kmm_map_bam" : "kmm_map_bgzf";
-    bool last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
-    const bool new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
-    const int fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
-    if (bam ? fmt != 0 : fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2 && fmt != KMM_FORMAT_SAM)
-        return fail(KMM_ERR_INVALID_ARG, bam ? "kmm_map_bam: flags take KMM_FORMAT_NEW_STREAM and KMM_FORMAT_LAST_CHUNK only"
-                                             : "kmm_map_bgzf: format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2) or "
-                                               "KMM_FORMAT_SAM (8)");
+    KMMCHK(check_k(c.k));
+    c.last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
+    c.new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
+    c.fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
+    if (text ? c.fmt != KMM_FORMAT_FASTQ && c.fmt != KMM_FORMAT_FASTA2 && c.fmt != KMM_FORMAT_SAM : c.fmt != 0)
+        return fail(KMM_ERR_INVALID_ARG, text ? "%s: format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2) or KMM_FORMAT_SAM (8)"
+                                              : "%s: flags take KMM_FORMAT_NEW_STREAM and KMM_FORMAT_LAST_CHUNK only", c.who);
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
-    if (consumed_comp)
-        *consumed_comp = 0;
-    if (n_records)
-        *n_records = 0;
+    if (c.consumed_comp)
+        *c.consumed_comp = 0;
+    if (c.n_records)
+        *c.n_records = 0;
     if (n_comp > 0 && is_device_ptr(comp))
-        return fail(KMM_ERR_INVALID_ARG, "%s takes the compressed bytes from host memory (the member chain is read there)", who);
+        return fail(KMM_ERR_INVALID_ARG, "%s takes the compressed bytes from host memory%s", c.who,
+                    chain ? " (the member chain is read there)" : "");
     HIPCHK(hipSetDevice(ix->device));
-    if (new_stream)
+    return KMM_OK;
+}
+
+static int ensure_crc_tables(kmm_index_t *ix) // the CRC32 tables (slicing by 8), once per handle
+{
+    if (ix->bgzf_crc.p)
+        return KMM_OK;
+    std::vector<uint32_t> t(kmm_gz::CRC_TABLE_WORDS);
+    for (int kk = 0; kk < 8; ++kk)
+        for (uint32_t bb = 0; bb < 256u; ++bb)
+            t[(size_t)kk * 256 + bb] = kmm_gz::crc_table_entry(kk, bb);
+    for (int kk = 0; kk < kmm_gz::CRC_SHIFT_WORDS; ++kk) // (x^(8 * 2^kk): a part's register moved forward by the bytes behind it)
+        t[8 * 256 + kk] = kmm_gz::crc_shift_table_entry(kk);
+    KMMCHK(ensure(ix->bgzf_crc, t.size() * 4));
+    HIPCHK(hipMemcpy(ix->bgzf_crc.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    return KMM_OK;
+}
+
+// The bytes behind a call's last complete record, d_raw[used, n_raw), are carried to the next call (none on the last one).
+static int keep_carry(kmm_index_t *ix, const StreamCall &c, const uint8_t *d_raw, int64_t used, int64_t n_raw, DevBuf &carry,
+                      int64_t &carry_len)
+{
+    const int64_t tail = n_raw - used;
+    if (c.last_chunk && tail > 0) {
+        carry_len = 0;
+        return fail(KMM_ERR_MALFORMED, "%s: the stream ends with %lld bytes that form no complete record", c.who, (long long)tail);
+    }
+    if (tail > 0) {
+        KMMCHK(ensure(carry, (size_t)tail + 64)); // (may free and reallocate: a device-wide sync, rare)
+        HIPCHK(hipMemcpyAsync(carry.p, d_raw + used, (size_t)tail, hipMemcpyDeviceToDevice, ix->stream));
+    }
+    carry_len = tail;
+    return KMM_OK;
+}
+
+// The verified inflated bytes d_raw[head, n_raw) of a text stream call (kmm_map_bgzf, kmm_map_gzip): on LAST_CHUNK a last line
+// without its newline gets one (last_byte = d_raw[n_raw - 1]), then the records are mapped; *used: where the last complete one ends.
+static int map_text_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw, int64_t head, int64_t &n_raw, size_t cap,
+                             uint8_t last_byte, int64_t *used)
+{
+    if (c.last_chunk && n_raw > head && last_byte != 10) { // a last line without its newline gets one (as the file readers do)
+        if (cap < (size_t)n_raw + 1)
+            return fail(KMM_ERR_INTERNAL, "%s: no room for the final newline", c.who);
+        HIPCHK(hipMemsetAsync(d_raw + n_raw, 10, 1, ix->stream));
+        ++n_raw;
+    }
+    int64_t recs = 0;
+    *used = 0;
+    if (n_raw > head)
+        KMMCHK(kmm_map_records(ix, d_raw + head, n_raw - head, c.fmt, c.k, c.max_freq, c.also_revcomp, c.lut, used, &recs));
+    *used += head;
+    if (c.n_records)
+        *c.n_records = recs;
+    return KMM_OK;
+}
+
+// What bgzf_inflate returns: the verified inflated bytes d_raw[head, n_raw) (the carry in front) in the buffer pair `cur`;
+// d_raw stays NULL when there is no member and no carry to finish (the call is over).
+struct BgzfCall {
+    BgzfStaged st;
+    int cur = 0;
+    uint8_t *d_raw = nullptr;
+    int64_t head = 0, n_raw = 0;
+    uint8_t last_byte = 10; // d_raw[n_raw - 1] on LAST_CHUNK
+    uint32_t n_members = 0;
+    bool from_pre = false;
+    std::chrono::steady_clock::time_point t_0;
+    double ms_stage = 0, ms_scan = 0, ms_inflate = 0;
+};
+
+// kmm_map_bgzf and kmm_map_bam up to their verified inflated bytes: the chunk is staged and its member chain walked (or both were
+// done under the call before), the members are inflated behind the carried bytes and their CRC32s checked by kernels on the
+// handle's stream, and the chunk announced behind this one is staged meanwhile.  narrow (kmm_map_bgzf: a rank's share of a
+// file) may set b.head and b.n_raw while the kernels run.
+static int bgzf_inflate(kmm_index_t *ix, StreamCall &c, const uint8_t *comp, int64_t n_comp, BgzfCall &b,
+                        int (*narrow)(kmm_index_t *, const StreamCall &, BgzfCall &))
+{
+    const char *who = c.who;
+    if (c.new_stream)
         ix->bgzf_carry_len = 0;
-    static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
-    const auto t_0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
+    const auto t_0 = b.t_0 = std::chrono::steady_clock::now();
     // The compressed bytes go through a RING of page-locked memory (8 slots of 16 MiB; from a file mapping — pageable memory —
     // the runtime's own staging is slow, and a page-locked buffer the size of the window costs ~50 ms per GB to make, more
     // than the whole call): the packing threads copy 1 MiB pieces into the slots, a slot leaves for HBM as soon as it is full
     // and is refilled when its copy has landed.  The member chain is read from the caller's bytes BEHIND the threads — what
     // they have copied is mapped into the process, so the walk (two cache lines per member) pays no page fault — and at the
     // same time: the calling thread has nothing else to do while the threads copy.
-    const int cur = ix->bgzf_cur;
+    const int cur = b.cur = ix->bgzf_cur;
     ix->bgzf_cur ^= 1;
     if (!ix->bgzf_done[cur])
         HIPCHK(hipEventCreateWithFlags(&ix->bgzf_done[cur], hipEventDisableTiming));
@@ -3219,16 +3277,15 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     // 3.5 GiB per call; what a prestaged chain leaves for a carry ("debug_bgzf_call_cap_kb": a small file reaches the cap)
     const unsigned long long CALL_CAP = ix->dbg_bgzf_call_cap_kb > 0 ? (unsigned long long)ix->dbg_bgzf_call_cap_kb << 10 : 7ull << 29,
                              PRE_CARRY = ix->dbg_bgzf_call_cap_kb > 0 ? CALL_CAP / 4 : 256ull << 20;
-    BgzfStaged st;
-    bool from_pre = false;
+    BgzfStaged &st = b.st;
     if (ix->bgzf_pre_valid && ix->bgzf_pre_from == comp && ix->bgzf_pre_n == n_comp && ix->bgzf_pre_buf == cur &&
         (unsigned long long)carry <= PRE_CARRY) {
         st = std::move(ix->bgzf_pre); // staged and walked while the chunk before this one was being inflated
         st.ms_scan_inside = 0;
-        from_pre = true;
+        b.from_pre = true;
     }
     ix->bgzf_pre_valid = false;
-    if (!from_pre) {
+    if (!b.from_pre) {
         if (ix->bgzf_used[cur])
             HIPCHK(hipStreamWaitEvent(ix->copy_stream, ix->bgzf_done[cur], 0)); // the kernels that last read these buffers are done
         KMMCHK(ensure(ix->bgzf_comp[cur], (size_t)n_comp + 64));
@@ -3237,8 +3294,8 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     uint8_t *d_comp = (uint8_t *)ix->bgzf_comp[cur].p;
     const bool staged = st.staged;
     if (st.hit_cap)
-        last_chunk = false; // (the call stops at its own size limit: the caller continues with the same flags)
-    const double ms_stage = ms_since(t_0) - st.ms_scan_inside;
+        c.last_chunk = false; // (the call stops at its own size limit: the caller continues with the same flags)
+    const double ms_stage = b.ms_stage = ms_since(t_0) - st.ms_scan_inside;
     const uint64_t p = st.p;
     if (st.chain_err) {
         (void)hipStreamSynchronize(ix->copy_stream); // (the page-locked ring is free again)
@@ -3251,39 +3308,30 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     std::vector<unsigned long long> &m_off = st.m_off, &o_off = st.o_rel;
     for (unsigned long long &o : o_off) // (the inflated bytes carried over from the call before lie in front)
         o += (unsigned long long)carry;
-    const uint32_t n_members = (uint32_t)(m_off.size() - 1);
+    const uint32_t n_members = b.n_members = (uint32_t)(m_off.size() - 1);
     const int64_t n_used = (int64_t)p, n_total = (int64_t)o_off.back();
-    if (consumed_comp)
-        *consumed_comp = n_used;
-    if (last_chunk && n_used != n_comp) {
+    if (c.consumed_comp)
+        *c.consumed_comp = n_used;
+    if (c.last_chunk && n_used != n_comp) {
         (void)hipStreamSynchronize(ix->copy_stream);
         return fail(KMM_ERR_MALFORMED, "%s: the file ends inside a BGZF member (%lld bytes behind the last whole member)", who,
                     (long long)(n_comp - n_used));
     }
-    if (n_members == 0 && !(last_chunk && carry > 0)) {
+    if (n_members == 0 && !(c.last_chunk && carry > 0)) {
         HIPCHK(hipStreamSynchronize(ix->copy_stream)); // (the page-locked buffer is free again)
         return KMM_OK;
     }
-    const double ms_scan = ms_since(t_0) - ms_stage;
+    b.ms_scan = ms_since(t_0) - ms_stage;
     KMMCHK(ensure(ix->bgzf_raw[cur], (size_t)n_total + 4096));
     KMMCHK(ensure(ix->bgzf_meta[cur], (size_t)(n_members + 1) * 16 + 64));
     KMMCHK(ensure(ix->bgzf_err, 64));
-    if (!ix->bgzf_crc.p) { // the CRC32 tables (slicing by 8), once per handle
-        std::vector<uint32_t> t(kmm_gz::CRC_TABLE_WORDS);
-        for (int kk = 0; kk < 8; ++kk)
-            for (uint32_t bb = 0; bb < 256u; ++bb)
-                t[(size_t)kk * 256 + bb] = kmm_gz::crc_table_entry(kk, bb);
-        for (int kk = 0; kk < kmm_gz::CRC_SHIFT_WORDS; ++kk) // (x^(8 * 2^kk): a part's register moved forward by the bytes behind it)
-            t[8 * 256 + kk] = kmm_gz::crc_shift_table_entry(kk);
-        KMMCHK(ensure(ix->bgzf_crc, t.size() * 4));
-        HIPCHK(hipMemcpy(ix->bgzf_crc.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    }
+    KMMCHK(ensure_crc_tables(ix));
     const uint32_t grid_threads = ((n_members < 65536u ? n_members : 65536u) + 63u) / 64u * 64u;
     if (n_members) {
         KMMCHK(ensure(ix->bgzf_tabs, (size_t)grid_threads * kmm_gz::SCRATCH_BYTES));
         KMMCHK(ensure(ix->bgzf_status, (size_t)n_members + 64));
     }
-    uint8_t *d_raw = (uint8_t *)ix->bgzf_raw[cur].p;
+    uint8_t *d_raw = b.d_raw = (uint8_t *)ix->bgzf_raw[cur].p;
     unsigned long long *d_moff = (unsigned long long *)ix->bgzf_meta[cur].p, *d_ooff = d_moff + (n_members + 1);
     if (n_members) {
         if (!staged)
@@ -3335,35 +3383,15 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
     }
     ix->bgzf_hint_ptr = nullptr;
     ix->bgzf_hint_n = 0;
-    // A RANK'S SHARE of a file (kmer_mapper map with several ranks, bgzf_ranges.py): its first member starts inside a record
-    // that belongs to the rank before it — "bgzf_head_skip" bytes of the stream's first member are passed over — and its last
-    // member holds the start of the next rank's first record — only "bgzf_tail_stop" bytes of the last member are taken.
-    int64_t head = 0, n_raw = n_total;
-    if (new_stream && !bam) {
-        head = ix->bgzf_head_skip;
-        ix->bgzf_head_skip = 0;
-    }
-    if (last_chunk && ix->bgzf_tail_stop >= 0 && !bam) {
-        if (n_members == 0 || (unsigned long long)ix->bgzf_tail_stop > o_off[n_members] - o_off[n_members - 1]) {
-            (void)hipStreamSynchronize(ix->stream);
-            return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf: bgzf_tail_stop %lld lies beyond the last member's %llu bytes",
-                        (long long)ix->bgzf_tail_stop, n_members ? o_off[n_members] - o_off[n_members - 1] : 0ull);
-        }
-        n_raw = (int64_t)o_off[n_members - 1] + ix->bgzf_tail_stop;
-        ix->bgzf_tail_stop = -1;
-    }
-    if (head > n_raw) {
-        (void)hipStreamSynchronize(ix->stream);
-        return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf: bgzf_head_skip %lld lies beyond the %lld bytes of the call", (long long)head,
-                    (long long)n_raw);
-    }
+    b.n_raw = n_total;
+    if (narrow)
+        KMMCHK(narrow(ix, c, b));
     unsigned int err[4] = {0, 0, 0, 0};
-    uint8_t last_byte = 10;
     HIPCHK(hipMemcpyAsync(err, ix->bgzf_err.p, sizeof err, hipMemcpyDeviceToHost, ix->stream));
-    if (last_chunk && n_raw > head)
-        HIPCHK(hipMemcpyAsync(&last_byte, d_raw + n_raw - 1, 1, hipMemcpyDeviceToHost, ix->stream));
+    if (c.last_chunk && b.n_raw > b.head)
+        HIPCHK(hipMemcpyAsync(&b.last_byte, d_raw + b.n_raw - 1, 1, hipMemcpyDeviceToHost, ix->stream));
     HIPCHK(hipStreamSynchronize(ix->stream)); // (CRC32 / ISIZE of every member are checked before a byte is mapped)
-    const double ms_inflate = ms_since(t_0) - ms_scan - ms_stage;
+    b.ms_inflate = ms_since(t_0) - b.ms_scan - ms_stage;
     ix->bgzf_calls++;
     ix->bgzf_members += n_members;
     if (err[0]) {
@@ -3374,46 +3402,67 @@ static int map_bgzf_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, 
         return fail(KMM_ERR_MALFORMED, "%s: %u corrupt BGZF member(s); the first starts at compressed byte %llu of the chunk: %s",
                     who, err[0], err[1] < n_members ? m_off[err[1]] : 0ull, err[2] < 12 ? why[err[2]] : "?");
     }
-    if (!bam && last_chunk && n_raw > head && last_byte != 10) { // a last line without its newline gets one (as the file readers do)
-        HIPCHK(hipMemsetAsync(d_raw + n_raw, 10, 1, ix->stream));
-        ++n_raw;
-    }
-    int64_t used = 0, recs = 0;
-    if (bam) {
-        bool short_header = false;
-        const int rc = bam_map_inflated(ix, d_raw, n_raw, new_stream, last_chunk, k, max_freq, also_revcomp, lut, &used, &recs, &short_header);
-        if (rc != KMM_OK || short_header) { // (an error, or a first window that ends inside the header: nothing used, nothing kept)
-            ix->bgzf_carry_len = 0;
-            ix->bgzf_pre_valid = false;
-            if (consumed_comp)
-                *consumed_comp = 0;
-            HIPCHK(hipEventRecord(ix->bgzf_done[cur], ix->stream));
-            ix->bgzf_used[cur] = true;
-            return rc;
-        }
-    } else if (n_raw > head)
-        KMMCHK(kmm_map_records(ix, d_raw + head, n_raw - head, fmt, k, max_freq, also_revcomp, lut, &used, &recs));
-    used += head;
-    if (n_records)
-        *n_records = recs;
+    return KMM_OK;
+}
+
+// The end of a kmm_map_bgzf / kmm_map_bam call whose records are mapped up to d_raw[used]: the rest is carried, and the buffers
+// `cur` are free again once the handle's stream has passed what the call queued.
+static int bgzf_finish(kmm_index_t *ix, const StreamCall &c, const BgzfCall &b, int64_t used)
+{
+    static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
     if (verbose)
         fprintf(stderr, "libkmm: %s: %u members, %lld -> %lld bytes: member scan %.2f ms, buffers + staging + copy %.2f ms%s, "
-                "copy tail + inflate kernel%s %.2f ms, records %.2f ms\n", who, n_members, (long long)n_used, (long long)n_total, ms_scan, ms_stage,
-                from_pre ? " (staged and walked under the call before)" : "", ix->bgzf_pre_valid ? " + the next chunk's staging" : "",
-                ms_inflate, ms_since(t_0) - ms_scan - ms_stage - ms_inflate);
-    const int64_t tail = n_raw - used;
-    if (last_chunk && tail > 0) {
-        ix->bgzf_carry_len = 0;
-        return fail(KMM_ERR_MALFORMED, "%s: the stream ends with %lld bytes that form no complete record", who, (long long)tail);
-    }
-    if (tail > 0) {
-        KMMCHK(ensure(ix->bgzf_carry, (size_t)tail + 64)); // (may free and reallocate: a device-wide sync, rare)
-        HIPCHK(hipMemcpyAsync(ix->bgzf_carry.p, d_raw + used, (size_t)tail, hipMemcpyDeviceToDevice, ix->stream));
-    }
-    ix->bgzf_carry_len = tail;
-    HIPCHK(hipEventRecord(ix->bgzf_done[cur], ix->stream));
-    ix->bgzf_used[cur] = true;
+                "copy tail + inflate kernel%s %.2f ms, records %.2f ms\n", c.who, b.n_members, (long long)b.st.p, (long long)b.st.o_rel.back(),
+                b.ms_scan, b.ms_stage, b.from_pre ? " (staged and walked under the call before)" : "",
+                ix->bgzf_pre_valid ? " + the next chunk's staging" : "", b.ms_inflate, ms_since(b.t_0) - b.ms_scan - b.ms_stage - b.ms_inflate);
+    KMMCHK(keep_carry(ix, c, b.d_raw, used, b.n_raw, ix->bgzf_carry, ix->bgzf_carry_len));
+    HIPCHK(hipEventRecord(ix->bgzf_done[b.cur], ix->stream));
+    ix->bgzf_used[b.cur] = true;
     return KMM_OK;
+}
+
+// A RANK'S SHARE of a file (kmer_mapper map with several ranks, bgzf_ranges.py): its first member starts inside a record
+// that belongs to the rank before it — "bgzf_head_skip" bytes of the stream's first member are passed over — and its last
+// member holds the start of the next rank's first record — only "bgzf_tail_stop" bytes of the last member are taken.
+static int bgzf_rank_share(kmm_index_t *ix, const StreamCall &c, BgzfCall &b)
+{
+    const uint32_t n_members = b.n_members;
+    const std::vector<unsigned long long> &o_off = b.st.o_rel;
+    if (c.new_stream) {
+        b.head = ix->bgzf_head_skip;
+        ix->bgzf_head_skip = 0;
+    }
+    if (c.last_chunk && ix->bgzf_tail_stop >= 0) {
+        if (n_members == 0 || (unsigned long long)ix->bgzf_tail_stop > o_off[n_members] - o_off[n_members - 1]) {
+            (void)hipStreamSynchronize(ix->stream);
+            return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf: bgzf_tail_stop %lld lies beyond the last member's %llu bytes",
+                        (long long)ix->bgzf_tail_stop, n_members ? o_off[n_members] - o_off[n_members - 1] : 0ull);
+        }
+        b.n_raw = (int64_t)o_off[n_members - 1] + ix->bgzf_tail_stop;
+        ix->bgzf_tail_stop = -1;
+    }
+    if (b.head > b.n_raw) {
+        (void)hipStreamSynchronize(ix->stream);
+        return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf: bgzf_head_skip %lld lies beyond the %lld bytes of the call", (long long)b.head,
+                    (long long)b.n_raw);
+    }
+    return KMM_OK;
+}
+
+int kmm_map_bgzf(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
+                 const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
+{
+    StreamCall c{"kmm_map_bgzf", k, max_freq, also_revcomp, lut, consumed_comp, n_records};
+    return guarded(c.who, [&] {
+        KMMCHK(stream_call_start(ix, c, comp, n_comp, format, true, true));
+        BgzfCall b;
+        KMMCHK(bgzf_inflate(ix, c, comp, n_comp, b, bgzf_rank_share));
+        if (!b.d_raw)
+            return KMM_OK;
+        int64_t used = 0;
+        KMMCHK(map_text_inflated(ix, c, b.d_raw, b.head, b.n_raw, ix->bgzf_raw[b.cur].cap, b.last_byte, &used));
+        return bgzf_finish(ix, c, b, used);
+    });
 }
 
 // ---- kmm_map_bam: BAM records found and decoded on the GPU (kmm_bam.hpp; the orchestration there, run_call, is shared with the
@@ -3486,14 +3535,12 @@ struct BamGpuBackend {
 // The inflated bytes of a kmm_map_bam call (d_raw[0, n_raw): the carry of the call before in front): the header on a stream's
 // first call, then the records up to the last complete one (*used), decoded into two-line FASTA in HBM and mapped by
 // kmm_map_records.  *short_header: a first window that ends inside the header (nothing is used).
-static int bam_map_inflated(kmm_index_t *ix, uint8_t *d_raw, int64_t n_raw, bool new_stream, bool last_chunk, int k, int max_freq,
-                            int also_revcomp, const uint8_t *lut, int64_t *used, int64_t *n_records, bool *short_header)
+static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw, int64_t n_raw, int64_t *used, bool *short_header)
 {
     *used = 0;
-    *n_records = 0;
     *short_header = false;
     uint64_t start0 = 0;
-    if (new_stream) {
+    if (c.new_stream) {
         // the header (magic, l_text, text, n_ref, the references) is read back in growing prefixes: its length is only known by
         // walking it, and it is read once per stream
         ix->bam_n_ref = -1;
@@ -3511,7 +3558,7 @@ static int bam_map_inflated(kmm_index_t *ix, uint8_t *d_raw, int64_t n_raw, bool
             if (r == 0)
                 break;
             if (want == (uint64_t)n_raw) {
-                if (last_chunk)
+                if (c.last_chunk)
                     return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside the BAM header (%lld bytes)", (long long)n_raw);
                 *short_header = true;
                 return KMM_OK;
@@ -3532,7 +3579,7 @@ static int bam_map_inflated(kmm_index_t *ix, uint8_t *d_raw, int64_t n_raw, bool
     if (co.err_pos != kmm_bam::NONE)
         return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the record at inflated byte %llu of the call does not fit its block_size (or its "
                     "refID / next_refID / read_name are not a record's)", co.err_pos);
-    if (last_chunk && co.consumed != (uint64_t)n_raw)
+    if (c.last_chunk && co.consumed != (uint64_t)n_raw)
         return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside a record (%lld bytes behind the last complete one)",
                     (long long)(n_raw - (int64_t)co.consumed));
     ix->bam_calls++;
@@ -3544,20 +3591,39 @@ static int bam_map_inflated(kmm_index_t *ix, uint8_t *d_raw, int64_t n_raw, bool
     KMMCHK(ensure(ix->bam_out, (size_t)co.out_bytes + 64));
     KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p));
     int64_t taken = 0, recs = 0;
-    KMMCHK(kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, KMM_FORMAT_FASTA2, k, max_freq, also_revcomp, lut,
-                           &taken, &recs));
+    KMMCHK(kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, KMM_FORMAT_FASTA2, c.k, c.max_freq, c.also_revcomp,
+                           c.lut, &taken, &recs));
     if (taken != (int64_t)co.out_bytes || recs != (int64_t)co.recs)
         return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %llu decoded bytes, %lld of %llu records mapped", (long long)taken,
                     co.out_bytes, (long long)recs, co.recs);
-    *n_records = recs;
+    if (c.n_records)
+        *c.n_records = recs;
     return KMM_OK;
 }
 
 int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags, int k, int max_freq, int also_revcomp,
                 const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
 {
-    return guarded("kmm_map_bam", [&] {
-        return map_bgzf_entry(ix, comp, n_comp, flags, k, max_freq, also_revcomp, lut, consumed_comp, n_records, true);
+    StreamCall c{"kmm_map_bam", k, max_freq, also_revcomp, lut, consumed_comp, n_records};
+    return guarded(c.who, [&] {
+        KMMCHK(stream_call_start(ix, c, comp, n_comp, flags, false, true));
+        BgzfCall b;
+        KMMCHK(bgzf_inflate(ix, c, comp, n_comp, b, nullptr));
+        if (!b.d_raw)
+            return KMM_OK;
+        int64_t used = 0;
+        bool short_header = false;
+        const int rc = bam_map_inflated(ix, c, b.d_raw, b.n_raw, &used, &short_header);
+        if (rc != KMM_OK || short_header) { // (an error, or a first window that ends inside the header: nothing used, nothing kept)
+            ix->bgzf_carry_len = 0;
+            ix->bgzf_pre_valid = false;
+            if (c.consumed_comp)
+                *c.consumed_comp = 0;
+            HIPCHK(hipEventRecord(ix->bgzf_done[b.cur], ix->stream));
+            ix->bgzf_used[b.cur] = true;
+            return rc;
+        }
+        return bgzf_finish(ix, c, b, used);
     });
 }
 
@@ -3569,7 +3635,8 @@ struct GzGpuBackend {
     const uint8_t *d_in = nullptr;
     uint32_t n_pad = 0;
     uint64_t n = 0;
-    uint8_t *d_out = nullptr; // where the call's inflated bytes go
+    int64_t carry = 0;        // inflated bytes carried over from the call before: they lie in front in gz_raw
+    uint8_t *d_out = nullptr; // where the call's inflated bytes go: gz_raw behind the carried bytes
     size_t blk = 0, used = 0; // arena block in use, bytes used in it
     int rc = KMM_OK;
     uint32_t n_chunks = 0;
@@ -3625,7 +3692,7 @@ struct GzGpuBackend {
         if (!hip(hipGetLastError(), "k_gz_find") ||
             !hip(hipMemcpyAsync(starts, ix->gz_res.p, (size_t)n_cand * 8, hipMemcpyDeviceToHost, ix->stream), "starts") || !sync())
             return false;
-        ms_find += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ms_find += ms_since(t0);
         return true;
     }
     bool decode(const kmm_gunzip::Work *w, kmm_gunzip::Result *r, size_t k)
@@ -3640,7 +3707,7 @@ struct GzGpuBackend {
         if (!hip(hipGetLastError(), "k_gz_decode") ||
             !hip(hipMemcpyAsync(r, ix->gz_res.p, k * sizeof(kmm_gunzip::Result), hipMemcpyDeviceToHost, ix->stream), "results") || !sync())
             return false;
-        ms_decode += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ms_decode += ms_since(t0);
         return true;
     }
     bool windows(const kmm_gunzip::MapRef *maps, uint32_t nc, uint32_t G)
@@ -3661,11 +3728,29 @@ struct GzGpuBackend {
         launches += 3;
         if (!hip(hipGetLastError(), "window kernels") || !sync())
             return false;
-        ms_windows += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ms_windows += ms_since(t0);
         return true;
     }
     bool resolve(const kmm_gunzip::PieceRef *p, size_t k, uint64_t *bad)
     {
+        uint64_t need = 0;
+        for (size_t i = 0; i < k; ++i)
+            need = p[i].off + p[i].n > need ? p[i].off + p[i].n : need;
+        DevBuf &raw = ix->gz_raw;
+        if (raw.cap < (size_t)carry + need + 4096) { // (the carried bytes move along)
+            DevBuf nb;
+            if ((rc = ensure(nb, (size_t)carry + need + need / 8 + 4096)) != KMM_OK)
+                return false;
+            if (carry > 0 && !hip(hipMemcpyAsync(nb.p, ix->gz_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream), "carry"))
+                return false;
+            if (!sync())
+                return false;
+            release(raw);
+            raw = nb;
+        } else if (carry > 0 && !hip(hipMemcpyAsync(raw.p, ix->gz_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream), "carry")) {
+            return false;
+        }
+        d_out = (uint8_t *)raw.p + carry;
         const auto t0 = std::chrono::steady_clock::now();
         *bad = 0;
         if (!k)
@@ -3682,7 +3767,7 @@ struct GzGpuBackend {
             !sync())
             return false;
         *bad = e;
-        ms_resolve += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ms_resolve += ms_since(t0);
         return true;
     }
     bool crc(const kmm_gunzip::Part *p, size_t k, uint32_t *regs)
@@ -3696,203 +3781,117 @@ struct GzGpuBackend {
         if (!hip(hipGetLastError(), "k_gz_crc") || !hip(hipMemcpyAsync(regs, ix->gz_res.p, k * 4, hipMemcpyDeviceToHost, ix->stream), "regs") ||
             !sync())
             return false;
-        ms_crc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        ms_crc += ms_since(t0);
         return true;
     }
 };
 
-static int map_gzip_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
-                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
-
 int kmm_map_gzip(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
                  const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
 {
-    return guarded("kmm_map_gzip", [&] { return map_gzip_entry(ix, comp, n_comp, format, k, max_freq, also_revcomp, lut, consumed_comp, n_records); });
-}
-
-static int map_gzip_entry(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int format, int k, int max_freq, int also_revcomp,
-                          const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
-{
-    if (!ix)
-        return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
-    KMMCHK(check_k(k));
-    bool last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
-    const bool new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
-    const int fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
-    if (fmt != KMM_FORMAT_FASTQ && fmt != KMM_FORMAT_FASTA2 && fmt != KMM_FORMAT_SAM)
-        return fail(KMM_ERR_INVALID_ARG, "kmm_map_gzip: format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2) or KMM_FORMAT_SAM (8)");
-    if (n_comp < 0 || (n_comp > 0 && !comp))
-        return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
-    if (consumed_comp)
-        *consumed_comp = 0;
-    if (n_records)
-        *n_records = 0;
-    if (n_comp > 0 && is_device_ptr(comp))
-        return fail(KMM_ERR_INVALID_ARG, "kmm_map_gzip takes the compressed bytes from host memory");
-    HIPCHK(hipSetDevice(ix->device));
-    static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
-    const auto t_0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point a) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
-    constexpr int64_t MAX_WINDOW = (int64_t)1 << 31;   // compressed bytes one call looks at (the lanes' byte positions are 32-bit)
-    constexpr unsigned long long CALL_CAP = 7ull << 29; // 3.5 GiB of inflated bytes per call, as kmm_map_bgzf
-    bool window_cut = false;
-    if (n_comp > MAX_WINDOW) {
-        n_comp = MAX_WINDOW;
-        window_cut = true;
-    }
-    if (new_stream) {
-        ix->gz_carry_len = 0;
-        ix->gz_state = kmm_gunzip::StreamState();
-        ix->gz_ratio = 4.0;
-    }
-    KMMCHK(ensure(ix->gz_window, kmm_gunzip::WIN));
-    if (new_stream)
-        HIPCHK(hipMemsetAsync(ix->gz_window.p, 0, kmm_gunzip::WIN, ix->stream));
-    if (!ix->bgzf_crc.p) { // the CRC32 tables (slicing by 8), once per handle (shared with kmm_map_bgzf)
-        std::vector<uint32_t> t(kmm_gz::CRC_TABLE_WORDS);
-        for (int kk = 0; kk < 8; ++kk)
-            for (uint32_t bb = 0; bb < 256u; ++bb)
-                t[(size_t)kk * 256 + bb] = kmm_gz::crc_table_entry(kk, bb);
-        for (int kk = 0; kk < kmm_gz::CRC_SHIFT_WORDS; ++kk)
-            t[8 * 256 + kk] = kmm_gz::crc_shift_table_entry(kk);
-        KMMCHK(ensure(ix->bgzf_crc, t.size() * 4));
-        HIPCHK(hipMemcpy(ix->bgzf_crc.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    }
-    // the compressed bytes reach HBM through the page-locked staging ring of kmm_map_bgzf (no member chain to walk)
-    const uint32_t n_pad = (uint32_t)(n_comp < 16 ? 16 : n_comp) + 64u;
-    KMMCHK(ensure(ix->gz_comp, n_pad));
-    HIPCHK(hipStreamSynchronize(ix->stream)); // (the kernels of the call before have let go of gz_comp)
-    uint8_t *d_comp = (uint8_t *)ix->gz_comp.p;
-    HIPCHK(hipMemsetAsync(d_comp + n_comp, 0, n_pad - (uint32_t)n_comp, ix->copy_stream));
-    if (n_comp > 0) {
-        BgzfStaged st;
-        KMMCHK(bgzf_stage_and_scan(ix, comp, 0, n_comp, d_comp, 0, st, false));
-        if (!st.staged)
-            HIPCHK(hipMemcpyAsync(d_comp, comp, (size_t)n_comp, hipMemcpyHostToDevice, ix->copy_stream));
-    }
-    KMMCHK(stage_copies_done(ix));
-    HIPCHK(hipStreamSynchronize(ix->copy_stream));
-    const double ms_stage = ms_since(t_0);
-    // inflate
-    GzGpuBackend be;
-    be.ix = ix;
-    be.ratio = ix->gz_ratio;
-    be.d_in = d_comp;
-    be.n_pad = n_pad;
-    be.n = (uint64_t)n_comp;
-    const int64_t carry = ix->gz_carry_len;
-    // the output: the call inflates into gz_raw behind the carried bytes; its size is known once the chunks stand, so the
-    // buffer is made large enough for the window at the stream's ratio and grown (before any byte lands) if it must be
-    const uint64_t S = ix->dbg_gzip_chunk_kb > 0 ? (uint64_t)ix->dbg_gzip_chunk_kb << 10 : (uint64_t)32 << 10;
-    kmm_gunzip::StreamState state = ix->gz_state;
-    kmm_gunzip::CallOut co;
-    kmm_gunzip::CallStats cs;
-    struct RawBackend : GzGpuBackend {
-        int64_t carry = 0;
-        bool resolve(const kmm_gunzip::PieceRef *p, size_t k, uint64_t *bad)
-        {
-            uint64_t need = 0;
-            for (size_t i = 0; i < k; ++i)
-                need = p[i].off + p[i].n > need ? p[i].off + p[i].n : need;
-            DevBuf &raw = ix->gz_raw;
-            if (raw.cap < (size_t)carry + need + 4096) { // (the carried bytes move along)
-                DevBuf nb;
-                if ((rc = ensure(nb, (size_t)carry + need + need / 8 + 4096)) != KMM_OK)
-                    return false;
-                if (carry > 0 && !hip(hipMemcpyAsync(nb.p, ix->gz_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream), "carry"))
-                    return false;
-                if (!sync())
-                    return false;
-                release(raw);
-                raw = nb;
-            } else if (carry > 0 && !hip(hipMemcpyAsync(raw.p, ix->gz_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream), "carry")) {
-                return false;
-            }
-            d_out = (uint8_t *)raw.p + carry;
-            return GzGpuBackend::resolve(p, k, bad);
+    StreamCall c{"kmm_map_gzip", k, max_freq, also_revcomp, lut, consumed_comp, n_records};
+    return guarded(c.who, [&] {
+        KMMCHK(stream_call_start(ix, c, comp, n_comp, format, true, false));
+        static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
+        const auto t_0 = std::chrono::steady_clock::now();
+        constexpr int64_t MAX_WINDOW = (int64_t)1 << 31;   // compressed bytes one call looks at (the lanes' byte positions are 32-bit)
+        constexpr unsigned long long CALL_CAP = 7ull << 29; // 3.5 GiB of inflated bytes per call, as kmm_map_bgzf
+        bool window_cut = false;
+        if (n_comp > MAX_WINDOW) {
+            n_comp = MAX_WINDOW;
+            window_cut = true;
         }
-    } rb;
-    static_cast<GzGpuBackend &>(rb) = be;
-    rb.carry = carry;
-    if (carry == 0 && ix->gz_raw.p == nullptr)
-        KMMCHK(ensure(ix->gz_raw, 4096));
-    const int rr = kmm_gunzip::run_call(rb, comp, (uint64_t)n_comp, last_chunk && !window_cut, S, CALL_CAP - (unsigned long long)carry, state, co, cs);
-    if (rr != 0)
-        return rb.rc != KMM_OK ? rb.rc : fail(KMM_ERR_INTERNAL, "kmm_map_gzip: backend failure");
-    ix->gzip_calls++;
-    ix->gzip_chunks += (int64_t)cs.chunks;
-    ix->gzip_false_starts += (int64_t)cs.false_starts;
-    ix->gzip_continuations += (int64_t)cs.continuations;
-    auto release_arena = [&] { // the stream has ended (or cannot go on): its symbol slots go back to the device
-        for (DevBuf &b : ix->gz_arena)
-            release(b);
-        ix->gz_arena.clear();
-    };
-    if (co.err) {
-        static const char *why[] = {"", "header", "reserved block type", "stored block", "code lengths", "Huffman code", "invalid symbol",
-                                    "distance too far back", "more data than a block can hold", "compressed data ended early",
-                                    "ISIZE mismatch", "CRC32 mismatch"};
-        ix->gz_carry_len = 0;
-        release_arena();
-        return fail(KMM_ERR_MALFORMED, "kmm_map_gzip: corrupt gzip stream near compressed byte %llu of the chunk: %s",
-                    (unsigned long long)co.err_at, co.err < 12 ? why[co.err] : "?");
-    }
-    if (co.hit_cap || window_cut)
-        last_chunk = false; // (the call stops at its own size limit: the caller continues with the same flags)
-    ix->gzip_members += (int64_t)cs.members;
-    ix->gzip_inflated += (int64_t)co.n_out;
-    ix->gz_state = state;
-    if (co.consumed > 0 && co.n_out > 0) {
-        const double r = (double)co.n_out / (double)co.consumed;
-        ix->gz_ratio = r < 1.0 ? 1.0 : r > 1032.0 ? 1032.0 : r;
-    }
-    if (consumed_comp)
-        *consumed_comp = (int64_t)co.consumed;
-    const double ms_inflate = ms_since(t_0) - ms_stage;
-    uint8_t *d_raw = (uint8_t *)ix->gz_raw.p;
-    int64_t n_raw = carry + (int64_t)co.n_out;
-    if (n_raw == 0) {
-        if (last_chunk)
+        if (c.new_stream) {
+            ix->gz_carry_len = 0;
+            ix->gz_state = kmm_gunzip::StreamState();
+            ix->gz_ratio = 4.0;
+        }
+        KMMCHK(ensure(ix->gz_window, kmm_gunzip::WIN));
+        if (c.new_stream)
+            HIPCHK(hipMemsetAsync(ix->gz_window.p, 0, kmm_gunzip::WIN, ix->stream));
+        KMMCHK(ensure_crc_tables(ix));
+        // the compressed bytes reach HBM through the page-locked staging ring of kmm_map_bgzf (no member chain to walk)
+        const uint32_t n_pad = (uint32_t)(n_comp < 16 ? 16 : n_comp) + 64u;
+        KMMCHK(ensure(ix->gz_comp, n_pad));
+        HIPCHK(hipStreamSynchronize(ix->stream)); // (the kernels of the call before have let go of gz_comp)
+        uint8_t *d_comp = (uint8_t *)ix->gz_comp.p;
+        HIPCHK(hipMemsetAsync(d_comp + n_comp, 0, n_pad - (uint32_t)n_comp, ix->copy_stream));
+        if (n_comp > 0) {
+            BgzfStaged st;
+            KMMCHK(bgzf_stage_and_scan(ix, comp, 0, n_comp, d_comp, 0, st, false));
+            if (!st.staged)
+                HIPCHK(hipMemcpyAsync(d_comp, comp, (size_t)n_comp, hipMemcpyHostToDevice, ix->copy_stream));
+        }
+        KMMCHK(stage_copies_done(ix));
+        HIPCHK(hipStreamSynchronize(ix->copy_stream));
+        const double ms_stage = ms_since(t_0);
+        // inflate
+        const int64_t carry = ix->gz_carry_len;
+        // the output: the call inflates into gz_raw behind the carried bytes; its size is known once the chunks stand, so the
+        // buffer is made large enough for the window at the stream's ratio and grown (before any byte lands) if it must be
+        const uint64_t S = ix->dbg_gzip_chunk_kb > 0 ? (uint64_t)ix->dbg_gzip_chunk_kb << 10 : (uint64_t)32 << 10;
+        kmm_gunzip::StreamState state = ix->gz_state;
+        kmm_gunzip::CallOut co;
+        kmm_gunzip::CallStats cs;
+        GzGpuBackend be{ix, ix->gz_ratio, d_comp, n_pad, (uint64_t)n_comp, carry};
+        if (carry == 0 && ix->gz_raw.p == nullptr)
+            KMMCHK(ensure(ix->gz_raw, 4096));
+        const int rr = kmm_gunzip::run_call(be, comp, (uint64_t)n_comp, c.last_chunk && !window_cut, S, CALL_CAP - (unsigned long long)carry, state, co, cs);
+        if (rr != 0)
+            return be.rc != KMM_OK ? be.rc : fail(KMM_ERR_INTERNAL, "kmm_map_gzip: backend failure");
+        ix->gzip_calls++;
+        ix->gzip_chunks += (int64_t)cs.chunks;
+        ix->gzip_false_starts += (int64_t)cs.false_starts;
+        ix->gzip_continuations += (int64_t)cs.continuations;
+        auto release_arena = [&] { // the stream has ended (or cannot go on): its symbol slots go back to the device
+            for (DevBuf &b : ix->gz_arena)
+                release(b);
+            ix->gz_arena.clear();
+        };
+        if (co.err) {
+            static const char *why[] = {"", "header", "reserved block type", "stored block", "code lengths", "Huffman code", "invalid symbol",
+                                        "distance too far back", "more data than a block can hold", "compressed data ended early",
+                                        "ISIZE mismatch", "CRC32 mismatch"};
+            ix->gz_carry_len = 0;
+            release_arena();
+            return fail(KMM_ERR_MALFORMED, "kmm_map_gzip: corrupt gzip stream near compressed byte %llu of the chunk: %s",
+                        (unsigned long long)co.err_at, co.err < 12 ? why[co.err] : "?");
+        }
+        if (co.hit_cap || window_cut)
+            c.last_chunk = false; // (the call stops at its own size limit: the caller continues with the same flags)
+        ix->gzip_members += (int64_t)cs.members;
+        ix->gzip_inflated += (int64_t)co.n_out;
+        ix->gz_state = state;
+        if (co.consumed > 0 && co.n_out > 0) {
+            const double r = (double)co.n_out / (double)co.consumed;
+            ix->gz_ratio = r < 1.0 ? 1.0 : r > 1032.0 ? 1032.0 : r;
+        }
+        if (c.consumed_comp)
+            *c.consumed_comp = (int64_t)co.consumed;
+        const double ms_inflate = ms_since(t_0) - ms_stage;
+        uint8_t *d_raw = (uint8_t *)ix->gz_raw.p;
+        int64_t n_raw = carry + (int64_t)co.n_out;
+        if (n_raw > 0) {
+            uint8_t last_byte = 10;
+            if (c.last_chunk) {
+                HIPCHK(hipMemcpyAsync(&last_byte, d_raw + n_raw - 1, 1, hipMemcpyDeviceToHost, ix->stream));
+                HIPCHK(hipStreamSynchronize(ix->stream));
+            }
+            int64_t used = 0;
+            KMMCHK(map_text_inflated(ix, c, d_raw, 0, n_raw, ix->gz_raw.cap, last_byte, &used));
+            if (verbose)
+                fprintf(stderr, "libkmm: kmm_map_gzip: %lld -> %llu bytes, %llu chunks (%llu false starts, %llu continuations), %d launches: "
+                        "staging %.2f ms, inflate %.2f ms (find %.2f, decode %.2f, windows %.2f, resolve %.2f, crc %.2f), records %.2f ms\n",
+                        (long long)co.consumed, (unsigned long long)co.n_out, (unsigned long long)cs.chunks, (unsigned long long)cs.false_starts,
+                        (unsigned long long)cs.continuations, be.launches, ms_stage, ms_inflate, be.ms_find, be.ms_decode, be.ms_windows,
+                        be.ms_resolve, be.ms_crc, ms_since(t_0) - ms_stage - ms_inflate);
+            KMMCHK(keep_carry(ix, c, d_raw, used, n_raw, ix->gz_carry, ix->gz_carry_len));
+            HIPCHK(hipStreamSynchronize(ix->stream));
+        }
+        if (c.last_chunk)
             release_arena();
         return KMM_OK;
-    }
-    uint8_t last_byte = 10;
-    if (last_chunk) {
-        HIPCHK(hipMemcpyAsync(&last_byte, d_raw + n_raw - 1, 1, hipMemcpyDeviceToHost, ix->stream));
-        HIPCHK(hipStreamSynchronize(ix->stream));
-        if (last_byte != 10) { // a last line without its newline gets one (as the file readers do)
-            if (ix->gz_raw.cap < (size_t)n_raw + 1)
-                return fail(KMM_ERR_INTERNAL, "kmm_map_gzip: no room for the final newline");
-            HIPCHK(hipMemsetAsync(d_raw + n_raw, 10, 1, ix->stream));
-            ++n_raw;
-        }
-    }
-    int64_t used = 0, recs = 0;
-    KMMCHK(kmm_map_records(ix, d_raw, n_raw, fmt, k, max_freq, also_revcomp, lut, &used, &recs));
-    if (n_records)
-        *n_records = recs;
-    if (verbose)
-        fprintf(stderr, "libkmm: kmm_map_gzip: %lld -> %llu bytes, %llu chunks (%llu false starts, %llu continuations), %d launches: staging %.2f ms, "
-                "inflate %.2f ms (find %.2f, decode %.2f, windows %.2f, resolve %.2f, crc %.2f), records %.2f ms\n",
-                (long long)co.consumed, (unsigned long long)co.n_out, (unsigned long long)cs.chunks, (unsigned long long)cs.false_starts,
-                (unsigned long long)cs.continuations, rb.launches, ms_stage, ms_inflate, rb.ms_find, rb.ms_decode, rb.ms_windows, rb.ms_resolve,
-                rb.ms_crc, ms_since(t_0) - ms_stage - ms_inflate);
-    const int64_t tail = n_raw - used;
-    if (last_chunk && tail > 0) {
-        ix->gz_carry_len = 0;
-        return fail(KMM_ERR_MALFORMED, "kmm_map_gzip: the stream ends with %lld bytes that form no complete record", (long long)tail);
-    }
-    if (tail > 0) {
-        KMMCHK(ensure(ix->gz_carry, (size_t)tail + 64)); // (may free and reallocate: a device-wide sync, rare)
-        HIPCHK(hipMemcpyAsync(ix->gz_carry.p, d_raw + used, (size_t)tail, hipMemcpyDeviceToDevice, ix->stream));
-    }
-    ix->gz_carry_len = tail;
-    HIPCHK(hipStreamSynchronize(ix->stream));
-    if (last_chunk)
-        release_arena();
-    return KMM_OK;
+    });
 }
 
 int kmm_in_index(kmm_index_t *ix, const uint64_t *kmers, int64_t n, uint8_t *out)

@@ -17,6 +17,14 @@ def _is_torch_tensor(x):
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
 
+def _n_bytes(b, n_bytes):
+    """The bytes of `b` a call takes: all of them, or the first n_bytes."""
+    n = b.n if n_bytes is None else int(n_bytes)
+    if n > b.n:
+        raise ValueError("n_bytes exceeds the buffer")
+    return n
+
+
 class _Arg:
     """A borrowed pointer for one C call: numpy array (host) or torch tensor (host or device)."""
 
@@ -197,15 +205,32 @@ class DeviceIndex:
         Returns (consumed_bytes, n_records); the caller carries raw[consumed:] to the next chunk."""
         b = _Arg(raw, np.uint8, "raw")
         t = _Arg(lut, np.uint8, "lut")
-        n = b.n if n_bytes is None else int(n_bytes)
-        if n > b.n:
-            raise ValueError("n_bytes exceeds the buffer")
+        n = _n_bytes(b, n_bytes)
         consumed = ctypes.c_int64(0)
         n_rec = ctypes.c_int64(0)
         _lib.check(_lib.lib().kmm_map_records(self._h, b.ptr, n, int(fmt), int(k),
                                               int(max_index_lookup_frequency), int(bool(also_revcomp)),
                                               t.ptr, ctypes.byref(consumed), ctypes.byref(n_rec)))
         return consumed.value, n_rec.value
+
+    def _hint_next(self, next_chunk):
+        if next_chunk is not None and len(next_chunk):
+            # the bytes that follow `comp` in the caller's memory (a view of the same file mapping): staged under this chunk's
+            # inflate kernel (kmm_map_bgzf_hint_next); the next call passes comp[used:] + next_chunk as one view
+            nx = _Arg(next_chunk, np.uint8, "next_chunk")
+            _lib.check(_lib.lib().kmm_map_bgzf_hint_next(self._h, nx.ptr, nx.n))
+
+    def _map_stream(self, entry, comp, n_bytes, fmt, first, last, k, max_index_lookup_frequency, also_revcomp, lut):
+        """One call of a compressed stream's entry point (kmm_map_bgzf / kmm_map_gzip / kmm_map_bam): (used, n_records)."""
+        b = _Arg(comp, np.uint8, "comp")
+        t = _Arg(lut, np.uint8, "lut")
+        n = _n_bytes(b, n_bytes)
+        used = ctypes.c_int64(0)
+        n_rec = ctypes.c_int64(0)
+        flags = (_lib.FORMAT_NEW_STREAM if first else 0) | (_lib.FORMAT_LAST_CHUNK if last else 0)
+        _lib.check(getattr(_lib.lib(), entry)(self._h, b.ptr, n, int(fmt) | flags, int(k), int(max_index_lookup_frequency),
+                                              int(bool(also_revcomp)), t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
+        return used.value, n_rec.value
 
     def map_bgzf(self, comp, n_bytes=None, fmt=_lib.FORMAT_FASTQ, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
                  lut=None, first=False, last=False, head_skip=0, tail_stop=None, next_chunk=None):
@@ -216,43 +241,19 @@ class DeviceIndex:
         first / last chunk.  A rank's share of a file (bgzf_ranges.rank_member_range): head_skip = inflated bytes of the
         FIRST chunk's first member that belong to the rank before; tail_stop = how many inflated bytes of the LAST chunk's
         last member are this rank's (None: all).  next_chunk: see below."""
-        if next_chunk is not None and len(next_chunk):
-            # the bytes that follow `comp` in the caller's memory (a view of the same file mapping): staged under this chunk's
-            # inflate kernel (kmm_map_bgzf_hint_next); the next call passes comp[used:] + next_chunk as one view
-            nx = _Arg(next_chunk, np.uint8, "next_chunk")
-            _lib.check(_lib.lib().kmm_map_bgzf_hint_next(self._h, nx.ptr, nx.n))
+        self._hint_next(next_chunk)
         if head_skip:
             self.set_param("bgzf_head_skip", int(head_skip))
         if tail_stop is not None:
             self.set_param("bgzf_tail_stop", int(tail_stop))
-        b = _Arg(comp, np.uint8, "comp")
-        t = _Arg(lut, np.uint8, "lut")
-        n = b.n if n_bytes is None else int(n_bytes)
-        if n > b.n:
-            raise ValueError("n_bytes exceeds the buffer")
-        used = ctypes.c_int64(0)
-        n_rec = ctypes.c_int64(0)
-        flags = (_lib.FORMAT_NEW_STREAM if first else 0) | (_lib.FORMAT_LAST_CHUNK if last else 0)
-        _lib.check(_lib.lib().kmm_map_bgzf(self._h, b.ptr, n, int(fmt) | flags, int(k), int(max_index_lookup_frequency),
-                                           int(bool(also_revcomp)), t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
-        return used.value, n_rec.value
+        return self._map_stream("kmm_map_bgzf", comp, n_bytes, fmt, first, last, k, max_index_lookup_frequency, also_revcomp, lut)
 
     def map_gzip(self, comp, n_bytes=None, fmt=_lib.FORMAT_FASTQ, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
                  lut=None, first=False, last=False):
         """Map a window of a PLAIN gzip-compressed FASTQ (fmt=4) / two-line FASTA (fmt=2) / SAM (fmt=8) file, inflated on the GPU
         (kmm_map_gzip).  `comp` is any prefix of the rest of the file; returns (compressed bytes used, records mapped):
         continue at comp[used:].  first / last mark the file's first / last window (per call: nothing is kept for later)."""
-        b = _Arg(comp, np.uint8, "comp")
-        t = _Arg(lut, np.uint8, "lut")
-        n = b.n if n_bytes is None else int(n_bytes)
-        if n > b.n:
-            raise ValueError("n_bytes exceeds the buffer")
-        used = ctypes.c_int64(0)
-        n_rec = ctypes.c_int64(0)
-        flags = (_lib.FORMAT_NEW_STREAM if first else 0) | (_lib.FORMAT_LAST_CHUNK if last else 0)
-        _lib.check(_lib.lib().kmm_map_gzip(self._h, b.ptr, n, int(fmt) | flags, int(k), int(max_index_lookup_frequency),
-                                           int(bool(also_revcomp)), t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
-        return used.value, n_rec.value
+        return self._map_stream("kmm_map_gzip", comp, n_bytes, fmt, first, last, k, max_index_lookup_frequency, also_revcomp, lut)
 
     def map_bam(self, comp, first, last, next_chunk=None, n_bytes=None, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
                 lut=None):
@@ -261,20 +262,8 @@ class DeviceIndex:
         last mark the file's first / last window (the header is read on the first; a first window that ends inside the header
         uses nothing: bring a longer one).  next_chunk: the bytes that follow `comp` in the caller's memory, staged under this
         window's inflate kernel (as map_bgzf)."""
-        if next_chunk is not None and len(next_chunk):
-            nx = _Arg(next_chunk, np.uint8, "next_chunk")
-            _lib.check(_lib.lib().kmm_map_bgzf_hint_next(self._h, nx.ptr, nx.n))
-        b = _Arg(comp, np.uint8, "comp")
-        t = _Arg(lut, np.uint8, "lut")
-        n = b.n if n_bytes is None else int(n_bytes)
-        if n > b.n:
-            raise ValueError("n_bytes exceeds the buffer")
-        used = ctypes.c_int64(0)
-        n_rec = ctypes.c_int64(0)
-        flags = (_lib.FORMAT_NEW_STREAM if first else 0) | (_lib.FORMAT_LAST_CHUNK if last else 0)
-        _lib.check(_lib.lib().kmm_map_bam(self._h, b.ptr, n, flags, int(k), int(max_index_lookup_frequency), int(bool(also_revcomp)),
-                                          t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
-        return used.value, n_rec.value
+        self._hint_next(next_chunk)
+        return self._map_stream("kmm_map_bam", comp, n_bytes, 0, first, last, k, max_index_lookup_frequency, also_revcomp, lut)
 
     def map_packed(self, codes, n_bases, n_reads, read_len=0, read_starts=None, k=31, max_index_lookup_frequency=1000,
                    also_revcomp=False):

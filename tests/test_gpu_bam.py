@@ -50,7 +50,7 @@ def _expect(oracle, index, mx, comp, k=31, excl=0, also_revcomp=False):
 
 
 def _feed(dev, comp, step=1 << 40, hinted=False, k=31, also_revcomp=False):
-    """The CLI's loop (command_line_interface._map_bam_file): windows that END at fixed places (anywhere in a member), each
+    """The CLI's loop (command_line_interface._map_compressed_file): windows that END at fixed places (anywhere in a member), each
     call told which bytes follow when hinted; a first window inside the header is made longer."""
     buf = np.frombuffer(comp, dtype=np.uint8)
     size, pos, total = len(comp), 0, 0

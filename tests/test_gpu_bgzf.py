@@ -69,7 +69,7 @@ def _feed(dev, comp, fmt, k, step):
 
 
 def _feed_hinted(dev, comp, fmt, k, step):
-    """The CLI's loop (command_line_interface._map_bgzf_file): windows that END at fixed places, each call told which bytes
+    """The CLI's loop (command_line_interface._map_compressed_file): windows that END at fixed places, each call told which bytes
     follow (kmm_map_bgzf_hint_next: staged under the call's own inflate kernel)."""
     buf = np.frombuffer(comp, dtype=np.uint8)
     size, pos, total = len(comp), 0, 0
