@@ -21,6 +21,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "kmm.h"
@@ -89,20 +90,44 @@ static double ms_since(std::chrono::steady_clock::time_point a)
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// Move-only owners of what the host side allocates.  HipOwned holds one HIP handle (a device array, an event, a stream) and
+// gives it back when it is reset, replaced or destroyed; put() hands the creating call (hipMalloc, hipEventCreate*,
+// hipStreamCreate*) the slot to fill.  hipFree waits for the whole device: a reset() in the middle of a call is a
+// synchronisation point.
+template <typename H, hipError_t (*Free)(H)>
+struct HipOwned {
+    H h = nullptr;
+    HipOwned() = default;
+    HipOwned(HipOwned &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    HipOwned &operator=(HipOwned &&o) noexcept { if (this != &o) { (void)reset(); h = std::exchange(o.h, nullptr); } return *this; }
+    ~HipOwned() { (void)reset(); }
+    hipError_t reset() { H x = std::exchange(h, nullptr); return x ? Free(x) : hipSuccess; }
+    H *put() { (void)reset(); return &h; }
+    operator H() const { return h; }
+};
+template <typename T>
+hipError_t free_device(T *p) { return hipFree(p); }
+template <typename T>
+using DevPtr = HipOwned<T *, free_device<T>>;
+using Event = HipOwned<hipEvent_t, hipEventDestroy>;
+using Stream = HipOwned<hipStream_t, hipStreamDestroy>;
+
+// A device buffer that only grows (ensure).
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { (void)reset(); p = std::exchange(o.p, nullptr); cap = std::exchange(o.cap, 0); } return *this; }
+    ~DevBuf() { (void)reset(); }
+    hipError_t reset() { cap = 0; void *q = std::exchange(p, nullptr); return q ? hipFree(q) : hipSuccess; }
 };
 
 int ensure(DevBuf &b, size_t bytes)
 {
     if (bytes <= b.cap && b.p)
         return KMM_OK;
-    if (b.p) {
-        HIPCHK(hipFree(b.p)); // blocks until the device is idle: safe w.r.t. in-flight kernels
-        b.p = nullptr;
-        b.cap = 0;
-    }
+    HIPCHK(b.reset()); // blocks until the device is idle: safe w.r.t. in-flight kernels
     size_t want = bytes < 256 ? 256 : bytes;
     hipError_t e = hipMalloc(&b.p, want);
     if (e != hipSuccess) {
@@ -112,14 +137,6 @@ int ensure(DevBuf &b, size_t bytes)
     }
     b.cap = want;
     return KMM_OK;
-}
-
-void release(DevBuf &b)
-{
-    if (b.p)
-        (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
 }
 
 bool is_device_ptr(const void *p)
@@ -153,7 +170,7 @@ void default_lut(uint8_t lut[256])
 
 struct Stage {
     DevBuf bases, offsets, tile_first, start_bits, kmers, lut, aux;
-    hipEvent_t done = nullptr; // the last kernel that read this stage has finished
+    Event done; // the last kernel that read this stage has finished
     bool used = false;
 };
 
@@ -206,6 +223,17 @@ struct PinnedShelf {
     }
 };
 static PinnedShelf g_shelf;
+
+// A page-locked buffer of the handle, given back to the shelf when it is reset or destroyed.
+struct PinnedBuf {
+    uint8_t *p = nullptr;
+    size_t bytes = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { reset(); }
+    void reset() { g_shelf.give(std::exchange(p, nullptr), std::exchange(bytes, 0)); }
+};
 constexpr size_t RING_SLOT = (size_t)16 << 20;
 #ifndef KMM_RING_SLOTS
 #define KMM_RING_SLOTS 8 // (A/B builds: a ring the size of a batch never makes the packing threads wait)
@@ -214,8 +242,8 @@ constexpr int RING_SLOTS = KMM_RING_SLOTS;
 
 
 struct TimedEvent {
-    hipEvent_t start, stop;
-    int kernel_id;
+    Event start, stop;
+    int kernel_id = 0;
 };
 
 // What kmm_map_bgzf knows about a chunk of compressed bytes once they are on their way to HBM: the member chain.
@@ -229,14 +257,36 @@ struct BgzfStaged {
     double ms_scan_inside = 0;
 };
 
-struct kmm_index {
+// The handle's streams: a base of kmm_index, so that they are destroyed after everything else in it.
+struct IndexStreams {
+    Stream stream;      // kernels
+    Stream copy_stream; // host -> HBM staging, overlaps the previous kernel
+};
+
+// The radix path's view of the index (rx_build), a base of kmm_index: the view (or its 16-bit directory alone) is dropped
+// with one assignment, and the arrays keep their rx_* names in the handle.
+struct RxDir16 {
+    DevPtr<uint16_t> rx_pstart16;   // slice-relative 16-bit directory + first entry of every slice (for the current
+    DevPtr<uint32_t> rx_slice_e0;   // part_shift; null when a slice holds more than 65535 entries or HBM is short)
+    DevPtr<uint16_t> rx_slice_fmax; // largest frequency of every slice (with the two above)
+};
+struct RxArrays : RxDir16 {
+    uint64_t rx_S = 0;        // entries in bucket order
+    DevPtr<uint32_t> rx_pstart;
+    DevPtr<uint64_t> rx_pkeys;     // packed form for the current (w, f2)
+    DevPtr<uint64_t> rx_pkeys_raw; // the k-mers themselves (re-packed when part_shift changes)
+    DevPtr<uint16_t> rx_pfreq;
+    DevPtr<uint32_t> rx_pnodes, rx_porig, rx_ecnt, rx_ecnt_acc;
+    DevPtr<uint32_t> rx_norder, rx_nnode; // entries in node order (k_rx_flush_sorted); absent if memory is short
+    DevPtr<uint32_t> rx_occ;   // bit h = bucket h holds an entry: pass 2's empty-bucket filter (k_rx_p2f); optional
+};
+
+struct kmm_index : IndexStreams, RxArrays {
     int device = 0;
-    hipStream_t stream = nullptr;      // kernels
-    hipStream_t copy_stream = nullptr; // host -> HBM staging, overlaps the previous kernel
-    hipEvent_t copied = nullptr;
-    uint4 *buckets = nullptr;
-    uint4 *entries = nullptr;
-    uint32_t *occ = nullptr;           // occupancy bitmap, only for indexes small enough (see occ_max_bytes)
+    Event copied;
+    DevPtr<uint4> buckets;
+    DevPtr<uint4> entries;
+    DevPtr<uint32_t> occ;              // occupancy bitmap, only for indexes small enough (see occ_max_bytes)
     bool use_occ = true;
     int occ_shift = 0;                 // log2(bitmap bits per bucket)
     uint32_t bloom_words = 0;          // != 0: occ is a word-blocked Bloom filter
@@ -247,13 +297,13 @@ struct kmm_index {
     int rx_why_not = 0;                // why the radix path is unavailable: 0 it is available, 1 modulo >= 2^31, 2 more
                                        // than 512 x 512 slices / slices too dense for LDS, 3 out of memory, 4 the
                                        // buckets of the index overlap (sum of bucket sizes > n_entries)
-    uint32_t *counts = nullptr;
-    uint32_t *own_counts_buf = nullptr;
-    uint8_t *lut_default = nullptr;
-    uint8_t *lut_codes = nullptr;        // codes 0..3 map to themselves: flat reads compacted from raw records (k_rec_scatter)
-    unsigned long long *first_bad = nullptr;
-    unsigned long long *stats = nullptr;
-    unsigned long long *queue = nullptr; // tile counter of the dynamic schedule
+    uint32_t *counts = nullptr;          // own_counts_buf or the caller's buffer (kmm_bind_counts)
+    DevPtr<uint32_t> own_counts_buf;
+    DevPtr<uint8_t> lut_default;
+    DevPtr<uint8_t> lut_codes;           // codes 0..3 map to themselves: flat reads compacted from raw records (k_rec_scatter)
+    DevPtr<unsigned long long> first_bad;
+    DevPtr<unsigned long long> stats;
+    DevPtr<unsigned long long> queue;    // tile counter of the dynamic schedule
     bool dynamic_schedule = true;
     int dyn_chunk = 16;                  // tiles per grab
     uint64_t modulo = 0, magic = 0;
@@ -282,19 +332,17 @@ struct kmm_index {
     int host_pack_threads = 0;     // "host_pack_threads": reads / raw records in host memory are packed to 2 bits per base by that
                                    // many host threads before they cross PCIe (default: min(16, the process's CPU budget))
     std::unique_ptr<kmm_hostpack::Workers> pack_pool; // the packing threads, asleep between calls
-    uint8_t *pack_pinned = nullptr; // page-locked home of a packed records batch (kmm_hostpack.hpp)
-    size_t pack_pinned_bytes = 0;
-    uint8_t *ring[RING_SLOTS] = {}; // the page-locked staging ring (ensure_ring)
-    uint8_t *pack_bits_pinned = nullptr; // ... and of the read-start bitset of packed raw records
-    size_t pack_bits_pinned_bytes = 0;
+    PinnedBuf pack_pinned;          // page-locked home of a packed records batch (kmm_hostpack.hpp)
+    PinnedBuf ring[RING_SLOTS];     // the page-locked staging ring (ensure_ring)
+    PinnedBuf pack_bits_pinned;     // ... and of the read-start bitset of packed raw records
     int64_t host_packed_calls = 0, host_packed_record_calls = 0;
     int64_t host_pack_slice_kb = 0; // "host_pack_slice_kb": raw bytes per slice of the records packer (0: its default)
     // kmm_map_bgzf: BGZF members inflated on the GPU (kmm_gpu_inflate.hpp).  Two sets of buffers in turn (the copy of call
     // i + 1 runs under the kernels of call i); the uncompressed bytes behind a call's last complete record wait in `carry`
     // for the next call.
     DevBuf bgzf_comp[2], bgzf_raw[2], bgzf_meta[2], bgzf_tabs, bgzf_err, bgzf_carry, bgzf_crc, bgzf_status;
-    hipEvent_t bgzf_done[2] = {nullptr, nullptr};
-    hipEvent_t bgzf_slot_ev[RING_SLOTS] = {}; // copies out of / into the slots of the staging ring
+    Event bgzf_done[2];
+    Event bgzf_slot_ev[RING_SLOTS]; // copies out of / into the slots of the staging ring
     bool bgzf_used[2] = {false, false};
     int bgzf_cur = 0;
     int64_t bgzf_carry_len = 0;
@@ -336,18 +384,7 @@ struct kmm_index {
     int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
     int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
-    uint64_t rx_S = 0;        // entries in bucket order
-    uint32_t *rx_pstart = nullptr;
-    uint64_t *rx_pkeys = nullptr;     // packed form for the current (w, f2)
-    uint64_t *rx_pkeys_raw = nullptr; // the k-mers themselves (re-packed when part_shift changes)
-    uint16_t *rx_pstart16 = nullptr;  // slice-relative 16-bit directory + first entry of every slice (for the current
-    uint32_t *rx_slice_e0 = nullptr;  // part_shift; null when a slice holds more than 65535 entries or HBM is short)
-    uint16_t *rx_slice_fmax = nullptr; // largest frequency of every slice (with the two above)
-    uint16_t *rx_pfreq = nullptr;
-    uint32_t *rx_pnodes = nullptr, *rx_porig = nullptr, *rx_ecnt = nullptr, *rx_ecnt_acc = nullptr;
-    uint32_t *rx_norder = nullptr, *rx_nnode = nullptr; // entries in node order (k_rx_flush_sorted); absent if memory is short
     int rx_occ_shift = 0;         // k_rx_p2f folds 2^rx_occ_shift buckets into one bit of its LDS bitmap
-    uint32_t *rx_occ = nullptr;   // bit h = bucket h holds an entry: pass 2's empty-bucket filter (k_rx_p2f); optional
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
     bool rx_packed = true;        // "radix_packed_tiles": pass 1 on reads of one length takes tiles of whole reads
     bool ecnt_dirty = false;  // rx_ecnt holds hits that are not in `counts` yet
@@ -363,8 +400,8 @@ struct kmm_index {
     // flush of node range s under the reduce of node range s - 1 (kmm_comm_reduce_counts): "comm_overlap_slices"
     int comm_slices = 8;
     int64_t comm_sliced_reduces = 0; // kmm_comm_reduce_counts calls that issued one reduce per node range ("comm_sliced_reduces")
-    hipStream_t comm_stream = nullptr;
-    std::vector<hipEvent_t> comm_events;
+    Stream comm_stream;
+    std::vector<Event> comm_events;
     std::vector<uint64_t> flush_cuts; // entry (node order) where node range s begins, for comm_slices ranges; [slices + 1]
     // timing
     bool timing = false;
@@ -402,11 +439,11 @@ struct ScopedTimer {
         if (!ix->timing)
             return KMM_OK;
         if (!ix->ev_free.empty()) {
-            ev = ix->ev_free.back();
+            ev = std::move(ix->ev_free.back());
             ix->ev_free.pop_back();
         } else {
-            HIPCHK(hipEventCreate(&ev.start));
-            HIPCHK(hipEventCreate(&ev.stop));
+            HIPCHK(hipEventCreate(ev.start.put()));
+            HIPCHK(hipEventCreate(ev.stop.put()));
         }
         ev.kernel_id = kernel_id;
         HIPCHK(hipEventRecord(ev.start, ix->stream));
@@ -418,7 +455,7 @@ struct ScopedTimer {
         if (!active)
             return KMM_OK;
         HIPCHK(hipEventRecord(ev.stop, ix->stream));
-        ix->ev_used.push_back(ev);
+        ix->ev_used.push_back(std::move(ev));
         active = false;
         return KMM_OK;
     }
@@ -719,8 +756,8 @@ int launch_rx(kmm_index *ix, const ReadsView &rv, const uint64_t *kmers_in, int6
         if (rc != KMM_ERR_NOMEM || cap <= ((int64_t)1 << 28) || n_src_total <= 1)
             return rc;
         (void)hipGetLastError();
-        release(ix->rx_buf1);
-        release(ix->rx_buf2);
+        (void)ix->rx_buf1.reset();
+        (void)ix->rx_buf2.reset();
         // the next size that really is smaller: one sub-batch more than this attempt had
         const int64_t next_src = (n_src_total + n_sub) / (n_sub + 1);
         cap = next_src * RX_B * X;
@@ -959,11 +996,11 @@ int direct_build(kmm_index *ix, const Src &src, int64_t n_entries, size_t occ_by
 {
     const uint64_t M = ix->modulo;
     const size_t nb = sizeof(uint4) * (size_t)M * (ix->wide ? 2 : 1), ne = sizeof(uint4) * (size_t)(n_entries > 0 ? n_entries : 1);
-    hipError_t e = hipMalloc(&ix->buckets, nb);
-    if (e == hipSuccess) e = hipMalloc(&ix->entries, ne);
+    hipError_t e = hipMalloc(ix->buckets.put(), nb);
+    if (e == hipSuccess) e = hipMalloc(ix->entries.put(), ne);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        if (ix->buckets) { (void)hipFree(ix->buckets); ix->buckets = nullptr; }
+        (void)ix->buckets.reset();
         return fail(e == hipErrorOutOfMemory ? KMM_ERR_NOMEM : KMM_ERR_HIP, "direct view of the index (%zu + %zu bytes): %s",
                     nb, ne, hipGetErrorString(e));
     }
@@ -979,7 +1016,7 @@ int direct_build(kmm_index *ix, const Src &src, int64_t n_entries, size_t occ_by
     e = hipGetLastError();
     // occupancy bitmap / Bloom filter (16-byte layout only), built from the k-mers while they are here
     if (e == hipSuccess && occ_bytes) {
-        e = hipMalloc(&ix->occ, occ_bytes);
+        e = hipMalloc(ix->occ.put(), occ_bytes);
         if (e == hipSuccess) e = hipMemsetAsync(ix->occ, 0, occ_bytes, ix->stream);
         if (e == hipSuccess && n_entries > 0) {
             if (ix->bloom_words)
@@ -1008,7 +1045,6 @@ int ensure_direct(kmm_index *ix)
     IdxRx src;
     src.pstart = ix->rx_pstart; src.kmers = ix->rx_pkeys_raw; src.nodes = ix->rx_pnodes; src.freqs = ix->rx_pfreq;
     const int rc = direct_build(ix, src, (int64_t)ix->rx_S, ix->occ_bytes_plan, (uint32_t *)d_err.p);
-    release(d_err);
     if (rc == KMM_OK)
         ix->direct_deferred = false;
     return rc;
@@ -1121,98 +1157,10 @@ void kmm_index_destroy(kmm_index_t *ix)
         (void)hipStreamSynchronize(ix->stream);
     if (ix->copy_stream)
         (void)hipStreamSynchronize(ix->copy_stream);
-    for (Stage &s : ix->stage) {
-        release(s.bases);
-        release(s.offsets);
-        release(s.tile_first);
-        release(s.start_bits);
-        release(s.kmers);
-        release(s.lut);
-        release(s.aux);
-        if (s.done)
-            (void)hipEventDestroy(s.done);
-    }
-    release(ix->rx_meta);
-    release(ix->rx_buf1);
-    release(ix->rx_buf2);
-    release(ix->rx_probe);
-    for (int i = 0; i < 2; ++i) {
-        release(ix->bgzf_comp[i]);
-        release(ix->bgzf_raw[i]);
-        release(ix->bgzf_meta[i]);
-        if (ix->bgzf_done[i])
-            (void)hipEventDestroy(ix->bgzf_done[i]);
-    }
-    for (hipEvent_t &ev : ix->bgzf_slot_ev) {
-        if (ev)
-            (void)hipEventDestroy(ev);
-        ev = nullptr;
-    }
-    release(ix->bgzf_status);
-    release(ix->bgzf_tabs);
-    release(ix->bgzf_crc);
-    release(ix->bgzf_err);
-    release(ix->bgzf_carry);
-    for (DevBuf *b : {&ix->bam_tiles[0], &ix->bam_tiles[1], &ix->bam_bad, &ix->bam_base, &ix->bam_ctl, &ix->bam_out})
-        release(*b);
-    for (DevBuf *b : {&ix->sam_tiles, &ix->sam_base, &ix->sam_ctl})
-        release(*b);
-    for (DevBuf *b : {&ix->gz_comp, &ix->gz_raw, &ix->gz_carry, &ix->gz_window, &ix->gz_tabs, &ix->gz_meta, &ix->gz_res, &ix->gz_win,
-                      &ix->gz_gmaps, &ix->gz_gwin, &ix->gz_err})
-        release(*b);
-    for (DevBuf &b : ix->gz_arena)
-        release(b);
-    ix->pack_pool.reset();
-    g_shelf.give(ix->pack_pinned, ix->pack_pinned_bytes);
-    for (uint8_t *&slot : ix->ring) {
-        g_shelf.give(slot, RING_SLOT);
-        slot = nullptr;
-    }
-    g_shelf.give(ix->pack_bits_pinned, ix->pack_bits_pinned_bytes);
-    for (hipEvent_t e : ix->comm_events)
-        (void)hipEventDestroy(e);
-    if (ix->comm_stream)
-        (void)hipStreamDestroy(ix->comm_stream);
-    for (void *q : {(void *)ix->rx_pstart16, (void *)ix->rx_slice_e0, (void *)ix->rx_slice_fmax, (void *)ix->rx_pstart, (void *)ix->rx_pkeys, (void *)ix->rx_pkeys_raw, (void *)ix->rx_pfreq, (void *)ix->rx_pnodes,
-                    (void *)ix->rx_porig, (void *)ix->rx_ecnt, (void *)ix->rx_ecnt_acc, (void *)ix->rx_norder, (void *)ix->rx_nnode,
-                    (void *)ix->rx_occ})
-        if (q)
-            (void)hipFree(q);
-    for (auto &ev : ix->ev_used) {
-        (void)hipEventDestroy(ev.start);
-        (void)hipEventDestroy(ev.stop);
-    }
-    for (auto &ev : ix->ev_free) {
-        (void)hipEventDestroy(ev.start);
-        (void)hipEventDestroy(ev.stop);
-    }
-    if (ix->copied)
-        (void)hipEventDestroy(ix->copied);
-    if (ix->buckets)
-        (void)hipFree(ix->buckets);
-    if (ix->entries)
-        (void)hipFree(ix->entries);
-    if (ix->occ)
-        (void)hipFree(ix->occ);
-    if (ix->own_counts_buf)
-        (void)hipFree(ix->own_counts_buf);
-    if (ix->lut_default)
-        (void)hipFree(ix->lut_default);
-    if (ix->lut_codes)
-        (void)hipFree(ix->lut_codes);
-    if (ix->first_bad)
-        (void)hipFree(ix->first_bad);
-    if (ix->stats)
-        (void)hipFree(ix->stats);
-    if (ix->queue)
-        (void)hipFree(ix->queue);
+    ix->pack_pool.reset(); // (its threads are joined before their page-locked buffers go back to the shelf)
     if (ix->comm && g_rccl.lib)
         (void)g_rccl.CommDestroy(ix->comm);
-    if (ix->copy_stream)
-        (void)hipStreamDestroy(ix->copy_stream);
-    if (ix->stream)
-        (void)hipStreamDestroy(ix->stream);
-    delete ix;
+    delete ix; // every buffer, event and stream of the handle frees itself; the streams go last
 }
 
 // The entry k-mers in the packed form of the current (w, f2) (kmm_radix.hpp); synchronous.
@@ -1237,16 +1185,12 @@ static int rx_repack_keys(kmm_index *ix)
     ix->rx_fits_small = mx[1] <= odd;
     ix->rx_fits_mid = mx[2] <= odd;
     // 16-bit slice-relative directory: pass 3 loads 2 B per bucket instead of 4 (optional: 2 B x modulo of HBM)
-    for (void **q : {(void **)&ix->rx_pstart16, (void **)&ix->rx_slice_e0, (void **)&ix->rx_slice_fmax}) {
-        if (*q)
-            (void)hipFree(*q);
-        *q = nullptr;
-    }
+    static_cast<RxDir16 &>(*ix) = RxDir16();
     if (ix->rx_max_slice <= 65535u && !getenv("KMM_RX_NO_P16")) {
         const size_t n16 = ((size_t)ix->rx_PF << ix->rx_w) + 8;
-        if (hipMalloc(&ix->rx_pstart16, n16 * 2) == hipSuccess &&
-            hipMalloc(&ix->rx_slice_e0, ((size_t)ix->rx_PF + 2) * 4) == hipSuccess &&
-            hipMalloc(&ix->rx_slice_fmax, ((size_t)ix->rx_PF + 2) * 2) == hipSuccess) {
+        if (hipMalloc(ix->rx_pstart16.put(), n16 * 2) == hipSuccess &&
+            hipMalloc(ix->rx_slice_e0.put(), ((size_t)ix->rx_PF + 2) * 4) == hipSuccess &&
+            hipMalloc(ix->rx_slice_fmax.put(), ((size_t)ix->rx_PF + 2) * 2) == hipSuccess) {
             hipLaunchKernelGGL(k_rx_pstart16, dim3(grid_for(ix, (int64_t)((n16 + 255) / 256), 16)), dim3(256), 0, ix->stream,
                                ix->rx_pstart, ix->modulo, ix->rx_w, ix->rx_PF, ix->rx_pstart16, ix->rx_slice_e0);
             HIPCHK(hipGetLastError());
@@ -1256,11 +1200,7 @@ static int rx_repack_keys(kmm_index *ix)
             HIPCHK(hipStreamSynchronize(ix->stream));
         } else {
             (void)hipGetLastError();
-            for (void **q : {(void **)&ix->rx_pstart16, (void **)&ix->rx_slice_e0, (void **)&ix->rx_slice_fmax}) {
-                if (*q)
-                    (void)hipFree(*q);
-                *q = nullptr;
-            }
+            static_cast<RxDir16 &>(*ix) = RxDir16();
         }
     }
     return KMM_OK;
@@ -1285,7 +1225,7 @@ static int rx_build(kmm_index *ix, const int32_t *h2i, const int32_t *nk, const 
     bool overlap = false;
     do {
         if ((rc = ensure(sizes, (size_t)(M + 1) * 4))) break;
-        if ((e = hipMalloc(&ix->rx_pstart, (size_t)(M + 1) * 4))) break;
+        if ((e = hipMalloc(ix->rx_pstart.put(), (size_t)(M + 1) * 4))) break;
         hipLaunchKernelGGL(k_rx_bucket_sizes, dim3(grid_for(ix, (int64_t)((M + 256) / 256), 16)), dim3(256), 0,
                            ix->stream, h2i, nk, M, ix->n_entries, (uint32_t *)sizes.p);
         // an index whose buckets overlap (sum of the bucket sizes > n_entries: legal for the reference's loop, which only
@@ -1309,22 +1249,21 @@ static int rx_build(kmm_index *ix, const int32_t *h2i, const int32_t *nk, const 
         {   // occupancy bitmap for pass 2's empty-bucket filter, padded by one coarse partition's worth of words
             // (k_rx_p2f loads whole partitions); optional: without the memory for it the plain pass 2 runs
             const size_t occ_words = (size_t)((M + 31) / 32) + ((size_t)1 << (P2F_LOGBITS + 2 - 5)); // (up to 4 buckets per LDS bit)
-            if (hipMalloc(&ix->rx_occ, occ_words * 4) == hipSuccess) {
+            if (hipMalloc(ix->rx_occ.put(), occ_words * 4) == hipSuccess) {
                 if ((e = hipMemsetAsync(ix->rx_occ, 0, occ_words * 4, ix->stream))) break;
                 hipLaunchKernelGGL(k_rx_build_occ, dim3(grid_for(ix, (int64_t)((M / 32 + 256) / 256), 16)), dim3(256), 0, ix->stream,
                                    ix->rx_pstart, M, ix->rx_occ);
             } else {
                 (void)hipGetLastError();
-                ix->rx_occ = nullptr;
             }
         }
         const size_t S = total ? total : 1;
-        if ((e = hipMalloc(&ix->rx_pkeys, S * 8))) break;
-        if ((e = hipMalloc(&ix->rx_pkeys_raw, S * 8))) break;
-        if ((e = hipMalloc(&ix->rx_pfreq, S * 2))) break;
-        if ((e = hipMalloc(&ix->rx_pnodes, S * 4))) break;
-        if ((e = hipMalloc(&ix->rx_porig, S * 4))) break;
-        if ((e = hipMalloc(&ix->rx_ecnt, S * 4))) break;
+        if ((e = hipMalloc(ix->rx_pkeys.put(), S * 8))) break;
+        if ((e = hipMalloc(ix->rx_pkeys_raw.put(), S * 8))) break;
+        if ((e = hipMalloc(ix->rx_pfreq.put(), S * 2))) break;
+        if ((e = hipMalloc(ix->rx_pnodes.put(), S * 4))) break;
+        if ((e = hipMalloc(ix->rx_porig.put(), S * 4))) break;
+        if ((e = hipMalloc(ix->rx_ecnt.put(), S * 4))) break;
         if ((e = hipMemsetAsync(ix->rx_ecnt, 0, S * 4, ix->stream))) break;
         hipLaunchKernelGGL(k_rx_pack, dim3(grid_for(ix, (int64_t)((M + 255) / 256), 16)), dim3(256), 0, ix->stream, h2i,
                            kmers, nodes, freqs, M, ix->max_node_id, ix->rx_pstart, ix->rx_pkeys_raw, ix->rx_pfreq,
@@ -1341,7 +1280,7 @@ static int rx_build(kmm_index *ix, const int32_t *h2i, const int32_t *nk, const 
             DevBuf hist, cursor;
             if (n_nodes + 1 < 0xFFFFFFFFull && (uint64_t)total / n_nodes < 8 && ensure(hist, (size_t)(n_nodes + 1) * 4) == KMM_OK &&
                 ensure(cursor, (size_t)(n_nodes + 1) * 4) == KMM_OK &&
-                hipMalloc(&ix->rx_norder, S * 4) == hipSuccess && hipMalloc(&ix->rx_nnode, S * 4) == hipSuccess) {
+                hipMalloc(ix->rx_norder.put(), S * 4) == hipSuccess && hipMalloc(ix->rx_nnode.put(), S * 4) == hipSuccess) {
                 bool ok = hipMemsetAsync(hist.p, 0, (size_t)(n_nodes + 1) * 4, ix->stream) == hipSuccess;
                 hipLaunchKernelGGL(k_rx_node_hist, dim3(grid_for(ix, (int64_t)((S + 255) / 256), 16)), dim3(256), 0,
                                    ix->stream, ix->rx_pnodes, (uint64_t)total, (uint32_t *)hist.p);
@@ -1352,38 +1291,24 @@ static int rx_build(kmm_index *ix, const int32_t *h2i, const int32_t *nk, const 
                                    ix->rx_nnode);
                 ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(ix->stream) == hipSuccess;
                 if (!ok) {
-                    (void)hipFree(ix->rx_norder);
-                    (void)hipFree(ix->rx_nnode);
-                    ix->rx_norder = ix->rx_nnode = nullptr;
+                    (void)ix->rx_norder.reset();
+                    (void)ix->rx_nnode.reset();
                 }
             } else {
                 (void)hipGetLastError();
-                if (ix->rx_norder)
-                    (void)hipFree(ix->rx_norder);
-                if (ix->rx_nnode)
-                    (void)hipFree(ix->rx_nnode);
-                ix->rx_norder = ix->rx_nnode = nullptr;
+                (void)ix->rx_norder.reset();
+                (void)ix->rx_nnode.reset();
             }
-            release(hist);
-            release(cursor);
         }
     } while (0);
-    release(sizes);
-    for (DevBuf &b : scratch)
-        release(b);
+    (void)sizes.reset(); // (here, not at the end: the repack below allocates the optional 16-bit directory)
+    scratch.clear();
     if (rc != KMM_OK || e != hipSuccess || overlap) {
         // the radix view is optional: without the memory for it (or for an index with overlapping buckets) the
         // direct path serves every batch; any other failure is an error
         const bool nomem = rc == KMM_ERR_NOMEM || e == hipErrorOutOfMemory;
         (void)hipGetLastError();
-        for (void **q : {(void **)&ix->rx_pstart16, (void **)&ix->rx_slice_e0, (void **)&ix->rx_slice_fmax, (void **)&ix->rx_pstart, (void **)&ix->rx_pkeys, (void **)&ix->rx_pkeys_raw, (void **)&ix->rx_pfreq,
-                         (void **)&ix->rx_pnodes, (void **)&ix->rx_porig, (void **)&ix->rx_ecnt, (void **)&ix->rx_norder,
-                         (void **)&ix->rx_nnode, (void **)&ix->rx_occ}) {
-            if (*q)
-                (void)hipFree(*q);
-            *q = nullptr;
-        }
-        ix->rx_S = 0;
+        static_cast<RxArrays &>(*ix) = RxArrays();
         ix->rx_ok = false;
         if (overlap || nomem) {
             ix->rx_why_not = overlap ? 4 : 3;
@@ -1458,11 +1383,11 @@ static int index_create_impl(kmm_index *ix, const int32_t *h2i, const int32_t *n
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, ix->device));
     ix->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIPCHK(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&ix->copy_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&ix->copied, hipEventDisableTiming));
+    HIPCHK(hipStreamCreateWithFlags(ix->stream.put(), hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(ix->copy_stream.put(), hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(ix->copied.put(), hipEventDisableTiming));
     for (Stage &s : ix->stage)
-        HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(s.done.put(), hipEventDisableTiming));
 
     // layout: small indexes get 16-byte buckets + the L2 occupancy bitmap, larger ones 32-byte buckets
     size_t occ_max = KMM_OCC_MAX_BYTES;
@@ -1504,18 +1429,18 @@ static int index_create_impl(kmm_index *ix, const int32_t *h2i, const int32_t *n
     ix->wide = !with_occ;
     if (const char *env = getenv("KMM_WIDE_BUCKETS")) // experiments: force the bucket layout (0 / 1)
         ix->wide = atoi(env) != 0;
-    HIPCHK(hipMalloc(&ix->own_counts_buf, sizeof(uint32_t) * (size_t)(ix->max_node_id + 1)));
+    HIPCHK(hipMalloc(ix->own_counts_buf.put(), sizeof(uint32_t) * (size_t)(ix->max_node_id + 1)));
     ix->counts = ix->own_counts_buf;
     HIPCHK(hipMemsetAsync(ix->counts, 0, sizeof(uint32_t) * (size_t)(ix->max_node_id + 1), ix->stream));
-    HIPCHK(hipMalloc(&ix->lut_default, 256));
-    HIPCHK(hipMalloc(&ix->first_bad, 3 * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&ix->queue, 4 * sizeof(unsigned long long))); // (a tile queue head; also the result cells of small reductions)
-    HIPCHK(hipMalloc(&ix->stats, KMM_STAT_BYTES));
+    HIPCHK(hipMalloc(ix->lut_default.put(), 256));
+    HIPCHK(hipMalloc(ix->first_bad.put(), 3 * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc(ix->queue.put(), 4 * sizeof(unsigned long long))); // (a tile queue head; also the result cells of small reductions)
+    HIPCHK(hipMalloc(ix->stats.put(), KMM_STAT_BYTES));
     HIPCHK(hipMemset(ix->stats, 0, KMM_STAT_BYTES));
     uint8_t lut[256];
     default_lut(lut);
     HIPCHK(hipMemcpy(ix->lut_default, lut, 256, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&ix->lut_codes, 256));
+    HIPCHK(hipMalloc(ix->lut_codes.put(), 256));
     memset(lut, 0xFF, sizeof lut);
     lut[0] = 0; lut[1] = 1; lut[2] = 2; lut[3] = 3;
     HIPCHK(hipMemcpy(ix->lut_codes, lut, 256, hipMemcpyHostToDevice));
@@ -1589,7 +1514,6 @@ static int index_create_impl(kmm_index *ix, const int32_t *h2i, const int32_t *n
             rc = direct_build(ix, src, N, with_occ ? occ_bytes : 0, (uint32_t *)d_err.p);
         }
     }
-    release(d_h2i); release(d_nk); release(d_km); release(d_nd); release(d_fr); release(d_err);
     if (rc != KMM_OK)
         return rc;
     if (err & 1u)
@@ -1703,7 +1627,7 @@ int kmm_synchronize(kmm_index_t *ix)
 }
 
 static bool ensure_pack_pool(kmm_index_t *ix);
-static bool ensure_pinned(uint8_t *&p, size_t &have, size_t want);
+static bool ensure_pinned(PinnedBuf &b, size_t want);
 
 // The staging ring: RING_SLOTS page-locked buffers of RING_SLOT bytes, each an allocation of its own.  Host threads fill a
 // slot, a copy engine empties it (or the other way round), and a slot is touched by one side at a time.  Why a ring and not
@@ -1715,7 +1639,7 @@ static bool ensure_pinned(uint8_t *&p, size_t &have, size_t want);
 static bool ensure_ring(kmm_index_t *ix)
 {
     for (int i = 0; i < RING_SLOTS; ++i) {
-        if (ix->ring[i])
+        if (ix->ring[i].p)
             continue;
         size_t got = 0;
         uint8_t *p = g_shelf.take(RING_SLOT, &got);
@@ -1727,10 +1651,11 @@ static bool ensure_ring(kmm_index_t *ix)
             (void)hipGetLastError();
             return false;
         }
-        ix->ring[i] = p;
+        ix->ring[i].p = p;
+        ix->ring[i].bytes = RING_SLOT;
     }
     for (int i = 0; i < RING_SLOTS; ++i)
-        if (!ix->bgzf_slot_ev[i] && hipEventCreateWithFlags(&ix->bgzf_slot_ev[i], hipEventDisableTiming) != hipSuccess) {
+        if (!ix->bgzf_slot_ev[i] && hipEventCreateWithFlags(ix->bgzf_slot_ev[i].put(), hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
@@ -1752,7 +1677,7 @@ static int fetch_to_pageable(kmm_index_t *ix, uint8_t *dst, const uint8_t *src, 
     const size_t n_slots = (bytes + SLOT - 1) / SLOT;
     auto issue = [&](size_t c) -> int {
         const size_t b0 = c * SLOT, len = bytes - b0 < SLOT ? bytes - b0 : SLOT;
-        HIPCHK(hipMemcpyAsync(ix->ring[c % SLOTS], src + b0, len, hipMemcpyDeviceToHost, ix->copy_stream));
+        HIPCHK(hipMemcpyAsync(ix->ring[c % SLOTS].p, src + b0, len, hipMemcpyDeviceToHost, ix->copy_stream));
         HIPCHK(hipEventRecord(ix->bgzf_slot_ev[c % SLOTS], ix->copy_stream));
         return KMM_OK;
     };
@@ -1762,7 +1687,7 @@ static int fetch_to_pageable(kmm_index_t *ix, uint8_t *dst, const uint8_t *src, 
     for (size_t c = 0; c < n_slots; ++c) {
         HIPCHK(hipEventSynchronize(ix->bgzf_slot_ev[c % SLOTS]));
         const size_t b0 = c * SLOT, len = bytes - b0 < SLOT ? bytes - b0 : SLOT;
-        const uint8_t *from = ix->ring[c % SLOTS];
+        const uint8_t *from = ix->ring[c % SLOTS].p;
         const size_t per = ((len + (size_t)T - 1) / (size_t)T + 63) & ~(size_t)63;
         ix->pack_pool->start([=](int w) {
             const size_t a = (size_t)w * per;
@@ -1864,11 +1789,11 @@ int kmm_comm_reduce_counts(kmm_index_t *ix, int root)
         const bool by_range = ix->rx_norder && !ix->rx_ecnt_acc && ix->rx_flush_sorted;
         ix->comm_sliced_reduces++;
         if (!ix->comm_stream)
-            HIPCHK(hipStreamCreateWithFlags(&ix->comm_stream, hipStreamNonBlocking));
+            HIPCHK(hipStreamCreateWithFlags(ix->comm_stream.put(), hipStreamNonBlocking));
         while ((int)ix->comm_events.size() < S + 1) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ix->comm_events.push_back(e);
+            Event e;
+            HIPCHK(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+            ix->comm_events.push_back(std::move(e));
         }
         if (!by_range)
             KMMCHK(rx_flush(ix)); // (every hit is in `counts`; the ranges below then only travel)
@@ -1886,8 +1811,6 @@ int kmm_comm_reduce_counts(kmm_index_t *ix, int root)
             ix->flush_cuts.assign(S + 1, 0);
             HIPCHK(hipMemcpyAsync(ix->flush_cuts.data(), d_c.p, (S + 1) * 8, hipMemcpyDeviceToHost, ix->stream));
             HIPCHK(hipStreamSynchronize(ix->stream));
-            release(d_b);
-            release(d_c);
             ix->flush_cuts[0] = 0;
             ix->flush_cuts[S] = ix->rx_S;
         }
@@ -2018,7 +1941,6 @@ int kmm_get_kmer_counts(kmm_index_t *ix, uint32_t *out)
         e = hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, ix->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(ix->stream);
-    release(tmp);
     if (e != hipSuccess)
         return fail(KMM_ERR_HIP, "kmm_get_kmer_counts: %s", hipGetErrorString(e));
     return KMM_OK;
@@ -2122,22 +2044,20 @@ static bool ensure_pack_pool(kmm_index_t *ix)
 }
 
 // page-locked home of a packed batch: grown, never shrunk; false = none to be had
-static bool ensure_pinned(uint8_t *&p, size_t &have, size_t want)
+static bool ensure_pinned(PinnedBuf &b, size_t want)
 {
-    if (have >= want)
+    if (b.bytes >= want)
         return true;
-    g_shelf.give(p, have);
-    p = nullptr;
-    have = 0;
-    if ((p = g_shelf.take(want, &have)))
+    b.reset();
+    if ((b.p = g_shelf.take(want, &b.bytes)))
         return true;
     const size_t take = want + want / 8;
-    if (hipHostMalloc(reinterpret_cast<void **>(&p), take, hipHostMallocDefault) != hipSuccess) {
+    if (hipHostMalloc(reinterpret_cast<void **>(&b.p), take, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
-        p = nullptr;
+        b.p = nullptr;
         return false;
     }
-    have = take;
+    b.bytes = take;
     return true;
 }
 
@@ -2174,7 +2094,7 @@ static int map_reads_host_packed(kmm_index_t *ix, const uint8_t *bases, const in
         f.store(0, std::memory_order_relaxed);
     std::atomic<size_t> next{0}, slots_free{(size_t)SLOTS};
     std::atomic<bool> stop{false}, bad{false};
-    uint8_t *const *ring = ix->ring;
+    const PinnedBuf *ring = ix->ring;
     ix->pack_pool->start([&](int) {
         for (;;) {
             const size_t c = next.fetch_add(1);
@@ -2194,7 +2114,7 @@ static int map_reads_host_packed(kmm_index_t *ix, const uint8_t *bases, const in
             if (stop.load(std::memory_order_relaxed))
                 return;
             const size_t b0 = c * CHUNK, len = total - b0 < CHUNK ? total - b0 : CHUNK;
-            if (!bad.load(std::memory_order_relaxed) && !kmm_hostpack::pack2(bases + b0, len, ring[piece % SLOTS] + (c % PER_SLOT) * (CHUNK / 4)))
+            if (!bad.load(std::memory_order_relaxed) && !kmm_hostpack::pack2(bases + b0, len, ring[piece % SLOTS].p + (c % PER_SLOT) * (CHUNK / 4)))
                 bad.store(true);
             filled[piece].fetch_add(1, std::memory_order_release);
         }
@@ -2237,7 +2157,7 @@ static int map_reads_host_packed(kmm_index_t *ix, const uint8_t *bases, const in
             rc = fail(KMM_ERR_HIP, "hipEventRecord: %s", hipGetErrorString(hipGetLastError()));
 #else
         hipStream_t cs = ix->copy_stream;
-        if (hipMemcpyAsync((uint8_t *)s.kmers.p + b0, ring[c % SLOTS], len, hipMemcpyHostToDevice, cs) != hipSuccess ||
+        if (hipMemcpyAsync((uint8_t *)s.kmers.p + b0, ring[c % SLOTS].p, len, hipMemcpyHostToDevice, cs) != hipSuccess ||
             hipEventRecord(ix->bgzf_slot_ev[c % SLOTS], cs) != hipSuccess)
             rc = fail(KMM_ERR_HIP, "copy of packed reads: %s", hipGetErrorString(hipGetLastError()));
 #endif
@@ -2308,8 +2228,7 @@ static int map_records_host_packed(kmm_index_t *ix, const uint8_t *raw, int64_t 
     const size_t code_bytes = (n / 4 + 1024 + 63) & ~(size_t)63, bits_bytes = (n / 8 + 256 + 63) & ~(size_t)63;
     static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
     const auto t_0 = std::chrono::steady_clock::now();
-    if (!ensure_pack_pool(ix) || !ensure_pinned(ix->pack_pinned, ix->pack_pinned_bytes, code_bytes) ||
-        !ensure_pinned(ix->pack_bits_pinned, ix->pack_bits_pinned_bytes, bits_bytes))
+    if (!ensure_pack_pool(ix) || !ensure_pinned(ix->pack_pinned, code_bytes) || !ensure_pinned(ix->pack_bits_pinned, bits_bytes))
         return KMM_OK;
     Stage &s = next_stage(ix);
     KMMCHK(stage_acquire(ix, s));
@@ -2318,8 +2237,8 @@ static int map_records_host_packed(kmm_index_t *ix, const uint8_t *raw, int64_t 
     const auto t_1 = std::chrono::steady_clock::now();
     kmm_hostpack::RecordsJob job;
     const size_t slice = ix->host_pack_slice_kb > 0 ? (size_t)ix->host_pack_slice_kb << 10 : kmm_hostpack::RecordsJob::slice_bytes();
-    job.prepare(raw, n, format == KMM_FORMAT_FASTQ ? 4 : 2, reinterpret_cast<uint64_t *>(ix->pack_pinned),
-                reinterpret_cast<uint32_t *>(ix->pack_bits_pinned), slice);
+    job.prepare(raw, n, format == KMM_FORMAT_FASTQ ? 4 : 2, reinterpret_cast<uint64_t *>(ix->pack_pinned.p),
+                reinterpret_cast<uint32_t *>(ix->pack_bits_pinned.p), slice);
     ix->pack_pool->start([&job](int) { job.run(); });
     // groups of slices (32 MiB of raw bytes): the words of the stream that lie wholly below the group's end are final
     const size_t GROUP = std::max<size_t>(1, ((size_t)32 << 20) / slice);
@@ -2328,7 +2247,7 @@ static int map_records_host_packed(kmm_index_t *ix, const uint8_t *raw, int64_t 
     for (size_t g1 = GROUP; g1 < job.n_slices() && rc == KMM_OK; g1 += GROUP) {
         const uint64_t upto_w = job.wait_packed_prefix(g1) >> 5;
         if (upto_w > copied_w) {
-            if (hipMemcpyAsync((uint8_t *)s.kmers.p + copied_w * 8, ix->pack_pinned + copied_w * 8, (size_t)(upto_w - copied_w) * 8,
+            if (hipMemcpyAsync((uint8_t *)s.kmers.p + copied_w * 8, ix->pack_pinned.p + copied_w * 8, (size_t)(upto_w - copied_w) * 8,
                                hipMemcpyHostToDevice, ix->copy_stream) != hipSuccess)
                 rc = fail(KMM_ERR_HIP, "hipMemcpyAsync of packed records: %s", hipGetErrorString(hipGetLastError()));
             copied_w = upto_w;
@@ -2357,7 +2276,7 @@ static int map_records_host_packed(kmm_index_t *ix, const uint8_t *raw, int64_t 
     {   // the rest of the stream: from the word that holds the last base's neighbourhood (finish() cleaned it) to the zero
         // words behind it
         const uint64_t end_w = ((uint64_t)r.n_bases >> 5) + 40, from_w = copied_w < ((uint64_t)r.n_bases >> 5) ? copied_w : ((uint64_t)r.n_bases >> 5);
-        HIPCHK(hipMemcpyAsync((uint8_t *)s.kmers.p + from_w * 8, ix->pack_pinned + from_w * 8, (size_t)(end_w - from_w) * 8,
+        HIPCHK(hipMemcpyAsync((uint8_t *)s.kmers.p + from_w * 8, ix->pack_pinned.p + from_w * 8, (size_t)(end_w - from_w) * 8,
                               hipMemcpyHostToDevice, ix->copy_stream));
     }
     const bool uniform = r.uniform_len >= 16;
@@ -2366,7 +2285,7 @@ static int map_records_host_packed(kmm_index_t *ix, const uint8_t *raw, int64_t 
     if (!uniform) { // ragged reads: the read-start bitset crosses too (1 bit per base)
         n_words = r.n_bases / 32 + 2;
         KMMCHK(ensure(s.start_bits, (size_t)n_words * 4));
-        HIPCHK(hipMemcpyAsync(s.start_bits.p, ix->pack_bits_pinned, (size_t)n_words * 4, hipMemcpyHostToDevice, ix->copy_stream));
+        HIPCHK(hipMemcpyAsync(s.start_bits.p, ix->pack_bits_pinned.p, (size_t)n_words * 4, hipMemcpyHostToDevice, ix->copy_stream));
         start_bits = (const uint32_t *)s.start_bits.p;
     }
     KMMCHK(rec_launch_flat(ix, (const uint32_t *)s.kmers.p, r.n_bases, r.n_records, start_bits, n_words, uniform ? r.uniform_len : 0, k,
@@ -3064,7 +2983,7 @@ static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre
             f.store(0, std::memory_order_relaxed);
         std::atomic<size_t> next{0}, slots_free{(size_t)SLOTS}; // slot-sized pieces [0, slots_free) may be written
         std::atomic<bool> stop{false};
-        uint8_t *const *ring = ix->ring;
+        const PinnedBuf *ring = ix->ring;
         ix->pack_pool->start([&](int) {
             for (;;) {
                 const size_t c = next.fetch_add(1);
@@ -3083,7 +3002,7 @@ static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre
                 if (stop.load(std::memory_order_relaxed))
                     return;
                 const size_t b0 = c * SUB, len = n_stage - b0 < SUB ? n_stage - b0 : SUB;
-                memcpy(ring[piece % SLOTS] + (b0 - piece * SLOT), comp + pre + b0, len);
+                memcpy(ring[piece % SLOTS].p + (b0 - piece * SLOT), comp + pre + b0, len);
                 filled[piece].fetch_add(1, std::memory_order_release);
             }
         });
@@ -3114,7 +3033,7 @@ static int bgzf_stage_and_scan(kmm_index_t *ix, const uint8_t *comp, int64_t pre
                 if (!did)
                     std::this_thread::sleep_for(std::chrono::microseconds(20));
             }
-            if (hipMemcpyAsync(d_comp + pre + b0, ring[c % SLOTS], len, hipMemcpyHostToDevice, ix->copy_stream) != hipSuccess ||
+            if (hipMemcpyAsync(d_comp + pre + b0, ring[c % SLOTS].p, len, hipMemcpyHostToDevice, ix->copy_stream) != hipSuccess ||
                 hipEventRecord(ix->bgzf_slot_ev[c % SLOTS], ix->copy_stream) != hipSuccess)
                 rc = fail(KMM_ERR_HIP, "copy of compressed bytes: %s", hipGetErrorString(hipGetLastError()));
             // a slot is written again only when its copy has landed: the oldest one is waited for when the ring is full
@@ -3272,7 +3191,7 @@ static int bgzf_inflate(kmm_index_t *ix, StreamCall &c, const uint8_t *comp, int
     const int cur = b.cur = ix->bgzf_cur;
     ix->bgzf_cur ^= 1;
     if (!ix->bgzf_done[cur])
-        HIPCHK(hipEventCreateWithFlags(&ix->bgzf_done[cur], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(ix->bgzf_done[cur].put(), hipEventDisableTiming));
     const int64_t carry = ix->bgzf_carry_len;
     // 3.5 GiB per call; what a prestaged chain leaves for a carry ("debug_bgzf_call_cap_kb": a small file reaches the cap)
     const unsigned long long CALL_CAP = ix->dbg_bgzf_call_cap_kb > 0 ? (unsigned long long)ix->dbg_bgzf_call_cap_kb << 10 : 7ull << 29,
@@ -3745,8 +3664,8 @@ struct GzGpuBackend {
                 return false;
             if (!sync())
                 return false;
-            release(raw);
-            raw = nb;
+            (void)raw.reset();
+            raw = std::move(nb);
         } else if (carry > 0 && !hip(hipMemcpyAsync(raw.p, ix->gz_carry.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream), "carry")) {
             return false;
         }
@@ -3843,17 +3762,12 @@ int kmm_map_gzip(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int forma
         ix->gzip_chunks += (int64_t)cs.chunks;
         ix->gzip_false_starts += (int64_t)cs.false_starts;
         ix->gzip_continuations += (int64_t)cs.continuations;
-        auto release_arena = [&] { // the stream has ended (or cannot go on): its symbol slots go back to the device
-            for (DevBuf &b : ix->gz_arena)
-                release(b);
-            ix->gz_arena.clear();
-        };
         if (co.err) {
             static const char *why[] = {"", "header", "reserved block type", "stored block", "code lengths", "Huffman code", "invalid symbol",
                                         "distance too far back", "more data than a block can hold", "compressed data ended early",
                                         "ISIZE mismatch", "CRC32 mismatch"};
             ix->gz_carry_len = 0;
-            release_arena();
+            ix->gz_arena.clear(); // the stream cannot go on: its symbol slots go back to the device
             return fail(KMM_ERR_MALFORMED, "kmm_map_gzip: corrupt gzip stream near compressed byte %llu of the chunk: %s",
                         (unsigned long long)co.err_at, co.err < 12 ? why[co.err] : "?");
         }
@@ -3889,7 +3803,7 @@ int kmm_map_gzip(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int forma
             HIPCHK(hipStreamSynchronize(ix->stream));
         }
         if (c.last_chunk)
-            release_arena();
+            ix->gz_arena.clear(); // the stream has ended: its symbol slots go back to the device
         return KMM_OK;
     });
 }
@@ -3924,7 +3838,6 @@ int kmm_in_index(kmm_index_t *ix, const uint64_t *kmers, int64_t n, uint8_t *out
         e = hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, ix->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(ix->stream);
-    release(tmp);
     if (e != hipSuccess)
         return fail(KMM_ERR_HIP, "kmm_in_index: %s", hipGetErrorString(e));
     return stage_release(ix, s, staged);
@@ -3969,11 +3882,11 @@ int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offs
     if (!bases || (n_out > 0 && !out))
         return fail(KMM_ERR_INVALID_ARG, "bases / out is NULL");
 
+    Stream st; // a stream of its own: other handles' work on this device is not stalled (destroyed after the buffers)
     DevBuf d_bases, d_offs, d_lut, d_out, d_bad, d_tf, d_cnt, d_sup;
     int rc = KMM_OK;
     hipError_t e = hipSuccess;
-    hipStream_t st = nullptr; // a stream of its own: other handles' work on this device is not stalled
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
     auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) -> hipError_t {
         hipError_t x = hipMemcpyAsync(dst, src, bytes, kind, st);
         return x == hipSuccess ? hipStreamSynchronize(st) : x;
@@ -4070,10 +3983,7 @@ int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offs
         if (!out_dev && n_out)
             if ((e = copy(out, d_out.p, (size_t)n_out * 8, hipMemcpyDeviceToHost))) break;
     } while (0);
-    release(d_bases); release(d_offs); release(d_lut); release(d_out); release(d_bad); release(d_tf);
-    release(d_cnt); release(d_sup);
     (void)hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
     if (rc != KMM_OK)
         return rc;
     if (e != hipSuccess)
@@ -4103,12 +4013,12 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
     HIPCHK(hipSetDevice(device));
     const uint64_t M = modulo;
     const uint64_t magic = magic_for(M);
+    Stream st; // a stream of its own: other handles' work on this device is not stalled (destroyed after the buffers)
     DevBuf d_km, d_nd, d_nk, d_h2i, d_cur, d_src, d_ko, d_no, d_fo, d_list, d_ksort;
     std::vector<DevBuf> scratch(2 * SCAN_MAX_LEVELS);
     int rc = KMM_OK;
     hipError_t e = hipSuccess;
-    hipStream_t st = nullptr; // a stream of its own: other handles' work on this device is not stalled
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
     auto up = [&](DevBuf &b, const void *src, size_t bytes, const void **dev) -> bool {
         if (bytes == 0 || is_device_ptr(src)) {
             *dev = src;
@@ -4190,14 +4100,7 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
         if (!down(n_kmers, w_nk, (size_t)M * 4)) break;
         if (!down(hashes_to_index, w_h2i, (size_t)M * 4)) break;
     } while (0);
-    release(d_km); release(d_nd); release(d_nk); release(d_h2i); release(d_cur); release(d_src);
-    release(d_ko); release(d_no); release(d_fo); release(d_list); release(d_ksort);
-    for (DevBuf &b : scratch)
-        release(b);
-    if (st) {
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamDestroy(st);
-    }
+    (void)hipStreamSynchronize(st);
     if (rc != KMM_OK)
         return rc;
     if (e != hipSuccess)
@@ -4248,7 +4151,7 @@ int kmm_get_timing(kmm_index_t *ix, int kernel_id, double *kernel_ms, int64_t *n
         HIPCHK(hipEventElapsedTime(&ms, ev.start, ev.stop));
         ix->ms_total[ev.kernel_id] += ms;
         ix->launches[ev.kernel_id] += 1;
-        ix->ev_free.push_back(ev);
+        ix->ev_free.push_back(std::move(ev));
     }
     ix->ev_used.clear();
     if (kernel_ms)
@@ -4332,11 +4235,10 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         HIPCHK(hipStreamSynchronize(ix->stream));
         if (value && !ix->rx_ecnt_acc) {
             const size_t S = ix->rx_S ? ix->rx_S : 1;
-            HIPCHK(hipMalloc(&ix->rx_ecnt_acc, S * 4));
+            HIPCHK(hipMalloc(ix->rx_ecnt_acc.put(), S * 4));
             HIPCHK(hipMemset(ix->rx_ecnt_acc, 0, S * 4));
         } else if (!value && ix->rx_ecnt_acc) {
-            HIPCHK(hipFree(ix->rx_ecnt_acc));
-            ix->rx_ecnt_acc = nullptr;
+            HIPCHK(ix->rx_ecnt_acc.reset());
         }
     } else if (!strcmp(name, "grid_per_cu")) {
         if (value < 1 || value > 1024)

@@ -854,6 +854,41 @@ def test_handles_do_not_leak_device_memory(kmm, syn):
     assert free0 - free1 < 64 << 20, "leaked %.1f MiB of HBM" % ((free0 - free1) / 2 ** 20)
 
 
+def test_error_paths_do_not_leak_device_memory(kmm, syn):
+    """Calls that fail after allocating (an inconsistent index, an `out` one element short) and the switches that free
+    and allocate index arrays (count_kmers mode, part_shift): free HBM returns to its level."""
+    import copy
+    import torch
+    index, genome = syn.make_index(1000000, seed=241)
+    bases, offs = syn.make_ragged_reads(genome, 20000, 0, 200, seed=242)
+    n_out = int(np.maximum(np.diff(offs) - 30, 0).sum())
+    bad = copy.copy(index)
+    bad._n_kmers = index._n_kmers.copy()
+    bad._n_kmers[int(np.flatnonzero(bad._n_kmers)[0])] = index._kmers.shape[0] + 1    # bucket reaches past the entries
+
+    with kmm.DeviceIndex.from_index(index) as dev:
+        assert dev.get_param("radix_available") == 1
+        shift = dev.get_param("part_shift")
+
+        def cycle(n):
+            for i in range(n):
+                with pytest.raises(ValueError, match="inconsistent"):
+                    kmm.DeviceIndex.from_index(bad)
+                with pytest.raises(ValueError):
+                    kmm.extract_kmers(bases, offs, 31, out=np.empty(n_out - 1, dtype=np.uint64))
+                dev.count_kmers_mode(True)
+                dev.count_kmers_mode(False)
+                dev.set_param("part_shift", shift - (i & 1))
+
+        cycle(3)                                  # warm up allocator pools
+        torch.cuda.synchronize()
+        free0, _ = torch.cuda.mem_get_info()
+        cycle(40)
+        torch.cuda.synchronize()
+        free1, _ = torch.cuda.mem_get_info()
+    assert free0 - free1 < 64 << 20, "leaked %.1f MiB of HBM" % ((free0 - free1) / 2 ** 20)
+
+
 def test_cli_tiny_chunk_size_grows_until_a_record_fits(kmm, syn, oracle, tmp_path):
     """`-c 64` is smaller than one FASTQ record: the raw chunker must grow instead of looping forever."""
     from kmer_mapper_amd import reads_io
