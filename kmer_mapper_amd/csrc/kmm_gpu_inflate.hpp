@@ -55,7 +55,12 @@ constexpr int PRIM_WORDS = PRIM_LIT + PRIM_DIST + PRIM_TMP;                     
 #if defined(KMM_GZ_EXPERIMENT_SEC_IN_LDS) || defined(KMM_GZ_EXPERIMENT_PAD_LDS) // (tools/gz_phase.py: what do the subtables' trips cost?)
 constexpr int SEC_LIT = 512, SEC_DIST = 384, SEC_WORDS = SEC_LIT + SEC_DIST;
 #else
-constexpr int SEC_LIT = 1024, SEC_DIST = 1024, SEC_WORDS = SEC_LIT + SEC_DIST;                     // uint16 per lane (HBM)
+// The subtables' sizes are the proven bounds of what a valid code can need: the sum over the primary indexes of 2^(longest code
+// under the index - primary bits), maximised over every code the decoder accepts (286 literal / length symbols at 8 primary
+// bits: 404 entries; 30 distance symbols at 5 bits: 1040 — counts per length 1..15 = 0,3,0,0,0,13,5,1,1,1,1,1,1,1,2).
+// tests/test_inflate_vs_zlib_on_the_cpu.py recomputes both bounds exactly (zlib's examples/enough.c, restated) and checks
+// them against these constants and the link's 11-bit offset.
+constexpr int SEC_LIT = 1024, SEC_DIST = 1040, SEC_WORDS = SEC_LIT + SEC_DIST;                     // uint16 per lane (HBM)
 #endif
 constexpr uint32_t LINK = 0x8000u;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -105,7 +110,10 @@ KMM_HD inline uint32_t lens_get(const uint64_t *w, int i) { return (uint32_t)(w[
 // code of every length: the two arrays the sweeps index by a code length live in LDS, not in the lane's private memory,
 // where every step of such a chain is a round trip to HBM / L2.  Two sweeps over the symbols: the primary entries of the
 // prefixes that need a subtable first hold the longest code length under them, then the link.  Returns OK or E_TABLE.
-// allow_incomplete: a distance code may consist of one code.
+// allow_incomplete (literal / length and distance codes): what zlib accepts besides a complete code — no code at all (a
+// distance code of a literal-only block; a literal / length code without one is refused by the caller: no end-of-block code),
+// or ONE code of length 1; its other bit pattern, like every bit pattern without a code, decodes as "no code" (E_SYMBOL).
+// Any other incomplete code (one code of length 2 or more, two codes of length 3, ...) is refused, as zlib refuses it.
 KMM_HD inline int build_table(const uint64_t *lens, int at, int n, int pb, uint16_t *prim, uint16_t *tmp, uint16_t *sec, int sec_cap,
                               bool allow_incomplete)
 {
@@ -122,7 +130,8 @@ KMM_HD inline int build_table(const uint64_t *lens, int at, int n, int pb, uint1
             w >>= 4;
         }
     }
-    if (count[0] == n)
+    const bool none = count[0] == n; // (no code at all)
+    if (none && !allow_incomplete)
         return E_TABLE;
     int left = 1; // Kraft: code space still free
     bool any_long = false;
@@ -139,7 +148,7 @@ KMM_HD inline int build_table(const uint64_t *lens, int at, int n, int pb, uint1
             any_long = any_long || (l > pb && c);
         }
     }
-    if (left > 0 && !allow_incomplete)
+    if (left > 0 && !(allow_incomplete && (none || (count[1 * PS] == 1 && count[0] == n - 1))))
         return E_TABLE;
     const uint32_t psize = 1u << pb, pmask = psize - 1u;
     for (uint32_t i = 0; i < psize; ++i)
@@ -481,14 +490,14 @@ KMM_HD inline int block_header(Bits &b, uint32_t n_in, uint8_t *out, uint32_t n_
         return bits_consumed_bytes(b) > n_in ? E_INPUT : OK;
     }
     uint64_t lens[LENS_WORDS];
-    int hlit = 288, hdist = 30;
-    if (type == 1u) { // fixed code (RFC 1951 3.2.6): 144 x 8, 112 x 9, 24 x 7, 8 x 8 bits; 30 distance codes of 5
+    int hlit = 288, hdist = 32;
+    if (type == 1u) { // fixed code (RFC 1951 3.2.6): 144 x 8, 112 x 9, 24 x 7, 8 x 8 bits; 32 distance codes of 5
         for (int i = 0; i < 9; ++i) lens[i] = 0x8888888888888888ull;
         for (int i = 9; i < 16; ++i) lens[i] = 0x9999999999999999ull;
         lens[16] = 0x7777777777777777ull;
         lens[17] = 0x8888888877777777ull;
         lens[18] = 0x5555555555555555ull;
-        lens[19] = 0x0055555555555555ull;
+        lens[19] = 0x5555555555555555ull; // (32 distance codes: 30 and 31 have a code and are refused where they are used)
     } else {
         hlit = (int)bits_take(b, 5) + 257;
         hdist = (int)bits_take(b, 5) + 1;
@@ -548,7 +557,7 @@ KMM_HD inline int block_header(Bits &b, uint32_t n_in, uint8_t *out, uint32_t n_
         if (lens_get(lens, 256) == 0)
             return E_TABLE; // no end-of-block code
     }
-    if (build_table(lens, 0, hlit, LIT_PB, lit, tmp, lit2, SEC_LIT, false) != OK ||
+    if (build_table(lens, 0, hlit, LIT_PB, lit, tmp, lit2, SEC_LIT, true) != OK ||
         build_table(lens, hlit, hdist, DIST_PB, dst, tmp, dst2, SEC_DIST, true) != OK)
         return E_TABLE;
     return OK;

@@ -242,9 +242,20 @@ inline bool read_dynamic_header(Bits &b, Huff &lit, Huff &dist)
     }
     if (!lens[256])
         return false; // no end-of-block code
-    if (build_huff(lens, (int)hlit, LIT_PB, lit, false) != 0)
+    // Both codes: complete, or what zlib accepts besides — ONE code of length 1 (RFC 1951 3.2.7), or, for the distance code,
+    // none (a literal-only block).  Any other incomplete code is refused, as zlib refuses it (kmm_gpu_inflate.hpp's rule).
+    auto one_code_of_length_1 = [&](uint32_t at, uint32_t n) {
+        int k = 0, ones = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            k += lens[at + j] != 0;
+            ones += lens[at + j] == 1;
+        }
+        return k == 1 && ones == 1;
+    };
+    const bool lit_one = one_code_of_length_1(0, hlit);
+    const int lrc = build_huff(lens, (int)hlit, LIT_PB, lit, lit_one);
+    if (!(lrc == 0 || (lrc == 1 && lit_one)))
         return false;
-    // distance code: complete, or incomplete with at most one code (RFC 1951 3.2.7), or none (a literal-only block)
     int n_dist = 0;
     for (uint32_t k = 0; k < hdist; ++k)
         n_dist += lens[hlit + k] != 0;
@@ -253,8 +264,9 @@ inline bool read_dynamic_header(Bits &b, Huff &lit, Huff &dist)
         dist.pb = DIST_PB;
         return true;
     }
-    const int rc = build_huff(lens + hlit, (int)hdist, DIST_PB, dist, n_dist == 1);
-    return rc == 0 || (rc == 1 && n_dist == 1);
+    const bool dist_one = one_code_of_length_1(hlit, hdist);
+    const int rc = build_huff(lens + hlit, (int)hdist, DIST_PB, dist, dist_one);
+    return rc == 0 || (rc == 1 && dist_one);
 }
 
 inline void fixed_tables(Huff &lit, Huff &dist)
