@@ -11,28 +11,17 @@ import zlib
 
 import numpy as np
 
+from .gz_io import BGZF_MAGIC, bgzf_member_size
 from .reads_io import _NL, _is_record_start
-
-_MAGIC = b"\x1f\x8b\x08\x04"
 
 
 def member_end(buf, p):
-    """End offset of the BGZF member that starts at compressed byte p (SAM specification 4.1: gzip header with the BC extra
-    subfield, BSIZE = total size - 1); ValueError if there is none."""
-    size = len(buf)
-    if p + 18 > size or buf[p:p + 4] != _MAGIC:
-        raise ValueError("no BGZF member at compressed byte %d" % p)
-    xlen = struct.unpack_from("<H", buf, p + 10)[0]
-    q = p + 12
-    while q + 4 <= p + 12 + xlen:
-        si1, si2, slen = struct.unpack_from("<BBH", buf, q)
-        if si1 == 66 and si2 == 67 and slen == 2 and q + 6 <= size:
-            end = p + struct.unpack_from("<H", buf, q + 4)[0] + 1
-            if end > size or end < p + 12 + xlen + 8:
-                break
-            return end
-        q += 4 + slen
-    raise ValueError("BGZF member at compressed byte %d has no size / runs past the end of the file" % p)
+    """End offset of the BGZF member that starts at compressed byte p (gz_io.bgzf_member_size); ValueError if there is none
+    or it runs past the end of the file."""
+    size = bgzf_member_size(buf, p)
+    if not size or p + size > len(buf):
+        raise ValueError("no BGZF member at compressed byte %d (or it has no size / runs past the end of the file)" % p)
+    return p + size
 
 
 def member_chain(buf):
@@ -89,7 +78,7 @@ def member_at_or_after(buf, t):
         return 0, None
     p = max(0, t - 70000)
     while True:
-        p = buf.find(_MAGIC, p) if p > 0 else 0
+        p = buf.find(BGZF_MAGIC, p) if p > 0 else 0
         if p < 0 or p >= size:
             return size, None
         if _holds(buf, p):

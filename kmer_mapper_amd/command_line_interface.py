@@ -32,8 +32,8 @@ from .distributed import chunk_owner
 from .engine import DeviceIndex
 from .kmer_index import KmerIndex
 from . import _lib
-from .reads_io import (MmapChunker, RawChunker, PrefetchingRawChunker, prefetch, rank_byte_range, read_chunks, records_cut,
-                       sniff_format)
+from .reads_io import (MmapChunker, RawChunker, PrefetchingRawChunker, prefetch, probe_input, rank_byte_range, read_chunks,
+                       records_cut)
 
 
 def main():
@@ -121,15 +121,56 @@ def map_gpu(index, chunks, k, hash_map_size=0, map_reverse_complements=False,
     return node_counts
 
 
+def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ):
+    """How map_gpu_raw reads the file: (route, populate, steer).  fmt: the GPU's record format ("fasta_ml" = wrapped FASTA);
+    probe: reads_io.probe_input of the file; env: where the KMM_CLI_* switches of A/B runs are read.
+
+    route "bam" / "bgzf" / "gzip": the compressed bytes go to the GPU as they lie in the file mapping and are inflated there
+    (_map_compressed_file).  BGZF (.gz written by bgzip / htslib: independent members of <= 64 KiB): one GPU thread inflates one
+    member — the host's inflater (10.8 GB/s of FASTQ on 16 cores) is out of the way; several ranks each take the members that
+    start in their share of the compressed bytes (bgzf_ranges.py).  Plain gzip (`gzip reads.fq`: one deflate stream, no member
+    sizes), one rank: speculative block starts, one lane per ~32 KiB of compressed bytes (kmm_map_gzip); opt-in
+    (KMM_CLI_GPU_GUNZIP=1) until it beats the host inflater's route on the same box (profiles/gzip_gpu/).  BAM is
+    told by its content, whatever its name.
+    route "mmap": a plain FASTQ / two-line FASTA with host packing is mapped into memory and its chunks handed to the packer
+    threads as views of the page cache (MmapChunker: no copy, nothing pinned).  populate: helper threads map its pages ahead
+    (MADV_POPULATE_READ) while the index goes up — the 16 packer threads otherwise take a page fault per 64 KiB of a fresh
+    mapping, all in one address space (profiles/r05/cli_populate_ab.txt); steer: the packer threads run next to the file's
+    page-cache pages.
+    route "prefetch": any other input the host inflates: two pinned buffers and a reader thread, the next batch is inflated
+    while the GPU works on this one (BGZF 5.7 -> 6.5 GB/s end to end); plain files are read at memory speed and the second
+    pinned buffer costs more than the overlap returns (3 GB FASTQ: 0.30 s with one buffer, 0.37 s with two), so they take
+    route "raw": one pinned buffer (RawChunker)."""
+    gpu_inflate = probe.inflate and fmt in ("fastq", "fasta", "sam") and not env.get("KMM_CLI_NO_GPU_INFLATE")
+    if fmt == "bam":
+        return "bam", False, False
+    if gpu_inflate and probe.container == "bgzf":
+        return "bgzf", False, False
+    if gpu_inflate and probe.container == "gzip" and world_size == 1 and env.get("KMM_CLI_GPU_GUNZIP", "") not in ("", "0"):
+        return "gzip", False, False
+    if probe.inflate:
+        return ("raw" if env.get("KMM_CLI_NO_PREFETCH") else "prefetch"), False, False
+    if fmt in ("fastq", "fasta") and n_threads > 1 and has_device and not env.get("KMM_CLI_NO_MMAP"):
+        return "mmap", not env.get("KMM_CLI_NO_POPULATE"), not env.get("KMM_CLI_NO_PACKER_STEERING")
+    return "raw", False, False
+
+
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
-                exclude_flags=0):
+                exclude_flags=0, probe=None):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
     on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
-    extracted on the GPU (KMM_FORMAT_SAM on the routes of a FASTQ; exclude_flags filters it too)."""
+    extracted on the GPU (KMM_FORMAT_SAM on the routes of a FASTQ; exclude_flags filters it too).  probe: reads_io.probe_input
+    of the file, if the caller has it."""
     _check_bam_route(fmt, world_size, exclude_flags)
     t_index = time.perf_counter()
+    probe = probe_input(path) if probe is None else probe
+    has_device = _lib.device_count() > 0
+    # (decided BEFORE anything is made: the prefetching chunker starts a reader thread and page-locks two batch buffers —
+    # making and freeing those cost the BGZF route 100 ms of its map phase until it was noticed)
+    route, populate, steer = choose_route(fmt, probe, world_size, n_threads, has_device)
+    seekable = not probe.inflate
     # page-locked memory is slow to make (~50 ms per GB): the staging buffers of the host packer are made by a helper thread
     # WHILE the index is uploaded and repacked, not inside the map phase.  (The count vector needs none: kmm_get_node_counts
     # brings a large vector to ordinary memory through the handle's page-locked ring at the link's rate.)
@@ -139,28 +180,22 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     def prepare_host_memory():
         try:
             size = os.stat(path).st_size
-            if n_threads > 1 and not str(path).endswith(".gz"):
-                _lib.check(_lib.lib().kmm_host_reserve(min(size // max(world_size, 1) + (1 << 20), 2 << 30)))
+            _lib.check(_lib.lib().kmm_host_reserve(min(size // max(world_size, 1) + (1 << 20), 2 << 30)))
         except Exception as exc:                         # noqa: BLE001 - an optimisation: the map calls allocate what is missing
             logging.debug("host memory was not prepared ahead: %s", exc)
 
     helper = threading.Thread(target=prepare_host_memory, daemon=True)
     # (.gz input needs 128 MB of it, made in 7 ms by the first call that wants it; behind a helper thread the same allocation
     # came back 100 ms after the index upload it was meant to hide behind: profiles/r05/bgzf_e2e_v6_*.txt)
-    if _lib.device_count() > 0 and n_threads > 1 and not str(path).endswith(".gz"):
+    if has_device and n_threads > 1 and seekable:
         helper.start()
-    # A plain FASTQ / two-line FASTA is mapped into memory and handed to the packer threads as it lies in the page cache
-    # (MmapChunker).  The mapping is made HERE, before the index goes up, and helper threads populate its page tables
-    # meanwhile (MADV_POPULATE_READ): the 16 packer threads otherwise take a page fault per 64 KiB of a fresh mapping,
-    # all in one address space (profiles/r05/cli_populate_ab.txt).
-    seekable = not str(path).endswith(".gz")
     byte_range = rank_byte_range(path, fmt, rank, world_size) if (world_size > 1 and seekable) else None
-    early = None
-    if (seekable and fmt in ("fastq", "fasta") and n_threads > 1 and _lib.device_count() > 0
-            and not os.environ.get("KMM_CLI_NO_MMAP")):
-        early = MmapChunker(path, int(chunk_size), byte_range, pinned=True)
-        if not os.environ.get("KMM_CLI_NO_POPULATE"):
-            early.populate(n_threads=max(1, min(4, host_threads(n_threads, world_size) // 2)))
+    # the file mapping of route "mmap" is made HERE, and its pages populated, while the index goes up
+    chunker = None
+    if route == "mmap":
+        chunker = MmapChunker(path, int(chunk_size), byte_range, pinned=True)
+        if populate:
+            chunker.populate(n_threads=max(1, min(4, host_threads(n_threads, world_size) // 2)))
     # (the scan for the largest node id — 30 ms on one thread for 10^8 entries — runs with the helpers above already at work)
     max_node_id = index.max_node_id() if hasattr(index, "max_node_id") else int(np.max(index._nodes))
     dev = DeviceIndex.from_index(index, max_node_id, device=device)
@@ -202,42 +237,12 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             # call packed by the host threads (profiles/r05/cli_mid_sized_file.txt)
             batch_bytes = min(int(share) + (1 << 20), 2 << 30)
             logging.info("Chunks of %d bytes are accumulated into ONE GPU batch of %d bytes (radix path)", chunk_size, batch_bytes)
-    # .gz input: two pinned buffers and a reader thread — the next batch is inflated while the GPU works on this one
-    # (BGZF 5.7 -> 6.5 GB/s end to end); plain files are read at memory speed and the second pinned buffer costs more
-    # than the overlap returns (3 GB FASTQ: 0.30 s with one buffer, 0.37 s with two)
-    use_prefetch = not seekable and not os.environ.get("KMM_CLI_NO_PREFETCH")
-    # plain FASTQ / two-line FASTA with host packing: the chunks are views of the file mapping (no copy, nothing pinned)
-    use_mmap = (seekable and fmt in ("fastq", "fasta") and dev.get_param("host_pack_threads") > 0
-                and not os.environ.get("KMM_CLI_NO_MMAP"))
-    # BGZF (.gz written by bgzip / htslib: independent members of <= 64 KiB): the compressed bytes go to the GPU as they lie
-    # in the file mapping, one GPU thread inflates one member, the records are parsed there too (kmm_map_bgzf) — the host's
-    # inflater (10.8 GB/s of FASTQ on 16 cores) is out of the way.  Several ranks: each takes the members that start in its share
-    # of the compressed bytes, resynchronised to the records at both ends (bgzf_ranges.py).
-    # (Decided BEFORE a chunker is made: the prefetching one starts a reader thread and page-locks two batch buffers — making
-    # and freeing those cost this route 100 ms of its map phase until it was noticed.)
-    gpu_inflate = (not seekable and fmt in ("fastq", "fasta", "sam") and not os.environ.get("KMM_CLI_NO_GPU_INFLATE")
-                   and _is_bgzf(path))
-    # plain gzip (`gzip reads.fq`: one deflate stream, no member sizes), one rank: the stream is inflated on the GPU too
-    # (kmm_map_gzip: speculative block starts, one lane per ~32 KiB of compressed bytes).  Opt-in (KMM_CLI_GPU_GUNZIP=1)
-    # until it beats the host inflater's route on the same box (profiles/gzip_gpu/).
-    gpu_gunzip = (not gpu_inflate and world_size == 1 and not seekable and fmt in ("fastq", "fasta", "sam")
-                  and os.environ.get("KMM_CLI_GPU_GUNZIP", "") not in ("", "0")
-                  and not os.environ.get("KMM_CLI_NO_GPU_INFLATE") and _is_gzip(path))
-    gpu_inflate = gpu_inflate or gpu_gunzip
-    # BAM (told by its content, reads_io.sniff_format): its BGZF members go to the GPU like a .fq.gz's, the records are found
-    # and their SEQ decoded there (kmm_map_bam)
-    bam = fmt == "bam"
-    gpu_inflate = gpu_inflate or bam
-    if early is not None and use_mmap and not gpu_inflate:
-        chunker = early
+    if route in ("prefetch", "raw"):
+        chunker = (PrefetchingRawChunker if route == "prefetch" else RawChunker)(path, batch_bytes, byte_range, pinned=True)
+    elif route == "mmap":
         chunker.chunk_size = batch_bytes
-    else:
-        if early is not None:
-            early.close()
-        chunker = None if gpu_inflate else (MmapChunker if use_mmap else PrefetchingRawChunker if use_prefetch
-                                            else RawChunker)(path, batch_bytes, byte_range, pinned=True)
     steered_from = None
-    if chunker is not None and chunker is early and not os.environ.get("KMM_CLI_NO_PACKER_STEERING"):
+    if steer:
         # the packer threads are made by the first map call and inherit this thread's CPUs: next to the file's pages
         from .distributed import packer_cpus_near
         try:
@@ -258,10 +263,10 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         dev.set_param("bam_exclude_flags", int(exclude_flags))
     t_start = time.perf_counter()
     n_reads = n_bytes = 0
-    if gpu_inflate:
+    if route in ("bam", "bgzf", "gzip"):
         if helper.ident is not None:
             helper.join()
-        return _map_compressed_file(dev, path, "bam" if bam else "gzip" if gpu_gunzip else "bgzf", kfmt, k, max_index_lookup_frequency,
+        return _map_compressed_file(dev, path, route, kfmt, k, max_index_lookup_frequency,
                                     map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
                                     world_size=world_size, fmt=fmt)
     try:
@@ -328,26 +333,6 @@ def _log_path_taken(n_radix, n_direct, n_host_packed=0):
                  "by the host threads)"
                  % ("radix" if n_radix and not n_direct else "direct" if n_direct and not n_radix else "mixed", n_radix, n_direct,
                     n_host_packed))
-
-
-def _is_bgzf(path):
-    """Does the file start with a BGZF member (gzip header with the BC extra subfield, SAM specification 4.1)?"""
-    try:
-        with open(path, "rb") as f:
-            h = f.read(18)
-    except OSError:
-        return False
-    return len(h) == 18 and h[:4] == b"\x1f\x8b\x08\x04" and h[12:14] == b"BC" and h[14:16] == b"\x02\x00"
-
-
-def _is_gzip(path):
-    """Does the file start with a gzip member header (RFC 1952: 1f 8b, deflate)?"""
-    try:
-        with open(path, "rb") as f:
-            h = f.read(3)
-    except OSError:
-        return False
-    return h == b"\x1f\x8b\x08"
 
 
 _GZIP_CALL_INFLATED = 3 << 30      # inflated bytes a kmm_map_gzip window is sized for (a call takes at most 3.5 GiB)
@@ -497,12 +482,6 @@ def map_bnp(args):
     start_time = time.perf_counter()
     kmer_index = _get_kmer_index_from_args(args)
 
-    n_bytes = os.stat(args.reads).st_size
-    if str(args.reads).endswith(".gz"):
-        n_bytes *= 6.5  # rough estimate for gzipped to give a progress (reference :92-93)
-    logging.info("N bytes of reads: %d" % n_bytes)
-    logging.info("Approx number of chunks of %d bytes: %d" % (args.chunk_size, int(n_bytes / args.chunk_size)))
-
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -536,8 +515,15 @@ def map_bnp(args):
     # 172 GB/s of FASTQ from the GPU's own node, 132 spread over both sockets: profiles/r05/hostpack_rate.txt)
     from .distributed import bind_to_gpu_numa_node
     logging.info("Rank %d: host side bound to its GPU's NUMA node: %s", rank, bind_to_gpu_numa_node(device))
+    # (the read file is opened first HERE, on the GPU's NUMA node)
+    probe = probe_input(args.reads)
+    n_bytes = os.stat(args.reads).st_size
+    if probe.inflate:
+        n_bytes *= 6.5  # rough estimate for gzipped to give a progress (reference :92-93)
+    logging.info("N bytes of reads: %d" % n_bytes)
+    logging.info("Approx number of chunks of %d bytes: %d" % (args.chunk_size, int(n_bytes / args.chunk_size)))
     revcomp = bool(getattr(args, "map_reverse_complements", False))
-    fmt, two_line = sniff_format(args.reads)
+    fmt = probe.fmt
     exclude_flags = int(getattr(args, "exclude_flags", 0) or 0)
     _check_bam_route(fmt, world, exclude_flags)
     if fmt == "bam" and getattr(args, "host_parser", False):
@@ -545,15 +531,14 @@ def map_bnp(args):
     if fmt == "sam" and getattr(args, "host_parser", False):
         raise ValueError("--host-parser does not read SAM: its SEQ column is extracted on the GPU (drop --host-parser)")
     if not getattr(args, "host_parser", False):
-        if fmt == "fasta" and not two_line:
+        if fmt == "fasta" and not probe.two_line:
             fmt = "fasta_ml"           # wrapped sequence lines: unwrapped on the GPU (KMM_FORMAT_FASTA)
         node_counts = map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, revcomp, max_freq,
                                   device=device, rank=rank, world_size=world, before_fetch=before_fetch,
-                                  n_threads=args.n_threads, exclude_flags=exclude_flags)
+                                  n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe)
     else:
         logging.info("Using the host FASTA/FASTQ parser")
-        seekable = not str(args.reads).endswith(".gz")
-        if world > 1 and seekable:
+        if world > 1 and not probe.inflate:
             chunks = read_chunks(args.reads, min_chunk_size=args.chunk_size,
                                  byte_range=rank_byte_range(args.reads, fmt, rank, world))
         elif world > 1:

@@ -15,19 +15,51 @@ from concurrent.futures import ThreadPoolExecutor
 _BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
-def _bgzf_block_size(header):
-    """Total size of the BGZF member that starts with the 18 bytes `header`, or 0 if it is not BGZF."""
-    if len(header) < 18 or header[:4] != b"\x1f\x8b\x08\x04":
+BGZF_MAGIC = b"\x1f\x8b\x08\x04"          # gzip, deflate, FEXTRA
+
+
+def bgzf_member_size(buf, p=0):
+    """Total size of the BGZF member whose header starts at byte p of `buf` (bytes-like / mmap), or 0 if there is none there.
+    SAM specification 4.1: a gzip header with extra subfields, one of them BC with SLEN 2 holding BSIZE = total size - 1.  The
+    subfields are walked in order and the first BC decides, as the device's bgzf_member_size does; the member's own bytes may
+    run past the end of `buf`.  Every BGZF header in the package is judged here."""
+    n = len(buf)
+    if p + 18 > n or buf[p:p + 4] != BGZF_MAGIC:
         return 0
-    xlen = struct.unpack_from("<H", header, 10)[0]
-    if xlen < 6 or header[12:14] != b"BC" or struct.unpack_from("<H", header, 14)[0] != 2:
-        return 0
-    return struct.unpack_from("<H", header, 16)[0] + 1
+    xlen = struct.unpack_from("<H", buf, p + 10)[0]
+    q, stop = p + 12, min(p + 12 + xlen, n)
+    while q + 4 <= stop:
+        si1, si2, slen = struct.unpack_from("<BBH", buf, q)
+        if si1 == 66 and si2 == 67 and slen == 2 and q + 6 <= stop:
+            total = struct.unpack_from("<H", buf, q + 4)[0] + 1
+            return total if total >= 12 + xlen + 8 else 0
+        q += 4 + slen
+    return 0
+
+
+_bgzf_block_size = bgzf_member_size      # (the name the reader's tests know it by)
+
+
+def container(head):
+    """"bgzf" | "gzip" | None: what the first bytes of a file say it is — a BGZF member, another gzip member (RFC 1952:
+    1f 8b, deflate), or neither."""
+    if bgzf_member_size(head):
+        return "bgzf"
+    return "gzip" if head[:3] == b"\x1f\x8b\x08" else None
 
 
 def is_bgzf(path):
     with open(path, "rb") as f:
-        return _bgzf_block_size(f.read(18)) > 0
+        return container(f.read(1 << 16)) == "bgzf"
+
+
+def _member_size_at(f, off):
+    """bgzf_member_size of the member at byte `off` of the open file f: its fixed header, then its extra subfields."""
+    f.seek(off)
+    head = f.read(12)
+    if len(head) == 12:
+        head += f.read(struct.unpack_from("<H", head, 10)[0])
+    return bgzf_member_size(head)
 
 
 def _inflate_member(raw):
@@ -117,8 +149,7 @@ def _bgzf_pieces(path, n_threads, group_bytes=1 << 22):
                 while off < size and len(pending) < 3 * n_threads:
                     start, sizes, acc = off, [], 0
                     while off < size and acc < group_bytes:
-                        f.seek(off)
-                        s = _bgzf_block_size(f.read(18))
+                        s = _member_size_at(f, off)
                         if not s:
                             raise ValueError("%s: not a BGZF member at byte %d" % (path, off))
                         sizes.append(s)

@@ -11,19 +11,25 @@ import gzip
 import queue
 import re
 import threading
+from typing import NamedTuple, Optional
 
 import numpy as np
 
+from . import gz_io
 from .util import ReadBatch
 
 _NL = 10
 _CR = 13
 
 
+def host_inflates(path):
+    """Does the host reader inflate the file?  By its name, as the reference's reader decides (bnp.open): one ending in .gz."""
+    return str(path).endswith(".gz")
+
+
 def _open(path):
-    if str(path).endswith(".gz"):
-        from .gz_io import open_gz
-        return open_gz(path)            # BGZF members are inflated on several cores, plain gzip on one
+    if host_inflates(path):
+        return gz_io.open_gz(path)      # BGZF members are inflated on several cores, plain gzip on one
     from . import _io
     if _io.available():
         return _io.NativeStream(path)   # parallel pread into the caller's (pinned) buffer
@@ -35,10 +41,7 @@ def _detect_format(first_byte, path):
         return "fasta"
     if first_byte == ord("@"):
         return "fastq"
-    name = str(path).lower()
-    for ext in (".gz",):
-        if name.endswith(ext):
-            name = name[: -len(ext)]
+    name = str(path).lower().removesuffix(".gz")
     if name.endswith((".fq", ".fastq")):
         return "fastq"
     if name.endswith((".fa", ".fasta", ".fna")):
@@ -335,24 +338,17 @@ def _looks_like_sam(head):
     return head[:1] not in (b"@", b">") and _sam_record_line(lines[0])
 
 
-def is_bam(path):
-    """Is the file BGZF whose first inflated bytes are the BAM magic "BAM\\1" (whatever its name)?"""
+def _starts_bam(head):
+    """Does the BGZF member at the start of `head` inflate to bytes that begin with the BAM magic "BAM\\1"?"""
     import zlib
     try:
-        with open(path, "rb") as f:
-            h = f.read(1 << 16)
-    except OSError:
-        return False
-    if len(h) < 18 or h[:4] != b"\x1f\x8b\x08\x04" or h[12:14] != b"BC" or h[14:16] != b"\x02\x00":
-        return False
-    try:
-        d = zlib.decompressobj(-15)
-        head = d.decompress(h[18:], 4)
-        while len(head) < 4 and not d.eof and d.unconsumed_tail:
-            head += d.decompress(d.unconsumed_tail, 4 - len(head))
+        d = zlib.decompressobj(31)                    # (zlib reads the gzip header, extra subfields included)
+        out = d.decompress(head, 4)
+        while len(out) < 4 and not d.eof and d.unconsumed_tail:
+            out += d.decompress(d.unconsumed_tail, 4 - len(out))
     except zlib.error:
         return False
-    return head[:4] == b"BAM\1"
+    return out[:4] == b"BAM\1"
 
 
 # ------------------------------------------------------------------------------------------------
@@ -488,27 +484,63 @@ def records_cut(buf, fmt, at_eof=False):
 # ------------------------------------------------------------------------------------------------
 # Raw-chunk reader for the GPU record parser (kmm_map_records): the host only moves bytes.
 # ------------------------------------------------------------------------------------------------
-def sniff_format(path, probe_bytes=1 << 16):
-    """Returns ("fastq" | "fasta" | "bam" | "sam", gpu_parsable).  Two-line FASTA and 4-line FASTQ can be parsed on
-    the GPU; FASTA whose sequences are wrapped over several lines needs the host parser.  BAM is told by its content (a BGZF
-    member whose inflated bytes start with "BAM\\1"), whatever the file is called; its records are decoded on the GPU.  SAM
-    text (plain, BGZF or gzip) is told by its content too (_looks_like_sam), not by its name; its SEQ column is extracted on
-    the GPU."""
-    if is_bam(path):
-        return "bam", True
+class InputProbe(NamedTuple):
+    """What route selection needs to know about a read file (probe_input)."""
+    fmt: str                   # "fastq" | "fasta" | "bam" | "sam"
+    two_line: bool             # parsable on the GPU as it lies (FASTA: one sequence line per record)
+    inflate: bool              # the host reader inflates it (host_inflates: its name)
+    container: Optional[str]   # "bgzf" | "gzip" | None, from its first bytes (gz_io.container)
+
+
+def probe_input(path, probe_bytes=1 << 16):
+    """Format and container of a read file, each judged once.  Two-line FASTA and 4-line FASTQ can be parsed on the GPU;
+    FASTA whose sequences are wrapped over several lines needs the host parser or the GPU's unwrapping.  BAM is told by its
+    content (a BGZF member whose inflated bytes start with "BAM\\1"), whatever the file is called; its records are decoded on
+    the GPU.  SAM text (plain, BGZF or gzip) is told by its content too (_looks_like_sam), not by its name; its SEQ column is
+    extracted on the GPU."""
+    with open(path, "rb") as f:
+        raw = f.read(1 << 16)
+    inflate, cont = host_inflates(path), gz_io.container(raw)
+    if cont == "bgzf" and _starts_bam(raw):
+        return InputProbe("bam", True, inflate, cont)
     with _open(path) as f:
-        head = f.read(probe_bytes)
+        head = bytes(f.read(probe_bytes))
     if not head:
-        return "fasta", True
-    if _looks_like_sam(bytes(head)):
-        return "sam", True
+        return InputProbe("fasta", True, inflate, cont)
+    if _looks_like_sam(head):
+        return InputProbe("sam", True, inflate, cont)
     fmt = _detect_format(head[0], path)
     if fmt == "fastq":
-        return fmt, True
+        return InputProbe(fmt, True, inflate, cont)
     lines = head.split(b"\n")
     complete = lines[:-1] if len(lines) > 1 else lines
     ok = all((ln[:1] == b">") == (i % 2 == 0) for i, ln in enumerate(complete) if ln or i % 2 == 0)
-    return fmt, ok
+    return InputProbe(fmt, ok, inflate, cont)
+
+
+def sniff_format(path, probe_bytes=1 << 16):
+    """("fastq" | "fasta" | "bam" | "sam", gpu_parsable) of probe_input."""
+    return probe_input(path, probe_bytes)[:2]
+
+
+def _host_buffer(n, pinned):
+    """(uint8 buffer of n bytes, the pointer _free_host_buffers takes back or None).  pinned: page-locked host memory
+    (kmm_host_alloc), so that the staging copy of kmm_map_records runs at the PCIe link's rate."""
+    if not pinned:
+        return np.empty(n, dtype=np.uint8), None
+    import ctypes
+    from . import _lib
+    p = ctypes.c_void_p()
+    _lib.check(_lib.lib().kmm_host_alloc(n, ctypes.byref(p)))
+    return np.frombuffer((ctypes.c_uint8 * n).from_address(p.value), dtype=np.uint8), p
+
+
+def _free_host_buffers(pointers):
+    """Frees what _host_buffer page-locked (the caller has dropped its views of it)."""
+    from . import _lib
+    for p in pointers:
+        if p is not None:
+            _lib.lib().kmm_host_free(p)
 
 
 class RawChunker:
@@ -521,23 +553,25 @@ class RawChunker:
         kmm_map_records runs at the PCIe link's rate."""
         self.f = _open(path)
         self.chunk_size = int(chunk_size)
-        self._pinned = None
-        n = self.chunk_size + (1 << 20)
-        if pinned:
-            import ctypes
-            from . import _lib
-            p = ctypes.c_void_p()
-            _lib.check(_lib.lib().kmm_host_alloc(n, ctypes.byref(p)))
-            self._pinned = p
-            self.buf = np.frombuffer((ctypes.c_uint8 * n).from_address(p.value), dtype=np.uint8)
-        else:
-            self.buf = np.empty(n, dtype=np.uint8)
+        self.buf, self._pinned = _host_buffer(self.chunk_size + (1 << 20), pinned)
         self.fill = 0
         self.eof = False
         self.left = None
         if byte_range is not None:
             self.f.seek(byte_range[0])
             self.left = byte_range[1] - byte_range[0]
+
+    @classmethod
+    def over_stream(cls, f, chunk_size, left, head):
+        """The same loop over the open stream `f` from where another reader stopped: `head` = the bytes it read that the
+        consumer has not used, `left` = what remains of the byte range (None: the rest of the stream).  Ordinary memory."""
+        self = cls.__new__(cls)
+        self.f, self.chunk_size, self.left, self._pinned = f, int(chunk_size), left, None
+        self.buf = np.empty(max(2 * len(head), self.chunk_size + (1 << 20)), dtype=np.uint8)
+        self.buf[:len(head)] = head
+        self.fill = len(head)
+        self.eof = False
+        return self
 
     def next_chunk(self):
         """Returns a uint8 view (valid until the next call) or None at end of input."""
@@ -571,11 +605,9 @@ class RawChunker:
 
     def close(self):
         self.f.close()
-        if self._pinned is not None:
-            from . import _lib
-            self.buf = np.empty(0, dtype=np.uint8)          # drop the view before the memory goes away
-            _lib.lib().kmm_host_free(self._pinned)
-            self._pinned = None
+        self.buf = np.empty(0, dtype=np.uint8)              # drop the view before the memory goes away
+        _free_host_buffers([self._pinned])
+        self._pinned = None
 
 
 class MmapChunker:
@@ -711,8 +743,8 @@ class PrefetchingRawChunker:
     PCIe, record parser, map kernels) works on one chunk, the next one is read — and, for .gz input, inflated by the
     native reader's threads — into the other buffer.  The unused tail of a chunk (at most one record, as a rule) is
     copied in front of the next chunk's bytes, into head room kept for it; anything out of the ordinary (a record longer
-    than the head room, a consumer that used nothing) ends the prefetching and continues on one growing buffer exactly
-    as RawChunker does.  (`kmer_mapper map` on BGZF input: inflate and the GPU's share no longer take turns.)"""
+    than the head room, a consumer that used nothing) ends the prefetching, and a RawChunker over the same stream reads the
+    rest.  (`kmer_mapper map` on BGZF input: inflate and the GPU's share no longer take turns.)"""
 
     HEAD = 4 << 20
 
@@ -720,19 +752,11 @@ class PrefetchingRawChunker:
         import threading
         self.f = _open(path)
         self.chunk_size = int(chunk_size)
-        self._pinned = []
-        self._bufs = []
-        n = self.HEAD + self.chunk_size + (1 << 20)
+        self._bufs, self._pinned = [], []
         for _ in range(2):
-            if pinned:
-                import ctypes
-                from . import _lib
-                p = ctypes.c_void_p()
-                _lib.check(_lib.lib().kmm_host_alloc(n, ctypes.byref(p)))
-                self._pinned.append(p)
-                self._bufs.append(np.frombuffer((ctypes.c_uint8 * n).from_address(p.value), dtype=np.uint8))
-            else:
-                self._bufs.append(np.empty(n, dtype=np.uint8))
+            buf, p = _host_buffer(self.HEAD + self.chunk_size + (1 << 20), pinned)
+            self._bufs.append(buf)
+            self._pinned.append(p)
         self.left = None
         if byte_range is not None:
             self.f.seek(byte_range[0])
@@ -745,7 +769,7 @@ class PrefetchingRawChunker:
         self._next_fill = 0              # bytes the reader put into the other buffer
         self._next_eof = False
         self._carry = 0                  # carried-over bytes in front of the other buffer's data
-        self._fallback = None            # a plain RawChunker-like state once prefetching has ended
+        self._fallback = None            # the RawChunker that reads the rest once prefetching has ended
         self._err = None
         self._lock = threading.Lock()
         self._thread = None
@@ -790,7 +814,10 @@ class PrefetchingRawChunker:
     def next_chunk(self):
         """Returns a uint8 view (valid until the next call) or None at end of input."""
         if self._fallback is not None:
-            return self._fb_next()
+            self._fallback.chunk_size = self.chunk_size  # (the consumer may have asked for longer chunks)
+            buf = self._fallback.next_chunk()
+            self.eof = self._fallback.eof
+            return buf
         if self._handed:                                 # asked again without consumed(): the consumer could not use
             self._handed = False                         # the chunk (a record longer than it) and wants a longer one
             return self._to_fallback_and_next()
@@ -815,7 +842,7 @@ class PrefetchingRawChunker:
 
     def consumed(self, n):
         if self._fallback is not None:
-            return self._fb_consumed(n)
+            return self._fallback.consumed(n)
         self._handed = False
         rest = (self._end - self._start) - n
         if self.eof:                                     # nothing more will come: the rest stays in this buffer
@@ -837,51 +864,16 @@ class PrefetchingRawChunker:
         if not self.eof:
             self._start_read(1 - self._cur)
 
-    # --- fallback: everything that is left, on one growing pageable buffer (RawChunker's loop)
+    # --- fallback: everything that is left, RawChunker's loop on one growing pageable buffer
     def _to_fallback(self):
         self._join()
         cur = self._bufs[self._cur][self._start:self._end]
         nxt = self._bufs[1 - self._cur][self.HEAD:self.HEAD + self._next_fill] if not self.eof else cur[:0]
-        buf = np.empty(max(2 * (len(cur) + len(nxt)), self.chunk_size + (1 << 20)), dtype=np.uint8)
-        buf[:len(cur)] = cur
-        buf[len(cur):len(cur) + len(nxt)] = nxt
-        self._fallback = {"buf": buf, "fill": len(cur) + len(nxt)}
-        self.eof = self._src_eof
+        self._fallback = RawChunker.over_stream(self.f, self.chunk_size, self.left, np.concatenate([cur, nxt]))
 
     def _to_fallback_and_next(self):
         self._to_fallback()
-        return self._fb_next()
-
-    def _fb_next(self):
-        st = self._fallback
-        if self.eof and st["fill"] == 0:
-            return None
-        if st["fill"] == st["buf"].shape[0]:
-            st["buf"] = np.concatenate([st["buf"], np.empty_like(st["buf"])])
-        while not self.eof and st["fill"] < min(self.chunk_size, st["buf"].shape[0]):
-            want = memoryview(st["buf"])[st["fill"]:]
-            if self.left is not None:
-                want = want[:min(len(want), self.left)]
-            got = self.f.readinto(want) if len(want) else 0
-            if self.left is not None:
-                self.left -= got or 0
-            if not got:
-                self.eof = True
-                if st["fill"] and st["buf"][st["fill"] - 1] != _NL:
-                    if st["fill"] == st["buf"].shape[0]:
-                        st["buf"] = np.concatenate([st["buf"], np.empty(16, np.uint8)])
-                    st["buf"][st["fill"]] = _NL
-                    st["fill"] += 1
-                break
-            st["fill"] += got
-        return st["buf"][:st["fill"]] if st["fill"] else None
-
-    def _fb_consumed(self, n):
-        st = self._fallback
-        rest = st["fill"] - n
-        if rest:
-            st["buf"][:rest] = st["buf"][n:st["fill"]]
-        st["fill"] = rest
+        return self.next_chunk()
 
     def close(self):
         try:
@@ -889,9 +881,6 @@ class PrefetchingRawChunker:
         except BaseException:            # noqa: BLE001 - closing: the consumer's error (if any) is the one to report
             pass
         self.f.close()
-        if self._pinned:
-            from . import _lib
-            self._bufs = []
-            for p in self._pinned:
-                _lib.lib().kmm_host_free(p)
-            self._pinned = []
+        self._bufs = []
+        _free_host_buffers(self._pinned)
+        self._pinned = []

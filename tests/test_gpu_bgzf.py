@@ -292,3 +292,31 @@ def test_cli_maps_a_bgzf_file_through_the_gpu_inflater(kmm, syn, oracle, tmp_pat
     assert "BGZF members inflated on the GPU" in caplog.text
     monkeypatch.setenv("KMM_CLI_NO_GPU_INFLATE", "1")
     assert np.array_equal(map_bnp(ns), expect)
+
+
+def test_cli_maps_bgzf_with_bc_behind_another_subfield_on_the_gpu(kmm, syn, oracle, tmp_path, caplog):
+    """Members whose extra field carries another subfield in front of BC (SAM specification 4.1 asks for BC among them, not
+    first): the CLI's probe calls the file BGZF, the members are inflated on the GPU, and the counts are the oracle's."""
+    import argparse
+    import logging
+    from kmer_mapper_amd.command_line_interface import map_bnp
+    index, genome = syn.make_index(8000, seed=741)
+    mx = index.max_node_id()
+    bases, offs = syn.make_ragged_reads(genome, 8000, 20, 200, seed=742)
+    reads = [bases[offs[i]:offs[i + 1]].tobytes() for i in range(len(offs) - 1)]
+    expect, _ = oracle.map_reads(index, mx, bases, offs, 31, n_threads=4)
+    raw = _fastq(reads, np.random.default_rng(6))
+    members = []
+    for p in range(0, len(raw), 0xFF00):
+        m = _member(raw[p:p + 0xFF00])           # XLEN 6 -> 12: "XY" with 2 bytes of data, then BC
+        members.append(m[:10] + struct.pack("<H", 12) + b"XY\x02\x00ab" + m[12:16] + struct.pack("<H", struct.unpack_from("<H", m, 16)[0] + 6)
+                       + m[18:])
+    path = str(tmp_path / "reads.fq.gz")
+    open(path, "wb").write(b"".join(members) + _EOF)
+    ns = argparse.Namespace(kmer_index=index, index_bundle=None, reads=path, kmer_size=31, n_threads=8, chunk_size=400_000,
+                            output_file=None, debug=None, max_hits_per_kmer=1000, gpu=True, gpu_hash_map_size=0,
+                            map_reverse_complements=False)
+    with caplog.at_level(logging.INFO):
+        got = map_bnp(ns)
+    assert "BGZF members inflated on the GPU" in caplog.text
+    assert np.array_equal(got, expect)

@@ -83,6 +83,57 @@ def test_cli_routes_reach_the_device_and_fail_there_without_a_gpu(tmp_path, name
         map_bnp(ns)
 
 
+def test_cli_route_table():
+    """command_line_interface.choose_route: one row of map_gpu_raw's route table per case, every KMM_CLI_* switch toggled.
+    Compressed = the host reader's .gz name rule (probe.inflate); BGZF / plain gzip from the file's first bytes."""
+    from kmer_mapper_amd.command_line_interface import choose_route
+    from kmer_mapper_amd.reads_io import InputProbe
+
+    def route(fmt, inflate=False, container=None, world_size=1, n_threads=16, has_device=True, **env):
+        probe = InputProbe("fasta" if fmt == "fasta_ml" else fmt, fmt != "fasta_ml", inflate, container)
+        return choose_route(fmt, probe, world_size, n_threads, has_device, env={"KMM_CLI_" + k: v for k, v in env.items()})
+
+    plain = ("fastq", "fasta", "fasta_ml", "sam")
+    # BAM: its own route, whatever its name or the switches
+    for inflate in (False, True):
+        assert route("bam", inflate, "bgzf") == ("bam", False, False)
+        assert route("bam", inflate, "bgzf", NO_GPU_INFLATE="1", NO_PREFETCH="1") == ("bam", False, False)
+    # compressed BGZF FASTQ / two-line FASTA / SAM: members inflated on the GPU, any number of ranks
+    for fmt in ("fastq", "fasta", "sam"):
+        for world in (1, 4):
+            assert route(fmt, True, "bgzf", world_size=world) == ("bgzf", False, False)
+            assert route(fmt, True, "bgzf", world_size=world, GPU_GUNZIP="1") == ("bgzf", False, False)
+        assert route(fmt, True, "bgzf", NO_GPU_INFLATE="1") == ("prefetch", False, False)
+    assert route("fasta_ml", True, "bgzf") == ("prefetch", False, False)
+    # compressed plain gzip, one rank: on the GPU only with KMM_CLI_GPU_GUNZIP set and not 0
+    for fmt in ("fastq", "fasta", "sam"):
+        assert route(fmt, True, "gzip", GPU_GUNZIP="1") == ("gzip", False, False)
+        assert route(fmt, True, "gzip") == ("prefetch", False, False)
+        assert route(fmt, True, "gzip", GPU_GUNZIP="0") == ("prefetch", False, False)
+        assert route(fmt, True, "gzip", GPU_GUNZIP="") == ("prefetch", False, False)
+        assert route(fmt, True, "gzip", GPU_GUNZIP="1", NO_GPU_INFLATE="1") == ("prefetch", False, False)
+        assert route(fmt, True, "gzip", world_size=2, GPU_GUNZIP="1") == ("prefetch", False, False)
+    assert route("fasta_ml", True, "gzip", GPU_GUNZIP="1") == ("prefetch", False, False)
+    # plain FASTQ / two-line FASTA, host packing, a device: views of the file mapping
+    for fmt in ("fastq", "fasta"):
+        for world in (1, 4):
+            assert route(fmt, world_size=world) == ("mmap", True, True)
+        assert route(fmt, NO_POPULATE="1") == ("mmap", False, True)
+        assert route(fmt, NO_PACKER_STEERING="1") == ("mmap", True, False)
+        assert route(fmt, NO_MMAP="1") == ("raw", False, False)
+        assert route(fmt, n_threads=1) == ("raw", False, False)
+        assert route(fmt, has_device=False) == ("raw", False, False)
+    # any other compressed input: the prefetching reader, unless switched off; everything else: one pinned buffer
+    for fmt in plain:
+        for container in ("gzip", None):
+            assert route(fmt, True, container, world_size=2) == ("prefetch", False, False)
+            assert route(fmt, True, container, world_size=2, NO_PREFETCH="1") == ("raw", False, False)
+        assert route(fmt, True, "bgzf", NO_GPU_INFLATE="1", NO_PREFETCH="1") == ("raw", False, False)
+    for fmt in ("fasta_ml", "sam"):
+        assert route(fmt) == ("raw", False, False)
+        assert route(fmt, container="gzip") == ("raw", False, False)      # (the name decides what the host inflates)
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "kmer_mapper_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -428,12 +428,17 @@ def test_native_reader_equals_python_reader_on_every_kind_of_file(tmp_path):
     assert r.stdout == data
 
 
-@pytest.mark.parametrize("chunk_size", [500, 4096, 100_000, 10_000_000])
+class _NoHeadRoom(reads_io.PrefetchingRawChunker):
+    HEAD = 0        # any unused tail is longer than the head room: the first such chunk hands the rest to the RawChunker fallback
+
+
+@pytest.mark.parametrize("chunk_size", [500, 4096, 100_000, 500_000, 10_000_000])
 @pytest.mark.parametrize("trailing_newline", [True, False])
 def test_prefetching_chunker_hands_out_the_same_records_as_the_plain_one(tmp_path, chunk_size, trailing_newline):
     """PrefetchingRawChunker (two buffers + a reader thread, what `kmer_mapper map` feeds the GPU parser from) and
     RawChunker cut by the same consumer give the same byte stream: ordinary chunks, records longer than a chunk (the
-    consumer uses nothing and asks again), a last line without its newline."""
+    consumer uses nothing and asks again), a last line without its newline — also once prefetching has ended and its
+    fallback reads the rest (_NoHeadRoom; chunk_size 500_000: the reader has already seen the end of the file then)."""
     rng = np.random.default_rng(5)
     recs = []
     for i in range(2000):
@@ -443,7 +448,7 @@ def test_prefetching_chunker_hands_out_the_same_records_as_the_plain_one(tmp_pat
     data = b"".join(recs)
     path = tmp_path / "x.fq"
     path.write_bytes(data if trailing_newline else data[:-1])
-    for cls in (reads_io.RawChunker, reads_io.PrefetchingRawChunker):
+    for cls in (reads_io.RawChunker, reads_io.PrefetchingRawChunker, _NoHeadRoom):
         ch = cls(str(path), chunk_size)
         out, calls = [], 0
         try:
@@ -460,9 +465,70 @@ def test_prefetching_chunker_hands_out_the_same_records_as_the_plain_one(tmp_pat
                     continue
                 out.append(bytes(b[:used]))
                 ch.consumed(used)
+            if cls is _NoHeadRoom and chunk_size < len(data):
+                assert isinstance(ch._fallback, reads_io.RawChunker)
         finally:
             ch.close()
         assert b"".join(out) == data, cls.__name__
+
+
+def _bgzf_bc_second(data, block=20_000):
+    """`data` as BGZF members whose extra field carries another subfield ("XY", 2 bytes) IN FRONT of BC, and the EOF member."""
+    out = []
+    for p in range(0, len(data), block):
+        chunk = data[p:p + block]
+        c = zlib.compressobj(6, zlib.DEFLATED, -15)
+        payload = c.compress(chunk) + c.flush()
+        out.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff" + struct.pack("<H", 12) + b"XY\x02\x00ab" + b"BC\x02\x00"
+                   + struct.pack("<H", 24 + len(payload) + 8 - 1) + payload + struct.pack("<II", zlib.crc32(chunk), len(chunk)))
+    return b"".join(out) + reads_io.BGZF_EOF
+
+
+def test_a_bgzf_member_with_bc_behind_another_subfield_is_bgzf_everywhere(tmp_path):
+    """SAM specification 4.1 asks for BC among the extra subfields, not first.  The one header parser (gz_io.bgzf_member_size,
+    the device's rule) finds it behind another subfield: the probe calls such a file BGZF (the GPU inflater's route), and the
+    pure-Python and native readers, the rank ranges' member walk and the host parser read the plain file's reads from it."""
+    from kmer_mapper_amd import _io, bgzf_ranges, gz_io
+    from kmer_mapper_amd.command_line_interface import choose_route
+    rng = np.random.default_rng(31)
+    plain = str(tmp_path / "t.fq")
+    _random_fastq(plain, 3000, rng)
+    data = open(plain, "rb").read()
+    path = str(tmp_path / "t.fq.gz")
+    comp = _bgzf_bc_second(data)
+    open(path, "wb").write(comp)
+    first = gz_io.bgzf_member_size(comp)
+    assert first == struct.unpack_from("<H", comp, 22)[0] + 1 and comp[first:first + 4] == gz_io.BGZF_MAGIC
+    assert gz_io.is_bgzf(path)
+    probe = reads_io.probe_input(path)
+    assert probe == reads_io.InputProbe("fastq", True, True, "bgzf")
+    assert choose_route("fastq", probe, 1, 16, True, env={})[0] == "bgzf"
+    assert len(bgzf_ranges.member_chain(comp)) == -(-len(data) // 20_000) + 2
+    _io.build()
+    for native in (False, True):
+        with gz_io.open_gz(path, 4, native=native) as s:
+            assert s.read() == data, native
+    got = np.concatenate([c.bases for c in reads_io.read_chunks(path, 50_000)])
+    assert np.array_equal(got, np.concatenate([c.bases for c in reads_io.read_chunks(plain, 50_000)]))
+
+
+def test_probe_input_tells_format_name_rule_and_container(tmp_path, ragged):
+    """probe_input: the sniffed format, the host reader's .gz name rule and the container the first bytes show, each once."""
+    import gzip
+    from kmer_mapper_amd import gz_io
+    P = reads_io.InputProbe
+    fq = str(tmp_path / "a.fq")
+    reads_io.write_fastq(fq, ragged)
+    data = open(fq, "rb").read()
+    gz_io.write_bgzf(str(tmp_path / "b.fq.gz"), data)
+    open(str(tmp_path / "g.fq.gz"), "wb").write(gzip.compress(data))
+    reads_io.write_bam(str(tmp_path / "r.bam"), ragged)
+    reads_io.write_fasta(str(tmp_path / "m.fa.gz"), ragged, gz=True, line_width=50)
+    assert reads_io.probe_input(fq) == P("fastq", True, False, None)
+    assert reads_io.probe_input(str(tmp_path / "b.fq.gz")) == P("fastq", True, True, "bgzf")
+    assert reads_io.probe_input(str(tmp_path / "g.fq.gz")) == P("fastq", True, True, "gzip")
+    assert reads_io.probe_input(str(tmp_path / "r.bam")) == P("bam", True, False, "bgzf")
+    assert reads_io.probe_input(str(tmp_path / "m.fa.gz")) == P("fasta", False, True, "gzip")
 
 
 def test_prefetching_chunker_reports_a_truncated_gz_in_the_consumers_thread(tmp_path):
