@@ -48,7 +48,10 @@
 // Nothing depends on partition sizes being balanced: block areas and items are exact, a run that is longer
 // than expected is just a longer contiguous copy, a partition with many items is probed by several work
 // items.  Buckets whose entries lie beyond the slice's LDS key capacity (RX_ECAP entries per fine partition)
-// are walked in HBM instead, so results never depend on the layout.
+// are walked in HBM instead, so results never depend on the layout.  (Held to that by tests/test_gpu_radix_skew.py on the
+// batches of tests/skew_cases.py: one k-mer 12 M times, 99 % poly-A beside cold partitions whose items span 9000 blocks,
+// tandem repeats, sorted hashes, one bucket, one slice, the last partition — 391 coarse partitions of which one holds
+// (nearly) everything.  What such batches cost pass 3: profiles/skew/README.md.)
 // ------------------------------------------------------------------------------------------------
 constexpr int RX_NT = 512;            // threads per workgroup of the three passes
 constexpr int RX_B = 8192;            // positions per pass-1 block = k-mer capacity of a block area / item: each
