@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "kmm.h"
+#include "kmm_radix_plan.hpp" // (plain C++ with standard headers of its own: before the namespace the kernels live in)
 
 namespace {
 
@@ -315,14 +316,14 @@ struct kmm_index : IndexStreams, RxArrays {
     int path = 0;         // 0 auto, 1 direct, 2 radix
     int grid_per_cu = 64; // upper bound on workgroups per CU of the grid-stride fused kernel
     bool rx_ok = false;   // the index fits the radix path's fan-out (<= 512 x 512 fine partitions)
-    int rx_w = 12, rx_f2 = 0; // log2 buckets per fine partition, log2 fine partitions per coarse one
-    uint32_t rx_PF = 1, rx_F1 = 1, rx_F2 = 1;
+    RxGeometry rx_geo;    // slice width and fan-out (kmm_radix_plan.hpp); assigned whole, a refused configuration leaves it as it was
+    bool rx_no_mid = false; // experiments (KMM_RX_NO_MID, read at creation): pass 3 without its 4608-key variants
     bool rx_flush_sorted = true; // "radix_sorted_flush": use the node-ordered entry list for the flush
     uint32_t rx_max_slice = 0; // most entries in one fine partition's slice (for the current part_shift)
     bool rx_fits_small = false, rx_fits_mid = false; // all but one slice in 1000 hold at most RX_ECAP / RX_ECAP_MID entries
     int rx_grid_per_cu = 2;   // persistent workgroups of passes 2 and 3 per CU (1: leave room for another stream's kernels)
     int64_t rx_min_units = 0; // auto: batches of at least this many positions / k-mers take the radix path
-    int64_t rx_sub_cap = ((int64_t)1 << 32) - 2 * RX_B; // k-mer slots per sub-batch of the radix path ("radix_sub_batch_kmers")
+    int64_t rx_sub_cap = RX_SUB_CAP_MAX; // k-mer slots per sub-batch of the radix path ("radix_sub_batch_kmers")
     int64_t rx_sub_cap_eff = 0;  // > 0: the smaller size an out-of-memory call settled on, tried first by the next calls
     int rx_sub_cap_eff_age = 0;  // calls since then (at 16 the caller's cap is tried again)
     int64_t rx_sub_cap_last = 0; // the size the last radix call ran with ("radix_sub_batch_kmers_effective")
@@ -384,7 +385,6 @@ struct kmm_index : IndexStreams, RxArrays {
     int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
     int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
-    int rx_occ_shift = 0;         // k_rx_p2f folds 2^rx_occ_shift buckets into one bit of its LDS bitmap
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
     bool rx_packed = true;        // "radix_packed_tiles": pass 1 on reads of one length takes tiles of whole reads
     bool ecnt_dirty = false;  // rx_ecnt holds hits that are not in `counts` yet
@@ -461,41 +461,10 @@ struct ScopedTimer {
     }
 };
 
-int rx_flush(kmm_index *ix);
+int rx_flush(kmm_index *ix); // (kmm_radix_host.hpp)
+int rx_check_conservation(kmm_index *ix);
 int ensure_direct(kmm_index *ix);
 constexpr size_t KMM_STAT_BYTES = (size_t)KMM_STAT_SHARDS * KMM_STAT_STRIDE * 8;
-
-// Self-check of the radix path at every synchronising call: every k-mer pass 1 emitted must have been gathered by
-// pass 2 and probed by pass 3 (or dropped by pass 2's empty-bucket filter).  The three passes count independently
-// (per-lane registers -> one sharded atomic per wavefront at kernel end), so a work item that is handed out twice, skipped, or
-// seen differently by the wavefronts of one workgroup (the round-2 race) shows up here instead of as
-// silently wrong counts.  Called with both streams drained.
-int rx_check_conservation(kmm_index *ix)
-{
-    if (!ix->rx_unchecked)
-        return KMM_OK;
-    ix->rx_unchecked = false;
-    static thread_local std::vector<unsigned long long> st;
-    st.resize(KMM_STAT_BYTES / 8);
-    HIPCHK(hipMemcpy(st.data(), ix->stats, KMM_STAT_BYTES, hipMemcpyDeviceToHost));
-    unsigned long long p1 = 0, p2 = 0, p3 = 0, dropped = 0;
-    for (int i = 0; i < KMM_STAT_SHARDS; ++i) {
-        const unsigned long long *sh = st.data() + (size_t)i * KMM_STAT_STRIDE;
-        p1 += sh[KMM_STAT_RX_P1];
-        p2 += sh[2];
-        p3 += sh[3];
-        dropped += sh[KMM_STAT_RX_DROPPED];
-    }
-    if (p1 == p2 && p2 == p3 + dropped)
-        return KMM_OK;
-    const int rc = fail(KMM_ERR_INTERNAL, "radix path self-check failed: pass 1 emitted %llu k-mers, pass 2 gathered %llu, "
-                        "pass 3 probed %llu (+ %llu dropped as absent) since the counters were last reset: the node counts "
-                        "are invalid until kmm_reset_counts [latest map call #%llu on this handle]",
-                        p1, p2, p3, dropped, (unsigned long long)ix->map_calls);
-    ix->sticky_rc = rc;
-    ix->sticky_msg = g_err;
-    return rc;
-}
 
 // Drain the streams and surface deferred device-side errors (invalid bases, malformed records, bad offsets).
 // The reference raises before any count of the offending chunk is added (bionumpy's encoder, util.py:72); here
@@ -633,291 +602,33 @@ constexpr size_t KMM_OCC_SWEET_BYTES = (size_t)5 << 20; // bitmap size that stil
 constexpr int TILE_S = 4;
 constexpr int TILE_T = 256 * TILE_S;
 
-// Fan-out of the radix path for 2^w buckets per fine partition: F1 coarse x F2 fine partitions, each at most `maxf`
-// (<= RX_MAXF = 512: 512 x 512 slices of 8192 buckets cover every modulo the index format's int32 tables allow,
-// mapper.pyx:22-23,31-32).  f2_force >= 0 (experiments, KMM_RX_F2): that many fine-partition bits.
-bool rx_configure(kmm_index *ix, int w, int maxf = RX_MAXF, int f2_force = -1)
+// Exclusive scan of n uint32 values on the device (in -> out): 1024-wide block scans, recursing on the
+// block totals (n < 2^32 needs at most 4 levels).  All launches go to `stream`; ensure() may hipFree (device-wide sync).  `scratch` holds one DevBuf pair per level and is sized
+// by the caller ONCE — it must not reallocate while outer levels hold references into it.
+constexpr size_t SCAN_MAX_LEVELS = 8;
+int scan_exclusive(const uint32_t *in, uint32_t *out, uint64_t n, std::vector<DevBuf> &scratch,
+                   size_t level, hipStream_t stream)
 {
-    if (w < 0 || w > 13 || ix->modulo >= (1ull << 31)) // (pass 1 divides with a 32-bit remainder)
-        return false;
-    const uint64_t PF = (ix->modulo + (1ull << w) - 1) >> w;
-    if (PF > (uint64_t)maxf * maxf)
-        return false;
-    int lg = 0;
-    while ((1ull << lg) < PF)
-        ++lg;
-    int f2 = (lg + 1) / 2;
-    bool for_filter = false;
-    int occ_shift = 0;
-    // pass 2's empty-bucket filter has 2^19 bits of LDS per coarse partition: take fewer fine-partition bits — more,
-    // smaller coarse partitions — when pass 1's fan-out stays within 512; tables too large for that at one bit per
-    // bucket get one bit per 2 or 4 buckets (sparse tables such as modulo 452 930 477 with 1e8 entries still lose
-    // half of their k-mers there; at load factor 0.5 a bit per 4 buckets would pass 86 %: not taken)
-    if (ix->rx_filter && w + f2 > P2F_LOGBITS) {
-        const double load = ix->rx_S ? (double)ix->rx_S / (double)ix->modulo : 0.5;
-        for (int gs = 0; gs <= 2 && !for_filter; ++gs) {
-            const int fb = P2F_LOGBITS + gs - w;
-            if (fb < 0 || load * (double)(1 << gs) > 0.75)
-                continue;
-            if (((PF + (1ull << fb) - 1) >> fb) <= (uint64_t)RX_MAXF && fb <= 9) {
-                f2 = fb;
-                occ_shift = gs;
-                for_filter = true;
-            }
-        }
-    }
-    if (f2_force >= 0) {
-        f2 = f2_force;
-        occ_shift = w + f2 > P2F_LOGBITS ? w + f2 - P2F_LOGBITS : 0; // (rx_filter_active refuses more than 2)
-    }
-    // the packed form (kmm_radix.hpp) keeps floor(q / modulo) above w + f2 hash bits: it must fit for EVERY
-    // 64-bit q (callers may hand over arbitrary uint64 values), else give the quotient more room
-    const uint64_t max_quo = ~0ull / ix->modulo;
-    auto fits = [&](int sh) { return sh == 0 || (sh < 64 && (max_quo >> (64 - sh)) == 0); };
-    while (f2 > 0 && !fits(w + f2))
-        --f2;
-    if (!fits(w + f2))
-        return false;
-    const uint64_t F2 = 1ull << f2, F1 = (PF + F2 - 1) / F2;
-    if (F2 > (uint64_t)maxf || F1 > (uint64_t)(for_filter ? RX_MAXF : maxf))
-        return false;
-    ix->rx_w = w;
-    ix->rx_f2 = f2;
-    ix->rx_occ_shift = w + f2 > P2F_LOGBITS ? w + f2 - P2F_LOGBITS : 0; // (the filter's bits never outnumber its LDS)
-    (void)occ_shift;
-    ix->rx_PF = (uint32_t)PF;
-    ix->rx_F1 = (uint32_t)F1;
-    ix->rx_F2 = (uint32_t)F2;
-    return true;
-}
-
-// Pass 2 filters k-mers of empty buckets (k_rx_p2f) when a coarse partition's bitmap fits its 64 KB of LDS and its
-// first bucket starts a bitmap word.
-bool rx_filter_active(const kmm_index *ix)
-{
-    const int sh = ix->rx_w + ix->rx_f2;
-    return ix->rx_filter && ix->rx_occ && sh - ix->rx_occ_shift >= 5 && ix->rx_occ_shift <= 2;
-}
-
-bool use_radix(const kmm_index *ix, int64_t units)
-{
-    if (!ix->rx_ok || ix->path == 1)
-        return false;
-    return ix->path == 2 || ix->rx_ecnt_acc || units >= ix->rx_min_units;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// One sub-batch of the radix path: pass 1 (reads or k-mers -> blocks sorted by coarse partition), the
-// directory scan, pass 2 (items sorted by fine partition), pass 3 (LDS probe).  Hits land in rx_ecnt.
-template <int MODE>
-int launch_rx(kmm_index *ix, const ReadsView &rv, const uint64_t *kmers_in, int64_t n_in, int k, int max_freq,
-              int also_rc)
-{
-    const IndexView iv = view_of(ix);
-    const int64_t units = MODE == MODE_KMERS ? n_in : rv.total;
-    // blocks of pass 1: 8192 positions, or (packed tiles) the reads of two tiles
-    const int64_t n_src_total = MODE == MODE_PACKED ? (rv.n_reads + 2 * (int64_t)rv.pk_rpt - 1) / (2 * (int64_t)rv.pk_rpt)
-                                                    : (units + RX_B - 1) / RX_B;
-    const uint32_t X = also_rc ? 2u : 1u;
-    const uint32_t F1 = ix->rx_F1, F2 = ix->rx_F2;
-    // Sub-batches.  Every sub-batch streams the index slices once (pass 3) and pays the per-work-item costs once, so they
-    // are as large as the 32-bit prefixes allow: a coarse partition's k-mers are numbered with 32 bits and in the worst
-    // case (one k-mer repeated) ALL of a sub-batch's k-mers fall into one coarse partition, hence fewer than 2^32 k-mer
-    // slots per sub-batch (r03: 2^31; the 1 B-k-mer index streamed its 14 GB of slices twice per 28 M-read batch).  Every
-    // other offset is 64-bit or relative (to a table's first block, to a work item's first item).  Without the HBM for
-    // the buffers of that size the call takes one sub-batch more, and again, down to 2^28 slots per sub-batch; the handle
-    // remembers the size that fitted ("radix_sub_batch_kmers_effective") for its next 15 calls and then tries the caller's
-    // cap again — an allocation that failed because something else held the memory for a moment does not shrink the handle's
-    // sub-batches for good (round 4 halved "radix_sub_batch_kmers" itself: four failing rounds for a 2^29-slot batch, for ever).
-    // Sub-batches of equal size: no small last one.
-    int64_t n_sub = 1, max_src = 0;
-    static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
-    const auto t_0 = std::chrono::steady_clock::now();
-    if (ix->rx_sub_cap_eff > 0 && ++ix->rx_sub_cap_eff_age >= 16)
-        ix->rx_sub_cap_eff = 0;
-    int64_t cap = ix->rx_sub_cap_eff > 0 && ix->rx_sub_cap_eff < ix->rx_sub_cap ? ix->rx_sub_cap_eff : ix->rx_sub_cap;
-    for (;;) {
-        const int64_t cap_src = (cap / RX_B) / X > 0 ? (cap / RX_B) / X : 1;
-        n_sub = (n_src_total + cap_src - 1) / cap_src;
-        max_src = n_sub ? (n_src_total + n_sub - 1) / n_sub : cap_src;
-        const size_t NBm = (size_t)max_src * X, chunks_m = (NBm + RX_CH - 1) / RX_CH, items_m = NBm + F1 + 1;
-        const size_t meta = align256(NBm * (F1 + 1) * 2) + align256((size_t)F1 * (NBm + 1) * 4) + align256((size_t)F1 * NBm * 2) +
-                            align256(chunks_m * F1 * 4) + 3 * align256((size_t)(F1 + 1) * 4) + align256(items_m * 8) +
-                            align256(items_m * (F2 + 1) * 2) + align256(items_m * (F2 + 1) * 2 + 256) + align256(64) + align256(2048);
-        int rc = ix->dbg_rx_buf_limit && NBm * RX_B * 8 > (size_t)ix->dbg_rx_buf_limit ? (int)KMM_ERR_NOMEM // (test hook)
-                                                                                         : ensure(ix->rx_meta, meta);
-        if (rc == KMM_OK)
-            rc = ensure(ix->rx_buf1, NBm * RX_B * 8);
-        if (rc == KMM_OK)
-            rc = ensure(ix->rx_buf2, items_m * RX_B * 8);
-        if (rc == KMM_OK)
-            break;
-        if (rc != KMM_ERR_NOMEM || cap <= ((int64_t)1 << 28) || n_src_total <= 1)
-            return rc;
-        (void)hipGetLastError();
-        (void)ix->rx_buf1.reset();
-        (void)ix->rx_buf2.reset();
-        // the next size that really is smaller: one sub-batch more than this attempt had
-        const int64_t next_src = (n_src_total + n_sub) / (n_sub + 1);
-        cap = next_src * RX_B * X;
-        if (cap < ((int64_t)1 << 28))
-            cap = (int64_t)1 << 28;
-        ix->rx_sub_cap_eff = cap;
-        ix->rx_sub_cap_eff_age = 0;
-    }
-    ix->rx_sub_cap_last = cap;
-    const double ms_buffers = ms_since(t_0);
-    for (int64_t s0 = 0; s0 < n_src_total; s0 += max_src) {
-        const uint32_t n_src = (uint32_t)(n_src_total - s0 < max_src ? n_src_total - s0 : max_src);
-        const uint32_t NB = n_src * X;
-        const uint32_t chunks = (NB + RX_CH - 1) / RX_CH;
-        const size_t max_items = (size_t)NB + F1 + 1;
-        RxView rx;
-        memset(&rx, 0, sizeof rx);
-        rx.pstart = ix->rx_pstart; rx.pkeys = ix->rx_pkeys; rx.pfreq = ix->rx_pfreq; rx.ecnt = ix->rx_ecnt;
-        rx.pstart16 = ix->rx_pstart16; rx.slice_e0 = ix->rx_slice_e0; rx.slice_fmax = ix->rx_slice_fmax;
-        rx.occ = ix->rx_occ;
-        rx.occ_shift = rx_filter_active(ix) ? ix->rx_occ_shift : 3; // (3: k_rx_p2f without its filter)
-        rx.p2f_k = NB / 2048u < 4u ? 4u : (NB / 2048u > (uint32_t)P2F_KMAX ? (uint32_t)P2F_KMAX : NB / 2048u);
-        rx.w = ix->rx_w; rx.f2 = ix->rx_f2; rx.PF = ix->rx_PF; rx.F1 = F1; rx.F2 = F2;
-        rx.NB = NB; rx.max_items = (uint32_t)max_items;
-        size_t off = 0;
-        auto carve = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
-        const size_t o_start1 = carve((size_t)NB * (F1 + 1) * 2), o_P1T = carve((size_t)F1 * (NB + 1) * 4),
-                     o_S1T = carve((size_t)F1 * NB * 2), o_csum = carve((size_t)chunks * F1 * 4),
-                     o_T1 = carve((size_t)F1 * 4), o_ib = carve((size_t)(F1 + 1) * 4), o_wb = carve((size_t)(F1 + 1) * 4),
-                     o_desc = carve(max_items * 8), o_start2 = carve(max_items * (F2 + 1) * 2), o_start2T = carve(max_items * (F2 + 1) * 2 + 256),
-                     o_ctrl = carve(64),
-                     o_queue = carve(2048);
-        KMMCHK(ensure(ix->rx_meta, off));
-        KMMCHK(ensure(ix->rx_buf1, (size_t)NB * RX_B * 8));
-        KMMCHK(ensure(ix->rx_buf2, max_items * RX_B * 8));
-        uint8_t *m = (uint8_t *)ix->rx_meta.p;
-        rx.start1 = (uint16_t *)(m + o_start1); rx.P1T = (uint32_t *)(m + o_P1T); rx.S1T = (uint16_t *)(m + o_S1T);
-        rx.csum = (uint32_t *)(m + o_csum); rx.T1 = (uint32_t *)(m + o_T1); rx.item_base = (uint32_t *)(m + o_ib);
-        rx.work_base = (uint32_t *)(m + o_wb); rx.item_desc = (uint2 *)(m + o_desc);
-        rx.start2 = (uint16_t *)(m + o_start2); rx.start2T = (uint16_t *)(m + o_start2T);
-        rx.ctrl = (uint32_t *)(m + o_ctrl);
-        rx.queue = (unsigned long long *)(m + o_queue);
-        rx.buf1 = (uint64_t *)ix->rx_buf1.p;
-        rx.buf2 = (uint64_t *)ix->rx_buf2.p;
-#if RX_PROBE_ANY
-        KMMCHK(ensure(ix->rx_probe, max_items * RX_B * 8));
-        rx.probe = (uint64_t *)ix->rx_probe.p;
-#endif
-        ix->dbg_T1 = rx.T1; ix->dbg_item_base = rx.item_base; ix->dbg_start1 = rx.start1; ix->dbg_F1 = F1; ix->dbg_NB = NB;
-        HIPCHK(hipMemsetAsync(m + o_ctrl, 0, align256(64) + 2048, ix->stream));
-        ScopedTimer tm;
-        KMMCHK(tm.begin(ix, KMM_KERNEL_RX_P1));
-        static const int p1_per_cu = getenv("KMM_RX_P1_GRID_PER_CU") ? atoi(getenv("KMM_RX_P1_GRID_PER_CU")) : 8; // (experiments)
-        const int64_t g1cap = (int64_t)ix->n_cu * (p1_per_cu > 0 ? p1_per_cu : 8);
-        const dim3 g1((unsigned)(n_src < g1cap ? n_src : g1cap));
-        const int64_t tile0 = s0 * (RX_B / (MODE == MODE_RECORDS ? 1024 : 4096));
-        const uint64_t *src_kmers = kmers_in ? kmers_in + s0 * RX_B : nullptr;
-        constexpr bool CAN_C2 = MODE == MODE_PACKED || MODE == MODE_UNIFORM || MODE == MODE_GENERAL;
-        if (rv.codes2 && !CAN_C2)
-            return fail(KMM_ERR_INTERNAL, "2-bit code input reaches pass 1 through the flat-read modes only");
-        if constexpr (CAN_C2) {
-            if (rv.codes2 && also_rc)
-                hipLaunchKernelGGL((k_rx_p1<MODE, true, true>), g1, dim3(RX_NT), 0, ix->stream, rv, src_kmers, n_in - s0 * RX_B,
-                                   iv, rx, k, tile0, n_src);
-            else if (rv.codes2)
-                hipLaunchKernelGGL((k_rx_p1<MODE, false, true>), g1, dim3(RX_NT), 0, ix->stream, rv, src_kmers, n_in - s0 * RX_B,
-                                   iv, rx, k, tile0, n_src);
-        }
-        if (rv.codes2) {
-        } else if (also_rc)
-            hipLaunchKernelGGL((k_rx_p1<MODE, true>), g1, dim3(RX_NT), 0, ix->stream, rv, src_kmers, n_in - s0 * RX_B,
-                               iv, rx, k, tile0, n_src);
-        else
-            hipLaunchKernelGGL((k_rx_p1<MODE, false>), g1, dim3(RX_NT), 0, ix->stream, rv, src_kmers, n_in - s0 * RX_B,
-                               iv, rx, k, tile0, n_src);
-        HIPCHK(hipGetLastError());
-        KMMCHK(tm.end());
-        KMMCHK(tm.begin(ix, KMM_KERNEL_RX_SCAN));
-        hipLaunchKernelGGL(k_rx_colsum, dim3(chunks), dim3(256), 0, ix->stream, rx);
-        hipLaunchKernelGGL(k_rx_chunkscan, dim3(F1), dim3(256), 0, ix->stream, rx, chunks);
-        hipLaunchKernelGGL(k_rx_tables, dim3(1), dim3(512), 0, ix->stream, rx);
-        hipLaunchKernelGGL(k_rx_colscan, dim3(chunks, (F1 + 255) / 256), dim3(256), 0, ix->stream, rx);
-        HIPCHK(hipGetLastError());
-        KMMCHK(tm.end());
-        KMMCHK(tm.begin(ix, KMM_KERNEL_RX_P2));
-        if (ix->rx_filter) { // gather by k-mer; where a coarse partition's occupancy bitmap fits LDS (one bit per 1, 2 or 4
-                           // buckets) the k-mers of empty buckets are dropped here
-            const bool flt = rx_filter_active(ix), small = F2 <= 128;
-            auto kern = flt ? (small ? k_rx_p2f<true, true> : k_rx_p2f<true, false>)
-                            : (small ? k_rx_p2f<false, true> : k_rx_p2f<false, false>);
-            hipLaunchKernelGGL(kern, dim3(ix->n_cu), dim3(P2F_NT), 0, ix->stream, iv, rx);
-        } else {
-            hipLaunchKernelGGL(k_rx_p2, dim3(ix->n_cu * ix->rx_grid_per_cu), dim3(RX_NT), 0, ix->stream, iv, rx);
-        }
-        HIPCHK(hipGetLastError());
-        KMMCHK(tm.end());
-        KMMCHK(tm.begin(ix, KMM_KERNEL_RX_SCAN));
-        hipLaunchKernelGGL(k_rx_tr2, dim3((unsigned)((max_items + RX_TR2 - 1) / RX_TR2)), dim3(256), 0, ix->stream, rx);
-        HIPCHK(hipGetLastError());
-        KMMCHK(tm.end());
-        KMMCHK(tm.begin(ix, KMM_KERNEL_RX_P3));
-        const bool p16 = ix->rx_pstart16 != nullptr; // (implies: no slice beyond 65535 entries)
-        if (ix->rx_w > 12 && ix->rx_fits_small && p16)
-            // 8192-bucket slices whose entries all fit 4096 keys: 16-bit directory, two workgroups per CU
-            hipLaunchKernelGGL((k_rx_p3<RX_WMAX_BIG, RX_ECAP, 4, uint16_t, RX_SUBCAP3, true>), dim3(ix->n_cu * ix->rx_grid_per_cu),
-                               dim3(RX_NT), 0, ix->stream, iv, rx, max_freq);
-        else if (ix->rx_w > 12 && ix->rx_fits_small && ix->rx_max_slice <= 65535u)
-            hipLaunchKernelGGL((k_rx_p3<RX_WMAX_BIG, RX_ECAP, 4, uint16_t>), dim3(ix->n_cu * ix->rx_grid_per_cu), dim3(RX_NT),
-                               0, ix->stream, iv, rx, max_freq);
-        else if (ix->rx_w > 12 && ix->rx_fits_mid && p16 && !getenv("KMM_RX_NO_MID"))
-            // ... at most 4608 keys (load factor 0.5): the same with a shorter piece list
-            hipLaunchKernelGGL((k_rx_p3<RX_WMAX_BIG, RX_ECAP_MID, 4, uint16_t, 1024, true>), dim3(ix->n_cu * ix->rx_grid_per_cu),
-                               dim3(RX_NT), 0, ix->stream, iv, rx, max_freq);
-        else if (ix->rx_w > 12 && ix->rx_fits_mid && ix->rx_max_slice <= 65535u && !getenv("KMM_RX_NO_MID"))
-            hipLaunchKernelGGL((k_rx_p3<RX_WMAX_BIG, RX_ECAP_MID, 4, uint16_t, 1024>), dim3(ix->n_cu * ix->rx_grid_per_cu),
-                               dim3(RX_NT), 0, ix->stream, iv, rx, max_freq);
-        else if (ix->rx_w > 12)
-            hipLaunchKernelGGL((k_rx_p3<RX_WMAX_BIG, RX_ECAP_BIG, 2, uint32_t>), dim3(ix->n_cu), dim3(RX_NT), 0, ix->stream,
-                               iv, rx, max_freq);
-        else if (ix->rx_w <= 12 && p16)
-            // slices of up to 4096 buckets (the usual case): 16-bit directory loaded as it is
-            hipLaunchKernelGGL((k_rx_p3<RX_WMAX, RX_ECAP, 4, uint16_t, RX_SUBCAP3, true>), dim3(ix->n_cu * ix->rx_grid_per_cu),
-                               dim3(RX_NT), 0, ix->stream, iv, rx, max_freq);
-        else
-            hipLaunchKernelGGL((k_rx_p3<RX_WMAX, RX_ECAP, 4, uint32_t>), dim3(ix->n_cu * ix->rx_grid_per_cu), dim3(RX_NT), 0,
-                               ix->stream, iv, rx, max_freq);
-        HIPCHK(hipGetLastError());
-        KMMCHK(tm.end());
-        ix->ecnt_dirty = true;
-        ix->rx_unchecked = true;
-    }
-    ix->n_radix_batches++;
-    if (verbose && ms_since(t_0) > 20.0)
-        fprintf(stderr, "libkmm: radix passes of %lld positions: %.2f ms for the batch buffers (%zu + %zu + %zu bytes), %.2f ms to issue %lld "
-                "sub-batch(es)\n", (long long)units, ms_buffers, ix->rx_meta.cap, ix->rx_buf1.cap, ix->rx_buf2.cap, ms_since(t_0) - ms_buffers,
-                (long long)n_sub);
-    return KMM_OK;
-}
-
-// Per-entry hits of the radix path -> node counts (mapper.pyx:68 summed per entry first).  Asynchronous.
-int rx_flush(kmm_index *ix)
-{
-    if (!ix->ecnt_dirty)
-        return KMM_OK;
-    ScopedTimer tm;
-    KMMCHK(tm.begin(ix, KMM_KERNEL_RX_FLUSH));
-    if (ix->rx_norder && !ix->rx_ecnt_acc && ix->rx_flush_sorted) {
-        // entries in node order: a gather of the counts + atomics that walk the count vector front to back
-        hipLaunchKernelGGL(k_rx_flush_sorted, dim3(ix->n_cu * 8), dim3(256), 0, ix->stream, view_of(ix), ix->rx_ecnt,
-                           ix->rx_norder, ix->rx_nnode, ix->rx_S);
-        HIPCHK(hipMemsetAsync(ix->rx_ecnt, 0, (size_t)ix->rx_S * 4, ix->stream));
-    } else {
-        hipLaunchKernelGGL(k_rx_flush, dim3(ix->n_cu * 8), dim3(256), 0, ix->stream, view_of(ix), ix->rx_ecnt,
-                           ix->rx_pnodes, ix->rx_S, ix->rx_ecnt_acc);
-    }
+    const uint64_t n_blocks = (n + 1023) / 1024;
+    if (level >= SCAN_MAX_LEVELS || scratch.size() < 2 * SCAN_MAX_LEVELS)
+        return fail(KMM_ERR_INVALID_ARG, "scan_exclusive: level %zu out of range", level);
+    DevBuf &sums = scratch[2 * level], &pre = scratch[2 * level + 1];
+    KMMCHK(ensure(sums, (size_t)n_blocks * 4));
+    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)n_blocks), dim3(1024), 0, stream, in, out, (uint32_t *)sums.p, n);
     HIPCHK(hipGetLastError());
-    KMMCHK(tm.end());
-    ix->ecnt_dirty = false;
+    if (n_blocks == 1)
+        return KMM_OK;
+    KMMCHK(ensure(pre, (size_t)n_blocks * 4));
+    KMMCHK(scan_exclusive((const uint32_t *)sums.p, (uint32_t *)pre.p, n_blocks, scratch, level + 1, stream));
+    uint64_t g = (n + 255) / 256;
+    if (g > 65536)
+        g = 65536;
+    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)g), dim3(256), 0, stream, out, (const uint32_t *)pre.p, n);
+    HIPCHK(hipGetLastError());
     return KMM_OK;
 }
+
+#include "kmm_radix_host.hpp"
 
 template <int MODE>
 int launch_map_reads(kmm_index *ix, const ReadsView &rv, int k, int max_freq, int also_rc)
@@ -963,31 +674,6 @@ int launch_map_reads(kmm_index *ix, const ReadsView &rv, int k, int max_freq, in
     }
 }
 
-// Exclusive scan of n uint32 values on the device (in -> out): 1024-wide block scans, recursing on the
-// block totals (n < 2^32 needs at most 4 levels).  All launches go to `stream`; ensure() may hipFree (device-wide sync).  `scratch` holds one DevBuf pair per level and is sized
-// by the caller ONCE — it must not reallocate while outer levels hold references into it.
-constexpr size_t SCAN_MAX_LEVELS = 8;
-int scan_exclusive(const uint32_t *in, uint32_t *out, uint64_t n, std::vector<DevBuf> &scratch,
-                   size_t level, hipStream_t stream)
-{
-    const uint64_t n_blocks = (n + 1023) / 1024;
-    if (level >= SCAN_MAX_LEVELS || scratch.size() < 2 * SCAN_MAX_LEVELS)
-        return fail(KMM_ERR_INVALID_ARG, "scan_exclusive: level %zu out of range", level);
-    DevBuf &sums = scratch[2 * level], &pre = scratch[2 * level + 1];
-    KMMCHK(ensure(sums, (size_t)n_blocks * 4));
-    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)n_blocks), dim3(1024), 0, stream, in, out, (uint32_t *)sums.p, n);
-    HIPCHK(hipGetLastError());
-    if (n_blocks == 1)
-        return KMM_OK;
-    KMMCHK(ensure(pre, (size_t)n_blocks * 4));
-    KMMCHK(scan_exclusive((const uint32_t *)sums.p, (uint32_t *)pre.p, n_blocks, scratch, level + 1, stream));
-    uint64_t g = (n + 255) / 256;
-    if (g > 65536)
-        g = 65536;
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)g), dim3(256), 0, stream, out, (const uint32_t *)pre.p, n);
-    HIPCHK(hipGetLastError());
-    return KMM_OK;
-}
 
 // The direct view (kmm_probe.hpp): bucket records + 16-byte entries (+ the L2 pre-filter for small indexes), packed
 // from the caller's arrays at creation or from the radix view's bucket-ordered copy later.  Synchronous.
@@ -1163,214 +849,6 @@ void kmm_index_destroy(kmm_index_t *ix)
     delete ix; // every buffer, event and stream of the handle frees itself; the streams go last
 }
 
-// The entry k-mers in the packed form of the current (w, f2) (kmm_radix.hpp); synchronous.
-static int rx_repack_keys(kmm_index *ix)
-{
-    if (ix->rx_S)
-        hipLaunchKernelGGL(k_rx_pack_keys, dim3(grid_for(ix, (int64_t)((ix->rx_S + 255) / 256), 16)), dim3(256), 0,
-                           ix->stream, ix->rx_pkeys_raw, ix->rx_S, view_of(ix), ix->rx_w + ix->rx_f2, ix->rx_pkeys);
-    HIPCHK(hipGetLastError());
-    // most entries of one slice: decides whether pass 3 may keep a 16-bit directory (ix->queue serves as the cell)
-    HIPCHK(hipMemsetAsync(ix->queue, 0, 3 * sizeof(unsigned long long), ix->stream));
-    hipLaunchKernelGGL(k_rx_max_slice, dim3(grid_for(ix, (int64_t)((ix->rx_PF + 255) / 256), 16)), dim3(256), 0, ix->stream,
-                       ix->rx_pstart, ix->modulo, ix->rx_w, ix->rx_PF, ix->queue);
-    HIPCHK(hipGetLastError());
-    unsigned long long mx[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(mx, ix->queue, sizeof mx, hipMemcpyDeviceToHost, ix->stream));
-    HIPCHK(hipStreamSynchronize(ix->stream));
-    ix->rx_max_slice = (uint32_t)mx[0];
-    // a slice with more entries than pass 3 keeps in LDS has the buckets behind them walked in HBM: fine for the odd
-    // slice (a k-mer stored under 1500 nodes), not as the rule — at most one slice in a thousand (or one slice)
-    const unsigned long long odd = ix->rx_PF / 1000 > 1 ? ix->rx_PF / 1000 : 1;
-    ix->rx_fits_small = mx[1] <= odd;
-    ix->rx_fits_mid = mx[2] <= odd;
-    // 16-bit slice-relative directory: pass 3 loads 2 B per bucket instead of 4 (optional: 2 B x modulo of HBM)
-    static_cast<RxDir16 &>(*ix) = RxDir16();
-    if (ix->rx_max_slice <= 65535u && !getenv("KMM_RX_NO_P16")) {
-        const size_t n16 = ((size_t)ix->rx_PF << ix->rx_w) + 8;
-        if (hipMalloc(ix->rx_pstart16.put(), n16 * 2) == hipSuccess &&
-            hipMalloc(ix->rx_slice_e0.put(), ((size_t)ix->rx_PF + 2) * 4) == hipSuccess &&
-            hipMalloc(ix->rx_slice_fmax.put(), ((size_t)ix->rx_PF + 2) * 2) == hipSuccess) {
-            hipLaunchKernelGGL(k_rx_pstart16, dim3(grid_for(ix, (int64_t)((n16 + 255) / 256), 16)), dim3(256), 0, ix->stream,
-                               ix->rx_pstart, ix->modulo, ix->rx_w, ix->rx_PF, ix->rx_pstart16, ix->rx_slice_e0);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_rx_slice_fmax, dim3(grid_for(ix, (int64_t)((ix->rx_PF + 3) / 4), 16)), dim3(256), 0, ix->stream,
-                               ix->rx_slice_e0, ix->rx_pfreq, ix->rx_PF, ix->rx_slice_fmax);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(ix->stream));
-        } else {
-            (void)hipGetLastError();
-            static_cast<RxDir16 &>(*ix) = RxDir16();
-        }
-    }
-    return KMM_OK;
-}
-
-// Radix-path view of the index (kmm_radix.hpp): entries regrouped in bucket order (whatever order the caller's
-// hashes_to_index uses) + the exclusive prefix of the bucket sizes, which serves as the bucket directory of any
-// 2^w-bucket slice.  Built from the raw arrays while they are still in HBM.
-static int rx_build(kmm_index *ix, const int32_t *h2i, const int32_t *nk, const uint64_t *kmers,
-                    const int32_t *nodes, const uint16_t *freqs)
-{
-    const uint64_t M = ix->modulo;
-    if (const char *env = getenv("KMM_RX_FILTER")) // experiments: 0 = plain pass 2 and the fan-out chosen without the filter
-        ix->rx_filter = atoi(env) != 0;
-    ix->rx_why_not = 1;
-    if (M >= (1ull << 31))
-        return KMM_OK; // beyond the index format's int32 tables: no radix path; the direct path serves every batch
-    DevBuf sizes;
-    std::vector<DevBuf> scratch(2 * SCAN_MAX_LEVELS);
-    int rc = KMM_OK;
-    hipError_t e = hipSuccess;
-    bool overlap = false;
-    do {
-        if ((rc = ensure(sizes, (size_t)(M + 1) * 4))) break;
-        if ((e = hipMalloc(ix->rx_pstart.put(), (size_t)(M + 1) * 4))) break;
-        hipLaunchKernelGGL(k_rx_bucket_sizes, dim3(grid_for(ix, (int64_t)((M + 256) / 256), 16)), dim3(256), 0,
-                           ix->stream, h2i, nk, M, ix->n_entries, (uint32_t *)sizes.p);
-        // an index whose buckets overlap (sum of the bucket sizes > n_entries: legal for the reference's loop, which only
-        // follows (start, count) per bucket) has no bucket-ordered copy of bounded size, and a 32-bit prefix could
-        // wrap: such an index is served by the direct path alone
-        unsigned long long sum64 = 0;
-        if ((e = hipMemsetAsync(ix->queue, 0, sizeof(unsigned long long), ix->stream))) break;
-        hipLaunchKernelGGL(k_sum_u32, dim3(grid_for(ix, (int64_t)((M + 256) / 256), 8)), dim3(256), 0, ix->stream,
-                           (const uint32_t *)sizes.p, M + 1, ix->queue);
-        if ((e = hipMemcpyAsync(&sum64, ix->queue, 8, hipMemcpyDeviceToHost, ix->stream))) break;
-        if ((e = hipStreamSynchronize(ix->stream))) break;
-        if (sum64 > (unsigned long long)ix->n_entries) {
-            overlap = true;
-            break;
-        }
-        if ((rc = scan_exclusive((const uint32_t *)sizes.p, ix->rx_pstart, M + 1, scratch, 0, ix->stream))) break;
-        uint32_t total = 0;
-        if ((e = hipMemcpyAsync(&total, ix->rx_pstart + M, 4, hipMemcpyDeviceToHost, ix->stream))) break;
-        if ((e = hipStreamSynchronize(ix->stream))) break;
-        ix->rx_S = total; // = sum64 <= n_entries < 2^31
-        {   // occupancy bitmap for pass 2's empty-bucket filter, padded by one coarse partition's worth of words
-            // (k_rx_p2f loads whole partitions); optional: without the memory for it the plain pass 2 runs
-            const size_t occ_words = (size_t)((M + 31) / 32) + ((size_t)1 << (P2F_LOGBITS + 2 - 5)); // (up to 4 buckets per LDS bit)
-            if (hipMalloc(ix->rx_occ.put(), occ_words * 4) == hipSuccess) {
-                if ((e = hipMemsetAsync(ix->rx_occ, 0, occ_words * 4, ix->stream))) break;
-                hipLaunchKernelGGL(k_rx_build_occ, dim3(grid_for(ix, (int64_t)((M / 32 + 256) / 256), 16)), dim3(256), 0, ix->stream,
-                                   ix->rx_pstart, M, ix->rx_occ);
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-        const size_t S = total ? total : 1;
-        if ((e = hipMalloc(ix->rx_pkeys.put(), S * 8))) break;
-        if ((e = hipMalloc(ix->rx_pkeys_raw.put(), S * 8))) break;
-        if ((e = hipMalloc(ix->rx_pfreq.put(), S * 2))) break;
-        if ((e = hipMalloc(ix->rx_pnodes.put(), S * 4))) break;
-        if ((e = hipMalloc(ix->rx_porig.put(), S * 4))) break;
-        if ((e = hipMalloc(ix->rx_ecnt.put(), S * 4))) break;
-        if ((e = hipMemsetAsync(ix->rx_ecnt, 0, S * 4, ix->stream))) break;
-        hipLaunchKernelGGL(k_rx_pack, dim3(grid_for(ix, (int64_t)((M + 255) / 256), 16)), dim3(256), 0, ix->stream, h2i,
-                           kmers, nodes, freqs, M, ix->max_node_id, ix->rx_pstart, ix->rx_pkeys_raw, ix->rx_pfreq,
-                           ix->rx_pnodes, ix->rx_porig);
-        if ((e = hipGetLastError())) break;
-        if ((e = hipStreamSynchronize(ix->stream))) break;
-        // the entries once more in NODE order, for the flush (k_rx_flush_sorted): counting sort by node.  Optional:
-        // without the memory for it the flush walks the entries in bucket order (k_rx_flush).
-        // (few nodes with many entries each — a graph with 1000 hot nodes — aggregate in the bucket-order kernel's
-        // LDS table instead: 1.1 ms against 2.3 ms per flush at 10^8 entries / 1000 nodes; 4.0 against 2.0 ms when
-        // every entry has its own node)
-        if (total) {
-            const uint64_t n_nodes = (uint64_t)ix->max_node_id + 1;
-            DevBuf hist, cursor;
-            if (n_nodes + 1 < 0xFFFFFFFFull && (uint64_t)total / n_nodes < 8 && ensure(hist, (size_t)(n_nodes + 1) * 4) == KMM_OK &&
-                ensure(cursor, (size_t)(n_nodes + 1) * 4) == KMM_OK &&
-                hipMalloc(ix->rx_norder.put(), S * 4) == hipSuccess && hipMalloc(ix->rx_nnode.put(), S * 4) == hipSuccess) {
-                bool ok = hipMemsetAsync(hist.p, 0, (size_t)(n_nodes + 1) * 4, ix->stream) == hipSuccess;
-                hipLaunchKernelGGL(k_rx_node_hist, dim3(grid_for(ix, (int64_t)((S + 255) / 256), 16)), dim3(256), 0,
-                                   ix->stream, ix->rx_pnodes, (uint64_t)total, (uint32_t *)hist.p);
-                ok = ok && scan_exclusive((const uint32_t *)hist.p, (uint32_t *)cursor.p, n_nodes + 1, scratch, 0,
-                                          ix->stream) == KMM_OK;
-                hipLaunchKernelGGL(k_rx_node_scatter, dim3(grid_for(ix, (int64_t)((S + 255) / 256), 16)), dim3(256), 0,
-                                   ix->stream, ix->rx_pnodes, (uint64_t)total, (uint32_t *)cursor.p, ix->rx_norder,
-                                   ix->rx_nnode);
-                ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(ix->stream) == hipSuccess;
-                if (!ok) {
-                    (void)ix->rx_norder.reset();
-                    (void)ix->rx_nnode.reset();
-                }
-            } else {
-                (void)hipGetLastError();
-                (void)ix->rx_norder.reset();
-                (void)ix->rx_nnode.reset();
-            }
-        }
-    } while (0);
-    (void)sizes.reset(); // (here, not at the end: the repack below allocates the optional 16-bit directory)
-    scratch.clear();
-    if (rc != KMM_OK || e != hipSuccess || overlap) {
-        // the radix view is optional: without the memory for it (or for an index with overlapping buckets) the
-        // direct path serves every batch; any other failure is an error
-        const bool nomem = rc == KMM_ERR_NOMEM || e == hipErrorOutOfMemory;
-        (void)hipGetLastError();
-        static_cast<RxArrays &>(*ix) = RxArrays();
-        ix->rx_ok = false;
-        if (overlap || nomem) {
-            ix->rx_why_not = overlap ? 4 : 3;
-            if (getenv("KMM_VERBOSE"))
-                fprintf(stderr, "libkmm: radix view not built (%s): every batch takes the direct path\n",
-                        overlap ? "the buckets of the index overlap" : "out of HBM");
-            return KMM_OK;
-        }
-        if (rc != KMM_OK)
-            return rc;
-        return fail(KMM_ERR_HIP, "radix index build: %s", hipGetErrorString(e));
-    }
-    // 2^w buckets per fine partition: as many as keep a slice's entries (load factor x 2^w) well inside the LDS key
-    // capacity; fewer when the table is dense.  The fan-out must fit 256 x 256 fine partitions.
-    int w = 12;
-    if (const char *env = getenv("KMM_RX_W")) // experiments / tests: force the slice width
-        w = atoi(env);
-    else
-        while (w > 0 && ((double)ix->rx_S / (double)M * (double)(1u << w) * 1.3 + 64.0 > (double)RX_ECAP ||
-                         (1ull << w) > M))
-            --w;
-    // Fan-out, in order of preference (runs between the passes get shorter, then pass 3 loses its second workgroup
-    // per CU): up to 256 x 256 slices of 2^w buckets; 256 x 256 slices of 8192 buckets whose entries fit 4096 keys
-    // (16-bit LDS directory, two workgroups of pass 3 per CU); up to 512 x 512 slices of 4096 buckets; slices of 8192
-    // buckets with up to 8192 keys (one workgroup of pass 3 per CU), 256 x 256, then 512 x 512: every modulo below
-    // 2^31 is covered as long as the load factor lets a slice's entries fit LDS.
-    const int f2_force = getenv("KMM_RX_F2") ? atoi(getenv("KMM_RX_F2")) : -1; // experiments: fine-partition bits
-    const double load = (double)ix->rx_S / (double)M;
-    const bool fits13_small = load * 8192.0 * 1.3 + 64.0 <= (double)RX_ECAP;
-    const bool fits13 = load * 8192.0 * 1.3 + 64.0 <= (double)RX_ECAP_BIG;
-    ix->rx_ok = rx_configure(ix, w, f2_force >= 0 ? RX_MAXF : 256, f2_force);
-    if (!ix->rx_ok && w == 12 && !getenv("KMM_RX_W")) {
-        ix->rx_ok = (fits13_small && rx_configure(ix, 13, 256)) || rx_configure(ix, 12, RX_MAXF) ||
-                    (fits13 && (rx_configure(ix, 13, 256) || rx_configure(ix, 13, RX_MAXF)));
-    } else if (!ix->rx_ok) {
-        ix->rx_ok = rx_configure(ix, w, RX_MAXF);
-    }
-    ix->rx_why_not = ix->rx_ok ? 0 : 2;
-    if (getenv("KMM_VERBOSE"))
-        fprintf(stderr, "libkmm: modulo %llu, %llu entries: radix path %s (2^%d buckets per slice, %u x %u partitions)\n",
-                (unsigned long long)M, (unsigned long long)ix->rx_S, ix->rx_ok ? "available" : "NOT available: slices too "
-                "dense for LDS or more than 512 x 512 of them", ix->rx_w, ix->rx_F1, ix->rx_F2);
-    if (ix->rx_ok)
-        KMMCHK(rx_repack_keys(ix));
-    // auto: the radix path streams the whole directory + key arrays once per batch (4 B x modulo + 14 B x entries) and
-    // then costs ~6.5 ps per k-mer (10 ps at the 1 B-k-mer index: shorter runs); the direct kernel has no fixed cost and
-    // runs at ~60 G k-mers/s below ~1 GB of index, ~38 G above.  The batch size where the two meet
-    // (profiles/r03/path_crossover.txt: 16-20 M positions at the 10 M index, ~52 M at the 100 M index; units are
-    // base positions, 1.25 per k-mer at 150 bp):
-    {
-        const double bytes = (double)M * 4.0 + (double)ix->rx_S * 14.0;
-        const double fixed = 50e-6 + bytes / 2.6e12;
-        const double per_kmer_radix = 6.5e-12 * (1.0 + bytes / 40e9);
-        const double per_kmer_direct = 1.0 / (bytes < 1e9 ? 60e9 : 38e9);
-        ix->rx_min_units = (int64_t)(1.25 * fixed / (per_kmer_direct - per_kmer_radix));
-    }
-    if (ix->rx_min_units < ((int64_t)1 << 22))
-        ix->rx_min_units = (int64_t)1 << 22;
-    if (const char *env = getenv("KMM_RX_MIN_UNITS"))
-        ix->rx_min_units = strtoll(env, nullptr, 10);
-    return KMM_OK;
-}
 
 static bool ensure_ring(kmm_index_t *ix);
 
@@ -4178,34 +3656,29 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
                         "and slices whose entries fit LDS)", (unsigned long long)ix->modulo);
         ix->path = (int)value;
     } else if (!strcmp(name, "part_shift")) {
-        if (!rx_configure(ix, (int)value))
+        const int rc = rx_reconfigure(ix, (int)value, -1, true);
+        if (rc == RX_REFUSED)
             return fail(KMM_ERR_INVALID_ARG, "part_shift %lld: needs 0 <= shift <= 13, at most 512 x 512 fine partitions "
                         "and 2^shift small enough for the quotient of a 64-bit k-mer by the modulo to fit beside "
                         "the hash bits", (long long)value);
-        ix->rx_ok = ix->rx_pstart != nullptr;
-        if (ix->rx_ok) {
-            KMMCHK(rx_flush(ix)); // nothing of the old layout may be pending
-            KMMCHK(rx_repack_keys(ix));
-        }
+        KMMCHK(rc);
     } else if (!strcmp(name, "radix_packed_tiles")) {
         ix->rx_packed = value != 0;
     } else if (!strcmp(name, "radix_filter")) {
         // 1 (default): pass 2 drops the k-mers of empty buckets where a coarse partition's bitmap fits LDS (the
         // fan-out is chosen for it); 0: the plain pass 2
         ix->rx_filter = value != 0;
-        if (ix->rx_pstart && rx_configure(ix, ix->rx_w)) {
-            KMMCHK(rx_flush(ix));
-            KMMCHK(rx_repack_keys(ix));
+        if (ix->rx_pstart) { // (the fan-out is derived anew: a forced "fine_bits" is dropped; refused: the old one stays)
+            const int rc = rx_reconfigure(ix, ix->rx_geo.w, -1, false);
+            if (rc != RX_REFUSED)
+                KMMCHK(rc);
         }
     } else if (!strcmp(name, "fine_bits")) {
         // experiments: split the current slice width's fan-out as F2 = 2^value fine partitions per coarse partition
-        if (value < 0 || value > 9 || !rx_configure(ix, ix->rx_w, RX_MAXF, (int)value))
+        const int rc = value < 0 || value > 9 ? RX_REFUSED : rx_reconfigure(ix, ix->rx_geo.w, (int)value, true);
+        if (rc == RX_REFUSED)
             return fail(KMM_ERR_INVALID_ARG, "fine_bits %lld: both fan-outs must stay within 512", (long long)value);
-        ix->rx_ok = ix->rx_pstart != nullptr;
-        if (ix->rx_ok) {
-            KMMCHK(rx_flush(ix));
-            KMMCHK(rx_repack_keys(ix));
-        }
+        KMMCHK(rc);
     } else if (!strcmp(name, "radix_min_units")) {
         ix->rx_min_units = value;
     } else if (!strcmp(name, "radix_sub_batch_kmers")) {
@@ -4318,7 +3791,7 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
     if (!strcmp(name, "path"))
         *value = ix->path;
     else if (!strcmp(name, "part_shift"))
-        *value = ix->rx_w;
+        *value = ix->rx_geo.w;
     else if (!strcmp(name, "radix_min_units"))
         *value = ix->rx_min_units;
     else if (!strcmp(name, "radix_grid_per_cu"))
@@ -4429,25 +3902,21 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
     else if (!strcmp(name, "direct_view_bytes"))
         *value = (int64_t)ix->direct_bytes;
     else if (!strcmp(name, "radix_view_bytes"))
-        *value = ix->rx_pstart ? (int64_t)((ix->modulo + 1) * 4 + (ix->rx_S ? ix->rx_S : 1) * (8 + 8 + 2 + 4 + 4 + 4 + (ix->rx_norder ? 8 : 0)))
-                               : 0;
+        *value = ix->rx_pstart ? (int64_t)rx_view_bytes(ix->modulo, ix->rx_S, ix->rx_norder != nullptr) : 0;
     else if (!strcmp(name, "radix_filter"))
         *value = (ix->rx_ok && rx_filter_active(ix)) ? 1 : 0;
     else if (!strcmp(name, "radix_p3_keys_in_lds")) // entries of a slice pass 3 keeps in LDS (the rest is walked in HBM)
-        *value = !ix->rx_ok ? 0
-                 : ix->rx_w <= 12 ? RX_ECAP
-                 : (ix->rx_fits_small && ix->rx_max_slice <= 65535u) ? RX_ECAP
-                 : (ix->rx_fits_mid && ix->rx_max_slice <= 65535u && !getenv("KMM_RX_NO_MID")) ? RX_ECAP_MID : RX_ECAP_BIG;
+        *value = ix->rx_ok ? rx_p3_shape(rx_p3_variant(ix)).keys_in_lds : 0;
     else if (!strcmp(name, "radix_filter_buckets_per_bit")) // 1, 2 or 4 (0: no filter)
-        *value = (ix->rx_ok && rx_filter_active(ix)) ? (1 << ix->rx_occ_shift) : 0;
+        *value = (ix->rx_ok && rx_filter_active(ix)) ? (1 << ix->rx_geo.occ_shift) : 0;
     else if (!strcmp(name, "radix_packed_tiles"))
         *value = ix->rx_packed ? 1 : 0;
     else if (!strcmp(name, "n_fine_per_coarse"))
-        *value = ix->rx_ok ? ix->rx_F2 : 0;
+        *value = ix->rx_ok ? ix->rx_geo.F2 : 0;
     else if (!strcmp(name, "count_kmers"))
         *value = ix->rx_ecnt_acc ? 1 : 0;
     else if (!strcmp(name, "n_coarse_partitions"))
-        *value = ix->rx_ok ? ix->rx_F1 : 0;
+        *value = ix->rx_ok ? ix->rx_geo.F1 : 0;
     else if (!strcmp(name, "radix_p2_kmers") || !strcmp(name, "radix_p3_kmers") || !strcmp(name, "radix_p2_dropped") ||
              !strncmp(name, "stats_slot_", 11)) {
         // conservation check of the radix path: k-mers gathered by pass 2 / probed by pass 3 since the last
@@ -4479,7 +3948,7 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
     else if (!strcmp(name, "wide_buckets"))
         *value = ix->wide ? 1 : 0;
     else if (!strcmp(name, "n_partitions"))
-        *value = ix->rx_ok ? ix->rx_PF : 0;
+        *value = ix->rx_ok ? ix->rx_geo.PF : 0;
     else
         return fail(KMM_ERR_INVALID_ARG, "unknown parameter '%s'", name);
     return KMM_OK;

@@ -2,6 +2,7 @@
 // Radix path: two block-local partition passes by hash range, then a probe of LDS-resident index slices.
 #pragma once
 #include <type_traits>
+#include "kmm_radix_plan.hpp" // the constants both sides need (RX_B, RX_CH, RX_MAXF, RX_IC, RX_ECAP*, P2F_*) and the host's decisions
 
 // ------------------------------------------------------------------------------------------------
 // Why.  A probe that goes to HBM costs one 64-byte fabric request per k-mer and MI355X serves ~55 G
@@ -43,7 +44,7 @@
 // quotient and the hash bits BELOW the coarse partition number.  Inside a coarse partition (and so inside a
 // fine one) x determines q, the fine partition is bits [w, w + f2) of x and the bucket inside the slice bits
 // [0, w): only pass 1 divides by the modulo (mapper.pyx:54), passes 2 and 3 shift and compare.  The index keys
-// are kept in the same form.  rx_configure guarantees that the quotient of ANY 64-bit value fits the upper bits.
+// are kept in the same form.  rx_geometry (kmm_radix_plan.hpp) guarantees that the quotient of ANY 64-bit value fits the upper bits.
 //
 // Nothing depends on partition sizes being balanced: block areas and items are exact, a run that is longer
 // than expected is just a longer contiguous copy, a partition with many items is probed by several work
@@ -54,16 +55,7 @@
 // (nearly) everything.  What such batches cost pass 3: profiles/skew/README.md.)
 // ------------------------------------------------------------------------------------------------
 constexpr int RX_NT = 512;            // threads per workgroup of the three passes
-constexpr int RX_B = 8192;            // positions per pass-1 block = k-mer capacity of a block area / item: each
-                                      // 256-thread half of the workgroup owns 4096 of them (flat reads: one tile of
-                                      // 16 windows per lane; records mode: four tiles of 4 windows per lane)
 constexpr int RX_KPT = RX_B / RX_NT;  // 16 k-mers per thread
-constexpr int RX_MAXF = 512;          // largest fan-out of one pass (512 x 512 slices of 8192 buckets = every modulo < 2^32)
-#ifndef RX_CHV
-#define RX_CHV 256
-#endif
-constexpr int RX_CH = RX_CHV;            // blocks per chunk of the directory scan
-constexpr int RX_IC = 1024;           // pass-2 items per pass-3 work item
 #ifndef RX_LPR2V
 #define RX_LPR2V 16
 #endif
@@ -114,11 +106,8 @@ constexpr int RX_U2 = RX_U2V;         // ... pass 2
 #define RX_LOAD3(p) (*(p))
 #endif
 constexpr int RX_WMAX = 4096;         // buckets per fine partition (LDS directory): two workgroups of pass 3 per CU
-constexpr int RX_ECAP = 4096;         // entries of a fine partition kept in LDS (keys + counters)
 constexpr int RX_WMAX_BIG = 8192;     // slices of indexes with more than 256 x 256 x 4096 buckets (e.g. the customary
-constexpr int RX_ECAP_BIG = 8192;     // modulo 452 930 477): 140 KB of LDS, one workgroup of pass 3 per CU
-constexpr int RX_ECAP_MID = 4608;     // 8192-bucket slices at load factor 0.5 (4096 +- 64 entries): 16-bit directory, 1024-piece
-                                      // list, 77 KB of LDS: two workgroups per CU (the 1 B-k-mer index)
+                                      // modulo 452 930 477); entries kept in LDS: RX_ECAP, RX_ECAP_MID, RX_ECAP_BIG (kmm_radix_plan.hpp)
 constexpr uint32_t RX_FILTERED = 0x80000000u; // pass 3: top bit of an LDS hit counter = entry excluded by max_freq
 enum { MODE_KMERS = 3 };              // pass-1 source: a uint64 k-mer array instead of read bytes
 
@@ -184,7 +173,7 @@ struct RxView {
 // q -> packed form; *coarse gets the coarse partition (= hash >> (w + f2)).
 __device__ __forceinline__ uint64_t rx_pack(const IndexView &iv, int sh, uint64_t q, uint32_t *coarse)
 {
-    uint32_t h; // modulo < 2^31 on this path (rx_configure)
+    uint32_t h; // modulo < 2^31 on this path (rx_geometry)
     const uint64_t quo = fastdiv_m31(q, (uint32_t)iv.modulo, iv.magic, &h);
     *coarse = h >> sh;
     return (quo << sh) | (uint64_t)(h & ((1u << sh) - 1u));
@@ -1281,8 +1270,6 @@ __device__ __forceinline__ uint32_t rx_fold4(uint32_t x)
 
 constexpr int P2F_NT = 1024;
 constexpr int P2F_KPT = RX_B / P2F_NT;   // 8 k-mers per thread and item
-constexpr int P2F_KMAX = 64;             // most items per work unit (rx.p2f_k: chosen per batch, launch_rx)
-constexpr int P2F_LOGBITS = 19;          // buckets per coarse partition the LDS bitmap covers: 2^19 (64 KB)
 
 // FILTER false: coarse partitions beyond 2^21 buckets (no bitmap fits) — the kernel is still the faster pass 2
 // FSMALL: at most 128 fine partitions (the launch knows): only the per-wavefront scan is compiled into the sort
@@ -1655,7 +1642,7 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
 // pass 3
 // ------------------------------------------------------------------------------------------------
 // DirT: type of the LDS directory; uint16_t (half the LDS: 8192-bucket slices with two workgroups per CU) only when
-// no slice of the index holds more than 65535 entries (launch_rx checks).
+// no slice of the index holds more than 65535 entries (rx_choose_p3 checks).
 // P16: the slice's directory comes from rx.pstart16 (two buckets per 32-bit load, already relative to the slice).
 template <int WMAX, int ECAP, int WPS, typename DirT, int SUBCAP = RX_SUBCAP3, bool P16 = false>
 __global__ void __launch_bounds__(RX_NT, WPS) k_rx_p3(IndexView iv, RxView rx, int max_freq)
