@@ -53,6 +53,24 @@ extern "C" {
 #define KMM_MAX_K 31               /* a k-mer is packed 2 bits/base into a uint64; bionumpy's
                                       get_kmers (util.py:72) is used with k <= 31                */
 
+/*
+ * The `lut` argument of every entry point is uint8[256] with three kinds of entries: 0..3 = the base's 2-bit code, 0xFF = not
+ * a nucleotide (KMM_ERR_INVALID_BASE), and KMM_LUT_BREAK = a BREAK: a byte that is a base of its read but has no code (N, the
+ * IUPAC ambiguity letters).  No k-mer that contains a break byte is looked up, forward or reverse complement, and it raises no
+ * error; the windows on either side that do not contain it are mapped as before (what jellyfish, KMC and others do with N).
+ *   - A break inside a read is equivalent to ending the read before it and starting a new one behind it; the library
+ *     represents it that way (two bits of the read-start bitset), so the mapping kernels are the ragged ones.
+ *   - *n_records is unaffected (the record is still one record); kmm_get_stats' n_lookups counts only the surviving windows.
+ *   - k == 1 with a table that has a break entry is KMM_ERR_INVALID_ARG (the bitset rule "no read start inside (p, p+k-1]"
+ *     cannot kill a window of one base; refused rather than silently counted).
+ *   - kmm_extract_kmers with a break entry is KMM_ERR_INVALID_ARG: its n_out contract is per read.
+ *   - kmm_map_packed takes no table: its caller expresses breaks through read_starts.
+ *   - lut == NULL stays the reference's table (N -> A, every other letter an error): nothing changes without a break entry.
+ *   - Tables with a break entry take the device routes only (the host packer, "host_pack_threads", serves lut == NULL), and
+ *     reads of one length with such a table take the ragged front end (they do not count in "flat_uniform_batches").
+ */
+#define KMM_LUT_BREAK 0xFE
+
 typedef struct kmm_index kmm_index_t;
 
 /* Library / device probes. */
@@ -146,8 +164,8 @@ int kmm_map_kmers(kmm_index_t *idx, const uint64_t *kmers, int64_t n,
  * non-decreasing, which is checked on the GPU and reported by the next synchronising call as
  * KMM_ERR_INVALID_ARG).  Every window of k
  * bases inside one read is packed first-base-lowest, 2 bits/base through `lut`
- * (uint8[256]: 0..3 = code, 0xFF = not a nucleotide; NULL = A,C,G,T->0,1,2,3 case-insensitive
- * with N->A) and looked up as in kmm_map_kmers.  A byte with lut 0xFF makes the NEXT
+ * (uint8[256]: 0..3 = code, 0xFF = not a nucleotide, KMM_LUT_BREAK = a base no k-mer may contain;
+ * NULL = A,C,G,T->0,1,2,3 case-insensitive with N->A) and looked up as in kmm_map_kmers.  A byte with lut 0xFF makes the NEXT
  * synchronising call fail with KMM_ERR_INVALID_BASE (the reference's encoder raises).
  */
 int kmm_map_reads(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_offsets,
@@ -412,7 +430,9 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      (csrc/kmm_hostpack.hpp: AVX-512 VBMI / AVX2 / scalar; for records the sequence lines go straight
  *                      from the raw bytes to the 2-bit stream + read-start bitset, by the rules of the device parser); a
  *                      byte outside the table or a malformed record sends the call down the ordinary route, which reports
- *                      it with its offset.  0: the bytes cross as they are.  Default: min(16, "host_cpu_budget") when that
+ *                      it with its offset.  The packer knows no breaks (KMM_LUT_BREAK): a table with a break entry is a
+                      caller's table like any other and takes the device routes — the raw bytes cross PCIe as they are
+                      (the price on plain FASTQ: profiles/ambiguous/README.md).  0: the bytes cross as they are.  Default: min(16, "host_cpu_budget") when that
  *                      budget — the CPUs of the affinity mask but one, cut by the cgroup's CPU quota — is at least 8, else
  *                      0; environment KMM_HOST_PACK_THREADS overrides it at index creation.
  *                      "host_packed_calls" / "host_packed_record_calls" (read-only) count the calls that took the route;

@@ -19,6 +19,10 @@ Differences that follow from replacing the engine (all documented in DESIGN.md):
     re-synchronised to record starts, reads_io.rank_byte_range: no rank reads or scans another rank's bytes);
     ranks sharing one .gz stream (not seekable) take chunk i mod WORLD_SIZE and cut the chunks they skip by the
     record parser's own rule (newline count, reads_io.records_cut); the count vectors are summed with one RCCL reduce; rank 0 writes the output.
+  * `--ambiguous-bases skip` (extension; default `a` = the reference, N counted as A and every other letter an error): a
+    k-mer that contains N or an IUPAC ambiguity letter is not counted, the windows on either side of it are
+    (util.ambiguous_skip_lut, KMM_LUT_BREAK).  Such a table takes the device routes: the raw bytes of a plain file cross
+    PCIe as they are, the host threads do not pack them.
 """
 import argparse
 import logging
@@ -86,8 +90,9 @@ def host_threads(n_threads, world_size=1):
 
 
 def map_gpu(index, chunks, k, hash_map_size=0, map_reverse_complements=False,
-            max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16):
+            max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16, lut=None):
     """command_line_interface.py:59-79 on the HIP engine: chunks -> fused kmm_map_reads calls.
+    lut: the lookup table of every call (None: the default; util.ambiguous_skip_lut() for --ambiguous-bases skip).
     before_fetch(dev): called with the open handle after the last chunk and before the counts are copied to the
     host (the multi-rank reduce runs there, on the device)."""
     max_node_id = index.max_node_id() if hasattr(index, "max_node_id") else int(np.max(index._nodes))
@@ -103,10 +108,10 @@ def map_gpu(index, chunks, k, hash_map_size=0, map_reverse_complements=False,
             L = chunk.uniform_length
             if L is not None:
                 dev.map_reads_uniform(chunk.bases, len(chunk), L, k, max_index_lookup_frequency,
-                                      also_revcomp=map_reverse_complements)
+                                      also_revcomp=map_reverse_complements, lut=lut)
             else:
                 dev.map_reads(chunk.bases, chunk.offsets, k, max_index_lookup_frequency,
-                              also_revcomp=map_reverse_complements)
+                              also_revcomp=map_reverse_complements, lut=lut)
             n_kmers += chunk.n_kmers(k)
             logging.debug("GPU: chunk %d (%d reads) submitted in %.5f sec", i, len(chunk),
                           time.perf_counter() - t0)
@@ -121,7 +126,7 @@ def map_gpu(index, chunks, k, hash_map_size=0, map_reverse_complements=False,
     return node_counts
 
 
-def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ):
+def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, lut=None):
     """How map_gpu_raw reads the file: (route, populate, steer).  fmt: the GPU's record format ("fasta_ml" = wrapped FASTA);
     probe: reads_io.probe_input of the file; env: where the KMM_CLI_* switches of A/B runs are read.
 
@@ -140,7 +145,9 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ):
     route "prefetch": any other input the host inflates: two pinned buffers and a reader thread, the next batch is inflated
     while the GPU works on this one (BGZF 5.7 -> 6.5 GB/s end to end); plain files are read at memory speed and the second
     pinned buffer costs more than the overlap returns (3 GB FASTQ: 0.30 s with one buffer, 0.37 s with two), so they take
-    route "raw": one pinned buffer (RawChunker)."""
+    route "raw": one pinned buffer (RawChunker).
+    lut: a caller's lookup table (--ambiguous-bases skip) is never taken by the host packer, so route "mmap", which counts
+    on it (pageable views of the page cache), gives way to "raw": the bytes cross PCIe from a pinned buffer."""
     gpu_inflate = probe.inflate and fmt in ("fastq", "fasta", "sam") and not env.get("KMM_CLI_NO_GPU_INFLATE")
     if fmt == "bam":
         return "bam", False, False
@@ -150,26 +157,26 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ):
         return "gzip", False, False
     if probe.inflate:
         return ("raw" if env.get("KMM_CLI_NO_PREFETCH") else "prefetch"), False, False
-    if fmt in ("fastq", "fasta") and n_threads > 1 and has_device and not env.get("KMM_CLI_NO_MMAP"):
+    if fmt in ("fastq", "fasta") and n_threads > 1 and has_device and lut is None and not env.get("KMM_CLI_NO_MMAP"):
         return "mmap", not env.get("KMM_CLI_NO_POPULATE"), not env.get("KMM_CLI_NO_PACKER_STEERING")
     return "raw", False, False
 
 
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
-                exclude_flags=0, probe=None):
+                exclude_flags=0, probe=None, lut=None):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
     on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
     extracted on the GPU (KMM_FORMAT_SAM on the routes of a FASTQ; exclude_flags filters it too).  probe: reads_io.probe_input
-    of the file, if the caller has it."""
+    of the file, if the caller has it.  lut: the lookup table of every call, on every route (None: the default)."""
     _check_bam_route(fmt, world_size, exclude_flags)
     t_index = time.perf_counter()
     probe = probe_input(path) if probe is None else probe
     has_device = _lib.device_count() > 0
     # (decided BEFORE anything is made: the prefetching chunker starts a reader thread and page-locks two batch buffers —
     # making and freeing those cost the BGZF route 100 ms of its map phase until it was noticed)
-    route, populate, steer = choose_route(fmt, probe, world_size, n_threads, has_device)
+    route, populate, steer = choose_route(fmt, probe, world_size, n_threads, has_device, lut=lut)
     seekable = not probe.inflate
     # page-locked memory is slow to make (~50 ms per GB): the staging buffers of the host packer are made by a helper thread
     # WHILE the index is uploaded and repacked, not inside the map phase.  (The count vector needs none: kmm_get_node_counts
@@ -187,7 +194,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     helper = threading.Thread(target=prepare_host_memory, daemon=True)
     # (.gz input needs 128 MB of it, made in 7 ms by the first call that wants it; behind a helper thread the same allocation
     # came back 100 ms after the index upload it was meant to hide behind: profiles/r05/bgzf_e2e_v6_*.txt)
-    if has_device and n_threads > 1 and seekable:
+    if has_device and n_threads > 1 and seekable and lut is None:      # (the packer's buffers: no packer with a table)
         helper.start()
     byte_range = rank_byte_range(path, fmt, rank, world_size) if (world_size > 1 and seekable) else None
     # the file mapping of route "mmap" is made HERE, and its pages populated, while the index goes up
@@ -268,7 +275,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             helper.join()
         return _map_compressed_file(dev, path, route, kfmt, k, max_index_lookup_frequency,
                                     map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
-                                    world_size=world_size, fmt=fmt)
+                                    world_size=world_size, fmt=fmt, lut=lut)
     try:
         i = 0
         while True:
@@ -278,7 +285,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             last = _lib.FORMAT_LAST_CHUNK if (fmt == "fasta_ml" and chunker.eof) else 0
             if owns(i):
                 used, n_rec = dev.map_records(buf, buf.shape[0], kfmt | last, k, max_index_lookup_frequency,
-                                              also_revcomp=map_reverse_complements)
+                                              also_revcomp=map_reverse_complements, lut=lut)
             else:   # a chunk of a shared .gz stream that another rank maps: only its record boundary is needed,
                     # cut by the SAME rule as the GPU parser's `consumed` (newline count), at end of input too
                 used, n_rec = records_cut(buf, fmt, chunker.eof), 0
@@ -354,7 +361,7 @@ _COMPRESSED_ROUTES = {
 
 
 def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None, rank=0,
-                         world_size=1, fmt="fastq"):
+                         world_size=1, fmt="fastq", lut=None):
     """`kmer_mapper map -f reads.fq.gz | reads.bam` with the GPU inflater: windows of the file mapping -> kmm_map_<route>.
 
     route "gzip" (PLAIN gzip, kmm_map_gzip): each call goes on where the one before could verify a deflate block boundary.
@@ -396,7 +403,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
                         if size - end < window // 4:     # (no short tail call: a call's time is its slowest lane's)
                             end = size
                         used, n_rec = dev.map_gzip(whole[pos:end], fmt=kfmt, k=k, max_index_lookup_frequency=max_freq,
-                                                   also_revcomp=revcomp, first=pos == 0, last=end == size)
+                                                   also_revcomp=revcomp, first=pos == 0, last=end == size, lut=lut)
                         n_reads += n_rec
                         if used == 0:
                             if end == size:
@@ -421,7 +428,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
                         nxt = min(end + window, size)
                         # each window is announced to the call before it (next_chunk: staged under that call's inflate kernel)
                         common = dict(first=pos == lo, last=end == size, k=k, max_index_lookup_frequency=max_freq,
-                                      also_revcomp=revcomp, next_chunk=whole[end:nxt] if nxt > end else None)
+                                      also_revcomp=revcomp, next_chunk=whole[end:nxt] if nxt > end else None, lut=lut)
                         if route == "bam":
                             used, n_rec = dev.map_bam(whole[pos:end], **common)
                             if used == 0 and end == size:
@@ -526,6 +533,12 @@ def map_bnp(args):
     fmt = probe.fmt
     exclude_flags = int(getattr(args, "exclude_flags", 0) or 0)
     _check_bam_route(fmt, world, exclude_flags)
+    lut = None
+    if getattr(args, "ambiguous_bases", "a") == "skip":
+        from .util import ambiguous_skip_lut
+        lut = ambiguous_skip_lut()
+        if k < 2:
+            raise ValueError("--ambiguous-bases skip needs -k 2 or more")
     if fmt == "bam" and getattr(args, "host_parser", False):
         raise ValueError("--host-parser does not read BAM: its records are decoded on the GPU (drop --host-parser)")
     if fmt == "sam" and getattr(args, "host_parser", False):
@@ -535,7 +548,7 @@ def map_bnp(args):
             fmt = "fasta_ml"           # wrapped sequence lines: unwrapped on the GPU (KMM_FORMAT_FASTA)
         node_counts = map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, revcomp, max_freq,
                                   device=device, rank=rank, world_size=world, before_fetch=before_fetch,
-                                  n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe)
+                                  n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe, lut=lut)
     else:
         logging.info("Using the host FASTA/FASTQ parser")
         if world > 1 and not probe.inflate:
@@ -549,7 +562,7 @@ def map_bnp(args):
         chunks = prefetch(chunks)
         node_counts = map_gpu(kmer_index, chunks, k, getattr(args, "gpu_hash_map_size", 0), revcomp,
                               max_freq, device=device, rank=rank, world_size=world, before_fetch=before_fetch,
-                              n_threads=args.n_threads)
+                              n_threads=args.n_threads, lut=lut)
 
     if world > 1:
         if before_fetch is None:        # gloo rehearsal on a 1-GPU box: the sum runs on the host copies
@@ -569,9 +582,7 @@ def map_bnp(args):
     return node_counts
 
 
-def run_argument_parser(args):
-    logging.basicConfig(stream=sys.stdout, level=logging.INFO,
-                        format='%(asctime)s %(levelname)s: %(message)s')
+def build_argument_parser():
     parser = argparse.ArgumentParser(
         description='Kmer Mapper',
         prog='kmer_mapper',
@@ -608,7 +619,18 @@ def run_argument_parser(args):
     subparser.add_argument("--exclude-flags", default=0, type=lambda v: int(v, 0),
                            help="Extension, SAM and BAM input only: leave out records whose FLAG has any of these bits (samtools view -F; "
                                 "e.g. 0x900 = secondary and supplementary alignments). Default 0: every record, as the reference.")
+    subparser.add_argument("--ambiguous-bases", choices=("a", "skip"), default="a",
+                           help="a (default): N is counted as A and any other letter is an error, as the reference. skip "
+                                "(extension): no k-mer that contains N or an IUPAC ambiguity letter is counted; the k-mers on "
+                                "either side of it are.")
     subparser.set_defaults(func=map_bnp)
+    return parser
+
+
+def run_argument_parser(args):
+    logging.basicConfig(stream=sys.stdout, level=logging.INFO,
+                        format='%(asctime)s %(levelname)s: %(message)s')
+    parser = build_argument_parser()
 
     if len(args) == 0:
         parser.print_help()

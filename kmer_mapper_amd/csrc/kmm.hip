@@ -582,13 +582,44 @@ int stage_release(kmm_index *ix, Stage &s, bool staged)
     return KMM_OK;
 }
 
-int resolve_lut(kmm_index *ix, Stage &s, const uint8_t *lut, const uint8_t **dev, bool *staged)
+// Does the caller's lookup table have a break entry (KMM_LUT_BREAK)?  A table in HBM is copied back (256 bytes).
+int lut_has_break(const uint8_t *lut, bool *has_break)
 {
+    *has_break = false;
+    if (!lut)
+        return KMM_OK; // (the default table: N -> A, no breaks)
+    uint8_t copy[256];
+    if (is_device_ptr(lut)) {
+        HIPCHK(hipMemcpy(copy, lut, 256, hipMemcpyDeviceToHost));
+        lut = copy;
+    }
+    *has_break = memchr(lut, KMM_LUT_BREAK, 256) != nullptr;
+    return KMM_OK;
+}
+
+// has_break: whether the table has a break entry — the call then marks the break bytes as one-base reads in its
+// read-start bitset (k_mark_breaks, k_rec_scatter<true>, MODE_RECORDS_BRK) and takes the ragged front ends.
+int resolve_lut(kmm_index *ix, Stage &s, const uint8_t *lut, const uint8_t **dev, bool *staged, bool *has_break)
+{
+    KMMCHK(lut_has_break(lut, has_break));
     if (!lut) {
         *dev = ix->lut_default;
         return KMM_OK;
     }
     return stage_in<uint8_t>(ix, s.lut, lut, 256, dev, staged);
+}
+
+// k == 1 with a break table: "no read start inside (p, p + k - 1]" is an empty condition — the break's own window
+// could not be killed.  Refused by every entry point that takes a table.
+int check_k_lut(int k, const uint8_t *lut)
+{
+    if (k != 1 || !lut)
+        return KMM_OK;
+    bool has_break = false;
+    KMMCHK(lut_has_break(lut, &has_break));
+    if (has_break)
+        return fail(KMM_ERR_INVALID_ARG, "k = 1 with a lookup table that has a break entry (KMM_LUT_BREAK): needs k >= 2");
+    return KMM_OK;
 }
 
 // Layout choice by index size (profiles/r01/partitioned_path_ablation.md, ms per 1.2e9 k-mers, same box):
@@ -636,7 +667,7 @@ int launch_map_reads(kmm_index *ix, const ReadsView &rv, int k, int max_freq, in
     const int64_t n_tiles = (rv.total + TILE_T - 1) / TILE_T;
     // raw records reach this function only for the direct path: on the radix path they are compacted into flat reads
     // first (map_records_piece_radix)
-    const bool radix = MODE == MODE_RECORDS ? false : use_radix(ix, rv.total);
+    const bool radix = mode_is_records(MODE) ? false : use_radix(ix, rv.total);
     if (!radix) {
         KMMCHK(ensure_direct(ix));
         ix->n_direct_batches++;
@@ -665,7 +696,7 @@ int launch_map_reads(kmm_index *ix, const ReadsView &rv, int k, int max_freq, in
         HIPCHK(hipGetLastError());
         return tm.end();
     }
-    if constexpr (MODE == MODE_RECORDS) {
+    if constexpr (mode_is_records(MODE)) {
         return fail(KMM_ERR_INTERNAL, "raw records reach the radix path as flat reads only");
     } else {
         if (MODE == MODE_UNIFORM && rv.pk_rpt) // reads of one length: tiles of whole reads, every computed window a real k-mer
@@ -1816,25 +1847,28 @@ static int map_reads_common(kmm_index_t *ix, const uint8_t *bases, const int64_t
     ReadsView rv;
     memset(&rv, 0, sizeof rv);
     KMMCHK(stage_in<uint8_t>(ix, s.bases, bases, (size_t)total, &rv.bases, &staged));
-    KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &staged));
+    bool has_break = false;
+    KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &staged, &has_break));
     rv.total = total;
     rv.n_reads = n_reads;
     rv.first_bad = ix->first_bad;
     const int64_t n_tiles = (total + TILE_T - 1) / TILE_T;
-    // the uniform kernel's wrap-around handles one read boundary per lane: needs read_len >= S
-    const bool uniform_kernel = uniform && read_len >= 16;
+    // the uniform kernel's wrap-around handles one read boundary per lane: needs read_len >= S.  A table with a break
+    // entry: the breaks are read boundaries only the bitset can hold — the ragged front end
+    const bool uniform_kernel = uniform && read_len >= 16 && !has_break;
     if (uniform_kernel) {
         set_uniform_geometry(ix, rv, read_len, k);
         KMMCHK(stage_copies_done(ix));
         KMMCHK(launch_map_reads<MODE_UNIFORM>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
     } else {
-        if (uniform) {
+        const bool arithmetic_starts = uniform && has_break; // (no offsets array: nothing on this route reads one)
+        if (uniform && !arithmetic_starts) {
             KMMCHK(ensure(s.offsets, (size_t)(n_reads + 1) * 8));
             hipLaunchKernelGGL(k_iota_offsets, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256),
                                0, ix->stream, (int64_t *)s.offsets.p, n_reads, read_len);
             HIPCHK(hipGetLastError());
             rv.offsets = (const int64_t *)s.offsets.p;
-        } else {
+        } else if (!uniform) {
             KMMCHK(stage_in<int64_t>(ix, s.offsets, read_offsets, (size_t)(n_reads + 1), &rv.offsets,
                                      &staged));
         }
@@ -1844,8 +1878,15 @@ static int map_reads_common(kmm_index_t *ix, const uint8_t *bases, const int64_t
         rv.n_start_words = n_words;
         KMMCHK(stage_copies_done(ix));
         HIPCHK(hipMemsetAsync(s.start_bits.p, 0, (size_t)n_words * 4, ix->stream));
-        hipLaunchKernelGGL(k_mark_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
-                           rv.offsets, n_reads, total, (uint32_t *)s.start_bits.p);
+        if (arithmetic_starts)
+            hipLaunchKernelGGL(k_mark_uniform_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                               n_reads, read_len, (uint32_t *)s.start_bits.p);
+        else
+            hipLaunchKernelGGL(k_mark_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                               rv.offsets, n_reads, total, (uint32_t *)s.start_bits.p);
+        if (has_break) // every break byte: a one-base read
+            hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (total + 256 * 16 * BRK_U - 1) / (256 * 16 * BRK_U), 8)), dim3(256), 0,
+                               ix->stream, rv.bases, total, rv.lut, (uint32_t *)s.start_bits.p);
         if (!uniform)
             hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(ix, (n_reads + 255) / 256, 8)), dim3(256), 0,
                                ix->stream, rv.offsets, n_reads, ix->first_bad);
@@ -1867,6 +1908,7 @@ int kmm_map_reads(kmm_index_t *ix, const uint8_t *bases, const int64_t *read_off
         return KMM_OK;
     if (!read_offsets)
         return fail(KMM_ERR_INVALID_ARG, "read_offsets is NULL");
+    KMMCHK(check_k_lut(k, lut));
     return guarded("kmm_map_reads", [&] { return map_reads_common(ix, bases, read_offsets, n_reads, 0, k, max_freq, also_revcomp, lut); });
 }
 
@@ -1880,6 +1922,7 @@ int kmm_map_reads_uniform(kmm_index_t *ix, const uint8_t *bases, int64_t n_reads
         return fail(KMM_ERR_INVALID_ARG, "n_reads / read_len negative");
     if (n_reads == 0 || read_len == 0)
         return KMM_OK;
+    KMMCHK(check_k_lut(k, lut));
     return guarded("kmm_map_reads_uniform", [&] { return map_reads_common(ix, bases, nullptr, n_reads, read_len, k, max_freq, also_revcomp, lut); });
 }
 
@@ -1900,7 +1943,7 @@ static bool records_take_radix(const kmm_index_t *ix, int64_t n_bytes, int forma
 // buffer is free afterwards) and returns where the piece's last complete record ends, its records, the flat length
 // after it, and whether its reads have one length.
 static int rec_compact_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, int64_t n_bytes, int format, const uint8_t *d_lut,
-                             int64_t flat_base, uint32_t *flat, uint32_t *start_bits, int64_t *consumed, int64_t *n_records,
+                             bool has_break, int64_t flat_base, uint32_t *flat, uint32_t *start_bits, int64_t *consumed, int64_t *n_records,
                              int64_t *flat_end, int64_t *uniform_len)
 {
     const int64_t n_tiles = (n_bytes + REC_TB - 1) / REC_TB; // 4 KiB tiles: one wavefront, 64 bytes per lane
@@ -1938,9 +1981,12 @@ static int rec_compact_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, in
         hipLaunchKernelGGL(k_rec_seq_scan, dim3(n_super), dim3(1024), 0, cs, tile_seq, tile_nl, super_nl, n_tiles, pm, tile_pre, super_seq);
         hipLaunchKernelGGL(k_super_scan, dim3(1), dim3(1024), 0, cs, super_seq, n_super, (uint32_t *)(d_out + 8));
     }
-    if (!(skip & 4))
-        hipLaunchKernelGGL(k_rec_scatter, g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_nl, super_nl, tile_pre, super_seq, d_info,
-                           d_lut, pm, hc, flat, (uint64_t)flat_base, start_bits, ix->first_bad, d_out);
+    if (!(skip & 4) && has_break) // (break bytes become one-base reads: k_rec_uniform then finds more starts than records)
+        hipLaunchKernelGGL(k_rec_scatter<true>, g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_nl, super_nl, tile_pre, super_seq,
+                           d_info, d_lut, pm, hc, flat, (uint64_t)flat_base, start_bits, ix->first_bad, d_out);
+    else if (!(skip & 4))
+        hipLaunchKernelGGL(k_rec_scatter<false>, g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_nl, super_nl, tile_pre, super_seq,
+                           d_info, d_lut, pm, hc, flat, (uint64_t)flat_base, start_bits, ix->first_bad, d_out);
     if (!(skip & 8))
         hipLaunchKernelGGL(k_rec_uniform, dim3(grid_for(ix, (n_bytes / 32 + 256) / 256, 4)), dim3(256), 0, cs, start_bits,
                            (uint64_t)flat_base, d_info, d_out);
@@ -1986,7 +2032,8 @@ static int rec_launch_flat(kmm_index_t *ix, const uint32_t *flat, int64_t total,
 
 // One piece, compacted and mapped by itself (the unwrapped pieces of multi-line FASTA come this way).
 static int map_records_piece_radix(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, int64_t n_bytes, int format, int k,
-                                   int max_freq, int also_revcomp, const uint8_t *d_lut, int64_t *consumed, int64_t *n_records)
+                                   int max_freq, int also_revcomp, const uint8_t *d_lut, bool has_break, int64_t *consumed,
+                                   int64_t *n_records)
 {
     const size_t n_words = (size_t)n_bytes / 32 + 2, code_bytes = ((size_t)n_bytes / 4 + 256) & ~(size_t)15;
     KMMCHK(ensure(s.start_bits, n_words * 4));
@@ -1995,7 +2042,7 @@ static int map_records_piece_radix(kmm_index_t *ix, Stage &s, const uint8_t *d_r
     HIPCHK(hipMemsetAsync(s.start_bits.p, 0, n_words * 4, ix->stream));
     HIPCHK(hipMemsetAsync(s.kmers.p, 0, code_bytes, ix->stream));
     int64_t flat_end = 0, L = 0;
-    KMMCHK(rec_compact_piece(ix, s, d_raw, n_bytes, format, d_lut, 0, (uint32_t *)s.kmers.p, (uint32_t *)s.start_bits.p, consumed,
+    KMMCHK(rec_compact_piece(ix, s, d_raw, n_bytes, format, d_lut, has_break, 0, (uint32_t *)s.kmers.p, (uint32_t *)s.start_bits.p, consumed,
                              n_records, &flat_end, &L));
     if (*consumed <= 0 || flat_end <= 0)
         return KMM_OK;
@@ -2018,7 +2065,8 @@ static int map_records_radix_call(kmm_index_t *ix, const uint8_t *raw, int64_t n
     ix->map_calls++;
     bool staged = false;
     const uint8_t *d_lut = nullptr;
-    KMMCHK(resolve_lut(ix, s, lut, &d_lut, &staged));
+    bool has_break = false;
+    KMMCHK(resolve_lut(ix, s, lut, &d_lut, &staged, &has_break));
     if (staged)
         KMMCHK(stage_copies_done(ix)); // (a caller's lookup table staged from the host)
     const bool on_device = is_device_ptr(raw);
@@ -2042,7 +2090,7 @@ static int map_records_radix_call(kmm_index_t *ix, const uint8_t *raw, int64_t n
             d_raw = (const uint8_t *)s.bases.p;
         }
         int64_t used = 0, nr = 0, flat_end = flat, Lp = 0;
-        KMMCHK(rec_compact_piece(ix, s, d_raw, len, format, d_lut, flat, (uint32_t *)s.kmers.p, (uint32_t *)s.start_bits.p, &used, &nr,
+        KMMCHK(rec_compact_piece(ix, s, d_raw, len, format, d_lut, has_break, flat, (uint32_t *)s.kmers.p, (uint32_t *)s.start_bits.p, &used, &nr,
                                  &flat_end, &Lp));
         if (used > 0) {
             L = (L == -1 || L == Lp) ? Lp : 0; // one length over all pieces, or none
@@ -2083,9 +2131,11 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     ReadsView rv;
     memset(&rv, 0, sizeof rv);
     KMMCHK(stage_in<uint8_t>(ix, s.bases, raw, (size_t)n_bytes, &rv.bases, &staged));
-    KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &staged));
+    bool has_break = false;
+    KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &staged, &has_break));
     if (records_take_radix(ix, n_bytes, format)) {
-        KMMCHK(map_records_piece_radix(ix, s, rv.bases, n_bytes, format, k, max_freq, also_revcomp, rv.lut, consumed, n_records));
+        KMMCHK(map_records_piece_radix(ix, s, rv.bases, n_bytes, format, k, max_freq, also_revcomp, rv.lut, has_break, consumed,
+                                       n_records));
         return stage_release(ix, s, false);
     }
     const int64_t n_tiles = (n_bytes + TILE_T - 1) / TILE_T;
@@ -2117,7 +2167,10 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         rv.period_mask = (uint32_t)format - 1u;
         rv.header_char = format == KMM_FORMAT_FASTQ ? (uint32_t)'@' : (uint32_t)'>';
         KMMCHK(stage_copies_done(ix));
-        KMMCHK(launch_map_reads<MODE_RECORDS>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
+        if (has_break) // (a break byte on a sequence line: a break like the bytes outside the sequence lines)
+            KMMCHK(launch_map_reads<MODE_RECORDS_BRK>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
+        else
+            KMMCHK(launch_map_reads<MODE_RECORDS>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
     }
     return stage_release(ix, s, false);
 }
@@ -2289,6 +2342,7 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     if (!raw)
         return fail(KMM_ERR_INVALID_ARG, "raw is NULL");
     HIPCHK(hipSetDevice(ix->device));
+    KMMCHK(check_k_lut(k, lut));
     // chunks beyond 2^30 bytes are mapped piece by piece: every piece starts where the previous one's last complete
     // record ended, so the pieces cut the chunk exactly as one census over all of it would
     // (multi-line FASTA and SAM are turned into two-line FASTA on the device first: never the host packer, whose parser knows
@@ -2563,6 +2617,7 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
     if (!ix)
         return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
     KMMCHK(check_k(c.k));
+    KMMCHK(check_k_lut(c.k, c.lut));
     c.last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
     c.new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
     c.fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
@@ -3379,6 +3434,9 @@ int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offs
     } else {
         default_lut(lutbuf);
     }
+    if (e == hipSuccess && memchr(lutbuf, KMM_LUT_BREAK, 256))
+        return fail(KMM_ERR_INVALID_ARG, "kmm_extract_kmers: the lookup table has a break entry (KMM_LUT_BREAK); n_out is "
+                    "defined per read, which a break would split");
     unsigned long long bad[2] = {NO_BAD, NO_BAD};
     int64_t produced = 0;
     const int64_t n_tiles = (total + TILE_T - 1) / TILE_T;

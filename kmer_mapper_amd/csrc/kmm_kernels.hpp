@@ -135,6 +135,76 @@ __global__ void k_mark_starts(const int64_t *__restrict__ offs, int64_t n_reads,
     }
 }
 
+// Reads of one length whose lookup table has a break entry take the ragged front end: their arithmetic starts
+// r * read_len, r = 0 .. n_reads, into the same bitset (no offsets array is made for them).
+__global__ void k_mark_uniform_starts(int64_t n_reads, int64_t read_len, uint32_t *__restrict__ bits)
+{
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n_reads; r += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = r * read_len;
+        atomicOr(&bits[o >> 5], 1u << (o & 31));
+    }
+}
+
+// Break bytes (lookup table entry KMM_LUT_BREAK: N, IUPAC letters) -> the read-start bitset.  A break at flat position b
+// is a one-base read: bits b and b + 1.  With "no read start inside (p, p + k - 1]" (k >= 2) the window that starts at b
+// dies of bit b + 1 and every earlier window that contains b of bit b; the windows behind b live.  So the mapping
+// kernels need no notion of a break: this pre-pass runs only for calls whose table has a break entry.
+// A pure stream: one byte per base in, one bit per base (touched only where a break is) out.  Per round a workgroup
+// takes 16 KiB: BRK_U 16-byte loads per lane, all issued before the first is consumed; each byte goes through an LDS
+// copy of the table (1 = break) into a 16-position mask, two neighbouring lanes make one 32-position word, and the
+// even lane ORs word | word << 1 into the bitset — one atomic per word that holds a break, plus one for bit 31's
+// carry into the next word.  bits: total / 32 + 2 words (bit `total` may be set by the last base).
+constexpr int BRK_U = 4;
+__global__ void __launch_bounds__(256) k_mark_breaks(const uint8_t *__restrict__ bases, int64_t total,
+                                                     const uint8_t *__restrict__ lut, uint32_t *__restrict__ bits)
+{
+    __shared__ uint32_t s_brk[256];
+    s_brk[threadIdx.x] = lut[threadIdx.x] == KMM_LUT_BREAK ? 1u : 0u;
+    __syncthreads();
+    const bool aligned = (((uintptr_t)bases) & 15u) == 0;
+    constexpr int64_t SPAN = (int64_t)256 * 16 * BRK_U;
+    for (int64_t base = (int64_t)blockIdx.x * SPAN; base < total; base += (int64_t)gridDim.x * SPAN) {
+        uint32_t w[BRK_U][4];
+#pragma unroll
+        for (int u = 0; u < BRK_U; ++u) {
+            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
+            if (p + 16 <= total) {
+                u32x4 x;
+                if (aligned)
+                    x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bases + p));
+                else
+                    __builtin_memcpy(&x, bases + p, 16); // (one unaligned 16-byte load: rec_load16)
+                w[u][0] = x[0]; w[u][1] = x[1]; w[u][2] = x[2]; w[u][3] = x[3];
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    w[u][i] = p < total ? tile_load_bytes4(bases, total, p + 4 * i) : 0u;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < BRK_U; ++u) {
+            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
+            uint32_t m = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                m |= s_brk[(w[u][i >> 2] >> (8 * (i & 3))) & 0xFFu] << i;
+            const int64_t left = total - p; // (bytes past the end of the chunk are staged as 0, which may be a break entry)
+            if (left < 16)
+                m &= left > 0 ? (1u << left) - 1u : 0u;
+            const uint32_t hi = (uint32_t)__shfl_xor((int)m, 1);
+            if (!(threadIdx.x & 1u)) {
+                const uint32_t word = m | (hi << 16);
+                if (word) {
+                    const int64_t wi = p >> 5; // (p is a multiple of 32 for even lanes)
+                    atomicOr(&bits[wi], word | (word << 1));
+                    if (word >> 31)
+                        atomicOr(&bits[wi + 1], 1u);
+                }
+            }
+        }
+    }
+}
+
 // read_offsets must be non-decreasing; checked here (off the host's critical path) and reported at the
 // next synchronising call.  A violation cannot make the map kernels touch memory out of bounds.
 __global__ void k_check_offsets(const int64_t *__restrict__ offs, int64_t n_reads, unsigned long long *first_bad)

@@ -57,6 +57,10 @@ struct ReadsView {
 };
 
 enum { MODE_GENERAL = 0, MODE_UNIFORM = 1, MODE_RECORDS = 2, MODE_PACKED = 4 }; // (3 = MODE_KMERS, kmm_radix.hpp)
+// Records mode for a lookup table with a break entry (KMM_LUT_BREAK): a sequence byte with that entry is a break like the
+// bytes outside the sequence lines.  A mode of its own, so that the kernels of every other table carry no test for it.
+enum { MODE_RECORDS_BRK = 6 };
+constexpr bool mode_is_records(int mode) { return mode == MODE_RECORDS || mode == MODE_RECORDS_BRK; }
 
 // Exact x % m for any m >= 1 with one 64x64->hi multiply: q = hi64(x * floor(2^64/m)) is either
 // floor(x/m) or one less (x * (2^64/m - magic) / 2^64 < 1), so a single conditional subtract

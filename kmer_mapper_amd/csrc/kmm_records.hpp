@@ -503,6 +503,11 @@ __global__ void __launch_bounds__(1024) k_rec_seq_scan(const unsigned long long 
 // without a code, [1] a record line that does not start with the header character / '+' (raw byte offsets).
 // (r04 history: 16 bytes per lane and 1 KiB tiles cost ~700 instructions per tile, most of them per-tile overhead —
 // scans, table lookups, loop control — and ran at 1.35 ms per GiB; 64 bytes per lane share that overhead four ways.)
+// BRK (a lookup table with a break entry, KMM_LUT_BREAK): a sequence byte with that entry stays in the 2-bit stream as a
+// one-base read of any code — its flat position f and f + 1 are added to the read starts.  The positions are the
+// compacted ones, so the byte behind the break needs no carry into the next lane or tile (unlike the byte behind a '\r',
+// which is dropped from the stream): f + 1 is that byte's position wherever it lies, or the end of the flat reads.
+template <bool BRK>
 __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__ raw, int64_t n, int64_t n_tiles,
                                                      const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
                                                      const uint32_t *__restrict__ tile_pre, const uint32_t *__restrict__ super_pre,
@@ -621,19 +626,24 @@ __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__
         // (dst0 & 15) + rank: word j of the row is word (dst0 >> 4) + j of the output
         const uint32_t mis = (uint32_t)dst0 & 15u;
         uint32_t q = mis + pre, bad = 0xFFFFFFFFu;
+        uint64_t brk = 0; // BRK: the lane's sequence bytes that are breaks
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const uint32_t seq16 = (uint32_t)(seq >> (16 * j)) & 0xFFFFu;
             if (!seq16)
                 continue;
-            uint32_t call = 0, bad_m = 0;
+            uint32_t call = 0, bad_m = 0, brk_m = 0;
 #pragma unroll
             for (uint32_t i = 0; i < 16u; ++i) {
                 const uint32_t l = s_lut[(cur.w[j][i >> 2] >> (8u * (i & 3u))) & 0xFFu];
                 bad_m |= (l == 0xFFu ? 1u : 0u) << i;
+                if (BRK)
+                    brk_m |= (l == (uint32_t)KMM_LUT_BREAK ? 1u : 0u) << i;
                 call |= (l & 3u) << (2u * i);
             }
             bad_m &= seq16;
+            if (BRK)
+                brk |= (uint64_t)(brk_m & seq16) << (16 * j);
             if (bad_m && bad == 0xFFFFFFFFu)
                 bad = 16u * (uint32_t)j + (uint32_t)__builtin_ctz(bad_m);
             uint32_t cw = 0, k2 = 0, m = seq16;
@@ -654,6 +664,15 @@ __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__
         }
         if (bad != 0xFFFFFFFFu)
             atomicMin(&first_bad[0], (unsigned long long)(p + bad));
+        if (BRK) {
+            while (brk) { // (rare: one pair of marks per break byte)
+                const uint32_t i = (uint32_t)__builtin_ctzll(brk);
+                brk &= brk - 1ull;
+                const uint64_t f = dst0 + pre + (uint32_t)__popcll(seq & ((1ull << i) - 1ull));
+                atomicOr(&start_bits[f >> 5], 1u << (f & 31u));
+                atomicOr(&start_bits[(f + 1u) >> 5], 1u << ((f + 1u) & 31u));
+            }
+        }
         __builtin_amdgcn_wave_barrier();
         // words only this tile writes by plain stores; the first and last word may be shared with the neighbouring tiles
         const uint32_t n_w = (mis + tot + 15u) >> 4;       // words of the row that hold codes

@@ -96,7 +96,7 @@ __device__ __forceinline__ void tile_load_vec(const ReadsView &rv, const TileCon
 {
     constexpr int T = TileSmem<S>::T;
     constexpr int NV = TileSmem<S>::NV;
-    constexpr int NMAIN = MODE == MODE_RECORDS ? NV : T / 16;
+    constexpr int NMAIN = mode_is_records(MODE) ? NV : T / 16;
     static_assert(NMAIN <= 256, "one staged 16-byte vector per thread");
     raw.w[0] = raw.w[1] = raw.w[2] = raw.w[3] = 0u;
     raw.halo = 0u;
@@ -132,7 +132,7 @@ __device__ __forceinline__ void tile_load_vec(const ReadsView &rv, const TileCon
                 raw.w[i] = tile_load_bytes4(rv, p + i * 4);
         }
     }
-    if (MODE != MODE_RECORDS && tid < 12) {
+    if (!mode_is_records(MODE) && tid < 12) {
         const int64_t p = tile * T + T + (int64_t)tid * 4;
         if (tc.aligned && p + 4 <= total)
             raw.halo = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(rv.bases + p));
@@ -153,7 +153,7 @@ __device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileCo
 {
     const uint32_t (&w)[4] = raw.w;
     constexpr bool UNIFORM = MODE == MODE_UNIFORM;
-    constexpr bool RECORDS = MODE == MODE_RECORDS;
+    constexpr bool RECORDS = mode_is_records(MODE);
     constexpr int T = TileSmem<S>::T;
     constexpr int NV = TileSmem<S>::NV;
     constexpr int NB = TileSmem<S>::NB;
@@ -199,8 +199,10 @@ __device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileCo
                 const uint32_t line = line0 + (uint32_t)__popc(nl & ((1u << i) - 1u));
                 const uint32_t phase = line & rv.period_mask;
                 const bool term = ((nl | cr) >> i) & 1u;
-                const bool is_seq = phase == 1u && !term && p + i < total;
                 const uint32_t l = sm.lut[c];
+                bool is_seq = phase == 1u && !term && p + i < total;
+                if (MODE == MODE_RECORDS_BRK) // (a break byte: a base of its read that no window may contain)
+                    is_seq = is_seq && l != KMM_LUT_BREAK;
                 if (is_seq && l == 0xFFu)
                     bad = i;
                 if (((first >> i) & 1u) && p + i < total &&

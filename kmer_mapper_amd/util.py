@@ -9,6 +9,28 @@ import numpy as np
 
 from .engine import extract_kmers
 
+LUT_BREAK = 0xFE      # KMM_LUT_BREAK (include/kmm.h): a base that no k-mer may contain
+AMBIGUOUS_LETTERS = "NRYKMSWBDHV"   # N and the ten IUPAC ambiguity codes
+
+
+def default_lut():
+    """The table behind lut=None: A C G T -> 0 1 2 3 in both cases, N -> A (command_line_interface.py:41), every other
+    byte 0xFF (not a nucleotide)."""
+    lut = np.full(256, 0xFF, dtype=np.uint8)
+    for code, letter in enumerate("ACGT"):
+        lut[ord(letter)] = lut[ord(letter.lower())] = code
+    lut[ord("N")] = lut[ord("n")] = 0
+    return lut
+
+
+def ambiguous_skip_lut():
+    """The default table with N and the IUPAC ambiguity letters R Y K M S W B D H V, both cases, set to the break code: a
+    k-mer that contains one of them is not counted, the windows on either side are (`--ambiguous-bases skip`)."""
+    lut = default_lut()
+    for letter in AMBIGUOUS_LETTERS:
+        lut[ord(letter)] = lut[ord(letter.lower())] = LUT_BREAK
+    return lut
+
 
 class ReadBatch:
     """A chunk of reads: `bases` uint8[sum(len)] (ASCII), `offsets` int64[n_reads+1].
