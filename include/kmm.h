@@ -413,6 +413,16 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *   "radix_filter"     1 (default) = pass 2 drops the k-mers whose bucket is empty (they cannot match: mapper.pyx:55-58)
  *                      wherever a coarse partition's occupancy bitmap fits 64 KB of LDS, at one bit per bucket or — sparse
  *                      tables — per 2 or 4 buckets ("radix_filter_buckets_per_bit", read-only); the fan-out is chosen for it
+ *   "radix_filter_slots" 1 (default) = where the coarse partitions have exactly 2^19 buckets at one bit per bucket (the
+ *                      fan-out chosen for the filter: the 10 M- and 100 M-k-mer indexes) the filter spends 3 bits per PAIR
+ *                      of buckets, keyed by bucket and by the k-mer's quotient (96 KB of LDS; an array of 96 KB per coarse
+ *                      partition in HBM, optional like the bitmap): 28 % of the absent k-mers pass instead of 39 % at
+ *                      load factor 0.5, the counts are the same.  0 = the bucket bitmap there too (also: environment
+ *                      variable KMM_RX_FILTER_SLOTS=0 at creation).  "radix_filter_bits_per_partition" (read-only): the
+ *                      filter bits of one coarse partition in LDS — 786432, or 524288 and fewer with the bitmap, 0
+ *                      without a filter.  The sort buffer beside the slot filter holds 5888 k-mers: an item with more
+ *                      survivors is placed and copied out in rounds ("radix_p2_multi_round_items", read-only, counts
+ *                      them since the statistics were last reset)
  *   "radix_packed_tiles" 1 (default) = pass 1 on reads of one length works on tiles of whole reads (no windows across
  *                      read boundaries are computed)
  *   "fine_bits"        experiments: log2 fine partitions per coarse partition of the radix path
@@ -466,6 +476,8 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      the compaction kernels of kmm_map_records on the copy stream, next to the radix passes; skip one
  *                      of them; directory sums of pass 1) and of the tests ("debug_rx_buffer_limit": a pass-1 buffer
  *                      beyond that many bytes counts as out of memory: the call takes more sub-batches;
+ *                      "debug_p2f_round_slots": slots of pass 2's sort buffer in use beside the slot filter, even, in
+ *                      [512, 5888] — ordinary batches then take several rounds per item;
  *                      "debug_skew_p2_counter": trips the conservation check; "debug_ring_slot_kb": slot size of the
  *                      page-locked staging ring): not for callers, no effect at 0
  * Read-only (kmm_get_param): "radix_available", "radix_unavailable_reason" (0 available, 1 modulo >= 2^31, 2 slices too

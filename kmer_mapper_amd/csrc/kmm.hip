@@ -271,7 +271,10 @@ struct RxDir16 {
     DevPtr<uint32_t> rx_slice_e0;   // part_shift; null when a slice holds more than 65535 entries or HBM is short)
     DevPtr<uint16_t> rx_slice_fmax; // largest frequency of every slice (with the two above)
 };
-struct RxArrays : RxDir16 {
+struct RxSlotFilter {
+    DevPtr<uint32_t> rx_slots;      // [F1][P2F_SLOT_WORDS] pass 2's slot filter (rx_filter_slot) for the current (w, f2); null where
+};                                  // the geometry has none (RxGeometry::slot_filter), it is switched off, or HBM is short
+struct RxArrays : RxDir16, RxSlotFilter {
     uint64_t rx_S = 0;        // entries in bucket order
     DevPtr<uint32_t> rx_pstart;
     DevPtr<uint64_t> rx_pkeys;     // packed form for the current (w, f2)
@@ -386,6 +389,8 @@ struct kmm_index : IndexStreams, RxArrays {
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
     int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
+    bool rx_filter_slots = true;  // "radix_filter_slots": where the geometry allows it the filter is the slot filter (0: the bucket bitmap)
+    uint32_t dbg_p2f_cap = P2F_SLOTS; // test hook ("debug_p2f_round_slots"): sort-buffer slots k_rx_p2f uses beside the slot filter
     bool rx_packed = true;        // "radix_packed_tiles": pass 1 on reads of one length takes tiles of whole reads
     bool ecnt_dirty = false;  // rx_ecnt holds hits that are not in `counts` yet
     bool rx_unchecked = false; // radix passes have run since the conservation counters were last compared (drain)
@@ -462,6 +467,8 @@ struct ScopedTimer {
 };
 
 int rx_flush(kmm_index *ix); // (kmm_radix_host.hpp)
+int rx_build_slots(kmm_index *ix);
+bool rx_slots_active(const kmm_index *ix);
 int rx_check_conservation(kmm_index *ix);
 int ensure_direct(kmm_index *ix);
 constexpr size_t KMM_STAT_BYTES = (size_t)KMM_STAT_SHARDS * KMM_STAT_STRIDE * 8;
@@ -3731,6 +3738,17 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
             if (rc != RX_REFUSED)
                 KMMCHK(rc);
         }
+    } else if (!strcmp(name, "radix_filter_slots")) {
+        // 1 (default): coarse partitions of 2^19 buckets are filtered with 3 bits per bucket pair keyed by bucket and
+        // quotient (rx_filter_slot); 0: with the bucket bitmap, as every other geometry
+        ix->rx_filter_slots = value != 0;
+        if (ix->rx_pstart && ix->rx_ok)
+            KMMCHK(rx_build_slots(ix));
+    } else if (!strcmp(name, "debug_p2f_round_slots")) {
+        // test hook of the rounds of k_rx_p2f's placement: sort-buffer slots in use beside the slot filter
+        if (value < 512 || value > P2F_SLOTS || (value & 1))
+            return fail(KMM_ERR_INVALID_ARG, "debug_p2f_round_slots must be even and in [512, %d]", P2F_SLOTS);
+        ix->dbg_p2f_cap = (uint32_t)value;
     } else if (!strcmp(name, "fine_bits")) {
         // experiments: split the current slice width's fan-out as F2 = 2^value fine partitions per coarse partition
         const int rc = value < 0 || value > 9 ? RX_REFUSED : rx_reconfigure(ix, ix->rx_geo.w, (int)value, true);
@@ -3967,6 +3985,14 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->rx_ok ? rx_p3_shape(rx_p3_variant(ix)).keys_in_lds : 0;
     else if (!strcmp(name, "radix_filter_buckets_per_bit")) // 1, 2 or 4 (0: no filter)
         *value = (ix->rx_ok && rx_filter_active(ix)) ? (1 << ix->rx_geo.occ_shift) : 0;
+    else if (!strcmp(name, "radix_filter_slots")) // 1: pass 2 filters with the slot filter
+        *value = (ix->rx_ok && rx_slots_active(ix)) ? 1 : 0;
+    else if (!strcmp(name, "radix_filter_bits_per_partition")) // filter bits of one coarse partition in LDS (0: no filter)
+        *value = !(ix->rx_ok && rx_filter_active(ix)) ? 0
+                 : rx_slots_active(ix)                ? (int64_t)P2F_SLOT_WORDS * 32
+                                                      : (int64_t)1 << (ix->rx_geo.w + ix->rx_geo.f2 - ix->rx_geo.occ_shift);
+    else if (!strcmp(name, "debug_p2f_round_slots"))
+        *value = ix->dbg_p2f_cap;
     else if (!strcmp(name, "radix_packed_tiles"))
         *value = ix->rx_packed ? 1 : 0;
     else if (!strcmp(name, "n_fine_per_coarse"))
@@ -3976,7 +4002,7 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
     else if (!strcmp(name, "n_coarse_partitions"))
         *value = ix->rx_ok ? ix->rx_geo.F1 : 0;
     else if (!strcmp(name, "radix_p2_kmers") || !strcmp(name, "radix_p3_kmers") || !strcmp(name, "radix_p2_dropped") ||
-             !strncmp(name, "stats_slot_", 11)) {
+             !strcmp(name, "radix_p2_multi_round_items") || !strncmp(name, "stats_slot_", 11)) {
         // conservation check of the radix path: k-mers gathered by pass 2 / probed by pass 3 since the last
         // kmm_get_stats(reset): both must equal the lookups pass 1 emitted
         HIPCHK(hipSetDevice(ix->device));
@@ -3985,6 +4011,7 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         HIPCHK(hipMemcpy(st.data(), ix->stats, KMM_STAT_BYTES, hipMemcpyDeviceToHost));
         // ("stats_slot_<n>": raw counter n of the statistics block; slots 4.. are only written by diagnostic builds)
         const int slot = name[0] == 's' ? atoi(name + 11) : !strcmp(name, "radix_p2_dropped") ? KMM_STAT_RX_DROPPED
+                                                          : !strcmp(name, "radix_p2_multi_round_items") ? KMM_STAT_RX_MULTI
                                                           : name[7] == '2' ? 2 : 3;
         if (slot < 0 || slot >= KMM_STAT_STRIDE)
             return fail(KMM_ERR_INVALID_ARG, "unknown parameter '%s'", name);

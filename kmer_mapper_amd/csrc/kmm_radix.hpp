@@ -123,6 +123,8 @@ struct RxView {
     const uint16_t *pfreq;  // [S]
     uint32_t *ecnt;         // [S] per-entry hit counts not yet added to the node counts
     const uint32_t *occ;    // bit h = bucket h holds an entry (padded by one coarse partition's worth of words), or null
+    const uint32_t *slots;  // [F1][P2F_SLOT_WORDS] pass 2's slot filter (rx_filter_slot), partition-major; null: the bitmap serves
+    uint32_t p2f_cap;       // k_rx_p2f with the slot filter: slots of its sort buffer in use (P2F_SLOTS; fewer: test hook)
     uint32_t p2f_k;         // k_rx_p2f: items per work unit (one bitmap load, one pipeline fill: 16 / 32 / 64 items measured
                             // 4.47 / 4.40 / 4.36 ms at configs[2]); fewer for small batches, so that every CU gets units
     int w, f2;              // sh = w + f2: hash bits below the coarse partition number
@@ -351,15 +353,23 @@ struct RxNoHook {
 // non-temporal copy-out), one after the placement.  ENDBAR = false leaves out the one after the copy-out:
 // the caller then guarantees a barrier of its own before sbuf is written again and before the next call's ranking
 // (which needs the counters this call clears during its copy-out).
+// CAPMAX < RX_B: sbuf holds fewer slots than the workgroup has k-mers — `cap` of them (even, <= CAPMAX; uniform).  A call
+// whose keyed k-mers outnumber them places and copies out in ROUNDS: round r holds the sorted positions [r cap, (r + 1) cap);
+// the placement is predicated on the position, positions are recomputed from the ranks and the bases, a barrier pair lies
+// between two rounds.  `total <= cap` is a uniform test in front of all that: the one-round path is the code of
+// CAPMAX = RX_B, barrier for barrier.  multi_stat: counter that gets one more for every call that took several rounds.
 template <int RB, bool ENDBAR, bool ONEBAR, int NT = RX_NT, bool NTSTORE = ONEBAR, typename PrepFn,
-          typename MidFn = RxNoHook, int WAVESCAN = 0, bool NOWTID = false, typename PostFn = RxNoHook>
+          typename MidFn = RxNoHook, int WAVESCAN = 0, bool NOWTID = false, typename PostFn = RxNoHook, int CAPMAX = RX_B>
 __device__ __forceinline__ void rx_sort_emit(uint64_t (&q)[RX_B / NT], PrepFn prep, int F, uint64_t *sbuf,
                                              uint32_t *s_cnt, uint32_t *s_base, uint32_t *s_wave,
                                              uint64_t *__restrict__ out, uint16_t *__restrict__ dir_row,
                                              unsigned long long *pt_acc = nullptr, MidFn mid = MidFn(),
                                              int n_slots = RX_B / NT, int wave_s = -1, PostFn post = PostFn(),
-                                             uint64_t *probe_out = nullptr, int probe_den = 0)
+                                             uint64_t *probe_out = nullptr, int probe_den = 0, uint32_t cap = RX_B,
+                                             unsigned long long *multi_stat = nullptr)
 {
+    static_assert(CAPMAX <= RX_B && CAPMAX % 2 == 0, "rounds start at 16-byte boundaries of the output");
+    constexpr bool ROUNDS = CAPMAX < RX_B;
     // `post` runs after the placement, before its barrier (pass 1 stages the NEXT tile's codes there: that barrier then
     // also publishes them and the tile's own barrier goes)
     // NOWTID: the thread index is rebuilt from the wavefront's number wave_s (uniform, a scalar register) behind every
@@ -402,7 +412,29 @@ __device__ __forceinline__ void rx_sort_emit(uint64_t (&q)[RX_B / NT], PrepFn pr
     RX_PT(2); // keys + ranks
     mid();
     uint32_t total;
-    if (WAVESCAN == 2 || (WAVESCAN == 1 && F <= 128)) { // (2: the caller guarantees F <= 128 — no other form is compiled)
+    uint32_t packed = 0; // (per-wavefront scan: the bases, two per lane)
+    const bool by_wave = WAVESCAN == 2 || (WAVESCAN == 1 && F <= 128); // (2: the caller guarantees F <= 128 — no other form is compiled)
+    // where slot h goes in the sorted order (the rounds beyond the first recompute it)
+    auto pos_of = [&](int h) {
+        const uint32_t key = cr[h] >> 16;
+        if (by_wave) {
+            const uint32_t pk = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((key >> 1) << 2), (int)packed);
+            return (pk & 0xFFFFu) + ((key & 1u) ? pk >> 16 : 0u) + (cr[h] & 0xFFFFu);
+        }
+        return s_base[key < (uint32_t)F ? key : 0u] + (cr[h] & 0xFFFFu);
+    };
+    // first round of several: only the positions below cap
+    auto place_first = [&]() {
+#pragma unroll
+        for (int h = 0; h < KPT; ++h) {
+            if (h >= n_slots)
+                break;
+            const uint32_t pos = pos_of(h);
+            if ((cr[h] >> 16) < (uint32_t)F && pos < cap)
+                sbuf[pos] = q[h];
+        }
+    };
+    if (by_wave) {
         // Fan-outs up to 128: EVERY wavefront scans the counters for itself (two per lane, six DPP additions) and keeps
         // the bases in registers — a k-mer's base comes from lane key / 2 through the LDS crossbar (ds_bpermute) instead
         // of an LDS table the whole workgroup would have to wait for at a barrier.
@@ -419,7 +451,10 @@ __device__ __forceinline__ void rx_sort_emit(uint64_t (&q)[RX_B / NT], PrepFn pr
             if (lane == 63 && F == 128)
                 dir_row[128] = (uint16_t)inc;
         }
-        const uint32_t packed = ex0 | (p.x << 16); // (both <= 8192)
+        packed = ex0 | (p.x << 16); // (both <= 8192)
+        if (ROUNDS && total > cap) { // (uniform)
+            place_first();
+        } else {
 #pragma unroll
         for (int h = 0; h < KPT; ++h) {
             if (h >= n_slots)
@@ -429,6 +464,7 @@ __device__ __forceinline__ void rx_sort_emit(uint64_t (&q)[RX_B / NT], PrepFn pr
             const uint32_t pos = (pk & 0xFFFFu) + ((key & 1u) ? pk >> 16 : 0u) + (cr[h] & 0xFFFFu);
             if (key < (uint32_t)F)
                 sbuf[pos] = q[h];
+        }
         }
     } else {
     tid = tid_now();
@@ -452,6 +488,9 @@ __device__ __forceinline__ void rx_sort_emit(uint64_t (&q)[RX_B / NT], PrepFn pr
     // (one slot after the other: reading all 16 run starts first and then writing — 16 overlapping LDS round trips —
     // measured SLOWER, pass 1 4.41 vs 3.62 ms, pass 2 4.75 vs 4.30 ms; a slot without a k-mer is skipped under
     // predication: writing it to a dummy element instead measured slower in k_rx_p2f, 3.70 vs 3.60 ms)
+    if (ROUNDS && total > cap) { // (uniform)
+        place_first();
+    } else {
 #pragma unroll
     for (int h = 0; h < KPT; ++h) {
         if (h >= n_slots)
@@ -461,11 +500,12 @@ __device__ __forceinline__ void rx_sort_emit(uint64_t (&q)[RX_B / NT], PrepFn pr
             sbuf[pos] = q[h];
     }
     }
+    }
     post();
     __syncthreads();
     RX_PT(3); // scan + placement
     tid = tid_now();
-    if (WAVESCAN == 2 || (WAVESCAN == 1 && F <= 128)) {
+    if (by_wave) {
         // (per-wavefront scans read the counters up to here; the callers of this form alternate between two counter
         // arrays, so the next ranking never touches the array cleared now)
         if (tid <= F)
@@ -475,7 +515,8 @@ __device__ __forceinline__ void rx_sort_emit(uint64_t (&q)[RX_B / NT], PrepFn pr
     }
     const uint4 *s4 = reinterpret_cast<const uint4 *>(sbuf);
     uint4 *o4 = reinterpret_cast<uint4 *>(out);
-    for (uint32_t i = tid; i < (total + 1) / 2; i += NT) {
+    const uint32_t n_first = ROUNDS && total > cap ? cap : total;
+    for (uint32_t i = tid; i < (n_first + 1) / 2; i += NT) {
         if (NTSTORE) { // (pass 1) streamed out past L2: the directory rows the scan kernels read next stay there
             typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
             const uint4 v = s4[i];
@@ -493,6 +534,28 @@ __device__ __forceinline__ void rx_sort_emit(uint64_t (&q)[RX_B / NT], PrepFn pr
             } else {
                 reinterpret_cast<uint4 *>(probe_out)[i / (uint32_t)probe_den] = s4[i];
             }
+        }
+    }
+    if constexpr (ROUNDS) {
+        if (total > cap) { // (uniform; rare: an item nearly all of whose k-mers survive the filter)
+            for (uint32_t lo = cap; lo < total; lo += cap) {
+                __syncthreads(); // the previous round has been copied out
+#pragma unroll
+                for (int h = 0; h < KPT; ++h) {
+                    if (h >= n_slots)
+                        break;
+                    const uint32_t pos = pos_of(h) - lo; // (below lo: wraps beyond cap)
+                    if ((cr[h] >> 16) < (uint32_t)F && pos < cap)
+                        sbuf[pos] = q[h];
+                }
+                __syncthreads();
+                const uint32_t n = total - lo < cap ? total - lo : cap;
+                uint4 *o4r = reinterpret_cast<uint4 *>(out + lo); // (cap is even: 16-byte aligned)
+                for (uint32_t i = tid; i < (n + 1) / 2; i += NT)
+                    o4r[i] = s4[i];
+            }
+            if (multi_stat && tid == 0)
+                atomicAdd(multi_stat, 1ull);
         }
     }
     if (ENDBAR)
@@ -1271,13 +1334,20 @@ __device__ __forceinline__ uint32_t rx_fold4(uint32_t x)
 constexpr int P2F_NT = 1024;
 constexpr int P2F_KPT = RX_B / P2F_NT;   // 8 k-mers per thread and item
 
-// FILTER false: coarse partitions beyond 2^21 buckets (no bitmap fits) — the kernel is still the faster pass 2
+// FILTER P2F_NONE: coarse partitions beyond 2^21 buckets (no bitmap fits) — the kernel is still the faster pass 2
+// FILTER P2F_SLOT: coarse partitions of exactly 2^19 buckets: the slot filter (rx_filter_slot, kmm_radix_plan.hpp) — 3 bits
+//   per bucket pair, keyed by bucket AND quotient, 96 KB of LDS; 28 % of the absent k-mers pass instead of 39 %.  The 32 KB
+//   more come out of the sort buffer, which the filter keeps half empty: P2F_SLOTS slots; an item with more survivors than
+//   that is placed and copied out in rounds (rx_sort_emit; rx.p2f_cap: the slots in use, fewer only under the test hook)
 // FSMALL: at most 128 fine partitions (the launch knows): only the per-wavefront scan is compiled into the sort
-template <bool FILTER, bool FSMALL>
+enum { P2F_NONE = 0, P2F_BITMAP = 1, P2F_SLOT = 2 };
+template <int FILTER, bool FSMALL>
 __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
 {
-    __shared__ uint32_t s_bits[(1 << P2F_LOGBITS) / 32];
-    __shared__ uint64_t sbuf[RX_B];
+    constexpr bool SLOT = FILTER == P2F_SLOT;
+    constexpr int CAPMAX = SLOT ? P2F_SLOTS : RX_B;
+    __shared__ __attribute__((aligned(16))) uint32_t s_bits[SLOT ? P2F_SLOT_WORDS : (1 << P2F_LOGBITS) / 32];
+    __shared__ __attribute__((aligned(16))) uint64_t sbuf[CAPMAX];
     __shared__ uint32_t t_vs[P2F_NT + 64]; // run table of the item being requested: where run t starts in the
     __shared__ uint32_t t_off[P2F_NT];    // coarse partition's virtual array; t_off[t] + v = where k-mer v of run t lies
                                           // in pass 1's output, relative to the table's first block
@@ -1293,13 +1363,16 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t NB = rx.NB;
     const int F2 = (int)rx.F2, w = rx.w;
-    const uint32_t bmask = (1u << (rx.w + rx.f2)) - 1u;          // bucket inside the coarse partition
+    const uint32_t bmask = SLOT ? (1u << P2F_LOGBITS) - 1u : (1u << (rx.w + rx.f2)) - 1u; // bucket inside the coarse partition
     const uint32_t gs = (uint32_t)rx.occ_shift;                  // buckets per bitmap bit: 2^gs (coarse partitions of
                                                                  // up to 2^21 buckets: sparse tables such as modulo 452 930 477)
-    constexpr bool nofilt = !FILTER;                             // (a template parameter: as a run-time branch around the
+    constexpr bool nofilt = FILTER == P2F_NONE;                             // (a template parameter: as a run-time branch around the
                                                                  // bitmap test it cost 13 % — the test's LDS reads no longer
                                                                  // moved ahead of the requests)
-    const uint32_t nwords = nofilt ? 0u : (((uint32_t)F2 << w) >> gs) / 32u; // bitmap words of one coarse partition in LDS (<= 16384)
+    const uint32_t nwords = nofilt ? 0u : SLOT ? (uint32_t)P2F_SLOT_WORDS
+                                               : (((uint32_t)F2 << w) >> gs) / 32u; // filter words of one coarse partition in LDS
+    unsigned long long *const multi_stat = // items that took several rounds (SLOT only)
+        &iv.stats[(size_t)(blockIdx.x % KMM_STAT_SHARDS) * KMM_STAT_STRIDE + KMM_STAT_RX_MULTI];
     const uint32_t spare = rx_spare_key();
     uint32_t gathered = 0, dropped = 0; // conservation check: gathered = pass 1's lookups = pass 3's probes + dropped
     const uint32_t cs = (rx.F1 + 7u) / 8u;
@@ -1338,12 +1411,12 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
         if ((uint32_t)tid < n_it)
             s_b0[tid] = rx.item_desc[ib + j0 + tid].x;
         if (nofilt) {
-        } else if (gs == 0) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(rx.occ + (size_t)cc * nwords);
+        } else if (SLOT || gs == 0) {
+            const uint4 *src = reinterpret_cast<const uint4 *>((SLOT ? rx.slots : rx.occ) + (size_t)cc * nwords);
             uint4 *dst = reinterpret_cast<uint4 *>(s_bits);
             for (uint32_t i = tid; i < nwords / 4u; i += P2F_NT)
                 dst[i] = src[i];
-            for (uint32_t i = (nwords & ~3u) + tid; i < nwords; i += P2F_NT) // (tiny tables)
+            for (uint32_t i = (nwords & ~3u) + tid; !SLOT && i < nwords; i += P2F_NT) // (tiny tables)
                 s_bits[i] = rx.occ[(size_t)cc * nwords + i];
         } else {
             // the index keeps one bit per bucket; 2 or 4 neighbouring buckets are folded into one LDS bit here
@@ -1562,7 +1635,8 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
 #pragma unroll
                 for (int u = 0; u < P2F_KPT; ++u) {
                     const uint32_t xl = (uint32_t)xa[u]; // packed form: the hash bits below the coarse partition number
-                    const uint32_t bit = (xl & bmask) >> gs; // are the low w + f2 <= 22 bits
+                    const uint32_t bit = SLOT ? rx_filter_slot(xl & bmask, xa[u] >> P2F_LOGBITS) // are the low w + f2 <= 22 bits
+                                              : (xl & bmask) >> gs;
                     const uint32_t ok = (s_bits[bit >> 5] >> (bit & 31u)) & (vma >> u) & 1u;
                     n_ok += ok;
                     keys[u] = ok ? __builtin_amdgcn_ubfe(xl, (uint32_t)w, (uint32_t)rx.f2) : spare;
@@ -1588,10 +1662,11 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
                         rd = load_desc(s_b0[j + 3u]);
                 }
             };
-            rx_sort_emit<P2F_KPT, false, true, P2F_NT, false, decltype(fine), decltype(mid), (FSMALL ? 2 : 1)>(
+            rx_sort_emit<P2F_KPT, false, true, P2F_NT, false, decltype(fine), decltype(mid), (FSMALL ? 2 : 1), false, RxNoHook, CAPMAX>(
                 xa, fine, F2, sbuf, s_cnt2[j & 1u], s_base, s_wave, rx.buf2 + (size_t)item * RX_B,
                 rx.start2 + (size_t)item * (F2 + 1) RX_PT_ARG2, mid, P2F_KPT, -1, RxNoHook(),
-                RX_PROBE_P2W ? rx.probe + (size_t)item * RX_B : nullptr, RX_PROBE_P2W);
+                RX_PROBE_P2W ? rx.probe + (size_t)item * RX_B : nullptr, RX_PROBE_P2W, SLOT ? rx.p2f_cap : (uint32_t)RX_B,
+                SLOT ? multi_stat : nullptr);
             if (tid < RX_B / 32)
                 t_sbits[(j + 1u) & 1u][tid] = 0u; // item j + 1's mask has served (its requests lie before barrier 1); item
             if (tid == 0)                         // j + 3's bits are set behind the next item's barrier 1
@@ -2196,6 +2271,22 @@ __global__ void __launch_bounds__(256) k_rx_pstart16(const uint32_t *__restrict_
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
         slice_e0[PF] = pstart[modulo];
+}
+
+// Pass 2's slot filter (rx_filter_slot): one thread per bucket h sets the bit of each of its entries in the words of its
+// coarse partition h >> sh.  pkeys: the entries in the packed form of the current geometry (k_rx_pack_keys); slots: zeroed.
+__global__ void __launch_bounds__(256) k_rx_build_slots(const uint32_t *__restrict__ pstart, const uint64_t *__restrict__ pkeys,
+                                                       uint64_t modulo, int sh, uint32_t *__restrict__ slots)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t h = (uint64_t)blockIdx.x * 256 + threadIdx.x; h < modulo; h += stride) {
+        uint32_t *part = slots + (size_t)(h >> sh) * P2F_SLOT_WORDS;
+        const uint32_t b = (uint32_t)h & ((1u << sh) - 1u);
+        for (uint32_t e = pstart[h], e1 = pstart[h + 1]; e < e1; ++e) {
+            const uint32_t bit = rx_filter_slot(b, pkeys[e] >> sh);
+            atomicOr(&part[bit >> 5], 1u << (bit & 31u));
+        }
+    }
 }
 
 __global__ void __launch_bounds__(256) k_rx_build_occ(const uint32_t *__restrict__ pstart, uint64_t modulo, uint32_t *__restrict__ occ)

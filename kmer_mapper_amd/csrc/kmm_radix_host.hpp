@@ -45,6 +45,12 @@ bool rx_filter_active(const kmm_index *ix)
     return ix->rx_filter && ix->rx_occ && g.w + g.f2 - g.occ_shift >= 5 && g.occ_shift <= 2;
 }
 
+// ... with the slot filter (rx_filter_slot) where the coarse partitions have exactly 2^19 buckets and the array is there
+bool rx_slots_active(const kmm_index *ix)
+{
+    return rx_filter_active(ix) && ix->rx_geo.slot_filter && ix->rx_filter_slots && ix->rx_slots;
+}
+
 bool use_radix(const kmm_index *ix, int64_t units)
 {
     if (!ix->rx_ok || ix->path == 1)
@@ -67,6 +73,8 @@ RxView rx_view_of(const kmm_index *ix, const RxScratch &sc, uint32_t NB)
     rx.pstart = ix->rx_pstart; rx.pkeys = ix->rx_pkeys; rx.pfreq = ix->rx_pfreq; rx.ecnt = ix->rx_ecnt;
     rx.pstart16 = ix->rx_pstart16; rx.slice_e0 = ix->rx_slice_e0; rx.slice_fmax = ix->rx_slice_fmax;
     rx.occ = ix->rx_occ;
+    rx.slots = rx_slots_active(ix) ? (const uint32_t *)ix->rx_slots : nullptr;
+    rx.p2f_cap = ix->dbg_p2f_cap;
     rx.occ_shift = rx_filter_active(ix) ? g.occ_shift : 3; // (3: k_rx_p2f without its filter)
     rx.p2f_k = NB / 2048u < 4u ? 4u : (NB / 2048u > (uint32_t)P2F_KMAX ? (uint32_t)P2F_KMAX : NB / 2048u);
     rx.w = g.w; rx.f2 = g.f2; rx.PF = g.PF; rx.F1 = g.F1; rx.F2 = g.F2;
@@ -123,10 +131,11 @@ void rx_launch_p2(kmm_index *ix, const IndexView &iv, const RxView &rx)
         return;
     }
     // gather by k-mer; where a coarse partition's occupancy bitmap fits LDS (one bit per 1, 2 or 4 buckets) the k-mers of
-    // empty buckets are dropped here
+    // empty buckets are dropped here; with the slot filter also those whose bucket pair holds no entry that chose their bit
     const bool flt = rx_filter_active(ix), small = rx.F2 <= 128;
-    auto kern = flt ? (small ? k_rx_p2f<true, true> : k_rx_p2f<true, false>)
-                    : (small ? k_rx_p2f<false, true> : k_rx_p2f<false, false>);
+    auto kern = rx.slots ? (small ? k_rx_p2f<P2F_SLOT, true> : k_rx_p2f<P2F_SLOT, false>)
+                : flt    ? (small ? k_rx_p2f<P2F_BITMAP, true> : k_rx_p2f<P2F_BITMAP, false>)
+                         : (small ? k_rx_p2f<P2F_NONE, true> : k_rx_p2f<P2F_NONE, false>);
     hipLaunchKernelGGL(kern, dim3(ix->n_cu), dim3(P2F_NT), 0, ix->stream, iv, rx);
 }
 
@@ -271,7 +280,30 @@ int rx_flush(kmm_index *ix)
     return KMM_OK;
 }
 
-// The entry k-mers in the packed form of the current (w, f2) (kmm_radix.hpp); synchronous.
+// Pass 2's slot filter for the current (w, f2), from the packed keys: built where the geometry has one and "radix_filter_slots"
+// asks for it, dropped otherwise.  Optional: without the HBM for it (96 KB per coarse partition) the bucket bitmap serves.
+// Synchronous.
+int rx_build_slots(kmm_index *ix)
+{
+    static_cast<RxSlotFilter &>(*ix) = RxSlotFilter();
+    if (!ix->rx_filter || !ix->rx_geo.slot_filter || !ix->rx_filter_slots || !ix->rx_occ)
+        return KMM_OK;
+    const size_t bytes = (size_t)ix->rx_geo.F1 * P2F_SLOT_WORDS * 4;
+    if (hipMalloc(ix->rx_slots.put(), bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        static_cast<RxSlotFilter &>(*ix) = RxSlotFilter();
+        return KMM_OK;
+    }
+    HIPCHK(hipMemsetAsync(ix->rx_slots, 0, bytes, ix->stream));
+    hipLaunchKernelGGL(k_rx_build_slots, dim3(grid_for(ix, (int64_t)((ix->modulo + 255) / 256), 16)), dim3(256), 0, ix->stream,
+                       ix->rx_pstart, ix->rx_pkeys, ix->modulo, ix->rx_geo.w + ix->rx_geo.f2, ix->rx_slots);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    return KMM_OK;
+}
+
+// The entry k-mers in the packed form of the current (w, f2) (kmm_radix.hpp), and what else depends on the geometry: the
+// 16-bit directory, the slot filter; synchronous.
 int rx_repack_keys(kmm_index *ix)
 {
     if (ix->rx_S)
@@ -311,7 +343,7 @@ int rx_repack_keys(kmm_index *ix)
             static_cast<RxDir16 &>(*ix) = RxDir16();
         }
     }
-    return KMM_OK;
+    return rx_build_slots(ix);
 }
 
 // Radix-path view of the index (kmm_radix.hpp): entries regrouped in bucket order (whatever order the caller's
@@ -323,6 +355,8 @@ int rx_build(kmm_index *ix, const int32_t *h2i, const int32_t *nk, const uint64_
     const uint64_t M = ix->modulo;
     if (const char *env = getenv("KMM_RX_FILTER")) // experiments: 0 = plain pass 2 and the fan-out chosen without the filter
         ix->rx_filter = atoi(env) != 0;
+    if (const char *env = getenv("KMM_RX_FILTER_SLOTS")) // experiments: 0 = the bucket bitmap where the slot filter would serve
+        ix->rx_filter_slots = atoi(env) != 0;
     ix->rx_why_not = 1;
     if (M >= (1ull << 31))
         return KMM_OK; // beyond the index format's int32 tables: no radix path; the direct path serves every batch

@@ -1,8 +1,9 @@
 // kmm_radix_plan.hpp — part of libkmm (MI355X / gfx950); included by kmm_radix.hpp.
 // The decisions of the radix path that are plain integer arithmetic, each stated once: the fan-out of an index (RxGeometry),
 // the scratch layout of a sub-batch (RxScratch), the split of a batch into sub-batches, which pass-3 kernel runs
-// (RxP3Variant), the bytes of the radix view and the batch size where the radix path takes over.  Standard C++17: no HIP
-// header, no kmm_index — tests/test_radix_plan_on_the_cpu.py compiles it by itself with g++.
+// (RxP3Variant), the bytes of the radix view, the batch size where the radix path takes over, and the bit a k-mer tests in
+// pass 2's slot filter (rx_filter_slot: host, kernels and tests share the one definition).  Standard C++17: no HIP header, no
+// kmm_index — tests/test_radix_plan_on_the_cpu.py and tests/test_radix_filter_slots_on_the_cpu.py compile it by themselves with g++.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -23,6 +24,31 @@ constexpr int RX_ECAP_MID = 4608;     // 8192-bucket slices at load factor 0.5 (
                                       // list, 77 KB of LDS: two workgroups per CU (the 1 B-k-mer index)
 constexpr int P2F_KMAX = 64;             // most items per work unit (rx.p2f_k: chosen per batch, rx_view_of)
 constexpr int P2F_LOGBITS = 19;          // buckets per coarse partition the LDS bitmap covers: 2^19 (64 KB)
+constexpr int P2F_SLOT_WORDS = 3 << (P2F_LOGBITS - 6); // 32-bit words of the slot filter of one coarse partition: 3 bits per
+                                         // bucket PAIR, 3 x 2^18 bits = 96 KB (rx_filter_slot)
+constexpr int P2F_SLOTS = 5888;          // k-mers k_rx_p2f's sort buffer holds beside the slot filter (even; an item with more
+                                         // survivors than that — 72 % of its k-mers — is placed and copied out in rounds).
+                                         // 96 KB + 46 KB + 17.3 KB of tables (fan-outs beyond 128: with the scan's table of
+                                         // bases) = 163 120 of the 163 840 bytes a workgroup may declare; 6144 would not fit
+
+// Pass 2's slot filter, for coarse partitions of exactly 2^P2F_LOGBITS buckets at one bit per bucket (RxGeometry::slot_filter).
+// The bucket bitmap spends 2 bits per entry at load factor 0.5 and passes 1 - e^-0.5 = 39.3 % of the absent k-mers.  Keyed by
+// the k-mer as well it does better with the same kind of test: every pair of buckets shares 3 bits, an entry sets the one
+// its (bucket parity, quotient) selects, and an absent k-mer passes only where an entry of its bucket pair chose the same
+// bit: 1 - e^-1/3 = 28.3 %.  No false negatives: an entry and a k-mer equal to it have the same bucket and quotient.
+//   b: bucket inside the coarse partition (sh = w + f2 bits); quot: the quotient part of the packed form (x >> sh; any
+//   64-bit value).  Returns the bit index in [0, 3 x 2^(sh - 1)).
+// Full-rate operations only (a 32-bit multiply is quarter rate, and pass 2 is as much bound by its vector ALUs as by anything):
+// the quotient folded to 24 bits, the parity xored into bit 23, a 24-bit multiplicative mix (v_mul_u32_u24) whose bits
+// [16, 32) — every one of the 24 input bits reaches the upper ones — are mapped to 0 .. 2 with a second 24-bit multiply.
+// Nine vector instructions per k-mer in k_rx_p2f, where sh is a constant and the quotient has 45 bits.
+constexpr uint32_t rx_filter_slot(uint32_t b, uint64_t quot)
+{
+    const uint32_t v = ((uint32_t)quot ^ (uint32_t)(quot >> 24) ^ (uint32_t)(quot >> 48)) + (b << 23); // (+: one v_lshl_add_u32;
+                                                                       // below bit 24 it is the xor: b << 23 has no lower bits)
+    const uint32_t h16 = ((v & 0xFFFFFFu) * 0x9E3779u) >> 16;
+    return 3u * (b >> 1) + ((h16 * 3u) >> 16);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Geometry: 2^w buckets per fine partition, F2 = 2^f2 fine partitions per coarse one, F1 coarse partitions
@@ -30,6 +56,7 @@ constexpr int P2F_LOGBITS = 19;          // buckets per coarse partition the LDS
 struct RxGeometry {
     int w = 12, f2 = 0;      // log2 buckets per fine partition, log2 fine partitions per coarse one
     int occ_shift = 0;       // k_rx_p2f folds 2^occ_shift buckets into one bit of its LDS bitmap
+    bool slot_filter = false; // coarse partitions of 2^P2F_LOGBITS buckets at one bit per bucket: the slot filter applies
     uint32_t PF = 1, F1 = 1, F2 = 1;
 };
 
@@ -84,6 +111,7 @@ inline std::optional<RxGeometry> rx_geometry(uint64_t modulo, uint64_t S, bool f
     g.f2 = f2;
     g.occ_shift = w + f2 > P2F_LOGBITS ? w + f2 - P2F_LOGBITS : 0; // (the filter's bits never outnumber its LDS;
                                                                    // rx_filter_active refuses more than 2)
+    g.slot_filter = w + f2 == P2F_LOGBITS; // (then occ_shift = 0)
     g.PF = (uint32_t)PF;
     g.F1 = (uint32_t)F1;
     g.F2 = (uint32_t)F2;
