@@ -216,7 +216,9 @@ int kmm_map_reads_uniform(kmm_index_t *idx, const uint8_t *bases, int64_t n_read
  *   - "bam_exclude_flags" (kmm_set_param) leaves out records with FLAG & mask;
  *   - *consumed = the byte after the chunk's last '\n' (a record never spans a newline); '\r' before '\n' is tolerated;
  *   - refused with KMM_ERR_MALFORMED, nothing of the call mapped, the message naming the first bad line's byte offset: a
- *     record line with fewer than 10 TABs, a FLAG that is no decimal integer in [0, 65535], an empty line.
+ *     record line with fewer than 10 TABs, a FLAG that is no decimal integer in [0, 65535], an empty line;
+ *   - refused with KMM_ERR_INVALID_ARG while "min_base_quality" (kmm_set_param) is above 0, on every entry point that takes
+ *     the format: the writer emits two-line FASTA, the QUAL column is not carried to the mapper.
  * Counters (kmm_get_param): "sam_calls", "sam_records", "sam_records_excluded", "sam_header_lines". */
 #define KMM_FORMAT_SAM 8
 int kmm_map_records(kmm_index_t *idx, const uint8_t *raw, int64_t n_bytes, int format, int k,
@@ -298,6 +300,8 @@ int kmm_map_gzip(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int form
  * "bam_exclude_flags" drops records with flag & mask (samtools view -F).  *n_records: records mapped by this call.
  * Counters (kmm_get_param): "bam_calls", "bam_records", "bam_records_excluded", "bam_header_bytes", "bam_false_starts",
  * "bam_continuations".  SAM text is read by kmm_map_bgzf / kmm_map_gzip / kmm_map_records (KMM_FORMAT_SAM); CRAM is not read.
+ * While "min_base_quality" (kmm_set_param) is above 0 the call is refused with KMM_ERR_INVALID_ARG: the records' qual bytes
+ * are not decoded, and ignoring the floor silently is not an option.
  */
 int kmm_map_bam(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int flags, int k, int max_index_lookup_frequency,
                 int also_revcomp, const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
@@ -463,6 +467,24 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      default: every record, as the reference; 0x900 = no secondary and supplementary alignments).  Read-only: "bam_calls",
  *                      "bam_records" (mapped), "bam_records_excluded", "bam_header_bytes", "bam_false_starts" (speculative
  *                      starts the link check rejected), "bam_continuations" (tiles walked again from the exit before them)
+ *   "min_base_quality" a base-quality floor Q for FASTQ, 0 .. 93 (default 0 = off: nothing changes, bit for bit; anything else
+ *                      KMM_ERR_INVALID_ARG).  With Q > 0, on every call that parses KMM_FORMAT_FASTQ records (kmm_map_records,
+ *                      kmm_map_bgzf, kmm_map_gzip), a base whose quality byte q (Phred+33, unsigned — a byte below '!'
+ *                      included) has q < 33 + Q is a break at that base exactly as a KMM_LUT_BREAK byte is: no window that
+ *                      contains it is looked up, forward or reverse complement, the windows on either side are, *n_records
+ *                      is unaffected and kmm_get_stats' n_lookups counts the surviving windows.  A table with break entries
+ *                      combines with it: a base is dead if either rule kills it.  k = 1 is KMM_ERR_INVALID_ARG (as for a
+ *                      break table).  KMM_FORMAT_FASTA2 / KMM_FORMAT_FASTA have no qualities: no effect.  KMM_FORMAT_SAM and
+ *                      kmm_map_bam are refused with KMM_ERR_INVALID_ARG while Q > 0.  The FASTQ piece always takes
+ *                      compaction + the radix path, at every batch size and whatever "path" says (as kmm_map_packed; an
+ *                      index with "radix_available" 0: KMM_ERR_INVALID_ARG), and never the host packer
+ *                      ("host_packed_record_calls" does not move).  A record whose quality line does not have as many
+ *                      non-terminator bytes as its sequence line is KMM_ERR_MALFORMED at the next synchronising call, with
+ *                      the raw byte offset of the quality line's '\n' (with Q = 0 nothing new is checked).  Read-only
+ *                      "quality_masked_bases": sequence bases whose quality byte was below the floor since the statistics
+ *                      were last reset (kmm_get_stats(reset)); synchronises like kmm_get_stats
+ *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
+ *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the
  *                      default, 3.5 GiB) — a small file then reaches the cap.  Read-only "flat_uniform_batches": flat reads
  *                      of one length that took the uniform / packed front ends of the radix path

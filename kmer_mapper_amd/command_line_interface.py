@@ -23,6 +23,11 @@ Differences that follow from replacing the engine (all documented in DESIGN.md):
     k-mer that contains N or an IUPAC ambiguity letter is not counted, the windows on either side of it are
     (util.ambiguous_skip_lut, KMM_LUT_BREAK).  Such a table takes the device routes: the raw bytes of a plain file cross
     PCIe as they are, the host threads do not pack them.
+  * `--min-base-quality Q` (extension; default 0 = off): a FASTQ base whose quality byte is below '!' + Q is treated like such
+    a break — no k-mer over it is counted (kmm_set_param "min_base_quality").  The qualities are read on the
+    GPU, so the flag takes the device routes as a table does (plain, BGZF, gzip); it combines with `--ambiguous-bases
+    skip`.  SAM / BAM input and `--host-parser` hand the library reads without qualities and are refused; FASTA has none:
+    one warning, mapped as before.
 """
 import argparse
 import logging
@@ -126,7 +131,7 @@ def map_gpu(index, chunks, k, hash_map_size=0, map_reverse_complements=False,
     return node_counts
 
 
-def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, lut=None):
+def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, lut=None, min_base_quality=0):
     """How map_gpu_raw reads the file: (route, populate, steer).  fmt: the GPU's record format ("fasta_ml" = wrapped FASTA);
     probe: reads_io.probe_input of the file; env: where the KMM_CLI_* switches of A/B runs are read.
 
@@ -147,7 +152,8 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
     pinned buffer costs more than the overlap returns (3 GB FASTQ: 0.30 s with one buffer, 0.37 s with two), so they take
     route "raw": one pinned buffer (RawChunker).
     lut: a caller's lookup table (--ambiguous-bases skip) is never taken by the host packer, so route "mmap", which counts
-    on it (pageable views of the page cache), gives way to "raw": the bytes cross PCIe from a pinned buffer."""
+    on it (pageable views of the page cache), gives way to "raw": the bytes cross PCIe from a pinned buffer.
+    min_base_quality > 0: the same — the packer drops the quality lines the GPU is to read."""
     gpu_inflate = probe.inflate and fmt in ("fastq", "fasta", "sam") and not env.get("KMM_CLI_NO_GPU_INFLATE")
     if fmt == "bam":
         return "bam", False, False
@@ -157,26 +163,30 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
         return "gzip", False, False
     if probe.inflate:
         return ("raw" if env.get("KMM_CLI_NO_PREFETCH") else "prefetch"), False, False
-    if fmt in ("fastq", "fasta") and n_threads > 1 and has_device and lut is None and not env.get("KMM_CLI_NO_MMAP"):
+    if (fmt in ("fastq", "fasta") and n_threads > 1 and has_device and lut is None and not min_base_quality
+            and not env.get("KMM_CLI_NO_MMAP")):
         return "mmap", not env.get("KMM_CLI_NO_POPULATE"), not env.get("KMM_CLI_NO_PACKER_STEERING")
     return "raw", False, False
 
 
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
-                exclude_flags=0, probe=None, lut=None):
+                exclude_flags=0, probe=None, lut=None, min_base_quality=0):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
     on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
     extracted on the GPU (KMM_FORMAT_SAM on the routes of a FASTQ; exclude_flags filters it too).  probe: reads_io.probe_input
-    of the file, if the caller has it.  lut: the lookup table of every call, on every route (None: the default)."""
+    of the file, if the caller has it.  lut: the lookup table of every call, on every route (None: the default).
+    min_base_quality: the handle's "min_base_quality", set before the first map call on every route (FASTQ alone has qualities:
+    SAM / BAM are refused before the index goes up, FASTA is mapped as before with a warning)."""
     _check_bam_route(fmt, world_size, exclude_flags)
+    min_base_quality = check_min_base_quality(min_base_quality, k, fmt)
     t_index = time.perf_counter()
     probe = probe_input(path) if probe is None else probe
     has_device = _lib.device_count() > 0
     # (decided BEFORE anything is made: the prefetching chunker starts a reader thread and page-locks two batch buffers —
     # making and freeing those cost the BGZF route 100 ms of its map phase until it was noticed)
-    route, populate, steer = choose_route(fmt, probe, world_size, n_threads, has_device, lut=lut)
+    route, populate, steer = choose_route(fmt, probe, world_size, n_threads, has_device, lut=lut, min_base_quality=min_base_quality)
     seekable = not probe.inflate
     # page-locked memory is slow to make (~50 ms per GB): the staging buffers of the host packer are made by a helper thread
     # WHILE the index is uploaded and repacked, not inside the map phase.  (The count vector needs none: kmm_get_node_counts
@@ -194,7 +204,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     helper = threading.Thread(target=prepare_host_memory, daemon=True)
     # (.gz input needs 128 MB of it, made in 7 ms by the first call that wants it; behind a helper thread the same allocation
     # came back 100 ms after the index upload it was meant to hide behind: profiles/r05/bgzf_e2e_v6_*.txt)
-    if has_device and n_threads > 1 and seekable and lut is None:      # (the packer's buffers: no packer with a table)
+    if has_device and n_threads > 1 and seekable and lut is None and not min_base_quality:  # (the packer's buffers: no packer
+                                                                                             # with a table or a quality floor)
         helper.start()
     byte_range = rank_byte_range(path, fmt, rank, world_size) if (world_size > 1 and seekable) else None
     # the file mapping of route "mmap" is made HERE, and its pages populated, while the index goes up
@@ -212,6 +223,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     # the raw bytes cross PCIe and the GPU parses them
     n_host = host_threads(n_threads, world_size)
     dev.set_param("host_pack_threads", n_host if n_threads > 1 else 0)
+    if min_base_quality:
+        dev.set_param("min_base_quality", min_base_quality)
     from . import _io
     _io.set_default_threads(n_host)
     logging.info("%d host thread(s) read and pack the read bytes (-t %d, CPU budget %d)", n_host, n_threads, _io.cpu_budget())
@@ -275,7 +288,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             helper.join()
         return _map_compressed_file(dev, path, route, kfmt, k, max_index_lookup_frequency,
                                     map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
-                                    world_size=world_size, fmt=fmt, lut=lut)
+                                    world_size=world_size, fmt=fmt, lut=lut, min_base_quality=min_base_quality)
     try:
         i = 0
         while True:
@@ -302,6 +315,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         n_lookups, n_hits = dev.get_stats()
         n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
         n_host_packed = dev.get_param("host_packed_record_calls")
+        n_masked = dev.get_param("quality_masked_bases") if min_base_quality else None
         if before_fetch is not None:
             before_fetch(dev)
         if helper.is_alive() or helper.ident is not None:
@@ -331,8 +345,36 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     logging.info("Mapped %d reads from %d bytes (%.1f MB/s, GPU record parser): %d k-mer lookups "
                  "(%.1f M/s), %d index hits" % (n_reads, n_bytes, n_bytes / max(dt, 1e-9) / 1e6, n_lookups,
                                                   n_lookups / max(dt, 1e-9) / 1e6, n_hits))
+    _log_quality_masked(min_base_quality, n_masked)
     _log_path_taken(n_radix, n_direct, n_host_packed)
     return node_counts
+
+
+def _log_quality_masked(min_base_quality, n_masked):
+    if min_base_quality:
+        logging.info("quality_masked_bases: %d bases below Q%d, no k-mer over them counted", n_masked, min_base_quality)
+
+
+def check_min_base_quality(min_base_quality, k, fmt=None, host_parser=False):
+    """--min-base-quality against what it cannot go with, before anything is uploaded; returns the floor that applies (0 for
+    FASTA, which has no qualities, after one warning).  fmt None: the format is not known yet (the argument parser)."""
+    q = int(min_base_quality or 0)
+    if not 0 <= q <= 93:
+        raise ValueError("--min-base-quality must lie in 0 .. 93 (Phred+33 qualities are '!' .. '~')")
+    if q == 0:
+        return 0
+    if k < 2:
+        raise ValueError("--min-base-quality needs -k 2 or more")
+    if fmt in ("sam", "bam"):
+        raise ValueError("--min-base-quality applies to FASTQ input: the QUAL column of %s records is not carried to the GPU "
+                         "(convert to FASTQ, or drop the option)" % fmt.upper())
+    if host_parser:
+        raise ValueError("--min-base-quality reads the qualities on the GPU: the host parser hands it reads without them "
+                         "(drop --host-parser)")
+    if fmt in ("fasta", "fasta_ml"):
+        logging.warning("--min-base-quality %d has no effect on FASTA input: it has no qualities", q)
+        return 0
+    return q
 
 
 def _log_path_taken(n_radix, n_direct, n_host_packed=0):
@@ -361,7 +403,7 @@ _COMPRESSED_ROUTES = {
 
 
 def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None, rank=0,
-                         world_size=1, fmt="fastq", lut=None):
+                         world_size=1, fmt="fastq", lut=None, min_base_quality=0):
     """`kmer_mapper map -f reads.fq.gz | reads.bam` with the GPU inflater: windows of the file mapping -> kmm_map_<route>.
 
     route "gzip" (PLAIN gzip, kmm_map_gzip): each call goes on where the one before could verify a deflate block boundary.
@@ -454,6 +496,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
                     pass
         n_lookups, n_hits = dev.get_stats()
         counts = [dev.get_param(c) for c in counters]
+        n_masked = dev.get_param("quality_masked_bases") if min_base_quality else None
         n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
         if before_fetch is not None:
             before_fetch(dev)
@@ -467,6 +510,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
     logging.info("Time spent only on hashing and counting hashes: %.5f" % dt)
     logging.info(summary % (n_reads, size - lo, (size - lo) / max(dt, 1e-9) / 1e6, *counts, n_lookups,
                             n_lookups / max(dt, 1e-9) / 1e6, n_hits))
+    _log_quality_masked(min_base_quality, n_masked)
     _log_path_taken(n_radix, n_direct)
     return node_counts
 
@@ -539,6 +583,7 @@ def map_bnp(args):
         lut = ambiguous_skip_lut()
         if k < 2:
             raise ValueError("--ambiguous-bases skip needs -k 2 or more")
+    min_q = check_min_base_quality(getattr(args, "min_base_quality", 0), k, fmt, bool(getattr(args, "host_parser", False)))
     if fmt == "bam" and getattr(args, "host_parser", False):
         raise ValueError("--host-parser does not read BAM: its records are decoded on the GPU (drop --host-parser)")
     if fmt == "sam" and getattr(args, "host_parser", False):
@@ -548,7 +593,8 @@ def map_bnp(args):
             fmt = "fasta_ml"           # wrapped sequence lines: unwrapped on the GPU (KMM_FORMAT_FASTA)
         node_counts = map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, revcomp, max_freq,
                                   device=device, rank=rank, world_size=world, before_fetch=before_fetch,
-                                  n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe, lut=lut)
+                                  n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe, lut=lut,
+                                  min_base_quality=min_q)
     else:
         logging.info("Using the host FASTA/FASTQ parser")
         if world > 1 and not probe.inflate:
@@ -623,6 +669,10 @@ def build_argument_parser():
                            help="a (default): N is counted as A and any other letter is an error, as the reference. skip "
                                 "(extension): no k-mer that contains N or an IUPAC ambiguity letter is counted; the k-mers on "
                                 "either side of it are.")
+    subparser.add_argument("--min-base-quality", default=0, type=int, metavar="Q",
+                           help="Extension, FASTQ input: a base whose Phred+33 quality is below Q (0 .. 93) is skipped like an "
+                                "ambiguous base under --ambiguous-bases skip: no k-mer that contains it is counted. Default 0: "
+                                "qualities are not read.")
     subparser.set_defaults(func=map_bnp)
     return parser
 
@@ -637,6 +687,11 @@ def run_argument_parser(args):
         sys.exit(1)
 
     args = parser.parse_args(args)
+    if getattr(args, "min_base_quality", 0):     # (refused here: before the index file is read)
+        try:
+            check_min_base_quality(args.min_base_quality, args.kmer_size)
+        except ValueError as exc:
+            parser.error(str(exc))
     return args.func(args)
 
 

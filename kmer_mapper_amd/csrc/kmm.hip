@@ -388,6 +388,8 @@ struct kmm_index : IndexStreams, RxArrays {
     int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
     int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
+    int min_base_quality = 0;    // "min_base_quality": > 0: a FASTQ base whose quality byte is below 33 + this is a break
+    int64_t dbg_rec_piece_kb = 0; // test hook ("debug_records_piece_kb"): bytes per piece of kmm_map_records, KiB (0: 2^30 bytes)
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
     bool rx_filter_slots = true;  // "radix_filter_slots": where the geometry allows it the filter is the slot filter (0: the bucket bitmap)
     uint32_t dbg_p2f_cap = P2F_SLOTS; // test hook ("debug_p2f_round_slots"): sort-buffer slots k_rx_p2f uses beside the slot filter
@@ -500,8 +502,10 @@ int drain(kmm_index *ix)
         else if (bad[1] != NO_BAD)
             rc = fail(KMM_ERR_MALFORMED,
                       "record structure violated at byte offset %llu of a mapped chunk (a record line "
-                      "does not start with '@' / '+' / '>'): multi-line FASTA/FASTQ is not supported by "
-                      "the GPU reader%s", bad[1], where);
+                      "does not start with '@' / '+' / '>'%s): multi-line FASTA/FASTQ is not supported by "
+                      "the GPU reader%s", bad[1],
+                      ix->min_base_quality > 0 ? ", or a quality line that ends there is not as long as its sequence line "
+                                                 "(checked with min_base_quality set)" : "", where);
         else
             rc = fail(KMM_ERR_INVALID_BASE,
                       "read byte at offset %llu of a mapped chunk is not a nucleotide under the "
@@ -1940,6 +1944,33 @@ static bool records_take_radix(const kmm_index_t *ix, int64_t n_bytes, int forma
     return use_radix(ix, format == KMM_FORMAT_FASTQ ? n_bytes / 2 : n_bytes);
 }
 
+// Bytes per piece of a kmm_map_records call ("debug_records_piece_kb": tests cut a small file into several pieces).
+static int64_t records_piece_max(const kmm_index_t *ix)
+{
+    return ix->dbg_rec_piece_kb > 0 ? ix->dbg_rec_piece_kb << 10 : (int64_t)1 << 30;
+}
+
+// The quality floor that applies to records of this format: "min_base_quality" for FASTQ, none for the formats without
+// quality lines.
+static int records_quality(const kmm_index_t *ix, int format)
+{
+    return format == KMM_FORMAT_FASTQ ? ix->min_base_quality : 0;
+}
+
+// "min_base_quality" > 0 and what it cannot go with: k = 1 (the masked base's own window could not be killed: check_k_lut)
+// and the formats whose writers emit two-line FASTA, without QUAL (sam: KMM_FORMAT_SAM or kmm_map_bam).
+static int check_quality(const kmm_index_t *ix, const char *who, int k, bool sam)
+{
+    if (ix->min_base_quality <= 0)
+        return KMM_OK;
+    if (sam)
+        return fail(KMM_ERR_INVALID_ARG, "%s: min_base_quality %d is set, and SAM / BAM records are mapped without their QUAL "
+                    "column: set it to 0 for this input", who, ix->min_base_quality);
+    if (k == 1)
+        return fail(KMM_ERR_INVALID_ARG, "%s: k = 1 with min_base_quality %d: needs k >= 2", who, ix->min_base_quality);
+    return KMM_OK;
+}
+
 // Raw records on the radix path (r04): census -> the sequence bytes compacted into flat reads of 2-bit codes (one per
 // byte) + the read-start bitset (kmm_records.hpp, k_rec_count2 .. k_rec_uniform), all on the copy stream, i.e. under
 // the previous call's map kernels; then pass 1 runs on flat reads — on packed tiles when the reads have one length —
@@ -1949,9 +1980,11 @@ static bool records_take_radix(const kmm_index_t *ix, int64_t n_bytes, int forma
 // bytes), appended to the flat reads at flat position `flat_base`.  Synchronises the copy stream (the caller's host
 // buffer is free afterwards) and returns where the piece's last complete record ends, its records, the flat length
 // after it, and whether its reads have one length.
+// qual: the quality floor of a FASTQ piece (0: none) — a second prefix, over the quality bytes, gives k_rec_scatter's quality
+// variant the flat position of every tile's first quality byte; n_bit_words: the words of start_bits.
 static int rec_compact_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, int64_t n_bytes, int format, const uint8_t *d_lut,
-                             bool has_break, int64_t flat_base, uint32_t *flat, uint32_t *start_bits, int64_t *consumed, int64_t *n_records,
-                             int64_t *flat_end, int64_t *uniform_len)
+                             bool has_break, int qual, size_t n_bit_words, int64_t flat_base, uint32_t *flat, uint32_t *start_bits,
+                             int64_t *consumed, int64_t *n_records, int64_t *flat_end, int64_t *uniform_len)
 {
     const int64_t n_tiles = (n_bytes + REC_TB - 1) / REC_TB; // 4 KiB tiles: one wavefront, 64 bytes per lane
     const int n_super = (int)((n_tiles + 1023) / 1024);
@@ -1960,6 +1993,7 @@ static int rec_compact_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, in
     auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     const size_t o_nl = carve(n_pad * 4), o_seq = carve(n_pad * 8), o_pre = carve(n_pad * 4), o_snl = carve((size_t)n_super * 4 + 64),
                  o_sseq = carve((size_t)n_super * 4 + 64), o_info = carve(256), o_out = carve(256);
+    const size_t o_qpre = qual ? carve(n_pad * 4) : 0, o_sq = qual ? carve((size_t)n_super * 4 + 64) : 0;
     KMMCHK(ensure(s.aux, off));
     uint8_t *a = (uint8_t *)s.aux.p;
     uint32_t *tile_nl = (uint32_t *)(a + o_nl), *tile_pre = (uint32_t *)(a + o_pre), *super_nl = (uint32_t *)(a + o_snl),
@@ -1985,10 +2019,26 @@ static int rec_compact_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, in
         hipLaunchKernelGGL(k_rec_scan1, dim3(n_super), dim3(1024), 0, cs, tile_nl, super_nl);
         hipLaunchKernelGGL(k_rec_scan2, dim3(1), dim3(1024), 0, cs, d_raw, n_bytes, n_super, tile_nl, super_nl, (uint32_t)format, d_info,
                            (int)REC_TB);
-        hipLaunchKernelGGL(k_rec_seq_scan, dim3(n_super), dim3(1024), 0, cs, tile_seq, tile_nl, super_nl, n_tiles, pm, tile_pre, super_seq);
+        hipLaunchKernelGGL(k_rec_seq_scan, dim3(n_super), dim3(1024), 0, cs, tile_seq, tile_nl, super_nl, n_tiles, pm, 1u, tile_pre, super_seq);
         hipLaunchKernelGGL(k_super_scan, dim3(1), dim3(1024), 0, cs, super_seq, n_super, (uint32_t *)(d_out + 8));
     }
-    if (!(skip & 4) && has_break) // (break bytes become one-base reads: k_rec_uniform then finds more starts than records)
+    if (qual) { // (never with "debug_records_skip": map_records_entry)
+        RecQual q;
+        uint32_t *tile_q = (uint32_t *)(a + o_qpre), *super_q = (uint32_t *)(a + o_sq);
+        hipLaunchKernelGGL(k_rec_seq_scan, dim3(n_super), dim3(1024), 0, cs, tile_seq, tile_nl, super_nl, n_tiles, pm, 3u, tile_q, super_q);
+        hipLaunchKernelGGL(k_super_scan, dim3(1), dim3(1024), 0, cs, super_q, n_super, (uint32_t *)(d_out + 9));
+        q.tile_pre = tile_q;
+        q.super_pre = super_q;
+        q.masked = ix->stats;
+        q.thresh = 33u + (uint32_t)qual;
+        q.n_words = (uint32_t)n_bit_words; // (a call holds fewer than 2^37 bytes)
+        if (has_break)
+            hipLaunchKernelGGL((k_rec_scatter<true, true>), g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_nl, super_nl, tile_pre, super_seq,
+                               d_info, d_lut, pm, hc, flat, (uint64_t)flat_base, start_bits, ix->first_bad, d_out, q);
+        else
+            hipLaunchKernelGGL((k_rec_scatter<false, true>), g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_nl, super_nl, tile_pre, super_seq,
+                               d_info, d_lut, pm, hc, flat, (uint64_t)flat_base, start_bits, ix->first_bad, d_out, q);
+    } else if (!(skip & 4) && has_break) // (break bytes become one-base reads: k_rec_uniform then finds more starts than records)
         hipLaunchKernelGGL(k_rec_scatter<true>, g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_nl, super_nl, tile_pre, super_seq,
                            d_info, d_lut, pm, hc, flat, (uint64_t)flat_base, start_bits, ix->first_bad, d_out);
     else if (!(skip & 4))
@@ -2049,8 +2099,9 @@ static int map_records_piece_radix(kmm_index_t *ix, Stage &s, const uint8_t *d_r
     HIPCHK(hipMemsetAsync(s.start_bits.p, 0, n_words * 4, ix->stream));
     HIPCHK(hipMemsetAsync(s.kmers.p, 0, code_bytes, ix->stream));
     int64_t flat_end = 0, L = 0;
-    KMMCHK(rec_compact_piece(ix, s, d_raw, n_bytes, format, d_lut, has_break, 0, (uint32_t *)s.kmers.p, (uint32_t *)s.start_bits.p, consumed,
-                             n_records, &flat_end, &L));
+    // (no quality floor here: a FASTQ call with one is map_records_radix_call's, whatever its size)
+    KMMCHK(rec_compact_piece(ix, s, d_raw, n_bytes, format, d_lut, has_break, 0, n_words, 0, (uint32_t *)s.kmers.p,
+                             (uint32_t *)s.start_bits.p, consumed, n_records, &flat_end, &L));
     if (*consumed <= 0 || flat_end <= 0)
         return KMM_OK;
     return rec_launch_flat(ix, (const uint32_t *)s.kmers.p, flat_end, *n_records, (const uint32_t *)s.start_bits.p, (int64_t)n_words,
@@ -2085,7 +2136,8 @@ static int map_records_radix_call(kmm_index_t *ix, const uint8_t *raw, int64_t n
         HIPCHK(hipMemsetAsync(s.start_bits.p, 0, n_words * 4, ms));
         HIPCHK(hipMemsetAsync(s.kmers.p, 0, code_bytes, ms));
     }
-    const int64_t piece_max = (int64_t)1 << 30;
+    const int64_t piece_max = records_piece_max(ix);
+    const int qual = records_quality(ix, format);
     int64_t off = 0, recs = 0, flat = 0, L = -1;
     while (off < n_bytes) {
         const int64_t len = n_bytes - off < piece_max ? n_bytes - off : piece_max;
@@ -2097,8 +2149,8 @@ static int map_records_radix_call(kmm_index_t *ix, const uint8_t *raw, int64_t n
             d_raw = (const uint8_t *)s.bases.p;
         }
         int64_t used = 0, nr = 0, flat_end = flat, Lp = 0;
-        KMMCHK(rec_compact_piece(ix, s, d_raw, len, format, d_lut, has_break, flat, (uint32_t *)s.kmers.p, (uint32_t *)s.start_bits.p, &used, &nr,
-                                 &flat_end, &Lp));
+        KMMCHK(rec_compact_piece(ix, s, d_raw, len, format, d_lut, has_break, qual, n_words, flat, (uint32_t *)s.kmers.p,
+                                 (uint32_t *)s.start_bits.p, &used, &nr, &flat_end, &Lp));
         if (used > 0) {
             L = (L == -1 || L == Lp) ? Lp : 0; // one length over all pieces, or none
             flat = flat_end;
@@ -2350,6 +2402,18 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         return fail(KMM_ERR_INVALID_ARG, "raw is NULL");
     HIPCHK(hipSetDevice(ix->device));
     KMMCHK(check_k_lut(k, lut));
+    KMMCHK(check_quality(ix, "kmm_map_records", k, format == KMM_FORMAT_SAM));
+    // A quality floor on FASTQ: always compaction + the radix path, whatever the batch size and "path" say (as kmm_map_packed) —
+    // the records front end of the direct path has no flat positions to put a quality mark on — and never the host packer,
+    // whose parser skips the quality lines.
+    if (records_quality(ix, format) > 0) {
+        if (!ix->rx_ok)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_map_records: min_base_quality needs the radix path, which is not available for this "
+                        "index (kmm_get_param \"radix_unavailable_reason\")");
+        if (ix->dbg_rec_skip)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_map_records: min_base_quality does not go with debug_records_skip");
+        return map_records_radix_call(ix, raw, n_bytes, format, k, max_freq, also_revcomp, lut, consumed, n_records);
+    }
     // chunks beyond 2^30 bytes are mapped piece by piece: every piece starts where the previous one's last complete
     // record ended, so the pieces cut the chunk exactly as one census over all of it would
     // (multi-line FASTA and SAM are turned into two-line FASTA on the device first: never the host packer, whose parser knows
@@ -2364,7 +2428,7 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         }
         return map_records_radix_call(ix, raw, n_bytes, format, k, max_freq, also_revcomp, lut, consumed, n_records);
     }
-    const int64_t piece_max = (int64_t)1 << 30;
+    const int64_t piece_max = records_piece_max(ix);
     int64_t off = 0, recs = 0;
     if (format == KMM_FORMAT_SAM && n_bytes > piece_max) {
         // a SAM chunk of several pieces is checked whole first: a malformed line in a later piece maps nothing of the call
@@ -2631,6 +2695,7 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
     if (text ? c.fmt != KMM_FORMAT_FASTQ && c.fmt != KMM_FORMAT_FASTA2 && c.fmt != KMM_FORMAT_SAM : c.fmt != 0)
         return fail(KMM_ERR_INVALID_ARG, text ? "%s: format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2) or KMM_FORMAT_SAM (8)"
                                               : "%s: flags take KMM_FORMAT_NEW_STREAM and KMM_FORMAT_LAST_CHUNK only", c.who);
+    KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
     if (c.consumed_comp)
@@ -3845,6 +3910,16 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         ix->dbg_rx_buf_limit = value;
     } else if (!strcmp(name, "debug_records_skip")) {
         ix->dbg_rec_skip = (int)value;
+    } else if (!strcmp(name, "min_base_quality")) {
+        // > 0: a FASTQ base whose quality byte is below '!' + value is a break, on every call that parses FASTQ records
+        if (value < 0 || value > 93)
+            return fail(KMM_ERR_INVALID_ARG, "min_base_quality outside [0, 93]");
+        ix->min_base_quality = (int)value;
+    } else if (!strcmp(name, "debug_records_piece_kb")) {
+        // test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a few hundred KB then make several pieces
+        if (value < 0 || value > (1 << 20))
+            return fail(KMM_ERR_INVALID_ARG, "debug_records_piece_kb outside [0, 2^20]");
+        ix->dbg_rec_piece_kb = value;
     } else if (!strcmp(name, "debug_skew_p2_counter")) {
         // test hook of the conservation self-check: adds `value` to the device-side "gathered by pass 2" counter, as a
         // doubly processed work item would; the next synchronising call must fail with KMM_ERR_INTERNAL
@@ -3896,6 +3971,10 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->gzip_inflated;
     else if (!strcmp(name, "debug_gzip_chunk_kb"))
         *value = ix->dbg_gzip_chunk_kb;
+    else if (!strcmp(name, "min_base_quality"))
+        *value = ix->min_base_quality;
+    else if (!strcmp(name, "debug_records_piece_kb"))
+        *value = ix->dbg_rec_piece_kb;
     else if (!strcmp(name, "bam_calls")) // kmm_map_bam calls that mapped their records (a window inside the header not counted)
         *value = ix->bam_calls;
     else if (!strcmp(name, "bam_records")) // BAM records mapped
@@ -4002,7 +4081,7 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
     else if (!strcmp(name, "n_coarse_partitions"))
         *value = ix->rx_ok ? ix->rx_geo.F1 : 0;
     else if (!strcmp(name, "radix_p2_kmers") || !strcmp(name, "radix_p3_kmers") || !strcmp(name, "radix_p2_dropped") ||
-             !strcmp(name, "radix_p2_multi_round_items") || !strncmp(name, "stats_slot_", 11)) {
+             !strcmp(name, "radix_p2_multi_round_items") || !strcmp(name, "quality_masked_bases") || !strncmp(name, "stats_slot_", 11)) {
         // conservation check of the radix path: k-mers gathered by pass 2 / probed by pass 3 since the last
         // kmm_get_stats(reset): both must equal the lookups pass 1 emitted
         HIPCHK(hipSetDevice(ix->device));
@@ -4010,7 +4089,9 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         std::vector<unsigned long long> st(KMM_STAT_BYTES / 8);
         HIPCHK(hipMemcpy(st.data(), ix->stats, KMM_STAT_BYTES, hipMemcpyDeviceToHost));
         // ("stats_slot_<n>": raw counter n of the statistics block; slots 4.. are only written by diagnostic builds)
-        const int slot = name[0] == 's' ? atoi(name + 11) : !strcmp(name, "radix_p2_dropped") ? KMM_STAT_RX_DROPPED
+        // ("quality_masked_bases": FASTQ bases whose quality byte was below "min_base_quality", since the same reset)
+        const int slot = name[0] == 's' ? atoi(name + 11) : name[0] == 'q' ? KMM_STAT_QUAL_MASKED
+                                                          : !strcmp(name, "radix_p2_dropped") ? KMM_STAT_RX_DROPPED
                                                           : !strcmp(name, "radix_p2_multi_round_items") ? KMM_STAT_RX_MULTI
                                                           : name[7] == '2' ? 2 : 3;
         if (slot < 0 || slot >= KMM_STAT_STRIDE)

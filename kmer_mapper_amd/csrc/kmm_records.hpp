@@ -468,12 +468,13 @@ __global__ void __launch_bounds__(256) k_rec_count2(const uint8_t *__restrict__ 
     }
 }
 
-// One workgroup per super-tile, after the newline prefix is complete: the sequence bytes of every tile — the bytes of
-// the lines with (line number mod period) == 1 — as an exclusive prefix inside the super-tile + the super-tile's total.
+// One workgroup per super-tile, after the newline prefix is complete: the bytes of every tile that lie on the lines with
+// (line number mod period) == phase — 1: the sequence bytes, 3: the quality bytes of FASTQ — as an exclusive prefix
+// inside the super-tile + the super-tile's total.
 __global__ void __launch_bounds__(1024) k_rec_seq_scan(const unsigned long long *__restrict__ tile_seq,
                                                        const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
-                                                       int64_t n_tiles, uint32_t period_mask, uint32_t *__restrict__ tile_pre,
-                                                       uint32_t *__restrict__ super_tot)
+                                                       int64_t n_tiles, uint32_t period_mask, uint32_t phase,
+                                                       uint32_t *__restrict__ tile_pre, uint32_t *__restrict__ super_tot)
 {
     __shared__ uint32_t s_a[1024];
     const int t = threadIdx.x;
@@ -481,10 +482,10 @@ __global__ void __launch_bounds__(1024) k_rec_seq_scan(const unsigned long long 
     uint32_t c = 0;
     if (tile < n_tiles) {
         const uint32_t line0 = super_nl[blockIdx.x] + tile_nl[tile];
-        // a byte with r newlines before it inside the tile lies on line line0 + r: sequence iff (line0 + r) & mask == 1
+        // a byte with r newlines before it inside the tile lies on line line0 + r: counted iff (line0 + r) & mask == phase
         unsigned long long f = tile_seq[tile];
         for (uint32_t r = 0; r < 4u; ++r, f >>= 16)
-            if (((line0 + r) & period_mask) == 1u)
+            if (((line0 + r) & period_mask) == phase)
                 c += (uint32_t)(f & 0xFFFFu);
     }
     s_a[t] = c;
@@ -507,7 +508,27 @@ __global__ void __launch_bounds__(1024) k_rec_seq_scan(const unsigned long long 
 // one-base read of any code — its flat position f and f + 1 are added to the read starts.  The positions are the
 // compacted ones, so the byte behind the break needs no carry into the next lane or tile (unlike the byte behind a '\r',
 // which is dropped from the stream): f + 1 is that byte's position wherever it lies, or the end of the flat reads.
-template <bool BRK>
+// QUAL (FASTQ with "min_base_quality" > 0): the j-th quality byte of the piece and its j-th sequence byte are
+// the same flat position as long as every record so far has lines of equal length, which is checked at every newline that
+// ends a quality line (first_bad[1]).  So a quality byte below q.thresh is a break at its OWN flat position — the tile's
+// quality base (a second prefix, over the phase-3 bytes) + the lane's prefix + the rank inside the lane — whichever tile
+// holds the base.  The lane's low bytes are gathered into a mask in flat space and OR-ed into the bitset as whole words
+// (m | m << 1, as k_mark_breaks does): low bases come in runs, not one at a time like N.
+struct RecQual {
+    const uint32_t *tile_pre, *super_pre; // prefix of the quality bytes, as tile_pre / super_pre of the sequence bytes
+    unsigned long long *masked;           // the handle's statistics block: counter of the low bytes, one shard per tile
+    uint32_t thresh;                      // a quality byte below it (33 + Q) is low
+    uint32_t n_words;                     // words of start_bits: no mark beyond them, whatever the file holds
+};
+
+// 0x80-per-byte flags of the bytes of x that are below t (unsigned; 1 <= t <= 128)
+__device__ __forceinline__ uint32_t bytes_below(uint32_t x, uint32_t t)
+{
+    // (with bit 7 set no byte borrows from its neighbour: bit 7 of the difference = the low seven bits are >= t)
+    return ~((((x & 0x7F7F7F7Fu) | 0x80808080u) - t * 0x01010101u) | x) & 0x80808080u;
+}
+
+template <bool BRK, bool QUAL = false>
 __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__ raw, int64_t n, int64_t n_tiles,
                                                      const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
                                                      const uint32_t *__restrict__ tile_pre, const uint32_t *__restrict__ super_pre,
@@ -515,7 +536,7 @@ __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__
                                                      uint32_t period_mask, uint32_t header_char, uint32_t *__restrict__ codes,
                                                      uint64_t flat_base, uint32_t *__restrict__ start_bits,
                                                      unsigned long long *__restrict__ first_bad,
-                                                     unsigned long long *__restrict__ out_info)
+                                                     unsigned long long *__restrict__ out_info, RecQual q = RecQual())
 {
     __shared__ uint32_t s_lut[256];
     __shared__ uint32_t s_row[4][264]; // a tile's codes: at most 4096 + 15 -> 257 words
@@ -539,7 +560,7 @@ __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__
     rec_load64(raw, n32, t_begin * REC_TB + (uint32_t)lane * 64u, cur);
     uint32_t carry_nl = t_begin == 0 ? 1u : (raw[t_begin * REC_TB - 1u] == 10u ? 1u : 0u); // does the byte before the tile end a line?
     uint32_t carry_cr = t_begin == 0 ? 0u : (raw[t_begin * REC_TB - 1u] == 13u ? 1u : 0u); // ... is it a '\r'?
-    uint32_t m_line = 0, m_dst = 0;
+    uint32_t m_line = 0, m_dst = 0, m_qdst = 0;
     for (uint32_t tile = t_begin; tile < t_end; ++tile) {
         const uint32_t p = tile * REC_TB + (uint32_t)lane * 64u;
         const int slot = (int)((tile - t_begin) & 63u);
@@ -548,6 +569,8 @@ __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__
             if (t < t_end) {
                 m_line = super_nl[t >> 10] + tile_nl[t];
                 m_dst = super_pre[t >> 10] + tile_pre[t];
+                if (QUAL)
+                    m_qdst = q.super_pre[t >> 10] + q.tile_pre[t];
             }
         }
         if (tile + 1u < t_end)
@@ -625,7 +648,7 @@ __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__
         // the runs of sequence bytes moved down to bit 0, the word OR-ed into the wavefront's row at code position
         // (dst0 & 15) + rank: word j of the row is word (dst0 >> 4) + j of the output
         const uint32_t mis = (uint32_t)dst0 & 15u;
-        uint32_t q = mis + pre, bad = 0xFFFFFFFFu;
+        uint32_t qp = mis + pre, bad = 0xFFFFFFFFu;
         uint64_t brk = 0; // BRK: the lane's sequence bytes that are breaks
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -656,11 +679,11 @@ __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__
                 k2 += 2u * len;
                 m &= ~(((1u << len) - 1u) << a);
             }
-            const uint32_t sh = (q & 15u) * 2u;
-            atomicOr(&row[q >> 4], cw << sh);
+            const uint32_t sh = (qp & 15u) * 2u;
+            atomicOr(&row[qp >> 4], cw << sh);
             if (sh && (k2 + sh > 32u))
-                atomicOr(&row[(q >> 4) + 1u], cw >> (32u - sh));
-            q += k2 >> 1;
+                atomicOr(&row[(qp >> 4) + 1u], cw >> (32u - sh));
+            qp += k2 >> 1;
         }
         if (bad != 0xFFFFFFFFu)
             atomicMin(&first_bad[0], (unsigned long long)(p + bad));
@@ -671,6 +694,60 @@ __global__ void __launch_bounds__(256) k_rec_scatter(const uint8_t *__restrict__
                 const uint64_t f = dst0 + pre + (uint32_t)__popcll(seq & ((1ull << i) - 1ull));
                 atomicOr(&start_bits[f >> 5], 1u << (f & 31u));
                 atomicOr(&start_bits[(f + 1u) >> 5], 1u << ((f + 1u) & 31u));
+            }
+        }
+        if (QUAL) {
+            const uint64_t qdst0 = flat_base + (uint32_t)__builtin_amdgcn_readlane((int)m_qdst, slot); // flat position of the tile's first quality byte
+            const uint64_t qual_line = s0 & s1 & inside;   // (the line's terminator included)
+            const uint64_t qb = qual_line & ~(nl | cr);
+            const uint32_t qcnt = (uint32_t)__popcll(qb);
+            const uint32_t qpre = wave_scan_incl(qcnt) - qcnt;
+            // a quality line ends: as many sequence bytes as quality bytes so far, or the positions above belong to other bases
+            uint64_t ends = nl & qual_line;
+            while (ends) {
+                const uint32_t i = (uint32_t)__builtin_ctzll(ends);
+                ends &= ends - 1ull;
+                const uint64_t below = (1ull << i) - 1ull;
+                if (dst0 + pre + (uint32_t)__popcll(seq & below) != qdst0 + qpre + (uint32_t)__popcll(qb & below)) {
+                    atomicMin(&first_bad[1], (unsigned long long)(p + i));
+                    break;
+                }
+            }
+            uint64_t low = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    low |= (uint64_t)flags_to_bits(bytes_below(cur.w[j][i], q.thresh)) << (16 * j + 4 * i);
+            low &= qb;
+            const uint32_t n_low = wave_sum((uint32_t)__popcll(low));
+            if (lane == 0 && n_low)
+                atomicAdd(&q.masked[(size_t)(tile % (uint32_t)KMM_STAT_SHARDS) * KMM_STAT_STRIDE + KMM_STAT_QUAL_MASKED],
+                          (unsigned long long)n_low);
+            if (low) {
+                // the low bytes in flat space: the runs of quality bytes moved down to bit 0, as the codes above
+                uint64_t mf = 0, m = qb;
+                uint32_t k1 = 0;
+                while (m) {
+                    const uint32_t a = (uint32_t)__builtin_ctzll(m);
+                    const uint64_t rest = ~(m >> a);
+                    const uint32_t len = rest ? (uint32_t)__builtin_ctzll(rest) : 64u;
+                    const uint64_t run = len >= 64u ? ~0ull : (1ull << len) - 1ull;
+                    mf |= ((low >> a) & run) << k1;
+                    k1 += len;
+                    m &= ~(run << a);
+                }
+                // bits f and f + 1 of every low base f = f0 + (bit of mf): 65 bits at bit offset f0 & 31 -> three words
+                const uint64_t f0 = qdst0 + qpre, wi = f0 >> 5;
+                const uint32_t sh = (uint32_t)f0 & 31u;
+                const unsigned __int128 marks = ((unsigned __int128)mf | ((unsigned __int128)mf << 1)) << sh;
+                const uint32_t w0 = (uint32_t)marks, w1 = (uint32_t)(marks >> 32), w2 = (uint32_t)(marks >> 64);
+                if (w0 && wi < q.n_words)
+                    atomicOr(&start_bits[wi], w0);
+                if (w1 && wi + 1u < q.n_words)
+                    atomicOr(&start_bits[wi + 1u], w1);
+                if (w2 && wi + 2u < q.n_words)
+                    atomicOr(&start_bits[wi + 2u], w2);
             }
         }
         __builtin_amdgcn_wave_barrier();

@@ -202,7 +202,11 @@ class DeviceIndex:
                     also_revcomp=False, lut=None):
         """Map a raw FASTQ (fmt=4) / two-line FASTA (fmt=2) / SAM (fmt=8; "bam_exclude_flags" filters it) chunk parsed on
         the GPU.
-        Returns (consumed_bytes, n_records); the caller carries raw[consumed:] to the next chunk."""
+        Returns (consumed_bytes, n_records); the caller carries raw[consumed:] to the next chunk.
+        A base-quality floor needs no method of its own: set_param("min_base_quality", Q) makes every FASTQ base whose
+        quality byte is below '!' + Q a break, on this call and on map_bgzf / map_gzip (no effect on FASTA; SAM and map_bam
+        are refused while it is set), and get_param("quality_masked_bases") counts the bases it masked since the last
+        get_stats(reset=True)."""
         b = _Arg(raw, np.uint8, "raw")
         t = _Arg(lut, np.uint8, "lut")
         n = _n_bytes(b, n_bytes)
