@@ -427,6 +427,10 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      without a filter.  The sort buffer beside the slot filter holds 5888 k-mers: an item with more
  *                      survivors is placed and copied out in rounds ("radix_p2_multi_round_items", read-only, counts
  *                      them since the statistics were last reset)
+ *   "radix_p3_fingerprints" 1 (default) = pass 3 keeps one fingerprint byte per LDS-resident entry and reads the 8-byte keys
+ *                      of the entries whose byte equals the k-mer's only (the variant for slices of up to 4096 buckets with
+ *                      the 16-bit directory: the 10 M- and 100 M-k-mer indexes; reads 1 only where that variant runs);
+ *                      0 = every entry of a bucket is compared (also: KMM_RX_P3_FP=0 at creation).  The counts are the same
  *   "radix_packed_tiles" 1 (default) = pass 1 on reads of one length works on tiles of whole reads (no windows across
  *                      read boundaries are computed)
  *   "fine_bits"        experiments: log2 fine partitions per coarse partition of the radix path
@@ -500,6 +504,7 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      beyond that many bytes counts as out of memory: the call takes more sub-batches;
  *                      "debug_p2f_round_slots": slots of pass 2's sort buffer in use beside the slot filter, even, in
  *                      [512, 5888] — ordinary batches then take several rounds per item;
+ *                      "debug_p3_key_reads" (read-only): 8-byte key reads of pass 3's probes, -DRX_P3_FP_STATS builds;
  *                      "debug_skew_p2_counter": trips the conservation check; "debug_ring_slot_kb": slot size of the
  *                      page-locked staging ring): not for callers, no effect at 0
  * Read-only (kmm_get_param): "radix_available", "radix_unavailable_reason" (0 available, 1 modulo >= 2^31, 2 slices too

@@ -392,6 +392,7 @@ struct kmm_index : IndexStreams, RxArrays {
     int64_t dbg_rec_piece_kb = 0; // test hook ("debug_records_piece_kb"): bytes per piece of kmm_map_records, KiB (0: 2^30 bytes)
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
     bool rx_filter_slots = true;  // "radix_filter_slots": where the geometry allows it the filter is the slot filter (0: the bucket bitmap)
+    bool rx_p3_fp = true;         // "radix_p3_fingerprints": pass 3 probes through fingerprint bytes where its variant has that form
     uint32_t dbg_p2f_cap = P2F_SLOTS; // test hook ("debug_p2f_round_slots"): sort-buffer slots k_rx_p2f uses beside the slot filter
     bool rx_packed = true;        // "radix_packed_tiles": pass 1 on reads of one length takes tiles of whole reads
     bool ecnt_dirty = false;  // rx_ecnt holds hits that are not in `counts` yet
@@ -3809,6 +3810,9 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         ix->rx_filter_slots = value != 0;
         if (ix->rx_pstart && ix->rx_ok)
             KMMCHK(rx_build_slots(ix));
+    } else if (!strcmp(name, "radix_p3_fingerprints")) {
+        // 1 (default): the pass-3 variants that have the fingerprint form of the probe (rx_p3_shape) run it; 0: the plain entry loop
+        ix->rx_p3_fp = value != 0;
     } else if (!strcmp(name, "debug_p2f_round_slots")) {
         // test hook of the rounds of k_rx_p2f's placement: sort-buffer slots in use beside the slot filter
         if (value < 512 || value > P2F_SLOTS || (value & 1))
@@ -4066,6 +4070,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = (ix->rx_ok && rx_filter_active(ix)) ? (1 << ix->rx_geo.occ_shift) : 0;
     else if (!strcmp(name, "radix_filter_slots")) // 1: pass 2 filters with the slot filter
         *value = (ix->rx_ok && rx_slots_active(ix)) ? 1 : 0;
+    else if (!strcmp(name, "radix_p3_fingerprints")) // 1: pass 3 probes through fingerprint bytes
+        *value = (ix->rx_ok && rx_p3_fp_active(ix)) ? 1 : 0;
     else if (!strcmp(name, "radix_filter_bits_per_partition")) // filter bits of one coarse partition in LDS (0: no filter)
         *value = !(ix->rx_ok && rx_filter_active(ix)) ? 0
                  : rx_slots_active(ix)                ? (int64_t)P2F_SLOT_WORDS * 32
@@ -4081,7 +4087,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
     else if (!strcmp(name, "n_coarse_partitions"))
         *value = ix->rx_ok ? ix->rx_geo.F1 : 0;
     else if (!strcmp(name, "radix_p2_kmers") || !strcmp(name, "radix_p3_kmers") || !strcmp(name, "radix_p2_dropped") ||
-             !strcmp(name, "radix_p2_multi_round_items") || !strcmp(name, "quality_masked_bases") || !strncmp(name, "stats_slot_", 11)) {
+             !strcmp(name, "radix_p2_multi_round_items") || !strcmp(name, "quality_masked_bases") ||
+             !strcmp(name, "debug_p3_key_reads") || !strncmp(name, "stats_slot_", 11)) {
         // conservation check of the radix path: k-mers gathered by pass 2 / probed by pass 3 since the last
         // kmm_get_stats(reset): both must equal the lookups pass 1 emitted
         HIPCHK(hipSetDevice(ix->device));
@@ -4090,7 +4097,9 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         HIPCHK(hipMemcpy(st.data(), ix->stats, KMM_STAT_BYTES, hipMemcpyDeviceToHost));
         // ("stats_slot_<n>": raw counter n of the statistics block; slots 4.. are only written by diagnostic builds)
         // ("quality_masked_bases": FASTQ bases whose quality byte was below "min_base_quality", since the same reset)
+        // ("debug_p3_key_reads": 8-byte key reads of pass 3's probes; counted by -DRX_P3_FP_STATS builds only, else 0)
         const int slot = name[0] == 's' ? atoi(name + 11) : name[0] == 'q' ? KMM_STAT_QUAL_MASKED
+                                                          : name[0] == 'd' ? KMM_STAT_RX_P3_KEYS
                                                           : !strcmp(name, "radix_p2_dropped") ? KMM_STAT_RX_DROPPED
                                                           : !strcmp(name, "radix_p2_multi_round_items") ? KMM_STAT_RX_MULTI
                                                           : name[7] == '2' ? 2 : 3;

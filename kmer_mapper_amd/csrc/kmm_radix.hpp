@@ -29,7 +29,8 @@
 //   pass 3  k_rx_p3   work item (fine partition f, up to 1024 items of its coarse partition): loads f's slice
 //                     (directory, keys) into LDS, streams f's runs from the items, probes LDS, counts hits per
 //                     entry in LDS (an entry the frequency filter of mapper.pyx:64-66 excludes carries a flag in
-//                     its counter), then adds the counters to the per-entry count vector `ecnt` (contiguous atomics)
+//                     its counter), then adds the counters to the per-entry count vector `ecnt` (contiguous atomics);
+//                     slices of up to 4096 buckets are probed through one fingerprint byte per entry (FP, below)
 //   flush   k_rx_flush_sorted / k_rx_flush  at the next synchronising call: counts[node[e]] += ecnt[e]  (mapper.pyx:68
 //                     summed per entry first — the reference's GpuCounter does exactly this, gpu_counter.py:26-37)
 //
@@ -1719,10 +1720,20 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
 // DirT: type of the LDS directory; uint16_t (half the LDS: 8192-bucket slices with two workgroups per CU) only when
 // no slice of the index holds more than 65535 entries (rx_choose_p3 checks).
 // P16: the slice's directory comes from rx.pstart16 (two buckets per 32-bit load, already relative to the slice).
-template <int WMAX, int ECAP, int WPS, typename DirT, int SUBCAP = RX_SUBCAP3, bool P16 = false>
+// FP: one fingerprint byte per LDS-resident entry (rx_p3_fp, kmm_radix_plan.hpp) beside the keys; a probe tests the bytes of
+// its bucket's first RX_P3_FP_ENTRIES entries and reads the keys of the candidates only.  The counts are the same.
+// -DRX_P3_FP_STATS (diagnostic builds): the 8-byte key reads the lanes issue for entries of their buckets, summed like
+// `probed` into statistics slot KMM_STAT_RX_P3_KEYS ("debug_p3_key_reads"), with and without FP.
+#ifdef RX_P3_FP_STATS
+#define RX_P3_KEY_READ(cond) key_reads += (cond) ? 1u : 0u
+#else
+#define RX_P3_KEY_READ(cond)
+#endif
+template <int WMAX, int ECAP, int WPS, typename DirT, int SUBCAP = RX_SUBCAP3, bool P16 = false, bool FP = false>
 __global__ void __launch_bounds__(RX_NT, WPS) k_rx_p3(IndexView iv, RxView rx, int max_freq)
 {
     static_assert(!P16 || sizeof(DirT) == 2, "the 16-bit directory is copied as it is");
+    __shared__ uint32_t sfp[FP ? (ECAP + 8) / 4 : 1]; // byte i: fingerprint of entry i (+ 8 bytes: the second word of the last bucket)
     __shared__ __attribute__((aligned(4))) DirT sdir[WMAX + 2]; // bucket b of the slice holds entries [sdir[b], sdir[b + 1]) - e0
     __shared__ uint64_t skeys[ECAP];
     __shared__ uint32_t scnt[ECAP];
@@ -1741,6 +1752,10 @@ __global__ void __launch_bounds__(RX_NT, WPS) k_rx_p3(IndexView iv, RxView rx, i
     unsigned long long *counters = rx.queue + 128;
     const uint32_t home = rx_xcc_id();
     uint32_t hits = 0, probed = 0, scan_flip = 0;
+#ifdef RX_P3_FP_STATS
+    uint32_t key_reads = 0;
+#endif
+    const int sh = rx.w + rx.f2; // the quotient part of the packed form lies above these bits
     __syncthreads(); // s_wb is loaded
     // A work item's description (uniform): its fine partition's place in the index and its items.  It is worked
     // out — two dependent loads — while the PREVIOUS work item streams its k-mers.
@@ -1878,6 +1893,8 @@ __global__ void __launch_bounds__(RX_NT, WPS) k_rx_p3(IndexView iv, RxView rx, i
             const uint32_t i = tid + j * RX_NT;
             if (i < ne) {
                 skeys[i] = kv[j];
+                if constexpr (FP)
+                    reinterpret_cast<uint8_t *>(sfp)[i] = (uint8_t)rx_p3_fp(kv[j] >> sh);
                 scnt[i] = (int)fv[j] <= max_freq ? 0u : RX_FILTERED; // the frequency filter of mapper.pyx:64-66
             }
         }
@@ -1991,6 +2008,58 @@ __global__ void __launch_bounds__(RX_NT, WPS) k_rx_p3(IndexView iv, RxView rx, i
                             }
                             mx = cn[i] > mx ? cn[i] : mx;
                         }
+                        if constexpr (FP) {
+                            // The fingerprint bytes of the bucket's first entries — two aligned words per k-mer, the four
+                            // k-mers' requested together — against the k-mer's: only the candidates' keys are read.  The loop
+                            // runs while any k-mer of the group has a candidate left (the lowest one each trip): 1.3 trips
+                            // per wavefront instead of 4.2, 0.47 key reads per probe instead of 1.19 (modelled,
+                            // tests/test_radix_p3_fp_on_the_cpu.py).  Entry 4 is tested, behind the loop, where a lane of the
+                            // wavefront has a bucket of five (one probe in 500).  (A bucket cut by the HBM walk above has
+                            // cn = 0; its st may lie beyond the LDS copy and is not used as an index.)
+                            uint32_t f0[RX_G3], f1[RX_G3], fp4[RX_G3], cm[RX_G3], any = 0;
+#pragma unroll
+                            for (int i = 0; i < RX_G3; ++i) {
+                                const uint32_t wi = (OVER && !cn[i] ? 0u : st[i]) >> 2;
+                                f0[i] = sfp[wi];
+                                f1[i] = sfp[wi + 1u];
+                            }
+#pragma unroll
+                            for (int i = 0; i < RX_G3; ++i) {
+                                fp4[i] = rx_p3_fp4(x[g0 + i] >> sh);
+                                const uint32_t lo = __builtin_amdgcn_alignbit(f1[i], f0[i], 8u * st[i]); // bytes st .. st + 3
+                                cm[i] = rx_p3_match4(lo, fp4[i], cn[i]);
+                                any |= cm[i];
+                            }
+                            // (a mask has bit 8 j for entry j: the lowest bit's number is the key's byte offset in the bucket)
+                            while (any) {
+                                uint64_t key[RX_G3];
+                                uint32_t e8[RX_G3];
+#pragma unroll
+                                for (int i = 0; i < RX_G3; ++i) {
+                                    e8[i] = cm[i] ? 8u * st[i] + (uint32_t)__builtin_ctz(cm[i]) : 0u;
+                                    key[i] = *reinterpret_cast<const uint64_t *>(reinterpret_cast<const char *>(skeys) + e8[i]);
+                                    RX_P3_KEY_READ(cm[i] != 0u);
+                                }
+                                any = 0;
+#pragma unroll
+                                for (int i = 0; i < RX_G3; ++i) {
+                                    if (cm[i] && key[i] == x[g0 + i])
+                                        atomicAdd(reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(scnt) + (e8[i] >> 1)), 1u);
+                                    cm[i] &= cm[i] - 1u;
+                                    any |= cm[i];
+                                }
+                            }
+                            if (mx >= (uint32_t)RX_P3_FP_ENTRIES) { // entry 4: byte 0 of the second word, shifted like the first
+#pragma unroll
+                                for (int i = 0; i < RX_G3; ++i) {
+                                    if (rx_p3_match_entry4(f1[i] >> (8u * (st[i] & 3u)), fp4[i], cn[i])) {
+                                        RX_P3_KEY_READ(true);
+                                        if (skeys[st[i] + 4u] == x[g0 + i])
+                                            atomicAdd(&scnt[st[i] + 4u], 1u);
+                                    }
+                                }
+                            }
+                        }
                         // One loop over j < the longest of the group's buckets: ~4.2 trips per wavefront (the longest of its
                         // 64 x RX_G3 buckets) for 1.3 entries per bucket.  Round 4 measured what the trips behind the second
                         // cost — capping the loop (wrong counts) takes pass 3 from 3.00 ms to 2.37 / 2.43 / 2.73 / 2.91 at 1 /
@@ -2001,11 +2070,14 @@ __global__ void __launch_bounds__(RX_NT, WPS) k_rx_p3(IndexView iv, RxView rx, i
                         // no read from the second trip on 3.01.  The 5 % of probes that meet a bucket of three or more entries
                         // cost ~15 % of the pass whichever lanes do them: it is their SIMD slots, not the loop's form
                         // (profiles/r04/ab_pass3_entry_loop.txt).
-                        for (uint32_t j = 0; j < mx; ++j) {
+                        // (FP: entries 5 and up of a longer bucket — one probe in 8000 — are walked this way: those lanes' trips.)
+                        for (uint32_t j = FP ? RX_P3_FP_ENTRIES : 0; j < mx; ++j) {
                             uint64_t key[RX_G3];
 #pragma unroll
-                            for (int i = 0; i < RX_G3; ++i)
+                            for (int i = 0; i < RX_G3; ++i) {
                                 key[i] = skeys[j < cn[i] ? st[i] + j : 0u];
+                                RX_P3_KEY_READ(j < cn[i]);
+                            }
 #pragma unroll
                             for (int i = 0; i < RX_G3; ++i)
                                 if (j < cn[i] && key[i] == x[g0 + i])
@@ -2048,6 +2120,9 @@ __global__ void __launch_bounds__(RX_NT, WPS) k_rx_p3(IndexView iv, RxView rx, i
     RX_PT_END(iv, 4);
     rx_stat_add(iv, 1, hits);
     rx_stat_add(iv, 3, probed); // conservation check ("radix_p3_kmers")
+#ifdef RX_P3_FP_STATS
+    rx_stat_add(iv, KMM_STAT_RX_P3_KEYS, key_reads);
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------

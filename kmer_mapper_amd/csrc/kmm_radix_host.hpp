@@ -64,6 +64,12 @@ RxP3Variant rx_p3_variant(const kmm_index *ix)
                         ix->rx_no_mid);
 }
 
+// Pass 3 probes through fingerprint bytes: the variant has that form and "radix_p3_fingerprints" asks for it
+bool rx_p3_fp_active(const kmm_index *ix)
+{
+    return ix->rx_p3_fp && rx_p3_shape(rx_p3_variant(ix)).fingerprints;
+}
+
 // The kernels' view of a sub-batch of NB blocks whose tables lie in rx_meta as `sc` says.
 RxView rx_view_of(const kmm_index *ix, const RxScratch &sc, uint32_t NB)
 {
@@ -139,14 +145,22 @@ void rx_launch_p2(kmm_index *ix, const IndexView &iv, const RxView &rx)
     hipLaunchKernelGGL(kern, dim3(ix->n_cu), dim3(P2F_NT), 0, ix->stream, iv, rx);
 }
 
-// (the only place that names instantiations of k_rx_p3: one per RxP3Variant)
+// (the only place that names instantiations of k_rx_p3: one per RxP3Variant, and the fingerprint form of those whose shape
+// has one)
 void rx_launch_p3(kmm_index *ix, const IndexView &iv, const RxView &rx, int max_freq)
 {
     const RxP3Variant v = rx_p3_variant(ix);
     const dim3 grid(ix->n_cu * (rx_p3_shape(v).wg_per_cu > 1 ? ix->rx_grid_per_cu : 1));
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(RX_NT), 0, ix->stream, iv, rx, max_freq); };
+    static_assert(rx_p3_shape(RxP3Variant::W12_DIR16).fingerprints && rx_p3_fp_shapes() == 1,
+                  "RX_P3_SHAPES promises the fingerprint form exactly where an instantiation is named below");
     switch (v) {
-    case RxP3Variant::W12_DIR16:       go(k_rx_p3<RX_WMAX, RX_ECAP, 4, uint16_t, RX_SUBCAP3, true>); break;
+    case RxP3Variant::W12_DIR16:
+        if (rx_p3_fp_active(ix))
+            go(k_rx_p3<RX_WMAX, RX_ECAP, 4, uint16_t, RX_SUBCAP3, true, true>);
+        else
+            go(k_rx_p3<RX_WMAX, RX_ECAP, 4, uint16_t, RX_SUBCAP3, true>);
+        break;
     case RxP3Variant::W12:             go(k_rx_p3<RX_WMAX, RX_ECAP, 4, uint32_t>); break;
     case RxP3Variant::W13_SMALL_DIR16: go(k_rx_p3<RX_WMAX_BIG, RX_ECAP, 4, uint16_t, RX_SUBCAP3, true>); break;
     case RxP3Variant::W13_SMALL:       go(k_rx_p3<RX_WMAX_BIG, RX_ECAP, 4, uint16_t>); break;
@@ -357,6 +371,8 @@ int rx_build(kmm_index *ix, const int32_t *h2i, const int32_t *nk, const uint64_
         ix->rx_filter = atoi(env) != 0;
     if (const char *env = getenv("KMM_RX_FILTER_SLOTS")) // experiments: 0 = the bucket bitmap where the slot filter would serve
         ix->rx_filter_slots = atoi(env) != 0;
+    if (const char *env = getenv("KMM_RX_P3_FP")) // experiments: 0 = pass 3's plain entry loop where the fingerprint form would serve
+        ix->rx_p3_fp = atoi(env) != 0;
     ix->rx_why_not = 1;
     if (M >= (1ull << 31))
         return KMM_OK; // beyond the index format's int32 tables: no radix path; the direct path serves every batch

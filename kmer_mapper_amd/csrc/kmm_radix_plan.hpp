@@ -2,8 +2,10 @@
 // The decisions of the radix path that are plain integer arithmetic, each stated once: the fan-out of an index (RxGeometry),
 // the scratch layout of a sub-batch (RxScratch), the split of a batch into sub-batches, which pass-3 kernel runs
 // (RxP3Variant), the bytes of the radix view, the batch size where the radix path takes over, and the bit a k-mer tests in
-// pass 2's slot filter (rx_filter_slot: host, kernels and tests share the one definition).  Standard C++17: no HIP header, no
-// kmm_index — tests/test_radix_plan_on_the_cpu.py and tests/test_radix_filter_slots_on_the_cpu.py compile it by themselves with g++.
+// pass 2's slot filter (rx_filter_slot: host, kernels and tests share the one definition), the fingerprint byte pass 3 keeps of
+// every LDS-resident entry and the test of a bucket's bytes against it (rx_p3_fp, rx_p3_candidates).  Standard C++17: no HIP
+// header, no kmm_index — tests/test_radix_plan_on_the_cpu.py, tests/test_radix_filter_slots_on_the_cpu.py and
+// tests/test_radix_p3_fp_on_the_cpu.py compile it by themselves with g++.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -48,6 +50,70 @@ constexpr uint32_t rx_filter_slot(uint32_t b, uint64_t quot)
                                                                        // below bit 24 it is the xor: b << 23 has no lower bits)
     const uint32_t h16 = ((v & 0xFFFFFFu) * 0x9E3779u) >> 16;
     return 3u * (b >> 1) + ((h16 * 3u) >> 16);
+}
+
+// Pass 3's fingerprints.  Beside the 8-byte key of every LDS-resident entry k_rx_p3 keeps ONE byte of it, and a probe reads
+// the bytes of its bucket's first five entries (two aligned 32-bit words) instead of their keys: only entries whose byte equals
+// the k-mer's are compared in full, so an absent k-mer — more than half of what reaches pass 3 — reads a key once in 256
+// entries, and the wavefront's trips over the entries follow the candidates, not the longest bucket.
+//   quot: the quotient part of the packed form (x >> (w + f2)): the bits below are the bucket (constant inside a slice) and
+//   the fine partition.  The same 24-bit fold as rx_filter_slot, another odd multiplier, bits [16, 24) of the 24-bit
+//   product: full-rate operations, and independent of the bit the slot filter tested (every k-mer that reaches pass 3 passed
+//   that test; tests/test_radix_p3_fp_on_the_cpu.py holds the false-candidate rate to 1/256).
+// The kernel works on the byte in all four bytes of a word (rx_p3_fp4) and on masks with one bit per BYTE (rx_p3_match4,
+// rx_p3_match_entry4); rx_p3_candidates states the same test with one bit per entry, for the tests.  On the device the
+// multiply is spelled v_mul_u32_u24 — of a product whose bits [16, 24) alone are used the compiler drops the 24-bit mask and
+// then takes the quarter-rate 32-bit multiply — and the byte is spread with one v_perm_b32.
+#if defined(__HIPCC__)
+#define RX_PLAN_HD __host__ __device__
+#else
+#define RX_PLAN_HD
+#endif
+constexpr int RX_P3_FP_ENTRIES = 5; // entries of a bucket tested by fingerprint; the ones behind them are walked key by key
+
+RX_PLAN_HD inline uint32_t rx_p3_fp4(uint64_t quot)
+{
+    const uint32_t v = (uint32_t)quot ^ (uint32_t)(quot >> 24) ^ (uint32_t)(quot >> 48);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t h = __umul24(v, 0xB5297Bu);
+    return __builtin_amdgcn_perm(h, h, 0x02020202u); // byte 2 of the product in every byte
+#else
+    return (((v & 0xFFFFFFu) * 0xB5297Bu >> 16) & 0xFFu) * 0x01010101u;
+#endif
+}
+RX_PLAN_HD inline uint32_t rx_p3_fp(uint64_t quot) { return rx_p3_fp4(quot) & 0xFFu; }
+
+// lo: the fingerprint bytes of the bucket's entries 0 .. 3 (byte j = entry j); fp4: the k-mer's, in every byte; cn: entries
+// of the bucket.  Returns bit 8 j for every entry j < min(cn, 4) whose byte equals the k-mer's.  The key compare stays the
+// arbiter: a spurious bit costs one compare, a MISSING bit would be a wrong count.  The SWAR zero-byte test
+// (x - 0x01..01) & ~x & 0x80..80 marks every zero byte; it may also mark a byte 0x01 above a marked one (the borrow), never
+// drop one.  (The width of the last step is at most 31: bit 24, entry 3, lies below it.)
+RX_PLAN_HD inline uint32_t rx_p3_match4(uint32_t lo, uint32_t fp4, uint32_t cn)
+{
+    const uint32_t x = lo ^ fp4;
+    const uint32_t z = ((x - 0x01010101u) & ~x & 0x80808080u) >> 7;
+    const uint32_t width = 8u * cn < 31u ? 8u * cn : 31u;
+    return z & ((1u << width) - 1u);
+}
+// hi: the word whose byte 0 belongs to entry 4.  Bit 31 if the bucket has that entry and its byte equals the k-mer's.
+// ((x - 1) & ~x: the bits below the lowest set one; bit 7 is among them iff byte 0 is zero.)
+RX_PLAN_HD inline uint32_t rx_p3_match_entry4(uint32_t hi, uint32_t fp4, uint32_t cn)
+{
+    const uint32_t x = hi ^ fp4;
+    return cn >= (uint32_t)RX_P3_FP_ENTRIES ? ((x - 1u) & ~x & 0x80u) << 24 : 0u;
+}
+// The entry the lowest bit of such a mask (not 0) stands for: bits 0, 8, 16, 24, 31 -> 0 .. 4.
+RX_PLAN_HD inline uint32_t rx_p3_first_entry(uint32_t m) { return ((uint32_t)__builtin_ctz(m) + 1u) >> 3; }
+
+// f: the 64-bit window of fingerprint bytes that starts at the bucket's first entry (byte j = entry j); fp: the k-mer's;
+// cn: entries of the bucket.  Returns the mask (bit j = entry j) of the entries below min(cn, 5) whose byte equals fp.
+RX_PLAN_HD inline uint32_t rx_p3_candidates(uint64_t f, uint32_t fp, uint32_t cn)
+{
+    const uint32_t fp4 = fp * 0x01010101u;
+    uint32_t m = rx_p3_match4((uint32_t)f, fp4, cn) | rx_p3_match_entry4((uint32_t)(f >> 32), fp4, cn), out = 0;
+    for (; m; m &= m - 1u)
+        out |= 1u << rx_p3_first_entry(m);
+    return out;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -244,14 +310,24 @@ struct RxP3Shape {
     int keys_in_lds;   // entries of a slice kept in LDS (the rest is walked in HBM)
     int wg_per_cu;
     bool dir16;        // the slice's directory is loaded from RxView::pstart16
+    bool fingerprints = false; // the kernel has the fingerprint form of the probe (rx_p3_fp): only where one byte per key more
+                               // still leaves LDS for two workgroups per CU — 71 776 + 4 104 B; W12 (79 968 B) and the
+                               // 8192-bucket variants do not fit and keep the plain entry loop
 };
 constexpr RxP3Shape RX_P3_SHAPES[] = {
-    {RX_ECAP, 2, true}, {RX_ECAP, 2, false},         // W12_DIR16, W12
+    {RX_ECAP, 2, true, true}, {RX_ECAP, 2, false},   // W12_DIR16, W12
     {RX_ECAP, 2, true}, {RX_ECAP, 2, false},         // W13_SMALL_DIR16, W13_SMALL
     {RX_ECAP_MID, 2, true}, {RX_ECAP_MID, 2, false}, // W13_MID_DIR16, W13_MID
     {RX_ECAP_BIG, 1, false},                         // W13_BIG
 };
 constexpr const RxP3Shape &rx_p3_shape(RxP3Variant v) { return RX_P3_SHAPES[(int)v]; }
+constexpr int rx_p3_fp_shapes()
+{
+    int n = 0;
+    for (const RxP3Shape &s : RX_P3_SHAPES)
+        n += s.fingerprints ? 1 : 0;
+    return n;
+}
 
 // fits_small / fits_mid: all but one slice in 1000 hold at most RX_ECAP / RX_ECAP_MID entries; p16: the 16-bit directory
 // exists (implies max_slice <= 65535); no_mid (experiments, KMM_RX_NO_MID): the 4608-key variants are not used.
