@@ -176,6 +176,28 @@ int kmm_map_reads(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_of
 int kmm_map_reads_uniform(kmm_index_t *idx, const uint8_t *bases, int64_t n_reads,
                           int64_t read_len, int k, int max_index_lookup_frequency,
                           int also_revcomp, const uint8_t *lut);
+/*
+ * kmm_map_reads_qual — flat reads with their quality bytes as a second array (a bionumpy chunk's .sequence + .quality,
+ * pysam / htslib records, a basecaller's output in HBM): "min_base_quality" (kmm_set_param) for callers that hold no FASTQ
+ * text.  read_offsets != NULL: ragged reads as in kmm_map_reads, read_len is ignored; read_offsets == NULL: n_reads reads of
+ * read_len back to back as in kmm_map_reads_uniform.  quals[p] is the quality byte of bases[p] (the same total length);
+ * bases, quals and read_offsets are each host or device memory, independently.  qual_base: 33 (Phred+33 text, as in FASTQ)
+ * or 0 (raw Phred, as BAM stores it); anything else KMM_ERR_INVALID_ARG.
+ * With the handle's floor Q > 0 a base is masked iff the unsigned byte has quals[p] < qual_base + Q — with qual_base 33 a
+ * byte below '!' is masked, as on the FASTQ routes; with qual_base 0 BAM's 0xFF ("absent") never is, at any Q.  A masked
+ * base is a break exactly as a KMM_LUT_BREAK byte: no window that contains it is looked up, forward or reverse complement,
+ * the windows on either side are, and kmm_get_stats' n_lookups counts the surviving windows.  A table with break entries
+ * combines with it (a base is dead if either rule kills it); "quality_masked_bases" counts the bases whose byte was below
+ * the floor, whether or not the table breaks them too; a byte with lut 0xFF stays KMM_ERR_INVALID_BASE at the next
+ * synchronising call, whatever its quality.  quals == NULL and k = 1 are KMM_ERR_INVALID_ARG.  The host packer is never
+ * used, reads of one length take the ragged front end (they do not count in "flat_uniform_batches"), and the path is
+ * chosen as for any flat batch, by size and "path": an index with "radix_available" 0 is served by the direct path.
+ * With Q = 0 the call IS kmm_map_reads / kmm_map_reads_uniform: quals is not read and may be NULL, the same routes and
+ * counters.
+ */
+int kmm_map_reads_qual(kmm_index_t *idx, const uint8_t *bases, const uint8_t *quals, int qual_base,
+                       const int64_t *read_offsets, int64_t n_reads, int64_t read_len, int k,
+                       int max_index_lookup_frequency, int also_revcomp, const uint8_t *lut);
 
 /*
  * kmm_map_records — maps a RAW chunk of a FASTQ (format = 4 lines per record) or two-line FASTA
@@ -486,7 +508,9 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      non-terminator bytes as its sequence line is KMM_ERR_MALFORMED at the next synchronising call, with
  *                      the raw byte offset of the quality line's '\n' (with Q = 0 nothing new is checked).  Read-only
  *                      "quality_masked_bases": sequence bases whose quality byte was below the floor since the statistics
- *                      were last reset (kmm_get_stats(reset)); synchronises like kmm_get_stats
+ *                      were last reset (kmm_get_stats(reset)); synchronises like kmm_get_stats.  Flat reads
+ *                      (kmm_map_reads, kmm_map_reads_uniform) carry no qualities and are unaffected; kmm_map_reads_qual
+ *                      takes them as a second array and applies the same floor (its own rules are at its declaration)
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the

@@ -61,6 +61,7 @@ SIGNATURES = {
     "kmm_map_reads": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P]),
     "kmm_map_reads_uniform": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
                                          _c.c_int, _P]),
+    "kmm_map_reads_qual": (_c.c_int, [_P, _P, _P, _c.c_int, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P]),
     "kmm_map_records": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
     "kmm_map_bgzf": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
     "kmm_map_bgzf_hint_next": (_c.c_int, [_P, _P, _c.c_int64]),

@@ -170,7 +170,7 @@ void default_lut(uint8_t lut[256])
 }
 
 struct Stage {
-    DevBuf bases, offsets, tile_first, start_bits, kmers, lut, aux;
+    DevBuf bases, quals, offsets, tile_first, start_bits, kmers, lut, aux;
     Event done; // the last kernel that read this stage has finished
     bool used = false;
 };
@@ -388,7 +388,7 @@ struct kmm_index : IndexStreams, RxArrays {
     int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
     int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
-    int min_base_quality = 0;    // "min_base_quality": > 0: a FASTQ base whose quality byte is below 33 + this is a break
+    int min_base_quality = 0;    // "min_base_quality": > 0: a FASTQ base whose quality byte is below 33 + this is a break (flat reads: 4.11)
     int64_t dbg_rec_piece_kb = 0; // test hook ("debug_records_piece_kb"): bytes per piece of kmm_map_records, KiB (0: 2^30 bytes)
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
     bool rx_filter_slots = true;  // "radix_filter_slots": where the geometry allows it the filter is the slot filter (0: the bucket bitmap)
@@ -1814,9 +1814,11 @@ static int map_records_host_packed(kmm_index_t *ix, const uint8_t *raw, int64_t 
     return stage_release(ix, s, true);
 }
 
+// quals != NULL (kmm_map_reads_qual with a floor set): quals[p] < qual_thresh makes base p a break (k_mark_low_quals); like a
+// table with a break entry that means the ragged front end, and never the host packer, which knows no breaks.
 static int map_reads_common(kmm_index_t *ix, const uint8_t *bases, const int64_t *read_offsets,
                             int64_t n_reads, int64_t read_len, int k, int max_freq,
-                            int also_revcomp, const uint8_t *lut)
+                            int also_revcomp, const uint8_t *lut, const uint8_t *quals = nullptr, uint32_t qual_thresh = 0)
 {
     const bool uniform = (read_offsets == nullptr);
     HIPCHK(hipSetDevice(ix->device));
@@ -1843,7 +1845,7 @@ static int map_reads_common(kmm_index_t *ix, const uint8_t *bases, const int64_t
         return KMM_OK;
     if (!bases)
         return fail(KMM_ERR_INVALID_ARG, "bases is NULL");
-    if (ix->host_pack_threads > 0 && (uniform ? read_len >= 16 : !offs_on_device) && !lut && use_radix(ix, total) &&
+    if (ix->host_pack_threads > 0 && (uniform ? read_len >= 16 : !offs_on_device) && !lut && !quals && use_radix(ix, total) &&
         !is_device_ptr(bases)) {
         bool done = false;
         KMMCHK(map_reads_host_packed(ix, bases, uniform ? nullptr : read_offsets, total, n_reads, read_len, k, max_freq, also_revcomp,
@@ -1859,6 +1861,9 @@ static int map_reads_common(kmm_index_t *ix, const uint8_t *bases, const int64_t
     ReadsView rv;
     memset(&rv, 0, sizeof rv);
     KMMCHK(stage_in<uint8_t>(ix, s.bases, bases, (size_t)total, &rv.bases, &staged));
+    const uint8_t *d_quals = nullptr;
+    if (quals)
+        KMMCHK(stage_in<uint8_t>(ix, s.quals, quals, (size_t)total, &d_quals, &staged));
     bool has_break = false;
     KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &staged, &has_break));
     rv.total = total;
@@ -1866,14 +1871,14 @@ static int map_reads_common(kmm_index_t *ix, const uint8_t *bases, const int64_t
     rv.first_bad = ix->first_bad;
     const int64_t n_tiles = (total + TILE_T - 1) / TILE_T;
     // the uniform kernel's wrap-around handles one read boundary per lane: needs read_len >= S.  A table with a break
-    // entry: the breaks are read boundaries only the bitset can hold — the ragged front end
-    const bool uniform_kernel = uniform && read_len >= 16 && !has_break;
+    // entry or a quality floor: the breaks are read boundaries only the bitset can hold — the ragged front end
+    const bool uniform_kernel = uniform && read_len >= 16 && !has_break && !quals;
     if (uniform_kernel) {
         set_uniform_geometry(ix, rv, read_len, k);
         KMMCHK(stage_copies_done(ix));
         KMMCHK(launch_map_reads<MODE_UNIFORM>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
     } else {
-        const bool arithmetic_starts = uniform && has_break; // (no offsets array: nothing on this route reads one)
+        const bool arithmetic_starts = uniform && (has_break || quals); // (no offsets array: nothing on this route reads one)
         if (uniform && !arithmetic_starts) {
             KMMCHK(ensure(s.offsets, (size_t)(n_reads + 1) * 8));
             hipLaunchKernelGGL(k_iota_offsets, dim3((unsigned)((n_reads + 1 + 255) / 256)), dim3(256),
@@ -1899,6 +1904,9 @@ static int map_reads_common(kmm_index_t *ix, const uint8_t *bases, const int64_t
         if (has_break) // every break byte: a one-base read
             hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (total + 256 * 16 * BRK_U - 1) / (256 * 16 * BRK_U), 8)), dim3(256), 0,
                                ix->stream, rv.bases, total, rv.lut, (uint32_t *)s.start_bits.p);
+        if (quals) // every quality byte below the floor: a one-base read, too
+            hipLaunchKernelGGL(k_mark_low_quals, dim3(grid_for(ix, (total + 256 * 16 * QUAL_U - 1) / (256 * 16 * QUAL_U), 8)), dim3(256), 0,
+                               ix->stream, d_quals, total, qual_thresh, (uint32_t *)s.start_bits.p, (unsigned long long *)ix->stats);
         if (!uniform)
             hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(ix, (n_reads + 255) / 256, 8)), dim3(256), 0,
                                ix->stream, rv.offsets, n_reads, ix->first_bad);
@@ -1970,6 +1978,31 @@ static int check_quality(const kmm_index_t *ix, const char *who, int k, bool sam
     if (k == 1)
         return fail(KMM_ERR_INVALID_ARG, "%s: k = 1 with min_base_quality %d: needs k >= 2", who, ix->min_base_quality);
     return KMM_OK;
+}
+
+// Flat reads with their quality bytes: kmm_map_reads (read_offsets given) or kmm_map_reads_uniform (NULL) with
+// "min_base_quality" applied to quals[p] < qual_base + Q.  With the floor off the call is one of those two, quals unread.
+int kmm_map_reads_qual(kmm_index_t *ix, const uint8_t *bases, const uint8_t *quals, int qual_base, const int64_t *read_offsets,
+                       int64_t n_reads, int64_t read_len, int k, int max_freq, int also_revcomp, const uint8_t *lut)
+{
+    if (!ix)
+        return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(check_k(k));
+    if (qual_base != 0 && qual_base != 33)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_map_reads_qual: qual_base %d: 33 (Phred+33 text) or 0 (raw Phred)", qual_base);
+    if (n_reads < 0 || (!read_offsets && read_len < 0))
+        return fail(KMM_ERR_INVALID_ARG, "n_reads / read_len negative");
+    if (n_reads == 0 || (!read_offsets && read_len == 0))
+        return KMM_OK;
+    KMMCHK(check_k_lut(k, lut));
+    KMMCHK(check_quality(ix, "kmm_map_reads_qual", k, false));
+    const int q = ix->min_base_quality;
+    if (q > 0 && !quals)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_map_reads_qual: quals is NULL with min_base_quality %d", q);
+    return guarded("kmm_map_reads_qual", [&] {
+        return map_reads_common(ix, bases, read_offsets, n_reads, read_offsets ? 0 : read_len, k, max_freq, also_revcomp, lut,
+                                q > 0 ? quals : nullptr, (uint32_t)(qual_base + q));
+    });
 }
 
 // Raw records on the radix path (r04): census -> the sequence bytes compacted into flat reads of 2-bit codes (one per

@@ -205,6 +205,78 @@ __global__ void __launch_bounds__(256) k_mark_breaks(const uint8_t *__restrict__
     }
 }
 
+// Quality bytes of flat reads (kmm_map_reads_qual with "min_base_quality" > 0) -> the read-start bitset:
+// quals[p] < thresh (unsigned; thresh = qual_base + Q, 1 .. 126) makes base p a one-base read, bits p and p + 1, exactly
+// as a break byte above; runs behind k_mark_starts / k_mark_breaks in stream order, on the same words.
+// The same stream as k_mark_breaks — 16 KiB per workgroup and round, QUAL_U 16-byte loads per lane issued before the
+// first is consumed — but the test is a compare, four bytes per operation (bytes_below, kmm_records.hpp), so there is no
+// LDS table, and low bytes are DENSE: at a few per cent of low bases most 32-position words hold one.  The word is
+// still written with a no-return atomic OR by the even lane that formed it (plus one for bit 31's carry): the
+// alternative — the incoming carry by shuffle and a plain load / OR / store of the word, atomics only at the wave's seam
+// — puts a dependent load between the compare and the store and has two write forms to keep right, while the atomic is
+// issued and forgotten and the L2 does the same read-modify-write either way (measured: the plain form takes 3.3 times as
+// long, profiles/flat_quality/README.md); the words are 1/8 of the bytes read.
+// Positions at or past `total` are cleared before anything else, so the highest mark is bit `total`: word total / 32 of
+// the total / 32 + 2 the bitset has, whatever the bytes hold.  The low bytes are counted per lane (before the << 1),
+// summed over the wave and the workgroup, and added once per workgroup to statistics slot KMM_STAT_QUAL_MASKED.
+constexpr int QUAL_U = 4;
+__global__ void __launch_bounds__(256) k_mark_low_quals(const uint8_t *__restrict__ quals, int64_t total, uint32_t thresh,
+                                                        uint32_t *__restrict__ bits, unsigned long long *__restrict__ stats)
+{
+    __shared__ uint32_t s_wave[4];
+    const bool aligned = (((uintptr_t)quals) & 15u) == 0;
+    constexpr int64_t SPAN = (int64_t)256 * 16 * QUAL_U;
+    uint32_t n_low = 0;
+    for (int64_t base = (int64_t)blockIdx.x * SPAN; base < total; base += (int64_t)gridDim.x * SPAN) {
+        uint32_t w[QUAL_U][4];
+#pragma unroll
+        for (int u = 0; u < QUAL_U; ++u) {
+            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
+            if (p + 16 <= total) {
+                u32x4 x;
+                if (aligned)
+                    x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(quals + p));
+                else
+                    __builtin_memcpy(&x, quals + p, 16); // (one unaligned 16-byte load: rec_load16)
+                w[u][0] = x[0]; w[u][1] = x[1]; w[u][2] = x[2]; w[u][3] = x[3];
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    w[u][i] = p < total ? tile_load_bytes4(quals, total, p + 4 * i) : 0u;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < QUAL_U; ++u) {
+            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
+            uint32_t m = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                m |= flags_to_bits(bytes_below(w[u][i], thresh)) << (4 * i);
+            const int64_t left = total - p; // (bytes past the end read as 0, which is below every threshold)
+            if (left < 16)
+                m &= left > 0 ? (1u << left) - 1u : 0u;
+            n_low += (uint32_t)__popc(m);
+            const uint32_t hi = (uint32_t)__shfl_xor((int)m, 1);
+            if (!(threadIdx.x & 1u)) {
+                const uint32_t word = m | (hi << 16);
+                if (word) {
+                    const int64_t wi = p >> 5; // (p is a multiple of 32 for even lanes)
+                    atomicOr(&bits[wi], word | (word << 1));
+                    if (word >> 31)
+                        atomicOr(&bits[wi + 1], 1u);
+                }
+            }
+        }
+    }
+    n_low = wave_sum(n_low);
+    if ((threadIdx.x & 63) == 0)
+        s_wave[threadIdx.x >> 6] = n_low;
+    __syncthreads();
+    const uint32_t n_wg = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    if (threadIdx.x == 0 && n_wg)
+        atomicAdd(&stats[(size_t)(blockIdx.x % KMM_STAT_SHARDS) * KMM_STAT_STRIDE + KMM_STAT_QUAL_MASKED], (unsigned long long)n_wg);
+}
+
 // read_offsets must be non-decreasing; checked here (off the host's critical path) and reported at the
 // next synchronising call.  A violation cannot make the map kernels touch memory out of bounds.
 __global__ void k_check_offsets(const int64_t *__restrict__ offs, int64_t n_reads, unsigned long long *first_bad)

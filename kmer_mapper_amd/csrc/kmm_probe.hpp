@@ -154,7 +154,7 @@ constexpr int KMM_STAT_STRIDE = 32; // unsigned long longs = 256 bytes between s
 // slots: [0] k-mer lookups, [1] hits, [2] k-mers gathered by radix pass 2, [3] probed by radix pass 3, [4..15] phase
 // timers of diagnostic builds, [16] k-mers emitted by radix pass 1, [17] dropped by pass 2's empty-bucket filter,
 // [18] pass-2 items placed and copied out in several rounds (slot filter: more survivors than sort-buffer slots),
-// [19] FASTQ bases masked by "min_base_quality" (k_rec_scatter's quality variant), [20] 8-byte key reads of pass 3's probes
+// [19] bases masked by "min_base_quality" (k_rec_scatter's quality variant, k_mark_low_quals), [20] 8-byte key reads of pass 3's probes
 // (-DRX_P3_FP_STATS builds only)
 constexpr int KMM_STAT_RX_P1 = 16, KMM_STAT_RX_DROPPED = 17, KMM_STAT_RX_MULTI = 18, KMM_STAT_QUAL_MASKED = 19, KMM_STAT_RX_P3_KEYS = 20;
 constexpr int AGG_LOG_SLOTS = 11;

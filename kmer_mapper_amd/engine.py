@@ -174,8 +174,20 @@ class DeviceIndex:
         _lib.check(_lib.lib().kmm_map_kmers(self._h, a.ptr, a.n, int(max_index_lookup_frequency),
                                             int(bool(also_revcomp)), int(k)))
 
+    def _map_reads_qual(self, b, qualities, qual_base, o, n_reads, read_len, k, max_index_lookup_frequency, also_revcomp, t):
+        """kmm_map_reads_qual: the reads of map_reads (o given) / map_reads_uniform (o None) with one quality byte per base."""
+        q = _Arg(qualities, np.uint8, "qualities")
+        if q.n != b.n:
+            raise ValueError("qualities holds %d bytes, bases %d: one quality byte per base" % (q.n, b.n))
+        _lib.check(_lib.lib().kmm_map_reads_qual(self._h, b.ptr, q.ptr, int(qual_base), o.ptr if o is not None else None,
+                                                 int(n_reads), int(read_len), int(k), int(max_index_lookup_frequency),
+                                                 int(bool(also_revcomp)), t.ptr))
+
     def map_reads(self, bases, read_offsets, k=31, max_index_lookup_frequency=1000,
-                  also_revcomp=False, lut=None):
+                  also_revcomp=False, lut=None, qualities=None, qual_base=33):
+        """qualities: one quality byte per base (what `bases` takes, host or device) — with set_param("min_base_quality", Q)
+        a base whose byte is below qual_base + Q is a break (kmm_map_reads_qual; qual_base 33 = Phred+33 text, 0 = raw
+        Phred as BAM stores it).  None: kmm_map_reads, which knows no floor."""
         b = _Arg(bases, np.uint8, "bases")
         o = _Arg(read_offsets, np.int64, "read_offsets")
         t = _Arg(lut, np.uint8, "lut")
@@ -183,17 +195,23 @@ class DeviceIndex:
             raise ValueError("lut must have 256 entries")
         if o.n < 1:
             raise ValueError("read_offsets needs n_reads+1 entries")
+        if qualities is not None:
+            return self._map_reads_qual(b, qualities, qual_base, o, o.n - 1, 0, k, max_index_lookup_frequency, also_revcomp, t)
         _lib.check(_lib.lib().kmm_map_reads(self._h, b.ptr, o.ptr, o.n - 1, int(k),
                                             int(max_index_lookup_frequency),
                                             int(bool(also_revcomp)), t.ptr))
 
     def map_reads_uniform(self, bases, n_reads, read_len, k=31, max_index_lookup_frequency=1000,
-                          also_revcomp=False, lut=None):
+                          also_revcomp=False, lut=None, qualities=None, qual_base=33):
+        """qualities / qual_base: as map_reads."""
         b = _Arg(bases, np.uint8, "bases")
         t = _Arg(lut, np.uint8, "lut")
         if b.n < int(n_reads) * int(read_len):
             raise ValueError("bases holds %d bytes, need n_reads*read_len=%d"
                              % (b.n, int(n_reads) * int(read_len)))
+        if qualities is not None:
+            return self._map_reads_qual(b, qualities, qual_base, None, n_reads, read_len, k, max_index_lookup_frequency,
+                                        also_revcomp, t)
         _lib.check(_lib.lib().kmm_map_reads_uniform(self._h, b.ptr, int(n_reads), int(read_len),
                                                     int(k), int(max_index_lookup_frequency),
                                                     int(bool(also_revcomp)), t.ptr))
@@ -203,10 +221,11 @@ class DeviceIndex:
         """Map a raw FASTQ (fmt=4) / two-line FASTA (fmt=2) / SAM (fmt=8; "bam_exclude_flags" filters it) chunk parsed on
         the GPU.
         Returns (consumed_bytes, n_records); the caller carries raw[consumed:] to the next chunk.
-        A base-quality floor needs no method of its own: set_param("min_base_quality", Q) makes every FASTQ base whose
+        A base-quality floor is a parameter of the handle: set_param("min_base_quality", Q) makes every FASTQ base whose
         quality byte is below '!' + Q a break, on this call and on map_bgzf / map_gzip (no effect on FASTA; SAM and map_bam
         are refused while it is set), and get_param("quality_masked_bases") counts the bases it masked since the last
-        get_stats(reset=True)."""
+        get_stats(reset=True).  Reads already held as arrays bring their quality bytes to map_reads / map_reads_uniform
+        (qualities=...), which apply the same floor."""
         b = _Arg(raw, np.uint8, "raw")
         t = _Arg(lut, np.uint8, "lut")
         n = _n_bytes(b, n_bytes)
