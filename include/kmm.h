@@ -240,7 +240,9 @@ int kmm_map_reads_qual(kmm_index_t *idx, const uint8_t *bases, const uint8_t *qu
  *   - refused with KMM_ERR_MALFORMED, nothing of the call mapped, the message naming the first bad line's byte offset: a
  *     record line with fewer than 10 TABs, a FLAG that is no decimal integer in [0, 65535], an empty line;
  *   - refused with KMM_ERR_INVALID_ARG while "min_base_quality" (kmm_set_param) is above 0, on every entry point that takes
- *     the format: the writer emits two-line FASTA, the QUAL column is not carried to the mapper.
+ *     the format: the writer emits two-line FASTA, the QUAL column is not carried to the mapper — unless "use_record_qual"
+ *     (kmm_set_param) is 1: field 11 (QUAL, Phred+33) is then written beside SEQ and the floor applied to it.  A QUAL that
+ *     is not "*" and not as long as SEQ (SEQ "*": length 0) is one more KMM_ERR_MALFORMED of the list above.
  * Counters (kmm_get_param): "sam_calls", "sam_records", "sam_records_excluded", "sam_header_lines". */
 #define KMM_FORMAT_SAM 8
 int kmm_map_records(kmm_index_t *idx, const uint8_t *raw, int64_t n_bytes, int format, int k,
@@ -323,7 +325,8 @@ int kmm_map_gzip(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int form
  * Counters (kmm_get_param): "bam_calls", "bam_records", "bam_records_excluded", "bam_header_bytes", "bam_false_starts",
  * "bam_continuations".  SAM text is read by kmm_map_bgzf / kmm_map_gzip / kmm_map_records (KMM_FORMAT_SAM); CRAM is not read.
  * While "min_base_quality" (kmm_set_param) is above 0 the call is refused with KMM_ERR_INVALID_ARG: the records' qual bytes
- * are not decoded, and ignoring the floor silently is not an option.
+ * are not decoded, and ignoring the floor silently is not an option — unless "use_record_qual" (kmm_set_param) is 1: the
+ * qual bytes (raw Phred) are then decoded beside SEQ and the floor applied to them.
  */
 int kmm_map_bam(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int flags, int k, int max_index_lookup_frequency,
                 int also_revcomp, const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
@@ -501,7 +504,7 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      is unaffected and kmm_get_stats' n_lookups counts the surviving windows.  A table with break entries
  *                      combines with it: a base is dead if either rule kills it.  k = 1 is KMM_ERR_INVALID_ARG (as for a
  *                      break table).  KMM_FORMAT_FASTA2 / KMM_FORMAT_FASTA have no qualities: no effect.  KMM_FORMAT_SAM and
- *                      kmm_map_bam are refused with KMM_ERR_INVALID_ARG while Q > 0.  The FASTQ piece always takes
+ *                      kmm_map_bam are refused with KMM_ERR_INVALID_ARG while Q > 0, unless "use_record_qual" is 1.  The FASTQ piece always takes
  *                      compaction + the radix path, at every batch size and whatever "path" says (as kmm_map_packed; an
  *                      index with "radix_available" 0: KMM_ERR_INVALID_ARG), and never the host packer
  *                      ("host_packed_record_calls" does not move).  A record whose quality line does not have as many
@@ -511,6 +514,26 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      were last reset (kmm_get_stats(reset)); synchronises like kmm_get_stats.  Flat reads
  *                      (kmm_map_reads, kmm_map_reads_uniform) carry no qualities and are unaffected; kmm_map_reads_qual
  *                      takes them as a second array and applies the same floor (its own rules are at its declaration)
+ *   "use_record_qual"  0 (default) or 1; anything else KMM_ERR_INVALID_ARG.  0: the library as it is without the parameter, bit
+ *                      for bit, the refusals above included.  1 and "min_base_quality" Q > 0: kmm_map_bam, and
+ *                      kmm_map_records / kmm_map_bgzf / kmm_map_gzip with KMM_FORMAT_SAM, are served: every kept record's
+ *                      QUAL is decoded beside its SEQ (csrc/kmm_bam.hpp, csrc/kmm_sam.hpp) and the floor applied
+ *                      with the rules of "min_base_quality".  BAM qual bytes are raw Phred: a base is masked iff its byte
+ *                      is < Q (0xFF and every other byte >= 93 are never masked); SAM QUAL bytes are Phred+33: masked iff
+ *                      the unsigned byte is < 33 + Q.  A SAM QUAL that is exactly "*" (a one-base read's too, as htslib reads
+ *                      it) and BAM qual bytes that start with 0xFF mean that the record stores no qualities: every base of
+ *                      it survives — the caller who sets the switch accepts that — and the record is counted.  Records
+ *                      dropped by "bam_exclude_flags" are not looked at.  *n_records, "sam_records" / "bam_records" are
+ *                      unaffected; "quality_masked_bases" counts the low bytes of the kept records.  The records reach the
+ *                      mapper as four-line FASTQ text in HBM, so what holds for KMM_FORMAT_FASTQ with a floor holds here:
+ *                      compaction + the radix path whatever "path" says, and an index with "radix_available" 0 is refused
+ *                      with KMM_ERR_INVALID_ARG ("min_base_quality needs the radix path"); k = 1 is KMM_ERR_INVALID_ARG.  A
+ *                      SAM record whose QUAL is not "*" and not as long as its SEQ is KMM_ERR_MALFORMED, nothing of the call
+ *                      mapped, the message naming the line's byte offset in the chunk (BAM: block_size already holds l_seq
+ *                      qual bytes).  1 and Q = 0: QUAL is not read, not even its length — the calls are the ones without the
+ *                      switch.  No effect on FASTQ, FASTA or flat reads.  Read-only "records_without_qual": kept SAM / BAM
+ *                      records with at least one base that store no qualities, counted while the floor is applied, since
+ *                      the statistics were last reset (kmm_get_stats(reset)); synchronises like "quality_masked_bases"
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the

@@ -171,16 +171,19 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
 
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
-                exclude_flags=0, probe=None, lut=None, min_base_quality=0):
+                exclude_flags=0, probe=None, lut=None, min_base_quality=0, use_record_qual=False):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
     on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
     extracted on the GPU (KMM_FORMAT_SAM on the routes of a FASTQ; exclude_flags filters it too).  probe: reads_io.probe_input
     of the file, if the caller has it.  lut: the lookup table of every call, on every route (None: the default).
-    min_base_quality: the handle's "min_base_quality", set before the first map call on every route (FASTQ alone has qualities:
-    SAM / BAM are refused before the index goes up, FASTA is mapped as before with a warning)."""
+    min_base_quality: the handle's "min_base_quality", set before the first map call on every route (FASTQ has qualities;
+    SAM / BAM are refused before the index goes up unless use_record_qual is given; FASTA is mapped as before with a warning).
+    use_record_qual: the handle's "use_record_qual" — the QUAL of SAM / BAM records is decoded on the GPU and the floor applied
+    (DESIGN 4.12); records that store no qualities pass unmasked and are counted ("records_without_qual")."""
     _check_bam_route(fmt, world_size, exclude_flags)
-    min_base_quality = check_min_base_quality(min_base_quality, k, fmt)
+    use_record_qual = check_use_record_qual(use_record_qual, fmt, min_base_quality)
+    min_base_quality = check_min_base_quality(min_base_quality, k, fmt, use_record_qual=use_record_qual)
     t_index = time.perf_counter()
     probe = probe_input(path) if probe is None else probe
     has_device = _lib.device_count() > 0
@@ -225,6 +228,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     dev.set_param("host_pack_threads", n_host if n_threads > 1 else 0)
     if min_base_quality:
         dev.set_param("min_base_quality", min_base_quality)
+    if use_record_qual:
+        dev.set_param("use_record_qual", 1)
     from . import _io
     _io.set_default_threads(n_host)
     logging.info("%d host thread(s) read and pack the read bytes (-t %d, CPU budget %d)", n_host, n_threads, _io.cpu_budget())
@@ -288,7 +293,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             helper.join()
         return _map_compressed_file(dev, path, route, kfmt, k, max_index_lookup_frequency,
                                     map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
-                                    world_size=world_size, fmt=fmt, lut=lut, min_base_quality=min_base_quality)
+                                    world_size=world_size, fmt=fmt, lut=lut, min_base_quality=min_base_quality,
+                                    use_record_qual=use_record_qual)
     try:
         i = 0
         while True:
@@ -316,6 +322,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
         n_host_packed = dev.get_param("host_packed_record_calls")
         n_masked = dev.get_param("quality_masked_bases") if min_base_quality else None
+        n_no_qual = dev.get_param("records_without_qual") if (min_base_quality and use_record_qual) else 0
         if before_fetch is not None:
             before_fetch(dev)
         if helper.is_alive() or helper.ident is not None:
@@ -345,19 +352,35 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     logging.info("Mapped %d reads from %d bytes (%.1f MB/s, GPU record parser): %d k-mer lookups "
                  "(%.1f M/s), %d index hits" % (n_reads, n_bytes, n_bytes / max(dt, 1e-9) / 1e6, n_lookups,
                                                   n_lookups / max(dt, 1e-9) / 1e6, n_hits))
-    _log_quality_masked(min_base_quality, n_masked)
+    _log_quality_masked(min_base_quality, n_masked, n_no_qual)
     _log_path_taken(n_radix, n_direct, n_host_packed)
     return node_counts
 
 
-def _log_quality_masked(min_base_quality, n_masked):
+def _log_quality_masked(min_base_quality, n_masked, n_no_qual=0):
     if min_base_quality:
         logging.info("quality_masked_bases: %d bases below Q%d, no k-mer over them counted", n_masked, min_base_quality)
+        if n_no_qual:
+            logging.info("records_without_qual: %d records store no qualities (QUAL '*' / 0xFF): they passed Q%d unmasked",
+                         n_no_qual, min_base_quality)
 
 
-def check_min_base_quality(min_base_quality, k, fmt=None, host_parser=False):
+def check_use_record_qual(use_record_qual, fmt, min_base_quality):
+    """--use-record-qual against what it cannot go with; returns whether it applies (not without a floor: one warning)."""
+    if not use_record_qual:
+        return False
+    if fmt not in ("sam", "bam"):
+        raise ValueError("--use-record-qual applies to SAM and BAM input only (the reads are %s)" % fmt)
+    if not int(min_base_quality or 0):
+        logging.warning("--use-record-qual has no effect without --min-base-quality: QUAL is not read")
+        return False
+    return True
+
+
+def check_min_base_quality(min_base_quality, k, fmt=None, host_parser=False, use_record_qual=False):
     """--min-base-quality against what it cannot go with, before anything is uploaded; returns the floor that applies (0 for
-    FASTA, which has no qualities, after one warning).  fmt None: the format is not known yet (the argument parser)."""
+    FASTA, which has no qualities, after one warning).  fmt None: the format is not known yet (the argument parser).
+    use_record_qual: SAM and BAM are served — their QUAL is decoded on the GPU (--use-record-qual)."""
     q = int(min_base_quality or 0)
     if not 0 <= q <= 93:
         raise ValueError("--min-base-quality must lie in 0 .. 93 (Phred+33 qualities are '!' .. '~')")
@@ -365,9 +388,10 @@ def check_min_base_quality(min_base_quality, k, fmt=None, host_parser=False):
         return 0
     if k < 2:
         raise ValueError("--min-base-quality needs -k 2 or more")
-    if fmt in ("sam", "bam"):
+    if fmt in ("sam", "bam") and not use_record_qual:
         raise ValueError("--min-base-quality applies to FASTQ input: the QUAL column of %s records is not carried to the GPU "
-                         "(convert to FASTQ, or drop the option)" % fmt.upper())
+                         "(convert to FASTQ, or drop the option; or pass --use-record-qual to have it decoded there: records "
+                         "that store no qualities then pass the floor unmasked)" % fmt.upper())
     if host_parser:
         raise ValueError("--min-base-quality reads the qualities on the GPU: the host parser hands it reads without them "
                          "(drop --host-parser)")
@@ -403,7 +427,7 @@ _COMPRESSED_ROUTES = {
 
 
 def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None, rank=0,
-                         world_size=1, fmt="fastq", lut=None, min_base_quality=0):
+                         world_size=1, fmt="fastq", lut=None, min_base_quality=0, use_record_qual=False):
     """`kmer_mapper map -f reads.fq.gz | reads.bam` with the GPU inflater: windows of the file mapping -> kmm_map_<route>.
 
     route "gzip" (PLAIN gzip, kmm_map_gzip): each call goes on where the one before could verify a deflate block boundary.
@@ -497,6 +521,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
         n_lookups, n_hits = dev.get_stats()
         counts = [dev.get_param(c) for c in counters]
         n_masked = dev.get_param("quality_masked_bases") if min_base_quality else None
+        n_no_qual = dev.get_param("records_without_qual") if (min_base_quality and use_record_qual) else 0
         n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
         if before_fetch is not None:
             before_fetch(dev)
@@ -510,7 +535,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
     logging.info("Time spent only on hashing and counting hashes: %.5f" % dt)
     logging.info(summary % (n_reads, size - lo, (size - lo) / max(dt, 1e-9) / 1e6, *counts, n_lookups,
                             n_lookups / max(dt, 1e-9) / 1e6, n_hits))
-    _log_quality_masked(min_base_quality, n_masked)
+    _log_quality_masked(min_base_quality, n_masked, n_no_qual)
     _log_path_taken(n_radix, n_direct)
     return node_counts
 
@@ -583,7 +608,9 @@ def map_bnp(args):
         lut = ambiguous_skip_lut()
         if k < 2:
             raise ValueError("--ambiguous-bases skip needs -k 2 or more")
-    min_q = check_min_base_quality(getattr(args, "min_base_quality", 0), k, fmt, bool(getattr(args, "host_parser", False)))
+    use_qual = check_use_record_qual(bool(getattr(args, "use_record_qual", False)), fmt, getattr(args, "min_base_quality", 0))
+    min_q = check_min_base_quality(getattr(args, "min_base_quality", 0), k, fmt, bool(getattr(args, "host_parser", False)),
+                                   use_record_qual=use_qual)
     if fmt == "bam" and getattr(args, "host_parser", False):
         raise ValueError("--host-parser does not read BAM: its records are decoded on the GPU (drop --host-parser)")
     if fmt == "sam" and getattr(args, "host_parser", False):
@@ -594,7 +621,7 @@ def map_bnp(args):
         node_counts = map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, revcomp, max_freq,
                                   device=device, rank=rank, world_size=world, before_fetch=before_fetch,
                                   n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe, lut=lut,
-                                  min_base_quality=min_q)
+                                  min_base_quality=min_q, use_record_qual=use_qual)
     else:
         logging.info("Using the host FASTA/FASTQ parser")
         if world > 1 and not probe.inflate:
@@ -670,9 +697,13 @@ def build_argument_parser():
                                 "(extension): no k-mer that contains N or an IUPAC ambiguity letter is counted; the k-mers on "
                                 "either side of it are.")
     subparser.add_argument("--min-base-quality", default=0, type=int, metavar="Q",
-                           help="Extension, FASTQ input: a base whose Phred+33 quality is below Q (0 .. 93) is skipped like an "
+                           help="Extension, FASTQ input (SAM / BAM with --use-record-qual): a base whose Phred+33 quality is below Q (0 .. 93) is skipped like an "
                                 "ambiguous base under --ambiguous-bases skip: no k-mer that contains it is counted. Default 0: "
                                 "qualities are not read.")
+    subparser.add_argument("--use-record-qual", action="store_true",
+                           help="Extension, SAM and BAM input only, with --min-base-quality: decode every record's QUAL on the GPU "
+                                "and apply the floor to it. Records that store no qualities (QUAL '*', 0xFF in BAM) pass unmasked "
+                                "and are counted in the log. Without it, --min-base-quality is refused on SAM and BAM.")
     subparser.set_defaults(func=map_bnp)
     return parser
 

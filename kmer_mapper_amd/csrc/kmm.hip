@@ -389,6 +389,7 @@ struct kmm_index : IndexStreams, RxArrays {
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
     int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
     int min_base_quality = 0;    // "min_base_quality": > 0: a FASTQ base whose quality byte is below 33 + this is a break (flat reads: 4.11)
+    int use_record_qual = 0;     // "use_record_qual": 1: with a floor set, SAM / BAM records are mapped with their QUAL
     int64_t dbg_rec_piece_kb = 0; // test hook ("debug_records_piece_kb"): bytes per piece of kmm_map_records, KiB (0: 2^30 bytes)
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
     bool rx_filter_slots = true;  // "radix_filter_slots": where the geometry allows it the filter is the slot filter (0: the bucket bitmap)
@@ -1966,15 +1967,29 @@ static int records_quality(const kmm_index_t *ix, int format)
     return format == KMM_FORMAT_FASTQ ? ix->min_base_quality : 0;
 }
 
+// The quality floor that applies to SAM / BAM records: "min_base_quality" once "use_record_qual" is set (the decoders then
+// write four-line FASTQ), else none — QUAL is not read at all, not even its length.
+static int record_quality(const kmm_index_t *ix)
+{
+    return ix->use_record_qual ? ix->min_base_quality : 0;
+}
+
 // "min_base_quality" > 0 and what it cannot go with: k = 1 (the masked base's own window could not be killed: check_k_lut)
-// and the formats whose writers emit two-line FASTA, without QUAL (sam: KMM_FORMAT_SAM or kmm_map_bam).
+// and the formats whose writers emit two-line FASTA, without QUAL (sam: KMM_FORMAT_SAM or kmm_map_bam), unless
+// "use_record_qual" asks for their quality variants — whose FASTQ text is mapped by the radix path alone.
 static int check_quality(const kmm_index_t *ix, const char *who, int k, bool sam)
 {
     if (ix->min_base_quality <= 0)
         return KMM_OK;
-    if (sam)
+    if (sam && !ix->use_record_qual)
         return fail(KMM_ERR_INVALID_ARG, "%s: min_base_quality %d is set, and SAM / BAM records are mapped without their QUAL "
-                    "column: set it to 0 for this input", who, ix->min_base_quality);
+                    "column: set it to 0 for this input, or set \"use_record_qual\" to 1 (records that store no qualities then "
+                    "pass the floor unmasked: \"records_without_qual\")", who, ix->min_base_quality);
+    if (sam && !ix->rx_ok)
+        return fail(KMM_ERR_INVALID_ARG, "%s: min_base_quality needs the radix path, which is not available for this "
+                    "index (kmm_get_param \"radix_unavailable_reason\")", who);
+    if (sam && ix->dbg_rec_skip)
+        return fail(KMM_ERR_INVALID_ARG, "%s: min_base_quality does not go with debug_records_skip", who);
     if (k == 1)
         return fail(KMM_ERR_INVALID_ARG, "%s: k = 1 with min_base_quality %d: needs k >= 2", who, ix->min_base_quality);
     return KMM_OK;
@@ -2358,25 +2373,28 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
     KMMCHK(ensure(ix->sam_tiles, (size_t)n_tiles * sizeof(kmm_sam::Tile) + 64));
     KMMCHK(ensure(ix->sam_base, (size_t)n_tiles * 8 + 64));
     KMMCHK(ensure(ix->sam_ctl, 256));
-    if (!dry)
+    const bool qual = record_quality(ix) > 0; // the quality variant: four-line FASTQ, mapped with the floor
+    if (!dry && !qual)
         KMMCHK(ensure(s.kmers, (size_t)n_bytes + 16)); // (a record's output is never longer than its line)
     kmm_sam::Tile *tiles = (kmm_sam::Tile *)ix->sam_tiles.p;
     unsigned long long *base = (unsigned long long *)ix->sam_base.p;
     kmm_sam::Totals *d_tot = (kmm_sam::Totals *)ix->sam_ctl.p;
-    uint8_t *out = (uint8_t *)s.kmers.p;
     const uint32_t excl = ix->bam_excl;
     KMMCHK(stage_copies_done(ix));
     hipStream_t cs = ix->stream; // (kernels run on the handle's stream only: see rec_compact_piece)
     const dim3 gw((unsigned)grid_for(ix, (int64_t)((n_tiles + 3) / 4), 16)); // one wavefront per tile, 4 per block, grid-stride
-    hipLaunchKernelGGL(kmm_sam::k_sam_count, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl, tiles);
+    if (qual)
+        hipLaunchKernelGGL(kmm_sam::k_sam_count_q, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl, tiles);
+    else
+        hipLaunchKernelGGL(kmm_sam::k_sam_count, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl, tiles);
     hipLaunchKernelGGL(kmm_sam::k_sam_totals, dim3(1), dim3(1024), 0, cs, (const kmm_sam::Tile *)tiles, n_tiles, base, d_tot);
     HIPCHK(hipGetLastError());
     kmm_sam::Totals h;
     HIPCHK(hipMemcpyAsync(&h, d_tot, sizeof h, hipMemcpyDeviceToHost, cs));
     HIPCHK(hipStreamSynchronize(cs)); // (the borrowed host buffer is free from here on)
     if (h.err != kmm_sam::NONE) {
-        static const char *why[4] = {"?", "fewer than 11 TAB-separated fields", "FLAG is not a decimal integer in [0, 65535]",
-                                     "an empty line"};
+        static const char *why[4] = {"QUAL is not \"*\" and not as long as SEQ", "fewer than 11 TAB-separated fields",
+                                     "FLAG is not a decimal integer in [0, 65535]", "an empty line"};
         (void)stage_release(ix, s, false);
         return fail(KMM_ERR_MALFORMED, "kmm_map_records: SAM line at byte %llu of the chunk: %s (nothing of the call is mapped)",
                     (unsigned long long)at + (h.err >> 2), why[h.err & 3]);
@@ -2387,7 +2405,27 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
         ix->sam_records += (int64_t)h.recs;
         ix->sam_excluded += (int64_t)h.excluded;
         ix->sam_header_lines += (int64_t)h.headers;
-        if (h.recs > 0) {
+        if (h.recs > 0 && qual) {
+            // (with QUAL "*" a record's four-line FASTQ is longer than its line: the buffer is sized from the totals)
+            rc = ensure(s.kmers, (size_t)h.out_bytes + 16);
+            if (rc == KMM_OK) {
+                hipLaunchKernelGGL(kmm_sam::k_sam_write_q, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
+                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
+                                   ix->stats + KMM_STAT_REC_NO_QUAL);
+                const hipError_t e = hipGetLastError();
+                if (e != hipSuccess)
+                    rc = fail(KMM_ERR_HIP, "kmm_map_records: k_sam_write_q: %s", hipGetErrorString(e));
+            }
+            // the records as FASTQ, from HBM, through compaction and the radix path, where the floor is applied
+            int64_t used = 0;
+            if (rc == KMM_OK)
+                rc = map_records_radix_call(ix, (const uint8_t *)s.kmers.p, (int64_t)h.out_bytes, KMM_FORMAT_FASTQ, k, max_freq,
+                                            also_revcomp, lut, &used, n_records);
+            if (rc == KMM_OK && (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs))
+                rc = fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %llu written bytes, %lld of %llu records mapped", (long long)used,
+                          h.out_bytes, (long long)*n_records, h.recs);
+        } else if (h.recs > 0) {
+            uint8_t *out = (uint8_t *)s.kmers.p;
             hipLaunchKernelGGL(kmm_sam::k_sam_write, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
                                (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out);
             HIPCHK(hipGetLastError());
@@ -2440,6 +2478,7 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     // A quality floor on FASTQ: always compaction + the radix path, whatever the batch size and "path" say (as kmm_map_packed) —
     // the records front end of the direct path has no flat positions to put a quality mark on — and never the host packer,
     // whose parser skips the quality lines.
+    // (SAM with "use_record_qual" comes back here as FASTQ text, piece by piece: map_sam_piece)
     if (records_quality(ix, format) > 0) {
         if (!ix->rx_ok)
             return fail(KMM_ERR_INVALID_ARG, "kmm_map_records: min_base_quality needs the radix path, which is not available for this "
@@ -3031,6 +3070,7 @@ struct BamGpuBackend {
     uint64_t n;
     int32_t n_ref;
     uint32_t excl;
+    bool qual = false; // the quality variant: four-line FASTQ, 2 l_seq + 6 bytes per kept record
     int cur = 0;
 
     kmm_bam::Tile *tiles(int i) { return (kmm_bam::Tile *)ix->bam_tiles[i].p; }
@@ -3048,7 +3088,10 @@ struct BamGpuBackend {
         cur = 0;
         HIPCHK(hipMemsetAsync(ctl(), 0, sizeof(kmm_bam::Ctl), ix->stream));
         HIPCHK(hipMemsetAsync(&ctl()->err_pos, 0xFF, 8, ix->stream)); // (no error)
-        hipLaunchKernelGGL(kmm_bam::k_bam_spec, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl, tiles(0));
+        if (qual)
+            hipLaunchKernelGGL(kmm_bam::k_bam_spec_q, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl, tiles(0));
+        else
+            hipLaunchKernelGGL(kmm_bam::k_bam_spec, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl, tiles(0));
         HIPCHK(hipGetLastError());
         return KMM_OK;
     }
@@ -3065,8 +3108,12 @@ struct BamGpuBackend {
     }
     int fix(uint64_t n_tiles, uint64_t start0)
     {
-        hipLaunchKernelGGL(kmm_bam::k_bam_fix, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl,
-                           (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
+        if (qual)
+            hipLaunchKernelGGL(kmm_bam::k_bam_fix_q, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl,
+                               (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
+        else
+            hipLaunchKernelGGL(kmm_bam::k_bam_fix, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl,
+                               (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
         HIPCHK(hipGetLastError());
         cur ^= 1;
         return KMM_OK;
@@ -3083,8 +3130,13 @@ struct BamGpuBackend {
     }
     int decode(uint64_t n_tiles, uint8_t *out)
     {
-        hipLaunchKernelGGL(kmm_bam::k_bam_decode, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
-                           (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out);
+        if (qual)
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode_q, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
+                               (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out,
+                               ix->stats + KMM_STAT_REC_NO_QUAL);
+        else
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
+                               (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out);
         HIPCHK(hipGetLastError());
         return KMM_OK;
     }
@@ -3129,7 +3181,8 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     } else if (ix->bam_n_ref < 0) {
         return fail(KMM_ERR_INVALID_ARG, "kmm_map_bam: no BAM stream was started on this handle (KMM_FORMAT_NEW_STREAM)");
     }
-    BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl};
+    const bool qual = record_quality(ix) > 0;
+    BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl, qual};
     kmm_bam::CallOut co;
     KMMCHK(kmm_bam::run_call(be, (uint64_t)n_raw, start0, co));
     ix->bam_false_starts += (int64_t)co.false_starts;
@@ -3149,8 +3202,9 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     KMMCHK(ensure(ix->bam_out, (size_t)co.out_bytes + 64));
     KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p));
     int64_t taken = 0, recs = 0;
-    KMMCHK(kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, KMM_FORMAT_FASTA2, c.k, c.max_freq, c.also_revcomp,
-                           c.lut, &taken, &recs));
+    // (the quality variant's text is FASTQ: compaction and the radix path, where "min_base_quality" is applied)
+    KMMCHK(kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, qual ? KMM_FORMAT_FASTQ : KMM_FORMAT_FASTA2, c.k,
+                           c.max_freq, c.also_revcomp, c.lut, &taken, &recs));
     if (taken != (int64_t)co.out_bytes || recs != (int64_t)co.recs)
         return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %llu decoded bytes, %lld of %llu records mapped", (long long)taken,
                     co.out_bytes, (long long)recs, co.recs);
@@ -3952,6 +4006,11 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value < 0 || value > 93)
             return fail(KMM_ERR_INVALID_ARG, "min_base_quality outside [0, 93]");
         ix->min_base_quality = (int)value;
+    } else if (!strcmp(name, "use_record_qual")) {
+        // 1: with "min_base_quality" > 0, kmm_map_bam and KMM_FORMAT_SAM decode every record's QUAL and apply the floor
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "use_record_qual takes 0 or 1");
+        ix->use_record_qual = (int)value;
     } else if (!strcmp(name, "debug_records_piece_kb")) {
         // test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a few hundred KB then make several pieces
         if (value < 0 || value > (1 << 20))
@@ -4010,6 +4069,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->dbg_gzip_chunk_kb;
     else if (!strcmp(name, "min_base_quality"))
         *value = ix->min_base_quality;
+    else if (!strcmp(name, "use_record_qual"))
+        *value = ix->use_record_qual;
     else if (!strcmp(name, "debug_records_piece_kb"))
         *value = ix->dbg_rec_piece_kb;
     else if (!strcmp(name, "bam_calls")) // kmm_map_bam calls that mapped their records (a window inside the header not counted)
@@ -4121,6 +4182,7 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->rx_ok ? ix->rx_geo.F1 : 0;
     else if (!strcmp(name, "radix_p2_kmers") || !strcmp(name, "radix_p3_kmers") || !strcmp(name, "radix_p2_dropped") ||
              !strcmp(name, "radix_p2_multi_round_items") || !strcmp(name, "quality_masked_bases") ||
+             !strcmp(name, "records_without_qual") ||
              !strcmp(name, "debug_p3_key_reads") || !strncmp(name, "stats_slot_", 11)) {
         // conservation check of the radix path: k-mers gathered by pass 2 / probed by pass 3 since the last
         // kmm_get_stats(reset): both must equal the lookups pass 1 emitted
@@ -4130,8 +4192,10 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         HIPCHK(hipMemcpy(st.data(), ix->stats, KMM_STAT_BYTES, hipMemcpyDeviceToHost));
         // ("stats_slot_<n>": raw counter n of the statistics block; slots 4.. are only written by diagnostic builds)
         // ("quality_masked_bases": FASTQ bases whose quality byte was below "min_base_quality", since the same reset)
+        // ("records_without_qual": SAM / BAM records with bases and no qualities that were mapped with a floor, since the same reset)
         // ("debug_p3_key_reads": 8-byte key reads of pass 3's probes; counted by -DRX_P3_FP_STATS builds only, else 0)
         const int slot = name[0] == 's' ? atoi(name + 11) : name[0] == 'q' ? KMM_STAT_QUAL_MASKED
+                                                          : !strcmp(name, "records_without_qual") ? KMM_STAT_REC_NO_QUAL
                                                           : name[0] == 'd' ? KMM_STAT_RX_P3_KEYS
                                                           : !strcmp(name, "radix_p2_dropped") ? KMM_STAT_RX_DROPPED
                                                           : !strcmp(name, "radix_p2_multi_round_items") ? KMM_STAT_RX_MULTI

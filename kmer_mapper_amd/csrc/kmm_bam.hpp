@@ -18,6 +18,9 @@
 //               "\n": the 4-bit codes =ACMGRSVTWYHKDBN as letters), 64 lanes over a record's bases.  The library maps that with
 //               kmm_map_records: the LUT, the invalid-base rule, the radix / direct choice and the uniform-length path are
 //               the ones every other input takes.
+// The quality variant (<true> / k_bam_*_q; "use_record_qual" with a floor) writes every kept record as four-line
+// FASTQ instead ("@\n" SEQ "\n+\n" QUAL "\n", the raw Phred bytes as Phred+33 clipped at '~'): 2 l_seq + 6 bytes per record, which
+// the library maps as KMM_FORMAT_FASTQ, where "min_base_quality" is applied.
 // Exactness never depends on the plausibility test: a wrong guess only costs a fix.  Every read is bounds-checked against n.
 #pragma once
 
@@ -118,8 +121,23 @@ struct Walk {
     bool bad;
 };
 
+// Output bytes of one kept record: two-line FASTA, or (Q) four-line FASTQ.
+template <bool Q>
+KMM_BAM_HD uint32_t out_len(uint32_t l_seq)
+{
+    return Q ? 2u * l_seq + 6u : l_seq + 3u;
+}
+
+// Walk::bytes and Tile::bytes are uint32.  The records that start in one tile, all but the last, end before the next one starts,
+// i.e. inside the tile: their 4 + block_size sum to less than TILE, there are at most TILE / 36 of them (block_size >= 32), and
+// l_seq + (l_seq + 1) / 2 <= block_size bounds every l_seq by 2/3 block_size.  The last one has block_size < 2^31.  So a tile's
+// quality output is below 2 * (2/3) * (TILE + 2^31) + 6 * (TILE / 36 + 1) (the FASTA output is smaller still):
+constexpr uint64_t MAX_TILE_OUT = 4ull * ((uint64_t)TILE + 0x80000000ull) / 3 + 6ull * (TILE / 36 + 1);
+static_assert(MAX_TILE_OUT < 0x100000000ull, "a tile's output bytes fit uint32");
+
 // The chain from p (a record start) to the first start at or past te; it stops early at a record that does not end inside
 // d[0, n) (exit = its start) or at a malformed one (bad, exit = its start).
+template <bool Q = false>
 KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int32_t n_ref, uint32_t excl, Walk &w)
 {
     w.recs = w.excluded = w.bytes = 0;
@@ -137,7 +155,7 @@ KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int3
             ++w.excluded;
         else {
             ++w.recs;
-            w.bytes += h.l_seq + 3u;
+            w.bytes += out_len<Q>(h.l_seq);
         }
         p += 4ull + h.bs;
     }
@@ -147,6 +165,7 @@ KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int3
 KMM_BAM_HD uint64_t tile_end(uint64_t t, uint64_t n) { return (t + 1) * TILE < n ? (t + 1) * TILE : n; }
 
 // The claim of tile t once its start is known (entry = a record start) or guessed.
+template <bool Q = false>
 KMM_BAM_HD void claim_from(const uint8_t *d, uint64_t n, uint64_t t, uint64_t entry, int32_t n_ref, uint32_t excl, uint32_t spec,
                            Tile &o)
 {
@@ -157,7 +176,7 @@ KMM_BAM_HD void claim_from(const uint8_t *d, uint64_t n, uint64_t t, uint64_t en
         return;
     }
     Walk w;
-    walk(d, n, entry, tile_end(t, n), n_ref, excl, w);
+    walk<Q>(d, n, entry, tile_end(t, n), n_ref, excl, w);
     o.entry = w.bad ? INVALID : entry;
     o.exit = w.bad ? INVALID : w.exit;
     o.recs = w.recs;
@@ -190,6 +209,7 @@ KMM_BAM_HD bool agrees(const uint8_t *d, uint64_t n, uint64_t t, const Tile &c, 
 // ---- the per-tile steps, shared by the kernels and the CPU backend ----
 
 // spec, one tile (scalar form: the kernel tests 64 positions at a time, with the same `plausible`)
+template <bool Q = false>
 inline void spec_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, uint64_t start0, int32_t n_ref, uint32_t excl, Tile &o)
 {
     uint64_t entry = NONE;
@@ -199,16 +219,17 @@ inline void spec_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, uint64_t 
         for (uint64_t c = t * TILE, e = tile_end(t, n); c < e && entry == NONE; ++c)
             if (plausible(d, n, c, n_ref))
                 entry = c;
-    claim_from(d, n, t, entry, n_ref, excl, 1u, o);
+    claim_from<Q>(d, n, t, entry, n_ref, excl, 1u, o);
 }
 
 // fix, one tile: its claim is walked again from the exit before it.  verified: that exit is exact (t is the first tile
 // that disagrees), so a malformed record met on the way is an error of the file (returns its position, else NONE).
+template <bool Q = false>
 KMM_BAM_HD uint64_t fix_tile(const uint8_t *d, uint64_t n, uint64_t t, uint64_t prev, bool verified, int32_t n_ref, uint32_t excl,
                              Tile &o)
 {
     Walk w;
-    walk(d, n, prev, tile_end(t, n), n_ref, excl, w);
+    walk<Q>(d, n, prev, tile_end(t, n), n_ref, excl, w);
     o.spec = 0;
     o.recs = w.recs;
     o.excluded = w.excluded;
@@ -243,6 +264,40 @@ KMM_BAM_HD void decode_record(const uint8_t *rec, const RecHead &h, uint8_t *out
         out[2 + 2 * j] = base_letter(b >> 4);
         if (2 * j + 1 < h.l_seq)
             out[3 + 2 * j] = base_letter(b);
+    }
+}
+
+// The quality bytes of a record (l_seq raw Phred values behind the packed bases; inside block_size: record_at)
+KMM_BAM_HD const uint8_t *qual_of(const uint8_t *rec, const RecHead &h) { return rec + seq_offset(h) + (h.l_seq + 1u) / 2u; }
+
+// Are the record's qualities absent?  (0xFF bytes; as htslib, the first one decides.)  A record without bases has none to miss.
+KMM_BAM_HD bool qual_absent(const uint8_t *rec, const RecHead &h) { return h.l_seq > 0 && qual_of(rec, h)[0] == 0xFFu; }
+
+// A raw Phred byte as Phred+33 text, clipped at '~': 0xFF (absent) and every byte >= 93 become '~', which no floor <= 93 masks.
+KMM_BAM_HD uint8_t qual_letter(uint32_t q) { return (uint8_t)(q >= 93u ? 126u : q + 33u); }
+
+// decode, the quality variant: "@\n" + letters + "\n+\n" + qualities + "\n" at out[0] (2 l_seq + 6 bytes)
+KMM_BAM_HD void decode_record_q(const uint8_t *rec, const RecHead &h, uint8_t *out, uint32_t lane, uint32_t lanes)
+{
+    const uint8_t *seq = rec + seq_offset(h), *qual = qual_of(rec, h);
+    const uint32_t n_bytes = (h.l_seq + 1u) / 2u;
+    uint8_t *oq = out + 5ull + h.l_seq;
+    if (lane == 0) {
+        out[0] = '@';
+        out[1] = '\n';
+        out[2ull + h.l_seq] = '\n';
+        out[3ull + h.l_seq] = '+';
+        out[4ull + h.l_seq] = '\n';
+        oq[h.l_seq] = '\n';
+    }
+    for (uint32_t j = lane; j < n_bytes; j += lanes) {
+        const uint32_t b = seq[j];
+        out[2ull + 2ull * j] = base_letter(b >> 4);
+        oq[2ull * j] = qual_letter(qual[2ull * j]);
+        if (2 * j + 1 < h.l_seq) {
+            out[3ull + 2ull * j] = base_letter(b);
+            oq[2ull * j + 1] = qual_letter(qual[2ull * j + 1]);
+        }
     }
 }
 
@@ -336,6 +391,8 @@ struct CpuBackend {
     uint64_t n = 0;
     int32_t n_ref = 0;
     uint32_t excl = 0;
+    bool qual = false;     // the quality variant: decode() writes four-line FASTQ
+    uint64_t no_qual = 0;  // kept records whose qualities are absent (counted by decode() of the quality variant)
     std::vector<Tile> cur, nxt;
     std::vector<uint64_t> base;
     uint64_t false_starts = 0;
@@ -347,7 +404,10 @@ struct CpuBackend {
         false_starts = 0;
         first_bad = err_pos = NONE;
         for (uint64_t t = 0; t < n_tiles; ++t)
-            spec_tile_scalar(d, n, t, start0, n_ref, excl, cur[t]);
+            if (qual)
+                spec_tile_scalar<true>(d, n, t, start0, n_ref, excl, cur[t]);
+            else
+                spec_tile_scalar(d, n, t, start0, n_ref, excl, cur[t]);
         return 0;
     }
     uint64_t first_bad = NONE, err_pos = NONE;
@@ -376,7 +436,8 @@ struct CpuBackend {
             }
             if (cur[t].spec && cur[t].entry != NONE)
                 ++false_starts;
-            const uint64_t e = fix_tile(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t]);
+            const uint64_t e = qual ? fix_tile<true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t])
+                                    : fix_tile(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t]);
             if (e != NONE && (err_pos == NONE || e < err_pos))
                 err_pos = e;
         }
@@ -407,7 +468,11 @@ struct CpuBackend {
                 RecHead h;
                 if (record_at(d, n, p, n_ref, h) != REC_OK)
                     break;
-                if (!(h.flag & excl)) {
+                if (!(h.flag & excl) && qual) {
+                    decode_record_q(d + p, h, out + o, 0, 1);
+                    o += 2ull * h.l_seq + 6ull;
+                    no_qual += qual_absent(d + p, h) ? 1u : 0u;
+                } else if (!(h.flag & excl)) {
                     decode_record(d + p, h, out + o, 0, 1);
                     o += h.l_seq + 3ull;
                 }
@@ -420,8 +485,9 @@ struct CpuBackend {
 #if defined(__HIPCC__)
 // spec: one wavefront per tile (grid-stride); lanes test 64 consecutive positions, the lowest plausible one is the start;
 // lane 0 walks the chain from it.
-__global__ void __launch_bounds__(256) k_bam_spec(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
-                                                  int32_t n_ref, uint32_t excl, Tile *__restrict__ out)
+template <bool Q>
+__device__ __forceinline__ void bam_spec_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                               int32_t n_ref, uint32_t excl, Tile *__restrict__ out)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
@@ -439,7 +505,7 @@ __global__ void __launch_bounds__(256) k_bam_spec(const uint8_t *__restrict__ d,
         if (lane == 0) {
             Walk w;
             if (entry != NONE)
-                walk(d, n, entry, tile_end(t, n), n_ref, excl, w);
+                walk<Q>(d, n, entry, tile_end(t, n), n_ref, excl, w);
             const bool none = entry == NONE, bad = !none && w.bad;
             out[t].entry = bad ? INVALID : entry;
             out[t].exit = none ? NONE : bad ? INVALID : w.exit;
@@ -449,6 +515,17 @@ __global__ void __launch_bounds__(256) k_bam_spec(const uint8_t *__restrict__ d,
             out[t].spec = 1u;
         }
     }
+}
+
+__global__ void __launch_bounds__(256) k_bam_spec(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                  int32_t n_ref, uint32_t excl, Tile *__restrict__ out)
+{
+    bam_spec_tiles<false>(d, n, n_tiles, start0, n_ref, excl, out);
+}
+__global__ void __launch_bounds__(256) k_bam_spec_q(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                    int32_t n_ref, uint32_t excl, Tile *__restrict__ out)
+{
+    bam_spec_tiles<true>(d, n, n_tiles, start0, n_ref, excl, out);
 }
 
 // check: one lane per tile; bad[t] = its claim disagrees with the exit before it
@@ -467,9 +544,10 @@ __global__ void __launch_bounds__(256) k_bam_check(const uint8_t *__restrict__ d
 }
 
 // fix: one lane per tile; claims that agree are copied, the others walked again from the exit before them
-__global__ void __launch_bounds__(256) k_bam_fix(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
-                                                 int32_t n_ref, uint32_t excl, const Tile *__restrict__ in, const uint8_t *__restrict__ bad,
-                                                 Tile *__restrict__ out, Ctl *__restrict__ ctl)
+template <bool Q>
+__device__ __forceinline__ void bam_fix_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                              int32_t n_ref, uint32_t excl, const Tile *__restrict__ in, const uint8_t *__restrict__ bad,
+                                              Tile *__restrict__ out, Ctl *__restrict__ ctl)
 {
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tiles; t += (uint64_t)gridDim.x * blockDim.x) {
         const Tile c = in[t];
@@ -480,11 +558,24 @@ __global__ void __launch_bounds__(256) k_bam_fix(const uint8_t *__restrict__ d, 
         if (c.spec && c.entry != NONE)
             atomicAdd(&ctl->false_starts, 1ull);
         Tile o;
-        const uint64_t e = fix_tile(d, n, t, prev_exit(in, t, start0), t == ctl->first_bad, n_ref, excl, o);
+        const uint64_t e = fix_tile<Q>(d, n, t, prev_exit(in, t, start0), t == ctl->first_bad, n_ref, excl, o);
         out[t] = o;
         if (e != NONE)
             atomicMin(&ctl->err_pos, (unsigned long long)e);
     }
+}
+
+__global__ void __launch_bounds__(256) k_bam_fix(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                 int32_t n_ref, uint32_t excl, const Tile *__restrict__ in, const uint8_t *__restrict__ bad,
+                                                 Tile *__restrict__ out, Ctl *__restrict__ ctl)
+{
+    bam_fix_tiles<false>(d, n, n_tiles, start0, n_ref, excl, in, bad, out, ctl);
+}
+__global__ void __launch_bounds__(256) k_bam_fix_q(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                   int32_t n_ref, uint32_t excl, const Tile *__restrict__ in,
+                                                   const uint8_t *__restrict__ bad, Tile *__restrict__ out, Ctl *__restrict__ ctl)
+{
+    bam_fix_tiles<true>(d, n, n_tiles, start0, n_ref, excl, in, bad, out, ctl);
 }
 
 // totals: one workgroup of 1024 threads, each over a run of consecutive tiles: the exclusive scan of the tiles' output bytes
@@ -563,6 +654,37 @@ __global__ void __launch_bounds__(256) k_bam_decode(const uint8_t *__restrict__ 
             }
             p += 4ull + h.bs;
         }
+    }
+}
+
+// decode, the quality variant: the same walk, four-line FASTQ per kept record; the kept records whose qualities are absent are
+// counted per tile and added to *no_qual (one atomic per tile that has any).
+__global__ void __launch_bounds__(256) k_bam_decode_q(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                      uint32_t excl, const Tile *__restrict__ in,
+                                                      const unsigned long long *__restrict__ base, uint8_t *__restrict__ out,
+                                                      unsigned long long *__restrict__ no_qual)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        const Tile c = in[t];
+        if (c.entry == NONE || c.recs == 0)
+            continue;
+        uint64_t p = c.entry, o = base[t];
+        uint32_t absent = 0;
+        while (p < c.exit) {
+            RecHead h;
+            if (record_at(d, n, p, n_ref, h) != REC_OK) // (cannot happen on a verified chain; bounds all the same)
+                break;
+            if (!(h.flag & excl)) {
+                decode_record_q(d + p, h, out + o, lane, 64u);
+                o += 2ull * h.l_seq + 6ull;
+                absent += qual_absent(d + p, h) ? 1u : 0u;
+            }
+            p += 4ull + h.bs;
+        }
+        if (lane == 0 && absent)
+            atomicAdd(no_qual, (unsigned long long)absent);
     }
 }
 #endif

@@ -14,6 +14,9 @@
 //   3. write   the same walk again, every kept record written as ">\n" SEQ "\n" (SEQ "*": an empty line), 64 lanes per SEQ.
 // kmm_map_records then maps that text as two-line FASTA: the LUT, the invalid-base rule and the radix / direct choice are the
 // ones every other input takes.  Every read is bounds-checked against n.
+// The quality variant (<true> / k_sam_*_q; "use_record_qual" with a floor) also finds TAB 11, checks that QUAL is
+// "*" or as long as SEQ, and writes every kept record as four-line FASTQ ("@\n" SEQ "\n+\n" QUAL "\n"; QUAL "*": '~' per base),
+// 2 |SEQ| + 6 bytes per record, which the library maps as KMM_FORMAT_FASTQ, where "min_base_quality" is applied.
 #pragma once
 
 #include <cstdint>
@@ -31,11 +34,14 @@ namespace kmm_sam {
 constexpr uint64_t NONE = ~0ull;
 constexpr uint32_t TILE = 1024;       // bytes per tile (the lines that start in it are its own)
 constexpr uint32_t WIN = 1024;        // bytes one wavefront reads per step of a line: 64 lanes x 16 bytes
-enum Err : uint32_t { ERR_FIELDS = 1, ERR_FLAG = 2, ERR_EMPTY = 3 }; // an error word = line start << 2 | code
+enum Err : uint32_t { ERR_QUAL = 0, ERR_FIELDS = 1, ERR_FLAG = 2, ERR_EMPTY = 3 }; // an error word = line start << 2 | code
+// (ERR_QUAL: the quality variant only — QUAL is not "*" and not as long as SEQ)
 enum Kind : uint32_t { K_KEPT = 0, K_EXCLUDED = 1, K_HEADER = 2, K_BAD = 3 };
 
 // One tile's lines: records kept / excluded, header lines, output bytes, the end of its last complete line (0: none), the
-// first malformed line (NONE: none).
+// first malformed line (NONE: none).  bytes is uint32: a piece holds at most 2^30 bytes, the SEQs of the lines that start in one
+// tile lie in it one behind the other, and at most TILE lines start there: at most 2 * 2^30 + 6 * TILE output bytes, four-line
+// FASTQ included.
 struct Tile {
     uint32_t recs, excluded, headers, bytes;
     uint64_t last_end, err;
@@ -45,16 +51,24 @@ struct Totals {
     unsigned long long recs, excluded, headers, out_bytes, consumed, err;
 };
 
-// Where a line's fields lie: its newline (NONE: no newline before n), TABs 1, 2, 9 and 10 (NONE: the line has fewer)
-struct Line {
+// Where a line's fields lie: its newline (NONE: no newline before n), TABs 1, 2, 9 and 10 (NONE: the line has fewer); the
+// quality variant (NT = 5) also looks for TAB 11, behind QUAL
+template <int NT>
+struct LineT {
     uint64_t end;
-    uint64_t tab[4];
+    uint64_t tab[NT];
 };
-KMM_SAM_HD uint32_t want_tab(int w) { return w < 2 ? (uint32_t)w + 1u : (uint32_t)w + 7u; } // 1, 2, 9, 10
+typedef LineT<4> Line;
+typedef LineT<5> LineQ;
+KMM_SAM_HD uint32_t want_tab(int w) { return w < 2 ? (uint32_t)w + 1u : (uint32_t)w + 7u; } // 1, 2, 9, 10, 11
 
 struct LineInfo {
     uint32_t kind, err;
     uint64_t seq, seq_len; // SEQ of a record ("*": length 0)
+};
+struct LineInfoQ : LineInfo {
+    uint64_t qual; // QUAL of a record: seq_len bytes at d[qual], or
+    bool absent;   // "*": the record stores no qualities
 };
 
 // TAB / newline masks of one lane's 16 bytes d[a + 16 lane, +16), restricted to [s, n).  d + a is 16-byte aligned; on the
@@ -150,6 +164,60 @@ KMM_SAM_HD void classify(const uint8_t *d, uint64_t s, const Line &L, uint32_t e
     o.kind = (flag & excl) ? K_EXCLUDED : K_KEPT;
 }
 
+// The quality variant: what the line is, and its QUAL — the bytes between TAB 10 and TAB 11 (or the line's end, without a CR in
+// front of the newline).  A QUAL that is exactly "*" is absent, for a one-base read too (as htslib reads it); any other QUAL has
+// to be as long as SEQ.
+KMM_SAM_HD void classify(const uint8_t *d, uint64_t s, const LineQ &L, uint32_t excl, LineInfoQ &o)
+{
+    Line l4;
+    l4.end = L.end;
+    for (int w = 0; w < 4; ++w)
+        l4.tab[w] = L.tab[w];
+    classify(d, s, l4, excl, o);
+    o.qual = 0;
+    o.absent = false;
+    if (o.kind != K_KEPT && o.kind != K_EXCLUDED)
+        return;
+    const uint64_t qs = L.tab[3] + 1;
+    uint64_t qe = L.tab[4];
+    if (qe == NONE) {
+        qe = L.end;
+        if (qe > qs && d[qe - 1] == 13u)
+            --qe;
+    }
+    o.qual = qs;
+    o.absent = qe - qs == 1 && d[qs] == (uint8_t)'*';
+    if (!o.absent && qe - qs != o.seq_len) {
+        o.kind = K_BAD;
+        o.err = ERR_QUAL;
+    }
+}
+
+template <bool Q>
+KMM_SAM_HD uint32_t out_len(uint64_t seq_len)
+{
+    return Q ? 2u * (uint32_t)seq_len + 6u : (uint32_t)seq_len + 3u;
+}
+
+// The quality variant of emit: "@\n" + SEQ + "\n+\n" + QUAL + "\n" at out[0]; an absent QUAL is written as '~' per base, which no
+// floor masks
+KMM_SAM_HD void emit(const uint8_t *d, const LineInfoQ &li, uint8_t *out, uint32_t lane, uint32_t lanes)
+{
+    uint8_t *oq = out + 5 + li.seq_len;
+    if (lane == 0) {
+        out[0] = '@';
+        out[1] = '\n';
+        out[2 + li.seq_len] = '\n';
+        out[3 + li.seq_len] = '+';
+        out[4 + li.seq_len] = '\n';
+        oq[li.seq_len] = '\n';
+    }
+    for (uint64_t j = lane; j < li.seq_len; j += lanes) {
+        out[2 + j] = d[li.seq + j];
+        oq[j] = li.absent ? (uint8_t)'~' : d[li.qual + j];
+    }
+}
+
 // One kept record's output (lane `lane` of `lanes`): ">\n" + SEQ + "\n" at out[0]
 KMM_SAM_HD void emit(const uint8_t *d, const LineInfo &li, uint8_t *out, uint32_t lane, uint32_t lanes)
 {
@@ -165,10 +233,11 @@ KMM_SAM_HD void emit(const uint8_t *d, const LineInfo &li, uint8_t *out, uint32_
 // The line that starts at s, scanned window by window as the wavefront does, one lane after the other (the CPU form of
 // scan_line_wave below: the same masks, the same prefix over the lanes).  tabs: false = the newline only; windows that start
 // at or past `stop` are not read (L.end NONE).
-inline void scan_line_lanes(const uint8_t *d, uint64_t n, uint64_t s, bool tabs, uint64_t stop, Line &L)
+template <int NT>
+inline void scan_line_lanes(const uint8_t *d, uint64_t n, uint64_t s, bool tabs, uint64_t stop, LineT<NT> &L)
 {
     L.end = NONE;
-    for (int w = 0; w < 4; ++w)
+    for (int w = 0; w < NT; ++w)
         L.tab[w] = NONE;
     uint32_t seen = 0; // TABs of the line before the window
     for (int64_t a = first_window(d, s); a < (int64_t)n && a < (int64_t)stop; a += WIN) {
@@ -178,7 +247,7 @@ inline void scan_line_lanes(const uint8_t *d, uint64_t n, uint64_t s, bool tabs,
             if (nm)
                 tm &= (nm & (0u - nm)) - 1u; // (TABs behind the newline are another line's)
             const uint32_t cnt = tabs ? (uint32_t)__builtin_popcount(tm) : 0u;
-            for (int w = 0; w < 4 && tabs; ++w) {
+            for (int w = 0; w < NT && tabs; ++w) {
                 const uint32_t k = want_tab(w);
                 if (L.tab[w] == NONE && seen < k && k <= seen + cnt)
                     L.tab[w] = (uint64_t)(a + 16 * (int64_t)lane + nth_bit(tm, k - seen));
@@ -192,13 +261,22 @@ inline void scan_line_lanes(const uint8_t *d, uint64_t n, uint64_t s, bool tabs,
     }
 }
 
+template <bool Q>
+struct InfoOf {
+    typedef LineInfo type;
+};
+template <>
+struct InfoOf<true> {
+    typedef LineInfoQ type;
+};
+
 KMM_SAM_HD uint64_t tile_end(uint64_t t, uint64_t n) { return (t + 1) * TILE < n ? (t + 1) * TILE : n; }
 
 // The walk over tile t's lines, written once against a scanner (scan(s, tabs, stop, Line &)) and a sink for the kept records
 // (sink(LineInfo, offset of its output inside the tile's)).  The tile's first line starts at its first byte when the byte
 // before is a newline (or the tile is the first), else behind the first newline inside the tile — looked for inside the tile
 // only, so that a long line costs its own tiles one window each.
-template <class Scan, class Sink>
+template <bool Q = false, class Scan, class Sink>
 KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t excl, Scan &scan, Sink &sink, Tile &o)
 {
     o.recs = o.excluded = o.headers = o.bytes = 0;
@@ -206,7 +284,7 @@ KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t exc
     o.err = NONE;
     const uint64_t ts = t * TILE, te = tile_end(t, n);
     uint64_t s = ts;
-    Line L;
+    LineT<Q ? 5 : 4> L;
     if (ts > 0 && d[ts - 1] != 10u) {
         scan(ts, false, te, L); // (the line in progress at the tile's start belongs to a tile before)
         if (L.end == NONE)
@@ -217,7 +295,7 @@ KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t exc
         scan(s, true, n, L);
         if (L.end == NONE)
             return; // (no newline before the chunk ends: the line waits for the next call)
-        LineInfo li;
+        typename InfoOf<Q>::type li;
         classify(d, s, L, excl, li);
         if (li.kind == K_BAD) {
             o.err = s << 2 | li.err;
@@ -230,7 +308,7 @@ KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t exc
         else {
             sink(li, o.bytes);
             ++o.recs;
-            o.bytes += (uint32_t)li.seq_len + 3u;
+            o.bytes += out_len<Q>(li.seq_len);
         }
         o.last_end = L.end + 1;
         s = L.end + 1;
@@ -241,20 +319,34 @@ KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t exc
 struct CpuScan {
     const uint8_t *d;
     uint64_t n;
-    void operator()(uint64_t s, bool tabs, uint64_t stop, Line &L) { scan_line_lanes(d, n, s, tabs, stop, L); }
+    template <int NT>
+    void operator()(uint64_t s, bool tabs, uint64_t stop, LineT<NT> &L)
+    {
+        scan_line_lanes(d, n, s, tabs, stop, L);
+    }
 };
 struct CpuSink {
     const uint8_t *d;
     uint8_t *out; // null: the count pass
+    uint64_t no_qual = 0; // (the quality variant) kept records with bases whose QUAL is absent
     void operator()(const LineInfo &li, uint32_t at)
     {
         if (out)
             emit(d, li, out + at, 0, 1);
     }
+    void operator()(const LineInfoQ &li, uint32_t at)
+    {
+        if (out) {
+            emit(d, li, out + at, 0, 1);
+            no_qual += li.absent && li.seq_len > 0 ? 1u : 0u;
+        }
+    }
 };
 
 // One chunk on the CPU: the count pass, the totals, the write pass (out: at least tot.out_bytes; null = count only).
-inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out, Totals &tot)
+// Q: the quality variant (four-line FASTQ out; *no_qual: the kept records whose QUAL is absent, counted by the write pass).
+template <bool Q = false>
+inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out, Totals &tot, uint64_t *no_qual = nullptr)
 {
     tot = Totals{0, 0, 0, 0, 0, NONE};
     const uint64_t n_tiles = (n + TILE - 1) / TILE;
@@ -263,7 +355,7 @@ inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out,
     CpuSink count{d, nullptr};
     for (uint64_t t = 0; t < n_tiles; ++t) {
         Tile o;
-        walk_tile(d, n, t, excl, sc, count, o);
+        walk_tile<Q>(d, n, t, excl, sc, count, o);
         base[t] = tot.out_bytes;
         tot.recs += o.recs;
         tot.excluded += o.excluded;
@@ -279,19 +371,23 @@ inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out,
     for (uint64_t t = 0; t < n_tiles; ++t) {
         CpuSink write{d, out + base[t]};
         Tile o;
-        walk_tile(d, n, t, excl, sc, write, o);
+        walk_tile<Q>(d, n, t, excl, sc, write, o);
+        if (no_qual)
+            *no_qual += write.no_qual;
     }
 }
 
 #if defined(__HIPCC__)
 // The line that starts at s, one wavefront: 64 lanes x 16 bytes per window; the newline is the first lane (ballot) with one,
 // TAB k lies in the lane whose prefix of TAB counts passes k.  Wave-uniform result.
-__device__ __forceinline__ void scan_line_wave(const uint8_t *__restrict__ d, uint64_t n, uint64_t s, bool tabs, uint64_t stop, Line &L)
+template <int NT>
+__device__ __forceinline__ void scan_line_wave(const uint8_t *__restrict__ d, uint64_t n, uint64_t s, bool tabs, uint64_t stop,
+                                               LineT<NT> &L)
 {
     const uint32_t lane = threadIdx.x & 63u;
     L.end = NONE;
 #pragma unroll
-    for (int w = 0; w < 4; ++w)
+    for (int w = 0; w < NT; ++w)
         L.tab[w] = NONE;
     uint32_t seen = 0;
     for (int64_t a = first_window(d, s); a < (int64_t)n && a < (int64_t)stop; a += WIN) {
@@ -303,7 +399,7 @@ __device__ __forceinline__ void scan_line_wave(const uint8_t *__restrict__ d, ui
             tm &= (nm & (0u - nm)) - 1u;
         else if (lane > cut)
             tm = 0;
-        if (tabs && L.tab[3] == NONE) {
+        if (tabs && L.tab[NT - 1] == NONE) {
             const uint32_t cnt = (uint32_t)__popc(tm);
             uint32_t incl = cnt;
 #pragma unroll
@@ -314,7 +410,7 @@ __device__ __forceinline__ void scan_line_wave(const uint8_t *__restrict__ d, ui
             }
             const uint32_t before = seen + incl - cnt;
 #pragma unroll
-            for (int w = 0; w < 4; ++w) {
+            for (int w = 0; w < NT; ++w) {
                 const uint32_t k = want_tab(w);
                 const bool mine = L.tab[w] == NONE && before < k && k <= before + cnt;
                 const unsigned long long m = __ballot(mine);
@@ -337,7 +433,11 @@ __device__ __forceinline__ void scan_line_wave(const uint8_t *__restrict__ d, ui
 struct WaveScan {
     const uint8_t *d;
     uint64_t n;
-    __device__ void operator()(uint64_t s, bool tabs, uint64_t stop, Line &L) { scan_line_wave(d, n, s, tabs, stop, L); }
+    template <int NT>
+    __device__ void operator()(uint64_t s, bool tabs, uint64_t stop, LineT<NT> &L)
+    {
+        scan_line_wave(d, n, s, tabs, stop, L);
+    }
 };
 struct NoSink {
     __device__ void operator()(const LineInfo &, uint32_t) {}
@@ -346,6 +446,16 @@ struct WaveSink {
     const uint8_t *d;
     uint8_t *out;
     __device__ void operator()(const LineInfo &li, uint32_t at) { emit(d, li, out + at, threadIdx.x & 63u, 64u); }
+};
+struct WaveSinkQ {
+    const uint8_t *d;
+    uint8_t *out;
+    uint32_t no_qual; // kept records with bases whose QUAL is absent (wave-uniform)
+    __device__ void operator()(const LineInfoQ &li, uint32_t at)
+    {
+        emit(d, li, out + at, threadIdx.x & 63u, 64u);
+        no_qual += li.absent && li.seq_len > 0 ? 1u : 0u;
+    }
 };
 
 // count: one wavefront per tile (grid-stride)
@@ -358,6 +468,21 @@ __global__ void __launch_bounds__(256) k_sam_count(const uint8_t *__restrict__ d
     for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
         Tile o;
         walk_tile(d, n, t, excl, sc, none, o);
+        if ((threadIdx.x & 63u) == 0)
+            tiles[t] = o;
+    }
+}
+
+// count, the quality variant (TAB 11 found, QUAL checked against SEQ, four-line FASTQ lengths)
+__global__ void __launch_bounds__(256) k_sam_count_q(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint32_t excl,
+                                                     Tile *__restrict__ tiles)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    WaveScan sc{d, n};
+    NoSink none;
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        Tile o;
+        walk_tile<true>(d, n, t, excl, sc, none, o);
         if ((threadIdx.x & 63u) == 0)
             tiles[t] = o;
     }
@@ -437,6 +562,25 @@ __global__ void __launch_bounds__(256) k_sam_write(const uint8_t *__restrict__ d
         WaveSink sink{d, out + base[t]};
         Tile o;
         walk_tile(d, n, t, excl, sc, sink, o);
+    }
+}
+
+// write, the quality variant: four-line FASTQ per kept record; the kept records whose QUAL is absent are counted per tile and
+// added to *no_qual (one atomic per tile that has any)
+__global__ void __launch_bounds__(256) k_sam_write_q(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint32_t excl,
+                                                     const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                     uint8_t *__restrict__ out, unsigned long long *__restrict__ no_qual)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    WaveScan sc{d, n};
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        if (tiles[t].recs == 0)
+            continue;
+        WaveSinkQ sink{d, out + base[t], 0u};
+        Tile o;
+        walk_tile<true>(d, n, t, excl, sc, sink, o);
+        if ((threadIdx.x & 63u) == 0 && sink.no_qual)
+            atomicAdd(no_qual, (unsigned long long)sink.no_qual);
     }
 }
 #endif

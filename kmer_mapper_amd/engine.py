@@ -223,7 +223,8 @@ class DeviceIndex:
         Returns (consumed_bytes, n_records); the caller carries raw[consumed:] to the next chunk.
         A base-quality floor is a parameter of the handle: set_param("min_base_quality", Q) makes every FASTQ base whose
         quality byte is below '!' + Q a break, on this call and on map_bgzf / map_gzip (no effect on FASTA; SAM and map_bam
-        are refused while it is set), and get_param("quality_masked_bases") counts the bases it masked since the last
+        are refused while it is set, unless set_param("use_record_qual", 1) has their QUAL decoded beside SEQ:
+        get_param("records_without_qual") then counts the records that store none and passed unmasked), and get_param("quality_masked_bases") counts the bases it masked since the last
         get_stats(reset=True).  Reads already held as arrays bring their quality bytes to map_reads / map_reads_uniform
         (qualities=...), which apply the same floor."""
         b = _Arg(raw, np.uint8, "raw")

@@ -274,38 +274,60 @@ def bgzf_members(data, block=0xFF00, level=6):
 BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
-def write_bam(path, batch, names=None, flags=None, refs=(), text=b"@HD\tVN:1.6\tSO:unsorted\n", level=6, block=0xFF00):
-    """Write the reads of `batch` as an unaligned BAM file (for tools and tests): every read one record (name r<i> unless
-    `names`, FLAG 4 unless `flags`, quality 'I').  The header goes in members of its own, the records in members of at most
-    `block` inflated bytes, and the file ends with the empty EOF member, as htslib writes it."""
+def _read_quals(quals, i, n, default):
+    """Read i's quality bytes from `quals` (None: `default` per base; an entry None: the read stores none -> None)."""
+    if quals is None:
+        return default * n
+    if quals[i] is None:
+        return None
+    q = bytes(quals[i])
+    if len(q) != n:
+        raise ValueError("read %d has %d bases and %d quality bytes" % (i, n, len(q)))
+    return q
+
+
+def bam_records(batch, names=None, flags=None, quals=None):
+    """The reads of `batch` as BAM records, one behind the other (bam_record; quals: see write_bam)."""
     recs = []
     for i in range(len(batch)):
         seq = batch.bases[batch.offsets[i]:batch.offsets[i + 1]].tobytes()
         recs.append(bam_record(seq, names[i] if names is not None else b"r%d" % i, int(flags[i]) if flags is not None else 4,
-                               qual=b"\x28" * len(seq)))
+                               qual=_read_quals(quals, i, len(seq), b"\x28")))
+    return b"".join(recs)
+
+
+def write_bam(path, batch, names=None, flags=None, refs=(), text=b"@HD\tVN:1.6\tSO:unsorted\n", level=6, block=0xFF00,
+              quals=None):
+    """Write the reads of `batch` as an unaligned BAM file (for tools and tests): every read one record (name r<i> unless
+    `names`, FLAG 4 unless `flags`, quality 'I' unless `quals`: per read its raw Phred bytes, or None = absent, 0xFF bytes).
+    The header goes in members of its own, the records in members of at most `block` inflated bytes, and the file ends with
+    the empty EOF member, as htslib writes it."""
+    records = bam_records(batch, names, flags, quals)
     with open(path, "wb") as f:
         f.write(bgzf_members(bam_header(refs, text), block, level))
-        f.write(bgzf_members(b"".join(recs), block, level))
+        f.write(bgzf_members(records, block, level))
         f.write(BGZF_EOF)
 
 
-def sam_text(batch, names=None, flags=None, header=b"@HD\tVN:1.6\tSO:unsorted\n"):
+def sam_text(batch, names=None, flags=None, header=b"@HD\tVN:1.6\tSO:unsorted\n", quals=None):
     """The reads of `batch` as SAM text (SAM/BAM specification 1.4): `header` (header lines, each ending in a newline), then one
-    unaligned record per read: QNAME r<i> unless `names`, FLAG 4 unless `flags`, SEQ (an empty read: "*"), QUAL 'I'."""
+    unaligned record per read: QNAME r<i> unless `names`, FLAG 4 unless `flags`, SEQ (an empty read: "*"), QUAL 'I' unless
+    `quals`: per read its Phred+33 bytes, or None = absent ("*")."""
     out = [bytes(header)]
     for i in range(len(batch)):
         seq = batch.bases[batch.offsets[i]:batch.offsets[i + 1]].tobytes()
         name = names[i] if names is not None else b"r%d" % i
         flag = int(flags[i]) if flags is not None else 4
-        out.append(b"%s\t%d\t*\t0\t0\t*\t*\t0\t0\t%s\t%s\n" % (name, flag, seq or b"*", b"I" * len(seq) if seq else b"*"))
+        qual = _read_quals(quals, i, len(seq), b"I")
+        out.append(b"%s\t%d\t*\t0\t0\t*\t*\t0\t0\t%s\t%s\n" % (name, flag, seq or b"*", qual or b"*"))
     return b"".join(out)
 
 
 def write_sam(path, batch, names=None, flags=None, header=b"@HD\tVN:1.6\tSO:unsorted\n", bgzf=False, gz=False, level=6,
-              block=0xFF00):
+              block=0xFF00, quals=None):
     """Write the reads of `batch` as a SAM file (sam_text; for tools and tests): plain, BGZF (bgzf=True: members of at most
-    `block` inflated bytes and the EOF member, as htslib writes .sam.gz) or plain gzip (gz=True)."""
-    data = sam_text(batch, names, flags, header)
+    `block` inflated bytes and the EOF member, as htslib writes .sam.gz) or plain gzip (gz=True).  quals: see sam_text."""
+    data = sam_text(batch, names, flags, header, quals)
     with open(path, "wb") as f:
         if bgzf:
             f.write(bgzf_members(data, block, level) + BGZF_EOF)

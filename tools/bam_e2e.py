@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """`kmer_mapper map` on the same synthetic reads written once as BGZF FASTQ (.fq.gz) and once as unaligned BAM, both at zlib
 level 6 in members of 0xFF00 inflated bytes; the two CLI routes alternated in one job.
-    python tools/bam_e2e.py [n_reads=10000000] [n_index=100000000] [out_dir=/tmp/kmm_bam] [reps=3]
+    python tools/bam_e2e.py [n_reads=10000000] [n_index=100000000] [out_dir=/tmp/kmm_bam] [reps=3] [min_q=0]
 The FASTQ is tools/bgzf_e2e.py's (names SRR0000001.<i>, binned qualities); the BAM holds the same names, bases and qualities
 (Phred values, FLAG 4).  Prints per repetition the CLI's map phase on either route (its "hashing and counting" line) and the
-end-to-end time; KMM_VERBOSE=1 in the environment adds the library's per-call split.  The count vectors must be equal."""
+end-to-end time; KMM_VERBOSE=1 in the environment adds the library's per-call split.  The count vectors must be equal.
+min_q > 0 adds both routes once more with --min-base-quality min_q (the BAM with --use-record-qual), alternated with
+the floor-off runs: "<route>@Q"; their count vectors must be equal too."""
 import argparse
 import os
 import sys
@@ -58,6 +60,7 @@ def main():
     n_index = int(sys.argv[2]) if len(sys.argv) > 2 else 100_000_000
     out_dir = sys.argv[3] if len(sys.argv) > 3 else "/tmp/kmm_bam"
     reps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+    min_q = int(sys.argv[5]) if len(sys.argv) > 5 else 0
     L = 150
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
@@ -78,18 +81,20 @@ def main():
     from kmer_mapper_amd.command_line_interface import map_bnp
 
     def cli(kind):
-        ns = argparse.Namespace(kmer_index=index, index_bundle=None, reads=paths[kind], kmer_size=31, n_threads=16, chunk_size=2_500_000,
+        route, floor = kind.split("@")[0], kind.endswith("@Q")
+        ns = argparse.Namespace(kmer_index=index, index_bundle=None, reads=paths[route], kmer_size=31, n_threads=16, chunk_size=2_500_000,
                                 output_file=None, debug=None, max_hits_per_kmer=1000, gpu=True, gpu_hash_map_size=0,
                                 map_reverse_complements=False, apply_max_hits_per_kmer=False, host_parser=False, device=0,
-                                exclude_flags=0)
+                                exclude_flags=0, min_base_quality=min_q if floor else 0, use_record_qual=floor and route == "bam")
         time.sleep(4)  # (a handle just closed leaves the driver VRAM to wipe: see tools/bgzf_e2e.py)
         t = time.perf_counter()
         c = map_bnp(ns)
         return c, time.perf_counter() - t
 
-    outs, times = {}, {"fastq.gz": [], "bam": []}
+    kinds = ["fastq.gz", "bam"] + (["fastq.gz@Q", "bam@Q"] if min_q > 0 else [])
+    outs, times = {}, {k: [] for k in kinds}
     for rep in range(reps):
-        for kind in ("fastq.gz", "bam"):
+        for kind in kinds:
             c, dt = cli(kind)
             outs[kind] = c
             times[kind].append(dt)
@@ -100,6 +105,10 @@ def main():
               flush=True)
     same = np.array_equal(outs["fastq.gz"], outs["bam"])
     print("counts: BGZF FASTQ route == BAM route: %s" % same, flush=True)
+    if min_q > 0:
+        same_q = np.array_equal(outs["fastq.gz@Q"], outs["bam@Q"])
+        print("counts at Q%d: BGZF FASTQ route == BAM route: %s" % (min_q, same_q), flush=True)
+        same = same and same_q
     for p in paths.values():
         os.remove(p)
     if not same:

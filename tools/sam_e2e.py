@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """`kmer_mapper map` on the same synthetic reads written as BGZF FASTQ (.fq.gz), unaligned BAM, BGZF SAM (.sam.gz) and plain SAM
 (.sam); the four CLI routes alternated in one job.
-    python tools/sam_e2e.py [n_reads=4000000] [n_index=10000000] [out_dir=/tmp/kmm_sam] [reps=3]
+    python tools/sam_e2e.py [n_reads=4000000] [n_index=10000000] [out_dir=/tmp/kmm_sam] [reps=3] [min_q=0]
 The FASTQ is tools/bgzf_e2e.py's (names SRR0000001.<i>, binned qualities), the BAM tools/bam_e2e.py's; the SAM files hold the same
 names, bases and qualities (FLAG 4, no header but @HD), compressed files at zlib level 6 in members of 0xFF00 inflated bytes.
 Prints per repetition the CLI's map phase on every route (its "hashing and counting" line) and the end-to-end time;
-KMM_VERBOSE=1 in the environment adds the library's per-call split.  The count vectors must be equal."""
+KMM_VERBOSE=1 in the environment adds the library's per-call split.  The count vectors must be equal.
+min_q > 0 adds every route once more with --min-base-quality min_q (SAM and BAM with --use-record-qual), alternated
+with the floor-off runs: "<route>@Q".  Their count vectors must be equal too — the BGZF FASTQ at the same floor is the yardstick,
+the route the records' text hand-off ends in (KMM_E2E_QUAL=full41 draws the qualities from all 41 values)."""
 import argparse
 import os
 import sys
@@ -45,6 +48,7 @@ def main():
     n_index = int(sys.argv[2]) if len(sys.argv) > 2 else 10_000_000
     out_dir = sys.argv[3] if len(sys.argv) > 3 else "/tmp/kmm_sam"
     reps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+    min_q = int(sys.argv[5]) if len(sys.argv) > 5 else 0
     L = 150
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
@@ -69,18 +73,21 @@ def main():
     from kmer_mapper_amd.command_line_interface import map_bnp
 
     def cli(kind):
-        ns = argparse.Namespace(kmer_index=index, index_bundle=None, reads=paths[kind], kmer_size=31, n_threads=16, chunk_size=2_500_000,
+        route, floor = kind.split("@")[0], kind.endswith("@Q")
+        ns = argparse.Namespace(kmer_index=index, index_bundle=None, reads=paths[route], kmer_size=31, n_threads=16, chunk_size=2_500_000,
                                 output_file=None, debug=None, max_hits_per_kmer=1000, gpu=True, gpu_hash_map_size=0,
                                 map_reverse_complements=False, apply_max_hits_per_kmer=False, host_parser=False, device=0,
-                                exclude_flags=0)
+                                exclude_flags=0, min_base_quality=min_q if floor else 0,
+                                use_record_qual=floor and route != "fastq.gz")
         time.sleep(4)  # (a handle just closed leaves the driver VRAM to wipe: see tools/bgzf_e2e.py)
         t = time.perf_counter()
         c = map_bnp(ns)
         return c, time.perf_counter() - t
 
-    outs, times = {}, {k: [] for k in paths}
+    kinds = list(paths) + ([k + "@Q" for k in paths] if min_q > 0 else [])
+    outs, times = {}, {k: [] for k in kinds}
     for rep in range(reps):
-        for kind in paths:
+        for kind in kinds:
             c, dt = cli(kind)
             outs[kind] = c
             times[kind].append(dt)
@@ -91,6 +98,11 @@ def main():
               flush=True)
     same = all(np.array_equal(outs["fastq.gz"], outs[k]) for k in paths)
     print("counts: BGZF FASTQ route == BAM route == BGZF SAM route == plain SAM route: %s" % same, flush=True)
+    if min_q > 0:
+        same_q = all(np.array_equal(outs["fastq.gz@Q"], outs[k + "@Q"]) for k in paths)
+        print("counts at Q%d: BGZF FASTQ route == BAM route == BGZF SAM route == plain SAM route: %s; they differ from the floor-off "
+              "counts: %s" % (min_q, same_q, not np.array_equal(outs["fastq.gz"], outs["fastq.gz@Q"])), flush=True)
+        same = same and same_q
     for p in paths.values():
         os.remove(p)
     if not same:
