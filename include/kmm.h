@@ -25,8 +25,9 @@
  *     decreasing read offsets) are reported by the next synchronising call and then STAY on the handle:
  *     the chunk's valid windows are already counted by then (the reference raises before counting anything
  *     of that chunk), so every later synchronising call fails with the same code until kmm_reset_counts
- *     clears the counts and the error together.  A caller-owned buffer (kmm_bind_counts) must be zeroed by
- *     the caller as well.
+ *     clears the counts and the error together — an error of the calls before it that no synchronising call
+ *     has reported yet included: it is never reported against the counts of the calls after the reset.  A
+ *     caller-owned buffer (kmm_bind_counts) must be zeroed by the caller as well.
  *   - Counts are uint32 and wrap modulo 2^32 exactly like the reference (mapper.pyx:37,68).
  */
 #ifndef KMM_H
@@ -222,7 +223,22 @@ int kmm_map_reads_qual(kmm_index_t *idx, const uint8_t *bases, const uint8_t *qu
 /* Multi-line FASTA (sequences wrapped over several lines; `bnp.open` reads those too): the chunk is unwrapped into
  * two-line FASTA on the GPU first.  A record is only known to be complete once the NEXT header line has been seen, so
  * *consumed stops at the start of the chunk's last header line — unless the caller ORs KMM_FORMAT_LAST_CHUNK into
- * `format` (the chunk ends the file: everything is consumed). */
+ * `format` (the chunk ends the file: everything is consumed).
+ *   - a line terminator ('\n', or a '\r' right before one) is dropped iff its line does not start with '>' and the byte
+ *     behind it exists and is not '>': blank lines are dropped, inside a record and between two;
+ *   - a header line followed by an empty line (">h\n\n") is a read of length 0 that counts in *n_records;
+ *   - a header line directly followed by a header line (or by the end of the chunk), and bytes before the first '>', are
+ *     errors: KMM_ERR_MALFORMED from the call, or KMM_ERR_MALFORMED / KMM_ERR_INVALID_BASE at the next synchronising call,
+ *     as for two-line FASTA; a '\r' on a sequence line that no '\n' follows is KMM_ERR_MALFORMED from the call, nothing
+ *     of its piece mapped (the last byte of a chunk that does not end the file is not looked at: it lies in the record
+ *     that is not consumed);
+ *   - at the end of the file the last line must end with a newline, as for the other formats: a final line without one is
+ *     KMM_ERR_MALFORMED with KMM_FORMAT_LAST_CHUNK (the records before it are already counted);
+ *   - the call cuts a chunk into pieces (of 2^30 bytes) that each end where a header line starts; only the piece that ends
+ *     the chunk is told that the file ends.  A piece of full size that holds no whole record — one record exceeds a piece —
+ *     is KMM_ERR_MALFORMED, with and without KMM_FORMAT_LAST_CHUNK, the message naming the piece's offset: the call never
+ *     returns KMM_OK with part of a last chunk unconsumed.  The pieces before it are already counted (the rule for every
+ *     error the device finds). */
 #define KMM_FORMAT_FASTA 1
 #define KMM_FORMAT_LAST_CHUNK 0x100
 /* SAM text (SAM/BAM specification 1.4; what `samtools view`, aligners and simulators write; `bnp.open` reads it and the

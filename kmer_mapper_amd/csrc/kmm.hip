@@ -1103,6 +1103,9 @@ int kmm_reset_counts(kmm_index_t *ix)
     if (ix->rx_ecnt_acc)
         HIPCHK(hipMemsetAsync(ix->rx_ecnt_acc, 0, sizeof(uint32_t) * (size_t)(ix->rx_S ? ix->rx_S : 1), ix->stream));
     ix->ecnt_dirty = false;
+    // an error that the kernels of an earlier map call have found, or will find, and no synchronising call has reported yet
+    // goes with that call's counts: left in place it would be reported against the counts of the calls AFTER this reset
+    HIPCHK(hipMemsetAsync(ix->first_bad, 0xFF, 3 * sizeof(unsigned long long), ix->stream));
     if (ix->sticky_rc != KMM_OK) { // the error of a mapped chunk goes away together with its partial counts
         unsigned long long nb[3] = {NO_BAD, NO_BAD, NO_BAD};
         HIPCHK(hipStreamSynchronize(ix->stream));
@@ -2306,6 +2309,7 @@ static int map_multiline_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_by
     uint32_t *super_tot = (uint32_t *)s.offsets.p;
     uint8_t *cells = (uint8_t *)s.offsets.p + (((size_t)n_super * 4 + 15) & ~(size_t)15);
     uint32_t *d_total = (uint32_t *)cells;                       // kept bytes of the whole chunk
+    int *d_lone_cr = (int *)(cells + 4);                         // first '\r' of a sequence line without '\n' (0x7F7F7F7F: none)
     int *d_last_header = (int *)(cells + 8);                     // start of the last header line (-1: none)
     unsigned long long *d_out_len = (unsigned long long *)(cells + 16);
     int32_t *tile_last = (int32_t *)s.start_bits.p, *tile_prev = tile_last + n_tiles;
@@ -2314,17 +2318,24 @@ static int map_multiline_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_by
     hipStream_t cs = ix->stream; // (kernels run on the handle's stream only: see rec_compact_piece)
     HIPCHK(hipMemsetAsync(tile_cnt, 0, (size_t)n_super * 1024 * 4, cs));
     HIPCHK(hipMemsetAsync(d_last_header, 0xFF, 4, cs));
+    HIPCHK(hipMemsetAsync(d_lone_cr, 0x7F, 4, cs)); // (beyond every position of a piece: pieces have at most 2^30 bytes)
     const dim3 g4((unsigned)((n_tiles + 3) / 4));
     hipLaunchKernelGGL(k_ml_tile_last, g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_last);
     hipLaunchKernelGGL(k_ml_scan, dim3(1), dim3(1024), 0, cs, tile_last, n_tiles, tile_prev);
-    hipLaunchKernelGGL(k_ml_flags, g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_prev, tile_cnt, d_last_header);
+    hipLaunchKernelGGL(k_ml_flags, g4, dim3(256), 0, cs, d_raw, n_bytes, n_tiles, tile_prev, tile_cnt, d_last_header,
+                       d_lone_cr);
     hipLaunchKernelGGL(k_rec_scan1, dim3(n_super), dim3(1024), 0, cs, tile_cnt, super_tot);
     hipLaunchKernelGGL(k_super_scan, dim3(1), dim3(1024), 0, cs, super_tot, n_super, d_total);
     HIPCHK(hipGetLastError());
-    struct { uint32_t total; uint32_t pad; int last_header; } h = {0, 0, -1};
+    struct { uint32_t total; int lone_cr; int last_header; } h = {0, 0x7F7F7F7F, -1};
     HIPCHK(hipMemcpyAsync(&h, cells, 12, hipMemcpyDeviceToHost, cs));
     HIPCHK(hipStreamSynchronize(cs)); // (the borrowed host buffer is free from here on)
     const int64_t limit = last ? n_bytes : (h.last_header > 0 ? (int64_t)h.last_header : 0);
+    if ((int64_t)h.lone_cr < limit) {
+        (void)stage_release(ix, s, false);
+        return fail(KMM_ERR_MALFORMED, "multi-line FASTA chunk: the '\\r' at byte %d of the piece is not followed by '\\n' (nothing of "
+                    "the piece is mapped)", h.lone_cr);
+    }
     int64_t out_len = 0;
     if (limit > 0) {
         unsigned long long ol = h.total;
@@ -2525,6 +2536,12 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
                                        &used, &nr));
         else
             KMMCHK(map_records_piece(ix, raw + off, len, format, k, max_freq, also_revcomp, lut, &used, &nr));
+        // a multi-line FASTA record that fills a whole piece: no later piece, no longer chunk and no further call can ever
+        // complete it, and with KMM_FORMAT_LAST_CHUNK the rest of the file would be dropped behind a KMM_OK
+        if (format == KMM_FORMAT_FASTA && used == 0 && len == piece_max)
+            return fail(KMM_ERR_MALFORMED, "kmm_map_records: multi-line FASTA: the piece at byte %lld of the chunk holds no whole "
+                        "record: one record exceeds a piece of %lld bytes (the pieces before it are already counted)",
+                        (long long)off, (long long)piece_max);
         off += used;
         recs += nr;
         if (used == 0 || len < piece_max)

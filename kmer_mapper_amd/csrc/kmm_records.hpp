@@ -203,10 +203,11 @@ __device__ __forceinline__ bool ml_keep(const uint8_t *__restrict__ raw, int64_t
 }
 
 // One wavefront per tile, 16 bytes per lane: keep flags (16-bit mask per lane, recomputed by the scatter), kept bytes
-// per tile, and the start of the chunk's last header line (atomicMax).
+// per tile, the start of the chunk's last header line (atomicMax), and the first '\r' on a sequence line that no '\n'
+// follows (atomicMin): no terminator, and no base either — the two-line parser behind the unwrap would take it for a line end.
 __global__ void __launch_bounds__(256) k_ml_flags(const uint8_t *__restrict__ raw, int64_t n, int64_t n_tiles,
                                                   const int32_t *__restrict__ tile_prev, uint32_t *__restrict__ tile_cnt,
-                                                  int *__restrict__ last_header)
+                                                  int *__restrict__ last_header, int *__restrict__ lone_cr)
 {
     const int lane = threadIdx.x & 63;
     const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -231,7 +232,7 @@ __global__ void __launch_bounds__(256) k_ml_flags(const uint8_t *__restrict__ ra
     const int32_t tp = tile_prev[tile];
     prev = prev > tp ? prev : tp;
     uint32_t kept = 0;
-    int hdr = -1;
+    int hdr = -1, cr = 0x7FFFFFFF;
     for (int i = 0; i < 16; ++i) {
         const int64_t q = p + i;
         if (q >= n)
@@ -239,6 +240,8 @@ __global__ void __launch_bounds__(256) k_ml_flags(const uint8_t *__restrict__ ra
         const uint32_t c = raw[q];
         if (ml_keep(raw, n, q, c, prev))
             ++kept;
+        if (c == 13u && !(q + 1 < n && raw[q + 1] == 10u) && raw[prev + 1] != (uint8_t)'>' && (int)q < cr)
+            cr = (int)q;
         if (c == (uint32_t)'>' && (int64_t)prev + 1 == q)
             hdr = (int)q; // a header line starts here
         if (c == 10u)
@@ -249,11 +252,15 @@ __global__ void __launch_bounds__(256) k_ml_flags(const uint8_t *__restrict__ ra
         kept += __shfl_xor(kept, d);
         const int o = __shfl_xor(hdr, d);
         hdr = o > hdr ? o : hdr;
+        const int oc = __shfl_xor(cr, d);
+        cr = oc < cr ? oc : cr;
     }
     if (lane == 0) {
         tile_cnt[tile] = kept;
         if (hdr >= 0)
             atomicMax(last_header, hdr);
+        if (cr != 0x7FFFFFFF)
+            atomicMin(lone_cr, cr);
     }
 }
 
