@@ -248,9 +248,10 @@ int kmm_map_reads_qual(kmm_index_t *idx, const uint8_t *bases, const uint8_t *qu
  *   - a line whose first byte is '@' is a header line, skipped wherever it appears (concatenated files), counted in
  *     "sam_header_lines";
  *   - every other line is one record with at least 11 TAB-separated fields; field 10 (SEQ) is mapped AS STORED (reverse-
- *     strand records are not flipped, as in kmm_map_bam) through the same lookup table as every other entry point (lut
- *     NULL: ACGT -> 0123, N -> A): "=" and the IUPAC codes are KMM_ERR_INVALID_BASE at the next synchronising call; optional
- *     fields behind QUAL are ignored.  SEQ "*" is a read without k-mers that counts in *n_records (as l_seq = 0 in BAM);
+ *     strand records are not flipped, as in kmm_map_bam) unless "original_strand" (kmm_set_param) is 1 — a kept record
+ *     whose FLAG has 0x10 is then reverse-complemented back letter by letter, its QUAL reversed — through the same lookup
+ *     table as every other entry point (lut NULL: ACGT -> 0123, N -> A): "=" and the IUPAC codes are
+ *     KMM_ERR_INVALID_BASE at the next synchronising call; optional fields behind QUAL are ignored.  SEQ "*" is a read without k-mers that counts in *n_records (as l_seq = 0 in BAM);
  *   - "bam_exclude_flags" (kmm_set_param) leaves out records with FLAG & mask;
  *   - *consumed = the byte after the chunk's last '\n' (a record never spans a newline); '\r' before '\n' is tolerated;
  *   - refused with KMM_ERR_MALFORMED, nothing of the call mapped, the message naming the first bad line's byte offset: a
@@ -330,7 +331,9 @@ int kmm_map_gzip(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int form
  * the header is checked (magic "BAM\1") and skipped (l_text, text, n_ref, the references; it may span many members — a first
  * window that ends inside it consumes nothing and maps nothing: bring a longer one); n_ref stays in the handle.  Record
  * starts are found speculatively per 16 KiB tile and verified by a link pass (csrc/kmm_bam.hpp); each record's
- * SEQ, AS STORED (reverse-strand records are not flipped, as bionumpy does not flip them), goes through the same 256-byte
+ * SEQ, AS STORED (reverse-strand records are not flipped, as bionumpy does not flip them) unless "original_strand"
+ * (kmm_set_param) is 1 — a kept record whose FLAG has 0x10 is then decoded in read orientation — goes through the same
+ * 256-byte
  * lookup table as every other entry point (lut NULL: ACGT -> 0123, N -> A, command_line_interface.py:41): "=" and the IUPAC
  * codes are KMM_ERR_INVALID_BASE at the next synchronising call, exactly as the same letter in a FASTQ.  A record with
  * l_seq = 0 is a read without k-mers; no k-mer spans two records.  Refused with KMM_ERR_MALFORMED, with nothing of the call
@@ -550,6 +553,28 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      switch.  No effect on FASTQ, FASTA or flat reads.  Read-only "records_without_qual": kept SAM / BAM
  *                      records with at least one base that store no qualities, counted while the floor is applied, since
  *                      the statistics were last reset (kmm_get_stats(reset)); synchronises like "quality_masked_bases"
+ *   "original_strand"  0 (default) or 1; anything else KMM_ERR_INVALID_ARG.  0: the library as it is without the parameter, bit
+ *                      for bit: SEQ as stored.  1: on kmm_map_bam, and on kmm_map_records / kmm_map_bgzf / kmm_map_gzip with
+ *                      KMM_FORMAT_SAM, every KEPT record whose FLAG has 0x10 — stored reverse-complemented by the aligner —
+ *                      is handed to the mapper in read orientation, as `samtools fastq` writes it (csrc/kmm_bam.hpp,
+ *                      csrc/kmm_sam.hpp).  SEQ is reversed and complemented: BAM by reversing the four bits of
+ *                      the base code, =ACMGRSVTWYHKDBN -> =TGKCYSBAWRDMHVN (htslib's table); SAM text by A<->T, C<->G,
+ *                      M<->K, R<->Y, V<->B, H<->D with upper and lower case each kept, W, S, N and every other byte ('=',
+ *                      '.', U, ...) left as it is — the same records as BAM and as upper-case SAM give the same text.  The
+ *                      lookup table is applied AFTER the flip, as for any other input: a KMM_LUT_BREAK letter breaks at its
+ *                      mirrored position, a 0xFF letter is KMM_ERR_INVALID_BASE at the next synchronising call, the default
+ *                      table turns the flipped read's N into A.  QUAL, where it is decoded ("use_record_qual" 1 and
+ *                      "min_base_quality" Q > 0), is reversed and not complemented, so the masked base is the one the
+ *                      sequencer called badly; absent qualities stay absent; "records_without_qual" and
+ *                      "quality_masked_bases" keep their meaning; with "use_record_qual" 0 and Q > 0 the calls are refused
+ *                      as without the switch.  A record with SEQ "*" / l_seq 0 has nothing to flip; records dropped by
+ *                      "bam_exclude_flags" are not looked at (0x900 drops the partial and repeated records that `samtools
+ *                      fastq` drops).  SEQ is flipped whole: clipping is not looked at.  *n_records, "bam_records",
+ *                      "sam_records", *consumed and the carry between calls are unaffected (a record carried over is
+ *                      flipped once, by the call that maps it).  No effect on FASTQ, FASTA, flat or packed reads.  Read-only
+ *                      "records_reversed": kept records with 0x10 and at least one base that were flipped since the
+ *                      statistics were last reset (kmm_get_stats(reset)); 0 while the switch is 0; synchronises like
+ *                      "quality_masked_bases"
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the

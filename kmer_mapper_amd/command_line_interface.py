@@ -171,7 +171,7 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
 
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
-                exclude_flags=0, probe=None, lut=None, min_base_quality=0, use_record_qual=False):
+                exclude_flags=0, probe=None, lut=None, min_base_quality=0, use_record_qual=False, original_strand=False):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
     on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
@@ -180,8 +180,11 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     min_base_quality: the handle's "min_base_quality", set before the first map call on every route (FASTQ has qualities;
     SAM / BAM are refused before the index goes up unless use_record_qual is given; FASTA is mapped as before with a warning).
     use_record_qual: the handle's "use_record_qual" — the QUAL of SAM / BAM records is decoded on the GPU and the floor applied
-    (DESIGN 4.12); records that store no qualities pass unmasked and are counted ("records_without_qual")."""
+    (DESIGN 4.12); records that store no qualities pass unmasked and are counted ("records_without_qual").
+    original_strand: the handle's "original_strand", SAM / BAM alone — the kept records whose FLAG has 0x10 are mapped in read
+    orientation (SEQ reverse-complemented back, QUAL reversed: DESIGN 4.13) and counted ("records_reversed")."""
     _check_bam_route(fmt, world_size, exclude_flags)
+    original_strand = check_original_strand(original_strand, fmt)
     use_record_qual = check_use_record_qual(use_record_qual, fmt, min_base_quality)
     min_base_quality = check_min_base_quality(min_base_quality, k, fmt, use_record_qual=use_record_qual)
     t_index = time.perf_counter()
@@ -230,6 +233,9 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         dev.set_param("min_base_quality", min_base_quality)
     if use_record_qual:
         dev.set_param("use_record_qual", 1)
+    if original_strand:
+        dev.set_param("original_strand", 1)
+        _log_original_strand_filter(exclude_flags)
     from . import _io
     _io.set_default_threads(n_host)
     logging.info("%d host thread(s) read and pack the read bytes (-t %d, CPU budget %d)", n_host, n_threads, _io.cpu_budget())
@@ -294,7 +300,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         return _map_compressed_file(dev, path, route, kfmt, k, max_index_lookup_frequency,
                                     map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
                                     world_size=world_size, fmt=fmt, lut=lut, min_base_quality=min_base_quality,
-                                    use_record_qual=use_record_qual)
+                                    use_record_qual=use_record_qual, original_strand=original_strand)
     try:
         i = 0
         while True:
@@ -323,6 +329,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         n_host_packed = dev.get_param("host_packed_record_calls")
         n_masked = dev.get_param("quality_masked_bases") if min_base_quality else None
         n_no_qual = dev.get_param("records_without_qual") if (min_base_quality and use_record_qual) else 0
+        n_reversed = dev.get_param("records_reversed") if original_strand else None
         if before_fetch is not None:
             before_fetch(dev)
         if helper.is_alive() or helper.ident is not None:
@@ -353,6 +360,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                  "(%.1f M/s), %d index hits" % (n_reads, n_bytes, n_bytes / max(dt, 1e-9) / 1e6, n_lookups,
                                                   n_lookups / max(dt, 1e-9) / 1e6, n_hits))
     _log_quality_masked(min_base_quality, n_masked, n_no_qual)
+    _log_records_reversed(n_reversed)
     _log_path_taken(n_radix, n_direct, n_host_packed)
     return node_counts
 
@@ -363,6 +371,27 @@ def _log_quality_masked(min_base_quality, n_masked, n_no_qual=0):
         if n_no_qual:
             logging.info("records_without_qual: %d records store no qualities (QUAL '*' / 0xFF): they passed Q%d unmasked",
                          n_no_qual, min_base_quality)
+
+
+def _log_records_reversed(n_reversed):
+    if n_reversed is not None:
+        logging.info("records_reversed: %d records with FLAG 0x10 were mapped in read orientation (--original-strand)", n_reversed)
+
+
+def _log_original_strand_filter(exclude_flags):
+    """--original-strand asks for the reads as sequenced: one line when the flag filter lets partial or repeated ones through."""
+    if int(exclude_flags) & 0x900 != 0x900:
+        logging.info("--original-strand without --exclude-flags 0x900: secondary and supplementary records hold partial or repeated "
+                     "reads, and `samtools fastq` leaves them out")
+
+
+def check_original_strand(original_strand, fmt):
+    """--original-strand against what it cannot go with; returns whether it applies."""
+    if not original_strand:
+        return False
+    if fmt not in ("sam", "bam"):
+        raise ValueError("--original-strand applies to SAM and BAM input only (the reads are %s)" % fmt)
+    return True
 
 
 def check_use_record_qual(use_record_qual, fmt, min_base_quality):
@@ -427,7 +456,7 @@ _COMPRESSED_ROUTES = {
 
 
 def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None, rank=0,
-                         world_size=1, fmt="fastq", lut=None, min_base_quality=0, use_record_qual=False):
+                         world_size=1, fmt="fastq", lut=None, min_base_quality=0, use_record_qual=False, original_strand=False):
     """`kmer_mapper map -f reads.fq.gz | reads.bam` with the GPU inflater: windows of the file mapping -> kmm_map_<route>.
 
     route "gzip" (PLAIN gzip, kmm_map_gzip): each call goes on where the one before could verify a deflate block boundary.
@@ -522,6 +551,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
         counts = [dev.get_param(c) for c in counters]
         n_masked = dev.get_param("quality_masked_bases") if min_base_quality else None
         n_no_qual = dev.get_param("records_without_qual") if (min_base_quality and use_record_qual) else 0
+        n_reversed = dev.get_param("records_reversed") if original_strand else None
         n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
         if before_fetch is not None:
             before_fetch(dev)
@@ -536,6 +566,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
     logging.info(summary % (n_reads, size - lo, (size - lo) / max(dt, 1e-9) / 1e6, *counts, n_lookups,
                             n_lookups / max(dt, 1e-9) / 1e6, n_hits))
     _log_quality_masked(min_base_quality, n_masked, n_no_qual)
+    _log_records_reversed(n_reversed)
     _log_path_taken(n_radix, n_direct)
     return node_counts
 
@@ -556,6 +587,8 @@ def map_bnp(args):
 
     k = args.kmer_size
     start_time = time.perf_counter()
+    if getattr(args, "original_strand", False):    # (refused here: before the index file is read)
+        check_original_strand(True, probe_input(args.reads).fmt)
     kmer_index = _get_kmer_index_from_args(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -591,7 +624,8 @@ def map_bnp(args):
     # 172 GB/s of FASTQ from the GPU's own node, 132 spread over both sockets: profiles/r05/hostpack_rate.txt)
     from .distributed import bind_to_gpu_numa_node
     logging.info("Rank %d: host side bound to its GPU's NUMA node: %s", rank, bind_to_gpu_numa_node(device))
-    # (the read file is opened first HERE, on the GPU's NUMA node)
+    # (the read file is opened first HERE, on the GPU's NUMA node — but for --original-strand, whose check above has read its
+    # first bytes already, to refuse before the index file is read)
     probe = probe_input(args.reads)
     n_bytes = os.stat(args.reads).st_size
     if probe.inflate:
@@ -611,6 +645,7 @@ def map_bnp(args):
     use_qual = check_use_record_qual(bool(getattr(args, "use_record_qual", False)), fmt, getattr(args, "min_base_quality", 0))
     min_q = check_min_base_quality(getattr(args, "min_base_quality", 0), k, fmt, bool(getattr(args, "host_parser", False)),
                                    use_record_qual=use_qual)
+    original_strand = check_original_strand(bool(getattr(args, "original_strand", False)), fmt)
     if fmt == "bam" and getattr(args, "host_parser", False):
         raise ValueError("--host-parser does not read BAM: its records are decoded on the GPU (drop --host-parser)")
     if fmt == "sam" and getattr(args, "host_parser", False):
@@ -621,7 +656,7 @@ def map_bnp(args):
         node_counts = map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, revcomp, max_freq,
                                   device=device, rank=rank, world_size=world, before_fetch=before_fetch,
                                   n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe, lut=lut,
-                                  min_base_quality=min_q, use_record_qual=use_qual)
+                                  min_base_quality=min_q, use_record_qual=use_qual, original_strand=original_strand)
     else:
         logging.info("Using the host FASTA/FASTQ parser")
         if world > 1 and not probe.inflate:
@@ -704,6 +739,11 @@ def build_argument_parser():
                            help="Extension, SAM and BAM input only, with --min-base-quality: decode every record's QUAL on the GPU "
                                 "and apply the floor to it. Records that store no qualities (QUAL '*', 0xFF in BAM) pass unmasked "
                                 "and are counted in the log. Without it, --min-base-quality is refused on SAM and BAM.")
+    subparser.add_argument("--original-strand", action="store_true",
+                           help="Extension, SAM and BAM input only: map every record whose FLAG has 0x10 (stored reverse-complemented "
+                                "by the aligner) in read orientation, SEQ flipped back and QUAL reversed on the GPU, as `samtools "
+                                "fastq` writes it; with --exclude-flags 0x900 the counts are those of the FASTQ the file was made "
+                                "from. Default: SEQ as stored, as the reference.")
     subparser.set_defaults(func=map_bnp)
     return parser
 

@@ -390,6 +390,7 @@ struct kmm_index : IndexStreams, RxArrays {
     int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
     int min_base_quality = 0;    // "min_base_quality": > 0: a FASTQ base whose quality byte is below 33 + this is a break (flat reads: 4.11)
     int use_record_qual = 0;     // "use_record_qual": 1: with a floor set, SAM / BAM records are mapped with their QUAL
+    int original_strand = 0;     // "original_strand": 1: kept SAM / BAM records with FLAG 0x10 are mapped in read orientation
     int64_t dbg_rec_piece_kb = 0; // test hook ("debug_records_piece_kb"): bytes per piece of kmm_map_records, KiB (0: 2^30 bytes)
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
     bool rx_filter_slots = true;  // "radix_filter_slots": where the geometry allows it the filter is the slot filter (0: the bucket bitmap)
@@ -2420,9 +2421,14 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
             // (with QUAL "*" a record's four-line FASTQ is longer than its line: the buffer is sized from the totals)
             rc = ensure(s.kmers, (size_t)h.out_bytes + 16);
             if (rc == KMM_OK) {
-                hipLaunchKernelGGL(kmm_sam::k_sam_write_q, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
-                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
-                                   ix->stats + KMM_STAT_REC_NO_QUAL);
+                if (ix->original_strand)
+                    hipLaunchKernelGGL(kmm_sam::k_sam_write_q_rev, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
+                                       (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
+                                       ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
+                else
+                    hipLaunchKernelGGL(kmm_sam::k_sam_write_q, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
+                                       (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
+                                       ix->stats + KMM_STAT_REC_NO_QUAL);
                 const hipError_t e = hipGetLastError();
                 if (e != hipSuccess)
                     rc = fail(KMM_ERR_HIP, "kmm_map_records: k_sam_write_q: %s", hipGetErrorString(e));
@@ -2437,8 +2443,12 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
                           h.out_bytes, (long long)*n_records, h.recs);
         } else if (h.recs > 0) {
             uint8_t *out = (uint8_t *)s.kmers.p;
-            hipLaunchKernelGGL(kmm_sam::k_sam_write, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
-                               (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out);
+            if (ix->original_strand)
+                hipLaunchKernelGGL(kmm_sam::k_sam_write_rev, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
+                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out, ix->stats + KMM_STAT_REC_REVERSED);
+            else
+                hipLaunchKernelGGL(kmm_sam::k_sam_write, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
+                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out);
             HIPCHK(hipGetLastError());
             // the records as two-line FASTA, from HBM, through the two-line parser (its kernels wait for the copy stream)
             int64_t used = 0;
@@ -3088,6 +3098,7 @@ struct BamGpuBackend {
     int32_t n_ref;
     uint32_t excl;
     bool qual = false; // the quality variant: four-line FASTQ, 2 l_seq + 6 bytes per kept record
+    bool orig = false; // "original_strand": decode writes the kept records with FLAG 0x10 in read orientation
     int cur = 0;
 
     kmm_bam::Tile *tiles(int i) { return (kmm_bam::Tile *)ix->bam_tiles[i].p; }
@@ -3147,10 +3158,18 @@ struct BamGpuBackend {
     }
     int decode(uint64_t n_tiles, uint8_t *out)
     {
-        if (qual)
+        if (qual && orig)
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_rev, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
+                               (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out,
+                               ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
+        else if (qual)
             hipLaunchKernelGGL(kmm_bam::k_bam_decode_q, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
                                (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out,
                                ix->stats + KMM_STAT_REC_NO_QUAL);
+        else if (orig)
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode_rev, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
+                               (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out,
+                               ix->stats + KMM_STAT_REC_REVERSED);
         else
             hipLaunchKernelGGL(kmm_bam::k_bam_decode, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
                                (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out);
@@ -3199,7 +3218,7 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
         return fail(KMM_ERR_INVALID_ARG, "kmm_map_bam: no BAM stream was started on this handle (KMM_FORMAT_NEW_STREAM)");
     }
     const bool qual = record_quality(ix) > 0;
-    BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl, qual};
+    BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl, qual, ix->original_strand != 0};
     kmm_bam::CallOut co;
     KMMCHK(kmm_bam::run_call(be, (uint64_t)n_raw, start0, co));
     ix->bam_false_starts += (int64_t)co.false_starts;
@@ -4028,6 +4047,11 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value != 0 && value != 1)
             return fail(KMM_ERR_INVALID_ARG, "use_record_qual takes 0 or 1");
         ix->use_record_qual = (int)value;
+    } else if (!strcmp(name, "original_strand")) {
+        // 1: kmm_map_bam and KMM_FORMAT_SAM hand every kept record whose FLAG has 0x10 to the mapper in read orientation
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "original_strand takes 0 or 1");
+        ix->original_strand = (int)value;
     } else if (!strcmp(name, "debug_records_piece_kb")) {
         // test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a few hundred KB then make several pieces
         if (value < 0 || value > (1 << 20))
@@ -4088,6 +4112,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->min_base_quality;
     else if (!strcmp(name, "use_record_qual"))
         *value = ix->use_record_qual;
+    else if (!strcmp(name, "original_strand"))
+        *value = ix->original_strand;
     else if (!strcmp(name, "debug_records_piece_kb"))
         *value = ix->dbg_rec_piece_kb;
     else if (!strcmp(name, "bam_calls")) // kmm_map_bam calls that mapped their records (a window inside the header not counted)
@@ -4199,7 +4225,7 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->rx_ok ? ix->rx_geo.F1 : 0;
     else if (!strcmp(name, "radix_p2_kmers") || !strcmp(name, "radix_p3_kmers") || !strcmp(name, "radix_p2_dropped") ||
              !strcmp(name, "radix_p2_multi_round_items") || !strcmp(name, "quality_masked_bases") ||
-             !strcmp(name, "records_without_qual") ||
+             !strcmp(name, "records_without_qual") || !strcmp(name, "records_reversed") ||
              !strcmp(name, "debug_p3_key_reads") || !strncmp(name, "stats_slot_", 11)) {
         // conservation check of the radix path: k-mers gathered by pass 2 / probed by pass 3 since the last
         // kmm_get_stats(reset): both must equal the lookups pass 1 emitted
@@ -4210,9 +4236,11 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         // ("stats_slot_<n>": raw counter n of the statistics block; slots 4.. are only written by diagnostic builds)
         // ("quality_masked_bases": FASTQ bases whose quality byte was below "min_base_quality", since the same reset)
         // ("records_without_qual": SAM / BAM records with bases and no qualities that were mapped with a floor, since the same reset)
+        // ("records_reversed": SAM / BAM records with FLAG 0x10 and bases written in read orientation ("original_strand"), since the same reset)
         // ("debug_p3_key_reads": 8-byte key reads of pass 3's probes; counted by -DRX_P3_FP_STATS builds only, else 0)
         const int slot = name[0] == 's' ? atoi(name + 11) : name[0] == 'q' ? KMM_STAT_QUAL_MASKED
                                                           : !strcmp(name, "records_without_qual") ? KMM_STAT_REC_NO_QUAL
+                                                          : !strcmp(name, "records_reversed") ? KMM_STAT_REC_REVERSED
                                                           : name[0] == 'd' ? KMM_STAT_RX_P3_KEYS
                                                           : !strcmp(name, "radix_p2_dropped") ? KMM_STAT_RX_DROPPED
                                                           : !strcmp(name, "radix_p2_multi_round_items") ? KMM_STAT_RX_MULTI

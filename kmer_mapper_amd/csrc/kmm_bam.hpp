@@ -21,6 +21,8 @@
 // The quality variant (<true> / k_bam_*_q; "use_record_qual" with a floor) writes every kept record as four-line
 // FASTQ instead ("@\n" SEQ "\n+\n" QUAL "\n", the raw Phred bytes as Phred+33 clipped at '~'): 2 l_seq + 6 bytes per record, which
 // the library maps as KMM_FORMAT_FASTQ, where "min_base_quality" is applied.
+// "original_strand"  has decode write the kept records whose FLAG has 0x10 in read orientation: SEQ reversed and
+// complemented, QUAL reversed.  The output lengths are the same: spec, link and totals do not know of the switch.
 // Exactness never depends on the plausibility test: a wrong guess only costs a fix.  Every read is bounds-checked against n.
 #pragma once
 
@@ -301,6 +303,68 @@ KMM_BAM_HD void decode_record_q(const uint8_t *rec, const RecHead &h, uint8_t *o
     }
 }
 
+// ---- "original_strand" (DESIGN 4.13): a kept record whose FLAG has 0x10 is stored reverse-complemented; the reversed forms
+// below write it in read orientation.  The output lengths are the forward forms', so nothing but decode knows of the switch.
+constexpr uint32_t FLAG_REVERSE = 0x10u;
+
+// The complement of a 4-bit base code is the code with its four bits reversed (A 1 <-> T 8, C 2 <-> G 4, M 3 <-> K 12, ...;
+// '=' 0 and N 15 are their own): "=TGKCYSBAWRDMHVN", htslib's table.
+KMM_BAM_HD uint32_t comp_code(uint32_t code)
+{
+    return ((code & 1u) << 3) | ((code & 2u) << 1) | ((code & 4u) >> 1) | ((code & 8u) >> 3);
+}
+
+// Is the record one the switch flips?  (0x10 and at least one base; wave-uniform: it depends on the record's head alone.)
+KMM_BAM_HD bool flipped(const RecHead &h, bool orig) { return orig && (h.flag & FLAG_REVERSE) != 0u && h.l_seq > 0u; }
+
+// decode, reversed: base i of the stored SEQ goes to position l_seq - 1 - i as its complement.  Byte j holds bases 2j (high
+// nibble) and 2j + 1 (low), which land side by side at l_seq - 2 - 2j and l_seq - 1 - 2j: the lanes of a wavefront store one
+// contiguous run, descending.  The low nibble of the last byte of an odd l_seq is padding: it would land on out[1], in front of
+// the sequence, and is not written.
+KMM_BAM_HD void decode_record_rev(const uint8_t *rec, const RecHead &h, uint8_t *out, uint32_t lane, uint32_t lanes)
+{
+    const uint8_t *seq = rec + seq_offset(h);
+    const uint32_t n_bytes = (h.l_seq + 1u) / 2u;
+    if (lane == 0) {
+        out[0] = '>';
+        out[1] = '\n';
+        out[2ull + h.l_seq] = '\n';
+    }
+    uint8_t *last = out + 1ull + h.l_seq; // the sequence's last byte
+    for (uint32_t j = lane; j < n_bytes; j += lanes) {
+        const uint32_t b = seq[j];
+        last[-2ll * j] = base_letter(comp_code(b >> 4));
+        if (2 * j + 1 < h.l_seq)
+            last[-2ll * j - 1] = base_letter(comp_code(b & 15u));
+    }
+}
+
+// decode, the quality variant, reversed: the letters as above, qual[i] at oq[l_seq - 1 - i] (reversed, not complemented)
+KMM_BAM_HD void decode_record_q_rev(const uint8_t *rec, const RecHead &h, uint8_t *out, uint32_t lane, uint32_t lanes)
+{
+    const uint8_t *seq = rec + seq_offset(h), *qual = qual_of(rec, h);
+    const uint32_t n_bytes = (h.l_seq + 1u) / 2u;
+    uint8_t *oq = out + 5ull + h.l_seq;
+    if (lane == 0) {
+        out[0] = '@';
+        out[1] = '\n';
+        out[2ull + h.l_seq] = '\n';
+        out[3ull + h.l_seq] = '+';
+        out[4ull + h.l_seq] = '\n';
+        oq[h.l_seq] = '\n';
+    }
+    uint8_t *last = out + 1ull + h.l_seq, *qlast = oq + h.l_seq - 1ull; // (l_seq 0: n_bytes 0, neither is used)
+    for (uint32_t j = lane; j < n_bytes; j += lanes) {
+        const uint32_t b = seq[j];
+        last[-2ll * j] = base_letter(comp_code(b >> 4));
+        qlast[-2ll * j] = qual_letter(qual[2ull * j]);
+        if (2 * j + 1 < h.l_seq) {
+            last[-2ll * j - 1] = base_letter(comp_code(b & 15u));
+            qlast[-2ll * j - 1] = qual_letter(qual[2ull * j + 1]);
+        }
+    }
+}
+
 // ---- the header (host side: the library reads it back once per stream) ----
 
 // d[0, n) = the stream's first inflated bytes.  0: the header ends at *hdr_end and names *n_ref references; 1: it goes on
@@ -393,6 +457,9 @@ struct CpuBackend {
     uint32_t excl = 0;
     bool qual = false;     // the quality variant: decode() writes four-line FASTQ
     uint64_t no_qual = 0;  // kept records whose qualities are absent (counted by decode() of the quality variant)
+    bool orig = false;     // "original_strand": decode() writes the kept records with FLAG 0x10 in read orientation
+    uint64_t reversed = 0; // the records decode() flipped
+    uint32_t lanes = 1;    // lanes decode() gives the per-record functions (the tests: 1 and 64), one after the other
     std::vector<Tile> cur, nxt;
     std::vector<uint64_t> base;
     uint64_t false_starts = 0;
@@ -468,12 +535,17 @@ struct CpuBackend {
                 RecHead h;
                 if (record_at(d, n, p, n_ref, h) != REC_OK)
                     break;
+                const bool rev = flipped(h, orig);
+                if (!(h.flag & excl))
+                    reversed += rev ? 1u : 0u;
                 if (!(h.flag & excl) && qual) {
-                    decode_record_q(d + p, h, out + o, 0, 1);
+                    for (uint32_t lane = 0; lane < lanes; ++lane)
+                        rev ? decode_record_q_rev(d + p, h, out + o, lane, lanes) : decode_record_q(d + p, h, out + o, lane, lanes);
                     o += 2ull * h.l_seq + 6ull;
                     no_qual += qual_absent(d + p, h) ? 1u : 0u;
                 } else if (!(h.flag & excl)) {
-                    decode_record(d + p, h, out + o, 0, 1);
+                    for (uint32_t lane = 0; lane < lanes; ++lane)
+                        rev ? decode_record_rev(d + p, h, out + o, lane, lanes) : decode_record(d + p, h, out + o, lane, lanes);
                     o += h.l_seq + 3ull;
                 }
                 p += 4ull + h.bs;
@@ -686,6 +758,70 @@ __global__ void __launch_bounds__(256) k_bam_decode_q(const uint8_t *__restrict_
         if (lane == 0 && absent)
             atomicAdd(no_qual, (unsigned long long)absent);
     }
+}
+
+// decode with "original_strand" on: the walks of k_bam_decode (Q false) and k_bam_decode_q (Q true), with every kept record whose
+// FLAG has 0x10 and that has bases written in read orientation — a wave-uniform choice per record — and counted per tile into
+// *reversed (one atomic per tile that has any).  Kernels of their own: the two above are what runs while the switch is off.
+template <bool Q>
+__device__ __forceinline__ void bam_decode_rev_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                     uint32_t excl, const Tile *__restrict__ in, const unsigned long long *__restrict__ base,
+                                                     uint8_t *__restrict__ out, unsigned long long *__restrict__ no_qual,
+                                                     unsigned long long *__restrict__ reversed)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        const Tile c = in[t];
+        if (c.entry == NONE || c.recs == 0)
+            continue;
+        uint64_t p = c.entry, o = base[t];
+        uint32_t absent = 0, flips = 0;
+        while (p < c.exit) {
+            RecHead h;
+            if (record_at(d, n, p, n_ref, h) != REC_OK) // (cannot happen on a verified chain; bounds all the same)
+                break;
+            if (!(h.flag & excl)) {
+                const bool rev = flipped(h, true);
+                if constexpr (Q) {
+                    if (rev)
+                        decode_record_q_rev(d + p, h, out + o, lane, 64u);
+                    else
+                        decode_record_q(d + p, h, out + o, lane, 64u);
+                    o += 2ull * h.l_seq + 6ull;
+                    absent += qual_absent(d + p, h) ? 1u : 0u;
+                } else {
+                    if (rev)
+                        decode_record_rev(d + p, h, out + o, lane, 64u);
+                    else
+                        decode_record(d + p, h, out + o, lane, 64u);
+                    o += h.l_seq + 3ull;
+                }
+                flips += rev ? 1u : 0u;
+            }
+            p += 4ull + h.bs;
+        }
+        if (Q && lane == 0 && absent)
+            atomicAdd(no_qual, (unsigned long long)absent);
+        if (lane == 0 && flips)
+            atomicAdd(reversed, (unsigned long long)flips);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_bam_decode_rev(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                        uint32_t excl, const Tile *__restrict__ in,
+                                                        const unsigned long long *__restrict__ base, uint8_t *__restrict__ out,
+                                                        unsigned long long *__restrict__ reversed)
+{
+    bam_decode_rev_tiles<false>(d, n, n_tiles, n_ref, excl, in, base, out, nullptr, reversed);
+}
+__global__ void __launch_bounds__(256) k_bam_decode_q_rev(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                          uint32_t excl, const Tile *__restrict__ in,
+                                                          const unsigned long long *__restrict__ base, uint8_t *__restrict__ out,
+                                                          unsigned long long *__restrict__ no_qual,
+                                                          unsigned long long *__restrict__ reversed)
+{
+    bam_decode_rev_tiles<true>(d, n, n_tiles, n_ref, excl, in, base, out, no_qual, reversed);
 }
 #endif
 

@@ -156,9 +156,10 @@ constexpr int KMM_STAT_STRIDE = 32; // unsigned long longs = 256 bytes between s
 // [18] pass-2 items placed and copied out in several rounds (slot filter: more survivors than sort-buffer slots),
 // [19] bases masked by "min_base_quality" (k_rec_scatter's quality variant, k_mark_low_quals), [20] 8-byte key reads of pass 3's probes
 // (-DRX_P3_FP_STATS builds only), [21] SAM / BAM records mapped with a floor whose qualities are absent (k_bam_decode_q, k_sam_write_q:
-// shard 0 only)
+// shard 0 only), [22] SAM / BAM records with FLAG 0x10 written in read orientation under "original_strand" (k_bam_decode*_rev,
+// k_sam_write*_rev: shard 0 only)
 constexpr int KMM_STAT_RX_P1 = 16, KMM_STAT_RX_DROPPED = 17, KMM_STAT_RX_MULTI = 18, KMM_STAT_QUAL_MASKED = 19, KMM_STAT_RX_P3_KEYS = 20;
-constexpr int KMM_STAT_REC_NO_QUAL = 21;
+constexpr int KMM_STAT_REC_NO_QUAL = 21, KMM_STAT_REC_REVERSED = 22;
 constexpr int AGG_LOG_SLOTS = 11;
 constexpr int AGG_SLOTS = 1 << AGG_LOG_SLOTS;
 constexpr uint32_t AGG_EMPTY = 0xFFFFFFFFu; // node ids are < 2^31

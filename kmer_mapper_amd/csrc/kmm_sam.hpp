@@ -17,6 +17,8 @@
 // The quality variant (<true> / k_sam_*_q; "use_record_qual" with a floor) also finds TAB 11, checks that QUAL is
 // "*" or as long as SEQ, and writes every kept record as four-line FASTQ ("@\n" SEQ "\n+\n" QUAL "\n"; QUAL "*": '~' per base),
 // 2 |SEQ| + 6 bytes per record, which the library maps as KMM_FORMAT_FASTQ, where "min_base_quality" is applied.
+// "original_strand"  has the write pass emit the kept records whose FLAG has 0x10 in read orientation: SEQ reversed
+// and complemented letter by letter, QUAL reversed.  The output lengths are the same: the count pass does not know of the switch.
 #pragma once
 
 #include <cstdint>
@@ -65,6 +67,7 @@ KMM_SAM_HD uint32_t want_tab(int w) { return w < 2 ? (uint32_t)w + 1u : (uint32_
 struct LineInfo {
     uint32_t kind, err;
     uint64_t seq, seq_len; // SEQ of a record ("*": length 0)
+    bool rev;              // FLAG has 0x10: the record is stored reverse-complemented
 };
 struct LineInfoQ : LineInfo {
     uint64_t qual; // QUAL of a record: seq_len bytes at d[qual], or
@@ -131,6 +134,7 @@ KMM_SAM_HD void classify(const uint8_t *d, uint64_t s, const Line &L, uint32_t e
     o.kind = K_BAD;
     o.err = 0;
     o.seq = o.seq_len = 0;
+    o.rev = false;
     const uint64_t e = L.end;
     if (e == s || (e == s + 1 && d[s] == 13u)) {
         o.err = ERR_EMPTY;
@@ -162,6 +166,7 @@ KMM_SAM_HD void classify(const uint8_t *d, uint64_t s, const Line &L, uint32_t e
     if (o.seq_len == 1 && d[o.seq] == (uint8_t)'*')
         o.seq_len = 0;
     o.kind = (flag & excl) ? K_EXCLUDED : K_KEPT;
+    o.rev = (flag & 0x10u) != 0u;
 }
 
 // The quality variant: what the line is, and its QUAL — the bytes between TAB 10 and TAB 11 (or the line's end, without a CR in
@@ -199,9 +204,23 @@ KMM_SAM_HD uint32_t out_len(uint64_t seq_len)
     return Q ? 2u * (uint32_t)seq_len + 6u : (uint32_t)seq_len + 3u;
 }
 
+// The complement of a SEQ letter ("original_strand"): A <-> T, C <-> G, M <-> K, R <-> Y, V <-> B, H <-> D, each case kept; W, S, N
+// and every other byte ('=', '.', U, ...) as they are.  On the 16 BAM letters it agrees with kmm_bam.hpp's comp_code.
+KMM_SAM_HD uint8_t comp_letter(uint8_t c)
+{
+    const uint32_t u = c & 0xDFu; // (a letter's upper case)
+    if (u < (uint32_t)'A' || u > (uint32_t)'Z')
+        return c;
+    return (uint8_t)((uint32_t)"TVGHEFCDIJMLKNOPQYSAUBWXRZ"[u - (uint32_t)'A'] | (c & 0x20u));
+}
+
+// Is the record one the switch flips?  (0x10 and at least one base.)
+KMM_SAM_HD bool flipped(const LineInfo &li, bool orig) { return orig && li.rev && li.seq_len > 0; }
+
 // The quality variant of emit: "@\n" + SEQ + "\n+\n" + QUAL + "\n" at out[0]; an absent QUAL is written as '~' per base, which no
-// floor masks
-KMM_SAM_HD void emit(const uint8_t *d, const LineInfoQ &li, uint8_t *out, uint32_t lane, uint32_t lanes)
+// floor masks.  rev: in read orientation — output byte j is the complement of SEQ's byte seq_len - 1 - j, and QUAL's byte
+// seq_len - 1 - j as it is (the stores ascend, the loads descend).
+KMM_SAM_HD void emit(const uint8_t *d, const LineInfoQ &li, uint8_t *out, uint32_t lane, uint32_t lanes, bool rev = false)
 {
     uint8_t *oq = out + 5 + li.seq_len;
     if (lane == 0) {
@@ -212,19 +231,32 @@ KMM_SAM_HD void emit(const uint8_t *d, const LineInfoQ &li, uint8_t *out, uint32
         out[4 + li.seq_len] = '\n';
         oq[li.seq_len] = '\n';
     }
+    if (rev) {
+        for (uint64_t j = lane; j < li.seq_len; j += lanes) {
+            const uint64_t m = li.seq_len - 1 - j;
+            out[2 + j] = comp_letter(d[li.seq + m]);
+            oq[j] = li.absent ? (uint8_t)'~' : d[li.qual + m];
+        }
+        return;
+    }
     for (uint64_t j = lane; j < li.seq_len; j += lanes) {
         out[2 + j] = d[li.seq + j];
         oq[j] = li.absent ? (uint8_t)'~' : d[li.qual + j];
     }
 }
 
-// One kept record's output (lane `lane` of `lanes`): ">\n" + SEQ + "\n" at out[0]
-KMM_SAM_HD void emit(const uint8_t *d, const LineInfo &li, uint8_t *out, uint32_t lane, uint32_t lanes)
+// One kept record's output (lane `lane` of `lanes`): ">\n" + SEQ + "\n" at out[0]; rev: in read orientation, as above
+KMM_SAM_HD void emit(const uint8_t *d, const LineInfo &li, uint8_t *out, uint32_t lane, uint32_t lanes, bool rev = false)
 {
     if (lane == 0) {
         out[0] = '>';
         out[1] = '\n';
         out[2 + li.seq_len] = '\n';
+    }
+    if (rev) {
+        for (uint64_t j = lane; j < li.seq_len; j += lanes)
+            out[2 + j] = comp_letter(d[li.seq + li.seq_len - 1 - j]);
+        return;
     }
     for (uint64_t j = lane; j < li.seq_len; j += lanes)
         out[2 + j] = d[li.seq + j];
@@ -329,24 +361,34 @@ struct CpuSink {
     const uint8_t *d;
     uint8_t *out; // null: the count pass
     uint64_t no_qual = 0; // (the quality variant) kept records with bases whose QUAL is absent
+    bool orig = false;     // "original_strand": the kept records with FLAG 0x10 are written in read orientation
+    uint32_t lanes = 1;    // lanes emit is called with, one after the other
+    uint64_t reversed = 0; // the records written flipped
     void operator()(const LineInfo &li, uint32_t at)
     {
-        if (out)
-            emit(d, li, out + at, 0, 1);
+        if (out) {
+            for (uint32_t lane = 0; lane < lanes; ++lane)
+                emit(d, li, out + at, lane, lanes, flipped(li, orig));
+            reversed += flipped(li, orig) ? 1u : 0u;
+        }
     }
     void operator()(const LineInfoQ &li, uint32_t at)
     {
         if (out) {
-            emit(d, li, out + at, 0, 1);
+            for (uint32_t lane = 0; lane < lanes; ++lane)
+                emit(d, li, out + at, lane, lanes, flipped(li, orig));
             no_qual += li.absent && li.seq_len > 0 ? 1u : 0u;
+            reversed += flipped(li, orig) ? 1u : 0u;
         }
     }
 };
 
 // One chunk on the CPU: the count pass, the totals, the write pass (out: at least tot.out_bytes; null = count only).
 // Q: the quality variant (four-line FASTQ out; *no_qual: the kept records whose QUAL is absent, counted by the write pass).
+// orig: "original_strand" (*reversed: the records the write pass flipped); lanes: what emit is called with.
 template <bool Q = false>
-inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out, Totals &tot, uint64_t *no_qual = nullptr)
+inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out, Totals &tot, uint64_t *no_qual = nullptr,
+                      bool orig = false, uint64_t *reversed = nullptr, uint32_t lanes = 1)
 {
     tot = Totals{0, 0, 0, 0, 0, NONE};
     const uint64_t n_tiles = (n + TILE - 1) / TILE;
@@ -370,10 +412,14 @@ inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out,
         return;
     for (uint64_t t = 0; t < n_tiles; ++t) {
         CpuSink write{d, out + base[t]};
+        write.orig = orig;
+        write.lanes = lanes;
         Tile o;
         walk_tile<Q>(d, n, t, excl, sc, write, o);
         if (no_qual)
             *no_qual += write.no_qual;
+        if (reversed)
+            *reversed += write.reversed;
     }
 }
 
@@ -455,6 +501,33 @@ struct WaveSinkQ {
     {
         emit(d, li, out + at, threadIdx.x & 63u, 64u);
         no_qual += li.absent && li.seq_len > 0 ? 1u : 0u;
+    }
+};
+
+// ("original_strand": the kept records with FLAG 0x10 and bases are written in read orientation, a wave-uniform choice per
+// record, and counted)
+struct WaveSinkRev {
+    const uint8_t *d;
+    uint8_t *out;
+    uint32_t reversed; // records written flipped (wave-uniform)
+    __device__ void operator()(const LineInfo &li, uint32_t at)
+    {
+        const bool rev = flipped(li, true);
+        emit(d, li, out + at, threadIdx.x & 63u, 64u, rev);
+        reversed += rev ? 1u : 0u;
+    }
+};
+struct WaveSinkQRev {
+    const uint8_t *d;
+    uint8_t *out;
+    uint32_t no_qual;  // kept records with bases whose QUAL is absent (wave-uniform)
+    uint32_t reversed; // records written flipped (wave-uniform)
+    __device__ void operator()(const LineInfoQ &li, uint32_t at)
+    {
+        const bool rev = flipped(li, true);
+        emit(d, li, out + at, threadIdx.x & 63u, 64u, rev);
+        no_qual += li.absent && li.seq_len > 0 ? 1u : 0u;
+        reversed += rev ? 1u : 0u;
     }
 };
 
@@ -581,6 +654,46 @@ __global__ void __launch_bounds__(256) k_sam_write_q(const uint8_t *__restrict__
         walk_tile<true>(d, n, t, excl, sc, sink, o);
         if ((threadIdx.x & 63u) == 0 && sink.no_qual)
             atomicAdd(no_qual, (unsigned long long)sink.no_qual);
+    }
+}
+
+// write with "original_strand" on: k_sam_write and k_sam_write_q with the kept records whose FLAG has 0x10 written in read
+// orientation and counted per tile into *reversed (one atomic per tile that has any).  Kernels of their own: the two above are
+// what runs while the switch is off.
+__global__ void __launch_bounds__(256) k_sam_write_rev(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint32_t excl,
+                                                       const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                       uint8_t *__restrict__ out, unsigned long long *__restrict__ reversed)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    WaveScan sc{d, n};
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        if (tiles[t].recs == 0)
+            continue;
+        WaveSinkRev sink{d, out + base[t], 0u};
+        Tile o;
+        walk_tile(d, n, t, excl, sc, sink, o);
+        if ((threadIdx.x & 63u) == 0 && sink.reversed)
+            atomicAdd(reversed, (unsigned long long)sink.reversed);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_sam_write_q_rev(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint32_t excl,
+                                                         const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                         uint8_t *__restrict__ out, unsigned long long *__restrict__ no_qual,
+                                                         unsigned long long *__restrict__ reversed)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    WaveScan sc{d, n};
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        if (tiles[t].recs == 0)
+            continue;
+        WaveSinkQRev sink{d, out + base[t], 0u, 0u};
+        Tile o;
+        walk_tile<true>(d, n, t, excl, sc, sink, o);
+        if ((threadIdx.x & 63u) == 0 && sink.no_qual)
+            atomicAdd(no_qual, (unsigned long long)sink.no_qual);
+        if ((threadIdx.x & 63u) == 0 && sink.reversed)
+            atomicAdd(reversed, (unsigned long long)sink.reversed);
     }
 }
 #endif

@@ -337,6 +337,21 @@ def write_sam(path, batch, names=None, flags=None, header=b"@HD\tVN:1.6\tSO:unso
             f.write(data)
 
 
+_COMPLEMENT = bytes.maketrans(b"ACGTMKRYVBHDacgtmkryvbhd", b"TGCAKMYRBVDHtgcakmyrbvdh")
+
+
+def stored_form(seq, qual=None, reverse=False):
+    """(SEQ, QUAL) as an aligner stores a read for a strand (for tools and tests; with FLAG | 0x10 it is what `bam_record` /
+    `sam_text` are given): forward as it is; reverse: SEQ reversed and complemented (A<->T, C<->G, M<->K, R<->Y, V<->B, H<->D,
+    each case kept; W, S, N and every other byte as they are: htslib's table on the BAM letters), QUAL reversed.  Its own
+    inverse: the stored form of a stored form is the read, which is what "original_strand" hands the mapper."""
+    seq = bytes(seq)
+    qual = None if qual is None else bytes(qual)
+    if not reverse:
+        return seq, qual
+    return seq.translate(_COMPLEMENT)[::-1], None if qual is None else qual[::-1]
+
+
 _SAM_HEADER = re.compile(rb"@(HD|SQ|RG|PG|CO)\t")
 
 

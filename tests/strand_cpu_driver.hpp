@@ -1,0 +1,137 @@
+// The CPU driver of "original_strand"  for the tests (tests/test_strand_on_the_cpu.py builds it as a shared library,
+// tests/strand_san_main.cpp as a sanitized executable): the window loops of bam_cpu_driver.hpp and sam_cpu_driver.hpp with the
+// switch, the plain or the quality variant, and the lane count the per-record functions are called with as arguments.
+#pragma once
+
+#include "kmm_bam.hpp"
+#include "kmm_sam.hpp"
+
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+// As bam_cpu (bam_cpu_driver.hpp).  qual: four-line FASTQ instead of two-line FASTA; orig: the switch; lanes: 1 or 64.
+// stats: [0] records, [1] excluded, [2] calls, [3] records without qualities, [4] records flipped, [5] error position.
+extern "C" int strand_bam_cpu(const uint8_t *data, uint64_t n, const uint64_t *cuts, int n_cuts, uint32_t excl, int qual, int orig,
+                              uint32_t lanes, uint8_t *out, uint64_t out_cap, uint64_t *out_n, uint64_t *stats)
+{
+    uint64_t pos = 0, w = 0, base = 0;
+    int32_t n_ref = -1;
+    uint64_t start0 = 0;
+    for (int i = 0; i < 6; ++i)
+        stats[i] = 0;
+    std::vector<uint8_t> carry;
+    for (int i = 0; i < n_cuts; ++i) {
+        const uint64_t end = cuts[i];
+        if (end < pos)
+            continue;
+        const bool last = end == n;
+        std::vector<uint8_t> win(carry);
+        win.insert(win.end(), data + pos, data + end);
+        if (n_ref < 0) {
+            uint64_t hdr_end = 0;
+            int32_t nr = 0;
+            const int r = kmm_bam::parse_header(win.data(), win.size(), &hdr_end, &nr);
+            if (r < 0)
+                return -1;
+            if (r > 0) {
+                if (last)
+                    return -2;
+                continue;
+            }
+            n_ref = nr;
+            start0 = hdr_end;
+        }
+        kmm_bam::CpuBackend be;
+        be.d = win.data();
+        be.n = win.size();
+        be.n_ref = n_ref;
+        be.excl = excl;
+        be.qual = qual != 0;
+        be.orig = orig != 0;
+        be.lanes = lanes;
+        kmm_bam::CallOut co;
+        if (kmm_bam::run_call(be, win.size(), start0, co) != 0)
+            return -6;
+        ++stats[2];
+        if (co.err_pos != kmm_bam::NONE) {
+            stats[5] = base + co.err_pos;
+            return -3;
+        }
+        if (last && co.consumed != win.size())
+            return -4;
+        if (w + co.out_bytes > out_cap)
+            return -5;
+        if (co.recs) {
+            // exactly the totals' size, on the heap: a write in front of out[0] or behind the last byte is the sanitizer's
+            std::vector<uint8_t> exact(co.out_bytes);
+            be.decode(exact.data());
+            memcpy(out + w, exact.data(), exact.size());
+        }
+        w += co.out_bytes;
+        stats[0] += co.recs;
+        stats[1] += co.excluded;
+        stats[3] += be.no_qual;
+        stats[4] += be.reversed;
+        carry.assign(win.begin() + (std::ptrdiff_t)co.consumed, win.end());
+        base += co.consumed;
+        pos = end;
+        start0 = 0;
+    }
+    *out_n = w;
+    return 0;
+}
+
+template <bool Q>
+static int strand_sam_windows(const uint8_t *data, uint64_t n, const uint64_t *cuts, int n_cuts, uint32_t excl, bool orig, uint32_t lanes,
+                              uint8_t *out, uint64_t out_cap, uint64_t *out_n, uint64_t *stats)
+{
+    uint64_t pos = 0, w = 0, base = 0;
+    for (int i = 0; i < 6; ++i)
+        stats[i] = 0;
+    std::vector<uint8_t> carry;
+    for (int i = 0; i < n_cuts; ++i) {
+        const uint64_t end = cuts[i];
+        if (end < pos)
+            continue;
+        const bool last = end == n;
+        std::vector<uint8_t> win(carry);
+        win.insert(win.end(), data + pos, data + end);
+        if (last && !win.empty() && win.back() != 10)
+            win.push_back(10);
+        kmm_sam::Totals t;
+        kmm_sam::cpu_chunk<Q>(win.data(), win.size(), excl, nullptr, t);
+        ++stats[2];
+        if (t.err != kmm_sam::NONE) {
+            stats[5] = (base + (t.err >> 2)) << 2 | (t.err & 3);
+            return -3;
+        }
+        if (w + t.out_bytes > out_cap)
+            return -5;
+        if (t.out_bytes) {
+            std::vector<uint8_t> exact(t.out_bytes); // (see strand_bam_cpu)
+            kmm_sam::cpu_chunk<Q>(win.data(), win.size(), excl, exact.data(), t, &stats[3], orig, &stats[4], lanes);
+            memcpy(out + w, exact.data(), exact.size());
+        }
+        w += t.out_bytes;
+        stats[0] += t.recs;
+        stats[1] += t.excluded;
+        carry.assign(win.begin() + (std::ptrdiff_t)t.consumed, win.end());
+        base += t.consumed;
+        pos = end;
+    }
+    *out_n = w;
+    return 0;
+}
+
+// As sam_cpu (sam_cpu_driver.hpp), with the arguments and statistics of strand_bam_cpu.
+extern "C" int strand_sam_cpu(const uint8_t *data, uint64_t n, const uint64_t *cuts, int n_cuts, uint32_t excl, int qual, int orig,
+                              uint32_t lanes, uint8_t *out, uint64_t out_cap, uint64_t *out_n, uint64_t *stats)
+{
+    return qual ? strand_sam_windows<true>(data, n, cuts, n_cuts, excl, orig != 0, lanes, out, out_cap, out_n, stats)
+                : strand_sam_windows<false>(data, n, cuts, n_cuts, excl, orig != 0, lanes, out, out_cap, out_n, stats);
+}
+
+// The two complements: of a SAM letter, and of a BAM code as the letter it decodes to
+extern "C" uint32_t strand_comp_letter(uint32_t c) { return kmm_sam::comp_letter((uint8_t)c); }
+extern "C" uint32_t strand_comp_code_letter(uint32_t code) { return kmm_bam::base_letter(kmm_bam::comp_code(code)); }
