@@ -351,6 +351,37 @@ int kmm_map_bam(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int flags
                 int also_revcomp, const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records);
 
 /*
+ * A RANK'S SHARE of a BAM file (several processes on one file; kmer_mapper_amd/bgzf_ranges.py rank_member_range_bam).
+ * KMM_FORMAT_MID_STREAM, OR-ed with KMM_FORMAT_NEW_STREAM into the flags of kmm_map_bam (anything else: KMM_ERR_INVALID_ARG):
+ * the stream does not begin with the file's header.  n_ref is the caller's — kmm_set_param "bam_n_ref", >= 0, else
+ * KMM_ERR_INVALID_ARG — and the first record starts "bgzf_head_skip" inflated bytes into the call's first member.  On every
+ * kmm_map_bam stream "bgzf_tail_stop" cuts the last call's last member as it does for kmm_map_bgzf ("bgzf_head_skip" is passed
+ * over by a stream that begins with the header).  A cut that is no record boundary is "the file ends inside a record",
+ * KMM_ERR_MALFORMED with nothing of the call mapped: the net under a wrongly guessed boundary.
+ *
+ * kmm_bam_header — comp (host memory) starts at the file's first member: growing prefixes of its members are inflated on the
+ * GPU until the header is walked.  *n_ref: its reference count; *hdr_member / *hdr_skip: where the first record lies — the
+ * compressed offset of the member that holds the first byte behind the header, and that byte's offset in the member's inflated
+ * bytes (a header that ends with a member: the next member that holds a byte, skip 0).  A window that ends inside the header:
+ * KMM_OK with *n_ref = -1 — bring a longer one.  A bad magic or lengths no header can have, or a corrupt member:
+ * KMM_ERR_MALFORMED.  Maps nothing and leaves a stream in progress on the handle alone.
+ *
+ * kmm_bam_find_record_start — comp (host memory) starts at a member boundary anywhere in the file.  Its whole members are
+ * inflated and checked (CRC32, ISIZE), and a kernel finds the smallest inflated offset from which a chain of records HOLDS to
+ * the end of those bytes: every record's fields fit its block_size and [-1, n_ref) until one runs past the end, at least one
+ * record is whole, and when comp ends the file (its whole members end exactly at n_comp) the chain ends at the last byte.
+ * The first true record start always holds; a position in front of it holds only if the bytes there chain on like records
+ * to the window's end — kmm_map_bam's tail stop turns such a guess into an error of the share in front of it.
+ * *member: the compressed offset, relative to comp, of the member that holds the offset; *skip: the offset inside it.
+ * (n_comp, 0): comp ends the file and no record starts in it (empty members, or the tail of a record that began in front).
+ * *member = -1 with KMM_OK: no chain holds — a record is longer than the window's bytes: bring a longer window.  A corrupt
+ * member: KMM_ERR_MALFORMED.  Maps nothing and leaves a stream in progress on the handle alone.  n_ref: from kmm_bam_header.
+ */
+#define KMM_FORMAT_MID_STREAM 0x200
+int kmm_bam_header(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int32_t *n_ref, int64_t *hdr_member, int64_t *hdr_skip);
+int kmm_bam_find_record_start(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int32_t n_ref, int64_t *member, int64_t *skip);
+
+/*
  * kmm_map_packed — reads the caller already holds as 2-BIT CODES (its own encoder, a .2bit-style store, the output of a
  * host-side packer): the same mapping as kmm_map_reads without the byte -> code step, and a quarter of the bytes over
  * PCIe.  This is the form the library's own host packer produces when kmm_map_reads* / kmm_map_records are handed host
@@ -499,12 +530,18 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      0; environment KMM_HOST_PACK_THREADS overrides it at index creation.
  *                      "host_packed_calls" / "host_packed_record_calls" (read-only) count the calls that took the route;
  *                      "host_pack_slice_kb": raw bytes per slice the records packer hands its threads (0 = default, 1024)
- *   "bgzf_head_skip" / "bgzf_tail_stop"  a RANK'S SHARE of a BGZF file (several processes on one file, kmm_map_bgzf): the next
+ *   "bgzf_head_skip" / "bgzf_tail_stop"  a RANK'S SHARE of a BGZF file (several processes on one file, kmm_map_bgzf; kmm_map_bam with
+ *                      KMM_FORMAT_MID_STREAM takes the head skip, every kmm_map_bam stream the tail stop): the next
  *                      call with KMM_FORMAT_NEW_STREAM passes over that many inflated bytes of its first member (they end a
  *                      record of the rank before), the next call with KMM_FORMAT_LAST_CHUNK takes only that many inflated
  *                      bytes of its last member (the rest starts the next rank's first record); each is used once
  *                      (tail: -1 = all, the default).  The boundaries are the caller's business
  *                      (kmer_mapper_amd/bgzf_ranges.py: record-structure resynchronisation on the members around a boundary)
+ *   "bam_n_ref"        n_ref of the next kmm_map_bam stream started with KMM_FORMAT_MID_STREAM (kmm_bam_header returns it): -1
+ *                      (default: not set) or 0 .. 2^31 - 1; read/write
+ *   "debug_bam_resync_kb" test hook of kmm_bam_find_record_start: inflated bytes it examines at most, in KiB — the bytes end at the
+ *                      cap as if the window did, so a small file shows the "longer window" answer and a forged chain can reach
+ *                      the end; not for callers, no effect at 0
  *   "debug_gzip_chunk_kb" test hook of kmm_map_gzip: spacing of the chunk search in KiB (0 = the default, 32; a test file of a
  *                      few MB then has hundreds of chunks).  Read-only: "gzip_calls", "gzip_members" (members whose CRC32 and
  *                      ISIZE were checked), "gzip_chunks" (speculative starts decoded, every call's first chunk included),

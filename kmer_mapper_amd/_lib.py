@@ -23,6 +23,7 @@ KMM_ERR_MALFORMED = -6
 KMM_ERR_INTERNAL = -7
 FORMAT_FASTA2, FORMAT_FASTQ = 2, 4
 FORMAT_FASTA, FORMAT_LAST_CHUNK, FORMAT_NEW_STREAM = 1, 0x100, 0x400      # multi-line FASTA (unwrapped on the GPU); flag: the chunk ends the file
+FORMAT_MID_STREAM = 0x200       # kmm_map_bam, with FORMAT_NEW_STREAM: the stream begins behind the header (a rank's share of a BAM file)
 FORMAT_SAM = 8                  # SAM text: the SEQ column extracted on the GPU (kmm_map_records / kmm_map_bgzf / kmm_map_gzip)
 
 # kernel ids of kmm_get_timing (include/kmm.h)
@@ -67,6 +68,8 @@ SIGNATURES = {
     "kmm_map_bgzf_hint_next": (_c.c_int, [_P, _P, _c.c_int64]),
     "kmm_map_gzip": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
     "kmm_map_bam": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
+    "kmm_bam_header": (_c.c_int, [_P, _P, _c.c_int64, _P, _P, _P]),
+    "kmm_bam_find_record_start": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int32, _P, _P]),
     "kmm_map_packed": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int, _c.c_int, _c.c_int]),
     "kmm_extract_kmers": (_c.c_int, [_c.c_int, _P, _P, _c.c_int64, _c.c_int, _P, _P, _c.c_int64]),
     "kmm_build_index": (_c.c_int, [_c.c_int, _P, _P, _c.c_int64, _c.c_uint64, _P, _P, _P, _P, _P]),

@@ -5,7 +5,8 @@ buffer ended, usually inside a record.  The rule is the one of reads_io.find_rec
 inflated bytes of the few members around a boundary (inflated here on the host with zlib: two or three members per
 boundary); the ranges of ranks 0..world-1 partition the file's records exactly.  Nothing here walks the whole file: a
 boundary is found from its byte position (the next member header whose chain of BSIZE fields holds), so a 100 GB file costs
-a rank what a 100 MB one does."""
+a rank what a 100 MB one does.  A BAM file's records are binary: its boundaries are judged on the GPU
+(rank_member_range_bam, at the end of the file)."""
 import struct
 import zlib
 
@@ -153,3 +154,80 @@ def rank_member_range(buf, fmt, rank, world_size):
     if (m1, s1) < (m0, s0):
         m1, s1 = m0, s0
     return m0, s0, m1, s1
+
+
+# ---- BAM: the record structure is binary, a boundary is judged on the GPU (kmm_bam_find_record_start) ----
+
+_BAM_WINDOW = 1 << 20        # compressed bytes of the first window a boundary is looked for in
+_BAM_WINDOW_MAX = 64 << 20   # ... and of the last one tried (a record longer than that: one rank)
+
+
+def _bam_header(dev, a):
+    """(n_ref, hdr_member, hdr_skip) of the BAM file in the uint8 array `a` (dev.bam_header on growing windows)."""
+    size, w = a.shape[0], _BAM_WINDOW
+    while True:
+        n_ref, member, skip = dev.bam_header(a[:min(w, size)])
+        if n_ref >= 0:
+            return n_ref, member, skip
+        if w >= size:
+            raise ValueError("the BAM file ends inside its header (%d bytes)" % size)
+        w *= 4
+
+
+def _bam_record_start(dev, a, m, n_ref):
+    """B = (member, skip) of the first record start the GPU finds at or after the member at compressed byte m: windows of
+    1 MiB (or the rest of the file), doubled while no chain of records holds in them."""
+    size, w, step = a.shape[0], _BAM_WINDOW, 0
+    cap_kb = dev.get_param("debug_bam_resync_kb")    # (the test hook caps what a call examines: it doubles with the window)
+    try:
+        while True:
+            if cap_kb:
+                dev.set_param("debug_bam_resync_kb", cap_kb << step)
+            end = min(m + w, size)
+            member, skip = dev.bam_find_record_start(a[m:end], n_ref)
+            if member >= 0:
+                return m + member, skip
+            if w >= _BAM_WINDOW_MAX or (end == size and not cap_kb):
+                raise ValueError("no chain of BAM records holds in the %d compressed bytes behind byte %d: a record longer than "
+                                 "the window, or a damaged file — map it with one rank (WORLD_SIZE=1)" % (end - m, m))
+            w *= 2
+            step += 1
+    finally:
+        if cap_kb:
+            dev.set_param("debug_bam_resync_kb", cap_kb)
+
+
+def rank_member_range_bam(dev, buf, rank, world_size):
+    """What `rank` of `world_size` maps of the BAM file in `buf` (bytes-like / mmap): (lo, head_skip, hi, tail_stop, n_ref) as
+    rank_member_range, plus the header's reference count.  dev: an engine.DeviceIndex — boundaries are judged on the GPU.
+
+    Boundary B(r) = (member, skip), a position in (compressed member offset, inflated offset inside it) order: B(0) = (0, 0),
+    B(world_size) = (size, 0); else, with m the first member at or after compressed byte size * r // world_size: the first
+    record behind the header if m lies at or before it, else what kmm_bam_find_record_start answers at m.  Rank r maps the
+    records whose first byte lies in [B(r), B(r + 1)); rank 0 starts with the header, the others behind it (mid_stream) at
+    lo's member with head_skip.  B(r) == B(r + 1) is an empty share (lo == hi, head_skip == tail_stop).  Every rank computes its
+    two boundaries itself, from the same bytes with the same function: neighbours agree by construction.  A guessed B(r) that
+    is no record start lies inside a record of rank r - 1, whose tail stop then cuts that record and fails its last call —
+    the result is exact or an error.  B(r) > B(r + 1) can only come from such a guess and is refused here."""
+    a = np.frombuffer(buf, dtype=np.uint8)
+    size = a.shape[0]
+    n_ref, hdr_member, hdr_skip = _bam_header(dev, a)
+
+    def boundary(r):
+        if r <= 0:
+            return 0, 0
+        if r >= world_size:
+            return size, 0
+        m, _ = member_at_or_after(buf, size * r // world_size)
+        if m <= hdr_member:
+            return hdr_member, hdr_skip
+        if m >= size:
+            return size, 0
+        return _bam_record_start(dev, a, m, n_ref)
+
+    (m0, s0), (m1, s1) = boundary(rank), boundary(rank + 1)
+    if (m1, s1) < (m0, s0):
+        raise ValueError("the record boundaries guessed for ranks %d and %d of the BAM file are out of order ((%d, %d) then (%d, %d)): "
+                         "one of them lies inside a record — map the file with one rank (WORLD_SIZE=1)"
+                         % (rank, rank + 1, m0, s0, m1, s1))
+    return m0, s0, m1, s1, n_ref

@@ -19,6 +19,8 @@ Differences that follow from replacing the engine (all documented in DESIGN.md):
     re-synchronised to record starts, reads_io.rank_byte_range: no rank reads or scans another rank's bytes);
     ranks sharing one .gz stream (not seekable) take chunk i mod WORLD_SIZE and cut the chunks they skip by the
     record parser's own rule (newline count, reads_io.records_cut); the count vectors are summed with one RCCL reduce; rank 0 writes the output.
+    A BAM file is shared only with `--shard-bam` (extension): each rank maps a member range whose ends it finds on the GPU
+    (bgzf_ranges.rank_member_range_bam).
   * `--ambiguous-bases skip` (extension; default `a` = the reference, N counted as A and every other letter an error): a
     k-mer that contains N or an IUPAC ambiguity letter is not counted, the windows on either side of it are
     (util.ambiguous_skip_lut, KMM_LUT_BREAK).  Such a table takes the device routes: the raw bytes of a plain file cross
@@ -171,7 +173,8 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
 
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
-                exclude_flags=0, probe=None, lut=None, min_base_quality=0, use_record_qual=False, original_strand=False):
+                exclude_flags=0, probe=None, lut=None, min_base_quality=0, use_record_qual=False, original_strand=False,
+                shard_bam=False):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
     on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
@@ -182,8 +185,10 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     use_record_qual: the handle's "use_record_qual" — the QUAL of SAM / BAM records is decoded on the GPU and the floor applied
     (DESIGN 4.12); records that store no qualities pass unmasked and are counted ("records_without_qual").
     original_strand: the handle's "original_strand", SAM / BAM alone — the kept records whose FLAG has 0x10 are mapped in read
-    orientation (SEQ reverse-complemented back, QUAL reversed: DESIGN 4.13) and counted ("records_reversed")."""
-    _check_bam_route(fmt, world_size, exclude_flags)
+    orientation (SEQ reverse-complemented back, QUAL reversed: DESIGN 4.13) and counted ("records_reversed").
+    shard_bam: several ranks on one BAM file each map their member range, its ends trimmed to record starts found on the GPU
+    (bgzf_ranges.rank_member_range_bam); without it several ranks on a BAM file are refused."""
+    _check_bam_route(fmt, world_size, exclude_flags, shard_bam=shard_bam)
     original_strand = check_original_strand(original_strand, fmt)
     use_record_qual = check_use_record_qual(use_record_qual, fmt, min_base_quality)
     min_base_quality = check_min_base_quality(min_base_quality, k, fmt, use_record_qual=use_record_qual)
@@ -300,7 +305,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         return _map_compressed_file(dev, path, route, kfmt, k, max_index_lookup_frequency,
                                     map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
                                     world_size=world_size, fmt=fmt, lut=lut, min_base_quality=min_base_quality,
-                                    use_record_qual=use_record_qual, original_strand=original_strand)
+                                    use_record_qual=use_record_qual, original_strand=original_strand, shard_bam=shard_bam)
     try:
         i = 0
         while True:
@@ -456,14 +461,17 @@ _COMPRESSED_ROUTES = {
 
 
 def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None, rank=0,
-                         world_size=1, fmt="fastq", lut=None, min_base_quality=0, use_record_qual=False, original_strand=False):
+                         world_size=1, fmt="fastq", lut=None, min_base_quality=0, use_record_qual=False, original_strand=False,
+                         shard_bam=False):
     """`kmer_mapper map -f reads.fq.gz | reads.bam` with the GPU inflater: windows of the file mapping -> kmm_map_<route>.
 
     route "gzip" (PLAIN gzip, kmm_map_gzip): each call goes on where the one before could verify a deflate block boundary.
     route "bgzf" / "bam" (kmm_map_bgzf / kmm_map_bam): each window starts at a member boundary; members are inflated and the
     records parsed (BAM: found and their SEQ decoded) on the GPU, and the handle carries the bytes behind a window's last
     complete record to the next one.  BGZF with several ranks: each maps its member range (bgzf_ranges.rank_member_range),
-    the first member's head and the last member's tail trimmed to the record boundaries the ranks agree on."""
+    the first member's head and the last member's tail trimmed to the record boundaries the ranks agree on.  BAM with several
+    ranks (shard_bam): the same, the boundaries found on the GPU (bgzf_ranges.rank_member_range_bam); the ranks behind the
+    first start their stream behind the header (mid_stream), and a rank whose share is empty makes no map call."""
     import mmap
     counters, summary = _COMPRESSED_ROUTES[route]
     n_reads = lo = size = 0
@@ -474,12 +482,23 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
             file_size = os.fstat(f.fileno()).st_size
             mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
             try:
-                lo, size, head_skip, tail_stop = 0, file_size, 0, None
-                if world_size > 1:                       # (BGZF text alone: gzip and BAM are mapped by one rank)
+                lo, size, head_skip, tail_stop, mid_stream = 0, file_size, 0, None, False
+                if world_size > 1:                       # (BGZF text, and BAM with shard_bam: gzip is mapped by one rank)
                     from . import bgzf_ranges
-                    lo, s0, hi, s1 = bgzf_ranges.rank_member_range(mm, fmt, rank, world_size)
+                    if route == "bam":
+                        t_range = time.perf_counter()
+                        lo, s0, hi, s1, n_ref = bgzf_ranges.rank_member_range_bam(dev, mm, rank, world_size)
+                        mid_stream = (lo, s0) > (0, 0)
+                        if mid_stream:
+                            dev.set_param("bam_n_ref", n_ref)
+                        logging.info("Rank %d of %d found its BAM record boundaries on the GPU in %.1f ms (n_ref %d)", rank, world_size,
+                                     (time.perf_counter() - t_range) * 1e3, n_ref)
+                    else:
+                        lo, s0, hi, s1 = bgzf_ranges.rank_member_range(mm, fmt, rank, world_size)
                     size = bgzf_ranges.member_end(mm, hi) if s1 > 0 else hi
                     head_skip, tail_stop = s0, (s1 if s1 > 0 else None)
+                    if route == "bam" and (hi, s1) <= (lo, s0):   # an empty share: no map call, the rank still joins the reduce
+                        size = lo
                     logging.info("Rank %d of %d maps the BGZF members in compressed bytes [%d, %d) of %d: %d inflated bytes of the "
                                  "first member skipped, %s of the last one taken", rank, world_size, lo, size, file_size, s0,
                                  "all" if tail_stop is None else "%d bytes" % s1)
@@ -525,7 +544,9 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
                         common = dict(first=pos == lo, last=end == size, k=k, max_index_lookup_frequency=max_freq,
                                       also_revcomp=revcomp, next_chunk=whole[end:nxt] if nxt > end else None, lut=lut)
                         if route == "bam":
-                            used, n_rec = dev.map_bam(whole[pos:end], **common)
+                            used, n_rec = dev.map_bam(whole[pos:end], mid_stream=mid_stream and pos == lo,
+                                                      head_skip=head_skip if pos == lo else 0,
+                                                      tail_stop=tail_stop if end == size else None, **common)
                             if used == 0 and end == size:
                                 raise ValueError("%s: the BAM header or the trailing bytes are no complete BGZF member" % path)
                             if used == 0 and pos == lo:  # a header longer than the window: a longer one
@@ -571,11 +592,12 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
     return node_counts
 
 
-def _check_bam_route(fmt, world_size, exclude_flags):
-    """What the BAM route does not do (yet): several ranks on one file; and the flag filter is for SAM and BAM alone."""
-    if fmt == "bam" and world_size > 1:
+def _check_bam_route(fmt, world_size, exclude_flags, shard_bam=False):
+    """What the BAM route does only when asked (shard_bam): several ranks on one file; and the flag filter is for SAM and BAM alone."""
+    if fmt == "bam" and world_size > 1 and not shard_bam:
         raise ValueError("BAM input is mapped by one rank: sharding a BAM file over %d ranks needs the ranks to resynchronise "
-                         "to its records, which is not implemented (run without torchrun, WORLD_SIZE=1)" % world_size)
+                         "to its records, which is not implemented (run without torchrun, WORLD_SIZE=1)" % world_size +
+                         "; or pass --shard-bam: the ranks then find their record boundaries on the GPU")
     if exclude_flags and fmt not in ("bam", "sam"):
         raise ValueError("--exclude-flags applies to SAM and BAM input only (the reads are %s)" % fmt)
 
@@ -635,7 +657,8 @@ def map_bnp(args):
     revcomp = bool(getattr(args, "map_reverse_complements", False))
     fmt = probe.fmt
     exclude_flags = int(getattr(args, "exclude_flags", 0) or 0)
-    _check_bam_route(fmt, world, exclude_flags)
+    shard_bam = bool(getattr(args, "shard_bam", False))
+    _check_bam_route(fmt, world, exclude_flags, shard_bam=shard_bam)
     lut = None
     if getattr(args, "ambiguous_bases", "a") == "skip":
         from .util import ambiguous_skip_lut
@@ -656,7 +679,8 @@ def map_bnp(args):
         node_counts = map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, revcomp, max_freq,
                                   device=device, rank=rank, world_size=world, before_fetch=before_fetch,
                                   n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe, lut=lut,
-                                  min_base_quality=min_q, use_record_qual=use_qual, original_strand=original_strand)
+                                  min_base_quality=min_q, use_record_qual=use_qual, original_strand=original_strand,
+                                  shard_bam=shard_bam)
     else:
         logging.info("Using the host FASTA/FASTQ parser")
         if world > 1 and not probe.inflate:
@@ -744,6 +768,10 @@ def build_argument_parser():
                                 "by the aligner) in read orientation, SEQ flipped back and QUAL reversed on the GPU, as `samtools "
                                 "fastq` writes it; with --exclude-flags 0x900 the counts are those of the FASTQ the file was made "
                                 "from. Default: SEQ as stored, as the reference.")
+    subparser.add_argument("--shard-bam", action="store_true",
+                           help="Extension, BAM input under torchrun (WORLD_SIZE > 1): every rank maps its own member range of the "
+                                "file, trimmed at both ends to record starts that the ranks find on the GPU; a boundary guessed "
+                                "wrongly is an error, never a wrong count. Default: several ranks on one BAM file are refused.")
     subparser.set_defaults(func=map_bnp)
     return parser
 

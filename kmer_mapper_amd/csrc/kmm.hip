@@ -378,6 +378,12 @@ struct kmm_index : IndexStreams, RxArrays {
     int32_t bam_n_ref = -1;       // -1: no BAM stream started on this handle
     uint32_t bam_excl = 0;        // "bam_exclude_flags": records with flag & mask are not mapped (samtools view -F)
     int64_t bam_calls = 0, bam_records = 0, bam_excluded = 0, bam_header_bytes = 0, bam_false_starts = 0, bam_continuations = 0;
+    // kmm_bam_header / kmm_bam_find_record_start (a rank's share of a BAM file): buffers of their own — the compressed
+    // window, its inflated bytes, the member offsets, the inflater's error words and status bytes — so that a stream in
+    // progress on the handle is not touched
+    DevBuf rs_comp, rs_raw, rs_meta, rs_err, rs_status;
+    int64_t bam_n_ref_param = -1;     // "bam_n_ref": n_ref of a KMM_FORMAT_MID_STREAM stream (-1: not set)
+    int64_t dbg_bam_resync_kb = 0;    // test hook ("debug_bam_resync_kb"): inflated bytes kmm_bam_find_record_start examines at most, KiB (0: all)
     int64_t dbg_bgzf_call_cap_kb = 0; // test hook ("debug_bgzf_call_cap_kb"): inflated bytes a kmm_map_bgzf / kmm_map_bam call
                                       // takes at most, KiB (0: 3.5 GiB)
     int64_t flat_uniform_batches = 0; // flat reads mapped by the uniform / packed front ends of the radix path (rec_launch_flat)
@@ -2780,6 +2786,7 @@ struct StreamCall {
     int64_t *consumed_comp, *n_records;
     int fmt = 0; // the format without the stream flags (stream_call_start)
     bool new_stream = false, last_chunk = false;
+    bool mid_stream = false; // KMM_FORMAT_MID_STREAM (kmm_map_bam): the stream begins behind the header, at "bgzf_head_skip"
 };
 
 // text: FASTQ, two-line FASTA or SAM (else BAM: the flags alone); chain: a BGZF member chain is walked in the caller's bytes
@@ -2792,9 +2799,18 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
     c.last_chunk = (format & KMM_FORMAT_LAST_CHUNK) != 0;
     c.new_stream = (format & KMM_FORMAT_NEW_STREAM) != 0;
     c.fmt = format & ~(KMM_FORMAT_LAST_CHUNK | KMM_FORMAT_NEW_STREAM);
+    if (!text && (c.fmt & KMM_FORMAT_MID_STREAM)) { // (a text format keeps the bit and is refused below)
+        c.mid_stream = true;
+        c.fmt &= ~KMM_FORMAT_MID_STREAM;
+    }
     if (text ? c.fmt != KMM_FORMAT_FASTQ && c.fmt != KMM_FORMAT_FASTA2 && c.fmt != KMM_FORMAT_SAM : c.fmt != 0)
         return fail(KMM_ERR_INVALID_ARG, text ? "%s: format must be KMM_FORMAT_FASTQ (4), KMM_FORMAT_FASTA2 (2) or KMM_FORMAT_SAM (8)"
-                                              : "%s: flags take KMM_FORMAT_NEW_STREAM and KMM_FORMAT_LAST_CHUNK only", c.who);
+                                              : "%s: flags take KMM_FORMAT_NEW_STREAM, KMM_FORMAT_LAST_CHUNK and KMM_FORMAT_MID_STREAM only", c.who);
+    if (c.mid_stream && !c.new_stream)
+        return fail(KMM_ERR_INVALID_ARG, "%s: KMM_FORMAT_MID_STREAM goes with KMM_FORMAT_NEW_STREAM, on a stream's first call", c.who);
+    if (c.mid_stream && ix->bam_n_ref_param < 0)
+        return fail(KMM_ERR_INVALID_ARG, "%s: KMM_FORMAT_MID_STREAM needs \"bam_n_ref\" (kmm_set_param): a stream that begins behind "
+                                         "the header does not say how many references the file has", c.who);
     KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
@@ -2869,6 +2885,7 @@ struct BgzfCall {
     int cur = 0;
     uint8_t *d_raw = nullptr;
     int64_t head = 0, n_raw = 0;
+    int64_t tail_stop = -1; // >= 0: "bgzf_tail_stop" cut the last member there (bgzf_rank_share)
     uint8_t last_byte = 10; // d_raw[n_raw - 1] on LAST_CHUNK
     uint32_t n_members = 0;
     bool from_pre = false;
@@ -3045,7 +3062,7 @@ static int bgzf_finish(kmm_index_t *ix, const StreamCall &c, const BgzfCall &b, 
     return KMM_OK;
 }
 
-// A RANK'S SHARE of a file (kmer_mapper map with several ranks, bgzf_ranges.py): its first member starts inside a record
+// A RANK'S SHARE of a file (kmer_mapper map with several ranks, bgzf_ranges.py; kmm_map_bgzf and kmm_map_bam): its first member starts inside a record
 // that belongs to the rank before it — "bgzf_head_skip" bytes of the stream's first member are passed over — and its last
 // member holds the start of the next rank's first record — only "bgzf_tail_stop" bytes of the last member are taken.
 static int bgzf_rank_share(kmm_index_t *ix, const StreamCall &c, BgzfCall &b)
@@ -3059,15 +3076,16 @@ static int bgzf_rank_share(kmm_index_t *ix, const StreamCall &c, BgzfCall &b)
     if (c.last_chunk && ix->bgzf_tail_stop >= 0) {
         if (n_members == 0 || (unsigned long long)ix->bgzf_tail_stop > o_off[n_members] - o_off[n_members - 1]) {
             (void)hipStreamSynchronize(ix->stream);
-            return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf: bgzf_tail_stop %lld lies beyond the last member's %llu bytes",
+            return fail(KMM_ERR_INVALID_ARG, "%s: bgzf_tail_stop %lld lies beyond the last member's %llu bytes", c.who,
                         (long long)ix->bgzf_tail_stop, n_members ? o_off[n_members] - o_off[n_members - 1] : 0ull);
         }
         b.n_raw = (int64_t)o_off[n_members - 1] + ix->bgzf_tail_stop;
+        b.tail_stop = ix->bgzf_tail_stop;
         ix->bgzf_tail_stop = -1;
     }
     if (b.head > b.n_raw) {
         (void)hipStreamSynchronize(ix->stream);
-        return fail(KMM_ERR_INVALID_ARG, "kmm_map_bgzf: bgzf_head_skip %lld lies beyond the %lld bytes of the call", (long long)b.head,
+        return fail(KMM_ERR_INVALID_ARG, "%s: bgzf_head_skip %lld lies beyond the %lld bytes of the call", c.who, (long long)b.head,
                     (long long)b.n_raw);
     }
     return KMM_OK;
@@ -3181,12 +3199,18 @@ struct BamGpuBackend {
 // The inflated bytes of a kmm_map_bam call (d_raw[0, n_raw): the carry of the call before in front): the header on a stream's
 // first call, then the records up to the last complete one (*used), decoded into two-line FASTA in HBM and mapped by
 // kmm_map_records.  *short_header: a first window that ends inside the header (nothing is used).
-static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw, int64_t n_raw, int64_t *used, bool *short_header)
+static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw, int64_t head, int64_t tail_stop, int64_t n_raw,
+                            int64_t *used, bool *short_header)
 {
     *used = 0;
     *short_header = false;
     uint64_t start0 = 0;
-    if (c.new_stream) {
+    if (c.mid_stream) {
+        // a rank's share: no header — n_ref is the caller's ("bam_n_ref"), the first record starts `head` bytes
+        // into the stream's first member ("bgzf_head_skip"), where kmm_bam_find_record_start found it
+        ix->bam_n_ref = (int32_t)ix->bam_n_ref_param;
+        start0 = (uint64_t)head;
+    } else if (c.new_stream) {
         // the header (magic, l_text, text, n_ref, the references) is read back in growing prefixes: its length is only known by
         // walking it, and it is read once per stream
         ix->bam_n_ref = -1;
@@ -3226,6 +3250,11 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     if (co.err_pos != kmm_bam::NONE)
         return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the record at inflated byte %llu of the call does not fit its block_size (or its "
                     "refID / next_refID / read_name are not a record's)", co.err_pos);
+    if (c.last_chunk && co.consumed != (uint64_t)n_raw && tail_stop >= 0)
+        return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside a record (%lld bytes behind the last complete one): "
+                    "\"bgzf_tail_stop\" cut the last member after %lld inflated bytes, which is no record boundary (a share boundary "
+                    "guessed by kmm_bam_find_record_start lay inside a record: map the file with one rank)",
+                    (long long)(n_raw - (int64_t)co.consumed), (long long)tail_stop);
     if (c.last_chunk && co.consumed != (uint64_t)n_raw)
         return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside a record (%lld bytes behind the last complete one)",
                     (long long)(n_raw - (int64_t)co.consumed));
@@ -3256,12 +3285,12 @@ int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags,
     return guarded(c.who, [&] {
         KMMCHK(stream_call_start(ix, c, comp, n_comp, flags, false, true));
         BgzfCall b;
-        KMMCHK(bgzf_inflate(ix, c, comp, n_comp, b, nullptr));
+        KMMCHK(bgzf_inflate(ix, c, comp, n_comp, b, bgzf_rank_share));
         if (!b.d_raw)
             return KMM_OK;
         int64_t used = 0;
         bool short_header = false;
-        const int rc = bam_map_inflated(ix, c, b.d_raw, b.n_raw, &used, &short_header);
+        const int rc = bam_map_inflated(ix, c, b.d_raw, b.head, b.tail_stop, b.n_raw, &used, &short_header);
         if (rc != KMM_OK || short_header) { // (an error, or a first window that ends inside the header: nothing used, nothing kept)
             ix->bgzf_carry_len = 0;
             ix->bgzf_pre_valid = false;
@@ -3272,6 +3301,181 @@ int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags,
             return rc;
         }
         return bgzf_finish(ix, c, b, used);
+    });
+}
+
+// ---- kmm_bam_header, kmm_bam_find_record_start: where a rank's share of a BAM file begins.  Both inflate whole
+// members of the caller's window into buffers of their own (rs_*) on the handle's stream and leave its stream state alone.
+
+// The chain of whole members at the head of comp[0, n_comp): m_off / o_off as k_inflate_bgzf takes them, p = where it ends.
+struct RsChain {
+    std::vector<unsigned long long> m_off{0ull}, o_off{0ull};
+    uint64_t p = 0;
+    uint32_t n_members() const { return (uint32_t)(m_off.size() - 1); }
+};
+
+// Walks the chain on from c.p until it holds at least out_want inflated bytes, or to the last whole member of the window (an
+// incomplete one ends the chain: the caller brings it again in a longer window).
+static int rs_scan(const char *who, const uint8_t *comp, int64_t n_comp, unsigned long long out_want, RsChain &c)
+{
+    const uint64_t limit = (uint64_t)n_comp;
+    while (c.o_off.back() < out_want && c.p + 18 <= limit && c.m_off.size() < 0x7FFFFFFFu) {
+        const uint64_t p = c.p;
+        const uint32_t ms = kmm_gz::bgzf_member_size(comp + p, limit - p);
+        if (!ms) {
+            const uint32_t xlen = (uint32_t)comp[p + 10] | ((uint32_t)comp[p + 11] << 8);
+            if (comp[p] == 0x1f && comp[p + 1] == 0x8b && comp[p + 2] == 8 && (comp[p + 3] & 4) && p + 12 + xlen + 8 > limit)
+                break; // (a header that runs past the window)
+            return fail(KMM_ERR_MALFORMED, "%s: no BGZF member at compressed byte %llu of the window", who, (unsigned long long)p);
+        }
+        if (p + ms > limit)
+            break;
+        const uint32_t isize = kmm_gz::rd32(comp + p + ms - 4);
+        if ((uint64_t)isize > (uint64_t)ms * 1032ull + 64ull)
+            return fail(KMM_ERR_MALFORMED, "%s: member at compressed byte %llu claims %u inflated bytes for %u compressed ones", who,
+                        (unsigned long long)p, isize, ms);
+        c.p = p + ms;
+        c.m_off.push_back(c.p);
+        c.o_off.push_back(c.o_off.back() + isize);
+    }
+    return KMM_OK;
+}
+
+// Inflates the chain's members into rs_raw and checks their CRC32s (k_inflate_bgzf, k_crc_bgzf, as bgzf_inflate launches
+// them); synchronises.  A corrupt member is KMM_ERR_MALFORMED.
+static int rs_inflate(kmm_index_t *ix, const char *who, const uint8_t *comp, const RsChain &c)
+{
+    const uint32_t n_members = c.n_members();
+    KMMCHK(ensure(ix->rs_comp, (size_t)c.p + 64));
+    KMMCHK(ensure(ix->rs_raw, (size_t)c.o_off.back() + 4096));
+    KMMCHK(ensure(ix->rs_meta, (size_t)(n_members + 1) * 16 + 64));
+    KMMCHK(ensure(ix->rs_err, 64));
+    KMMCHK(ensure(ix->rs_status, (size_t)n_members + 64));
+    KMMCHK(ensure_crc_tables(ix));
+    const uint32_t grid_threads = ((n_members < 65536u ? n_members : 65536u) + 63u) / 64u * 64u;
+    KMMCHK(ensure(ix->bgzf_tabs, (size_t)grid_threads * kmm_gz::SCRATCH_BYTES)); // (scratch of the inflater: the stream orders its users)
+    uint8_t *d_comp = (uint8_t *)ix->rs_comp.p, *d_raw = (uint8_t *)ix->rs_raw.p;
+    unsigned long long *d_moff = (unsigned long long *)ix->rs_meta.p, *d_ooff = d_moff + (n_members + 1);
+    const unsigned int err0[4] = {0u, 0xFFFFFFFFu, 0u, 0u};
+    HIPCHK(hipMemcpyAsync(d_comp, comp, (size_t)c.p, hipMemcpyHostToDevice, ix->stream));
+    HIPCHK(hipMemcpyAsync(d_moff, c.m_off.data(), (size_t)(n_members + 1) * 8, hipMemcpyHostToDevice, ix->stream));
+    HIPCHK(hipMemcpyAsync(d_ooff, c.o_off.data(), (size_t)(n_members + 1) * 8, hipMemcpyHostToDevice, ix->stream));
+    HIPCHK(hipMemcpyAsync(ix->rs_err.p, err0, sizeof err0, hipMemcpyHostToDevice, ix->stream));
+    HIPCHK(hipMemsetAsync(ix->rs_status.p, 0, n_members, ix->stream));
+    hipLaunchKernelGGL(kmm_gz::k_inflate_bgzf, dim3(grid_threads / 64u), dim3(64), 0, ix->stream, d_comp, d_moff, d_ooff, d_raw, n_members,
+                       (uint8_t *)ix->bgzf_tabs.p, (const uint32_t *)nullptr, (unsigned int *)ix->rs_err.p, (unsigned long long *)nullptr,
+                       (uint8_t *)ix->rs_status.p);
+    hipLaunchKernelGGL(kmm_gz::k_crc_bgzf, dim3((n_members + 63u) / 64u), dim3(256), 0, ix->stream, d_comp, d_moff, d_ooff,
+                       (const uint8_t *)d_raw, n_members, (const uint32_t *)ix->bgzf_crc.p, (unsigned int *)ix->rs_err.p,
+                       (const uint8_t *)ix->rs_status.p);
+    HIPCHK(hipGetLastError());
+    unsigned int err[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(err, ix->rs_err.p, sizeof err, hipMemcpyDeviceToHost, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    if (err[0])
+        return fail(KMM_ERR_MALFORMED, "%s: %u corrupt BGZF member(s); the first starts at compressed byte %llu of the window (inflater code %u)",
+                    who, err[0], err[1] < n_members ? c.m_off[err[1]] : 0ull, err[2]);
+    return KMM_OK;
+}
+
+static int rs_args(kmm_index_t *ix, const char *who, const uint8_t *comp, int64_t n_comp)
+{
+    if (!ix)
+        return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    if (n_comp < 0 || (n_comp > 0 && !comp))
+        return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
+    if (n_comp > 0 && is_device_ptr(comp))
+        return fail(KMM_ERR_INVALID_ARG, "%s takes the compressed bytes from host memory (the member chain is read there)", who);
+    HIPCHK(hipSetDevice(ix->device));
+    return KMM_OK;
+}
+
+int kmm_bam_header(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int32_t *n_ref, int64_t *hdr_member, int64_t *hdr_skip)
+{
+    const char *who = "kmm_bam_header";
+    return guarded(who, [&] {
+        KMMCHK(rs_args(ix, who, comp, n_comp));
+        if (!n_ref || !hdr_member || !hdr_skip)
+            return fail(KMM_ERR_INVALID_ARG, "%s: n_ref, hdr_member or hdr_skip is NULL", who);
+        *n_ref = -1;
+        *hdr_member = *hdr_skip = 0;
+        // growing prefixes of the window's members are inflated and read back: the header's length is only known by walking it
+        RsChain c;
+        std::vector<uint8_t> h;
+        uint64_t hdr_end = 0;
+        for (unsigned long long want = 1ull << 16;; want *= 4) {
+            const uint64_t p_before = c.p;
+            KMMCHK(rs_scan(who, comp, n_comp, want, c));
+            if (c.p != p_before)
+                KMMCHK(rs_inflate(ix, who, comp, c));
+            h.resize((size_t)c.o_off.back());
+            if (!h.empty()) {
+                HIPCHK(hipMemcpyAsync(h.data(), ix->rs_raw.p, h.size(), hipMemcpyDeviceToHost, ix->stream));
+                HIPCHK(hipStreamSynchronize(ix->stream));
+            }
+            int32_t nr = 0;
+            const int r = h.empty() ? 1 : kmm_bam::parse_header(h.data(), h.size(), &hdr_end, &nr);
+            if (r < 0)
+                return fail(KMM_ERR_MALFORMED, "%s: the file does not start with a BAM header (magic \"BAM\\1\", lengths)", who);
+            if (r == 0) {
+                *n_ref = nr;
+                break;
+            }
+            if (c.o_off.back() < want) // (the window's whole members are all in: it ends inside the header)
+                return KMM_OK;
+        }
+        // the first byte behind the header: in the member that holds it — behind the inflated prefix, the next member that
+        // holds a byte at all (the chain goes on over empty members; at the window's end: there, skip 0)
+        while (hdr_end >= c.o_off.back()) {
+            const uint64_t p_before = c.p;
+            KMMCHK(rs_scan(who, comp, n_comp, c.o_off.back() + 1, c));
+            if (c.p == p_before)
+                break;
+        }
+        kmm_bam::locate(c.m_off.data(), c.o_off.data(), c.n_members(), hdr_end, hdr_member, hdr_skip);
+        return KMM_OK;
+    });
+}
+
+int kmm_bam_find_record_start(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int32_t n_ref, int64_t *member, int64_t *skip)
+{
+    const char *who = "kmm_bam_find_record_start";
+    return guarded(who, [&] {
+        KMMCHK(rs_args(ix, who, comp, n_comp));
+        if (!member || !skip)
+            return fail(KMM_ERR_INVALID_ARG, "%s: member or skip is NULL", who);
+        if (n_ref < 0)
+            return fail(KMM_ERR_INVALID_ARG, "%s: n_ref negative (kmm_bam_header returns it)", who);
+        *member = -1;
+        *skip = 0;
+        const auto t_0 = std::chrono::steady_clock::now();
+        // ("debug_bam_resync_kb": the examined bytes end at the cap, as if the window did)
+        const unsigned long long cap = ix->dbg_bam_resync_kb > 0 ? (unsigned long long)ix->dbg_bam_resync_kb << 10 : ~0ull;
+        RsChain c;
+        KMMCHK(rs_scan(who, comp, n_comp, cap, c));
+        bool at_eof = false;
+        const uint64_t n = kmm_bam::resync_extent(c.o_off.back(), ix->dbg_bam_resync_kb > 0 ? cap : 0, c.p == (uint64_t)n_comp, &at_eof);
+        if (n == 0) { // (no whole member, or only empty ones)
+            kmm_bam::resync_answer(c.m_off.data(), c.o_off.data(), c.n_members(), kmm_bam::NONE, at_eof, member, skip);
+            return KMM_OK;
+        }
+        KMMCHK(rs_inflate(ix, who, comp, c));
+        const double ms_inflate = ms_since(t_0);
+        unsigned long long *d_best = (unsigned long long *)((uint8_t *)ix->rs_err.p + 32), best = kmm_bam::NONE;
+        const uint64_t n_tiles = (n + kmm_bam::TILE - 1) / kmm_bam::TILE;
+        HIPCHK(hipMemsetAsync(d_best, 0xFF, 8, ix->stream));
+        hipLaunchKernelGGL(kmm_bam::k_bam_resync, dim3((unsigned)grid_for(ix, (int64_t)((n_tiles + 3) / 4), 16)), dim3(256), 0, ix->stream,
+                           (const uint8_t *)ix->rs_raw.p, n, n_tiles, n_ref, at_eof ? 1u : 0u, d_best);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&best, d_best, 8, hipMemcpyDeviceToHost, ix->stream));
+        HIPCHK(hipStreamSynchronize(ix->stream));
+        static const bool verbose = getenv("KMM_VERBOSE") != nullptr;
+        if (verbose)
+            fprintf(stderr, "libkmm: %s: %u members, %lld -> %llu bytes examined%s: copy + inflate + CRC %.2f ms, resync kernel %.2f ms\n", who,
+                    c.n_members(), (long long)c.p, (unsigned long long)n, at_eof ? " (to the end of the file)" : "", ms_inflate,
+                    ms_since(t_0) - ms_inflate);
+        kmm_bam::resync_answer(c.m_off.data(), c.o_off.data(), c.n_members(), best, at_eof, member, skip);
+        return KMM_OK;
     });
 }
 
@@ -4022,6 +4226,16 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value < 0 || value > 0xFFFF)
             return fail(KMM_ERR_INVALID_ARG, "bam_exclude_flags outside [0, 0xFFFF]");
         ix->bam_excl = (uint32_t)value;
+    } else if (!strcmp(name, "bam_n_ref")) {
+        // n_ref of the next KMM_FORMAT_MID_STREAM stream of kmm_map_bam (kmm_bam_header returns it); -1 = not set
+        if (value < -1 || value > 0x7FFFFFFFll)
+            return fail(KMM_ERR_INVALID_ARG, "bam_n_ref outside [-1, 2^31)");
+        ix->bam_n_ref_param = value;
+    } else if (!strcmp(name, "debug_bam_resync_kb")) {
+        // test hook of kmm_bam_find_record_start: inflated bytes it examines at most, KiB (0 = all the window's whole members)
+        if (value < 0 || value > (1ll << 32))
+            return fail(KMM_ERR_INVALID_ARG, "debug_bam_resync_kb outside [0, 2^32]");
+        ix->dbg_bam_resync_kb = value;
     } else if (!strcmp(name, "debug_bgzf_call_cap_kb")) {
         // test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, KiB (0 = the default, 3.5 GiB)
         if (value < 0 || value > (7ll << 19))
@@ -4140,6 +4354,10 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->sam_header_lines;
     else if (!strcmp(name, "debug_bgzf_call_cap_kb"))
         *value = ix->dbg_bgzf_call_cap_kb;
+    else if (!strcmp(name, "bam_n_ref"))
+        *value = ix->bam_n_ref_param;
+    else if (!strcmp(name, "debug_bam_resync_kb"))
+        *value = ix->dbg_bam_resync_kb;
     else if (!strcmp(name, "flat_uniform_batches")) // flat reads of one length mapped by the uniform / packed front ends
         *value = ix->flat_uniform_batches;
     else if (!strcmp(name, "bgzf_members")) // BGZF members inflated on the GPU by kmm_map_bgzf

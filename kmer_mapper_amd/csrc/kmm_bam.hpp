@@ -24,6 +24,9 @@
 // "original_strand"  has decode write the kept records whose FLAG has 0x10 in read orientation: SEQ reversed and
 // complemented, QUAL reversed.  The output lengths are the same: spec, link and totals do not know of the switch.
 // Exactness never depends on the plausibility test: a wrong guess only costs a fix.  Every read is bounds-checked against n.
+// resync (kmm_bam_find_record_start) is the other use of the plausibility test: in inflated bytes that begin anywhere
+// in the stream — a rank's share of a file — k_bam_resync finds the lowest position from which the chain of records holds to the
+// end of the bytes.  There a wrong guess is caught by the share in front of it, whose last record it cuts.
 #pragma once
 
 #include <cstdint>
@@ -243,6 +246,89 @@ KMM_BAM_HD uint64_t fix_tile(const uint8_t *d, uint64_t n, uint64_t t, uint64_t 
     o.entry = prev;
     o.exit = w.exit;
     return NONE;
+}
+
+// ---- resync (kmm_bam_find_record_start): where does the first record start in inflated bytes d[0, n) that begin
+// somewhere in the stream?  The smallest position from which the chain of records holds to the end of d.
+
+// Does the chain from p hold?  Every record is REC_OK until one is REC_SHORT at the end of the bytes, at least one is whole,
+// and at the end of the file (at_eof) the chain ends exactly at n.  A true record start always holds.
+KMM_BAM_HD bool chain_holds(const uint8_t *d, uint64_t n, uint64_t p, int32_t n_ref, bool at_eof)
+{
+    bool whole = false;
+    for (;;) { // (p grows by at least 36 per round)
+        RecHead h;
+        const int r = record_at(d, n, p, n_ref, h);
+        if (r == REC_BAD)
+            return false;
+        if (r == REC_SHORT)
+            return whole && (!at_eof || p == n);
+        whole = true;
+        p += 4ull + h.bs;
+    }
+}
+
+// resync, one tile (scalar form: the kernel tests 64 positions at a time, with the same `plausible` — which every holding
+// position passes — and walks the survivors in ascending order): the tile's lowest holding position, or NONE
+inline uint64_t resync_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, int32_t n_ref, bool at_eof)
+{
+    for (uint64_t c = t * TILE, e = tile_end(t, n); c < e; ++c)
+        if (plausible(d, n, c, n_ref) && chain_holds(d, n, c, n_ref, at_eof))
+            return c;
+    return NONE;
+}
+
+// resync, all tiles (the CPU form of k_bam_resync): the lowest holding position of d[0, n), or NONE
+inline uint64_t resync_scalar(const uint8_t *d, uint64_t n, int32_t n_ref, bool at_eof)
+{
+    for (uint64_t t = 0, n_tiles = (n + TILE - 1) / TILE; t < n_tiles; ++t) {
+        const uint64_t p = resync_tile_scalar(d, n, t, n_ref, at_eof);
+        if (p != NONE)
+            return p;
+    }
+    return NONE;
+}
+
+// The inflated position p as (member, offset inside it): the member that HOLDS byte p, i.e. the first one that ends behind p
+// (empty members hold nothing).  m_off / o_off: where the n_members members start in the compressed / inflated bytes
+// (n_members + 1 entries each).  p at or behind the last member's end: (m_off[n_members], 0).
+inline void locate(const unsigned long long *m_off, const unsigned long long *o_off, uint64_t n_members, uint64_t p, int64_t *member,
+                   int64_t *skip)
+{
+    uint64_t lo = 0, hi = n_members; // the first j with o_off[j + 1] > p
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) / 2;
+        if (o_off[mid + 1] > p)
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    *member = (int64_t)m_off[lo];
+    *skip = lo < n_members ? (int64_t)(p - o_off[lo]) : 0;
+}
+
+// The bytes a resync examines of a window whose whole members inflate to n_total bytes: all of them, or `cap` (the test hook;
+// 0: none).  *at_eof: the window's whole members end where the window does (whole) and every byte is examined — the caller
+// brought the rest of the file.
+inline uint64_t resync_extent(uint64_t n_total, uint64_t cap, bool whole, bool *at_eof)
+{
+    const uint64_t n = cap && cap < n_total ? cap : n_total;
+    *at_eof = whole && n == n_total;
+    return n;
+}
+
+// What kmm_bam_find_record_start answers: `best` = the lowest holding position (NONE: no chain holds) as (member, skip); at the
+// end of the file, with no record start in the bytes, (m_off[n_members], 0) — they end a record that began in front of them,
+// or are empty; else member -1: a longer window is needed.
+inline void resync_answer(const unsigned long long *m_off, const unsigned long long *o_off, uint64_t n_members, uint64_t best, bool at_eof,
+                          int64_t *member, int64_t *skip)
+{
+    *member = -1;
+    *skip = 0;
+    if (best != NONE)
+        locate(m_off, o_off, n_members, best, member, skip);
+    else if (at_eof)
+        *member = (int64_t)m_off[n_members];
 }
 
 // "=ACMGRSVTWYHKDBN": the letters of the 4-bit base codes (SAM/BAM specification 4.2.3)
@@ -822,6 +908,35 @@ __global__ void __launch_bounds__(256) k_bam_decode_q_rev(const uint8_t *__restr
                                                           unsigned long long *__restrict__ reversed)
 {
     bam_decode_rev_tiles<true>(d, n, n_tiles, n_ref, excl, in, base, out, no_qual, reversed);
+}
+
+// resync: one wavefront per tile (grid-stride), the shape of spec; lanes test 64 consecutive positions, the survivors are
+// walked to the end of the bytes in ascending order — the same walk in every lane: the position comes from a ballot, so the
+// loads are one address per wavefront and nothing diverges — and the tile's lowest holding position goes to *best (a 64-bit
+// minimum, NONE before the launch).  A wavefront stops where a lower position is known to hold.  No scratch: a claim is a word.
+__global__ void __launch_bounds__(256) k_bam_resync(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                    uint32_t at_eof, unsigned long long *__restrict__ best)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        uint64_t found = NONE;
+        for (uint64_t c0 = t * TILE, e = tile_end(t, n); c0 < e && found == NONE; c0 += 64u) {
+            // (a lower position holds already: nothing from here on can be the minimum; the ballot keeps the wavefront together)
+            if (__ballot(__hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= c0))
+                break;
+            const uint64_t c = c0 + lane;
+            unsigned long long m = __ballot(c < e && plausible(d, n, c, n_ref));
+            while (m && found == NONE) {
+                const uint64_t s = c0 + (uint64_t)(__ffsll((long long)m) - 1);
+                m &= m - 1;
+                if (chain_holds(d, n, s, n_ref, at_eof != 0u))
+                    found = s;
+            }
+        }
+        if (found != NONE && lane == 0)
+            atomicMin(best, (unsigned long long)found);
+    }
 }
 #endif
 

@@ -244,14 +244,14 @@ class DeviceIndex:
             nx = _Arg(next_chunk, np.uint8, "next_chunk")
             _lib.check(_lib.lib().kmm_map_bgzf_hint_next(self._h, nx.ptr, nx.n))
 
-    def _map_stream(self, entry, comp, n_bytes, fmt, first, last, k, max_index_lookup_frequency, also_revcomp, lut):
+    def _map_stream(self, entry, comp, n_bytes, fmt, first, last, k, max_index_lookup_frequency, also_revcomp, lut, more_flags=0):
         """One call of a compressed stream's entry point (kmm_map_bgzf / kmm_map_gzip / kmm_map_bam): (used, n_records)."""
         b = _Arg(comp, np.uint8, "comp")
         t = _Arg(lut, np.uint8, "lut")
         n = _n_bytes(b, n_bytes)
         used = ctypes.c_int64(0)
         n_rec = ctypes.c_int64(0)
-        flags = (_lib.FORMAT_NEW_STREAM if first else 0) | (_lib.FORMAT_LAST_CHUNK if last else 0)
+        flags = (_lib.FORMAT_NEW_STREAM if first else 0) | (_lib.FORMAT_LAST_CHUNK if last else 0) | more_flags
         _lib.check(getattr(_lib.lib(), entry)(self._h, b.ptr, n, int(fmt) | flags, int(k), int(max_index_lookup_frequency),
                                               int(bool(also_revcomp)), t.ptr, ctypes.byref(used), ctypes.byref(n_rec)))
         return used.value, n_rec.value
@@ -280,14 +280,45 @@ class DeviceIndex:
         return self._map_stream("kmm_map_gzip", comp, n_bytes, fmt, first, last, k, max_index_lookup_frequency, also_revcomp, lut)
 
     def map_bam(self, comp, first, last, next_chunk=None, n_bytes=None, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
-                lut=None):
+                lut=None, mid_stream=False, head_skip=0, tail_stop=None):
         """Map a window of a BAM file (kmm_map_bam): BGZF members inflated, records found and their SEQ decoded on the GPU.
         `comp` starts at a member boundary; returns (compressed bytes used, records mapped): continue at comp[used:].  first /
         last mark the file's first / last window (the header is read on the first; a first window that ends inside the header
         uses nothing: bring a longer one).  next_chunk: the bytes that follow `comp` in the caller's memory, staged under this
-        window's inflate kernel (as map_bgzf)."""
+        window's inflate kernel (as map_bgzf).
+        A rank's share of a file (bgzf_ranges.rank_member_range_bam): mid_stream = the stream begins behind the header — its
+        first call (first=True) expects no header, takes n_ref from set_param("bam_n_ref", ...) and starts at the record
+        head_skip inflated bytes into the first member; tail_stop = how many inflated bytes of the LAST window's last member
+        are this rank's (None: all).  Both are written on every first / last call, so a stream that failed leaves no stale
+        value for the next file."""
         self._hint_next(next_chunk)
-        return self._map_stream("kmm_map_bam", comp, n_bytes, 0, first, last, k, max_index_lookup_frequency, also_revcomp, lut)
+        if first:
+            self.set_param("bgzf_head_skip", int(head_skip))
+        if last:
+            self.set_param("bgzf_tail_stop", -1 if tail_stop is None else int(tail_stop))
+        return self._map_stream("kmm_map_bam", comp, n_bytes, 0, first, last, k, max_index_lookup_frequency, also_revcomp, lut,
+                                more_flags=_lib.FORMAT_MID_STREAM if mid_stream else 0)
+
+    def bam_header(self, comp, n_bytes=None):
+        """kmm_bam_header: `comp` starts at a BAM file's first member.  Returns (n_ref, hdr_member, hdr_skip): the reference count
+        and where the first record lies (compressed offset of its member, offset in the member's inflated bytes); n_ref = -1:
+        the window ends inside the header — bring a longer one."""
+        b = _Arg(comp, np.uint8, "comp")
+        n_ref, member, skip = ctypes.c_int32(-1), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.lib().kmm_bam_header(self._h, b.ptr, _n_bytes(b, n_bytes), ctypes.byref(n_ref), ctypes.byref(member),
+                                             ctypes.byref(skip)))
+        return n_ref.value, member.value, skip.value
+
+    def bam_find_record_start(self, comp, n_ref, n_bytes=None):
+        """kmm_bam_find_record_start: `comp` starts at a member boundary of a BAM file with n_ref references.  Returns
+        (member, skip): the first position from which a chain of records holds to the end of the window's whole members, as
+        the compressed offset (relative to comp) of the member that holds it and the offset in that member's inflated bytes;
+        (len, 0): comp ends the file and no record starts in it; member = -1: no chain holds — bring a longer window."""
+        b = _Arg(comp, np.uint8, "comp")
+        member, skip = ctypes.c_int64(-1), ctypes.c_int64(0)
+        _lib.check(_lib.lib().kmm_bam_find_record_start(self._h, b.ptr, _n_bytes(b, n_bytes), int(n_ref), ctypes.byref(member),
+                                                        ctypes.byref(skip)))
+        return member.value, skip.value
 
     def map_packed(self, codes, n_bases, n_reads, read_len=0, read_starts=None, k=31, max_index_lookup_frequency=1000,
                    also_revcomp=False):
