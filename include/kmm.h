@@ -252,7 +252,9 @@ int kmm_map_reads_qual(kmm_index_t *idx, const uint8_t *bases, const uint8_t *qu
  *     whose FLAG has 0x10 is then reverse-complemented back letter by letter, its QUAL reversed — through the same lookup
  *     table as every other entry point (lut NULL: ACGT -> 0123, N -> A): "=" and the IUPAC codes are
  *     KMM_ERR_INVALID_BASE at the next synchronising call; optional fields behind QUAL are ignored.  SEQ "*" is a read without k-mers that counts in *n_records (as l_seq = 0 in BAM);
- *   - "bam_exclude_flags" (kmm_set_param) leaves out records with FLAG & mask;
+ *   - "bam_exclude_flags" (kmm_set_param) leaves out records with FLAG & mask; "bam_include_flags", "bam_min_mapq" and
+ *     kmm_set_record_regions select further (RECORD SELECTION below: FLAG, MAPQ, RNAME, POS and CIGAR, fields 2 to 6, are read
+ *     on the GPU, each only while a rule needs it; a needed field that is malformed is one more KMM_ERR_MALFORMED of the list);
  *   - *consumed = the byte after the chunk's last '\n' (a record never spans a newline); '\r' before '\n' is tolerated;
  *   - refused with KMM_ERR_MALFORMED, nothing of the call mapped, the message naming the first bad line's byte offset: a
  *     record line with fewer than 10 TABs, a FLAG that is no decimal integer in [0, 65535], an empty line;
@@ -380,6 +382,52 @@ int kmm_map_bam(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int flags
 #define KMM_FORMAT_MID_STREAM 0x200
 int kmm_bam_header(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int32_t *n_ref, int64_t *hdr_member, int64_t *hdr_skip);
 int kmm_bam_find_record_start(kmm_index_t *idx, const uint8_t *comp, int64_t n_comp, int32_t n_ref, int64_t *member, int64_t *skip);
+
+/*
+ * RECORD SELECTION — which SAM / BAM records are mapped, decided on the GPU inside the record the decode kernels hold (DESIGN
+ * 4.15).  One rule for kmm_map_bam and KMM_FORMAT_SAM: the same records written either way give the same counts.  A record is
+ * KEPT iff all of
+ *   1. (FLAG & "bam_exclude_flags") == 0                         (samtools view -F)
+ *   2. (FLAG & "bam_include_flags") == "bam_include_flags"       (samtools view -f; 0 .. 0xFFFF, default 0)
+ *   3. MAPQ >= "bam_min_mapq"                                    (samtools view -q; 0 .. 255, default 0; numeric, 255 included)
+ *   4. with a region list set (kmm_set_record_regions): the record overlaps a region on its reference, by htslib's rule.
+ *      Positions are 0-based, half-open.  rec_beg = pos (SAM: POS - 1); rec_end = rec_beg + the summed lengths of the CIGAR
+ *      operations M, D, N, = and X (64-bit; I, S, H and P never count; the long-CIGAR placeholder <l_seq>S<n>N counts its N) —
+ *      or rec_beg + 1 when FLAG has 0x4, there is no CIGAR (BAM n_cigar_op 0, SAM "*") or the sum is 0.  Overlap: beg < rec_end
+ *      && rec_beg < end.  A record without a reference (BAM refID -1, SAM RNAME "*") is kept iff keep_unplaced; one with a
+ *      reference and no position (BAM pos < 0, SAM POS 0) overlaps nothing.
+ * A record that is not kept is not looked at further (no SEQ / QUAL decode, no strand flip), counts in "bam_records_excluded" /
+ * "sam_records_excluded" whatever the reason, and not in *n_records, "bam_records", "sam_records", "records_reversed" or
+ * "records_without_qual".  With nothing set the library runs the kernels it ran before the selection existed, bit for bit.
+ *
+ * kmm_set_record_regions — the region list: regions[i] = reference (ref_id for kmm_map_bam, ref_name for KMM_FORMAT_SAM; give
+ * both to serve both), [beg, end) 0-based half-open.  beg < 0 or end <= beg: KMM_ERR_INVALID_ARG.  n_regions == 0 clears the
+ * list (keep_unplaced then has no effect: "the unplaced records alone" is no region list — the unmapped records are
+ * "bam_include_flags" 4).  The library sorts the list by (reference, beg), merges overlapping and abutting
+ * intervals, and keeps it in a small device buffer of the handle, where the kernels binary-search it; "record_regions"
+ * (kmm_get_param, read-only) is the number of intervals after merging.  Limits: KMM_MAX_RECORD_REGIONS regions over
+ * KMM_MAX_REGION_REFERENCES distinct references, names of at most KMM_MAX_REGION_NAME_BYTES bytes (not empty, not "*"); more:
+ * KMM_ERR_INVALID_ARG, the list in force unchanged.  kmm_map_bam uses ref_id: a list with a negative one, or one outside
+ * [0, n_ref) of the stream, is KMM_ERR_INVALID_ARG from the map call, with nothing mapped.  KMM_FORMAT_SAM uses ref_name, compared
+ * with RNAME exactly and whole ("chr1" does not select "chr10"); a list with a NULL one is KMM_ERR_INVALID_ARG from the map call.
+ * No @SQ header is needed.  The selection holds until changed, across streams and calls, like "bam_exclude_flags"; a record
+ * carried between two calls is judged once, by the call that maps it.  Formats other than SAM / BAM are not affected.
+ *
+ * KMM_FORMAT_SAM reads a field only when a rule that needs it is set, of the records that passed the rules before it: MAPQ with
+ * a floor above 0; RNAME with a region list, and POS and CIGAR of the records whose RNAME the list names.  A field that is read
+ * and malformed — MAPQ or POS empty or not decimal, MAPQ above 255, POS above 2^31 - 1, a CIGAR that is neither "*" nor
+ * ([0-9]+[MIDNSHP=X])+ or has an operation longer than 2^28 - 1 — is KMM_ERR_MALFORMED with the line's byte offset and nothing
+ * of the call mapped.  With no rule set such a field stays as unnoticed as it was.
+ */
+#define KMM_MAX_RECORD_REGIONS 4096
+#define KMM_MAX_REGION_REFERENCES 256
+#define KMM_MAX_REGION_NAME_BYTES 255
+typedef struct {
+    const char *ref_name; /* KMM_FORMAT_SAM: the reference's name (NULL: the list serves kmm_map_bam only) */
+    int32_t ref_id;       /* kmm_map_bam: its index in the file's header (negative: the list serves KMM_FORMAT_SAM only) */
+    int64_t beg, end;     /* 0-based, half-open */
+} kmm_region_t;
+int kmm_set_record_regions(kmm_index_t *idx, const kmm_region_t *regions, int n_regions, int keep_unplaced);
 
 /*
  * kmm_map_packed — reads the caller already holds as 2-BIT CODES (its own encoder, a .2bit-style store, the output of a
@@ -552,6 +600,10 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      default: every record, as the reference; 0x900 = no secondary and supplementary alignments).  Read-only: "bam_calls",
  *                      "bam_records" (mapped), "bam_records_excluded", "bam_header_bytes", "bam_false_starts" (speculative
  *                      starts the link check rejected), "bam_continuations" (tiles walked again from the exit before them)
+ *   "bam_include_flags" kmm_map_bam and KMM_FORMAT_SAM: only records whose FLAG has ALL of these bits are mapped (0 .. 0xFFFF,
+ *                      default 0: every record; samtools view -f; RECORD SELECTION above)
+ *   "bam_min_mapq"     kmm_map_bam and KMM_FORMAT_SAM: only records with MAPQ >= this are mapped (0 .. 255, default 0: MAPQ is not
+ *                      read; samtools view -q).  Read-only: "record_regions" (intervals of kmm_set_record_regions after merging)
  *   "min_base_quality" a base-quality floor Q for FASTQ, 0 .. 93 (default 0 = off: nothing changes, bit for bit; anything else
  *                      KMM_ERR_INVALID_ARG).  With Q > 0, on every call that parses KMM_FORMAT_FASTQ records (kmm_map_records,
  *                      kmm_map_bgzf, kmm_map_gzip), a base whose quality byte q (Phred+33, unsigned — a byte below '!'

@@ -77,9 +77,15 @@ SIGNATURES = {
     "kmm_set_timing": (_c.c_int, [_P, _c.c_int]),
     "kmm_get_stats": (_c.c_int, [_P, _c.c_int, _P, _P]),
     "kmm_get_timing": (_c.c_int, [_P, _c.c_int, _P, _P]),
+    "kmm_set_record_regions": (_c.c_int, [_P, _P, _c.c_int, _c.c_int]),
     "kmm_set_param": (_c.c_int, [_P, _c.c_char_p, _c.c_int64]),
     "kmm_get_param": (_c.c_int, [_P, _c.c_char_p, _P]),
 }
+
+
+class Region(ctypes.Structure):
+    """kmm_region_t (include/kmm.h)"""
+    _fields_ = [("ref_name", _c.c_char_p), ("ref_id", _c.c_int32), ("beg", _c.c_int64), ("end", _c.c_int64)]
 
 
 def build(force=False, verbose=False):

@@ -30,6 +30,12 @@ Differences that follow from replacing the engine (all documented in DESIGN.md):
     GPU, so the flag takes the device routes as a table does (plain, BGZF, gzip); it combines with `--ambiguous-bases
     skip`.  SAM / BAM input and `--host-parser` hand the library reads without qualities and are refused; FASTA has none:
     one warning, mapped as before.
+  * `--include-flags`, `--min-mapq`, `--regions`, `--regions-file` (extensions, SAM and BAM input only, beside `--exclude-flags`):
+    which records are mapped — `samtools view -f / -q / regions / -L` without the pipe: the rule is applied on the GPU inside
+    the record the decode kernels hold (kmm_set_param "bam_include_flags" / "bam_min_mapq", kmm_set_record_regions; DESIGN
+    4.15).  Regions take samtools syntax (1-based, inclusive; `*` = the records without a reference), the file is BED.  For BAM
+    the names are resolved against the file's header; SAM needs none.  They combine with `--exclude-flags`,
+    `--use-record-qual`, `--original-strand`, `--shard-bam` and several ranks on SAM.
 """
 import argparse
 import logging
@@ -174,7 +180,7 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
                 exclude_flags=0, probe=None, lut=None, min_base_quality=0, use_record_qual=False, original_strand=False,
-                shard_bam=False):
+                shard_bam=False, record_select=None):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
     on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
@@ -187,8 +193,11 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     original_strand: the handle's "original_strand", SAM / BAM alone — the kept records whose FLAG has 0x10 are mapped in read
     orientation (SEQ reverse-complemented back, QUAL reversed: DESIGN 4.13) and counted ("records_reversed").
     shard_bam: several ranks on one BAM file each map their member range, its ends trimmed to record starts found on the GPU
-    (bgzf_ranges.rank_member_range_bam); without it several ranks on a BAM file are refused."""
+    (bgzf_ranges.rank_member_range_bam); without it several ranks on a BAM file are refused.
+    record_select: check_record_select's dict (include flags, MAPQ floor, regions; SAM / BAM alone) or None: no
+    selection, and no call that sets one."""
     _check_bam_route(fmt, world_size, exclude_flags, shard_bam=shard_bam)
+    record_select = check_record_select(fmt, **(record_select or {}))
     original_strand = check_original_strand(original_strand, fmt)
     use_record_qual = check_use_record_qual(use_record_qual, fmt, min_base_quality)
     min_base_quality = check_min_base_quality(min_base_quality, k, fmt, use_record_qual=use_record_qual)
@@ -297,6 +306,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     # SAM: lines parsed on the GPU, the SEQ column written as two-line FASTA there; BAM: records decoded there
     if fmt in ("sam", "bam"):
         dev.set_param("bam_exclude_flags", int(exclude_flags))
+    if record_select:
+        apply_record_select(dev, path, fmt, record_select, exclude_flags)
     t_start = time.perf_counter()
     n_reads = n_bytes = 0
     if route in ("bam", "bgzf", "gzip"):
@@ -305,7 +316,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         return _map_compressed_file(dev, path, route, kfmt, k, max_index_lookup_frequency,
                                     map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
                                     world_size=world_size, fmt=fmt, lut=lut, min_base_quality=min_base_quality,
-                                    use_record_qual=use_record_qual, original_strand=original_strand, shard_bam=shard_bam)
+                                    use_record_qual=use_record_qual, original_strand=original_strand, shard_bam=shard_bam,
+                                    record_select=bool(record_select))
     try:
         i = 0
         while True:
@@ -335,6 +347,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         n_masked = dev.get_param("quality_masked_bases") if min_base_quality else None
         n_no_qual = dev.get_param("records_without_qual") if (min_base_quality and use_record_qual) else 0
         n_reversed = dev.get_param("records_reversed") if original_strand else None
+        n_selected = (dev.get_param("sam_records"), dev.get_param("sam_records_excluded")) if record_select else None
         if before_fetch is not None:
             before_fetch(dev)
         if helper.is_alive() or helper.ident is not None:
@@ -366,8 +379,69 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                                                   n_lookups / max(dt, 1e-9) / 1e6, n_hits))
     _log_quality_masked(min_base_quality, n_masked, n_no_qual)
     _log_records_reversed(n_reversed)
+    _log_records_selected(n_selected)
     _log_path_taken(n_radix, n_direct, n_host_packed)
     return node_counts
+
+
+def check_record_select(fmt, include_flags=0, min_mapq=0, regions=None, regions_file=None):
+    """--include-flags / --min-mapq / --regions / --regions-file as one dict, or None when none of them is given; on input that
+    is neither SAM nor BAM they are refused, as --exclude-flags is; values the library would refuse are refused here."""
+    include_flags, min_mapq = int(include_flags or 0), int(min_mapq or 0)
+    regions = [r for r in (regions or []) if r]
+    given = [name for name, v in (("--include-flags", include_flags), ("--min-mapq", min_mapq), ("--regions", regions),
+                                  ("--regions-file", regions_file)) if v]
+    if not given:
+        return None
+    if fmt not in ("bam", "sam"):
+        raise ValueError("%s applies to SAM and BAM input only (the reads are %s)" % (given[0], fmt))
+    if not 0 <= include_flags <= 0xFFFF:
+        raise ValueError("--include-flags outside [0, 0xFFFF]")
+    if not 0 <= min_mapq <= 255:
+        raise ValueError("--min-mapq outside [0, 255]")
+    if regions and not regions_file and all(t.strip() == "*" for r in regions for t in str(r).split(",")):
+        # (a list of no regions is no list — kmm_set_record_regions clears it — so '*' has nothing to add the unplaced records to)
+        raise ValueError("--regions '*' alone selects nothing: it adds the records without a reference to a region list; give "
+                         "--include-flags 4 for the unmapped records, or a region beside it")
+    return dict(include_flags=include_flags, min_mapq=min_mapq, regions=regions, regions_file=regions_file)
+
+
+def resolve_record_regions(path, fmt, select):
+    """The regions of --regions and --regions-file as ([(ref_name, ref_id, beg, end)], keep_unplaced): for BAM against the
+    references of the file's header (an unknown name is an error that names it), for SAM by name alone."""
+    from . import reads_io, util
+    references = reads_io.bam_references(path) if fmt == "bam" else None
+    regions, keep_unplaced = [], False
+    for text in select["regions"]:
+        got, unplaced = util.parse_regions(text, references)
+        regions += got
+        keep_unplaced = keep_unplaced or unplaced
+    if select["regions_file"]:
+        regions += util.read_bed_regions(select["regions_file"], references)
+    return regions, keep_unplaced
+
+
+def apply_record_select(dev, path, fmt, select, exclude_flags=0):
+    """The selection set on the handle, and one line that says which rules are in force."""
+    if select["include_flags"]:
+        dev.set_param("bam_include_flags", select["include_flags"])
+    if select["min_mapq"]:
+        dev.set_param("bam_min_mapq", select["min_mapq"])
+    regions, keep_unplaced = resolve_record_regions(path, fmt, select)
+    if regions:
+        dev.set_record_regions(regions, keep_unplaced)
+    elif keep_unplaced:                    # (an empty --regions-file beside '*': check_record_select has refused '*' alone)
+        raise ValueError("--regions '*' with no region beside it selects nothing: give --include-flags 4 for the unmapped records")
+    logging.info("Records are selected on the GPU: exclude flags 0x%x, include flags 0x%x, MAPQ >= %d, %s", int(exclude_flags),
+                 select["include_flags"], select["min_mapq"],
+                 "%d region(s) (%d after merging)%s" % (len(regions), dev.get_param("record_regions"),
+                                                       ", and the records without a reference" if keep_unplaced else "")
+                 if regions else "no region list")
+
+
+def _log_records_selected(n_selected):
+    if n_selected is not None:
+        logging.info("Record selection: %d records kept and mapped, %d excluded" % tuple(n_selected))
 
 
 def _log_quality_masked(min_base_quality, n_masked, n_no_qual=0):
@@ -462,7 +536,7 @@ _COMPRESSED_ROUTES = {
 
 def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None, rank=0,
                          world_size=1, fmt="fastq", lut=None, min_base_quality=0, use_record_qual=False, original_strand=False,
-                         shard_bam=False):
+                         shard_bam=False, record_select=False):
     """`kmer_mapper map -f reads.fq.gz | reads.bam` with the GPU inflater: windows of the file mapping -> kmm_map_<route>.
 
     route "gzip" (PLAIN gzip, kmm_map_gzip): each call goes on where the one before could verify a deflate block boundary.
@@ -573,6 +647,10 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
         n_masked = dev.get_param("quality_masked_bases") if min_base_quality else None
         n_no_qual = dev.get_param("records_without_qual") if (min_base_quality and use_record_qual) else 0
         n_reversed = dev.get_param("records_reversed") if original_strand else None
+        n_selected = None
+        if record_select:
+            which = "bam" if route == "bam" else "sam"
+            n_selected = (dev.get_param(which + "_records"), dev.get_param(which + "_records_excluded"))
         n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
         if before_fetch is not None:
             before_fetch(dev)
@@ -588,6 +666,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
                             n_lookups / max(dt, 1e-9) / 1e6, n_hits))
     _log_quality_masked(min_base_quality, n_masked, n_no_qual)
     _log_records_reversed(n_reversed)
+    _log_records_selected(n_selected)
     _log_path_taken(n_radix, n_direct)
     return node_counts
 
@@ -611,6 +690,10 @@ def map_bnp(args):
     start_time = time.perf_counter()
     if getattr(args, "original_strand", False):    # (refused here: before the index file is read)
         check_original_strand(True, probe_input(args.reads).fmt)
+    select_args = dict(include_flags=getattr(args, "include_flags", 0), min_mapq=getattr(args, "min_mapq", 0),
+                       regions=getattr(args, "regions", None), regions_file=getattr(args, "regions_file", None))
+    if any(select_args.values()):                  # (likewise)
+        check_record_select(probe_input(args.reads).fmt, **select_args)
     kmer_index = _get_kmer_index_from_args(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -669,6 +752,7 @@ def map_bnp(args):
     min_q = check_min_base_quality(getattr(args, "min_base_quality", 0), k, fmt, bool(getattr(args, "host_parser", False)),
                                    use_record_qual=use_qual)
     original_strand = check_original_strand(bool(getattr(args, "original_strand", False)), fmt)
+    record_select = check_record_select(fmt, **select_args)
     if fmt == "bam" and getattr(args, "host_parser", False):
         raise ValueError("--host-parser does not read BAM: its records are decoded on the GPU (drop --host-parser)")
     if fmt == "sam" and getattr(args, "host_parser", False):
@@ -680,7 +764,7 @@ def map_bnp(args):
                                   device=device, rank=rank, world_size=world, before_fetch=before_fetch,
                                   n_threads=args.n_threads, exclude_flags=exclude_flags, probe=probe, lut=lut,
                                   min_base_quality=min_q, use_record_qual=use_qual, original_strand=original_strand,
-                                  shard_bam=shard_bam)
+                                  shard_bam=shard_bam, **({"record_select": record_select} if record_select else {}))
     else:
         logging.info("Using the host FASTA/FASTQ parser")
         if world > 1 and not probe.inflate:
@@ -751,6 +835,22 @@ def build_argument_parser():
     subparser.add_argument("--exclude-flags", default=0, type=lambda v: int(v, 0),
                            help="Extension, SAM and BAM input only: leave out records whose FLAG has any of these bits (samtools view -F; "
                                 "e.g. 0x900 = secondary and supplementary alignments). Default 0: every record, as the reference.")
+    subparser.add_argument("--include-flags", default=0, type=lambda v: int(v, 0),
+                           help="Extension, SAM and BAM input only: map only records whose FLAG has all of these bits (samtools view "
+                                "-f; e.g. 0x2 = proper pairs, 4 = unmapped reads). Default 0: every record.")
+    subparser.add_argument("--min-mapq", default=0, type=int, metavar="Q",
+                           help="Extension, SAM and BAM input only: map only records with MAPQ >= Q (samtools view -q; 0 .. 255). "
+                                "Default 0: MAPQ is not read.")
+    subparser.add_argument("--regions", action="append", default=None, metavar="REGIONS",
+                           help="Extension, SAM and BAM input only: map only records that overlap one of these regions, decided on "
+                                "the GPU from RNAME / POS / CIGAR. Comma-separated, repeatable, samtools syntax: chr6:28,000,000-"
+                                "34,000,000 (1-based, inclusive), chr6:5, chr6, '*' = also the records without a reference ('*' "
+                                "alone is refused: it adds to a list; --include-flags 4 gives the unmapped records). In one "
+                                "string a comma in front of exactly three digits is a thousands separator: chr1:5,100 is "
+                                "chr1:5100, and a reference named by three digits needs a --regions of its own.")
+    subparser.add_argument("--regions-file", default=None, metavar="BED",
+                           help="Extension, SAM and BAM input only: regions from a BED file (three columns, 0-based half-open; "
+                                "'#', 'track' and 'browser' lines are skipped); adds to --regions.")
     subparser.add_argument("--ambiguous-bases", choices=("a", "skip"), default="a",
                            help="a (default): N is counted as A and any other letter is an error, as the reference. skip "
                                 "(extension): no k-mer that contains N or an IUPAC ambiguity letter is counted; the k-mers on "

@@ -390,6 +390,16 @@ struct kmm_index : IndexStreams, RxArrays {
     // KMM_FORMAT_SAM (kmm_sam.hpp): the tiles' line counts, their output offsets, the totals; the filter is bam_excl
     DevBuf sam_tiles, sam_base, sam_ctl;
     int64_t sam_calls = 0, sam_records = 0, sam_excluded = 0, sam_header_lines = 0;
+    // record selection (kmm_select.hpp): "bam_include_flags", "bam_min_mapq" and the region list of
+    // kmm_set_record_regions, merged twice — by refID for kmm_map_bam (sel_iv_id; empty when a region came without an id) and by
+    // name for KMM_FORMAT_SAM (sel_iv_name, the names in sel_names; empty when one came without a name) — and held in one small
+    // device buffer: the two interval lists, the name offsets, the name bytes
+    uint32_t bam_incl = 0, bam_min_mapq = 0;
+    int sel_n_regions = 0, sel_keep_unplaced = 0; // regions as given (0: no list)
+    std::vector<kmm_sel::Interval> sel_iv_id, sel_iv_name;
+    std::vector<std::string> sel_names;
+    DevBuf sel_buf;
+    size_t sel_off_name_iv = 0, sel_off_name_off = 0, sel_off_names = 0;
     int dbg_bgzf_slot_kb = 0;     // test hook ("debug_bgzf_ring_slot_kb"): slot size of kmm_map_bgzf's staging ring (a power of two, >= 4)
     int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
@@ -2373,6 +2383,38 @@ static int map_multiline_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_by
     return rc != KMM_OK ? rc : rel;
 }
 
+// The selection a SAM (by_name) / BAM call runs under: the masks, the floor and — with a region list set — the interval list of
+// that front end in the handle's device buffer.  A list that cannot serve the front end is refused here, before anything is
+// mapped: regions without a name for SAM; for BAM, regions without an id, or an id outside [0, n_ref) of the stream.
+static int selection_of(const kmm_index_t *ix, const char *who, bool by_name, int32_t n_ref, kmm_sel::Sel &sel)
+{
+    sel = kmm_sel::Sel();
+    sel.excl = ix->bam_excl;
+    sel.incl = ix->bam_incl;
+    sel.min_mapq = ix->bam_min_mapq;
+    if (ix->sel_n_regions == 0)
+        return KMM_OK;
+    const std::vector<kmm_sel::Interval> &iv = by_name ? ix->sel_iv_name : ix->sel_iv_id;
+    if (iv.empty())
+        return fail(KMM_ERR_INVALID_ARG, by_name ? "%s: the region list of kmm_set_record_regions has a region without ref_name, which SAM "
+                                                   "records are selected by (nothing is mapped)"
+                                                 : "%s: the region list of kmm_set_record_regions has a region without ref_id (negative), which "
+                                                   "BAM records are selected by (nothing is mapped)", who);
+    if (!by_name && iv.back().ref >= (int64_t)n_ref)
+        return fail(KMM_ERR_INVALID_ARG, "%s: the region list names ref_id %lld, the stream has %d references (nothing is mapped)", who,
+                    (long long)iv.back().ref, (int)n_ref);
+    const uint8_t *b = (const uint8_t *)ix->sel_buf.p;
+    sel.n_iv = (uint32_t)iv.size();
+    sel.keep_unplaced = ix->sel_keep_unplaced ? 1u : 0u;
+    sel.iv = (const kmm_sel::Interval *)(by_name ? b + ix->sel_off_name_iv : b);
+    if (by_name) {
+        sel.n_names = (uint32_t)ix->sel_names.size();
+        sel.name_off = (const uint32_t *)(b + ix->sel_off_name_off);
+        sel.names = b + ix->sel_off_names;
+    }
+    return KMM_OK;
+}
+
 // One piece of a SAM chunk (kmm_sam.hpp): its lines counted and checked on the device, the SEQ of every kept record written as
 // two-line FASTA into the stage's second buffer, which map_records_piece then maps.  Only complete lines are taken (*consumed:
 // the byte after the piece's last newline).  dry: the count and the checks only (a chunk of several pieces is checked whole
@@ -2398,10 +2440,21 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
     unsigned long long *base = (unsigned long long *)ix->sam_base.p;
     kmm_sam::Totals *d_tot = (kmm_sam::Totals *)ix->sam_ctl.p;
     const uint32_t excl = ix->bam_excl;
+    kmm_sel::Sel sel; // a selection beyond excl: the k_sam_*_sel kernels run
+    const int src = selection_of(ix, "kmm_map_records (KMM_FORMAT_SAM)", true, 0, sel);
+    if (src != KMM_OK) {
+        (void)stage_release(ix, s, false);
+        return src;
+    }
+    const bool selected = !sel.flags_only();
     KMMCHK(stage_copies_done(ix));
     hipStream_t cs = ix->stream; // (kernels run on the handle's stream only: see rec_compact_piece)
     const dim3 gw((unsigned)grid_for(ix, (int64_t)((n_tiles + 3) / 4), 16)); // one wavefront per tile, 4 per block, grid-stride
-    if (qual)
+    if (selected && qual)
+        hipLaunchKernelGGL(kmm_sam::k_sam_count_q_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel, tiles);
+    else if (selected)
+        hipLaunchKernelGGL(kmm_sam::k_sam_count_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel, tiles);
+    else if (qual)
         hipLaunchKernelGGL(kmm_sam::k_sam_count_q, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl, tiles);
     else
         hipLaunchKernelGGL(kmm_sam::k_sam_count, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl, tiles);
@@ -2411,11 +2464,16 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
     HIPCHK(hipMemcpyAsync(&h, d_tot, sizeof h, hipMemcpyDeviceToHost, cs));
     HIPCHK(hipStreamSynchronize(cs)); // (the borrowed host buffer is free from here on)
     if (h.err != kmm_sam::NONE) {
-        static const char *why[4] = {"QUAL is not \"*\" and not as long as SEQ", "fewer than 11 TAB-separated fields",
-                                     "FLAG is not a decimal integer in [0, 65535]", "an empty line"};
+        static const char *why[8] = {"QUAL is not \"*\" and not as long as SEQ", "fewer than 11 TAB-separated fields",
+                                     "FLAG is not a decimal integer in [0, 65535]", "an empty line",
+                                     "MAPQ is not a decimal integer in [0, 255] (\"bam_min_mapq\" reads it)",
+                                     "POS is not a decimal integer in [0, 2^31 - 1] (the region list reads it)",
+                                     "CIGAR is neither \"*\" nor ([0-9]+[MIDNSHP=X])+ with lengths up to 2^28 - 1 (the region list reads it)",
+                                     "?"};
+        const unsigned shift = selected ? 3u : 2u; // (kmm_sam::err_shift)
         (void)stage_release(ix, s, false);
         return fail(KMM_ERR_MALFORMED, "kmm_map_records: SAM line at byte %llu of the chunk: %s (nothing of the call is mapped)",
-                    (unsigned long long)at + (h.err >> 2), why[h.err & 3]);
+                    (unsigned long long)at + (h.err >> shift), why[h.err & ((1u << shift) - 1u)]);
     }
     *consumed = (int64_t)h.consumed;
     int rc = KMM_OK;
@@ -2427,7 +2485,15 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
             // (with QUAL "*" a record's four-line FASTQ is longer than its line: the buffer is sized from the totals)
             rc = ensure(s.kmers, (size_t)h.out_bytes + 16);
             if (rc == KMM_OK) {
-                if (ix->original_strand)
+                if (selected && ix->original_strand)
+                    hipLaunchKernelGGL(kmm_sam::k_sam_write_q_rev_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel,
+                                       (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
+                                       ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
+                else if (selected)
+                    hipLaunchKernelGGL(kmm_sam::k_sam_write_q_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel,
+                                       (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
+                                       ix->stats + KMM_STAT_REC_NO_QUAL);
+                else if (ix->original_strand)
                     hipLaunchKernelGGL(kmm_sam::k_sam_write_q_rev, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
                                        (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
                                        ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
@@ -2449,7 +2515,13 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
                           h.out_bytes, (long long)*n_records, h.recs);
         } else if (h.recs > 0) {
             uint8_t *out = (uint8_t *)s.kmers.p;
-            if (ix->original_strand)
+            if (selected && ix->original_strand)
+                hipLaunchKernelGGL(kmm_sam::k_sam_write_rev_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel,
+                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out, ix->stats + KMM_STAT_REC_REVERSED);
+            else if (selected)
+                hipLaunchKernelGGL(kmm_sam::k_sam_write_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel,
+                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out);
+            else if (ix->original_strand)
                 hipLaunchKernelGGL(kmm_sam::k_sam_write_rev, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
                                    (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out, ix->stats + KMM_STAT_REC_REVERSED);
             else
@@ -3117,6 +3189,8 @@ struct BamGpuBackend {
     uint32_t excl;
     bool qual = false; // the quality variant: four-line FASTQ, 2 l_seq + 6 bytes per kept record
     bool orig = false; // "original_strand": decode writes the kept records with FLAG 0x10 in read orientation
+    bool selected = false; // a selection beyond excl is set (sel): the k_bam_*_sel kernels run
+    kmm_bam::Sel sel;
     int cur = 0;
 
     kmm_bam::Tile *tiles(int i) { return (kmm_bam::Tile *)ix->bam_tiles[i].p; }
@@ -3134,7 +3208,11 @@ struct BamGpuBackend {
         cur = 0;
         HIPCHK(hipMemsetAsync(ctl(), 0, sizeof(kmm_bam::Ctl), ix->stream));
         HIPCHK(hipMemsetAsync(&ctl()->err_pos, 0xFF, 8, ix->stream)); // (no error)
-        if (qual)
+        if (selected && qual)
+            hipLaunchKernelGGL(kmm_bam::k_bam_spec_q_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel, tiles(0));
+        else if (selected)
+            hipLaunchKernelGGL(kmm_bam::k_bam_spec_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel, tiles(0));
+        else if (qual)
             hipLaunchKernelGGL(kmm_bam::k_bam_spec_q, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl, tiles(0));
         else
             hipLaunchKernelGGL(kmm_bam::k_bam_spec, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl, tiles(0));
@@ -3154,7 +3232,13 @@ struct BamGpuBackend {
     }
     int fix(uint64_t n_tiles, uint64_t start0)
     {
-        if (qual)
+        if (selected && qual)
+            hipLaunchKernelGGL(kmm_bam::k_bam_fix_q_sel, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
+                               (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
+        else if (selected)
+            hipLaunchKernelGGL(kmm_bam::k_bam_fix_sel, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
+                               (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
+        else if (qual)
             hipLaunchKernelGGL(kmm_bam::k_bam_fix_q, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl,
                                (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
         else
@@ -3176,7 +3260,20 @@ struct BamGpuBackend {
     }
     int decode(uint64_t n_tiles, uint8_t *out)
     {
-        if (qual && orig)
+        const kmm_bam::Tile *tl = (const kmm_bam::Tile *)tiles(cur);
+        const unsigned long long *bs = (const unsigned long long *)ix->bam_base.p;
+        if (selected && qual && orig)
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_rev_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs,
+                               out, ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
+        else if (selected && qual)
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs,
+                               out, ix->stats + KMM_STAT_REC_NO_QUAL);
+        else if (selected && orig)
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode_rev_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs,
+                               out, ix->stats + KMM_STAT_REC_REVERSED);
+        else if (selected)
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs, out);
+        else if (qual && orig)
             hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_rev, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
                                (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out,
                                ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
@@ -3243,6 +3340,8 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     }
     const bool qual = record_quality(ix) > 0;
     BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl, qual, ix->original_strand != 0};
+    KMMCHK(selection_of(ix, "kmm_map_bam", false, ix->bam_n_ref, be.sel));
+    be.selected = !be.sel.flags_only();
     kmm_bam::CallOut co;
     KMMCHK(kmm_bam::run_call(be, (uint64_t)n_raw, start0, co));
     ix->bam_false_starts += (int64_t)co.false_starts;
@@ -4099,6 +4198,87 @@ int kmm_get_timing(kmm_index_t *ix, int kernel_id, double *kernel_ms, int64_t *n
     return KMM_OK;
 }
 
+int kmm_set_record_regions(kmm_index_t *ix, const kmm_region_t *regions, int n_regions, int keep_unplaced)
+{
+    return guarded("kmm_set_record_regions", [&]() -> int {
+        if (!ix || n_regions < 0 || (n_regions > 0 && !regions))
+            return fail(KMM_ERR_INVALID_ARG, "kmm_set_record_regions: NULL argument or n_regions negative");
+        if (n_regions > KMM_MAX_RECORD_REGIONS)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_set_record_regions: %d regions, at most %d are taken", n_regions, KMM_MAX_RECORD_REGIONS);
+        // the list is judged whole before the handle changes: by id and by name, each usable only when every region has one
+        std::vector<kmm_sel::Interval> by_id, by_name;
+        std::vector<std::string> names;
+        bool ids = true, named = true;
+        for (int i = 0; i < n_regions; ++i) {
+            const kmm_region_t &r = regions[i];
+            if (r.beg < 0 || r.end <= r.beg)
+                return fail(KMM_ERR_INVALID_ARG, "kmm_set_record_regions: region %d is [%lld, %lld): beg < 0 or end <= beg", i,
+                            (long long)r.beg, (long long)r.end);
+            if (r.ref_name && (r.ref_name[0] == 0 || strlen(r.ref_name) > (size_t)KMM_MAX_REGION_NAME_BYTES || !strcmp(r.ref_name, "*")))
+                return fail(KMM_ERR_INVALID_ARG, "kmm_set_record_regions: region %d: ref_name is empty, \"*\" or longer than %d bytes", i,
+                            KMM_MAX_REGION_NAME_BYTES);
+            ids = ids && r.ref_id >= 0;
+            named = named && r.ref_name != nullptr;
+            if (r.ref_name)
+                names.push_back(r.ref_name);
+        }
+        if (n_regions > 0 && !ids && !named)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_set_record_regions: every region needs a ref_id (>= 0; BAM) or every region a ref_name (SAM)");
+        std::sort(names.begin(), names.end());
+        names.erase(std::unique(names.begin(), names.end()), names.end());
+        if (!named)
+            names.clear();
+        for (int i = 0; i < n_regions; ++i) {
+            const kmm_region_t &r = regions[i];
+            if (ids)
+                by_id.push_back(kmm_sel::Interval{(int64_t)r.ref_id, r.beg, r.end});
+            if (named)
+                by_name.push_back(kmm_sel::Interval{(int64_t)(std::lower_bound(names.begin(), names.end(), std::string(r.ref_name)) - names.begin()),
+                                                    r.beg, r.end});
+        }
+        kmm_sel::merge_intervals(by_id);
+        kmm_sel::merge_intervals(by_name);
+        std::vector<int64_t> refs;
+        for (const kmm_sel::Interval &v : by_id)
+            if (refs.empty() || refs.back() != v.ref)
+                refs.push_back(v.ref);
+        if (refs.size() > (size_t)KMM_MAX_REGION_REFERENCES || names.size() > (size_t)KMM_MAX_REGION_REFERENCES)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_set_record_regions: regions on %zu distinct references, at most %d are taken",
+                        std::max(refs.size(), names.size()), KMM_MAX_REGION_REFERENCES);
+        // the device buffer: [intervals by id][intervals by name][name offsets][name bytes]
+        const size_t off_name_iv = by_id.size() * sizeof(kmm_sel::Interval), off_name_off = off_name_iv + by_name.size() * sizeof(kmm_sel::Interval),
+                     off_names = off_name_off + (names.size() + 1) * 4;
+        std::vector<uint8_t> h(off_names);
+        if (!by_id.empty())
+            memcpy(h.data(), by_id.data(), off_name_iv);
+        if (!by_name.empty())
+            memcpy(h.data() + off_name_iv, by_name.data(), off_name_off - off_name_iv);
+        uint32_t at = 0;
+        for (size_t i = 0; i <= names.size(); ++i) {
+            memcpy(h.data() + off_name_off + 4 * i, &at, 4);
+            if (i < names.size()) {
+                h.insert(h.end(), names[i].begin(), names[i].end());
+                at += (uint32_t)names[i].size();
+            }
+        }
+        HIPCHK(hipSetDevice(ix->device));
+        HIPCHK(hipStreamSynchronize(ix->stream)); // (kernels of a call before may read the list in place)
+        if (n_regions > 0) {
+            KMMCHK(ensure(ix->sel_buf, h.size() + 64));
+            HIPCHK(hipMemcpy(ix->sel_buf.p, h.data(), h.size(), hipMemcpyHostToDevice));
+        }
+        ix->sel_n_regions = n_regions;
+        ix->sel_keep_unplaced = n_regions > 0 && keep_unplaced ? 1 : 0;
+        ix->sel_iv_id.swap(by_id);
+        ix->sel_iv_name.swap(by_name);
+        ix->sel_names.swap(names);
+        ix->sel_off_name_iv = off_name_iv;
+        ix->sel_off_name_off = off_name_off;
+        ix->sel_off_names = off_names;
+        return KMM_OK;
+    });
+}
+
 int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
 {
     if (!ix || !name)
@@ -4226,6 +4406,14 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value < 0 || value > 0xFFFF)
             return fail(KMM_ERR_INVALID_ARG, "bam_exclude_flags outside [0, 0xFFFF]");
         ix->bam_excl = (uint32_t)value;
+    } else if (!strcmp(name, "bam_include_flags")) {
+        if (value < 0 || value > 0xFFFF)
+            return fail(KMM_ERR_INVALID_ARG, "bam_include_flags outside [0, 0xFFFF]");
+        ix->bam_incl = (uint32_t)value;
+    } else if (!strcmp(name, "bam_min_mapq")) {
+        if (value < 0 || value > 255)
+            return fail(KMM_ERR_INVALID_ARG, "bam_min_mapq outside [0, 255]");
+        ix->bam_min_mapq = (uint32_t)value;
     } else if (!strcmp(name, "bam_n_ref")) {
         // n_ref of the next KMM_FORMAT_MID_STREAM stream of kmm_map_bam (kmm_bam_header returns it); -1 = not set
         if (value < -1 || value > 0x7FFFFFFFll)
@@ -4344,6 +4532,12 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->bam_continuations;
     else if (!strcmp(name, "bam_exclude_flags"))
         *value = ix->bam_excl;
+    else if (!strcmp(name, "bam_include_flags"))
+        *value = ix->bam_incl;
+    else if (!strcmp(name, "bam_min_mapq"))
+        *value = ix->bam_min_mapq;
+    else if (!strcmp(name, "record_regions")) // intervals of kmm_set_record_regions after merging (by ref_id; by name where no id was given)
+        *value = (int64_t)(ix->sel_iv_id.empty() ? ix->sel_iv_name.size() : ix->sel_iv_id.size());
     else if (!strcmp(name, "sam_calls")) // kmm_map_records calls (direct, or on the inflated bytes of kmm_map_bgzf / _gzip) on SAM
         *value = ix->sam_calls;
     else if (!strcmp(name, "sam_records")) // SAM records mapped

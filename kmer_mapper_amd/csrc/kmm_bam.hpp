@@ -23,6 +23,9 @@
 // the library maps as KMM_FORMAT_FASTQ, where "min_base_quality" is applied.
 // "original_strand"  has decode write the kept records whose FLAG has 0x10 in read orientation: SEQ reversed and
 // complemented, QUAL reversed.  The output lengths are the same: spec, link and totals do not know of the switch.
+// Record selection (kmm_select.hpp has the rule): with an include mask, a MAPQ floor or a region list set, spec, fix,
+// decode and the CPU backend run as their <.., true> / k_bam_*_sel forms, which ask ONE predicate, kept(), about every record:
+// counting and writing can never disagree.  Without one, the forms above run, as they did before the selection existed.
 // Exactness never depends on the plausibility test: a wrong guess only costs a fix.  Every read is bounds-checked against n.
 // resync (kmm_bam_find_record_start) is the other use of the plausibility test: in inflated bytes that begin anywhere
 // in the stream — a rank's share of a file — k_bam_resync finds the lowest position from which the chain of records holds to the
@@ -32,6 +35,8 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "kmm_select.hpp"
 
 #if defined(__HIPCC__)
 #define KMM_BAM_HD __host__ __device__ __forceinline__
@@ -120,6 +125,55 @@ KMM_BAM_HD bool plausible(const uint8_t *d, uint64_t n, uint64_t c, int32_t n_re
     return true;
 }
 
+// ---- record selection: refID, pos, MAPQ and the CIGAR words lie in front of SEQ, inside the bounds record_at checked
+using kmm_sel::Sel;
+
+// The reference span of the record's CIGAR, the share of lane `lane` of `lanes` (operations lane, lane + lanes, ...): the lengths
+// of M, D, N, = and X summed in 64 bits.  I, S, H and P never count; the long-CIGAR placeholder <l_seq>S<n>N counts its N.
+KMM_BAM_HD uint64_t cigar_span_part(const uint8_t *rec, const RecHead &h, uint32_t lane, uint32_t lanes)
+{
+    const uint8_t *c = rec + 36ull + h.l_name;
+    uint64_t span = 0;
+    for (uint32_t j = lane; j < h.n_cigar; j += lanes) {
+        const uint32_t w = rd32(c + 4ull * j);
+        if (kmm_sel::consumes_ref(w))
+            span += w >> 4;
+    }
+    return span;
+}
+
+// Rules 1 to 3 of the record at rec (flag masks, MAPQ) and what rule 4 says without the CIGAR: 1 kept, 0 not kept, -1 the
+// CIGAR's span decides (the record starts outside every region and may reach into one).
+KMM_BAM_HD int kept_without_cigar(const uint8_t *rec, const RecHead &h, const Sel &s)
+{
+    if (!kmm_sel::flags_pass(h.flag, s) || (uint32_t)rec[13] < s.min_mapq)
+        return 0;
+    if (s.n_iv == 0)
+        return 1;
+    const int32_t ref = (int32_t)rd32(rec + 4), pos = (int32_t)rd32(rec + 8);
+    if (ref < 0)
+        return s.keep_unplaced ? 1 : 0;
+    if (kmm_sel::region_pass(s, ref, pos, h.flag, 0)) // (its first base lies in a region: no span can change that)
+        return 1;
+    return pos < 0 || (h.flag & kmm_sel::FLAG_UNMAPPED) || h.n_cigar == 0 ? 0 : -1;
+}
+
+// THE predicate: is the record at rec mapped?  S false: the exclude mask alone, as before the selection existed.  lanes > 1: the
+// callers' lanes walk the CIGAR together, one after the other here (the CPU form of kept_wave below).
+template <bool S>
+KMM_BAM_HD bool kept(const uint8_t *rec, const RecHead &h, uint32_t excl, const Sel &s, uint32_t lanes = 1)
+{
+    if (!S)
+        return !(h.flag & excl);
+    const int r = kept_without_cigar(rec, h, s);
+    if (r >= 0)
+        return r != 0;
+    uint64_t span = 0;
+    for (uint32_t lane = 0; lane < lanes; ++lane)
+        span += cigar_span_part(rec, h, lane, lanes);
+    return kmm_sel::region_pass(s, (int32_t)rd32(rec + 4), (int32_t)rd32(rec + 8), h.flag, span);
+}
+
 struct Walk {
     uint64_t exit;
     uint32_t recs, excluded, bytes;
@@ -142,8 +196,8 @@ static_assert(MAX_TILE_OUT < 0x100000000ull, "a tile's output bytes fit uint32")
 
 // The chain from p (a record start) to the first start at or past te; it stops early at a record that does not end inside
 // d[0, n) (exit = its start) or at a malformed one (bad, exit = its start).
-template <bool Q = false>
-KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int32_t n_ref, uint32_t excl, Walk &w)
+template <bool Q = false, bool S = false>
+KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int32_t n_ref, uint32_t excl, Walk &w, const Sel &sel = Sel())
 {
     w.recs = w.excluded = w.bytes = 0;
     w.bad = false;
@@ -156,7 +210,7 @@ KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int3
             w.bad = true;
             break;
         }
-        if (h.flag & excl)
+        if (!kept<S>(d + p, h, excl, sel))
             ++w.excluded;
         else {
             ++w.recs;
@@ -170,9 +224,9 @@ KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int3
 KMM_BAM_HD uint64_t tile_end(uint64_t t, uint64_t n) { return (t + 1) * TILE < n ? (t + 1) * TILE : n; }
 
 // The claim of tile t once its start is known (entry = a record start) or guessed.
-template <bool Q = false>
+template <bool Q = false, bool S = false>
 KMM_BAM_HD void claim_from(const uint8_t *d, uint64_t n, uint64_t t, uint64_t entry, int32_t n_ref, uint32_t excl, uint32_t spec,
-                           Tile &o)
+                           Tile &o, const Sel &sel = Sel())
 {
     o.spec = spec;
     if (entry == NONE) {
@@ -181,7 +235,7 @@ KMM_BAM_HD void claim_from(const uint8_t *d, uint64_t n, uint64_t t, uint64_t en
         return;
     }
     Walk w;
-    walk<Q>(d, n, entry, tile_end(t, n), n_ref, excl, w);
+    walk<Q, S>(d, n, entry, tile_end(t, n), n_ref, excl, w, sel);
     o.entry = w.bad ? INVALID : entry;
     o.exit = w.bad ? INVALID : w.exit;
     o.recs = w.recs;
@@ -214,8 +268,9 @@ KMM_BAM_HD bool agrees(const uint8_t *d, uint64_t n, uint64_t t, const Tile &c, 
 // ---- the per-tile steps, shared by the kernels and the CPU backend ----
 
 // spec, one tile (scalar form: the kernel tests 64 positions at a time, with the same `plausible`)
-template <bool Q = false>
-inline void spec_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, uint64_t start0, int32_t n_ref, uint32_t excl, Tile &o)
+template <bool Q = false, bool S = false>
+inline void spec_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, uint64_t start0, int32_t n_ref, uint32_t excl, Tile &o,
+                             const Sel &sel = Sel())
 {
     uint64_t entry = NONE;
     if (t == 0)
@@ -224,17 +279,17 @@ inline void spec_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, uint64_t 
         for (uint64_t c = t * TILE, e = tile_end(t, n); c < e && entry == NONE; ++c)
             if (plausible(d, n, c, n_ref))
                 entry = c;
-    claim_from<Q>(d, n, t, entry, n_ref, excl, 1u, o);
+    claim_from<Q, S>(d, n, t, entry, n_ref, excl, 1u, o, sel);
 }
 
 // fix, one tile: its claim is walked again from the exit before it.  verified: that exit is exact (t is the first tile
 // that disagrees), so a malformed record met on the way is an error of the file (returns its position, else NONE).
-template <bool Q = false>
+template <bool Q = false, bool S = false>
 KMM_BAM_HD uint64_t fix_tile(const uint8_t *d, uint64_t n, uint64_t t, uint64_t prev, bool verified, int32_t n_ref, uint32_t excl,
-                             Tile &o)
+                             Tile &o, const Sel &sel = Sel())
 {
     Walk w;
-    walk<Q>(d, n, prev, tile_end(t, n), n_ref, excl, w);
+    walk<Q, S>(d, n, prev, tile_end(t, n), n_ref, excl, w, sel);
     o.spec = 0;
     o.recs = w.recs;
     o.excluded = w.excluded;
@@ -546,18 +601,34 @@ struct CpuBackend {
     bool orig = false;     // "original_strand": decode() writes the kept records with FLAG 0x10 in read orientation
     uint64_t reversed = 0; // the records decode() flipped
     uint32_t lanes = 1;    // lanes decode() gives the per-record functions (the tests: 1 and 64), one after the other
+    Sel sel;               // the selection beyond excl (its own excl is not read: eff()); default: flags only
     std::vector<Tile> cur, nxt;
     std::vector<uint64_t> base;
     uint64_t false_starts = 0;
 
+    Sel eff() const
+    {
+        Sel s = sel;
+        s.excl = excl;
+        return s;
+    }
+    bool is_kept(uint64_t p, const RecHead &h) const
+    {
+        return sel.flags_only() ? kept<false>(d + p, h, excl, sel) : kept<true>(d + p, h, excl, eff(), lanes);
+    }
     int spec(uint64_t n_tiles, uint64_t start0)
     {
         cur.assign(n_tiles, Tile());
         nxt.assign(n_tiles, Tile());
         false_starts = 0;
         first_bad = err_pos = NONE;
+        const bool s = !sel.flags_only();
         for (uint64_t t = 0; t < n_tiles; ++t)
-            if (qual)
+            if (qual && s)
+                spec_tile_scalar<true, true>(d, n, t, start0, n_ref, excl, cur[t], eff());
+            else if (s)
+                spec_tile_scalar<false, true>(d, n, t, start0, n_ref, excl, cur[t], eff());
+            else if (qual)
                 spec_tile_scalar<true>(d, n, t, start0, n_ref, excl, cur[t]);
             else
                 spec_tile_scalar(d, n, t, start0, n_ref, excl, cur[t]);
@@ -589,8 +660,11 @@ struct CpuBackend {
             }
             if (cur[t].spec && cur[t].entry != NONE)
                 ++false_starts;
-            const uint64_t e = qual ? fix_tile<true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t])
-                                    : fix_tile(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t]);
+            const bool s = !sel.flags_only();
+            const uint64_t e = qual && s ? fix_tile<true, true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t], eff())
+                               : s       ? fix_tile<false, true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t], eff())
+                               : qual    ? fix_tile<true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t])
+                                         : fix_tile(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t]);
             if (e != NONE && (err_pos == NONE || e < err_pos))
                 err_pos = e;
         }
@@ -621,15 +695,15 @@ struct CpuBackend {
                 RecHead h;
                 if (record_at(d, n, p, n_ref, h) != REC_OK)
                     break;
-                const bool rev = flipped(h, orig);
-                if (!(h.flag & excl))
+                const bool rev = flipped(h, orig), keep = is_kept(p, h);
+                if (keep)
                     reversed += rev ? 1u : 0u;
-                if (!(h.flag & excl) && qual) {
+                if (keep && qual) {
                     for (uint32_t lane = 0; lane < lanes; ++lane)
                         rev ? decode_record_q_rev(d + p, h, out + o, lane, lanes) : decode_record_q(d + p, h, out + o, lane, lanes);
                     o += 2ull * h.l_seq + 6ull;
                     no_qual += qual_absent(d + p, h) ? 1u : 0u;
-                } else if (!(h.flag & excl)) {
+                } else if (keep) {
                     for (uint32_t lane = 0; lane < lanes; ++lane)
                         rev ? decode_record_rev(d + p, h, out + o, lane, lanes) : decode_record(d + p, h, out + o, lane, lanes);
                     o += h.l_seq + 3ull;
@@ -643,9 +717,9 @@ struct CpuBackend {
 #if defined(__HIPCC__)
 // spec: one wavefront per tile (grid-stride); lanes test 64 consecutive positions, the lowest plausible one is the start;
 // lane 0 walks the chain from it.
-template <bool Q>
+template <bool Q, bool S = false>
 __device__ __forceinline__ void bam_spec_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
-                                               int32_t n_ref, uint32_t excl, Tile *__restrict__ out)
+                                               int32_t n_ref, uint32_t excl, Tile *__restrict__ out, const Sel &sel = Sel())
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
@@ -663,7 +737,7 @@ __device__ __forceinline__ void bam_spec_tiles(const uint8_t *__restrict__ d, ui
         if (lane == 0) {
             Walk w;
             if (entry != NONE)
-                walk<Q>(d, n, entry, tile_end(t, n), n_ref, excl, w);
+                walk<Q, S>(d, n, entry, tile_end(t, n), n_ref, excl, w, sel);
             const bool none = entry == NONE, bad = !none && w.bad;
             out[t].entry = bad ? INVALID : entry;
             out[t].exit = none ? NONE : bad ? INVALID : w.exit;
@@ -685,6 +759,18 @@ __global__ void __launch_bounds__(256) k_bam_spec_q(const uint8_t *__restrict__ 
 {
     bam_spec_tiles<true>(d, n, n_tiles, start0, n_ref, excl, out);
 }
+// spec with a selection set: the walking lane asks kept<true> — rules 1 to 3 from the record's head; a record that
+// starts outside every region has its CIGAR read by that one lane.  Kernels of their own: the two above run without a selection.
+__global__ void __launch_bounds__(256) k_bam_spec_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                      int32_t n_ref, Sel sel, Tile *__restrict__ out)
+{
+    bam_spec_tiles<false, true>(d, n, n_tiles, start0, n_ref, sel.excl, out, sel);
+}
+__global__ void __launch_bounds__(256) k_bam_spec_q_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                        int32_t n_ref, Sel sel, Tile *__restrict__ out)
+{
+    bam_spec_tiles<true, true>(d, n, n_tiles, start0, n_ref, sel.excl, out, sel);
+}
 
 // check: one lane per tile; bad[t] = its claim disagrees with the exit before it
 __global__ void __launch_bounds__(256) k_bam_check(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
@@ -702,10 +788,10 @@ __global__ void __launch_bounds__(256) k_bam_check(const uint8_t *__restrict__ d
 }
 
 // fix: one lane per tile; claims that agree are copied, the others walked again from the exit before them
-template <bool Q>
+template <bool Q, bool S = false>
 __device__ __forceinline__ void bam_fix_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
                                               int32_t n_ref, uint32_t excl, const Tile *__restrict__ in, const uint8_t *__restrict__ bad,
-                                              Tile *__restrict__ out, Ctl *__restrict__ ctl)
+                                              Tile *__restrict__ out, Ctl *__restrict__ ctl, const Sel &sel = Sel())
 {
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tiles; t += (uint64_t)gridDim.x * blockDim.x) {
         const Tile c = in[t];
@@ -716,7 +802,7 @@ __device__ __forceinline__ void bam_fix_tiles(const uint8_t *__restrict__ d, uin
         if (c.spec && c.entry != NONE)
             atomicAdd(&ctl->false_starts, 1ull);
         Tile o;
-        const uint64_t e = fix_tile<Q>(d, n, t, prev_exit(in, t, start0), t == ctl->first_bad, n_ref, excl, o);
+        const uint64_t e = fix_tile<Q, S>(d, n, t, prev_exit(in, t, start0), t == ctl->first_bad, n_ref, excl, o, sel);
         out[t] = o;
         if (e != NONE)
             atomicMin(&ctl->err_pos, (unsigned long long)e);
@@ -734,6 +820,18 @@ __global__ void __launch_bounds__(256) k_bam_fix_q(const uint8_t *__restrict__ d
                                                    const uint8_t *__restrict__ bad, Tile *__restrict__ out, Ctl *__restrict__ ctl)
 {
     bam_fix_tiles<true>(d, n, n_tiles, start0, n_ref, excl, in, bad, out, ctl);
+}
+__global__ void __launch_bounds__(256) k_bam_fix_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                     int32_t n_ref, Sel sel, const Tile *__restrict__ in, const uint8_t *__restrict__ bad,
+                                                     Tile *__restrict__ out, Ctl *__restrict__ ctl)
+{
+    bam_fix_tiles<false, true>(d, n, n_tiles, start0, n_ref, sel.excl, in, bad, out, ctl, sel);
+}
+__global__ void __launch_bounds__(256) k_bam_fix_q_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                       int32_t n_ref, Sel sel, const Tile *__restrict__ in,
+                                                       const uint8_t *__restrict__ bad, Tile *__restrict__ out, Ctl *__restrict__ ctl)
+{
+    bam_fix_tiles<true, true>(d, n, n_tiles, start0, n_ref, sel.excl, in, bad, out, ctl, sel);
 }
 
 // totals: one workgroup of 1024 threads, each over a run of consecutive tiles: the exclusive scan of the tiles' output bytes
@@ -908,6 +1006,99 @@ __global__ void __launch_bounds__(256) k_bam_decode_q_rev(const uint8_t *__restr
                                                           unsigned long long *__restrict__ reversed)
 {
     bam_decode_rev_tiles<true>(d, n, n_tiles, n_ref, excl, in, base, out, no_qual, reversed);
+}
+
+// decode with a selection set: the walk of the kernels above with kept() as the whole wavefront asks it — the same
+// rules 1 to 3, the same shortcut for a record that starts inside a region, and where the CIGAR decides, 64 operations per step,
+// one per lane, summed over the wavefront: the very sum the walking lane of spec / fix made, so the two agree on every record.
+__device__ __forceinline__ bool kept_wave(const uint8_t *rec, const RecHead &h, const Sel &s)
+{
+    const int r = kept_without_cigar(rec, h, s); // (wave-uniform: the record's head)
+    if (r >= 0)
+        return r != 0;
+    uint64_t span = cigar_span_part(rec, h, threadIdx.x & 63u, 64u);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)span, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(span >> 32), o);
+        span += (uint64_t)hi << 32 | lo;
+    }
+    return kmm_sel::region_pass(s, (int32_t)rd32(rec + 4), (int32_t)rd32(rec + 8), h.flag, span);
+}
+
+// Q: four-line FASTQ (no_qual counted); R: "original_strand" (reversed counted).  Both count kept records only.
+template <bool Q, bool R>
+__device__ __forceinline__ void bam_decode_sel_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                     const Sel &sel, const Tile *__restrict__ in, const unsigned long long *__restrict__ base,
+                                                     uint8_t *__restrict__ out, unsigned long long *__restrict__ no_qual,
+                                                     unsigned long long *__restrict__ reversed)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        const Tile c = in[t];
+        if (c.entry == NONE || c.recs == 0)
+            continue;
+        uint64_t p = c.entry, o = base[t];
+        const uint64_t o_end = o + c.bytes; // (the tile's share of `out`: what its walk counted)
+        uint32_t absent = 0, flips = 0;
+        while (p < c.exit) {
+            RecHead h;
+            if (record_at(d, n, p, n_ref, h) != REC_OK) // (cannot happen on a verified chain; bounds all the same)
+                break;
+            if (kept_wave(d + p, h, sel)) {
+                if (o + out_len<Q>(h.l_seq) > o_end) // (cannot happen: the walk and this pass ask one predicate; bounds all the same)
+                    break;
+                const bool rev = flipped(h, R);
+                if constexpr (Q) {
+                    if (rev)
+                        decode_record_q_rev(d + p, h, out + o, lane, 64u);
+                    else
+                        decode_record_q(d + p, h, out + o, lane, 64u);
+                    absent += qual_absent(d + p, h) ? 1u : 0u;
+                } else {
+                    if (rev)
+                        decode_record_rev(d + p, h, out + o, lane, 64u);
+                    else
+                        decode_record(d + p, h, out + o, lane, 64u);
+                }
+                o += out_len<Q>(h.l_seq);
+                flips += rev ? 1u : 0u;
+            }
+            p += 4ull + h.bs;
+        }
+        if (Q && lane == 0 && absent)
+            atomicAdd(no_qual, (unsigned long long)absent);
+        if (R && lane == 0 && flips)
+            atomicAdd(reversed, (unsigned long long)flips);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_bam_decode_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref, Sel sel,
+                                                        const Tile *__restrict__ in, const unsigned long long *__restrict__ base,
+                                                        uint8_t *__restrict__ out)
+{
+    bam_decode_sel_tiles<false, false>(d, n, n_tiles, n_ref, sel, in, base, out, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(256) k_bam_decode_q_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                          Sel sel, const Tile *__restrict__ in, const unsigned long long *__restrict__ base,
+                                                          uint8_t *__restrict__ out, unsigned long long *__restrict__ no_qual)
+{
+    bam_decode_sel_tiles<true, false>(d, n, n_tiles, n_ref, sel, in, base, out, no_qual, nullptr);
+}
+__global__ void __launch_bounds__(256) k_bam_decode_rev_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                            Sel sel, const Tile *__restrict__ in,
+                                                            const unsigned long long *__restrict__ base, uint8_t *__restrict__ out,
+                                                            unsigned long long *__restrict__ reversed)
+{
+    bam_decode_sel_tiles<false, true>(d, n, n_tiles, n_ref, sel, in, base, out, nullptr, reversed);
+}
+__global__ void __launch_bounds__(256) k_bam_decode_q_rev_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref,
+                                                              Sel sel, const Tile *__restrict__ in,
+                                                              const unsigned long long *__restrict__ base, uint8_t *__restrict__ out,
+                                                              unsigned long long *__restrict__ no_qual,
+                                                              unsigned long long *__restrict__ reversed)
+{
+    bam_decode_sel_tiles<true, true>(d, n, n_tiles, n_ref, sel, in, base, out, no_qual, reversed);
 }
 
 // resync: one wavefront per tile (grid-stride), the shape of spec; lanes test 64 consecutive positions, the survivors are

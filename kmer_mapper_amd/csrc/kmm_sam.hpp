@@ -19,11 +19,18 @@
 // 2 |SEQ| + 6 bytes per record, which the library maps as KMM_FORMAT_FASTQ, where "min_base_quality" is applied.
 // "original_strand"  has the write pass emit the kept records whose FLAG has 0x10 in read orientation: SEQ reversed
 // and complemented letter by letter, QUAL reversed.  The output lengths are the same: the count pass does not know of the switch.
+// Record selection (kmm_select.hpp has the rule): with an include mask, a MAPQ floor or a region list set, the count
+// and write passes run as their <.., true> / k_sam_*_sel forms: the line scan also finds TABs 3 to 6, and classify_sel reads, of
+// the records that pass the flag masks, MAPQ (with a floor) and RNAME, POS and CIGAR (with regions; RNAME looked up in the
+// handle's name table, POS and CIGAR read only of records on a listed reference).  A field that is read and malformed fails the
+// call (ERR_MAPQ, ERR_POS, ERR_CIGAR); a field no rule needs is not looked at.
 #pragma once
 
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "kmm_select.hpp"
 
 #if defined(__HIPCC__)
 #define KMM_SAM_HD __host__ __device__ __forceinline__
@@ -36,8 +43,14 @@ namespace kmm_sam {
 constexpr uint64_t NONE = ~0ull;
 constexpr uint32_t TILE = 1024;       // bytes per tile (the lines that start in it are its own)
 constexpr uint32_t WIN = 1024;        // bytes one wavefront reads per step of a line: 64 lanes x 16 bytes
-enum Err : uint32_t { ERR_QUAL = 0, ERR_FIELDS = 1, ERR_FLAG = 2, ERR_EMPTY = 3 }; // an error word = line start << 2 | code
-// (ERR_QUAL: the quality variant only — QUAL is not "*" and not as long as SEQ)
+enum Err : uint32_t { ERR_QUAL = 0, ERR_FIELDS = 1, ERR_FLAG = 2, ERR_EMPTY = 3, ERR_MAPQ = 4, ERR_POS = 5, ERR_CIGAR = 6 };
+// an error word = line start << 2 | code; with a selection (S: codes up to 6) line start << 3 | code
+// (ERR_QUAL: the quality variant only — QUAL is not "*" and not as long as SEQ.  With a selection only: ERR_MAPQ — MAPQ is not a
+// decimal integer in [0, 255]; ERR_POS — POS is not one in [0, 2^31 - 1]; ERR_CIGAR — CIGAR is neither "*" nor
+// ([0-9]+[MIDNSHP=X])+ with every length in [0, 2^28 - 1])
+using kmm_sel::Sel;
+template <bool S>
+KMM_SAM_HD uint32_t err_shift() { return S ? 3u : 2u; }
 enum Kind : uint32_t { K_KEPT = 0, K_EXCLUDED = 1, K_HEADER = 2, K_BAD = 3 };
 
 // One tile's lines: records kept / excluded, header lines, output bytes, the end of its last complete line (0: none), the
@@ -62,12 +75,20 @@ struct LineT {
 };
 typedef LineT<4> Line;
 typedef LineT<5> LineQ;
-KMM_SAM_HD uint32_t want_tab(int w) { return w < 2 ? (uint32_t)w + 1u : (uint32_t)w + 7u; } // 1, 2, 9, 10, 11
+// NT 4 / 5: TABs 1, 2, 9, 10, 11; with a selection (NT 8 / 9): 1 to 6, 9, 10, 11
+template <int NT>
+KMM_SAM_HD uint32_t want_tab(int w)
+{
+    if (NT >= 8)
+        return w < 6 ? (uint32_t)w + 1u : (uint32_t)w + 3u;
+    return w < 2 ? (uint32_t)w + 1u : (uint32_t)w + 7u;
+}
 
 struct LineInfo {
     uint32_t kind, err;
     uint64_t seq, seq_len; // SEQ of a record ("*": length 0)
     bool rev;              // FLAG has 0x10: the record is stored reverse-complemented
+    uint32_t flag;         // FLAG of a record
 };
 struct LineInfoQ : LineInfo {
     uint64_t qual; // QUAL of a record: seq_len bytes at d[qual], or
@@ -135,6 +156,7 @@ KMM_SAM_HD void classify(const uint8_t *d, uint64_t s, const Line &L, uint32_t e
     o.err = 0;
     o.seq = o.seq_len = 0;
     o.rev = false;
+    o.flag = 0;
     const uint64_t e = L.end;
     if (e == s || (e == s + 1 && d[s] == 13u)) {
         o.err = ERR_EMPTY;
@@ -167,6 +189,7 @@ KMM_SAM_HD void classify(const uint8_t *d, uint64_t s, const Line &L, uint32_t e
         o.seq_len = 0;
     o.kind = (flag & excl) ? K_EXCLUDED : K_KEPT;
     o.rev = (flag & 0x10u) != 0u;
+    o.flag = flag;
 }
 
 // The quality variant: what the line is, and its QUAL — the bytes between TAB 10 and TAB 11 (or the line's end, without a CR in
@@ -196,6 +219,143 @@ KMM_SAM_HD void classify(const uint8_t *d, uint64_t s, const LineQ &L, uint32_t 
         o.kind = K_BAD;
         o.err = ERR_QUAL;
     }
+}
+
+// ---- record selection ----
+
+// The decimal field d[b, e): false when it is empty, holds anything but digits, or exceeds max.
+KMM_SAM_HD bool parse_decimal(const uint8_t *d, uint64_t b, uint64_t e, uint64_t max, uint64_t &v)
+{
+    v = 0;
+    bool ok = e > b;
+    for (uint64_t q = b; q < e && ok; ++q) {
+        const uint32_t c = d[q];
+        ok = c >= (uint32_t)'0' && c <= (uint32_t)'9';
+        v = v * 10u + (c - (uint32_t)'0');
+        ok = ok && v <= max;
+    }
+    return ok;
+}
+
+KMM_SAM_HD bool is_digit(uint32_t c) { return c >= (uint32_t)'0' && c <= (uint32_t)'9'; }
+
+// The BAM code (0..8) of a CIGAR operation letter, 15: none
+KMM_SAM_HD uint32_t cigar_op(uint32_t c)
+{
+    switch (c) {
+    case 'M': return 0u;
+    case 'I': return 1u;
+    case 'D': return 2u;
+    case 'N': return 3u;
+    case 'S': return 4u;
+    case 'H': return 5u;
+    case 'P': return 6u;
+    case '=': return 7u;
+    case 'X': return 8u;
+    default: return 15u;
+    }
+}
+
+// The CIGAR text d[b, e) (not "*", not empty), the share of lane `lane` of `lanes`: the bytes b + lane, b + lane + lanes, ...
+// Every byte is judged where it stands, so the lanes need nothing of each other: a digit needs a byte behind it; an operation
+// letter needs the digits in front of it, which it reads (its length; M, D, N, = and X add it to span); any other byte is
+// malformed.  Together the lanes accept exactly ([0-9]+[MIDNSHP=X])+ with every length <= 2^28 - 1.
+KMM_SAM_HD bool cigar_text_part(const uint8_t *d, uint64_t b, uint64_t e, uint32_t lane, uint32_t lanes, uint64_t &span)
+{
+    bool ok = true;
+    for (uint64_t i = b + lane; i < e; i += lanes) {
+        const uint32_t c = d[i];
+        if (is_digit(c)) {
+            ok = ok && i + 1 < e;
+            continue;
+        }
+        const uint32_t op = cigar_op(c);
+        uint64_t q = i;
+        while (q > b && is_digit(d[q - 1]))
+            --q;
+        uint64_t v = 0;
+        for (uint64_t r = q; r < i; ++r) {
+            v = v * 10u + (d[r] - (uint32_t)'0');
+            if (v > kmm_sel::MAX_CIGAR_LEN)
+                v = kmm_sel::MAX_CIGAR_LEN + 1ull; // (too long, however many digits follow)
+        }
+        ok = ok && op != 15u && q < i && v <= kmm_sel::MAX_CIGAR_LEN;
+        if (op != 15u && kmm_sel::consumes_ref(op))
+            span += v;
+    }
+    return ok;
+}
+
+// The index of the name d[b, e) in the selection's name table, -1: not there (compared exactly and whole)
+KMM_SAM_HD int64_t find_name(const Sel &sel, const uint8_t *d, uint64_t b, uint64_t e)
+{
+    for (uint32_t i = 0; i < sel.n_names; ++i) {
+        const uint32_t o = sel.name_off[i], len = sel.name_off[i + 1] - o;
+        if ((uint64_t)len != e - b)
+            continue;
+        bool same = true;
+        for (uint32_t j = 0; j < len && same; ++j)
+            same = sel.names[o + j] == d[b + j];
+        if (same)
+            return (int64_t)i;
+    }
+    return -1;
+}
+
+// What the line is under a selection.  L holds TABs 1 to 6, 9, 10 (and 11: the quality variant).  The line's class, FLAG, SEQ and
+// (quality variant) QUAL are judged as without a selection; then, of a record, the rules in turn — each field read only when its
+// rule is set and the rules before it passed.  scan.cigar(b, e, span): the CIGAR text, read by the scanner's lanes together.
+template <int NT, class Info, class Scan>
+KMM_SAM_HD void classify_sel(const uint8_t *d, uint64_t s, const LineT<NT> &L, const Sel &sel, Scan &scan, Info &o)
+{
+    LineT<NT - 4> l;
+    l.end = L.end;
+    l.tab[0] = L.tab[0];
+    l.tab[1] = L.tab[1];
+    for (int w = 2; w < NT - 4; ++w)
+        l.tab[w] = L.tab[w + 4];
+    classify(d, s, l, 0u, o);
+    if (o.kind != K_KEPT)
+        return;
+    o.kind = K_EXCLUDED;
+    if (!kmm_sel::flags_pass(o.flag, sel))
+        return;
+    uint64_t v = 0;
+    if (sel.min_mapq > 0) {
+        if (!parse_decimal(d, L.tab[3] + 1, L.tab[4], 255u, v)) {
+            o.kind = K_BAD;
+            o.err = ERR_MAPQ;
+            return;
+        }
+        if (v < sel.min_mapq)
+            return;
+    }
+    if (sel.n_iv > 0) {
+        const uint64_t nb = L.tab[1] + 1, ne = L.tab[2];
+        if (ne - nb == 1 && d[nb] == (uint8_t)'*') {
+            if (sel.keep_unplaced)
+                o.kind = K_KEPT;
+            return;
+        }
+        const int64_t ref = find_name(sel, d, nb, ne);
+        if (ref < 0)
+            return;
+        if (!parse_decimal(d, L.tab[2] + 1, L.tab[3], 0x7FFFFFFFu, v)) {
+            o.kind = K_BAD;
+            o.err = ERR_POS;
+            return;
+        }
+        const uint64_t cb = L.tab[4] + 1, ce = L.tab[5];
+        uint64_t span = 0;
+        if (!(ce - cb == 1 && d[cb] == (uint8_t)'*') && (ce == cb || !scan.cigar(cb, ce, span))) {
+            o.kind = K_BAD;
+            o.err = ERR_CIGAR;
+            return;
+        }
+        if (!kmm_sel::region_pass(sel, ref, (int64_t)v - 1, o.flag, span))
+            return;
+    }
+    o.kind = K_KEPT;
 }
 
 template <bool Q>
@@ -280,7 +440,7 @@ inline void scan_line_lanes(const uint8_t *d, uint64_t n, uint64_t s, bool tabs,
                 tm &= (nm & (0u - nm)) - 1u; // (TABs behind the newline are another line's)
             const uint32_t cnt = tabs ? (uint32_t)__builtin_popcount(tm) : 0u;
             for (int w = 0; w < NT && tabs; ++w) {
-                const uint32_t k = want_tab(w);
+                const uint32_t k = want_tab<NT>(w);
                 if (L.tab[w] == NONE && seen < k && k <= seen + cnt)
                     L.tab[w] = (uint64_t)(a + 16 * (int64_t)lane + nth_bit(tm, k - seen));
             }
@@ -308,15 +468,15 @@ KMM_SAM_HD uint64_t tile_end(uint64_t t, uint64_t n) { return (t + 1) * TILE < n
 // (sink(LineInfo, offset of its output inside the tile's)).  The tile's first line starts at its first byte when the byte
 // before is a newline (or the tile is the first), else behind the first newline inside the tile — looked for inside the tile
 // only, so that a long line costs its own tiles one window each.
-template <bool Q = false, class Scan, class Sink>
-KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t excl, Scan &scan, Sink &sink, Tile &o)
+template <bool Q = false, bool S = false, class Scan, class Sink>
+KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t excl, Scan &scan, Sink &sink, Tile &o, const Sel &sel = Sel())
 {
     o.recs = o.excluded = o.headers = o.bytes = 0;
     o.last_end = 0;
     o.err = NONE;
     const uint64_t ts = t * TILE, te = tile_end(t, n);
     uint64_t s = ts;
-    LineT<Q ? 5 : 4> L;
+    LineT<(Q ? 5 : 4) + (S ? 4 : 0)> L;
     if (ts > 0 && d[ts - 1] != 10u) {
         scan(ts, false, te, L); // (the line in progress at the tile's start belongs to a tile before)
         if (L.end == NONE)
@@ -328,9 +488,12 @@ KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t exc
         if (L.end == NONE)
             return; // (no newline before the chunk ends: the line waits for the next call)
         typename InfoOf<Q>::type li;
-        classify(d, s, L, excl, li);
+        if constexpr (S)
+            classify_sel(d, s, L, sel, scan, li);
+        else
+            classify(d, s, L, excl, li);
         if (li.kind == K_BAD) {
-            o.err = s << 2 | li.err;
+            o.err = s << err_shift<S>() | li.err;
             return;
         }
         if (li.kind == K_HEADER)
@@ -351,10 +514,18 @@ KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t exc
 struct CpuScan {
     const uint8_t *d;
     uint64_t n;
+    uint32_t lanes = 64; // lanes cigar() reads a CIGAR text with, one after the other
     template <int NT>
     void operator()(uint64_t s, bool tabs, uint64_t stop, LineT<NT> &L)
     {
         scan_line_lanes(d, n, s, tabs, stop, L);
+    }
+    bool cigar(uint64_t b, uint64_t e, uint64_t &span)
+    {
+        bool ok = true;
+        for (uint32_t lane = 0; lane < lanes; ++lane)
+            ok = cigar_text_part(d, b, e, lane, lanes, span) && ok;
+        return ok;
     }
 };
 struct CpuSink {
@@ -386,18 +557,26 @@ struct CpuSink {
 // One chunk on the CPU: the count pass, the totals, the write pass (out: at least tot.out_bytes; null = count only).
 // Q: the quality variant (four-line FASTQ out; *no_qual: the kept records whose QUAL is absent, counted by the write pass).
 // orig: "original_strand" (*reversed: the records the write pass flipped); lanes: what emit is called with.
+// sel: the selection beyond excl (its own excl is not read); null or flags only: none.  With one, tot.err is line start << 3 | code.
 template <bool Q = false>
 inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out, Totals &tot, uint64_t *no_qual = nullptr,
-                      bool orig = false, uint64_t *reversed = nullptr, uint32_t lanes = 1)
+                      bool orig = false, uint64_t *reversed = nullptr, uint32_t lanes = 1, const Sel *sel = nullptr)
 {
     tot = Totals{0, 0, 0, 0, 0, NONE};
     const uint64_t n_tiles = (n + TILE - 1) / TILE;
     std::vector<uint64_t> base(n_tiles);
     CpuScan sc{d, n};
+    sc.lanes = lanes;
     CpuSink count{d, nullptr};
+    const bool selected = sel && !sel->flags_only();
+    Sel eff = selected ? *sel : Sel();
+    eff.excl = excl;
     for (uint64_t t = 0; t < n_tiles; ++t) {
         Tile o;
-        walk_tile<Q>(d, n, t, excl, sc, count, o);
+        if (selected)
+            walk_tile<Q, true>(d, n, t, excl, sc, count, o, eff);
+        else
+            walk_tile<Q>(d, n, t, excl, sc, count, o);
         base[t] = tot.out_bytes;
         tot.recs += o.recs;
         tot.excluded += o.excluded;
@@ -415,7 +594,10 @@ inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out,
         write.orig = orig;
         write.lanes = lanes;
         Tile o;
-        walk_tile<Q>(d, n, t, excl, sc, write, o);
+        if (selected)
+            walk_tile<Q, true>(d, n, t, excl, sc, write, o, eff);
+        else
+            walk_tile<Q>(d, n, t, excl, sc, write, o);
         if (no_qual)
             *no_qual += write.no_qual;
         if (reversed)
@@ -457,7 +639,7 @@ __device__ __forceinline__ void scan_line_wave(const uint8_t *__restrict__ d, ui
             const uint32_t before = seen + incl - cnt;
 #pragma unroll
             for (int w = 0; w < NT; ++w) {
-                const uint32_t k = want_tab(w);
+                const uint32_t k = want_tab<NT>(w);
                 const bool mine = L.tab[w] == NONE && before < k && k <= before + cnt;
                 const unsigned long long m = __ballot(mine);
                 if (m) {
@@ -483,6 +665,19 @@ struct WaveScan {
     __device__ void operator()(uint64_t s, bool tabs, uint64_t stop, LineT<NT> &L)
     {
         scan_line_wave(d, n, s, tabs, stop, L);
+    }
+    // (with a selection) the CIGAR text d[b, e): 64 bytes per step, one per lane; the verdict and the span are wave-uniform
+    __device__ bool cigar(uint64_t b, uint64_t e, uint64_t &span)
+    {
+        uint64_t part = 0;
+        const bool ok = cigar_text_part(d, b, e, threadIdx.x & 63u, 64u, part);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)part, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(part >> 32), o);
+            part += (uint64_t)hi << 32 | lo;
+        }
+        span += part;
+        return __ballot(!ok) == 0ull;
     }
 };
 struct NoSink {
@@ -690,6 +885,120 @@ __global__ void __launch_bounds__(256) k_sam_write_q_rev(const uint8_t *__restri
         WaveSinkQRev sink{d, out + base[t], 0u, 0u};
         Tile o;
         walk_tile<true>(d, n, t, excl, sc, sink, o);
+        if ((threadIdx.x & 63u) == 0 && sink.no_qual)
+            atomicAdd(no_qual, (unsigned long long)sink.no_qual);
+        if ((threadIdx.x & 63u) == 0 && sink.reversed)
+            atomicAdd(reversed, (unsigned long long)sink.reversed);
+    }
+}
+
+// ---- with a selection set: the passes above as <.., true>; kernels of their own — the ones above are what runs
+// without one.  sel.excl is the exclude mask.
+template <bool Q>
+__device__ __forceinline__ void sam_count_sel_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, const Sel &sel,
+                                                    Tile *__restrict__ tiles)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    WaveScan sc{d, n};
+    NoSink none;
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        Tile o;
+        walk_tile<Q, true>(d, n, t, sel.excl, sc, none, o, sel);
+        if ((threadIdx.x & 63u) == 0)
+            tiles[t] = o;
+    }
+}
+__global__ void __launch_bounds__(256) k_sam_count_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, Sel sel,
+                                                       Tile *__restrict__ tiles)
+{
+    sam_count_sel_tiles<false>(d, n, n_tiles, sel, tiles);
+}
+__global__ void __launch_bounds__(256) k_sam_count_q_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, Sel sel,
+                                                         Tile *__restrict__ tiles)
+{
+    sam_count_sel_tiles<true>(d, n, n_tiles, sel, tiles);
+}
+
+// A sink that stops at the end of the tile's share of the output (what the count pass gave it): the two passes ask one
+// predicate, so it never does; bounds all the same.
+template <class Inner>
+struct BoundedSink {
+    Inner in;
+    uint32_t cap;
+    __device__ void operator()(const LineInfo &li, uint32_t at)
+    {
+        if ((uint64_t)at + li.seq_len + 3u <= (uint64_t)cap)
+            in(li, at);
+    }
+    __device__ void operator()(const LineInfoQ &li, uint32_t at)
+    {
+        if ((uint64_t)at + 2u * li.seq_len + 6u <= (uint64_t)cap)
+            in(li, at);
+    }
+};
+
+template <bool Q, class Inner>
+__device__ __forceinline__ void sam_write_sel_tile(const uint8_t *__restrict__ d, uint64_t n, uint64_t t, const Sel &sel, uint32_t cap,
+                                                   Inner &inner)
+{
+    WaveScan sc{d, n};
+    BoundedSink<Inner> sink{inner, cap};
+    Tile o;
+    walk_tile<Q, true>(d, n, t, sel.excl, sc, sink, o, sel);
+    inner = sink.in;
+}
+
+__global__ void __launch_bounds__(256) k_sam_write_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, Sel sel,
+                                                       const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                       uint8_t *__restrict__ out)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        if (tiles[t].recs == 0)
+            continue;
+        WaveSink sink{d, out + base[t]};
+        sam_write_sel_tile<false>(d, n, t, sel, tiles[t].bytes, sink);
+    }
+}
+__global__ void __launch_bounds__(256) k_sam_write_q_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, Sel sel,
+                                                         const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                         uint8_t *__restrict__ out, unsigned long long *__restrict__ no_qual)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        if (tiles[t].recs == 0)
+            continue;
+        WaveSinkQ sink{d, out + base[t], 0u};
+        sam_write_sel_tile<true>(d, n, t, sel, tiles[t].bytes, sink);
+        if ((threadIdx.x & 63u) == 0 && sink.no_qual)
+            atomicAdd(no_qual, (unsigned long long)sink.no_qual);
+    }
+}
+__global__ void __launch_bounds__(256) k_sam_write_rev_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, Sel sel,
+                                                           const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                           uint8_t *__restrict__ out, unsigned long long *__restrict__ reversed)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        if (tiles[t].recs == 0)
+            continue;
+        WaveSinkRev sink{d, out + base[t], 0u};
+        sam_write_sel_tile<false>(d, n, t, sel, tiles[t].bytes, sink);
+        if ((threadIdx.x & 63u) == 0 && sink.reversed)
+            atomicAdd(reversed, (unsigned long long)sink.reversed);
+    }
+}
+__global__ void __launch_bounds__(256) k_sam_write_q_rev_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, Sel sel,
+                                                             const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                             uint8_t *__restrict__ out, unsigned long long *__restrict__ no_qual,
+                                                             unsigned long long *__restrict__ reversed)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        if (tiles[t].recs == 0)
+            continue;
+        WaveSinkQRev sink{d, out + base[t], 0u, 0u};
+        sam_write_sel_tile<true>(d, n, t, sel, tiles[t].bytes, sink);
         if ((threadIdx.x & 63u) == 0 && sink.no_qual)
             atomicAdd(no_qual, (unsigned long long)sink.no_qual);
         if ((threadIdx.x & 63u) == 0 && sink.reversed)

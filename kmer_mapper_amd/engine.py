@@ -363,6 +363,20 @@ class DeviceIndex:
         "count_kmers"."""
         _lib.check(_lib.lib().kmm_set_param(self._h, name.encode(), int(value)))
 
+    def set_record_regions(self, regions, keep_unplaced=False):
+        """kmm_set_record_regions: only SAM / BAM records that overlap one of `regions` are mapped (beside "bam_exclude_flags",
+        "bam_include_flags" and "bam_min_mapq"; include/kmm.h RECORD SELECTION).  regions: [(ref_name, ref_id, beg, end)],
+        0-based half-open, as util.parse_regions / util.read_bed_regions give them — ref_name (str / bytes, or None) selects SAM
+        records, ref_id (an index into the BAM header's references, or None / -1) BAM records.  keep_unplaced: the records
+        without a reference pass.  An empty list clears the selection.  get_param("record_regions"): intervals after merging."""
+        regions = list(regions or ())
+        arr = (_lib.Region * max(len(regions), 1))()
+        for i, (name, ref_id, beg, end) in enumerate(regions):
+            arr[i].ref_name = None if name is None else (name if isinstance(name, bytes) else str(name).encode())
+            arr[i].ref_id = -1 if ref_id is None else int(ref_id)
+            arr[i].beg, arr[i].end = int(beg), int(end)
+        _lib.check(_lib.lib().kmm_set_record_regions(self._h, arr, len(regions), int(bool(keep_unplaced))))
+
     def get_param(self, name):
         v = ctypes.c_int64(0)
         _lib.check(_lib.lib().kmm_get_param(self._h, name.encode(), ctypes.byref(v)))

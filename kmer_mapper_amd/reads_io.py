@@ -255,6 +255,61 @@ def bam_header(refs=(), text=b""):
     return b"".join(out)
 
 
+def bam_references(path_or_buffer):
+    """The references of a BAM file's header, [(name, length)], in header order: a record's refID is an index into it.  Only
+    the header is needed, so only the file's first BGZF members are inflated, here on the host (zlib), one at a time until the
+    header is whole — it may span several."""
+    import os
+    import struct
+    import zlib
+    f = open(path_or_buffer, "rb") if isinstance(path_or_buffer, (str, os.PathLike)) else None
+    data = b"" if f else bytes(path_or_buffer)
+    raw, at = b"", 0
+
+    def more():
+        """One more member's inflated bytes; False at the end of the file."""
+        nonlocal raw, at, data
+        if f:
+            head = f.read(18)
+        else:
+            head = data[at:at + 18]
+        if len(head) < 18:
+            return False
+        if head[:4] != b"\x1f\x8b\x08\x04" or head[12:14] != b"BC":
+            raise ValueError("not a BAM file: no BGZF member at byte %d" % at)
+        size = struct.unpack("<H", head[16:18])[0] + 1
+        body = f.read(size - 18) if f else data[at + 18:at + size]
+        if len(body) < size - 18:
+            raise ValueError("the BAM file ends inside a BGZF member (byte %d)" % at)
+        at += size
+        raw += zlib.decompress(body[:-8], -15)
+        return True
+
+    def need(n):
+        while len(raw) < n:
+            if not more():
+                raise ValueError("the BAM file ends inside its header")
+    try:
+        need(12)
+        if raw[:4] != b"BAM\1":
+            raise ValueError("not a BAM file: the magic is %r" % raw[:4])
+        p = 8 + struct.unpack("<I", raw[4:8])[0]
+        need(p + 4)
+        n_ref = struct.unpack("<I", raw[p:p + 4])[0]
+        p += 4
+        refs = []
+        for _ in range(n_ref):
+            need(p + 4)
+            l_name = struct.unpack("<I", raw[p:p + 4])[0]
+            need(p + 8 + l_name)
+            refs.append((raw[p + 4:p + 4 + l_name].rstrip(b"\0").decode(), struct.unpack("<I", raw[p + 4 + l_name:p + 8 + l_name])[0]))
+            p += 8 + l_name
+        return refs
+    finally:
+        if f:
+            f.close()
+
+
 def bgzf_members(data, block=0xFF00, level=6):
     """`data` as BGZF members of at most `block` inflated bytes (no EOF member)."""
     import struct

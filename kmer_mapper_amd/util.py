@@ -86,3 +86,86 @@ def as_read_batch(chunk_sequence):
 def get_kmer_hashes_from_chunk_sequence(chunk_sequence, kmer_size, lut=None, device=0):
     batch = as_read_batch(chunk_sequence)
     return extract_kmers(batch.bases, batch.offsets, kmer_size, lut=lut, device=device)
+
+
+REGION_END_MAX = (1 << 31) - 1     # "to the end of the reference": behind every position a record can have
+
+
+def _reference_ids(references):
+    return None if references is None else {(n.decode() if isinstance(n, bytes) else str(n)): i for i, (n, _) in enumerate(references)}
+
+
+def _parse_interval(text, spec):
+    """`5`, `5-`, `5-9`, commas allowed: 1-based inclusive -> (beg, end) 0-based half-open; None: `text` is no interval."""
+    t = text.replace(",", "")
+    first, dash, last = t.partition("-")
+    if not first.isdigit() or (last and not last.isdigit()):
+        return None
+    beg = max(int(first) - 1, 0)
+    end = int(last) if last else REGION_END_MAX
+    if end <= beg:
+        raise ValueError("region %r: the end lies before the start" % spec)
+    return beg, end
+
+
+def parse_regions(text_or_list, references=None):
+    """Regions in samtools syntax -> ([(ref_name, ref_id, beg, end)], keep_unplaced), 0-based half-open, for
+    DeviceIndex.set_record_regions.  `text_or_list`: one string of comma-separated regions — a comma in front of exactly three digits is
+    a thousands separator, so a reference named by three digits goes into a list — or a list of region strings.  A region: `chr6:28,000,000-34,000,000` (1-based, inclusive), `chr6:5` or
+    `chr6:5-` (from base 5 to the end), a bare reference name (all of it), or `*`: the records without a reference.
+    references: the file's [(name, length)] (reads_io.bam_references) — names become ids, an unknown name is an error that names
+    it, and a name that itself contains ':' is found as htslib finds it: the whole string is tried as a name first.  None (SAM
+    needs no header): the ids are -1, and a string is split at its last ':' when what follows reads as an interval."""
+    import re
+    if isinstance(text_or_list, (str, bytes)):
+        text = text_or_list.decode() if isinstance(text_or_list, bytes) else text_or_list
+        specs = [t for t in re.split(r",(?!\d{3}(?:\D|$))", text)]          # (a comma in front of three digits separates thousands)
+    else:
+        specs = [t.decode() if isinstance(t, bytes) else str(t) for t in text_or_list]
+    ids = _reference_ids(references)
+    regions, keep_unplaced = [], False
+    for spec in (t.strip() for t in specs):
+        if not spec:
+            raise ValueError("an empty region in %r" % (text_or_list,))
+        if spec == "*":
+            keep_unplaced = True
+            continue
+        name, interval = spec, (0, REGION_END_MAX)
+        if ids is None or spec not in ids:                                  # (htslib: the whole string as a name first)
+            head, colon, tail = spec.rpartition(":")
+            got = _parse_interval(tail, spec) if colon and head else None
+            if got is not None:
+                name, interval = head, got
+            elif ids is not None:
+                raise ValueError("region %r: the file has no reference named %r" % (spec, spec))
+        if ids is not None and name not in ids:
+            raise ValueError("region %r: the file has no reference named %r" % (spec, name))
+        if name == "*" or len(name.encode()) > 255:
+            raise ValueError("region %r: %r cannot be a reference name" % (spec, name))
+        regions.append((name, -1 if ids is None else ids[name], interval[0], interval[1]))
+    return regions, keep_unplaced
+
+
+def read_bed_regions(path_or_lines, references=None):
+    """The regions of a BED file -> [(ref_name, ref_id, beg, end)]: three columns (more are ignored), 0-based half-open as they
+    stand; empty lines and lines that start with '#', 'track' or 'browser' are skipped.  references: as parse_regions."""
+    if isinstance(path_or_lines, (str, bytes)):
+        with open(path_or_lines, "r") as f:
+            lines = f.read().splitlines()
+    else:
+        lines = [t.decode() if isinstance(t, bytes) else t for t in path_or_lines]
+    ids = _reference_ids(references)
+    regions = []
+    for no, line in enumerate(lines, 1):
+        if not line.strip() or line.startswith("#") or line.split()[0] in ("track", "browser"):
+            continue
+        cols = line.rstrip("\r\n").split("\t") if "\t" in line else line.split()
+        if len(cols) < 3 or not cols[1].isdigit() or not cols[2].isdigit():
+            raise ValueError("BED line %d: three columns (name, start, end) are needed: %r" % (no, line))
+        name, beg, end = cols[0], int(cols[1]), int(cols[2])
+        if end <= beg:
+            raise ValueError("BED line %d: the end lies at or before the start: %r" % (no, line))
+        if ids is not None and name not in ids:
+            raise ValueError("BED line %d: the file has no reference named %r" % (no, name))
+        regions.append((name, -1 if ids is None else ids[name], beg, end))
+    return regions
