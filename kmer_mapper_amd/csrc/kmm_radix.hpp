@@ -19,9 +19,12 @@
 //   pass 1  k_rx_p1   reads (or a k-mer array) -> k-mers; every workgroup sorts a block of 8192 positions
 //                     by COARSE partition inside LDS and writes the sorted block contiguously into its own
 //                     block area, plus a directory row start1[block][0..F1] (where each run starts)
-//           k_rx_colsum / k_rx_chunkscan / k_rx_tables / k_rx_colscan   column prefix of the directory: P1T[c][block] = k-mers of
-//                     coarse partition c before that block, so that c's runs form one virtual array; it is
-//                     cut into items of 8192 k-mers (item_desc = first block, c)
+//           k_rx_colsum / k_rx_chunkscan / k_rx_tables / k_rx_colscan   column prefix of the directory: the k-mers of
+//                     coarse partition c before each block, so that c's runs form one virtual array; it is cut
+//                     into items of 8192 k-mers.  Kept for pass 2: S1T[c][block] = the directory transposed, and
+//                     item_desc = (first block, where that block's run starts in the virtual array): k_rx_p2f
+//                     rebuilds the other run starts from the run lengths S1T[c + 1][b] - S1T[c][b].  (k_rx_p2
+//                     reads them from P1T[c][block], which only the scan in front of it writes.)
 //   pass 2  k_rx_p2f  item (c, j): gathers its 8192 k-mers from the runs (each ~B/F1 k-mers, contiguous), drops those
 //                     whose bucket is empty (LDS bitmap of the coarse partition, where one fits), sorts the rest by
 //                     FINE partition inside LDS, writes the sorted item + directory row start2
@@ -136,13 +139,13 @@ struct RxView {
     uint32_t max_items;
     uint64_t *buf1, *buf2;
     uint16_t *start1;      // [NB][F1 + 1]
-    uint32_t *P1T;         // [F1][NB + 1]
+    uint32_t *P1T;         // [F1][NB + 1]  (written and read only with k_rx_p2, "radix_filter" = 0)
     uint16_t *S1T;         // [F1][NB]
     uint32_t *csum;        // [chunks][F1]
     uint32_t *T1;          // [F1]
     uint32_t *item_base;   // [F1 + 1]
     uint32_t *work_base;   // [F1 + 1] pass-3 rows (coarse partition, chunk of RX_IC items) before coarse partition c
-    uint2 *item_desc;      // [max_items] {first block, coarse partition}
+    uint2 *item_desc;      // [max_items] {first block, virtual start of that block's run} (k_rx_p2: {first block, coarse partition})
     uint16_t *start2;      // [max_items][F2 + 1]
     uint16_t *start2T;     // [F2 + 1][max_items] (transposed for pass 3: one fine partition's run starts are contiguous)
     uint32_t *ctrl;        // [0] items, [1] pass-3 rows, [2] most items of one coarse partition
@@ -948,6 +951,8 @@ __device__ __forceinline__ uint32_t scan256_excl(uint32_t v, uint32_t *s_wave4, 
 }
 
 // One workgroup per coarse partition: its chunk sums -> exclusive chunk offsets (in place), the partition total.
+// WITH_P: as in k_rx_colscan.
+template <bool WITH_P>
 __global__ void __launch_bounds__(256) k_rx_chunkscan(RxView rx, uint32_t n_chunks)
 {
     __shared__ uint32_t s_wave4[4];
@@ -964,7 +969,8 @@ __global__ void __launch_bounds__(256) k_rx_chunkscan(RxView rx, uint32_t n_chun
     }
     if (threadIdx.x == 0) {
         rx.T1[c] = carry;
-        rx.P1T[(size_t)c * (rx.NB + 1) + rx.NB] = carry;
+        if constexpr (WITH_P) // (the closing entry of the partition's P1T row: k_rx_p2 reads P[b + 1])
+            rx.P1T[(size_t)c * (rx.NB + 1) + rx.NB] = carry;
     }
 }
 
@@ -1030,10 +1036,20 @@ __global__ void __launch_bounds__(512) k_rx_tables(RxView rx)
 // registers instead — a thread holds 32 consecutive entries of its row: 16-byte stores, no LDS, no barrier — and it was
 // slower, the more so the shorter the pieces: directory scans 0.624 -> 0.675 ms at 32 blocks per step, 0.825 at 16,
 // 0.976 at 8 (profiles/r04/ab_colscan_direct_stores.txt): the kernel is bound by the granularity of its writes.)
+// WITH_P = false (k_rx_p2f follows): no P1T.  A run's length is the difference of two neighbouring columns of the
+// directory row, which pass 2 reads as S1T[c + 1][b] - S1T[c][b]; the one absolute position it needs per item, the
+// virtual start of the run of the item's first block, travels in item_desc.y.  With 16-bit values only the tile holds 64
+// blocks (two register rounds of 32), so a partition's piece is 128 bytes again.  Measured (profiles/run_lengths): all scan
+// kernels 0.63 ms with P1T, 0.357 without; 0.376 with the 32-block tile (64-byte pieces).  Taking hi[u] from the next
+// lane's lo[u] (ds_bpermute) instead of loading it: 0.77 ms.  Loading the 64 directory rows as one contiguous piece into LDS
+// (16-byte loads, one workgroup per chunk) and walking the columns there: 0.385.
+template <bool WITH_P>
 __global__ void __launch_bounds__(256) k_rx_colscan(RxView rx)
 {
-    constexpr int TB = 32, CW = 256; // blocks per tile; coarse partitions per sweep (F1 > 256: two sweeps = grid.y)
-    __shared__ uint32_t tP[CW][TB + 1];
+    constexpr int RB = 32;                    // blocks per register round
+    constexpr int TB = WITH_P ? 32 : 64, CW = 256; // blocks per tile; coarse partitions per sweep (F1 > 256: two sweeps = grid.y)
+    static_assert(RX_CH % TB == 0 && TB % RB == 0, "a chunk is whole tiles, a tile whole register rounds");
+    __shared__ uint32_t tP[WITH_P ? CW : 1][TB + 1];
     __shared__ uint16_t tS[CW][TB + 2];
     const uint32_t F1 = rx.F1, NB = rx.NB;
     const uint32_t b0 = blockIdx.x * RX_CH;
@@ -1049,35 +1065,47 @@ __global__ void __launch_bounds__(256) k_rx_colscan(RxView rx)
     for (uint32_t t0 = b0; t0 < b1; t0 += TB) {
         const uint32_t nb = b1 - t0 < (uint32_t)TB ? b1 - t0 : (uint32_t)TB;
         if (c < F1) {
-            const uint16_t *p = rx.start1 + (size_t)t0 * ld + c;
-            uint32_t lo[TB], hi[TB];
+#pragma unroll 1
+            for (uint32_t r0 = 0; r0 < (uint32_t)TB; r0 += RB) { // (the registers of one round serve the next)
+                const uint16_t *p = rx.start1 + (size_t)(t0 + r0) * ld + c;
+                uint32_t lo[RB], hi[RB];
 #pragma unroll
-            for (int u = 0; u < TB; ++u) { // independent loads first: the walk is latency-bound
-                lo[u] = (uint32_t)u < nb ? p[u * ld] : 0u;
-                hi[u] = (uint32_t)u < nb ? p[u * ld + 1] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < TB; ++u) {
-                const uint32_t cnt = hi[u] - lo[u];
-                tP[threadIdx.x][u] = run;
-                tS[threadIdx.x][u] = (uint16_t)lo[u];
-                if (cnt) { // items whose first k-mer lies in this run
-                    uint32_t m = (run + RX_B - 1) / RX_B;
-                    while ((uint64_t)m * RX_B < (uint64_t)run + cnt) {
-                        rx.item_desc[ib + m] = make_uint2(t0 + u, c);
-                        ++m;
-                    }
+                for (int u = 0; u < RB; ++u) { // independent loads first: the walk is latency-bound
+                    lo[u] = r0 + (uint32_t)u < nb ? p[u * ld] : 0u;
+                    hi[u] = r0 + (uint32_t)u < nb ? p[u * ld + 1] : 0u;
                 }
-                run += cnt;
+#pragma unroll
+                for (int u = 0; u < RB; ++u) {
+                    const uint32_t cnt = hi[u] - lo[u];
+                    if constexpr (WITH_P)
+                        tP[threadIdx.x][r0 + u] = run;
+                    tS[threadIdx.x][r0 + u] = (uint16_t)lo[u];
+                    if (cnt) { // items whose first k-mer lies in this run
+                        uint32_t m = (run + RX_B - 1) / RX_B;
+                        while ((uint64_t)m * RX_B < (uint64_t)run + cnt) {
+                            rx.item_desc[ib + m] = make_uint2(t0 + r0 + u, WITH_P ? c : run);
+                            ++m;
+                        }
+                    }
+                    run += cnt;
+                }
             }
         }
         __syncthreads();
-        // two partitions per wavefront instruction, 32 consecutive blocks each
-        const uint32_t bi = lane & 31;
-        for (uint32_t cc = wave * 2 + (lane >> 5); cc < nc; cc += 8) {
-            if (bi < nb) {
-                rx.P1T[(size_t)(cb + cc) * (NB + 1) + t0 + bi] = tP[cc][bi];
-                rx.S1T[(size_t)(cb + cc) * NB + t0 + bi] = tS[cc][bi];
+        if constexpr (WITH_P) {
+            // two partitions per wavefront instruction, 32 consecutive blocks each
+            const uint32_t bi = lane & 31;
+            for (uint32_t cc = wave * 2 + (lane >> 5); cc < nc; cc += 8) {
+                if (bi < nb) {
+                    rx.P1T[(size_t)(cb + cc) * (NB + 1) + t0 + bi] = tP[cc][bi];
+                    rx.S1T[(size_t)(cb + cc) * NB + t0 + bi] = tS[cc][bi];
+                }
+            }
+        } else {
+            // one partition per wavefront instruction, 64 consecutive blocks
+            for (uint32_t cc = wave; cc < nc; cc += 4) {
+                if (lane < nb)
+                    rx.S1T[(size_t)(cb + cc) * NB + t0 + lane] = tS[cc][lane];
             }
         }
         __syncthreads();
@@ -1358,7 +1386,8 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
     __shared__ uint32_t t_empty[2];            // two masks); != 0: an EMPTY run starts inside the item (mask unusable)
     __shared__ __attribute__((aligned(8))) uint32_t s_cnt2[2][RX_MAXF + 2 + 64]; // the sort's counters: items alternate
     __shared__ uint32_t s_base[RX_MAXF + 1], s_wave[4];
-    __shared__ uint32_t s_b0[P2F_KMAX];
+    __shared__ uint32_t s_b0[P2F_KMAX], s_v0[P2F_KMAX]; // the unit's items: first block, virtual start of that block's run
+    __shared__ uint32_t s_tot[3][P2F_NT / 64]; // run lengths summed per wavefront: rows 0 / 1 by item parity, 2: more_rounds
     __shared__ uint32_t s_idx;
     const int tid = threadIdx.x, lane = tid & 63;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1384,9 +1413,16 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
         s_cnt2[0][tid] = s_cnt2[1][tid] = 0; // (rx_sort_emit)
     RX_PT_DECL;
 
+    // A thread's run of a table: no absolute positions are stored between the passes.  The run's length is the difference
+    // of two neighbouring columns of pass 1's directory row (both <= RX_B: 16 bits each); where the run starts in the
+    // coarse partition's virtual array = the start of the table's first run (item_desc.y, or where the previous table of
+    // the item ended) + the lengths of the table's runs before it: a prefix over the 1024 threads, `inc` its
+    // per-wavefront part (prescan), the wavefronts' totals through s_tot and one barrier (put_table).
+    // (load_desc leaves the two loaded values as they are: arithmetic on them at the place of the loads made the compiler
+    // wait there — s_waitcnt vmcnt(0), which also drains the k-mer requests in flight: pass 2 5.97 -> 6.52 ms)
     struct RunDesc {
-        uint32_t vs, ve, st;
-    };
+        uint32_t a, b; // as loaded: start inside the block, the next coarse partition's start there (both <= RX_B);
+    };                 // after prescan: length << 16 | start, inclusive prefix of the lengths over the wavefront
     for (uint32_t turn = 0; turn < 8u; ++turn) {
     const uint32_t sub = (home + turn) & 7u;
     for (;;) {
@@ -1406,11 +1442,18 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
         const uint32_t j0 = cu * P2F_K;
         const uint32_t n_it = n_items_c - j0 < P2F_K ? n_items_c - j0 : P2F_K;
         const uint32_t Tc = rx.T1[cc];
-        const uint32_t *P = rx.P1T + (size_t)cc * (NB + 1);
+        // where a run ends inside its block = where the next coarse partition's begins: the next row of S1T, or, behind the
+        // last coarse partition, the block's total in the directory row itself (strided: one partition in F1)
         const uint16_t *S = rx.S1T + (size_t)cc * NB;
+        const bool last_c = cc + 1u >= rx.F1;
+        const uint16_t *SN = last_c ? rx.start1 + rx.F1 : S + NB;
+        const uint32_t sn = last_c ? rx.F1 + 1u : 1u;
         // unit prologue: first blocks of the unit's items, the coarse partition's bitmap
-        if ((uint32_t)tid < n_it)
-            s_b0[tid] = rx.item_desc[ib + j0 + tid].x;
+        if ((uint32_t)tid < n_it) {
+            const uint2 d = rx.item_desc[ib + j0 + tid];
+            s_b0[tid] = d.x;
+            s_v0[tid] = d.y;
+        }
         if (nofilt) {
         } else if (SLOT || gs == 0) {
             const uint4 *src = reinterpret_cast<const uint4 *>((SLOT ? rx.slots : rx.occ) + (size_t)cc * nwords);
@@ -1449,34 +1492,54 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
         auto load_desc = [&](uint32_t bb) {
             RunDesc r;
             const uint32_t b = bb + tid;
-            r.vs = 0xFFFFFFFFu; r.ve = 0xFFFFFFFFu; r.st = 0;
+            r.a = 0; r.b = 0; // (a thread beyond the last block: an empty run where the partition ends)
             if (b < NB) {
-                r.vs = P[b];
-                r.ve = P[b + 1];
-                r.st = S[b];
+                r.a = S[b];
+                r.b = SN[b * sn]; // (32 bits: 2^32 directory entries would belong to 2^23 blocks, 512 GB of k-mers)
             }
             return r;
+        };
+        // the wavefront's part of the prefix; a barrier lies between this and put_table of the same row (every lane active)
+        auto prescan = [&](RunDesc &r, uint32_t row) {
+            const uint32_t len = r.b - r.a;
+            r.a |= len << 16;
+            r.b = wave_scan_incl(len);
+            if (lane == 63)
+                s_tot[row][wave] = r.b;
         };
         // Table of the runs [bb, bb + 1024) for the item [lo, hi).  Besides its own row every thread marks the run of
         // each k-mer lo + 64 a that lies in its run (t_aux), and of the item's last covered k-mer (t_last): the search of
         // a wavefront's 64 consecutive k-mers then starts from two table indices a few runs apart instead of 0 .. 1023.
-        auto put_table = [&](const RunDesc &r, uint32_t lo, uint32_t hi, int mb = -1) {
+        // v0: where the table's first run starts; row: the row of s_tot that prescan(r, row) wrote before the last barrier.
+        // Threads beyond the last block (b >= NB) carry an empty run at the running total, and a table that has reached
+        // NB has summed every run of the partition from v0 on: that total is Tc >= hi.  So without a sentinel value
+        //   * such a thread sets no mask bit and no t_empty (vs < hi fails), marks no t_aux / t_last (from < to fails);
+        //   * cover = t_vs[P2F_NT] >= hi as soon as the table holds the partition's last block: more_rounds ends;
+        //   * the binary search and the broadcast walk move between the table indices A[u] and A[u + 1] only, whatever
+        //     the entries say: an entry Tc <= v can be stepped onto only by a slot beyond the partition's end, which
+        //     holds no bit of the returned mask, and whose element index is clamped into pass 1's output like any other.
+        auto put_table = [&](const RunDesc &r, uint32_t v0, uint32_t row, uint32_t lo, uint32_t hi, int mb = -1) {
+            const uint32_t len = r.a >> 16, st = r.a & 0xFFFFu;
+            // the totals of the wavefronts below: lanes 0 .. 15 hold one each, lane 15 of the scan their sum
+            const uint32_t tot = s_tot[row][lane & 15];
+            const uint32_t below = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl((uint32_t)lane < wave ? tot : 0u), 15);
+            const uint32_t vs = v0 + below + r.b - len, ve = vs + len;
             // (first table of an item, mb = the item's mask: cleared two items ago, behind that item's barriers)
-            if (mb >= 0 && r.vs != 0xFFFFFFFFu && r.vs > lo && r.vs < hi) {
-                if (r.ve > r.vs)
-                    atomicOr(&t_sbits[mb][(r.vs - lo) >> 5], 1u << ((r.vs - lo) & 31u));
+            if (mb >= 0 && vs > lo && vs < hi) {
+                if (len > 0u)
+                    atomicOr(&t_sbits[mb][(vs - lo) >> 5], 1u << ((vs - lo) & 31u));
                 else
                     t_empty[mb] = 1u; // two runs would share the bit
             }
-            t_vs[tid] = r.vs;
-            t_off[tid] = (uint32_t)tid * RX_B + r.st - r.vs; // (modulo 2^32: the sum with v is < 1025 x 8192)
+            t_vs[tid] = vs;
+            t_off[tid] = (uint32_t)tid * RX_B + st - vs; // (modulo 2^32: the sum with v is < 1025 x 8192)
             if (tid == P2F_NT - 1) {
-                t_vs[P2F_NT] = r.ve; // virtual position the table covers up to (all ones: to the partition's end)
-                if (r.ve < hi)
+                t_vs[P2F_NT] = ve; // virtual position the table covers up to (the partition's total once it reaches NB)
+                if (ve < hi)
                     t_last = P2F_NT - 1;
             }
-            const uint32_t from = r.vs > lo ? r.vs : lo, to = r.ve < hi ? r.ve : hi;
-            if (r.vs != 0xFFFFFFFFu && from < to) {
+            const uint32_t from = vs > lo ? vs : lo, to = ve < hi ? ve : hi;
+            if (from < to) { // (never an empty run)
                 for (uint32_t a = (from - lo + 63u) >> 6; lo + (a << 6) < to; ++a)
                     t_aux[a] = (uint16_t)tid;
                 if (to == hi)
@@ -1593,15 +1656,18 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
         // One item: xa holds its k-mers (mask vma); the next item's are requested into xb while this one is sorted.
         uint32_t cover = 0, b0 = 0;
         RunDesc rd;
-        rd.vs = rd.ve = 0xFFFFFFFFu; rd.st = 0;
+        rd.a = 0; rd.b = 0;
         // rounds beyond the first 1024 runs of item j (rare: tiny runs): table by table, into the same slots
         auto more_rounds = [&](uint32_t j, uint64_t (&x)[P2F_KPT], uint32_t &vm) {
             const uint32_t lo = item_lo(j), n = item_n(j), hi = lo + n;
             uint32_t bb = b0 + P2F_NT;
-            while (cover < hi) { // (uniform)
-                __syncthreads(); // the table's last readers are done
-                const RunDesc r2 = load_desc(bb);
-                put_table(r2, lo, hi);
+            // (uniform; the next table starts where this one ended.  bb < NB: a table beyond the last block would add nothing
+            // to cover — tables that do not sum to the partition's total fail the conservation check instead of looping)
+            while (cover < hi && bb < NB) {
+                RunDesc r2 = load_desc(bb);
+                prescan(r2, 2u);
+                __syncthreads(); // the table's last readers are done; the wavefronts' totals are published
+                put_table(r2, cover, 2u, lo, hi);
                 __syncthreads();
                 const uint32_t cover2 = t_vs[P2F_NT];
                 vm |= fill(std::true_type(), bb, lo, n, cover, cover2, x);
@@ -1646,6 +1712,11 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
             gathered += (uint32_t)__popc(vma);
             dropped += (uint32_t)__popc(vma) - n_ok;
             RX_PT(5); // waiting for the requests + filter
+            // item j + 2's run lengths, requested one item ago, behind item j's k-mers: they are here.  (Behind the requests of
+            // item j + 1 instead, the wait for them drained those requests in front of the ranking.)  Barrier 1 publishes
+            // the wavefronts' totals.
+            if (j + 2u < n_it)
+                prescan(rd, j & 1u);
             if (j + 1u < n_it) {
                 const uint32_t lo1 = item_lo(j + 1u), n1 = item_n(j + 1u);
                 b0 = s_b0[j + 1u];
@@ -1658,7 +1729,7 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
             auto fine = [&](int i) { return keys[i]; };
             auto mid = [&]() { // between barrier 1 and the scan: every request of item j + 1 has read the table
                 if (j + 2u < n_it) {
-                    put_table(rd, item_lo(j + 2u), item_lo(j + 2u) + item_n(j + 2u), (int)(j & 1u));
+                    put_table(rd, s_v0[j + 2u], j & 1u, item_lo(j + 2u), item_lo(j + 2u) + item_n(j + 2u), (int)(j & 1u));
                     if (j + 3u < n_it)
                         rd = load_desc(s_b0[j + 3u]);
                 }
@@ -1679,9 +1750,13 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
         uint32_t vm0 = 0, vm1 = 0;
         b0 = s_b0[0];
         rd = load_desc(b0);
-        put_table(rd, item_lo(0), item_lo(0) + item_n(0), 0);
-        if (n_it > 1u)
+        prescan(rd, 0u);
+        __syncthreads();
+        put_table(rd, s_v0[0], 0u, item_lo(0), item_lo(0) + item_n(0), 0);
+        if (n_it > 1u) {
             rd = load_desc(s_b0[1]);
+            prescan(rd, 1u);
+        }
         __syncthreads();
         cover = t_vs[P2F_NT];
         vm0 = fill(std::false_type(), b0, item_lo(0), item_n(0), item_lo(0), cover, x0, 0);
@@ -1695,7 +1770,7 @@ __global__ void __launch_bounds__(P2F_NT) k_rx_p2f(IndexView iv, RxView rx)
         if (tid == 0)
             t_empty[0] = 0u;
         if (n_it > 1u) {
-            put_table(rd, item_lo(1), item_lo(1) + item_n(1), 1);
+            put_table(rd, s_v0[1], 1u, item_lo(1), item_lo(1) + item_n(1), 1);
             if (n_it > 2u)
                 rd = load_desc(s_b0[2]);
         }

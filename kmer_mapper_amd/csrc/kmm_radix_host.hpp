@@ -243,10 +243,15 @@ int launch_rx(kmm_index *ix, const ReadsView &rv, const uint64_t *kmers_in, int6
         HIPCHK(hipGetLastError());
         KMMCHK(tm.end());
         KMMCHK(tm.begin(ix, KMM_KERNEL_RX_SCAN));
+        // (the scan's form follows the pass 2 rx_launch_p2 is about to choose: k_rx_p2 reads the absolute run starts P1T,
+        // k_rx_p2f rebuilds them from the run lengths and item_desc.y, and the scan then leaves the P1T area alone)
+        const bool with_p = !ix->rx_filter;
+        auto chunkscan = with_p ? k_rx_chunkscan<true> : k_rx_chunkscan<false>;
+        auto colscan = with_p ? k_rx_colscan<true> : k_rx_colscan<false>;
         hipLaunchKernelGGL(k_rx_colsum, dim3(sc.chunks), dim3(256), 0, ix->stream, rx);
-        hipLaunchKernelGGL(k_rx_chunkscan, dim3(F1), dim3(256), 0, ix->stream, rx, sc.chunks);
+        hipLaunchKernelGGL(chunkscan, dim3(F1), dim3(256), 0, ix->stream, rx, sc.chunks);
         hipLaunchKernelGGL(k_rx_tables, dim3(1), dim3(512), 0, ix->stream, rx);
-        hipLaunchKernelGGL(k_rx_colscan, dim3(sc.chunks, (F1 + 255) / 256), dim3(256), 0, ix->stream, rx);
+        hipLaunchKernelGGL(colscan, dim3(sc.chunks, (F1 + 255) / 256), dim3(256), 0, ix->stream, rx);
         HIPCHK(hipGetLastError());
         KMMCHK(tm.end());
         KMMCHK(tm.begin(ix, KMM_KERNEL_RX_P2));

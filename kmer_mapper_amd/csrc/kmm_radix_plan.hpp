@@ -244,7 +244,7 @@ inline RxScratch rx_scratch(uint32_t NB, uint32_t F1, uint32_t F2)
     size_t off = 0;
     auto carve = [&](size_t bytes) { const size_t o = off; off += rx_align256(bytes); return o; };
     s.start1 = carve((size_t)NB * (F1 + 1) * 2);            // uint16 [NB][F1 + 1]
-    s.P1T = carve((size_t)F1 * ((size_t)NB + 1) * 4);       // uint32 [F1][NB + 1]
+    s.P1T = carve((size_t)F1 * ((size_t)NB + 1) * 4);       // uint32 [F1][NB + 1] (k_rx_p2 only: unused in front of k_rx_p2f)
     s.S1T = carve((size_t)F1 * NB * 2);                     // uint16 [F1][NB]
     s.csum = carve((size_t)s.chunks * F1 * 4);              // uint32 [chunks][F1]
     s.T1 = carve((size_t)F1 * 4);                           // uint32 [F1]
