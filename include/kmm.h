@@ -476,6 +476,34 @@ int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offs
 int kmm_in_index(kmm_index_t *idx, const uint64_t *kmers, int64_t n, uint8_t *out);
 
 /*
+ * kmm_read_hits — per read, how many of its k-mers are in the index.  A fused kernel: read bytes -> k-mers
+ * -> one gather per k-mer -> per-read sums; no k-mer is written to memory.
+ * Reads as in kmm_map_reads_qual: read_offsets != NULL: ragged reads (int64[n_reads + 1], read_offsets[0] == 0,
+ * non-decreasing), read_len ignored; read_offsets == NULL: n_reads reads of read_len bytes back to back.  bases and
+ * read_offsets may each be host or device memory.  lut as everywhere (NULL: the reference's table; KMM_LUT_BREAK entries
+ * are breaks; k == 1 with a break table is KMM_ERR_INVALID_ARG).
+ *   - hits[r]: the number of windows of read r that are hits.  A window with k-mer q is a hit iff some entry l of bucket
+ *     q % modulo has kmers[l] == q and frequencies[l] <= max_index_lookup_frequency; with also_revcomp, iff that holds for
+ *     q or for the reverse complement of q.  A window counts once, however many entries or orientations match (a k-mer
+ *     under five nodes, a palindrome: one hit).  With max_index_lookup_frequency >= 65535 and also_revcomp == 0, hits[r] is
+ *     the sum of kmm_in_index over the read's k-mers.
+ *   - windows[r] (windows may be NULL): the number of windows of read r that were looked up: max(len_r - k + 1, 0) minus
+ *     the windows that contain a break byte.  hits[r] <= windows[r].
+ *   - both are uint32[n_reads], host or device, written in full (a read without windows gets 0); counts wrap modulo 2^32.
+ * A pure query: node counts, per-k-mer counts, kmm_get_stats, the handle's stream state (BGZF, gzip, BAM carry) and any
+ * sticky error are left as they were.  Synchronous like kmm_in_index: runs on the handle's stream and returns when the
+ * outputs are complete.  Served by the direct view on every index ("radix_available" 0 included); "read_hits_calls"
+ * (kmm_get_param, read-only) counts the calls.
+ * Errors come from the call itself and are never left on the handle: a byte with table entry 0xFF is
+ * KMM_ERR_INVALID_BASE, the message naming its flat position; decreasing offsets, read_offsets[0] != 0, hits == NULL with
+ * n_reads > 0 and k out of range are KMM_ERR_INVALID_ARG.  After an error the outputs are unspecified.  n_reads == 0 or no
+ * bases at all is KMM_OK, the outputs zeroed where they exist.
+ */
+int kmm_read_hits(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len,
+                  int k, int max_index_lookup_frequency, int also_revcomp, const uint8_t *lut, uint32_t *hits,
+                  uint32_t *windows);
+
+/*
  * kmm_build_index — builds the Kmer Index arrays on the GPU from flat (k-mer, node) pairs: replaces
  * graph_kmer_index's KmerIndex.from_flat_kmers(flat_kmers, modulo) (reference call site
  * tests/test_mapping.py:36-38; gpu_counter.py:16 builds its table from the same pairs).  Entries are

@@ -798,6 +798,60 @@ def map_bnp(args):
     return node_counts
 
 
+def check_read_hits_input(fmt, world_size):
+    """`kmer_mapper read-hits` takes FASTA / FASTQ in one process; everything else is refused before the index is read."""
+    if fmt in ("sam", "bam"):
+        raise ValueError("read-hits does not read %s files: per-read hits are implemented for FASTA and FASTQ (plain or .gz) "
+                         "only; SAM and BAM input is out of scope" % fmt.upper())
+    if world_size > 1:
+        raise ValueError("read-hits runs in one process: WORLD_SIZE=%d (torchrun) is out of scope, run it without torchrun"
+                         % world_size)
+
+
+def read_hits_file(args):
+    """`kmer_mapper read-hits`: per read of a FASTA / FASTQ file, in file order, the number of its k-mers that are in the
+    index (kmm_read_hits) -> <out>.npy (uint32), with --windows also the number of windows looked up -> <out>.windows.npy."""
+    k = args.kmer_size
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    check_read_hits_input(probe_input(args.reads).fmt, world)
+    lut = None
+    if args.ambiguous_bases == "skip":
+        from .util import ambiguous_skip_lut
+        lut = ambiguous_skip_lut()
+        if k < 2:
+            raise ValueError("--ambiguous-bases skip needs -k 2 or more")
+    kmer_index = _get_kmer_index_from_args(args)
+    max_node_id = kmer_index.max_node_id() if hasattr(kmer_index, "max_node_id") else int(np.max(kmer_index._nodes))
+    revcomp = bool(args.map_reverse_complements)
+    hits, wins = [], []
+    dev = DeviceIndex.from_index(kmer_index, max_node_id, device=args.device)
+    try:
+        for chunk in prefetch(read_chunks(args.reads, min_chunk_size=args.chunk_size)):
+            L = chunk.uniform_length
+            if L is not None:
+                res = dev.read_hits(chunk.bases, n_reads=len(chunk), read_len=L, k=k, max_index_lookup_frequency=args.max_hits_per_kmer,
+                                    also_revcomp=revcomp, lut=lut, windows=True)
+            else:
+                res = dev.read_hits(chunk.bases, chunk.offsets, k=k, max_index_lookup_frequency=args.max_hits_per_kmer,
+                                    also_revcomp=revcomp, lut=lut, windows=True)
+            hits.append(res[0])
+            wins.append(res[1])
+    finally:
+        dev.close()
+    hits = np.concatenate(hits) if hits else np.zeros(0, np.uint32)
+    wins = np.concatenate(wins) if wins else np.zeros(0, np.uint32)
+    n_reads, n_sel = hits.shape[0], int((hits >= args.min_hits).sum())
+    logging.info("%d reads; %d (%.2f %%) have at least %d k-mer%s in the index", n_reads, n_sel,
+                 100.0 * n_sel / max(n_reads, 1), args.min_hits, "" if args.min_hits == 1 else "s")
+    if args.output_file is not None:
+        np.save(args.output_file, hits)
+        logging.info("Saved per-read hits to %s.npy" % args.output_file)
+        if args.windows:
+            np.save(str(args.output_file) + ".windows", wins)
+            logging.info("Saved per-read windows to %s.windows.npy" % args.output_file)
+    return (hits, wins) if args.windows else hits
+
+
 def build_argument_parser():
     parser = argparse.ArgumentParser(
         description='Kmer Mapper',
@@ -873,6 +927,28 @@ def build_argument_parser():
                                 "file, trimmed at both ends to record starts that the ranks find on the GPU; a boundary guessed "
                                 "wrongly is an error, never a wrong count. Default: several ranks on one BAM file are refused.")
     subparser.set_defaults(func=map_bnp)
+
+    sub = subparsers.add_parser("read-hits", help="Extension: per read, the number of its k-mers that are in a kmer index")
+    sub.add_argument("-i", "--kmer-index", required=False)
+    sub.add_argument("-b", "--index-bundle", required=False)
+    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format (SAM and BAM are refused)")
+    sub.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
+    sub.add_argument("-c", "--chunk-size", required=False, type=int, default=2500000, help="N bytes to process in each chunk")
+    sub.add_argument("-o", "--output-file", required=True,
+                     help="<out>.npy: uint32, one value per read in file order; with --windows also <out>.windows.npy")
+    sub.add_argument("-I", "--max-hits-per-kmer", required=False, default=1000, type=int,
+                     help="A k-mer whose index entries all have a frequency above this is no hit. Applied as given.")
+    sub.add_argument("-r", "--map-reverse-complements", default=False, type=bool,
+                     help="A window also hits when the reverse complement of its k-mer is in the index. Default False.")
+    sub.add_argument("--ambiguous-bases", choices=("a", "skip"), default="a",
+                     help="a (default): N is looked up as A and any other letter is an error. skip: no window that contains N "
+                          "or an IUPAC ambiguity letter is looked up (it is not counted in --windows either).")
+    sub.add_argument("--windows", action="store_true", help="Also write the number of windows looked up per read.")
+    sub.add_argument("--min-hits", default=1, type=int, metavar="N",
+                     help="The log reports how many reads have at least N hits. Default 1.")
+    sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
+    sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
+    sub.set_defaults(func=read_hits_file)
     return parser
 
 

@@ -85,6 +85,7 @@ static double ms_since(std::chrono::steady_clock::time_point a)
 #include "kmm_tile.hpp"
 #include "kmm_records.hpp"
 #include "kmm_kernels.hpp"
+#include "kmm_read_hits.hpp"
 #include "kmm_radix.hpp"
 #include "kmm_build.hpp"
 
@@ -420,6 +421,7 @@ struct kmm_index : IndexStreams, RxArrays {
     int sticky_rc = KMM_OK;
     std::string sticky_msg;
     uint64_t map_calls = 0;   // sequence number of map calls on this handle (error reports name the call)
+    int64_t read_hits_calls = 0; // kmm_read_hits calls that were accepted ("read_hits_calls")
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
     int comm_rank = -1, comm_size = 0;
@@ -801,6 +803,156 @@ int check_k(int k)
 {
     if (k < 1 || k > KMM_MAX_K)
         return fail(KMM_ERR_INVALID_ARG, "k=%d outside [1, %d]", k, KMM_MAX_K);
+    return KMM_OK;
+}
+
+template <int MODE>
+int launch_read_hits(kmm_index *ix, const ReadsView &rv, int k, int max_freq, int also_rc, const int64_t *tile_first_read,
+                     uint32_t *hits, uint32_t *windows)
+{
+    const int64_t n_tiles = (rv.total + TILE_T - 1) / TILE_T;
+    const IndexView iv = view_of(ix);
+    const dim3 grid((unsigned)grid_for_tiles(ix, n_tiles));
+    // the probe flavour as launch_map_reads chooses it
+    if (iv.occ && iv.wide)
+        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, PROBE_WIDE_FILTER>), grid, dim3(256), 0, ix->stream, rv, iv, k, max_freq,
+                           also_rc, n_tiles, tile_first_read, hits, windows);
+    else if (iv.occ)
+        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, PROBE_BITMAP>), grid, dim3(256), 0, ix->stream, rv, iv, k, max_freq,
+                           also_rc, n_tiles, tile_first_read, hits, windows);
+    else if (iv.wide)
+        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, PROBE_WIDE>), grid, dim3(256), 0, ix->stream, rv, iv, k, max_freq,
+                           also_rc, n_tiles, tile_first_read, hits, windows);
+    else
+        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, PROBE_NARROW>), grid, dim3(256), 0, ix->stream, rv, iv, k, max_freq,
+                           also_rc, n_tiles, tile_first_read, hits, windows);
+    HIPCHK(hipGetLastError());
+    return KMM_OK;
+}
+
+// The ReadsView is prepared as map_reads_common prepares it (staging, lookup table, the uniform front end for reads of 16
+// bases and more without breaks, else the read-start bitset and k_mark_breaks), with two differences: the bad-byte and
+// bad-offset words are the call's own (in the stage's aux buffer, never ix->first_bad), and reads of one length that take
+// the ragged front end get no offsets array: their starts and their read ids are arithmetic.
+int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len, int k,
+                   int max_freq, int also_revcomp, const uint8_t *lut, uint32_t *hits, uint32_t *windows)
+{
+    const bool uniform = read_offsets == nullptr;
+    HIPCHK(hipSetDevice(ix->device));
+    int64_t total = 0;
+    if (uniform) {
+        if (read_len > 0 && n_reads > INT64_MAX / read_len)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: n_reads * read_len overflows");
+        total = n_reads * read_len;
+    } else {
+        int64_t ends[2] = {0, 0};
+        if (is_device_ptr(read_offsets)) {
+            HIPCHK(hipMemcpy(&ends[0], read_offsets, 8, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&ends[1], read_offsets + n_reads, 8, hipMemcpyDeviceToHost));
+        } else {
+            ends[0] = read_offsets[0];
+            ends[1] = read_offsets[n_reads];
+        }
+        if (ends[0] != 0)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: read_offsets[0] must be 0 (got %lld)", (long long)ends[0]);
+        if (ends[1] < 0)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: read_offsets[n_reads] negative");
+        total = ends[1];
+    }
+    if (total > 0 && !bases)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: bases is NULL");
+    const bool hits_dev = is_device_ptr(hits), win_dev = windows && is_device_ptr(windows);
+    const size_t out_bytes = (size_t)n_reads * 4;
+    if (total == 0) { // nothing to look up: the outputs are written in full all the same
+        hipError_t e = hits_dev ? hipMemsetAsync(hits, 0, out_bytes, ix->stream) : (memset(hits, 0, out_bytes), hipSuccess);
+        if (e == hipSuccess && windows)
+            e = win_dev ? hipMemsetAsync(windows, 0, out_bytes, ix->stream) : (memset(windows, 0, out_bytes), hipSuccess);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(ix->stream);
+        if (e != hipSuccess)
+            return fail(KMM_ERR_HIP, "kmm_read_hits: %s", hipGetErrorString(e));
+        ix->read_hits_calls++;
+        return KMM_OK;
+    }
+    KMMCHK(ensure_direct(ix));
+    Stage &s = next_stage(ix);
+    KMMCHK(stage_acquire(ix, s));
+    bool staged = false;
+    ReadsView rv;
+    memset(&rv, 0, sizeof rv);
+    KMMCHK(stage_in<uint8_t>(ix, s.bases, bases, (size_t)total, &rv.bases, &staged));
+    bool has_break = false;
+    KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &staged, &has_break));
+    if (!uniform)
+        KMMCHK(stage_in<int64_t>(ix, s.offsets, read_offsets, (size_t)(n_reads + 1), &rv.offsets, &staged));
+    rv.total = total;
+    rv.n_reads = n_reads;
+    if (uniform) {
+        rv.read_len = (uint64_t)read_len;
+        rv.read_len_magic = magic_for((uint64_t)read_len);
+    }
+    const int64_t n_tiles = (total + TILE_T - 1) / TILE_T;
+    // aux: [0, 256) the call's three error words; then the outputs of a caller that gave host arrays
+    const size_t out_slot = (out_bytes + 255) & ~(size_t)255;
+    KMMCHK(ensure(s.aux, 256 + 2 * out_slot));
+    unsigned long long *d_bad = (unsigned long long *)s.aux.p;
+    uint32_t *d_hits = hits_dev ? hits : (uint32_t *)((uint8_t *)s.aux.p + 256);
+    uint32_t *d_win = !windows ? nullptr : (win_dev ? windows : (uint32_t *)((uint8_t *)s.aux.p + 256 + out_slot));
+    rv.first_bad = d_bad;
+    const bool uniform_kernel = uniform && read_len >= 16 && !has_break;
+    const int64_t n_words = total / 32 + 2;
+    if (!uniform_kernel)
+        KMMCHK(ensure(s.start_bits, (size_t)n_words * 4));
+    if (!uniform)
+        KMMCHK(ensure(s.tile_first, (size_t)(n_tiles + 1) * 8));
+    KMMCHK(stage_copies_done(ix));
+    HIPCHK(hipMemsetAsync(d_bad, 0xFF, 3 * sizeof(unsigned long long), ix->stream));
+    HIPCHK(hipMemsetAsync(d_hits, 0, out_bytes, ix->stream));
+    if (d_win)
+        HIPCHK(hipMemsetAsync(d_win, 0, out_bytes, ix->stream));
+    const int rc_flag = also_revcomp ? 1 : 0;
+    if (uniform_kernel) {
+        KMMCHK(launch_read_hits<MODE_UNIFORM>(ix, rv, k, max_freq, rc_flag, nullptr, d_hits, d_win));
+    } else {
+        rv.start_bits = (const uint32_t *)s.start_bits.p;
+        rv.n_start_words = n_words;
+        HIPCHK(hipMemsetAsync(s.start_bits.p, 0, (size_t)n_words * 4, ix->stream));
+        if (uniform)
+            hipLaunchKernelGGL(k_mark_uniform_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                               n_reads, read_len, (uint32_t *)s.start_bits.p);
+        else
+            hipLaunchKernelGGL(k_mark_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                               rv.offsets, n_reads, total, (uint32_t *)s.start_bits.p);
+        if (has_break) // every break byte: a one-base read
+            hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (total + 256 * 16 * BRK_U - 1) / (256 * 16 * BRK_U), 8)), dim3(256), 0,
+                               ix->stream, rv.bases, total, rv.lut, (uint32_t *)s.start_bits.p);
+        if (!uniform) {
+            hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(ix, (n_reads + 255) / 256, 8)), dim3(256), 0, ix->stream,
+                               rv.offsets, n_reads, d_bad);
+            hipLaunchKernelGGL(k_rh_tile_reads, dim3(grid_for(ix, (n_tiles + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                               rv.offsets, n_reads, total, n_tiles, (int64_t)TILE_T, (int64_t *)s.tile_first.p);
+        }
+        HIPCHK(hipGetLastError());
+        KMMCHK(launch_read_hits<MODE_GENERAL>(ix, rv, k, max_freq, rc_flag, (const int64_t *)s.tile_first.p, d_hits, d_win));
+    }
+    unsigned long long bad[3] = {NO_BAD, NO_BAD, NO_BAD};
+    hipError_t e = hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ix->stream);
+    if (e == hipSuccess && !hits_dev)
+        e = hipMemcpyAsync(hits, d_hits, out_bytes, hipMemcpyDeviceToHost, ix->stream);
+    if (e == hipSuccess && windows && !win_dev)
+        e = hipMemcpyAsync(windows, d_win, out_bytes, hipMemcpyDeviceToHost, ix->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(ix->stream);
+    if (e != hipSuccess)
+        return fail(KMM_ERR_HIP, "kmm_read_hits: %s", hipGetErrorString(e));
+    KMMCHK(stage_release(ix, s, staged));
+    // errors of this call are this call's: nothing is left on the handle
+    if (bad[2] != NO_BAD)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: read_offsets is not non-decreasing at read %llu", bad[2]);
+    if (bad[0] != NO_BAD)
+        return fail(KMM_ERR_INVALID_BASE, "kmm_read_hits: read byte at offset %llu is not a nucleotide under the lookup table "
+                    "(the reference's DNA encoder raises here)", bad[0]);
+    ix->read_hits_calls++;
     return KMM_OK;
 }
 
@@ -3875,6 +4027,24 @@ int kmm_in_index(kmm_index_t *ix, const uint64_t *kmers, int64_t n, uint8_t *out
     return stage_release(ix, s, staged);
 }
 
+int kmm_read_hits(kmm_index_t *ix, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len, int k,
+                  int max_freq, int also_revcomp, const uint8_t *lut, uint32_t *hits, uint32_t *windows)
+{
+    if (!ix)
+        return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(check_k(k));
+    if (n_reads < 0 || (!read_offsets && read_len < 0))
+        return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: n_reads / read_len negative");
+    if (n_reads == 0)
+        return KMM_OK;
+    if (!hits)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: hits is NULL");
+    KMMCHK(check_k_lut(k, lut));
+    return guarded("kmm_read_hits", [&] {
+        return read_hits_impl(ix, bases, read_offsets, n_reads, read_len, k, max_freq, also_revcomp, lut, hits, windows);
+    });
+}
+
 int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads,
                       int k, const uint8_t *lut, uint64_t *out, int64_t n_out)
 {
@@ -4518,6 +4688,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->original_strand;
     else if (!strcmp(name, "debug_records_piece_kb"))
         *value = ix->dbg_rec_piece_kb;
+    else if (!strcmp(name, "read_hits_calls")) // kmm_read_hits calls (a pure query: no other counter moves)
+        *value = ix->read_hits_calls;
     else if (!strcmp(name, "bam_calls")) // kmm_map_bam calls that mapped their records (a window inside the header not counted)
         *value = ix->bam_calls;
     else if (!strcmp(name, "bam_records")) // BAM records mapped

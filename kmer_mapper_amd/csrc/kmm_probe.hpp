@@ -422,3 +422,138 @@ __device__ __forceinline__ void probe_batch(const IndexView &iv, NodeAgg &agg, L
     else
         probe_batch_impl<U, false>(iv, agg, st, q, valid, max_freq);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Membership probe (kmm_read_hits, kmm_read_hits.hpp): the gathers and the filter stage of probe_batch_impl /
+// probe_batch_wide above, but nothing is counted: bit u of the result is set iff some entry of k-mer u's bucket holds
+// that k-mer with a frequency of at most max_freq.  A k-mer under several nodes is one bit; no NodeAgg, no LaneStats.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool entry_matches(uint4 e, uint64_t q, int max_freq)
+{
+    return ((uint64_t)e.x | ((uint64_t)e.y << 32)) == q && (int)e.w <= max_freq;
+}
+
+template <int U, bool FILTER>
+__device__ __forceinline__ uint32_t member_batch_impl(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid,
+                                                      int max_freq)
+{
+    uint64_t h[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        h[u] = fastmod(q[u], iv.modulo, iv.magic);
+    if (FILTER)
+        valid = filter_stage<U>(iv, q, h, valid);
+    uint4 b[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        b[u] = make_uint4(0u, 0u, 0u, 0u);
+        if ((valid >> u) & 1u) {
+            if (FILTER) { // streamed once: keep the bitmap, not these lines, in L2
+                u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(&iv.buckets[h[u]]));
+                b[u] = make_uint4(x[0], x[1], x[2], x[3]);
+            } else {
+                b[u] = iv.buckets[h[u]];
+            }
+        }
+    }
+    uint32_t hit = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t kind = b[u].w & 3u;
+        if (kind == 1u) {
+            const uint64_t ek = (uint64_t)b[u].x | ((uint64_t)b[u].y << 32);
+            if (ek == q[u] && (int)(b[u].w >> 16) <= max_freq)
+                hit |= 1u << u;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if ((b[u].w & 3u) == 2u) {
+            const uint32_t st = b[u].x, cn = b[u].y; // cn >= 2 by construction
+            if (b[u].w & 4u) { // fingerprints present: skip the walk unless one of them matches
+                const uint32_t f = kmer_fp16(q[u]);
+                const bool may = f == (b[u].z & 0xFFFFu) || f == (b[u].z >> 16) ||
+                                 (cn > 2u && f == (b[u].w >> 16));
+                if (!may)
+                    continue;
+            }
+            const uint4 e0 = iv.entries[st];
+            const uint4 e1 = iv.entries[(uint64_t)st + 1];
+            bool m = entry_matches(e0, q[u], max_freq) || entry_matches(e1, q[u], max_freq);
+            for (uint32_t j = 2; j < cn && !m; ++j)
+                m = entry_matches(iv.entries[(uint64_t)st + j], q[u], max_freq);
+            if (m)
+                hit |= 1u << u;
+        }
+    }
+    return hit;
+}
+
+template <int U, bool FILTER>
+__device__ __forceinline__ uint32_t member_batch_wide(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid,
+                                                      int max_freq)
+{
+    uint64_t h[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        h[u] = fastmod(q[u], iv.modulo, iv.magic);
+    if (FILTER)
+        valid = filter_stage<U>(iv, q, h, valid);
+    uint4 a[U], b[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        a[u] = make_uint4(0u, 0u, 0u, 0u);
+        if ((valid >> u) & 1u)
+            a[u] = iv.buckets[2 * h[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        b[u] = make_uint4(0u, 0u, 0u, 0u);
+        if ((a[u].w & 3u) == 2u)
+            b[u] = iv.buckets[2 * h[u] + 1];
+    }
+    uint32_t hit = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t kind = a[u].w & 3u;
+        if (kind == 1u || kind == 2u) {
+            const uint64_t ek = (uint64_t)a[u].x | ((uint64_t)a[u].y << 32);
+            if (ek == q[u] && (int)(a[u].w >> 16) <= max_freq)
+                hit |= 1u << u;
+        }
+        if (kind == 2u) {
+            const uint64_t ek = (uint64_t)b[u].x | ((uint64_t)b[u].y << 32);
+            if (ek == q[u] && (int)(b[u].w >> 16) <= max_freq)
+                hit |= 1u << u;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if ((a[u].w & 3u) == 3u) {
+            const uint32_t st = a[u].x, cn = a[u].y; // cn >= 3 by construction
+            const uint4 e0 = iv.entries[st];
+            const uint4 e1 = iv.entries[(uint64_t)st + 1];
+            const uint4 e2 = iv.entries[(uint64_t)st + 2];
+            bool m = entry_matches(e0, q[u], max_freq) || entry_matches(e1, q[u], max_freq) ||
+                     entry_matches(e2, q[u], max_freq);
+            for (uint32_t j = 3; j < cn && !m; ++j)
+                m = entry_matches(iv.entries[(uint64_t)st + j], q[u], max_freq);
+            if (m)
+                hit |= 1u << u;
+        }
+    }
+    return hit;
+}
+
+template <int U, int PROBE>
+__device__ __forceinline__ uint32_t member_batch(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid, int max_freq)
+{
+    if (PROBE == PROBE_BITMAP)
+        return member_batch_impl<U, true>(iv, q, valid, max_freq);
+    else if (PROBE == PROBE_WIDE)
+        return member_batch_wide<U, false>(iv, q, valid, max_freq);
+    else if (PROBE == PROBE_WIDE_FILTER)
+        return member_batch_wide<U, true>(iv, q, valid, max_freq);
+    else
+        return member_batch_impl<U, false>(iv, q, valid, max_freq);
+}

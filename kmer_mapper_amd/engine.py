@@ -339,6 +339,44 @@ class DeviceIndex:
         _lib.check(_lib.lib().kmm_in_index(self._h, a.ptr, a.n, out.ctypes.data_as(_P)))
         return out
 
+    def read_hits(self, bases, read_offsets=None, n_reads=None, read_len=None, k=31, max_index_lookup_frequency=1000,
+                  also_revcomp=False, lut=None, windows=False):
+        """kmm_read_hits: per read, how many of its k-mers are in the index (a window is a hit once, whatever the number of
+        entries or orientations that match; entries above max_index_lookup_frequency do not count).  read_offsets given:
+        ragged reads; else n_reads reads of read_len bytes.  A pure query: the counts of the handle do not move.
+        numpy in -> numpy uint32[n_reads] out; torch device tensors in -> torch device tensors out.  windows=True returns
+        (hits, windows): windows[r] = the windows of read r that were looked up (those over a break byte are not)."""
+        b = _Arg(bases, np.uint8, "bases")
+        t = _Arg(lut, np.uint8, "lut")
+        if lut is not None and t.n != 256:
+            raise ValueError("lut must have 256 entries")
+        if read_offsets is not None:
+            o = _Arg(read_offsets, np.int64, "read_offsets")
+            if o.n < 1:
+                raise ValueError("read_offsets needs n_reads+1 entries")
+            n, L, optr = o.n - 1, 0, o.ptr
+        else:
+            if n_reads is None or read_len is None:
+                raise ValueError("read_hits needs read_offsets, or n_reads and read_len")
+            n, L, optr = int(n_reads), int(read_len), None
+            if n < 0 or L < 0:
+                raise ValueError("n_reads / read_len negative")
+            if b.n < n * L:
+                raise ValueError("bases holds %d bytes, need n_reads*read_len=%d" % (b.n, n * L))
+        if _is_torch_tensor(bases) and bases.is_cuda:
+            import torch
+            dt = getattr(torch, "uint32", torch.int32)
+            hits = torch.zeros(n, dtype=dt, device=bases.device)
+            win = torch.zeros(n, dtype=dt, device=bases.device) if windows else None
+            hp, wp = _P(hits.data_ptr()), (_P(win.data_ptr()) if windows else None)
+        else:
+            hits = np.zeros(n, dtype=np.uint32)
+            win = np.zeros(n, dtype=np.uint32) if windows else None
+            hp, wp = hits.ctypes.data_as(_P), (win.ctypes.data_as(_P) if windows else None)
+        _lib.check(_lib.lib().kmm_read_hits(self._h, b.ptr, optr, n, L, int(k), int(max_index_lookup_frequency),
+                                            int(bool(also_revcomp)), t.ptr, hp, wp))
+        return (hits, win) if windows else hits
+
     # -- measurement -----------------------------------------------------------------------------
     def set_timing(self, on=True):
         _lib.check(_lib.lib().kmm_set_timing(self._h, int(bool(on))))

@@ -106,3 +106,15 @@ def in_graph_index(index, kmers, max_index_lookup_frequency=1000):
 
 
 in_graph_index_no_memory_maps = in_graph_index
+
+
+def read_hits(index, reads, k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, windows=False, device=0):
+    """Extension (no counterpart in mapper.pyx, whose in_graph_index answers per k-mer): per read, how many of its k-mers
+    are in the index -> np.uint32[n_reads]; windows=True: (hits, windows looked up).  `reads`: what util.as_read_batch
+    takes (a ReadBatch, a (bases, offsets) pair or a list of reads).  DeviceIndex.read_hits on the cached handle."""
+    from .util import as_read_batch
+    batch = as_read_batch(reads)
+    max_node_id = int(np.max(index._nodes)) if len(index._nodes) else 0
+    return _device_index(index, max_node_id, device).read_hits(batch.bases, batch.offsets, k=k,
+                                                               max_index_lookup_frequency=max_index_lookup_frequency,
+                                                               also_revcomp=also_revcomp, lut=lut, windows=windows)
