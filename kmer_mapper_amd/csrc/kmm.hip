@@ -11,6 +11,7 @@
 // each byte is fetched from HBM exactly once with 16-byte coalesced loads.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -21,6 +22,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -561,6 +563,39 @@ int grid_for_tiles(const kmm_index *ix, int64_t n_tiles)
     return (int)(g < 1 ? 1 : g);
 }
 
+// The schedule of a direct launch over n_units tiles or spans (device side: for_owned_units, kmm_kernels.hpp).  Large
+// launches: persistent workgroups, one per CU slot, and the dynamic unit queue, zeroed here; small ones: the static
+// schedule, queue == null.
+struct DirectSchedule {
+    dim3 grid;
+    unsigned long long *queue;
+};
+
+int direct_schedule(kmm_index *ix, int64_t n_units, DirectSchedule *sched)
+{
+    const int64_t slots = (int64_t)ix->n_cu * 8;
+    const bool dynamic = ix->dynamic_schedule && n_units >= slots * 4 * ix->dyn_chunk;
+    if (dynamic)
+        HIPCHK(hipMemsetAsync(ix->queue, 0, 3 * sizeof(unsigned long long), ix->stream));
+    sched->grid = dim3(dynamic ? (unsigned)slots : (unsigned)grid_for_tiles(ix, n_units));
+    sched->queue = dynamic ? ix->queue : nullptr;
+    return KMM_OK;
+}
+
+// The probe flavour of an index view (kmm_probe.hpp) as a compile-time constant: f(std::integral_constant<int, PROBE_...>).
+template <typename F>
+void with_probe_flavour(const IndexView &iv, F &&f)
+{
+    if (iv.occ && iv.wide)
+        f(std::integral_constant<int, PROBE_WIDE_FILTER>{});
+    else if (iv.occ)
+        f(std::integral_constant<int, PROBE_BITMAP>{});
+    else if (iv.wide)
+        f(std::integral_constant<int, PROBE_WIDE>{});
+    else
+        f(std::integral_constant<int, PROBE_NARROW>{});
+}
+
 // Stage a host array into the given device buffer on the copy stream; device arrays pass through.
 template <typename TT>
 int stage_in(kmm_index *ix, DevBuf &buf, const TT *src, size_t count, const TT **dev, bool *staged)
@@ -706,25 +741,12 @@ int launch_map_reads(kmm_index *ix, const ReadsView &rv, int k, int max_freq, in
         const IndexView iv = view_of(ix); // (the direct view may have been packed just now)
         ScopedTimer tm;
         KMMCHK(tm.begin(ix, KMM_KERNEL_MAP_READS));
-        // large launches: persistent workgroups + dynamic tile queue; small ones: static schedule
-        const int64_t slots = (int64_t)ix->n_cu * 8;
-        const bool dynamic = ix->dynamic_schedule && n_tiles >= slots * 4 * ix->dyn_chunk;
-        if (dynamic)
-            HIPCHK(hipMemsetAsync(ix->queue, 0, 3 * sizeof(unsigned long long), ix->stream));
-        const dim3 grid(dynamic ? (unsigned)slots : (unsigned)grid_for_tiles(ix, n_tiles));
-        unsigned long long *queue = dynamic ? ix->queue : nullptr;
-        if (iv.occ && iv.wide)
-            hipLaunchKernelGGL((k_map_reads<TILE_S, MODE, PROBE_WIDE_FILTER>), grid, dim3(256), 0, ix->stream, rv,
-                               iv, k, max_freq, also_rc, (int64_t)0, n_tiles, queue, ix->dyn_chunk);
-        else if (iv.occ)
-            hipLaunchKernelGGL((k_map_reads<TILE_S, MODE, PROBE_BITMAP>), grid, dim3(256), 0, ix->stream, rv, iv, k,
-                               max_freq, also_rc, (int64_t)0, n_tiles, queue, ix->dyn_chunk);
-        else if (iv.wide)
-            hipLaunchKernelGGL((k_map_reads<TILE_S, MODE, PROBE_WIDE>), grid, dim3(256), 0, ix->stream, rv, iv, k,
-                               max_freq, also_rc, (int64_t)0, n_tiles, queue, ix->dyn_chunk);
-        else
-            hipLaunchKernelGGL((k_map_reads<TILE_S, MODE, PROBE_NARROW>), grid, dim3(256), 0, ix->stream, rv, iv, k,
-                               max_freq, also_rc, (int64_t)0, n_tiles, queue, ix->dyn_chunk);
+        DirectSchedule sched;
+        KMMCHK(direct_schedule(ix, n_tiles, &sched));
+        with_probe_flavour(iv, [&](auto probe) {
+            hipLaunchKernelGGL((k_map_reads<TILE_S, MODE, decltype(probe)::value>), sched.grid, dim3(256), 0, ix->stream, rv, iv,
+                               k, max_freq, also_rc, (int64_t)0, n_tiles, sched.queue, ix->dyn_chunk);
+        });
         HIPCHK(hipGetLastError());
         return tm.end();
     }
@@ -813,19 +835,10 @@ int launch_read_hits(kmm_index *ix, const ReadsView &rv, int k, int max_freq, in
     const int64_t n_tiles = (rv.total + TILE_T - 1) / TILE_T;
     const IndexView iv = view_of(ix);
     const dim3 grid((unsigned)grid_for_tiles(ix, n_tiles));
-    // the probe flavour as launch_map_reads chooses it
-    if (iv.occ && iv.wide)
-        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, PROBE_WIDE_FILTER>), grid, dim3(256), 0, ix->stream, rv, iv, k, max_freq,
-                           also_rc, n_tiles, tile_first_read, hits, windows);
-    else if (iv.occ)
-        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, PROBE_BITMAP>), grid, dim3(256), 0, ix->stream, rv, iv, k, max_freq,
-                           also_rc, n_tiles, tile_first_read, hits, windows);
-    else if (iv.wide)
-        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, PROBE_WIDE>), grid, dim3(256), 0, ix->stream, rv, iv, k, max_freq,
-                           also_rc, n_tiles, tile_first_read, hits, windows);
-    else
-        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, PROBE_NARROW>), grid, dim3(256), 0, ix->stream, rv, iv, k, max_freq,
-                           also_rc, n_tiles, tile_first_read, hits, windows);
+    with_probe_flavour(iv, [&](auto probe) {
+        hipLaunchKernelGGL((k_read_hits<TILE_S, MODE, decltype(probe)::value>), grid, dim3(256), 0, ix->stream, rv, iv, k,
+                           max_freq, also_rc, n_tiles, tile_first_read, hits, windows);
+    });
     HIPCHK(hipGetLastError());
     return KMM_OK;
 }
@@ -924,7 +937,7 @@ int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offs
             hipLaunchKernelGGL(k_mark_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
                                rv.offsets, n_reads, total, (uint32_t *)s.start_bits.p);
         if (has_break) // every break byte: a one-base read
-            hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (total + 256 * 16 * BRK_U - 1) / (256 * 16 * BRK_U), 8)), dim3(256), 0,
+            hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (total + 256 * 16 * MARK_U - 1) / (256 * 16 * MARK_U), 8)), dim3(256), 0,
                                ix->stream, rv.bases, total, rv.lut, (uint32_t *)s.start_bits.p);
         if (!uniform) {
             hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(ix, (n_reads + 255) / 256, 8)), dim3(256), 0, ix->stream,
@@ -1674,24 +1687,12 @@ int kmm_map_kmers(kmm_index_t *ix, const uint64_t *kmers, int64_t n, int max_fre
     {
         const IndexView iv = view_of(ix);
         const int64_t n_spans = (n + 256 * U - 1) / (256 * U);
-        const int64_t slots = (int64_t)ix->n_cu * 8;
-        const bool dynamic = ix->dynamic_schedule && n_spans >= slots * 4 * ix->dyn_chunk;
-        if (dynamic)
-            HIPCHK(hipMemsetAsync(ix->queue, 0, 3 * sizeof(unsigned long long), ix->stream));
-        const dim3 grid(dynamic ? (unsigned)slots : (unsigned)grid_for_tiles(ix, n_spans));
-        unsigned long long *queue = dynamic ? ix->queue : nullptr;
-        if (iv.occ && iv.wide)
-            hipLaunchKernelGGL((k_map_kmers<U, PROBE_WIDE_FILTER>), grid, dim3(256), 0, ix->stream, d_kmers, n, iv,
-                               max_freq, also_revcomp ? 1 : 0, k, queue, ix->dyn_chunk);
-        else if (iv.occ)
-            hipLaunchKernelGGL((k_map_kmers<U, PROBE_BITMAP>), grid, dim3(256), 0, ix->stream, d_kmers, n, iv,
-                               max_freq, also_revcomp ? 1 : 0, k, queue, ix->dyn_chunk);
-        else if (iv.wide)
-            hipLaunchKernelGGL((k_map_kmers<U, PROBE_WIDE>), grid, dim3(256), 0, ix->stream, d_kmers, n, iv,
-                               max_freq, also_revcomp ? 1 : 0, k, queue, ix->dyn_chunk);
-        else
-            hipLaunchKernelGGL((k_map_kmers<U, PROBE_NARROW>), grid, dim3(256), 0, ix->stream, d_kmers, n, iv,
-                               max_freq, also_revcomp ? 1 : 0, k, queue, ix->dyn_chunk);
+        DirectSchedule sched;
+        KMMCHK(direct_schedule(ix, n_spans, &sched));
+        with_probe_flavour(iv, [&](auto probe) {
+            hipLaunchKernelGGL((k_map_kmers<U, decltype(probe)::value>), sched.grid, dim3(256), 0, ix->stream, d_kmers, n, iv,
+                               max_freq, also_revcomp ? 1 : 0, k, sched.queue, ix->dyn_chunk);
+        });
     }
     HIPCHK(hipGetLastError());
     KMMCHK(tm.end());
@@ -2075,10 +2076,10 @@ static int map_reads_common(kmm_index_t *ix, const uint8_t *bases, const int64_t
             hipLaunchKernelGGL(k_mark_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
                                rv.offsets, n_reads, total, (uint32_t *)s.start_bits.p);
         if (has_break) // every break byte: a one-base read
-            hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (total + 256 * 16 * BRK_U - 1) / (256 * 16 * BRK_U), 8)), dim3(256), 0,
+            hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (total + 256 * 16 * MARK_U - 1) / (256 * 16 * MARK_U), 8)), dim3(256), 0,
                                ix->stream, rv.bases, total, rv.lut, (uint32_t *)s.start_bits.p);
         if (quals) // every quality byte below the floor: a one-base read, too
-            hipLaunchKernelGGL(k_mark_low_quals, dim3(grid_for(ix, (total + 256 * 16 * QUAL_U - 1) / (256 * 16 * QUAL_U), 8)), dim3(256), 0,
+            hipLaunchKernelGGL(k_mark_low_quals, dim3(grid_for(ix, (total + 256 * 16 * MARK_U - 1) / (256 * 16 * MARK_U), 8)), dim3(256), 0,
                                ix->stream, d_quals, total, qual_thresh, (uint32_t *)s.start_bits.p, (unsigned long long *)ix->stats);
         if (!uniform)
             hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(ix, (n_reads + 255) / 256, 8)), dim3(256), 0,

@@ -25,9 +25,38 @@ __device__ __forceinline__ void map_one_tile(const ReadsView &rv, const IndexVie
     }
 }
 
-// `queue` == null: static grid-stride schedule.  Otherwise the workgroups are persistent (one per CU
-// slot) and pull chunks of `chunk` consecutive tiles from a device-side counter, so that the last
-// round of a large launch does not leave CU slots idle while a few workgroups finish their fixed share.
+// The schedule of a direct launch (host side: direct_schedule, kmm.hip): body(unit) for every unit of [begin, end) that
+// this workgroup owns.  `queue` == null: static grid-stride schedule.  Otherwise the workgroups are persistent (one per CU
+// slot) and pull chunks of `chunk` consecutive units from a device-side counter, so that the last round of a large launch
+// does not leave CU slots idle while a few workgroups finish their fixed share.  Call with the whole workgroup.
+template <typename Body>
+__device__ __forceinline__ void for_owned_units(int64_t begin, int64_t end, unsigned long long *queue, int chunk, Body &&body)
+{
+    __shared__ unsigned long long s_next;
+    if (!queue) {
+        for (int64_t unit = begin + blockIdx.x; unit < end; unit += gridDim.x)
+            body(unit);
+        return;
+    }
+    for (;;) {
+        if (threadIdx.x == 0)
+            s_next = atomicAdd(queue, (unsigned long long)chunk);
+        __syncthreads();
+        // (one value for the whole workgroup: read through the scalar unit, the chunk's bounds then live in SGPRs like the
+        // static schedule's)
+        const uint64_t grabbed = s_next;
+        const int64_t first = begin + (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(grabbed >> 32)) << 32) |
+                                                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)grabbed));
+        __syncthreads(); // s_next may be rewritten only after everyone has read it
+        if (first >= end)
+            break;
+        const int64_t last = first + chunk < end ? first + chunk : end;
+        for (int64_t unit = first; unit < last; ++unit)
+            body(unit);
+    }
+}
+
+// The units are tiles.
 template <int S, int MODE, int PROBE>
 __global__ void __launch_bounds__(256) k_map_reads(ReadsView rv, IndexView iv, int k, int max_freq,
                                                    int also_rc, int64_t tile_begin, int64_t tile_end,
@@ -35,28 +64,13 @@ __global__ void __launch_bounds__(256) k_map_reads(ReadsView rv, IndexView iv, i
 {
     __shared__ TileSmem<S> sm;
     __shared__ NodeAgg agg;
-    __shared__ unsigned long long s_next;
     LaneStats st;
     sm.lut[threadIdx.x] = rv.lut[threadIdx.x];
     agg_init(agg); // ordered before the first agg_add by the barriers inside tile_kmers
     const TileConst tc = tile_const(rv, k);
-    if (!queue) {
-        for (int64_t tile = tile_begin + blockIdx.x; tile < tile_end; tile += gridDim.x)
-            map_one_tile<S, MODE, PROBE>(rv, iv, tc, tile, k, max_freq, also_rc, sm, agg, st);
-    } else {
-        for (;;) {
-            if (threadIdx.x == 0)
-                s_next = atomicAdd(queue, (unsigned long long)chunk);
-            __syncthreads();
-            const int64_t first = tile_begin + (int64_t)s_next;
-            __syncthreads(); // s_next may be rewritten only after everyone has read it
-            if (first >= tile_end)
-                break;
-            const int64_t last = first + chunk < tile_end ? first + chunk : tile_end;
-            for (int64_t tile = first; tile < last; ++tile)
-                map_one_tile<S, MODE, PROBE>(rv, iv, tc, tile, k, max_freq, also_rc, sm, agg, st);
-        }
-    }
+    for_owned_units(tile_begin, tile_end, queue, chunk, [&](int64_t tile) {
+        map_one_tile<S, MODE, PROBE>(rv, iv, tc, tile, k, max_freq, also_rc, sm, agg, st);
+    });
     stats_reduce(agg, st);
     __syncthreads();
     agg_flush(iv, agg);
@@ -90,35 +104,21 @@ __device__ __forceinline__ void map_kmer_span(const uint64_t *__restrict__ kmers
     }
 }
 
-// `queue` as in k_map_reads: null = static grid-stride over spans of 256*U k-mers, otherwise persistent
-// workgroups pulling `chunk` consecutive spans per grab.
+// The units are spans of 256*U k-mers.
 template <int U, int PROBE>
 __global__ void __launch_bounds__(256) k_map_kmers(const uint64_t *__restrict__ kmers, int64_t n,
                                                    IndexView iv, int max_freq, int also_rc, int k,
                                                    unsigned long long *queue, int chunk)
 {
     __shared__ NodeAgg agg;
-    __shared__ unsigned long long s_next;
     LaneStats st;
     agg_init(agg);
     __syncthreads();
-    const int64_t span = (int64_t)256 * U;
-    if (!queue) {
-        for (int64_t base = (int64_t)blockIdx.x * span; base < n; base += (int64_t)gridDim.x * span)
-            map_kmer_span<U, PROBE>(kmers, n, base, iv, max_freq, also_rc, k, agg, st);
-    } else {
-        for (;;) {
-            if (threadIdx.x == 0)
-                s_next = atomicAdd(queue, (unsigned long long)chunk);
-            __syncthreads();
-            const int64_t first = (int64_t)s_next * span;
-            __syncthreads();
-            if (first >= n)
-                break;
-            for (int c = 0; c < chunk && first + c * span < n; ++c)
-                map_kmer_span<U, PROBE>(kmers, n, first + c * span, iv, max_freq, also_rc, k, agg, st);
-        }
-    }
+    constexpr int64_t span = (int64_t)256 * U;
+    const int64_t n_spans = (n + span - 1) / span;
+    for_owned_units(0, n_spans, queue, chunk, [&](int64_t s) {
+        map_kmer_span<U, PROBE>(kmers, n, s * span, iv, max_freq, also_rc, k, agg, st);
+    });
     stats_reduce(agg, st);
     __syncthreads();
     agg_flush(iv, agg);
@@ -145,129 +145,104 @@ __global__ void k_mark_uniform_starts(int64_t n_reads, int64_t read_len, uint32_
     }
 }
 
-// Break bytes (lookup table entry KMM_LUT_BREAK: N, IUPAC letters) -> the read-start bitset.  A break at flat position b
-// is a one-base read: bits b and b + 1.  With "no read start inside (p, p + k - 1]" (k >= 2) the window that starts at b
-// dies of bit b + 1 and every earlier window that contains b of bit b; the windows behind b live.  So the mapping
-// kernels need no notion of a break: this pre-pass runs only for calls whose table has a break entry.
-// A pure stream: one byte per base in, one bit per base (touched only where a break is) out.  Per round a workgroup
-// takes 16 KiB: BRK_U 16-byte loads per lane, all issued before the first is consumed; each byte goes through an LDS
-// copy of the table (1 = break) into a 16-position mask, two neighbouring lanes make one 32-position word, and the
-// even lane ORs word | word << 1 into the bitset — one atomic per word that holds a break, plus one for bit 31's
-// carry into the next word.  bits: total / 32 + 2 words (bit `total` may be set by the last base).
-constexpr int BRK_U = 4;
+// The marking stream of k_mark_breaks and k_mark_low_quals: one byte per base position in, one bit per position (touched
+// only where something is marked) out.  A marked position b is a one-base read: bits b and b + 1 of the read-start bitset.
+// With "no read start inside (p, p + k - 1]" (k >= 2) the window that starts at b dies of bit b + 1 and every earlier window
+// that contains b of bit b; the windows behind b live.  So the mapping kernels need no notion of a break or of a quality.
+// Per round a workgroup takes 16 KiB: MARK_U 16-byte loads per lane, all issued before the first is consumed;
+// classify(four words) turns a lane's 16 bytes into a 16-position mask, two neighbouring lanes make one 32-position word,
+// and the even lane ORs word | word << 1 into the bitset — one atomic per word that holds a mark, plus one for bit 31's
+// carry into the next word.  The marks may be DENSE (low qualities: at a few per cent of low bases most 32-position words
+// hold one).  The word is still written with a no-return atomic OR by the even lane that formed it: the alternative — the
+// incoming carry by shuffle and a plain load / OR / store of the word, atomics only at the wave's seam — puts a dependent
+// load between the compare and the store and has two write forms to keep right, while the atomic is issued and forgotten
+// and the L2 does the same read-modify-write either way (measured: the plain form takes 3.3 times as long,
+// profiles/flat_quality/README.md); the words are 1/8 of the bytes read.
+// Bytes past the end are staged as 0, which the classifier may mark: positions at or past `total` are cleared before
+// anything else, so the highest mark is bit `total`: word total / 32 of the total / 32 + 2 the bitset has, whatever the
+// bytes hold.  Returns the number of positions this lane marked (before the << 1).
+constexpr int MARK_U = 4;
+template <typename Classify>
+__device__ __forceinline__ uint32_t mark_stream(const uint8_t *__restrict__ bytes, int64_t total, uint32_t *__restrict__ bits,
+                                                Classify classify)
+{
+    const bool aligned = (((uintptr_t)bytes) & 15u) == 0;
+    constexpr int64_t SPAN = (int64_t)256 * 16 * MARK_U;
+    uint32_t n_marked = 0;
+    for (int64_t base = (int64_t)blockIdx.x * SPAN; base < total; base += (int64_t)gridDim.x * SPAN) {
+        uint32_t w[MARK_U][4];
+#pragma unroll
+        for (int u = 0; u < MARK_U; ++u) {
+            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
+            if (p + 16 <= total) {
+                u32x4 x;
+                if (aligned)
+                    x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bytes + p));
+                else
+                    __builtin_memcpy(&x, bytes + p, 16); // (one unaligned 16-byte load: rec_load16)
+                w[u][0] = x[0]; w[u][1] = x[1]; w[u][2] = x[2]; w[u][3] = x[3];
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    w[u][i] = p < total ? tile_load_bytes4(bytes, total, p + 4 * i) : 0u;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < MARK_U; ++u) {
+            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
+            uint32_t m = classify(w[u]);
+            const int64_t left = total - p;
+            if (left < 16)
+                m &= left > 0 ? (1u << left) - 1u : 0u;
+            n_marked += (uint32_t)__popc(m);
+            const uint32_t hi = (uint32_t)__shfl_xor((int)m, 1);
+            if (!(threadIdx.x & 1u)) {
+                const uint32_t word = m | (hi << 16);
+                if (word) {
+                    const int64_t wi = p >> 5; // (p is a multiple of 32 for even lanes)
+                    atomicOr(&bits[wi], word | (word << 1));
+                    if (word >> 31)
+                        atomicOr(&bits[wi + 1], 1u);
+                }
+            }
+        }
+    }
+    return n_marked;
+}
+
+// Break bytes (lookup table entry KMM_LUT_BREAK: N, IUPAC letters) -> the read-start bitset.  This pre-pass runs only for
+// calls whose table has a break entry.  Each byte goes through an LDS copy of the table (1 = break).
 __global__ void __launch_bounds__(256) k_mark_breaks(const uint8_t *__restrict__ bases, int64_t total,
                                                      const uint8_t *__restrict__ lut, uint32_t *__restrict__ bits)
 {
     __shared__ uint32_t s_brk[256];
     s_brk[threadIdx.x] = lut[threadIdx.x] == KMM_LUT_BREAK ? 1u : 0u;
     __syncthreads();
-    const bool aligned = (((uintptr_t)bases) & 15u) == 0;
-    constexpr int64_t SPAN = (int64_t)256 * 16 * BRK_U;
-    for (int64_t base = (int64_t)blockIdx.x * SPAN; base < total; base += (int64_t)gridDim.x * SPAN) {
-        uint32_t w[BRK_U][4];
+    mark_stream(bases, total, bits, [&](const uint32_t (&w)[4]) {
+        uint32_t m = 0;
 #pragma unroll
-        for (int u = 0; u < BRK_U; ++u) {
-            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
-            if (p + 16 <= total) {
-                u32x4 x;
-                if (aligned)
-                    x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(bases + p));
-                else
-                    __builtin_memcpy(&x, bases + p, 16); // (one unaligned 16-byte load: rec_load16)
-                w[u][0] = x[0]; w[u][1] = x[1]; w[u][2] = x[2]; w[u][3] = x[3];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    w[u][i] = p < total ? tile_load_bytes4(bases, total, p + 4 * i) : 0u;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < BRK_U; ++u) {
-            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
-            uint32_t m = 0;
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                m |= s_brk[(w[u][i >> 2] >> (8 * (i & 3))) & 0xFFu] << i;
-            const int64_t left = total - p; // (bytes past the end of the chunk are staged as 0, which may be a break entry)
-            if (left < 16)
-                m &= left > 0 ? (1u << left) - 1u : 0u;
-            const uint32_t hi = (uint32_t)__shfl_xor((int)m, 1);
-            if (!(threadIdx.x & 1u)) {
-                const uint32_t word = m | (hi << 16);
-                if (word) {
-                    const int64_t wi = p >> 5; // (p is a multiple of 32 for even lanes)
-                    atomicOr(&bits[wi], word | (word << 1));
-                    if (word >> 31)
-                        atomicOr(&bits[wi + 1], 1u);
-                }
-            }
-        }
-    }
+        for (int i = 0; i < 16; ++i)
+            m |= s_brk[(w[i >> 2] >> (8 * (i & 3))) & 0xFFu] << i;
+        return m;
+    });
 }
 
 // Quality bytes of flat reads (kmm_map_reads_qual with "min_base_quality" > 0) -> the read-start bitset:
-// quals[p] < thresh (unsigned; thresh = qual_base + Q, 1 .. 126) makes base p a one-base read, bits p and p + 1, exactly
-// as a break byte above; runs behind k_mark_starts / k_mark_breaks in stream order, on the same words.
-// The same stream as k_mark_breaks — 16 KiB per workgroup and round, QUAL_U 16-byte loads per lane issued before the
-// first is consumed — but the test is a compare, four bytes per operation (bytes_below, kmm_records.hpp), so there is no
-// LDS table, and low bytes are DENSE: at a few per cent of low bases most 32-position words hold one.  The word is
-// still written with a no-return atomic OR by the even lane that formed it (plus one for bit 31's carry): the
-// alternative — the incoming carry by shuffle and a plain load / OR / store of the word, atomics only at the wave's seam
-// — puts a dependent load between the compare and the store and has two write forms to keep right, while the atomic is
-// issued and forgotten and the L2 does the same read-modify-write either way (measured: the plain form takes 3.3 times as
-// long, profiles/flat_quality/README.md); the words are 1/8 of the bytes read.
-// Positions at or past `total` are cleared before anything else, so the highest mark is bit `total`: word total / 32 of
-// the total / 32 + 2 the bitset has, whatever the bytes hold.  The low bytes are counted per lane (before the << 1),
-// summed over the wave and the workgroup, and added once per workgroup to statistics slot KMM_STAT_QUAL_MASKED.
-constexpr int QUAL_U = 4;
+// quals[p] < thresh (unsigned; thresh = qual_base + Q, 1 .. 126) marks base p; runs behind k_mark_starts / k_mark_breaks in
+// stream order, on the same words.  The test is a compare, four bytes per operation (bytes_below, kmm_records.hpp), so
+// there is no LDS table.  The low bytes each lane marked are summed over the wave and the workgroup, and added once per
+// workgroup to statistics slot KMM_STAT_QUAL_MASKED.
 __global__ void __launch_bounds__(256) k_mark_low_quals(const uint8_t *__restrict__ quals, int64_t total, uint32_t thresh,
                                                         uint32_t *__restrict__ bits, unsigned long long *__restrict__ stats)
 {
     __shared__ uint32_t s_wave[4];
-    const bool aligned = (((uintptr_t)quals) & 15u) == 0;
-    constexpr int64_t SPAN = (int64_t)256 * 16 * QUAL_U;
-    uint32_t n_low = 0;
-    for (int64_t base = (int64_t)blockIdx.x * SPAN; base < total; base += (int64_t)gridDim.x * SPAN) {
-        uint32_t w[QUAL_U][4];
+    uint32_t n_low = mark_stream(quals, total, bits, [&](const uint32_t (&w)[4]) {
+        uint32_t m = 0;
 #pragma unroll
-        for (int u = 0; u < QUAL_U; ++u) {
-            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
-            if (p + 16 <= total) {
-                u32x4 x;
-                if (aligned)
-                    x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(quals + p));
-                else
-                    __builtin_memcpy(&x, quals + p, 16); // (one unaligned 16-byte load: rec_load16)
-                w[u][0] = x[0]; w[u][1] = x[1]; w[u][2] = x[2]; w[u][3] = x[3];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    w[u][i] = p < total ? tile_load_bytes4(quals, total, p + 4 * i) : 0u;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < QUAL_U; ++u) {
-            const int64_t p = base + ((int64_t)u * 256 + threadIdx.x) * 16;
-            uint32_t m = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                m |= flags_to_bits(bytes_below(w[u][i], thresh)) << (4 * i);
-            const int64_t left = total - p; // (bytes past the end read as 0, which is below every threshold)
-            if (left < 16)
-                m &= left > 0 ? (1u << left) - 1u : 0u;
-            n_low += (uint32_t)__popc(m);
-            const uint32_t hi = (uint32_t)__shfl_xor((int)m, 1);
-            if (!(threadIdx.x & 1u)) {
-                const uint32_t word = m | (hi << 16);
-                if (word) {
-                    const int64_t wi = p >> 5; // (p is a multiple of 32 for even lanes)
-                    atomicOr(&bits[wi], word | (word << 1));
-                    if (word >> 31)
-                        atomicOr(&bits[wi + 1], 1u);
-                }
-            }
-        }
-    }
+        for (int i = 0; i < 4; ++i)
+            m |= flags_to_bits(bytes_below(w[i], thresh)) << (4 * i);
+        return m;
+    });
     n_low = wave_sum(n_low);
     if ((threadIdx.x & 63) == 0)
         s_wave[threadIdx.x >> 6] = n_low;
@@ -370,50 +345,20 @@ __global__ void __launch_bounds__(256) k_extract_write(ReadsView rv, int k, int6
     }
 }
 
-// in_graph_index (mapper.pyx:112-127): first match wins, no frequency filter.
+// in_graph_index (mapper.pyx:112-127): first match wins, no frequency filter.  The membership walk of one k-mer with the
+// largest bound there is: stored frequencies are 16-bit, so every entry passes.
 __global__ void k_in_index(const uint64_t *__restrict__ kmers, int64_t n, IndexView iv,
                            uint8_t *__restrict__ out)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t q = kmers[i];
-        const uint64_t hq = fastmod(q, iv.modulo, iv.magic);
-        if (iv.wide) {
-            const uint4 a = iv.buckets[2 * hq];
-            const uint32_t kd = a.w & 3u;
-            uint8_t hw = 0;
-            if (kd == 1u || kd == 2u)
-                hw = (((uint64_t)a.x | ((uint64_t)a.y << 32)) == q) ? 1 : 0;
-            if (kd == 2u && !hw) {
-                const uint4 b2 = iv.buckets[2 * hq + 1];
-                hw = (((uint64_t)b2.x | ((uint64_t)b2.y << 32)) == q) ? 1 : 0;
-            } else if (kd == 3u) {
-                for (uint32_t j = 0; j < a.y; ++j) {
-                    uint4 e = iv.entries[(uint64_t)a.x + j];
-                    if (((uint64_t)e.x | ((uint64_t)e.y << 32)) == q) {
-                        hw = 1;
-                        break;
-                    }
-                }
-            }
-            out[i] = hw;
-            continue;
-        }
-        const uint4 b = iv.buckets[hq];
-        const uint32_t kind = b.w & 3u;
-        uint8_t hit = 0;
-        if (kind == 1u) {
-            hit = (((uint64_t)b.x | ((uint64_t)b.y << 32)) == q) ? 1 : 0;
-        } else if (kind == 2u) {
-            for (uint32_t j = 0; j < b.y; ++j) {
-                uint4 e = iv.entries[(uint64_t)b.x + j];
-                if (((uint64_t)e.x | ((uint64_t)e.y << 32)) == q) {
-                    hit = 1;
-                    break;
-                }
-            }
-        }
-        out[i] = hit;
+        const uint64_t q[1] = {kmers[i]};
+        MemberSink sink;
+        if (iv.wide)
+            walk_wide<1, false>(iv, q, 1u, INT_MAX, sink);
+        else
+            walk_narrow<1, false>(iv, q, 1u, INT_MAX, sink);
+        out[i] = (uint8_t)sink.bits;
     }
 }
 

@@ -238,15 +238,6 @@ __device__ __forceinline__ void stats_reduce(NodeAgg &agg, const LaneStats &st)
     }
 }
 
-// mapper.pyx:60-68 for one entry.
-__device__ __forceinline__ void count_if_match(const IndexView &iv, NodeAgg &agg, uint4 e, uint64_t q,
-                                               int max_freq, uint32_t &hits)
-{
-    uint64_t ek = (uint64_t)e.x | ((uint64_t)e.y << 32);
-    if (ek == q && (int)e.w <= max_freq)
-        agg_add(iv, agg, e.z, hits);
-}
-
 // Pre-filter stage shared by the probe flavours: clears the `valid` bit of every k-mer the L2/Infinity-Cache
 // resident filter proves absent from the index (Bloom filter keyed by the k-mer, or per-bucket bitmap keyed
 // by bucket and fingerprint bits).  One 4-byte access per k-mer, all U in flight together.
@@ -288,16 +279,53 @@ __device__ __forceinline__ uint32_t filter_stage(const IndexView &iv, const uint
     return valid;
 }
 
+// mapper.pyx:60-68 for one entry of `entries`, and for an entry stored inline in a bucket record (frequency in w >> 16).
+__device__ __forceinline__ bool entry_matches(uint4 e, uint64_t q, int max_freq)
+{
+    return ((uint64_t)e.x | ((uint64_t)e.y << 32)) == q && (int)e.w <= max_freq;
+}
+
+__device__ __forceinline__ bool inline_matches(uint4 b, uint64_t q, int max_freq)
+{
+    return ((uint64_t)b.x | ((uint64_t)b.y << 32)) == q && (int)(b.w >> 16) <= max_freq;
+}
+
+// What a walk does with a match is its Sink's business: sink.match(u, node) is called once per entry that holds k-mer u
+// with a frequency of at most max_freq, and Sink::FIRST_ENDS says whether the first match ends the walk of that k-mer.
+// Sinks are passed by reference and inlined away.
+// Counting (k_map_reads, k_map_kmers): a k-mer under several nodes counts once per entry (mapper.pyx:60-68).
+struct CountSink {
+    static constexpr bool FIRST_ENDS = false;
+    const IndexView &iv;
+    NodeAgg &agg;
+    uint32_t &hits;
+    __device__ __forceinline__ void match(int, uint32_t node) { agg_add(iv, agg, node, hits); }
+};
+
+// Membership (k_read_hits, k_in_index): bit u is set iff some entry matches; a k-mer under several nodes is one bit.
+struct MemberSink {
+    static constexpr bool FIRST_ENDS = true;
+    uint32_t bits = 0;
+    __device__ __forceinline__ void match(int u, uint32_t) { bits |= 1u << u; }
+};
+
+template <typename Sink>
+__device__ __forceinline__ bool sink_entry(Sink &sink, int u, uint4 e, uint64_t q, int max_freq)
+{
+    const bool m = entry_matches(e, q, max_freq);
+    if (m)
+        sink.match(u, e.z);
+    return m;
+}
+
 // The probe of mapper.pyx:53-69 for U k-mers per lane.  All U bucket gathers are in flight before
 // any is consumed; empty and single-entry buckets (the common cases) finish there.  Buckets with
 // two or more entries (hash collisions, k-mers present under several nodes) then load their first
 // two entries together and walk the rest.
-template <int U, bool FILTER>
-__device__ __forceinline__ void probe_batch_impl(const IndexView &iv, NodeAgg &agg, LaneStats &ls,
-                                                 const uint64_t (&q)[U], uint32_t valid, int max_freq)
+template <int U, bool FILTER, typename Sink>
+__device__ __forceinline__ void walk_narrow(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid, int max_freq,
+                                            Sink &sink)
 {
-    uint32_t &hits = ls.hits;
-    ls.lookups += (uint32_t)__popc(valid);
     uint64_t h[U];
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -318,14 +346,9 @@ __device__ __forceinline__ void probe_batch_impl(const IndexView &iv, NodeAgg &a
         }
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint32_t kind = b[u].w & 3u;
-        if (kind == 1u) {
-            uint64_t ek = (uint64_t)b[u].x | ((uint64_t)b[u].y << 32);
-            if (ek == q[u] && (int)(b[u].w >> 16) <= max_freq)
-                agg_add(iv, agg, b[u].z, hits);
-        }
-    }
+    for (int u = 0; u < U; ++u)
+        if ((b[u].w & 3u) == 1u && inline_matches(b[u], q[u], max_freq))
+            sink.match(u, b[u].z);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if ((b[u].w & 3u) == 2u) {
@@ -339,10 +362,10 @@ __device__ __forceinline__ void probe_batch_impl(const IndexView &iv, NodeAgg &a
             }
             const uint4 e0 = iv.entries[st];
             const uint4 e1 = iv.entries[(uint64_t)st + 1];
-            count_if_match(iv, agg, e0, q[u], max_freq, hits);
-            count_if_match(iv, agg, e1, q[u], max_freq, hits);
-            for (uint32_t j = 2; j < cn; ++j)
-                count_if_match(iv, agg, iv.entries[(uint64_t)st + j], q[u], max_freq, hits);
+            bool matched = sink_entry(sink, u, e0, q[u], max_freq);
+            matched |= sink_entry(sink, u, e1, q[u], max_freq);
+            for (uint32_t j = 2; j < cn && !(Sink::FIRST_ENDS && matched); ++j)
+                matched |= sink_entry(sink, u, iv.entries[(uint64_t)st + j], q[u], max_freq);
         }
     }
 }
@@ -350,12 +373,10 @@ __device__ __forceinline__ void probe_batch_impl(const IndexView &iv, NodeAgg &a
 // Same probe on the wide (32-byte) bucket layout: one L2-missing gather (A) resolves empty and single
 // buckets, two-entry buckets add an L2 hit (B), only >= 3 entries (2.9 % of probes at load factor 0.5) walk
 // `entries`.
-template <int U, bool FILTER>
-__device__ __forceinline__ void probe_batch_wide(const IndexView &iv, NodeAgg &agg, LaneStats &ls,
-                                                 const uint64_t (&q)[U], uint32_t valid, int max_freq)
+template <int U, bool FILTER, typename Sink>
+__device__ __forceinline__ void walk_wide(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid, int max_freq,
+                                          Sink &sink)
 {
-    uint32_t &hits = ls.hits;
-    ls.lookups += (uint32_t)__popc(valid);
     uint64_t h[U];
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -378,16 +399,10 @@ __device__ __forceinline__ void probe_batch_wide(const IndexView &iv, NodeAgg &a
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const uint32_t kind = a[u].w & 3u;
-        if (kind == 1u || kind == 2u) {
-            const uint64_t ek = (uint64_t)a[u].x | ((uint64_t)a[u].y << 32);
-            if (ek == q[u] && (int)(a[u].w >> 16) <= max_freq)
-                agg_add(iv, agg, a[u].z, hits);
-        }
-        if (kind == 2u) {
-            const uint64_t ek = (uint64_t)b[u].x | ((uint64_t)b[u].y << 32);
-            if (ek == q[u] && (int)(b[u].w >> 16) <= max_freq)
-                agg_add(iv, agg, b[u].z, hits);
-        }
+        if ((kind == 1u || kind == 2u) && inline_matches(a[u], q[u], max_freq))
+            sink.match(u, a[u].z);
+        if (kind == 2u && inline_matches(b[u], q[u], max_freq))
+            sink.match(u, b[u].z);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -396,164 +411,47 @@ __device__ __forceinline__ void probe_batch_wide(const IndexView &iv, NodeAgg &a
             const uint4 e0 = iv.entries[st];
             const uint4 e1 = iv.entries[(uint64_t)st + 1];
             const uint4 e2 = iv.entries[(uint64_t)st + 2];
-            count_if_match(iv, agg, e0, q[u], max_freq, hits);
-            count_if_match(iv, agg, e1, q[u], max_freq, hits);
-            count_if_match(iv, agg, e2, q[u], max_freq, hits);
-            for (uint32_t j = 3; j < cn; ++j)
-                count_if_match(iv, agg, iv.entries[(uint64_t)st + j], q[u], max_freq, hits);
+            bool matched = sink_entry(sink, u, e0, q[u], max_freq);
+            matched |= sink_entry(sink, u, e1, q[u], max_freq);
+            matched |= sink_entry(sink, u, e2, q[u], max_freq);
+            for (uint32_t j = 3; j < cn && !(Sink::FIRST_ENDS && matched); ++j)
+                matched |= sink_entry(sink, u, iv.entries[(uint64_t)st + j], q[u], max_freq);
         }
     }
 }
 
 // Probe flavours are separate kernel instantiations (not run-time branches) so that each keeps its own
 // register budget: the bitmap flavour runs at 8 waves/SIMD, the wide one needs ~84 VGPRs.
+// Bit 0: the pre-filter stage runs; bit 1: the wide layout.
 enum { PROBE_NARROW = 0, PROBE_BITMAP = 1, PROBE_WIDE = 2, PROBE_WIDE_FILTER = 3 };
 
+template <int U, int PROBE, typename Sink>
+__device__ __forceinline__ void walk_batch(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid, int max_freq,
+                                           Sink &sink)
+{
+    constexpr bool FILTER = (PROBE & PROBE_BITMAP) != 0;
+    if (PROBE & PROBE_WIDE)
+        walk_wide<U, FILTER>(iv, q, valid, max_freq, sink);
+    else
+        walk_narrow<U, FILTER>(iv, q, valid, max_freq, sink);
+}
+
+// The counting probe: every match goes to its node's counter, the lane's lookups and hits to its LaneStats.
 template <int U, int PROBE>
 __device__ __forceinline__ void probe_batch(const IndexView &iv, NodeAgg &agg, LaneStats &st,
                                             const uint64_t (&q)[U], uint32_t valid, int max_freq)
 {
-    if (PROBE == PROBE_BITMAP)
-        probe_batch_impl<U, true>(iv, agg, st, q, valid, max_freq);
-    else if (PROBE == PROBE_WIDE)
-        probe_batch_wide<U, false>(iv, agg, st, q, valid, max_freq);
-    else if (PROBE == PROBE_WIDE_FILTER)
-        probe_batch_wide<U, true>(iv, agg, st, q, valid, max_freq);
-    else
-        probe_batch_impl<U, false>(iv, agg, st, q, valid, max_freq);
+    st.lookups += (uint32_t)__popc(valid);
+    CountSink sink{iv, agg, st.hits};
+    walk_batch<U, PROBE>(iv, q, valid, max_freq, sink);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Membership probe (kmm_read_hits, kmm_read_hits.hpp): the gathers and the filter stage of probe_batch_impl /
-// probe_batch_wide above, but nothing is counted: bit u of the result is set iff some entry of k-mer u's bucket holds
-// that k-mer with a frequency of at most max_freq.  A k-mer under several nodes is one bit; no NodeAgg, no LaneStats.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool entry_matches(uint4 e, uint64_t q, int max_freq)
-{
-    return ((uint64_t)e.x | ((uint64_t)e.y << 32)) == q && (int)e.w <= max_freq;
-}
-
-template <int U, bool FILTER>
-__device__ __forceinline__ uint32_t member_batch_impl(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid,
-                                                      int max_freq)
-{
-    uint64_t h[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        h[u] = fastmod(q[u], iv.modulo, iv.magic);
-    if (FILTER)
-        valid = filter_stage<U>(iv, q, h, valid);
-    uint4 b[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        b[u] = make_uint4(0u, 0u, 0u, 0u);
-        if ((valid >> u) & 1u) {
-            if (FILTER) { // streamed once: keep the bitmap, not these lines, in L2
-                u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(&iv.buckets[h[u]]));
-                b[u] = make_uint4(x[0], x[1], x[2], x[3]);
-            } else {
-                b[u] = iv.buckets[h[u]];
-            }
-        }
-    }
-    uint32_t hit = 0;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint32_t kind = b[u].w & 3u;
-        if (kind == 1u) {
-            const uint64_t ek = (uint64_t)b[u].x | ((uint64_t)b[u].y << 32);
-            if (ek == q[u] && (int)(b[u].w >> 16) <= max_freq)
-                hit |= 1u << u;
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        if ((b[u].w & 3u) == 2u) {
-            const uint32_t st = b[u].x, cn = b[u].y; // cn >= 2 by construction
-            if (b[u].w & 4u) { // fingerprints present: skip the walk unless one of them matches
-                const uint32_t f = kmer_fp16(q[u]);
-                const bool may = f == (b[u].z & 0xFFFFu) || f == (b[u].z >> 16) ||
-                                 (cn > 2u && f == (b[u].w >> 16));
-                if (!may)
-                    continue;
-            }
-            const uint4 e0 = iv.entries[st];
-            const uint4 e1 = iv.entries[(uint64_t)st + 1];
-            bool m = entry_matches(e0, q[u], max_freq) || entry_matches(e1, q[u], max_freq);
-            for (uint32_t j = 2; j < cn && !m; ++j)
-                m = entry_matches(iv.entries[(uint64_t)st + j], q[u], max_freq);
-            if (m)
-                hit |= 1u << u;
-        }
-    }
-    return hit;
-}
-
-template <int U, bool FILTER>
-__device__ __forceinline__ uint32_t member_batch_wide(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid,
-                                                      int max_freq)
-{
-    uint64_t h[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-        h[u] = fastmod(q[u], iv.modulo, iv.magic);
-    if (FILTER)
-        valid = filter_stage<U>(iv, q, h, valid);
-    uint4 a[U], b[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        a[u] = make_uint4(0u, 0u, 0u, 0u);
-        if ((valid >> u) & 1u)
-            a[u] = iv.buckets[2 * h[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        b[u] = make_uint4(0u, 0u, 0u, 0u);
-        if ((a[u].w & 3u) == 2u)
-            b[u] = iv.buckets[2 * h[u] + 1];
-    }
-    uint32_t hit = 0;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint32_t kind = a[u].w & 3u;
-        if (kind == 1u || kind == 2u) {
-            const uint64_t ek = (uint64_t)a[u].x | ((uint64_t)a[u].y << 32);
-            if (ek == q[u] && (int)(a[u].w >> 16) <= max_freq)
-                hit |= 1u << u;
-        }
-        if (kind == 2u) {
-            const uint64_t ek = (uint64_t)b[u].x | ((uint64_t)b[u].y << 32);
-            if (ek == q[u] && (int)(b[u].w >> 16) <= max_freq)
-                hit |= 1u << u;
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        if ((a[u].w & 3u) == 3u) {
-            const uint32_t st = a[u].x, cn = a[u].y; // cn >= 3 by construction
-            const uint4 e0 = iv.entries[st];
-            const uint4 e1 = iv.entries[(uint64_t)st + 1];
-            const uint4 e2 = iv.entries[(uint64_t)st + 2];
-            bool m = entry_matches(e0, q[u], max_freq) || entry_matches(e1, q[u], max_freq) ||
-                     entry_matches(e2, q[u], max_freq);
-            for (uint32_t j = 3; j < cn && !m; ++j)
-                m = entry_matches(iv.entries[(uint64_t)st + j], q[u], max_freq);
-            if (m)
-                hit |= 1u << u;
-        }
-    }
-    return hit;
-}
-
+// The membership probe (kmm_read_hits, kmm_read_hits.hpp): nothing is counted, bit u of the result is set iff some entry
+// of k-mer u's bucket holds that k-mer with a frequency of at most max_freq.  No NodeAgg, no LaneStats.
 template <int U, int PROBE>
 __device__ __forceinline__ uint32_t member_batch(const IndexView &iv, const uint64_t (&q)[U], uint32_t valid, int max_freq)
 {
-    if (PROBE == PROBE_BITMAP)
-        return member_batch_impl<U, true>(iv, q, valid, max_freq);
-    else if (PROBE == PROBE_WIDE)
-        return member_batch_wide<U, false>(iv, q, valid, max_freq);
-    else if (PROBE == PROBE_WIDE_FILTER)
-        return member_batch_wide<U, true>(iv, q, valid, max_freq);
-    else
-        return member_batch_impl<U, false>(iv, q, valid, max_freq);
+    MemberSink sink;
+    walk_batch<U, PROBE>(iv, q, valid, max_freq, sink);
+    return sink.bits;
 }
