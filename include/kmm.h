@@ -504,6 +504,38 @@ int kmm_read_hits(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_of
                   uint32_t *windows);
 
 /*
+ * The record-hits mode: kmm_read_hits for reads that are still records.  kmm_set_param(idx, "record_hits", v):
+ * 0 off (default), 1 hits, 2 hits and windows; any other value is KMM_ERR_INVALID_ARG; kmm_get_param returns it.  While the mode
+ * is on:
+ *   - kmm_map_records (FASTQ, two-line and multi-line FASTA, SAM), kmm_map_bgzf, kmm_map_gzip and kmm_map_bam keep parsing as
+ *     they do: the carry between stream calls, *consumed, *n_records, the record counters, record selection,
+ *     "original_strand", break tables and the error rules (device-found errors deferred and sticky, a KMM_ERR_MALFORMED call
+ *     maps nothing) are unchanged.  They no longer touch the node counts, the per-k-mer counts or kmm_get_stats.  Instead every
+ *     record that counts in *n_records appends one entry to a queue of the handle, in stream order: the sum of *n_records over
+ *     the calls is the number of entries appended.  A record that selection drops gets no entry; SEQ "*", l_seq = 0 and an empty
+ *     sequence line give an entry of 0 / 0; a call that fails appends nothing.
+ *   - hits and windows of an entry mean what they mean in kmm_read_hits: a window counts once whatever entries or orientations
+ *     match, max_index_lookup_frequency applies as given, with also_revcomp a hit is the OR over both orientations, break bytes
+ *     remove windows, hits <= windows.
+ *   - the calls take the direct records front end and the direct index view at every chunk size — never the radix path, never
+ *     the host packer — so an index with "radix_available" 0 is served.
+ *   - a record call with "min_base_quality" > 0 is KMM_ERR_INVALID_ARG, nothing mapped: the quality mask lives in the compaction
+ *     and the radix front end, and a floor in this mode is deliberately out of scope.  kmm_map_reads, kmm_map_reads_uniform,
+ *     kmm_map_reads_qual, kmm_map_packed and kmm_map_kmers are KMM_ERR_INVALID_ARG too: flat reads have kmm_read_hits.
+ * With the mode off every call runs exactly what it runs without this feature; entries still pending stay takeable.
+ * The queue is device memory of the library and grows as needed (before the probe kernel is launched; pending entries are kept).
+ * "record_hits_pending" (read-only) is the number of entries waiting, "record_hits_pending_mode" (read-only) the last non-zero
+ * mode, in which they were appended; kmm_reset_counts empties the queue.  Switching between
+ * modes 1 and 2 while entries are pending is KMM_ERR_INVALID_ARG (the pending entries have no windows, or have them).
+ *
+ * kmm_take_record_hits synchronises like kmm_get_node_counts — a sticky or deferred device error is returned and nothing is
+ * taken — then copies the oldest min(capacity, pending) entries to hits, and to windows when that is non-NULL (entries
+ * appended in mode 2 only: windows non-NULL otherwise is KMM_ERR_INVALID_ARG).  hits and windows are uint32 arrays in host or
+ * device memory, independently.  *n_taken: the entries copied; they leave the queue, the rest keep their order.
+ */
+int kmm_take_record_hits(kmm_index_t *idx, uint32_t *hits, uint32_t *windows, int64_t capacity, int64_t *n_taken);
+
+/*
  * kmm_build_index — builds the Kmer Index arrays on the GPU from flat (k-mer, node) pairs: replaces
  * graph_kmer_index's KmerIndex.from_flat_kmers(flat_kmers, modulo) (reference call site
  * tests/test_mapping.py:36-38; gpu_counter.py:16 builds its table from the same pairs).  Entries are
@@ -692,6 +724,9 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      "records_reversed": kept records with 0x10 and at least one base that were flipped since the
  *                      statistics were last reset (kmm_get_stats(reset)); 0 while the switch is 0; synchronises like
  *                      "quality_masked_bases"
+ *   "record_hits"      0 (default) / 1 / 2: the record-hits mode — the record calls append per-record index hits (2: and windows)
+ *                      to a queue of the handle instead of counting nodes; see kmm_take_record_hits.  Read-only
+ *                      "record_hits_pending", "record_hits_pending_mode"
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the

@@ -139,7 +139,7 @@ def map_gpu(index, chunks, k, hash_map_size=0, map_reverse_complements=False,
     return node_counts
 
 
-def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, lut=None, min_base_quality=0):
+def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, lut=None, min_base_quality=0, record_hits=False):
     """How map_gpu_raw reads the file: (route, populate, steer).  fmt: the GPU's record format ("fasta_ml" = wrapped FASTA);
     probe: reads_io.probe_input of the file; env: where the KMM_CLI_* switches of A/B runs are read.
 
@@ -161,7 +161,8 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
     route "raw": one pinned buffer (RawChunker).
     lut: a caller's lookup table (--ambiguous-bases skip) is never taken by the host packer, so route "mmap", which counts
     on it (pageable views of the page cache), gives way to "raw": the bytes cross PCIe from a pinned buffer.
-    min_base_quality > 0: the same — the packer drops the quality lines the GPU is to read."""
+    min_base_quality > 0: the same — the packer drops the quality lines the GPU is to read.
+    record_hits: the same — the record-hits mode never takes the host packer."""
     gpu_inflate = probe.inflate and fmt in ("fastq", "fasta", "sam") and not env.get("KMM_CLI_NO_GPU_INFLATE")
     if fmt == "bam":
         return "bam", False, False
@@ -172,7 +173,7 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
     if probe.inflate:
         return ("raw" if env.get("KMM_CLI_NO_PREFETCH") else "prefetch"), False, False
     if (fmt in ("fastq", "fasta") and n_threads > 1 and has_device and lut is None and not min_base_quality
-            and not env.get("KMM_CLI_NO_MMAP")):
+            and not record_hits and not env.get("KMM_CLI_NO_MMAP")):
         return "mmap", not env.get("KMM_CLI_NO_POPULATE"), not env.get("KMM_CLI_NO_PACKER_STEERING")
     return "raw", False, False
 
@@ -180,7 +181,7 @@ def choose_route(fmt, probe, world_size, n_threads, has_device, env=os.environ, 
 def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                 max_index_lookup_frequency=1000, device=0, rank=0, world_size=1, before_fetch=None, n_threads=16,
                 exclude_flags=0, probe=None, lut=None, min_base_quality=0, use_record_qual=False, original_strand=False,
-                shard_bam=False, record_select=None):
+                shard_bam=False, record_select=None, record_hits=None):
     """Same job as map_gpu, but the FASTQ / two-line FASTA records are parsed ON THE GPU
     (kmm_map_records): the host only reads (and for .gz inflates) raw bytes.  fmt "bam": a BAM file, inflated and decoded
     on the GPU (kmm_map_bam; exclude_flags = its "bam_exclude_flags").  fmt "sam": SAM text, plain, BGZF or gzip, its SEQ column
@@ -195,7 +196,10 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     shard_bam: several ranks on one BAM file each map their member range, its ends trimmed to record starts found on the GPU
     (bgzf_ranges.rank_member_range_bam); without it several ranks on a BAM file are refused.
     record_select: check_record_select's dict (include flags, MAPQ floor, regions; SAM / BAM alone) or None: no
-    selection, and no call that sets one."""
+    selection, and no call that sets one.
+    record_hits: RecordHitsSink or None — the handle's record-hits mode is switched on before the first map call, and the sink
+    takes the pending entries after every map call, on every route (the queue stays chunk-sized); the node counts returned are
+    then all zero."""
     _check_bam_route(fmt, world_size, exclude_flags, shard_bam=shard_bam)
     record_select = check_record_select(fmt, **(record_select or {}))
     original_strand = check_original_strand(original_strand, fmt)
@@ -206,7 +210,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     has_device = _lib.device_count() > 0
     # (decided BEFORE anything is made: the prefetching chunker starts a reader thread and page-locks two batch buffers —
     # making and freeing those cost the BGZF route 100 ms of its map phase until it was noticed)
-    route, populate, steer = choose_route(fmt, probe, world_size, n_threads, has_device, lut=lut, min_base_quality=min_base_quality)
+    route, populate, steer = choose_route(fmt, probe, world_size, n_threads, has_device, lut=lut, min_base_quality=min_base_quality,
+                                          record_hits=record_hits is not None)
     seekable = not probe.inflate
     # page-locked memory is slow to make (~50 ms per GB): the staging buffers of the host packer are made by a helper thread
     # WHILE the index is uploaded and repacked, not inside the map phase.  (The count vector needs none: kmm_get_node_counts
@@ -224,7 +229,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     helper = threading.Thread(target=prepare_host_memory, daemon=True)
     # (.gz input needs 128 MB of it, made in 7 ms by the first call that wants it; behind a helper thread the same allocation
     # came back 100 ms after the index upload it was meant to hide behind: profiles/r05/bgzf_e2e_v6_*.txt)
-    if has_device and n_threads > 1 and seekable and lut is None and not min_base_quality:  # (the packer's buffers: no packer
+    if has_device and n_threads > 1 and seekable and lut is None and not min_base_quality and record_hits is None:  # (the packer's buffers: no packer
                                                                                              # with a table or a quality floor)
         helper.start()
     byte_range = rank_byte_range(path, fmt, rank, world_size) if (world_size > 1 and seekable) else None
@@ -250,6 +255,9 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     if original_strand:
         dev.set_param("original_strand", 1)
         _log_original_strand_filter(exclude_flags)
+    if record_hits is not None:
+        record_hits.open(dev)
+        logging.info("Route: %s, records parsed on the GPU with the handle's record-hits mode", route)
     from . import _io
     _io.set_default_threads(n_host)
     logging.info("%d host thread(s) read and pack the read bytes (-t %d, CPU budget %d)", n_host, n_threads, _io.cpu_budget())
@@ -264,7 +272,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
         n_file = os.stat(path).st_size * (6.5 if not seekable else 1)
     except OSError:
         n_file = 0
-    if dev.get_param("radix_available") and not os.environ.get("KMM_CLI_NO_BATCHING"):
+    # (the record-hits mode never takes the radix path: its chunks stay -c bytes, and so does its queue)
+    if dev.get_param("radix_available") and not os.environ.get("KMM_CLI_NO_BATCHING") and record_hits is None:
         # (radix_min_units is where the radix path BREAKS EVEN with the direct kernel, in base positions ~ half the
         # FASTQ bytes; a batch twelve times that runs within 20 % of the path's large-batch rate.  Larger batches would
         # run the GPU closer to its large-batch rate, but end to end the host is the bound — reading the file into pinned
@@ -317,7 +326,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                                     map_reverse_complements, before_fetch, t_start, counts_out=prepared.get("counts"), rank=rank,
                                     world_size=world_size, fmt=fmt, lut=lut, min_base_quality=min_base_quality,
                                     use_record_qual=use_record_qual, original_strand=original_strand, shard_bam=shard_bam,
-                                    record_select=bool(record_select))
+                                    record_select=bool(record_select), record_hits=record_hits)
     try:
         i = 0
         while True:
@@ -328,6 +337,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             if owns(i):
                 used, n_rec = dev.map_records(buf, buf.shape[0], kfmt | last, k, max_index_lookup_frequency,
                                               also_revcomp=map_reverse_complements, lut=lut)
+                if record_hits is not None:
+                    record_hits.drain(dev)
             else:   # a chunk of a shared .gz stream that another rank maps: only its record boundary is needed,
                     # cut by the SAME rule as the GPU parser's `consumed` (newline count), at end of input too
                 used, n_rec = records_cut(buf, fmt, chunker.eof), 0
@@ -380,7 +391,7 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     _log_quality_masked(min_base_quality, n_masked, n_no_qual)
     _log_records_reversed(n_reversed)
     _log_records_selected(n_selected)
-    _log_path_taken(n_radix, n_direct, n_host_packed)
+    _log_path_taken(n_radix, n_direct, n_host_packed, record_hits)
     return node_counts
 
 
@@ -509,7 +520,11 @@ def check_min_base_quality(min_base_quality, k, fmt=None, host_parser=False, use
     return q
 
 
-def _log_path_taken(n_radix, n_direct, n_host_packed=0):
+def _log_path_taken(n_radix, n_direct, n_host_packed=0, record_hits=None):
+    if record_hits is not None:
+        logging.info("path_taken: direct records front end, record-hits mode (no node was counted: %d entries taken)",
+                     sum(len(h) for h in record_hits.hits))
+        return
     logging.info("path_taken: %s (%d batches on the radix path, %d on the direct path; %d batches packed to 2 bits per base "
                  "by the host threads)"
                  % ("radix" if n_radix and not n_direct else "direct" if n_direct and not n_radix else "mixed", n_radix, n_direct,
@@ -536,7 +551,7 @@ _COMPRESSED_ROUTES = {
 
 def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fetch, t_start, counts_out=None, rank=0,
                          world_size=1, fmt="fastq", lut=None, min_base_quality=0, use_record_qual=False, original_strand=False,
-                         shard_bam=False, record_select=False):
+                         shard_bam=False, record_select=False, record_hits=None):
     """`kmer_mapper map -f reads.fq.gz | reads.bam` with the GPU inflater: windows of the file mapping -> kmm_map_<route>.
 
     route "gzip" (PLAIN gzip, kmm_map_gzip): each call goes on where the one before could verify a deflate block boundary.
@@ -545,7 +560,8 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
     complete record to the next one.  BGZF with several ranks: each maps its member range (bgzf_ranges.rank_member_range),
     the first member's head and the last member's tail trimmed to the record boundaries the ranks agree on.  BAM with several
     ranks (shard_bam): the same, the boundaries found on the GPU (bgzf_ranges.rank_member_range_bam); the ranks behind the
-    first start their stream behind the header (mid_stream), and a rank whose share is empty makes no map call."""
+    first start their stream behind the header (mid_stream), and a rank whose share is empty makes no map call.
+    record_hits: as map_gpu_raw's — the sink takes the pending entries after every map call."""
     import mmap
     counters, summary = _COMPRESSED_ROUTES[route]
     n_reads = lo = size = 0
@@ -592,6 +608,8 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
                             end = size
                         used, n_rec = dev.map_gzip(whole[pos:end], fmt=kfmt, k=k, max_index_lookup_frequency=max_freq,
                                                    also_revcomp=revcomp, first=pos == 0, last=end == size, lut=lut)
+                        if record_hits is not None:
+                            record_hits.drain(dev)
                         n_reads += n_rec
                         if used == 0:
                             if end == size:
@@ -621,6 +639,8 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
                             used, n_rec = dev.map_bam(whole[pos:end], mid_stream=mid_stream and pos == lo,
                                                       head_skip=head_skip if pos == lo else 0,
                                                       tail_stop=tail_stop if end == size else None, **common)
+                            if record_hits is not None:
+                                record_hits.drain(dev)
                             if used == 0 and end == size:
                                 raise ValueError("%s: the BAM header or the trailing bytes are no complete BGZF member" % path)
                             if used == 0 and pos == lo:  # a header longer than the window: a longer one
@@ -629,6 +649,8 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
                         else:
                             used, n_rec = dev.map_bgzf(whole[pos:end], fmt=kfmt, head_skip=head_skip if pos == lo else 0,
                                                        tail_stop=tail_stop if end == size else None, **common)
+                            if record_hits is not None:
+                                record_hits.drain(dev)
                             if used == 0 and end == size:
                                 raise ValueError("trailing bytes of %s are no complete BGZF member" % path)
                         pos += used
@@ -667,7 +689,7 @@ def _map_compressed_file(dev, path, route, kfmt, k, max_freq, revcomp, before_fe
     _log_quality_masked(min_base_quality, n_masked, n_no_qual)
     _log_records_reversed(n_reversed)
     _log_records_selected(n_selected)
-    _log_path_taken(n_radix, n_direct)
+    _log_path_taken(n_radix, n_direct, record_hits=record_hits)
     return node_counts
 
 
@@ -798,9 +820,42 @@ def map_bnp(args):
     return node_counts
 
 
-def check_read_hits_input(fmt, world_size):
-    """`kmer_mapper read-hits` takes FASTA / FASTQ in one process; everything else is refused before the index is read."""
-    if fmt in ("sam", "bam"):
+class RecordHitsSink:
+    """The per-call hook of the shared drivers (map_gpu_raw, _map_compressed_file) for the record-hits mode:
+    open(dev) switches the mode on, drain(dev) takes what is pending after a map call; result() is the whole file's (hits,
+    windows), in file order."""
+
+    def __init__(self, windows=True):
+        self.windows = bool(windows)
+        self.hits, self.wins = [], []
+
+    def open(self, dev):
+        dev.record_hits(True, windows=self.windows)
+
+    def drain(self, dev):
+        if dev.get_param("record_hits_pending"):
+            got = dev.take_record_hits()
+            self.hits.append(got[0] if self.windows else got)
+            if self.windows:
+                self.wins.append(got[1])
+
+    def result(self):
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+        return cat(self.hits), (cat(self.wins) if self.windows else None)
+
+
+_READ_HITS_SELECTION = (("--exclude-flags", "exclude_flags"), ("--include-flags", "include_flags"), ("--min-mapq", "min_mapq"),
+                        ("--regions", "regions"), ("--regions-file", "regions_file"), ("--original-strand", "original_strand"))
+
+
+def check_read_hits_input(fmt, world_size, device_parser=False, selection=()):
+    """`kmer_mapper read-hits` takes FASTA / FASTQ in one process — with --device-parser also SAM and BAM, and the options
+    that select their records (selection: the names of those given); everything else is refused before the index is read."""
+    if selection and not device_parser:
+        raise ValueError("%s needs --device-parser: records are selected where they are parsed, on the GPU" % selection[0])
+    if selection and fmt not in ("sam", "bam"):
+        raise ValueError("%s applies to SAM and BAM input only (the reads are %s)" % (selection[0], fmt))
+    if fmt in ("sam", "bam") and not device_parser:
         raise ValueError("read-hits does not read %s files: per-read hits are implemented for FASTA and FASTQ (plain or .gz) "
                          "only; SAM and BAM input is out of scope" % fmt.upper())
     if world_size > 1:
@@ -810,10 +865,16 @@ def check_read_hits_input(fmt, world_size):
 
 def read_hits_file(args):
     """`kmer_mapper read-hits`: per read of a FASTA / FASTQ file, in file order, the number of its k-mers that are in the
-    index (kmm_read_hits) -> <out>.npy (uint32), with --windows also the number of windows looked up -> <out>.windows.npy."""
+    index (kmm_read_hits) -> <out>.npy (uint32), with --windows also the number of windows looked up -> <out>.windows.npy.
+    With --device-parser the records are parsed on the GPU (read_hits_file_device), and SAM and BAM are read too."""
     k = args.kmer_size
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    check_read_hits_input(probe_input(args.reads).fmt, world)
+    device_parser = bool(getattr(args, "device_parser", False))
+    selection = [opt for opt, name in _READ_HITS_SELECTION if getattr(args, name, None)]
+    probe = probe_input(args.reads)
+    check_read_hits_input(probe.fmt, world, device_parser, selection)
+    if device_parser:
+        return read_hits_file_device(args, probe)
     lut = None
     if args.ambiguous_bases == "skip":
         from .util import ambiguous_skip_lut
@@ -840,6 +901,38 @@ def read_hits_file(args):
         dev.close()
     hits = np.concatenate(hits) if hits else np.zeros(0, np.uint32)
     wins = np.concatenate(wins) if wins else np.zeros(0, np.uint32)
+    return _save_read_hits(args, hits, wins)
+
+
+def read_hits_file_device(args, probe):
+    """`kmer_mapper read-hits --device-parser`: the file goes down the route `map` would choose for it in one process
+    (choose_route: raw records, BGZF, gzip, SAM, BAM — parsed, inflated and selected on the GPU) with the handle's record-hits
+    mode on; the pending entries are taken after every map call."""
+    k = args.kmer_size
+    fmt = probe.fmt
+    select = check_record_select(fmt, include_flags=args.include_flags, min_mapq=args.min_mapq, regions=args.regions,
+                                 regions_file=args.regions_file)
+    original_strand = check_original_strand(bool(args.original_strand), fmt)
+    _check_bam_route(fmt, 1, int(args.exclude_flags or 0))
+    lut = None
+    if args.ambiguous_bases == "skip":
+        from .util import ambiguous_skip_lut
+        lut = ambiguous_skip_lut()
+        if k < 2:
+            raise ValueError("--ambiguous-bases skip needs -k 2 or more")
+    kmer_index = _get_kmer_index_from_args(args)
+    if fmt == "fasta" and not probe.two_line:
+        fmt = "fasta_ml"
+    sink = RecordHitsSink(windows=True)
+    logging.info("read-hits: records parsed on the GPU, record-hits mode (--device-parser)")
+    map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
+                device=args.device, n_threads=16, exclude_flags=int(args.exclude_flags or 0), probe=probe, lut=lut,
+                original_strand=original_strand, record_hits=sink, **({"record_select": select} if select else {}))
+    hits, wins = sink.result()
+    return _save_read_hits(args, hits, wins)
+
+
+def _save_read_hits(args, hits, wins):
     n_reads, n_sel = hits.shape[0], int((hits >= args.min_hits).sum())
     logging.info("%d reads; %d (%.2f %%) have at least %d k-mer%s in the index", n_reads, n_sel,
                  100.0 * n_sel / max(n_reads, 1), args.min_hits, "" if args.min_hits == 1 else "s")
@@ -931,7 +1024,7 @@ def build_argument_parser():
     sub = subparsers.add_parser("read-hits", help="Extension: per read, the number of its k-mers that are in a kmer index")
     sub.add_argument("-i", "--kmer-index", required=False)
     sub.add_argument("-b", "--index-bundle", required=False)
-    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format (SAM and BAM are refused)")
+    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format (SAM, .sam.gz and BAM with --device-parser only)")
     sub.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
     sub.add_argument("-c", "--chunk-size", required=False, type=int, default=2500000, help="N bytes to process in each chunk")
     sub.add_argument("-o", "--output-file", required=True,
@@ -948,6 +1041,24 @@ def build_argument_parser():
                      help="The log reports how many reads have at least N hits. Default 1.")
     sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
     sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
+    sub.add_argument("--device-parser", action="store_true",
+                     help="Parse the records on the GPU, on the route `map` takes for the file (.gz inflated there), with the "
+                          "library's record-hits mode. Also reads SAM (.sam, .sam.gz) and BAM.")
+    sub.add_argument("--exclude-flags", default=0, type=lambda v: int(v, 0),
+                     help="With --device-parser, SAM and BAM input only: leave out records whose FLAG has any of these bits.")
+    sub.add_argument("--include-flags", default=0, type=lambda v: int(v, 0),
+                     help="With --device-parser, SAM and BAM input only: only records whose FLAG has all of these bits "
+                          "(4 = unmapped reads).")
+    sub.add_argument("--min-mapq", default=0, type=int, metavar="Q",
+                     help="With --device-parser, SAM and BAM input only: only records with MAPQ >= Q.")
+    sub.add_argument("--regions", action="append", default=None, metavar="REGIONS",
+                     help="With --device-parser, SAM and BAM input only: only records that overlap one of these regions "
+                          "(syntax as `map --regions`).")
+    sub.add_argument("--regions-file", default=None, metavar="BED",
+                     help="With --device-parser, SAM and BAM input only: regions from a BED file; adds to --regions.")
+    sub.add_argument("--original-strand", action="store_true",
+                     help="With --device-parser, SAM and BAM input only: records whose FLAG has 0x10 are looked up in read "
+                          "orientation.")
     sub.set_defaults(func=read_hits_file)
     return parser
 

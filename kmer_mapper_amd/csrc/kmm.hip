@@ -424,6 +424,12 @@ struct kmm_index : IndexStreams, RxArrays {
     std::string sticky_msg;
     uint64_t map_calls = 0;   // sequence number of map calls on this handle (error reports name the call)
     int64_t read_hits_calls = 0; // kmm_read_hits calls that were accepted ("read_hits_calls")
+    // the record-hits mode: while "record_hits" is 1 or 2 the record calls append one entry per record to this
+    // queue instead of counting nodes.  Entries [rhq_head, rhq_head + rhq_pending) of both arrays wait for
+    // kmm_take_record_hits; rhq_mode: the last non-zero "record_hits" (whether the pending entries have their windows)
+    int record_hits = 0, rhq_mode = 0;
+    DevBuf rhq_hits, rhq_win;
+    int64_t rhq_head = 0, rhq_pending = 0, rhq_cap = 0;
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
     int comm_rank = -1, comm_size = 0;
@@ -969,6 +975,60 @@ int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offs
     return KMM_OK;
 }
 
+// ---- the record-hits queue
+// Room for n more entries behind the pending ones, zeroed on the handle's stream; *hits / *windows: the first new entry.  The
+// arrays grow here, before the probe kernel is launched (a piece's record count is known from its census): a new pair, the
+// pending entries copied to its start.  The caller adds n to rhq_pending once its kernel is launched.
+int rhq_reserve(kmm_index *ix, int64_t n, uint32_t **hits, uint32_t **windows)
+{
+    if (ix->rhq_pending == 0)
+        ix->rhq_head = 0;
+    if (ix->rhq_head + ix->rhq_pending + n > ix->rhq_cap) {
+        int64_t cap = 2 * (ix->rhq_pending + n);
+        if (cap < (1 << 16))
+            cap = 1 << 16;
+        DevBuf nh, nw;
+        KMMCHK(ensure(nh, (size_t)cap * 4));
+        KMMCHK(ensure(nw, (size_t)cap * 4));
+        if (ix->rhq_pending > 0) {
+            const size_t bytes = (size_t)ix->rhq_pending * 4;
+            HIPCHK(hipMemcpyAsync(nh.p, (const uint32_t *)ix->rhq_hits.p + ix->rhq_head, bytes, hipMemcpyDeviceToDevice, ix->stream));
+            HIPCHK(hipMemcpyAsync(nw.p, (const uint32_t *)ix->rhq_win.p + ix->rhq_head, bytes, hipMemcpyDeviceToDevice, ix->stream));
+        }
+        HIPCHK(hipStreamSynchronize(ix->stream)); // (the old pair is freed below)
+        ix->rhq_hits = std::move(nh);
+        ix->rhq_win = std::move(nw);
+        ix->rhq_head = 0;
+        ix->rhq_cap = cap;
+    }
+    *hits = (uint32_t *)ix->rhq_hits.p + ix->rhq_head + ix->rhq_pending;
+    *windows = (uint32_t *)ix->rhq_win.p + ix->rhq_head + ix->rhq_pending;
+    if (n > 0) {
+        HIPCHK(hipMemsetAsync(*hits, 0, (size_t)n * 4, ix->stream));
+        HIPCHK(hipMemsetAsync(*windows, 0, (size_t)n * 4, ix->stream));
+    }
+    return KMM_OK;
+}
+
+// The map calls without records have kmm_read_hits: refused while the mode is on, nothing mapped.
+int refuse_in_record_hits(const kmm_index *ix, const char *who)
+{
+    if (ix && ix->record_hits)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_hits\" is %d: the mode serves the record calls (kmm_map_records, kmm_map_bgzf, "
+                    "kmm_map_gzip, kmm_map_bam); reads held as flat arrays have kmm_read_hits (nothing is mapped)", who, ix->record_hits);
+    return KMM_OK;
+}
+
+// A record call while the mode is on and a quality floor is set: refused, nothing mapped (the quality mask lives in the
+// compaction and the radix front end, which the mode never takes).
+int refuse_quality_in_record_hits(const kmm_index *ix, const char *who)
+{
+    if (ix && ix->record_hits && ix->min_base_quality > 0)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_hits\" is %d and min_base_quality is %d: the record-hits mode applies no "
+                    "quality floor (nothing is mapped)", who, ix->record_hits, ix->min_base_quality);
+    return KMM_OK;
+}
+
 } // namespace
 
 // ================================================================================================
@@ -1285,6 +1345,7 @@ int kmm_reset_counts(kmm_index_t *ix)
     if (ix->rx_ecnt_acc)
         HIPCHK(hipMemsetAsync(ix->rx_ecnt_acc, 0, sizeof(uint32_t) * (size_t)(ix->rx_S ? ix->rx_S : 1), ix->stream));
     ix->ecnt_dirty = false;
+    ix->rhq_head = ix->rhq_pending = 0; // (the record-hits queue is emptied with the counts; its arrays stay)
     // an error that the kernels of an earlier map call have found, or will find, and no synchronising call has reported yet
     // goes with that call's counts: left in place it would be reported against the counts of the calls AFTER this reset
     HIPCHK(hipMemsetAsync(ix->first_bad, 0xFF, 3 * sizeof(unsigned long long), ix->stream));
@@ -1658,6 +1719,7 @@ int kmm_map_kmers(kmm_index_t *ix, const uint64_t *kmers, int64_t n, int max_fre
 {
     if (!ix)
         return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(refuse_in_record_hits(ix, "kmm_map_kmers"));
     if (n < 0 || (n > 0 && !kmers))
         return fail(KMM_ERR_INVALID_ARG, "kmers NULL or n negative");
     if (also_revcomp)
@@ -2095,6 +2157,7 @@ int kmm_map_reads(kmm_index_t *ix, const uint8_t *bases, const int64_t *read_off
 {
     if (!ix)
         return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(refuse_in_record_hits(ix, "kmm_map_reads"));
     KMMCHK(check_k(k));
     if (n_reads < 0)
         return fail(KMM_ERR_INVALID_ARG, "n_reads negative");
@@ -2111,6 +2174,7 @@ int kmm_map_reads_uniform(kmm_index_t *ix, const uint8_t *bases, int64_t n_reads
 {
     if (!ix)
         return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(refuse_in_record_hits(ix, "kmm_map_reads_uniform"));
     KMMCHK(check_k(k));
     if (n_reads < 0 || read_len < 0)
         return fail(KMM_ERR_INVALID_ARG, "n_reads / read_len negative");
@@ -2175,6 +2239,7 @@ int kmm_map_reads_qual(kmm_index_t *ix, const uint8_t *bases, const uint8_t *qua
 {
     if (!ix)
         return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(refuse_in_record_hits(ix, "kmm_map_reads_qual"));
     KMMCHK(check_k(k));
     if (qual_base != 0 && qual_base != 33)
         return fail(KMM_ERR_INVALID_ARG, "kmm_map_reads_qual: qual_base %d: 33 (Phred+33 text) or 0 (raw Phred)", qual_base);
@@ -2414,7 +2479,7 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     KMMCHK(stage_in<uint8_t>(ix, s.bases, raw, (size_t)n_bytes, &rv.bases, &staged));
     bool has_break = false;
     KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &staged, &has_break));
-    if (records_take_radix(ix, n_bytes, format)) {
+    if (!ix->record_hits && records_take_radix(ix, n_bytes, format)) {
         KMMCHK(map_records_piece_radix(ix, s, rv.bases, n_bytes, format, k, max_freq, also_revcomp, rv.lut, has_break, consumed,
                                        n_records));
         return stage_release(ix, s, false);
@@ -2448,7 +2513,20 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         rv.period_mask = (uint32_t)format - 1u;
         rv.header_char = format == KMM_FORMAT_FASTQ ? (uint32_t)'@' : (uint32_t)'>';
         KMMCHK(stage_copies_done(ix));
-        if (has_break) // (a break byte on a sequence line: a break like the bytes outside the sequence lines)
+        if (ix->record_hits) {
+            // the record-hits mode: one zeroed entry per record of the piece behind the pending ones, then the
+            // membership kernel on the same front end; the node counts, the per-k-mer counts and the statistics stay untouched
+            uint32_t *q_hits = nullptr, *q_win = nullptr;
+            KMMCHK(ensure_direct(ix));
+            KMMCHK(rhq_reserve(ix, out[1], &q_hits, &q_win));
+            if (ix->record_hits != 2)
+                q_win = nullptr;
+            if (has_break)
+                KMMCHK(launch_read_hits<MODE_RECORDS_BRK>(ix, rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, q_hits, q_win));
+            else
+                KMMCHK(launch_read_hits<MODE_RECORDS>(ix, rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, q_hits, q_win));
+            ix->rhq_pending += out[1];
+        } else if (has_break) // (a break byte on a sequence line: a break like the bytes outside the sequence lines)
             KMMCHK(launch_map_reads<MODE_RECORDS_BRK>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
         else
             KMMCHK(launch_map_reads<MODE_RECORDS>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
@@ -2700,7 +2778,13 @@ int kmm_map_records(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int fo
                     int max_freq, int also_revcomp, const uint8_t *lut, int64_t *consumed,
                     int64_t *n_records)
 {
-    return guarded("kmm_map_records", [&] { return map_records_entry(ix, raw, n_bytes, format, k, max_freq, also_revcomp, lut, consumed, n_records); });
+    return guarded("kmm_map_records", [&] {
+        const int64_t pending0 = ix ? ix->rhq_pending : 0;
+        const int rc = map_records_entry(ix, raw, n_bytes, format, k, max_freq, also_revcomp, lut, consumed, n_records);
+        if (rc != KMM_OK && ix)
+            ix->rhq_pending = pending0; // (record-hits mode: a call that fails reports no record and appends no entry)
+        return rc;
+    });
 }
 
 static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int format, int k, int max_freq, int also_revcomp,
@@ -2726,6 +2810,7 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         return fail(KMM_ERR_INVALID_ARG, "raw is NULL");
     HIPCHK(hipSetDevice(ix->device));
     KMMCHK(check_k_lut(k, lut));
+    KMMCHK(refuse_quality_in_record_hits(ix, "kmm_map_records"));
     KMMCHK(check_quality(ix, "kmm_map_records", k, format == KMM_FORMAT_SAM));
     // A quality floor on FASTQ: always compaction + the radix path, whatever the batch size and "path" say (as kmm_map_packed) —
     // the records front end of the direct path has no flat positions to put a quality mark on — and never the host packer,
@@ -2743,7 +2828,8 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     // record ended, so the pieces cut the chunk exactly as one census over all of it would
     // (multi-line FASTA and SAM are turned into two-line FASTA on the device first: never the host packer, whose parser knows
     // FASTQ and two-line FASTA only)
-    if (format != KMM_FORMAT_FASTA && format != KMM_FORMAT_SAM && records_take_radix(ix, n_bytes, format)) {
+    // (the record-hits mode takes the direct records front end at every size: neither the radix path nor the host packer)
+    if (!ix->record_hits && format != KMM_FORMAT_FASTA && format != KMM_FORMAT_SAM && records_take_radix(ix, n_bytes, format)) {
         // raw bytes in host memory: the host threads pack the sequence lines to 2 bits per base before they cross PCIe
         if (ix->host_pack_threads > 0 && !lut && !ix->dbg_rec_skip && !ix->dbg_rec_copy_stream && !is_device_ptr(raw)) {
             bool done = false;
@@ -2802,6 +2888,7 @@ int kmm_map_packed(kmm_index_t *ix, const uint32_t *codes, int64_t n_bases, int6
 {
     if (!ix)
         return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(refuse_in_record_hits(ix, "kmm_map_packed"));
     KMMCHK(check_k(k));
     if (n_bases < 0 || n_reads < 0 || read_len < 0)
         return fail(KMM_ERR_INVALID_ARG, "n_bases / n_reads / read_len negative");
@@ -3036,6 +3123,7 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
     if (c.mid_stream && ix->bam_n_ref_param < 0)
         return fail(KMM_ERR_INVALID_ARG, "%s: KMM_FORMAT_MID_STREAM needs \"bam_n_ref\" (kmm_set_param): a stream that begins behind "
                                          "the header does not say how many references the file has", c.who);
+    KMMCHK(refuse_quality_in_record_hits(ix, c.who));
     KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
@@ -4046,6 +4134,35 @@ int kmm_read_hits(kmm_index_t *ix, const uint8_t *bases, const int64_t *read_off
     });
 }
 
+int kmm_take_record_hits(kmm_index_t *ix, uint32_t *hits, uint32_t *windows, int64_t capacity, int64_t *n_taken)
+{
+    if (!ix || !n_taken)
+        return fail(KMM_ERR_INVALID_ARG, "NULL argument");
+    *n_taken = 0;
+    if (capacity < 0 || (capacity > 0 && !hits))
+        return fail(KMM_ERR_INVALID_ARG, "kmm_take_record_hits: capacity negative, or hits is NULL");
+    if (windows && ix->rhq_mode != 2)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_take_record_hits: windows given, and the entries were appended with \"record_hits\" %d: "
+                    "windows are kept in mode 2 only (nothing is taken)", ix->rhq_mode);
+    HIPCHK(hipSetDevice(ix->device));
+    KMMCHK(drain(ix)); // (a sticky or deferred device error: returned, nothing taken)
+    const int64_t n = capacity < ix->rhq_pending ? capacity : ix->rhq_pending;
+    if (n > 0) {
+        const size_t bytes = (size_t)n * 4;
+        HIPCHK(hipMemcpy(hits, (const uint32_t *)ix->rhq_hits.p + ix->rhq_head, bytes,
+                         is_device_ptr(hits) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+        if (windows)
+            HIPCHK(hipMemcpy(windows, (const uint32_t *)ix->rhq_win.p + ix->rhq_head, bytes,
+                             is_device_ptr(windows) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    }
+    ix->rhq_head += n;
+    ix->rhq_pending -= n;
+    if (ix->rhq_pending == 0)
+        ix->rhq_head = 0;
+    *n_taken = n;
+    return KMM_OK;
+}
+
 int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads,
                       int k, const uint8_t *lut, uint64_t *out, int64_t n_out)
 {
@@ -4615,6 +4732,17 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value < 0 || value > 93)
             return fail(KMM_ERR_INVALID_ARG, "min_base_quality outside [0, 93]");
         ix->min_base_quality = (int)value;
+    } else if (!strcmp(name, "record_hits")) {
+        // 1 / 2: the record calls append per-record index hits (2: and windows) to the handle's queue instead of counting
+        // nodes (kmm_take_record_hits); 0: off, entries still pending stay takeable
+        if (value < 0 || value > 2)
+            return fail(KMM_ERR_INVALID_ARG, "record_hits takes 0 (off), 1 (hits) or 2 (hits and windows)");
+        if (value != 0 && ix->rhq_pending > 0 && ix->rhq_mode != (int)value)
+            return fail(KMM_ERR_INVALID_ARG, "record_hits %lld with %lld entries of mode %d pending: take them (kmm_take_record_hits) "
+                        "or empty the queue (kmm_reset_counts) first", (long long)value, (long long)ix->rhq_pending, ix->rhq_mode);
+        ix->record_hits = (int)value;
+        if (value != 0)
+            ix->rhq_mode = (int)value;
     } else if (!strcmp(name, "use_record_qual")) {
         // 1: with "min_base_quality" > 0, kmm_map_bam and KMM_FORMAT_SAM decode every record's QUAL and apply the floor
         if (value != 0 && value != 1)
@@ -4689,6 +4817,12 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->original_strand;
     else if (!strcmp(name, "debug_records_piece_kb"))
         *value = ix->dbg_rec_piece_kb;
+    else if (!strcmp(name, "record_hits"))
+        *value = ix->record_hits;
+    else if (!strcmp(name, "record_hits_pending")) // entries waiting for kmm_take_record_hits
+        *value = ix->rhq_pending;
+    else if (!strcmp(name, "record_hits_pending_mode")) // the mode the pending entries were appended in (2: they have windows)
+        *value = ix->rhq_mode;
     else if (!strcmp(name, "read_hits_calls")) // kmm_read_hits calls (a pure query: no other counter moves)
         *value = ix->read_hits_calls;
     else if (!strcmp(name, "bam_calls")) // kmm_map_bam calls that mapped their records (a window inside the header not counted)

@@ -68,6 +68,53 @@ KMM_RH_HD void rh_cursor_advance(const int64_t *offs, RhCursor &c, int64_t p)
     rh_cursor_load(offs, c);
 }
 
+// ---- records mode: the reads are the records of raw two-line FASTA / FASTQ text, and the read of a position
+// is arithmetic on its line number (the newlines before it): lines_per_record = 1 << period_shift, 2 or 4.
+KMM_RH_HD uint32_t rh_record_of_line(uint32_t line, uint32_t period_shift)
+{
+    return line >> period_shift;
+}
+
+// The line of byte j of a lane whose first byte lies on line `line0`; nl: bit i = the lane's byte i is '\n' (a newline
+// belongs to the line it ends).
+KMM_RH_HD uint32_t rh_line_of_byte(uint32_t line0, uint32_t nl, int j)
+{
+    return line0 + (uint32_t)__builtin_popcount(nl & ((1u << j) - 1u));
+}
+
+// One run of a read's windows inside a lane.
+struct RhRun {
+    uint32_t r, h, w;
+};
+
+// Fold the lane's S windows (valid / hit: bit j = window j exists / is in the index) into runs of one record each.  A run
+// that ends inside the lane goes to flush(r, h, w) — a lane's first byte often lies in the record before its window's
+// ("\nC\n>" of ">\nA\n>\nC\n>\nG\n" at k = 1), and nothing here counts on a lane's windows sharing one record — and the last
+// one stays in `run` for the reduction across the wavefront.  A lane without windows leaves the record of its first byte
+// with sums of zero; flush may be called with sums of zero.
+template <int S, typename Flush>
+KMM_RH_HD void rh_fold_records(uint32_t line0, uint32_t nl, uint32_t period_shift, uint32_t valid, uint32_t hit, RhRun &run,
+                               Flush &&flush)
+{
+    run.r = rh_record_of_line(line0, period_shift);
+    run.h = run.w = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < S; ++j) {
+        if (!((valid >> j) & 1u))
+            continue;
+        const uint32_t r = rh_record_of_line(rh_line_of_byte(line0, nl, j), period_shift);
+        if (r != run.r) {
+            flush(run.r, run.h, run.w);
+            run.r = r;
+            run.h = run.w = 0;
+        }
+        run.h += (hit >> j) & 1u;
+        run.w += 1u;
+    }
+}
+
 #if defined(__HIPCC__)
 
 // tile_first_read[t] for t = 0 .. n_tiles (rh_tile_first_read): one search over all offsets per tile boundary, so that the
@@ -125,6 +172,9 @@ __device__ __forceinline__ void rh_wave_reduce(uint32_t *__restrict__ hits, uint
 // rv.offsets and tile_first_read — or, for reads of one length that took the ragged front end (shorter than 16 bases, or a
 // table with breaks), rv.offsets == null and the division again.  The read id never comes from the read-start bitset:
 // breaks set bits there too.
+// MODE_RECORDS, MODE_RECORDS_BRK: raw two-line FASTA / FASTQ text; the reads are its records and the read id
+// comes from the line number that stage 1 of the records front end forms (TileLines).  hits / windows point at the piece's
+// first entry, zeroed on the stream before the launch: a record without a window keeps its zeros.
 template <int S, int MODE, int PROBE>
 __global__ void __launch_bounds__(256) k_read_hits(ReadsView rv, IndexView iv, int k, int max_freq, int also_rc,
                                                    int64_t n_tiles, const int64_t *__restrict__ tile_first_read,
@@ -135,9 +185,18 @@ __global__ void __launch_bounds__(256) k_read_hits(ReadsView rv, IndexView iv, i
     sm.lut[threadIdx.x] = rv.lut[threadIdx.x];
     const TileConst tc = tile_const(rv, k);
     const bool by_offsets = MODE == MODE_GENERAL && rv.offsets != nullptr;
+    [[maybe_unused]] TileLines tl;
+    if constexpr (mode_is_records(MODE)) {
+        __shared__ uint32_t line_stage[2 * TileSmem<S>::NV];
+        tl.stage = line_stage;
+    }
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         uint64_t q[S];
-        const uint32_t valid = tile_kmers<S, MODE>(rv, tc, tile, k, sm, q);
+        uint32_t valid;
+        if constexpr (mode_is_records(MODE))
+            valid = tile_kmers<S, MODE>(rv, tc, tile, k, sm, q, (int)threadIdx.x, &tl);
+        else
+            valid = tile_kmers<S, MODE>(rv, tc, tile, k, sm, q);
         uint32_t hit = 0;
         if (__builtin_amdgcn_ballot_w64(valid != 0)) {
             hit = member_batch<S, PROBE>(iv, q, valid, max_freq);
@@ -148,6 +207,13 @@ __global__ void __launch_bounds__(256) k_read_hits(ReadsView rv, IndexView iv, i
                     q[j] = revcomp(q[j], k);
                 hit |= member_batch<S, PROBE>(iv, q, miss, max_freq);
             }
+        }
+        if constexpr (mode_is_records(MODE)) {
+            RhRun run;
+            rh_fold_records<S>(tl.line, tl.nl, (uint32_t)__popc(rv.period_mask), valid, hit, run,
+                               [&](uint32_t r, uint32_t h, uint32_t w) { rh_emit(hits, windows, (int64_t)r, h, w); });
+            rh_wave_reduce(hits, windows, (int64_t)run.r, run.h | (run.w << 16));
+            continue;
         }
         // fold the lane's windows into runs of (read, hits, windows); a run that ends inside the lane goes out at once
         int64_t p0 = tile * T + (int64_t)threadIdx.x * S;

@@ -36,6 +36,15 @@ struct TileWin {
     uint64_t lo, hi;
 };
 
+// Records mode: where the lane's S bytes lie among the chunk's lines.  `line` = newlines before the lane's first position
+// (a position's record is its line number divided by the lines per record), `nl` = bit j: byte j of the lane is '\n'.
+// `stage` is the caller's: 2 * TileSmem<S>::NV words of LDS, through which stage 1's per-vector figures reach the lanes of
+// stage 3 (kept out of TileSmem: the kernels that do not ask carry no word of it).
+struct TileLines {
+    uint32_t *stage;
+    uint32_t line, nl;
+};
+
 __device__ __forceinline__ TileConst tile_const(const ReadsView &rv, int k)
 {
     TileConst c;
@@ -146,11 +155,14 @@ __device__ __forceinline__ void tile_load_vec(const ReadsView &rv, const TileCon
 // own TileSmem, and all of them pass through the same barriers.
 // TOPBAR = false: the caller guarantees that a workgroup barrier already lies between the previous tile's last LDS
 // read (and the code table's staging) and this call.
-template <int S, int MODE, bool TOPBAR = true, bool C2 = false>
+// LINES (records mode): `lines` is given and filled (a template parameter, so that the kernels that do not ask compile
+// exactly the code they had: a run-time test on the pointer changed the register counts of k_map_reads' record kernels).
+template <int S, int MODE, bool TOPBAR = true, bool C2 = false, bool LINES = false>
 __device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileConst &tc, int64_t tile,
                                                int k, TileSmem<S> &sm, uint64_t (&q)[S], const int tid,
-                                               const TileRaw &raw, TileWin *win = nullptr)
+                                               const TileRaw &raw, TileWin *win = nullptr, TileLines *lines = nullptr)
 {
+    static_assert(!LINES || (mode_is_records(MODE) && 16 % S == 0), "TileLines: records mode, a lane's positions inside one vector");
     const uint32_t (&w)[4] = raw.w;
     constexpr bool UNIFORM = MODE == MODE_UNIFORM;
     constexpr bool RECORDS = mode_is_records(MODE);
@@ -190,6 +202,10 @@ __device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileCo
             uint32_t line0 = t0 < total ? rv.super_nl[(tile * (T / 1024)) >> 10] + rv.tile_nl[tile * (T / 1024)] : 0u;
             for (int i = 0; i < v; ++i)
                 line0 += sm.codes[i];
+            if constexpr (LINES) { // (the caller's own LDS words: read in stage 3, behind this stage's barriers)
+                lines->stage[2 * v] = line0;
+                lines->stage[2 * v + 1] = nl;
+            }
             // first byte of a line: preceded by '\n' (or the very first byte of the chunk)
             const uint32_t prev_nl = (p == 0) ? 1u : (p - 1 < total ? (rv.bases[p - 1] == 10u) : 0u);
             const uint32_t first = ((nl << 1) | prev_nl) & 0xFFFFu;
@@ -391,6 +407,12 @@ __device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileCo
         win->lo = lo;
         win->hi = hi;
     }
+    if constexpr (LINES) { // the lane's S bytes lie inside one staged vector (S divides 16)
+        const uint32_t vl = lines->stage[2 * (q0 >> 4)], vn = lines->stage[2 * (q0 >> 4) + 1];
+        const int sh = q0 & 15;
+        lines->line = vl + (uint32_t)__popc(vn & ((1u << sh) - 1u));
+        lines->nl = (vn >> sh) & ((1u << S) - 1u);
+    }
 #pragma unroll
     for (int j = 0; j < S; ++j)
         q[j] = (j == 0 ? lo : ((lo >> (2 * j)) | (hi << (64 - 2 * j)))) & tc.kmask;
@@ -404,6 +426,15 @@ __device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileCo
     TileRaw raw;
     tile_load_vec<S, MODE>(rv, tc, tile, tid, raw);
     return tile_kmers<S, MODE>(rv, tc, tile, k, sm, q, tid, raw);
+}
+
+template <int S, int MODE>
+__device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileConst &tc, int64_t tile,
+                                               int k, TileSmem<S> &sm, uint64_t (&q)[S], const int tid, TileLines *lines)
+{
+    TileRaw raw;
+    tile_load_vec<S, MODE>(rv, tc, tile, tid, raw);
+    return tile_kmers<S, MODE, true, false, true>(rv, tc, tile, k, sm, q, tid, raw, nullptr, lines);
 }
 
 template <int S, int MODE>

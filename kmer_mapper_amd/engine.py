@@ -377,6 +377,36 @@ class DeviceIndex:
                                             int(bool(also_revcomp)), t.ptr, hp, wp))
         return (hits, win) if windows else hits
 
+    def record_hits(self, on=True, windows=False):
+        """The record-hits mode (include/kmm.h): while it is on, map_records / map_bgzf / map_gzip / map_bam
+        append one entry per record — its index hits, with windows=True also its windows, as read_hits defines them — to a
+        queue of the handle instead of counting nodes; take_record_hits() fetches them.  on=False: the calls count nodes
+        again; entries still pending stay takeable."""
+        self.set_param("record_hits", (2 if windows else 1) if on else 0)
+
+    def take_record_hits(self, capacity=None, out=None):
+        """kmm_take_record_hits: the oldest pending entries (all of them, or at most `capacity`), in stream order, as numpy
+        uint32 arrays: hits — or (hits, windows) when the entries were appended with windows=True.  They leave the queue.
+        out: (hits, windows-or-None) arrays or torch tensors to write into instead (host or device, uint32 / int32; their
+        length is the capacity); then the number of entries taken is returned."""
+        with_windows = self.get_param("record_hits_pending_mode") == 2 if out is None else out[1] is not None
+        taken = ctypes.c_int64(0)
+        if out is not None:
+            h, w = _Arg(out[0], np.uint32, "hits"), _Arg(out[1], np.uint32, "windows")
+            cap = h.n if capacity is None else min(int(capacity), h.n)
+            if with_windows and w.n < cap:
+                raise ValueError("windows holds %d entries, hits %d" % (w.n, cap))
+            _lib.check(_lib.lib().kmm_take_record_hits(self._h, h.ptr, w.ptr, cap, ctypes.byref(taken)))
+            return taken.value
+        pending = self.get_param("record_hits_pending")
+        cap = pending if capacity is None else min(int(capacity), pending)
+        hits = np.zeros(cap, dtype=np.uint32)
+        win = np.zeros(cap, dtype=np.uint32) if with_windows else None
+        _lib.check(_lib.lib().kmm_take_record_hits(self._h, hits.ctypes.data_as(_P),
+                                                   win.ctypes.data_as(_P) if with_windows else None, cap, ctypes.byref(taken)))
+        hits = hits[:taken.value]
+        return (hits, win[:taken.value]) if with_windows else hits
+
     # -- measurement -----------------------------------------------------------------------------
     def set_timing(self, on=True):
         _lib.check(_lib.lib().kmm_set_timing(self._h, int(bool(on))))

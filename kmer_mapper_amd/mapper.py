@@ -118,3 +118,27 @@ def read_hits(index, reads, k=31, max_index_lookup_frequency=1000, also_revcomp=
     return _device_index(index, max_node_id, device).read_hits(batch.bases, batch.offsets, k=k,
                                                                max_index_lookup_frequency=max_index_lookup_frequency,
                                                                also_revcomp=also_revcomp, lut=lut, windows=windows)
+
+
+def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, windows=False, device=0):
+    """Extension: read_hits for reads that are still records — `raw` is a chunk of FASTQ (fmt "fastq"), two-line FASTA ("fasta")
+    or SAM ("sam") text (bytes, a uint8 array or a torch tensor, host or device), parsed on the GPU with the cached handle's
+    record-hits mode (DeviceIndex.record_hits / take_record_hits).  Returns (hits, consumed) — with windows=True
+    (hits, windows, consumed): one entry per whole record of the chunk, in order; raw[consumed:] is the incomplete last record,
+    to be put in front of the next chunk.  The handle's node counts do not move, and the mode is off again afterwards."""
+    from . import _lib
+    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "sam": _lib.FORMAT_SAM}[fmt]
+    if isinstance(raw, (bytes, bytearray, memoryview)):
+        raw = np.frombuffer(bytes(raw), dtype=np.uint8)
+    max_node_id = int(np.max(index._nodes)) if len(index._nodes) else 0
+    dev = _device_index(index, max_node_id, device)
+    if dev.get_param("record_hits_pending"):
+        raise ValueError("the cached handle has record hits pending: take them first (DeviceIndex.take_record_hits)")
+    dev.record_hits(True, windows=windows)
+    try:
+        consumed, _ = dev.map_records(raw, fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency,
+                                      also_revcomp=also_revcomp, lut=lut)
+        got = dev.take_record_hits()
+    finally:
+        dev.record_hits(False)
+    return (got[0], got[1], consumed) if windows else (got, consumed)
