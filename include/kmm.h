@@ -536,6 +536,47 @@ int kmm_read_hits(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_of
 int kmm_take_record_hits(kmm_index_t *idx, uint32_t *hits, uint32_t *windows, int64_t capacity, int64_t *n_taken);
 
 /*
+ * The record-keep mode: the reads that the record-hits mode counted, written back out.  It extends that mode:
+ * with "record_keep" 0 (default) every call runs the kernels it runs without this feature.  kmm_set_param / kmm_get_param:
+ *   "record_keep"               0 / 1 (anything else KMM_ERR_INVALID_ARG): the record calls also append the TEXT of every kept
+ *                               record to a byte queue of the handle
+ *   "record_keep_min_hits"      0 .. 2^32 - 1, default 1
+ *   "record_keep_min_permille"  0 .. 1000, default 0
+ *   "record_keep_invert"        0 / 1, default 0
+ *   "record_keep_pending_bytes", "record_keep_pending_records"  read-only; they synchronise like "quality_masked_bases"
+ * The keep rule of a record with entry (hits, windows), in 64-bit arithmetic:
+ *   match = hits >= min_hits && 1000 * hits >= min_permille * windows;   keep = match != invert
+ * so a record without windows matches iff min_hits is 0.
+ * Refused with KMM_ERR_INVALID_ARG, nothing mapped and nothing appended to either queue, while "record_keep" is 1:
+ *   - a record call with "record_hits" 0 (the rule reads that mode's entries);
+ *   - a record call with "record_keep_min_permille" > 0 and "record_hits" 1 (the rule needs windows, which mode 2 keeps);
+ *   - kmm_map_bam, and KMM_FORMAT_SAM on every entry point that takes it: their records are decoded to ">\n" SEQ on the device
+ *     and the read's name (QNAME) is not carried, so the text would be useless.  Carrying the name is out of scope;
+ *   - whatever the record-hits mode refuses ("min_base_quality" > 0, the flat-read calls).
+ * Appended by kmm_map_records (KMM_FORMAT_FASTQ, KMM_FORMAT_FASTA2, KMM_FORMAT_FASTA), kmm_map_bgzf and kmm_map_gzip: exactly
+ * the records that count in *n_records, each at most once (a record carried between two stream calls is judged by the call that
+ * maps it), in stream order, contiguously, nothing between them.
+ *   - FASTQ and two-line FASTA: the record's bytes as the parser sees them, from the first byte of its header line through the
+ *     '\n' that ends its last line; header, '+' line, qualities and '\r' untouched.  For kmm_map_records on well-formed input
+ *     these are the caller's bytes verbatim.
+ *   - the stream routes: the inflated bytes; a final line without a newline has got one on KMM_FORMAT_LAST_CHUNK.
+ *   - multi-line FASTA: the record as UNWRAPPED two-line text (header line, then the sequence on one line), which is what the
+ *     device-side unwrap hands to the parser — not the caller's line breaks.
+ * The hits queue is unaffected: one entry per record, kept or not, so the keep rule over the taken entries names exactly the
+ * kept records.  A call that fails appends nothing to either queue (pieces before a failing piece included).  Node counts,
+ * per-k-mer counts, kmm_get_stats and the compressed streams' carry stay as in the record-hits mode.
+ * The queue is device memory of the library; it grows before a piece's kernels are launched (pending bytes are kept), and its
+ * tail lives on the device, so a map call gains no host round trip.  Changing the rule or "record_keep" while bytes are pending
+ * is allowed: they stay takeable.  kmm_reset_counts empties the queue.
+ *
+ * kmm_take_kept_records synchronises like kmm_take_record_hits — a sticky or deferred device error is returned and nothing is
+ * taken.  If capacity is at least the pending bytes, ALL of them are copied to out (host or device memory), *n_bytes and
+ * *n_records are set and the queue is emptied; otherwise KMM_ERR_INVALID_ARG, the message names the bytes needed, and nothing is
+ * taken: whole queue or nothing, records are never split.  out == NULL with capacity 0 on an empty queue is KMM_OK with zeros.
+ */
+int kmm_take_kept_records(kmm_index_t *idx, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records);
+
+/*
  * kmm_build_index — builds the Kmer Index arrays on the GPU from flat (k-mer, node) pairs: replaces
  * graph_kmer_index's KmerIndex.from_flat_kmers(flat_kmers, modulo) (reference call site
  * tests/test_mapping.py:36-38; gpu_counter.py:16 builds its table from the same pairs).  Entries are
@@ -727,6 +768,10 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *   "record_hits"      0 (default) / 1 / 2: the record-hits mode — the record calls append per-record index hits (2: and windows)
  *                      to a queue of the handle instead of counting nodes; see kmm_take_record_hits.  Read-only
  *                      "record_hits_pending", "record_hits_pending_mode"
+ *   "record_keep"      0 (default) / 1: in the record-hits mode the record calls also append the text of the records that pass
+ *                      the keep rule ("record_keep_min_hits", "record_keep_min_permille", "record_keep_invert") to a byte queue
+ *                      of the handle; see kmm_take_kept_records.  Read-only "record_keep_pending_bytes",
+ *                      "record_keep_pending_records"
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the

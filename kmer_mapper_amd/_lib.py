@@ -76,6 +76,7 @@ SIGNATURES = {
     "kmm_in_index": (_c.c_int, [_P, _P, _c.c_int64, _P]),
     "kmm_read_hits": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
     "kmm_take_record_hits": (_c.c_int, [_P, _P, _P, _c.c_int64, _P]),
+    "kmm_take_kept_records": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),
     "kmm_set_timing": (_c.c_int, [_P, _c.c_int]),
     "kmm_get_stats": (_c.c_int, [_P, _c.c_int, _P, _P]),
     "kmm_get_timing": (_c.c_int, [_P, _c.c_int, _P, _P]),

@@ -945,6 +945,85 @@ def _save_read_hits(args, hits, wins):
     return (hits, wins) if args.windows else hits
 
 
+class RecordKeepSink(RecordHitsSink):
+    """The same hook for `select-reads`: open(dev) sets record-hits mode 2 and the keep rule, drain(dev) takes
+    both queues after every map call — so both stay chunk-sized — and appends the kept records' bytes to `out`, a binary file
+    object; seen / kept count the records."""
+
+    def __init__(self, out, min_hits=1, min_permille=0, invert=False):
+        super().__init__(windows=True)
+        self.out = out
+        self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
+        self.seen = self.kept = self.kept_bytes = 0
+
+    def open(self, dev):
+        super().open(dev)
+        dev.record_keep(True, **self.rule)
+
+    def drain(self, dev):
+        if dev.get_param("record_hits_pending"):
+            got = dev.take_record_hits()
+            self.hits.append(got[0])
+            self.wins.append(got[1])
+            self.seen += int(got[0].shape[0])
+        text, n = dev.take_kept_records()
+        if text.shape[0]:
+            self.out.write(memoryview(text))
+        self.kept += int(n)
+        self.kept_bytes += int(text.shape[0])
+
+
+def check_select_reads_input(fmt, world_size, reads, output):
+    """`kmer_mapper select-reads` takes FASTA / FASTQ (plain or .gz) in one process and never writes over its input; everything
+    else is refused before the index is read."""
+    if fmt in ("sam", "bam"):
+        raise ValueError("select-reads does not read %s files: their records are decoded on the GPU without the read's name, so "
+                         "the selected text would be useless; SAM and BAM input is out of scope" % fmt.upper())
+    if world_size > 1:
+        raise ValueError("select-reads runs in one process: WORLD_SIZE=%d (torchrun) is out of scope, run it without torchrun"
+                         % world_size)
+    if os.path.abspath(str(output)) == os.path.abspath(str(reads)) or (os.path.exists(str(output)) and os.path.samefile(str(output), str(reads))):
+        raise ValueError("select-reads: -o %s is the input file (-f): the output would overwrite the reads" % output)
+
+
+def select_reads_file(args):
+    """`kmer_mapper select-reads`: the reads of a FASTA / FASTQ file that pass the keep rule, written to -o as uncompressed
+    text, in file order.  The file goes down the route `map` would choose for it in one process (choose_route: raw records,
+    BGZF, gzip — parsed and inflated on the GPU) with the handle's record-hits mode 2 and record-keep mode on; both queues are
+    taken after every map call.  Wrapped FASTA comes out unwrapped (two-line)."""
+    k = args.kmer_size
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    probe = probe_input(args.reads)
+    check_select_reads_input(probe.fmt, world, args.reads, args.output_file)
+    if not 0 <= args.min_hit_permille <= 1000:
+        raise ValueError("--min-hit-permille outside [0, 1000]")
+    if args.min_hits < 0:
+        raise ValueError("--min-hits negative")
+    fmt = probe.fmt
+    lut = None
+    if args.ambiguous_bases == "skip":
+        from .util import ambiguous_skip_lut
+        lut = ambiguous_skip_lut()
+        if k < 2:
+            raise ValueError("--ambiguous-bases skip needs -k 2 or more")
+    kmer_index = _get_kmer_index_from_args(args)
+    if fmt == "fasta" and not probe.two_line:
+        fmt = "fasta_ml"
+    logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes")
+    with open(args.output_file, "wb") as out:
+        sink = RecordKeepSink(out, min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert)
+        map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
+                    device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink)
+    hits, wins = sink.result()
+    logging.info("%d reads seen, %d (%.2f %%) kept: %d bytes written to %s", sink.seen, sink.kept,
+                 100.0 * sink.kept / max(sink.seen, 1), sink.kept_bytes, args.output_file)
+    if args.hits_output is not None:
+        np.save(args.hits_output, hits)
+        np.save(str(args.hits_output) + ".windows", wins)
+        logging.info("Saved per-read hits to %s.npy and windows to %s.windows.npy", args.hits_output, args.hits_output)
+    return sink.seen, sink.kept
+
+
 def build_argument_parser():
     parser = argparse.ArgumentParser(
         description='Kmer Mapper',
@@ -1060,6 +1139,32 @@ def build_argument_parser():
                      help="With --device-parser, SAM and BAM input only: records whose FLAG has 0x10 are looked up in read "
                           "orientation.")
     sub.set_defaults(func=read_hits_file)
+
+    sub = subparsers.add_parser("select-reads", help="Extension: write the reads whose k-mers hit a kmer index back out")
+    sub.add_argument("-i", "--kmer-index", required=False)
+    sub.add_argument("-b", "--index-bundle", required=False)
+    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format")
+    sub.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
+    sub.add_argument("-c", "--chunk-size", required=False, type=int, default=2500000, help="N bytes to process in each chunk")
+    sub.add_argument("-o", "--output-file", required=True,
+                     help="The kept reads as uncompressed text, in file order, every record as it stands in the (inflated) input; "
+                          "wrapped FASTA comes out unwrapped")
+    sub.add_argument("--min-hits", default=1, type=int, metavar="N", help="Keep a read with at least N k-mers in the index. Default 1.")
+    sub.add_argument("--min-hit-permille", default=0, type=int, metavar="P",
+                     help="... and with at least P per mille of its windows in the index (0 .. 1000). Default 0.")
+    sub.add_argument("--invert", action="store_true", help="Keep the reads the rule does not match instead (depletion).")
+    sub.add_argument("-I", "--max-hits-per-kmer", required=False, default=1000, type=int,
+                     help="A k-mer whose index entries all have a frequency above this is no hit. Applied as given.")
+    sub.add_argument("-r", "--map-reverse-complements", default=False, type=bool,
+                     help="A window also hits when the reverse complement of its k-mer is in the index. Default False.")
+    sub.add_argument("--ambiguous-bases", choices=("a", "skip"), default="a",
+                     help="a (default): N is looked up as A and any other letter is an error. skip: no window that contains N "
+                          "or an IUPAC ambiguity letter is looked up.")
+    sub.add_argument("--hits-output", default=None, metavar="OUT",
+                     help="Also write the per-read hits of ALL reads to <OUT>.npy and their windows to <OUT>.windows.npy.")
+    sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
+    sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
+    sub.set_defaults(func=select_reads_file)
     return parser
 
 

@@ -88,6 +88,7 @@ static double ms_since(std::chrono::steady_clock::time_point a)
 #include "kmm_records.hpp"
 #include "kmm_kernels.hpp"
 #include "kmm_read_hits.hpp"
+#include "kmm_record_keep.hpp"
 #include "kmm_radix.hpp"
 #include "kmm_build.hpp"
 
@@ -430,6 +431,16 @@ struct kmm_index : IndexStreams, RxArrays {
     int record_hits = 0, rhq_mode = 0;
     DevBuf rhq_hits, rhq_win;
     int64_t rhq_head = 0, rhq_pending = 0, rhq_cap = 0;
+    // the record-keep mode: with "record_keep" 1 the record calls also append the text of every record whose entry
+    // passes the keep rule to rkq.  rk_ctl (device): {bytes, records} of the queue's true tail, advanced by the kernels; the same
+    // pair as a call found it (put back when the call fails); the kept bytes and records of the piece at work.  rkq_bound: what
+    // the host knows, an upper bound of the pending bytes (the consumed bytes of the pieces since the last take), which the queue
+    // holds room for before a piece's kernels are launched.  rk_tile / rk_super: kept bytes, and behind them kept records, per
+    // tile and super-tile of that piece.
+    int record_keep = 0, rk_invert = 0, rk_min_permille = 0;
+    int64_t rk_min_hits = 1;
+    DevBuf rkq, rk_ctl, rk_tile, rk_super;
+    int64_t rkq_bound = 0, rkq_cap = 0;
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
     int comm_rank = -1, comm_size = 0;
@@ -1029,6 +1040,91 @@ int refuse_quality_in_record_hits(const kmm_index *ix, const char *who)
     return KMM_OK;
 }
 
+// ---- the record-keep queue
+// What a record call is refused for while "record_keep" is 1 (nothing is mapped, nothing appended).  sam_or_bam: the call decodes
+// SAM or BAM records, whose text on the device is ">\n" SEQ: the read's name is not carried.
+int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam)
+{
+    if (!ix || !ix->record_keep)
+        return KMM_OK;
+    if (!ix->record_hits)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep\" is 1 and \"record_hits\" is 0: the keep rule reads the entries of the "
+                    "record-hits mode, set it to 1 or 2 (nothing is mapped)", who);
+    if (ix->rk_min_permille > 0 && ix->record_hits != 2)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep_min_permille\" is %d and \"record_hits\" is 1: the rule needs the windows, "
+                    "which mode 2 keeps (nothing is mapped)", who, ix->rk_min_permille);
+    if (sam_or_bam)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep\" is 1: SAM and BAM records are decoded to \">\\n\" SEQ without the read's "
+                    "name (QNAME is not carried), their text would be useless (nothing is mapped)", who);
+    return KMM_OK;
+}
+
+// Room for n more bytes behind rkq_bound pending ones, made before a piece's kernels are launched (n: its consumed bytes, more
+// than it can keep); the control words on first use.  A new queue gets the pending bytes on the handle's stream.
+int rkq_reserve(kmm_index *ix, int64_t n)
+{
+    if (!ix->rk_ctl.p) {
+        KMMCHK(ensure(ix->rk_ctl, 64));
+        HIPCHK(hipMemsetAsync(ix->rk_ctl.p, 0, 64, ix->stream));
+    }
+    if (ix->rkq_bound + n > ix->rkq_cap) {
+        int64_t cap = 2 * (ix->rkq_bound + n);
+        if (cap < (1 << 20))
+            cap = 1 << 20;
+        DevBuf nb;
+        KMMCHK(ensure(nb, (size_t)cap + 16));
+        if (ix->rkq_bound > 0)
+            HIPCHK(hipMemcpyAsync(nb.p, ix->rkq.p, (size_t)ix->rkq_bound, hipMemcpyDeviceToDevice, ix->stream));
+        HIPCHK(hipStreamSynchronize(ix->stream)); // (the old queue is freed below)
+        ix->rkq = std::move(nb);
+        ix->rkq_cap = cap;
+    }
+    return KMM_OK;
+}
+
+// The kept records of one piece, behind its k_read_hits (the entries are sums of atomics over that whole grid: complete only
+// when it has ended).  hits / windows: the piece's n_records entries (windows null in mode 1); consumed: where its last whole
+// record ends.
+int record_keep_piece(kmm_index *ix, const ReadsView &rv, int64_t n_bytes, int64_t consumed, int64_t n_records, const uint32_t *hits,
+                      const uint32_t *windows)
+{
+    const int64_t n_tiles = (consumed + 1023) / 1024;
+    const int n_super = (int)((n_tiles + 1023) / 1024);
+    KMMCHK(ensure(ix->rk_tile, (size_t)n_super * 1024 * 8));
+    KMMCHK(ensure(ix->rk_super, (size_t)n_super * 8 + 64));
+    KMMCHK(rkq_reserve(ix, consumed));
+    // (kept bytes per tile and super-tile, and behind them the kept records)
+    uint32_t *tile_cnt = (uint32_t *)ix->rk_tile.p, *super_tot = (uint32_t *)ix->rk_super.p;
+    uint32_t *tile_rec = tile_cnt + (size_t)n_super * 1024, *super_rec = super_tot + n_super;
+    unsigned long long *tail = (unsigned long long *)ix->rk_ctl.p;
+    uint32_t *d_total = (uint32_t *)((uint8_t *)ix->rk_ctl.p + 32);
+    const RkRule rule = {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert};
+    const dim3 g4((unsigned)((n_tiles + 3) / 4));
+    HIPCHK(hipMemsetAsync(tile_cnt, 0, (size_t)n_super * 1024 * 8, ix->stream));
+    hipLaunchKernelGGL(k_rk_flags, g4, dim3(256), 0, ix->stream, rv.bases, n_bytes, consumed, n_tiles, rv.tile_nl, rv.super_nl,
+                       rv.period_mask, hits, windows, n_records, rule, tile_cnt, tile_rec);
+    hipLaunchKernelGGL(k_rec_scan1, dim3(n_super), dim3(1024), 0, ix->stream, tile_cnt, super_tot);
+    hipLaunchKernelGGL(k_super_scan, dim3(1), dim3(1024), 0, ix->stream, super_tot, n_super, d_total);
+    hipLaunchKernelGGL(k_rec_scan1, dim3(n_super), dim3(1024), 0, ix->stream, tile_rec, super_rec);
+    hipLaunchKernelGGL(k_super_scan, dim3(1), dim3(1024), 0, ix->stream, super_rec, n_super, d_total + 1);
+    hipLaunchKernelGGL(k_rk_scatter, g4, dim3(256), 0, ix->stream, rv.bases, n_bytes, consumed, n_tiles, rv.tile_nl, rv.super_nl,
+                       rv.period_mask, hits, windows, n_records, rule, (const uint32_t *)tile_cnt, (const uint32_t *)super_tot,
+                       (const unsigned long long *)tail, (uint8_t *)ix->rkq.p);
+    hipLaunchKernelGGL(k_rk_advance, dim3(1), dim3(64), 0, ix->stream, tail, (const uint32_t *)d_total);
+    HIPCHK(hipGetLastError());
+    ix->rkq_bound += consumed;
+    return KMM_OK;
+}
+
+// The queue's true tail {bytes, records}, behind the caller's synchronisation.
+int rkq_tail(kmm_index *ix, unsigned long long (&tail)[2])
+{
+    tail[0] = tail[1] = 0;
+    if (ix->rk_ctl.p)
+        HIPCHK(hipMemcpy(tail, ix->rk_ctl.p, 16, hipMemcpyDeviceToHost));
+    return KMM_OK;
+}
+
 } // namespace
 
 // ================================================================================================
@@ -1346,6 +1442,9 @@ int kmm_reset_counts(kmm_index_t *ix)
         HIPCHK(hipMemsetAsync(ix->rx_ecnt_acc, 0, sizeof(uint32_t) * (size_t)(ix->rx_S ? ix->rx_S : 1), ix->stream));
     ix->ecnt_dirty = false;
     ix->rhq_head = ix->rhq_pending = 0; // (the record-hits queue is emptied with the counts; its arrays stay)
+    if (ix->rk_ctl.p)
+        HIPCHK(hipMemsetAsync(ix->rk_ctl.p, 0, 16, ix->stream)); // (and the queue of kept records)
+    ix->rkq_bound = 0;
     // an error that the kernels of an earlier map call have found, or will find, and no synchronising call has reported yet
     // goes with that call's counts: left in place it would be reported against the counts of the calls AFTER this reset
     HIPCHK(hipMemsetAsync(ix->first_bad, 0xFF, 3 * sizeof(unsigned long long), ix->stream));
@@ -2526,6 +2625,8 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
             else
                 KMMCHK(launch_read_hits<MODE_RECORDS>(ix, rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, q_hits, q_win));
             ix->rhq_pending += out[1];
+            if (ix->record_keep)
+                KMMCHK(record_keep_piece(ix, rv, n_bytes, out[0], out[1], q_hits, q_win));
         } else if (has_break) // (a break byte on a sequence line: a break like the bytes outside the sequence lines)
             KMMCHK(launch_map_reads<MODE_RECORDS_BRK>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
         else
@@ -2779,10 +2880,23 @@ int kmm_map_records(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int fo
                     int64_t *n_records)
 {
     return guarded("kmm_map_records", [&] {
-        const int64_t pending0 = ix ? ix->rhq_pending : 0;
+        const int64_t pending0 = ix ? ix->rhq_pending : 0, bound0 = ix ? ix->rkq_bound : 0;
+        const bool keep = ix && ix->record_keep && ix->record_hits;
+        if (keep) { // the queue's tail as the call finds it, kept on the device: a call that fails puts it back
+            HIPCHK(hipSetDevice(ix->device));
+            KMMCHK(rkq_reserve(ix, 0));
+            HIPCHK(hipMemcpyAsync((uint8_t *)ix->rk_ctl.p + 16, ix->rk_ctl.p, 16, hipMemcpyDeviceToDevice, ix->stream));
+        }
         const int rc = map_records_entry(ix, raw, n_bytes, format, k, max_freq, also_revcomp, lut, consumed, n_records);
         if (rc != KMM_OK && ix)
             ix->rhq_pending = pending0; // (record-hits mode: a call that fails reports no record and appends no entry)
+        if (rc != KMM_OK && keep) {
+            const std::string msg = g_err; // (the failure's message, not the copy's)
+            if (hipMemcpyAsync(ix->rk_ctl.p, (const uint8_t *)ix->rk_ctl.p + 16, 16, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess)
+                (void)hipGetLastError();
+            ix->rkq_bound = bound0;
+            g_err = msg;
+        }
         return rc;
     });
 }
@@ -2811,6 +2925,7 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     HIPCHK(hipSetDevice(ix->device));
     KMMCHK(check_k_lut(k, lut));
     KMMCHK(refuse_quality_in_record_hits(ix, "kmm_map_records"));
+    KMMCHK(refuse_record_keep(ix, "kmm_map_records", format == KMM_FORMAT_SAM));
     KMMCHK(check_quality(ix, "kmm_map_records", k, format == KMM_FORMAT_SAM));
     // A quality floor on FASTQ: always compaction + the radix path, whatever the batch size and "path" say (as kmm_map_packed) —
     // the records front end of the direct path has no flat positions to put a quality mark on — and never the host packer,
@@ -3124,6 +3239,7 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
         return fail(KMM_ERR_INVALID_ARG, "%s: KMM_FORMAT_MID_STREAM needs \"bam_n_ref\" (kmm_set_param): a stream that begins behind "
                                          "the header does not say how many references the file has", c.who);
     KMMCHK(refuse_quality_in_record_hits(ix, c.who));
+    KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM));
     KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
@@ -4163,6 +4279,30 @@ int kmm_take_record_hits(kmm_index_t *ix, uint32_t *hits, uint32_t *windows, int
     return KMM_OK;
 }
 
+int kmm_take_kept_records(kmm_index_t *ix, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records)
+{
+    if (!ix || !n_bytes || !n_records)
+        return fail(KMM_ERR_INVALID_ARG, "NULL argument");
+    *n_bytes = *n_records = 0;
+    if (capacity < 0 || (capacity > 0 && !out))
+        return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_records: capacity negative, or out is NULL");
+    HIPCHK(hipSetDevice(ix->device));
+    KMMCHK(drain(ix)); // (a sticky or deferred device error: returned, nothing taken)
+    unsigned long long tail[2];
+    KMMCHK(rkq_tail(ix, tail));
+    if ((unsigned long long)capacity < tail[0])
+        return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_records: %llu bytes of %llu records are pending and capacity is %lld: the queue is "
+                    "taken whole (nothing is taken)", tail[0], tail[1], (long long)capacity);
+    if (tail[0] > 0) {
+        HIPCHK(hipMemcpy(out, ix->rkq.p, (size_t)tail[0], is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+        HIPCHK(hipMemset(ix->rk_ctl.p, 0, 16));
+    }
+    ix->rkq_bound = 0;
+    *n_bytes = (int64_t)tail[0];
+    *n_records = (int64_t)tail[1];
+    return KMM_OK;
+}
+
 int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads,
                       int k, const uint8_t *lut, uint64_t *out, int64_t n_out)
 {
@@ -4743,6 +4883,26 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         ix->record_hits = (int)value;
         if (value != 0)
             ix->rhq_mode = (int)value;
+    } else if (!strcmp(name, "record_keep")) {
+        // 1: in the record-hits mode the record calls also append the text of every record whose entry passes the keep rule to
+        // the handle's byte queue (kmm_take_kept_records); 0: off, bytes still pending stay takeable
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "record_keep takes 0 or 1");
+        ix->record_keep = (int)value;
+    } else if (!strcmp(name, "record_keep_min_hits")) {
+        if (value < 0 || value > 0xFFFFFFFFll)
+            return fail(KMM_ERR_INVALID_ARG, "record_keep_min_hits outside [0, 2^32 - 1]");
+        ix->rk_min_hits = value;
+    } else if (!strcmp(name, "record_keep_min_permille")) {
+        if (value < 0 || value > 1000)
+            return fail(KMM_ERR_INVALID_ARG, "record_keep_min_permille outside [0, 1000]");
+        ix->rk_min_permille = (int)value;
+    } else if (!strcmp(name, "record_keep_invert")) {
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "record_keep_invert takes 0 or 1");
+        ix->rk_invert = (int)value;
+    } else if (!strcmp(name, "record_keep_pending_bytes") || !strcmp(name, "record_keep_pending_records")) {
+        return fail(KMM_ERR_INVALID_ARG, "%s is read-only", name);
     } else if (!strcmp(name, "use_record_qual")) {
         // 1: with "min_base_quality" > 0, kmm_map_bam and KMM_FORMAT_SAM decode every record's QUAL and apply the floor
         if (value != 0 && value != 1)
@@ -4823,7 +4983,22 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->rhq_pending;
     else if (!strcmp(name, "record_hits_pending_mode")) // the mode the pending entries were appended in (2: they have windows)
         *value = ix->rhq_mode;
-    else if (!strcmp(name, "read_hits_calls")) // kmm_read_hits calls (a pure query: no other counter moves)
+    else if (!strcmp(name, "record_keep"))
+        *value = ix->record_keep;
+    else if (!strcmp(name, "record_keep_min_hits"))
+        *value = ix->rk_min_hits;
+    else if (!strcmp(name, "record_keep_min_permille"))
+        *value = ix->rk_min_permille;
+    else if (!strcmp(name, "record_keep_invert"))
+        *value = ix->rk_invert;
+    else if (!strcmp(name, "record_keep_pending_bytes") || !strcmp(name, "record_keep_pending_records")) {
+        // the true tail of the queue of kept records lives on the device: behind a synchronisation, as "quality_masked_bases"
+        HIPCHK(hipSetDevice(ix->device));
+        KMMCHK(drain(ix));
+        unsigned long long tail[2];
+        KMMCHK(rkq_tail(ix, tail));
+        *value = (int64_t)tail[name[20] == 'b' ? 0 : 1];
+    } else if (!strcmp(name, "read_hits_calls")) // kmm_read_hits calls (a pure query: no other counter moves)
         *value = ix->read_hits_calls;
     else if (!strcmp(name, "bam_calls")) // kmm_map_bam calls that mapped their records (a window inside the header not counted)
         *value = ix->bam_calls;

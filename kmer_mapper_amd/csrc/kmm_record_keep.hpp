@@ -1,0 +1,213 @@
+// kmm_record_keep.hpp — part of libkmm (MI355X / gfx950); included by kmm.hip inside its anonymous namespace.
+// The record-keep mode: behind k_read_hits in records mode, the TEXT of every record whose entry passes the keep
+// rule is appended to a byte queue of the handle.  The record of a byte is arithmetic on its line number (the newline census
+// of the records front end), its keep flag a look at the entry k_read_hits has just written:
+//   k_rk_flags     keep flags -> kept bytes and kept records per 1024-byte tile
+//   (k_rec_scan1 + k_super_scan: prefix sums of the byte counts; the same pair sums the record counts)
+//   k_rk_scatter   the kept bytes of four tiles, compacted in LDS, written as one contiguous span of the queue
+//   k_rk_advance   the queue's tail moves behind the piece's bytes and records
+// The arithmetic is plain C++ (KMM_RH_HD): the CPU tier compiles this header with g++.
+#pragma once
+
+#include "kmm_read_hits.hpp"
+
+// The keep rule (include/kmm.h): hits and windows of a record's entry; windows is 0 where the mode keeps none (min_permille
+// is 0 there).
+struct RkRule {
+    uint32_t min_hits, min_permille, invert;
+};
+
+KMM_RH_HD bool rk_keep(uint32_t hits, uint32_t windows, const RkRule &rule)
+{
+    const bool match = hits >= rule.min_hits && 1000ull * (uint64_t)hits >= (uint64_t)rule.min_permille * (uint64_t)windows;
+    return match != (rule.invert != 0u);
+}
+
+// Keep mask of a lane's LANE bytes at piece positions p0 .. p0 + LANE - 1: bit j = byte j lies before `consumed` and belongs to
+// a kept record.  line0: the line of the lane's first byte; nl: bit j = byte j is '\n' (it belongs to the line it ends).
+// keep_of(record) is asked once per record the lane touches, never for a byte at or behind `consumed`.
+template <int LANE, typename KeepOf>
+KMM_RH_HD uint32_t rk_lane_mask(uint32_t line0, uint32_t nl, uint32_t period_shift, int64_t p0, int64_t consumed, KeepOf &&keep_of)
+{
+    if (p0 >= consumed)
+        return 0u;
+    uint32_t mask = 0, line = line0, rec = rh_record_of_line(line0, period_shift);
+    bool keep = keep_of(rec);
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < LANE; ++j) {
+        const bool inside = p0 + j < consumed;
+        const uint32_t r = rh_record_of_line(line, period_shift);
+        if (inside && r != rec) {
+            rec = r;
+            keep = keep_of(rec);
+        }
+        mask |= (keep && inside ? 1u : 0u) << j;
+        line += (nl >> j) & 1u;
+    }
+    return mask;
+}
+
+// Kept records that END inside the lane: kept newlines on the last line of a record.
+template <int LANE>
+KMM_RH_HD uint32_t rk_lane_records(uint32_t line0, uint32_t nl, uint32_t period_mask, uint32_t mask)
+{
+    uint32_t n = 0, ends = nl & mask;
+    while (ends) {
+        const int j = __builtin_ctz(ends);
+        ends &= ends - 1u;
+        n += (rh_line_of_byte(line0, nl, j) & period_mask) == period_mask ? 1u : 0u;
+    }
+    return n;
+}
+
+// Destination of a lane's first kept byte: the queue's tail, the kept bytes of the super-tiles and tiles in front (exclusive
+// prefixes, 32-bit inside a piece) and of the lanes in front inside the tile.
+KMM_RH_HD int64_t rk_dest(int64_t tail, uint32_t super_pre, uint32_t tile_pre, uint32_t rank)
+{
+    return tail + (int64_t)super_pre + (int64_t)tile_pre + (int64_t)rank;
+}
+
+// How a span of `len` bytes that starts `a` (0 .. 15) bytes behind a 16-byte line is written: bytes [a, head_end) and
+// [tail_begin, a + len) one by one, [full_begin, full_end) as whole 16-byte lines.  Nothing outside [a, a + len) is named.
+struct RkSpan {
+    uint32_t head_end, full_begin, full_end, tail_begin;
+};
+
+KMM_RH_HD RkSpan rk_span(uint32_t a, uint32_t len)
+{
+    RkSpan s;
+    const uint32_t hi = a + len;
+    s.full_begin = (a + 15u) & ~15u;
+    s.full_end = hi & ~15u;
+    s.head_end = s.full_begin < hi ? s.full_begin : hi;
+    s.tail_begin = s.full_end > s.head_end ? s.full_end : s.head_end;
+    if (s.full_end < s.full_begin)
+        s.full_end = s.full_begin; // (a span inside one line: no whole line)
+    return s;
+}
+
+#if defined(__HIPCC__)
+
+// What both per-byte kernels know of a lane: its 16 bytes, their newlines, its keep mask and the line of its first byte.
+struct RkLane {
+    uint32_t w[4];
+    uint32_t nl, mask, line0;
+};
+
+// One wavefront per tile; called with all 64 lanes active (a tile behind the piece: no bytes, no mask).  hits / windows: the
+// piece's entries (n_records of them), complete; windows null: mode 1.
+__device__ __forceinline__ void rk_lane_front(const uint8_t *__restrict__ raw, int64_t n, int64_t consumed, int64_t n_tiles, int64_t tile,
+                                              int lane, const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
+                                              uint32_t period_mask, const uint32_t *__restrict__ hits, const uint32_t *__restrict__ windows,
+                                              int64_t n_records, const RkRule &rule, RkLane &L)
+{
+    const int64_t p = tile * 1024 + lane * 16;
+    L.w[0] = L.w[1] = L.w[2] = L.w[3] = 0u;
+    if (tile < n_tiles && p + 16 <= n) {
+        u32x4 x; // (a piece starts at any byte offset: one 16-byte load, aligned or not, as rec_load16)
+        __builtin_memcpy(&x, raw + p, 16);
+        L.w[0] = x[0]; L.w[1] = x[1]; L.w[2] = x[2]; L.w[3] = x[3];
+    } else if (tile < n_tiles) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) // (the piece's last bytes; what lies behind them reads as zero)
+            if (p + j < n)
+                L.w[j >> 2] |= (uint32_t)raw[p + j] << (8 * (j & 3));
+    }
+    uint32_t cr;
+    rec_masks(L.w, L.nl, cr);
+    const uint32_t cnt = (uint32_t)__popc(L.nl);
+    const uint32_t incl = wave_scan_incl(cnt);
+    uint32_t base = 0;
+    if (tile < n_tiles)
+        base = super_nl[tile >> 10] + tile_nl[tile];
+    L.line0 = base + incl - cnt;
+    const int64_t end = tile < n_tiles ? consumed : 0;
+    L.mask = rk_lane_mask<16>(L.line0, L.nl, (uint32_t)__popc(period_mask), p, end, [&](uint32_t r) {
+        if ((int64_t)r >= n_records)
+            return false;
+        return rk_keep(hits[r], windows ? windows[r] : 0u, rule);
+    });
+}
+
+// (The record counts go through an array and the scans, not through an atomic on the tail: one atomic per tile on one address
+// added 3.9 ms to a chunk of 300 000 tiles, eight times what the whole mode costs now: profiles/record_keep/README.md.)
+__global__ void __launch_bounds__(256) k_rk_flags(const uint8_t *__restrict__ raw, int64_t n, int64_t consumed, int64_t n_tiles,
+                                                  const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
+                                                  uint32_t period_mask, const uint32_t *__restrict__ hits,
+                                                  const uint32_t *__restrict__ windows, int64_t n_records, RkRule rule,
+                                                  uint32_t *__restrict__ tile_cnt, uint32_t *__restrict__ tile_rec)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= n_tiles)
+        return;
+    RkLane L;
+    rk_lane_front(raw, n, consumed, n_tiles, tile, lane, tile_nl, super_nl, period_mask, hits, windows, n_records, rule, L);
+    const uint32_t kept = wave_sum((uint32_t)__popc(L.mask));
+    const uint32_t recs = wave_sum(rk_lane_records<16>(L.line0, L.nl, period_mask, L.mask));
+    if (lane == 0) {
+        tile_cnt[tile] = kept;
+        tile_rec[tile] = recs;
+    }
+}
+
+// One workgroup per four tiles (one super-tile holds 256 such groups: a group never straddles two).  The kept bytes of the four
+// tiles go to LDS in order, shifted so that LDS byte i and queue byte (dst - a + i) share their place inside a 16-byte line;
+// the span [a, a + len) then leaves as whole 16-byte lines, its ragged head and tail byte by byte.  The neighbouring groups
+// write the other bytes of the first and the last line: no byte outside the span is written, none of the queue is read.
+__global__ void __launch_bounds__(256) k_rk_scatter(const uint8_t *__restrict__ raw, int64_t n, int64_t consumed, int64_t n_tiles,
+                                                    const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
+                                                    uint32_t period_mask, const uint32_t *__restrict__ hits,
+                                                    const uint32_t *__restrict__ windows, int64_t n_records, RkRule rule,
+                                                    const uint32_t *__restrict__ tile_pre, const uint32_t *__restrict__ super_pre,
+                                                    const unsigned long long *__restrict__ tail, uint8_t *__restrict__ queue)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s_buf[4096 + 16];
+    __shared__ uint32_t s_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tile0 = (int64_t)blockIdx.x * 4, tile = tile0 + wave;
+    RkLane L;
+    rk_lane_front(raw, n, consumed, n_tiles, tile, lane, tile_nl, super_nl, period_mask, hits, windows, n_records, rule, L);
+    const uint32_t kept = (uint32_t)__popc(L.mask);
+    const uint32_t incl = wave_scan_incl(kept);
+    if (lane == 63)
+        s_cnt[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, len = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t c = s_cnt[i];
+        before += i < wave ? c : 0u;
+        len += c;
+    }
+    if (len == 0) // (the same for the whole group)
+        return;
+    const int64_t dst = rk_dest((int64_t)tail[0], super_pre[tile0 >> 10], tile_pre[tile0], 0u);
+    const uint32_t a = (uint32_t)dst & 15u;
+    uint32_t o = a + before + (incl - kept);
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if ((L.mask >> j) & 1u)
+            s_buf[o++] = (uint8_t)(L.w[j >> 2] >> (8 * (j & 3)));
+    __syncthreads();
+    uint8_t *g = queue + (dst - (int64_t)a); // (the 16-byte line the span starts in)
+    const RkSpan sp = rk_span(a, len);
+    const uint32_t t = threadIdx.x;
+    if (a + t < sp.head_end)
+        g[a + t] = s_buf[a + t];
+    for (uint32_t i = sp.full_begin + 16u * t; i + 16u <= sp.full_end; i += 16u * 256u)
+        *reinterpret_cast<u32x4 *>(g + i) = *reinterpret_cast<const u32x4 *>(s_buf + i);
+    if (sp.tail_begin + t < a + len)
+        g[sp.tail_begin + t] = s_buf[sp.tail_begin + t];
+}
+
+// tail: {bytes, records} of the queue; total: {kept bytes, kept records} of the piece.
+__global__ void k_rk_advance(unsigned long long *tail, const uint32_t *__restrict__ total)
+{
+    if (threadIdx.x < 2 && blockIdx.x == 0)
+        tail[threadIdx.x] += (unsigned long long)total[threadIdx.x];
+}
+
+#endif // __HIPCC__

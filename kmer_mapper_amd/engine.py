@@ -407,6 +407,31 @@ class DeviceIndex:
         hits = hits[:taken.value]
         return (hits, win[:taken.value]) if with_windows else hits
 
+    def record_keep(self, on=True, min_hits=1, min_permille=0, invert=False):
+        """The record-keep mode (include/kmm.h), on top of record_hits(): the record calls also append the TEXT of
+        every record whose entry passes the keep rule — hits >= min_hits and 1000 * hits >= min_permille * windows, the
+        outcome flipped by invert — to a byte queue of the handle; take_kept_records() fetches it.  min_permille > 0 needs
+        record_hits(windows=True).  on=False: nothing more is appended; bytes still pending stay takeable."""
+        self.set_param("record_keep_min_hits", int(min_hits))
+        self.set_param("record_keep_min_permille", int(min_permille))
+        self.set_param("record_keep_invert", int(bool(invert)))
+        self.set_param("record_keep", int(bool(on)))
+
+    def take_kept_records(self, out=None):
+        """kmm_take_kept_records: ALL pending bytes — the kept records, whole, in stream order — as (np.uint8 array, n_records);
+        they leave the queue.  out: a uint8 array or torch tensor (host or device) to write into instead, at least as long as
+        the pending bytes; then (n_bytes, n_records) is returned."""
+        n_bytes, n_records = ctypes.c_int64(0), ctypes.c_int64(0)
+        if out is not None:
+            o = _Arg(out, np.uint8, "out")
+            _lib.check(_lib.lib().kmm_take_kept_records(self._h, o.ptr, o.n, ctypes.byref(n_bytes), ctypes.byref(n_records)))
+            return n_bytes.value, n_records.value
+        pending = self.get_param("record_keep_pending_bytes")
+        buf = np.empty(pending, dtype=np.uint8)
+        _lib.check(_lib.lib().kmm_take_kept_records(self._h, buf.ctypes.data_as(_P) if pending else None, pending,
+                                                    ctypes.byref(n_bytes), ctypes.byref(n_records)))
+        return buf[:n_bytes.value], n_records.value
+
     # -- measurement -----------------------------------------------------------------------------
     def set_timing(self, on=True):
         _lib.check(_lib.lib().kmm_set_timing(self._h, int(bool(on))))

@@ -142,3 +142,30 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
     finally:
         dev.record_hits(False)
     return (got[0], got[1], consumed) if windows else (got, consumed)
+
+
+def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
+                   min_permille=0, invert=False, device=0):
+    """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
+    text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
+    (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
+    bytes as the parser saw them, in order and contiguous, and one entry per whole record of the chunk, kept or not
+    (DeviceIndex.record_keep / take_kept_records).  The mode is off again afterwards."""
+    from . import _lib
+    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "sam": _lib.FORMAT_SAM}[fmt]
+    if isinstance(raw, (bytes, bytearray, memoryview)):
+        raw = np.frombuffer(bytes(raw), dtype=np.uint8)
+    max_node_id = int(np.max(index._nodes)) if len(index._nodes) else 0
+    dev = _device_index(index, max_node_id, device)
+    if dev.get_param("record_hits_pending") or dev.get_param("record_keep_pending_bytes"):
+        raise ValueError("the cached handle has record hits or kept records pending: take them first")
+    dev.record_hits(True, windows=True)
+    dev.record_keep(True, min_hits=min_hits, min_permille=min_permille, invert=invert)
+    try:
+        dev.map_records(raw, fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp, lut=lut)
+        hits, windows = dev.take_record_hits()
+        text, _ = dev.take_kept_records()
+    finally:
+        dev.record_keep(False)
+        dev.record_hits(False)
+    return text.tobytes(), hits, windows
