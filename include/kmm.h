@@ -209,6 +209,9 @@ int kmm_map_reads_qual(kmm_index_t *idx, const uint8_t *bases, const uint8_t *qu
  * lines up to there exactly like kmm_map_reads, and returns in *consumed how many bytes it used (the
  * caller prepends the remaining raw[consumed:] to the next chunk; at end of file the last line must end
  * with a newline) and in *n_records the number of reads mapped.  '\r' before '\n' is tolerated.
+ * A '\r' inside a sequence line that no '\n' follows is dropped and breaks the read — no window spans it, the windows on
+ * either side of it are mapped — on every route (the direct path, the device-side compaction, the host packer); multi-line
+ * FASTA keeps its own rule (below).
  * The call returns once the chunk is staged and scanned (so *consumed is valid and the host buffer is
  * free); the mapping kernels run asynchronously like every other map call.  Chunks of any size: beyond 2^30
  * bytes the library scans the chunk piece by piece (each piece starts at the end of the previous one's last
@@ -774,6 +777,10 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      "record_keep_pending_records"
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
+ *   "debug_records_grid" test hook of kmm_map_records: workgroups (four wavefronts each) of the two per-tile kernels of the
+ *                      device-side compaction, 0 .. 65536 (anything else KMM_ERR_INVALID_ARG; 0 = the default, chosen from the
+ *                      piece's size and the device's CUs) — with 1 a file of a few KB gives every wavefront the range of
+ *                      consecutive 4 KiB tiles that only a piece beyond 32 MiB has otherwise; not for callers, no effect at 0
  *   "debug_bgzf_call_cap_kb" test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, in KiB (0 = the
  *                      default, 3.5 GiB) — a small file then reaches the cap.  Read-only "flat_uniform_batches": flat reads
  *                      of one length that took the uniform / packed front ends of the radix path

@@ -412,6 +412,7 @@ struct kmm_index : IndexStreams, RxArrays {
     int use_record_qual = 0;     // "use_record_qual": 1: with a floor set, SAM / BAM records are mapped with their QUAL
     int original_strand = 0;     // "original_strand": 1: kept SAM / BAM records with FLAG 0x10 are mapped in read orientation
     int64_t dbg_rec_piece_kb = 0; // test hook ("debug_records_piece_kb"): bytes per piece of kmm_map_records, KiB (0: 2^30 bytes)
+    int dbg_rec_grid = 0;         // test hook ("debug_records_grid"): workgroups of the compaction's per-tile kernels (0: grid_for)
     bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
     bool rx_filter_slots = true;  // "radix_filter_slots": where the geometry allows it the filter is the slot filter (0: the bucket bitmap)
     bool rx_p3_fp = true;         // "radix_p3_fingerprints": pass 3 probes through fingerprint bytes where its variant has that form
@@ -2395,7 +2396,9 @@ static int rec_compact_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, in
     hipStream_t cs = ix->dbg_rec_copy_stream ? ix->copy_stream : ix->stream;
     const int skip = ix->dbg_rec_skip;
     const uint32_t pm = (uint32_t)format - 1u, hc = format == KMM_FORMAT_FASTQ ? (uint32_t)'@' : (uint32_t)'>';
-    const dim3 g4((unsigned)grid_for(ix, (n_tiles + 3) / 4, 8)); // persistent wavefronts: tiles t, t + waves, ...
+    // persistent wavefronts: tiles t, t + waves, ... ("debug_records_grid": a few wavefronts give a small file the long tile
+    // ranges per wavefront that only a piece beyond 32 MiB has otherwise)
+    const dim3 g4((unsigned)(ix->dbg_rec_grid > 0 ? ix->dbg_rec_grid : grid_for(ix, (n_tiles + 3) / 4, 8)));
     HIPCHK(hipMemsetAsync(tile_nl, 0, n_pad * 4, cs));
     HIPCHK(hipMemsetAsync(tile_seq, 0, n_pad * 8, cs));
     HIPCHK(hipMemsetAsync(d_info, 0, 512, cs)); // (info and out_info: neighbours)
@@ -4918,6 +4921,11 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value < 0 || value > (1 << 20))
             return fail(KMM_ERR_INVALID_ARG, "debug_records_piece_kb outside [0, 2^20]");
         ix->dbg_rec_piece_kb = value;
+    } else if (!strcmp(name, "debug_records_grid")) {
+        // test hook of kmm_map_records: workgroups (of four wavefronts) of k_rec_count2 and k_rec_scatter (0 = the default, grid_for)
+        if (value < 0 || value > 65536)
+            return fail(KMM_ERR_INVALID_ARG, "debug_records_grid outside [0, 65536]");
+        ix->dbg_rec_grid = (int)value;
     } else if (!strcmp(name, "debug_skew_p2_counter")) {
         // test hook of the conservation self-check: adds `value` to the device-side "gathered by pass 2" counter, as a
         // doubly processed work item would; the next synchronising call must fail with KMM_ERR_INTERNAL
@@ -4977,6 +4985,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->original_strand;
     else if (!strcmp(name, "debug_records_piece_kb"))
         *value = ix->dbg_rec_piece_kb;
+    else if (!strcmp(name, "debug_records_grid"))
+        *value = ix->dbg_rec_grid;
     else if (!strcmp(name, "record_hits"))
         *value = ix->record_hits;
     else if (!strcmp(name, "record_hits_pending")) // entries waiting for kmm_take_record_hits
