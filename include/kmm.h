@@ -553,10 +553,12 @@ int kmm_take_record_hits(kmm_index_t *idx, uint32_t *hits, uint32_t *windows, in
  * Refused with KMM_ERR_INVALID_ARG, nothing mapped and nothing appended to either queue, while "record_keep" is 1:
  *   - a record call with "record_hits" 0 (the rule reads that mode's entries);
  *   - a record call with "record_keep_min_permille" > 0 and "record_hits" 1 (the rule needs windows, which mode 2 keeps);
- *   - kmm_map_bam, and KMM_FORMAT_SAM on every entry point that takes it: their records are decoded to ">\n" SEQ on the device
- *     and the read's name (QNAME) is not carried, so the text would be useless.  Carrying the name is out of scope;
+ *   - kmm_map_bam with "record_names" 0, and KMM_FORMAT_SAM on every entry point that takes it whatever "record_names" says:
+ *     their records are decoded to ">\n" SEQ on the device and the read's name (QNAME) is not carried, so the text would be
+ *     useless.  kmm_map_bam with "record_names" 1 carries it (below); SAM text is out of scope;
  *   - whatever the record-hits mode refuses ("min_base_quality" > 0, the flat-read calls).
- * Appended by kmm_map_records (KMM_FORMAT_FASTQ, KMM_FORMAT_FASTA2, KMM_FORMAT_FASTA), kmm_map_bgzf and kmm_map_gzip: exactly
+ * Appended by kmm_map_records (KMM_FORMAT_FASTQ, KMM_FORMAT_FASTA2, KMM_FORMAT_FASTA), kmm_map_bgzf, kmm_map_gzip and, with
+ * "record_names" 1, kmm_map_bam (the records' named FASTQ text: THE NAMED FORM below): exactly
  * the records that count in *n_records, each at most once (a record carried between two stream calls is judged by the call that
  * maps it), in stream order, contiguously, nothing between them.
  *   - FASTQ and two-line FASTA: the record's bytes as the parser sees them, from the first byte of its header line through the
@@ -571,6 +573,27 @@ int kmm_take_record_hits(kmm_index_t *idx, uint32_t *hits, uint32_t *windows, in
  * The queue is device memory of the library; it grows before a piece's kernels are launched (pending bytes are kept), and its
  * tail lives on the device, so a map call gains no host round trip.  Changing the rule or "record_keep" while bytes are pending
  * is allowed: they stay takeable.  kmm_reset_counts empties the queue.
+ *
+ * THE NAMED FORM of the BAM decode.  "record_names" 0 / 1 (default 0; anything else KMM_ERR_INVALID_ARG): while it
+ * is 1 and "record_hits" is 1 or 2, kmm_map_bam decodes every record that passes the selection (exclude / include flags, MAPQ
+ * floor, regions) into four-line FASTQ that carries the read's name and qualities, and hands that text to the records front
+ * end as KMM_FORMAT_FASTQ — one (hits, windows) entry per record as in the record-hits mode, and with "record_keep" 1 the text of
+ * the kept records goes to the byte queue:
+ *     '@' NAME [ "/1" | "/2" ] '\n'  SEQ '\n'  "+\n"  QUAL '\n'           (l_read_name - 1) + suffix + 2 * l_seq + 6 bytes
+ *   NAME   the l_read_name - 1 bytes in front of the terminating NUL; every byte outside 0x21 .. 0x7E is written as '?' (a NUL in
+ *          the middle, a tab or a newline of a damaged file cannot break a line).  Read-only "record_name_bytes_replaced": the
+ *          bytes so replaced since the statistics were last reset (kmm_get_stats(reset)) or kmm_reset_counts emptied the queue;
+ *          synchronises like "quality_masked_bases"
+ *   suffix only with "record_names_mate_suffix" 1 (0 / 1, default 0): "/1" iff FLAG has 0x40 and not 0x80, "/2" iff 0x80 and not
+ *          0x40, else nothing — the rule of `samtools fastq` without -n
+ *   SEQ    the letters =ACMGRSVTWYHKDBN as stored; with "original_strand" 1 a record with FLAG 0x10 and at least one base is
+ *          written in read orientation (SEQ complemented and reversed, QUAL reversed) and counted in "records_reversed"
+ *   QUAL   Phred + 33, clipped at '~'; a record whose qualities are absent (first byte 0xFF) gets '"' (0x22) for every base, the
+ *          default of `samtools fastq -v 1`, and is counted in "records_without_qual"
+ * A record without bases gives "@NAME\n\n+\n\n".  With "record_names" 0 every call launches the kernels it launched without the
+ * parameter.  Refused with KMM_ERR_INVALID_ARG, nothing mapped: kmm_map_bam with "record_names" 1 and "record_hits" 0.  The
+ * parameter is not read by any other call: the FASTA / FASTQ routes are unaffected, KMM_FORMAT_SAM with "record_keep" 1 stays
+ * refused, and so does a quality floor in the record-hits mode.
  *
  * kmm_take_kept_records synchronises like kmm_take_record_hits — a sticky or deferred device error is returned and nothing is
  * taken.  If capacity is at least the pending bytes, ALL of them are copied to out (host or device memory), *n_bytes and
@@ -775,6 +798,10 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      the keep rule ("record_keep_min_hits", "record_keep_min_permille", "record_keep_invert") to a byte queue
  *                      of the handle; see kmm_take_kept_records.  Read-only "record_keep_pending_bytes",
  *                      "record_keep_pending_records"
+ *   "record_names"     0 (default) / 1: in the record-hits mode kmm_map_bam decodes the selected records into four-line FASTQ with
+ *                      their names and qualities — the text "record_keep" appends for BAM input; "record_names_mate_suffix"
+ *                      0 (default) / 1: "/1" / "/2" behind the names.  Read-only "record_name_bytes_replaced".  See
+ *                      kmm_take_kept_records, THE NAMED FORM
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_records_grid" test hook of kmm_map_records: workgroups (four wavefronts each) of the two per-tile kernels of the

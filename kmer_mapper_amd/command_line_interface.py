@@ -950,15 +950,26 @@ class RecordKeepSink(RecordHitsSink):
     both queues after every map call — so both stay chunk-sized — and appends the kept records' bytes to `out`, a binary file
     object; seen / kept count the records."""
 
-    def __init__(self, out, min_hits=1, min_permille=0, invert=False):
+    def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False):
         super().__init__(windows=True)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
         self.seen = self.kept = self.kept_bytes = 0
+        # BAM input (DESIGN 4.20): the decode carries QNAME and QUAL — four-line FASTQ — with "/1" / "/2" on request
+        self.names, self.mate_suffix = bool(names), bool(mate_suffix)
+        self.counters = {}
 
     def open(self, dev):
         super().open(dev)
         dev.record_keep(True, **self.rule)
+        if self.names:
+            dev.record_names(True, mate_suffix=self.mate_suffix)
+
+    def finish(self, dev):
+        """The named decode's counters, read once behind the last map call (the drivers' before_fetch hook)."""
+        if self.names:
+            self.counters = {name: dev.get_param(name)
+                             for name in ("records_reversed", "records_without_qual", "record_name_bytes_replaced")}
 
     def drain(self, dev):
         if dev.get_param("record_hits_pending"):
@@ -973,12 +984,25 @@ class RecordKeepSink(RecordHitsSink):
         self.kept_bytes += int(text.shape[0])
 
 
-def check_select_reads_input(fmt, world_size, reads, output):
-    """`kmer_mapper select-reads` takes FASTA / FASTQ (plain or .gz) in one process and never writes over its input; everything
-    else is refused before the index is read."""
-    if fmt in ("sam", "bam"):
+_SELECT_READS_BAM_ONLY = (("--bam-to-fastq", "bam_to_fastq"), ("--exclude-flags", "exclude_flags"), ("--include-flags", "include_flags"),
+                          ("--min-mapq", "min_mapq"), ("--regions", "regions"), ("--regions-file", "regions_file"),
+                          ("--as-stored", "as_stored"), ("--mate-suffix", "mate_suffix"))
+
+
+def check_select_reads_input(fmt, world_size, reads, output, bam_to_fastq=False, bam_options=()):
+    """`kmer_mapper select-reads` takes FASTA / FASTQ (plain or .gz) — and with --bam-to-fastq a BAM file, whose kept records
+    come out as FASTQ — in one process and never writes over its input; everything else is refused before the
+    index is read.  bam_options: the names of the options given that go with BAM input alone."""
+    if fmt == "bam" and not bam_to_fastq:
         raise ValueError("select-reads does not read %s files: their records are decoded on the GPU without the read's name, so "
-                         "the selected text would be useless; SAM and BAM input is out of scope" % fmt.upper())
+                         "the selected text would be useless; SAM and BAM input is out of scope — unless --bam-to-fastq asks for "
+                         "a BAM file's kept records as FASTQ, with their names and qualities" % fmt.upper())
+    if fmt == "sam":
+        raise ValueError("select-reads does not read %s files: their records are decoded on the GPU without the read's name, so "
+                         "the selected text would be useless; SAM and BAM input is out of scope (--bam-to-fastq reads BAM, not "
+                         "SAM text: `samtools view -b` makes one of the other)" % fmt.upper())
+    if bam_options and fmt != "bam":
+        raise ValueError("%s applies to BAM input only (the reads are %s)" % (bam_options[0], fmt))
     if world_size > 1:
         raise ValueError("select-reads runs in one process: WORLD_SIZE=%d (torchrun) is out of scope, run it without torchrun"
                          % world_size)
@@ -994,12 +1018,25 @@ def select_reads_file(args):
     k = args.kmer_size
     world = int(os.environ.get("WORLD_SIZE", "1"))
     probe = probe_input(args.reads)
-    check_select_reads_input(probe.fmt, world, args.reads, args.output_file)
+    bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None)]
+    check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options)
     if not 0 <= args.min_hit_permille <= 1000:
         raise ValueError("--min-hit-permille outside [0, 1000]")
     if args.min_hits < 0:
         raise ValueError("--min-hits negative")
     fmt = probe.fmt
+    bam = fmt == "bam"
+    more = {}
+    if bam:
+        # (the route `read-hits --device-parser` takes for BAM, with the names on; reverse-strand records in read orientation
+        # unless --as-stored: a FASTQ of reverse-complemented reads is not what anyone wants from a BAM file)
+        opt = lambda name, default=None: getattr(args, name, default)
+        select = check_record_select(fmt, include_flags=opt("include_flags", 0), min_mapq=opt("min_mapq", 0), regions=opt("regions"),
+                                     regions_file=opt("regions_file"))
+        exclude_flags = int(opt("exclude_flags", 0) or 0)
+        _check_bam_route(fmt, 1, exclude_flags)
+        more = dict(exclude_flags=exclude_flags, original_strand=check_original_strand(not opt("as_stored", False), fmt),
+                    **({"record_select": select} if select else {}))
     lut = None
     if args.ambiguous_bases == "skip":
         from .util import ambiguous_skip_lut
@@ -1009,14 +1046,17 @@ def select_reads_file(args):
     kmer_index = _get_kmer_index_from_args(args)
     if fmt == "fasta" and not probe.two_line:
         fmt = "fasta_ml"
-    logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes")
+    logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes%s",
+                 "; BAM records decoded to FASTQ with their names (--bam-to-fastq)" if bam else "")
     with open(args.output_file, "wb") as out:
-        sink = RecordKeepSink(out, min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert)
+        sink = RecordKeepSink(out, min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert, names=bam,
+                              mate_suffix=bam and bool(getattr(args, "mate_suffix", False)))
         map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
-                    device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink)
+                    device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more)
     hits, wins = sink.result()
-    logging.info("%d reads seen, %d (%.2f %%) kept: %d bytes written to %s", sink.seen, sink.kept,
-                 100.0 * sink.kept / max(sink.seen, 1), sink.kept_bytes, args.output_file)
+    logging.info("%d reads seen, %d (%.2f %%) kept: %d bytes written to %s%s", sink.seen, sink.kept,
+                 100.0 * sink.kept / max(sink.seen, 1), sink.kept_bytes, args.output_file,
+                 "".join("; %s %d" % (name, v) for name, v in sink.counters.items() if v))
     if args.hits_output is not None:
         np.save(args.hits_output, hits)
         np.save(str(args.hits_output) + ".windows", wins)
@@ -1143,7 +1183,7 @@ def build_argument_parser():
     sub = subparsers.add_parser("select-reads", help="Extension: write the reads whose k-mers hit a kmer index back out")
     sub.add_argument("-i", "--kmer-index", required=False)
     sub.add_argument("-b", "--index-bundle", required=False)
-    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format")
+    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format (BAM with --bam-to-fastq)")
     sub.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
     sub.add_argument("-c", "--chunk-size", required=False, type=int, default=2500000, help="N bytes to process in each chunk")
     sub.add_argument("-o", "--output-file", required=True,
@@ -1162,6 +1202,26 @@ def build_argument_parser():
                           "or an IUPAC ambiguity letter is looked up.")
     sub.add_argument("--hits-output", default=None, metavar="OUT",
                      help="Also write the per-read hits of ALL reads to <OUT>.npy and their windows to <OUT>.windows.npy.")
+    # (the BAM options are absent from the namespace unless given: a call without them parses as it did before they existed)
+    sub.add_argument("--bam-to-fastq", action="store_true", default=argparse.SUPPRESS,
+                     help="Read a BAM file: its records are inflated, selected and decoded on the GPU, and the kept ones are "
+                          "written as four-line FASTQ with their names and qualities (absent qualities as '\"'; name bytes outside "
+                          "'!' .. '~' as '?'). Records with FLAG 0x10 come out in read orientation.")
+    sub.add_argument("--exclude-flags", default=argparse.SUPPRESS, type=lambda v: int(v, 0),
+                     help="BAM input only: leave out records whose FLAG has any of these bits (0x900: secondary and supplementary).")
+    sub.add_argument("--include-flags", default=argparse.SUPPRESS, type=lambda v: int(v, 0),
+                     help="BAM input only: only records whose FLAG has all of these bits (4 = unmapped reads).")
+    sub.add_argument("--min-mapq", default=argparse.SUPPRESS, type=int, metavar="Q", help="BAM input only: only records with MAPQ >= Q.")
+    sub.add_argument("--regions", action="append", default=argparse.SUPPRESS, metavar="REGIONS",
+                     help="BAM input only: only records that overlap one of these regions (syntax as `map --regions`).")
+    sub.add_argument("--regions-file", default=argparse.SUPPRESS, metavar="BED",
+                     help="BAM input only: regions from a BED file; adds to --regions.")
+    sub.add_argument("--as-stored", action="store_true", default=argparse.SUPPRESS,
+                     help="BAM input only: write records with FLAG 0x10 as the file stores them (reverse-complemented), not in read "
+                          "orientation.")
+    sub.add_argument("--mate-suffix", action="store_true", default=argparse.SUPPRESS,
+                     help="BAM input only: /1 behind the name of a first mate (FLAG 0x40 and not 0x80), /2 behind a second "
+                          "(0x80 and not 0x40), as `samtools fastq` without -n.")
     sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
     sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
     sub.set_defaults(func=select_reads_file)

@@ -439,6 +439,10 @@ struct kmm_index : IndexStreams, RxArrays {
     // holds room for before a piece's kernels are launched.  rk_tile / rk_super: kept bytes, and behind them kept records, per
     // tile and super-tile of that piece.
     int record_keep = 0, rk_invert = 0, rk_min_permille = 0;
+    // the named form of the BAM decode: with "record_names" 1 kmm_map_bam, in the record-hits mode, decodes the selected
+    // records into four-line FASTQ that carries QNAME and QUAL (k_bam_*_named) — the text "record_keep" appends;
+    // "record_names_mate_suffix" 1: "/1" / "/2" behind the name
+    int record_names = 0, record_names_mate_suffix = 0;
     int64_t rk_min_hits = 1;
     DevBuf rkq, rk_ctl, rk_tile, rk_super;
     int64_t rkq_bound = 0, rkq_cap = 0;
@@ -1043,8 +1047,9 @@ int refuse_quality_in_record_hits(const kmm_index *ix, const char *who)
 
 // ---- the record-keep queue
 // What a record call is refused for while "record_keep" is 1 (nothing is mapped, nothing appended).  sam_or_bam: the call decodes
-// SAM or BAM records, whose text on the device is ">\n" SEQ: the read's name is not carried.
-int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam)
+// SAM or BAM records, whose text on the device is ">\n" SEQ: the read's name is not carried — unless the call is kmm_map_bam with
+// "record_names" 1 (named), whose decode carries it.
+int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam, bool named = false)
 {
     if (!ix || !ix->record_keep)
         return KMM_OK;
@@ -1054,7 +1059,7 @@ int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam)
     if (ix->rk_min_permille > 0 && ix->record_hits != 2)
         return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep_min_permille\" is %d and \"record_hits\" is 1: the rule needs the windows, "
                     "which mode 2 keeps (nothing is mapped)", who, ix->rk_min_permille);
-    if (sam_or_bam)
+    if (sam_or_bam && !named)
         return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep\" is 1: SAM and BAM records are decoded to \">\\n\" SEQ without the read's "
                     "name (QNAME is not carried), their text would be useless (nothing is mapped)", who);
     return KMM_OK;
@@ -1446,6 +1451,9 @@ int kmm_reset_counts(kmm_index_t *ix)
     if (ix->rk_ctl.p)
         HIPCHK(hipMemsetAsync(ix->rk_ctl.p, 0, 16, ix->stream)); // (and the queue of kept records)
     ix->rkq_bound = 0;
+    // ("record_name_bytes_replaced" counts bytes of the text that queue held: it restarts with it.  The named decode adds to the
+    // first shard alone; the other statistics stay, as before, until kmm_get_stats(reset).)
+    HIPCHK(hipMemsetAsync(ix->stats + KMM_STAT_REC_NAME_REPLACED, 0, sizeof(unsigned long long), ix->stream));
     // an error that the kernels of an earlier map call have found, or will find, and no synchronising call has reported yet
     // goes with that call's counts: left in place it would be reported against the counts of the calls AFTER this reset
     HIPCHK(hipMemsetAsync(ix->first_bad, 0xFF, 3 * sizeof(unsigned long long), ix->stream));
@@ -3242,7 +3250,12 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
         return fail(KMM_ERR_INVALID_ARG, "%s: KMM_FORMAT_MID_STREAM needs \"bam_n_ref\" (kmm_set_param): a stream that begins behind "
                                          "the header does not say how many references the file has", c.who);
     KMMCHK(refuse_quality_in_record_hits(ix, c.who));
-    KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM));
+    // ("record_names", DESIGN 4.20: kmm_map_bam alone — the text routes never read it, SAM text stays refused)
+    if (!text && ix->record_names && !ix->record_hits)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_names\" is 1 and \"record_hits\" is 0: the named FASTQ form of the decode serves "
+                    "the record-hits mode (and \"record_keep\"), set \"record_hits\" to 1 or 2, or \"record_names\" to 0 (nothing is mapped)",
+                    c.who);
+    KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM, !text && ix->record_names != 0));
     KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
@@ -3552,6 +3565,8 @@ struct BamGpuBackend {
     bool selected = false; // a selection beyond excl is set (sel): the k_bam_*_sel kernels run
     kmm_bam::Sel sel;
     int cur = 0;
+    bool named = false; // the named form ("record_names"): the k_bam_*_named kernels run, whatever the selection
+    bool sfx = false;   // ... with "/1" / "/2" behind the name
 
     kmm_bam::Tile *tiles(int i) { return (kmm_bam::Tile *)ix->bam_tiles[i].p; }
     kmm_bam::Ctl *ctl() { return (kmm_bam::Ctl *)ix->bam_ctl.p; }
@@ -3568,7 +3583,10 @@ struct BamGpuBackend {
         cur = 0;
         HIPCHK(hipMemsetAsync(ctl(), 0, sizeof(kmm_bam::Ctl), ix->stream));
         HIPCHK(hipMemsetAsync(&ctl()->err_pos, 0xFF, 8, ix->stream)); // (no error)
-        if (selected && qual)
+        if (named)
+            hipLaunchKernelGGL(kmm_bam::k_bam_spec_named, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
+                               sfx ? 1u : 0u, tiles(0));
+        else if (selected && qual)
             hipLaunchKernelGGL(kmm_bam::k_bam_spec_q_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel, tiles(0));
         else if (selected)
             hipLaunchKernelGGL(kmm_bam::k_bam_spec_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel, tiles(0));
@@ -3592,7 +3610,10 @@ struct BamGpuBackend {
     }
     int fix(uint64_t n_tiles, uint64_t start0)
     {
-        if (selected && qual)
+        if (named)
+            hipLaunchKernelGGL(kmm_bam::k_bam_fix_named, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
+                               sfx ? 1u : 0u, (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
+        else if (selected && qual)
             hipLaunchKernelGGL(kmm_bam::k_bam_fix_q_sel, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
                                (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
         else if (selected)
@@ -3622,7 +3643,11 @@ struct BamGpuBackend {
     {
         const kmm_bam::Tile *tl = (const kmm_bam::Tile *)tiles(cur);
         const unsigned long long *bs = (const unsigned long long *)ix->bam_base.p;
-        if (selected && qual && orig)
+        if (named)
+            hipLaunchKernelGGL(kmm_bam::k_bam_decode_named, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel,
+                               orig ? 1u : 0u, sfx ? 1u : 0u, tl, bs, out, ix->stats + KMM_STAT_REC_NO_QUAL,
+                               ix->stats + KMM_STAT_REC_REVERSED, ix->stats + KMM_STAT_REC_NAME_REPLACED);
+        else if (selected && qual && orig)
             hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_rev_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs,
                                out, ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
         else if (selected && qual)
@@ -3702,6 +3727,10 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl, qual, ix->original_strand != 0};
     KMMCHK(selection_of(ix, "kmm_map_bam", false, ix->bam_n_ref, be.sel));
     be.selected = !be.sel.flags_only();
+    // (the named form: stream_call_start let the call through with "record_hits" on; a quality floor is refused in that mode, so
+    // `qual` is false here and the text goes to the records front end as FASTQ all the same)
+    be.named = ix->record_names != 0;
+    be.sfx = ix->record_names_mate_suffix != 0;
     kmm_bam::CallOut co;
     KMMCHK(kmm_bam::run_call(be, (uint64_t)n_raw, start0, co));
     ix->bam_false_starts += (int64_t)co.false_starts;
@@ -3727,7 +3756,7 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p));
     int64_t taken = 0, recs = 0;
     // (the quality variant's text is FASTQ: compaction and the radix path, where "min_base_quality" is applied)
-    KMMCHK(kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, qual ? KMM_FORMAT_FASTQ : KMM_FORMAT_FASTA2, c.k,
+    KMMCHK(kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, qual || be.named ? KMM_FORMAT_FASTQ : KMM_FORMAT_FASTA2, c.k,
                            c.max_freq, c.also_revcomp, c.lut, &taken, &recs));
     if (taken != (int64_t)co.out_bytes || recs != (int64_t)co.recs)
         return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %llu decoded bytes, %lld of %llu records mapped", (long long)taken,
@@ -4911,6 +4940,11 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value != 0 && value != 1)
             return fail(KMM_ERR_INVALID_ARG, "use_record_qual takes 0 or 1");
         ix->use_record_qual = (int)value;
+    } else if (!strcmp(name, "record_names") || !strcmp(name, "record_names_mate_suffix")) {
+        // 1: kmm_map_bam in the record-hits mode decodes to named four-line FASTQ; the suffix: "/1" / "/2"
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "%s takes 0 or 1", name);
+        (name[12] ? ix->record_names_mate_suffix : ix->record_names) = (int)value;
     } else if (!strcmp(name, "original_strand")) {
         // 1: kmm_map_bam and KMM_FORMAT_SAM hand every kept record whose FLAG has 0x10 to the mapper in read orientation
         if (value != 0 && value != 1)
@@ -4993,6 +5027,10 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->rhq_pending;
     else if (!strcmp(name, "record_hits_pending_mode")) // the mode the pending entries were appended in (2: they have windows)
         *value = ix->rhq_mode;
+    else if (!strcmp(name, "record_names"))
+        *value = ix->record_names;
+    else if (!strcmp(name, "record_names_mate_suffix"))
+        *value = ix->record_names_mate_suffix;
     else if (!strcmp(name, "record_keep"))
         *value = ix->record_keep;
     else if (!strcmp(name, "record_keep_min_hits"))
@@ -5129,7 +5167,7 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->rx_ok ? ix->rx_geo.F1 : 0;
     else if (!strcmp(name, "radix_p2_kmers") || !strcmp(name, "radix_p3_kmers") || !strcmp(name, "radix_p2_dropped") ||
              !strcmp(name, "radix_p2_multi_round_items") || !strcmp(name, "quality_masked_bases") ||
-             !strcmp(name, "records_without_qual") || !strcmp(name, "records_reversed") ||
+             !strcmp(name, "records_without_qual") || !strcmp(name, "records_reversed") || !strcmp(name, "record_name_bytes_replaced") ||
              !strcmp(name, "debug_p3_key_reads") || !strncmp(name, "stats_slot_", 11)) {
         // conservation check of the radix path: k-mers gathered by pass 2 / probed by pass 3 since the last
         // kmm_get_stats(reset): both must equal the lookups pass 1 emitted
@@ -5141,10 +5179,12 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         // ("quality_masked_bases": FASTQ bases whose quality byte was below "min_base_quality", since the same reset)
         // ("records_without_qual": SAM / BAM records with bases and no qualities that were mapped with a floor, since the same reset)
         // ("records_reversed": SAM / BAM records with FLAG 0x10 and bases written in read orientation ("original_strand"), since the same reset)
+        // ("record_name_bytes_replaced": QNAME bytes outside '!' .. '~' written as '?' by the named BAM decode ("record_names"), since the same reset)
         // ("debug_p3_key_reads": 8-byte key reads of pass 3's probes; counted by -DRX_P3_FP_STATS builds only, else 0)
         const int slot = name[0] == 's' ? atoi(name + 11) : name[0] == 'q' ? KMM_STAT_QUAL_MASKED
                                                           : !strcmp(name, "records_without_qual") ? KMM_STAT_REC_NO_QUAL
                                                           : !strcmp(name, "records_reversed") ? KMM_STAT_REC_REVERSED
+                                                          : !strcmp(name, "record_name_bytes_replaced") ? KMM_STAT_REC_NAME_REPLACED
                                                           : name[0] == 'd' ? KMM_STAT_RX_P3_KEYS
                                                           : !strcmp(name, "radix_p2_dropped") ? KMM_STAT_RX_DROPPED
                                                           : !strcmp(name, "radix_p2_multi_round_items") ? KMM_STAT_RX_MULTI

@@ -21,6 +21,10 @@
 // The quality variant (<true> / k_bam_*_q; "use_record_qual" with a floor) writes every kept record as four-line
 // FASTQ instead ("@\n" SEQ "\n+\n" QUAL "\n", the raw Phred bytes as Phred+33 clipped at '~'): 2 l_seq + 6 bytes per record, which
 // the library maps as KMM_FORMAT_FASTQ, where "min_base_quality" is applied.
+// The named form ("record_names"; k_bam_*_named) writes every selected record as four-line FASTQ WITH its identity:
+// '@' NAME [ "/1" | "/2" ] '\n' SEQ '\n' "+\n" QUAL '\n' — the name's bytes outside '!' .. '~' as '?', absent qualities as '"' — the
+// text the record-keep mode appends for BAM input.  Its length comes from the record's head too, so it is a third output form of
+// spec, link and totals (FORM_NAMED), not a mechanism of its own.
 // "original_strand"  has decode write the kept records whose FLAG has 0x10 in read orientation: SEQ reversed and
 // complemented, QUAL reversed.  The output lengths are the same: spec, link and totals do not know of the switch.
 // Record selection (kmm_select.hpp has the rule): with an include mask, a MAPQ floor or a region list set, spec, fix,
@@ -180,24 +184,52 @@ struct Walk {
     bool bad;
 };
 
+// The output forms of a kept record: two-line FASTA, four-line FASTQ without a name (the quality variant), and the NAMED form
+// ("record_names"): four-line FASTQ that carries QNAME and, when asked for, the mate suffix.  The templates below take
+// the form as an int (their callers from before the named form pass false / true: 0 / 1).
+constexpr int FORM_FASTA = 0, FORM_FASTQ = 1, FORM_NAMED = 2;
+
 // Output bytes of one kept record: two-line FASTA, or (Q) four-line FASTQ.
-template <bool Q>
+template <int Q>
 KMM_BAM_HD uint32_t out_len(uint32_t l_seq)
 {
     return Q ? 2u * l_seq + 6u : l_seq + 3u;
 }
 
+// The mate suffix of the named form: 1 ("/1") iff FLAG has 0x40 and not 0x80, 2 ("/2") iff 0x80 and not 0x40, else 0 (none) — the
+// rule of `samtools fastq` without -n.  on: "record_names_mate_suffix".
+KMM_BAM_HD uint32_t mate_of(uint32_t flag, bool on)
+{
+    const uint32_t m = flag & 0xC0u;
+    return !on ? 0u : m == 0x40u ? 1u : m == 0x80u ? 2u : 0u;
+}
+
+// Output bytes of one kept record in the named form: '@' NAME [/1 | /2] '\n' SEQ '\n' "+\n" QUAL '\n' — from the record's head
+// alone, as the other forms' (l_name >= 1: record_at).
+KMM_BAM_HD uint32_t out_len_named(const RecHead &h, bool sfx)
+{
+    return (h.l_name - 1u) + (mate_of(h.flag, sfx) ? 2u : 0u) + 2u * h.l_seq + 6u;
+}
+
+template <int Q>
+KMM_BAM_HD uint32_t rec_out_len(const RecHead &h, bool sfx)
+{
+    return Q == FORM_NAMED ? out_len_named(h, sfx) : out_len<Q>(h.l_seq);
+}
+
 // Walk::bytes and Tile::bytes are uint32.  The records that start in one tile, all but the last, end before the next one starts,
 // i.e. inside the tile: their 4 + block_size sum to less than TILE, there are at most TILE / 36 of them (block_size >= 32), and
 // l_seq + (l_seq + 1) / 2 <= block_size bounds every l_seq by 2/3 block_size.  The last one has block_size < 2^31.  So a tile's
-// quality output is below 2 * (2/3) * (TILE + 2^31) + 6 * (TILE / 36 + 1) (the FASTA output is smaller still):
-constexpr uint64_t MAX_TILE_OUT = 4ull * ((uint64_t)TILE + 0x80000000ull) / 3 + 6ull * (TILE / 36 + 1);
+// quality output is below 2 * (2/3) * (TILE + 2^31) + 6 * (TILE / 36 + 1) (the FASTA output is smaller still).  The named form
+// adds a record's name and mate suffix: l_name - 1 <= 254 and 2 more bytes, at most 256 per record:
+constexpr uint64_t MAX_TILE_OUT = 4ull * ((uint64_t)TILE + 0x80000000ull) / 3 + (6ull + 256ull) * (TILE / 36 + 1);
 static_assert(MAX_TILE_OUT < 0x100000000ull, "a tile's output bytes fit uint32");
 
 // The chain from p (a record start) to the first start at or past te; it stops early at a record that does not end inside
 // d[0, n) (exit = its start) or at a malformed one (bad, exit = its start).
-template <bool Q = false, bool S = false>
-KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int32_t n_ref, uint32_t excl, Walk &w, const Sel &sel = Sel())
+template <int Q = 0, bool S = false>
+KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int32_t n_ref, uint32_t excl, Walk &w, const Sel &sel = Sel(),
+                     bool sfx = false)
 {
     w.recs = w.excluded = w.bytes = 0;
     w.bad = false;
@@ -214,7 +246,7 @@ KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int3
             ++w.excluded;
         else {
             ++w.recs;
-            w.bytes += out_len<Q>(h.l_seq);
+            w.bytes += rec_out_len<Q>(h, sfx);
         }
         p += 4ull + h.bs;
     }
@@ -224,9 +256,9 @@ KMM_BAM_HD void walk(const uint8_t *d, uint64_t n, uint64_t p, uint64_t te, int3
 KMM_BAM_HD uint64_t tile_end(uint64_t t, uint64_t n) { return (t + 1) * TILE < n ? (t + 1) * TILE : n; }
 
 // The claim of tile t once its start is known (entry = a record start) or guessed.
-template <bool Q = false, bool S = false>
+template <int Q = 0, bool S = false>
 KMM_BAM_HD void claim_from(const uint8_t *d, uint64_t n, uint64_t t, uint64_t entry, int32_t n_ref, uint32_t excl, uint32_t spec,
-                           Tile &o, const Sel &sel = Sel())
+                           Tile &o, const Sel &sel = Sel(), bool sfx = false)
 {
     o.spec = spec;
     if (entry == NONE) {
@@ -235,7 +267,7 @@ KMM_BAM_HD void claim_from(const uint8_t *d, uint64_t n, uint64_t t, uint64_t en
         return;
     }
     Walk w;
-    walk<Q, S>(d, n, entry, tile_end(t, n), n_ref, excl, w, sel);
+    walk<Q, S>(d, n, entry, tile_end(t, n), n_ref, excl, w, sel, sfx);
     o.entry = w.bad ? INVALID : entry;
     o.exit = w.bad ? INVALID : w.exit;
     o.recs = w.recs;
@@ -268,9 +300,9 @@ KMM_BAM_HD bool agrees(const uint8_t *d, uint64_t n, uint64_t t, const Tile &c, 
 // ---- the per-tile steps, shared by the kernels and the CPU backend ----
 
 // spec, one tile (scalar form: the kernel tests 64 positions at a time, with the same `plausible`)
-template <bool Q = false, bool S = false>
+template <int Q = 0, bool S = false>
 inline void spec_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, uint64_t start0, int32_t n_ref, uint32_t excl, Tile &o,
-                             const Sel &sel = Sel())
+                             const Sel &sel = Sel(), bool sfx = false)
 {
     uint64_t entry = NONE;
     if (t == 0)
@@ -279,17 +311,17 @@ inline void spec_tile_scalar(const uint8_t *d, uint64_t n, uint64_t t, uint64_t 
         for (uint64_t c = t * TILE, e = tile_end(t, n); c < e && entry == NONE; ++c)
             if (plausible(d, n, c, n_ref))
                 entry = c;
-    claim_from<Q, S>(d, n, t, entry, n_ref, excl, 1u, o, sel);
+    claim_from<Q, S>(d, n, t, entry, n_ref, excl, 1u, o, sel, sfx);
 }
 
 // fix, one tile: its claim is walked again from the exit before it.  verified: that exit is exact (t is the first tile
 // that disagrees), so a malformed record met on the way is an error of the file (returns its position, else NONE).
-template <bool Q = false, bool S = false>
+template <int Q = 0, bool S = false>
 KMM_BAM_HD uint64_t fix_tile(const uint8_t *d, uint64_t n, uint64_t t, uint64_t prev, bool verified, int32_t n_ref, uint32_t excl,
-                             Tile &o, const Sel &sel = Sel())
+                             Tile &o, const Sel &sel = Sel(), bool sfx = false)
 {
     Walk w;
-    walk<Q, S>(d, n, prev, tile_end(t, n), n_ref, excl, w, sel);
+    walk<Q, S>(d, n, prev, tile_end(t, n), n_ref, excl, w, sel, sfx);
     o.spec = 0;
     o.recs = w.recs;
     o.excluded = w.excluded;
@@ -506,6 +538,89 @@ KMM_BAM_HD void decode_record_q_rev(const uint8_t *rec, const RecHead &h, uint8_
     }
 }
 
+// ---- the named form ("record_names"): '@' NAME [/1 | /2] '\n' SEQ '\n' "+\n" QUAL '\n'
+// A name byte as text: the bytes outside 0x21 .. 0x7E ('!' .. '~') become '?' — a NUL in the middle, a tab or a newline in a
+// damaged file cannot break the line arithmetic of the records front end.
+KMM_BAM_HD uint8_t name_letter(uint32_t c) { return (uint8_t)(c - 0x21u <= 0x5Du ? c : (uint32_t)'?'); }
+
+// The quality letter every base of a record without qualities gets: '"' (Phred 1), the default of `samtools fastq -v 1` — not the
+// '~' of the floor variant, which passes a floor but would claim the best quality in a file that is kept.
+constexpr uint8_t QUAL_ABSENT_LETTER = 0x22u;
+
+// The head of a named record, the share of lane `lane` of `lanes`: '@', the name (bytes lane, lane + lanes, ...), the suffix and
+// the three line ends around SEQ and QUAL.  Returns how many of ITS name bytes the lane replaced, and *body = where SEQ starts.
+KMM_BAM_HD uint32_t named_head(const uint8_t *rec, const RecHead &h, uint8_t *out, uint32_t lane, uint32_t lanes, bool sfx, uint8_t **body)
+{
+    const uint8_t *name = rec + 36;
+    const uint32_t nl = h.l_name - 1u, mate = mate_of(h.flag, sfx);
+    uint8_t *seq = out + 1ull + nl + (mate ? 2u : 0u) + 1ull;
+    uint32_t replaced = 0;
+    for (uint32_t j = lane; j < nl; j += lanes) {
+        const uint32_t c = name[j];
+        const uint8_t t = name_letter(c);
+        out[1ull + j] = t;
+        replaced += t != c ? 1u : 0u;
+    }
+    if (lane == 0) {
+        out[0] = '@';
+        if (mate) {
+            out[1ull + nl] = '/';
+            out[2ull + nl] = (uint8_t)('0' + mate);
+        }
+        seq[-1] = '\n';
+        seq[h.l_seq] = '\n';
+        seq[1ull + h.l_seq] = '+';
+        seq[2ull + h.l_seq] = '\n';
+        seq[3ull + 2ull * h.l_seq] = '\n';
+    }
+    *body = seq;
+    return replaced;
+}
+
+// decode, the named form (lane `lane` of `lanes`): out_len_named bytes at out[0]; returns the lane's replaced name bytes.  The
+// letters are decode_record's, the qualities qual_letter's — or QUAL_ABSENT_LETTER throughout when the record stores none.
+KMM_BAM_HD uint32_t decode_record_named(const uint8_t *rec, const RecHead &h, uint8_t *out, uint32_t lane, uint32_t lanes, bool sfx)
+{
+    uint8_t *os;
+    const uint32_t replaced = named_head(rec, h, out, lane, lanes, sfx, &os);
+    const uint8_t *seq = rec + seq_offset(h), *qual = qual_of(rec, h);
+    const uint32_t n_bytes = (h.l_seq + 1u) / 2u;
+    const bool absent = qual_absent(rec, h);
+    uint8_t *oq = os + 3ull + h.l_seq;
+    for (uint32_t j = lane; j < n_bytes; j += lanes) {
+        const uint32_t b = seq[j];
+        os[2ull * j] = base_letter(b >> 4);
+        oq[2ull * j] = absent ? QUAL_ABSENT_LETTER : qual_letter(qual[2ull * j]);
+        if (2 * j + 1 < h.l_seq) {
+            os[2ull * j + 1] = base_letter(b);
+            oq[2ull * j + 1] = absent ? QUAL_ABSENT_LETTER : qual_letter(qual[2ull * j + 1]);
+        }
+    }
+    return replaced;
+}
+
+// decode, the named form, reversed (a record flipped() accepts: l_seq > 0): SEQ complemented and reversed, QUAL reversed, as
+// decode_record_q_rev writes them; the name is not touched by the strand.
+KMM_BAM_HD uint32_t decode_record_named_rev(const uint8_t *rec, const RecHead &h, uint8_t *out, uint32_t lane, uint32_t lanes, bool sfx)
+{
+    uint8_t *os;
+    const uint32_t replaced = named_head(rec, h, out, lane, lanes, sfx, &os);
+    const uint8_t *seq = rec + seq_offset(h), *qual = qual_of(rec, h);
+    const uint32_t n_bytes = (h.l_seq + 1u) / 2u;
+    const bool absent = qual_absent(rec, h);
+    uint8_t *last = os + h.l_seq - 1ull, *qlast = os + 2ull + 2ull * h.l_seq; // the last letter, the last quality
+    for (uint32_t j = lane; j < n_bytes; j += lanes) {
+        const uint32_t b = seq[j];
+        last[-2ll * j] = base_letter(comp_code(b >> 4));
+        qlast[-2ll * j] = absent ? QUAL_ABSENT_LETTER : qual_letter(qual[2ull * j]);
+        if (2 * j + 1 < h.l_seq) {
+            last[-2ll * j - 1] = base_letter(comp_code(b & 15u));
+            qlast[-2ll * j - 1] = absent ? QUAL_ABSENT_LETTER : qual_letter(qual[2ull * j + 1]);
+        }
+    }
+    return replaced;
+}
+
 // ---- the header (host side: the library reads it back once per stream) ----
 
 // d[0, n) = the stream's first inflated bytes.  0: the header ends at *hdr_end and names *n_ref references; 1: it goes on
@@ -590,7 +705,8 @@ int run_call(B &be, uint64_t n, uint64_t start0, CallOut &co)
     return 0;
 }
 
-// The CPU backend (the tests): the same per-tile steps in loops; decode() writes the two-line FASTA of the call.
+// The CPU backend (the tests): the same per-tile steps in loops; decode() writes the two-line FASTA of the call (or its four-line
+// FASTQ: `qual`, `named`).
 struct CpuBackend {
     const uint8_t *d = nullptr;
     uint64_t n = 0;
@@ -602,6 +718,9 @@ struct CpuBackend {
     uint64_t reversed = 0; // the records decode() flipped
     uint32_t lanes = 1;    // lanes decode() gives the per-record functions (the tests: 1 and 64), one after the other
     Sel sel;               // the selection beyond excl (its own excl is not read: eff()); default: flags only
+    bool named = false;    // the named form ("record_names"): decode() writes four-line FASTQ with QNAME; `qual` is not read
+    bool mate_suffix = false; // the named form: "/1" / "/2" behind the name ("record_names_mate_suffix")
+    uint64_t replaced = 0; // the named form: name bytes outside '!' .. '~' that decode() wrote as '?'
     std::vector<Tile> cur, nxt;
     std::vector<uint64_t> base;
     uint64_t false_starts = 0;
@@ -614,7 +733,7 @@ struct CpuBackend {
     }
     bool is_kept(uint64_t p, const RecHead &h) const
     {
-        return sel.flags_only() ? kept<false>(d + p, h, excl, sel) : kept<true>(d + p, h, excl, eff(), lanes);
+        return sel.flags_only() && !named ? kept<false>(d + p, h, excl, sel) : kept<true>(d + p, h, excl, eff(), lanes);
     }
     int spec(uint64_t n_tiles, uint64_t start0)
     {
@@ -624,7 +743,9 @@ struct CpuBackend {
         first_bad = err_pos = NONE;
         const bool s = !sel.flags_only();
         for (uint64_t t = 0; t < n_tiles; ++t)
-            if (qual && s)
+            if (named) // (one form for every selection, as the kernels: kept<true> with no selection set is the exclude mask)
+                spec_tile_scalar<FORM_NAMED, true>(d, n, t, start0, n_ref, excl, cur[t], eff(), mate_suffix);
+            else if (qual && s)
                 spec_tile_scalar<true, true>(d, n, t, start0, n_ref, excl, cur[t], eff());
             else if (s)
                 spec_tile_scalar<false, true>(d, n, t, start0, n_ref, excl, cur[t], eff());
@@ -661,7 +782,8 @@ struct CpuBackend {
             if (cur[t].spec && cur[t].entry != NONE)
                 ++false_starts;
             const bool s = !sel.flags_only();
-            const uint64_t e = qual && s ? fix_tile<true, true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t], eff())
+            const uint64_t e = named     ? fix_tile<FORM_NAMED, true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t], eff(), mate_suffix)
+                               : qual && s ? fix_tile<true, true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t], eff())
                                : s       ? fix_tile<false, true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t], eff())
                                : qual    ? fix_tile<true>(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t])
                                          : fix_tile(d, n, t, prev, t == first_bad, n_ref, excl, nxt[t]);
@@ -698,7 +820,13 @@ struct CpuBackend {
                 const bool rev = flipped(h, orig), keep = is_kept(p, h);
                 if (keep)
                     reversed += rev ? 1u : 0u;
-                if (keep && qual) {
+                if (keep && named) {
+                    for (uint32_t lane = 0; lane < lanes; ++lane)
+                        replaced += rev ? decode_record_named_rev(d + p, h, out + o, lane, lanes, mate_suffix)
+                                        : decode_record_named(d + p, h, out + o, lane, lanes, mate_suffix);
+                    o += out_len_named(h, mate_suffix);
+                    no_qual += qual_absent(d + p, h) ? 1u : 0u;
+                } else if (keep && qual) {
                     for (uint32_t lane = 0; lane < lanes; ++lane)
                         rev ? decode_record_q_rev(d + p, h, out + o, lane, lanes) : decode_record_q(d + p, h, out + o, lane, lanes);
                     o += 2ull * h.l_seq + 6ull;
@@ -717,9 +845,10 @@ struct CpuBackend {
 #if defined(__HIPCC__)
 // spec: one wavefront per tile (grid-stride); lanes test 64 consecutive positions, the lowest plausible one is the start;
 // lane 0 walks the chain from it.
-template <bool Q, bool S = false>
+template <int Q, bool S = false>
 __device__ __forceinline__ void bam_spec_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
-                                               int32_t n_ref, uint32_t excl, Tile *__restrict__ out, const Sel &sel = Sel())
+                                               int32_t n_ref, uint32_t excl, Tile *__restrict__ out, const Sel &sel = Sel(),
+                                               bool sfx = false)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
@@ -737,7 +866,7 @@ __device__ __forceinline__ void bam_spec_tiles(const uint8_t *__restrict__ d, ui
         if (lane == 0) {
             Walk w;
             if (entry != NONE)
-                walk<Q, S>(d, n, entry, tile_end(t, n), n_ref, excl, w, sel);
+                walk<Q, S>(d, n, entry, tile_end(t, n), n_ref, excl, w, sel, sfx);
             const bool none = entry == NONE, bad = !none && w.bad;
             out[t].entry = bad ? INVALID : entry;
             out[t].exit = none ? NONE : bad ? INVALID : w.exit;
@@ -772,6 +901,14 @@ __global__ void __launch_bounds__(256) k_bam_spec_q_sel(const uint8_t *__restric
     bam_spec_tiles<true, true>(d, n, n_tiles, start0, n_ref, sel.excl, out, sel);
 }
 
+// spec, the named form ("record_names"): ONE kernel for every selection — kept<true> with no selection set is the
+// exclude mask — with the mate-suffix switch as a wave-uniform argument (it changes a record's output length by 0 or 2).
+__global__ void __launch_bounds__(256) k_bam_spec_named(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                        int32_t n_ref, Sel sel, uint32_t sfx, Tile *__restrict__ out)
+{
+    bam_spec_tiles<FORM_NAMED, true>(d, n, n_tiles, start0, n_ref, sel.excl, out, sel, sfx != 0u);
+}
+
 // check: one lane per tile; bad[t] = its claim disagrees with the exit before it
 __global__ void __launch_bounds__(256) k_bam_check(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
                                                    int32_t n_ref, const Tile *__restrict__ in, uint8_t *__restrict__ bad,
@@ -788,10 +925,10 @@ __global__ void __launch_bounds__(256) k_bam_check(const uint8_t *__restrict__ d
 }
 
 // fix: one lane per tile; claims that agree are copied, the others walked again from the exit before them
-template <bool Q, bool S = false>
+template <int Q, bool S = false>
 __device__ __forceinline__ void bam_fix_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
                                               int32_t n_ref, uint32_t excl, const Tile *__restrict__ in, const uint8_t *__restrict__ bad,
-                                              Tile *__restrict__ out, Ctl *__restrict__ ctl, const Sel &sel = Sel())
+                                              Tile *__restrict__ out, Ctl *__restrict__ ctl, const Sel &sel = Sel(), bool sfx = false)
 {
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tiles; t += (uint64_t)gridDim.x * blockDim.x) {
         const Tile c = in[t];
@@ -802,7 +939,7 @@ __device__ __forceinline__ void bam_fix_tiles(const uint8_t *__restrict__ d, uin
         if (c.spec && c.entry != NONE)
             atomicAdd(&ctl->false_starts, 1ull);
         Tile o;
-        const uint64_t e = fix_tile<Q, S>(d, n, t, prev_exit(in, t, start0), t == ctl->first_bad, n_ref, excl, o, sel);
+        const uint64_t e = fix_tile<Q, S>(d, n, t, prev_exit(in, t, start0), t == ctl->first_bad, n_ref, excl, o, sel, sfx);
         out[t] = o;
         if (e != NONE)
             atomicMin(&ctl->err_pos, (unsigned long long)e);
@@ -832,6 +969,13 @@ __global__ void __launch_bounds__(256) k_bam_fix_q_sel(const uint8_t *__restrict
                                                        const uint8_t *__restrict__ bad, Tile *__restrict__ out, Ctl *__restrict__ ctl)
 {
     bam_fix_tiles<true, true>(d, n, n_tiles, start0, n_ref, sel.excl, in, bad, out, ctl, sel);
+}
+
+__global__ void __launch_bounds__(256) k_bam_fix_named(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint64_t start0,
+                                                       int32_t n_ref, Sel sel, uint32_t sfx, const Tile *__restrict__ in,
+                                                       const uint8_t *__restrict__ bad, Tile *__restrict__ out, Ctl *__restrict__ ctl)
+{
+    bam_fix_tiles<FORM_NAMED, true>(d, n, n_tiles, start0, n_ref, sel.excl, in, bad, out, ctl, sel, sfx != 0u);
 }
 
 // totals: one workgroup of 1024 threads, each over a run of consecutive tiles: the exclusive scan of the tiles' output bytes
@@ -1099,6 +1243,55 @@ __global__ void __launch_bounds__(256) k_bam_decode_q_rev_sel(const uint8_t *__r
                                                               unsigned long long *__restrict__ reversed)
 {
     bam_decode_sel_tiles<true, true>(d, n, n_tiles, n_ref, sel, in, base, out, no_qual, reversed);
+}
+
+// decode, the named form ("record_names"): the walk of bam_decode_sel_tiles — kept_wave is the predicate of
+// k_bam_spec_named / k_bam_fix_named — with the strand switch (orig) and the mate suffix (sfx) as wave-uniform arguments: one
+// kernel for every combination.  64 lanes over a kept record's name bytes, then over its bases; byte stores into disjoint
+// ranges.  Per tile: the kept records without qualities, the flipped ones and the replaced name bytes (the lanes' shares summed
+// over the wavefront), each added with one atomic per tile that has any.
+__global__ void __launch_bounds__(256) k_bam_decode_named(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref, Sel sel,
+                                                          uint32_t orig, uint32_t sfx, const Tile *__restrict__ in,
+                                                          const unsigned long long *__restrict__ base, uint8_t *__restrict__ out,
+                                                          unsigned long long *__restrict__ no_qual, unsigned long long *__restrict__ reversed,
+                                                          unsigned long long *__restrict__ replaced)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        const Tile c = in[t];
+        if (c.entry == NONE || c.recs == 0)
+            continue;
+        uint64_t p = c.entry, o = base[t];
+        const uint64_t o_end = o + c.bytes; // (the tile's share of `out`: what its walk counted)
+        uint32_t absent = 0, flips = 0, repl = 0;
+        while (p < c.exit) {
+            RecHead h;
+            if (record_at(d, n, p, n_ref, h) != REC_OK) // (cannot happen on a verified chain; bounds all the same)
+                break;
+            if (kept_wave(d + p, h, sel)) {
+                const uint32_t len = out_len_named(h, sfx != 0u);
+                if (o + len > o_end) // (cannot happen: the walk and this pass ask one predicate; bounds all the same)
+                    break;
+                const bool rev = flipped(h, orig != 0u);
+                repl += rev ? decode_record_named_rev(d + p, h, out + o, lane, 64u, sfx != 0u)
+                            : decode_record_named(d + p, h, out + o, lane, 64u, sfx != 0u);
+                o += len;
+                absent += qual_absent(d + p, h) ? 1u : 0u;
+                flips += rev ? 1u : 0u;
+            }
+            p += 4ull + h.bs;
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+            repl += (uint32_t)__shfl_xor((int)repl, s);
+        if (lane == 0 && absent)
+            atomicAdd(no_qual, (unsigned long long)absent);
+        if (lane == 0 && flips)
+            atomicAdd(reversed, (unsigned long long)flips);
+        if (lane == 0 && repl)
+            atomicAdd(replaced, (unsigned long long)repl);
+    }
 }
 
 // resync: one wavefront per tile (grid-stride), the shape of spec; lanes test 64 consecutive positions, the survivors are

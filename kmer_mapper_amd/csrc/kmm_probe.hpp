@@ -159,7 +159,7 @@ constexpr int KMM_STAT_STRIDE = 32; // unsigned long longs = 256 bytes between s
 // shard 0 only), [22] SAM / BAM records with FLAG 0x10 written in read orientation under "original_strand" (k_bam_decode*_rev,
 // k_sam_write*_rev: shard 0 only)
 constexpr int KMM_STAT_RX_P1 = 16, KMM_STAT_RX_DROPPED = 17, KMM_STAT_RX_MULTI = 18, KMM_STAT_QUAL_MASKED = 19, KMM_STAT_RX_P3_KEYS = 20;
-constexpr int KMM_STAT_REC_NO_QUAL = 21, KMM_STAT_REC_REVERSED = 22;
+constexpr int KMM_STAT_REC_NO_QUAL = 21, KMM_STAT_REC_REVERSED = 22, KMM_STAT_REC_NAME_REPLACED = 23;
 constexpr int AGG_LOG_SLOTS = 11;
 constexpr int AGG_SLOTS = 1 << AGG_LOG_SLOTS;
 constexpr uint32_t AGG_EMPTY = 0xFFFFFFFFu; // node ids are < 2^31

@@ -417,6 +417,15 @@ class DeviceIndex:
         self.set_param("record_keep_invert", int(bool(invert)))
         self.set_param("record_keep", int(bool(on)))
 
+    def record_names(self, on=True, mate_suffix=False):
+        """The named form of the BAM decode (include/kmm.h), on top of record_hits(): map_bam decodes every selected
+        record into four-line FASTQ that carries the read's name and qualities ('@' NAME '\\n' SEQ '\\n' "+\\n" QUAL '\\n') instead
+        of ">\\n" SEQ — the text record_keep() appends for BAM input.  Name bytes outside '!' .. '~' are written as '?'
+        (get_param("record_name_bytes_replaced")); records without qualities get '"' per base.  mate_suffix: "/1" behind the
+        name of a record whose FLAG has 0x40 and not 0x80, "/2" for 0x80 and not 0x40.  The text routes never read it."""
+        self.set_param("record_names_mate_suffix", int(bool(mate_suffix)))
+        self.set_param("record_names", int(bool(on)))
+
     def take_kept_records(self, out=None):
         """kmm_take_kept_records: ALL pending bytes — the kept records, whole, in stream order — as (np.uint8 array, n_records);
         they leave the queue.  out: a uint8 array or torch tensor (host or device) to write into instead, at least as long as

@@ -145,14 +145,19 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
 
 
 def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
-                   min_permille=0, invert=False, device=0):
+                   min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False):
     """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
     text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
     (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
     bytes as the parser saw them, in order and contiguous, and one entry per whole record of the chunk, kept or not
-    (DeviceIndex.record_keep / take_kept_records).  The mode is off again afterwards."""
+    (DeviceIndex.record_keep / take_kept_records).  The mode is off again afterwards.
+    fmt "bam": `raw` is a WHOLE BAM file held as bytes; its records — those whose FLAG has none of exclude_flags — are decoded on
+    the GPU into four-line FASTQ that carries QNAME and QUAL (DeviceIndex.record_names), and the text returned is
+    that FASTQ.  original_strand: records with FLAG 0x10 in read orientation; mate_suffix: "/1" / "/2" behind the names."""
     from . import _lib
-    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "sam": _lib.FORMAT_SAM}[fmt]
+    if fmt != "bam" and (exclude_flags or original_strand or mate_suffix):
+        raise ValueError("exclude_flags, original_strand and mate_suffix go with fmt=\"bam\"")
+    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "sam": _lib.FORMAT_SAM, "bam": 0}[fmt]
     if isinstance(raw, (bytes, bytearray, memoryview)):
         raw = np.frombuffer(bytes(raw), dtype=np.uint8)
     max_node_id = int(np.max(index._nodes)) if len(index._nodes) else 0
@@ -161,11 +166,24 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
         raise ValueError("the cached handle has record hits or kept records pending: take them first")
     dev.record_hits(True, windows=True)
     dev.record_keep(True, min_hits=min_hits, min_permille=min_permille, invert=invert)
+    before = None
     try:
-        dev.map_records(raw, fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp, lut=lut)
+        if fmt == "bam":
+            before = (dev.get_param("bam_exclude_flags"), dev.get_param("original_strand"))
+            dev.set_param("bam_exclude_flags", int(exclude_flags))
+            dev.set_param("original_strand", int(bool(original_strand)))
+            dev.record_names(True, mate_suffix=mate_suffix)
+            dev.map_bam(raw, first=True, last=True, k=k, max_index_lookup_frequency=max_index_lookup_frequency,
+                        also_revcomp=also_revcomp, lut=lut)
+        else:
+            dev.map_records(raw, fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp, lut=lut)
         hits, windows = dev.take_record_hits()
         text, _ = dev.take_kept_records()
     finally:
+        if before is not None:                                                      # (the handle is cached: as it was found)
+            dev.record_names(False)
+            dev.set_param("bam_exclude_flags", before[0])
+            dev.set_param("original_strand", before[1])
         dev.record_keep(False)
         dev.record_hits(False)
     return text.tobytes(), hits, windows
