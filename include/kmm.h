@@ -603,6 +603,39 @@ int kmm_take_record_hits(kmm_index_t *idx, uint32_t *hits, uint32_t *windows, in
 int kmm_take_kept_records(kmm_index_t *idx, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records);
 
 /*
+ * KEEPING MATES TOGETHER.  The keep rule above sees one record; paired-end reads need both mates kept or both
+ * dropped.  Per mate, match = hits >= min_hits && 1000 * hits >= min_permille * windows (the rule without its inversion), and
+ *   pair_match = "record_pairs_rule" 0 (any, default): match1 || match2;  1 (both): match1 && match2
+ *   keep       = pair_match != "record_keep_invert", for both mates alike.
+ *
+ * INTERLEAVED INPUT: "record_pairs" 0 (default) / 1 (anything else, and any "record_pairs_rule" but 0 / 1, is
+ * KMM_ERR_INVALID_ARG).  With 1, and only while "record_keep" is 1 (with "record_keep" 0 neither parameter changes anything),
+ * records 2i and 2i + 1 of a stream are mates: kmm_map_records with KMM_FORMAT_FASTQ / KMM_FORMAT_FASTA2, kmm_map_bgzf and
+ * kmm_map_gzip take whole pairs only — *n_records is even and *consumed ends a pair, for every piece of a chunk beyond the piece
+ * limit as well — and a complete record behind the last whole pair stays unconsumed like an incomplete one: on the stream routes
+ * the KMM_FORMAT_LAST_CHUNK call is then KMM_ERR_MALFORMED ("ends with an unpaired record") and appends nothing.  The hits queue
+ * is as without pairs: one entry per record, in order.  Refused with KMM_ERR_INVALID_ARG while "record_keep" and "record_pairs"
+ * are both 1, nothing mapped, nothing appended: KMM_FORMAT_FASTA (multi-line), KMM_FORMAT_SAM, and kmm_map_bam with or without
+ * "record_names".  Changing "record_pairs" while hit entries are pending is refused, like a change of the record-hits mode.
+ *
+ * TWO BUFFERS: kmm_map_record_pairs maps record i of raw1 and record i of raw2 as mates, by position (names are not compared).
+ * format is KMM_FORMAT_FASTQ or KMM_FORMAT_FASTA2, the same for both; each buffer lies in host or in device memory,
+ * independently.  The call needs "record_hits" 1 or 2 and "record_keep" 1 (else KMM_ERR_INVALID_ARG); "record_pairs" is not
+ * read.  Only whole pairs are taken: m = min(whole records of raw1, of raw2) per piece pair ("debug_records_piece_kb" applies to
+ * both buffers), *n_pairs is their sum, *consumed1 / *consumed2 the bytes used of each buffer — the byte behind its last taken
+ * record.  The hits queue gains 2 * *n_pairs entries in pair order (entry 2i mate 1, entry 2i + 1 mate 2: what the interleaved
+ * file would have appended); the kept mate-1 text goes to the queue of kmm_take_kept_records, the kept mate-2 text to a second
+ * queue of the handle.  A failing call restores the hits queue and both text queues; kmm_reset_counts empties both.  After any
+ * successful sequence of calls the two text queues of a handle that is fed through this call alone hold equally many records.
+ *
+ * kmm_take_kept_mates: mate 0 is kmm_take_kept_records, mate 1 the same contract on the second queue, anything else
+ * KMM_ERR_INVALID_ARG.  Read-only "record_keep_pending_bytes_mate2", "record_keep_pending_records_mate2".
+ */
+int kmm_map_record_pairs(kmm_index_t *idx, const uint8_t *raw1, int64_t n1, const uint8_t *raw2, int64_t n2, int format, int k,
+                         int max_freq, int also_revcomp, const uint8_t *lut, int64_t *consumed1, int64_t *consumed2, int64_t *n_pairs);
+int kmm_take_kept_mates(kmm_index_t *idx, int mate, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records);
+
+/*
  * kmm_build_index — builds the Kmer Index arrays on the GPU from flat (k-mer, node) pairs: replaces
  * graph_kmer_index's KmerIndex.from_flat_kmers(flat_kmers, modulo) (reference call site
  * tests/test_mapping.py:36-38; gpu_counter.py:16 builds its table from the same pairs).  Entries are
@@ -798,6 +831,9 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      the keep rule ("record_keep_min_hits", "record_keep_min_permille", "record_keep_invert") to a byte queue
  *                      of the handle; see kmm_take_kept_records.  Read-only "record_keep_pending_bytes",
  *                      "record_keep_pending_records"
+ *   "record_pairs"     0 (default) / 1: while "record_keep" is 1 the records of a stream are interleaved mates, kept or dropped
+ *                      together; "record_pairs_rule" 0 (default: any mate matches) / 1 (both do).  See kmm_map_record_pairs,
+ *                      KEEPING MATES TOGETHER.  Read-only "record_keep_pending_bytes_mate2", "record_keep_pending_records_mate2"
  *   "record_names"     0 (default) / 1: in the record-hits mode kmm_map_bam decodes the selected records into four-line FASTQ with
  *                      their names and qualities — the text "record_keep" appends for BAM input; "record_names_mate_suffix"
  *                      0 (default) / 1: "/1" / "/2" behind the names.  Read-only "record_name_bytes_replaced".  See

@@ -77,6 +77,8 @@ SIGNATURES = {
     "kmm_read_hits": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
     "kmm_take_record_hits": (_c.c_int, [_P, _P, _P, _c.c_int64, _P]),
     "kmm_take_kept_records": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),
+    "kmm_map_record_pairs": (_c.c_int, [_P, _P, _c.c_int64, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
+    "kmm_take_kept_mates": (_c.c_int, [_P, _c.c_int, _P, _c.c_int64, _P, _P]),
     "kmm_set_timing": (_c.c_int, [_P, _c.c_int]),
     "kmm_get_stats": (_c.c_int, [_P, _c.c_int, _P, _P]),
     "kmm_get_timing": (_c.c_int, [_P, _c.c_int, _P, _P]),

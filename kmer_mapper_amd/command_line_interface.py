@@ -950,7 +950,8 @@ class RecordKeepSink(RecordHitsSink):
     both queues after every map call — so both stay chunk-sized — and appends the kept records' bytes to `out`, a binary file
     object; seen / kept count the records."""
 
-    def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False):
+    def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False, pairs=False, pair_rule="any",
+                 out2=None):
         super().__init__(windows=True)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
@@ -958,12 +959,17 @@ class RecordKeepSink(RecordHitsSink):
         # BAM input: the decode carries QNAME and QUAL — four-line FASTQ — with "/1" / "/2" on request
         self.names, self.mate_suffix = bool(names), bool(mate_suffix)
         self.counters = {}
+        # mates kept together: pairs: the stream is interleaved ("record_pairs"); out2: the file of the mate-2
+        # texts of map_record_pairs, whose queue is drained with the other two
+        self.pairs, self.pair_rule, self.out2 = bool(pairs), pair_rule, out2
 
     def open(self, dev):
         super().open(dev)
         dev.record_keep(True, **self.rule)
         if self.names:
             dev.record_names(True, mate_suffix=self.mate_suffix)
+        if self.pairs or self.out2 is not None:
+            dev.record_pairs(self.pairs, rule=self.pair_rule)
 
     def finish(self, dev):
         """The named decode's counters, read once behind the last map call (the drivers' before_fetch hook)."""
@@ -982,6 +988,14 @@ class RecordKeepSink(RecordHitsSink):
             self.out.write(memoryview(text))
         self.kept += int(n)
         self.kept_bytes += int(text.shape[0])
+        if self.out2 is not None:
+            text2, n2 = dev.take_kept_mates(1)
+            if n2 != n:
+                raise RuntimeError("select-reads: %d mate-1 and %d mate-2 records kept by one call" % (n, n2))
+            if text2.shape[0]:
+                self.out2.write(memoryview(text2))
+            self.kept += int(n2)
+            self.kept_bytes += int(text2.shape[0])
 
 
 _SELECT_READS_BAM_ONLY = (("--bam-to-fastq", "bam_to_fastq"), ("--exclude-flags", "exclude_flags"), ("--include-flags", "include_flags"),
@@ -1010,14 +1024,119 @@ def check_select_reads_input(fmt, world_size, reads, output, bam_to_fastq=False,
         raise ValueError("select-reads: -o %s is the input file (-f): the output would overwrite the reads" % output)
 
 
+def _same_file(a, b):
+    a, b = str(a), str(b)
+    return os.path.abspath(a) == os.path.abspath(b) or (os.path.exists(a) and os.path.exists(b) and os.path.samefile(a, b))
+
+
+def check_select_reads_pairs(probe, reads, output, interleaved=False, reads2=None, output2=None, pair_rule=None):
+    """The pair forms of `kmer_mapper select-reads`: --interleaved (-f holds mates in turn) or -f2 with -o2 (two
+    files in, two out), FASTQ or two-line FASTA, plain or .gz.  What does not go together is refused before the index is read.
+    Returns the probe of -f2 (None without it)."""
+    if interleaved and reads2 is not None:
+        raise ValueError("select-reads: --interleaved says that -f holds both mates; it does not go with -f2/--reads2")
+    if reads2 is not None and output2 is None:
+        raise ValueError("select-reads: -f2/--reads2 needs -o2/--output2, the file of the kept mate-2 reads")
+    if output2 is not None and reads2 is None:
+        raise ValueError("select-reads: -o2/--output2 goes with -f2/--reads2")
+    if pair_rule is not None and not interleaved and reads2 is None:
+        raise ValueError("select-reads: --pair-rule goes with --interleaved or -f2/--reads2")
+    if not interleaved and reads2 is None:
+        return None
+
+    def pairable(p, path):
+        if p.fmt in ("sam", "bam") or (p.fmt == "fasta" and not p.two_line):
+            raise ValueError("select-reads: mates are kept together in FASTQ and two-line FASTA files; %s is %s, which is out of scope "
+                             "for --interleaved and -f2 (a BAM file's mates: `samtools fastq` first)"
+                             % (path, "multi-line FASTA" if p.fmt == "fasta" else p.fmt.upper()))
+
+    pairable(probe, reads)
+    probe2 = None
+    if reads2 is not None:
+        probe2 = probe_input(reads2)
+        pairable(probe2, reads2)
+        if probe2.fmt != probe.fmt:
+            raise ValueError("select-reads: -f %s is %s and -f2 %s is %s: the two inputs differ in format" % (reads, probe.fmt, reads2, probe2.fmt))
+    inputs = [("-f", reads)] + ([("-f2", reads2)] if reads2 is not None else [])
+    outputs = [("-o", output)] + ([("-o2", output2)] if output2 is not None else [])
+    for o_opt, o in outputs:
+        for i_opt, i in inputs:
+            if _same_file(o, i):
+                raise ValueError("select-reads: %s %s is the input file (%s): the output would overwrite the reads" % (o_opt, o, i_opt))
+    if output2 is not None and _same_file(output, output2):
+        raise ValueError("select-reads: -o and -o2 name the same file %s" % output)
+    if reads2 is not None and _same_file(reads, reads2):
+        raise ValueError("select-reads: -f and -f2 name the same file %s" % reads)
+    return probe2
+
+
+def _records_left(chunker, period):
+    """The whole records a chunker still holds or can read (the error path at the end of paired input)."""
+    n_lines = 0
+    while True:
+        buf = chunker.next_chunk()
+        if buf is None:
+            break
+        n_lines += int(np.count_nonzero(buf == 10))
+        chunker.consumed(buf.shape[0])
+    return n_lines // period
+
+
+def select_read_pairs_files(index, reads1, reads2, chunk_size, fmt, k, sink, map_reverse_complements=False,
+                            max_index_lookup_frequency=1000, device=0, lut=None):
+    """Two files in step: record i of reads1 and record i of reads2 are mates.  Both files are read by the host
+    readers (RawChunker: plain text as it lies, .gz inflated by gz_io.open_gz), the unconsumed tail of each is carried into its
+    next chunk, every pair of chunks goes through DeviceIndex.map_record_pairs and the sink drains the three queues after every
+    call.  Returns the number of pairs; files of different record counts are an error that names both counts."""
+    period = {"fastq": 4, "fasta": 2}[fmt]
+    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2}[fmt]
+    max_node_id = index.max_node_id() if hasattr(index, "max_node_id") else int(np.max(index._nodes))
+    dev = DeviceIndex.from_index(index, max_node_id, device=device)
+    chunkers = []
+    n_pairs = 0
+    try:
+        sink.open(dev)
+        chunkers = [RawChunker(path, int(chunk_size), pinned=True) for path in (reads1, reads2)]
+        while True:
+            bufs = [c.next_chunk() for c in chunkers]
+            if bufs[0] is None or bufs[1] is None:
+                break
+            used1, used2, m = dev.map_record_pairs(bufs[0], bufs[1], fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency,
+                                                   also_revcomp=map_reverse_complements, lut=lut)
+            sink.drain(dev)
+            if m == 0:
+                if all(c.eof for c in chunkers):
+                    break
+                for c in chunkers:                   # a record longer than the chunk: read more
+                    if not c.eof:
+                        c.chunk_size *= 2
+                continue
+            n_pairs += m
+            chunkers[0].consumed(used1)
+            chunkers[1].consumed(used2)
+        left = [_records_left(c, period) for c in chunkers]
+        if left[0] or left[1]:
+            raise ValueError("select-reads: %s holds %d records and %s holds %d: the files are not mates of each other (%d pairs were "
+                             "written)" % (reads1, n_pairs + left[0], reads2, n_pairs + left[1], n_pairs))
+    finally:
+        for c in chunkers:
+            c.close()
+        dev.close()
+    return n_pairs
+
+
 def select_reads_file(args):
     """`kmer_mapper select-reads`: the reads of a FASTA / FASTQ file that pass the keep rule, written to -o as uncompressed
     text, in file order.  The file goes down the route `map` would choose for it in one process (choose_route: raw records,
     BGZF, gzip — parsed and inflated on the GPU) with the handle's record-hits mode 2 and record-keep mode on; both queues are
-    taken after every map call.  Wrapped FASTA comes out unwrapped (two-line)."""
+    taken after every map call.  Wrapped FASTA comes out unwrapped (two-line).
+    --interleaved / -f2 with -o2: paired-end reads, whose mates are kept or dropped together."""
     k = args.kmer_size
     world = int(os.environ.get("WORLD_SIZE", "1"))
     probe = probe_input(args.reads)
+    interleaved, reads2, output2 = bool(getattr(args, "interleaved", False)), getattr(args, "reads2", None), getattr(args, "output2", None)
+    pair_rule = getattr(args, "pair_rule", None)
+    check_select_reads_pairs(probe, args.reads, args.output_file, interleaved, reads2, output2, pair_rule)
     bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None)]
     check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options)
     if not 0 <= args.min_hit_permille <= 1000:
@@ -1048,11 +1167,33 @@ def select_reads_file(args):
         fmt = "fasta_ml"
     logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes%s",
                  "; BAM records decoded to FASTQ with their names (--bam-to-fastq)" if bam else "")
-    with open(args.output_file, "wb") as out:
-        sink = RecordKeepSink(out, min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert, names=bam,
-                              mate_suffix=bam and bool(getattr(args, "mate_suffix", False)))
-        map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
-                    device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more)
+    rule = dict(min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert)
+    if reads2 is not None:
+        logging.info("select-reads: -f and -f2 are read in step by the host readers (two compressed streams are not inflated on the "
+                     "GPU in step); mates are kept together, pair rule '%s'", pair_rule or "any")
+        with open(args.output_file, "wb") as out, open(output2, "wb") as out2:
+            sink = RecordKeepSink(out, pair_rule=pair_rule or "any", out2=out2, **rule)
+            select_read_pairs_files(kmer_index, args.reads, reads2, args.chunk_size, fmt, k, sink, bool(args.map_reverse_complements),
+                                    args.max_hits_per_kmer, device=args.device, lut=lut)
+    else:
+        with open(args.output_file, "wb") as out:
+            sink = RecordKeepSink(out, names=bam, mate_suffix=bam and bool(getattr(args, "mate_suffix", False)), pairs=interleaved,
+                                  pair_rule=pair_rule or "any", **rule)
+            try:
+                map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
+                            device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more)
+            except ValueError as exc:
+                if not interleaved or not ("unpaired record" in str(exc) or "do not form a complete record" in str(exc)):
+                    raise
+                # (the error path alone: the file's lines counted once more on the host, to name both sides)
+                counter = RawChunker(args.reads, 1 << 22)
+                try:
+                    n_whole = _records_left(counter, {"fastq": 4, "fasta": 2}[fmt])
+                finally:
+                    counter.close()
+                raise ValueError("select-reads --interleaved: %s does not end with a whole pair: it holds %d whole records, %d mate-1 "
+                                 "and %d mate-2%s (%s)" % (args.reads, n_whole, (n_whole + 1) // 2, n_whole // 2, "" if n_whole % 2 else
+                                                           ", and an incomplete record behind them", exc)) from exc
     hits, wins = sink.result()
     logging.info("%d reads seen, %d (%.2f %%) kept: %d bytes written to %s%s", sink.seen, sink.kept,
                  100.0 * sink.kept / max(sink.seen, 1), sink.kept_bytes, args.output_file,
@@ -1222,6 +1363,19 @@ def build_argument_parser():
     sub.add_argument("--mate-suffix", action="store_true", default=argparse.SUPPRESS,
                      help="BAM input only: /1 behind the name of a first mate (FLAG 0x40 and not 0x80), /2 behind a second "
                           "(0x80 and not 0x40), as `samtools fastq` without -n.")
+    # (the pair options too)
+    sub.add_argument("--interleaved", action="store_true", default=argparse.SUPPRESS,
+                     help="Paired-end reads in one file: -f holds mates in turn (records 2i and 2i + 1), FASTQ or two-line FASTA, "
+                          "plain or .gz (inflated on the GPU as for `map`). Both mates of a pair are kept or both dropped.")
+    sub.add_argument("-f2", "--reads2", default=argparse.SUPPRESS, metavar="FILE",
+                     help="Paired-end reads in two files: record i of -f and record i of FILE are mates (by position; names are "
+                          "not compared). Needs -o2. Both files are read, and .gz inflated, by the host readers: two compressed "
+                          "streams are not inflated on the GPU in step.")
+    sub.add_argument("-o2", "--output2", default=argparse.SUPPRESS, metavar="FILE",
+                     help="The kept mate-2 reads (of -f2); -o then holds the kept mate-1 reads, record for record in step.")
+    sub.add_argument("--pair-rule", choices=("any", "both"), default=argparse.SUPPRESS,
+                     help="With --interleaved or -f2: a pair matches when any of its mates passes --min-hits / --min-hit-permille "
+                          "(default), or only when both do; --invert then flips the pair's outcome.")
     sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
     sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
     sub.set_defaults(func=select_reads_file)

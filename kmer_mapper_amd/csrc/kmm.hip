@@ -433,8 +433,8 @@ struct kmm_index : IndexStreams, RxArrays {
     DevBuf rhq_hits, rhq_win;
     int64_t rhq_head = 0, rhq_pending = 0, rhq_cap = 0;
     // the record-keep mode: with "record_keep" 1 the record calls also append the text of every record whose entry
-    // passes the keep rule to rkq.  rk_ctl (device): {bytes, records} of the queue's true tail, advanced by the kernels; the same
-    // pair as a call found it (put back when the call fails); the kept bytes and records of the piece at work.  rkq_bound: what
+    // passes the keep rule to rkq[0].  ctl (device): {bytes, records} of the queue's true tail, advanced by the kernels; the same
+    // pair as a call found it (put back when the call fails); the kept bytes and records of the piece at work.  bound: what
     // the host knows, an upper bound of the pending bytes (the consumed bytes of the pieces since the last take), which the queue
     // holds room for before a piece's kernels are launched.  rk_tile / rk_super: kept bytes, and behind them kept records, per
     // tile and super-tile of that piece.
@@ -444,8 +444,20 @@ struct kmm_index : IndexStreams, RxArrays {
     // "record_names_mate_suffix" 1: "/1" / "/2" behind the name
     int record_names = 0, record_names_mate_suffix = 0;
     int64_t rk_min_hits = 1;
-    DevBuf rkq, rk_ctl, rk_tile, rk_super;
-    int64_t rkq_bound = 0, rkq_cap = 0;
+    // [0]: the queue of kept text; [1]: the mate-2 texts of kmm_map_record_pairs, whose mate-1 texts go to [0]
+    struct RkQueue {
+        DevBuf text, ctl;
+        int64_t bound = 0, cap = 0;
+    } rkq[2];
+    DevBuf rk_tile, rk_super;
+    // keeping mates together: "record_pairs" 1: the records of a stream are interleaved, 2i and 2i + 1 are mates,
+    // and the keep rule is rk_pair_keep over their two entries ("record_pairs_rule": RK_PAIR_ANY / RK_PAIR_BOTH); both are read
+    // only while "record_keep" is 1.  rk_snap: what the last kmm_map_records found (entries pending, the bound of rkq[0]; the
+    // tail is kept on the device), which a stream call whose last chunk ends with an unpaired record puts back.
+    // rk_pair_entries: the per-buffer entries of kmm_map_record_pairs before they are zipped into the queue.
+    int record_pairs = 0, rk_pair_rule = 0;
+    struct { int64_t pending = 0, bound = 0; bool valid = false; } rk_snap;
+    DevBuf rk_pair_entries;
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
     int comm_rank = -1, comm_size = 0;
@@ -995,26 +1007,32 @@ int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offs
 // Room for n more entries behind the pending ones, zeroed on the handle's stream; *hits / *windows: the first new entry.  The
 // arrays grow here, before the probe kernel is launched (a piece's record count is known from its census): a new pair, the
 // pending entries copied to its start.  The caller adds n to rhq_pending once its kernel is launched.
-int rhq_reserve(kmm_index *ix, int64_t n, uint32_t **hits, uint32_t **windows)
+// even (the pair forms of the keep kernels load a pair's two entries as 8 bytes): the first new entry lies at an even index
+// of the arrays — where a take of an odd number of entries has left it at an odd one, the pending entries move.
+int rhq_reserve(kmm_index *ix, int64_t n, uint32_t **hits, uint32_t **windows, bool even = false)
 {
     if (ix->rhq_pending == 0)
         ix->rhq_head = 0;
-    if (ix->rhq_head + ix->rhq_pending + n > ix->rhq_cap) {
-        int64_t cap = 2 * (ix->rhq_pending + n);
+    const bool odd = even && ((ix->rhq_head + ix->rhq_pending) & 1) != 0;
+    if (odd || ix->rhq_head + ix->rhq_pending + n > ix->rhq_cap) {
+        int64_t cap = 2 * (ix->rhq_pending + n) + 2;
         if (cap < (1 << 16))
             cap = 1 << 16;
+        const int64_t head = even ? (ix->rhq_pending & 1) : 0;
         DevBuf nh, nw;
         KMMCHK(ensure(nh, (size_t)cap * 4));
         KMMCHK(ensure(nw, (size_t)cap * 4));
         if (ix->rhq_pending > 0) {
             const size_t bytes = (size_t)ix->rhq_pending * 4;
-            HIPCHK(hipMemcpyAsync(nh.p, (const uint32_t *)ix->rhq_hits.p + ix->rhq_head, bytes, hipMemcpyDeviceToDevice, ix->stream));
-            HIPCHK(hipMemcpyAsync(nw.p, (const uint32_t *)ix->rhq_win.p + ix->rhq_head, bytes, hipMemcpyDeviceToDevice, ix->stream));
+            HIPCHK(hipMemcpyAsync((uint32_t *)nh.p + head, (const uint32_t *)ix->rhq_hits.p + ix->rhq_head, bytes, hipMemcpyDeviceToDevice,
+                                  ix->stream));
+            HIPCHK(hipMemcpyAsync((uint32_t *)nw.p + head, (const uint32_t *)ix->rhq_win.p + ix->rhq_head, bytes, hipMemcpyDeviceToDevice,
+                                  ix->stream));
         }
         HIPCHK(hipStreamSynchronize(ix->stream)); // (the old pair is freed below)
         ix->rhq_hits = std::move(nh);
         ix->rhq_win = std::move(nw);
-        ix->rhq_head = 0;
+        ix->rhq_head = head;
         ix->rhq_cap = cap;
     }
     *hits = (uint32_t *)ix->rhq_hits.p + ix->rhq_head + ix->rhq_pending;
@@ -1049,7 +1067,9 @@ int refuse_quality_in_record_hits(const kmm_index *ix, const char *who)
 // What a record call is refused for while "record_keep" is 1 (nothing is mapped, nothing appended).  sam_or_bam: the call decodes
 // SAM or BAM records, whose text on the device is ">\n" SEQ: the read's name is not carried — unless the call is kmm_map_bam with
 // "record_names" 1 (named), whose decode carries it.
-int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam, bool named = false)
+// multiline: the call unwraps multi-line FASTA.  With "record_pairs" 1 as well only the routes whose pieces can
+// end behind a mate 2 are served: FASTQ and two-line FASTA text.
+int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam, bool named = false, bool multiline = false)
 {
     if (!ix || !ix->record_keep)
         return KMM_OK;
@@ -1062,72 +1082,111 @@ int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam, bo
     if (sam_or_bam && !named)
         return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep\" is 1: SAM and BAM records are decoded to \">\\n\" SEQ without the read's "
                     "name (QNAME is not carried), their text would be useless (nothing is mapped)", who);
+    if (ix->record_pairs && sam_or_bam)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep\" and \"record_pairs\" are 1: the decode of SAM and BAM records hands over "
+                    "whole windows, not pair-aligned ones; mates are kept together on FASTQ and two-line FASTA text only (nothing is "
+                    "mapped)", who);
+    if (ix->record_pairs && multiline)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep\" and \"record_pairs\" are 1: the unwrap of multi-line FASTA cuts at header "
+                    "lines, not behind a mate 2; mates are kept together on FASTQ and two-line FASTA text only (nothing is mapped)", who);
     return KMM_OK;
 }
 
-// Room for n more bytes behind rkq_bound pending ones, made before a piece's kernels are launched (n: its consumed bytes, more
-// than it can keep); the control words on first use.  A new queue gets the pending bytes on the handle's stream.
-int rkq_reserve(kmm_index *ix, int64_t n)
+// Are the records of a FASTQ / two-line FASTA stream taken as interleaved mates?
+bool record_pairs_on(const kmm_index *ix)
 {
-    if (!ix->rk_ctl.p) {
-        KMMCHK(ensure(ix->rk_ctl, 64));
-        HIPCHK(hipMemsetAsync(ix->rk_ctl.p, 0, 64, ix->stream));
+    return ix->record_hits && ix->record_keep && ix->record_pairs;
+}
+
+// Room for n more bytes behind q.bound pending ones, made before a piece's kernels are launched (n: its consumed bytes, more
+// than it can keep); the control words on first use.  A new queue gets the pending bytes on the handle's stream.
+int rkq_reserve(kmm_index *ix, kmm_index::RkQueue &q, int64_t n)
+{
+    if (!q.ctl.p) {
+        KMMCHK(ensure(q.ctl, 64));
+        HIPCHK(hipMemsetAsync(q.ctl.p, 0, 64, ix->stream));
     }
-    if (ix->rkq_bound + n > ix->rkq_cap) {
-        int64_t cap = 2 * (ix->rkq_bound + n);
+    if (q.bound + n > q.cap) {
+        int64_t cap = 2 * (q.bound + n);
         if (cap < (1 << 20))
             cap = 1 << 20;
         DevBuf nb;
         KMMCHK(ensure(nb, (size_t)cap + 16));
-        if (ix->rkq_bound > 0)
-            HIPCHK(hipMemcpyAsync(nb.p, ix->rkq.p, (size_t)ix->rkq_bound, hipMemcpyDeviceToDevice, ix->stream));
+        if (q.bound > 0)
+            HIPCHK(hipMemcpyAsync(nb.p, q.text.p, (size_t)q.bound, hipMemcpyDeviceToDevice, ix->stream));
         HIPCHK(hipStreamSynchronize(ix->stream)); // (the old queue is freed below)
-        ix->rkq = std::move(nb);
-        ix->rkq_cap = cap;
+        q.text = std::move(nb);
+        q.cap = cap;
     }
     return KMM_OK;
+}
+
+// A queue's tail as a call finds it, kept on the device behind the tail itself, and put back by a call that fails.
+int rkq_mark(kmm_index *ix, kmm_index::RkQueue &q)
+{
+    KMMCHK(rkq_reserve(ix, q, 0));
+    HIPCHK(hipMemcpyAsync((uint8_t *)q.ctl.p + 16, q.ctl.p, 16, hipMemcpyDeviceToDevice, ix->stream));
+    return KMM_OK;
+}
+
+void rkq_rollback(kmm_index *ix, kmm_index::RkQueue &q, int64_t bound0)
+{
+    const std::string msg = g_err; // (the failure's message, not the copy's)
+    if (q.ctl.p && hipMemcpyAsync(q.ctl.p, (const uint8_t *)q.ctl.p + 16, 16, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess)
+        (void)hipGetLastError();
+    q.bound = bound0;
+    g_err = msg;
 }
 
 // The kept records of one piece, behind its k_read_hits (the entries are sums of atomics over that whole grid: complete only
 // when it has ended).  hits / windows: the piece's n_records entries (windows null in mode 1); consumed: where its last whole
 // record ends.
-int record_keep_piece(kmm_index *ix, const ReadsView &rv, int64_t n_bytes, int64_t consumed, int64_t n_records, const uint32_t *hits,
-                      const uint32_t *windows)
+// PAIR (kmm_record_keep.hpp): 0: one entry per record; else the entries are those of the piece's pairs, two per pair, the first
+// at an even index of the queue's arrays; 1: record r of this buffer is pair r (kmm_map_record_pairs), 2: records 2p and
+// 2p + 1 are pair p (interleaved).  q: the queue the text goes to.
+template <int PAIR>
+int record_keep_piece(kmm_index *ix, kmm_index::RkQueue &q, const ReadsView &rv, int64_t n_bytes, int64_t consumed, int64_t n_records,
+                      const uint32_t *hits, const uint32_t *windows)
 {
     const int64_t n_tiles = (consumed + 1023) / 1024;
     const int n_super = (int)((n_tiles + 1023) / 1024);
     KMMCHK(ensure(ix->rk_tile, (size_t)n_super * 1024 * 8));
     KMMCHK(ensure(ix->rk_super, (size_t)n_super * 8 + 64));
-    KMMCHK(rkq_reserve(ix, consumed));
+    KMMCHK(rkq_reserve(ix, q, consumed));
     // (kept bytes per tile and super-tile, and behind them the kept records)
     uint32_t *tile_cnt = (uint32_t *)ix->rk_tile.p, *super_tot = (uint32_t *)ix->rk_super.p;
     uint32_t *tile_rec = tile_cnt + (size_t)n_super * 1024, *super_rec = super_tot + n_super;
-    unsigned long long *tail = (unsigned long long *)ix->rk_ctl.p;
-    uint32_t *d_total = (uint32_t *)((uint8_t *)ix->rk_ctl.p + 32);
-    const RkRule rule = {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert};
+    unsigned long long *tail = (unsigned long long *)q.ctl.p;
+    uint32_t *d_total = (uint32_t *)((uint8_t *)q.ctl.p + 32);
+    const RkRule one = {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert};
+    typename RkRuleOf<PAIR>::type rule;
+    if constexpr (PAIR == 0)
+        rule = one;
+    else
+        rule = RkPairRule{one, (uint32_t)ix->rk_pair_rule};
     const dim3 g4((unsigned)((n_tiles + 3) / 4));
     HIPCHK(hipMemsetAsync(tile_cnt, 0, (size_t)n_super * 1024 * 8, ix->stream));
-    hipLaunchKernelGGL(k_rk_flags, g4, dim3(256), 0, ix->stream, rv.bases, n_bytes, consumed, n_tiles, rv.tile_nl, rv.super_nl,
+    hipLaunchKernelGGL(k_rk_flags<PAIR>, g4, dim3(256), 0, ix->stream, rv.bases, n_bytes, consumed, n_tiles, rv.tile_nl, rv.super_nl,
                        rv.period_mask, hits, windows, n_records, rule, tile_cnt, tile_rec);
     hipLaunchKernelGGL(k_rec_scan1, dim3(n_super), dim3(1024), 0, ix->stream, tile_cnt, super_tot);
     hipLaunchKernelGGL(k_super_scan, dim3(1), dim3(1024), 0, ix->stream, super_tot, n_super, d_total);
     hipLaunchKernelGGL(k_rec_scan1, dim3(n_super), dim3(1024), 0, ix->stream, tile_rec, super_rec);
     hipLaunchKernelGGL(k_super_scan, dim3(1), dim3(1024), 0, ix->stream, super_rec, n_super, d_total + 1);
-    hipLaunchKernelGGL(k_rk_scatter, g4, dim3(256), 0, ix->stream, rv.bases, n_bytes, consumed, n_tiles, rv.tile_nl, rv.super_nl,
+    hipLaunchKernelGGL(k_rk_scatter<PAIR>, g4, dim3(256), 0, ix->stream, rv.bases, n_bytes, consumed, n_tiles, rv.tile_nl, rv.super_nl,
                        rv.period_mask, hits, windows, n_records, rule, (const uint32_t *)tile_cnt, (const uint32_t *)super_tot,
-                       (const unsigned long long *)tail, (uint8_t *)ix->rkq.p);
+                       (const unsigned long long *)tail, (uint8_t *)q.text.p);
     hipLaunchKernelGGL(k_rk_advance, dim3(1), dim3(64), 0, ix->stream, tail, (const uint32_t *)d_total);
     HIPCHK(hipGetLastError());
-    ix->rkq_bound += consumed;
+    q.bound += consumed;
     return KMM_OK;
 }
 
 // The queue's true tail {bytes, records}, behind the caller's synchronisation.
-int rkq_tail(kmm_index *ix, unsigned long long (&tail)[2])
+int rkq_tail(const kmm_index::RkQueue &q, unsigned long long (&tail)[2])
 {
     tail[0] = tail[1] = 0;
-    if (ix->rk_ctl.p)
-        HIPCHK(hipMemcpy(tail, ix->rk_ctl.p, 16, hipMemcpyDeviceToHost));
+    if (q.ctl.p)
+        HIPCHK(hipMemcpy(tail, q.ctl.p, 16, hipMemcpyDeviceToHost));
     return KMM_OK;
 }
 
@@ -1448,9 +1507,12 @@ int kmm_reset_counts(kmm_index_t *ix)
         HIPCHK(hipMemsetAsync(ix->rx_ecnt_acc, 0, sizeof(uint32_t) * (size_t)(ix->rx_S ? ix->rx_S : 1), ix->stream));
     ix->ecnt_dirty = false;
     ix->rhq_head = ix->rhq_pending = 0; // (the record-hits queue is emptied with the counts; its arrays stay)
-    if (ix->rk_ctl.p)
-        HIPCHK(hipMemsetAsync(ix->rk_ctl.p, 0, 16, ix->stream)); // (and the queue of kept records)
-    ix->rkq_bound = 0;
+    for (auto &q : ix->rkq) { // (and the queues of kept records)
+        if (q.ctl.p)
+            HIPCHK(hipMemsetAsync(q.ctl.p, 0, 16, ix->stream));
+        q.bound = 0;
+    }
+    ix->rk_snap.valid = false;
     // ("record_name_bytes_replaced" counts bytes of the text that queue held: it restarts with it.  The named decode adds to the
     // first shard alone; the other statistics stay, as before, until kmm_get_stats(reset).)
     HIPCHK(hipMemsetAsync(ix->stats + KMM_STAT_REC_NAME_REPLACED, 0, sizeof(unsigned long long), ix->stream));
@@ -2607,12 +2669,16 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     hipLaunchKernelGGL(k_rec_count, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, ix->stream,
                        rv.bases, n_bytes, n_tiles, tile_cnt);
     hipLaunchKernelGGL(k_rec_scan1, dim3(n_super), dim3(1024), 0, ix->stream, tile_cnt, super_tot);
+    // ("record_pairs", DESIGN 4.21: the piece ends behind a mate 2 — the census counts pairs, records of twice the lines)
+    const bool pairs = record_pairs_on(ix);
     hipLaunchKernelGGL(k_rec_scan2, dim3(1), dim3(1024), 0, ix->stream, rv.bases, n_bytes, n_super,
-                       tile_cnt, super_tot, (uint32_t)format, d_out, 1024);
+                       tile_cnt, super_tot, (uint32_t)format * (pairs ? 2u : 1u), d_out, 1024);
     HIPCHK(hipGetLastError());
     int64_t out[3] = {0, 0, 0};
     HIPCHK(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, ix->stream));
     HIPCHK(hipStreamSynchronize(ix->stream)); // (it waited for the copy: the borrowed host buffer is free from here on)
+    if (pairs)
+        out[1] *= 2;
     *consumed = out[0];
     *n_records = out[1];
     if (out[0] > 0) {
@@ -2628,7 +2694,7 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
             // membership kernel on the same front end; the node counts, the per-k-mer counts and the statistics stay untouched
             uint32_t *q_hits = nullptr, *q_win = nullptr;
             KMMCHK(ensure_direct(ix));
-            KMMCHK(rhq_reserve(ix, out[1], &q_hits, &q_win));
+            KMMCHK(rhq_reserve(ix, out[1], &q_hits, &q_win, pairs));
             if (ix->record_hits != 2)
                 q_win = nullptr;
             if (has_break)
@@ -2636,8 +2702,10 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
             else
                 KMMCHK(launch_read_hits<MODE_RECORDS>(ix, rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, q_hits, q_win));
             ix->rhq_pending += out[1];
-            if (ix->record_keep)
-                KMMCHK(record_keep_piece(ix, rv, n_bytes, out[0], out[1], q_hits, q_win));
+            if (pairs)
+                KMMCHK(record_keep_piece<2>(ix, ix->rkq[0], rv, n_bytes, out[0], out[1], q_hits, q_win));
+            else if (ix->record_keep)
+                KMMCHK(record_keep_piece<0>(ix, ix->rkq[0], rv, n_bytes, out[0], out[1], q_hits, q_win));
         } else if (has_break) // (a break byte on a sequence line: a break like the bytes outside the sequence lines)
             KMMCHK(launch_map_reads<MODE_RECORDS_BRK>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
         else
@@ -2891,23 +2959,22 @@ int kmm_map_records(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int fo
                     int64_t *n_records)
 {
     return guarded("kmm_map_records", [&] {
-        const int64_t pending0 = ix ? ix->rhq_pending : 0, bound0 = ix ? ix->rkq_bound : 0;
+        const int64_t pending0 = ix ? ix->rhq_pending : 0, bound0 = ix ? ix->rkq[0].bound : 0;
         const bool keep = ix && ix->record_keep && ix->record_hits;
+        if (ix)
+            ix->rk_snap.valid = false;
         if (keep) { // the queue's tail as the call finds it, kept on the device: a call that fails puts it back
             HIPCHK(hipSetDevice(ix->device));
-            KMMCHK(rkq_reserve(ix, 0));
-            HIPCHK(hipMemcpyAsync((uint8_t *)ix->rk_ctl.p + 16, ix->rk_ctl.p, 16, hipMemcpyDeviceToDevice, ix->stream));
+            KMMCHK(rkq_mark(ix, ix->rkq[0]));
+            ix->rk_snap.pending = pending0;
+            ix->rk_snap.bound = bound0;
+            ix->rk_snap.valid = true; // (a stream call that finds its last chunk ending with an unpaired record: keep_carry)
         }
         const int rc = map_records_entry(ix, raw, n_bytes, format, k, max_freq, also_revcomp, lut, consumed, n_records);
         if (rc != KMM_OK && ix)
             ix->rhq_pending = pending0; // (record-hits mode: a call that fails reports no record and appends no entry)
-        if (rc != KMM_OK && keep) {
-            const std::string msg = g_err; // (the failure's message, not the copy's)
-            if (hipMemcpyAsync(ix->rk_ctl.p, (const uint8_t *)ix->rk_ctl.p + 16, 16, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess)
-                (void)hipGetLastError();
-            ix->rkq_bound = bound0;
-            g_err = msg;
-        }
+        if (rc != KMM_OK && keep)
+            rkq_rollback(ix, ix->rkq[0], bound0);
         return rc;
     });
 }
@@ -2936,7 +3003,7 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     HIPCHK(hipSetDevice(ix->device));
     KMMCHK(check_k_lut(k, lut));
     KMMCHK(refuse_quality_in_record_hits(ix, "kmm_map_records"));
-    KMMCHK(refuse_record_keep(ix, "kmm_map_records", format == KMM_FORMAT_SAM));
+    KMMCHK(refuse_record_keep(ix, "kmm_map_records", format == KMM_FORMAT_SAM, false, format == KMM_FORMAT_FASTA));
     KMMCHK(check_quality(ix, "kmm_map_records", k, format == KMM_FORMAT_SAM));
     // A quality floor on FASTQ: always compaction + the radix path, whatever the batch size and "path" say (as kmm_map_packed) —
     // the records front end of the direct path has no flat positions to put a quality mark on — and never the host packer,
@@ -3007,6 +3074,194 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     if (n_records)
         *n_records = recs;
     return KMM_OK;
+}
+
+// ---- kmm_map_record_pairs: the mates of a pair in two buffers, record i of one beside record i of the other.
+// One buffer's piece of a piece pair: its stage, its census (as map_records_piece takes it) and where it is cut.
+struct PairSide {
+    Stage *s = nullptr;
+    ReadsView rv;
+    int64_t len = 0, cut = 0;
+    int n_super = 0;
+    uint32_t *tile_cnt = nullptr, *super_tot = nullptr;
+    int64_t *d_out = nullptr; // {consumed, n_records, n_lines} of k_rec_scan2, {cut} of k_rec_cut
+    int64_t out[4] = {0, 0, 0, 0};
+};
+
+static int pair_side_census(kmm_index_t *ix, PairSide &p, const uint8_t *raw, int64_t len, int format)
+{
+    memset(&p.rv, 0, sizeof p.rv);
+    p.len = len;
+    if (len == 0)
+        return KMM_OK;
+    bool staged = false;
+    KMMCHK(stage_in<uint8_t>(ix, p.s->bases, raw, (size_t)len, &p.rv.bases, &staged));
+    const int64_t n_tiles = (len + TILE_T - 1) / TILE_T;
+    p.n_super = (int)((n_tiles + 1023) / 1024);
+    KMMCHK(ensure(p.s->tile_first, (size_t)p.n_super * 1024 * 4));
+    KMMCHK(ensure(p.s->offsets, (size_t)p.n_super * 4 + 64));
+    p.tile_cnt = (uint32_t *)p.s->tile_first.p;
+    p.super_tot = (uint32_t *)p.s->offsets.p;
+    p.d_out = (int64_t *)((uint8_t *)p.s->offsets.p + (((size_t)p.n_super * 4 + 15) & ~(size_t)15));
+    KMMCHK(stage_copies_done(ix));
+    HIPCHK(hipMemsetAsync(p.tile_cnt, 0, (size_t)p.n_super * 1024 * 4, ix->stream));
+    hipLaunchKernelGGL(k_rec_count, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, ix->stream, p.rv.bases, len, n_tiles, p.tile_cnt);
+    hipLaunchKernelGGL(k_rec_scan1, dim3(p.n_super), dim3(1024), 0, ix->stream, p.tile_cnt, p.super_tot);
+    hipLaunchKernelGGL(k_rec_scan2, dim3(1), dim3(1024), 0, ix->stream, p.rv.bases, len, p.n_super, p.tile_cnt, p.super_tot,
+                       (uint32_t)format, p.d_out, 1024);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(p.out, p.d_out, 24, hipMemcpyDeviceToHost, ix->stream));
+    return KMM_OK;
+}
+
+// One piece pair: both censuses, the cut of the buffer that holds more whole records than the other, the hit kernel once per
+// buffer, the entries zipped into the queue in pair order, the pair forms of the keep kernels once per buffer.
+static int map_record_pairs_piece(kmm_index_t *ix, const uint8_t *raw1, int64_t len1, const uint8_t *raw2, int64_t len2, int format, int k,
+                                  int max_freq, int also_revcomp, const uint8_t *lut, int64_t *used1, int64_t *used2, int64_t *n_pairs)
+{
+    *used1 = *used2 = *n_pairs = 0;
+    PairSide side[2];
+    side[0].s = &next_stage(ix);
+    side[1].s = &next_stage(ix);
+    KMMCHK(stage_acquire(ix, *side[0].s));
+    KMMCHK(stage_acquire(ix, *side[1].s));
+    ix->map_calls++;
+    bool staged = false, has_break = false;
+    const uint8_t *d_lut = nullptr;
+    KMMCHK(resolve_lut(ix, *side[0].s, lut, &d_lut, &staged, &has_break));
+    KMMCHK(pair_side_census(ix, side[0], raw1, len1, format));
+    KMMCHK(pair_side_census(ix, side[1], raw2, len2, format));
+    HIPCHK(hipStreamSynchronize(ix->stream)); // (it waited for the copies: the borrowed host buffers are free from here on)
+    const int64_t m = side[0].out[1] < side[1].out[1] ? side[0].out[1] : side[1].out[1];
+    bool cuts = false;
+    for (PairSide &p : side) {
+        p.cut = p.out[0];
+        if (m == 0 || p.out[1] == m)
+            continue;
+        // more whole records than the other buffer: the byte behind record m, line m * format of the census
+        hipLaunchKernelGGL(k_rec_cut, dim3(1), dim3(1024), 0, ix->stream, p.rv.bases, p.len, p.n_super, (const uint32_t *)p.tile_cnt,
+                           (const uint32_t *)p.super_tot, (const int64_t *)p.d_out, (uint32_t)(m * format), p.d_out + 3);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&p.cut, p.d_out + 3, 8, hipMemcpyDeviceToHost, ix->stream));
+        cuts = true;
+    }
+    if (cuts)
+        HIPCHK(hipStreamSynchronize(ix->stream));
+    if (m > 0) {
+        for (const PairSide &p : side)
+            if (p.cut <= 0 || p.cut > p.out[0])
+                return fail(KMM_ERR_INTERNAL, "kmm_map_record_pairs: record %lld of a buffer with %lld whole records in %lld bytes ends "
+                            "at byte %lld", (long long)m, (long long)p.out[1], (long long)p.out[0], (long long)p.cut);
+        uint32_t *q_hits = nullptr, *q_win = nullptr;
+        KMMCHK(ensure_direct(ix));
+        KMMCHK(rhq_reserve(ix, 2 * m, &q_hits, &q_win, true));
+        if (ix->record_hits != 2)
+            q_win = nullptr;
+        // (the entries of each buffer by themselves first — sums of atomics, zeroed — then zipped: entry 2i is mate 1 of pair i)
+        const size_t stride = ((size_t)m + 63) & ~(size_t)63;
+        KMMCHK(ensure(ix->rk_pair_entries, stride * 16));
+        uint32_t *e = (uint32_t *)ix->rk_pair_entries.p;
+        HIPCHK(hipMemsetAsync(e, 0, stride * 16, ix->stream));
+        KMMCHK(stage_copies_done(ix)); // (a lookup table staged from the host)
+        for (int i = 0; i < 2; ++i) {
+            PairSide &p = side[i];
+            p.rv.total = p.cut;
+            p.rv.lut = d_lut;
+            p.rv.first_bad = ix->first_bad;
+            p.rv.tile_nl = p.tile_cnt;
+            p.rv.super_nl = p.super_tot;
+            p.rv.period_mask = (uint32_t)format - 1u;
+            p.rv.header_char = format == KMM_FORMAT_FASTQ ? (uint32_t)'@' : (uint32_t)'>';
+            uint32_t *h = e + (size_t)i * stride, *w = q_win ? e + (size_t)(2 + i) * stride : nullptr;
+            if (has_break)
+                KMMCHK(launch_read_hits<MODE_RECORDS_BRK>(ix, p.rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, h, w));
+            else
+                KMMCHK(launch_read_hits<MODE_RECORDS>(ix, p.rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, h, w));
+        }
+        const dim3 gz((unsigned)grid_for(ix, (m + 255) / 256, 8));
+        hipLaunchKernelGGL(k_rk_zip, gz, dim3(256), 0, ix->stream, (const uint32_t *)e, (const uint32_t *)(e + stride), m, q_hits);
+        if (q_win)
+            hipLaunchKernelGGL(k_rk_zip, gz, dim3(256), 0, ix->stream, (const uint32_t *)(e + 2 * stride), (const uint32_t *)(e + 3 * stride), m,
+                               q_win);
+        HIPCHK(hipGetLastError());
+        ix->rhq_pending += 2 * m;
+        for (int i = 0; i < 2; ++i)
+            KMMCHK(record_keep_piece<1>(ix, ix->rkq[i], side[i].rv, side[i].len, side[i].cut, m, q_hits, q_win));
+        *used1 = side[0].cut;
+        *used2 = side[1].cut;
+        *n_pairs = m;
+    }
+    KMMCHK(stage_release(ix, *side[0].s, false));
+    return stage_release(ix, *side[1].s, false);
+}
+
+static int map_record_pairs_entry(kmm_index_t *ix, const uint8_t *raw1, int64_t n1, const uint8_t *raw2, int64_t n2, int format, int k,
+                                  int max_freq, int also_revcomp, const uint8_t *lut, int64_t *consumed1, int64_t *consumed2,
+                                  int64_t *n_pairs)
+{
+    const char *who = "kmm_map_record_pairs";
+    KMMCHK(check_k(k));
+    if (format != KMM_FORMAT_FASTQ && format != KMM_FORMAT_FASTA2)
+        return fail(KMM_ERR_INVALID_ARG, "%s: format must be KMM_FORMAT_FASTQ (4) or KMM_FORMAT_FASTA2 (2), the same for both buffers "
+                    "(nothing is mapped)", who);
+    if (n1 < 0 || n2 < 0)
+        return fail(KMM_ERR_INVALID_ARG, "%s: n1 or n2 negative", who);
+    if ((n1 > 0 && !raw1) || (n2 > 0 && !raw2))
+        return fail(KMM_ERR_INVALID_ARG, "%s: raw1 or raw2 is NULL", who);
+    HIPCHK(hipSetDevice(ix->device));
+    KMMCHK(check_k_lut(k, lut));
+    KMMCHK(refuse_quality_in_record_hits(ix, who));
+    if (!ix->record_hits || !ix->record_keep)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_hits\" is %d and \"record_keep\" is %d: the call appends the entries and the kept "
+                    "text of both mates, set \"record_hits\" to 1 or 2 and \"record_keep\" to 1 (nothing is mapped)", who, ix->record_hits,
+                    ix->record_keep);
+    if (ix->rk_min_permille > 0 && ix->record_hits != 2)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep_min_permille\" is %d and \"record_hits\" is 1: the rule needs the windows, "
+                    "which mode 2 keeps (nothing is mapped)", who, ix->rk_min_permille);
+    const int64_t piece_max = records_piece_max(ix);
+    int64_t off1 = 0, off2 = 0, pairs = 0;
+    while (off1 < n1 && off2 < n2) {
+        const int64_t len1 = n1 - off1 < piece_max ? n1 - off1 : piece_max, len2 = n2 - off2 < piece_max ? n2 - off2 : piece_max;
+        int64_t used1 = 0, used2 = 0, m = 0;
+        KMMCHK(map_record_pairs_piece(ix, raw1 + off1, len1, raw2 + off2, len2, format, k, max_freq, also_revcomp, lut, &used1, &used2, &m));
+        off1 += used1;
+        off2 += used2;
+        pairs += m;
+        if (m == 0 || (len1 < piece_max && len2 < piece_max))
+            break; // no complete pair left in reach / the last piece pair
+    }
+    *consumed1 = off1;
+    *consumed2 = off2;
+    *n_pairs = pairs;
+    return KMM_OK;
+}
+
+int kmm_map_record_pairs(kmm_index_t *ix, const uint8_t *raw1, int64_t n1, const uint8_t *raw2, int64_t n2, int format, int k,
+                         int max_freq, int also_revcomp, const uint8_t *lut, int64_t *consumed1, int64_t *consumed2, int64_t *n_pairs)
+{
+    return guarded("kmm_map_record_pairs", [&] {
+        if (!ix || !consumed1 || !consumed2 || !n_pairs)
+            return fail(KMM_ERR_INVALID_ARG, "NULL argument");
+        *consumed1 = *consumed2 = *n_pairs = 0;
+        const int64_t pending0 = ix->rhq_pending, bound0[2] = {ix->rkq[0].bound, ix->rkq[1].bound};
+        const bool keep = ix->record_keep && ix->record_hits;
+        ix->rk_snap.valid = false;
+        if (keep) { // both queues' tails as the call finds them, kept on the device: a call that fails puts them back
+            HIPCHK(hipSetDevice(ix->device));
+            KMMCHK(rkq_mark(ix, ix->rkq[0]));
+            KMMCHK(rkq_mark(ix, ix->rkq[1]));
+        }
+        const int rc = map_record_pairs_entry(ix, raw1, n1, raw2, n2, format, k, max_freq, also_revcomp, lut, consumed1, consumed2, n_pairs);
+        if (rc != KMM_OK) {
+            ix->rhq_pending = pending0;
+            *consumed1 = *consumed2 = *n_pairs = 0;
+            if (keep) {
+                rkq_rollback(ix, ix->rkq[0], bound0[0]);
+                rkq_rollback(ix, ix->rkq[1], bound0[1]);
+            }
+        }
+        return rc;
+    });
 }
 
 int kmm_map_packed(kmm_index_t *ix, const uint32_t *codes, int64_t n_bases, int64_t n_reads, int64_t read_len,
@@ -3290,6 +3545,18 @@ static int keep_carry(kmm_index_t *ix, const StreamCall &c, const uint8_t *d_raw
                       int64_t &carry_len)
 {
     const int64_t tail = n_raw - used;
+    if (c.last_chunk && tail > 0 && record_pairs_on(ix)) {
+        // ("record_pairs": a complete record behind the last whole pair stays unconsumed like an incomplete one; nothing of the
+        // call stays in the queues — the pairs in front of it were appended by the call's kmm_map_records, which succeeded)
+        carry_len = 0;
+        if (ix->rk_snap.valid) {
+            ix->rhq_pending = ix->rk_snap.pending;
+            rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
+            ix->rk_snap.valid = false;
+        }
+        return fail(KMM_ERR_MALFORMED, "%s: \"record_pairs\" is 1 and the stream ends with an unpaired record: the last %lld bytes "
+                    "form no complete pair of records (nothing of the call is appended)", c.who, (long long)tail);
+    }
     if (c.last_chunk && tail > 0) {
         carry_len = 0;
         return fail(KMM_ERR_MALFORMED, "%s: the stream ends with %lld bytes that form no complete record", c.who, (long long)tail);
@@ -3315,6 +3582,7 @@ static int map_text_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_ra
     }
     int64_t recs = 0;
     *used = 0;
+    ix->rk_snap.valid = false; // (what keep_carry may put back is this call's, never an earlier one's)
     if (n_raw > head)
         KMMCHK(kmm_map_records(ix, d_raw + head, n_raw - head, c.fmt, c.k, c.max_freq, c.also_revcomp, c.lut, used, &recs));
     *used += head;
@@ -4311,28 +4579,42 @@ int kmm_take_record_hits(kmm_index_t *ix, uint32_t *hits, uint32_t *windows, int
     return KMM_OK;
 }
 
-int kmm_take_kept_records(kmm_index_t *ix, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records)
+static int take_kept(kmm_index_t *ix, const char *who, int mate, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records)
 {
     if (!ix || !n_bytes || !n_records)
         return fail(KMM_ERR_INVALID_ARG, "NULL argument");
     *n_bytes = *n_records = 0;
     if (capacity < 0 || (capacity > 0 && !out))
-        return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_records: capacity negative, or out is NULL");
+        return fail(KMM_ERR_INVALID_ARG, "%s: capacity negative, or out is NULL", who);
     HIPCHK(hipSetDevice(ix->device));
     KMMCHK(drain(ix)); // (a sticky or deferred device error: returned, nothing taken)
+    kmm_index::RkQueue &q = ix->rkq[mate];
     unsigned long long tail[2];
-    KMMCHK(rkq_tail(ix, tail));
+    KMMCHK(rkq_tail(q, tail));
     if ((unsigned long long)capacity < tail[0])
-        return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_records: %llu bytes of %llu records are pending and capacity is %lld: the queue is "
-                    "taken whole (nothing is taken)", tail[0], tail[1], (long long)capacity);
+        return fail(KMM_ERR_INVALID_ARG, "%s: %llu bytes of %llu records are pending and capacity is %lld: the queue is "
+                    "taken whole (nothing is taken)", who, tail[0], tail[1], (long long)capacity);
     if (tail[0] > 0) {
-        HIPCHK(hipMemcpy(out, ix->rkq.p, (size_t)tail[0], is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
-        HIPCHK(hipMemset(ix->rk_ctl.p, 0, 16));
+        HIPCHK(hipMemcpy(out, q.text.p, (size_t)tail[0], is_device_ptr(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+        HIPCHK(hipMemset(q.ctl.p, 0, 16));
     }
-    ix->rkq_bound = 0;
+    q.bound = 0;
     *n_bytes = (int64_t)tail[0];
     *n_records = (int64_t)tail[1];
     return KMM_OK;
+}
+
+int kmm_take_kept_records(kmm_index_t *ix, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records)
+{
+    return take_kept(ix, "kmm_take_kept_records", 0, out, capacity, n_bytes, n_records);
+}
+
+int kmm_take_kept_mates(kmm_index_t *ix, int mate, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records)
+{
+    if (mate != 0 && mate != 1)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_mates: mate is %d: 0 (the queue of kmm_take_kept_records) or 1 (the mate-2 "
+                    "texts of kmm_map_record_pairs)", mate);
+    return take_kept(ix, "kmm_take_kept_mates", mate, out, capacity, n_bytes, n_records);
 }
 
 int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads,
@@ -4933,7 +5215,22 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value != 0 && value != 1)
             return fail(KMM_ERR_INVALID_ARG, "record_keep_invert takes 0 or 1");
         ix->rk_invert = (int)value;
-    } else if (!strcmp(name, "record_keep_pending_bytes") || !strcmp(name, "record_keep_pending_records")) {
+    } else if (!strcmp(name, "record_pairs")) {
+        // 1: while "record_keep" is 1 the records of a stream are interleaved mates — 2i and 2i + 1 — kept or dropped together
+        // (DESIGN 4.21); the calls then append even counts, which the pending entries of the other setting need not be
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "record_pairs takes 0 or 1");
+        if ((int)value != ix->record_pairs && ix->rhq_pending > 0)
+            return fail(KMM_ERR_INVALID_ARG, "record_pairs %lld with %lld entries pending that were appended under record_pairs %d: take "
+                        "them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
+                        (long long)ix->rhq_pending, ix->record_pairs);
+        ix->record_pairs = (int)value;
+    } else if (!strcmp(name, "record_pairs_rule")) {
+        if (value != (int64_t)RK_PAIR_ANY && value != (int64_t)RK_PAIR_BOTH)
+            return fail(KMM_ERR_INVALID_ARG, "record_pairs_rule takes 0 (a pair matches when any mate does) or 1 (when both do)");
+        ix->rk_pair_rule = (int)value;
+    } else if (!strcmp(name, "record_keep_pending_bytes") || !strcmp(name, "record_keep_pending_records") ||
+               !strcmp(name, "record_keep_pending_bytes_mate2") || !strcmp(name, "record_keep_pending_records_mate2")) {
         return fail(KMM_ERR_INVALID_ARG, "%s is read-only", name);
     } else if (!strcmp(name, "use_record_qual")) {
         // 1: with "min_base_quality" > 0, kmm_map_bam and KMM_FORMAT_SAM decode every record's QUAL and apply the floor
@@ -5039,12 +5336,17 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->rk_min_permille;
     else if (!strcmp(name, "record_keep_invert"))
         *value = ix->rk_invert;
-    else if (!strcmp(name, "record_keep_pending_bytes") || !strcmp(name, "record_keep_pending_records")) {
+    else if (!strcmp(name, "record_pairs"))
+        *value = ix->record_pairs;
+    else if (!strcmp(name, "record_pairs_rule"))
+        *value = ix->rk_pair_rule;
+    else if (!strcmp(name, "record_keep_pending_bytes") || !strcmp(name, "record_keep_pending_records") ||
+             !strcmp(name, "record_keep_pending_bytes_mate2") || !strcmp(name, "record_keep_pending_records_mate2")) {
         // the true tail of the queue of kept records lives on the device: behind a synchronisation, as "quality_masked_bases"
         HIPCHK(hipSetDevice(ix->device));
         KMMCHK(drain(ix));
         unsigned long long tail[2];
-        KMMCHK(rkq_tail(ix, tail));
+        KMMCHK(rkq_tail(ix->rkq[strstr(name, "_mate2") ? 1 : 0], tail));
         *value = (int64_t)tail[name[20] == 'b' ? 0 : 1];
     } else if (!strcmp(name, "read_hits_calls")) // kmm_read_hits calls (a pure query: no other counter moves)
         *value = ix->read_hits_calls;

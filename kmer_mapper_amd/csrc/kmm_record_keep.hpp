@@ -6,6 +6,8 @@
 //   (k_rec_scan1 + k_super_scan: prefix sums of the byte counts; the same pair sums the record counts)
 //   k_rk_scatter   the kept bytes of four tiles, compacted in LDS, written as one contiguous span of the queue
 //   k_rk_advance   the queue's tail moves behind the piece's bytes and records
+// Mates kept together: k_rk_flags and k_rk_scatter are templates over PAIR — 0 is the code above, 1 and 2 ask the
+// pair rule of the two entries of a record's pair — and k_rk_zip puts the entries of two buffers into the queue in pair order.
 // The arithmetic is plain C++ (KMM_RH_HD): the CPU tier compiles this header with g++.
 #pragma once
 
@@ -21,6 +23,38 @@ KMM_RH_HD bool rk_keep(uint32_t hits, uint32_t windows, const RkRule &rule)
 {
     const bool match = hits >= rule.min_hits && 1000ull * (uint64_t)hits >= (uint64_t)rule.min_permille * (uint64_t)windows;
     return match != (rule.invert != 0u);
+}
+
+// The pair rule: mates are kept or dropped together.  `match` of a mate is the rule above without its inversion;
+// the pair matches when ANY mate does, or only when BOTH do, and the inversion is applied to the pair.
+enum : uint32_t { RK_PAIR_ANY = 0u, RK_PAIR_BOTH = 1u };
+
+struct RkPairRule {
+    RkRule rule;
+    uint32_t pair_rule;
+};
+
+KMM_RH_HD bool rk_match(uint32_t hits, uint32_t windows, const RkRule &rule)
+{
+    return hits >= rule.min_hits && 1000ull * (uint64_t)hits >= (uint64_t)rule.min_permille * (uint64_t)windows;
+}
+
+KMM_RH_HD bool rk_pair_keep(uint32_t h1, uint32_t w1, uint32_t h2, uint32_t w2, const RkRule &rule, uint32_t pair_rule)
+{
+    const bool m1 = rk_match(h1, w1, rule), m2 = rk_match(h2, w2, rule);
+    const bool pair_match = pair_rule == RK_PAIR_ANY ? (m1 || m2) : (m1 && m2);
+    return pair_match != (rule.invert != 0u);
+}
+
+// The pair forms of the kernels below, PAIR: 0 none (one record, one entry); 1: record r of the buffer is pair r (the two-file
+// call: the buffer holds one mate of every pair); 2: records 2p and 2p + 1 are pair p (interleaved).  The entries of pair p
+// are 2p and 2p + 1 in every form.
+template <int PAIR> struct RkRuleOf { typedef RkPairRule type; };
+template <> struct RkRuleOf<0> { typedef RkRule type; };
+
+KMM_RH_HD uint32_t rk_pair_of_record(uint32_t record, uint32_t pair_shift)
+{
+    return record >> pair_shift;
 }
 
 // Keep mask of a lane's LANE bytes at piece positions p0 .. p0 + LANE - 1: bit j = byte j lies before `consumed` and belongs to
@@ -90,6 +124,8 @@ KMM_RH_HD RkSpan rk_span(uint32_t a, uint32_t len)
 
 #if defined(__HIPCC__)
 
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2))); // (the two entries of a pair: one 8-byte load)
+
 // What both per-byte kernels know of a lane: its 16 bytes, their newlines, its keep mask and the line of its first byte.
 struct RkLane {
     uint32_t w[4];
@@ -98,10 +134,13 @@ struct RkLane {
 
 // One wavefront per tile; called with all 64 lanes active (a tile behind the piece: no bytes, no mask).  hits / windows: the
 // piece's entries (n_records of them), complete; windows null: mode 1.
+// PAIR != 0: hits / windows are the entries of the piece's pairs, two per pair, 8-byte aligned; n_records counts the records of
+// `raw` (PAIR 1: as many as pairs; PAIR 2: twice as many).
+template <int PAIR>
 __device__ __forceinline__ void rk_lane_front(const uint8_t *__restrict__ raw, int64_t n, int64_t consumed, int64_t n_tiles, int64_t tile,
                                               int lane, const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
                                               uint32_t period_mask, const uint32_t *__restrict__ hits, const uint32_t *__restrict__ windows,
-                                              int64_t n_records, const RkRule &rule, RkLane &L)
+                                              int64_t n_records, const typename RkRuleOf<PAIR>::type &rule, RkLane &L)
 {
     const int64_t p = tile * 1024 + lane * 16;
     L.w[0] = L.w[1] = L.w[2] = L.w[3] = 0u;
@@ -127,16 +166,26 @@ __device__ __forceinline__ void rk_lane_front(const uint8_t *__restrict__ raw, i
     L.mask = rk_lane_mask<16>(L.line0, L.nl, (uint32_t)__popc(period_mask), p, end, [&](uint32_t r) {
         if ((int64_t)r >= n_records)
             return false;
-        return rk_keep(hits[r], windows ? windows[r] : 0u, rule);
+        if constexpr (PAIR == 0) {
+            return rk_keep(hits[r], windows ? windows[r] : 0u, rule);
+        } else {
+            const size_t e = 2 * (size_t)rk_pair_of_record(r, (uint32_t)(PAIR - 1)); // (both entries exist: n_records is whole pairs)
+            const u32x2 h = *reinterpret_cast<const u32x2 *>(hits + e);
+            u32x2 w = {0u, 0u};
+            if (windows)
+                w = *reinterpret_cast<const u32x2 *>(windows + e);
+            return rk_pair_keep(h[0], w[0], h[1], w[1], rule.rule, rule.pair_rule);
+        }
     });
 }
 
 // (The record counts go through an array and the scans, not through an atomic on the tail: one atomic per tile on one address
 // added 3.9 ms to a chunk of 300 000 tiles, eight times what the whole mode costs now: profiles/record_keep/README.md.)
+template <int PAIR>
 __global__ void __launch_bounds__(256) k_rk_flags(const uint8_t *__restrict__ raw, int64_t n, int64_t consumed, int64_t n_tiles,
                                                   const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
                                                   uint32_t period_mask, const uint32_t *__restrict__ hits,
-                                                  const uint32_t *__restrict__ windows, int64_t n_records, RkRule rule,
+                                                  const uint32_t *__restrict__ windows, int64_t n_records, typename RkRuleOf<PAIR>::type rule,
                                                   uint32_t *__restrict__ tile_cnt, uint32_t *__restrict__ tile_rec)
 {
     const int lane = threadIdx.x & 63;
@@ -144,7 +193,7 @@ __global__ void __launch_bounds__(256) k_rk_flags(const uint8_t *__restrict__ ra
     if (tile >= n_tiles)
         return;
     RkLane L;
-    rk_lane_front(raw, n, consumed, n_tiles, tile, lane, tile_nl, super_nl, period_mask, hits, windows, n_records, rule, L);
+    rk_lane_front<PAIR>(raw, n, consumed, n_tiles, tile, lane, tile_nl, super_nl, period_mask, hits, windows, n_records, rule, L);
     const uint32_t kept = wave_sum((uint32_t)__popc(L.mask));
     const uint32_t recs = wave_sum(rk_lane_records<16>(L.line0, L.nl, period_mask, L.mask));
     if (lane == 0) {
@@ -157,10 +206,11 @@ __global__ void __launch_bounds__(256) k_rk_flags(const uint8_t *__restrict__ ra
 // tiles go to LDS in order, shifted so that LDS byte i and queue byte (dst - a + i) share their place inside a 16-byte line;
 // the span [a, a + len) then leaves as whole 16-byte lines, its ragged head and tail byte by byte.  The neighbouring groups
 // write the other bytes of the first and the last line: no byte outside the span is written, none of the queue is read.
+template <int PAIR>
 __global__ void __launch_bounds__(256) k_rk_scatter(const uint8_t *__restrict__ raw, int64_t n, int64_t consumed, int64_t n_tiles,
                                                     const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
                                                     uint32_t period_mask, const uint32_t *__restrict__ hits,
-                                                    const uint32_t *__restrict__ windows, int64_t n_records, RkRule rule,
+                                                    const uint32_t *__restrict__ windows, int64_t n_records, typename RkRuleOf<PAIR>::type rule,
                                                     const uint32_t *__restrict__ tile_pre, const uint32_t *__restrict__ super_pre,
                                                     const unsigned long long *__restrict__ tail, uint8_t *__restrict__ queue)
 {
@@ -169,7 +219,7 @@ __global__ void __launch_bounds__(256) k_rk_scatter(const uint8_t *__restrict__ 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t tile0 = (int64_t)blockIdx.x * 4, tile = tile0 + wave;
     RkLane L;
-    rk_lane_front(raw, n, consumed, n_tiles, tile, lane, tile_nl, super_nl, period_mask, hits, windows, n_records, rule, L);
+    rk_lane_front<PAIR>(raw, n, consumed, n_tiles, tile, lane, tile_nl, super_nl, period_mask, hits, windows, n_records, rule, L);
     const uint32_t kept = (uint32_t)__popc(L.mask);
     const uint32_t incl = wave_scan_incl(kept);
     if (lane == 63)
@@ -208,6 +258,19 @@ __global__ void k_rk_advance(unsigned long long *tail, const uint32_t *__restric
 {
     if (threadIdx.x < 2 && blockIdx.x == 0)
         tail[threadIdx.x] += (unsigned long long)total[threadIdx.x];
+}
+
+// The entries of the two buffers of kmm_map_record_pairs (m each, in record order) in pair order: out[2i] = mate1[i],
+// out[2i + 1] = mate2[i], as the interleaved file would have appended them.  out is 8-byte aligned.
+__global__ void __launch_bounds__(256) k_rk_zip(const uint32_t *__restrict__ mate1, const uint32_t *__restrict__ mate2, int64_t m,
+                                                uint32_t *__restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        u32x2 e;
+        e[0] = mate1[i];
+        e[1] = mate2[i];
+        *reinterpret_cast<u32x2 *>(out + 2 * i) = e;
+    }
 }
 
 #endif // __HIPCC__

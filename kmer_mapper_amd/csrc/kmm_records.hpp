@@ -2,6 +2,8 @@
 // Records mode pre-pass: newline census of raw FASTQ / two-line FASTA chunks.
 #pragma once
 
+#include "kmm_line_search.hpp"
+
 // ------------------------------------------------------------------------------------------------
 // Records mode pre-pass: newline census of a raw FASTQ / two-line FASTA chunk (tile = 1024 bytes,
 // super-tile = 1024 tiles), so that every tile knows the line number of its first byte, and the
@@ -121,6 +123,58 @@ __global__ void __launch_bounds__(1024) k_rec_scan2(const uint8_t *__restrict__ 
         out[1] = target / period;
         out[2] = total;
     }
+}
+
+// One workgroup, behind k_rec_scan1 + k_rec_scan2 over the same chunk (tile_pre: newlines in front of a tile inside its
+// super-tile; super_pre: in front of a super-tile; census: k_rec_scan2's out, whose [2] is the chunk's newline count): the byte
+// position just behind the chunk's target-th newline -> out[0], for 1 <= target <= census[2]; -1 for any other target (nothing
+// is read through an index the search did not find).  kmm_map_record_pairs cuts the buffer that holds more records than its
+// mate's at the record both have; 1024-byte tiles.
+__global__ void __launch_bounds__(1024) k_rec_cut(const uint8_t *__restrict__ raw, int64_t n, int n_super,
+                                                  const uint32_t *__restrict__ tile_pre, const uint32_t *__restrict__ super_pre,
+                                                  const int64_t *__restrict__ census, uint32_t target, int64_t *out)
+{
+    __shared__ uint32_t s_a[1024];
+    __shared__ uint32_t s_rem, s_super_cnt;
+    __shared__ int s_super;
+    __shared__ int64_t s_tile;
+    const int t = threadIdx.x;
+    const uint32_t total = (uint32_t)census[2];
+    if (t == 0) {
+        s_super = -1;
+        s_tile = -1;
+        out[0] = -1;
+    }
+    __syncthreads();
+    if (t < n_super) {
+        const uint32_t pre = super_pre[t], nxt = t + 1 < n_super ? super_pre[t + 1] : total;
+        if (ls_slot_holds(pre, nxt, target)) {
+            s_super = t;
+            s_rem = ls_rank_in_slot(pre, target);
+            s_super_cnt = nxt - pre;
+        }
+    }
+    __syncthreads();
+    const int sup = s_super;
+    if (sup < 0) // (uniform)
+        return;
+    const uint32_t rem = s_rem;
+    const uint32_t pre = tile_pre[(size_t)sup * 1024 + t];
+    const uint32_t nxt = t < 1023 ? tile_pre[(size_t)sup * 1024 + t + 1] : s_super_cnt;
+    if (ls_slot_holds(pre, nxt, rem))
+        s_tile = (int64_t)sup * 1024 + t;
+    __syncthreads();
+    const int64_t tile = s_tile;
+    if (tile < 0) // (uniform)
+        return;
+    const uint32_t r = ls_rank_in_slot(tile_pre[tile], rem); // the r-th newline of the tile
+    const int64_t pos = tile * 1024 + t;
+    const uint32_t is_nl = (pos < n && raw[pos] == 10u) ? 1u : 0u;
+    s_a[t] = is_nl;
+    __syncthreads();
+    block_scan_1024(s_a);
+    if (is_nl && s_a[t] == r)
+        out[0] = pos + 1;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -441,6 +441,48 @@ class DeviceIndex:
                                                     ctypes.byref(n_bytes), ctypes.byref(n_records)))
         return buf[:n_bytes.value], n_records.value
 
+    PAIR_RULES = {"any": 0, "both": 1}
+
+    def record_pairs(self, on=True, rule="any"):
+        """Keeping mates together (include/kmm.h), on top of record_keep(): the records of a stream are interleaved —
+        2i and 2i + 1 are mates — and both are kept or both dropped: a pair matches when `rule` "any" of its mates passes the
+        keep rule (without its inversion), or only when "both" do, and invert flips the pair's outcome.  map_records (FASTQ,
+        two-line FASTA), map_bgzf and map_gzip then take whole pairs only.  rule is also the rule of map_record_pairs, which
+        does not read `on`.  Refused while hit entries are pending."""
+        if rule not in self.PAIR_RULES:
+            raise ValueError("rule must be 'any' or 'both', not %r" % (rule,))
+        self.set_param("record_pairs_rule", self.PAIR_RULES[rule])
+        self.set_param("record_pairs", int(bool(on)))
+
+    def map_record_pairs(self, raw1, raw2, fmt=_lib.FORMAT_FASTQ, k=31, max_index_lookup_frequency=1000, also_revcomp=False,
+                         lut=None, n_bytes1=None, n_bytes2=None):
+        """kmm_map_record_pairs: record i of raw1 and record i of raw2 (FASTQ or two-line FASTA chunks, each in host or device
+        memory) are mates, kept or dropped together under record_keep()'s rule and record_pairs()'s pair rule.  The hits queue
+        gains two entries per pair (mate 1, mate 2); the kept mate-1 text goes to the queue of take_kept_records(), the kept
+        mate-2 text to take_kept_mates(1).  Returns (consumed1, consumed2, n_pairs): only whole pairs are taken, the caller
+        carries raw1[consumed1:] and raw2[consumed2:] to the next chunks."""
+        a, b = _Arg(raw1, np.uint8, "raw1"), _Arg(raw2, np.uint8, "raw2")
+        t = _Arg(lut, np.uint8, "lut")
+        c1, c2, n_pairs = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(_lib.lib().kmm_map_record_pairs(self._h, a.ptr, _n_bytes(a, n_bytes1), b.ptr, _n_bytes(b, n_bytes2), int(fmt), int(k),
+                                                   int(max_index_lookup_frequency), int(bool(also_revcomp)), t.ptr,
+                                                   ctypes.byref(c1), ctypes.byref(c2), ctypes.byref(n_pairs)))
+        return c1.value, c2.value, n_pairs.value
+
+    def take_kept_mates(self, mate, out=None):
+        """kmm_take_kept_mates: take_kept_records() on the queue of mate 0 (the same queue) or mate 1 (the mate-2 texts of
+        map_record_pairs)."""
+        n_bytes, n_records = ctypes.c_int64(0), ctypes.c_int64(0)
+        if out is not None:
+            o = _Arg(out, np.uint8, "out")
+            _lib.check(_lib.lib().kmm_take_kept_mates(self._h, int(mate), o.ptr, o.n, ctypes.byref(n_bytes), ctypes.byref(n_records)))
+            return n_bytes.value, n_records.value
+        pending = self.get_param("record_keep_pending_bytes_mate2" if int(mate) == 1 else "record_keep_pending_bytes")
+        buf = np.empty(pending, dtype=np.uint8)
+        _lib.check(_lib.lib().kmm_take_kept_mates(self._h, int(mate), buf.ctypes.data_as(_P) if pending else None, pending,
+                                                  ctypes.byref(n_bytes), ctypes.byref(n_records)))
+        return buf[:n_bytes.value], n_records.value
+
     # -- measurement -----------------------------------------------------------------------------
     def set_timing(self, on=True):
         _lib.check(_lib.lib().kmm_set_timing(self._h, int(bool(on))))

@@ -187,3 +187,45 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
         dev.record_keep(False)
         dev.record_hits(False)
     return text.tobytes(), hits, windows
+
+
+def select_record_pairs(index, raw1, raw2=None, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None,
+                        min_hits=1, min_permille=0, invert=False, pair_rule="any", device=0):
+    """Extension: select_records for paired-end reads, whose mates are kept or dropped together.  raw2 None: `raw1`
+    holds the mates interleaved, records 2i and 2i + 1; else record i of raw1 and record i of raw2 are mates (fmt "fastq" or
+    "fasta", two-line, the same for both; each of bytes, a uint8 array or a torch tensor, host or device).  Per mate, match is
+    hits >= min_hits and 1000 * hits >= min_permille * windows; a pair matches when pair_rule "any" mate does, or only when
+    "both" do, and is kept iff match != invert.  Returns (text1, text2, hits, windows): the kept records of raw1 and of raw2 in
+    order — text2 None for interleaved input, whose kept pairs are text1 — and one entry per record of every whole pair, in pair
+    order (mate 1, mate 2).  Records behind the last whole pair are not looked at.  The cached handle is left as it was found."""
+    from . import _lib
+    kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2}[fmt]
+    as_array = lambda raw: np.frombuffer(bytes(raw), dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else raw
+    raw1, raw2 = as_array(raw1), None if raw2 is None else as_array(raw2)
+    max_node_id = int(np.max(index._nodes)) if len(index._nodes) else 0
+    dev = _device_index(index, max_node_id, device)
+    if (dev.get_param("record_hits_pending") or dev.get_param("record_keep_pending_bytes")
+            or dev.get_param("record_keep_pending_bytes_mate2")):
+        raise ValueError("the cached handle has record hits or kept records pending: take them first")
+    before = (dev.get_param("record_pairs"), dev.get_param("record_pairs_rule"))
+    dev.record_hits(True, windows=True)
+    dev.record_keep(True, min_hits=min_hits, min_permille=min_permille, invert=invert)
+    try:
+        dev.record_pairs(raw2 is None, rule=pair_rule)
+        common = dict(fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp, lut=lut)
+        text2 = None
+        if raw2 is None:
+            dev.map_records(raw1, **common)
+        else:
+            dev.map_record_pairs(raw1, raw2, **common)
+        hits, windows = dev.take_record_hits()
+        text1, _ = dev.take_kept_records()
+        if raw2 is not None:
+            text2 = dev.take_kept_mates(1)[0].tobytes()
+    finally:
+        dev.record_keep(False)
+        dev.record_hits(False)
+        dev.set_param("record_pairs_rule", before[1])
+        if not dev.get_param("record_hits_pending"):                                   # (a failing call appended nothing)
+            dev.set_param("record_pairs", before[0])
+    return text1.tobytes(), text2, hits, windows
