@@ -636,6 +636,36 @@ int kmm_map_record_pairs(kmm_index_t *idx, const uint8_t *raw1, int64_t n1, cons
 int kmm_take_kept_mates(kmm_index_t *idx, int mate, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records);
 
 /*
+ * COMPRESSED OUTPUT.  Text that lies in device memory leaves it as BGZF: the input is cut every 65280 (0xFF00)
+ * bytes, as bgzip cuts it, and every piece becomes one member — the 18-byte header (1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6,
+ * 'B' 'C' 2, BSIZE = member size - 1), one final deflate block, the CRC32 of the piece, ISIZE.  The block is dynamic Huffman
+ * over LZ77 tokens, or stored whenever the dynamic form would not be smaller than the piece + 5 bytes: a member of n bytes of
+ * text is never larger than n + 31 bytes.  Zero bytes give zero members; NO end-of-file block is appended — the caller writes
+ * the 28-byte empty member once, at the end of a file.  The bytes are a pure function of the text: two calls, two devices and
+ * the g++ build of csrc/kmm_bgzf_out.hpp give identical members.
+ *
+ * kmm_bgzf_bound(n): what n bytes of text can need, n + 31 * ceil(n / 65280); 0 for n == 0; -1 for n < 0.
+ *
+ * kmm_bgzf_compress — an operator like kmm_extract_kmers (no handle; a stream of its own): in[0, n) -> out, *n_out the bytes
+ * written.  in and out may each be host or device memory.  capacity < kmm_bgzf_bound(n) is KMM_ERR_INVALID_ARG, the message
+ * names the bound, and nothing is written.
+ *
+ * kmm_take_kept_bgzf — kmm_take_kept_mates with the queue's text compressed on the device, so that only the members cross the
+ * link: mate 0 is the queue of kmm_take_kept_records, mate 1 the mate-2 queue of kmm_map_record_pairs, anything else
+ * KMM_ERR_INVALID_ARG.  It synchronises first — a sticky or deferred device error is returned and nothing is taken.  capacity is
+ * judged against kmm_bgzf_bound(pending bytes): if it is at least that, ALL pending text is compressed, the members are copied
+ * to out (host or device memory), *n_comp is their bytes, *n_bytes the text they hold, *n_records its records, and the queue is
+ * emptied; otherwise KMM_ERR_INVALID_ARG, the message names the bound, nothing is taken and the queue stays takeable by either
+ * kind of take.  out == NULL with capacity 0 on an empty queue is KMM_OK with zeros.  Every take ends its last member:
+ * concatenated takes are a valid BGZF stream (short last members are the price).  The plain takes are untouched; the two kinds
+ * may be mixed on one handle.  With timing on the kernels are timed as KMM_KERNEL_BGZF_DEFLATE and KMM_KERNEL_BGZF_GATHER.
+ */
+int64_t kmm_bgzf_bound(int64_t n);
+int kmm_bgzf_compress(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t capacity, int64_t *n_out);
+int kmm_take_kept_bgzf(kmm_index_t *idx, int mate, uint8_t *out, int64_t capacity, int64_t *n_comp, int64_t *n_bytes,
+                       int64_t *n_records);
+
+/*
  * kmm_build_index — builds the Kmer Index arrays on the GPU from flat (k-mer, node) pairs: replaces
  * graph_kmer_index's KmerIndex.from_flat_kmers(flat_kmers, modulo) (reference call site
  * tests/test_mapping.py:36-38; gpu_counter.py:16 builds its table from the same pairs).  Entries are
@@ -663,7 +693,9 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
 #define KMM_KERNEL_RX_P2 4        /* radix path, pass 2: items sorted by fine hash range               */
 #define KMM_KERNEL_RX_P3 5        /* radix path, pass 3: probe of LDS-resident index slices + counting */
 #define KMM_KERNEL_RX_FLUSH 6     /* radix path: per-entry hit counts -> node counts                   */
-#define KMM_N_KERNELS 7
+#define KMM_KERNEL_BGZF_DEFLATE 7 /* BGZF writer: text -> one member per 65280 bytes, in slots             */
+#define KMM_KERNEL_BGZF_GATHER 8  /* BGZF writer: member offsets + the members one behind the other       */
+#define KMM_N_KERNELS 9
 int kmm_set_timing(kmm_index_t *idx, int enabled);
 /* Work done by the map calls of this handle since creation (or the last call with reset != 0):
  * k-mer lookups performed (windows, doubled with also_revcomp) and count increments (index hits that

@@ -28,8 +28,9 @@ FORMAT_SAM = 8                  # SAM text: the SEQ column extracted on the GPU 
 
 # kernel ids of kmm_get_timing (include/kmm.h)
 (KERNEL_MAP_READS, KERNEL_MAP_KMERS, KERNEL_RX_P1, KERNEL_RX_SCAN, KERNEL_RX_P2, KERNEL_RX_P3,
- KERNEL_RX_FLUSH) = range(7)
-KERNEL_NAMES = ("k_map_reads", "k_map_kmers", "k_rx_p1", "k_rx_scan", "k_rx_p2", "k_rx_p3", "k_rx_flush")
+ KERNEL_RX_FLUSH, KERNEL_BGZF_DEFLATE, KERNEL_BGZF_GATHER) = range(9)
+KERNEL_NAMES = ("k_map_reads", "k_map_kmers", "k_rx_p1", "k_rx_scan", "k_rx_p2", "k_rx_p3", "k_rx_flush", "k_bz_deflate",
+                "k_bz_gather")
 
 _c = ctypes
 _P = ctypes.c_void_p
@@ -79,6 +80,9 @@ SIGNATURES = {
     "kmm_take_kept_records": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),
     "kmm_map_record_pairs": (_c.c_int, [_P, _P, _c.c_int64, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     "kmm_take_kept_mates": (_c.c_int, [_P, _c.c_int, _P, _c.c_int64, _P, _P]),
+    "kmm_bgzf_bound": (_c.c_int64, [_c.c_int64]),
+    "kmm_bgzf_compress": (_c.c_int, [_c.c_int, _P, _c.c_int64, _P, _c.c_int64, _P]),
+    "kmm_take_kept_bgzf": (_c.c_int, [_P, _c.c_int, _P, _c.c_int64, _P, _P, _P]),
     "kmm_set_timing": (_c.c_int, [_P, _c.c_int]),
     "kmm_get_stats": (_c.c_int, [_P, _c.c_int, _P, _P]),
     "kmm_get_timing": (_c.c_int, [_P, _c.c_int, _P, _P]),

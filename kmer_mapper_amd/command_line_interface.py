@@ -948,10 +948,11 @@ def _save_read_hits(args, hits, wins):
 class RecordKeepSink(RecordHitsSink):
     """The same hook for `select-reads`: open(dev) sets record-hits mode 2 and the keep rule, drain(dev) takes
     both queues after every map call — so both stay chunk-sized — and appends the kept records' bytes to `out`, a binary file
-    object; seen / kept count the records."""
+    object; seen / kept count the records.  bgzf: the kept text is deflated on the GPU and `out` (and out2) get
+    BGZF members — every drain ends its last member; close() writes the end-of-file block; kept_bytes still counts text."""
 
     def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False, pairs=False, pair_rule="any",
-                 out2=None):
+                 out2=None, bgzf=False):
         super().__init__(windows=True)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
@@ -962,6 +963,8 @@ class RecordKeepSink(RecordHitsSink):
         # mates kept together: pairs: the stream is interleaved ("record_pairs"); out2: the file of the mate-2
         # texts of map_record_pairs, whose queue is drained with the other two
         self.pairs, self.pair_rule, self.out2 = bool(pairs), pair_rule, out2
+        self.bgzf = bool(bgzf)
+        self.written = 0                     # bytes written to out and out2 (the members' with bgzf, else the text's)
 
     def open(self, dev):
         super().open(dev)
@@ -983,19 +986,34 @@ class RecordKeepSink(RecordHitsSink):
             self.hits.append(got[0])
             self.wins.append(got[1])
             self.seen += int(got[0].shape[0])
-        text, n = dev.take_kept_records()
-        if text.shape[0]:
-            self.out.write(memoryview(text))
-        self.kept += int(n)
-        self.kept_bytes += int(text.shape[0])
+        n = self._take(dev, 0, self.out)
         if self.out2 is not None:
-            text2, n2 = dev.take_kept_mates(1)
+            n2 = self._take(dev, 1, self.out2)
             if n2 != n:
                 raise RuntimeError("select-reads: %d mate-1 and %d mate-2 records kept by one call" % (n, n2))
-            if text2.shape[0]:
-                self.out2.write(memoryview(text2))
-            self.kept += int(n2)
-            self.kept_bytes += int(text2.shape[0])
+
+    def _take(self, dev, mate, out):
+        """One queue into its file; returns the records taken."""
+        if self.bgzf:
+            data, n_text, n = dev.take_kept_bgzf(mate)
+        else:
+            data, n = dev.take_kept_mates(mate)
+            n_text = int(data.shape[0])
+        if data.shape[0]:
+            out.write(memoryview(data))
+        self.written += int(data.shape[0])
+        self.kept += int(n)
+        self.kept_bytes += int(n_text)
+        return n
+
+    def close(self):
+        """Behind the last drain: the block that ends a BGZF file."""
+        if self.bgzf:
+            from .gz_io import BGZF_EOF
+            for out in (self.out, self.out2):
+                if out is not None:
+                    out.write(BGZF_EOF)
+                    self.written += len(BGZF_EOF)
 
 
 _SELECT_READS_BAM_ONLY = (("--bam-to-fastq", "bam_to_fastq"), ("--exclude-flags", "exclude_flags"), ("--include-flags", "include_flags"),
@@ -1127,7 +1145,7 @@ def select_read_pairs_files(index, reads1, reads2, chunk_size, fmt, k, sink, map
 
 def select_reads_file(args):
     """`kmer_mapper select-reads`: the reads of a FASTA / FASTQ file that pass the keep rule, written to -o as uncompressed
-    text, in file order.  The file goes down the route `map` would choose for it in one process (choose_route: raw records,
+    text — with --bgzf as a BGZF file, deflated on the GPU — in file order.  The file goes down the route `map` would choose for it in one process (choose_route: raw records,
     BGZF, gzip — parsed and inflated on the GPU) with the handle's record-hits mode 2 and record-keep mode on; both queues are
     taken after every map call.  Wrapped FASTA comes out unwrapped (two-line).
     --interleaved / -f2 with -o2: paired-end reads, whose mates are kept or dropped together."""
@@ -1167,7 +1185,8 @@ def select_reads_file(args):
         fmt = "fasta_ml"
     logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes%s",
                  "; BAM records decoded to FASTQ with their names (--bam-to-fastq)" if bam else "")
-    rule = dict(min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert)
+    rule = dict(min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert,
+                bgzf=bool(getattr(args, "bgzf", False)))
     if reads2 is not None:
         logging.info("select-reads: -f and -f2 are read in step by the host readers (two compressed streams are not inflated on the "
                      "GPU in step); mates are kept together, pair rule '%s'", pair_rule or "any")
@@ -1175,6 +1194,7 @@ def select_reads_file(args):
             sink = RecordKeepSink(out, pair_rule=pair_rule or "any", out2=out2, **rule)
             select_read_pairs_files(kmer_index, args.reads, reads2, args.chunk_size, fmt, k, sink, bool(args.map_reverse_complements),
                                     args.max_hits_per_kmer, device=args.device, lut=lut)
+            sink.close()
     else:
         with open(args.output_file, "wb") as out:
             sink = RecordKeepSink(out, names=bam, mate_suffix=bam and bool(getattr(args, "mate_suffix", False)), pairs=interleaved,
@@ -1194,9 +1214,11 @@ def select_reads_file(args):
                 raise ValueError("select-reads --interleaved: %s does not end with a whole pair: it holds %d whole records, %d mate-1 "
                                  "and %d mate-2%s (%s)" % (args.reads, n_whole, (n_whole + 1) // 2, n_whole // 2, "" if n_whole % 2 else
                                                            ", and an incomplete record behind them", exc)) from exc
+            sink.close()
     hits, wins = sink.result()
-    logging.info("%d reads seen, %d (%.2f %%) kept: %d bytes written to %s%s", sink.seen, sink.kept,
-                 100.0 * sink.kept / max(sink.seen, 1), sink.kept_bytes, args.output_file,
+    logging.info("%d reads seen, %d (%.2f %%) kept: %d bytes %s %s%s", sink.seen, sink.kept,
+                 100.0 * sink.kept / max(sink.seen, 1), sink.kept_bytes,
+                 "written as %d bytes of BGZF to" % sink.written if sink.bgzf else "written to", args.output_file,
                  "".join("; %s %d" % (name, v) for name, v in sink.counters.items() if v))
     if args.hits_output is not None:
         np.save(args.hits_output, hits)
@@ -1376,6 +1398,9 @@ def build_argument_parser():
     sub.add_argument("--pair-rule", choices=("any", "both"), default=argparse.SUPPRESS,
                      help="With --interleaved or -f2: a pair matches when any of its mates passes --min-hits / --min-hit-permille "
                           "(default), or only when both do; --invert then flips the pair's outcome.")
+    sub.add_argument("--bgzf", action="store_true", default=argparse.SUPPRESS,
+                     help="Write -o (and -o2) as BGZF files: the kept text is deflated on the GPU, one member per 65280 bytes, and "
+                          "only the members are copied to the host. Without it the output is plain text, whatever -o is called.")
     sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
     sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
     sub.set_defaults(func=select_reads_file)

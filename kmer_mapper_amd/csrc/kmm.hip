@@ -187,8 +187,15 @@ constexpr unsigned long long NO_BAD = ~0ull;
 #include "kmm_hostpack.hpp"
 #include "kmm_gpu_inflate.hpp"
 #include "kmm_gpu_gunzip.hpp"
+#include "kmm_bgzf_out.hpp"
 #include "kmm_bam.hpp"
 #include "kmm_sam.hpp"
+
+// What the BGZF writer (kmm_bgzf_out.hpp) keeps between calls: the workgroups' candidate scratch, the member slots of
+// one round, their sizes and offsets, and the members one behind the other where they leave for host memory.
+struct BzScratch {
+    DevBuf cand, slots, sizes, offs, comp;
+};
 
 // Page-locked buffers are expensive to make (hipHostMalloc: ~50 ms per GB) and cheap to keep: the ones a handle gives up go
 // to a process-wide shelf (at most 8 GiB), and kmm_host_reserve puts buffers there ahead of time — from another thread,
@@ -458,6 +465,7 @@ struct kmm_index : IndexStreams, RxArrays {
     int record_pairs = 0, rk_pair_rule = 0;
     struct { int64_t pending = 0, bound = 0; bool valid = false; } rk_snap;
     DevBuf rk_pair_entries;
+    BzScratch bz; // kmm_take_kept_bgzf
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
     int comm_rank = -1, comm_size = 0;
@@ -4615,6 +4623,146 @@ int kmm_take_kept_mates(kmm_index_t *ix, int mate, uint8_t *out, int64_t capacit
         return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_mates: mate is %d: 0 (the queue of kmm_take_kept_records) or 1 (the mate-2 "
                     "texts of kmm_map_record_pairs)", mate);
     return take_kept(ix, "kmm_take_kept_mates", mate, out, capacity, n_bytes, n_records);
+}
+
+// d_in[0, n) (device memory) -> its BGZF members in out (host or device memory; at least kmm_bz::bound(n) bytes), on stream st,
+// BZ_ROUND members at a time: deflate into slots, offsets, gather; a round's bytes are known to the host before the next begins.
+// timed: the handle whose timing the kernels go to (st is its stream), or null.
+constexpr uint32_t BZ_ROUND = 2048; // (128 MiB of slots)
+
+static int bz_compress(hipStream_t st, int n_cu, BzScratch &s, const uint32_t *d_crcT, const uint8_t *d_in, int64_t n, uint8_t *out,
+                       int64_t *n_out, kmm_index *timed)
+{
+    *n_out = 0;
+    const int64_t n_members = kmm_bz::member_count(n);
+    if (n_members == 0)
+        return KMM_OK;
+    const bool out_dev = is_device_ptr(out);
+    const uint32_t round = (uint32_t)(n_members < (int64_t)BZ_ROUND ? n_members : (int64_t)BZ_ROUND);
+    const uint32_t grid_max = (uint32_t)n_cu * 4u; // (persistent workgroups: three to four fit a CU)
+    const uint32_t grid = round < grid_max ? round : grid_max;
+    KMMCHK(ensure(s.cand, (size_t)grid * kmm_bz::CAND_STRIDE * 2));
+    KMMCHK(ensure(s.slots, (size_t)round * kmm_bz::SLOT));
+    KMMCHK(ensure(s.sizes, (size_t)round * 4));
+    KMMCHK(ensure(s.offs, ((size_t)round + 1) * 8));
+    if (!out_dev)
+        KMMCHK(ensure(s.comp, (size_t)round * kmm_bz::SLOT));
+    int64_t written = 0;
+    for (int64_t m0 = 0; m0 < n_members; m0 += round) {
+        const uint32_t nm = (uint32_t)(n_members - m0 < (int64_t)round ? n_members - m0 : (int64_t)round);
+        const int64_t first = m0 * (int64_t)kmm_bz::BLOCK;
+        const int64_t bytes = n - first < (int64_t)nm * kmm_bz::BLOCK ? n - first : (int64_t)nm * kmm_bz::BLOCK;
+        uint8_t *dst = out_dev ? out + written : (uint8_t *)s.comp.p;
+        ScopedTimer tm;
+        if (timed)
+            KMMCHK(tm.begin(timed, KMM_KERNEL_BGZF_DEFLATE));
+        hipLaunchKernelGGL(kmm_bz::k_bz_deflate, dim3(nm < grid ? nm : grid), dim3(256), 0, st, d_in + first, bytes, nm, d_crcT,
+                           (uint16_t *)s.cand.p, (uint8_t *)s.slots.p, (uint32_t *)s.sizes.p);
+        KMMCHK(tm.end());
+        if (timed)
+            KMMCHK(tm.begin(timed, KMM_KERNEL_BGZF_GATHER));
+        hipLaunchKernelGGL(kmm_bz::k_bz_offsets, dim3(1), dim3(1024), 0, st, (const uint32_t *)s.sizes.p, nm, (unsigned long long *)s.offs.p);
+        hipLaunchKernelGGL(kmm_bz::k_bz_gather, dim3(nm), dim3(256), 0, st, (const uint8_t *)s.slots.p, (const uint32_t *)s.sizes.p,
+                           (const unsigned long long *)s.offs.p, dst);
+        KMMCHK(tm.end());
+        HIPCHK(hipGetLastError());
+        unsigned long long total = 0;
+        HIPCHK(hipMemcpyAsync(&total, (const unsigned long long *)s.offs.p + nm, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if ((int64_t)total > kmm_bz::bound(bytes))
+            return fail(KMM_ERR_INTERNAL, "BGZF writer: %llu bytes of members for %lld bytes of text", total, (long long)bytes);
+        if (!out_dev) {
+            HIPCHK(hipMemcpyAsync(out + written, s.comp.p, (size_t)total, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        written += (int64_t)total;
+    }
+    *n_out = written;
+    return KMM_OK;
+}
+
+int64_t kmm_bgzf_bound(int64_t n)
+{
+    return kmm_bz::bound(n);
+}
+
+int kmm_take_kept_bgzf(kmm_index_t *ix, int mate, uint8_t *out, int64_t capacity, int64_t *n_comp, int64_t *n_bytes, int64_t *n_records)
+{
+    if (!ix || !n_comp || !n_bytes || !n_records)
+        return fail(KMM_ERR_INVALID_ARG, "NULL argument");
+    *n_comp = *n_bytes = *n_records = 0;
+    if (mate != 0 && mate != 1)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_bgzf: mate is %d: 0 (the queue of kmm_take_kept_records) or 1 (the mate-2 "
+                    "texts of kmm_map_record_pairs)", mate);
+    if (capacity < 0 || (capacity > 0 && !out))
+        return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_bgzf: capacity negative, or out is NULL");
+    HIPCHK(hipSetDevice(ix->device));
+    KMMCHK(drain(ix)); // (a sticky or deferred device error: returned, nothing taken)
+    kmm_index::RkQueue &q = ix->rkq[mate];
+    unsigned long long tail[2];
+    KMMCHK(rkq_tail(q, tail));
+    const int64_t need = kmm_bz::bound((int64_t)tail[0]);
+    if (capacity < need)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_take_kept_bgzf: %llu bytes of %llu records are pending, their members can need %lld "
+                    "bytes (kmm_bgzf_bound) and capacity is %lld: the queue is taken whole (nothing is taken)", tail[0], tail[1],
+                    (long long)need, (long long)capacity);
+    if (tail[0] > 0) {
+        KMMCHK(ensure_crc_tables(ix));
+        KMMCHK(bz_compress(ix->stream, ix->n_cu, ix->bz, (const uint32_t *)ix->bgzf_crc.p, (const uint8_t *)q.text.p, (int64_t)tail[0], out,
+                           n_comp, ix));
+        HIPCHK(hipMemset(q.ctl.p, 0, 16));
+    }
+    q.bound = 0;
+    *n_bytes = (int64_t)tail[0];
+    *n_records = (int64_t)tail[1];
+    return KMM_OK;
+}
+
+int kmm_bgzf_compress(int device, const uint8_t *in, int64_t n, uint8_t *out, int64_t capacity, int64_t *n_out)
+{
+    if (!n_out)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_bgzf_compress: n_out is NULL");
+    *n_out = 0;
+    if (n < 0 || capacity < 0)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_bgzf_compress: negative size");
+    if (capacity < kmm_bz::bound(n))
+        return fail(KMM_ERR_INVALID_ARG, "kmm_bgzf_compress: the members of %lld bytes can need %lld bytes (kmm_bgzf_bound) and "
+                    "capacity is %lld (nothing is written)", (long long)n, (long long)kmm_bz::bound(n), (long long)capacity);
+    if (n == 0)
+        return KMM_OK;
+    if (!in || !out)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_bgzf_compress: in / out is NULL");
+    int ndev = 0;
+    hipError_t e0 = hipGetDeviceCount(&ndev);
+    if (e0 != hipSuccess || ndev < 1) {
+        (void)hipGetLastError();
+        return fail(KMM_ERR_HIP, "no HIP device available: libkmm has no CPU fallback");
+    }
+    HIPCHK(hipSetDevice(device));
+    int n_cu = 0;
+    HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+    Stream st; // (destroyed after the buffers)
+    BzScratch s;
+    DevBuf d_in, d_crc;
+    HIPCHK(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
+    std::vector<uint32_t> t(kmm_gz::CRC_TABLE_WORDS);
+    for (int kk = 0; kk < 8; ++kk)
+        for (uint32_t bb = 0; bb < 256u; ++bb)
+            t[(size_t)kk * 256 + bb] = kmm_gz::crc_table_entry(kk, bb);
+    for (int kk = 0; kk < kmm_gz::CRC_SHIFT_WORDS; ++kk)
+        t[8 * 256 + kk] = kmm_gz::crc_shift_table_entry(kk);
+    KMMCHK(ensure(d_crc, t.size() * 4));
+    HIPCHK(hipMemcpyAsync(d_crc.p, t.data(), t.size() * 4, hipMemcpyHostToDevice, st));
+    const uint8_t *p_in = in;
+    if (!is_device_ptr(in)) {
+        KMMCHK(ensure(d_in, (size_t)n));
+        HIPCHK(hipMemcpyAsync(d_in.p, in, (size_t)n, hipMemcpyHostToDevice, st));
+        p_in = (const uint8_t *)d_in.p;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    const int rc = bz_compress(st, n_cu > 0 ? n_cu : 256, s, (const uint32_t *)d_crc.p, p_in, n, out, n_out, nullptr);
+    (void)hipStreamSynchronize(st);
+    return rc;
 }
 
 int kmm_extract_kmers(int device, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads,

@@ -483,6 +483,24 @@ class DeviceIndex:
                                                   ctypes.byref(n_bytes), ctypes.byref(n_records)))
         return buf[:n_bytes.value], n_records.value
 
+    def take_kept_bgzf(self, mate=0, out=None):
+        """kmm_take_kept_bgzf: take_kept_mates() with the queue's text compressed on the device — BGZF members of at
+        most 65280 bytes of text each, no end-of-file block — so that only the members cross the link.  Returns (np.uint8
+        array of members, n_text_bytes, n_records); with out (a uint8 array or torch tensor, host or device, at least
+        kmm_bgzf_bound(pending bytes) long) the members are written there and (n_member_bytes, n_text_bytes, n_records) is
+        returned."""
+        n_comp, n_bytes, n_records = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        refs = (ctypes.byref(n_comp), ctypes.byref(n_bytes), ctypes.byref(n_records))
+        if out is not None:
+            o = _Arg(out, np.uint8, "out")
+            _lib.check(_lib.lib().kmm_take_kept_bgzf(self._h, int(mate), o.ptr, o.n, *refs))
+            return n_comp.value, n_bytes.value, n_records.value
+        pending = self.get_param("record_keep_pending_bytes_mate2" if int(mate) == 1 else "record_keep_pending_bytes")
+        cap = int(_lib.lib().kmm_bgzf_bound(pending))
+        buf = np.empty(cap, dtype=np.uint8)
+        _lib.check(_lib.lib().kmm_take_kept_bgzf(self._h, int(mate), buf.ctypes.data_as(_P) if cap else None, cap, *refs))
+        return buf[:n_comp.value], n_bytes.value, n_records.value
+
     # -- measurement -----------------------------------------------------------------------------
     def set_timing(self, on=True):
         _lib.check(_lib.lib().kmm_set_timing(self._h, int(bool(on))))

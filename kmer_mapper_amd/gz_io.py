@@ -13,6 +13,7 @@ from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 
 _BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+BGZF_EOF = _BGZF_EOF                      # the empty member that ends a BGZF file; the device-side writer never appends it
 
 
 BGZF_MAGIC = b"\x1f\x8b\x08\x04"          # gzip, deflate, FEXTRA

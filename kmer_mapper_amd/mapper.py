@@ -145,7 +145,7 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
 
 
 def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
-                   min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False):
+                   min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False, compress=False):
     """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
     text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
     (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
@@ -153,7 +153,9 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     (DeviceIndex.record_keep / take_kept_records).  The mode is off again afterwards.
     fmt "bam": `raw` is a WHOLE BAM file held as bytes; its records — those whose FLAG has none of exclude_flags — are decoded on
     the GPU into four-line FASTQ that carries QNAME and QUAL (DeviceIndex.record_names), and the text returned is
-    that FASTQ.  original_strand: records with FLAG 0x10 in read orientation; mate_suffix: "/1" / "/2" behind the names."""
+    that FASTQ.  original_strand: records with FLAG 0x10 in read orientation; mate_suffix: "/1" / "/2" behind the names.
+    compress: the text comes back as a BGZF file's bytes — deflated on the GPU (DeviceIndex.take_kept_bgzf), the
+    end-of-file block appended."""
     from . import _lib
     if fmt != "bam" and (exclude_flags or original_strand or mate_suffix):
         raise ValueError("exclude_flags, original_strand and mate_suffix go with fmt=\"bam\"")
@@ -178,7 +180,11 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
         else:
             dev.map_records(raw, fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp, lut=lut)
         hits, windows = dev.take_record_hits()
-        text, _ = dev.take_kept_records()
+        if compress:
+            from .gz_io import BGZF_EOF
+            text = dev.take_kept_bgzf()[0].tobytes() + BGZF_EOF
+        else:
+            text = dev.take_kept_records()[0].tobytes()
     finally:
         if before is not None:                                                      # (the handle is cached: as it was found)
             dev.record_names(False)
@@ -186,18 +192,19 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
             dev.set_param("original_strand", before[1])
         dev.record_keep(False)
         dev.record_hits(False)
-    return text.tobytes(), hits, windows
+    return text, hits, windows
 
 
 def select_record_pairs(index, raw1, raw2=None, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None,
-                        min_hits=1, min_permille=0, invert=False, pair_rule="any", device=0):
+                        min_hits=1, min_permille=0, invert=False, pair_rule="any", device=0, compress=False):
     """Extension: select_records for paired-end reads, whose mates are kept or dropped together.  raw2 None: `raw1`
     holds the mates interleaved, records 2i and 2i + 1; else record i of raw1 and record i of raw2 are mates (fmt "fastq" or
     "fasta", two-line, the same for both; each of bytes, a uint8 array or a torch tensor, host or device).  Per mate, match is
     hits >= min_hits and 1000 * hits >= min_permille * windows; a pair matches when pair_rule "any" mate does, or only when
     "both" do, and is kept iff match != invert.  Returns (text1, text2, hits, windows): the kept records of raw1 and of raw2 in
     order — text2 None for interleaved input, whose kept pairs are text1 — and one entry per record of every whole pair, in pair
-    order (mate 1, mate 2).  Records behind the last whole pair are not looked at.  The cached handle is left as it was found."""
+    order (mate 1, mate 2).  Records behind the last whole pair are not looked at.  The cached handle is left as it was found.
+    compress: text1, and text2 where there is one, are the bytes of BGZF files — deflated on the GPU."""
     from . import _lib
     kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2}[fmt]
     as_array = lambda raw: np.frombuffer(bytes(raw), dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else raw
@@ -219,13 +226,18 @@ def select_record_pairs(index, raw1, raw2=None, fmt="fastq", k=31, max_index_loo
         else:
             dev.map_record_pairs(raw1, raw2, **common)
         hits, windows = dev.take_record_hits()
-        text1, _ = dev.take_kept_records()
+        if compress:
+            from .gz_io import BGZF_EOF
+            take = lambda mate: dev.take_kept_bgzf(mate)[0].tobytes() + BGZF_EOF
+        else:
+            take = lambda mate: dev.take_kept_mates(mate)[0].tobytes()
+        text1 = take(0)
         if raw2 is not None:
-            text2 = dev.take_kept_mates(1)[0].tobytes()
+            text2 = take(1)
     finally:
         dev.record_keep(False)
         dev.record_hits(False)
         dev.set_param("record_pairs_rule", before[1])
         if not dev.get_param("record_hits_pending"):                                   # (a failing call appended nothing)
             dev.set_param("record_pairs", before[0])
-    return text1.tobytes(), text2, hits, windows
+    return text1, text2, hits, windows

@@ -32,6 +32,24 @@ def ambiguous_skip_lut():
     return lut
 
 
+def bgzf_compress(data, device=0):
+    """kmm_bgzf_compress: the BGZF members of `data` (bytes, a uint8 numpy array or a torch tensor, host or
+    device), deflated on the GPU — one member per 65280 bytes, no end-of-file block (gz_io.BGZF_EOF ends a file).  Returns a
+    np.uint8 array; the bytes are a pure function of the data."""
+    import ctypes
+    from . import _lib
+    from .engine import _Arg
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        data = np.frombuffer(data, dtype=np.uint8)
+    src = _Arg(data, np.uint8, "data")
+    cap = int(_lib.lib().kmm_bgzf_bound(src.n))
+    out = np.empty(cap, dtype=np.uint8)
+    n_out = ctypes.c_int64(0)
+    _lib.check(_lib.lib().kmm_bgzf_compress(int(device), src.ptr, src.n, out.ctypes.data_as(ctypes.c_void_p) if cap else None, cap,
+                                            ctypes.byref(n_out)))
+    return out[:n_out.value]
+
+
 class ReadBatch:
     """A chunk of reads: `bases` uint8[sum(len)] (ASCII), `offsets` int64[n_reads+1].
 
