@@ -630,6 +630,28 @@ int kmm_take_kept_records(kmm_index_t *idx, uint8_t *out, int64_t capacity, int6
  *
  * kmm_take_kept_mates: mate 0 is kmm_take_kept_records, mate 1 the same contract on the second queue, anything else
  * KMM_ERR_INVALID_ARG.  Read-only "record_keep_pending_bytes_mate2", "record_keep_pending_records_mate2".
+ *
+ * THE MATES OF A BAM STREAM: "record_names_pairs" 0 (default) / 1 (anything else KMM_ERR_INVALID_ARG), read by
+ * kmm_map_bam alone.  With 1 — and "record_names" 1, "record_hits" 1 or 2, "record_keep" 1 — the SELECTED records of a stream, in
+ * file order, are mates: kept records 2p and 2p + 1 are pair p, as in a file grouped by name (unaligned BAM, an aligner's unsorted
+ * output, `samtools collate`).  The keep rule is the pair rule above over their two entries ("record_pairs_rule",
+ * "record_keep_invert" as there); the hits queue gains one entry per record in pair order, the first of a call at an even index;
+ * the kept text, interleaved four-line FASTQ in stored order, goes to the queue of kmm_take_kept_records / kmm_take_kept_bgzf.
+ * Windows need not hold whole pairs: the text of an odd last selected record waits on the handle for its mate in the next call,
+ * through windows without a selected or without a complete record; *n_records counts the records appended, an even number.
+ *   THE MATE CHECK: the names of every pair are compared on the device — what the decode wrote behind '@', after the '?'
+ *   replacement, equal in length and in bytes; with "record_names_mate_suffix" 1 a trailing "/1" or "/2" is left out of the
+ *   comparison.  (The one edge: a QNAME that itself ends in "/1" or "/2" while FLAG carries no mate bit loses those two bytes in
+ *   the comparison too — "x/1" and "x" then count as mates.)  The first pair whose names differ fails the call that decoded its
+ *   second record with KMM_ERR_MALFORMED; the message names the pair's ordinal in the stream and what to do: collate the file by
+ *   name and exclude secondary and supplementary records (0x900).  A coordinate-sorted file fails at its first pair of strangers.
+ *   A stream whose KMM_FORMAT_LAST_CHUNK call leaves a record without its mate fails with KMM_ERR_MALFORMED ("the stream ends
+ *   with an unpaired record", with the count of selected records).  A failing call leaves the hits queue, the text queues, the
+ *   waiting mate, the node counts, the statistics and the decode's counters as it found them; the stream cannot be continued.
+ *   kmm_reset_counts and KMM_FORMAT_NEW_STREAM drop a waiting mate.
+ * Refused with KMM_ERR_INVALID_ARG, nothing mapped, nothing appended: kmm_map_bam with "record_names_pairs" 1 while "record_names"
+ * or "record_keep" is 0, or together with "record_pairs" 1 (which stays refused on BAM input as above); a change of
+ * "record_names_pairs" while hit entries are pending.  With 0 every call launches exactly what it launched without the parameter.
  */
 int kmm_map_record_pairs(kmm_index_t *idx, const uint8_t *raw1, int64_t n1, const uint8_t *raw2, int64_t n2, int format, int k,
                          int max_freq, int also_revcomp, const uint8_t *lut, int64_t *consumed1, int64_t *consumed2, int64_t *n_pairs);
@@ -869,7 +891,9 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *   "record_names"     0 (default) / 1: in the record-hits mode kmm_map_bam decodes the selected records into four-line FASTQ with
  *                      their names and qualities — the text "record_keep" appends for BAM input; "record_names_mate_suffix"
  *                      0 (default) / 1: "/1" / "/2" behind the names.  Read-only "record_name_bytes_replaced".  See
- *                      kmm_take_kept_records, THE NAMED FORM
+ *                      kmm_take_kept_records, THE NAMED FORM.  "record_names_pairs" 0 (default) / 1: with "record_names" and
+ *                      "record_keep", the selected records of a kmm_map_bam stream are mates in file order (2p, 2p + 1), their
+ *                      names are compared on the device and they are kept or dropped together; see THE MATES OF A BAM STREAM
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_records_grid" test hook of kmm_map_records: workgroups (four wavefronts each) of the two per-tile kernels of the

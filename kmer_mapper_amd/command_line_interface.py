@@ -952,7 +952,7 @@ class RecordKeepSink(RecordHitsSink):
     BGZF members — every drain ends its last member; close() writes the end-of-file block; kept_bytes still counts text."""
 
     def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False, pairs=False, pair_rule="any",
-                 out2=None, bgzf=False):
+                 out2=None, bgzf=False, bam_pairs=False):
         super().__init__(windows=True)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
@@ -963,6 +963,8 @@ class RecordKeepSink(RecordHitsSink):
         # mates kept together: pairs: the stream is interleaved ("record_pairs"); out2: the file of the mate-2
         # texts of map_record_pairs, whose queue is drained with the other two
         self.pairs, self.pair_rule, self.out2 = bool(pairs), pair_rule, out2
+        # the mates of a name-collated BAM file: the named decode's records are mates in file order
+        self.bam_pairs = bool(bam_pairs)
         self.bgzf = bool(bgzf)
         self.written = 0                     # bytes written to out and out2 (the members' with bgzf, else the text's)
 
@@ -970,7 +972,9 @@ class RecordKeepSink(RecordHitsSink):
         super().open(dev)
         dev.record_keep(True, **self.rule)
         if self.names:
-            dev.record_names(True, mate_suffix=self.mate_suffix)
+            dev.record_names(True, mate_suffix=self.mate_suffix, **({"pairs": True} if self.bam_pairs else {}))
+        if self.bam_pairs:
+            dev.record_pairs(False, rule=self.pair_rule)
         if self.pairs or self.out2 is not None:
             dev.record_pairs(self.pairs, rule=self.pair_rule)
 
@@ -1040,6 +1044,19 @@ def check_select_reads_input(fmt, world_size, reads, output, bam_to_fastq=False,
                          % world_size)
     if os.path.abspath(str(output)) == os.path.abspath(str(reads)) or (os.path.exists(str(output)) and os.path.samefile(str(output), str(reads))):
         raise ValueError("select-reads: -o %s is the input file (-f): the output would overwrite the reads" % output)
+
+
+def check_select_reads_bam_pairs(fmt, bam_to_fastq=False, interleaved=False, reads2=None, output2=None):
+    """--bam-pairs of `kmer_mapper select-reads`: a name-collated BAM file whose mates are kept together.  What
+    does not go with it is refused before the index is read and before -o is created."""
+    if fmt != "bam":
+        raise ValueError("--bam-pairs applies to BAM input only (the reads are %s; interleaved FASTQ has --interleaved)" % fmt)
+    if not bam_to_fastq:
+        raise ValueError("select-reads: --bam-pairs goes with --bam-to-fastq: the kept mates are written as interleaved FASTQ")
+    for given, opt in ((interleaved, "--interleaved"), (reads2 is not None, "-f2/--reads2"), (output2 is not None, "-o2/--output2")):
+        if given:
+            raise ValueError("select-reads: --bam-pairs does not go with %s: the mates lie in one BAM file (-f) and leave as one "
+                             "interleaved FASTQ file (-o)" % opt)
 
 
 def _same_file(a, b):
@@ -1154,7 +1171,10 @@ def select_reads_file(args):
     probe = probe_input(args.reads)
     interleaved, reads2, output2 = bool(getattr(args, "interleaved", False)), getattr(args, "reads2", None), getattr(args, "output2", None)
     pair_rule = getattr(args, "pair_rule", None)
-    check_select_reads_pairs(probe, args.reads, args.output_file, interleaved, reads2, output2, pair_rule)
+    bam_pairs = bool(getattr(args, "bam_pairs", False))
+    if bam_pairs:
+        check_select_reads_bam_pairs(probe.fmt, bool(getattr(args, "bam_to_fastq", False)), interleaved, reads2, output2)
+    check_select_reads_pairs(probe, args.reads, args.output_file, interleaved, reads2, output2, None if bam_pairs else pair_rule)
     bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None)]
     check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options)
     if not 0 <= args.min_hit_permille <= 1000:
@@ -1171,6 +1191,11 @@ def select_reads_file(args):
         select = check_record_select(fmt, include_flags=opt("include_flags", 0), min_mapq=opt("min_mapq", 0), regions=opt("regions"),
                                      regions_file=opt("regions_file"))
         exclude_flags = int(opt("exclude_flags", 0) or 0)
+        if bam_pairs:
+            # (a secondary or supplementary record between two mates would be taken for one of them: DESIGN 4.23)
+            logging.info("select-reads --bam-pairs: secondary and supplementary records are excluded (--exclude-flags 0x%x | 0x900 "
+                         "= 0x%x)", exclude_flags, exclude_flags | 0x900)
+            exclude_flags |= 0x900
         _check_bam_route(fmt, 1, exclude_flags)
         more = dict(exclude_flags=exclude_flags, original_strand=check_original_strand(not opt("as_stored", False), fmt),
                     **({"record_select": select} if select else {}))
@@ -1183,8 +1208,9 @@ def select_reads_file(args):
     kmer_index = _get_kmer_index_from_args(args)
     if fmt == "fasta" and not probe.two_line:
         fmt = "fasta_ml"
-    logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes%s",
-                 "; BAM records decoded to FASTQ with their names (--bam-to-fastq)" if bam else "")
+    logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes%s%s",
+                 "; BAM records decoded to FASTQ with their names (--bam-to-fastq)" if bam else "",
+                 "; neighbouring records are mates, kept together, pair rule '%s' (--bam-pairs)" % (pair_rule or "any") if bam_pairs else "")
     rule = dict(min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert,
                 bgzf=bool(getattr(args, "bgzf", False)))
     if reads2 is not None:
@@ -1198,7 +1224,7 @@ def select_reads_file(args):
     else:
         with open(args.output_file, "wb") as out:
             sink = RecordKeepSink(out, names=bam, mate_suffix=bam and bool(getattr(args, "mate_suffix", False)), pairs=interleaved,
-                                  pair_rule=pair_rule or "any", **rule)
+                                  pair_rule=pair_rule or "any", bam_pairs=bam_pairs, **rule)
             try:
                 map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
                             device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more)
@@ -1398,6 +1424,12 @@ def build_argument_parser():
     sub.add_argument("--pair-rule", choices=("any", "both"), default=argparse.SUPPRESS,
                      help="With --interleaved or -f2: a pair matches when any of its mates passes --min-hits / --min-hit-permille "
                           "(default), or only when both do; --invert then flips the pair's outcome.")
+    sub.add_argument("--bam-pairs", action="store_true", default=argparse.SUPPRESS,
+                     help="With --bam-to-fastq: the BAM file is grouped by name (as it leaves the sequencer or an aligner, or after "
+                          "`samtools collate`): neighbouring records are mates, both kept or both dropped (--pair-rule), and -o is "
+                          "interleaved FASTQ. Secondary and supplementary records (0x900) are excluded; the names of every pair are "
+                          "compared on the GPU, and neighbours that are no mates (a coordinate-sorted file) or a last record without "
+                          "its mate are an error.")
     sub.add_argument("--bgzf", action="store_true", default=argparse.SUPPRESS,
                      help="Write -o (and -o2) as BGZF files: the kept text is deflated on the GPU, one member per 65280 bytes, and "
                           "only the members are copied to the host. Without it the output is plain text, whatever -o is called.")

@@ -465,6 +465,16 @@ struct kmm_index : IndexStreams, RxArrays {
     int record_pairs = 0, rk_pair_rule = 0;
     struct { int64_t pending = 0, bound = 0; bool valid = false; } rk_snap;
     DevBuf rk_pair_entries;
+    // the mates of a name-collated BAM file: "record_names_pairs" 1: the selected records of a kmm_map_bam stream
+    // are mates in file order, 2p and 2p + 1.  bam_mate: the text of a window's odd last selected record, which the next window's
+    // decode writes behind (bam_mate_len bytes; 0: none); bam_pairs_done: pairs of the stream handed over so far (the ordinals
+    // of the error reports).  rk_mates_call: set around kmm_map_bam's inner kmm_map_records alone — that call then takes the
+    // interleaved pair form without "record_pairs", and every piece has its pairs' names compared (k_rk_pair_names), the first
+    // differing pair read back through rk_names_ctl (behind it: the decode's three counters as the call found them).
+    int record_names_pairs = 0;
+    bool rk_mates_call = false;
+    DevBuf bam_mate, rk_names_ctl;
+    int64_t bam_mate_len = 0, bam_pairs_done = 0;
     BzScratch bz; // kmm_take_kept_bgzf
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
@@ -1103,7 +1113,29 @@ int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam, bo
 // Are the records of a FASTQ / two-line FASTA stream taken as interleaved mates?
 bool record_pairs_on(const kmm_index *ix)
 {
-    return ix->record_hits && ix->record_keep && ix->record_pairs;
+    return ix->record_hits && ix->record_keep && (ix->record_pairs || ix->rk_mates_call);
+}
+
+// Are the selected records of a kmm_map_bam stream taken as mates ("record_names_pairs")?
+bool bam_mates_on(const kmm_index *ix)
+{
+    return ix->record_names_pairs && ix->record_names && ix->record_hits && ix->record_keep;
+}
+
+// The mate check of one piece of kmm_map_bam's inner records call: *bad is the first pair of the piece (its ordinal inside the
+// piece) whose two names differ, 0xFFFFFFFF when all agree.  One small read-back per piece, behind everything the piece queued.
+int pair_names_piece(kmm_index *ix, const ReadsView &rv, int64_t consumed, uint32_t *bad)
+{
+    const int64_t n_tiles = (consumed + 1023) / 1024;
+    KMMCHK(ensure(ix->rk_names_ctl, 64));
+    uint32_t *d_bad = (uint32_t *)ix->rk_names_ctl.p;
+    HIPCHK(hipMemsetAsync(d_bad, 0xFF, 4, ix->stream));
+    hipLaunchKernelGGL(k_rk_pair_names, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, ix->stream, rv.bases, consumed, n_tiles,
+                       (const uint32_t *)rv.tile_nl, (const uint32_t *)rv.super_nl, ix->record_names_mate_suffix ? 1u : 0u, d_bad);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(bad, d_bad, 4, hipMemcpyDeviceToHost, ix->stream));
+    HIPCHK(hipStreamSynchronize(ix->stream));
+    return KMM_OK;
 }
 
 // Room for n more bytes behind q.bound pending ones, made before a piece's kernels are launched (n: its consumed bytes, more
@@ -1521,6 +1553,7 @@ int kmm_reset_counts(kmm_index_t *ix)
         q.bound = 0;
     }
     ix->rk_snap.valid = false;
+    ix->bam_mate_len = ix->bam_pairs_done = 0; // (a mate 1 that waits for its mate belongs to the entries just dropped: DESIGN 4.23)
     // ("record_name_bytes_replaced" counts bytes of the text that queue held: it restarts with it.  The named decode adds to the
     // first shard alone; the other statistics stay, as before, until kmm_get_stats(reset).)
     HIPCHK(hipMemsetAsync(ix->stats + KMM_STAT_REC_NAME_REPLACED, 0, sizeof(unsigned long long), ix->stream));
@@ -2714,6 +2747,20 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
                 KMMCHK(record_keep_piece<2>(ix, ix->rkq[0], rv, n_bytes, out[0], out[1], q_hits, q_win));
             else if (ix->record_keep)
                 KMMCHK(record_keep_piece<0>(ix, ix->rkq[0], rv, n_bytes, out[0], out[1], q_hits, q_win));
+            if (pairs && ix->rk_mates_call) {
+                // (the text is kmm_map_bam's — neighbours that are no mates fail the call, which puts back what
+                // its pieces appended)
+                uint32_t bad = 0xFFFFFFFFu;
+                KMMCHK(pair_names_piece(ix, rv, out[0], &bad));
+                if (bad != 0xFFFFFFFFu) {
+                    const long long p = (long long)(ix->bam_pairs_done + (int64_t)bad);
+                    (void)stage_release(ix, s, false);
+                    return fail(KMM_ERR_MALFORMED, "kmm_map_bam: \"record_names_pairs\" is 1 and pair %lld of the stream is none: records "
+                                "%lld and %lld are not mates: collate the file by name (`samtools collate`) and exclude secondary and "
+                                "supplementary records (0x900) (nothing of the call is appended)", p, 2 * p, 2 * p + 1);
+                }
+                ix->bam_pairs_done += out[1] / 2;
+            }
         } else if (has_break) // (a break byte on a sequence line: a break like the bytes outside the sequence lines)
             KMMCHK(launch_map_reads<MODE_RECORDS_BRK>(ix, rv, k, max_freq, also_revcomp ? 1 : 0));
         else
@@ -3954,6 +4001,86 @@ struct BamGpuBackend {
     }
 };
 
+// "The stream ends with an unpaired record" (DESIGN 4.23): a mate 1 is left when the stream's last call has nothing more for it.
+static int bam_mates_unpaired(long long n_selected)
+{
+    return fail(KMM_ERR_MALFORMED, "kmm_map_bam: \"record_names_pairs\" is 1 and the stream ends with an unpaired record: it holds %lld "
+                "selected records, the last one has no mate (a selection that removes one mate of a pair is an error here; nothing of "
+                "the call is appended)", n_selected);
+}
+
+// The selected records of a kmm_map_bam window as mates ("record_names_pairs"), behind run_call: the window's
+// records are decoded BEHIND the text of the mate 1 that the window before left over, and the inner records call takes
+// carry + decoded text in the interleaved pair form (rk_mates_call: whole pairs only, the names of every pair compared).  An odd
+// last record's text stays unconsumed and becomes the next carry.  A call that fails leaves the carry, the ordinals, the queues
+// and the counters as it found them.
+static int bam_map_mates(kmm_index_t *ix, const StreamCall &c, BamGpuBackend &be, const kmm_bam::CallOut &co, int64_t n_raw)
+{
+    const int64_t carry = ix->bam_mate_len, pairs0 = ix->bam_pairs_done;
+    const int64_t n_rec = (int64_t)co.recs + (carry > 0 ? 1 : 0), n_text = carry + (int64_t)co.out_bytes;
+    const bool decoded = co.recs > 0;
+    unsigned long long *d_counters = nullptr; // (no-qual, reversed, replaced: neighbours in the first shard of the statistics)
+    static_assert(KMM_STAT_REC_REVERSED == KMM_STAT_REC_NO_QUAL + 1 && KMM_STAT_REC_NAME_REPLACED == KMM_STAT_REC_NO_QUAL + 2, "one copy");
+    auto put_back = [&](bool queues) {
+        const std::string msg = g_err;
+        ix->bam_pairs_done = pairs0;
+        ix->bam_calls--;
+        ix->bam_records -= (int64_t)co.recs;
+        ix->bam_excluded -= (int64_t)co.excluded;
+        ix->bam_false_starts -= (int64_t)co.false_starts;
+        ix->bam_continuations -= (int64_t)co.continuations;
+        if (d_counters && hipMemcpyAsync(ix->stats + KMM_STAT_REC_NO_QUAL, d_counters, 24, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess)
+            (void)hipGetLastError();
+        if (queues && ix->rk_snap.valid) { // (what the inner call appended: as keep_carry puts back an unpaired end of a text stream)
+            ix->rhq_pending = ix->rk_snap.pending;
+            rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
+        }
+        ix->rk_snap.valid = false;
+        g_err = msg;
+    };
+    ix->rk_snap.valid = false;
+    int64_t taken = 0, recs = 0;
+    if (decoded) {
+        KMMCHK(ensure(ix->rk_names_ctl, 64));
+        KMMCHK(ensure(ix->bam_out, (size_t)n_text + 64));
+        d_counters = (unsigned long long *)((uint8_t *)ix->rk_names_ctl.p + 16);
+        HIPCHK(hipMemcpyAsync(d_counters, ix->stats + KMM_STAT_REC_NO_QUAL, 24, hipMemcpyDeviceToDevice, ix->stream));
+        if (carry > 0)
+            HIPCHK(hipMemcpyAsync(ix->bam_out.p, ix->bam_mate.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream));
+        KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p + carry));
+        if (n_rec >= 2) {
+            ix->rk_mates_call = true;
+            const int rc = kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, n_text, KMM_FORMAT_FASTQ, c.k, c.max_freq, c.also_revcomp, c.lut,
+                                           &taken, &recs);
+            ix->rk_mates_call = false;
+            if (rc != KMM_OK) { // (the inner call has put its own entries and text back)
+                put_back(false);
+                return rc;
+            }
+            if (recs != (n_rec & ~(int64_t)1) || ((n_rec & 1) == 0 && taken != n_text) || taken > n_text) {
+                put_back(true);
+                return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %lld decoded bytes, %lld of %lld records mapped as pairs", (long long)taken,
+                            (long long)n_text, (long long)recs, (long long)n_rec);
+            }
+        }
+    }
+    const int64_t left = decoded ? n_text - taken : carry; // the text of a mate 1 whose mate has not come
+    if (c.last_chunk && left > 0) {
+        const long long n_selected = (long long)(2 * ix->bam_pairs_done + 1);
+        put_back(true);
+        return bam_mates_unpaired(n_selected);
+    }
+    if (decoded && left > 0) {
+        KMMCHK(ensure(ix->bam_mate, (size_t)left + 64)); // (may free and reallocate: a device-wide sync, rare)
+        HIPCHK(hipMemcpyAsync(ix->bam_mate.p, (const uint8_t *)ix->bam_out.p + taken, (size_t)left, hipMemcpyDeviceToDevice, ix->stream));
+    }
+    if (decoded)
+        ix->bam_mate_len = left;
+    if (c.n_records)
+        *c.n_records = recs;
+    return KMM_OK;
+}
+
 // The inflated bytes of a kmm_map_bam call (d_raw[0, n_raw): the carry of the call before in front): the header on a stream's
 // first call, then the records up to the last complete one (*used), decoded into two-line FASTA in HBM and mapped by
 // kmm_map_records.  *short_header: a first window that ends inside the header (nothing is used).
@@ -4026,6 +4153,8 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     ix->bam_records += (int64_t)co.recs;
     ix->bam_excluded += (int64_t)co.excluded;
     *used = (int64_t)co.consumed;
+    if (bam_mates_on(ix))
+        return bam_map_mates(ix, c, be, co, n_raw);
     if (co.recs == 0)
         return KMM_OK;
     KMMCHK(ensure(ix->bam_out, (size_t)co.out_bytes + 64));
@@ -4048,10 +4177,23 @@ int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags,
     StreamCall c{"kmm_map_bam", k, max_freq, also_revcomp, lut, consumed_comp, n_records};
     return guarded(c.who, [&] {
         KMMCHK(stream_call_start(ix, c, comp, n_comp, flags, false, true));
+        // ("record_names_pairs", DESIGN 4.23: read here alone)
+        if (ix->record_names_pairs && (!ix->record_names || !ix->record_keep))
+            return fail(KMM_ERR_INVALID_ARG, "kmm_map_bam: \"record_names_pairs\" is 1 and \"%s\" is 0: mates are kept together in the "
+                        "named FASTQ form of the decode under the keep rule, set \"record_names\" and \"record_keep\" to 1, or "
+                        "\"record_names_pairs\" to 0 (nothing is mapped)", ix->record_names ? "record_keep" : "record_names");
+        if (ix->record_names_pairs && ix->record_pairs)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_map_bam: \"record_names_pairs\" and \"record_pairs\" are 1: the first pairs the records "
+                        "of a BAM stream, the second those of FASTQ and two-line FASTA text; set one of them to 0 (nothing is mapped)");
+        if (c.new_stream)
+            ix->bam_mate_len = ix->bam_pairs_done = 0; // (a mate 1 left over belongs to the stream before)
         BgzfCall b;
         KMMCHK(bgzf_inflate(ix, c, comp, n_comp, b, bgzf_rank_share));
-        if (!b.d_raw)
+        if (!b.d_raw) { // (no member and no carried byte: a last call that brings nothing can still leave a mate 1 alone)
+            if (c.last_chunk && bam_mates_on(ix) && ix->bam_mate_len > 0)
+                return bam_mates_unpaired((long long)(2 * ix->bam_pairs_done + 1));
             return KMM_OK;
+        }
         int64_t used = 0;
         bool short_header = false;
         const int rc = bam_map_inflated(ix, c, b.d_raw, b.head, b.tail_stop, b.n_raw, &used, &short_header);
@@ -5373,6 +5515,16 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
                         "them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
                         (long long)ix->rhq_pending, ix->record_pairs);
         ix->record_pairs = (int)value;
+    } else if (!strcmp(name, "record_names_pairs")) {
+        // 1: kmm_map_bam with "record_names" and "record_keep" takes the selected records of a stream as mates in file order —
+        // 2p and 2p + 1 — checks that their names agree and keeps or drops them together; even counts, as "record_pairs"
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "record_names_pairs takes 0 or 1");
+        if ((int)value != ix->record_names_pairs && ix->rhq_pending > 0)
+            return fail(KMM_ERR_INVALID_ARG, "record_names_pairs %lld with %lld entries pending that were appended under record_names_pairs "
+                        "%d: take them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
+                        (long long)ix->rhq_pending, ix->record_names_pairs);
+        ix->record_names_pairs = (int)value;
     } else if (!strcmp(name, "record_pairs_rule")) {
         if (value != (int64_t)RK_PAIR_ANY && value != (int64_t)RK_PAIR_BOTH)
             return fail(KMM_ERR_INVALID_ARG, "record_pairs_rule takes 0 (a pair matches when any mate does) or 1 (when both do)");
@@ -5484,6 +5636,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->rk_min_permille;
     else if (!strcmp(name, "record_keep_invert"))
         *value = ix->rk_invert;
+    else if (!strcmp(name, "record_names_pairs"))
+        *value = ix->record_names_pairs;
     else if (!strcmp(name, "record_pairs"))
         *value = ix->record_pairs;
     else if (!strcmp(name, "record_pairs_rule"))

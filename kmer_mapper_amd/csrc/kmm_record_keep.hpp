@@ -8,6 +8,7 @@
 //   k_rk_advance   the queue's tail moves behind the piece's bytes and records
 // Mates kept together: k_rk_flags and k_rk_scatter are templates over PAIR — 0 is the code above, 1 and 2 ask the
 // pair rule of the two entries of a record's pair — and k_rk_zip puts the entries of two buffers into the queue in pair order.
+// The mates of a BAM stream: k_rk_pair_names compares the two name lines of every pair of the named decode's text.
 // The arithmetic is plain C++ (KMM_RH_HD): the CPU tier compiles this header with g++.
 #pragma once
 
@@ -120,6 +121,37 @@ KMM_RH_HD RkSpan rk_span(uint32_t a, uint32_t len)
     if (s.full_end < s.full_begin)
         s.full_end = s.full_begin; // (a span inside one line: no whole line)
     return s;
+}
+
+// The mate check: the two name lines of a pair of the named BAM decode's text, lines 8p and 8p + 4.
+// A name is what stands behind '@'; with the mate suffix on, a trailing "/1" or "/2" is left out of the comparison (so is one
+// that the QNAME itself ends in while FLAG carries no mate bit: include/kmm.h).
+KMM_RH_HD uint32_t rk_name_trim(const uint8_t *name, uint32_t len, bool mate_suffix)
+{
+    if (mate_suffix && len >= 2u && name[len - 2u] == (uint8_t)'/' && (name[len - 1u] == (uint8_t)'1' || name[len - 1u] == (uint8_t)'2'))
+        return len - 2u;
+    return len;
+}
+
+// Equal: equal length and equal bytes, behind the trim.
+KMM_RH_HD bool rk_names_equal(const uint8_t *a, uint32_t len_a, const uint8_t *b, uint32_t len_b, bool mate_suffix)
+{
+    const uint32_t la = rk_name_trim(a, len_a, mate_suffix), lb = rk_name_trim(b, len_b, mate_suffix);
+    if (la != lb)
+        return false;
+    for (uint32_t i = 0; i < la; ++i)
+        if (a[i] != b[i])
+            return false;
+    return true;
+}
+
+// Where mate 2's name line starts, from mate 1's alone: at: its '@'; name_end, seq_end: the newlines that end its name line and
+// its SEQ line.  The decode writes SEQ and QUAL of one length, so no newline behind seq_end has to be looked for:
+// '@' name '\n' | SEQ '\n' | "+\n" | QUAL '\n' | '@' of mate 2.
+KMM_RH_HD int64_t rk_mate2_line(int64_t at, int64_t name_end, int64_t seq_end)
+{
+    const int64_t name = name_end - at, l_seq = seq_end - name_end - 1;
+    return at + name + 1 + 2 * (l_seq + 1) + 2;
 }
 
 #if defined(__HIPCC__)
@@ -270,6 +302,117 @@ __global__ void __launch_bounds__(256) k_rk_zip(const uint32_t *__restrict__ mat
         e[0] = mate1[i];
         e[1] = mate2[i];
         *reinterpret_cast<u32x2 *>(out + 2 * i) = e;
+    }
+}
+
+// ---- the mate check: are records 2p and 2p + 1 of the named BAM decode's text mates — do their names agree?
+// A lane's 16 bytes at piece position p; what lies at or behind `limit` reads as zero (and is not read).
+__device__ __forceinline__ void rk_load16(const uint8_t *__restrict__ raw, int64_t p, int64_t limit, uint32_t (&w)[4])
+{
+    w[0] = w[1] = w[2] = w[3] = 0u;
+    if (p + 16 <= limit) {
+        u32x4 x;
+        __builtin_memcpy(&x, raw + p, 16);
+        w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; w[3] = x[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (p + j < limit)
+                w[j >> 2] |= (uint32_t)raw[p + j] << (8 * (j & 3));
+    }
+}
+
+// The whole wavefront looks for the first `want` (1 or 2) newlines at or behind `from` and before `limit`, 1024 bytes a round:
+// e[t] is newline t's position in every lane, -1 where the bytes end first.  from, limit and want are the same in all lanes.
+__device__ __forceinline__ void rk_wave_newlines(const uint8_t *__restrict__ raw, int64_t from, int64_t limit, int lane, uint32_t want,
+                                                 int64_t (&e)[2])
+{
+    e[0] = e[1] = -1;
+    uint32_t seen = 0;
+    for (int64_t base = from; base < limit && seen < want; base += 1024) {
+        uint32_t w[4], nl, cr;
+        rk_load16(raw, base + lane * 16, limit, w);
+        rec_masks(w, nl, cr);
+        const uint32_t cnt = (uint32_t)__popc(nl), incl = wave_scan_incl(cnt), before = seen + incl - cnt;
+#pragma unroll
+        for (uint32_t t = 0; t < 2u; ++t) {
+            const bool mine = t < want && before <= t && t < before + cnt; // (newline t of the search is one of this lane's)
+            const unsigned long long who = __ballot(mine);
+            if (who) {
+                uint32_t m = nl;
+                for (uint32_t i = before; mine && i < t; ++i)
+                    m &= m - 1u;
+                const int off = lane * 16 + (mine ? __builtin_ctz(m) : 0);
+                e[t] = base + __shfl(off, __builtin_ctzll(who));
+            }
+        }
+        seen += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    }
+}
+
+// One wavefront per 1024-byte tile of the piece's consumed bytes, as the keep kernels; tile_nl / super_nl: the newline census
+// (the line of every byte).  Every '@' that starts a line 8p inside the tile is a pair's: the wavefront finds the ends of mate 1's
+// name and SEQ lines, steps to mate 2's name line by arithmetic (rk_mate2_line), finds its end, and compares the names 64 bytes a
+// round.  Nothing at or behind `consumed` is read: the pairs in front of it are whole.  first_bad: the piece's first pair
+// (ordinal inside the piece) whose names differ — or whose text is not what the decode writes — else 0xFFFFFFFF as it was set.
+__global__ void __launch_bounds__(256) k_rk_pair_names(const uint8_t *__restrict__ raw, int64_t consumed, int64_t n_tiles,
+                                                       const uint32_t *__restrict__ tile_nl, const uint32_t *__restrict__ super_nl,
+                                                       uint32_t mate_suffix, uint32_t *__restrict__ first_bad)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= n_tiles)
+        return;
+    const int64_t p = tile * 1024 + lane * 16;
+    uint32_t w[4], nl, cr;
+    rk_load16(raw, p, consumed, w);
+    rec_masks(w, nl, cr);
+    const uint32_t cnt = (uint32_t)__popc(nl);
+    const uint32_t line0 = super_nl[tile >> 10] + tile_nl[tile] + wave_scan_incl(cnt) - cnt;
+    // a line's first byte: behind a newline, or the piece's first
+    uint32_t prev = (uint32_t)__shfl_up((int)(nl >> 15), 1) & 1u;
+    if (lane == 0)
+        prev = tile == 0 || raw[p - 1] == (uint8_t)'\n' ? 1u : 0u;
+    const uint32_t starts = ((nl << 1) | prev) & 0xFFFFu;
+    uint32_t first = 0; // ... of those the first bytes of the lines 8p
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+        if (((starts >> j) & 1u) && p + j < consumed && (rh_line_of_byte(line0, nl, j) & 7u) == 0u)
+            first |= 1u << j;
+    for (;;) {
+        const unsigned long long who = __ballot(first != 0u);
+        if (!who)
+            break;
+        const int src = __builtin_ctzll(who);
+        const int j_own = first ? __builtin_ctz(first) : 0;
+        const int j = __shfl(j_own, src);
+        const uint32_t pair = (uint32_t)__shfl((int)rh_line_of_byte(line0, nl, j_own), src) >> 3;
+        if (lane == src)
+            first &= first - 1u;
+        const int64_t at = tile * 1024 + src * 16 + j;
+        int64_t e[2], f[2];
+        rk_wave_newlines(raw, at, consumed, lane, 2u, e);
+        bool bad = raw[at] != (uint8_t)'@' || e[1] < 0;
+        int64_t at2 = 0;
+        if (!bad) {
+            at2 = rk_mate2_line(at, e[0], e[1]);
+            bad = at2 >= consumed || raw[at2 - 1] != (uint8_t)'\n' || raw[at2] != (uint8_t)'@';
+        }
+        if (!bad) {
+            rk_wave_newlines(raw, at2, consumed, lane, 1u, f);
+            bad = f[0] < 0;
+        }
+        if (!bad) {
+            const uint8_t *a = raw + at + 1, *b = raw + at2 + 1;
+            const uint32_t la = rk_name_trim(a, (uint32_t)(e[0] - at - 1), mate_suffix != 0u);
+            const uint32_t lb = rk_name_trim(b, (uint32_t)(f[0] - at2 - 1), mate_suffix != 0u);
+            bool differ = la != lb;
+            for (uint32_t i = (uint32_t)lane; !differ && i < la; i += 64u)
+                differ = a[i] != b[i];
+            bad = __ballot(differ) != 0ull;
+        }
+        if (bad && lane == 0)
+            atomicMin(first_bad, pair);
     }
 }
 

@@ -417,12 +417,16 @@ class DeviceIndex:
         self.set_param("record_keep_invert", int(bool(invert)))
         self.set_param("record_keep", int(bool(on)))
 
-    def record_names(self, on=True, mate_suffix=False):
+    def record_names(self, on=True, mate_suffix=False, pairs=False):
         """The named form of the BAM decode (include/kmm.h), on top of record_hits(): map_bam decodes every selected
         record into four-line FASTQ that carries the read's name and qualities ('@' NAME '\\n' SEQ '\\n' "+\\n" QUAL '\\n') instead
         of ">\\n" SEQ — the text record_keep() appends for BAM input.  Name bytes outside '!' .. '~' are written as '?'
         (get_param("record_name_bytes_replaced")); records without qualities get '"' per base.  mate_suffix: "/1" behind the
-        name of a record whose FLAG has 0x40 and not 0x80, "/2" for 0x80 and not 0x40.  The text routes never read it."""
+        name of a record whose FLAG has 0x40 and not 0x80, "/2" for 0x80 and not 0x40.  The text routes never read it.
+        pairs (with record_keep()): the selected records of a map_bam stream are mates in file order — 2p and 2p + 1,
+        as in a name-collated file — kept or dropped together under record_pairs()'s rule; their names are compared on the GPU
+        and a pair of strangers, or an unpaired last record, fails the call.  Refused while hit entries are pending."""
+        self.set_param("record_names_pairs", int(bool(on and pairs)))
         self.set_param("record_names_mate_suffix", int(bool(mate_suffix)))
         self.set_param("record_names", int(bool(on)))
 

@@ -145,7 +145,8 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
 
 
 def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
-                   min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False, compress=False):
+                   min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False, compress=False, pairs=False,
+                   pair_rule="any"):
     """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
     text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
     (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
@@ -155,10 +156,18 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     the GPU into four-line FASTQ that carries QNAME and QUAL (DeviceIndex.record_names), and the text returned is
     that FASTQ.  original_strand: records with FLAG 0x10 in read orientation; mate_suffix: "/1" / "/2" behind the names.
     compress: the text comes back as a BGZF file's bytes — deflated on the GPU (DeviceIndex.take_kept_bgzf), the
-    end-of-file block appended."""
+    end-of-file block appended.
+    pairs (fmt "bam"): the file is name-collated — its selected records are mates in file order, 2p and 2p + 1 — and
+    mates are kept or dropped together: a pair matches when pair_rule "any" mate does, or only when "both" do.  The text is
+    interleaved FASTQ, the entries lie in pair order.  Neighbours whose names differ, or an unpaired last record, raise
+    ValueError with the library's hint (collate by name; exclude secondary and supplementary records, 0x900)."""
     from . import _lib
     if fmt != "bam" and (exclude_flags or original_strand or mate_suffix):
         raise ValueError("exclude_flags, original_strand and mate_suffix go with fmt=\"bam\"")
+    if pairs and fmt != "bam":
+        raise ValueError("pairs goes with fmt=\"bam\" (interleaved FASTQ / FASTA text: select_record_pairs)")
+    if pair_rule not in ("any", "both"):
+        raise ValueError("pair_rule must be 'any' or 'both', not %r" % (pair_rule,))
     kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "sam": _lib.FORMAT_SAM, "bam": 0}[fmt]
     if isinstance(raw, (bytes, bytearray, memoryview)):
         raw = np.frombuffer(bytes(raw), dtype=np.uint8)
@@ -171,10 +180,12 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     before = None
     try:
         if fmt == "bam":
-            before = (dev.get_param("bam_exclude_flags"), dev.get_param("original_strand"))
+            before = (dev.get_param("bam_exclude_flags"), dev.get_param("original_strand"), dev.get_param("record_pairs_rule"))
             dev.set_param("bam_exclude_flags", int(exclude_flags))
             dev.set_param("original_strand", int(bool(original_strand)))
-            dev.record_names(True, mate_suffix=mate_suffix)
+            if pairs:
+                dev.set_param("record_pairs_rule", dev.PAIR_RULES[pair_rule])
+            dev.record_names(True, mate_suffix=mate_suffix, pairs=pairs)
             dev.map_bam(raw, first=True, last=True, k=k, max_index_lookup_frequency=max_index_lookup_frequency,
                         also_revcomp=also_revcomp, lut=lut)
         else:
@@ -187,9 +198,13 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
             text = dev.take_kept_records()[0].tobytes()
     finally:
         if before is not None:                                                      # (the handle is cached: as it was found)
-            dev.record_names(False)
+            if pairs and dev.get_param("record_hits_pending"):                      # (a take that failed: the switch stays with its entries)
+                dev.set_param("record_names", 0)
+            else:
+                dev.record_names(False)
             dev.set_param("bam_exclude_flags", before[0])
             dev.set_param("original_strand", before[1])
+            dev.set_param("record_pairs_rule", before[2])
         dev.record_keep(False)
         dev.record_hits(False)
     return text, hits, windows
