@@ -652,7 +652,33 @@ int kmm_take_kept_records(kmm_index_t *idx, uint8_t *out, int64_t capacity, int6
  * Refused with KMM_ERR_INVALID_ARG, nothing mapped, nothing appended: kmm_map_bam with "record_names_pairs" 1 while "record_names"
  * or "record_keep" is 0, or together with "record_pairs" 1 (which stays refused on BAM input as above); a change of
  * "record_names_pairs" while hit entries are pending.  With 0 every call launches exactly what it launched without the parameter.
+ *
+ * THE RAW FORM: BAM RECORDS KEPT AS BAM RECORDS.  "record_bam" 0 (default) / 1 (anything else KMM_ERR_INVALID_ARG),
+ * read by kmm_map_bam alone; the text routes and KMM_FORMAT_SAM never read it.  With 1 — and "record_hits" 1 or 2, "record_keep" 1 —
+ * the selected records of a call are decoded in the two-line FASTA form ("original_strand" honoured, as in the record-hits mode
+ * without the switch) and mapped; the hits queue gains one entry per selected record in file order, exactly the entries the
+ * record-hits mode appends with the switch off.  Behind that, every selected record whose entry passes the keep rule
+ * ("record_keep_min_hits", "record_keep_min_permille", "record_keep_invert") is appended to the queue of kmm_take_kept_records /
+ * kmm_take_kept_bgzf AS IT STANDS IN THE FILE: its block_size word and the block_size bytes behind it, untouched — RNAME, POS, MAPQ,
+ * CIGAR, the mate fields and every aux tag included — in file order.  "record_keep_pending_records" counts records as it does for
+ * text.  The queue's tail stays on the device; the call makes no host round trip beyond those of the record-hits mode.
+ * *n_records, "bam_records", "bam_records_excluded", the carry between windows, the node counts and kmm_get_stats behave as in the
+ * record-hits mode.  A failing call (a malformed record behind good ones, a failure of the inner records call) appends nothing
+ * to either queue.  A kept record that spans many 16 KiB tiles (a long read) is copied by one wavefront.
+ *   The bytes taken are headerless: a BAM file is kmm_bam_stream_header's bytes and the taken bytes, BGZF-compressed, and the
+ *   28-byte end-of-file member.  kmm_bam_stream_header(idx, out, capacity, n_bytes): the header of the last stream started on the
+ *   handle with KMM_FORMAT_NEW_STREAM, from the magic through the last reference, copied to out (host memory); *n_bytes its
+ *   length.  capacity below it: KMM_ERR_INVALID_ARG, the message and *n_bytes name the size.  No stream started, a first window
+ *   that ended inside the header, or a KMM_FORMAT_MID_STREAM share: KMM_ERR_INVALID_ARG.  (kmm_bam_header, DESIGN 4.14, is the
+ *   other call: it finds where the header of a file ENDS, for a rank's share.)
+ * Refused with KMM_ERR_INVALID_ARG, nothing mapped, nothing appended: kmm_map_bam with "record_bam" 1 while "record_hits" or
+ * "record_keep" is 0; with "record_names" 1 (one output form per queue); with "record_names_pairs" 1 or "record_pairs" 1; with
+ * KMM_FORMAT_MID_STREAM; a change of "record_bam" while "record_keep_pending_bytes" > 0 (text and raw records never share a
+ * queue).  With 0 every call launches exactly what it launched without the parameter.  With timing on the kernels of the raw
+ * form are timed together as KMM_KERNEL_BAM_RAW.  Out of scope: mates kept together, a rank's share, SAM text in or out, @PG
+ * lines and .bai / .csi indices, uncompressed BAM, edited records.
  */
+int kmm_bam_stream_header(kmm_index_t *idx, uint8_t *out, int64_t capacity, int64_t *n_bytes);
 int kmm_map_record_pairs(kmm_index_t *idx, const uint8_t *raw1, int64_t n1, const uint8_t *raw2, int64_t n2, int format, int k,
                          int max_freq, int also_revcomp, const uint8_t *lut, int64_t *consumed1, int64_t *consumed2, int64_t *n_pairs);
 int kmm_take_kept_mates(kmm_index_t *idx, int mate, uint8_t *out, int64_t capacity, int64_t *n_bytes, int64_t *n_records);
@@ -717,7 +743,8 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
 #define KMM_KERNEL_RX_FLUSH 6     /* radix path: per-entry hit counts -> node counts                   */
 #define KMM_KERNEL_BGZF_DEFLATE 7 /* BGZF writer: text -> one member per 65280 bytes, in slots             */
 #define KMM_KERNEL_BGZF_GATHER 8  /* BGZF writer: member offsets + the members one behind the other       */
-#define KMM_N_KERNELS 9
+#define KMM_KERNEL_BAM_RAW 9      /* "record_bam": record base, count, scans, copy and advance of the kept BAM records */
+#define KMM_N_KERNELS 10
 int kmm_set_timing(kmm_index_t *idx, int enabled);
 /* Work done by the map calls of this handle since creation (or the last call with reset != 0):
  * k-mer lookups performed (windows, doubled with also_revcomp) and count increments (index hits that
@@ -894,6 +921,8 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      kmm_take_kept_records, THE NAMED FORM.  "record_names_pairs" 0 (default) / 1: with "record_names" and
  *                      "record_keep", the selected records of a kmm_map_bam stream are mates in file order (2p, 2p + 1), their
  *                      names are compared on the device and they are kept or dropped together; see THE MATES OF A BAM STREAM
+ *   "record_bam"       0 (default) / 1: kmm_map_bam with "record_hits" and "record_keep" appends the kept records' own bytes
+ *                      (block_size word and all) to the keep queue instead of text; see THE RAW FORM, kmm_bam_stream_header
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_records_grid" test hook of kmm_map_records: workgroups (four wavefronts each) of the two per-tile kernels of the

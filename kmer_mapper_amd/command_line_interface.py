@@ -952,7 +952,7 @@ class RecordKeepSink(RecordHitsSink):
     BGZF members — every drain ends its last member; close() writes the end-of-file block; kept_bytes still counts text."""
 
     def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False, pairs=False, pair_rule="any",
-                 out2=None, bgzf=False, bam_pairs=False):
+                 out2=None, bgzf=False, bam_pairs=False, bam_out=False):
         super().__init__(windows=True)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
@@ -965,7 +965,11 @@ class RecordKeepSink(RecordHitsSink):
         self.pairs, self.pair_rule, self.out2 = bool(pairs), pair_rule, out2
         # the mates of a name-collated BAM file: the named decode's records are mates in file order
         self.bam_pairs = bool(bam_pairs)
-        self.bgzf = bool(bgzf)
+        # BAM out: the kept records as they stand in the file ("record_bam"), always BGZF, behind the input's header —
+        # written once, as members of its own, in front of the first take
+        self.bam_out = bool(bam_out)
+        self.header_written = False
+        self.bgzf = bool(bgzf) or self.bam_out
         self.written = 0                     # bytes written to out and out2 (the members' with bgzf, else the text's)
 
     def open(self, dev):
@@ -973,6 +977,8 @@ class RecordKeepSink(RecordHitsSink):
         dev.record_keep(True, **self.rule)
         if self.names:
             dev.record_names(True, mate_suffix=self.mate_suffix, **({"pairs": True} if self.bam_pairs else {}))
+        if self.bam_out:
+            dev.record_bam(True)
         if self.bam_pairs:
             dev.record_pairs(False, rule=self.pair_rule)
         if self.pairs or self.out2 is not None:
@@ -990,11 +996,25 @@ class RecordKeepSink(RecordHitsSink):
             self.hits.append(got[0])
             self.wins.append(got[1])
             self.seen += int(got[0].shape[0])
+        if self.bam_out and not self.header_written:
+            self._write_header(dev)
         n = self._take(dev, 0, self.out)
         if self.out2 is not None:
             n2 = self._take(dev, 1, self.out2)
             if n2 != n:
                 raise RuntimeError("select-reads: %d mate-1 and %d mate-2 records kept by one call" % (n, n2))
+
+    def _write_header(self, dev):
+        """The input's header, verbatim, as BGZF members of its own — once the stream's first windows have brought all of it."""
+        from .util import bgzf_compress
+        try:
+            header = dev.bam_header()
+        except ValueError:                   # (the windows so far ended inside the header: no record was mapped either)
+            return
+        members = bgzf_compress(header, device=getattr(dev, "device", 0))
+        self.out.write(memoryview(members))
+        self.written += int(members.shape[0])
+        self.header_written = True
 
     def _take(self, dev, mate, out):
         """One queue into its file; returns the records taken."""
@@ -1012,6 +1032,8 @@ class RecordKeepSink(RecordHitsSink):
 
     def close(self):
         """Behind the last drain: the block that ends a BGZF file."""
+        if self.bam_out and not self.header_written:
+            raise RuntimeError("select-reads --bam-out: the input's header was never read: nothing to write in front of the records")
         if self.bgzf:
             from .gz_io import BGZF_EOF
             for out in (self.out, self.out2):
@@ -1022,17 +1044,19 @@ class RecordKeepSink(RecordHitsSink):
 
 _SELECT_READS_BAM_ONLY = (("--bam-to-fastq", "bam_to_fastq"), ("--exclude-flags", "exclude_flags"), ("--include-flags", "include_flags"),
                           ("--min-mapq", "min_mapq"), ("--regions", "regions"), ("--regions-file", "regions_file"),
-                          ("--as-stored", "as_stored"), ("--mate-suffix", "mate_suffix"))
+                          ("--as-stored", "as_stored"), ("--mate-suffix", "mate_suffix"), ("--bam-out", "bam_out"))
 
 
-def check_select_reads_input(fmt, world_size, reads, output, bam_to_fastq=False, bam_options=()):
+def check_select_reads_input(fmt, world_size, reads, output, bam_to_fastq=False, bam_options=(), bam_out=False):
     """`kmer_mapper select-reads` takes FASTA / FASTQ (plain or .gz) — and with --bam-to-fastq a BAM file, whose kept records
-    come out as FASTQ — in one process and never writes over its input; everything else is refused before the
-    index is read.  bam_options: the names of the options given that go with BAM input alone."""
-    if fmt == "bam" and not bam_to_fastq:
+    come out as FASTQ, with --bam-out a BAM file whose kept records come out as BAM records — in one
+    process and never writes over its input; everything else is refused before the index is read.  bam_options: the names of
+    the options given that go with BAM input alone."""
+    if fmt == "bam" and not bam_to_fastq and not bam_out:
         raise ValueError("select-reads does not read %s files: their records are decoded on the GPU without the read's name, so "
                          "the selected text would be useless; SAM and BAM input is out of scope — unless --bam-to-fastq asks for "
-                         "a BAM file's kept records as FASTQ, with their names and qualities" % fmt.upper())
+                         "a BAM file's kept records as FASTQ, with their names and qualities (or --bam-out for the kept records "
+                         "as a BAM file)" % fmt.upper())
     if fmt == "sam":
         raise ValueError("select-reads does not read %s files: their records are decoded on the GPU without the read's name, so "
                          "the selected text would be useless; SAM and BAM input is out of scope (--bam-to-fastq reads BAM, not "
@@ -1044,6 +1068,21 @@ def check_select_reads_input(fmt, world_size, reads, output, bam_to_fastq=False,
                          % world_size)
     if os.path.abspath(str(output)) == os.path.abspath(str(reads)) or (os.path.exists(str(output)) and os.path.samefile(str(output), str(reads))):
         raise ValueError("select-reads: -o %s is the input file (-f): the output would overwrite the reads" % output)
+
+
+def check_select_reads_bam_out(fmt, given):
+    """--bam-out of `kmer_mapper select-reads`: a BAM file in, the kept records out as a BAM file, untouched and in
+    file order.  given: the names of the other options given that change the form of the output or pair the reads — none goes
+    with it.  Refused before the index is read and before -o is created."""
+    if fmt != "bam":
+        raise ValueError("--bam-out applies to BAM input only (the reads are %s): BAM records are written from BAM records" % fmt)
+    for opt in given:
+        why = {"--bam-to-fastq": "the kept records leave as FASTQ text or as BAM records, not both",
+               "--as-stored": "the records are written as they stand in the file in any case; the strand matters to the hits alone, "
+                              "which are counted in read orientation",
+               "--mate-suffix": "the names are not rewritten"}.get(opt, "mates are not kept together in BAM output, which has one "
+                                                                        "input file (-f) and one output file (-o)")
+        raise ValueError("select-reads: --bam-out does not go with %s: %s" % (opt, why))
 
 
 def check_select_reads_bam_pairs(fmt, bam_to_fastq=False, interleaved=False, reads2=None, output2=None):
@@ -1172,11 +1211,18 @@ def select_reads_file(args):
     interleaved, reads2, output2 = bool(getattr(args, "interleaved", False)), getattr(args, "reads2", None), getattr(args, "output2", None)
     pair_rule = getattr(args, "pair_rule", None)
     bam_pairs = bool(getattr(args, "bam_pairs", False))
+    bam_out = bool(getattr(args, "bam_out", False))
+    if bam_out:
+        check_select_reads_bam_out(probe.fmt, [opt for opt, name in (("--bam-to-fastq", "bam_to_fastq"), ("--as-stored", "as_stored"),
+                                                                     ("--mate-suffix", "mate_suffix"), ("--bam-pairs", "bam_pairs"),
+                                                                     ("--interleaved", "interleaved"), ("-f2/--reads2", "reads2"),
+                                                                     ("-o2/--output2", "output2")) if getattr(args, name, None)])
     if bam_pairs:
         check_select_reads_bam_pairs(probe.fmt, bool(getattr(args, "bam_to_fastq", False)), interleaved, reads2, output2)
     check_select_reads_pairs(probe, args.reads, args.output_file, interleaved, reads2, output2, None if bam_pairs else pair_rule)
     bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None)]
-    check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options)
+    check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options,
+                             bam_out)
     if not 0 <= args.min_hit_permille <= 1000:
         raise ValueError("--min-hit-permille outside [0, 1000]")
     if args.min_hits < 0:
@@ -1209,6 +1255,7 @@ def select_reads_file(args):
     if fmt == "fasta" and not probe.two_line:
         fmt = "fasta_ml"
     logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes%s%s",
+                 "; the kept BAM records written as they stand, behind the input's header (--bam-out)" if bam_out else
                  "; BAM records decoded to FASTQ with their names (--bam-to-fastq)" if bam else "",
                  "; neighbouring records are mates, kept together, pair rule '%s' (--bam-pairs)" % (pair_rule or "any") if bam_pairs else "")
     rule = dict(min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert,
@@ -1223,8 +1270,8 @@ def select_reads_file(args):
             sink.close()
     else:
         with open(args.output_file, "wb") as out:
-            sink = RecordKeepSink(out, names=bam, mate_suffix=bam and bool(getattr(args, "mate_suffix", False)), pairs=interleaved,
-                                  pair_rule=pair_rule or "any", bam_pairs=bam_pairs, **rule)
+            sink = RecordKeepSink(out, names=bam and not bam_out, mate_suffix=bam and bool(getattr(args, "mate_suffix", False)),
+                                  pairs=interleaved, pair_rule=pair_rule or "any", bam_pairs=bam_pairs, bam_out=bam_out, **rule)
             try:
                 map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
                             device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more)
@@ -1372,7 +1419,7 @@ def build_argument_parser():
     sub = subparsers.add_parser("select-reads", help="Extension: write the reads whose k-mers hit a kmer index back out")
     sub.add_argument("-i", "--kmer-index", required=False)
     sub.add_argument("-b", "--index-bundle", required=False)
-    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format (BAM with --bam-to-fastq)")
+    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format (BAM with --bam-to-fastq or --bam-out)")
     sub.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
     sub.add_argument("-c", "--chunk-size", required=False, type=int, default=2500000, help="N bytes to process in each chunk")
     sub.add_argument("-o", "--output-file", required=True,
@@ -1430,6 +1477,13 @@ def build_argument_parser():
                           "interleaved FASTQ. Secondary and supplementary records (0x900) are excluded; the names of every pair are "
                           "compared on the GPU, and neighbours that are no mates (a coordinate-sorted file) or a last record without "
                           "its mate are an error.")
+    sub.add_argument("--bam-out", action="store_true", default=argparse.SUPPRESS,
+                     help="Read a BAM file and write the kept records back out as a BAM file: every kept record as it stands in the "
+                          "input (RNAME, POS, MAPQ, CIGAR, mate fields and aux tags included), in file order, behind the input's header "
+                          "(verbatim: no @PG line; no index is written). -o is always BGZF, deflated on the GPU. Takes --min-hits, "
+                          "--min-hit-permille, --invert, --hits-output and the BAM selection options; the hits of records with FLAG "
+                          "0x10 are counted in read orientation. Does not go with --bam-to-fastq, --as-stored, --mate-suffix, "
+                          "--bam-pairs, --interleaved or -f2 / -o2.")
     sub.add_argument("--bgzf", action="store_true", default=argparse.SUPPRESS,
                      help="Write -o (and -o2) as BGZF files: the kept text is deflated on the GPU, one member per 65280 bytes, and "
                           "only the members are copied to the host. Without it the output is plain text, whatever -o is called.")

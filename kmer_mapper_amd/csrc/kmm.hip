@@ -475,6 +475,15 @@ struct kmm_index : IndexStreams, RxArrays {
     bool rk_mates_call = false;
     DevBuf bam_mate, rk_names_ctl;
     int64_t bam_mate_len = 0, bam_pairs_done = 0;
+    // the raw form: "record_bam" 1: kmm_map_bam with "record_hits" and "record_keep" maps the selected records in the
+    // two-line FASTA form and appends the kept records' own bytes (block_size word and all) to rkq[0].  rk_raw_call: set around
+    // that call's inner kmm_map_records alone, which then appends its entries but none of the FASTA text.  bam_raw: the record
+    // base, the kept bytes' base, the kept bytes and records per tile, the totals.  bam_hdr: the header of the last stream
+    // started with KMM_FORMAT_NEW_STREAM, magic through the last reference (kmm_bam_stream_header); bam_hdr_valid: there is one.
+    int record_bam = 0;
+    bool rk_raw_call = false, bam_hdr_valid = false;
+    DevBuf bam_raw;
+    std::vector<uint8_t> bam_hdr;
     BzScratch bz; // kmm_take_kept_bgzf
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
@@ -2745,7 +2754,7 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
             ix->rhq_pending += out[1];
             if (pairs)
                 KMMCHK(record_keep_piece<2>(ix, ix->rkq[0], rv, n_bytes, out[0], out[1], q_hits, q_win));
-            else if (ix->record_keep)
+            else if (ix->record_keep && !ix->rk_raw_call) // ("record_bam", DESIGN 4.24: kmm_map_bam appends the records' own bytes)
                 KMMCHK(record_keep_piece<0>(ix, ix->rkq[0], rv, n_bytes, out[0], out[1], q_hits, q_win));
             if (pairs && ix->rk_mates_call) {
                 // (the text is kmm_map_bam's — neighbours that are no mates fail the call, which puts back what
@@ -3565,7 +3574,24 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
         return fail(KMM_ERR_INVALID_ARG, "%s: \"record_names\" is 1 and \"record_hits\" is 0: the named FASTQ form of the decode serves "
                     "the record-hits mode (and \"record_keep\"), set \"record_hits\" to 1 or 2, or \"record_names\" to 0 (nothing is mapped)",
                     c.who);
-    KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM, !text && ix->record_names != 0));
+    // ("record_bam", DESIGN 4.24: kmm_map_bam alone, as "record_names" — one output form per queue, whole streams, no mates)
+    if (!text && ix->record_bam) {
+        if (!ix->record_hits || !ix->record_keep)
+            return fail(KMM_ERR_INVALID_ARG, "%s: \"record_bam\" is 1 and \"%s\" is 0: the kept records' own bytes are appended under the "
+                        "keep rule, which reads the entries of the record-hits mode; set \"record_hits\" to 1 or 2 and \"record_keep\" to 1, "
+                        "or \"record_bam\" to 0 (nothing is mapped)", c.who, ix->record_hits ? "record_keep" : "record_hits");
+        if (ix->record_names)
+            return fail(KMM_ERR_INVALID_ARG, "%s: \"record_bam\" and \"record_names\" are 1: the queue of kept records takes one form, the "
+                        "records' own bytes or their named FASTQ text; set one of them to 0 (nothing is mapped)", c.who);
+        if (ix->record_names_pairs || ix->record_pairs)
+            return fail(KMM_ERR_INVALID_ARG, "%s: \"record_bam\" and \"%s\" are 1: mates are not kept together in BAM output; set one of "
+                        "them to 0 (nothing is mapped)", c.who, ix->record_names_pairs ? "record_names_pairs" : "record_pairs");
+        if (c.mid_stream)
+            return fail(KMM_ERR_INVALID_ARG, "%s: \"record_bam\" is 1 and the stream begins behind the header (KMM_FORMAT_MID_STREAM): a "
+                        "rank's share of a file has no header to write in front of its records; map the file with one rank (nothing is "
+                        "mapped)", c.who);
+    }
+    KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM, !text && (ix->record_names != 0 || ix->record_bam != 0)));
     KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
@@ -4081,6 +4107,58 @@ static int bam_map_mates(kmm_index_t *ix, const StreamCall &c, BamGpuBackend &be
     return KMM_OK;
 }
 
+// The kept records of a kmm_map_bam window as they stand in the file ("record_bam"), behind the inner records call:
+// its co.recs entries are the last ones of the entry queue, one per selected record in file order.  Five steps on the handle's
+// stream, no read-back: the record base of every tile (a scan of Tile::recs), the kept raw bytes and records per tile, their
+// scans, the copy behind the queue's tail, the tail's advance.  The queue holds room for the window's consumed bytes first.
+static int bam_raw_keep(kmm_index_t *ix, BamGpuBackend &be, const kmm_bam::CallOut &co, int64_t n_raw)
+{
+    using kmm_bam::Tile;
+    static_assert(sizeof(Tile) == 32 && offsetof(Tile, recs) == 16, "k_bam_raw_scan reads Tile::recs as word 4 of 8");
+    const uint64_t n_tiles = ((uint64_t)n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE;
+    kmm_index::RkQueue &q = ix->rkq[0];
+    const size_t off_kept = 2 * (size_t)n_tiles * 8, off_tot = (off_kept + 2 * (size_t)n_tiles * 4 + 15) & ~(size_t)15;
+    KMMCHK(ensure(ix->bam_raw, off_tot + 64));
+    KMMCHK(rkq_reserve(ix, q, (int64_t)co.consumed));
+    uint8_t *w = (uint8_t *)ix->bam_raw.p;
+    unsigned long long *rec_base = (unsigned long long *)w, *byte_base = rec_base + n_tiles, *tot = (unsigned long long *)(w + off_tot);
+    uint32_t *kept_bytes = (uint32_t *)(w + off_kept), *kept_recs = kept_bytes + n_tiles;
+    const int64_t first = ix->rhq_head + ix->rhq_pending - (int64_t)co.recs; // (the inner call's entries: the queue's last)
+    if (first < 0)
+        return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %llu selected records and %lld entries pending", co.recs, (long long)ix->rhq_pending);
+    const uint32_t *hits = (const uint32_t *)ix->rhq_hits.p + first;
+    const uint32_t *windows = ix->record_hits == 2 ? (const uint32_t *)ix->rhq_win.p + first : nullptr;
+    const RkRule rule = {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert};
+    const Tile *tl = (const Tile *)be.tiles(be.cur);
+    unsigned long long *tail = (unsigned long long *)q.ctl.p;
+    const kmm_bam::Sel sel = be.sel; // (its excl is the exclude mask, which the form without a selection reads from here)
+    ScopedTimer tm;
+    KMMCHK(tm.begin(ix, KMM_KERNEL_BAM_RAW));
+    hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)tl + 4, 8u, n_tiles, rec_base, tot + 2);
+    if (be.selected)
+        hipLaunchKernelGGL(kmm_bam::k_bam_raw_count<true>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref, sel, tl,
+                           (const unsigned long long *)rec_base, hits, windows, co.recs, rule, kept_bytes, kept_recs);
+    else
+        hipLaunchKernelGGL(kmm_bam::k_bam_raw_count<false>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref, sel, tl,
+                           (const unsigned long long *)rec_base, hits, windows, co.recs, rule, kept_bytes, kept_recs);
+    hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)kept_bytes, 1u, n_tiles, byte_base, tot);
+    hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)kept_recs, 1u, n_tiles,
+                       (unsigned long long *)nullptr, tot + 1);
+    if (be.selected)
+        hipLaunchKernelGGL(kmm_bam::k_bam_raw_copy<true>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref, sel, tl,
+                           (const unsigned long long *)rec_base, hits, windows, co.recs, rule, (const uint32_t *)kept_bytes,
+                           (const unsigned long long *)byte_base, (const unsigned long long *)tail, (uint8_t *)q.text.p);
+    else
+        hipLaunchKernelGGL(kmm_bam::k_bam_raw_copy<false>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref, sel, tl,
+                           (const unsigned long long *)rec_base, hits, windows, co.recs, rule, (const uint32_t *)kept_bytes,
+                           (const unsigned long long *)byte_base, (const unsigned long long *)tail, (uint8_t *)q.text.p);
+    hipLaunchKernelGGL(kmm_bam::k_bam_raw_advance, dim3(1), dim3(64), 0, ix->stream, tail, (const unsigned long long *)tot);
+    KMMCHK(tm.end());
+    HIPCHK(hipGetLastError());
+    q.bound += (int64_t)co.consumed;
+    return KMM_OK;
+}
+
 // The inflated bytes of a kmm_map_bam call (d_raw[0, n_raw): the carry of the call before in front): the header on a stream's
 // first call, then the records up to the last complete one (*used), decoded into two-line FASTA in HBM and mapped by
 // kmm_map_records.  *short_header: a first window that ends inside the header (nothing is used).
@@ -4094,11 +4172,13 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
         // a rank's share: no header — n_ref is the caller's ("bam_n_ref"), the first record starts `head` bytes
         // into the stream's first member ("bgzf_head_skip"), where kmm_bam_find_record_start found it
         ix->bam_n_ref = (int32_t)ix->bam_n_ref_param;
+        ix->bam_hdr_valid = false; // (kmm_bam_stream_header: a share has no header)
         start0 = (uint64_t)head;
     } else if (c.new_stream) {
         // the header (magic, l_text, text, n_ref, the references) is read back in growing prefixes: its length is only known by
         // walking it, and it is read once per stream
         ix->bam_n_ref = -1;
+        ix->bam_hdr_valid = false;
         std::vector<uint8_t> h;
         uint64_t want = n_raw < (1 << 16) ? (uint64_t)n_raw : 1u << 16, hdr_end = 0;
         int32_t n_ref = 0;
@@ -4121,6 +4201,8 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
             want = want * 4 < (uint64_t)n_raw ? want * 4 : (uint64_t)n_raw;
         }
         ix->bam_n_ref = n_ref;
+        ix->bam_hdr.assign(h.begin(), h.begin() + (std::ptrdiff_t)hdr_end); // (kmm_bam_stream_header: magic through the last reference)
+        ix->bam_hdr_valid = true;
         ix->bam_header_bytes += (int64_t)hdr_end;
         start0 = hdr_end;
     } else if (ix->bam_n_ref < 0) {
@@ -4160,12 +4242,30 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     KMMCHK(ensure(ix->bam_out, (size_t)co.out_bytes + 64));
     KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p));
     int64_t taken = 0, recs = 0;
+    // ("record_bam", DESIGN 4.24: the inner call appends the entries and leaves the keep queue to bam_raw_keep below)
+    const bool raw = ix->record_bam && ix->record_hits && ix->record_keep;
+    ix->rk_raw_call = raw;
     // (the quality variant's text is FASTQ: compaction and the radix path, where "min_base_quality" is applied)
-    KMMCHK(kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, qual || be.named ? KMM_FORMAT_FASTQ : KMM_FORMAT_FASTA2, c.k,
-                           c.max_freq, c.also_revcomp, c.lut, &taken, &recs));
+    const int rc_in = kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, qual || be.named ? KMM_FORMAT_FASTQ : KMM_FORMAT_FASTA2,
+                                      c.k, c.max_freq, c.also_revcomp, c.lut, &taken, &recs);
+    ix->rk_raw_call = false;
+    KMMCHK(rc_in);
+    int rc = KMM_OK;
     if (taken != (int64_t)co.out_bytes || recs != (int64_t)co.recs)
-        return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %llu decoded bytes, %lld of %llu records mapped", (long long)taken,
-                    co.out_bytes, (long long)recs, co.recs);
+        rc = fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %llu decoded bytes, %lld of %llu records mapped", (long long)taken,
+                  co.out_bytes, (long long)recs, co.recs);
+    else if (raw)
+        rc = bam_raw_keep(ix, be, co, n_raw);
+    if (rc != KMM_OK && raw && ix->rk_snap.valid) { // (a failing call appends nothing to either queue: what the inner call found is put back)
+        ix->rhq_pending = ix->rk_snap.pending;
+        rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
+        ix->bam_calls--;
+        ix->bam_records -= (int64_t)co.recs;
+        ix->bam_excluded -= (int64_t)co.excluded;
+    }
+    if (raw)
+        ix->rk_snap.valid = false;
+    KMMCHK(rc);
     if (c.n_records)
         *c.n_records = recs;
     return KMM_OK;
@@ -4207,6 +4307,27 @@ int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags,
             return rc;
         }
         return bgzf_finish(ix, c, b, used);
+    });
+}
+
+int kmm_bam_stream_header(kmm_index_t *ix, uint8_t *out, int64_t capacity, int64_t *n_bytes)
+{
+    return guarded("kmm_bam_stream_header", [&] {
+        if (!ix)
+            return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+        if (n_bytes)
+            *n_bytes = 0;
+        if (!ix->bam_hdr_valid)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_bam_stream_header: no BAM stream with a header was started on this handle (kmm_map_bam with "
+                        "KMM_FORMAT_NEW_STREAM; a KMM_FORMAT_MID_STREAM share has none)");
+        const int64_t n = (int64_t)ix->bam_hdr.size();
+        if (n_bytes)
+            *n_bytes = n;
+        if (capacity < n || !out)
+            return fail(KMM_ERR_INVALID_ARG, "kmm_bam_stream_header: the header has %lld bytes, capacity is %lld", (long long)n,
+                        (long long)(out ? capacity : 0));
+        memcpy(out, ix->bam_hdr.data(), (size_t)n);
+        return KMM_OK;
     });
 }
 
@@ -5542,6 +5663,22 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value != 0 && value != 1)
             return fail(KMM_ERR_INVALID_ARG, "%s takes 0 or 1", name);
         (name[12] ? ix->record_names_mate_suffix : ix->record_names) = (int)value;
+    } else if (!strcmp(name, "record_bam")) {
+        // 1: kmm_map_bam with "record_hits" and "record_keep" appends the kept records' own bytes to the keep queue;
+        // text and raw records never share a queue: the switch does not move while kept bytes are pending
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "record_bam takes 0 or 1");
+        if ((int)value != ix->record_bam && ix->rkq[0].ctl.p) {
+            HIPCHK(hipSetDevice(ix->device));
+            KMMCHK(drain(ix));
+            unsigned long long tail[2];
+            KMMCHK(rkq_tail(ix->rkq[0], tail));
+            if (tail[0] > 0)
+                return fail(KMM_ERR_INVALID_ARG, "record_bam %lld with %llu kept bytes pending that were appended under record_bam %d: "
+                            "take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue (kmm_reset_counts) first",
+                            (long long)value, tail[0], ix->record_bam);
+        }
+        ix->record_bam = (int)value;
     } else if (!strcmp(name, "original_strand")) {
         // 1: kmm_map_bam and KMM_FORMAT_SAM hand every kept record whose FLAG has 0x10 to the mapper in read orientation
         if (value != 0 && value != 1)
@@ -5628,6 +5765,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->record_names;
     else if (!strcmp(name, "record_names_mate_suffix"))
         *value = ix->record_names_mate_suffix;
+    else if (!strcmp(name, "record_bam"))
+        *value = ix->record_bam;
     else if (!strcmp(name, "record_keep"))
         *value = ix->record_keep;
     else if (!strcmp(name, "record_keep_min_hits"))

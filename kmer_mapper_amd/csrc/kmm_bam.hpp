@@ -30,6 +30,9 @@
 // Record selection (kmm_select.hpp has the rule): with an include mask, a MAPQ floor or a region list set, spec, fix,
 // decode and the CPU backend run as their <.., true> / k_bam_*_sel forms, which ask ONE predicate, kept(), about every record:
 // counting and writing can never disagree.  Without one, the forms above run, as they did before the selection existed.
+// The raw form ("record_bam"; k_bam_raw_*): behind the record-hits mode's decode and mapping, the selected records whose
+// entry passes the keep rule are appended to the keep queue AS THEY STAND — block_size word and all — by a walk of the verified
+// claims with the same predicate: a scan of the tiles' record counts, a count, a scan of the kept bytes, a copy, the tail's advance.
 // Exactness never depends on the plausibility test: a wrong guess only costs a fix.  Every read is bounds-checked against n.
 // resync (kmm_bam_find_record_start) is the other use of the plausibility test: in inflated bytes that begin anywhere
 // in the stream — a rank's share of a file — k_bam_resync finds the lowest position from which the chain of records holds to the
@@ -40,6 +43,7 @@
 #include <cstring>
 #include <vector>
 
+#include "kmm_record_keep.hpp" // (the keep rule rk_keep and the store split rk_span of the raw form below)
 #include "kmm_select.hpp"
 
 #if defined(__HIPCC__)
@@ -224,6 +228,10 @@ KMM_BAM_HD uint32_t rec_out_len(const RecHead &h, bool sfx)
 // adds a record's name and mate suffix: l_name - 1 <= 254 and 2 more bytes, at most 256 per record:
 constexpr uint64_t MAX_TILE_OUT = 4ull * ((uint64_t)TILE + 0x80000000ull) / 3 + (6ull + 256ull) * (TILE / 36 + 1);
 static_assert(MAX_TILE_OUT < 0x100000000ull, "a tile's output bytes fit uint32");
+// The raw form ("record_bam") keeps a record as its own 4 + block_size bytes: by the same argument the kept raw bytes of
+// a tile are below TILE (the records that end inside it) plus 4 + (2^31 - 1) (the last one):
+constexpr uint64_t MAX_TILE_RAW = (uint64_t)TILE + 4ull + 0x7FFFFFFFull;
+static_assert(MAX_TILE_RAW < 0x100000000ull, "a tile's kept raw bytes fit uint32");
 
 // The chain from p (a record start) to the first start at or past te; it stops early at a record that does not end inside
 // d[0, n) (exit = its start) or at a malformed one (bad, exit = its start).
@@ -621,6 +629,68 @@ KMM_BAM_HD uint32_t decode_record_named_rev(const uint8_t *rec, const RecHead &h
     return replaced;
 }
 
+// ---- the raw form ("record_bam"): behind the record-hits mode, the selected records whose entry passes the keep rule
+// are appended to the keep queue as they stand in the file — d[p, p + 4 + block_size), untouched.  Selected record i of tile t
+// (in file order) has entry first + rec_base[t] + i of the call's entries, rec_base = the exclusive scan of Tile::recs.
+KMM_BAM_HD uint32_t raw_len(const RecHead &h) { return 4u + h.bs; } // (block_size < 2^31: record_at)
+
+// The walk of one verified tile: every selected record (is_selected: the predicate spec, fix and decode asked) meets its entry;
+// visit(p, len, off) is called for the kept ones, in file order — off = the raw bytes of the tile's kept records in front of it.
+// Every read of d is bounded by record_at, every entry index by n_entries and by the tile's own count.  Returns the tile's kept
+// raw bytes; *kept_recs its kept records.
+template <class Selected, class Visit>
+KMM_BAM_HD uint32_t raw_walk_tile(const uint8_t *d, uint64_t n, int32_t n_ref, const Tile &c, uint64_t entry0, const uint32_t *hits,
+                                  const uint32_t *windows, uint64_t n_entries, const RkRule &rule, uint32_t *kept_recs,
+                                  Selected &&is_selected, Visit &&visit)
+{
+    uint32_t bytes = 0, recs = 0;
+    if (c.entry != NONE && c.entry != INVALID && c.recs != 0) {
+        uint64_t p = c.entry, e = entry0;
+        const uint64_t e_end = entry0 + c.recs;
+        while (p < c.exit) {
+            RecHead h;
+            if (record_at(d, n, p, n_ref, h) != REC_OK) // (cannot happen on a verified chain; bounds all the same)
+                break;
+            if (is_selected(d + p, h)) {
+                if (e >= e_end || e >= n_entries) // (cannot happen: the walk that counted and this one ask one predicate)
+                    break;
+                if (rk_keep(hits[e], windows ? windows[e] : 0u, rule)) {
+                    visit(p, raw_len(h), bytes);
+                    bytes += raw_len(h);
+                    ++recs;
+                }
+                ++e;
+            }
+            p += 4ull + h.bs;
+        }
+    }
+    *kept_recs = recs;
+    return bytes;
+}
+
+// Where a kept record goes: the queue's tail, the kept raw bytes of the tiles in front, those of the tile's kept records in front.
+KMM_BAM_HD uint64_t raw_dest(uint64_t tail, uint64_t tile_base, uint32_t off) { return tail + tile_base + off; }
+
+// The share of lane `lane` of `lanes` in copying the len bytes at src to queue[dst, dst + len) (queue: 16-byte aligned).  rk_span
+// states the split: the ragged head and tail of the destination byte by byte, its aligned middle as 16-byte lines — one store
+// each, from one 16-byte load at whatever alignment the source has.  Nothing outside [dst, dst + len) is written, nothing of
+// the queue is read, nothing outside src[0, len) is read.
+KMM_BAM_HD void raw_copy_part(const uint8_t *src, uint8_t *queue, uint64_t dst, uint32_t len, uint32_t lane, uint32_t lanes)
+{
+    const uint32_t a = (uint32_t)(dst & 15u);
+    uint8_t *g = queue + (dst - a); // (the 16-byte line the record starts in: g[i] takes src[i - a])
+    const RkSpan sp = rk_span(a, len);
+    for (uint32_t i = a + lane; i < sp.head_end; i += lanes)
+        g[i] = src[i - a];
+    for (uint32_t i = sp.full_begin + 16u * lane; i < sp.full_end; i += 16u * lanes) {
+        uint32_t x[4];
+        __builtin_memcpy(x, src + (i - a), 16);
+        __builtin_memcpy(__builtin_assume_aligned(g + i, 16), x, 16);
+    }
+    for (uint32_t i = sp.tail_begin + lane; i < a + len; i += lanes)
+        g[i] = src[i - a];
+}
+
 // ---- the header (host side: the library reads it back once per stream) ----
 
 // d[0, n) = the stream's first inflated bytes.  0: the header ends at *hdr_end and names *n_ref references; 1: it goes on
@@ -838,6 +908,48 @@ struct CpuBackend {
                 }
                 p += 4ull + h.bs;
             }
+        }
+    }
+    // The raw form ("record_bam"), behind totals(): the call's selected records have the entries hits / windows
+    // [0, n_entries) (windows null: none kept).  raw_count(): the record base, the kept raw bytes per tile and their scan, as the
+    // kernels make them; returns the call's kept bytes.  raw_copy(): the records that pass `rule` copied to queue[tail, ...) with
+    // `lanes` lanes one after the other (queue: 16-byte aligned, room for tail + the counted bytes).
+    std::vector<uint64_t> raw_rec_base, raw_byte_base;
+    std::vector<uint32_t> raw_kept_bytes;
+    uint64_t raw_count(const uint32_t *hits, const uint32_t *windows, uint64_t n_entries, const RkRule &rule, uint64_t *kept_recs)
+    {
+        const auto is_sel = [&](const uint8_t *rec, const RecHead &h) { return is_kept((uint64_t)(rec - d), h); };
+        raw_rec_base.assign(cur.size(), 0);
+        raw_byte_base.assign(cur.size(), 0);
+        raw_kept_bytes.assign(cur.size(), 0);
+        uint64_t recs = 0, bytes = 0, kept = 0;
+        for (uint64_t t = 0; t < cur.size(); ++t) { // (a) the record base, (b) the count
+            raw_rec_base[t] = recs;
+            recs += cur[t].recs;
+            uint32_t kr = 0;
+            raw_kept_bytes[t] = raw_walk_tile(d, n, n_ref, cur[t], raw_rec_base[t], hits, windows, n_entries, rule, &kr, is_sel,
+                                              [](uint64_t, uint32_t, uint32_t) {});
+            kept += kr;
+        }
+        for (uint64_t t = 0; t < cur.size(); ++t) { // (c) the scan
+            raw_byte_base[t] = bytes;
+            bytes += raw_kept_bytes[t];
+        }
+        *kept_recs = kept;
+        return bytes;
+    }
+    void raw_copy(const uint32_t *hits, const uint32_t *windows, uint64_t n_entries, const RkRule &rule, uint8_t *queue, uint64_t tail)
+    {
+        const auto is_sel = [&](const uint8_t *rec, const RecHead &h) { return is_kept((uint64_t)(rec - d), h); };
+        for (uint64_t t = 0; t < cur.size(); ++t) { // (d) the copy
+            uint32_t kr = 0;
+            raw_walk_tile(d, n, n_ref, cur[t], raw_rec_base[t], hits, windows, n_entries, rule, &kr, is_sel,
+                          [&](uint64_t p, uint32_t len, uint32_t off) {
+                              if ((uint64_t)off + len > raw_kept_bytes[t]) // (the tile's share, as the kernel checks it)
+                                  return;
+                              for (uint32_t lane = 0; lane < lanes; ++lane)
+                                  raw_copy_part(d + p, queue, raw_dest(tail, raw_byte_base[t], off), len, lane, lanes);
+                          });
         }
     }
 };
@@ -1292,6 +1404,102 @@ __global__ void __launch_bounds__(256) k_bam_decode_named(const uint8_t *__restr
         if (lane == 0 && repl)
             atomicAdd(replaced, (unsigned long long)repl);
     }
+}
+
+// ---- the raw form ("record_bam"): the kept records' own bytes into the keep queue, behind the inner records call.
+// scan: one workgroup of 1024 threads, each over a run of consecutive tiles, as k_bam_totals: base[t] = the sum of v[stride * u]
+// over u < t (64-bit; base null: the total alone), *total = the sum over all tiles.  It serves Tile::recs (the record base), the
+// kept bytes (the destinations) and the kept records (their total).
+__global__ void __launch_bounds__(1024) k_bam_raw_scan(const uint32_t *__restrict__ v, uint32_t stride, uint64_t n_tiles,
+                                                       unsigned long long *__restrict__ base, unsigned long long *__restrict__ total)
+{
+    __shared__ unsigned long long s[1024];
+    const uint32_t i = threadIdx.x;
+    const uint64_t per = (n_tiles + 1023) / 1024, t0 = (uint64_t)i * per < n_tiles ? (uint64_t)i * per : n_tiles,
+                   t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
+    unsigned long long sum = 0;
+    for (uint64_t t = t0; t < t1; ++t)
+        sum += v[t * stride];
+    s[i] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024; off <<= 1) { // inclusive scan (Hillis-Steele)
+        const unsigned long long x = i >= off ? s[i - off] : 0ull;
+        __syncthreads();
+        s[i] += x;
+        __syncthreads();
+    }
+    if (base) {
+        unsigned long long b = s[i] - sum;
+        for (uint64_t t = t0; t < t1; ++t) {
+            base[t] = b;
+            b += v[t * stride];
+        }
+    }
+    if (i == 1023)
+        *total = s[1023];
+}
+
+// count: one wavefront per tile (grid-stride) walks its records with the predicate of spec, fix and decode (S: kept_wave, the
+// CIGAR walked by the whole wavefront; else the exclude mask) and looks every selected one's entry up: the tile's kept raw
+// bytes and kept records.  Every lane walks the same records: the loads are one address per wavefront.
+template <bool S>
+__global__ void __launch_bounds__(256) k_bam_raw_count(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref, Sel sel,
+                                                       const Tile *__restrict__ in, const unsigned long long *__restrict__ rec_base,
+                                                       const uint32_t *__restrict__ hits, const uint32_t *__restrict__ windows,
+                                                       uint64_t n_entries, RkRule rule, uint32_t *__restrict__ kept_bytes,
+                                                       uint32_t *__restrict__ kept_recs)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        uint32_t recs = 0;
+        const uint32_t bytes = raw_walk_tile(
+            d, n, n_ref, in[t], rec_base[t], hits, windows, n_entries, rule, &recs,
+            [&](const uint8_t *rec, const RecHead &h) { return S ? kept_wave(rec, h, sel) : !(h.flag & sel.excl); },
+            [](uint64_t, uint32_t, uint32_t) {});
+        if (lane == 0) {
+            kept_bytes[t] = bytes;
+            kept_recs[t] = recs;
+        }
+    }
+}
+
+// copy: the same walk; 64 lanes over every kept record's 4 + block_size bytes (raw_copy_part), written behind the queue's tail
+// (read from the device: {bytes, records}, as k_rk_scatter reads it) at the tile's base plus the kept bytes in front inside the
+// tile.  A record is copied by the wavefront that owns its start, however many tiles it spans.  A record that would pass the
+// tile's share (what count found) is not written: the same predicate and the same entries make that impossible.
+template <bool S>
+__global__ void __launch_bounds__(256) k_bam_raw_copy(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref, Sel sel,
+                                                      const Tile *__restrict__ in, const unsigned long long *__restrict__ rec_base,
+                                                      const uint32_t *__restrict__ hits, const uint32_t *__restrict__ windows,
+                                                      uint64_t n_entries, RkRule rule, const uint32_t *__restrict__ kept_bytes,
+                                                      const unsigned long long *__restrict__ byte_base,
+                                                      const unsigned long long *__restrict__ tail, uint8_t *__restrict__ queue)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    const uint64_t tail0 = tail[0];
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        const uint32_t share = kept_bytes[t];
+        if (share == 0)
+            continue;
+        const uint64_t base = byte_base[t];
+        uint32_t recs = 0;
+        raw_walk_tile(
+            d, n, n_ref, in[t], rec_base[t], hits, windows, n_entries, rule, &recs,
+            [&](const uint8_t *rec, const RecHead &h) { return S ? kept_wave(rec, h, sel) : !(h.flag & sel.excl); },
+            [&](uint64_t p, uint32_t len, uint32_t off) {
+                if ((uint64_t)off + len <= share)
+                    raw_copy_part(d + p, queue, raw_dest(tail0, base, off), len, lane, 64u);
+            });
+    }
+}
+
+// advance: the queue's tail {bytes, records} moves behind the call's kept bytes and records (k_rk_advance with 64-bit totals)
+__global__ void k_bam_raw_advance(unsigned long long *tail, const unsigned long long *__restrict__ total)
+{
+    if (threadIdx.x < 2 && blockIdx.x == 0)
+        tail[threadIdx.x] += total[threadIdx.x];
 }
 
 // resync: one wavefront per tile (grid-stride), the shape of spec; lanes test 64 consecutive positions, the survivors are

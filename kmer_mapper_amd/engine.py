@@ -299,10 +299,20 @@ class DeviceIndex:
         return self._map_stream("kmm_map_bam", comp, n_bytes, 0, first, last, k, max_index_lookup_frequency, also_revcomp, lut,
                                 more_flags=_lib.FORMAT_MID_STREAM if mid_stream else 0)
 
-    def bam_header(self, comp, n_bytes=None):
+    def bam_header(self, comp=None, n_bytes=None):
         """kmm_bam_header: `comp` starts at a BAM file's first member.  Returns (n_ref, hdr_member, hdr_skip): the reference count
         and where the first record lies (compressed offset of its member, offset in the member's inflated bytes); n_ref = -1:
-        the window ends inside the header — bring a longer one."""
+        the window ends inside the header — bring a longer one.
+        Without `comp` — kmm_bam_stream_header: the header of the last stream that map_bam started on this handle
+        with first=True, as bytes, from the magic through the last reference; ValueError when there is none (no stream, a first
+        window that ended inside the header, or a mid-stream share)."""
+        if comp is None:
+            n = ctypes.c_int64(0)
+            if _lib.lib().kmm_bam_stream_header(self._h, None, 0, ctypes.byref(n)) != _lib.KMM_OK and n.value == 0:
+                _lib.check(_lib.KMM_ERR_INVALID_ARG)                  # (no header: the library's message)
+            buf = np.empty(max(n.value, 1), dtype=np.uint8)
+            _lib.check(_lib.lib().kmm_bam_stream_header(self._h, buf.ctypes.data_as(_P), n.value, ctypes.byref(n)))
+            return buf[:n.value].tobytes()
         b = _Arg(comp, np.uint8, "comp")
         n_ref, member, skip = ctypes.c_int32(-1), ctypes.c_int64(0), ctypes.c_int64(0)
         _lib.check(_lib.lib().kmm_bam_header(self._h, b.ptr, _n_bytes(b, n_bytes), ctypes.byref(n_ref), ctypes.byref(member),
@@ -429,6 +439,13 @@ class DeviceIndex:
         self.set_param("record_names_pairs", int(bool(on and pairs)))
         self.set_param("record_names_mate_suffix", int(bool(mate_suffix)))
         self.set_param("record_names", int(bool(on)))
+
+    def record_bam(self, on=True):
+        """The raw form of the keep (include/kmm.h), on top of record_hits() and record_keep(): map_bam maps the
+        selected records as without the switch and appends every kept record AS IT STANDS IN THE FILE — its block_size word and
+        the block_size bytes behind it — to the queue of take_kept_records() / take_kept_bgzf(); bam_header() has the header that
+        goes in front.  The text routes never read it.  Refused while kept bytes are pending."""
+        self.set_param("record_bam", int(bool(on)))
 
     def take_kept_records(self, out=None):
         """kmm_take_kept_records: ALL pending bytes — the kept records, whole, in stream order — as (np.uint8 array, n_records);

@@ -146,7 +146,7 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
 
 def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
                    min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False, compress=False, pairs=False,
-                   pair_rule="any"):
+                   pair_rule="any", output="fastq"):
     """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
     text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
     (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
@@ -160,8 +160,19 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     pairs (fmt "bam"): the file is name-collated — its selected records are mates in file order, 2p and 2p + 1 — and
     mates are kept or dropped together: a pair matches when pair_rule "any" mate does, or only when "both" do.  The text is
     interleaved FASTQ, the entries lie in pair order.  Neighbours whose names differ, or an unpaired last record, raise
-    ValueError with the library's hint (collate by name; exclude secondary and supplementary records, 0x900)."""
+    ValueError with the library's hint (collate by name; exclude secondary and supplementary records, 0x900).
+    output "bam" (fmt "bam"): the kept records come back AS BAM RECORDS, untouched — RNAME, POS, MAPQ, CIGAR, mate
+    fields and aux tags included — and the text returned is the bytes of a complete BAM file: the input's header, verbatim, as BGZF
+    members of its own, the kept records' members (deflated on the GPU), the end-of-file block.  original_strand then applies
+    to the hits alone; mate_suffix, pairs and compress do not go with it."""
     from . import _lib
+    if output not in ("fastq", "bam"):
+        raise ValueError("output must be 'fastq' or 'bam', not %r" % (output,))
+    if output == "bam" and fmt != "bam":
+        raise ValueError("output=\"bam\" goes with fmt=\"bam\": BAM records are written from BAM records")
+    if output == "bam" and (mate_suffix or pairs or compress):
+        raise ValueError("output=\"bam\" does not go with mate_suffix, pairs or compress: the records are written as they stand, in "
+                         "file order, and a BAM file is always BGZF")
     if fmt != "bam" and (exclude_flags or original_strand or mate_suffix):
         raise ValueError("exclude_flags, original_strand and mate_suffix go with fmt=\"bam\"")
     if pairs and fmt != "bam":
@@ -185,20 +196,31 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
             dev.set_param("original_strand", int(bool(original_strand)))
             if pairs:
                 dev.set_param("record_pairs_rule", dev.PAIR_RULES[pair_rule])
-            dev.record_names(True, mate_suffix=mate_suffix, pairs=pairs)
+            if output == "bam":
+                dev.record_bam(True)
+            else:
+                dev.record_names(True, mate_suffix=mate_suffix, pairs=pairs)
             dev.map_bam(raw, first=True, last=True, k=k, max_index_lookup_frequency=max_index_lookup_frequency,
                         also_revcomp=also_revcomp, lut=lut)
         else:
             dev.map_records(raw, fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp, lut=lut)
         hits, windows = dev.take_record_hits()
-        if compress:
+        if output == "bam":
+            from .gz_io import BGZF_EOF
+            from .util import bgzf_compress
+            text = bgzf_compress(dev.bam_header(), device=device).tobytes() + dev.take_kept_bgzf()[0].tobytes() + BGZF_EOF
+        elif compress:
             from .gz_io import BGZF_EOF
             text = dev.take_kept_bgzf()[0].tobytes() + BGZF_EOF
         else:
             text = dev.take_kept_records()[0].tobytes()
     finally:
         if before is not None:                                                      # (the handle is cached: as it was found)
-            if pairs and dev.get_param("record_hits_pending"):                      # (a take that failed: the switch stays with its entries)
+            if output == "bam":
+                if dev.get_param("record_keep_pending_bytes"):                      # (a take that failed: raw records never meet text)
+                    dev.take_kept_records()
+                dev.record_bam(False)
+            elif pairs and dev.get_param("record_hits_pending"):                    # (a take that failed: the switch stays with its entries)
                 dev.set_param("record_names", 0)
             else:
                 dev.record_names(False)
