@@ -675,8 +675,33 @@ int kmm_take_kept_records(kmm_index_t *idx, uint8_t *out, int64_t capacity, int6
  * "record_keep" is 0; with "record_names" 1 (one output form per queue); with "record_names_pairs" 1 or "record_pairs" 1; with
  * KMM_FORMAT_MID_STREAM; a change of "record_bam" while "record_keep_pending_bytes" > 0 (text and raw records never share a
  * queue).  With 0 every call launches exactly what it launched without the parameter.  With timing on the kernels of the raw
- * form are timed together as KMM_KERNEL_BAM_RAW.  Out of scope: mates kept together, a rank's share, SAM text in or out, @PG
- * lines and .bai / .csi indices, uncompressed BAM, edited records.
+ * form are timed together as KMM_KERNEL_BAM_RAW.  Out of scope: a rank's share, SAM text in or out, @PG lines and .bai / .csi
+ * indices, uncompressed BAM, edited records.  (Mates kept together: "record_bam_mates", below.)
+ *
+ * MATES KEPT TOGETHER IN THE RAW FORM.  "record_bam_mates" 0 (default) / 1 (anything else KMM_ERR_INVALID_ARG), read
+ * by kmm_map_bam alone; it applies with "record_bam" 1, "record_hits" 1 or 2 and "record_keep" 1.  The selected records of the
+ * stream, in file order from KMM_FORMAT_NEW_STREAM, are mates: 2p and 2p + 1.  The keep decision is the pair rule of DESIGN 4.21
+ * over the two records' entries (the keep rule's parameters and "record_pairs_rule"; "original_strand" is honoured for the hits).
+ * For every kept pair the raw bytes of both records (4 + block_size each, untouched) are appended to the queue of
+ * kmm_take_kept_records / kmm_take_kept_bgzf in file order, mate 1 directly in front of mate 2; records that are not selected and
+ * lie between two mates are dropped like any record that is not selected.  "record_keep_pending_records" counts records, two per
+ * kept pair.  The hits queue gets one entry per record in pair order, whole pairs per call: windows need not hold whole pairs —
+ * the entry and the raw bytes of an odd last selected record wait on the handle for the call that brings its mate, through windows
+ * without a selected or a complete record; *n_records counts the entries appended, an even number.  One small read-back per window.
+ *   THE MATE CHECK: the read_name bytes of records 2p and 2p + 1 are compared on the device as they stand — equal l_read_name and
+ *   equal bytes, nothing trimmed.  The first pair of strangers fails the call that completes it with KMM_ERR_MALFORMED; the message
+ *   names the pair's ordinal in the stream and what to do: collate the file by name, exclude 0x900.  A KMM_FORMAT_LAST_CHUNK call
+ *   that leaves a mate 1 alone — also one that brings no member — fails with KMM_ERR_MALFORMED ("the stream ends with an unpaired
+ *   record", with the count of selected records).  Strangers come before an unpaired end.  A failing call appends nothing to either
+ *   queue, restores the pair ordinal, the BAM counters of the call and the decode's device counters and leaves the waiting mate as
+ *   it found it: a later call that brings its mate completes the pair.  (The bytes of an incomplete record that the stream carried
+ *   are dropped by a failed call that brought members, as on every route: the next call begins at a record start.)
+ *   kmm_reset_counts, KMM_FORMAT_NEW_STREAM and a change of "record_bam" or "record_bam_mates" drop a waiting mate.
+ * Refused with KMM_ERR_INVALID_ARG, nothing mapped: everything "record_bam" refuses, in its wording and first; kmm_map_bam with
+ * "record_bam_mates" 1 and "record_bam" 0; a change of "record_bam_mates" while hit entries or kept bytes are pending.  With 0
+ * every call launches exactly what it launched without the parameter.  With timing on the kernels are timed together as
+ * KMM_KERNEL_BAM_RAW_MATES.  Out of scope: coordinate-sorted input (the check reports it), singletons diverted, a rank's share,
+ * a requirement that FLAG has 0x1, 0x40 or 0x80.
  */
 int kmm_bam_stream_header(kmm_index_t *idx, uint8_t *out, int64_t capacity, int64_t *n_bytes);
 int kmm_map_record_pairs(kmm_index_t *idx, const uint8_t *raw1, int64_t n1, const uint8_t *raw2, int64_t n2, int format, int k,
@@ -744,7 +769,8 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
 #define KMM_KERNEL_BGZF_DEFLATE 7 /* BGZF writer: text -> one member per 65280 bytes, in slots             */
 #define KMM_KERNEL_BGZF_GATHER 8  /* BGZF writer: member offsets + the members one behind the other       */
 #define KMM_KERNEL_BAM_RAW 9      /* "record_bam": record base, count, scans, copy and advance of the kept BAM records */
-#define KMM_N_KERNELS 10
+#define KMM_KERNEL_BAM_RAW_MATES 10 /* "record_bam_mates": the pair forms of the above, the mate check and the carried mate 1 */
+#define KMM_N_KERNELS 11
 int kmm_set_timing(kmm_index_t *idx, int enabled);
 /* Work done by the map calls of this handle since creation (or the last call with reset != 0):
  * k-mer lookups performed (windows, doubled with also_revcomp) and count increments (index hits that

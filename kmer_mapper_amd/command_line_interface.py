@@ -952,7 +952,7 @@ class RecordKeepSink(RecordHitsSink):
     BGZF members — every drain ends its last member; close() writes the end-of-file block; kept_bytes still counts text."""
 
     def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False, pairs=False, pair_rule="any",
-                 out2=None, bgzf=False, bam_pairs=False, bam_out=False):
+                 out2=None, bgzf=False, bam_pairs=False, bam_out=False, bam_mates=False):
         super().__init__(windows=True)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
@@ -968,6 +968,8 @@ class RecordKeepSink(RecordHitsSink):
         # BAM out: the kept records as they stand in the file ("record_bam"), always BGZF, behind the input's header —
         # written once, as members of its own, in front of the first take
         self.bam_out = bool(bam_out)
+        # mates kept together in BAM out: the selected records are mates in file order ("record_bam_mates")
+        self.bam_mates = bool(bam_mates) and self.bam_out
         self.header_written = False
         self.bgzf = bool(bgzf) or self.bam_out
         self.written = 0                     # bytes written to out and out2 (the members' with bgzf, else the text's)
@@ -977,9 +979,11 @@ class RecordKeepSink(RecordHitsSink):
         dev.record_keep(True, **self.rule)
         if self.names:
             dev.record_names(True, mate_suffix=self.mate_suffix, **({"pairs": True} if self.bam_pairs else {}))
-        if self.bam_out:
+        if self.bam_mates:
+            dev.record_bam(True, mates=True)
+        elif self.bam_out:
             dev.record_bam(True)
-        if self.bam_pairs:
+        if self.bam_pairs or self.bam_mates:
             dev.record_pairs(False, rule=self.pair_rule)
         if self.pairs or self.out2 is not None:
             dev.record_pairs(self.pairs, rule=self.pair_rule)
@@ -1083,6 +1087,14 @@ def check_select_reads_bam_out(fmt, given):
                "--mate-suffix": "the names are not rewritten"}.get(opt, "mates are not kept together in BAM output, which has one "
                                                                         "input file (-f) and one output file (-o)")
         raise ValueError("select-reads: --bam-out does not go with %s: %s" % (opt, why))
+
+
+def check_select_reads_keep_mates(keep_mates, bam_out):
+    """--keep-mates of `kmer_mapper select-reads`: with --bam-out, the mates of a name-collated BAM file are kept or
+    dropped together and leave as BAM records.  Without --bam-out it is refused before the index is read."""
+    if keep_mates and not bam_out:
+        raise ValueError("select-reads: --keep-mates goes with --bam-out: the kept mates are written as BAM records; for FASTQ output "
+                         "a BAM file's mates have --bam-to-fastq --bam-pairs, and interleaved FASTQ / FASTA input has --interleaved")
 
 
 def check_select_reads_bam_pairs(fmt, bam_to_fastq=False, interleaved=False, reads2=None, output2=None):
@@ -1212,6 +1224,8 @@ def select_reads_file(args):
     pair_rule = getattr(args, "pair_rule", None)
     bam_pairs = bool(getattr(args, "bam_pairs", False))
     bam_out = bool(getattr(args, "bam_out", False))
+    keep_mates = bool(getattr(args, "keep_mates", False))
+    check_select_reads_keep_mates(keep_mates, bam_out)
     if bam_out:
         check_select_reads_bam_out(probe.fmt, [opt for opt, name in (("--bam-to-fastq", "bam_to_fastq"), ("--as-stored", "as_stored"),
                                                                      ("--mate-suffix", "mate_suffix"), ("--bam-pairs", "bam_pairs"),
@@ -1219,7 +1233,8 @@ def select_reads_file(args):
                                                                      ("-o2/--output2", "output2")) if getattr(args, name, None)])
     if bam_pairs:
         check_select_reads_bam_pairs(probe.fmt, bool(getattr(args, "bam_to_fastq", False)), interleaved, reads2, output2)
-    check_select_reads_pairs(probe, args.reads, args.output_file, interleaved, reads2, output2, None if bam_pairs else pair_rule)
+    check_select_reads_pairs(probe, args.reads, args.output_file, interleaved, reads2, output2,
+                             None if bam_pairs or keep_mates else pair_rule)
     bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None)]
     check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options,
                              bam_out)
@@ -1240,6 +1255,10 @@ def select_reads_file(args):
         if bam_pairs:
             # (a secondary or supplementary record between two mates would be taken for one of them: DESIGN 4.23)
             logging.info("select-reads --bam-pairs: secondary and supplementary records are excluded (--exclude-flags 0x%x | 0x900 "
+                         "= 0x%x)", exclude_flags, exclude_flags | 0x900)
+            exclude_flags |= 0x900
+        if keep_mates:
+            logging.info("select-reads --keep-mates: secondary and supplementary records are excluded (--exclude-flags 0x%x | 0x900 "
                          "= 0x%x)", exclude_flags, exclude_flags | 0x900)
             exclude_flags |= 0x900
         _check_bam_route(fmt, 1, exclude_flags)
@@ -1271,11 +1290,17 @@ def select_reads_file(args):
     else:
         with open(args.output_file, "wb") as out:
             sink = RecordKeepSink(out, names=bam and not bam_out, mate_suffix=bam and bool(getattr(args, "mate_suffix", False)),
-                                  pairs=interleaved, pair_rule=pair_rule or "any", bam_pairs=bam_pairs, bam_out=bam_out, **rule)
+                                  pairs=interleaved, pair_rule=pair_rule or "any", bam_pairs=bam_pairs, bam_out=bam_out,
+                                  **({"bam_mates": True} if keep_mates else {}), **rule)
             try:
                 map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
                             device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more)
             except ValueError as exc:
+                if keep_mates and ("are not mates" in str(exc) or "unpaired record" in str(exc)):
+                    # (a BAM file that stops in the middle looks like one that does not — -o is removed)
+                    out.close()
+                    os.remove(args.output_file)
+                    raise ValueError("select-reads --bam-out --keep-mates: %s (%s was removed)" % (exc, args.output_file)) from exc
                 if not interleaved or not ("unpaired record" in str(exc) or "do not form a complete record" in str(exc)):
                     raise
                 # (the error path alone: the file's lines counted once more on the host, to name both sides)
@@ -1484,6 +1509,13 @@ def build_argument_parser():
                           "--min-hit-permille, --invert, --hits-output and the BAM selection options; the hits of records with FLAG "
                           "0x10 are counted in read orientation. Does not go with --bam-to-fastq, --as-stored, --mate-suffix, "
                           "--bam-pairs, --interleaved or -f2 / -o2.")
+    sub.add_argument("--keep-mates", action="store_true", default=argparse.SUPPRESS,
+                     help="With --bam-out: the BAM file is grouped by name (unaligned BAM, an aligner's unsorted output, or after "
+                          "`samtools collate`): neighbouring selected records are mates, both kept or both dropped (--pair-rule), "
+                          "and both leave as BAM records, mate 1 directly in front of mate 2. Secondary and supplementary records "
+                          "(0x900) are excluded; the read names of every pair are compared on the GPU, and neighbours that are no "
+                          "mates (a coordinate-sorted file) or a last record without its mate are an error, after which -o is removed "
+                          "(--hits-output is written behind a complete run alone: such an error leaves none).")
     sub.add_argument("--bgzf", action="store_true", default=argparse.SUPPRESS,
                      help="Write -o (and -o2) as BGZF files: the kept text is deflated on the GPU, one member per 65280 bytes, and "
                           "only the members are copied to the host. Without it the output is plain text, whatever -o is called.")

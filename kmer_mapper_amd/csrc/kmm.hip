@@ -484,6 +484,16 @@ struct kmm_index : IndexStreams, RxArrays {
     bool rk_raw_call = false, bam_hdr_valid = false;
     DevBuf bam_raw;
     std::vector<uint8_t> bam_hdr;
+    // mates kept together in the raw form: "record_bam_mates" 1: the selected records of a kmm_map_bam stream are mates
+    // in file order and their own bytes are kept or dropped together.  The inner records call runs with rk_mates_call AND
+    // rk_raw_call: whole pairs, no text, no name lines to compare.  A window's odd last selected record waits twice: its FASTA text
+    // in bam_mate (bam_mate_len, as DESIGN 4.23), its raw bytes in bam_raw_mate (bam_raw_mate_len).  bam_raw_ctl: the call's three
+    // control words (kmm_bam.hpp k_bam_raw_count_pairs), read back once per window.  bam_raw_pos: where the selected record of
+    // every entry of the call starts, left by the count walk for the mate check.
+    int record_bam_mates = 0;
+    DevBuf bam_raw_mate, bam_raw_ctl, bam_raw_pos;
+    DevBuf bam_mate_next, bam_raw_mate_next; // the spare carry buffers: a call fills them before it appends and swaps them in when it is done
+    int64_t bam_raw_mate_len = 0;
     BzScratch bz; // kmm_take_kept_bgzf
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
@@ -1131,6 +1141,12 @@ bool bam_mates_on(const kmm_index *ix)
     return ix->record_names_pairs && ix->record_names && ix->record_hits && ix->record_keep;
 }
 
+// Are they taken as mates whose own bytes are kept ("record_bam_mates")?
+bool bam_raw_mates_on(const kmm_index *ix)
+{
+    return ix->record_bam_mates && ix->record_bam && ix->record_hits && ix->record_keep;
+}
+
 // The mate check of one piece of kmm_map_bam's inner records call: *bad is the first pair of the piece (its ordinal inside the
 // piece) whose two names differ, 0xFFFFFFFF when all agree.  One small read-back per piece, behind everything the piece queued.
 int pair_names_piece(kmm_index *ix, const ReadsView &rv, int64_t consumed, uint32_t *bad)
@@ -1563,6 +1579,7 @@ int kmm_reset_counts(kmm_index_t *ix)
     }
     ix->rk_snap.valid = false;
     ix->bam_mate_len = ix->bam_pairs_done = 0; // (a mate 1 that waits for its mate belongs to the entries just dropped: DESIGN 4.23)
+    ix->bam_raw_mate_len = 0;                  // (and so do its raw bytes: DESIGN 4.25)
     // ("record_name_bytes_replaced" counts bytes of the text that queue held: it restarts with it.  The named decode adds to the
     // first shard alone; the other statistics stay, as before, until kmm_get_stats(reset).)
     HIPCHK(hipMemsetAsync(ix->stats + KMM_STAT_REC_NAME_REPLACED, 0, sizeof(unsigned long long), ix->stream));
@@ -2752,11 +2769,13 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
             else
                 KMMCHK(launch_read_hits<MODE_RECORDS>(ix, rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, q_hits, q_win));
             ix->rhq_pending += out[1];
-            if (pairs)
+            if (pairs && ix->rk_raw_call) // ("record_bam_mates", DESIGN 4.25: whole pairs of entries; the bytes and the mate check are
+                ix->bam_pairs_done += out[1] / 2; // kmm_map_bam's, over the records themselves — this text has no names)
+            else if (pairs)
                 KMMCHK(record_keep_piece<2>(ix, ix->rkq[0], rv, n_bytes, out[0], out[1], q_hits, q_win));
             else if (ix->record_keep && !ix->rk_raw_call) // ("record_bam", DESIGN 4.24: kmm_map_bam appends the records' own bytes)
                 KMMCHK(record_keep_piece<0>(ix, ix->rkq[0], rv, n_bytes, out[0], out[1], q_hits, q_win));
-            if (pairs && ix->rk_mates_call) {
+            if (pairs && ix->rk_mates_call && !ix->rk_raw_call) {
                 // (the text is kmm_map_bam's — neighbours that are no mates fail the call, which puts back what
                 // its pieces appended)
                 uint32_t bad = 0xFFFFFFFFu;
@@ -3591,6 +3610,11 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
                         "rank's share of a file has no header to write in front of its records; map the file with one rank (nothing is "
                         "mapped)", c.who);
     }
+    // ("record_bam_mates", DESIGN 4.25: read by kmm_map_bam alone, behind everything "record_bam" refuses)
+    if (!text && ix->record_bam_mates && !ix->record_bam)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_bam_mates\" is 1 and \"record_bam\" is 0: mates are kept together in the raw form "
+                    "of the keep, set \"record_bam\" to 1 (with \"record_hits\" and \"record_keep\"), or \"record_bam_mates\" to 0; for "
+                    "FASTQ output there is \"record_names_pairs\" (nothing is mapped)", c.who);
     KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM, !text && (ix->record_names != 0 || ix->record_bam != 0)));
     KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
     if (n_comp < 0 || (n_comp > 0 && !comp))
@@ -4159,6 +4183,197 @@ static int bam_raw_keep(kmm_index_t *ix, BamGpuBackend &be, const kmm_bam::CallO
     return KMM_OK;
 }
 
+static int bam_raw_mates_unpaired(long long n_selected)
+{
+    return fail(KMM_ERR_MALFORMED, "kmm_map_bam: \"record_bam_mates\" is 1 and the stream ends with an unpaired record: it holds %lld "
+                "selected records, the last one has no mate (a selection that removes one mate of a pair is an error here; nothing of "
+                "the call is appended)", n_selected);
+}
+
+// The selected records of a kmm_map_bam window as mates whose own bytes are kept ("record_bam_mates"), behind run_call.
+// As bam_map_mates: the window's records are decoded behind the FASTA text of the mate 1 that the window before left over, and the
+// inner records call takes carry + decoded text in the pair form — whole pairs of entries, no text appended, no name lines
+// compared.  Then the raw walk in its pair form: record base, count (which reports the odd last record), the mate check over the
+// records' own read_name bytes, ONE read-back (strangers, the odd record), scans, the carried mate 1 to the queue's tail, the
+// tiles' records behind it, the tail's advance.  The odd last record's text and raw bytes become the next carry.  A call that fails
+// leaves the carries, the ordinal, the queues and the counters as it found them.
+static int bam_map_raw_mates(kmm_index_t *ix, const StreamCall &c, BamGpuBackend &be, const kmm_bam::CallOut &co, int64_t n_raw, bool qual)
+{
+    using kmm_bam::Tile;
+    const int64_t carry = ix->bam_mate_len, pairs0 = ix->bam_pairs_done, raw_carry = ix->bam_raw_mate_len;
+    const uint32_t carried = carry > 0 ? 1u : 0u;
+    const int64_t n_rec = (int64_t)co.recs + carried, n_text = carry + (int64_t)co.out_bytes;
+    unsigned long long *d_counters = nullptr;
+    auto put_back = [&](bool queues) {
+        const std::string msg = g_err;
+        ix->bam_pairs_done = pairs0;
+        ix->bam_calls--;
+        ix->bam_records -= (int64_t)co.recs;
+        ix->bam_excluded -= (int64_t)co.excluded;
+        ix->bam_false_starts -= (int64_t)co.false_starts;
+        ix->bam_continuations -= (int64_t)co.continuations;
+        if (d_counters && hipMemcpyAsync(ix->stats + KMM_STAT_REC_NO_QUAL, d_counters, 24, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess)
+            (void)hipGetLastError();
+        if (queues && ix->rk_snap.valid) {
+            ix->rhq_pending = ix->rk_snap.pending;
+            rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
+        }
+        ix->rk_snap.valid = false;
+        g_err = msg;
+    };
+    ix->rk_snap.valid = false;
+    if (carried && (raw_carry < 37 || raw_carry > 0x7FFFFFFFll + 4)) {
+        put_back(false);
+        return fail(KMM_ERR_INTERNAL, "kmm_map_bam: a mate 1 waits with %lld bytes of text and %lld raw bytes", (long long)carry, (long long)raw_carry);
+    }
+    if (co.recs == 0) { // (nothing selected: a mate 1 goes on waiting, unless the stream ends here)
+        if (c.last_chunk && carried) {
+            put_back(false);
+            return bam_raw_mates_unpaired((long long)(2 * pairs0 + 1));
+        }
+        return KMM_OK;
+    }
+    int64_t taken = 0, recs = 0;
+    unsigned long long h_ctl[3] = {kmm_bam::NONE, kmm_bam::NONE, kmm_bam::NONE};
+    const auto body = [&]() -> int {
+        KMMCHK(ensure(ix->rk_names_ctl, 64));
+        KMMCHK(ensure(ix->bam_raw_ctl, 64));
+        KMMCHK(ensure(ix->bam_out, (size_t)n_text + 64));
+        d_counters = (unsigned long long *)((uint8_t *)ix->rk_names_ctl.p + 16);
+        HIPCHK(hipMemcpyAsync(d_counters, ix->stats + KMM_STAT_REC_NO_QUAL, 24, hipMemcpyDeviceToDevice, ix->stream));
+        if (carried)
+            HIPCHK(hipMemcpyAsync(ix->bam_out.p, ix->bam_mate.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream));
+        const uint64_t n_tiles = ((uint64_t)n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE;
+        KMMCHK(be.decode(n_tiles, (uint8_t *)ix->bam_out.p + carry));
+        if (n_rec >= 2) {
+            ix->rk_mates_call = ix->rk_raw_call = true;
+            const int rc = kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, n_text, qual ? KMM_FORMAT_FASTQ : KMM_FORMAT_FASTA2, c.k, c.max_freq,
+                                           c.also_revcomp, c.lut, &taken, &recs);
+            ix->rk_mates_call = ix->rk_raw_call = false;
+            KMMCHK(rc); // (the inner call has put its own entries back)
+            if (recs != (n_rec & ~(int64_t)1) || ((n_rec & 1) == 0 && taken != n_text) || taken > n_text)
+                return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %lld decoded bytes, %lld of %lld records mapped as pairs", (long long)taken,
+                            (long long)n_text, (long long)recs, (long long)n_rec);
+        }
+        // the raw walk, pair form
+        kmm_index::RkQueue &q = ix->rkq[0];
+        const size_t off_kept = 2 * (size_t)n_tiles * 8, off_tot = (off_kept + 2 * (size_t)n_tiles * 4 + 15) & ~(size_t)15;
+        KMMCHK(ensure(ix->bam_raw, off_tot + 64));
+        uint8_t *w = (uint8_t *)ix->bam_raw.p;
+        unsigned long long *rec_base = (unsigned long long *)w, *byte_base = rec_base + n_tiles, *tot = (unsigned long long *)(w + off_tot);
+        uint32_t *kept_bytes = (uint32_t *)(w + off_kept), *kept_recs = kept_bytes + n_tiles;
+        unsigned long long *ctl = (unsigned long long *)ix->bam_raw_ctl.p;
+        const uint64_t n_entries = (uint64_t)recs;
+        KMMCHK(ensure(ix->bam_raw_pos, (size_t)n_entries * 8 + 64)); // (the start of every selected record that has an entry)
+        unsigned long long *pos = (unsigned long long *)ix->bam_raw_pos.p;
+        const int64_t first = ix->rhq_head + ix->rhq_pending - recs; // (the inner call's entries: the queue's last)
+        if (first < 0)
+            return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld entries of the call and %lld entries pending", (long long)recs, (long long)ix->rhq_pending);
+        // (no entries: the kernels read none — e >= n_entries comes first — and the pointers stay null)
+        const uint32_t *hits = n_entries ? (const uint32_t *)ix->rhq_hits.p + first : nullptr;
+        const uint32_t *windows = n_entries && ix->record_hits == 2 ? (const uint32_t *)ix->rhq_win.p + first : nullptr;
+        const RkPairRule rule = {{(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert}, (uint32_t)ix->rk_pair_rule};
+        const Tile *tl = (const Tile *)be.tiles(be.cur);
+        const kmm_bam::Sel sel = be.sel;
+        const uint8_t *d_carry = carried ? (const uint8_t *)ix->bam_raw_mate.p : nullptr;
+        const uint32_t carry_len = carried ? (uint32_t)raw_carry : 0u;
+        ScopedTimer tm;
+        KMMCHK(tm.begin(ix, KMM_KERNEL_BAM_RAW_MATES));
+        HIPCHK(hipMemsetAsync(ctl, 0xFF, 24, ix->stream));
+        if (n_entries > 0)
+            HIPCHK(hipMemsetAsync(pos, 0xFF, (size_t)n_entries * 8, ix->stream));
+        hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)tl + 4, 8u, n_tiles, rec_base, tot + 2);
+        if (be.selected)
+            hipLaunchKernelGGL(kmm_bam::k_bam_raw_count_pairs<true>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref,
+                               sel, tl, (const unsigned long long *)rec_base, hits, windows, n_entries, rule, carried, kept_bytes, kept_recs, pos,
+                               ctl);
+        else
+            hipLaunchKernelGGL(kmm_bam::k_bam_raw_count_pairs<false>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref,
+                               sel, tl, (const unsigned long long *)rec_base, hits, windows, n_entries, rule, carried, kept_bytes, kept_recs, pos,
+                               ctl);
+        if (n_entries > 0)
+            hipLaunchKernelGGL(kmm_bam::k_bam_raw_pair_names, be.wave_grid(n_entries / 2), dim3(256), 0, ix->stream, be.d,
+                               co.consumed, (const unsigned long long *)pos, n_entries, carried, d_carry, carry_len, ctl);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_ctl, ctl, 24, hipMemcpyDeviceToHost, ix->stream));
+        HIPCHK(hipStreamSynchronize(ix->stream));
+        if (h_ctl[0] != kmm_bam::NONE) {
+            (void)tm.end();
+            const long long p = (long long)(pairs0 + (int64_t)h_ctl[0]);
+            return fail(KMM_ERR_MALFORMED, "kmm_map_bam: \"record_bam_mates\" is 1 and pair %lld of the stream is none: records %lld and %lld "
+                        "are not mates (their read_name bytes differ): collate the file by name (`samtools collate`) and exclude secondary "
+                        "and supplementary records (0x900) (nothing of the call is appended)", p, 2 * p, 2 * p + 1);
+        }
+        const bool odd = (n_rec & 1) != 0;
+        if (odd != (h_ctl[1] != kmm_bam::NONE) || (odd && (h_ctl[1] >= co.consumed || h_ctl[2] > co.consumed - h_ctl[1]))) {
+            (void)tm.end();
+            return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld selected records with the carry, the odd last one reported at %llu (%llu bytes)",
+                        (long long)n_rec, h_ctl[1], h_ctl[2]);
+        }
+        if (c.last_chunk && odd) {
+            (void)tm.end();
+            return bam_raw_mates_unpaired((long long)(2 * ix->bam_pairs_done + 1));
+        }
+        if (odd) {
+            // the odd last record's text (what the inner call left) and raw bytes go to the SPARE carry buffers, before anything is
+            // appended: a failure here still leaves the queues and the waiting mate as the call found them
+            const int64_t left = n_text - taken;
+            KMMCHK(ensure(ix->bam_mate_next, (size_t)left + 64)); // (may free and reallocate: a device-wide sync, rare)
+            KMMCHK(ensure(ix->bam_raw_mate_next, (size_t)h_ctl[2] + 64));
+            HIPCHK(hipMemcpyAsync(ix->bam_mate_next.p, (const uint8_t *)ix->bam_out.p + taken, (size_t)left, hipMemcpyDeviceToDevice, ix->stream));
+            HIPCHK(hipMemcpyAsync(ix->bam_raw_mate_next.p, be.d + h_ctl[1], (size_t)h_ctl[2], hipMemcpyDeviceToDevice, ix->stream));
+        }
+        if (n_entries > 0) {
+            KMMCHK(rkq_reserve(ix, q, (int64_t)co.consumed + (int64_t)carry_len));
+            unsigned long long *tail = (unsigned long long *)q.ctl.p;
+            hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)kept_bytes, 1u, n_tiles, byte_base, tot);
+            hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)kept_recs, 1u, n_tiles,
+                               (unsigned long long *)nullptr, tot + 1);
+            if (carried) {
+                const unsigned blocks = (unsigned)std::min<uint64_t>(((uint64_t)carry_len + 4095) / 4096, 64);
+                hipLaunchKernelGGL(kmm_bam::k_bam_raw_carry, dim3(blocks), dim3(256), 0, ix->stream, d_carry, carry_len, hits, windows, n_entries,
+                                   rule, (const unsigned long long *)tail, (uint8_t *)q.text.p);
+            }
+            if (be.selected)
+                hipLaunchKernelGGL(kmm_bam::k_bam_raw_copy_pairs<true>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref,
+                                   sel, tl, (const unsigned long long *)rec_base, hits, windows, n_entries, rule, carried, carry_len,
+                                   (const uint32_t *)kept_bytes, (const unsigned long long *)byte_base, (const unsigned long long *)tail,
+                                   (uint8_t *)q.text.p);
+            else
+                hipLaunchKernelGGL(kmm_bam::k_bam_raw_copy_pairs<false>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref,
+                                   sel, tl, (const unsigned long long *)rec_base, hits, windows, n_entries, rule, carried, carry_len,
+                                   (const uint32_t *)kept_bytes, (const unsigned long long *)byte_base, (const unsigned long long *)tail,
+                                   (uint8_t *)q.text.p);
+            hipLaunchKernelGGL(kmm_bam::k_bam_raw_advance_pairs, dim3(1), dim3(64), 0, ix->stream, tail, (const unsigned long long *)tot, hits, windows,
+                               n_entries, rule, carried, carry_len);
+            HIPCHK(hipGetLastError());
+            q.bound += (int64_t)co.consumed + (int64_t)carry_len;
+        }
+        KMMCHK(tm.end());
+        return KMM_OK;
+    };
+    const int rc = body();
+    if (rc != KMM_OK) {
+        put_back(true);
+        return rc;
+    }
+    ix->rk_snap.valid = false;
+    // the next carry: what body() put into the spare buffers becomes the waiting mate (the kernels that read the old one are queued
+    // in front of whatever writes that buffer next); nothing here can fail
+    if ((n_rec & 1) != 0) {
+        std::swap(ix->bam_mate, ix->bam_mate_next);
+        std::swap(ix->bam_raw_mate, ix->bam_raw_mate_next);
+        ix->bam_mate_len = n_text - taken;
+        ix->bam_raw_mate_len = (int64_t)h_ctl[2];
+    } else {
+        ix->bam_mate_len = 0;
+        ix->bam_raw_mate_len = 0;
+    }
+    if (c.n_records)
+        *c.n_records = recs;
+    return KMM_OK;
+}
+
 // The inflated bytes of a kmm_map_bam call (d_raw[0, n_raw): the carry of the call before in front): the header on a stream's
 // first call, then the records up to the last complete one (*used), decoded into two-line FASTA in HBM and mapped by
 // kmm_map_records.  *short_header: a first window that ends inside the header (nothing is used).
@@ -4237,6 +4452,8 @@ static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw
     *used = (int64_t)co.consumed;
     if (bam_mates_on(ix))
         return bam_map_mates(ix, c, be, co, n_raw);
+    if (bam_raw_mates_on(ix))
+        return bam_map_raw_mates(ix, c, be, co, n_raw, qual);
     if (co.recs == 0)
         return KMM_OK;
     KMMCHK(ensure(ix->bam_out, (size_t)co.out_bytes + 64));
@@ -4286,12 +4503,14 @@ int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags,
             return fail(KMM_ERR_INVALID_ARG, "kmm_map_bam: \"record_names_pairs\" and \"record_pairs\" are 1: the first pairs the records "
                         "of a BAM stream, the second those of FASTQ and two-line FASTA text; set one of them to 0 (nothing is mapped)");
         if (c.new_stream)
-            ix->bam_mate_len = ix->bam_pairs_done = 0; // (a mate 1 left over belongs to the stream before)
+            ix->bam_mate_len = ix->bam_pairs_done = ix->bam_raw_mate_len = 0; // (a mate 1 left over belongs to the stream before)
         BgzfCall b;
         KMMCHK(bgzf_inflate(ix, c, comp, n_comp, b, bgzf_rank_share));
         if (!b.d_raw) { // (no member and no carried byte: a last call that brings nothing can still leave a mate 1 alone)
             if (c.last_chunk && bam_mates_on(ix) && ix->bam_mate_len > 0)
                 return bam_mates_unpaired((long long)(2 * ix->bam_pairs_done + 1));
+            if (c.last_chunk && bam_raw_mates_on(ix) && ix->bam_mate_len > 0)
+                return bam_raw_mates_unpaired((long long)(2 * ix->bam_pairs_done + 1));
             return KMM_OK;
         }
         int64_t used = 0;
@@ -5678,7 +5897,32 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
                             "take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue (kmm_reset_counts) first",
                             (long long)value, tail[0], ix->record_bam);
         }
+        if ((int)value != ix->record_bam) // (a waiting mate 1 holds FASTA text under the raw form, named FASTQ under DESIGN 4.23's)
+            ix->bam_mate_len = ix->bam_raw_mate_len = 0;
         ix->record_bam = (int)value;
+    } else if (!strcmp(name, "record_bam_mates")) {
+        // 1: kmm_map_bam with "record_bam" takes the selected records of a stream as mates in file order — 2p and 2p + 1 — checks
+        // that their read_name bytes agree and keeps or drops their own bytes together; even counts, as "record_pairs"
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "record_bam_mates takes 0 or 1");
+        if ((int)value != ix->record_bam_mates) {
+            if (ix->rhq_pending > 0)
+                return fail(KMM_ERR_INVALID_ARG, "record_bam_mates %lld with %lld entries pending that were appended under record_bam_mates "
+                            "%d: take them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
+                            (long long)ix->rhq_pending, ix->record_bam_mates);
+            if (ix->rkq[0].ctl.p) {
+                HIPCHK(hipSetDevice(ix->device));
+                KMMCHK(drain(ix));
+                unsigned long long tail[2];
+                KMMCHK(rkq_tail(ix->rkq[0], tail));
+                if (tail[0] > 0)
+                    return fail(KMM_ERR_INVALID_ARG, "record_bam_mates %lld with %llu kept bytes pending that were appended under "
+                                "record_bam_mates %d: take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue "
+                                "(kmm_reset_counts) first", (long long)value, tail[0], ix->record_bam_mates);
+            }
+            ix->bam_mate_len = ix->bam_raw_mate_len = 0; // (a mate 1 that waits under one pair mode is no carry of the other's)
+        }
+        ix->record_bam_mates = (int)value;
     } else if (!strcmp(name, "original_strand")) {
         // 1: kmm_map_bam and KMM_FORMAT_SAM hand every kept record whose FLAG has 0x10 to the mapper in read orientation
         if (value != 0 && value != 1)
@@ -5767,6 +6011,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->record_names_mate_suffix;
     else if (!strcmp(name, "record_bam"))
         *value = ix->record_bam;
+    else if (!strcmp(name, "record_bam_mates"))
+        *value = ix->record_bam_mates;
     else if (!strcmp(name, "record_keep"))
         *value = ix->record_keep;
     else if (!strcmp(name, "record_keep_min_hits"))

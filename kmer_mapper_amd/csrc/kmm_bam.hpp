@@ -33,6 +33,10 @@
 // The raw form ("record_bam"; k_bam_raw_*): behind the record-hits mode's decode and mapping, the selected records whose
 // entry passes the keep rule are appended to the keep queue AS THEY STAND — block_size word and all — by a walk of the verified
 // claims with the same predicate: a scan of the tiles' record counts, a count, a scan of the kept bytes, a copy, the tail's advance.
+// Mates kept together in the raw form ("record_bam_mates"; k_bam_raw_*_pairs, k_bam_raw_pair_names, k_bam_raw_carry): the
+// selected records are mates in file order; the count walk decides per pair, leaves every selected record's start by entry and
+// reports an odd last record, the mate check compares the read_name bytes of every pair from those starts, and the mate 1 that a
+// window left over goes to the queue from a buffer of the handle, in front of the next window's records.
 // Exactness never depends on the plausibility test: a wrong guess only costs a fix.  Every read is bounds-checked against n.
 // resync (kmm_bam_find_record_start) is the other use of the plausibility test: in inflated bytes that begin anywhere
 // in the stream — a rank's share of a file — k_bam_resync finds the lowest position from which the chain of records holds to the
@@ -691,6 +695,104 @@ KMM_BAM_HD void raw_copy_part(const uint8_t *src, uint8_t *queue, uint64_t dst, 
         g[i] = src[i - a];
 }
 
+// ---- mates kept together in the raw form ("record_bam_mates"): the selected records of the stream are mates in file
+// order, 2p and 2p + 1, kept or dropped together.  A call's entries are those of its whole pairs, n_entries = 2P of them; a mate 1
+// that the window before left over is entry 0 (`carried` = 1: its raw bytes wait in a buffer of the handle), so selected record i
+// of the call has entry carried + i.  The record whose entry would be 2P is the odd last one: it waits for the next call.
+
+// The two entries of the pair that entry e belongs to.
+KMM_BAM_HD uint64_t pair_first(uint64_t e) { return e & ~1ull; }
+KMM_BAM_HD uint64_t pair_second(uint64_t e) { return e | 1ull; }
+
+// Is the pair of entry e kept?  Both indices are bounded by the call's entry count.
+KMM_BAM_HD bool raw_pair_kept(const uint32_t *hits, const uint32_t *windows, uint64_t n_entries, uint64_t e, const RkPairRule &rule)
+{
+    const uint64_t a = pair_first(e), b = pair_second(e);
+    if (b >= n_entries)
+        return false;
+    return rk_pair_keep(hits[a], windows ? windows[a] : 0u, hits[b], windows ? windows[b] : 0u, rule.rule, rule.pair_rule);
+}
+
+// The bytes the carried mate 1 takes in front of the tiles' records: its length when its pair (entries 0 and 1) is kept.
+KMM_BAM_HD uint64_t raw_carry_shift(const uint32_t *hits, const uint32_t *windows, uint64_t n_entries, const RkPairRule &rule, uint32_t carried,
+                                    uint32_t carry_len)
+{
+    return carried && raw_pair_kept(hits, windows, n_entries, 0, rule) ? carry_len : 0u;
+}
+
+// The pair form of raw_walk_tile: entry0 = carried + the record base of the tile.  at(e, p) for every selected record that has an
+// entry (the mate check reads the starts by entry); visit(p, len, off) for every record of a kept pair; odd(p, len) for the odd
+// last record, which is neither counted nor visited (no selected record lies behind it).
+template <class Selected, class At, class Visit, class Odd>
+KMM_BAM_HD uint32_t raw_walk_tile_pairs(const uint8_t *d, uint64_t n, int32_t n_ref, const Tile &c, uint64_t entry0, const uint32_t *hits,
+                                        const uint32_t *windows, uint64_t n_entries, const RkPairRule &rule, uint32_t *kept_recs,
+                                        Selected &&is_selected, At &&at, Visit &&visit, Odd &&odd)
+{
+    uint32_t bytes = 0, recs = 0;
+    if (c.entry != NONE && c.entry != INVALID && c.recs != 0) {
+        uint64_t p = c.entry, e = entry0;
+        const uint64_t e_end = entry0 + c.recs;
+        while (p < c.exit) {
+            RecHead h;
+            if (record_at(d, n, p, n_ref, h) != REC_OK) // (cannot happen on a verified chain; bounds all the same)
+                break;
+            if (is_selected(d + p, h)) {
+                if (e >= e_end) // (cannot happen: the walk that counted and this one ask one predicate)
+                    break;
+                if (e >= n_entries) {
+                    if (e == n_entries)
+                        odd(p, raw_len(h));
+                    break;
+                }
+                at(e, p);
+                if (raw_pair_kept(hits, windows, n_entries, e, rule)) {
+                    visit(p, raw_len(h), bytes);
+                    bytes += raw_len(h);
+                    ++recs;
+                }
+                ++e;
+            }
+            p += 4ull + h.bs;
+        }
+    }
+    *kept_recs = recs;
+    return bytes;
+}
+
+// The mate check compares read_name as it stands: l bytes (l_read_name, the NUL included) at na and nb; the share of lane `lane`
+// of `lanes` — true iff one of its bytes differs.  The callers have compared the two lengths.
+KMM_BAM_HD bool names_differ_part(const uint8_t *na, const uint8_t *nb, uint32_t l, uint32_t lane, uint32_t lanes)
+{
+    bool diff = false;
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (uint32_t i = lane; i < l; i += lanes)
+        diff |= na[i] != nb[i];
+    return diff;
+}
+
+// The mate check of one pair: the records of entries 2P and 2P + 1 start at pos_a and pos_b of d[0, consumed) — the count walk left
+// the starts there, NONE where it left none — or, for the mate 1 that was carried in (a_carry: carry[0, carry_len) holds its raw
+// bytes), in the carry buffer.  Mates have equal l_read_name and equal read_name bytes; differ(na, nb, l) says whether any lane
+// found a difference.  Every read is bounded: the fixed head and the name lie in front of `consumed` (of carry_len).  True iff
+// the two are no mates; a pair whose starts are not both known is none.
+template <class Differ>
+KMM_BAM_HD bool raw_names_pair(const uint8_t *d, uint64_t consumed, uint64_t pos_a, uint64_t pos_b, bool a_carry, const uint8_t *carry,
+                               uint32_t carry_len, Differ &&differ)
+{
+    const uint8_t *a = a_carry ? carry : d + pos_a;
+    const uint64_t a_room = a_carry ? (uint64_t)carry_len : (pos_a < consumed ? consumed - pos_a : 0ull);
+    const uint64_t b_room = pos_b < consumed ? consumed - pos_b : 0ull;
+    if ((a_carry ? carry == nullptr : pos_a == NONE) || pos_b == NONE || a_room < 37 || b_room < 37)
+        return true;
+    const uint8_t *b = d + pos_b;
+    const uint32_t la = a[12], lb = b[12];
+    if (36ull + la > a_room || 36ull + lb > b_room)
+        return true;
+    return la != lb || differ(a + 36, b + 36, la);
+}
+
 // ---- the header (host side: the library reads it back once per stream) ----
 
 // d[0, n) = the stream's first inflated bytes.  0: the header ends at *hdr_end and names *n_ref references; 1: it goes on
@@ -951,6 +1053,77 @@ struct CpuBackend {
                                   raw_copy_part(d + p, queue, raw_dest(tail, raw_byte_base[t], off), len, lane, lanes);
                           });
         }
+    }
+    // Mates kept together ("record_bam_mates"): the pair forms of the two steps above, over the n_entries = 2P entries of
+    // the call's whole pairs (carried: a mate 1 was carried in and is entry 0).  raw_count_pairs() also reports the odd last record
+    // (*odd_pos NONE: there is none).  raw_pair_names(): the lowest pair ordinal of the call whose two records are no mates (NONE:
+    // all are), over the records in front of `consumed`.  raw_carry_copy(): the carried mate 1 to queue[tail, tail + len).
+    std::vector<uint64_t> raw_pos; // the start of the selected record of every entry (NONE: the carried one's, or none left)
+    uint64_t raw_count_pairs(const uint32_t *hits, const uint32_t *windows, uint64_t n_entries, const RkPairRule &rule, uint32_t carried,
+                             uint64_t *kept_recs, uint64_t *odd_pos, uint32_t *odd_len)
+    {
+        raw_pos.assign(n_entries, NONE);
+        const auto is_sel = [&](const uint8_t *rec, const RecHead &h) { return is_kept((uint64_t)(rec - d), h); };
+        raw_rec_base.assign(cur.size(), 0);
+        raw_byte_base.assign(cur.size(), 0);
+        raw_kept_bytes.assign(cur.size(), 0);
+        uint64_t recs = 0, bytes = 0, kept = 0;
+        *odd_pos = NONE;
+        *odd_len = 0;
+        for (uint64_t t = 0; t < cur.size(); ++t) {
+            raw_rec_base[t] = recs;
+            recs += cur[t].recs;
+            uint32_t kr = 0;
+            raw_kept_bytes[t] = raw_walk_tile_pairs(d, n, n_ref, cur[t], carried + raw_rec_base[t], hits, windows, n_entries, rule, &kr, is_sel,
+                                                    [&](uint64_t e, uint64_t p) { raw_pos[e] = p; },
+                                                    [](uint64_t, uint32_t, uint32_t) {},
+                                                    [&](uint64_t p, uint32_t len) {
+                                                        *odd_pos = p;
+                                                        *odd_len = len;
+                                                    });
+            kept += kr;
+        }
+        for (uint64_t t = 0; t < cur.size(); ++t) {
+            raw_byte_base[t] = bytes;
+            bytes += raw_kept_bytes[t];
+        }
+        *kept_recs = kept;
+        return bytes;
+    }
+    void raw_copy_pairs(const uint32_t *hits, const uint32_t *windows, uint64_t n_entries, const RkPairRule &rule, uint32_t carried,
+                        uint8_t *queue, uint64_t tail)
+    {
+        const auto is_sel = [&](const uint8_t *rec, const RecHead &h) { return is_kept((uint64_t)(rec - d), h); };
+        for (uint64_t t = 0; t < cur.size(); ++t) {
+            uint32_t kr = 0;
+            raw_walk_tile_pairs(d, n, n_ref, cur[t], carried + raw_rec_base[t], hits, windows, n_entries, rule, &kr, is_sel,
+                                [](uint64_t, uint64_t) {},
+                                [&](uint64_t p, uint32_t len, uint32_t off) {
+                                    if ((uint64_t)off + len > raw_kept_bytes[t])
+                                        return;
+                                    for (uint32_t lane = 0; lane < lanes; ++lane)
+                                        raw_copy_part(d + p, queue, raw_dest(tail, raw_byte_base[t], off), len, lane, lanes);
+                                },
+                                [](uint64_t, uint32_t) {});
+        }
+    }
+    uint64_t raw_pair_names(uint64_t consumed, uint64_t n_entries, uint32_t carried, const uint8_t *carry, uint32_t carry_len)
+    {
+        for (uint64_t pr = 0; 2 * pr + 1 < n_entries && 2 * pr + 1 < raw_pos.size(); ++pr)
+            if (raw_names_pair(d, consumed, raw_pos[2 * pr], raw_pos[2 * pr + 1], carried && pr == 0, carry, carry_len,
+                               [&](const uint8_t *na, const uint8_t *nb, uint32_t l) {
+                                   bool diff = false;
+                                   for (uint32_t lane = 0; lane < lanes; ++lane)
+                                       diff |= names_differ_part(na, nb, l, lane, lanes);
+                                   return diff;
+                               }))
+                return pr;
+        return NONE;
+    }
+    void raw_carry_copy(const uint8_t *carry, uint32_t len, uint8_t *queue, uint64_t tail) const
+    {
+        for (uint32_t lane = 0; lane < lanes; ++lane)
+            raw_copy_part(carry, queue, tail, len, lane, lanes);
     }
 };
 
@@ -1500,6 +1673,116 @@ __global__ void k_bam_raw_advance(unsigned long long *tail, const unsigned long 
 {
     if (threadIdx.x < 2 && blockIdx.x == 0)
         tail[threadIdx.x] += total[threadIdx.x];
+}
+
+// ---- mates kept together in the raw form ("record_bam_mates"): kernels of their own, so that the unpaired forms above
+// stay as they are.  ctl: three control words of the call — [0] the lowest pair ordinal whose records are no mates, [1] and [2]
+// the start and the length of the odd last record — all NONE before the launches.
+
+// count, the pair form: as k_bam_raw_count with raw_walk_tile_pairs; the wavefront that meets the odd last record reports it.
+template <bool S>
+__global__ void __launch_bounds__(256) k_bam_raw_count_pairs(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref, Sel sel,
+                                                             const Tile *__restrict__ in, const unsigned long long *__restrict__ rec_base,
+                                                             const uint32_t *__restrict__ hits, const uint32_t *__restrict__ windows,
+                                                             uint64_t n_entries, RkPairRule rule, uint32_t carried,
+                                                             uint32_t *__restrict__ kept_bytes, uint32_t *__restrict__ kept_recs,
+                                                             unsigned long long *__restrict__ pos, unsigned long long *__restrict__ ctl)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        uint32_t recs = 0;
+        const uint32_t bytes = raw_walk_tile_pairs(
+            d, n, n_ref, in[t], carried + rec_base[t], hits, windows, n_entries, rule, &recs,
+            [&](const uint8_t *rec, const RecHead &h) { return S ? kept_wave(rec, h, sel) : !(h.flag & sel.excl); },
+            [&](uint64_t e, uint64_t p) {
+                if (lane == 0)
+                    pos[e] = p;
+            },
+            [](uint64_t, uint32_t, uint32_t) {},
+            [&](uint64_t p, uint32_t len) {
+                if (lane == 0) {
+                    ctl[1] = p;
+                    ctl[2] = len;
+                }
+            });
+        if (lane == 0) {
+            kept_bytes[t] = bytes;
+            kept_recs[t] = recs;
+        }
+    }
+}
+
+// names: one wavefront per pair of the call (grid-stride) — raw_names_pair over the starts that the count walk left by entry; two
+// names are compared 64 bytes a round, a ballot says whether a lane found a difference.  The lowest ordinal of a pair of
+// strangers goes to ctl[0].  No chain is walked here: records that are not selected between two mates cost nothing.
+__global__ void __launch_bounds__(256) k_bam_raw_pair_names(const uint8_t *__restrict__ d, uint64_t consumed,
+                                                            const unsigned long long *__restrict__ pos, uint64_t n_entries, uint32_t carried,
+                                                            const uint8_t *__restrict__ carry, uint32_t carry_len,
+                                                            unsigned long long *__restrict__ ctl)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u), n_pairs = n_entries / 2;
+    for (uint64_t pr = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; pr < n_pairs; pr += waves) {
+        const bool strangers = raw_names_pair(
+            d, consumed, pos[2 * pr], pos[2 * pr + 1], carried && pr == 0, carry, carry_len,
+            [&](const uint8_t *na, const uint8_t *nb, uint32_t l) { return __ballot(names_differ_part(na, nb, l, lane, 64u)) != 0ull; });
+        if (lane == 0 && strangers)
+            atomicMin(ctl, (unsigned long long)pr);
+    }
+}
+
+// carry: the carried mate 1 goes to the queue's tail when its pair is kept — every thread of the grid a share of raw_copy_part.
+__global__ void __launch_bounds__(256) k_bam_raw_carry(const uint8_t *__restrict__ carry, uint32_t carry_len, const uint32_t *__restrict__ hits,
+                                                       const uint32_t *__restrict__ windows, uint64_t n_entries, RkPairRule rule,
+                                                       const unsigned long long *__restrict__ tail, uint8_t *__restrict__ queue)
+{
+    if (raw_carry_shift(hits, windows, n_entries, rule, 1u, carry_len) == 0)
+        return;
+    raw_copy_part(carry, queue, tail[0], carry_len, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+// copy, the pair form: as k_bam_raw_copy; the tiles' bytes lie behind the carried mate 1 where that one is kept.
+template <bool S>
+__global__ void __launch_bounds__(256) k_bam_raw_copy_pairs(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref, Sel sel,
+                                                            const Tile *__restrict__ in, const unsigned long long *__restrict__ rec_base,
+                                                            const uint32_t *__restrict__ hits, const uint32_t *__restrict__ windows,
+                                                            uint64_t n_entries, RkPairRule rule, uint32_t carried, uint32_t carry_len,
+                                                            const uint32_t *__restrict__ kept_bytes,
+                                                            const unsigned long long *__restrict__ byte_base,
+                                                            const unsigned long long *__restrict__ tail, uint8_t *__restrict__ queue)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    const uint64_t tail0 = tail[0] + raw_carry_shift(hits, windows, n_entries, rule, carried, carry_len);
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        const uint32_t share = kept_bytes[t];
+        if (share == 0)
+            continue;
+        const uint64_t base = byte_base[t];
+        uint32_t recs = 0;
+        raw_walk_tile_pairs(
+            d, n, n_ref, in[t], carried + rec_base[t], hits, windows, n_entries, rule, &recs,
+            [&](const uint8_t *rec, const RecHead &h) { return S ? kept_wave(rec, h, sel) : !(h.flag & sel.excl); },
+            [](uint64_t, uint64_t) {},
+            [&](uint64_t p, uint32_t len, uint32_t off) {
+                if ((uint64_t)off + len <= share)
+                    raw_copy_part(d + p, queue, raw_dest(tail0, base, off), len, lane, 64u);
+            },
+            [](uint64_t, uint32_t) {});
+    }
+}
+
+// advance, the pair form: the tiles' totals and the carried mate 1 where it is kept
+__global__ void k_bam_raw_advance_pairs(unsigned long long *tail, const unsigned long long *__restrict__ total, const uint32_t *__restrict__ hits,
+                                        const uint32_t *__restrict__ windows, uint64_t n_entries, RkPairRule rule, uint32_t carried,
+                                        uint32_t carry_len)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        const uint64_t shift = raw_carry_shift(hits, windows, n_entries, rule, carried, carry_len);
+        tail[0] += total[0] + shift;
+        tail[1] += total[1] + (shift ? 1ull : 0ull);
+    }
 }
 
 // resync: one wavefront per tile (grid-stride), the shape of spec; lanes test 64 consecutive positions, the survivors are

@@ -440,12 +440,19 @@ class DeviceIndex:
         self.set_param("record_names_mate_suffix", int(bool(mate_suffix)))
         self.set_param("record_names", int(bool(on)))
 
-    def record_bam(self, on=True):
+    def record_bam(self, on=True, mates=False):
         """The raw form of the keep (include/kmm.h), on top of record_hits() and record_keep(): map_bam maps the
         selected records as without the switch and appends every kept record AS IT STANDS IN THE FILE — its block_size word and
         the block_size bytes behind it — to the queue of take_kept_records() / take_kept_bgzf(); bam_header() has the header that
-        goes in front.  The text routes never read it.  Refused while kept bytes are pending."""
+        goes in front.  The text routes never read it.  Refused while kept bytes are pending.
+        mates: the selected records of a map_bam stream are mates in file order — 2p and 2p + 1, as in a
+        name-collated file — kept or dropped together under record_pairs()'s rule; their read_name bytes are compared on the GPU
+        and a pair of strangers, or an unpaired last record, fails the call.  Refused while hit entries or kept bytes are pending."""
+        if not (on and mates):
+            self.set_param("record_bam_mates", 0)
         self.set_param("record_bam", int(bool(on)))
+        if on and mates:
+            self.set_param("record_bam_mates", 1)
 
     def take_kept_records(self, out=None):
         """kmm_take_kept_records: ALL pending bytes — the kept records, whole, in stream order — as (np.uint8 array, n_records);

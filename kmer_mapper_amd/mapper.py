@@ -146,7 +146,7 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
 
 def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
                    min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False, compress=False, pairs=False,
-                   pair_rule="any", output="fastq"):
+                   pair_rule="any", output="fastq", keep_mates=False):
     """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
     text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
     (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
@@ -164,8 +164,13 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     output "bam" (fmt "bam"): the kept records come back AS BAM RECORDS, untouched — RNAME, POS, MAPQ, CIGAR, mate
     fields and aux tags included — and the text returned is the bytes of a complete BAM file: the input's header, verbatim, as BGZF
     members of its own, the kept records' members (deflated on the GPU), the end-of-file block.  original_strand then applies
-    to the hits alone; mate_suffix, pairs and compress do not go with it."""
+    to the hits alone; mate_suffix, pairs and compress do not go with it.
+    keep_mates (output "bam"): the file is name-collated and mates are kept or dropped together under pair_rule, as
+    with `pairs`, but as BAM records: both records of every kept pair, untouched, mate 1 directly in front of mate 2.  The mate
+    check compares the read_name bytes as they stand; strangers or an unpaired last record raise ValueError with the hint."""
     from . import _lib
+    if keep_mates and output != "bam":
+        raise ValueError("keep_mates goes with output=\"bam\": mates kept together as BAM records (FASTQ out: pairs=True)")
     if output not in ("fastq", "bam"):
         raise ValueError("output must be 'fastq' or 'bam', not %r" % (output,))
     if output == "bam" and fmt != "bam":
@@ -194,10 +199,10 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
             before = (dev.get_param("bam_exclude_flags"), dev.get_param("original_strand"), dev.get_param("record_pairs_rule"))
             dev.set_param("bam_exclude_flags", int(exclude_flags))
             dev.set_param("original_strand", int(bool(original_strand)))
-            if pairs:
+            if pairs or keep_mates:
                 dev.set_param("record_pairs_rule", dev.PAIR_RULES[pair_rule])
             if output == "bam":
-                dev.record_bam(True)
+                dev.record_bam(True, mates=keep_mates)
             else:
                 dev.record_names(True, mate_suffix=mate_suffix, pairs=pairs)
             dev.map_bam(raw, first=True, last=True, k=k, max_index_lookup_frequency=max_index_lookup_frequency,
@@ -219,6 +224,8 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
             if output == "bam":
                 if dev.get_param("record_keep_pending_bytes"):                      # (a take that failed: raw records never meet text)
                     dev.take_kept_records()
+                if keep_mates and dev.get_param("record_hits_pending"):             # (a take that failed: the switch stays with its entries)
+                    dev.take_record_hits()
                 dev.record_bam(False)
             elif pairs and dev.get_param("record_hits_pending"):                    # (a take that failed: the switch stays with its entries)
                 dev.set_param("record_names", 0)
