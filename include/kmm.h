@@ -702,6 +702,28 @@ int kmm_take_kept_records(kmm_index_t *idx, uint8_t *out, int64_t capacity, int6
  * every call launches exactly what it launched without the parameter.  With timing on the kernels are timed together as
  * KMM_KERNEL_BAM_RAW_MATES.  Out of scope: coordinate-sorted input (the check reports it), singletons diverted, a rank's share,
  * a requirement that FLAG has 0x1, 0x40 or 0x80.
+ *
+ * SAM LINES KEPT AS SAM LINES.  "record_sam" 0 (default) / 1 / 2 (anything else KMM_ERR_INVALID_ARG), read by
+ * KMM_FORMAT_SAM calls alone: kmm_map_records, and kmm_map_bgzf / kmm_map_gzip on their inflated bytes; FASTQ, FASTA and BAM calls
+ * never read it.  With 1 or 2 — and "record_hits" 1 or 2, "record_keep" 1 — the call's selected records are decoded to two-line
+ * FASTA and mapped as in the record-hits mode ("original_strand" honoured for the hits); the hits queue gains one entry per
+ * selected record in file order and none of the FASTA text is appended.  Behind that, every selected record whose entry passes
+ * the keep rule is appended to the queue of kmm_take_kept_records / kmm_take_kept_bgzf as its WHOLE LINE, from its first byte
+ * through its newline, untouched — a '\r' before the newline, lower-case SEQ and every tag come out as they went in — in file
+ * order.  With 1 every header line ('@' first) is appended too, verbatim, at its place in the stream; 2 drops the header lines
+ * (`samtools view` without -h: shares that are concatenated).  Records excluded by "bam_exclude_flags" or by the selection are not
+ * written.  "record_keep_pending_records" counts records, not header lines.  The one byte that is not input is the newline that
+ * KMM_FORMAT_LAST_CHUNK supplies for a final unterminated line on the stream routes.  "sam_records", "sam_records_excluded",
+ * "sam_header_lines", *consumed, *n_records, the node counts and kmm_get_stats are what the record-hits mode reports.  The queue's
+ * tail stays on the device; the call makes no host round trip beyond those of the record-hits mode, and no walk over the lines
+ * beyond the count and one write.  A failing call (a malformed line anywhere in the chunk, a failure of the inner call or behind
+ * it) appends nothing to either queue.
+ * Refused with KMM_ERR_INVALID_ARG, nothing mapped, nothing appended: a SAM call with "record_sam" non-zero while "record_hits" or
+ * "record_keep" is 0, or with "record_pairs" 1; a change of "record_sam" while "record_keep_pending_bytes" > 0 (raw lines and text
+ * never share a queue).  With 0 every call launches exactly what it launched without the parameter, and SAM stays refused in the
+ * keep mode with its text.  With timing on the kernels of the keep step are timed together as KMM_KERNEL_SAM_RAW.  Out of scope:
+ * mates kept together, SAM to FASTQ with names, SAM in with BAM out (or BAM in with SAM out), a rank's share, an @PG line, a
+ * quality floor (the record-hits mode refuses one).
  */
 int kmm_bam_stream_header(kmm_index_t *idx, uint8_t *out, int64_t capacity, int64_t *n_bytes);
 int kmm_map_record_pairs(kmm_index_t *idx, const uint8_t *raw1, int64_t n1, const uint8_t *raw2, int64_t n2, int format, int k,
@@ -770,7 +792,8 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
 #define KMM_KERNEL_BGZF_GATHER 8  /* BGZF writer: member offsets + the members one behind the other       */
 #define KMM_KERNEL_BAM_RAW 9      /* "record_bam": record base, count, scans, copy and advance of the kept BAM records */
 #define KMM_KERNEL_BAM_RAW_MATES 10 /* "record_bam_mates": the pair forms of the above, the mate check and the carried mate 1 */
-#define KMM_N_KERNELS 11
+#define KMM_KERNEL_SAM_RAW 11     /* "record_sam": the tiles' scan, flags, block scan, copy and advance of the kept SAM lines */
+#define KMM_N_KERNELS 12
 int kmm_set_timing(kmm_index_t *idx, int enabled);
 /* Work done by the map calls of this handle since creation (or the last call with reset != 0):
  * k-mer lookups performed (windows, doubled with also_revcomp) and count increments (index hits that
@@ -949,6 +972,8 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      names are compared on the device and they are kept or dropped together; see THE MATES OF A BAM STREAM
  *   "record_bam"       0 (default) / 1: kmm_map_bam with "record_hits" and "record_keep" appends the kept records' own bytes
  *                      (block_size word and all) to the keep queue instead of text; see THE RAW FORM, kmm_bam_stream_header
+ *   "record_sam"       0 (default) / 1 / 2: a KMM_FORMAT_SAM call with "record_hits" and "record_keep" appends the kept records'
+ *                      own lines to the keep queue, 1 with the header lines, 2 without; see SAM LINES KEPT AS SAM LINES
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_records_grid" test hook of kmm_map_records: workgroups (four wavefronts each) of the two per-tile kernels of the

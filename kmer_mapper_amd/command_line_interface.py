@@ -952,7 +952,7 @@ class RecordKeepSink(RecordHitsSink):
     BGZF members — every drain ends its last member; close() writes the end-of-file block; kept_bytes still counts text."""
 
     def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False, pairs=False, pair_rule="any",
-                 out2=None, bgzf=False, bam_pairs=False, bam_out=False, bam_mates=False):
+                 out2=None, bgzf=False, bam_pairs=False, bam_out=False, bam_mates=False, sam_out=False, sam_header=True):
         super().__init__(windows=True)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
@@ -970,6 +970,8 @@ class RecordKeepSink(RecordHitsSink):
         self.bam_out = bool(bam_out)
         # mates kept together in BAM out: the selected records are mates in file order ("record_bam_mates")
         self.bam_mates = bool(bam_mates) and self.bam_out
+        # SAM out: the kept records' own lines ("record_sam"), behind the header lines unless sam_header is off
+        self.sam_out, self.sam_header = bool(sam_out), bool(sam_header)
         self.header_written = False
         self.bgzf = bool(bgzf) or self.bam_out
         self.written = 0                     # bytes written to out and out2 (the members' with bgzf, else the text's)
@@ -983,6 +985,8 @@ class RecordKeepSink(RecordHitsSink):
             dev.record_bam(True, mates=True)
         elif self.bam_out:
             dev.record_bam(True)
+        if self.sam_out:
+            dev.record_sam(True, header=self.sam_header)
         if self.bam_pairs or self.bam_mates:
             dev.record_pairs(False, rule=self.pair_rule)
         if self.pairs or self.out2 is not None:
@@ -1051,20 +1055,21 @@ _SELECT_READS_BAM_ONLY = (("--bam-to-fastq", "bam_to_fastq"), ("--exclude-flags"
                           ("--as-stored", "as_stored"), ("--mate-suffix", "mate_suffix"), ("--bam-out", "bam_out"))
 
 
-def check_select_reads_input(fmt, world_size, reads, output, bam_to_fastq=False, bam_options=(), bam_out=False):
+def check_select_reads_input(fmt, world_size, reads, output, bam_to_fastq=False, bam_options=(), bam_out=False, sam_out=False):
     """`kmer_mapper select-reads` takes FASTA / FASTQ (plain or .gz) — and with --bam-to-fastq a BAM file, whose kept records
     come out as FASTQ, with --bam-out a BAM file whose kept records come out as BAM records — in one
     process and never writes over its input; everything else is refused before the index is read.  bam_options: the names of
-    the options given that go with BAM input alone."""
+    the options given that go with BAM input alone.  sam_out: --sam-out reads SAM text and writes the kept lines back."""
     if fmt == "bam" and not bam_to_fastq and not bam_out:
         raise ValueError("select-reads does not read %s files: their records are decoded on the GPU without the read's name, so "
                          "the selected text would be useless; SAM and BAM input is out of scope — unless --bam-to-fastq asks for "
                          "a BAM file's kept records as FASTQ, with their names and qualities (or --bam-out for the kept records "
                          "as a BAM file)" % fmt.upper())
-    if fmt == "sam":
+    if fmt == "sam" and not sam_out:
         raise ValueError("select-reads does not read %s files: their records are decoded on the GPU without the read's name, so "
                          "the selected text would be useless; SAM and BAM input is out of scope (--bam-to-fastq reads BAM, not "
-                         "SAM text: `samtools view -b` makes one of the other)" % fmt.upper())
+                         "SAM text: `samtools view -b` makes one of the other) — unless --sam-out asks for the kept records as "
+                         "SAM lines, untouched" % fmt.upper())
     if bam_options and fmt != "bam":
         raise ValueError("%s applies to BAM input only (the reads are %s)" % (bam_options[0], fmt))
     if world_size > 1:
@@ -1087,6 +1092,33 @@ def check_select_reads_bam_out(fmt, given):
                "--mate-suffix": "the names are not rewritten"}.get(opt, "mates are not kept together in BAM output, which has one "
                                                                         "input file (-f) and one output file (-o)")
         raise ValueError("select-reads: --bam-out does not go with %s: %s" % (opt, why))
+
+
+_SELECT_READS_NOT_WITH_SAM_OUT = (("--bam-to-fastq", "bam_to_fastq"), ("--bam-out", "bam_out"), ("--as-stored", "as_stored"),
+                                  ("--mate-suffix", "mate_suffix"), ("--bam-pairs", "bam_pairs"), ("--keep-mates", "keep_mates"),
+                                  ("--interleaved", "interleaved"), ("-f2/--reads2", "reads2"), ("-o2/--output2", "output2"))
+
+
+def check_select_reads_sam_out(fmt, sam_out, no_header=False, given=()):
+    """--sam-out of `kmer_mapper select-reads`: SAM text in (plain, BGZF or gzip), the kept records out as SAM
+    lines, untouched and in file order, behind the header lines (--no-header: without them).  given: the names of the other
+    options given that change the form of the output or pair the reads — none goes with it.  Refused before the index is read
+    and before -o is created."""
+    if no_header and not sam_out:
+        raise ValueError("select-reads: --no-header goes with --sam-out: it leaves the header lines out of SAM output")
+    if not sam_out:
+        return
+    if fmt != "sam":
+        raise ValueError("--sam-out applies to SAM input only (the reads are %s): SAM lines are written from SAM lines%s"
+                         % (fmt, "; a BAM file has --bam-out" if fmt == "bam" else ""))
+    for opt in given:
+        why = {"--bam-to-fastq": "it reads BAM, and the kept records leave as SAM lines, not as FASTQ",
+               "--bam-out": "BAM records are written from BAM records: `samtools view -b` makes a BAM file of the output",
+               "--as-stored": "the lines are written as they stand in the file in any case; the strand matters to the hits alone, "
+                              "which are counted in read orientation",
+               "--mate-suffix": "the names are not rewritten"}.get(opt, "mates are not kept together in SAM output, which has one "
+                                                                        "input file (-f) and one output file (-o)")
+        raise ValueError("select-reads: --sam-out does not go with %s: %s" % (opt, why))
 
 
 def check_select_reads_keep_mates(keep_mates, bam_out):
@@ -1225,6 +1257,9 @@ def select_reads_file(args):
     bam_pairs = bool(getattr(args, "bam_pairs", False))
     bam_out = bool(getattr(args, "bam_out", False))
     keep_mates = bool(getattr(args, "keep_mates", False))
+    sam_out = bool(getattr(args, "sam_out", False))
+    check_select_reads_sam_out(probe.fmt, sam_out, bool(getattr(args, "no_header", False)),
+                               [opt for opt, name in _SELECT_READS_NOT_WITH_SAM_OUT if getattr(args, name, None)])
     check_select_reads_keep_mates(keep_mates, bam_out)
     if bam_out:
         check_select_reads_bam_out(probe.fmt, [opt for opt, name in (("--bam-to-fastq", "bam_to_fastq"), ("--as-stored", "as_stored"),
@@ -1235,9 +1270,10 @@ def select_reads_file(args):
         check_select_reads_bam_pairs(probe.fmt, bool(getattr(args, "bam_to_fastq", False)), interleaved, reads2, output2)
     check_select_reads_pairs(probe, args.reads, args.output_file, interleaved, reads2, output2,
                              None if bam_pairs or keep_mates else pair_rule)
-    bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None)]
+    # (with --sam-out the options that select records apply to SAM too; those that change the output's form were refused above)
+    bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None) and not sam_out]
     check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options,
-                             bam_out)
+                             bam_out, sam_out)
     if not 0 <= args.min_hit_permille <= 1000:
         raise ValueError("--min-hit-permille outside [0, 1000]")
     if args.min_hits < 0:
@@ -1245,6 +1281,14 @@ def select_reads_file(args):
     fmt = probe.fmt
     bam = fmt == "bam"
     more = {}
+    if sam_out:
+        # (the route `read-hits --device-parser` takes for SAM — plain, BGZF or gzip — with the hits counted in read orientation,
+        # as --bam-out counts them; the lines leave as they stand)
+        opt = lambda name, default=None: getattr(args, name, default)
+        select = check_record_select(fmt, include_flags=opt("include_flags", 0), min_mapq=opt("min_mapq", 0), regions=opt("regions"),
+                                     regions_file=opt("regions_file"))
+        more = dict(exclude_flags=int(opt("exclude_flags", 0) or 0), original_strand=check_original_strand(True, fmt),
+                    **({"record_select": select} if select else {}))
     if bam:
         # (the route `read-hits --device-parser` takes for BAM, with the names on; reverse-strand records in read orientation
         # unless --as-stored: a FASTQ of reverse-complemented reads is not what anyone wants from a BAM file)
@@ -1275,6 +1319,8 @@ def select_reads_file(args):
         fmt = "fasta_ml"
     logging.info("select-reads: records parsed on the GPU, record-hits and record-keep modes%s%s",
                  "; the kept BAM records written as they stand, behind the input's header (--bam-out)" if bam_out else
+                 "; the kept SAM lines written as they stand, %s the header lines (--sam-out)"
+                 % ("without" if getattr(args, "no_header", False) else "behind") if sam_out else
                  "; BAM records decoded to FASTQ with their names (--bam-to-fastq)" if bam else "",
                  "; neighbouring records are mates, kept together, pair rule '%s' (--bam-pairs)" % (pair_rule or "any") if bam_pairs else "")
     rule = dict(min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert,
@@ -1291,7 +1337,8 @@ def select_reads_file(args):
         with open(args.output_file, "wb") as out:
             sink = RecordKeepSink(out, names=bam and not bam_out, mate_suffix=bam and bool(getattr(args, "mate_suffix", False)),
                                   pairs=interleaved, pair_rule=pair_rule or "any", bam_pairs=bam_pairs, bam_out=bam_out,
-                                  **({"bam_mates": True} if keep_mates else {}), **rule)
+                                  **({"bam_mates": True} if keep_mates else {}),
+                                  **({"sam_out": True, "sam_header": not getattr(args, "no_header", False)} if sam_out else {}), **rule)
             try:
                 map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
                             device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more)
@@ -1444,7 +1491,7 @@ def build_argument_parser():
     sub = subparsers.add_parser("select-reads", help="Extension: write the reads whose k-mers hit a kmer index back out")
     sub.add_argument("-i", "--kmer-index", required=False)
     sub.add_argument("-b", "--index-bundle", required=False)
-    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format (BAM with --bam-to-fastq or --bam-out)")
+    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format (BAM with --bam-to-fastq or --bam-out, SAM text with --sam-out)")
     sub.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
     sub.add_argument("-c", "--chunk-size", required=False, type=int, default=2500000, help="N bytes to process in each chunk")
     sub.add_argument("-o", "--output-file", required=True,
@@ -1516,6 +1563,16 @@ def build_argument_parser():
                           "(0x900) are excluded; the read names of every pair are compared on the GPU, and neighbours that are no "
                           "mates (a coordinate-sorted file) or a last record without its mate are an error, after which -o is removed "
                           "(--hits-output is written behind a complete run alone: such an error leaves none).")
+    sub.add_argument("--sam-out", action="store_true", default=argparse.SUPPRESS,
+                     help="Read SAM text (plain, BGZF or gzip; inflated and parsed on the GPU) and write the kept records back out as "
+                          "SAM lines: every kept record's whole line as it stands in the input (RNAME, POS, CIGAR and every tag "
+                          "included), in file order, behind the header lines (verbatim: no @PG line). Plain text, or BGZF with "
+                          "--bgzf (htslib reads it as .sam.gz). Takes --min-hits, --min-hit-permille, --invert, --hits-output, "
+                          "--exclude-flags, --include-flags, --min-mapq, --regions and --regions-file; the hits of records with "
+                          "FLAG 0x10 are counted in read orientation. Does not go with --bam-to-fastq, --bam-out, --as-stored, "
+                          "--mate-suffix, --bam-pairs, --keep-mates, --interleaved or -f2 / -o2.")
+    sub.add_argument("--no-header", action="store_true", default=argparse.SUPPRESS,
+                     help="With --sam-out: leave the header lines out (`samtools view` without -h), for shares that are concatenated.")
     sub.add_argument("--bgzf", action="store_true", default=argparse.SUPPRESS,
                      help="Write -o (and -o2) as BGZF files: the kept text is deflated on the GPU, one member per 65280 bytes, and "
                           "only the members are copied to the host. Without it the output is plain text, whatever -o is called.")

@@ -494,6 +494,12 @@ struct kmm_index : IndexStreams, RxArrays {
     DevBuf bam_raw_mate, bam_raw_ctl, bam_raw_pos;
     DevBuf bam_mate_next, bam_raw_mate_next; // the spare carry buffers: a call fills them before it appends and swaps them in when it is done
     int64_t bam_raw_mate_len = 0;
+    // SAM lines kept as SAM lines: "record_sam" 1 / 2: a KMM_FORMAT_SAM call with "record_hits" and "record_keep" maps
+    // the selected records in the two-line FASTA form (the inner piece call under rk_raw_call: entries, no text) and appends the
+    // kept records' own lines to rkq[0]; 1: the header lines as well.  sam_raw: per piece, the tiles' {records, header lines} in
+    // front, the spans of the write walk, their kept lengths and prefixes, the blocks' sums and bases, the totals.
+    int record_sam = 0;
+    DevBuf sam_raw;
     BzScratch bz; // kmm_take_kept_bgzf
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
@@ -1127,6 +1133,26 @@ int refuse_record_keep(const kmm_index *ix, const char *who, bool sam_or_bam, bo
         return fail(KMM_ERR_INVALID_ARG, "%s: \"record_keep\" and \"record_pairs\" are 1: the unwrap of multi-line FASTA cuts at header "
                     "lines, not behind a mate 2; mates are kept together on FASTQ and two-line FASTA text only (nothing is mapped)", who);
     return KMM_OK;
+}
+
+// What a KMM_FORMAT_SAM call is refused for while "record_sam" is 1 or 2 (nothing is mapped, nothing appended).  A
+// call that passes is `named` to refuse_record_keep: what it appends is the records' own lines, QNAME and all.
+int refuse_record_sam(const kmm_index *ix, const char *who)
+{
+    if (!ix->record_hits || !ix->record_keep)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_sam\" is %d and \"%s\" is 0: the kept records' own lines are appended under the "
+                    "keep rule, which reads the entries of the record-hits mode; set \"record_hits\" to 1 or 2 and \"record_keep\" to 1, "
+                    "or \"record_sam\" to 0 (nothing is mapped)", who, ix->record_sam, ix->record_hits ? "record_keep" : "record_hits");
+    if (ix->record_pairs)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_sam\" is %d and \"record_pairs\" is 1: mates are not kept together in SAM output; "
+                    "set one of them to 0 (nothing is mapped)", who, ix->record_sam);
+    return KMM_OK;
+}
+
+// Does a KMM_FORMAT_SAM call append the kept records' own lines ("record_sam")?
+bool sam_raw_on(const kmm_index *ix)
+{
+    return ix->record_sam && ix->record_hits && ix->record_keep;
 }
 
 // Are the records of a FASTQ / two-line FASTA stream taken as interleaved mates?
@@ -2909,6 +2935,100 @@ static int selection_of(const kmm_index_t *ix, const char *who, bool by_name, in
     return KMM_OK;
 }
 
+// The raw form of one counted and checked SAM piece ("record_sam"), in place of map_sam_piece's plain write and map:
+// the write walk also leaves one span per selected record (and, with 1, per header line); the inner piece call appends the records'
+// entries and none of their FASTA text; the keep step then asks the rule of every span's entry and copies the kept lines behind
+// the queue's tail (both prefixes — the tiles' records and header lines, the spans' kept bytes — are two-level scans over blocks of
+// 1024).  No walk over the lines beyond the one write; no read-back: the queue holds room for the piece's consumed
+// bytes before anything is launched.  A piece of header lines alone is served too.  The caller's kmm_map_records puts both queues
+// back when anything here fails.
+static int sam_raw_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, int64_t n_bytes, uint64_t n_tiles, dim3 gw, const kmm_sam::Totals &h,
+                         bool selected, const kmm_sel::Sel &sel, int k, int max_freq, int also_revcomp, const uint8_t *lut,
+                         int64_t *n_records)
+{
+    using kmm_sam::RawSpan;
+    using kmm_sam::Tile;
+    static_assert(sizeof(RawSpan) == 16, "a span is one 16-byte store");
+    const bool headers = ix->record_sam == 1;
+    const uint64_t n_spans = h.recs + (headers ? h.headers : 0ull);
+    if (n_spans == 0)
+        return KMM_OK;
+    kmm_index::RkQueue &q = ix->rkq[0];
+    const uint64_t n_blocks = (n_spans + kmm_sam::RAW_BLOCK - 1) / kmm_sam::RAW_BLOCK;    // of spans (k_sam_raw_flags)
+    const uint64_t n_tblocks = (n_tiles + kmm_sam::RAW_BLOCK - 1) / kmm_sam::RAW_BLOCK;   // of tiles (k_sam_raw_tiles)
+    // spans | tile_pre (2 per tile) | kept, pre (1 per span) | per block of spans, then per block of tiles: sums (2), bases (2) | totals
+    const size_t off_tile = (size_t)n_spans * 16, off_kept = off_tile + (size_t)n_tiles * 8, off_blk = off_kept + (size_t)n_spans * 8,
+                 off_tblk = off_blk + (size_t)n_blocks * 16, off_tot = (off_tblk + (size_t)n_tblocks * 16 + 15) & ~(size_t)15;
+    KMMCHK(ensure(ix->sam_raw, off_tot + 64));
+    KMMCHK(rkq_reserve(ix, q, (int64_t)h.consumed));
+    uint8_t *w = (uint8_t *)ix->sam_raw.p;
+    RawSpan *spans = (RawSpan *)w;
+    uint32_t *tile_pre = (uint32_t *)(w + off_tile), *kept = (uint32_t *)(w + off_kept), *pre = kept + n_spans;
+    uint32_t *blk_bytes = (uint32_t *)(w + off_blk), *blk_recs = blk_bytes + n_blocks, *blk_pre = blk_recs + n_blocks;
+    uint32_t *tblk_recs = (uint32_t *)(w + off_tblk), *tblk_hdrs = tblk_recs + n_tblocks, *tblk_pre = tblk_hdrs + n_tblocks;
+    unsigned long long *tot = (unsigned long long *)(w + off_tot); // the kept bytes and the kept records of the piece
+    const Tile *tiles = (const Tile *)ix->sam_tiles.p;
+    const unsigned long long *base = (const unsigned long long *)ix->sam_base.p;
+    uint8_t *out = (uint8_t *)s.kmers.p;
+    hipStream_t cs = ix->stream;
+    const uint64_t nb = (uint64_t)n_bytes;
+    {
+        ScopedTimer tm;
+        KMMCHK(tm.begin(ix, KMM_KERNEL_SAM_RAW));
+        HIPCHK(hipMemsetAsync(spans, 0, (size_t)n_spans * 16, cs)); // (a slot no walk fills has length 0: it is never copied)
+        hipLaunchKernelGGL(kmm_sam::k_sam_raw_tiles, dim3((unsigned)n_tblocks), dim3(1024), 0, cs, tiles, n_tiles, tile_pre, tblk_recs, tblk_hdrs);
+        hipLaunchKernelGGL(kmm_sam::k_sam_raw_scan, dim3(1), dim3(1024), 0, cs, (const uint32_t *)tblk_recs, (const uint32_t *)tblk_hdrs,
+                           n_tblocks, tblk_pre, (unsigned long long *)nullptr);
+        KMMCHK(tm.end());
+    }
+    const uint32_t hd = headers ? 1u : 0u;
+    if (selected && ix->original_strand)
+        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_rev_sel, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, sel, tiles, base, out,
+                           ix->stats + KMM_STAT_REC_REVERSED, (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
+    else if (selected)
+        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_sel, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, sel, tiles, base, out,
+                           (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
+    else if (ix->original_strand)
+        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_rev, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, (uint32_t)ix->bam_excl, tiles, base, out,
+                           ix->stats + KMM_STAT_REC_REVERSED, (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
+    else
+        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, (uint32_t)ix->bam_excl, tiles, base, out,
+                           (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
+    HIPCHK(hipGetLastError());
+    if (h.recs > 0) {
+        // the records as two-line FASTA, as without the raw form; the inner call appends the entries and leaves the keep queue alone
+        int64_t used = 0;
+        ix->rk_raw_call = true;
+        const int rc = map_records_piece(ix, out, (int64_t)h.out_bytes, KMM_FORMAT_FASTA2, k, max_freq, also_revcomp, lut, &used, n_records);
+        ix->rk_raw_call = false;
+        KMMCHK(rc);
+        if (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs)
+            return fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %llu written bytes, %lld of %llu records mapped", (long long)used, h.out_bytes,
+                        (long long)*n_records, h.recs);
+    }
+    const int64_t first = ix->rhq_head + ix->rhq_pending - (int64_t)h.recs; // (the inner call's entries: the queue's last)
+    if (first < 0)
+        return fail(KMM_ERR_INTERNAL, "kmm_map_records: %llu selected SAM records and %lld entries pending", h.recs, (long long)ix->rhq_pending);
+    const uint32_t *hits = h.recs > 0 ? (const uint32_t *)ix->rhq_hits.p + first : nullptr;
+    const uint32_t *windows = h.recs > 0 && ix->record_hits == 2 ? (const uint32_t *)ix->rhq_win.p + first : nullptr;
+    const RkRule rule = {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert};
+    unsigned long long *tail = (unsigned long long *)q.ctl.p;
+    ScopedTimer tm;
+    KMMCHK(tm.begin(ix, KMM_KERNEL_SAM_RAW));
+    hipLaunchKernelGGL(kmm_sam::k_sam_raw_flags, dim3((unsigned)n_blocks), dim3(1024), 0, cs, (const RawSpan *)spans, n_spans, h.consumed, hits,
+                       windows, h.recs, rule, kept, pre, blk_bytes, blk_recs);
+    hipLaunchKernelGGL(kmm_sam::k_sam_raw_scan, dim3(1), dim3(1024), 0, cs, (const uint32_t *)blk_bytes, (const uint32_t *)blk_recs,
+                       n_blocks, blk_pre, tot);
+    hipLaunchKernelGGL(kmm_sam::k_sam_raw_copy, dim3((unsigned)grid_for(ix, (int64_t)((n_spans + 3) / 4), 16)), dim3(256), 0, cs, d_raw,
+                       (const RawSpan *)spans, n_spans, (const uint32_t *)kept, (const uint32_t *)pre, (const uint32_t *)blk_pre,
+                       (const unsigned long long *)tail, (uint8_t *)q.text.p);
+    hipLaunchKernelGGL(kmm_bam::k_bam_raw_advance, dim3(1), dim3(64), 0, cs, tail, (const unsigned long long *)tot);
+    KMMCHK(tm.end());
+    HIPCHK(hipGetLastError());
+    q.bound += (int64_t)h.consumed;
+    return KMM_OK;
+}
+
 // One piece of a SAM chunk (kmm_sam.hpp): its lines counted and checked on the device, the SEQ of every kept record written as
 // two-line FASTA into the stage's second buffer, which map_records_piece then maps.  Only complete lines are taken (*consumed:
 // the byte after the piece's last newline).  dry: the count and the checks only (a chunk of several pieces is checked whole
@@ -3007,6 +3127,8 @@ static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, i
             if (rc == KMM_OK && (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs))
                 rc = fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %llu written bytes, %lld of %llu records mapped", (long long)used,
                           h.out_bytes, (long long)*n_records, h.recs);
+        } else if (sam_raw_on(ix)) {
+            rc = sam_raw_piece(ix, s, d_raw, n_bytes, n_tiles, gw, h, selected, sel, k, max_freq, also_revcomp, lut, n_records);
         } else if (h.recs > 0) {
             uint8_t *out = (uint8_t *)s.kmers.p;
             if (selected && ix->original_strand)
@@ -3086,7 +3208,10 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     HIPCHK(hipSetDevice(ix->device));
     KMMCHK(check_k_lut(k, lut));
     KMMCHK(refuse_quality_in_record_hits(ix, "kmm_map_records"));
-    KMMCHK(refuse_record_keep(ix, "kmm_map_records", format == KMM_FORMAT_SAM, false, format == KMM_FORMAT_FASTA));
+    const bool sam_lines = format == KMM_FORMAT_SAM && ix->record_sam != 0; // ("record_sam", DESIGN 4.26: read by SAM calls alone)
+    if (sam_lines)
+        KMMCHK(refuse_record_sam(ix, "kmm_map_records"));
+    KMMCHK(refuse_record_keep(ix, "kmm_map_records", format == KMM_FORMAT_SAM, sam_lines, format == KMM_FORMAT_FASTA));
     KMMCHK(check_quality(ix, "kmm_map_records", k, format == KMM_FORMAT_SAM));
     // A quality floor on FASTQ: always compaction + the radix path, whatever the batch size and "path" say (as kmm_map_packed) —
     // the records front end of the direct path has no flat positions to put a quality mark on — and never the host packer,
@@ -3615,7 +3740,12 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
         return fail(KMM_ERR_INVALID_ARG, "%s: \"record_bam_mates\" is 1 and \"record_bam\" is 0: mates are kept together in the raw form "
                     "of the keep, set \"record_bam\" to 1 (with \"record_hits\" and \"record_keep\"), or \"record_bam_mates\" to 0; for "
                     "FASTQ output there is \"record_names_pairs\" (nothing is mapped)", c.who);
-    KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM, !text && (ix->record_names != 0 || ix->record_bam != 0)));
+    // ("record_sam", DESIGN 4.26: read by the SAM text routes alone)
+    const bool sam_lines = text && c.fmt == KMM_FORMAT_SAM && ix->record_sam != 0;
+    if (sam_lines)
+        KMMCHK(refuse_record_sam(ix, c.who));
+    KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM,
+                              sam_lines || (!text && (ix->record_names != 0 || ix->record_bam != 0))));
     KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
     if (n_comp < 0 || (n_comp > 0 && !comp))
         return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
@@ -5900,6 +6030,22 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if ((int)value != ix->record_bam) // (a waiting mate 1 holds FASTA text under the raw form, named FASTQ under DESIGN 4.23's)
             ix->bam_mate_len = ix->bam_raw_mate_len = 0;
         ix->record_bam = (int)value;
+    } else if (!strcmp(name, "record_sam")) {
+        // 1 / 2: a KMM_FORMAT_SAM call with "record_hits" and "record_keep" appends the kept records' own lines to the keep queue,
+        // 1 with the header lines, 2 without; raw lines and text never share a queue, as "record_bam"
+        if (value < 0 || value > 2)
+            return fail(KMM_ERR_INVALID_ARG, "record_sam takes 0, 1 (header lines kept) or 2 (header lines dropped)");
+        if ((int)value != ix->record_sam && ix->rkq[0].ctl.p) {
+            HIPCHK(hipSetDevice(ix->device));
+            KMMCHK(drain(ix));
+            unsigned long long tail[2];
+            KMMCHK(rkq_tail(ix->rkq[0], tail));
+            if (tail[0] > 0)
+                return fail(KMM_ERR_INVALID_ARG, "record_sam %lld with %llu kept bytes pending that were appended under record_sam %d: "
+                            "take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue (kmm_reset_counts) first",
+                            (long long)value, tail[0], ix->record_sam);
+        }
+        ix->record_sam = (int)value;
     } else if (!strcmp(name, "record_bam_mates")) {
         // 1: kmm_map_bam with "record_bam" takes the selected records of a stream as mates in file order — 2p and 2p + 1 — checks
         // that their read_name bytes agree and keeps or drops their own bytes together; even counts, as "record_pairs"
@@ -6011,6 +6157,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->record_names_mate_suffix;
     else if (!strcmp(name, "record_bam"))
         *value = ix->record_bam;
+    else if (!strcmp(name, "record_sam"))
+        *value = ix->record_sam;
     else if (!strcmp(name, "record_bam_mates"))
         *value = ix->record_bam_mates;
     else if (!strcmp(name, "record_keep"))

@@ -24,12 +24,17 @@
 // the records that pass the flag masks, MAPQ (with a floor) and RNAME, POS and CIGAR (with regions; RNAME looked up in the
 // handle's name table, POS and CIGAR read only of records on a listed reference).  A field that is read and malformed fails the
 // call (ERR_MAPQ, ERR_POS, ERR_CIGAR); a field no rule needs is not looked at.
+// The raw form ("record_sam"): the write pass also leaves one span per line it considers (walk_tile<.., H = true> with
+// a SpanSink: the k_sam_write_spans* kernels); behind the inner records call k_sam_raw_flags asks the keep rule of every span's
+// entry and k_sam_raw_copy moves the kept lines, untouched, behind the keep queue's tail.  No further walk over the lines.
 #pragma once
 
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
+#include "kmm_bam.hpp" // (the raw form: the keep rule rk_keep, and raw_copy_part, a lane's share of a copy into the keep queue)
 #include "kmm_select.hpp"
 
 #if defined(__HIPCC__)
@@ -468,7 +473,9 @@ KMM_SAM_HD uint64_t tile_end(uint64_t t, uint64_t n) { return (t + 1) * TILE < n
 // (sink(LineInfo, offset of its output inside the tile's)).  The tile's first line starts at its first byte when the byte
 // before is a newline (or the tile is the first), else behind the first newline inside the tile — looked for inside the tile
 // only, so that a long line costs its own tiles one window each.
-template <bool Q = false, bool S = false, class Scan, class Sink>
+// H (the raw form): the sink is also told of every header line and every kept record as a line,
+// sink.line(start, length with the newline, header?); without it the walk is what it was.
+template <bool Q = false, bool S = false, bool H = false, class Scan, class Sink>
 KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t excl, Scan &scan, Sink &sink, Tile &o, const Sel &sel = Sel())
 {
     o.recs = o.excluded = o.headers = o.bytes = 0;
@@ -496,18 +503,99 @@ KMM_SAM_HD void walk_tile(const uint8_t *d, uint64_t n, uint64_t t, uint32_t exc
             o.err = s << err_shift<S>() | li.err;
             return;
         }
-        if (li.kind == K_HEADER)
+        if (li.kind == K_HEADER) {
+            if constexpr (H)
+                sink.line(s, L.end + 1 - s, true);
             ++o.headers;
-        else if (li.kind == K_EXCLUDED)
+        } else if (li.kind == K_EXCLUDED)
             ++o.excluded;
         else {
             sink(li, o.bytes);
+            if constexpr (H)
+                sink.line(s, L.end + 1 - s, false);
             ++o.recs;
             o.bytes += out_len<Q>(li.seq_len);
         }
         o.last_end = L.end + 1;
         s = L.end + 1;
     }
+}
+
+// ---- the raw form ("record_sam"): the kept lines as they stand, behind the record-hits mode.
+// One span per line the keep step considers, left by the write walk in file order: the selected records, and with "record_sam" 1
+// the header lines between them.  entry: the record's ordinal among the piece's selected records (the inner call's entries, in
+// file order), RAW_HEADER for a header line, which no rule drops.
+struct RawSpan {
+    uint64_t start; // of the line in the piece
+    uint32_t len;   // with its newline (a line lies inside a piece: below 2^30)
+    uint32_t entry;
+};
+constexpr uint32_t RAW_HEADER = 0xFFFFFFFFu;
+constexpr uint32_t RAW_BLOCK = 1024; // spans per block of k_sam_raw_flags: the kept bytes are summed per block, then over the blocks
+
+// The sink of the write walk with spans: the records go to the inner sink as they did; every line the walk reports becomes span
+// n of the tile's share spans[0, cap) (cap: what the count pass found — the two passes ask one predicate, so the share is never
+// passed; bounds all the same).  entry0: the selected records of the tiles in front.  lead: the lane that stores (the walk is
+// wave-uniform).
+template <class Inner>
+struct SpanSink {
+    Inner in;
+    RawSpan *spans;
+    uint32_t cap, entry0;
+    bool headers, lead;
+    uint32_t n = 0, recs = 0;
+    template <class Info>
+    KMM_SAM_HD void operator()(const Info &li, uint32_t at) { in(li, at); }
+    KMM_SAM_HD void line(uint64_t start, uint64_t len, bool header)
+    {
+        if (header && !headers)
+            return;
+        if (n < cap && lead) {
+            RawSpan sp;
+            sp.start = start;
+            sp.len = (uint32_t)len;
+            sp.entry = header ? RAW_HEADER : entry0 + recs;
+            spans[n] = sp;
+        }
+        ++n;
+        recs += header ? 0u : 1u;
+    }
+};
+
+// A tile's share of the spans, from the two-level scan of Tile::recs and Tile::headers: {records, header lines} of the tiles in
+// front = those of the blocks of RAW_BLOCK tiles in front (block) + those of the block's tiles in front (in_block).
+KMM_SAM_HD uint32_t raw_tile_spans(const Tile &c, bool headers) { return c.recs + (headers ? c.headers : 0u); }
+KMM_SAM_HD void raw_tile_pre(const uint32_t *in_block, const uint32_t *block, uint32_t (&pre)[2])
+{
+    pre[0] = in_block[0] + block[0];
+    pre[1] = in_block[1] + block[1];
+}
+KMM_SAM_HD uint64_t raw_tile_first(const uint32_t (&pre)[2], bool headers) { return (uint64_t)pre[0] + (headers ? pre[1] : 0u); }
+
+// The bytes a span adds to the queue: its line when it is a header line or its entry passes the rule, else 0.  A span that does
+// not lie inside the piece's consumed bytes, or whose entry the piece does not have, adds nothing (a slot the walk did not fill
+// reads as length 0).  hits / windows: the piece's n_entries entries (windows null: mode 1).
+KMM_SAM_HD uint32_t raw_kept_len(const RawSpan &sp, uint64_t consumed, const uint32_t *hits, const uint32_t *windows, uint64_t n_entries,
+                                 const RkRule &rule)
+{
+    if (sp.len == 0 || sp.start >= consumed || (uint64_t)sp.len > consumed - sp.start)
+        return 0u;
+    if (sp.entry == RAW_HEADER)
+        return sp.len;
+    if ((uint64_t)sp.entry >= n_entries)
+        return 0u;
+    return rk_keep(hits[sp.entry], windows ? windows[sp.entry] : 0u, rule) ? sp.len : 0u;
+}
+
+// Where a kept span goes: the queue's tail, the kept bytes of the blocks in front, those of the block's spans in front
+KMM_SAM_HD uint64_t raw_span_dest(uint64_t tail, uint32_t block_pre, uint32_t pre) { return tail + block_pre + pre; }
+
+// The share of lane `lane` of `lanes` in moving kept span sp to the queue (kmm_bam::raw_copy_part: rk_span's split — the
+// destination's aligned middle as 16-byte stores from 16-byte loads at the source's alignment, head and tail byte by byte; no
+// byte of the queue is read, none outside [dst, dst + len) written, none outside the span read).
+KMM_SAM_HD void raw_copy_span(const uint8_t *d, const RawSpan &sp, uint8_t *queue, uint64_t dst, uint32_t lane, uint32_t lanes)
+{
+    kmm_bam::raw_copy_part(d + sp.start, queue, dst, sp.len, lane, lanes);
 }
 
 // ---- the CPU form (the tests): the same walk, the lanes one after the other ----
@@ -603,6 +691,96 @@ inline void cpu_chunk(const uint8_t *d, uint64_t n, uint32_t excl, uint8_t *out,
         if (reversed)
             *reversed += write.reversed;
     }
+}
+
+// The raw form of one chunk on the CPU, as the library runs it: the count pass, the scan of the tiles, the write walk with spans
+// (text: the two-line FASTA it writes as before, at least tot.out_bytes), then — the caller maps the text and hands the entries
+// over — cpu_raw_keep.  mode: "record_sam" 1 or 2.
+struct CpuRaw {
+    Totals tot;
+    std::vector<RawSpan> spans;
+    uint64_t reversed = 0;
+};
+inline void cpu_raw_spans(const uint8_t *d, uint64_t n, uint32_t excl, int mode, uint8_t *text, CpuRaw &r, bool orig = false,
+                          uint32_t lanes = 1, const Sel *sel = nullptr)
+{
+    cpu_chunk<false>(d, n, excl, nullptr, r.tot, nullptr, orig, nullptr, lanes, sel);
+    r.spans.clear();
+    if (r.tot.err != NONE)
+        return;
+    const bool headers = mode == 1, selected = sel && !sel->flags_only();
+    Sel eff = selected ? *sel : Sel();
+    eff.excl = excl;
+    const uint64_t n_tiles = (n + TILE - 1) / TILE;
+    std::vector<Tile> tiles(n_tiles);
+    std::vector<uint64_t> base(n_tiles);
+    std::vector<uint32_t> in_block(2 * n_tiles), block(2 * ((n_tiles + RAW_BLOCK - 1) / RAW_BLOCK) + 2, 0u);
+    CpuScan sc{d, n};
+    sc.lanes = lanes;
+    CpuSink count{d, nullptr};
+    uint64_t bytes = 0;
+    uint32_t recs = 0, hdrs = 0;
+    for (uint64_t t = 0; t < n_tiles; ++t) {
+        if (selected)
+            walk_tile<false, true>(d, n, t, excl, sc, count, tiles[t], eff);
+        else
+            walk_tile<false>(d, n, t, excl, sc, count, tiles[t]);
+        base[t] = bytes;
+        if (t % RAW_BLOCK == 0) { // (the blocks' scan, then the scan inside the block: as k_sam_raw_scan and k_sam_raw_tiles)
+            block[2 * (t / RAW_BLOCK)] = recs;
+            block[2 * (t / RAW_BLOCK) + 1] = hdrs;
+        }
+        in_block[2 * t] = recs - block[2 * (t / RAW_BLOCK)];
+        in_block[2 * t + 1] = hdrs - block[2 * (t / RAW_BLOCK) + 1];
+        bytes += tiles[t].bytes;
+        recs += tiles[t].recs;
+        hdrs += tiles[t].headers;
+    }
+    r.spans.assign((size_t)recs + (headers ? hdrs : 0u), RawSpan{0, 0, 0});
+    for (uint64_t t = 0; t < n_tiles; ++t) {
+        const uint32_t cap = raw_tile_spans(tiles[t], headers);
+        if (cap == 0)
+            continue;
+        CpuSink write{d, text + base[t]};
+        write.orig = orig;
+        write.lanes = lanes;
+        uint32_t pre[2];
+        raw_tile_pre(&in_block[2 * t], &block[2 * (t / RAW_BLOCK)], pre);
+        SpanSink<CpuSink> sink{write, r.spans.data() + raw_tile_first(pre, headers), cap, pre[0], headers, true};
+        Tile o;
+        if (selected)
+            walk_tile<false, true, true>(d, n, t, excl, sc, sink, o, eff);
+        else
+            walk_tile<false, false, true>(d, n, t, excl, sc, sink, o);
+        r.reversed += sink.in.reversed;
+    }
+}
+
+// The keep step on the CPU: the flags, the two-level prefix (inside blocks of RAW_BLOCK spans, then over the blocks), the copy
+// with `lanes` lanes one after the other.  queue: 16-byte aligned, room behind tail for the kept bytes; returns them, *kept_recs
+// the kept records (header lines are not counted).
+inline uint64_t cpu_raw_keep(const uint8_t *d, const CpuRaw &r, const uint32_t *hits, const uint32_t *windows, uint64_t n_entries,
+                             const RkRule &rule, uint8_t *queue, uint64_t tail, uint32_t lanes, uint64_t *kept_recs)
+{
+    const size_t m = r.spans.size(), n_blocks = (m + RAW_BLOCK - 1) / RAW_BLOCK;
+    std::vector<uint32_t> kept(m), pre(m), block_pre(n_blocks + 1, 0u);
+    uint64_t recs = 0;
+    for (size_t b = 0; b < n_blocks; ++b) {
+        uint32_t sum = 0;
+        for (size_t i = b * RAW_BLOCK; i < m && i < (b + 1) * RAW_BLOCK; ++i) {
+            kept[i] = raw_kept_len(r.spans[i], r.tot.consumed, hits, windows, n_entries, rule);
+            pre[i] = sum;
+            sum += kept[i];
+            recs += kept[i] && r.spans[i].entry != RAW_HEADER ? 1u : 0u;
+        }
+        block_pre[b + 1] = block_pre[b] + sum;
+    }
+    for (size_t i = 0; i < m; ++i)
+        if (kept[i])
+            for (uint32_t lane = 0; lane < lanes; ++lane)
+                raw_copy_span(d, r.spans[i], queue, raw_span_dest(tail, block_pre[i / RAW_BLOCK], pre[i]), lane, lanes);
+    *kept_recs = recs;
+    return block_pre[n_blocks];
 }
 
 #if defined(__HIPCC__)
@@ -1003,6 +1181,219 @@ __global__ void __launch_bounds__(256) k_sam_write_q_rev_sel(const uint8_t *__re
             atomicAdd(no_qual, (unsigned long long)sink.no_qual);
         if ((threadIdx.x & 63u) == 0 && sink.reversed)
             atomicAdd(reversed, (unsigned long long)sink.reversed);
+    }
+}
+
+// ---- the raw form ("record_sam") ----
+// scan: the second level of both prefixes, over the sums of blocks of RAW_BLOCK items — the blocks of k_sam_raw_tiles (records and
+// header lines: the entry base and the span base of every tile) and the blocks of k_sam_raw_flags (kept bytes and kept records: the
+// destinations and the queue's advance).  One workgroup of 1024 threads, each over a run of consecutive blocks (the shape of
+// kmm_bam.hpp k_bam_raw_scan), two columns at once: pre[2 i] and pre[2 i + 1] = the sums of a[u] and b[u] over u < i (32-bit: both
+// columns count lines or bytes of one piece, below 2^31); total, where given, gets the two sums over all blocks.  (A piece of
+// 2^30 bytes has 1024 blocks of tiles: one per thread.  The first level is not this kernel's: over a million tiles, a thousand one
+// after the other per thread, it took 3.6 ms: profiles/sam_out/README.md.)
+__global__ void __launch_bounds__(1024) k_sam_raw_scan(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint64_t n_items,
+                                                       uint32_t *__restrict__ pre, unsigned long long *__restrict__ total)
+{
+    __shared__ unsigned long long s[1024];
+    const uint32_t i = threadIdx.x;
+    const uint64_t per = (n_items + 1023) / 1024, t0 = (uint64_t)i * per < n_items ? (uint64_t)i * per : n_items,
+                   t1 = t0 + per < n_items ? t0 + per : n_items;
+    unsigned long long sum = 0; // (the two columns side by side: neither reaches 2^32, no carry crosses)
+    for (uint64_t t = t0; t < t1; ++t)
+        sum += (unsigned long long)a[t] | (unsigned long long)b[t] << 32;
+    s[i] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024; off <<= 1) { // inclusive scan (Hillis-Steele)
+        const unsigned long long x = i >= off ? s[i - off] : 0ull;
+        __syncthreads();
+        s[i] += x;
+        __syncthreads();
+    }
+    unsigned long long run = s[i] - sum;
+    for (uint64_t t = t0; t < t1; ++t) {
+        pre[2 * t] = (uint32_t)run;
+        pre[2 * t + 1] = (uint32_t)(run >> 32);
+        run += (unsigned long long)a[t] | (unsigned long long)b[t] << 32;
+    }
+    if (total && i == 1023) {
+        total[0] = s[1023] & 0xFFFFFFFFull;
+        total[1] = s[1023] >> 32;
+    }
+}
+
+// The scan inside a workgroup of RAW_BLOCK threads over two columns side by side in 64 bits (neither reaches 2^32): returns the
+// thread's inclusive prefix, all = the workgroup's sum.  s: 16 words of LDS.
+__device__ __forceinline__ unsigned long long raw_block_scan(unsigned long long v, unsigned long long *s, unsigned long long &all)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)incl, o), hi = (uint32_t)__shfl_up((int)(uint32_t)(incl >> 32), o);
+        if ((int)lane >= o)
+            incl += (unsigned long long)hi << 32 | lo;
+    }
+    if (lane == 63)
+        s[wave] = incl;
+    __syncthreads();
+    unsigned long long before = 0;
+    all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 16; ++w) {
+        before += w < wave ? s[w] : 0ull;
+        all += s[w];
+    }
+    return before + incl;
+}
+
+// tiles: one thread per tile, RAW_BLOCK tiles per workgroup: pre[2 t] and pre[2 t + 1] = the selected records and the header lines
+// of the block's tiles in front of tile t, block_recs / block_headers the block's sums (k_sam_raw_scan over them gives the blocks'
+// bases: raw_tile_pre adds the two levels).
+__global__ void __launch_bounds__(1024) k_sam_raw_tiles(const Tile *__restrict__ tiles, uint64_t n_tiles, uint32_t *__restrict__ pre,
+                                                        uint32_t *__restrict__ block_recs, uint32_t *__restrict__ block_headers)
+{
+    static_assert(RAW_BLOCK == 1024, "one tile per thread of a 1024-thread workgroup");
+    __shared__ unsigned long long s[16];
+    const uint64_t t = (uint64_t)blockIdx.x * RAW_BLOCK + threadIdx.x;
+    unsigned long long v = 0, all;
+    if (t < n_tiles)
+        v = (unsigned long long)tiles[t].recs | (unsigned long long)tiles[t].headers << 32;
+    const unsigned long long excl = raw_block_scan(v, s, all) - v;
+    if (t < n_tiles) {
+        pre[2 * t] = (uint32_t)excl;
+        pre[2 * t + 1] = (uint32_t)(excl >> 32);
+    }
+    if (threadIdx.x == 0) {
+        block_recs[blockIdx.x] = (uint32_t)all;
+        block_headers[blockIdx.x] = (uint32_t)(all >> 32);
+    }
+}
+
+// write with spans: the write walk of k_sam_write / _sel / _rev / _rev_sel, its sink wrapped in a SpanSink — the FASTA text as
+// before, and span first + i for line i of the tile's share (tile_pre, block_pre: k_sam_raw_tiles and k_sam_raw_scan over its
+// blocks; headers: "record_sam" 1).
+// A tile that holds header lines alone is walked too.  Kernels of their own: the four above are what runs while "record_sam" is 0.
+template <bool S, bool REV>
+__device__ __forceinline__ void sam_write_spans_tiles(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, const Sel &sel,
+                                                      const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                      uint8_t *__restrict__ out, unsigned long long *__restrict__ reversed,
+                                                      const uint32_t *__restrict__ tile_pre, const uint32_t *__restrict__ block_pre,
+                                                      bool headers, RawSpan *__restrict__ spans, uint64_t n_spans)
+{
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    const bool lead = (threadIdx.x & 63u) == 0;
+    WaveScan sc{d, n};
+    for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; t < n_tiles; t += waves) {
+        const Tile c = tiles[t];
+        const uint32_t cap = raw_tile_spans(c, headers);
+        uint32_t pre[2];
+        raw_tile_pre(tile_pre + 2 * t, block_pre + 2 * (t / RAW_BLOCK), pre);
+        const uint64_t first = raw_tile_first(pre, headers);
+        if (cap == 0 || first + cap > n_spans)
+            continue;
+        typename std::conditional<REV, WaveSinkRev, WaveSink>::type inner{d, out + base[t]};
+        Tile o;
+        uint32_t flips = 0;
+        if constexpr (S) {
+            SpanSink<BoundedSink<decltype(inner)>> sink{{inner, c.bytes}, spans + first, cap, pre[0], headers, lead};
+            walk_tile<false, true, true>(d, n, t, sel.excl, sc, sink, o, sel);
+            if constexpr (REV)
+                flips = sink.in.in.reversed;
+        } else {
+            SpanSink<decltype(inner)> sink{inner, spans + first, cap, pre[0], headers, lead};
+            walk_tile<false, false, true>(d, n, t, sel.excl, sc, sink, o);
+            if constexpr (REV)
+                flips = sink.in.reversed;
+        }
+        if (REV && lead && flips)
+            atomicAdd(reversed, (unsigned long long)flips);
+    }
+}
+__global__ void __launch_bounds__(256) k_sam_write_spans(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint32_t excl,
+                                                         const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                         uint8_t *__restrict__ out, const uint32_t *__restrict__ tile_pre,
+                                                         const uint32_t *__restrict__ block_pre, uint32_t headers,
+                                                         RawSpan *__restrict__ spans, uint64_t n_spans)
+{
+    Sel sel;
+    sel.excl = excl;
+    sam_write_spans_tiles<false, false>(d, n, n_tiles, sel, tiles, base, out, nullptr, tile_pre, block_pre, headers != 0u, spans, n_spans);
+}
+__global__ void __launch_bounds__(256) k_sam_write_spans_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, Sel sel,
+                                                             const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                             uint8_t *__restrict__ out, const uint32_t *__restrict__ tile_pre,
+                                                             const uint32_t *__restrict__ block_pre, uint32_t headers,
+                                                             RawSpan *__restrict__ spans, uint64_t n_spans)
+{
+    sam_write_spans_tiles<true, false>(d, n, n_tiles, sel, tiles, base, out, nullptr, tile_pre, block_pre, headers != 0u, spans, n_spans);
+}
+__global__ void __launch_bounds__(256) k_sam_write_spans_rev(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, uint32_t excl,
+                                                             const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                             uint8_t *__restrict__ out, unsigned long long *__restrict__ reversed,
+                                                             const uint32_t *__restrict__ tile_pre, const uint32_t *__restrict__ block_pre,
+                                                             uint32_t headers, RawSpan *__restrict__ spans, uint64_t n_spans)
+{
+    Sel sel;
+    sel.excl = excl;
+    sam_write_spans_tiles<false, true>(d, n, n_tiles, sel, tiles, base, out, reversed, tile_pre, block_pre, headers != 0u, spans, n_spans);
+}
+__global__ void __launch_bounds__(256) k_sam_write_spans_rev_sel(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, Sel sel,
+                                                                 const Tile *__restrict__ tiles, const unsigned long long *__restrict__ base,
+                                                                 uint8_t *__restrict__ out, unsigned long long *__restrict__ reversed,
+                                                                 const uint32_t *__restrict__ tile_pre, const uint32_t *__restrict__ block_pre,
+                                                                 uint32_t headers, RawSpan *__restrict__ spans, uint64_t n_spans)
+{
+    sam_write_spans_tiles<true, true>(d, n, n_tiles, sel, tiles, base, out, reversed, tile_pre, block_pre, headers != 0u, spans, n_spans);
+}
+
+// flags: one thread per span, RAW_BLOCK spans per workgroup: kept[i] = the span's kept length or 0 (raw_kept_len), pre[i] = the kept
+// bytes of the block's spans in front, block_bytes / block_recs = the block's kept bytes and kept records (header lines are not
+// records).  hits / windows: the inner call's n_entries entries, complete behind its k_read_hits.
+__global__ void __launch_bounds__(1024) k_sam_raw_flags(const RawSpan *__restrict__ spans, uint64_t n_spans, uint64_t consumed,
+                                                        const uint32_t *__restrict__ hits, const uint32_t *__restrict__ windows,
+                                                        uint64_t n_entries, RkRule rule, uint32_t *__restrict__ kept,
+                                                        uint32_t *__restrict__ pre, uint32_t *__restrict__ block_bytes,
+                                                        uint32_t *__restrict__ block_recs)
+{
+    static_assert(RAW_BLOCK == 1024, "one span per thread of a 1024-thread workgroup");
+    __shared__ unsigned long long s[16];
+    const uint64_t i = (uint64_t)blockIdx.x * RAW_BLOCK + threadIdx.x;
+    uint32_t len = 0, rec = 0;
+    if (i < n_spans) {
+        const RawSpan sp = spans[i];
+        len = raw_kept_len(sp, consumed, hits, windows, n_entries, rule);
+        rec = len && sp.entry != RAW_HEADER ? 1u : 0u;
+    }
+    // (bytes and records side by side: a block's kept bytes lie below 2^31)
+    unsigned long long all;
+    const unsigned long long incl = raw_block_scan((unsigned long long)len | (unsigned long long)rec << 32, s, all);
+    if (i < n_spans) {
+        kept[i] = len;
+        pre[i] = (uint32_t)incl - len;
+    }
+    if (threadIdx.x == 0) {
+        block_bytes[blockIdx.x] = (uint32_t)all;
+        block_recs[blockIdx.x] = (uint32_t)(all >> 32);
+    }
+}
+
+// copy: one wavefront per kept span (grid-stride), its 64 lanes over the line's bytes (raw_copy_span), written behind the queue's
+// tail (read from the device: {bytes, records}, as k_rk_scatter reads it) at the block's base (block_pre[2 b]: k_sam_raw_scan over
+// the blocks) plus the span's prefix.  kept[i] is the span's own length or 0: the span was checked against `consumed` by flags.
+__global__ void __launch_bounds__(256) k_sam_raw_copy(const uint8_t *__restrict__ d, const RawSpan *__restrict__ spans, uint64_t n_spans,
+                                                      const uint32_t *__restrict__ kept, const uint32_t *__restrict__ pre,
+                                                      const uint32_t *__restrict__ block_pre, const unsigned long long *__restrict__ tail,
+                                                      uint8_t *__restrict__ queue)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    const uint64_t tail0 = tail[0];
+    for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; i < n_spans; i += waves) {
+        if (kept[i] == 0)
+            continue;
+        const RawSpan sp = spans[i];
+        raw_copy_span(d, sp, queue, raw_span_dest(tail0, block_pre[2 * (i / RAW_BLOCK)], pre[i]), lane, 64u);
     }
 }
 #endif

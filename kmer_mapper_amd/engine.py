@@ -454,6 +454,14 @@ class DeviceIndex:
         if on and mates:
             self.set_param("record_bam_mates", 1)
 
+    def record_sam(self, on=True, header=True):
+        """SAM lines kept as SAM lines (include/kmm.h), on top of record_hits() and record_keep(): a SAM call
+        (map_records, map_bgzf, map_gzip with FORMAT_SAM) maps the selected records as without the switch and appends every kept
+        record's WHOLE LINE, untouched, to the queue of take_kept_records() / take_kept_bgzf(); header=True: every header line
+        too, at its place in the stream; False: none (shares that are concatenated).  The other formats never read it.  Refused
+        while kept bytes are pending."""
+        self.set_param("record_sam", (1 if header else 2) if on else 0)
+
     def take_kept_records(self, out=None):
         """kmm_take_kept_records: ALL pending bytes — the kept records, whole, in stream order — as (np.uint8 array, n_records);
         they leave the queue.  out: a uint8 array or torch tensor (host or device) to write into instead, at least as long as

@@ -146,7 +146,7 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
 
 def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
                    min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False, compress=False, pairs=False,
-                   pair_rule="any", output="fastq", keep_mates=False):
+                   pair_rule="any", output="fastq", keep_mates=False, header=True):
     """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
     text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
     (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
@@ -167,12 +167,25 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     to the hits alone; mate_suffix, pairs and compress do not go with it.
     keep_mates (output "bam"): the file is name-collated and mates are kept or dropped together under pair_rule, as
     with `pairs`, but as BAM records: both records of every kept pair, untouched, mate 1 directly in front of mate 2.  The mate
-    check compares the read_name bytes as they stand; strangers or an unpaired last record raise ValueError with the hint."""
+    check compares the read_name bytes as they stand; strangers or an unpaired last record raise ValueError with the hint.
+    output "sam" (fmt "sam"): `raw` is SAM text and the text returned is SAM text — every kept record's whole line,
+    untouched, in file order, behind (header=True) every header line at its place; header=False drops the header lines.
+    Records whose FLAG has any of exclude_flags are not written; original_strand applies to the hits alone; compress: a complete
+    BGZF file (htslib reads it as .sam.gz).  The bytes behind the last newline are not looked at (len(text) tells with
+    min_hits=0).  mate_suffix, pairs and keep_mates do not go with it."""
     from . import _lib
+    if output == "sam":
+        if fmt != "sam":
+            raise ValueError("output=\"sam\" goes with fmt=\"sam\": SAM lines are written from SAM lines")
+        if mate_suffix or pairs or keep_mates:
+            raise ValueError("output=\"sam\" does not go with mate_suffix, pairs or keep_mates: the lines are written as they stand, in "
+                             "file order")
+        return _select_sam_lines(index, raw, k, max_index_lookup_frequency, also_revcomp, lut, min_hits, min_permille, invert, device,
+                                 exclude_flags, original_strand, compress, header)
     if keep_mates and output != "bam":
         raise ValueError("keep_mates goes with output=\"bam\": mates kept together as BAM records (FASTQ out: pairs=True)")
     if output not in ("fastq", "bam"):
-        raise ValueError("output must be 'fastq' or 'bam', not %r" % (output,))
+        raise ValueError("output must be 'fastq', 'bam' or 'sam', not %r" % (output,))
     if output == "bam" and fmt != "bam":
         raise ValueError("output=\"bam\" goes with fmt=\"bam\": BAM records are written from BAM records")
     if output == "bam" and (mate_suffix or pairs or compress):
@@ -234,6 +247,43 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
             dev.set_param("bam_exclude_flags", before[0])
             dev.set_param("original_strand", before[1])
             dev.set_param("record_pairs_rule", before[2])
+        dev.record_keep(False)
+        dev.record_hits(False)
+    return text, hits, windows
+
+
+def _select_sam_lines(index, raw, k, max_index_lookup_frequency, also_revcomp, lut, min_hits, min_permille, invert, device, exclude_flags,
+                      original_strand, compress, header):
+    """select_records(fmt="sam", output="sam"): DeviceIndex.record_sam around one map_records call; the cached handle is left as it
+    was found."""
+    from . import _lib
+    if isinstance(raw, (bytes, bytearray, memoryview)):
+        raw = np.frombuffer(bytes(raw), dtype=np.uint8)
+    max_node_id = int(np.max(index._nodes)) if len(index._nodes) else 0
+    dev = _device_index(index, max_node_id, device)
+    if dev.get_param("record_hits_pending") or dev.get_param("record_keep_pending_bytes"):
+        raise ValueError("the cached handle has record hits or kept records pending: take them first")
+    before = (dev.get_param("bam_exclude_flags"), dev.get_param("original_strand"))
+    dev.record_hits(True, windows=True)
+    dev.record_keep(True, min_hits=min_hits, min_permille=min_permille, invert=invert)
+    dev.record_sam(True, header=header)
+    try:
+        dev.set_param("bam_exclude_flags", int(exclude_flags))
+        dev.set_param("original_strand", int(bool(original_strand)))
+        dev.map_records(raw, fmt=_lib.FORMAT_SAM, k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp,
+                        lut=lut)
+        hits, windows = dev.take_record_hits()
+        if compress:
+            from .gz_io import BGZF_EOF
+            text = dev.take_kept_bgzf()[0].tobytes() + BGZF_EOF
+        else:
+            text = dev.take_kept_records()[0].tobytes()
+    finally:
+        if dev.get_param("record_keep_pending_bytes"):                              # (a take that failed: raw lines never meet text)
+            dev.take_kept_records()
+        dev.record_sam(False)
+        dev.set_param("bam_exclude_flags", before[0])
+        dev.set_param("original_strand", before[1])
         dev.record_keep(False)
         dev.record_hits(False)
     return text, hits, windows
