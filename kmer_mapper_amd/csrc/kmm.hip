@@ -9,6 +9,10 @@
 // memory-level parallelism (U independent bucket gathers in flight per lane, then U independent
 // first-entry gathers) at high occupancy; reads are staged through LDS as packed 2-bit codes so
 // each byte is fetched from HBM exactly once with 16-byte coalesced loads.
+//
+// File map.  Here: the handle, its helpers, the C entry points, StreamCall and the drivers of the compressed streams.  Kernels:
+// kmm_*.hpp.  Host code included further down, inside an anonymous namespace, behind the helpers it uses: kmm_radix_host.hpp (the
+// radix path), kmm_sam_host.hpp (the SAM pieces of kmm_map_records), kmm_bam_host.hpp (kmm_map_bam behind the inflater; rs_*).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -673,6 +677,16 @@ void with_probe_flavour(const IndexView &iv, F &&f)
         f(std::integral_constant<int, PROBE_NARROW>{});
 }
 
+// Whether a selection beyond the exclude mask is set, as a compile-time constant for the k_bam_raw_*<SELECTED> kernels: f(S).
+template <typename F>
+void with_selected(bool selected, F &&f)
+{
+    if (selected)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
 // Stage a host array into the given device buffer on the copy stream; device arrays pass through.
 template <typename TT>
 int stage_in(kmm_index *ix, DevBuf &buf, const TT *src, size_t count, const TT **dev, bool *staged)
@@ -1229,6 +1243,42 @@ void rkq_rollback(kmm_index *ix, kmm_index::RkQueue &q, int64_t bound0)
     g_err = msg;
 }
 
+// Both queues back to what the last kmm_map_records found (rk_snap), once: for an outer call that fails behind a good inner one.
+void rk_snap_restore(kmm_index *ix)
+{
+    if (ix->rk_snap.valid) {
+        ix->rhq_pending = ix->rk_snap.pending;
+        rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
+    }
+    ix->rk_snap.valid = false;
+}
+
+// rk_mates_call / rk_raw_call around one inner records call of kmm_map_bam or of a SAM piece: cleared on every way out.
+struct RkCallMode {
+    kmm_index *ix;
+    RkCallMode(kmm_index *ix_, bool mates, bool raw) : ix(ix_) { ix->rk_mates_call = mates, ix->rk_raw_call = raw; }
+    ~RkCallMode() { ix->rk_mates_call = ix->rk_raw_call = false; }
+};
+
+// The keep rule of the handle, for single records and for pairs.
+RkRule rk_rule(const kmm_index *ix) { return {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert}; }
+RkPairRule rk_pair_rule(const kmm_index *ix) { return {rk_rule(ix), (uint32_t)ix->rk_pair_rule}; }
+
+// The entries an inner records call has just appended: the last n of the entry queue.  Null pointers when n is 0 (the kernels
+// then read none), a null `windows` in mode 1.  false: fewer than n entries are pending (the caller's internal error).
+struct KeepEntries { const uint32_t *hits = nullptr, *windows = nullptr; uint64_t n = 0; };
+
+bool keep_entries_last(const kmm_index *ix, uint64_t n, KeepEntries &e)
+{
+    const int64_t first = ix->rhq_head + ix->rhq_pending - (int64_t)n;
+    if (first < 0)
+        return false;
+    e.n = n;
+    e.hits = n ? (const uint32_t *)ix->rhq_hits.p + first : nullptr;
+    e.windows = n && ix->record_hits == 2 ? (const uint32_t *)ix->rhq_win.p + first : nullptr;
+    return true;
+}
+
 // The kept records of one piece, behind its k_read_hits (the entries are sums of atomics over that whole grid: complete only
 // when it has ended).  hits / windows: the piece's n_records entries (windows null in mode 1); consumed: where its last whole
 // record ends.
@@ -1249,12 +1299,11 @@ int record_keep_piece(kmm_index *ix, kmm_index::RkQueue &q, const ReadsView &rv,
     uint32_t *tile_rec = tile_cnt + (size_t)n_super * 1024, *super_rec = super_tot + n_super;
     unsigned long long *tail = (unsigned long long *)q.ctl.p;
     uint32_t *d_total = (uint32_t *)((uint8_t *)q.ctl.p + 32);
-    const RkRule one = {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert};
     typename RkRuleOf<PAIR>::type rule;
     if constexpr (PAIR == 0)
-        rule = one;
+        rule = rk_rule(ix);
     else
-        rule = RkPairRule{one, (uint32_t)ix->rk_pair_rule};
+        rule = rk_pair_rule(ix);
     const dim3 g4((unsigned)((n_tiles + 3) / 4));
     HIPCHK(hipMemsetAsync(tile_cnt, 0, (size_t)n_super * 1024 * 8, ix->stream));
     hipLaunchKernelGGL(k_rk_flags<PAIR>, g4, dim3(256), 0, ix->stream, rv.bases, n_bytes, consumed, n_tiles, rv.tile_nl, rv.super_nl,
@@ -2935,226 +2984,9 @@ static int selection_of(const kmm_index_t *ix, const char *who, bool by_name, in
     return KMM_OK;
 }
 
-// The raw form of one counted and checked SAM piece ("record_sam"), in place of map_sam_piece's plain write and map:
-// the write walk also leaves one span per selected record (and, with 1, per header line); the inner piece call appends the records'
-// entries and none of their FASTA text; the keep step then asks the rule of every span's entry and copies the kept lines behind
-// the queue's tail (both prefixes — the tiles' records and header lines, the spans' kept bytes — are two-level scans over blocks of
-// 1024).  No walk over the lines beyond the one write; no read-back: the queue holds room for the piece's consumed
-// bytes before anything is launched.  A piece of header lines alone is served too.  The caller's kmm_map_records puts both queues
-// back when anything here fails.
-static int sam_raw_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, int64_t n_bytes, uint64_t n_tiles, dim3 gw, const kmm_sam::Totals &h,
-                         bool selected, const kmm_sel::Sel &sel, int k, int max_freq, int also_revcomp, const uint8_t *lut,
-                         int64_t *n_records)
-{
-    using kmm_sam::RawSpan;
-    using kmm_sam::Tile;
-    static_assert(sizeof(RawSpan) == 16, "a span is one 16-byte store");
-    const bool headers = ix->record_sam == 1;
-    const uint64_t n_spans = h.recs + (headers ? h.headers : 0ull);
-    if (n_spans == 0)
-        return KMM_OK;
-    kmm_index::RkQueue &q = ix->rkq[0];
-    const uint64_t n_blocks = (n_spans + kmm_sam::RAW_BLOCK - 1) / kmm_sam::RAW_BLOCK;    // of spans (k_sam_raw_flags)
-    const uint64_t n_tblocks = (n_tiles + kmm_sam::RAW_BLOCK - 1) / kmm_sam::RAW_BLOCK;   // of tiles (k_sam_raw_tiles)
-    // spans | tile_pre (2 per tile) | kept, pre (1 per span) | per block of spans, then per block of tiles: sums (2), bases (2) | totals
-    const size_t off_tile = (size_t)n_spans * 16, off_kept = off_tile + (size_t)n_tiles * 8, off_blk = off_kept + (size_t)n_spans * 8,
-                 off_tblk = off_blk + (size_t)n_blocks * 16, off_tot = (off_tblk + (size_t)n_tblocks * 16 + 15) & ~(size_t)15;
-    KMMCHK(ensure(ix->sam_raw, off_tot + 64));
-    KMMCHK(rkq_reserve(ix, q, (int64_t)h.consumed));
-    uint8_t *w = (uint8_t *)ix->sam_raw.p;
-    RawSpan *spans = (RawSpan *)w;
-    uint32_t *tile_pre = (uint32_t *)(w + off_tile), *kept = (uint32_t *)(w + off_kept), *pre = kept + n_spans;
-    uint32_t *blk_bytes = (uint32_t *)(w + off_blk), *blk_recs = blk_bytes + n_blocks, *blk_pre = blk_recs + n_blocks;
-    uint32_t *tblk_recs = (uint32_t *)(w + off_tblk), *tblk_hdrs = tblk_recs + n_tblocks, *tblk_pre = tblk_hdrs + n_tblocks;
-    unsigned long long *tot = (unsigned long long *)(w + off_tot); // the kept bytes and the kept records of the piece
-    const Tile *tiles = (const Tile *)ix->sam_tiles.p;
-    const unsigned long long *base = (const unsigned long long *)ix->sam_base.p;
-    uint8_t *out = (uint8_t *)s.kmers.p;
-    hipStream_t cs = ix->stream;
-    const uint64_t nb = (uint64_t)n_bytes;
-    {
-        ScopedTimer tm;
-        KMMCHK(tm.begin(ix, KMM_KERNEL_SAM_RAW));
-        HIPCHK(hipMemsetAsync(spans, 0, (size_t)n_spans * 16, cs)); // (a slot no walk fills has length 0: it is never copied)
-        hipLaunchKernelGGL(kmm_sam::k_sam_raw_tiles, dim3((unsigned)n_tblocks), dim3(1024), 0, cs, tiles, n_tiles, tile_pre, tblk_recs, tblk_hdrs);
-        hipLaunchKernelGGL(kmm_sam::k_sam_raw_scan, dim3(1), dim3(1024), 0, cs, (const uint32_t *)tblk_recs, (const uint32_t *)tblk_hdrs,
-                           n_tblocks, tblk_pre, (unsigned long long *)nullptr);
-        KMMCHK(tm.end());
-    }
-    const uint32_t hd = headers ? 1u : 0u;
-    if (selected && ix->original_strand)
-        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_rev_sel, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, sel, tiles, base, out,
-                           ix->stats + KMM_STAT_REC_REVERSED, (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
-    else if (selected)
-        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_sel, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, sel, tiles, base, out,
-                           (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
-    else if (ix->original_strand)
-        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_rev, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, (uint32_t)ix->bam_excl, tiles, base, out,
-                           ix->stats + KMM_STAT_REC_REVERSED, (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
-    else
-        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, (uint32_t)ix->bam_excl, tiles, base, out,
-                           (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
-    HIPCHK(hipGetLastError());
-    if (h.recs > 0) {
-        // the records as two-line FASTA, as without the raw form; the inner call appends the entries and leaves the keep queue alone
-        int64_t used = 0;
-        ix->rk_raw_call = true;
-        const int rc = map_records_piece(ix, out, (int64_t)h.out_bytes, KMM_FORMAT_FASTA2, k, max_freq, also_revcomp, lut, &used, n_records);
-        ix->rk_raw_call = false;
-        KMMCHK(rc);
-        if (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs)
-            return fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %llu written bytes, %lld of %llu records mapped", (long long)used, h.out_bytes,
-                        (long long)*n_records, h.recs);
-    }
-    const int64_t first = ix->rhq_head + ix->rhq_pending - (int64_t)h.recs; // (the inner call's entries: the queue's last)
-    if (first < 0)
-        return fail(KMM_ERR_INTERNAL, "kmm_map_records: %llu selected SAM records and %lld entries pending", h.recs, (long long)ix->rhq_pending);
-    const uint32_t *hits = h.recs > 0 ? (const uint32_t *)ix->rhq_hits.p + first : nullptr;
-    const uint32_t *windows = h.recs > 0 && ix->record_hits == 2 ? (const uint32_t *)ix->rhq_win.p + first : nullptr;
-    const RkRule rule = {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert};
-    unsigned long long *tail = (unsigned long long *)q.ctl.p;
-    ScopedTimer tm;
-    KMMCHK(tm.begin(ix, KMM_KERNEL_SAM_RAW));
-    hipLaunchKernelGGL(kmm_sam::k_sam_raw_flags, dim3((unsigned)n_blocks), dim3(1024), 0, cs, (const RawSpan *)spans, n_spans, h.consumed, hits,
-                       windows, h.recs, rule, kept, pre, blk_bytes, blk_recs);
-    hipLaunchKernelGGL(kmm_sam::k_sam_raw_scan, dim3(1), dim3(1024), 0, cs, (const uint32_t *)blk_bytes, (const uint32_t *)blk_recs,
-                       n_blocks, blk_pre, tot);
-    hipLaunchKernelGGL(kmm_sam::k_sam_raw_copy, dim3((unsigned)grid_for(ix, (int64_t)((n_spans + 3) / 4), 16)), dim3(256), 0, cs, d_raw,
-                       (const RawSpan *)spans, n_spans, (const uint32_t *)kept, (const uint32_t *)pre, (const uint32_t *)blk_pre,
-                       (const unsigned long long *)tail, (uint8_t *)q.text.p);
-    hipLaunchKernelGGL(kmm_bam::k_bam_raw_advance, dim3(1), dim3(64), 0, cs, tail, (const unsigned long long *)tot);
-    KMMCHK(tm.end());
-    HIPCHK(hipGetLastError());
-    q.bound += (int64_t)h.consumed;
-    return KMM_OK;
-}
-
-// One piece of a SAM chunk (kmm_sam.hpp): its lines counted and checked on the device, the SEQ of every kept record written as
-// two-line FASTA into the stage's second buffer, which map_records_piece then maps.  Only complete lines are taken (*consumed:
-// the byte after the piece's last newline).  dry: the count and the checks only (a chunk of several pieces is checked whole
-// before any of it is mapped).  at: the piece's offset in the caller's chunk (for the error message).
-static int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int64_t at, bool dry, int k, int max_freq,
-                         int also_revcomp, const uint8_t *lut, int64_t *consumed, int64_t *n_records)
-{
-    *consumed = 0;
-    *n_records = 0;
-    Stage &s = next_stage(ix);
-    KMMCHK(stage_acquire(ix, s));
-    bool staged = false;
-    const uint8_t *d_raw = nullptr;
-    KMMCHK(stage_in<uint8_t>(ix, s.bases, raw, (size_t)n_bytes, &d_raw, &staged));
-    const uint64_t n_tiles = ((uint64_t)n_bytes + kmm_sam::TILE - 1) / kmm_sam::TILE;
-    KMMCHK(ensure(ix->sam_tiles, (size_t)n_tiles * sizeof(kmm_sam::Tile) + 64));
-    KMMCHK(ensure(ix->sam_base, (size_t)n_tiles * 8 + 64));
-    KMMCHK(ensure(ix->sam_ctl, 256));
-    const bool qual = record_quality(ix) > 0; // the quality variant: four-line FASTQ, mapped with the floor
-    if (!dry && !qual)
-        KMMCHK(ensure(s.kmers, (size_t)n_bytes + 16)); // (a record's output is never longer than its line)
-    kmm_sam::Tile *tiles = (kmm_sam::Tile *)ix->sam_tiles.p;
-    unsigned long long *base = (unsigned long long *)ix->sam_base.p;
-    kmm_sam::Totals *d_tot = (kmm_sam::Totals *)ix->sam_ctl.p;
-    const uint32_t excl = ix->bam_excl;
-    kmm_sel::Sel sel; // a selection beyond excl: the k_sam_*_sel kernels run
-    const int src = selection_of(ix, "kmm_map_records (KMM_FORMAT_SAM)", true, 0, sel);
-    if (src != KMM_OK) {
-        (void)stage_release(ix, s, false);
-        return src;
-    }
-    const bool selected = !sel.flags_only();
-    KMMCHK(stage_copies_done(ix));
-    hipStream_t cs = ix->stream; // (kernels run on the handle's stream only: see rec_compact_piece)
-    const dim3 gw((unsigned)grid_for(ix, (int64_t)((n_tiles + 3) / 4), 16)); // one wavefront per tile, 4 per block, grid-stride
-    if (selected && qual)
-        hipLaunchKernelGGL(kmm_sam::k_sam_count_q_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel, tiles);
-    else if (selected)
-        hipLaunchKernelGGL(kmm_sam::k_sam_count_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel, tiles);
-    else if (qual)
-        hipLaunchKernelGGL(kmm_sam::k_sam_count_q, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl, tiles);
-    else
-        hipLaunchKernelGGL(kmm_sam::k_sam_count, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl, tiles);
-    hipLaunchKernelGGL(kmm_sam::k_sam_totals, dim3(1), dim3(1024), 0, cs, (const kmm_sam::Tile *)tiles, n_tiles, base, d_tot);
-    HIPCHK(hipGetLastError());
-    kmm_sam::Totals h;
-    HIPCHK(hipMemcpyAsync(&h, d_tot, sizeof h, hipMemcpyDeviceToHost, cs));
-    HIPCHK(hipStreamSynchronize(cs)); // (the borrowed host buffer is free from here on)
-    if (h.err != kmm_sam::NONE) {
-        static const char *why[8] = {"QUAL is not \"*\" and not as long as SEQ", "fewer than 11 TAB-separated fields",
-                                     "FLAG is not a decimal integer in [0, 65535]", "an empty line",
-                                     "MAPQ is not a decimal integer in [0, 255] (\"bam_min_mapq\" reads it)",
-                                     "POS is not a decimal integer in [0, 2^31 - 1] (the region list reads it)",
-                                     "CIGAR is neither \"*\" nor ([0-9]+[MIDNSHP=X])+ with lengths up to 2^28 - 1 (the region list reads it)",
-                                     "?"};
-        const unsigned shift = selected ? 3u : 2u; // (kmm_sam::err_shift)
-        (void)stage_release(ix, s, false);
-        return fail(KMM_ERR_MALFORMED, "kmm_map_records: SAM line at byte %llu of the chunk: %s (nothing of the call is mapped)",
-                    (unsigned long long)at + (h.err >> shift), why[h.err & ((1u << shift) - 1u)]);
-    }
-    *consumed = (int64_t)h.consumed;
-    int rc = KMM_OK;
-    if (!dry) {
-        ix->sam_records += (int64_t)h.recs;
-        ix->sam_excluded += (int64_t)h.excluded;
-        ix->sam_header_lines += (int64_t)h.headers;
-        if (h.recs > 0 && qual) {
-            // (with QUAL "*" a record's four-line FASTQ is longer than its line: the buffer is sized from the totals)
-            rc = ensure(s.kmers, (size_t)h.out_bytes + 16);
-            if (rc == KMM_OK) {
-                if (selected && ix->original_strand)
-                    hipLaunchKernelGGL(kmm_sam::k_sam_write_q_rev_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel,
-                                       (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
-                                       ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
-                else if (selected)
-                    hipLaunchKernelGGL(kmm_sam::k_sam_write_q_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel,
-                                       (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
-                                       ix->stats + KMM_STAT_REC_NO_QUAL);
-                else if (ix->original_strand)
-                    hipLaunchKernelGGL(kmm_sam::k_sam_write_q_rev, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
-                                       (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
-                                       ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
-                else
-                    hipLaunchKernelGGL(kmm_sam::k_sam_write_q, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
-                                       (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, (uint8_t *)s.kmers.p,
-                                       ix->stats + KMM_STAT_REC_NO_QUAL);
-                const hipError_t e = hipGetLastError();
-                if (e != hipSuccess)
-                    rc = fail(KMM_ERR_HIP, "kmm_map_records: k_sam_write_q: %s", hipGetErrorString(e));
-            }
-            // the records as FASTQ, from HBM, through compaction and the radix path, where the floor is applied
-            int64_t used = 0;
-            if (rc == KMM_OK)
-                rc = map_records_radix_call(ix, (const uint8_t *)s.kmers.p, (int64_t)h.out_bytes, KMM_FORMAT_FASTQ, k, max_freq,
-                                            also_revcomp, lut, &used, n_records);
-            if (rc == KMM_OK && (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs))
-                rc = fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %llu written bytes, %lld of %llu records mapped", (long long)used,
-                          h.out_bytes, (long long)*n_records, h.recs);
-        } else if (sam_raw_on(ix)) {
-            rc = sam_raw_piece(ix, s, d_raw, n_bytes, n_tiles, gw, h, selected, sel, k, max_freq, also_revcomp, lut, n_records);
-        } else if (h.recs > 0) {
-            uint8_t *out = (uint8_t *)s.kmers.p;
-            if (selected && ix->original_strand)
-                hipLaunchKernelGGL(kmm_sam::k_sam_write_rev_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel,
-                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out, ix->stats + KMM_STAT_REC_REVERSED);
-            else if (selected)
-                hipLaunchKernelGGL(kmm_sam::k_sam_write_sel, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, sel,
-                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out);
-            else if (ix->original_strand)
-                hipLaunchKernelGGL(kmm_sam::k_sam_write_rev, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
-                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out, ix->stats + KMM_STAT_REC_REVERSED);
-            else
-                hipLaunchKernelGGL(kmm_sam::k_sam_write, gw, dim3(256), 0, cs, d_raw, (uint64_t)n_bytes, n_tiles, excl,
-                                   (const kmm_sam::Tile *)tiles, (const unsigned long long *)base, out);
-            HIPCHK(hipGetLastError());
-            // the records as two-line FASTA, from HBM, through the two-line parser (its kernels wait for the copy stream)
-            int64_t used = 0;
-            rc = map_records_piece(ix, out, (int64_t)h.out_bytes, KMM_FORMAT_FASTA2, k, max_freq, also_revcomp, lut, &used, n_records);
-            if (rc == KMM_OK && (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs))
-                rc = fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %llu written bytes, %lld of %llu records mapped", (long long)used,
-                          h.out_bytes, (long long)*n_records, h.recs);
-        }
-    }
-    const int rel = stage_release(ix, s, false); // (after the inner call's kernels: they read this stage's buffer)
-    return rc != KMM_OK ? rc : rel;
-}
+namespace {
+#include "kmm_sam_host.hpp" // map_sam_piece, sam_raw_piece: behind the stages and map_records_piece, in front of kmm_map_records
+} // namespace
 
 static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int format, int k, int max_freq, int also_revcomp,
                              const uint8_t *lut, int64_t *consumed, int64_t *n_records);
@@ -3784,11 +3616,7 @@ static int keep_carry(kmm_index_t *ix, const StreamCall &c, const uint8_t *d_raw
         // ("record_pairs": a complete record behind the last whole pair stays unconsumed like an incomplete one; nothing of the
         // call stays in the queues — the pairs in front of it were appended by the call's kmm_map_records, which succeeded)
         carry_len = 0;
-        if (ix->rk_snap.valid) {
-            ix->rhq_pending = ix->rk_snap.pending;
-            rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
-            ix->rk_snap.valid = false;
-        }
+        rk_snap_restore(ix);
         return fail(KMM_ERR_MALFORMED, "%s: \"record_pairs\" is 1 and the stream ends with an unpaired record: the last %lld bytes "
                     "form no complete pair of records (nothing of the call is appended)", c.who, (long long)tail);
     }
@@ -4055,568 +3883,9 @@ int kmm_map_bgzf(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int forma
     });
 }
 
-// ---- kmm_map_bam: BAM records found and decoded on the GPU (kmm_bam.hpp; the orchestration there, run_call, is shared with the
-// CPU tests).  The backend: the handle's bam_* buffers, kernels on its stream.
-struct BamGpuBackend {
-    kmm_index_t *ix;
-    const uint8_t *d;
-    uint64_t n;
-    int32_t n_ref;
-    uint32_t excl;
-    bool qual = false; // the quality variant: four-line FASTQ, 2 l_seq + 6 bytes per kept record
-    bool orig = false; // "original_strand": decode writes the kept records with FLAG 0x10 in read orientation
-    bool selected = false; // a selection beyond excl is set (sel): the k_bam_*_sel kernels run
-    kmm_bam::Sel sel;
-    int cur = 0;
-    bool named = false; // the named form ("record_names"): the k_bam_*_named kernels run, whatever the selection
-    bool sfx = false;   // ... with "/1" / "/2" behind the name
-
-    kmm_bam::Tile *tiles(int i) { return (kmm_bam::Tile *)ix->bam_tiles[i].p; }
-    kmm_bam::Ctl *ctl() { return (kmm_bam::Ctl *)ix->bam_ctl.p; }
-    dim3 wave_grid(uint64_t n_tiles) { return dim3((unsigned)grid_for(ix, (int64_t)((n_tiles + 3) / 4), 16)); } // 4 waves per block
-    dim3 lane_grid(uint64_t n_tiles) { return dim3((unsigned)grid_for(ix, (int64_t)((n_tiles + 255) / 256), 16)); }
-
-    int spec(uint64_t n_tiles, uint64_t start0)
-    {
-        for (DevBuf &b : ix->bam_tiles)
-            KMMCHK(ensure(b, (size_t)n_tiles * sizeof(kmm_bam::Tile) + 64));
-        KMMCHK(ensure(ix->bam_bad, (size_t)n_tiles + 64));
-        KMMCHK(ensure(ix->bam_base, (size_t)n_tiles * 8 + 64));
-        KMMCHK(ensure(ix->bam_ctl, 256));
-        cur = 0;
-        HIPCHK(hipMemsetAsync(ctl(), 0, sizeof(kmm_bam::Ctl), ix->stream));
-        HIPCHK(hipMemsetAsync(&ctl()->err_pos, 0xFF, 8, ix->stream)); // (no error)
-        if (named)
-            hipLaunchKernelGGL(kmm_bam::k_bam_spec_named, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
-                               sfx ? 1u : 0u, tiles(0));
-        else if (selected && qual)
-            hipLaunchKernelGGL(kmm_bam::k_bam_spec_q_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel, tiles(0));
-        else if (selected)
-            hipLaunchKernelGGL(kmm_bam::k_bam_spec_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel, tiles(0));
-        else if (qual)
-            hipLaunchKernelGGL(kmm_bam::k_bam_spec_q, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl, tiles(0));
-        else
-            hipLaunchKernelGGL(kmm_bam::k_bam_spec, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl, tiles(0));
-        HIPCHK(hipGetLastError());
-        return KMM_OK;
-    }
-    int check(uint64_t n_tiles, uint64_t start0, kmm_bam::Ctl &h)
-    {
-        HIPCHK(hipMemsetAsync(&ctl()->n_bad, 0, 8, ix->stream));
-        HIPCHK(hipMemsetAsync(&ctl()->first_bad, 0xFF, 8, ix->stream));
-        hipLaunchKernelGGL(kmm_bam::k_bam_check, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref,
-                           (const kmm_bam::Tile *)tiles(cur), (uint8_t *)ix->bam_bad.p, ctl());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&h, ctl(), sizeof h, hipMemcpyDeviceToHost, ix->stream));
-        HIPCHK(hipStreamSynchronize(ix->stream));
-        return KMM_OK;
-    }
-    int fix(uint64_t n_tiles, uint64_t start0)
-    {
-        if (named)
-            hipLaunchKernelGGL(kmm_bam::k_bam_fix_named, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
-                               sfx ? 1u : 0u, (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
-        else if (selected && qual)
-            hipLaunchKernelGGL(kmm_bam::k_bam_fix_q_sel, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
-                               (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
-        else if (selected)
-            hipLaunchKernelGGL(kmm_bam::k_bam_fix_sel, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, sel,
-                               (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
-        else if (qual)
-            hipLaunchKernelGGL(kmm_bam::k_bam_fix_q, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl,
-                               (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
-        else
-            hipLaunchKernelGGL(kmm_bam::k_bam_fix, lane_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, start0, n_ref, excl,
-                               (const kmm_bam::Tile *)tiles(cur), (const uint8_t *)ix->bam_bad.p, tiles(cur ^ 1), ctl());
-        HIPCHK(hipGetLastError());
-        cur ^= 1;
-        return KMM_OK;
-    }
-    int totals(uint64_t n_tiles, uint64_t start0, kmm_bam::Totals &h)
-    {
-        kmm_bam::Totals *d_tot = (kmm_bam::Totals *)((uint8_t *)ix->bam_ctl.p + 128);
-        hipLaunchKernelGGL(kmm_bam::k_bam_totals, dim3(1), dim3(1024), 0, ix->stream, (const kmm_bam::Tile *)tiles(cur), n_tiles, start0,
-                           (unsigned long long *)ix->bam_base.p, d_tot);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&h, d_tot, sizeof h, hipMemcpyDeviceToHost, ix->stream));
-        HIPCHK(hipStreamSynchronize(ix->stream));
-        return KMM_OK;
-    }
-    int decode(uint64_t n_tiles, uint8_t *out)
-    {
-        const kmm_bam::Tile *tl = (const kmm_bam::Tile *)tiles(cur);
-        const unsigned long long *bs = (const unsigned long long *)ix->bam_base.p;
-        if (named)
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode_named, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel,
-                               orig ? 1u : 0u, sfx ? 1u : 0u, tl, bs, out, ix->stats + KMM_STAT_REC_NO_QUAL,
-                               ix->stats + KMM_STAT_REC_REVERSED, ix->stats + KMM_STAT_REC_NAME_REPLACED);
-        else if (selected && qual && orig)
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_rev_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs,
-                               out, ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
-        else if (selected && qual)
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs,
-                               out, ix->stats + KMM_STAT_REC_NO_QUAL);
-        else if (selected && orig)
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode_rev_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs,
-                               out, ix->stats + KMM_STAT_REC_REVERSED);
-        else if (selected)
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs, out);
-        else if (qual && orig)
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_rev, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
-                               (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out,
-                               ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
-        else if (qual)
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode_q, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
-                               (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out,
-                               ix->stats + KMM_STAT_REC_NO_QUAL);
-        else if (orig)
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode_rev, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
-                               (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out,
-                               ix->stats + KMM_STAT_REC_REVERSED);
-        else
-            hipLaunchKernelGGL(kmm_bam::k_bam_decode, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, excl,
-                               (const kmm_bam::Tile *)tiles(cur), (const unsigned long long *)ix->bam_base.p, out);
-        HIPCHK(hipGetLastError());
-        return KMM_OK;
-    }
-};
-
-// "The stream ends with an unpaired record" (DESIGN 4.23): a mate 1 is left when the stream's last call has nothing more for it.
-static int bam_mates_unpaired(long long n_selected)
-{
-    return fail(KMM_ERR_MALFORMED, "kmm_map_bam: \"record_names_pairs\" is 1 and the stream ends with an unpaired record: it holds %lld "
-                "selected records, the last one has no mate (a selection that removes one mate of a pair is an error here; nothing of "
-                "the call is appended)", n_selected);
-}
-
-// The selected records of a kmm_map_bam window as mates ("record_names_pairs"), behind run_call: the window's
-// records are decoded BEHIND the text of the mate 1 that the window before left over, and the inner records call takes
-// carry + decoded text in the interleaved pair form (rk_mates_call: whole pairs only, the names of every pair compared).  An odd
-// last record's text stays unconsumed and becomes the next carry.  A call that fails leaves the carry, the ordinals, the queues
-// and the counters as it found them.
-static int bam_map_mates(kmm_index_t *ix, const StreamCall &c, BamGpuBackend &be, const kmm_bam::CallOut &co, int64_t n_raw)
-{
-    const int64_t carry = ix->bam_mate_len, pairs0 = ix->bam_pairs_done;
-    const int64_t n_rec = (int64_t)co.recs + (carry > 0 ? 1 : 0), n_text = carry + (int64_t)co.out_bytes;
-    const bool decoded = co.recs > 0;
-    unsigned long long *d_counters = nullptr; // (no-qual, reversed, replaced: neighbours in the first shard of the statistics)
-    static_assert(KMM_STAT_REC_REVERSED == KMM_STAT_REC_NO_QUAL + 1 && KMM_STAT_REC_NAME_REPLACED == KMM_STAT_REC_NO_QUAL + 2, "one copy");
-    auto put_back = [&](bool queues) {
-        const std::string msg = g_err;
-        ix->bam_pairs_done = pairs0;
-        ix->bam_calls--;
-        ix->bam_records -= (int64_t)co.recs;
-        ix->bam_excluded -= (int64_t)co.excluded;
-        ix->bam_false_starts -= (int64_t)co.false_starts;
-        ix->bam_continuations -= (int64_t)co.continuations;
-        if (d_counters && hipMemcpyAsync(ix->stats + KMM_STAT_REC_NO_QUAL, d_counters, 24, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess)
-            (void)hipGetLastError();
-        if (queues && ix->rk_snap.valid) { // (what the inner call appended: as keep_carry puts back an unpaired end of a text stream)
-            ix->rhq_pending = ix->rk_snap.pending;
-            rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
-        }
-        ix->rk_snap.valid = false;
-        g_err = msg;
-    };
-    ix->rk_snap.valid = false;
-    int64_t taken = 0, recs = 0;
-    if (decoded) {
-        KMMCHK(ensure(ix->rk_names_ctl, 64));
-        KMMCHK(ensure(ix->bam_out, (size_t)n_text + 64));
-        d_counters = (unsigned long long *)((uint8_t *)ix->rk_names_ctl.p + 16);
-        HIPCHK(hipMemcpyAsync(d_counters, ix->stats + KMM_STAT_REC_NO_QUAL, 24, hipMemcpyDeviceToDevice, ix->stream));
-        if (carry > 0)
-            HIPCHK(hipMemcpyAsync(ix->bam_out.p, ix->bam_mate.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream));
-        KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p + carry));
-        if (n_rec >= 2) {
-            ix->rk_mates_call = true;
-            const int rc = kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, n_text, KMM_FORMAT_FASTQ, c.k, c.max_freq, c.also_revcomp, c.lut,
-                                           &taken, &recs);
-            ix->rk_mates_call = false;
-            if (rc != KMM_OK) { // (the inner call has put its own entries and text back)
-                put_back(false);
-                return rc;
-            }
-            if (recs != (n_rec & ~(int64_t)1) || ((n_rec & 1) == 0 && taken != n_text) || taken > n_text) {
-                put_back(true);
-                return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %lld decoded bytes, %lld of %lld records mapped as pairs", (long long)taken,
-                            (long long)n_text, (long long)recs, (long long)n_rec);
-            }
-        }
-    }
-    const int64_t left = decoded ? n_text - taken : carry; // the text of a mate 1 whose mate has not come
-    if (c.last_chunk && left > 0) {
-        const long long n_selected = (long long)(2 * ix->bam_pairs_done + 1);
-        put_back(true);
-        return bam_mates_unpaired(n_selected);
-    }
-    if (decoded && left > 0) {
-        KMMCHK(ensure(ix->bam_mate, (size_t)left + 64)); // (may free and reallocate: a device-wide sync, rare)
-        HIPCHK(hipMemcpyAsync(ix->bam_mate.p, (const uint8_t *)ix->bam_out.p + taken, (size_t)left, hipMemcpyDeviceToDevice, ix->stream));
-    }
-    if (decoded)
-        ix->bam_mate_len = left;
-    if (c.n_records)
-        *c.n_records = recs;
-    return KMM_OK;
-}
-
-// The kept records of a kmm_map_bam window as they stand in the file ("record_bam"), behind the inner records call:
-// its co.recs entries are the last ones of the entry queue, one per selected record in file order.  Five steps on the handle's
-// stream, no read-back: the record base of every tile (a scan of Tile::recs), the kept raw bytes and records per tile, their
-// scans, the copy behind the queue's tail, the tail's advance.  The queue holds room for the window's consumed bytes first.
-static int bam_raw_keep(kmm_index_t *ix, BamGpuBackend &be, const kmm_bam::CallOut &co, int64_t n_raw)
-{
-    using kmm_bam::Tile;
-    static_assert(sizeof(Tile) == 32 && offsetof(Tile, recs) == 16, "k_bam_raw_scan reads Tile::recs as word 4 of 8");
-    const uint64_t n_tiles = ((uint64_t)n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE;
-    kmm_index::RkQueue &q = ix->rkq[0];
-    const size_t off_kept = 2 * (size_t)n_tiles * 8, off_tot = (off_kept + 2 * (size_t)n_tiles * 4 + 15) & ~(size_t)15;
-    KMMCHK(ensure(ix->bam_raw, off_tot + 64));
-    KMMCHK(rkq_reserve(ix, q, (int64_t)co.consumed));
-    uint8_t *w = (uint8_t *)ix->bam_raw.p;
-    unsigned long long *rec_base = (unsigned long long *)w, *byte_base = rec_base + n_tiles, *tot = (unsigned long long *)(w + off_tot);
-    uint32_t *kept_bytes = (uint32_t *)(w + off_kept), *kept_recs = kept_bytes + n_tiles;
-    const int64_t first = ix->rhq_head + ix->rhq_pending - (int64_t)co.recs; // (the inner call's entries: the queue's last)
-    if (first < 0)
-        return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %llu selected records and %lld entries pending", co.recs, (long long)ix->rhq_pending);
-    const uint32_t *hits = (const uint32_t *)ix->rhq_hits.p + first;
-    const uint32_t *windows = ix->record_hits == 2 ? (const uint32_t *)ix->rhq_win.p + first : nullptr;
-    const RkRule rule = {(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert};
-    const Tile *tl = (const Tile *)be.tiles(be.cur);
-    unsigned long long *tail = (unsigned long long *)q.ctl.p;
-    const kmm_bam::Sel sel = be.sel; // (its excl is the exclude mask, which the form without a selection reads from here)
-    ScopedTimer tm;
-    KMMCHK(tm.begin(ix, KMM_KERNEL_BAM_RAW));
-    hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)tl + 4, 8u, n_tiles, rec_base, tot + 2);
-    if (be.selected)
-        hipLaunchKernelGGL(kmm_bam::k_bam_raw_count<true>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref, sel, tl,
-                           (const unsigned long long *)rec_base, hits, windows, co.recs, rule, kept_bytes, kept_recs);
-    else
-        hipLaunchKernelGGL(kmm_bam::k_bam_raw_count<false>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref, sel, tl,
-                           (const unsigned long long *)rec_base, hits, windows, co.recs, rule, kept_bytes, kept_recs);
-    hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)kept_bytes, 1u, n_tiles, byte_base, tot);
-    hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)kept_recs, 1u, n_tiles,
-                       (unsigned long long *)nullptr, tot + 1);
-    if (be.selected)
-        hipLaunchKernelGGL(kmm_bam::k_bam_raw_copy<true>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref, sel, tl,
-                           (const unsigned long long *)rec_base, hits, windows, co.recs, rule, (const uint32_t *)kept_bytes,
-                           (const unsigned long long *)byte_base, (const unsigned long long *)tail, (uint8_t *)q.text.p);
-    else
-        hipLaunchKernelGGL(kmm_bam::k_bam_raw_copy<false>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref, sel, tl,
-                           (const unsigned long long *)rec_base, hits, windows, co.recs, rule, (const uint32_t *)kept_bytes,
-                           (const unsigned long long *)byte_base, (const unsigned long long *)tail, (uint8_t *)q.text.p);
-    hipLaunchKernelGGL(kmm_bam::k_bam_raw_advance, dim3(1), dim3(64), 0, ix->stream, tail, (const unsigned long long *)tot);
-    KMMCHK(tm.end());
-    HIPCHK(hipGetLastError());
-    q.bound += (int64_t)co.consumed;
-    return KMM_OK;
-}
-
-static int bam_raw_mates_unpaired(long long n_selected)
-{
-    return fail(KMM_ERR_MALFORMED, "kmm_map_bam: \"record_bam_mates\" is 1 and the stream ends with an unpaired record: it holds %lld "
-                "selected records, the last one has no mate (a selection that removes one mate of a pair is an error here; nothing of "
-                "the call is appended)", n_selected);
-}
-
-// The selected records of a kmm_map_bam window as mates whose own bytes are kept ("record_bam_mates"), behind run_call.
-// As bam_map_mates: the window's records are decoded behind the FASTA text of the mate 1 that the window before left over, and the
-// inner records call takes carry + decoded text in the pair form — whole pairs of entries, no text appended, no name lines
-// compared.  Then the raw walk in its pair form: record base, count (which reports the odd last record), the mate check over the
-// records' own read_name bytes, ONE read-back (strangers, the odd record), scans, the carried mate 1 to the queue's tail, the
-// tiles' records behind it, the tail's advance.  The odd last record's text and raw bytes become the next carry.  A call that fails
-// leaves the carries, the ordinal, the queues and the counters as it found them.
-static int bam_map_raw_mates(kmm_index_t *ix, const StreamCall &c, BamGpuBackend &be, const kmm_bam::CallOut &co, int64_t n_raw, bool qual)
-{
-    using kmm_bam::Tile;
-    const int64_t carry = ix->bam_mate_len, pairs0 = ix->bam_pairs_done, raw_carry = ix->bam_raw_mate_len;
-    const uint32_t carried = carry > 0 ? 1u : 0u;
-    const int64_t n_rec = (int64_t)co.recs + carried, n_text = carry + (int64_t)co.out_bytes;
-    unsigned long long *d_counters = nullptr;
-    auto put_back = [&](bool queues) {
-        const std::string msg = g_err;
-        ix->bam_pairs_done = pairs0;
-        ix->bam_calls--;
-        ix->bam_records -= (int64_t)co.recs;
-        ix->bam_excluded -= (int64_t)co.excluded;
-        ix->bam_false_starts -= (int64_t)co.false_starts;
-        ix->bam_continuations -= (int64_t)co.continuations;
-        if (d_counters && hipMemcpyAsync(ix->stats + KMM_STAT_REC_NO_QUAL, d_counters, 24, hipMemcpyDeviceToDevice, ix->stream) != hipSuccess)
-            (void)hipGetLastError();
-        if (queues && ix->rk_snap.valid) {
-            ix->rhq_pending = ix->rk_snap.pending;
-            rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
-        }
-        ix->rk_snap.valid = false;
-        g_err = msg;
-    };
-    ix->rk_snap.valid = false;
-    if (carried && (raw_carry < 37 || raw_carry > 0x7FFFFFFFll + 4)) {
-        put_back(false);
-        return fail(KMM_ERR_INTERNAL, "kmm_map_bam: a mate 1 waits with %lld bytes of text and %lld raw bytes", (long long)carry, (long long)raw_carry);
-    }
-    if (co.recs == 0) { // (nothing selected: a mate 1 goes on waiting, unless the stream ends here)
-        if (c.last_chunk && carried) {
-            put_back(false);
-            return bam_raw_mates_unpaired((long long)(2 * pairs0 + 1));
-        }
-        return KMM_OK;
-    }
-    int64_t taken = 0, recs = 0;
-    unsigned long long h_ctl[3] = {kmm_bam::NONE, kmm_bam::NONE, kmm_bam::NONE};
-    const auto body = [&]() -> int {
-        KMMCHK(ensure(ix->rk_names_ctl, 64));
-        KMMCHK(ensure(ix->bam_raw_ctl, 64));
-        KMMCHK(ensure(ix->bam_out, (size_t)n_text + 64));
-        d_counters = (unsigned long long *)((uint8_t *)ix->rk_names_ctl.p + 16);
-        HIPCHK(hipMemcpyAsync(d_counters, ix->stats + KMM_STAT_REC_NO_QUAL, 24, hipMemcpyDeviceToDevice, ix->stream));
-        if (carried)
-            HIPCHK(hipMemcpyAsync(ix->bam_out.p, ix->bam_mate.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream));
-        const uint64_t n_tiles = ((uint64_t)n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE;
-        KMMCHK(be.decode(n_tiles, (uint8_t *)ix->bam_out.p + carry));
-        if (n_rec >= 2) {
-            ix->rk_mates_call = ix->rk_raw_call = true;
-            const int rc = kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, n_text, qual ? KMM_FORMAT_FASTQ : KMM_FORMAT_FASTA2, c.k, c.max_freq,
-                                           c.also_revcomp, c.lut, &taken, &recs);
-            ix->rk_mates_call = ix->rk_raw_call = false;
-            KMMCHK(rc); // (the inner call has put its own entries back)
-            if (recs != (n_rec & ~(int64_t)1) || ((n_rec & 1) == 0 && taken != n_text) || taken > n_text)
-                return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %lld decoded bytes, %lld of %lld records mapped as pairs", (long long)taken,
-                            (long long)n_text, (long long)recs, (long long)n_rec);
-        }
-        // the raw walk, pair form
-        kmm_index::RkQueue &q = ix->rkq[0];
-        const size_t off_kept = 2 * (size_t)n_tiles * 8, off_tot = (off_kept + 2 * (size_t)n_tiles * 4 + 15) & ~(size_t)15;
-        KMMCHK(ensure(ix->bam_raw, off_tot + 64));
-        uint8_t *w = (uint8_t *)ix->bam_raw.p;
-        unsigned long long *rec_base = (unsigned long long *)w, *byte_base = rec_base + n_tiles, *tot = (unsigned long long *)(w + off_tot);
-        uint32_t *kept_bytes = (uint32_t *)(w + off_kept), *kept_recs = kept_bytes + n_tiles;
-        unsigned long long *ctl = (unsigned long long *)ix->bam_raw_ctl.p;
-        const uint64_t n_entries = (uint64_t)recs;
-        KMMCHK(ensure(ix->bam_raw_pos, (size_t)n_entries * 8 + 64)); // (the start of every selected record that has an entry)
-        unsigned long long *pos = (unsigned long long *)ix->bam_raw_pos.p;
-        const int64_t first = ix->rhq_head + ix->rhq_pending - recs; // (the inner call's entries: the queue's last)
-        if (first < 0)
-            return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld entries of the call and %lld entries pending", (long long)recs, (long long)ix->rhq_pending);
-        // (no entries: the kernels read none — e >= n_entries comes first — and the pointers stay null)
-        const uint32_t *hits = n_entries ? (const uint32_t *)ix->rhq_hits.p + first : nullptr;
-        const uint32_t *windows = n_entries && ix->record_hits == 2 ? (const uint32_t *)ix->rhq_win.p + first : nullptr;
-        const RkPairRule rule = {{(uint32_t)ix->rk_min_hits, (uint32_t)ix->rk_min_permille, (uint32_t)ix->rk_invert}, (uint32_t)ix->rk_pair_rule};
-        const Tile *tl = (const Tile *)be.tiles(be.cur);
-        const kmm_bam::Sel sel = be.sel;
-        const uint8_t *d_carry = carried ? (const uint8_t *)ix->bam_raw_mate.p : nullptr;
-        const uint32_t carry_len = carried ? (uint32_t)raw_carry : 0u;
-        ScopedTimer tm;
-        KMMCHK(tm.begin(ix, KMM_KERNEL_BAM_RAW_MATES));
-        HIPCHK(hipMemsetAsync(ctl, 0xFF, 24, ix->stream));
-        if (n_entries > 0)
-            HIPCHK(hipMemsetAsync(pos, 0xFF, (size_t)n_entries * 8, ix->stream));
-        hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)tl + 4, 8u, n_tiles, rec_base, tot + 2);
-        if (be.selected)
-            hipLaunchKernelGGL(kmm_bam::k_bam_raw_count_pairs<true>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref,
-                               sel, tl, (const unsigned long long *)rec_base, hits, windows, n_entries, rule, carried, kept_bytes, kept_recs, pos,
-                               ctl);
-        else
-            hipLaunchKernelGGL(kmm_bam::k_bam_raw_count_pairs<false>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref,
-                               sel, tl, (const unsigned long long *)rec_base, hits, windows, n_entries, rule, carried, kept_bytes, kept_recs, pos,
-                               ctl);
-        if (n_entries > 0)
-            hipLaunchKernelGGL(kmm_bam::k_bam_raw_pair_names, be.wave_grid(n_entries / 2), dim3(256), 0, ix->stream, be.d,
-                               co.consumed, (const unsigned long long *)pos, n_entries, carried, d_carry, carry_len, ctl);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h_ctl, ctl, 24, hipMemcpyDeviceToHost, ix->stream));
-        HIPCHK(hipStreamSynchronize(ix->stream));
-        if (h_ctl[0] != kmm_bam::NONE) {
-            (void)tm.end();
-            const long long p = (long long)(pairs0 + (int64_t)h_ctl[0]);
-            return fail(KMM_ERR_MALFORMED, "kmm_map_bam: \"record_bam_mates\" is 1 and pair %lld of the stream is none: records %lld and %lld "
-                        "are not mates (their read_name bytes differ): collate the file by name (`samtools collate`) and exclude secondary "
-                        "and supplementary records (0x900) (nothing of the call is appended)", p, 2 * p, 2 * p + 1);
-        }
-        const bool odd = (n_rec & 1) != 0;
-        if (odd != (h_ctl[1] != kmm_bam::NONE) || (odd && (h_ctl[1] >= co.consumed || h_ctl[2] > co.consumed - h_ctl[1]))) {
-            (void)tm.end();
-            return fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld selected records with the carry, the odd last one reported at %llu (%llu bytes)",
-                        (long long)n_rec, h_ctl[1], h_ctl[2]);
-        }
-        if (c.last_chunk && odd) {
-            (void)tm.end();
-            return bam_raw_mates_unpaired((long long)(2 * ix->bam_pairs_done + 1));
-        }
-        if (odd) {
-            // the odd last record's text (what the inner call left) and raw bytes go to the SPARE carry buffers, before anything is
-            // appended: a failure here still leaves the queues and the waiting mate as the call found them
-            const int64_t left = n_text - taken;
-            KMMCHK(ensure(ix->bam_mate_next, (size_t)left + 64)); // (may free and reallocate: a device-wide sync, rare)
-            KMMCHK(ensure(ix->bam_raw_mate_next, (size_t)h_ctl[2] + 64));
-            HIPCHK(hipMemcpyAsync(ix->bam_mate_next.p, (const uint8_t *)ix->bam_out.p + taken, (size_t)left, hipMemcpyDeviceToDevice, ix->stream));
-            HIPCHK(hipMemcpyAsync(ix->bam_raw_mate_next.p, be.d + h_ctl[1], (size_t)h_ctl[2], hipMemcpyDeviceToDevice, ix->stream));
-        }
-        if (n_entries > 0) {
-            KMMCHK(rkq_reserve(ix, q, (int64_t)co.consumed + (int64_t)carry_len));
-            unsigned long long *tail = (unsigned long long *)q.ctl.p;
-            hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)kept_bytes, 1u, n_tiles, byte_base, tot);
-            hipLaunchKernelGGL(kmm_bam::k_bam_raw_scan, dim3(1), dim3(1024), 0, ix->stream, (const uint32_t *)kept_recs, 1u, n_tiles,
-                               (unsigned long long *)nullptr, tot + 1);
-            if (carried) {
-                const unsigned blocks = (unsigned)std::min<uint64_t>(((uint64_t)carry_len + 4095) / 4096, 64);
-                hipLaunchKernelGGL(kmm_bam::k_bam_raw_carry, dim3(blocks), dim3(256), 0, ix->stream, d_carry, carry_len, hits, windows, n_entries,
-                                   rule, (const unsigned long long *)tail, (uint8_t *)q.text.p);
-            }
-            if (be.selected)
-                hipLaunchKernelGGL(kmm_bam::k_bam_raw_copy_pairs<true>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref,
-                                   sel, tl, (const unsigned long long *)rec_base, hits, windows, n_entries, rule, carried, carry_len,
-                                   (const uint32_t *)kept_bytes, (const unsigned long long *)byte_base, (const unsigned long long *)tail,
-                                   (uint8_t *)q.text.p);
-            else
-                hipLaunchKernelGGL(kmm_bam::k_bam_raw_copy_pairs<false>, be.wave_grid(n_tiles), dim3(256), 0, ix->stream, be.d, be.n, n_tiles, be.n_ref,
-                                   sel, tl, (const unsigned long long *)rec_base, hits, windows, n_entries, rule, carried, carry_len,
-                                   (const uint32_t *)kept_bytes, (const unsigned long long *)byte_base, (const unsigned long long *)tail,
-                                   (uint8_t *)q.text.p);
-            hipLaunchKernelGGL(kmm_bam::k_bam_raw_advance_pairs, dim3(1), dim3(64), 0, ix->stream, tail, (const unsigned long long *)tot, hits, windows,
-                               n_entries, rule, carried, carry_len);
-            HIPCHK(hipGetLastError());
-            q.bound += (int64_t)co.consumed + (int64_t)carry_len;
-        }
-        KMMCHK(tm.end());
-        return KMM_OK;
-    };
-    const int rc = body();
-    if (rc != KMM_OK) {
-        put_back(true);
-        return rc;
-    }
-    ix->rk_snap.valid = false;
-    // the next carry: what body() put into the spare buffers becomes the waiting mate (the kernels that read the old one are queued
-    // in front of whatever writes that buffer next); nothing here can fail
-    if ((n_rec & 1) != 0) {
-        std::swap(ix->bam_mate, ix->bam_mate_next);
-        std::swap(ix->bam_raw_mate, ix->bam_raw_mate_next);
-        ix->bam_mate_len = n_text - taken;
-        ix->bam_raw_mate_len = (int64_t)h_ctl[2];
-    } else {
-        ix->bam_mate_len = 0;
-        ix->bam_raw_mate_len = 0;
-    }
-    if (c.n_records)
-        *c.n_records = recs;
-    return KMM_OK;
-}
-
-// The inflated bytes of a kmm_map_bam call (d_raw[0, n_raw): the carry of the call before in front): the header on a stream's
-// first call, then the records up to the last complete one (*used), decoded into two-line FASTA in HBM and mapped by
-// kmm_map_records.  *short_header: a first window that ends inside the header (nothing is used).
-static int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw, int64_t head, int64_t tail_stop, int64_t n_raw,
-                            int64_t *used, bool *short_header)
-{
-    *used = 0;
-    *short_header = false;
-    uint64_t start0 = 0;
-    if (c.mid_stream) {
-        // a rank's share: no header — n_ref is the caller's ("bam_n_ref"), the first record starts `head` bytes
-        // into the stream's first member ("bgzf_head_skip"), where kmm_bam_find_record_start found it
-        ix->bam_n_ref = (int32_t)ix->bam_n_ref_param;
-        ix->bam_hdr_valid = false; // (kmm_bam_stream_header: a share has no header)
-        start0 = (uint64_t)head;
-    } else if (c.new_stream) {
-        // the header (magic, l_text, text, n_ref, the references) is read back in growing prefixes: its length is only known by
-        // walking it, and it is read once per stream
-        ix->bam_n_ref = -1;
-        ix->bam_hdr_valid = false;
-        std::vector<uint8_t> h;
-        uint64_t want = n_raw < (1 << 16) ? (uint64_t)n_raw : 1u << 16, hdr_end = 0;
-        int32_t n_ref = 0;
-        for (;;) {
-            h.resize(want);
-            if (want)
-                HIPCHK(hipMemcpyAsync(h.data(), d_raw, want, hipMemcpyDeviceToHost, ix->stream));
-            HIPCHK(hipStreamSynchronize(ix->stream));
-            const int r = kmm_bam::parse_header(h.data(), want, &hdr_end, &n_ref);
-            if (r < 0)
-                return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the stream does not start with a BAM header (magic \"BAM\\1\", lengths)");
-            if (r == 0)
-                break;
-            if (want == (uint64_t)n_raw) {
-                if (c.last_chunk)
-                    return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside the BAM header (%lld bytes)", (long long)n_raw);
-                *short_header = true;
-                return KMM_OK;
-            }
-            want = want * 4 < (uint64_t)n_raw ? want * 4 : (uint64_t)n_raw;
-        }
-        ix->bam_n_ref = n_ref;
-        ix->bam_hdr.assign(h.begin(), h.begin() + (std::ptrdiff_t)hdr_end); // (kmm_bam_stream_header: magic through the last reference)
-        ix->bam_hdr_valid = true;
-        ix->bam_header_bytes += (int64_t)hdr_end;
-        start0 = hdr_end;
-    } else if (ix->bam_n_ref < 0) {
-        return fail(KMM_ERR_INVALID_ARG, "kmm_map_bam: no BAM stream was started on this handle (KMM_FORMAT_NEW_STREAM)");
-    }
-    const bool qual = record_quality(ix) > 0;
-    BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl, qual, ix->original_strand != 0};
-    KMMCHK(selection_of(ix, "kmm_map_bam", false, ix->bam_n_ref, be.sel));
-    be.selected = !be.sel.flags_only();
-    // (the named form: stream_call_start let the call through with "record_hits" on; a quality floor is refused in that mode, so
-    // `qual` is false here and the text goes to the records front end as FASTQ all the same)
-    be.named = ix->record_names != 0;
-    be.sfx = ix->record_names_mate_suffix != 0;
-    kmm_bam::CallOut co;
-    KMMCHK(kmm_bam::run_call(be, (uint64_t)n_raw, start0, co));
-    ix->bam_false_starts += (int64_t)co.false_starts;
-    ix->bam_continuations += (int64_t)co.continuations;
-    if (co.err_pos != kmm_bam::NONE)
-        return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the record at inflated byte %llu of the call does not fit its block_size (or its "
-                    "refID / next_refID / read_name are not a record's)", co.err_pos);
-    if (c.last_chunk && co.consumed != (uint64_t)n_raw && tail_stop >= 0)
-        return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside a record (%lld bytes behind the last complete one): "
-                    "\"bgzf_tail_stop\" cut the last member after %lld inflated bytes, which is no record boundary (a share boundary "
-                    "guessed by kmm_bam_find_record_start lay inside a record: map the file with one rank)",
-                    (long long)(n_raw - (int64_t)co.consumed), (long long)tail_stop);
-    if (c.last_chunk && co.consumed != (uint64_t)n_raw)
-        return fail(KMM_ERR_MALFORMED, "kmm_map_bam: the file ends inside a record (%lld bytes behind the last complete one)",
-                    (long long)(n_raw - (int64_t)co.consumed));
-    ix->bam_calls++;
-    ix->bam_records += (int64_t)co.recs;
-    ix->bam_excluded += (int64_t)co.excluded;
-    *used = (int64_t)co.consumed;
-    if (bam_mates_on(ix))
-        return bam_map_mates(ix, c, be, co, n_raw);
-    if (bam_raw_mates_on(ix))
-        return bam_map_raw_mates(ix, c, be, co, n_raw, qual);
-    if (co.recs == 0)
-        return KMM_OK;
-    KMMCHK(ensure(ix->bam_out, (size_t)co.out_bytes + 64));
-    KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p));
-    int64_t taken = 0, recs = 0;
-    // ("record_bam", DESIGN 4.24: the inner call appends the entries and leaves the keep queue to bam_raw_keep below)
-    const bool raw = ix->record_bam && ix->record_hits && ix->record_keep;
-    ix->rk_raw_call = raw;
-    // (the quality variant's text is FASTQ: compaction and the radix path, where "min_base_quality" is applied)
-    const int rc_in = kmm_map_records(ix, (const uint8_t *)ix->bam_out.p, (int64_t)co.out_bytes, qual || be.named ? KMM_FORMAT_FASTQ : KMM_FORMAT_FASTA2,
-                                      c.k, c.max_freq, c.also_revcomp, c.lut, &taken, &recs);
-    ix->rk_raw_call = false;
-    KMMCHK(rc_in);
-    int rc = KMM_OK;
-    if (taken != (int64_t)co.out_bytes || recs != (int64_t)co.recs)
-        rc = fail(KMM_ERR_INTERNAL, "kmm_map_bam: %lld of %llu decoded bytes, %lld of %llu records mapped", (long long)taken,
-                  co.out_bytes, (long long)recs, co.recs);
-    else if (raw)
-        rc = bam_raw_keep(ix, be, co, n_raw);
-    if (rc != KMM_OK && raw && ix->rk_snap.valid) { // (a failing call appends nothing to either queue: what the inner call found is put back)
-        ix->rhq_pending = ix->rk_snap.pending;
-        rkq_rollback(ix, ix->rkq[0], ix->rk_snap.bound);
-        ix->bam_calls--;
-        ix->bam_records -= (int64_t)co.recs;
-        ix->bam_excluded -= (int64_t)co.excluded;
-    }
-    if (raw)
-        ix->rk_snap.valid = false;
-    KMMCHK(rc);
-    if (c.n_records)
-        *c.n_records = recs;
-    return KMM_OK;
-}
+namespace {
+#include "kmm_bam_host.hpp" // bam_map_inflated and what it runs, rs_*: behind StreamCall and bgzf_inflate, in front of kmm_map_bam
+} // namespace
 
 int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags, int k, int max_freq, int also_revcomp,
                 const uint8_t *lut, int64_t *consumed_comp, int64_t *n_records)
@@ -4637,10 +3906,8 @@ int kmm_map_bam(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int flags,
         BgzfCall b;
         KMMCHK(bgzf_inflate(ix, c, comp, n_comp, b, bgzf_rank_share));
         if (!b.d_raw) { // (no member and no carried byte: a last call that brings nothing can still leave a mate 1 alone)
-            if (c.last_chunk && bam_mates_on(ix) && ix->bam_mate_len > 0)
-                return bam_mates_unpaired((long long)(2 * ix->bam_pairs_done + 1));
-            if (c.last_chunk && bam_raw_mates_on(ix) && ix->bam_mate_len > 0)
-                return bam_raw_mates_unpaired((long long)(2 * ix->bam_pairs_done + 1));
+            if (c.last_chunk && ix->bam_mate_len > 0 && (bam_mates_on(ix) || bam_raw_mates_on(ix)))
+                return bam_unpaired_end(bam_mates_on(ix) ? "record_names_pairs" : "record_bam_mates", 2 * ix->bam_pairs_done + 1);
             return KMM_OK;
         }
         int64_t used = 0;
@@ -4680,91 +3947,6 @@ int kmm_bam_stream_header(kmm_index_t *ix, uint8_t *out, int64_t capacity, int64
     });
 }
 
-// ---- kmm_bam_header, kmm_bam_find_record_start: where a rank's share of a BAM file begins.  Both inflate whole
-// members of the caller's window into buffers of their own (rs_*) on the handle's stream and leave its stream state alone.
-
-// The chain of whole members at the head of comp[0, n_comp): m_off / o_off as k_inflate_bgzf takes them, p = where it ends.
-struct RsChain {
-    std::vector<unsigned long long> m_off{0ull}, o_off{0ull};
-    uint64_t p = 0;
-    uint32_t n_members() const { return (uint32_t)(m_off.size() - 1); }
-};
-
-// Walks the chain on from c.p until it holds at least out_want inflated bytes, or to the last whole member of the window (an
-// incomplete one ends the chain: the caller brings it again in a longer window).
-static int rs_scan(const char *who, const uint8_t *comp, int64_t n_comp, unsigned long long out_want, RsChain &c)
-{
-    const uint64_t limit = (uint64_t)n_comp;
-    while (c.o_off.back() < out_want && c.p + 18 <= limit && c.m_off.size() < 0x7FFFFFFFu) {
-        const uint64_t p = c.p;
-        const uint32_t ms = kmm_gz::bgzf_member_size(comp + p, limit - p);
-        if (!ms) {
-            const uint32_t xlen = (uint32_t)comp[p + 10] | ((uint32_t)comp[p + 11] << 8);
-            if (comp[p] == 0x1f && comp[p + 1] == 0x8b && comp[p + 2] == 8 && (comp[p + 3] & 4) && p + 12 + xlen + 8 > limit)
-                break; // (a header that runs past the window)
-            return fail(KMM_ERR_MALFORMED, "%s: no BGZF member at compressed byte %llu of the window", who, (unsigned long long)p);
-        }
-        if (p + ms > limit)
-            break;
-        const uint32_t isize = kmm_gz::rd32(comp + p + ms - 4);
-        if ((uint64_t)isize > (uint64_t)ms * 1032ull + 64ull)
-            return fail(KMM_ERR_MALFORMED, "%s: member at compressed byte %llu claims %u inflated bytes for %u compressed ones", who,
-                        (unsigned long long)p, isize, ms);
-        c.p = p + ms;
-        c.m_off.push_back(c.p);
-        c.o_off.push_back(c.o_off.back() + isize);
-    }
-    return KMM_OK;
-}
-
-// Inflates the chain's members into rs_raw and checks their CRC32s (k_inflate_bgzf, k_crc_bgzf, as bgzf_inflate launches
-// them); synchronises.  A corrupt member is KMM_ERR_MALFORMED.
-static int rs_inflate(kmm_index_t *ix, const char *who, const uint8_t *comp, const RsChain &c)
-{
-    const uint32_t n_members = c.n_members();
-    KMMCHK(ensure(ix->rs_comp, (size_t)c.p + 64));
-    KMMCHK(ensure(ix->rs_raw, (size_t)c.o_off.back() + 4096));
-    KMMCHK(ensure(ix->rs_meta, (size_t)(n_members + 1) * 16 + 64));
-    KMMCHK(ensure(ix->rs_err, 64));
-    KMMCHK(ensure(ix->rs_status, (size_t)n_members + 64));
-    KMMCHK(ensure_crc_tables(ix));
-    const uint32_t grid_threads = ((n_members < 65536u ? n_members : 65536u) + 63u) / 64u * 64u;
-    KMMCHK(ensure(ix->bgzf_tabs, (size_t)grid_threads * kmm_gz::SCRATCH_BYTES)); // (scratch of the inflater: the stream orders its users)
-    uint8_t *d_comp = (uint8_t *)ix->rs_comp.p, *d_raw = (uint8_t *)ix->rs_raw.p;
-    unsigned long long *d_moff = (unsigned long long *)ix->rs_meta.p, *d_ooff = d_moff + (n_members + 1);
-    const unsigned int err0[4] = {0u, 0xFFFFFFFFu, 0u, 0u};
-    HIPCHK(hipMemcpyAsync(d_comp, comp, (size_t)c.p, hipMemcpyHostToDevice, ix->stream));
-    HIPCHK(hipMemcpyAsync(d_moff, c.m_off.data(), (size_t)(n_members + 1) * 8, hipMemcpyHostToDevice, ix->stream));
-    HIPCHK(hipMemcpyAsync(d_ooff, c.o_off.data(), (size_t)(n_members + 1) * 8, hipMemcpyHostToDevice, ix->stream));
-    HIPCHK(hipMemcpyAsync(ix->rs_err.p, err0, sizeof err0, hipMemcpyHostToDevice, ix->stream));
-    HIPCHK(hipMemsetAsync(ix->rs_status.p, 0, n_members, ix->stream));
-    hipLaunchKernelGGL(kmm_gz::k_inflate_bgzf, dim3(grid_threads / 64u), dim3(64), 0, ix->stream, d_comp, d_moff, d_ooff, d_raw, n_members,
-                       (uint8_t *)ix->bgzf_tabs.p, (const uint32_t *)nullptr, (unsigned int *)ix->rs_err.p, (unsigned long long *)nullptr,
-                       (uint8_t *)ix->rs_status.p);
-    hipLaunchKernelGGL(kmm_gz::k_crc_bgzf, dim3((n_members + 63u) / 64u), dim3(256), 0, ix->stream, d_comp, d_moff, d_ooff,
-                       (const uint8_t *)d_raw, n_members, (const uint32_t *)ix->bgzf_crc.p, (unsigned int *)ix->rs_err.p,
-                       (const uint8_t *)ix->rs_status.p);
-    HIPCHK(hipGetLastError());
-    unsigned int err[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(err, ix->rs_err.p, sizeof err, hipMemcpyDeviceToHost, ix->stream));
-    HIPCHK(hipStreamSynchronize(ix->stream));
-    if (err[0])
-        return fail(KMM_ERR_MALFORMED, "%s: %u corrupt BGZF member(s); the first starts at compressed byte %llu of the window (inflater code %u)",
-                    who, err[0], err[1] < n_members ? c.m_off[err[1]] : 0ull, err[2]);
-    return KMM_OK;
-}
-
-static int rs_args(kmm_index_t *ix, const char *who, const uint8_t *comp, int64_t n_comp)
-{
-    if (!ix)
-        return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
-    if (n_comp < 0 || (n_comp > 0 && !comp))
-        return fail(KMM_ERR_INVALID_ARG, "comp NULL or n_comp negative");
-    if (n_comp > 0 && is_device_ptr(comp))
-        return fail(KMM_ERR_INVALID_ARG, "%s takes the compressed bytes from host memory (the member chain is read there)", who);
-    HIPCHK(hipSetDevice(ix->device));
-    return KMM_OK;
-}
 
 int kmm_bam_header(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int32_t *n_ref, int64_t *hdr_member, int64_t *hdr_skip)
 {

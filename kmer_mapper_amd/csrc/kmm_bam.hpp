@@ -1,5 +1,5 @@
 // kmm_bam.hpp — part of libkmm: BAM records (SAM/BAM specification 4.2) found and decoded ON THE GPU (kmm_map_bam; included by
-// kmm.hip, compiled by itself with g++ in tests/test_bam_walk_on_the_cpu.py, where the very same orchestration runs on the CPU).
+// kmm.hip — the host side is kmm_bam_host.hpp —, compiled by itself with g++ in tests/test_bam_walk_on_the_cpu.py, where the very same orchestration runs on the CPU).
 //
 // A BAM file is a BGZF stream (kmm_gpu_inflate.hpp inflates it) holding a header and then records, each one prefixed by its
 // length: where a record starts is known only by walking the chain from the first one — a serial chain.  It is cut the way
@@ -829,7 +829,7 @@ inline int parse_header(const uint8_t *d, uint64_t n, uint64_t *hdr_end, int32_t
     return 0;
 }
 
-// ---- the orchestration, written once against a backend (GPU: kmm.hip; CPU: CpuBackend below) ----
+// ---- the orchestration, written once against a backend (GPU: BamGpuBackend, kmm_bam_host.hpp; CPU: CpuBackend below) ----
 //   be.spec(n_tiles, start0)                 the speculative claims into the current buffer
 //   be.check(n_tiles, start0, Ctl &)         counts the claims that disagree (synchronises: the control words come back)
 //   be.fix(n_tiles, start0)                  the disagreeing claims walked again, into the other buffer; swaps the buffers

@@ -1,5 +1,5 @@
 // kmm_sam.hpp — part of libkmm: SAM text records (SAM/BAM specification 1.4) turned into two-line FASTA ON THE GPU
-// (KMM_FORMAT_SAM; included by kmm.hip, compiled by itself with g++ in tests/test_sam_on_the_cpu.py, where the same per-line
+// (KMM_FORMAT_SAM; included by kmm.hip — the host side is kmm_sam_host.hpp —, compiled by itself with g++ in tests/test_sam_on_the_cpu.py, where the same per-line
 // steps run on the CPU).
 //
 // The QNAME grammar [!-?A-~]{1,254} cannot start with '@', so every line of a SAM stream is either a header line (first byte

@@ -4,11 +4,9 @@
 // QUAL '\n' per selected record.
 #pragma once
 
-#include "kmm_bam.hpp"
+#include "bam_windows_cpu.hpp"
 
-#include <cstddef>
-#include <cstring>
-#include <vector>
+#include <algorithm>
 
 // opt: excl, incl, min_mapq, n_regions, keep_unplaced, original_strand, mate_suffix, lanes.  regions: n_regions x (refID, beg,
 // end), merged here as the library merges them.  Windows end at cuts[0 .. n_cuts) (the last one = n).  out: the named FASTQ of
@@ -19,81 +17,39 @@
 extern "C" int bam_fastq_cpu(const uint8_t *data, uint64_t n, const uint64_t *cuts, int n_cuts, const uint32_t *opt,
                              const int64_t *regions, uint8_t *out, uint64_t out_cap, uint64_t *out_n, uint64_t *stats)
 {
-    uint64_t pos = 0, w = 0, base = 0; // base: stream offset of the window's first byte
-    int32_t n_ref = -1;
-    uint64_t start0 = 0;
     for (int i = 0; i <= 9; ++i)
         stats[i] = 0;
     std::vector<kmm_sel::Interval> iv;
     for (uint32_t i = 0; i < opt[3]; ++i)
         iv.push_back(kmm_sel::Interval{regions[3 * i], regions[3 * i + 1], regions[3 * i + 2]});
     kmm_sel::merge_intervals(iv);
-    std::vector<uint8_t> carry;
-    for (int i = 0; i < n_cuts; ++i) {
-        const uint64_t end = cuts[i];
-        if (end < pos)
-            continue;
-        const bool last = end == n;
-        std::vector<uint8_t> win(carry);
-        win.insert(win.end(), data + pos, data + end);
-        if (n_ref < 0) {
-            uint64_t hdr_end = 0;
-            int32_t nr = 0;
-            const int r = kmm_bam::parse_header(win.data(), win.size(), &hdr_end, &nr);
-            if (r < 0)
-                return -1;
-            if (r > 0) {
-                if (last)
-                    return -2;
-                continue; // (a first window inside the header uses nothing: the next one starts at the same place)
-            }
-            n_ref = nr;
-            start0 = hdr_end;
-            stats[5] = hdr_end;
-        }
-        kmm_bam::CpuBackend be;
-        be.d = win.data();
-        be.n = win.size();
-        be.n_ref = n_ref;
-        be.excl = opt[0];
-        be.sel.incl = opt[1];
-        be.sel.min_mapq = opt[2];
-        be.sel.n_iv = (uint32_t)iv.size();
-        be.sel.keep_unplaced = opt[4];
-        be.sel.iv = iv.data();
-        be.orig = opt[5] != 0;
-        be.named = true;
-        be.mate_suffix = opt[6] != 0;
-        be.lanes = opt[7];
-        kmm_bam::CallOut co;
-        if (kmm_bam::run_call(be, win.size(), start0, co) != 0)
-            return -6;
-        ++stats[4];
-        stats[2] += co.false_starts;
-        stats[3] += co.continuations;
-        if (co.err_pos != kmm_bam::NONE) {
-            stats[6] = base + co.err_pos;
-            return -3;
-        }
-        if (last && co.consumed != win.size())
-            return -4;
-        if (w + co.out_bytes > out_cap)
-            return -5;
-        if (co.recs)
-            be.decode(out + w);
-        w += co.out_bytes;
-        stats[0] += co.recs;
-        stats[1] += co.excluded;
-        stats[7] += be.no_qual;
-        stats[8] += be.reversed;
-        stats[9] += be.replaced;
-        carry.assign(win.begin() + (std::ptrdiff_t)co.consumed, win.end());
-        base += co.consumed;
-        pos = end;
-        start0 = 0;
-    }
-    *out_n = w;
-    return 0;
+    uint64_t w = 0;
+    const int rc = bam_windows::run(
+        data, n, cuts, n_cuts, stats, bam_windows::Slots{4, 6, 5, 2, 3},
+        [&](kmm_bam::CpuBackend &be) {
+            be.excl = opt[0];
+            be.sel.incl = opt[1];
+            be.sel.min_mapq = opt[2];
+            be.sel.n_iv = (uint32_t)iv.size();
+            be.sel.keep_unplaced = opt[4];
+            be.sel.iv = iv.data();
+            be.orig = opt[5] != 0;
+            be.named = true;
+            be.mate_suffix = opt[6] != 0;
+            be.lanes = opt[7];
+        },
+        [&](kmm_bam::CpuBackend &be, const kmm_bam::CallOut &co, const std::vector<uint8_t> &, uint64_t, bool) {
+            const int r = bam_windows::decode_to(be, co, out, out_cap, &w, false);
+            if (r != 0)
+                return r;
+            stats[7] += be.no_qual;
+            stats[8] += be.reversed;
+            stats[9] += be.replaced;
+            return 0;
+        });
+    if (rc == 0)
+        *out_n = w;
+    return rc;
 }
 
 // One record (rec[0, n): block_size and all) decoded by every lane of `lanes` on its own, twice — into bytes that were 0x00 and

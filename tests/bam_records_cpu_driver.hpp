@@ -4,7 +4,7 @@
 // kernels of "record_bam" run: the selected records whose entry passes the keep rule, copied as they stand.
 #pragma once
 
-#include "kmm_bam.hpp"
+#include "bam_windows_cpu.hpp"
 
 #include <cstddef>
 #include <cstdlib>
@@ -23,9 +23,7 @@ extern "C" int bam_records_cpu(const uint8_t *data, uint64_t n, const uint64_t *
                                const int64_t *regions, const uint32_t *hits, const uint32_t *windows, uint64_t n_entries, uint8_t *out,
                                uint64_t out_cap, uint64_t tail0, uint64_t *out_n, uint64_t *stats)
 {
-    uint64_t pos = 0, w = tail0, base = 0, done = 0; // base: stream offset of the window's first byte; done: entries used
-    int32_t n_ref = -1;
-    uint64_t start0 = 0;
+    uint64_t w = tail0, done = 0; // done: entries used
     for (int i = 0; i <= 5; ++i)
         stats[i] = 0;
     *out_n = 0;
@@ -41,79 +39,30 @@ extern "C" int bam_records_cpu(const uint8_t *data, uint64_t n, const uint64_t *
         return -9;
     uint8_t *queue = (uint8_t *)mem;
     memset(queue, (int)opt[9], (size_t)out_cap);
-    int rc = 0;
-    std::vector<uint8_t> carry;
-    for (int i = 0; i < n_cuts && rc == 0; ++i) {
-        const uint64_t end = cuts[i];
-        if (end < pos)
-            continue;
-        const bool last = end == n;
-        std::vector<uint8_t> win(carry);
-        win.insert(win.end(), data + pos, data + end);
-        if (n_ref < 0) {
-            uint64_t hdr_end = 0;
-            int32_t nr = 0;
-            const int r = kmm_bam::parse_header(win.data(), win.size(), &hdr_end, &nr);
-            if (r < 0) {
-                rc = -1;
-                break;
-            }
-            if (r > 0) {
-                if (last)
-                    rc = -2;
-                continue; // (a first window inside the header uses nothing: the next one starts at the same place)
-            }
-            n_ref = nr;
-            start0 = hdr_end;
-            stats[4] = hdr_end;
-        }
-        kmm_bam::CpuBackend be;
-        be.d = win.data();
-        be.n = win.size();
-        be.n_ref = n_ref;
-        be.excl = opt[0];
-        be.sel.incl = opt[1];
-        be.sel.min_mapq = opt[2];
-        be.sel.n_iv = (uint32_t)iv.size();
-        be.sel.keep_unplaced = opt[4];
-        be.sel.iv = iv.data();
-        be.lanes = opt[5];
-        kmm_bam::CallOut co;
-        if (kmm_bam::run_call(be, win.size(), start0, co) != 0) {
-            rc = -6;
-            break;
-        }
-        ++stats[3];
-        if (co.err_pos != kmm_bam::NONE) {
-            stats[5] = base + co.err_pos;
-            rc = -3;
-            break;
-        }
-        if (last && co.consumed != win.size()) {
-            rc = -4;
-            break;
-        }
-        if (done + co.recs > n_entries) {
-            rc = -8;
-            break;
-        }
-        uint64_t kept_recs = 0;
-        const uint64_t kept = be.raw_count(hits + done, windows ? windows + done : nullptr, co.recs, rule, &kept_recs);
-        if (w + kept > out_cap) {
-            rc = -5;
-            break;
-        }
-        be.raw_copy(hits + done, windows ? windows + done : nullptr, co.recs, rule, queue, w);
-        w += kept;
-        done += co.recs;
-        stats[0] += co.recs;
-        stats[1] += co.excluded;
-        stats[2] += kept_recs;
-        carry.assign(win.begin() + (std::ptrdiff_t)co.consumed, win.end());
-        base += co.consumed;
-        pos = end;
-        start0 = 0;
-    }
+    const int rc = bam_windows::run(
+        data, n, cuts, n_cuts, stats, bam_windows::Slots{3, 5, 4},
+        [&](kmm_bam::CpuBackend &be) {
+            be.excl = opt[0];
+            be.sel.incl = opt[1];
+            be.sel.min_mapq = opt[2];
+            be.sel.n_iv = (uint32_t)iv.size();
+            be.sel.keep_unplaced = opt[4];
+            be.sel.iv = iv.data();
+            be.lanes = opt[5];
+        },
+        [&](kmm_bam::CpuBackend &be, const kmm_bam::CallOut &co, const std::vector<uint8_t> &, uint64_t, bool) {
+            if (done + co.recs > n_entries)
+                return -8;
+            uint64_t kept_recs = 0;
+            const uint64_t kept = be.raw_count(hits + done, windows ? windows + done : nullptr, co.recs, rule, &kept_recs);
+            if (w + kept > out_cap)
+                return -5;
+            be.raw_copy(hits + done, windows ? windows + done : nullptr, co.recs, rule, queue, w);
+            w += kept;
+            done += co.recs;
+            stats[2] += kept_recs;
+            return 0;
+        });
     memcpy(out, queue, (size_t)out_cap);
     free(mem);
     if (rc == 0)

@@ -3,7 +3,7 @@
 // the window loops of bam_cpu_driver.hpp and sam_cpu_driver.hpp, with the four-line FASTQ output in place of the two-line FASTA.
 #pragma once
 
-#include "kmm_bam.hpp"
+#include "bam_windows_cpu.hpp"
 #include "kmm_sam.hpp"
 
 #include <cstddef>
@@ -14,70 +14,25 @@
 extern "C" int bam_qual_cpu(const uint8_t *data, uint64_t n, const uint64_t *cuts, int n_cuts, uint32_t excl, uint8_t *out,
                             uint64_t out_cap, uint64_t *out_n, uint64_t *stats)
 {
-    uint64_t pos = 0, w = 0, base = 0;
-    int32_t n_ref = -1;
-    uint64_t start0 = 0;
     for (int i = 0; i <= 7; ++i)
         stats[i] = 0;
-    std::vector<uint8_t> carry;
-    for (int i = 0; i < n_cuts; ++i) {
-        const uint64_t end = cuts[i];
-        if (end < pos)
-            continue;
-        const bool last = end == n;
-        std::vector<uint8_t> win(carry);
-        win.insert(win.end(), data + pos, data + end);
-        if (n_ref < 0) {
-            uint64_t hdr_end = 0;
-            int32_t nr = 0;
-            const int r = kmm_bam::parse_header(win.data(), win.size(), &hdr_end, &nr);
-            if (r < 0)
-                return -1;
-            if (r > 0) {
-                if (last)
-                    return -2;
-                continue;
-            }
-            n_ref = nr;
-            start0 = hdr_end;
-            stats[5] = hdr_end;
-        }
-        kmm_bam::CpuBackend be;
-        be.d = win.data();
-        be.n = win.size();
-        be.n_ref = n_ref;
-        be.excl = excl;
-        be.qual = true;
-        kmm_bam::CallOut co;
-        if (kmm_bam::run_call(be, win.size(), start0, co) != 0)
-            return -6;
-        ++stats[4];
-        stats[2] += co.false_starts;
-        stats[3] += co.continuations;
-        if (co.err_pos != kmm_bam::NONE) {
-            stats[6] = base + co.err_pos;
-            return -3;
-        }
-        if (last && co.consumed != win.size())
-            return -4;
-        if (w + co.out_bytes > out_cap)
-            return -5;
-        if (co.recs) {
-            std::vector<uint8_t> exact(co.out_bytes); // (exactly the totals' size: a write past it is caught by the sanitizer)
-            be.decode(exact.data());
-            memcpy(out + w, exact.data(), exact.size());
-        }
-        w += co.out_bytes;
-        stats[0] += co.recs;
-        stats[1] += co.excluded;
-        stats[7] += be.no_qual;
-        carry.assign(win.begin() + (std::ptrdiff_t)co.consumed, win.end());
-        base += co.consumed;
-        pos = end;
-        start0 = 0;
-    }
-    *out_n = w;
-    return 0;
+    uint64_t w = 0;
+    const int rc = bam_windows::run(
+        data, n, cuts, n_cuts, stats, bam_windows::Slots{4, 6, 5, 2, 3},
+        [&](kmm_bam::CpuBackend &be) {
+            be.excl = excl;
+            be.qual = true;
+        },
+        [&](kmm_bam::CpuBackend &be, const kmm_bam::CallOut &co, const std::vector<uint8_t> &, uint64_t, bool) {
+            const int r = bam_windows::decode_to(be, co, out, out_cap, &w, true);
+            if (r != 0)
+                return r;
+            stats[7] += be.no_qual;
+            return 0;
+        });
+    if (rc == 0)
+        *out_n = w;
+    return rc;
 }
 
 // As sam_cpu (sam_cpu_driver.hpp); out: the four-line FASTQ of the kept records; stats[5]: kept records with bases whose QUAL is

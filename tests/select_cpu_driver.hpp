@@ -4,7 +4,7 @@
 // merged here by kmm_sel::merge_intervals, as the library does before it uploads one.
 #pragma once
 
-#include "kmm_bam.hpp"
+#include "bam_windows_cpu.hpp"
 #include "kmm_sam.hpp"
 
 #include <cstddef>
@@ -38,71 +38,29 @@ extern "C" int select_bam_cpu(const uint8_t *data, uint64_t n, const uint64_t *c
                               const int64_t *iv3)
 {
     SelectTables tb(rules, iv3, nullptr, nullptr, 0);
-    uint64_t pos = 0, w = 0, base = 0;
-    int32_t n_ref = -1;
-    uint64_t start0 = 0;
     for (int i = 0; i < 7; ++i)
         stats[i] = 0;
-    std::vector<uint8_t> carry;
-    for (int i = 0; i < n_cuts; ++i) {
-        const uint64_t end = cuts[i];
-        if (end < pos)
-            continue;
-        const bool last = end == n;
-        std::vector<uint8_t> win(carry);
-        win.insert(win.end(), data + pos, data + end);
-        if (n_ref < 0) {
-            uint64_t hdr_end = 0;
-            int32_t nr = 0;
-            const int r = kmm_bam::parse_header(win.data(), win.size(), &hdr_end, &nr);
-            if (r < 0)
-                return -1;
-            if (r > 0) {
-                if (last)
-                    return -2;
-                continue;
-            }
-            n_ref = nr;
-            start0 = hdr_end;
-        }
-        kmm_bam::CpuBackend be;
-        be.d = win.data();
-        be.n = win.size();
-        be.n_ref = n_ref;
-        be.excl = excl;
-        be.qual = qual != 0;
-        be.orig = orig != 0;
-        be.lanes = lanes;
-        be.sel = tb.sel;
-        kmm_bam::CallOut co;
-        if (kmm_bam::run_call(be, win.size(), start0, co) != 0)
-            return -6;
-        ++stats[2];
-        if (co.err_pos != kmm_bam::NONE) {
-            stats[5] = base + co.err_pos;
-            return -3;
-        }
-        if (last && co.consumed != win.size())
-            return -4;
-        if (w + co.out_bytes > out_cap)
-            return -5;
-        if (co.recs) {
-            std::vector<uint8_t> exact(co.out_bytes); // (exactly the totals' size: a disagreement of walk and decode is the sanitizer's)
-            be.decode(exact.data());
-            memcpy(out + w, exact.data(), exact.size());
-        }
-        w += co.out_bytes;
-        stats[0] += co.recs;
-        stats[1] += co.excluded;
-        stats[3] += be.no_qual;
-        stats[4] += be.reversed;
-        carry.assign(win.begin() + (std::ptrdiff_t)co.consumed, win.end());
-        base += co.consumed;
-        pos = end;
-        start0 = 0;
-    }
-    *out_n = w;
-    return 0;
+    uint64_t w = 0;
+    const int rc = bam_windows::run(
+        data, n, cuts, n_cuts, stats, bam_windows::Slots{2, 5},
+        [&](kmm_bam::CpuBackend &be) {
+            be.excl = excl;
+            be.qual = qual != 0;
+            be.orig = orig != 0;
+            be.lanes = lanes;
+            be.sel = tb.sel;
+        },
+        [&](kmm_bam::CpuBackend &be, const kmm_bam::CallOut &co, const std::vector<uint8_t> &, uint64_t, bool) {
+            const int r = bam_windows::decode_to(be, co, out, out_cap, &w, true);
+            if (r != 0)
+                return r;
+            stats[3] += be.no_qual;
+            stats[4] += be.reversed;
+            return 0;
+        });
+    if (rc == 0)
+        *out_n = w;
+    return rc;
 }
 
 template <bool Q>

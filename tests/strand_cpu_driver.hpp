@@ -3,7 +3,7 @@
 // switch, the plain or the quality variant, and the lane count the per-record functions are called with as arguments.
 #pragma once
 
-#include "kmm_bam.hpp"
+#include "bam_windows_cpu.hpp"
 #include "kmm_sam.hpp"
 
 #include <cstddef>
@@ -15,71 +15,28 @@
 extern "C" int strand_bam_cpu(const uint8_t *data, uint64_t n, const uint64_t *cuts, int n_cuts, uint32_t excl, int qual, int orig,
                               uint32_t lanes, uint8_t *out, uint64_t out_cap, uint64_t *out_n, uint64_t *stats)
 {
-    uint64_t pos = 0, w = 0, base = 0;
-    int32_t n_ref = -1;
-    uint64_t start0 = 0;
     for (int i = 0; i < 6; ++i)
         stats[i] = 0;
-    std::vector<uint8_t> carry;
-    for (int i = 0; i < n_cuts; ++i) {
-        const uint64_t end = cuts[i];
-        if (end < pos)
-            continue;
-        const bool last = end == n;
-        std::vector<uint8_t> win(carry);
-        win.insert(win.end(), data + pos, data + end);
-        if (n_ref < 0) {
-            uint64_t hdr_end = 0;
-            int32_t nr = 0;
-            const int r = kmm_bam::parse_header(win.data(), win.size(), &hdr_end, &nr);
-            if (r < 0)
-                return -1;
-            if (r > 0) {
-                if (last)
-                    return -2;
-                continue;
-            }
-            n_ref = nr;
-            start0 = hdr_end;
-        }
-        kmm_bam::CpuBackend be;
-        be.d = win.data();
-        be.n = win.size();
-        be.n_ref = n_ref;
-        be.excl = excl;
-        be.qual = qual != 0;
-        be.orig = orig != 0;
-        be.lanes = lanes;
-        kmm_bam::CallOut co;
-        if (kmm_bam::run_call(be, win.size(), start0, co) != 0)
-            return -6;
-        ++stats[2];
-        if (co.err_pos != kmm_bam::NONE) {
-            stats[5] = base + co.err_pos;
-            return -3;
-        }
-        if (last && co.consumed != win.size())
-            return -4;
-        if (w + co.out_bytes > out_cap)
-            return -5;
-        if (co.recs) {
-            // exactly the totals' size, on the heap: a write in front of out[0] or behind the last byte is the sanitizer's
-            std::vector<uint8_t> exact(co.out_bytes);
-            be.decode(exact.data());
-            memcpy(out + w, exact.data(), exact.size());
-        }
-        w += co.out_bytes;
-        stats[0] += co.recs;
-        stats[1] += co.excluded;
-        stats[3] += be.no_qual;
-        stats[4] += be.reversed;
-        carry.assign(win.begin() + (std::ptrdiff_t)co.consumed, win.end());
-        base += co.consumed;
-        pos = end;
-        start0 = 0;
-    }
-    *out_n = w;
-    return 0;
+    uint64_t w = 0;
+    const int rc = bam_windows::run(
+        data, n, cuts, n_cuts, stats, bam_windows::Slots{2, 5},
+        [&](kmm_bam::CpuBackend &be) {
+            be.excl = excl;
+            be.qual = qual != 0;
+            be.orig = orig != 0;
+            be.lanes = lanes;
+        },
+        [&](kmm_bam::CpuBackend &be, const kmm_bam::CallOut &co, const std::vector<uint8_t> &, uint64_t, bool) {
+            const int r = bam_windows::decode_to(be, co, out, out_cap, &w, true);
+            if (r != 0)
+                return r;
+            stats[3] += be.no_qual;
+            stats[4] += be.reversed;
+            return 0;
+        });
+    if (rc == 0)
+        *out_n = w;
+    return rc;
 }
 
 template <bool Q>

@@ -452,7 +452,7 @@ def test_command_line_end_to_end(kmm, tmp_path, kind):
     index = rc.genome_index(K)
     pairs = _cli_pairs()
     both, (t1, t2) = rp.interleaved_text(rh.FASTQ, pairs), rp.two_texts(rh.FASTQ, pairs)
-    pack = {"plain": lambda t: t, "bgzf": lambda t: reads_io.bgzf_members(t, block=4001) + reads_io.BGZF_EOF, "gzip": lambda t: gzip.compress(t, 6)}[kind]
+    pack = {"plain": lambda t: t, "bgzf": lambda t: reads_io.bgzf_members(t, block=4001) + reads_io.BGZF_EOF, "gzip": lambda t: gzip.compress(t, 6, mtime=0)}[kind]  # (mtime: the files are compared with a second pack() below)
     ext = ".fq" if kind == "plain" else ".fq.gz"
     paths = {name: str(tmp_path / (name + ext)) for name in ("both", "r1", "r2")}
     for name, text in (("both", both), ("r1", t1), ("r2", t2)):
