@@ -522,8 +522,8 @@ int kmm_read_hits(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_of
  *     remove windows, hits <= windows.
  *   - the calls take the direct records front end and the direct index view at every chunk size — never the radix path, never
  *     the host packer — so an index with "radix_available" 0 is served.
- *   - a record call with "min_base_quality" > 0 is KMM_ERR_INVALID_ARG, nothing mapped: the quality mask lives in the compaction
- *     and the radix front end, and a floor in this mode is deliberately out of scope.  kmm_map_reads, kmm_map_reads_uniform,
+ *   - a record call with "min_base_quality" > 0 is KMM_ERR_INVALID_ARG, nothing mapped: that mask lives in the compaction
+ *     and the radix front end; the mode has a floor of its own, "record_hits_min_base_quality" (below).  kmm_map_reads, kmm_map_reads_uniform,
  *     kmm_map_reads_qual, kmm_map_packed and kmm_map_kmers are KMM_ERR_INVALID_ARG too: flat reads have kmm_read_hits.
  * With the mode off every call runs exactly what it runs without this feature; entries still pending stay takeable.
  * The queue is device memory of the library and grows as needed (before the probe kernel is launched; pending entries are kept).
@@ -535,6 +535,34 @@ int kmm_read_hits(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_of
  * taken — then copies the oldest min(capacity, pending) entries to hits, and to windows when that is non-NULL (entries
  * appended in mode 2 only: windows non-NULL otherwise is KMM_ERR_INVALID_ARG).  hits and windows are uint32 arrays in host or
  * device memory, independently.  *n_taken: the entries copied; they leave the queue, the rest keep their order.
+ *
+ * THE FLOOR OF THE MODE.  "record_hits_min_base_quality" Q, 0 .. 93, default 0 (anything else
+ * KMM_ERR_INVALID_ARG; kmm_set_param / kmm_get_param): the base-quality floor of the record calls WHILE "record_hits" IS 1 OR 2.
+ * No other call reads it; "min_base_quality" keeps its meaning for the node-count routes and stays refused with the mode on,
+ * which is why the mode's floor is a parameter of its own.  With Q = 0 every call launches exactly what it launches without
+ * the parameter.  With Q > 0:
+ *   - FASTQ text (kmm_map_records, kmm_map_bgzf, kmm_map_gzip, kmm_map_record_pairs; interleaved "record_pairs" included): byte i
+ *     of a record's quality line belongs to byte i of its sequence line, counted from the line starts.  A sequence base whose
+ *     quality byte, taken as unsigned, is < 33 + Q is a break exactly as a KMM_LUT_BREAK byte: no window that contains it is
+ *     looked up in either orientation, the windows on either side are, and it counts in neither hits nor windows.  A byte below
+ *     '!' is masked, a byte >= 0x80 is not.  *n_records does not change and the queue keeps one entry per record.  A break table
+ *     combines with the floor (a base is dead if either rule kills it); a 0xFF table entry stays KMM_ERR_INVALID_BASE whatever
+ *     the quality.  A record whose quality line is not as long as its sequence line (the bytes in front of the '\n', without the
+ *     '\r' of a CRLF end) is KMM_ERR_MALFORMED, deferred and sticky as with "min_base_quality"; the message names the raw offset
+ *     of the quality line's '\n' in its piece.
+ *   - THE KEPT TEXT IS NEVER ALTERED: the keep queue, kmm_take_kept_bgzf, both mate queues and the raw BAM form hold exactly the
+ *     bytes they hold without a floor; only which records pass the rule changes.
+ *   - two-line and multi-line FASTA have no qualities: the calls are served and the floor has no effect.
+ *   - kmm_map_bam (plain hits, "record_names" with and without "record_names_pairs", "record_bam", "record_bam_mates") and
+ *     KMM_FORMAT_SAM in the hits mode without keep need "use_record_qual" 1, else KMM_ERR_INVALID_ARG with nothing mapped.  The
+ *     decode's quality variants hand four-line FASTQ to the records call; QUAL is reversed under "original_strand".  A record
+ *     that stores no qualities (BAM: first byte 0xFF; SAM: "*") passes UNMASKED and counts in "records_without_qual", in every
+ *     form — in the named form its text still shows '"' for every base: the decode tells the mark pass which records are exempt.
+ *   - "record_sam" 1 / 2 with Q > 0 is KMM_ERR_INVALID_ARG, nothing mapped (that form's decode reads no QUAL); so is k = 1.
+ *   - "quality_masked_bases" counts the masked sequence bases of the records that count in *n_records.
+ *   - an index with "radix_available" 0 is served; Q may change while entries are pending (an entry keeps its call's floor).
+ * With timing on, the line-start and mark kernels in front of the hit kernel are timed as KMM_KERNEL_RH_QUAL_MARK.  Out of
+ * scope: a floor for flat kmm_read_hits, "record_sam", the host packer.
  */
 int kmm_take_record_hits(kmm_index_t *idx, uint32_t *hits, uint32_t *windows, int64_t capacity, int64_t *n_taken);
 
@@ -593,7 +621,7 @@ int kmm_take_record_hits(kmm_index_t *idx, uint32_t *hits, uint32_t *windows, in
  * A record without bases gives "@NAME\n\n+\n\n".  With "record_names" 0 every call launches the kernels it launched without the
  * parameter.  Refused with KMM_ERR_INVALID_ARG, nothing mapped: kmm_map_bam with "record_names" 1 and "record_hits" 0.  The
  * parameter is not read by any other call: the FASTA / FASTQ routes are unaffected, KMM_FORMAT_SAM with "record_keep" 1 stays
- * refused, and so does a quality floor in the record-hits mode.
+ * refused, and so does "min_base_quality" in the record-hits mode (its own floor, "record_hits_min_base_quality", is served).
  *
  * kmm_take_kept_records synchronises like kmm_take_record_hits — a sticky or deferred device error is returned and nothing is
  * taken.  If capacity is at least the pending bytes, ALL of them are copied to out (host or device memory), *n_bytes and
@@ -793,7 +821,8 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
 #define KMM_KERNEL_BAM_RAW 9      /* "record_bam": record base, count, scans, copy and advance of the kept BAM records */
 #define KMM_KERNEL_BAM_RAW_MATES 10 /* "record_bam_mates": the pair forms of the above, the mate check and the carried mate 1 */
 #define KMM_KERNEL_SAM_RAW 11     /* "record_sam": the tiles' scan, flags, block scan, copy and advance of the kept SAM lines */
-#define KMM_N_KERNELS 12
+#define KMM_KERNEL_RH_QUAL_MARK 12 /* "record_hits_min_base_quality": line starts and the mark pass in front of the hit kernel */
+#define KMM_N_KERNELS 13
 int kmm_set_timing(kmm_index_t *idx, int enabled);
 /* Work done by the map calls of this handle since creation (or the last call with reset != 0):
  * k-mer lookups performed (windows, doubled with also_revcomp) and count increments (index hits that

@@ -199,7 +199,8 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     selection, and no call that sets one.
     record_hits: RecordHitsSink or None — the handle's record-hits mode is switched on before the first map call, and the sink
     takes the pending entries after every map call, on every route (the queue stays chunk-sized); the node counts returned are
-    then all zero."""
+    then all zero; min_base_quality is then the MODE's floor ("record_hits_min_base_quality"), which the sink sets
+    with the mode: "min_base_quality" with the mode on is refused by the library."""
     _check_bam_route(fmt, world_size, exclude_flags, shard_bam=shard_bam)
     record_select = check_record_select(fmt, **(record_select or {}))
     original_strand = check_original_strand(original_strand, fmt)
@@ -248,8 +249,10 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
     # the raw bytes cross PCIe and the GPU parses them
     n_host = host_threads(n_threads, world_size)
     dev.set_param("host_pack_threads", n_host if n_threads > 1 else 0)
-    if min_base_quality:
+    if min_base_quality and record_hits is None:
         dev.set_param("min_base_quality", min_base_quality)
+    if record_hits is not None:
+        record_hits.min_base_quality = min_base_quality      # (the checked floor: 0 for FASTA)
     if use_record_qual:
         dev.set_param("use_record_qual", 1)
     if original_strand:
@@ -825,12 +828,13 @@ class RecordHitsSink:
     open(dev) switches the mode on, drain(dev) takes what is pending after a map call; result() is the whole file's (hits,
     windows), in file order."""
 
-    def __init__(self, windows=True):
+    def __init__(self, windows=True, min_base_quality=0):
         self.windows = bool(windows)
+        self.min_base_quality = int(min_base_quality or 0)   # the mode's floor (DESIGN 4.27), set with the mode
         self.hits, self.wins = [], []
 
     def open(self, dev):
-        dev.record_hits(True, windows=self.windows)
+        dev.record_hits(True, windows=self.windows, **({"min_base_quality": self.min_base_quality} if self.min_base_quality else {}))
 
     def drain(self, dev):
         if dev.get_param("record_hits_pending"):
@@ -870,6 +874,11 @@ def read_hits_file(args):
     k = args.kmer_size
     world = int(os.environ.get("WORLD_SIZE", "1"))
     device_parser = bool(getattr(args, "device_parser", False))
+    if int(getattr(args, "min_base_quality", 0) or 0) and not device_parser:
+        # (the floor lives in the library's record-hits mode, DESIGN 4.27: flat reads carry no qualities to kmm_read_hits)
+        logging.info("read-hits: --min-base-quality implies --device-parser: the qualities are read where the records are parsed, "
+                     "on the GPU")
+        device_parser = True
     selection = [opt for opt, name in _READ_HITS_SELECTION if getattr(args, name, None)]
     probe = probe_input(args.reads)
     check_read_hits_input(probe.fmt, world, device_parser, selection)
@@ -914,6 +923,9 @@ def read_hits_file_device(args, probe):
                                  regions_file=args.regions_file)
     original_strand = check_original_strand(bool(args.original_strand), fmt)
     _check_bam_route(fmt, 1, int(args.exclude_flags or 0))
+    # (the checks of `map`, before the index is read: k >= 2, SAM / BAM with --use-record-qual, FASTA warned about and served)
+    use_qual = check_use_record_qual(bool(getattr(args, "use_record_qual", False)), fmt, getattr(args, "min_base_quality", 0))
+    min_q = check_min_base_quality(getattr(args, "min_base_quality", 0), k, fmt, use_record_qual=use_qual)
     lut = None
     if args.ambiguous_bases == "skip":
         from .util import ambiguous_skip_lut
@@ -927,7 +939,8 @@ def read_hits_file_device(args, probe):
     logging.info("read-hits: records parsed on the GPU, record-hits mode (--device-parser)")
     map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
                 device=args.device, n_threads=16, exclude_flags=int(args.exclude_flags or 0), probe=probe, lut=lut,
-                original_strand=original_strand, record_hits=sink, **({"record_select": select} if select else {}))
+                original_strand=original_strand, record_hits=sink, min_base_quality=min_q, use_record_qual=use_qual,
+                **({"record_select": select} if select else {}))
     hits, wins = sink.result()
     return _save_read_hits(args, hits, wins)
 
@@ -952,8 +965,9 @@ class RecordKeepSink(RecordHitsSink):
     BGZF members — every drain ends its last member; close() writes the end-of-file block; kept_bytes still counts text."""
 
     def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False, pairs=False, pair_rule="any",
-                 out2=None, bgzf=False, bam_pairs=False, bam_out=False, bam_mates=False, sam_out=False, sam_header=True):
-        super().__init__(windows=True)
+                 out2=None, bgzf=False, bam_pairs=False, bam_out=False, bam_mates=False, sam_out=False, sam_header=True,
+                 min_base_quality=0):
+        super().__init__(windows=True, min_base_quality=min_base_quality)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
         self.seen = self.kept = self.kept_bytes = 0
@@ -1274,6 +1288,14 @@ def select_reads_file(args):
     bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None) and not sam_out]
     check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options,
                              bam_out, sam_out)
+    # (the floor of the record-hits mode, DESIGN 4.27, under the checks of `map`, before the index is read: k >= 2, BAM with
+    # --use-record-qual, FASTA warned about and served; SAM lines kept as SAM lines are mapped without their QUAL column)
+    if sam_out and int(getattr(args, "min_base_quality", 0) or 0):
+        raise ValueError("select-reads: --sam-out does not go with --min-base-quality: SAM lines kept as SAM lines are mapped without "
+                         "their QUAL column (a BAM file has --bam-to-fastq and --bam-out with --use-record-qual)")
+    use_qual = check_use_record_qual(bool(getattr(args, "use_record_qual", False)), probe.fmt, getattr(args, "min_base_quality", 0))
+    min_q = check_min_base_quality(getattr(args, "min_base_quality", 0), k, probe.fmt, use_record_qual=use_qual)
+    more_floor = dict(min_base_quality=min_q, use_record_qual=use_qual) if min_q else {}
     if not 0 <= args.min_hit_permille <= 1000:
         raise ValueError("--min-hit-permille outside [0, 1000]")
     if args.min_hits < 0:
@@ -1329,7 +1351,7 @@ def select_reads_file(args):
         logging.info("select-reads: -f and -f2 are read in step by the host readers (two compressed streams are not inflated on the "
                      "GPU in step); mates are kept together, pair rule '%s'", pair_rule or "any")
         with open(args.output_file, "wb") as out, open(output2, "wb") as out2:
-            sink = RecordKeepSink(out, pair_rule=pair_rule or "any", out2=out2, **rule)
+            sink = RecordKeepSink(out, pair_rule=pair_rule or "any", out2=out2, min_base_quality=min_q, **rule)
             select_read_pairs_files(kmer_index, args.reads, reads2, args.chunk_size, fmt, k, sink, bool(args.map_reverse_complements),
                                     args.max_hits_per_kmer, device=args.device, lut=lut)
             sink.close()
@@ -1341,7 +1363,8 @@ def select_reads_file(args):
                                   **({"sam_out": True, "sam_header": not getattr(args, "no_header", False)} if sam_out else {}), **rule)
             try:
                 map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
-                            device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more)
+                            device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more,
+                            **more_floor)
             except ValueError as exc:
                 if keep_mates and ("are not mates" in str(exc) or "unpaired record" in str(exc)):
                     # (a BAM file that stops in the middle looks like one that does not — -o is removed)
@@ -1486,6 +1509,13 @@ def build_argument_parser():
     sub.add_argument("--original-strand", action="store_true",
                      help="With --device-parser, SAM and BAM input only: records whose FLAG has 0x10 are looked up in read "
                           "orientation.")
+    sub.add_argument("--min-base-quality", default=argparse.SUPPRESS, type=int, metavar="Q",
+                     help="FASTQ input (SAM / BAM with --use-record-qual): a base whose Phred+33 quality is below Q (0 .. 93) is a "
+                          "break: no k-mer over it is looked up, and it counts in neither hits nor windows. Implies --device-parser. "
+                          "FASTA has no qualities (a warning). Needs -k 2 or more. Default 0: off.")
+    sub.add_argument("--use-record-qual", action="store_true", default=argparse.SUPPRESS,
+                     help="SAM and BAM input only, with --min-base-quality: decode every record's QUAL on the GPU and apply the "
+                          "floor to it. Records that store no qualities pass unmasked and are counted in the log.")
     sub.set_defaults(func=read_hits_file)
 
     sub = subparsers.add_parser("select-reads", help="Extension: write the reads whose k-mers hit a kmer index back out")
@@ -1576,6 +1606,14 @@ def build_argument_parser():
     sub.add_argument("--bgzf", action="store_true", default=argparse.SUPPRESS,
                      help="Write -o (and -o2) as BGZF files: the kept text is deflated on the GPU, one member per 65280 bytes, and "
                           "only the members are copied to the host. Without it the output is plain text, whatever -o is called.")
+    sub.add_argument("--min-base-quality", default=argparse.SUPPRESS, type=int, metavar="Q",
+                     help="FASTQ input (BAM with --use-record-qual): a base whose Phred+33 quality is below Q (0 .. 93) is a break "
+                          "for the keep rule: no k-mer over it is looked up, and it counts in neither hits nor windows. The reads "
+                          "are written as they stand. FASTA has no qualities (a warning). Needs -k 2 or more; does not go with "
+                          "--sam-out. Default 0: off.")
+    sub.add_argument("--use-record-qual", action="store_true", default=argparse.SUPPRESS,
+                     help="BAM input only, with --min-base-quality: apply the floor to every record's QUAL, decoded on the GPU. "
+                          "Records that store no qualities pass unmasked and are counted in the log.")
     sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
     sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
     sub.set_defaults(func=select_reads_file)

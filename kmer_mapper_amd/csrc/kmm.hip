@@ -92,6 +92,7 @@ static double ms_since(std::chrono::steady_clock::time_point a)
 #include "kmm_records.hpp"
 #include "kmm_kernels.hpp"
 #include "kmm_read_hits.hpp"
+#include "kmm_rh_qual.hpp"
 #include "kmm_record_keep.hpp"
 #include "kmm_radix.hpp"
 #include "kmm_build.hpp"
@@ -420,6 +421,15 @@ struct kmm_index : IndexStreams, RxArrays {
     int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
     int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
     int min_base_quality = 0;    // "min_base_quality": > 0: a FASTQ base whose quality byte is below 33 + this is a break (flat reads: 4.11)
+    // "record_hits_min_base_quality": the floor of the record calls while "record_hits" is 1 or 2 — a parameter of
+    // its own: "min_base_quality" with the mode on stays refused.  rq_exempt / rq_text_off: set around the inner records call of
+    // kmm_map_bam's named form — the records that pass unmasked (no stored qualities), by the offset of their quality line in
+    // the inner call's text, and where the piece at work starts in that text.  bam_mate_exempt: the flags of the waiting mate 1.
+    int rh_min_base_quality = 0;
+    const uint32_t *rq_exempt = nullptr;
+    int64_t rq_text_off = 0;
+    DevBuf rq_exempt_buf, bam_mate_exempt;
+    int64_t bam_mate_exempt_len = 0; // the bytes of waiting text that bam_mate_exempt holds flags for (0: none)
     int use_record_qual = 0;     // "use_record_qual": 1: with a floor set, SAM / BAM records are mapped with their QUAL
     int original_strand = 0;     // "original_strand": 1: kept SAM / BAM records with FLAG 0x10 are mapped in read orientation
     int64_t dbg_rec_piece_kb = 0; // test hook ("debug_records_piece_kb"): bytes per piece of kmm_map_records, KiB (0: 2^30 bytes)
@@ -609,7 +619,9 @@ int drain(kmm_index *ix)
                       "does not start with '@' / '+' / '>'%s): multi-line FASTA/FASTQ is not supported by "
                       "the GPU reader%s", bad[1],
                       ix->min_base_quality > 0 ? ", or a quality line that ends there is not as long as its sequence line "
-                                                 "(checked with min_base_quality set)" : "", where);
+                                                 "(checked with min_base_quality set)"
+                      : ix->rh_min_base_quality > 0 ? ", or a quality line that ends there is not as long as its sequence line "
+                                                      "(checked with record_hits_min_base_quality set)" : "", where);
         else
             rc = fail(KMM_ERR_INVALID_BASE,
                       "read byte at offset %llu of a mapped chunk is not a nucleotide under the "
@@ -1110,8 +1122,9 @@ int refuse_in_record_hits(const kmm_index *ix, const char *who)
     return KMM_OK;
 }
 
-// A record call while the mode is on and a quality floor is set: refused, nothing mapped (the quality mask lives in the
-// compaction and the radix front end, which the mode never takes).
+// A record call while the mode is on and "min_base_quality" is set: refused, nothing mapped (that mask lives in the
+// compaction and the radix front end, which the mode never takes; the mode's own floor is "record_hits_min_base_quality",
+// call_floor).
 int refuse_quality_in_record_hits(const kmm_index *ix, const char *who)
 {
     if (ix && ix->record_hits && ix->min_base_quality > 0)
@@ -1160,6 +1173,17 @@ int refuse_record_sam(const kmm_index *ix, const char *who)
     if (ix->record_pairs)
         return fail(KMM_ERR_INVALID_ARG, "%s: \"record_sam\" is %d and \"record_pairs\" is 1: mates are not kept together in SAM output; "
                     "set one of them to 0 (nothing is mapped)", who, ix->record_sam);
+    return KMM_OK;
+}
+
+// "record_sam" under the floor of the record-hits mode: refused, nothing mapped — the span-leaving decode of that
+// form has no quality variant, so there are no quality lines for the mark pass to read.
+int refuse_floor_with_record_sam(const kmm_index *ix, const char *who)
+{
+    if (ix->record_hits && ix->rh_min_base_quality > 0)
+        return fail(KMM_ERR_INVALID_ARG, "%s: \"record_sam\" is %d and record_hits_min_base_quality is %d: SAM lines kept as SAM lines are "
+                    "mapped without their QUAL column; set the floor to 0, or \"record_sam\" to 0 (nothing is mapped)", who,
+                    ix->record_sam, ix->rh_min_base_quality);
     return KMM_OK;
 }
 
@@ -2509,18 +2533,28 @@ static int64_t records_piece_max(const kmm_index_t *ix)
     return ix->dbg_rec_piece_kb > 0 ? ix->dbg_rec_piece_kb << 10 : (int64_t)1 << 30;
 }
 
-// The quality floor that applies to records of this format: "min_base_quality" for FASTQ, none for the formats without
-// quality lines.
-static int records_quality(const kmm_index_t *ix, int format)
+// The quality floor of a record call, by mode: "record_hits_min_base_quality" while "record_hits" is 1 or 2 (where
+// "min_base_quality" > 0 is refused), else "min_base_quality".
+static int call_floor(const kmm_index_t *ix)
 {
-    return format == KMM_FORMAT_FASTQ ? ix->min_base_quality : 0;
+    return ix->record_hits ? ix->rh_min_base_quality : ix->min_base_quality;
+}
+static const char *call_floor_name(const kmm_index_t *ix)
+{
+    return ix->record_hits ? "record_hits_min_base_quality" : "min_base_quality";
 }
 
-// The quality floor that applies to SAM / BAM records: "min_base_quality" once "use_record_qual" is set (the decoders then
+// The quality floor that applies to records of this format: the call's for FASTQ, none for the formats without quality lines.
+static int records_quality(const kmm_index_t *ix, int format)
+{
+    return format == KMM_FORMAT_FASTQ ? call_floor(ix) : 0;
+}
+
+// The quality floor that applies to SAM / BAM records: the call's once "use_record_qual" is set (the decoders then
 // write four-line FASTQ), else none — QUAL is not read at all, not even its length.
 static int record_quality(const kmm_index_t *ix)
 {
-    return ix->use_record_qual ? ix->min_base_quality : 0;
+    return ix->use_record_qual ? call_floor(ix) : 0;
 }
 
 // "min_base_quality" > 0 and what it cannot go with: k = 1 (the masked base's own window could not be killed: check_k_lut)
@@ -2528,19 +2562,22 @@ static int record_quality(const kmm_index_t *ix)
 // "use_record_qual" asks for their quality variants — whose FASTQ text is mapped by the radix path alone.
 static int check_quality(const kmm_index_t *ix, const char *who, int k, bool sam)
 {
-    if (ix->min_base_quality <= 0)
+    const int q = call_floor(ix);
+    const char *name = call_floor_name(ix);
+    if (q <= 0)
         return KMM_OK;
     if (sam && !ix->use_record_qual)
-        return fail(KMM_ERR_INVALID_ARG, "%s: min_base_quality %d is set, and SAM / BAM records are mapped without their QUAL "
+        return fail(KMM_ERR_INVALID_ARG, "%s: %s %d is set, and SAM / BAM records are mapped without their QUAL "
                     "column: set it to 0 for this input, or set \"use_record_qual\" to 1 (records that store no qualities then "
-                    "pass the floor unmasked: \"records_without_qual\")", who, ix->min_base_quality);
-    if (sam && !ix->rx_ok)
+                    "pass the floor unmasked: \"records_without_qual\")", who, name, q);
+    // (the record-hits mode marks the low bases in front of the direct front end, kmm_rh_qual.hpp: no radix path, no compaction)
+    if (sam && !ix->record_hits && !ix->rx_ok)
         return fail(KMM_ERR_INVALID_ARG, "%s: min_base_quality needs the radix path, which is not available for this "
                     "index (kmm_get_param \"radix_unavailable_reason\")", who);
-    if (sam && ix->dbg_rec_skip)
+    if (sam && !ix->record_hits && ix->dbg_rec_skip)
         return fail(KMM_ERR_INVALID_ARG, "%s: min_base_quality does not go with debug_records_skip", who);
     if (k == 1)
-        return fail(KMM_ERR_INVALID_ARG, "%s: k = 1 with min_base_quality %d: needs k >= 2", who, ix->min_base_quality);
+        return fail(KMM_ERR_INVALID_ARG, "%s: k = 1 with %s %d: needs k >= 2", who, name, q);
     return KMM_OK;
 }
 
@@ -2776,6 +2813,44 @@ static int map_records_radix_call(kmm_index_t *ix, const uint8_t *raw, int64_t n
     return stage_release(ix, s, false);
 }
 
+// The floor of the record-hits mode on one FASTQ piece (kmm_rh_qual.hpp), between the census and the hit kernel:
+// rv as the hit kernel takes it (total: the end of the piece's last complete record; the census arrays).  The bitset of the
+// low bases (one bit per raw byte, the halo of the last tile included) lies in the stage's start_bits, the line starts of the
+// piece's n_records records in its aux: neither is used by the direct records route.  Sets rv.dead; no host round trip.
+static int rq_mark_piece(kmm_index_t *ix, Stage &s, ReadsView &rv, int64_t n_records, int qual)
+{
+    const uint32_t n_tiles = (uint32_t)((rv.total + 1023) / 1024), n_lines = (uint32_t)(4 * n_records); // (a piece: at most 2^30 bytes)
+    const size_t dead_bytes = (size_t)n_tiles * 128 + 64;
+    KMMCHK(ensure(s.start_bits, dead_bytes));
+    KMMCHK(ensure(s.aux, (size_t)n_lines * 4 + 64));
+    ScopedTimer tm;
+    KMMCHK(tm.begin(ix, KMM_KERNEL_RH_QUAL_MARK));
+    HIPCHK(hipMemsetAsync(s.start_bits.p, 0, dead_bytes, ix->stream));
+    const dim3 grid((n_tiles + 3) / 4);
+    hipLaunchKernelGGL(k_rq_line_starts, grid, dim3(256), 0, ix->stream, rv.bases, (uint32_t)rv.total, n_tiles, rv.tile_nl, rv.super_nl,
+                       n_lines, (uint32_t *)s.aux.p);
+    hipLaunchKernelGGL(k_rq_mark, grid, dim3(256), 0, ix->stream, rv.bases, (uint32_t)rv.total, n_tiles, rv.tile_nl, rv.super_nl, n_lines,
+                       (const uint32_t *)s.aux.p, 33u + (uint32_t)qual, ix->rq_exempt, (uint64_t)ix->rq_text_off, (uint32_t *)s.start_bits.p,
+                       ix->first_bad, ix->stats);
+    HIPCHK(hipGetLastError());
+    KMMCHK(tm.end());
+    rv.dead = (const uint32_t *)s.start_bits.p;
+    return KMM_OK;
+}
+
+// The hit kernel of a piece of records: the variant for the table (a break entry) and the floor (rv.dead set: rq_mark_piece).
+static int launch_record_hits(kmm_index_t *ix, const ReadsView &rv, bool has_break, int k, int max_freq, int also_rc, uint32_t *hits,
+                              uint32_t *windows)
+{
+    if (rv.dead && has_break)
+        return launch_read_hits<MODE_RECORDS_BRK_QUAL>(ix, rv, k, max_freq, also_rc, nullptr, hits, windows);
+    if (rv.dead)
+        return launch_read_hits<MODE_RECORDS_QUAL>(ix, rv, k, max_freq, also_rc, nullptr, hits, windows);
+    if (has_break)
+        return launch_read_hits<MODE_RECORDS_BRK>(ix, rv, k, max_freq, also_rc, nullptr, hits, windows);
+    return launch_read_hits<MODE_RECORDS>(ix, rv, k, max_freq, also_rc, nullptr, hits, windows);
+}
+
 // One piece of at most 2^30 bytes (the newline census is a two-level scan over 1024 x 1024 tiles of 1024 bytes).
 static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int format, int k,
                              int max_freq, int also_revcomp, const uint8_t *lut, int64_t *consumed,
@@ -2839,10 +2914,9 @@ static int map_records_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
             KMMCHK(rhq_reserve(ix, out[1], &q_hits, &q_win, pairs));
             if (ix->record_hits != 2)
                 q_win = nullptr;
-            if (has_break)
-                KMMCHK(launch_read_hits<MODE_RECORDS_BRK>(ix, rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, q_hits, q_win));
-            else
-                KMMCHK(launch_read_hits<MODE_RECORDS>(ix, rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, q_hits, q_win));
+            if (const int qual = records_quality(ix, format))
+                KMMCHK(rq_mark_piece(ix, s, rv, out[1], qual));
+            KMMCHK(launch_record_hits(ix, rv, has_break, k, max_freq, also_revcomp ? 1 : 0, q_hits, q_win));
             ix->rhq_pending += out[1];
             if (pairs && ix->rk_raw_call) // ("record_bam_mates", DESIGN 4.25: whole pairs of entries; the bytes and the mate check are
                 ix->bam_pairs_done += out[1] / 2; // kmm_map_bam's, over the records themselves — this text has no names)
@@ -2984,12 +3058,12 @@ static int selection_of(const kmm_index_t *ix, const char *who, bool by_name, in
     return KMM_OK;
 }
 
+static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int format, int k, int max_freq, int also_revcomp,
+                             const uint8_t *lut, int64_t *consumed, int64_t *n_records);
+
 namespace {
 #include "kmm_sam_host.hpp" // map_sam_piece, sam_raw_piece: behind the stages and map_records_piece, in front of kmm_map_records
 } // namespace
-
-static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int format, int k, int max_freq, int also_revcomp,
-                             const uint8_t *lut, int64_t *consumed, int64_t *n_records);
 
 int kmm_map_records(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int format, int k,
                     int max_freq, int also_revcomp, const uint8_t *lut, int64_t *consumed,
@@ -3043,13 +3117,16 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     const bool sam_lines = format == KMM_FORMAT_SAM && ix->record_sam != 0; // ("record_sam", DESIGN 4.26: read by SAM calls alone)
     if (sam_lines)
         KMMCHK(refuse_record_sam(ix, "kmm_map_records"));
+    if (sam_lines)
+        KMMCHK(refuse_floor_with_record_sam(ix, "kmm_map_records"));
     KMMCHK(refuse_record_keep(ix, "kmm_map_records", format == KMM_FORMAT_SAM, sam_lines, format == KMM_FORMAT_FASTA));
     KMMCHK(check_quality(ix, "kmm_map_records", k, format == KMM_FORMAT_SAM));
     // A quality floor on FASTQ: always compaction + the radix path, whatever the batch size and "path" say (as kmm_map_packed) —
     // the records front end of the direct path has no flat positions to put a quality mark on — and never the host packer,
     // whose parser skips the quality lines.
     // (SAM with "use_record_qual" comes back here as FASTQ text, piece by piece: map_sam_piece)
-    if (records_quality(ix, format) > 0) {
+    // (the record-hits mode keeps the direct front end under its own floor: rq_mark_piece)
+    if (!ix->record_hits && records_quality(ix, format) > 0) {
         if (!ix->rx_ok)
             return fail(KMM_ERR_INVALID_ARG, "kmm_map_records: min_base_quality needs the radix path, which is not available for this "
                         "index (kmm_get_param \"radix_unavailable_reason\")");
@@ -3094,8 +3171,10 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         else if (format == KMM_FORMAT_FASTA)
             KMMCHK(map_multiline_piece(ix, raw + off, len, last_chunk && off + len == n_bytes, k, max_freq, also_revcomp, lut,
                                        &used, &nr));
-        else
+        else {
+            ix->rq_text_off = off; // (read by rq_mark_piece while kmm_map_bam's named form has set rq_exempt)
             KMMCHK(map_records_piece(ix, raw + off, len, format, k, max_freq, also_revcomp, lut, &used, &nr));
+        }
         // a multi-line FASTA record that fills a whole piece: no later piece, no longer chunk and no further call can ever
         // complete it, and with KMM_FORMAT_LAST_CHUNK the rest of the file would be dropped behind a KMM_OK
         if (format == KMM_FORMAT_FASTA && used == 0 && len == piece_max)
@@ -3213,10 +3292,9 @@ static int map_record_pairs_piece(kmm_index_t *ix, const uint8_t *raw1, int64_t 
             p.rv.period_mask = (uint32_t)format - 1u;
             p.rv.header_char = format == KMM_FORMAT_FASTQ ? (uint32_t)'@' : (uint32_t)'>';
             uint32_t *h = e + (size_t)i * stride, *w = q_win ? e + (size_t)(2 + i) * stride : nullptr;
-            if (has_break)
-                KMMCHK(launch_read_hits<MODE_RECORDS_BRK>(ix, p.rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, h, w));
-            else
-                KMMCHK(launch_read_hits<MODE_RECORDS>(ix, p.rv, k, max_freq, also_revcomp ? 1 : 0, nullptr, h, w));
+            if (const int qual = records_quality(ix, format))
+                KMMCHK(rq_mark_piece(ix, *p.s, p.rv, m, qual));
+            KMMCHK(launch_record_hits(ix, p.rv, has_break, k, max_freq, also_revcomp ? 1 : 0, h, w));
         }
         const dim3 gz((unsigned)grid_for(ix, (m + 255) / 256, 8));
         hipLaunchKernelGGL(k_rk_zip, gz, dim3(256), 0, ix->stream, (const uint32_t *)e, (const uint32_t *)(e + stride), m, q_hits);
@@ -3576,6 +3654,8 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
     const bool sam_lines = text && c.fmt == KMM_FORMAT_SAM && ix->record_sam != 0;
     if (sam_lines)
         KMMCHK(refuse_record_sam(ix, c.who));
+    if (sam_lines)
+        KMMCHK(refuse_floor_with_record_sam(ix, c.who));
     KMMCHK(refuse_record_keep(ix, c.who, !text || c.fmt == KMM_FORMAT_SAM,
                               sam_lines || (!text && (ix->record_names != 0 || ix->record_bam != 0))));
     KMMCHK(check_quality(ix, c.who, c.k, !text || c.fmt == KMM_FORMAT_SAM));
@@ -5128,6 +5208,12 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
         if (value < 0 || value > 93)
             return fail(KMM_ERR_INVALID_ARG, "min_base_quality outside [0, 93]");
         ix->min_base_quality = (int)value;
+    } else if (!strcmp(name, "record_hits_min_base_quality")) {
+        // the floor of the record calls while "record_hits" is 1 or 2; no other call reads it.  Entries may be
+        // pending: an entry holds what its record had under the floor of its own call
+        if (value < 0 || value > 93)
+            return fail(KMM_ERR_INVALID_ARG, "record_hits_min_base_quality outside [0, 93]");
+        ix->rh_min_base_quality = (int)value;
     } else if (!strcmp(name, "record_hits")) {
         // 1 / 2: the record calls append per-record index hits (2: and windows) to the handle's queue instead of counting
         // nodes (kmm_take_record_hits); 0: off, entries still pending stay takeable
@@ -5319,6 +5405,8 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->dbg_gzip_chunk_kb;
     else if (!strcmp(name, "min_base_quality"))
         *value = ix->min_base_quality;
+    else if (!strcmp(name, "record_hits_min_base_quality"))
+        *value = ix->rh_min_base_quality;
     else if (!strcmp(name, "use_record_qual"))
         *value = ix->use_record_qual;
     else if (!strcmp(name, "original_strand"))

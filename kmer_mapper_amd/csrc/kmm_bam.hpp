@@ -1535,11 +1535,15 @@ __global__ void __launch_bounds__(256) k_bam_decode_q_rev_sel(const uint8_t *__r
 // kernel for every combination.  64 lanes over a kept record's name bytes, then over its bases; byte stores into disjoint
 // ranges.  Per tile: the kept records without qualities, the flipped ones and the replaced name bytes (the lanes' shares summed
 // over the wavefront), each added with one atomic per tile that has any.
+// exempt (null: none): a bitset over the bytes of the text that `out` is part of, out[0] at its byte exempt_base,
+// zeroed by the caller — the bit of a kept record's first quality byte is set when the record stores no qualities: its '"'
+// letters are below every floor of 2 or more, and the mark pass of the record-hits mode lets such a record pass unmasked.
 __global__ void __launch_bounds__(256) k_bam_decode_named(const uint8_t *__restrict__ d, uint64_t n, uint64_t n_tiles, int32_t n_ref, Sel sel,
                                                           uint32_t orig, uint32_t sfx, const Tile *__restrict__ in,
                                                           const unsigned long long *__restrict__ base, uint8_t *__restrict__ out,
                                                           unsigned long long *__restrict__ no_qual, unsigned long long *__restrict__ reversed,
-                                                          unsigned long long *__restrict__ replaced)
+                                                          unsigned long long *__restrict__ replaced, uint32_t *__restrict__ exempt,
+                                                          uint64_t exempt_base)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
@@ -1561,6 +1565,10 @@ __global__ void __launch_bounds__(256) k_bam_decode_named(const uint8_t *__restr
                 const bool rev = flipped(h, orig != 0u);
                 repl += rev ? decode_record_named_rev(d + p, h, out + o, lane, 64u, sfx != 0u)
                             : decode_record_named(d + p, h, out + o, lane, 64u, sfx != 0u);
+                if (exempt && lane == 0 && qual_absent(d + p, h)) { // (the quality line: the record's last l_seq bytes and a '\n')
+                    const uint64_t q = exempt_base + o + len - 1u - h.l_seq;
+                    atomicOr(&exempt[q >> 5], 1u << (q & 31u));
+                }
                 o += len;
                 absent += qual_absent(d + p, h) ? 1u : 0u;
                 flips += rev ? 1u : 0u;

@@ -19,6 +19,8 @@ struct BamGpuBackend {
     int cur = 0;
     bool named = false; // the named form ("record_names"): the k_bam_*_named kernels run, whatever the selection
     bool sfx = false;   // ... with "/1" / "/2" behind the name
+    uint32_t *exempt = nullptr; // the named form under a floor: decode flags the records without qualities here, the
+    uint64_t exempt_base = 0;   // bit of their quality line's offset in the inner call's text, which decode's `out` starts at this byte of
 
     kmm_bam::Tile *tiles(int i) { return (kmm_bam::Tile *)ix->bam_tiles[i].p; }
     kmm_bam::Ctl *ctl() { return (kmm_bam::Ctl *)ix->bam_ctl.p; }
@@ -97,7 +99,7 @@ struct BamGpuBackend {
         if (named)
             hipLaunchKernelGGL(kmm_bam::k_bam_decode_named, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel,
                                orig ? 1u : 0u, sfx ? 1u : 0u, tl, bs, out, ix->stats + KMM_STAT_REC_NO_QUAL,
-                               ix->stats + KMM_STAT_REC_REVERSED, ix->stats + KMM_STAT_REC_NAME_REPLACED);
+                               ix->stats + KMM_STAT_REC_REVERSED, ix->stats + KMM_STAT_REC_NAME_REPLACED, exempt, exempt_base);
         else if (selected && qual && orig)
             hipLaunchKernelGGL(kmm_bam::k_bam_decode_q_rev_sel, wave_grid(n_tiles), dim3(256), 0, ix->stream, d, n, n_tiles, n_ref, sel, tl, bs,
                                out, ix->stats + KMM_STAT_REC_NO_QUAL, ix->stats + KMM_STAT_REC_REVERSED);
@@ -124,6 +126,29 @@ struct BamGpuBackend {
         return KMM_OK;
     }
 };
+
+// The named form under the floor of the record-hits mode, in front of decode: the handle's exemption bitset over
+// the n_text bytes of the inner records call's text, zeroed, the flags of the waiting mate 1's `carry` bytes at its start; decode
+// then writes behind them.  Any other form: nothing.  While the guard lives, the mark pass of the inner call reads the bitset.
+struct RqExemptCall {
+    kmm_index_t *ix;
+    ~RqExemptCall() { ix->rq_exempt = nullptr, ix->rq_text_off = 0; }
+};
+
+int bam_exempt_begin(kmm_index_t *ix, BamGpuBackend &be, int64_t n_text, int64_t carry)
+{
+    if (!be.named || !be.qual)
+        return KMM_OK;
+    const size_t bytes = ((size_t)n_text / 32 + 2) * 4, carried = ((size_t)carry + 31) / 32 * 4;
+    KMMCHK(ensure(ix->rq_exempt_buf, bytes));
+    HIPCHK(hipMemsetAsync(ix->rq_exempt_buf.p, 0, bytes, ix->stream));
+    if (carry > 0 && ix->bam_mate_exempt_len == carry)
+        HIPCHK(hipMemcpyAsync(ix->rq_exempt_buf.p, ix->bam_mate_exempt.p, carried, hipMemcpyDeviceToDevice, ix->stream));
+    be.exempt = (uint32_t *)ix->rq_exempt_buf.p;
+    be.exempt_base = (uint64_t)carry;
+    ix->rq_exempt = be.exempt;
+    return KMM_OK;
+}
 
 // "The stream ends with an unpaired record" (DESIGN 4.23): a mate 1 is left when the stream's last call has nothing more for it.
 // param: the parameter that pairs the records, "record_names_pairs" or "record_bam_mates" (4.25).
@@ -182,6 +207,8 @@ int bam_mates_front(kmm_index_t *ix, const StreamCall &c, BamGpuBackend &be, con
     HIPCHK(hipMemcpyAsync(undo.d_counters, ix->stats + KMM_STAT_REC_NO_QUAL, 24, hipMemcpyDeviceToDevice, ix->stream));
     if (carry > 0)
         HIPCHK(hipMemcpyAsync(ix->bam_out.p, ix->bam_mate.p, (size_t)carry, hipMemcpyDeviceToDevice, ix->stream));
+    const RqExemptCall exempting{ix};
+    KMMCHK(bam_exempt_begin(ix, be, n_text, carry));
     KMMCHK(be.decode(((uint64_t)n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p + carry));
     if (n_rec >= 2) {
         const RkCallMode mode(ix, true, raw);
@@ -213,9 +240,17 @@ int bam_map_mates(kmm_index_t *ix, const StreamCall &c, BamGpuBackend &be, const
     if (decoded && left > 0) {
         KMMCHK(ensure(ix->bam_mate, (size_t)left + 64)); // (may free and reallocate: a device-wide sync, rare)
         HIPCHK(hipMemcpyAsync(ix->bam_mate.p, (const uint8_t *)ix->bam_out.p + taken, (size_t)left, hipMemcpyDeviceToDevice, ix->stream));
+        if (be.exempt) { // (the waiting mate's exemption flag goes with its text)
+            KMMCHK(ensure(ix->bam_mate_exempt, ((size_t)left + 31) / 32 * 4 + 64));
+            hipLaunchKernelGGL(k_rq_bits_move, dim3((unsigned)grid_for(ix, (left / 32 + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                               (const uint32_t *)be.exempt, (uint64_t)taken, (uint64_t)left, (uint32_t *)ix->bam_mate_exempt.p);
+            HIPCHK(hipGetLastError());
+        }
     }
-    if (decoded)
+    if (decoded) {
         ix->bam_mate_len = left;
+        ix->bam_mate_exempt_len = be.exempt ? left : 0;
+    }
     if (c.n_records)
         *c.n_records = recs;
     return KMM_OK;
@@ -458,8 +493,8 @@ int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw, int64
     BamGpuBackend be{ix, d_raw, (uint64_t)n_raw, ix->bam_n_ref, ix->bam_excl, qual, ix->original_strand != 0};
     KMMCHK(selection_of(ix, "kmm_map_bam", false, ix->bam_n_ref, be.sel));
     be.selected = !be.sel.flags_only();
-    // (the named form: stream_call_start let the call through with "record_hits" on; a quality floor is refused in that mode, so
-    // `qual` is false here and the text goes to the records front end as FASTQ all the same)
+    // (the named form: its text goes to the records front end as FASTQ whatever `qual` says; under the floor of the record-hits
+    // mode — `qual` — decode also flags the records without qualities for the mark pass)
     be.named = ix->record_names != 0;
     be.sfx = ix->record_names_mate_suffix != 0;
     kmm_bam::CallOut co;
@@ -488,6 +523,8 @@ int bam_map_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_raw, int64
     if (co.recs == 0)
         return KMM_OK;
     KMMCHK(ensure(ix->bam_out, (size_t)co.out_bytes + 64));
+    const RqExemptCall exempting{ix};
+    KMMCHK(bam_exempt_begin(ix, be, (int64_t)co.out_bytes, 0));
     KMMCHK(be.decode((n_raw + kmm_bam::TILE - 1) / kmm_bam::TILE, (uint8_t *)ix->bam_out.p));
     int64_t taken = 0, recs = 0;
     // ("record_bam", DESIGN 4.24: the inner call appends the entries and leaves the keep queue to bam_raw_keep below)

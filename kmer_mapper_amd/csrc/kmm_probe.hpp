@@ -54,13 +54,21 @@ struct ReadsView {
     const uint32_t *super_nl;  // per super-tile: newlines before it
     uint32_t period_mask;      // lines per record - 1 (3 for FASTQ, 1 for two-line FASTA)
     uint32_t header_char;      // '@' or '>'
+    // records mode with a quality floor (MODE_RECORDS_QUAL / _BRK_QUAL, kmm_rh_qual.hpp): bit p = the sequence byte at raw
+    // offset p has a quality byte below the floor
+    const uint32_t *dead;
 };
 
 enum { MODE_GENERAL = 0, MODE_UNIFORM = 1, MODE_RECORDS = 2, MODE_PACKED = 4 }; // (3 = MODE_KMERS, kmm_radix.hpp)
 // Records mode for a lookup table with a break entry (KMM_LUT_BREAK): a sequence byte with that entry is a break like the
 // bytes outside the sequence lines.  A mode of its own, so that the kernels of every other table carry no test for it.
 enum { MODE_RECORDS_BRK = 6 };
-constexpr bool mode_is_records(int mode) { return mode == MODE_RECORDS || mode == MODE_RECORDS_BRK; }
+// Records mode under the quality floor of the record-hits mode: a sequence byte whose bit is set in
+// ReadsView::dead is a break too.  Modes of their own for the same reason.
+enum { MODE_RECORDS_QUAL = 10, MODE_RECORDS_BRK_QUAL = 14 };
+constexpr bool mode_records_qual(int mode) { return mode == MODE_RECORDS_QUAL || mode == MODE_RECORDS_BRK_QUAL; }
+constexpr bool mode_records_brk(int mode) { return mode == MODE_RECORDS_BRK || mode == MODE_RECORDS_BRK_QUAL; }
+constexpr bool mode_is_records(int mode) { return mode == MODE_RECORDS || mode == MODE_RECORDS_BRK || mode_records_qual(mode); }
 
 // Exact x % m for any m >= 1 with one 64x64->hi multiply: q = hi64(x * floor(2^64/m)) is either
 // floor(x/m) or one less (x * (2^64/m - magic) / 2^64 < 1), so a single conditional subtract

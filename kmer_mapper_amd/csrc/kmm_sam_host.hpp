@@ -179,9 +179,13 @@ int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int64_t 
                 if (e != hipSuccess)
                     rc = fail(KMM_ERR_HIP, "kmm_map_records: k_sam_write_q: %s", hipGetErrorString(e));
             }
-            // the records as FASTQ, from HBM, through compaction and the radix path, where the floor is applied
+            // the records as FASTQ, from HBM, through compaction and the radix path, where the floor is applied — in the
+            // record-hits mode through the direct records route, piece by piece, under that mode's floor
             int64_t used = 0;
-            if (rc == KMM_OK)
+            if (rc == KMM_OK && ix->record_hits)
+                rc = map_records_entry(ix, (const uint8_t *)s.kmers.p, (int64_t)h.out_bytes, KMM_FORMAT_FASTQ, k, max_freq, also_revcomp, lut,
+                                       &used, n_records);
+            else if (rc == KMM_OK)
                 rc = map_records_radix_call(ix, (const uint8_t *)s.kmers.p, (int64_t)h.out_bytes, KMM_FORMAT_FASTQ, k, max_freq,
                                             also_revcomp, lut, &used, n_records);
             if (rc == KMM_OK && (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs))

@@ -209,6 +209,9 @@ __device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileCo
             // first byte of a line: preceded by '\n' (or the very first byte of the chunk)
             const uint32_t prev_nl = (p == 0) ? 1u : (p - 1 < total ? (rv.bases[p - 1] == 10u) : 0u);
             const uint32_t first = ((nl << 1) | prev_nl) & 0xFFFFu;
+            [[maybe_unused]] uint32_t low = 0; // (the quality variants: the thread's 16 bits of the floor's bitset)
+            if constexpr (mode_records_qual(MODE))
+                low = (rv.dead[p >> 5] >> (p & 16)) & 0xFFFFu; // (p: a multiple of 16)
 #pragma unroll
             for (int i = 15; i >= 0; --i) {
                 const uint32_t c = (w[i >> 2] >> (8 * (i & 3))) & 0xFFu;
@@ -217,10 +220,12 @@ __device__ __forceinline__ uint32_t tile_kmers(const ReadsView &rv, const TileCo
                 const bool term = ((nl | cr) >> i) & 1u;
                 const uint32_t l = sm.lut[c];
                 bool is_seq = phase == 1u && !term && p + i < total;
-                if (MODE == MODE_RECORDS_BRK) // (a break byte: a base of its read that no window may contain)
+                if (mode_records_brk(MODE)) // (a break byte: a base of its read that no window may contain)
                     is_seq = is_seq && l != KMM_LUT_BREAK;
                 if (is_seq && l == 0xFFu)
                     bad = i;
+                if constexpr (mode_records_qual(MODE)) // (behind the test above: a byte without a code is one at every quality)
+                    is_seq = is_seq && !((low >> i) & 1u);
                 if (((first >> i) & 1u) && p + i < total &&
                     ((phase == 0u && c != rv.header_char) || (phase == 2u && c != '+')))
                     malformed = i;

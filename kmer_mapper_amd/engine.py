@@ -387,11 +387,15 @@ class DeviceIndex:
                                             int(bool(also_revcomp)), t.ptr, hp, wp))
         return (hits, win) if windows else hits
 
-    def record_hits(self, on=True, windows=False):
+    def record_hits(self, on=True, windows=False, min_base_quality=0):
         """The record-hits mode (include/kmm.h): while it is on, map_records / map_bgzf / map_gzip / map_bam
         append one entry per record — its index hits, with windows=True also its windows, as read_hits defines them — to a
         queue of the handle instead of counting nodes; take_record_hits() fetches them.  on=False: the calls count nodes
-        again; entries still pending stay takeable."""
+        again; entries still pending stay takeable.
+        min_base_quality: the mode's own floor, "record_hits_min_base_quality" (DESIGN 4.27): a FASTQ base whose quality byte is
+        below '!' + Q is a break for hits and windows alike, the kept text is never altered; SAM / BAM records need
+        set_param("use_record_qual", 1), and those that store no qualities pass unmasked.  0, and on=False: no floor."""
+        self.set_param("record_hits_min_base_quality", int(min_base_quality) if on else 0)
         self.set_param("record_hits", (2 if windows else 1) if on else 0)
 
     def take_record_hits(self, capacity=None, out=None):

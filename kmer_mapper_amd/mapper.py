@@ -120,12 +120,30 @@ def read_hits(index, reads, k=31, max_index_lookup_frequency=1000, also_revcomp=
                                                                also_revcomp=also_revcomp, lut=lut, windows=windows)
 
 
-def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, windows=False, device=0):
+def _floor_on(dev, windows, min_base_quality, use_record_qual):
+    """The record-hits mode with its floor on a cached handle; returns what _floor_off puts back."""
+    before = dev.get_param("use_record_qual")
+    dev.record_hits(True, windows=windows, min_base_quality=min_base_quality)
+    if min_base_quality:
+        dev.set_param("use_record_qual", int(bool(use_record_qual)))
+    return before
+
+
+def _floor_off(dev, before):
+    dev.record_hits(False)
+    dev.set_param("use_record_qual", before)
+
+
+def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, windows=False, device=0,
+                min_base_quality=0, use_record_qual=False):
     """Extension: read_hits for reads that are still records — `raw` is a chunk of FASTQ (fmt "fastq"), two-line FASTA ("fasta")
     or SAM ("sam") text (bytes, a uint8 array or a torch tensor, host or device), parsed on the GPU with the cached handle's
     record-hits mode (DeviceIndex.record_hits / take_record_hits).  Returns (hits, consumed) — with windows=True
     (hits, windows, consumed): one entry per whole record of the chunk, in order; raw[consumed:] is the incomplete last record,
-    to be put in front of the next chunk.  The handle's node counts do not move, and the mode is off again afterwards."""
+    to be put in front of the next chunk.  The handle's node counts do not move, and the mode is off again afterwards.
+    min_base_quality: a base whose quality byte is below '!' + Q is a break — no window over it is looked up, and it counts in
+    neither hits nor windows; FASTA has no qualities and is served unchanged; SAM needs use_record_qual=True (its
+    QUAL column is decoded on the GPU; a QUAL of "*" passes unmasked)."""
     from . import _lib
     kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2, "sam": _lib.FORMAT_SAM}[fmt]
     if isinstance(raw, (bytes, bytearray, memoryview)):
@@ -134,19 +152,19 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
     dev = _device_index(index, max_node_id, device)
     if dev.get_param("record_hits_pending"):
         raise ValueError("the cached handle has record hits pending: take them first (DeviceIndex.take_record_hits)")
-    dev.record_hits(True, windows=windows)
+    before = _floor_on(dev, windows, min_base_quality, use_record_qual)
     try:
         consumed, _ = dev.map_records(raw, fmt=kfmt, k=k, max_index_lookup_frequency=max_index_lookup_frequency,
                                       also_revcomp=also_revcomp, lut=lut)
         got = dev.take_record_hits()
     finally:
-        dev.record_hits(False)
+        _floor_off(dev, before)
     return (got[0], got[1], consumed) if windows else (got, consumed)
 
 
 def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
                    min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False, compress=False, pairs=False,
-                   pair_rule="any", output="fastq", keep_mates=False, header=True):
+                   pair_rule="any", output="fastq", keep_mates=False, header=True, min_base_quality=0, use_record_qual=False):
     """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
     text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
     (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
@@ -172,8 +190,13 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     untouched, in file order, behind (header=True) every header line at its place; header=False drops the header lines.
     Records whose FLAG has any of exclude_flags are not written; original_strand applies to the hits alone; compress: a complete
     BGZF file (htslib reads it as .sam.gz).  The bytes behind the last newline are not looked at (len(text) tells with
-    min_hits=0).  mate_suffix, pairs and keep_mates do not go with it."""
+    min_hits=0).  mate_suffix, pairs and keep_mates do not go with it.
+    min_base_quality: the floor of record_hits — it changes which records pass the rule, never the text that comes
+    back; fmt "bam" needs use_record_qual=True (records that store no qualities pass unmasked); output "sam" does not go with it."""
     from . import _lib
+    if output == "sam" and min_base_quality:
+        raise ValueError("output=\"sam\" does not go with min_base_quality: SAM lines kept as SAM lines are mapped without their QUAL "
+                         "column")
     if output == "sam":
         if fmt != "sam":
             raise ValueError("output=\"sam\" goes with fmt=\"sam\": SAM lines are written from SAM lines")
@@ -204,7 +227,7 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     dev = _device_index(index, max_node_id, device)
     if dev.get_param("record_hits_pending") or dev.get_param("record_keep_pending_bytes"):
         raise ValueError("the cached handle has record hits or kept records pending: take them first")
-    dev.record_hits(True, windows=True)
+    before_qual = _floor_on(dev, True, min_base_quality, use_record_qual)
     dev.record_keep(True, min_hits=min_hits, min_permille=min_permille, invert=invert)
     before = None
     try:
@@ -248,7 +271,7 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
             dev.set_param("original_strand", before[1])
             dev.set_param("record_pairs_rule", before[2])
         dev.record_keep(False)
-        dev.record_hits(False)
+        _floor_off(dev, before_qual)
     return text, hits, windows
 
 
@@ -290,7 +313,8 @@ def _select_sam_lines(index, raw, k, max_index_lookup_frequency, also_revcomp, l
 
 
 def select_record_pairs(index, raw1, raw2=None, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None,
-                        min_hits=1, min_permille=0, invert=False, pair_rule="any", device=0, compress=False):
+                        min_hits=1, min_permille=0, invert=False, pair_rule="any", device=0, compress=False, min_base_quality=0,
+                        use_record_qual=False):
     """Extension: select_records for paired-end reads, whose mates are kept or dropped together.  raw2 None: `raw1`
     holds the mates interleaved, records 2i and 2i + 1; else record i of raw1 and record i of raw2 are mates (fmt "fastq" or
     "fasta", two-line, the same for both; each of bytes, a uint8 array or a torch tensor, host or device).  Per mate, match is
@@ -298,7 +322,9 @@ def select_record_pairs(index, raw1, raw2=None, fmt="fastq", k=31, max_index_loo
     "both" do, and is kept iff match != invert.  Returns (text1, text2, hits, windows): the kept records of raw1 and of raw2 in
     order — text2 None for interleaved input, whose kept pairs are text1 — and one entry per record of every whole pair, in pair
     order (mate 1, mate 2).  Records behind the last whole pair are not looked at.  The cached handle is left as it was found.
-    compress: text1, and text2 where there is one, are the bytes of BGZF files — deflated on the GPU."""
+    compress: text1, and text2 where there is one, are the bytes of BGZF files — deflated on the GPU.
+    min_base_quality: the floor of record_hits, on both mates; use_record_qual is taken for symmetry with
+    select_records: FASTQ and FASTA text never need it."""
     from . import _lib
     kfmt = {"fastq": _lib.FORMAT_FASTQ, "fasta": _lib.FORMAT_FASTA2}[fmt]
     as_array = lambda raw: np.frombuffer(bytes(raw), dtype=np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else raw
@@ -309,7 +335,7 @@ def select_record_pairs(index, raw1, raw2=None, fmt="fastq", k=31, max_index_loo
             or dev.get_param("record_keep_pending_bytes_mate2")):
         raise ValueError("the cached handle has record hits or kept records pending: take them first")
     before = (dev.get_param("record_pairs"), dev.get_param("record_pairs_rule"))
-    dev.record_hits(True, windows=True)
+    before_qual = _floor_on(dev, True, min_base_quality, use_record_qual)
     dev.record_keep(True, min_hits=min_hits, min_permille=min_permille, invert=invert)
     try:
         dev.record_pairs(raw2 is None, rule=pair_rule)
@@ -330,7 +356,7 @@ def select_record_pairs(index, raw1, raw2=None, fmt="fastq", k=31, max_index_loo
             text2 = take(1)
     finally:
         dev.record_keep(False)
-        dev.record_hits(False)
+        _floor_off(dev, before_qual)
         dev.set_param("record_pairs_rule", before[1])
         if not dev.get_param("record_hits_pending"):                                   # (a failing call appended nothing)
             dev.set_param("record_pairs", before[0])
