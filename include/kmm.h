@@ -751,7 +751,41 @@ int kmm_take_kept_records(kmm_index_t *idx, uint8_t *out, int64_t capacity, int6
  * never share a queue).  With 0 every call launches exactly what it launched without the parameter, and SAM stays refused in the
  * keep mode with its text.  With timing on the kernels of the keep step are timed together as KMM_KERNEL_SAM_RAW.  Out of scope:
  * mates kept together, SAM to FASTQ with names, SAM in with BAM out (or BAM in with SAM out), a rank's share, an @PG line, a
- * quality floor (the record-hits mode refuses one).
+ * quality floor (the record-hits mode refuses one).  (Mates kept together: "record_sam_mates", below.)
+ *
+ * SAM MATES KEPT TOGETHER.  "record_sam_mates" 0 (default) / 1 (anything else, or 1 while "record_sam" is 0,
+ * KMM_ERR_INVALID_ARG), read by KMM_FORMAT_SAM calls alone — kmm_map_records, and kmm_map_bgzf / kmm_map_gzip on their inflated
+ * bytes — and only while "record_sam" is 1 or 2, "record_hits" 1 or 2 and "record_keep" 1.  The selected records of the stream (what
+ * passes "bam_exclude_flags" and the selection), in file order, are mates: 2p and 2p + 1, as bwa mem, minimap2 -a and bowtie2 write
+ * them once 0x900 is excluded.  The stream runs from KMM_FORMAT_NEW_STREAM on the stream routes; on kmm_map_records from the moment
+ * the parameter is set, or from kmm_reset_counts.  Header lines and lines that are not selected never take part in the pairing.
+ * The keep decision is the pair rule of DESIGN 4.21 over the two records' entries (the keep rule's parameters and
+ * "record_pairs_rule"): both mates are kept or both are dropped.  Both lines of a kept pair are appended as they stand, newlines
+ * included, mate 1 directly in front of mate 2, where mate 2 stands in the file; with "record_sam" 1 every header line is appended
+ * once, at its place relative to the pairs — a header line between the two mates of a pair comes out in front of the pair.  Lines
+ * that are not selected and lie between two mates are dropped like any others.  The kept bytes are a function of the text and the
+ * rules alone, however the text is cut into pieces, chunks or windows.  "record_keep_pending_records" counts records, two per kept
+ * pair.  The hits queue gets one entry per record in pair order, whole pairs per call, and *n_records — an even number — counts
+ * them; "sam_records", "sam_records_excluded", "sam_header_lines" and *consumed are what they are without the switch.
+ *   THE WAITING MATE: a selected record whose mate the call has not brought waits on the handle — its line and its FASTA text — for
+ *   the piece or call that brings the mate, through pieces and windows without a selected record; its entry arrives with its
+ *   mate's call.  Read-only "record_sam_mate_waiting" is 1 while one waits.  *consumed is never shortened for it.  One small
+ *   read-back per piece.
+ *   THE MATE CHECK: the bytes of both lines up to their first TAB are compared on the device as they stand — equal in length and
+ *   content, nothing trimmed, no "/1", no case folding.  Strangers fail the call that completes the pair with KMM_ERR_MALFORMED;
+ *   the message names the lowest such pair's ordinal in the stream and its records 2p and 2p + 1, says "are not mates", and what
+ *   to do: group the file by name, exclude 0x900.  A KMM_FORMAT_LAST_CHUNK call that leaves a mate 1 waiting — also one that
+ *   brings no byte; kmm_map_records reads the flag for SAM under this switch alone — fails with KMM_ERR_MALFORMED ("the stream ends
+ *   with an unpaired record", with the count of selected records).  Strangers come first.  A failing call appends nothing to
+ *   either queue, restores the pair ordinal and the SAM counters and leaves the waiting mate as it found it: a later call that
+ *   brings its mate completes the pair.  kmm_reset_counts, KMM_FORMAT_NEW_STREAM and a change of "record_sam" or "record_sam_mates"
+ *   drop a waiting mate.
+ * Refused with KMM_ERR_INVALID_ARG: everything "record_sam" refuses, in its wording ("record_pairs" 1 and the floor of the
+ * record-hits mode among it); a change of "record_sam_mates" while hit entries or kept bytes are pending.  With 0 every call
+ * launches exactly what it launched without the parameter.  With timing on the kernels are timed together as
+ * KMM_KERNEL_SAM_RAW_MATES, and KMM_KERNEL_SAM_RAW counts none.  Out of scope: coordinate-sorted input (the check reports it),
+ * singletons diverted, a requirement that FLAG has 0x1, 0x40 or 0x80, SAM to FASTQ, SAM in with BAM out, a quality floor, several
+ * ranks, an @PG line.
  */
 int kmm_bam_stream_header(kmm_index_t *idx, uint8_t *out, int64_t capacity, int64_t *n_bytes);
 int kmm_map_record_pairs(kmm_index_t *idx, const uint8_t *raw1, int64_t n1, const uint8_t *raw2, int64_t n2, int format, int k,
@@ -822,7 +856,8 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
 #define KMM_KERNEL_BAM_RAW_MATES 10 /* "record_bam_mates": the pair forms of the above, the mate check and the carried mate 1 */
 #define KMM_KERNEL_SAM_RAW 11     /* "record_sam": the tiles' scan, flags, block scan, copy and advance of the kept SAM lines */
 #define KMM_KERNEL_RH_QUAL_MARK 12 /* "record_hits_min_base_quality": line starts and the mark pass in front of the hit kernel */
-#define KMM_N_KERNELS 13
+#define KMM_KERNEL_SAM_RAW_MATES 13 /* "record_sam_mates": the pair forms of the above, the spans by entry and the mate check */
+#define KMM_N_KERNELS 14
 int kmm_set_timing(kmm_index_t *idx, int enabled);
 /* Work done by the map calls of this handle since creation (or the last call with reset != 0):
  * k-mer lookups performed (windows, doubled with also_revcomp) and count increments (index hits that
@@ -1003,6 +1038,9 @@ int kmm_get_kmer_counts(kmm_index_t *idx, uint32_t *out);
  *                      (block_size word and all) to the keep queue instead of text; see THE RAW FORM, kmm_bam_stream_header
  *   "record_sam"       0 (default) / 1 / 2: a KMM_FORMAT_SAM call with "record_hits" and "record_keep" appends the kept records'
  *                      own lines to the keep queue, 1 with the header lines, 2 without; see SAM LINES KEPT AS SAM LINES
+ *   "record_sam_mates" 0 (default) / 1: with "record_sam", the selected records of a SAM stream are mates in file order (2p,
+ *                      2p + 1), their QNAME bytes are compared on the device and their lines are kept or dropped together;
+ *                      read-only "record_sam_mate_waiting"; see SAM MATES KEPT TOGETHER
  *   "debug_records_piece_kb" test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a file of a
  *                      few hundred KB then has several pieces; not for callers, no effect at 0
  *   "debug_records_grid" test hook of kmm_map_records: workgroups (four wavefronts each) of the two per-tile kernels of the

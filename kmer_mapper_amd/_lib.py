@@ -29,9 +29,9 @@ FORMAT_SAM = 8                  # SAM text: the SEQ column extracted on the GPU 
 # kernel ids of kmm_get_timing (include/kmm.h)
 (KERNEL_MAP_READS, KERNEL_MAP_KMERS, KERNEL_RX_P1, KERNEL_RX_SCAN, KERNEL_RX_P2, KERNEL_RX_P3,
  KERNEL_RX_FLUSH, KERNEL_BGZF_DEFLATE, KERNEL_BGZF_GATHER, KERNEL_BAM_RAW, KERNEL_BAM_RAW_MATES, KERNEL_SAM_RAW,
- KERNEL_RH_QUAL_MARK) = range(13)
+ KERNEL_RH_QUAL_MARK, KERNEL_SAM_RAW_MATES) = range(14)
 KERNEL_NAMES = ("k_map_reads", "k_map_kmers", "k_rx_p1", "k_rx_scan", "k_rx_p2", "k_rx_p3", "k_rx_flush", "k_bz_deflate",
-                "k_bz_gather", "k_bam_raw", "k_bam_raw_mates", "k_sam_raw", "k_rh_qual_mark")
+                "k_bz_gather", "k_bam_raw", "k_bam_raw_mates", "k_sam_raw", "k_rh_qual_mark", "k_sam_raw_mates")
 
 _c = ctypes
 _P = ctypes.c_void_p

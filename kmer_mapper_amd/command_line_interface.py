@@ -330,13 +330,16 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
                                     world_size=world_size, fmt=fmt, lut=lut, min_base_quality=min_base_quality,
                                     use_record_qual=use_record_qual, original_strand=original_strand, shard_bam=shard_bam,
                                     record_select=bool(record_select), record_hits=record_hits)
+    # (mates kept together in SAM output, DESIGN 4.28: the file's last chunk says so, and an unpaired last record fails it)
+    sam_mates, said_last = fmt == "sam" and bool(getattr(record_hits, "sam_mates", False)), False
     try:
         i = 0
         while True:
             buf = chunker.next_chunk()
             if buf is None:
                 break
-            last = _lib.FORMAT_LAST_CHUNK if (fmt == "fasta_ml" and chunker.eof) else 0
+            last = _lib.FORMAT_LAST_CHUNK if ((fmt == "fasta_ml" or sam_mates) and chunker.eof) else 0
+            said_last = said_last or bool(last)
             if owns(i):
                 used, n_rec = dev.map_records(buf, buf.shape[0], kfmt | last, k, max_index_lookup_frequency,
                                               also_revcomp=map_reverse_complements, lut=lut)
@@ -354,6 +357,9 @@ def map_gpu_raw(index, path, chunk_size, fmt, k, map_reverse_complements=False,
             n_bytes += used
             chunker.consumed(used)
             i += 1
+        if sam_mates and not said_last:              # (the reader met the end of the file behind its last chunk)
+            dev.map_records(np.zeros(0, dtype=np.uint8), 0, kfmt | _lib.FORMAT_LAST_CHUNK, k, max_index_lookup_frequency,
+                            also_revcomp=map_reverse_complements, lut=lut)
         t_calls = time.perf_counter()
         n_lookups, n_hits = dev.get_stats()
         n_radix, n_direct = dev.get_param("radix_batches"), dev.get_param("direct_batches")
@@ -966,7 +972,7 @@ class RecordKeepSink(RecordHitsSink):
 
     def __init__(self, out, min_hits=1, min_permille=0, invert=False, names=False, mate_suffix=False, pairs=False, pair_rule="any",
                  out2=None, bgzf=False, bam_pairs=False, bam_out=False, bam_mates=False, sam_out=False, sam_header=True,
-                 min_base_quality=0):
+                 min_base_quality=0, sam_mates=False):
         super().__init__(windows=True, min_base_quality=min_base_quality)
         self.out = out
         self.rule = dict(min_hits=int(min_hits), min_permille=int(min_permille), invert=bool(invert))
@@ -986,6 +992,8 @@ class RecordKeepSink(RecordHitsSink):
         self.bam_mates = bool(bam_mates) and self.bam_out
         # SAM out: the kept records' own lines ("record_sam"), behind the header lines unless sam_header is off
         self.sam_out, self.sam_header = bool(sam_out), bool(sam_header)
+        # mates kept together in SAM out: the selected records are mates in file order ("record_sam_mates")
+        self.sam_mates = bool(sam_mates) and self.sam_out
         self.header_written = False
         self.bgzf = bool(bgzf) or self.bam_out
         self.written = 0                     # bytes written to out and out2 (the members' with bgzf, else the text's)
@@ -1000,8 +1008,8 @@ class RecordKeepSink(RecordHitsSink):
         elif self.bam_out:
             dev.record_bam(True)
         if self.sam_out:
-            dev.record_sam(True, header=self.sam_header)
-        if self.bam_pairs or self.bam_mates:
+            dev.record_sam(True, header=self.sam_header, **({"mates": True} if self.sam_mates else {}))
+        if self.bam_pairs or self.bam_mates or self.sam_mates:
             dev.record_pairs(False, rule=self.pair_rule)
         if self.pairs or self.out2 is not None:
             dev.record_pairs(self.pairs, rule=self.pair_rule)
@@ -1133,6 +1141,15 @@ def check_select_reads_sam_out(fmt, sam_out, no_header=False, given=()):
                "--mate-suffix": "the names are not rewritten"}.get(opt, "mates are not kept together in SAM output, which has one "
                                                                         "input file (-f) and one output file (-o)")
         raise ValueError("select-reads: --sam-out does not go with %s: %s" % (opt, why))
+
+
+def check_select_reads_sam_mates(sam_mates, sam_out):
+    """--sam-mates of `kmer_mapper select-reads`: with --sam-out, the mates of SAM text grouped by name — an
+    aligner's own output — are kept or dropped together and leave as SAM lines.  Without --sam-out it is refused before the index
+    is read and before -o is created."""
+    if sam_mates and not sam_out:
+        raise ValueError("select-reads: --sam-mates goes with --sam-out: the kept mates are written as SAM lines; a BAM file's mates "
+                         "have --bam-out --keep-mates, and interleaved FASTQ / FASTA input has --interleaved")
 
 
 def check_select_reads_keep_mates(keep_mates, bam_out):
@@ -1272,6 +1289,8 @@ def select_reads_file(args):
     bam_out = bool(getattr(args, "bam_out", False))
     keep_mates = bool(getattr(args, "keep_mates", False))
     sam_out = bool(getattr(args, "sam_out", False))
+    sam_mates = bool(getattr(args, "sam_mates", False))
+    check_select_reads_sam_mates(sam_mates, sam_out)
     check_select_reads_sam_out(probe.fmt, sam_out, bool(getattr(args, "no_header", False)),
                                [opt for opt, name in _SELECT_READS_NOT_WITH_SAM_OUT if getattr(args, name, None)])
     check_select_reads_keep_mates(keep_mates, bam_out)
@@ -1283,7 +1302,7 @@ def select_reads_file(args):
     if bam_pairs:
         check_select_reads_bam_pairs(probe.fmt, bool(getattr(args, "bam_to_fastq", False)), interleaved, reads2, output2)
     check_select_reads_pairs(probe, args.reads, args.output_file, interleaved, reads2, output2,
-                             None if bam_pairs or keep_mates else pair_rule)
+                             None if bam_pairs or keep_mates or sam_mates else pair_rule)
     # (with --sam-out the options that select records apply to SAM too; those that change the output's form were refused above)
     bam_options = [opt for opt, name in _SELECT_READS_BAM_ONLY if getattr(args, name, None) and not sam_out]
     check_select_reads_input(probe.fmt, world, args.reads, args.output_file, bool(getattr(args, "bam_to_fastq", False)), bam_options,
@@ -1309,7 +1328,13 @@ def select_reads_file(args):
         opt = lambda name, default=None: getattr(args, name, default)
         select = check_record_select(fmt, include_flags=opt("include_flags", 0), min_mapq=opt("min_mapq", 0), regions=opt("regions"),
                                      regions_file=opt("regions_file"))
-        more = dict(exclude_flags=int(opt("exclude_flags", 0) or 0), original_strand=check_original_strand(True, fmt),
+        exclude_flags = int(opt("exclude_flags", 0) or 0)
+        if sam_mates:
+            # (a secondary or supplementary line between two mates would be taken for one of them: DESIGN 4.28)
+            logging.info("select-reads --sam-mates: secondary and supplementary records are excluded (--exclude-flags 0x%x | 0x900 "
+                         "= 0x%x)", exclude_flags, exclude_flags | 0x900)
+            exclude_flags |= 0x900
+        more = dict(exclude_flags=exclude_flags, original_strand=check_original_strand(True, fmt),
                     **({"record_select": select} if select else {}))
     if bam:
         # (the route `read-hits --device-parser` takes for BAM, with the names on; reverse-strand records in read orientation
@@ -1344,7 +1369,9 @@ def select_reads_file(args):
                  "; the kept SAM lines written as they stand, %s the header lines (--sam-out)"
                  % ("without" if getattr(args, "no_header", False) else "behind") if sam_out else
                  "; BAM records decoded to FASTQ with their names (--bam-to-fastq)" if bam else "",
-                 "; neighbouring records are mates, kept together, pair rule '%s' (--bam-pairs)" % (pair_rule or "any") if bam_pairs else "")
+                 "; neighbouring records are mates, kept together, pair rule '%s' (--bam-pairs)" % (pair_rule or "any") if bam_pairs else
+                 "; neighbouring selected records are mates, kept together, pair rule '%s' (--sam-mates)" % (pair_rule or "any")
+                 if sam_mates else "")
     rule = dict(min_hits=args.min_hits, min_permille=args.min_hit_permille, invert=args.invert,
                 bgzf=bool(getattr(args, "bgzf", False)))
     if reads2 is not None:
@@ -1360,7 +1387,8 @@ def select_reads_file(args):
             sink = RecordKeepSink(out, names=bam and not bam_out, mate_suffix=bam and bool(getattr(args, "mate_suffix", False)),
                                   pairs=interleaved, pair_rule=pair_rule or "any", bam_pairs=bam_pairs, bam_out=bam_out,
                                   **({"bam_mates": True} if keep_mates else {}),
-                                  **({"sam_out": True, "sam_header": not getattr(args, "no_header", False)} if sam_out else {}), **rule)
+                                  **({"sam_out": True, "sam_header": not getattr(args, "no_header", False)} if sam_out else {}),
+                                  **({"sam_mates": True} if sam_mates else {}), **rule)
             try:
                 map_gpu_raw(kmer_index, args.reads, args.chunk_size, fmt, k, bool(args.map_reverse_complements), args.max_hits_per_kmer,
                             device=args.device, n_threads=16, probe=probe, lut=lut, record_hits=sink, before_fetch=sink.finish, **more,
@@ -1371,6 +1399,11 @@ def select_reads_file(args):
                     out.close()
                     os.remove(args.output_file)
                     raise ValueError("select-reads --bam-out --keep-mates: %s (%s was removed)" % (exc, args.output_file)) from exc
+                if sam_mates and ("are not mates" in str(exc) or "unpaired record" in str(exc)):
+                    # (a SAM file that stops in the middle looks like one that does not — -o is removed)
+                    out.close()
+                    os.remove(args.output_file)
+                    raise ValueError("select-reads --sam-out --sam-mates: %s (%s was removed)" % (exc, args.output_file)) from exc
                 if not interleaved or not ("unpaired record" in str(exc) or "do not form a complete record" in str(exc)):
                     raise
                 # (the error path alone: the file's lines counted once more on the host, to name both sides)
@@ -1601,6 +1634,13 @@ def build_argument_parser():
                           "--exclude-flags, --include-flags, --min-mapq, --regions and --regions-file; the hits of records with "
                           "FLAG 0x10 are counted in read orientation. Does not go with --bam-to-fastq, --bam-out, --as-stored, "
                           "--mate-suffix, --bam-pairs, --keep-mates, --interleaved or -f2 / -o2.")
+    sub.add_argument("--sam-mates", action="store_true", default=argparse.SUPPRESS,
+                     help="With --sam-out: the SAM text is grouped by name (as bwa mem, minimap2 -a and bowtie2 write it): "
+                          "neighbouring selected records are mates, and both lines are kept or both dropped (--pair-rule), mate 1 "
+                          "directly in front of mate 2. Secondary and supplementary records (0x900) are excluded; the QNAME bytes "
+                          "of every pair are compared on the GPU as they stand. Neighbours that are not mates (a coordinate-sorted "
+                          "file) or a last record without its mate are an error, after which -o is removed and no --hits-output "
+                          "is written.")
     sub.add_argument("--no-header", action="store_true", default=argparse.SUPPRESS,
                      help="With --sam-out: leave the header lines out (`samtools view` without -h), for shares that are concatenated.")
     sub.add_argument("--bgzf", action="store_true", default=argparse.SUPPRESS,

@@ -514,6 +514,17 @@ struct kmm_index : IndexStreams, RxArrays {
     // front, the spans of the write walk, their kept lengths and prefixes, the blocks' sums and bases, the totals.
     int record_sam = 0;
     DevBuf sam_raw;
+    // mates kept together in SAM output: "record_sam_mates" 1: the selected records of a SAM stream are mates in file
+    // order and their lines are kept or dropped together.  The inner piece call runs with rk_mates_call AND rk_raw_call, as under
+    // "record_bam_mates".  A piece's odd last selected record waits twice: its FASTA text in sam_mate (sam_mate_len), its line in
+    // sam_mate_line (sam_mate_line_len); sam_pairs_done: pairs of the stream handed over so far.  *_next: the spare buffers a piece
+    // fills before it appends and swaps in when it is done; *_call0: the waiting mate as the call found it (sam_mate_saved: it was
+    // moved there by a piece of the call), put back by a call that fails.  sam_mates_ctl: a piece's three control words;
+    // sam_span_of: its spans by entry.
+    int record_sam_mates = 0;
+    DevBuf sam_mate, sam_mate_line, sam_mate_next, sam_mate_line_next, sam_mate_call0, sam_mate_line_call0, sam_mates_ctl, sam_span_of;
+    int64_t sam_mate_len = 0, sam_mate_line_len = 0, sam_pairs_done = 0, sam_mate_len_call0 = 0, sam_mate_line_len_call0 = 0;
+    bool sam_mate_saved = false;
     BzScratch bz; // kmm_take_kept_bgzf
     uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
@@ -1193,6 +1204,19 @@ bool sam_raw_on(const kmm_index *ix)
     return ix->record_sam && ix->record_hits && ix->record_keep;
 }
 
+// Are the selected records of a SAM stream taken as mates whose lines are kept together ("record_sam_mates")?
+bool sam_raw_mates_on(const kmm_index *ix)
+{
+    return ix->record_sam_mates && sam_raw_on(ix);
+}
+
+// The waiting mate 1 of a SAM stream and the stream's pair ordinal are dropped (a new stream, emptied queues, a changed form).
+void sam_mates_drop(kmm_index *ix)
+{
+    ix->sam_mate_len = ix->sam_mate_line_len = ix->sam_pairs_done = 0;
+    ix->sam_mate_saved = false;
+}
+
 // Are the records of a FASTQ / two-line FASTA stream taken as interleaved mates?
 bool record_pairs_on(const kmm_index *ix)
 {
@@ -1679,6 +1703,7 @@ int kmm_reset_counts(kmm_index_t *ix)
     ix->rk_snap.valid = false;
     ix->bam_mate_len = ix->bam_pairs_done = 0; // (a mate 1 that waits for its mate belongs to the entries just dropped: DESIGN 4.23)
     ix->bam_raw_mate_len = 0;                  // (and so do its raw bytes: DESIGN 4.25)
+    sam_mates_drop(ix);                        // (and the waiting mate 1 of a SAM stream: DESIGN 4.28)
     // ("record_name_bytes_replaced" counts bytes of the text that queue held: it restarts with it.  The named decode adds to the
     // first shard alone; the other statistics stay, as before, until kmm_get_stats(reset).)
     HIPCHK(hipMemsetAsync(ix->stats + KMM_STAT_REC_NAME_REPLACED, 0, sizeof(unsigned long long), ix->stream));
@@ -3107,6 +3132,10 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         *consumed = 0;
     if (n_records)
         *n_records = 0;
+    // ("record_sam_mates", DESIGN 4.28: a last call that brings no byte can still leave a mate 1 alone)
+    const bool sam_mates = format == KMM_FORMAT_SAM && sam_raw_mates_on(ix);
+    if (n_bytes == 0 && last_chunk && sam_mates && ix->sam_mate_len > 0)
+        return sam_unpaired_end("kmm_map_records", 2 * ix->sam_pairs_done + 1);
     if (n_bytes == 0)
         return KMM_OK;
     if (!raw)
@@ -3151,6 +3180,7 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
     }
     const int64_t piece_max = records_piece_max(ix);
     int64_t off = 0, recs = 0;
+    SamMatesUndo sam_undo(ix, sam_mates); // (the pair form of "record_sam": a failing call leaves the waiting mate and the counters alone)
     if (format == KMM_FORMAT_SAM && n_bytes > piece_max) {
         // a SAM chunk of several pieces is checked whole first: a malformed line in a later piece maps nothing of the call
         while (off < n_bytes) {
@@ -3186,6 +3216,11 @@ static int map_records_entry(kmm_index_t *ix, const uint8_t *raw, int64_t n_byte
         if (used == 0 || len < piece_max)
             break; // no complete record left in reach / the last piece
     }
+    // (a mate 1 that waits behind the stream's last line has no mate; a line longer than a piece, which ends the call in front of
+    // it, is brought again: the stream goes on)
+    if (sam_mates && last_chunk && ix->sam_mate_len > 0 && n_bytes - off < piece_max)
+        return sam_unpaired_end("kmm_map_records", 2 * ix->sam_pairs_done + 1);
+    sam_undo.armed = false;
     if (format == KMM_FORMAT_SAM)
         ix->sam_calls++;
     if (consumed)
@@ -3669,6 +3704,16 @@ static int stream_call_start(kmm_index_t *ix, StreamCall &c, const uint8_t *comp
         return fail(KMM_ERR_INVALID_ARG, "%s takes the compressed bytes from host memory%s", c.who,
                     chain ? " (the member chain is read there)" : "");
     HIPCHK(hipSetDevice(ix->device));
+    if (text && c.new_stream && c.fmt == KMM_FORMAT_SAM)
+        sam_mates_drop(ix); // ("record_sam_mates", DESIGN 4.28: a mate 1 left over belongs to the stream before)
+    return KMM_OK;
+}
+
+// A text stream's last call that has no inflated byte to map: under "record_sam_mates" a mate 1 that still waits has no mate.
+static int sam_mates_empty_end(kmm_index_t *ix, const StreamCall &c)
+{
+    if (c.last_chunk && c.fmt == KMM_FORMAT_SAM && sam_raw_mates_on(ix) && ix->sam_mate_len > 0)
+        return kmm_map_records(ix, nullptr, 0, c.fmt | KMM_FORMAT_LAST_CHUNK, c.k, c.max_freq, c.also_revcomp, c.lut, nullptr, nullptr);
     return KMM_OK;
 }
 
@@ -3726,8 +3771,10 @@ static int map_text_inflated(kmm_index_t *ix, const StreamCall &c, uint8_t *d_ra
     int64_t recs = 0;
     *used = 0;
     ix->rk_snap.valid = false; // (what keep_carry may put back is this call's, never an earlier one's)
-    if (n_raw > head)
-        KMMCHK(kmm_map_records(ix, d_raw + head, n_raw - head, c.fmt, c.k, c.max_freq, c.also_revcomp, c.lut, used, &recs));
+    // ("record_sam_mates", DESIGN 4.28: the stream's last call says so — a mate 1 that still waits then has no mate)
+    const int last = c.last_chunk && c.fmt == KMM_FORMAT_SAM && sam_raw_mates_on(ix) ? KMM_FORMAT_LAST_CHUNK : 0;
+    if (n_raw > head || last)
+        KMMCHK(kmm_map_records(ix, d_raw + head, n_raw - head, c.fmt | last, c.k, c.max_freq, c.also_revcomp, c.lut, used, &recs));
     *used += head;
     if (c.n_records)
         *c.n_records = recs;
@@ -3956,7 +4003,7 @@ int kmm_map_bgzf(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int forma
         BgzfCall b;
         KMMCHK(bgzf_inflate(ix, c, comp, n_comp, b, bgzf_rank_share));
         if (!b.d_raw)
-            return KMM_OK;
+            return sam_mates_empty_end(ix, c);
         int64_t used = 0;
         KMMCHK(map_text_inflated(ix, c, b.d_raw, b.head, b.n_raw, ix->bgzf_raw[b.cur].cap, b.last_byte, &used));
         return bgzf_finish(ix, c, b, used);
@@ -4372,7 +4419,8 @@ int kmm_map_gzip(kmm_index_t *ix, const uint8_t *comp, int64_t n_comp, int forma
                         be.ms_resolve, be.ms_crc, ms_since(t_0) - ms_stage - ms_inflate);
             KMMCHK(keep_carry(ix, c, d_raw, used, n_raw, ix->gz_carry, ix->gz_carry_len));
             HIPCHK(hipStreamSynchronize(ix->stream));
-        }
+        } else
+            KMMCHK(sam_mates_empty_end(ix, c));
         if (c.last_chunk)
             ix->gz_arena.clear(); // the stream has ended: its symbol slots go back to the device
         return KMM_OK;
@@ -5313,7 +5361,35 @@ int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
                             "take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue (kmm_reset_counts) first",
                             (long long)value, tail[0], ix->record_sam);
         }
+        if ((int)value != ix->record_sam)
+            sam_mates_drop(ix); // (a mate 1 that waits under one form is no carry of another's: DESIGN 4.28)
         ix->record_sam = (int)value;
+    } else if (!strcmp(name, "record_sam_mates")) {
+        // 1: a KMM_FORMAT_SAM call under "record_sam" takes the selected records of the stream as mates in file order — 2p and
+        // 2p + 1 — checks that their QNAME bytes agree and keeps or drops their lines together; even counts
+        if (value != 0 && value != 1)
+            return fail(KMM_ERR_INVALID_ARG, "record_sam_mates takes 0 or 1");
+        if (value == 1 && !ix->record_sam)
+            return fail(KMM_ERR_INVALID_ARG, "record_sam_mates 1 with \"record_sam\" 0: mates are kept together in the raw form of the keep, "
+                        "set \"record_sam\" to 1 or 2 first (with \"record_hits\" and \"record_keep\")");
+        if ((int)value != ix->record_sam_mates) {
+            if (ix->rhq_pending > 0)
+                return fail(KMM_ERR_INVALID_ARG, "record_sam_mates %lld with %lld entries pending that were appended under record_sam_mates "
+                            "%d: take them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
+                            (long long)ix->rhq_pending, ix->record_sam_mates);
+            if (ix->rkq[0].ctl.p) {
+                HIPCHK(hipSetDevice(ix->device));
+                KMMCHK(drain(ix));
+                unsigned long long tail[2];
+                KMMCHK(rkq_tail(ix->rkq[0], tail));
+                if (tail[0] > 0)
+                    return fail(KMM_ERR_INVALID_ARG, "record_sam_mates %lld with %llu kept bytes pending that were appended under "
+                                "record_sam_mates %d: take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue "
+                                "(kmm_reset_counts) first", (long long)value, tail[0], ix->record_sam_mates);
+            }
+            sam_mates_drop(ix);
+        }
+        ix->record_sam_mates = (int)value;
     } else if (!strcmp(name, "record_bam_mates")) {
         // 1: kmm_map_bam with "record_bam" takes the selected records of a stream as mates in file order — 2p and 2p + 1 — checks
         // that their read_name bytes agree and keeps or drops their own bytes together; even counts, as "record_pairs"
@@ -5431,6 +5507,10 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
         *value = ix->record_sam;
     else if (!strcmp(name, "record_bam_mates"))
         *value = ix->record_bam_mates;
+    else if (!strcmp(name, "record_sam_mates"))
+        *value = ix->record_sam_mates;
+    else if (!strcmp(name, "record_sam_mate_waiting")) // (read-only) a selected SAM record waits for its mate
+        *value = ix->sam_mate_len > 0 ? 1 : 0;
     else if (!strcmp(name, "record_keep"))
         *value = ix->record_keep;
     else if (!strcmp(name, "record_keep_min_hits"))

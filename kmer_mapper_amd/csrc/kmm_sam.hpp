@@ -598,6 +598,140 @@ KMM_SAM_HD void raw_copy_span(const uint8_t *d, const RawSpan &sp, uint8_t *queu
     kmm_bam::raw_copy_part(d + sp.start, queue, dst, sp.len, lane, lanes);
 }
 
+// ---- mates kept together in the raw form ("record_sam_mates"): the selected records of the stream are mates in file
+// order, 2p and 2p + 1; their lines are kept or dropped together, mate 1 directly in front of mate 2.  A piece's entries are those
+// of its whole pairs, n_entries = 2P of them; a mate 1 that the piece or call before left over is entry 0 (`carried` = 1: its line
+// waits in a buffer of the handle), so selected record i of the piece has entry carried + i.  The record whose entry would be 2P is
+// the odd last one: it waits for the next piece.  span_of[i]: the span of selected record i (MATE_NONE where the walk left none).
+constexpr uint32_t MATE_NONE = 0xFFFFFFFFu;
+
+// One line of a pair: where its bytes are and how many (p null: there is no such line).
+struct MateLine {
+    const uint8_t *p;
+    uint32_t len;
+};
+
+// A span as the keep step may read it: filled by the walk and inside the piece's consumed bytes.
+KMM_SAM_HD bool raw_span_ok(const RawSpan &sp, uint64_t consumed)
+{
+    return sp.len != 0 && sp.start < consumed && (uint64_t)sp.len <= consumed - sp.start;
+}
+
+// The spans by entry: span i of the walk is that of selected record sp.entry (header lines and empty slots have none).
+KMM_SAM_HD void raw_span_of_store(const RawSpan &sp, uint64_t i, uint64_t n_recs, uint32_t *span_of)
+{
+    if (sp.len != 0 && sp.entry != RAW_HEADER && (uint64_t)sp.entry < n_recs)
+        span_of[sp.entry] = (uint32_t)i;
+}
+
+// What a piece of the pair form reads: its bytes and spans, the spans by entry, the waiting line.
+struct MatePiece {
+    const uint8_t *d;
+    uint64_t consumed;
+    const RawSpan *spans;
+    uint64_t n_spans;
+    const uint32_t *span_of;
+    uint64_t n_recs; // the piece's selected records
+    uint32_t carried;
+    const uint8_t *carry;
+    uint32_t carry_len;
+};
+
+// The line of entry g of the piece: the waiting one for entry 0 of a piece with a carry, else the span of record g - carried.
+KMM_SAM_HD MateLine raw_mate_line(const MatePiece &m, uint64_t g)
+{
+    if (m.carried && g == 0)
+        return MateLine{m.carry_len ? m.carry : nullptr, m.carry_len};
+    const uint64_t e = g - m.carried;
+    if (e >= m.n_recs)
+        return MateLine{nullptr, 0u};
+    const uint32_t i = m.span_of[e];
+    if ((uint64_t)i >= m.n_spans)
+        return MateLine{nullptr, 0u};
+    const RawSpan sp = m.spans[i];
+    if (!raw_span_ok(sp, m.consumed) || sp.entry != (uint32_t)e)
+        return MateLine{nullptr, 0u};
+    return MateLine{m.d + sp.start, sp.len};
+}
+
+// The share of lane `lane` of `lanes` in comparing two lines' names over bytes [j0, j1) (both lines hold j1 bytes): the lowest
+// position of its share where the lines differ or hold a TAB, as position << 1 | (they differ), MATE_NONE when there is none.
+// The lowest such position over all lanes decides: two TABs there end two equal names, anything else parts two strangers.
+KMM_SAM_HD uint32_t raw_names_part(const uint8_t *a, const uint8_t *b, uint32_t j0, uint32_t j1, uint32_t lane, uint32_t lanes)
+{
+    for (uint32_t j = j0 + lane; j < j1; j += lanes) {
+        const uint8_t x = a[j], y = b[j];
+        if (x != y || x == (uint8_t)'\t')
+            return j << 1 | (x != y ? 1u : 0u);
+    }
+    return MATE_NONE;
+}
+
+// Are two lines no mates?  Their bytes up to the first TAB must agree in length and content; a line without a TAB inside its span
+// is a stranger to every other.  `lanes` bytes a round; lowest(f): the minimum of f(lane) over the lanes, the same for all of them.
+template <class Lowest>
+KMM_SAM_HD bool raw_pair_strangers(const MateLine &a, const MateLine &b, uint32_t lanes, Lowest &&lowest)
+{
+    if (!a.p || !b.p)
+        return true;
+    const uint32_t m = a.len < b.len ? a.len : b.len;
+    for (uint32_t j0 = 0; j0 < m; j0 += lanes) {
+        const uint32_t j1 = m - j0 < lanes ? m : j0 + lanes;
+        const uint32_t c = lowest([&](uint32_t lane) { return raw_names_part(a.p, b.p, j0, j1, lane, lanes); });
+        if (c != MATE_NONE)
+            return (c & 1u) != 0u;
+    }
+    return true;
+}
+
+// The bytes a span adds to the queue in the pair form: a header line its own length; a mate 1 nothing at its own place; a mate 2
+// both lines' lengths when the pair is kept (rk_pair_keep over its two entries), so that mate 1 comes out directly in front of it
+// wherever a cut falls.  recs: the records it adds (2 for a kept pair).  odd: the span is the odd last record, which is neither
+// counted nor copied here.
+KMM_SAM_HD uint32_t raw_pair_kept_len(const MatePiece &m, const RawSpan &sp, const uint32_t *hits, const uint32_t *windows, uint64_t n_entries,
+                                      const RkPairRule &rule, uint32_t &recs, bool &odd)
+{
+    recs = 0u;
+    odd = false;
+    if (!raw_span_ok(sp, m.consumed))
+        return 0u;
+    if (sp.entry == RAW_HEADER)
+        return sp.len;
+    const uint64_t g = (uint64_t)sp.entry + m.carried;
+    if (g >= n_entries) {
+        odd = g == n_entries;
+        return 0u;
+    }
+    if ((g & 1ull) == 0ull || !kmm_bam::raw_pair_kept(hits, windows, n_entries, g, rule))
+        return 0u;
+    const MateLine first = raw_mate_line(m, g - 1);
+    if (!first.p)
+        return 0u;
+    recs = 2u;
+    return first.len + sp.len;
+}
+
+// The share of lane `lane` of `lanes` in moving a kept span of the pair form to the queue: a header line as it stands, a mate 2
+// behind its mate 1's line (from the piece, or from the waiting buffer).  kept: what raw_pair_kept_len gave for the span — the
+// copy writes exactly those bytes or none.
+KMM_SAM_HD void raw_pair_copy_span(const MatePiece &m, const RawSpan &sp, uint32_t kept, uint8_t *queue, uint64_t dst, uint32_t lane,
+                                   uint32_t lanes)
+{
+    if (sp.entry == RAW_HEADER) {
+        if (kept == sp.len)
+            kmm_bam::raw_copy_part(m.d + sp.start, queue, dst, sp.len, lane, lanes);
+        return;
+    }
+    const uint64_t g = (uint64_t)sp.entry + m.carried;
+    if (g == 0)
+        return;
+    const MateLine first = raw_mate_line(m, g - 1);
+    if (!first.p || (uint64_t)first.len + sp.len != (uint64_t)kept)
+        return;
+    kmm_bam::raw_copy_part(first.p, queue, dst, first.len, lane, lanes);
+    kmm_bam::raw_copy_part(m.d + sp.start, queue, dst + first.len, sp.len, lane, lanes);
+}
+
 // ---- the CPU form (the tests): the same walk, the lanes one after the other ----
 struct CpuScan {
     const uint8_t *d;
@@ -780,6 +914,61 @@ inline uint64_t cpu_raw_keep(const uint8_t *d, const CpuRaw &r, const uint32_t *
             for (uint32_t lane = 0; lane < lanes; ++lane)
                 raw_copy_span(d, r.spans[i], queue, raw_span_dest(tail, block_pre[i / RAW_BLOCK], pre[i]), lane, lanes);
     *kept_recs = recs;
+    return block_pre[n_blocks];
+}
+
+// The keep step of the pair form on the CPU ("record_sam_mates"), as the library runs it over one piece: the spans by entry, the
+// mate check (`lanes` bytes a round), the pair flags, the two-level prefix, the pair copy with `lanes` lanes one after the other.
+// carry[0, carry_len): the waiting mate 1's line (carried = 1) — entry 0.  hits / windows: the n_entries entries of the piece's
+// whole pairs.  Returns the kept bytes; *kept_recs the kept records; *stranger the lowest pair of the piece whose lines are no
+// mates (MATE_NONE: none; nothing is copied then); *odd_span the span of the odd last record (MATE_NONE: none).
+struct CpuMates {
+    uint64_t kept_recs = 0;
+    uint32_t stranger = MATE_NONE, odd_span = MATE_NONE;
+};
+inline uint64_t cpu_raw_mates_keep(const uint8_t *d, const CpuRaw &r, uint32_t carried, const uint8_t *carry, uint32_t carry_len,
+                                   const uint32_t *hits, const uint32_t *windows, uint64_t n_entries, const RkPairRule &rule, uint8_t *queue,
+                                   uint64_t tail, uint32_t lanes, CpuMates &o)
+{
+    const size_t m = r.spans.size(), n_blocks = (m + RAW_BLOCK - 1) / RAW_BLOCK;
+    std::vector<uint32_t> span_of((size_t)r.tot.recs + 1, MATE_NONE);
+    for (size_t i = 0; i < m; ++i)
+        raw_span_of_store(r.spans[i], i, r.tot.recs, span_of.data());
+    const MatePiece mp{d, r.tot.consumed, r.spans.data(), m, span_of.data(), r.tot.recs, carried, carry, carry_len};
+    o = CpuMates();
+    for (uint64_t p = 0; p < n_entries / 2; ++p) {
+        const bool bad = raw_pair_strangers(raw_mate_line(mp, 2 * p), raw_mate_line(mp, 2 * p + 1), lanes, [&](auto f) {
+            uint32_t low = MATE_NONE;
+            for (uint32_t lane = 0; lane < lanes; ++lane) {
+                const uint32_t c = f(lane);
+                low = c < low ? c : low;
+            }
+            return low;
+        });
+        if (bad && (uint32_t)p < o.stranger)
+            o.stranger = (uint32_t)p;
+    }
+    std::vector<uint32_t> kept(m), pre(m), block_pre(n_blocks + 1, 0u);
+    for (size_t b = 0; b < n_blocks; ++b) {
+        uint32_t sum = 0;
+        for (size_t i = b * RAW_BLOCK; i < m && i < (b + 1) * RAW_BLOCK; ++i) {
+            uint32_t recs = 0;
+            bool odd = false;
+            kept[i] = raw_pair_kept_len(mp, r.spans[i], hits, windows, n_entries, rule, recs, odd);
+            pre[i] = sum;
+            sum += kept[i];
+            o.kept_recs += recs;
+            if (odd)
+                o.odd_span = (uint32_t)i;
+        }
+        block_pre[b + 1] = block_pre[b] + sum;
+    }
+    if (o.stranger != MATE_NONE)
+        return 0;
+    for (size_t i = 0; i < m; ++i)
+        if (kept[i])
+            for (uint32_t lane = 0; lane < lanes; ++lane)
+                raw_pair_copy_span(mp, r.spans[i], kept[i], queue, raw_span_dest(tail, block_pre[i / RAW_BLOCK], pre[i]), lane, lanes);
     return block_pre[n_blocks];
 }
 
@@ -1394,6 +1583,93 @@ __global__ void __launch_bounds__(256) k_sam_raw_copy(const uint8_t *__restrict_
             continue;
         const RawSpan sp = spans[i];
         raw_copy_span(d, sp, queue, raw_span_dest(tail0, block_pre[2 * (i / RAW_BLOCK)], pre[i]), lane, 64u);
+    }
+}
+
+// ---- mates kept together in the raw form ("record_sam_mates"): kernels of their own, so that the unpaired forms
+// above stay as they are.  ctl: three control words of the piece — [0] the lowest pair of the piece whose lines are no mates, [1]
+// and [2] the start and the length of the odd last record's line — all ~0 before the launches.
+
+// span_of: one thread per span (grid-stride): the spans by entry (span_of is filled with MATE_NONE first).
+__global__ void __launch_bounds__(256) k_sam_raw_span_of(const RawSpan *__restrict__ spans, uint64_t n_spans, uint64_t n_recs,
+                                                         uint32_t *__restrict__ span_of)
+{
+    const uint64_t threads = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_spans; i += threads)
+        raw_span_of_store(spans[i], i, n_recs, span_of);
+}
+
+// The minimum of v over the wavefront's 64 lanes, in all of them.
+__device__ __forceinline__ uint32_t wave_lowest(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t x = (uint32_t)__shfl_xor((int)v, o);
+        v = x < v ? x : v;
+    }
+    return v;
+}
+
+// names: one wavefront per pair of the piece (grid-stride), 64 bytes of both lines a round (raw_pair_strangers: names are at most
+// 254 bytes and mostly under 40 — one round); every read lies inside a span the flags would accept, or inside the waiting line.
+// The lowest pair of strangers goes to ctl[0].
+__global__ void __launch_bounds__(256) k_sam_raw_pair_names(MatePiece m, uint64_t n_entries, unsigned long long *__restrict__ ctl)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u), n_pairs = n_entries / 2;
+    for (uint64_t pr = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; pr < n_pairs; pr += waves) {
+        const bool strangers = raw_pair_strangers(raw_mate_line(m, 2 * pr), raw_mate_line(m, 2 * pr + 1), 64u,
+                                                  [&](auto f) { return wave_lowest(f(lane)); });
+        if (lane == 0 && strangers)
+            atomicMin(ctl, (unsigned long long)pr);
+    }
+}
+
+// flags, the pair form: as k_sam_raw_flags with raw_pair_kept_len; the thread that meets the odd last record reports its line.
+__global__ void __launch_bounds__(1024) k_sam_raw_pair_flags(MatePiece m, const uint32_t *__restrict__ hits, const uint32_t *__restrict__ windows,
+                                                             uint64_t n_entries, RkPairRule rule, uint32_t *__restrict__ kept,
+                                                             uint32_t *__restrict__ pre, uint32_t *__restrict__ block_bytes,
+                                                             uint32_t *__restrict__ block_recs, unsigned long long *__restrict__ ctl)
+{
+    static_assert(RAW_BLOCK == 1024, "one span per thread of a 1024-thread workgroup");
+    __shared__ unsigned long long s[16];
+    const uint64_t i = (uint64_t)blockIdx.x * RAW_BLOCK + threadIdx.x;
+    uint32_t len = 0, rec = 0;
+    if (i < m.n_spans) {
+        const RawSpan sp = m.spans[i];
+        bool odd;
+        len = raw_pair_kept_len(m, sp, hits, windows, n_entries, rule, rec, odd);
+        if (odd) {
+            ctl[1] = sp.start;
+            ctl[2] = sp.len;
+        }
+    }
+    unsigned long long all;
+    const unsigned long long incl = raw_block_scan((unsigned long long)len | (unsigned long long)rec << 32, s, all);
+    if (i < m.n_spans) {
+        kept[i] = len;
+        pre[i] = (uint32_t)incl - len;
+    }
+    if (threadIdx.x == 0) {
+        block_bytes[blockIdx.x] = (uint32_t)all;
+        block_recs[blockIdx.x] = (uint32_t)(all >> 32);
+    }
+}
+
+// copy, the pair form: one wavefront per kept span (grid-stride): a header line as k_sam_raw_copy moves it, a mate 2 behind its
+// mate 1's line (raw_pair_copy_span).
+__global__ void __launch_bounds__(256) k_sam_raw_pair_copy(MatePiece m, const uint32_t *__restrict__ kept, const uint32_t *__restrict__ pre,
+                                                           const uint32_t *__restrict__ block_pre, const unsigned long long *__restrict__ tail,
+                                                           uint8_t *__restrict__ queue)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64u);
+    const uint64_t tail0 = tail[0];
+    for (uint64_t i = (uint64_t)blockIdx.x * (blockDim.x / 64u) + threadIdx.x / 64u; i < m.n_spans; i += waves) {
+        const uint32_t k = kept[i];
+        if (k == 0)
+            continue;
+        raw_pair_copy_span(m, m.spans[i], k, queue, raw_span_dest(tail0, block_pre[2 * (i / RAW_BLOCK)], pre[i]), lane, 64u);
     }
 }
 #endif

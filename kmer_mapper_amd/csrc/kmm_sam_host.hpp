@@ -1,7 +1,8 @@
 // kmm_sam_host.hpp — part of libkmm (MI355X / gfx950); included by kmm.hip inside an anonymous namespace, once the stages,
 // map_records_piece, map_records_radix_call, selection_of and the keep queue's helpers (rkq_reserve, keep_entries_last, rk_rule,
 // RkCallMode) are defined.  Host side of the SAM front end of kmm_map_records: one piece counted, checked, written as text and
-// mapped (map_sam_piece), and its raw form that keeps the records' own lines (sam_raw_piece).  The kernels are in kmm_sam.hpp.
+// mapped (map_sam_piece), its raw form that keeps the records' own lines (sam_raw_piece) and the pair form of that
+// (sam_raw_mates_piece, SamMatesUndo).  The kernels are in kmm_sam.hpp.
 #pragma once
 
 // The raw form of one counted and checked SAM piece ("record_sam"), in place of map_sam_piece's plain write and map:
@@ -89,6 +90,222 @@ int sam_raw_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, int64_t n_byt
     KMMCHK(tm.end());
     HIPCHK(hipGetLastError());
     q.bound += (int64_t)h.consumed;
+    return KMM_OK;
+}
+
+// "The stream ends with an unpaired record" (DESIGN 4.28): a mate 1 waits when the stream's last call has nothing more for it.
+int sam_unpaired_end(const char *who, int64_t n_selected)
+{
+    return fail(KMM_ERR_MALFORMED, "%s: \"record_sam_mates\" is 1 and the stream ends with an unpaired record: it holds %lld selected "
+                "records, the last one has no mate (a selection that removes one mate of a pair is an error here; nothing of the call "
+                "is appended)", who, (long long)n_selected);
+}
+
+// What a KMM_FORMAT_SAM call of the pair form has changed in the handle beyond the queues, taken back on every way out while
+// `armed`: the SAM counters, the pair ordinal, and the waiting mate, which the first piece that replaces it moves to the *_call0
+// buffers.  The failure's message stays.
+struct SamMatesUndo {
+    kmm_index_t *ix;
+    bool on;
+    int64_t records0, excluded0, headers0, pairs0;
+    bool armed = true;
+
+    explicit SamMatesUndo(kmm_index_t *ix_, bool on_)
+        : ix(ix_), on(on_), records0(ix_->sam_records), excluded0(ix_->sam_excluded), headers0(ix_->sam_header_lines), pairs0(ix_->sam_pairs_done)
+    {
+        if (on)
+            ix->sam_mate_saved = false;
+    }
+    ~SamMatesUndo()
+    {
+        if (!on)
+            return;
+        if (armed) {
+            ix->sam_records = records0;
+            ix->sam_excluded = excluded0;
+            ix->sam_header_lines = headers0;
+            ix->sam_pairs_done = pairs0;
+            if (ix->sam_mate_saved) {
+                std::swap(ix->sam_mate, ix->sam_mate_call0);
+                std::swap(ix->sam_mate_line, ix->sam_mate_line_call0);
+                ix->sam_mate_len = ix->sam_mate_len_call0;
+                ix->sam_mate_line_len = ix->sam_mate_line_len_call0;
+            }
+        }
+        ix->sam_mate_saved = false;
+    }
+};
+
+// The pair form of sam_raw_piece ("record_sam_mates"): the selected records of the stream are mates 2p and 2p + 1.
+// The write walk puts the piece's FASTA text BEHIND the text of the mate 1 that the piece or call before left over, and the inner
+// piece call takes both in the pair form — whole pairs of entries, no text appended (rk_mates_call with rk_raw_call, as
+// bam_map_raw_mates).  Then, over the spans the write walk left: the spans by entry, the mate check on the lines' own QNAME bytes,
+// the pair flags (which report the odd last record), ONE read-back (strangers, the odd record), the block scan, the pair copy, the
+// tail's advance.  The odd last record's text and line go to the spare buffers and become the waiting mate once nothing of the
+// piece can fail any more.  A piece without a selected record leaves the waiting mate alone and still writes its header lines.
+int sam_raw_mates_piece(kmm_index_t *ix, Stage &s, const uint8_t *d_raw, int64_t n_bytes, uint64_t n_tiles, dim3 gw, const kmm_sam::Totals &h,
+                        bool selected, const kmm_sel::Sel &sel, int k, int max_freq, int also_revcomp, const uint8_t *lut, int64_t *n_records)
+{
+    using kmm_sam::RawSpan;
+    const bool headers = ix->record_sam == 1;
+    const uint64_t n_spans = h.recs + (headers ? h.headers : 0ull);
+    if (n_spans == 0)
+        return KMM_OK;
+    const int64_t carry = ix->sam_mate_len, line_carry = ix->sam_mate_line_len, pairs0 = ix->sam_pairs_done;
+    const uint32_t carried = carry > 0 ? 1u : 0u;
+    if (carried && (line_carry < 1 || line_carry > 0x7FFFFFFFll))
+        return fail(KMM_ERR_INTERNAL, "kmm_map_records: a mate 1 waits with %lld bytes of text and a line of %lld bytes", (long long)carry,
+                    (long long)line_carry);
+    const uint32_t carry_len = carried ? (uint32_t)line_carry : 0u;
+    const int64_t n_rec = (int64_t)h.recs + carried, n_text = carry + (int64_t)h.out_bytes;
+    const uint64_t n_entries = h.recs > 0 ? (uint64_t)(n_rec & ~(int64_t)1) : 0ull; // (no selected record: the waiting mate stays)
+    const bool odd = h.recs > 0 && (n_rec & 1) != 0;
+    kmm_index::RkQueue &q = ix->rkq[0];
+    const uint64_t n_blocks = (n_spans + kmm_sam::RAW_BLOCK - 1) / kmm_sam::RAW_BLOCK;
+    const uint64_t n_tblocks = (n_tiles + kmm_sam::RAW_BLOCK - 1) / kmm_sam::RAW_BLOCK;
+    // (the layout of sam_raw_piece)
+    const size_t off_tile = (size_t)n_spans * 16, off_kept = off_tile + (size_t)n_tiles * 8, off_blk = off_kept + (size_t)n_spans * 8,
+                 off_tblk = off_blk + (size_t)n_blocks * 16, off_tot = (off_tblk + (size_t)n_tblocks * 16 + 15) & ~(size_t)15;
+    KMMCHK(ensure(ix->sam_raw, off_tot + 64));
+    KMMCHK(ensure(ix->sam_span_of, ((size_t)h.recs + 1) * 4 + 64));
+    KMMCHK(ensure(ix->sam_mates_ctl, 64));
+    KMMCHK(ensure(s.kmers, (size_t)n_bytes + (size_t)carry + 16)); // (the piece's text behind the waiting mate's)
+    KMMCHK(rkq_reserve(ix, q, (int64_t)h.consumed + (int64_t)carry_len));
+    uint8_t *w = (uint8_t *)ix->sam_raw.p;
+    RawSpan *spans = (RawSpan *)w;
+    uint32_t *tile_pre = (uint32_t *)(w + off_tile), *kept = (uint32_t *)(w + off_kept), *pre = kept + n_spans;
+    uint32_t *blk_bytes = (uint32_t *)(w + off_blk), *blk_recs = blk_bytes + n_blocks, *blk_pre = blk_recs + n_blocks;
+    uint32_t *tblk_recs = (uint32_t *)(w + off_tblk), *tblk_hdrs = tblk_recs + n_tblocks, *tblk_pre = tblk_hdrs + n_tblocks;
+    unsigned long long *tot = (unsigned long long *)(w + off_tot);
+    uint32_t *span_of = (uint32_t *)ix->sam_span_of.p;
+    unsigned long long *ctl = (unsigned long long *)ix->sam_mates_ctl.p;
+    const kmm_sam::Tile *tiles = (const kmm_sam::Tile *)ix->sam_tiles.p;
+    const unsigned long long *base = (const unsigned long long *)ix->sam_base.p;
+    uint8_t *text = (uint8_t *)s.kmers.p, *out = text + carry;
+    hipStream_t cs = ix->stream;
+    const uint64_t nb = (uint64_t)n_bytes;
+    const kmm_sam::MatePiece mp{d_raw, h.consumed, spans, n_spans, span_of, h.recs, carried,
+                                carried ? (const uint8_t *)ix->sam_mate_line.p : nullptr, carry_len};
+    {
+        ScopedTimer tm;
+        KMMCHK(tm.begin(ix, KMM_KERNEL_SAM_RAW_MATES));
+        HIPCHK(hipMemsetAsync(spans, 0, (size_t)n_spans * 16, cs));
+        HIPCHK(hipMemsetAsync(span_of, 0xFF, ((size_t)h.recs + 1) * 4, cs));
+        HIPCHK(hipMemsetAsync(ctl, 0xFF, 24, cs));
+        hipLaunchKernelGGL(kmm_sam::k_sam_raw_tiles, dim3((unsigned)n_tblocks), dim3(1024), 0, cs, tiles, n_tiles, tile_pre, tblk_recs, tblk_hdrs);
+        hipLaunchKernelGGL(kmm_sam::k_sam_raw_scan, dim3(1), dim3(1024), 0, cs, (const uint32_t *)tblk_recs, (const uint32_t *)tblk_hdrs,
+                           n_tblocks, tblk_pre, (unsigned long long *)nullptr);
+        KMMCHK(tm.end());
+    }
+    if (carried)
+        HIPCHK(hipMemcpyAsync(text, ix->sam_mate.p, (size_t)carry, hipMemcpyDeviceToDevice, cs));
+    const uint32_t hd = headers ? 1u : 0u;
+    if (selected && ix->original_strand)
+        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_rev_sel, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, sel, tiles, base, out,
+                           ix->stats + KMM_STAT_REC_REVERSED, (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
+    else if (selected)
+        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_sel, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, sel, tiles, base, out,
+                           (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
+    else if (ix->original_strand)
+        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans_rev, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, (uint32_t)ix->bam_excl, tiles, base, out,
+                           ix->stats + KMM_STAT_REC_REVERSED, (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
+    else
+        hipLaunchKernelGGL(kmm_sam::k_sam_write_spans, gw, dim3(256), 0, cs, d_raw, nb, n_tiles, (uint32_t)ix->bam_excl, tiles, base, out,
+                           (const uint32_t *)tile_pre, (const uint32_t *)tblk_pre, hd, spans, n_spans);
+    HIPCHK(hipGetLastError());
+    {
+        ScopedTimer tm;
+        KMMCHK(tm.begin(ix, KMM_KERNEL_SAM_RAW_MATES));
+        hipLaunchKernelGGL(kmm_sam::k_sam_raw_span_of, dim3((unsigned)grid_for(ix, (int64_t)((n_spans + 255) / 256), 16)), dim3(256), 0, cs,
+                           (const RawSpan *)spans, n_spans, h.recs, span_of);
+        if (n_entries > 0)
+            hipLaunchKernelGGL(kmm_sam::k_sam_raw_pair_names, dim3((unsigned)grid_for(ix, (int64_t)((n_entries / 2 + 3) / 4), 16)), dim3(256), 0,
+                               cs, mp, n_entries, ctl);
+        KMMCHK(tm.end());
+        HIPCHK(hipGetLastError());
+    }
+    int64_t taken = 0;
+    if (n_entries > 0) {
+        // carry + piece as two-line FASTA in the pair form: whole pairs of entries, no text appended, no name lines compared (the
+        // pair ordinal that form advances is kmm_map_bam's: it is put back, this stream has its own)
+        const int64_t bam_pairs0 = ix->bam_pairs_done;
+        int rc;
+        {
+            const RkCallMode mode(ix, true, true);
+            rc = map_records_piece(ix, text, n_text, KMM_FORMAT_FASTA2, k, max_freq, also_revcomp, lut, &taken, n_records);
+        }
+        ix->bam_pairs_done = bam_pairs0;
+        KMMCHK(rc);
+        if (*n_records != (int64_t)n_entries || (!odd && taken != n_text) || taken > n_text)
+            return fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %lld written bytes, %lld of %lld records mapped as pairs", (long long)taken,
+                        (long long)n_text, (long long)*n_records, (long long)n_rec);
+    }
+    KeepEntries e; // (the inner call's entries; none: the kernels read none — the entry bound comes first — and the pointers are null)
+    if (!keep_entries_last(ix, n_entries, e))
+        return fail(KMM_ERR_INTERNAL, "kmm_map_records: %llu entries of the SAM piece and %lld entries pending", (unsigned long long)n_entries,
+                    (long long)ix->rhq_pending);
+    const RkPairRule rule = rk_pair_rule(ix);
+    unsigned long long *tail = (unsigned long long *)q.ctl.p;
+    unsigned long long h_ctl[3] = {~0ull, ~0ull, ~0ull};
+    ScopedTimer tm;
+    KMMCHK(tm.begin(ix, KMM_KERNEL_SAM_RAW_MATES));
+    hipLaunchKernelGGL(kmm_sam::k_sam_raw_pair_flags, dim3((unsigned)n_blocks), dim3(1024), 0, cs, mp, e.hits, e.windows, n_entries, rule, kept,
+                       pre, blk_bytes, blk_recs, ctl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_ctl, ctl, 24, hipMemcpyDeviceToHost, cs));
+    HIPCHK(hipStreamSynchronize(cs));
+    if (h_ctl[0] != ~0ull) {
+        (void)tm.end();
+        const long long p = (long long)(pairs0 + (int64_t)h_ctl[0]);
+        return fail(KMM_ERR_MALFORMED, "kmm_map_records: \"record_sam_mates\" is 1 and pair %lld of the stream is none: selected records "
+                    "%lld and %lld are not mates (their QNAME bytes differ): group the file by name (an aligner's own output, or "
+                    "`samtools collate`) and exclude secondary and supplementary records (0x900) (nothing of the call is appended)", p,
+                    2 * p, 2 * p + 1);
+    }
+    if (odd != (h_ctl[1] != ~0ull) || (odd && (h_ctl[1] >= h.consumed || h_ctl[2] == 0 || h_ctl[2] > h.consumed - h_ctl[1]))) {
+        (void)tm.end();
+        return fail(KMM_ERR_INTERNAL, "kmm_map_records: %lld selected SAM records with the waiting one, the odd last one reported at %llu "
+                    "(%llu bytes)", (long long)n_rec, h_ctl[1], h_ctl[2]);
+    }
+    const int64_t left = odd ? n_text - taken : 0;
+    if (odd) {
+        // the odd last record's text (what the inner call left) and line go to the SPARE buffers, before anything is appended
+        if (left <= 0) {
+            (void)tm.end();
+            return fail(KMM_ERR_INTERNAL, "kmm_map_records: the odd last SAM record left %lld bytes of text", (long long)left);
+        }
+        KMMCHK(ensure(ix->sam_mate_next, (size_t)left + 64)); // (may free and reallocate: a device-wide sync, rare)
+        KMMCHK(ensure(ix->sam_mate_line_next, (size_t)h_ctl[2] + 64));
+        HIPCHK(hipMemcpyAsync(ix->sam_mate_next.p, text + taken, (size_t)left, hipMemcpyDeviceToDevice, cs));
+        HIPCHK(hipMemcpyAsync(ix->sam_mate_line_next.p, d_raw + h_ctl[1], (size_t)h_ctl[2], hipMemcpyDeviceToDevice, cs));
+    }
+    hipLaunchKernelGGL(kmm_sam::k_sam_raw_scan, dim3(1), dim3(1024), 0, cs, (const uint32_t *)blk_bytes, (const uint32_t *)blk_recs,
+                       n_blocks, blk_pre, tot);
+    hipLaunchKernelGGL(kmm_sam::k_sam_raw_pair_copy, dim3((unsigned)grid_for(ix, (int64_t)((n_spans + 3) / 4), 16)), dim3(256), 0, cs, mp,
+                       (const uint32_t *)kept, (const uint32_t *)pre, (const uint32_t *)blk_pre, (const unsigned long long *)tail,
+                       (uint8_t *)q.text.p);
+    hipLaunchKernelGGL(kmm_bam::k_bam_raw_advance, dim3(1), dim3(64), 0, cs, tail, (const unsigned long long *)tot);
+    KMMCHK(tm.end());
+    HIPCHK(hipGetLastError());
+    q.bound += (int64_t)h.consumed + (int64_t)carry_len;
+    ix->sam_pairs_done = pairs0 + (int64_t)n_entries / 2;
+    // the next waiting mate: nothing from here on can fail.  The one the call found goes to the *_call0 buffers first (the kernels
+    // that read it are queued in front of whatever writes a buffer next); a call that fails later swaps it back.
+    if (h.recs > 0) {
+        if (!ix->sam_mate_saved) {
+            std::swap(ix->sam_mate, ix->sam_mate_call0);
+            std::swap(ix->sam_mate_line, ix->sam_mate_line_call0);
+            ix->sam_mate_len_call0 = carry;
+            ix->sam_mate_line_len_call0 = line_carry;
+            ix->sam_mate_saved = true;
+        }
+        if (odd) {
+            std::swap(ix->sam_mate, ix->sam_mate_next);
+            std::swap(ix->sam_mate_line, ix->sam_mate_line_next);
+        }
+        ix->sam_mate_len = left;
+        ix->sam_mate_line_len = odd ? (int64_t)h_ctl[2] : 0;
+    }
     return KMM_OK;
 }
 
@@ -191,6 +408,8 @@ int map_sam_piece(kmm_index_t *ix, const uint8_t *raw, int64_t n_bytes, int64_t 
             if (rc == KMM_OK && (used != (int64_t)h.out_bytes || *n_records != (int64_t)h.recs))
                 rc = fail(KMM_ERR_INTERNAL, "SAM chunk: %lld of %llu written bytes, %lld of %llu records mapped", (long long)used,
                           h.out_bytes, (long long)*n_records, h.recs);
+        } else if (sam_raw_mates_on(ix)) {
+            rc = sam_raw_mates_piece(ix, s, d_raw, n_bytes, n_tiles, gw, h, selected, sel, k, max_freq, also_revcomp, lut, n_records);
         } else if (sam_raw_on(ix)) {
             rc = sam_raw_piece(ix, s, d_raw, n_bytes, n_tiles, gw, h, selected, sel, k, max_freq, also_revcomp, lut, n_records);
         } else if (h.recs > 0) {

@@ -458,13 +458,22 @@ class DeviceIndex:
         if on and mates:
             self.set_param("record_bam_mates", 1)
 
-    def record_sam(self, on=True, header=True):
+    def record_sam(self, on=True, header=True, mates=False):
         """SAM lines kept as SAM lines (include/kmm.h), on top of record_hits() and record_keep(): a SAM call
         (map_records, map_bgzf, map_gzip with FORMAT_SAM) maps the selected records as without the switch and appends every kept
         record's WHOLE LINE, untouched, to the queue of take_kept_records() / take_kept_bgzf(); header=True: every header line
         too, at its place in the stream; False: none (shares that are concatenated).  The other formats never read it.  Refused
-        while kept bytes are pending."""
+        while kept bytes are pending.
+        mates: the selected records of the stream are mates in file order — 2p and 2p + 1, as an aligner writes
+        them — kept or dropped together under record_pairs()'s rule, mate 1 directly in front of mate 2; their QNAME bytes are
+        compared on the GPU and a pair of strangers, or (with FORMAT_LAST_CHUNK / last=True) an unpaired last record, fails the
+        call.  get_param("record_sam_mate_waiting") tells whether a mate 1 waits for the next call.  Refused while hit entries
+        or kept bytes are pending."""
+        if not (on and mates):
+            self.set_param("record_sam_mates", 0)
         self.set_param("record_sam", (1 if header else 2) if on else 0)
+        if on and mates:
+            self.set_param("record_sam_mates", 1)
 
     def take_kept_records(self, out=None):
         """kmm_take_kept_records: ALL pending bytes — the kept records, whole, in stream order — as (np.uint8 array, n_records);

@@ -164,7 +164,8 @@ def record_hits(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, 
 
 def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, min_hits=1,
                    min_permille=0, invert=False, device=0, exclude_flags=0, original_strand=False, mate_suffix=False, compress=False, pairs=False,
-                   pair_rule="any", output="fastq", keep_mates=False, header=True, min_base_quality=0, use_record_qual=False):
+                   pair_rule="any", output="fastq", keep_mates=False, header=True, min_base_quality=0, use_record_qual=False,
+                   sam_mates=False):
     """Extension: record_hits that also hands back the reads it selects — `raw` as in record_hits (fmt "fastq" or "fasta"; SAM
     text does not carry the read's name through the device-side decode and is refused).  A record is kept iff
     (hits >= min_hits and 1000 * hits >= min_permille * windows) != invert.  Returns (text, hits, windows): the kept records'
@@ -191,9 +192,15 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
     Records whose FLAG has any of exclude_flags are not written; original_strand applies to the hits alone; compress: a complete
     BGZF file (htslib reads it as .sam.gz).  The bytes behind the last newline are not looked at (len(text) tells with
     min_hits=0).  mate_suffix, pairs and keep_mates do not go with it.
+    sam_mates (output "sam"): the text is grouped by name, as aligners write it — its selected records are mates in
+    file order — and both lines of a pair are kept or dropped together under pair_rule, mate 1 directly in front of mate 2; the
+    entries lie in pair order.  Neighbours whose QNAME bytes differ, or an unpaired last record, raise ValueError with the
+    library's hint (group by name; exclude secondary and supplementary records, 0x900).
     min_base_quality: the floor of record_hits — it changes which records pass the rule, never the text that comes
     back; fmt "bam" needs use_record_qual=True (records that store no qualities pass unmasked); output "sam" does not go with it."""
     from . import _lib
+    if sam_mates and output != "sam":
+        raise ValueError("sam_mates goes with output=\"sam\": mates kept together as SAM lines (BAM out: keep_mates=True)")
     if output == "sam" and min_base_quality:
         raise ValueError("output=\"sam\" does not go with min_base_quality: SAM lines kept as SAM lines are mapped without their QUAL "
                          "column")
@@ -203,8 +210,10 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
         if mate_suffix or pairs or keep_mates:
             raise ValueError("output=\"sam\" does not go with mate_suffix, pairs or keep_mates: the lines are written as they stand, in "
                              "file order")
+        if pair_rule not in ("any", "both"):
+            raise ValueError("pair_rule must be 'any' or 'both', not %r" % (pair_rule,))
         return _select_sam_lines(index, raw, k, max_index_lookup_frequency, also_revcomp, lut, min_hits, min_permille, invert, device,
-                                 exclude_flags, original_strand, compress, header)
+                                 exclude_flags, original_strand, compress, header, sam_mates, pair_rule)
     if keep_mates and output != "bam":
         raise ValueError("keep_mates goes with output=\"bam\": mates kept together as BAM records (FASTQ out: pairs=True)")
     if output not in ("fastq", "bam"):
@@ -276,9 +285,9 @@ def select_records(index, raw, fmt="fastq", k=31, max_index_lookup_frequency=100
 
 
 def _select_sam_lines(index, raw, k, max_index_lookup_frequency, also_revcomp, lut, min_hits, min_permille, invert, device, exclude_flags,
-                      original_strand, compress, header):
+                      original_strand, compress, header, mates=False, pair_rule="any"):
     """select_records(fmt="sam", output="sam"): DeviceIndex.record_sam around one map_records call; the cached handle is left as it
-    was found."""
+    was found.  mates: the pair form — `raw` is the whole stream, an unpaired last record fails the call."""
     from . import _lib
     if isinstance(raw, (bytes, bytearray, memoryview)):
         raw = np.frombuffer(bytes(raw), dtype=np.uint8)
@@ -286,14 +295,16 @@ def _select_sam_lines(index, raw, k, max_index_lookup_frequency, also_revcomp, l
     dev = _device_index(index, max_node_id, device)
     if dev.get_param("record_hits_pending") or dev.get_param("record_keep_pending_bytes"):
         raise ValueError("the cached handle has record hits or kept records pending: take them first")
-    before = (dev.get_param("bam_exclude_flags"), dev.get_param("original_strand"))
+    before = (dev.get_param("bam_exclude_flags"), dev.get_param("original_strand"), dev.get_param("record_pairs_rule"))
     dev.record_hits(True, windows=True)
     dev.record_keep(True, min_hits=min_hits, min_permille=min_permille, invert=invert)
-    dev.record_sam(True, header=header)
+    dev.record_sam(True, header=header, mates=mates)
     try:
         dev.set_param("bam_exclude_flags", int(exclude_flags))
         dev.set_param("original_strand", int(bool(original_strand)))
-        dev.map_records(raw, fmt=_lib.FORMAT_SAM, k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp,
+        if mates:
+            dev.set_param("record_pairs_rule", dev.PAIR_RULES[pair_rule])
+        dev.map_records(raw, fmt=_lib.FORMAT_SAM | (_lib.FORMAT_LAST_CHUNK if mates else 0), k=k, max_index_lookup_frequency=max_index_lookup_frequency, also_revcomp=also_revcomp,
                         lut=lut)
         hits, windows = dev.take_record_hits()
         if compress:
@@ -304,9 +315,12 @@ def _select_sam_lines(index, raw, k, max_index_lookup_frequency, also_revcomp, l
     finally:
         if dev.get_param("record_keep_pending_bytes"):                              # (a take that failed: raw lines never meet text)
             dev.take_kept_records()
+        if mates and dev.get_param("record_hits_pending"):                          # (a take that failed: the switch stays with its entries)
+            dev.take_record_hits()
         dev.record_sam(False)
         dev.set_param("bam_exclude_flags", before[0])
         dev.set_param("original_strand", before[1])
+        dev.set_param("record_pairs_rule", before[2])
         dev.record_keep(False)
         dev.record_hits(False)
     return text, hits, windows
