@@ -32,6 +32,7 @@
 
 #include "kmm.h"
 #include "kmm_radix_plan.hpp" // (plain C++ with standard headers of its own: before the namespace the kernels live in)
+#include "kmm_params.hpp"     // (the same: KmmKnobs, KmmCounters and the parameter table)
 
 namespace {
 
@@ -301,13 +302,12 @@ struct RxArrays : RxDir16, RxSlotFilter {
     DevPtr<uint32_t> rx_occ;   // bit h = bucket h holds an entry: pass 2's empty-bucket filter (k_rx_p2f); optional
 };
 
-struct kmm_index : IndexStreams, RxArrays {
+struct kmm_index : IndexStreams, RxArrays, KmmKnobs, KmmCounters { // (the stored parameter values and the counters: kmm_params.hpp)
     int device = 0;
     Event copied;
     DevPtr<uint4> buckets;
     DevPtr<uint4> entries;
     DevPtr<uint32_t> occ;              // occupancy bitmap, only for indexes small enough (see occ_max_bytes)
-    bool use_occ = true;
     int occ_shift = 0;                 // log2(bitmap bits per bucket)
     uint32_t bloom_words = 0;          // != 0: occ is a word-blocked Bloom filter
     bool wide = false;                 // 32-byte buckets (chosen when the index is too large for the bitmap)
@@ -324,39 +324,26 @@ struct kmm_index : IndexStreams, RxArrays {
     DevPtr<unsigned long long> first_bad;
     DevPtr<unsigned long long> stats;
     DevPtr<unsigned long long> queue;    // tile counter of the dynamic schedule
-    bool dynamic_schedule = true;
-    int dyn_chunk = 16;                  // tiles per grab
     uint64_t modulo = 0, magic = 0;
     int64_t n_entries = 0, max_node_id = 0;
     Stage stage[2];
     int cur = 0;
     int n_cu = 256;
-    // path selection / radix path state (kmm_radix.hpp)
-    int path = 0;         // 0 auto, 1 direct, 2 radix
-    int grid_per_cu = 64; // upper bound on workgroups per CU of the grid-stride fused kernel
+    // radix path state (kmm_radix.hpp)
     bool rx_ok = false;   // the index fits the radix path's fan-out (<= 512 x 512 fine partitions)
     RxGeometry rx_geo;    // slice width and fan-out (kmm_radix_plan.hpp); assigned whole, a refused configuration leaves it as it was
     bool rx_no_mid = false; // experiments (KMM_RX_NO_MID, read at creation): pass 3 without its 4608-key variants
-    bool rx_flush_sorted = true; // "radix_sorted_flush": use the node-ordered entry list for the flush
     uint32_t rx_max_slice = 0; // most entries in one fine partition's slice (for the current part_shift)
     bool rx_fits_small = false, rx_fits_mid = false; // all but one slice in 1000 hold at most RX_ECAP / RX_ECAP_MID entries
-    int rx_grid_per_cu = 2;   // persistent workgroups of passes 2 and 3 per CU (1: leave room for another stream's kernels)
-    int64_t rx_min_units = 0; // auto: batches of at least this many positions / k-mers take the radix path
-    int64_t rx_sub_cap = RX_SUB_CAP_MAX; // k-mer slots per sub-batch of the radix path ("radix_sub_batch_kmers")
     int64_t rx_sub_cap_eff = 0;  // > 0: the smaller size an out-of-memory call settled on, tried first by the next calls
     int rx_sub_cap_eff_age = 0;  // calls since then (at 16 the caller's cap is tried again)
-    int64_t rx_sub_cap_last = 0; // the size the last radix call ran with ("radix_sub_batch_kmers_effective")
     const uint32_t *dbg_T1 = nullptr, *dbg_item_base = nullptr; // the latest sub-batch's tables (debug_rx_* parameters)
     const uint16_t *dbg_start1 = nullptr;
     uint32_t dbg_F1 = 0, dbg_NB = 0;
-    int host_pack_threads = 0;     // "host_pack_threads": reads / raw records in host memory are packed to 2 bits per base by that
-                                   // many host threads before they cross PCIe (default: min(16, the process's CPU budget))
-    std::unique_ptr<kmm_hostpack::Workers> pack_pool; // the packing threads, asleep between calls
+    std::unique_ptr<kmm_hostpack::Workers> pack_pool; // the packing threads ("host_pack_threads"), asleep between calls
     PinnedBuf pack_pinned;          // page-locked home of a packed records batch (kmm_hostpack.hpp)
     PinnedBuf ring[RING_SLOTS];     // the page-locked staging ring (ensure_ring)
     PinnedBuf pack_bits_pinned;     // ... and of the read-start bitset of packed raw records
-    int64_t host_packed_calls = 0, host_packed_record_calls = 0;
-    int64_t host_pack_slice_kb = 0; // "host_pack_slice_kb": raw bytes per slice of the records packer (0: its default)
     // kmm_map_bgzf: BGZF members inflated on the GPU (kmm_gpu_inflate.hpp).  Two sets of buffers in turn (the copy of call
     // i + 1 runs under the kernels of call i); the uncompressed bytes behind a call's last complete record wait in `carry`
     // for the next call.
@@ -371,10 +358,7 @@ struct kmm_index : IndexStreams, RxArrays {
     const uint8_t *bgzf_pre_from = nullptr, *bgzf_hint_ptr = nullptr;
     int64_t bgzf_pre_n = 0, bgzf_hint_n = 0;
     int bgzf_pre_buf = 0;
-    int64_t bgzf_prestaged_calls = 0;
-    int64_t bgzf_head_skip = 0;  // "bgzf_head_skip": inflated bytes of the next NEW_STREAM call's first member that belong to someone else
-    int64_t bgzf_tail_stop = -1; // "bgzf_tail_stop": >= 0: of the next LAST_CHUNK call's last member only this many inflated bytes are taken
-    int64_t bgzf_calls = 0, bgzf_members = 0;
+    int64_t bgzf_calls = 0;
     // kmm_map_gzip: a plain gzip stream inflated on the GPU (kmm_gpu_gunzip.hpp).  The symbol slots come from an arena of
     // large blocks kept from call to call (a bump pointer per call); the stream's state (bit offset, mode, history length,
     // CRC register and length of the member in progress) and its last 32 KiB of output (gz_window) carry over.
@@ -384,61 +368,34 @@ struct kmm_index : IndexStreams, RxArrays {
     kmm_gunzip::StreamState gz_state;
     int64_t gz_carry_len = 0;
     double gz_ratio = 4.0;        // inflated / compressed bytes of the stream so far (the slots' size)
-    int64_t gzip_calls = 0, gzip_members = 0, gzip_chunks = 0, gzip_false_starts = 0, gzip_continuations = 0, gzip_inflated = 0;
-    int dbg_gzip_chunk_kb = 0;    // test hook ("debug_gzip_chunk_kb"): spacing of the chunk search, KiB (0: 32)
     // kmm_map_bam: the BGZF members of a BAM file inflated as for kmm_map_bgzf, the records found and decoded on the GPU
     // (kmm_bam.hpp): the tiles' claims (two buffers: the link passes read one and write the other), the control words, the
     // tiles' output offsets and the two-line FASTA the records become.  The stream's reference count (from its header)
     // validates refID / next_refID of every record.
     DevBuf bam_tiles[2], bam_bad, bam_base, bam_ctl, bam_out;
     int32_t bam_n_ref = -1;       // -1: no BAM stream started on this handle
-    uint32_t bam_excl = 0;        // "bam_exclude_flags": records with flag & mask are not mapped (samtools view -F)
-    int64_t bam_calls = 0, bam_records = 0, bam_excluded = 0, bam_header_bytes = 0, bam_false_starts = 0, bam_continuations = 0;
     // kmm_bam_header / kmm_bam_find_record_start (a rank's share of a BAM file): buffers of their own — the compressed
     // window, its inflated bytes, the member offsets, the inflater's error words and status bytes — so that a stream in
     // progress on the handle is not touched
     DevBuf rs_comp, rs_raw, rs_meta, rs_err, rs_status;
-    int64_t bam_n_ref_param = -1;     // "bam_n_ref": n_ref of a KMM_FORMAT_MID_STREAM stream (-1: not set)
-    int64_t dbg_bam_resync_kb = 0;    // test hook ("debug_bam_resync_kb"): inflated bytes kmm_bam_find_record_start examines at most, KiB (0: all)
-    int64_t dbg_bgzf_call_cap_kb = 0; // test hook ("debug_bgzf_call_cap_kb"): inflated bytes a kmm_map_bgzf / kmm_map_bam call
-                                      // takes at most, KiB (0: 3.5 GiB)
-    int64_t flat_uniform_batches = 0; // flat reads mapped by the uniform / packed front ends of the radix path (rec_launch_flat)
     // KMM_FORMAT_SAM (kmm_sam.hpp): the tiles' line counts, their output offsets, the totals; the filter is bam_excl
     DevBuf sam_tiles, sam_base, sam_ctl;
-    int64_t sam_calls = 0, sam_records = 0, sam_excluded = 0, sam_header_lines = 0;
     // record selection (kmm_select.hpp): "bam_include_flags", "bam_min_mapq" and the region list of
     // kmm_set_record_regions, merged twice — by refID for kmm_map_bam (sel_iv_id; empty when a region came without an id) and by
     // name for KMM_FORMAT_SAM (sel_iv_name, the names in sel_names; empty when one came without a name) — and held in one small
     // device buffer: the two interval lists, the name offsets, the name bytes
-    uint32_t bam_incl = 0, bam_min_mapq = 0;
     int sel_n_regions = 0, sel_keep_unplaced = 0; // regions as given (0: no list)
     std::vector<kmm_sel::Interval> sel_iv_id, sel_iv_name;
     std::vector<std::string> sel_names;
     DevBuf sel_buf;
     size_t sel_off_name_iv = 0, sel_off_name_off = 0, sel_off_names = 0;
-    int dbg_bgzf_slot_kb = 0;     // test hook ("debug_bgzf_ring_slot_kb"): slot size of kmm_map_bgzf's staging ring (a power of two, >= 4)
-    int64_t dbg_rx_buf_limit = 0; // test hook ("debug_rx_buffer_limit"): a pass-1 buffer beyond this many bytes counts as out of memory
-    int dbg_rec_copy_stream = 0; // experiments (tools/records_overlap_bisect.py): compaction kernels on the copy stream again,
-    int dbg_rec_skip = 0;        // and which of them to leave out (1 count2, 2 scans, 4 scatter, 8 uniform, 16 the large memsets)
-    int min_base_quality = 0;    // "min_base_quality": > 0: a FASTQ base whose quality byte is below 33 + this is a break (flat reads: 4.11)
-    // "record_hits_min_base_quality": the floor of the record calls while "record_hits" is 1 or 2 — a parameter of
-    // its own: "min_base_quality" with the mode on stays refused.  rq_exempt / rq_text_off: set around the inner records call of
-    // kmm_map_bam's named form — the records that pass unmasked (no stored qualities), by the offset of their quality line in
-    // the inner call's text, and where the piece at work starts in that text.  bam_mate_exempt: the flags of the waiting mate 1.
-    int rh_min_base_quality = 0;
+    // the floor of the record-hits mode ("record_hits_min_base_quality").  rq_exempt / rq_text_off: set around the inner
+    // records call of kmm_map_bam's named form — the records that pass unmasked (no stored qualities), by the offset of their quality
+    // line in the inner call's text, and where the piece at work starts in that text.  bam_mate_exempt: the flags of the waiting mate 1.
     const uint32_t *rq_exempt = nullptr;
     int64_t rq_text_off = 0;
     DevBuf rq_exempt_buf, bam_mate_exempt;
     int64_t bam_mate_exempt_len = 0; // the bytes of waiting text that bam_mate_exempt holds flags for (0: none)
-    int use_record_qual = 0;     // "use_record_qual": 1: with a floor set, SAM / BAM records are mapped with their QUAL
-    int original_strand = 0;     // "original_strand": 1: kept SAM / BAM records with FLAG 0x10 are mapped in read orientation
-    int64_t dbg_rec_piece_kb = 0; // test hook ("debug_records_piece_kb"): bytes per piece of kmm_map_records, KiB (0: 2^30 bytes)
-    int dbg_rec_grid = 0;         // test hook ("debug_records_grid"): workgroups of the compaction's per-tile kernels (0: grid_for)
-    bool rx_filter = true;        // "radix_filter": use the filtering pass 2 whenever a coarse partition's bitmap fits LDS
-    bool rx_filter_slots = true;  // "radix_filter_slots": where the geometry allows it the filter is the slot filter (0: the bucket bitmap)
-    bool rx_p3_fp = true;         // "radix_p3_fingerprints": pass 3 probes through fingerprint bytes where its variant has that form
-    uint32_t dbg_p2f_cap = P2F_SLOTS; // test hook ("debug_p2f_round_slots"): sort-buffer slots k_rx_p2f uses beside the slot filter
-    bool rx_packed = true;        // "radix_packed_tiles": pass 1 on reads of one length takes tiles of whole reads
     bool ecnt_dirty = false;  // rx_ecnt holds hits that are not in `counts` yet
     bool rx_unchecked = false; // radix passes have run since the conservation counters were last compared (drain)
     DevBuf rx_buf1, rx_buf2, rx_meta, rx_probe; // (rx_probe: scratch of the marginal-byte probe builds, kmm_radix.hpp)
@@ -446,11 +403,10 @@ struct kmm_index : IndexStreams, RxArrays {
     int sticky_rc = KMM_OK;
     std::string sticky_msg;
     uint64_t map_calls = 0;   // sequence number of map calls on this handle (error reports name the call)
-    int64_t read_hits_calls = 0; // kmm_read_hits calls that were accepted ("read_hits_calls")
     // the record-hits mode: while "record_hits" is 1 or 2 the record calls append one entry per record to this
     // queue instead of counting nodes.  Entries [rhq_head, rhq_head + rhq_pending) of both arrays wait for
     // kmm_take_record_hits; rhq_mode: the last non-zero "record_hits" (whether the pending entries have their windows)
-    int record_hits = 0, rhq_mode = 0;
+    int rhq_mode = 0;
     DevBuf rhq_hits, rhq_win;
     int64_t rhq_head = 0, rhq_pending = 0, rhq_cap = 0;
     // the record-keep mode: with "record_keep" 1 the record calls also append the text of every record whose entry
@@ -459,12 +415,6 @@ struct kmm_index : IndexStreams, RxArrays {
     // the host knows, an upper bound of the pending bytes (the consumed bytes of the pieces since the last take), which the queue
     // holds room for before a piece's kernels are launched.  rk_tile / rk_super: kept bytes, and behind them kept records, per
     // tile and super-tile of that piece.
-    int record_keep = 0, rk_invert = 0, rk_min_permille = 0;
-    // the named form of the BAM decode: with "record_names" 1 kmm_map_bam, in the record-hits mode, decodes the selected
-    // records into four-line FASTQ that carries QNAME and QUAL (k_bam_*_named) — the text "record_keep" appends;
-    // "record_names_mate_suffix" 1: "/1" / "/2" behind the name
-    int record_names = 0, record_names_mate_suffix = 0;
-    int64_t rk_min_hits = 1;
     // [0]: the queue of kept text; [1]: the mate-2 texts of kmm_map_record_pairs, whose mate-1 texts go to [0]
     struct RkQueue {
         DevBuf text, ctl;
@@ -476,7 +426,6 @@ struct kmm_index : IndexStreams, RxArrays {
     // only while "record_keep" is 1.  rk_snap: what the last kmm_map_records found (entries pending, the bound of rkq[0]; the
     // tail is kept on the device), which a stream call whose last chunk ends with an unpaired record puts back.
     // rk_pair_entries: the per-buffer entries of kmm_map_record_pairs before they are zipped into the queue.
-    int record_pairs = 0, rk_pair_rule = 0;
     struct { int64_t pending = 0, bound = 0; bool valid = false; } rk_snap;
     DevBuf rk_pair_entries;
     // the mates of a name-collated BAM file: "record_names_pairs" 1: the selected records of a kmm_map_bam stream
@@ -485,7 +434,6 @@ struct kmm_index : IndexStreams, RxArrays {
     // of the error reports).  rk_mates_call: set around kmm_map_bam's inner kmm_map_records alone — that call then takes the
     // interleaved pair form without "record_pairs", and every piece has its pairs' names compared (k_rk_pair_names), the first
     // differing pair read back through rk_names_ctl (behind it: the decode's three counters as the call found them).
-    int record_names_pairs = 0;
     bool rk_mates_call = false;
     DevBuf bam_mate, rk_names_ctl;
     int64_t bam_mate_len = 0, bam_pairs_done = 0;
@@ -494,7 +442,6 @@ struct kmm_index : IndexStreams, RxArrays {
     // that call's inner kmm_map_records alone, which then appends its entries but none of the FASTA text.  bam_raw: the record
     // base, the kept bytes' base, the kept bytes and records per tile, the totals.  bam_hdr: the header of the last stream
     // started with KMM_FORMAT_NEW_STREAM, magic through the last reference (kmm_bam_stream_header); bam_hdr_valid: there is one.
-    int record_bam = 0;
     bool rk_raw_call = false, bam_hdr_valid = false;
     DevBuf bam_raw;
     std::vector<uint8_t> bam_hdr;
@@ -504,7 +451,6 @@ struct kmm_index : IndexStreams, RxArrays {
     // in bam_mate (bam_mate_len, as DESIGN 4.23), its raw bytes in bam_raw_mate (bam_raw_mate_len).  bam_raw_ctl: the call's three
     // control words (kmm_bam.hpp k_bam_raw_count_pairs), read back once per window.  bam_raw_pos: where the selected record of
     // every entry of the call starts, left by the count walk for the mate check.
-    int record_bam_mates = 0;
     DevBuf bam_raw_mate, bam_raw_ctl, bam_raw_pos;
     DevBuf bam_mate_next, bam_raw_mate_next; // the spare carry buffers: a call fills them before it appends and swaps them in when it is done
     int64_t bam_raw_mate_len = 0;
@@ -512,7 +458,6 @@ struct kmm_index : IndexStreams, RxArrays {
     // the selected records in the two-line FASTA form (the inner piece call under rk_raw_call: entries, no text) and appends the
     // kept records' own lines to rkq[0]; 1: the header lines as well.  sam_raw: per piece, the tiles' {records, header lines} in
     // front, the spans of the write walk, their kept lengths and prefixes, the blocks' sums and bases, the totals.
-    int record_sam = 0;
     DevBuf sam_raw;
     // mates kept together in SAM output: "record_sam_mates" 1: the selected records of a SAM stream are mates in file
     // order and their lines are kept or dropped together.  The inner piece call runs with rk_mates_call AND rk_raw_call, as under
@@ -521,17 +466,12 @@ struct kmm_index : IndexStreams, RxArrays {
     // fills before it appends and swaps in when it is done; *_call0: the waiting mate as the call found it (sam_mate_saved: it was
     // moved there by a piece of the call), put back by a call that fails.  sam_mates_ctl: a piece's three control words;
     // sam_span_of: its spans by entry.
-    int record_sam_mates = 0;
     DevBuf sam_mate, sam_mate_line, sam_mate_next, sam_mate_line_next, sam_mate_call0, sam_mate_line_call0, sam_mates_ctl, sam_span_of;
     int64_t sam_mate_len = 0, sam_mate_line_len = 0, sam_pairs_done = 0, sam_mate_len_call0 = 0, sam_mate_line_len_call0 = 0;
     bool sam_mate_saved = false;
     BzScratch bz; // kmm_take_kept_bgzf
-    uint64_t n_radix_batches = 0, n_direct_batches = 0; // which path the batches took ("radix_batches" / "direct_batches")
     ncclComm_t comm = nullptr; // multi-process communicator of this handle (kmm_comm_init_rank)
     int comm_rank = -1, comm_size = 0;
-    // flush of node range s under the reduce of node range s - 1 (kmm_comm_reduce_counts): "comm_overlap_slices"
-    int comm_slices = 8;
-    int64_t comm_sliced_reduces = 0; // kmm_comm_reduce_counts calls that issued one reduce per node range ("comm_sliced_reduces")
     Stream comm_stream;
     std::vector<Event> comm_events;
     std::vector<uint64_t> flush_cuts; // entry (node order) where node range s begins, for comm_slices ranges; [slices + 1]
@@ -5091,355 +5031,28 @@ int kmm_set_record_regions(kmm_index_t *ix, const kmm_region_t *regions, int n_r
     });
 }
 
+} // extern "C"
+
+namespace {
+#include "kmm_params_host.hpp" // the rows of the parameter table that need the handle, find_param: behind everything they call
+} // namespace
+
+extern "C" {
+
 int kmm_set_param(kmm_index_t *ix, const char *name, int64_t value)
 {
     if (!ix || !name)
         return fail(KMM_ERR_INVALID_ARG, "NULL argument");
     HIPCHK(hipSetDevice(ix->device));
-    if (strncmp(name, "debug_records_", 14) != 0) // (the overlap experiment sets its switches between two calls in flight)
+    const kmm_params::Row *row = find_param(name);
+    if (!(row && row->no_sync))
         HIPCHK(hipStreamSynchronize(ix->stream)); // scratch layouts depend on the knobs
-    if (!strcmp(name, "path")) {
-        if (value < 0 || value > 2)
-            return fail(KMM_ERR_INVALID_ARG, "path must be 0 (auto), 1 (direct) or 2 (radix)");
-        if (value == 2 && !ix->rx_ok)
-            return fail(KMM_ERR_INVALID_ARG, "the radix path is not available for this index (modulo %llu: needs modulo < 2^31 "
-                        "and slices whose entries fit LDS)", (unsigned long long)ix->modulo);
-        ix->path = (int)value;
-    } else if (!strcmp(name, "part_shift")) {
-        const int rc = rx_reconfigure(ix, (int)value, -1, true);
-        if (rc == RX_REFUSED)
-            return fail(KMM_ERR_INVALID_ARG, "part_shift %lld: needs 0 <= shift <= 13, at most 512 x 512 fine partitions "
-                        "and 2^shift small enough for the quotient of a 64-bit k-mer by the modulo to fit beside "
-                        "the hash bits", (long long)value);
-        KMMCHK(rc);
-    } else if (!strcmp(name, "radix_packed_tiles")) {
-        ix->rx_packed = value != 0;
-    } else if (!strcmp(name, "radix_filter")) {
-        // 1 (default): pass 2 drops the k-mers of empty buckets where a coarse partition's bitmap fits LDS (the
-        // fan-out is chosen for it); 0: the plain pass 2
-        ix->rx_filter = value != 0;
-        if (ix->rx_pstart) { // (the fan-out is derived anew: a forced "fine_bits" is dropped; refused: the old one stays)
-            const int rc = rx_reconfigure(ix, ix->rx_geo.w, -1, false);
-            if (rc != RX_REFUSED)
-                KMMCHK(rc);
-        }
-    } else if (!strcmp(name, "radix_filter_slots")) {
-        // 1 (default): coarse partitions of 2^19 buckets are filtered with 3 bits per bucket pair keyed by bucket and
-        // quotient (rx_filter_slot); 0: with the bucket bitmap, as every other geometry
-        ix->rx_filter_slots = value != 0;
-        if (ix->rx_pstart && ix->rx_ok)
-            KMMCHK(rx_build_slots(ix));
-    } else if (!strcmp(name, "radix_p3_fingerprints")) {
-        // 1 (default): the pass-3 variants that have the fingerprint form of the probe (rx_p3_shape) run it; 0: the plain entry loop
-        ix->rx_p3_fp = value != 0;
-    } else if (!strcmp(name, "debug_p2f_round_slots")) {
-        // test hook of the rounds of k_rx_p2f's placement: sort-buffer slots in use beside the slot filter
-        if (value < 512 || value > P2F_SLOTS || (value & 1))
-            return fail(KMM_ERR_INVALID_ARG, "debug_p2f_round_slots must be even and in [512, %d]", P2F_SLOTS);
-        ix->dbg_p2f_cap = (uint32_t)value;
-    } else if (!strcmp(name, "fine_bits")) {
-        // experiments: split the current slice width's fan-out as F2 = 2^value fine partitions per coarse partition
-        const int rc = value < 0 || value > 9 ? RX_REFUSED : rx_reconfigure(ix, ix->rx_geo.w, (int)value, true);
-        if (rc == RX_REFUSED)
-            return fail(KMM_ERR_INVALID_ARG, "fine_bits %lld: both fan-outs must stay within 512", (long long)value);
-        KMMCHK(rc);
-    } else if (!strcmp(name, "radix_min_units")) {
-        ix->rx_min_units = value;
-    } else if (!strcmp(name, "radix_sub_batch_kmers")) {
-        // k-mer slots per sub-batch of the radix path: at most 2^32 - 2 blocks (launch_rx), at least a few blocks
-        if (value < 4 * RX_B || value > ((int64_t)1 << 32) - 2 * RX_B)
-            return fail(KMM_ERR_INVALID_ARG, "radix_sub_batch_kmers outside [%d, 2^32 - %d]", 4 * RX_B, 2 * RX_B);
-        ix->rx_sub_cap = value;
-        ix->rx_sub_cap_eff = 0;
-    } else if (!strcmp(name, "comm_overlap_slices")) {
-        // kmm_comm_reduce_counts: node ranges whose flush runs under the previous range's reduce (1: flush, then one reduce)
-        if (value < 1 || value > 64)
-            return fail(KMM_ERR_INVALID_ARG, "comm_overlap_slices outside [1, 64]");
-        ix->comm_slices = (int)value;
-        ix->flush_cuts.clear();
-    } else if (!strcmp(name, "radix_sorted_flush")) {
-        ix->rx_flush_sorted = value != 0;
-    } else if (!strcmp(name, "radix_grid_per_cu")) {
-        if (value < 1 || value > 2)
-            return fail(KMM_ERR_INVALID_ARG, "radix_grid_per_cu must be 1 or 2");
-        ix->rx_grid_per_cu = (int)value;
-    } else if (!strcmp(name, "count_kmers")) {
-        // per-k-mer counting mode (GpuCounter semantics, gpu_counter.py:23-37): every batch takes the radix path
-        // and the per-entry hit counts are kept (kmm_get_kmer_counts) besides being summed into the node counts
-        if (value && !ix->rx_ok)
-            return fail(KMM_ERR_INVALID_ARG, "count_kmers needs the radix path, which is not available for this index");
-        KMMCHK(rx_flush(ix));
-        HIPCHK(hipStreamSynchronize(ix->stream));
-        if (value && !ix->rx_ecnt_acc) {
-            const size_t S = ix->rx_S ? ix->rx_S : 1;
-            HIPCHK(hipMalloc(ix->rx_ecnt_acc.put(), S * 4));
-            HIPCHK(hipMemset(ix->rx_ecnt_acc, 0, S * 4));
-        } else if (!value && ix->rx_ecnt_acc) {
-            HIPCHK(ix->rx_ecnt_acc.reset());
-        }
-    } else if (!strcmp(name, "grid_per_cu")) {
-        if (value < 1 || value > 1024)
-            return fail(KMM_ERR_INVALID_ARG, "grid_per_cu outside [1, 1024]");
-        ix->grid_per_cu = (int)value;
-    } else if (!strcmp(name, "dynamic_schedule")) {
-        ix->dynamic_schedule = value != 0;
-    } else if (!strcmp(name, "dyn_chunk")) {
-        if (value < 1 || value > 4096)
-            return fail(KMM_ERR_INVALID_ARG, "dyn_chunk outside [1, 4096]");
-        ix->dyn_chunk = (int)value;
-    } else if (!strcmp(name, "occupancy_filter")) {
-        ix->use_occ = value != 0;
-    } else if (!strcmp(name, "debug_records_copy_stream")) {
-        // experiments only (tools/records_overlap_bisect.py): the compaction kernels of kmm_map_records on the copy stream,
-        // beside the previous call's passes, WITHOUT mapping the call's reads
-        ix->dbg_rec_copy_stream = value != 0;
-    } else if (!strcmp(name, "host_pack_threads")) {
-        // > 0: reads / raw records that arrive in host memory (default lookup table, radix-sized batch) are packed to 2 bits per
-        // base by that many host threads before they cross PCIe (kmm_hostpack.hpp); 0: they cross as they are
-        if (value < 0 || value > 256)
-            return fail(KMM_ERR_INVALID_ARG, "host_pack_threads outside [0, 256]");
-        ix->host_pack_threads = (int)value;
-    } else if (!strcmp(name, "host_pack_slice_kb")) {
-        // raw bytes per slice of the host records packer (kmm_hostpack.hpp RecordsJob), in KiB; 0 = its default (1024)
-        if (value < 0 || value > 65536)
-            return fail(KMM_ERR_INVALID_ARG, "host_pack_slice_kb outside [0, 65536]");
-        ix->host_pack_slice_kb = value;
-    } else if (!strcmp(name, "bgzf_head_skip")) {
-        if (value < 0)
-            return fail(KMM_ERR_INVALID_ARG, "bgzf_head_skip negative");
-        ix->bgzf_head_skip = value;
-    } else if (!strcmp(name, "bgzf_tail_stop")) {
-        ix->bgzf_tail_stop = value < 0 ? -1 : value;
-    } else if (!strcmp(name, "debug_bgzf_ring_slot_kb") || !strcmp(name, "debug_ring_slot_kb")) {
-        if (value != 0 && (value < 4 || value > (1 << 20) || (value & (value - 1))))
-            return fail(KMM_ERR_INVALID_ARG, "debug_ring_slot_kb: 0 or a power of two in [4, 2^20]");
-        ix->dbg_bgzf_slot_kb = (int)value;
-    } else if (!strcmp(name, "bam_exclude_flags")) {
-        if (value < 0 || value > 0xFFFF)
-            return fail(KMM_ERR_INVALID_ARG, "bam_exclude_flags outside [0, 0xFFFF]");
-        ix->bam_excl = (uint32_t)value;
-    } else if (!strcmp(name, "bam_include_flags")) {
-        if (value < 0 || value > 0xFFFF)
-            return fail(KMM_ERR_INVALID_ARG, "bam_include_flags outside [0, 0xFFFF]");
-        ix->bam_incl = (uint32_t)value;
-    } else if (!strcmp(name, "bam_min_mapq")) {
-        if (value < 0 || value > 255)
-            return fail(KMM_ERR_INVALID_ARG, "bam_min_mapq outside [0, 255]");
-        ix->bam_min_mapq = (uint32_t)value;
-    } else if (!strcmp(name, "bam_n_ref")) {
-        // n_ref of the next KMM_FORMAT_MID_STREAM stream of kmm_map_bam (kmm_bam_header returns it); -1 = not set
-        if (value < -1 || value > 0x7FFFFFFFll)
-            return fail(KMM_ERR_INVALID_ARG, "bam_n_ref outside [-1, 2^31)");
-        ix->bam_n_ref_param = value;
-    } else if (!strcmp(name, "debug_bam_resync_kb")) {
-        // test hook of kmm_bam_find_record_start: inflated bytes it examines at most, KiB (0 = all the window's whole members)
-        if (value < 0 || value > (1ll << 32))
-            return fail(KMM_ERR_INVALID_ARG, "debug_bam_resync_kb outside [0, 2^32]");
-        ix->dbg_bam_resync_kb = value;
-    } else if (!strcmp(name, "debug_bgzf_call_cap_kb")) {
-        // test hook of kmm_map_bgzf / kmm_map_bam: inflated bytes one call takes at most, KiB (0 = the default, 3.5 GiB)
-        if (value < 0 || value > (7ll << 19))
-            return fail(KMM_ERR_INVALID_ARG, "debug_bgzf_call_cap_kb outside [0, 3.5 GiB / 1 KiB]");
-        ix->dbg_bgzf_call_cap_kb = value;
-    } else if (!strcmp(name, "debug_gzip_chunk_kb")) {
-        // test hook of kmm_map_gzip: spacing of the chunk search in KiB (0 = the default, 32) — a few MB then make hundreds of chunks
-        if (value < 0 || value > (1 << 20))
-            return fail(KMM_ERR_INVALID_ARG, "debug_gzip_chunk_kb outside [0, 2^20]");
-        ix->dbg_gzip_chunk_kb = (int)value;
-    } else if (!strcmp(name, "debug_rx_buffer_limit")) {
-        // test hook of the out-of-memory route of launch_rx (the call takes more sub-batches until the buffers fit)
-        ix->dbg_rx_buf_limit = value;
-    } else if (!strcmp(name, "debug_records_skip")) {
-        ix->dbg_rec_skip = (int)value;
-    } else if (!strcmp(name, "min_base_quality")) {
-        // > 0: a FASTQ base whose quality byte is below '!' + value is a break, on every call that parses FASTQ records
-        if (value < 0 || value > 93)
-            return fail(KMM_ERR_INVALID_ARG, "min_base_quality outside [0, 93]");
-        ix->min_base_quality = (int)value;
-    } else if (!strcmp(name, "record_hits_min_base_quality")) {
-        // the floor of the record calls while "record_hits" is 1 or 2; no other call reads it.  Entries may be
-        // pending: an entry holds what its record had under the floor of its own call
-        if (value < 0 || value > 93)
-            return fail(KMM_ERR_INVALID_ARG, "record_hits_min_base_quality outside [0, 93]");
-        ix->rh_min_base_quality = (int)value;
-    } else if (!strcmp(name, "record_hits")) {
-        // 1 / 2: the record calls append per-record index hits (2: and windows) to the handle's queue instead of counting
-        // nodes (kmm_take_record_hits); 0: off, entries still pending stay takeable
-        if (value < 0 || value > 2)
-            return fail(KMM_ERR_INVALID_ARG, "record_hits takes 0 (off), 1 (hits) or 2 (hits and windows)");
-        if (value != 0 && ix->rhq_pending > 0 && ix->rhq_mode != (int)value)
-            return fail(KMM_ERR_INVALID_ARG, "record_hits %lld with %lld entries of mode %d pending: take them (kmm_take_record_hits) "
-                        "or empty the queue (kmm_reset_counts) first", (long long)value, (long long)ix->rhq_pending, ix->rhq_mode);
-        ix->record_hits = (int)value;
-        if (value != 0)
-            ix->rhq_mode = (int)value;
-    } else if (!strcmp(name, "record_keep")) {
-        // 1: in the record-hits mode the record calls also append the text of every record whose entry passes the keep rule to
-        // the handle's byte queue (kmm_take_kept_records); 0: off, bytes still pending stay takeable
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "record_keep takes 0 or 1");
-        ix->record_keep = (int)value;
-    } else if (!strcmp(name, "record_keep_min_hits")) {
-        if (value < 0 || value > 0xFFFFFFFFll)
-            return fail(KMM_ERR_INVALID_ARG, "record_keep_min_hits outside [0, 2^32 - 1]");
-        ix->rk_min_hits = value;
-    } else if (!strcmp(name, "record_keep_min_permille")) {
-        if (value < 0 || value > 1000)
-            return fail(KMM_ERR_INVALID_ARG, "record_keep_min_permille outside [0, 1000]");
-        ix->rk_min_permille = (int)value;
-    } else if (!strcmp(name, "record_keep_invert")) {
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "record_keep_invert takes 0 or 1");
-        ix->rk_invert = (int)value;
-    } else if (!strcmp(name, "record_pairs")) {
-        // 1: while "record_keep" is 1 the records of a stream are interleaved mates — 2i and 2i + 1 — kept or dropped together
-        // (DESIGN 4.21); the calls then append even counts, which the pending entries of the other setting need not be
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "record_pairs takes 0 or 1");
-        if ((int)value != ix->record_pairs && ix->rhq_pending > 0)
-            return fail(KMM_ERR_INVALID_ARG, "record_pairs %lld with %lld entries pending that were appended under record_pairs %d: take "
-                        "them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
-                        (long long)ix->rhq_pending, ix->record_pairs);
-        ix->record_pairs = (int)value;
-    } else if (!strcmp(name, "record_names_pairs")) {
-        // 1: kmm_map_bam with "record_names" and "record_keep" takes the selected records of a stream as mates in file order —
-        // 2p and 2p + 1 — checks that their names agree and keeps or drops them together; even counts, as "record_pairs"
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "record_names_pairs takes 0 or 1");
-        if ((int)value != ix->record_names_pairs && ix->rhq_pending > 0)
-            return fail(KMM_ERR_INVALID_ARG, "record_names_pairs %lld with %lld entries pending that were appended under record_names_pairs "
-                        "%d: take them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
-                        (long long)ix->rhq_pending, ix->record_names_pairs);
-        ix->record_names_pairs = (int)value;
-    } else if (!strcmp(name, "record_pairs_rule")) {
-        if (value != (int64_t)RK_PAIR_ANY && value != (int64_t)RK_PAIR_BOTH)
-            return fail(KMM_ERR_INVALID_ARG, "record_pairs_rule takes 0 (a pair matches when any mate does) or 1 (when both do)");
-        ix->rk_pair_rule = (int)value;
-    } else if (!strcmp(name, "record_keep_pending_bytes") || !strcmp(name, "record_keep_pending_records") ||
-               !strcmp(name, "record_keep_pending_bytes_mate2") || !strcmp(name, "record_keep_pending_records_mate2")) {
-        return fail(KMM_ERR_INVALID_ARG, "%s is read-only", name);
-    } else if (!strcmp(name, "use_record_qual")) {
-        // 1: with "min_base_quality" > 0, kmm_map_bam and KMM_FORMAT_SAM decode every record's QUAL and apply the floor
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "use_record_qual takes 0 or 1");
-        ix->use_record_qual = (int)value;
-    } else if (!strcmp(name, "record_names") || !strcmp(name, "record_names_mate_suffix")) {
-        // 1: kmm_map_bam in the record-hits mode decodes to named four-line FASTQ; the suffix: "/1" / "/2"
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "%s takes 0 or 1", name);
-        (name[12] ? ix->record_names_mate_suffix : ix->record_names) = (int)value;
-    } else if (!strcmp(name, "record_bam")) {
-        // 1: kmm_map_bam with "record_hits" and "record_keep" appends the kept records' own bytes to the keep queue;
-        // text and raw records never share a queue: the switch does not move while kept bytes are pending
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "record_bam takes 0 or 1");
-        if ((int)value != ix->record_bam && ix->rkq[0].ctl.p) {
-            HIPCHK(hipSetDevice(ix->device));
-            KMMCHK(drain(ix));
-            unsigned long long tail[2];
-            KMMCHK(rkq_tail(ix->rkq[0], tail));
-            if (tail[0] > 0)
-                return fail(KMM_ERR_INVALID_ARG, "record_bam %lld with %llu kept bytes pending that were appended under record_bam %d: "
-                            "take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue (kmm_reset_counts) first",
-                            (long long)value, tail[0], ix->record_bam);
-        }
-        if ((int)value != ix->record_bam) // (a waiting mate 1 holds FASTA text under the raw form, named FASTQ under DESIGN 4.23's)
-            ix->bam_mate_len = ix->bam_raw_mate_len = 0;
-        ix->record_bam = (int)value;
-    } else if (!strcmp(name, "record_sam")) {
-        // 1 / 2: a KMM_FORMAT_SAM call with "record_hits" and "record_keep" appends the kept records' own lines to the keep queue,
-        // 1 with the header lines, 2 without; raw lines and text never share a queue, as "record_bam"
-        if (value < 0 || value > 2)
-            return fail(KMM_ERR_INVALID_ARG, "record_sam takes 0, 1 (header lines kept) or 2 (header lines dropped)");
-        if ((int)value != ix->record_sam && ix->rkq[0].ctl.p) {
-            HIPCHK(hipSetDevice(ix->device));
-            KMMCHK(drain(ix));
-            unsigned long long tail[2];
-            KMMCHK(rkq_tail(ix->rkq[0], tail));
-            if (tail[0] > 0)
-                return fail(KMM_ERR_INVALID_ARG, "record_sam %lld with %llu kept bytes pending that were appended under record_sam %d: "
-                            "take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue (kmm_reset_counts) first",
-                            (long long)value, tail[0], ix->record_sam);
-        }
-        if ((int)value != ix->record_sam)
-            sam_mates_drop(ix); // (a mate 1 that waits under one form is no carry of another's: DESIGN 4.28)
-        ix->record_sam = (int)value;
-    } else if (!strcmp(name, "record_sam_mates")) {
-        // 1: a KMM_FORMAT_SAM call under "record_sam" takes the selected records of the stream as mates in file order — 2p and
-        // 2p + 1 — checks that their QNAME bytes agree and keeps or drops their lines together; even counts
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "record_sam_mates takes 0 or 1");
-        if (value == 1 && !ix->record_sam)
-            return fail(KMM_ERR_INVALID_ARG, "record_sam_mates 1 with \"record_sam\" 0: mates are kept together in the raw form of the keep, "
-                        "set \"record_sam\" to 1 or 2 first (with \"record_hits\" and \"record_keep\")");
-        if ((int)value != ix->record_sam_mates) {
-            if (ix->rhq_pending > 0)
-                return fail(KMM_ERR_INVALID_ARG, "record_sam_mates %lld with %lld entries pending that were appended under record_sam_mates "
-                            "%d: take them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
-                            (long long)ix->rhq_pending, ix->record_sam_mates);
-            if (ix->rkq[0].ctl.p) {
-                HIPCHK(hipSetDevice(ix->device));
-                KMMCHK(drain(ix));
-                unsigned long long tail[2];
-                KMMCHK(rkq_tail(ix->rkq[0], tail));
-                if (tail[0] > 0)
-                    return fail(KMM_ERR_INVALID_ARG, "record_sam_mates %lld with %llu kept bytes pending that were appended under "
-                                "record_sam_mates %d: take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue "
-                                "(kmm_reset_counts) first", (long long)value, tail[0], ix->record_sam_mates);
-            }
-            sam_mates_drop(ix);
-        }
-        ix->record_sam_mates = (int)value;
-    } else if (!strcmp(name, "record_bam_mates")) {
-        // 1: kmm_map_bam with "record_bam" takes the selected records of a stream as mates in file order — 2p and 2p + 1 — checks
-        // that their read_name bytes agree and keeps or drops their own bytes together; even counts, as "record_pairs"
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "record_bam_mates takes 0 or 1");
-        if ((int)value != ix->record_bam_mates) {
-            if (ix->rhq_pending > 0)
-                return fail(KMM_ERR_INVALID_ARG, "record_bam_mates %lld with %lld entries pending that were appended under record_bam_mates "
-                            "%d: take them (kmm_take_record_hits) or empty the queue (kmm_reset_counts) first", (long long)value,
-                            (long long)ix->rhq_pending, ix->record_bam_mates);
-            if (ix->rkq[0].ctl.p) {
-                HIPCHK(hipSetDevice(ix->device));
-                KMMCHK(drain(ix));
-                unsigned long long tail[2];
-                KMMCHK(rkq_tail(ix->rkq[0], tail));
-                if (tail[0] > 0)
-                    return fail(KMM_ERR_INVALID_ARG, "record_bam_mates %lld with %llu kept bytes pending that were appended under "
-                                "record_bam_mates %d: take them (kmm_take_kept_records, kmm_take_kept_bgzf) or empty the queue "
-                                "(kmm_reset_counts) first", (long long)value, tail[0], ix->record_bam_mates);
-            }
-            ix->bam_mate_len = ix->bam_raw_mate_len = 0; // (a mate 1 that waits under one pair mode is no carry of the other's)
-        }
-        ix->record_bam_mates = (int)value;
-    } else if (!strcmp(name, "original_strand")) {
-        // 1: kmm_map_bam and KMM_FORMAT_SAM hand every kept record whose FLAG has 0x10 to the mapper in read orientation
-        if (value != 0 && value != 1)
-            return fail(KMM_ERR_INVALID_ARG, "original_strand takes 0 or 1");
-        ix->original_strand = (int)value;
-    } else if (!strcmp(name, "debug_records_piece_kb")) {
-        // test hook of kmm_map_records: bytes per piece in KiB (0 = the default, 2^30 bytes) — a few hundred KB then make several pieces
-        if (value < 0 || value > (1 << 20))
-            return fail(KMM_ERR_INVALID_ARG, "debug_records_piece_kb outside [0, 2^20]");
-        ix->dbg_rec_piece_kb = value;
-    } else if (!strcmp(name, "debug_records_grid")) {
-        // test hook of kmm_map_records: workgroups (of four wavefronts) of k_rec_count2 and k_rec_scatter (0 = the default, grid_for)
-        if (value < 0 || value > 65536)
-            return fail(KMM_ERR_INVALID_ARG, "debug_records_grid outside [0, 65536]");
-        ix->dbg_rec_grid = (int)value;
-    } else if (!strcmp(name, "debug_skew_p2_counter")) {
-        // test hook of the conservation self-check: adds `value` to the device-side "gathered by pass 2" counter, as a
-        // doubly processed work item would; the next synchronising call must fail with KMM_ERR_INTERNAL
-        unsigned long long v = 0;
-        HIPCHK(hipMemcpy(&v, ix->stats + 2, 8, hipMemcpyDeviceToHost));
-        v += (unsigned long long)value;
-        HIPCHK(hipMemcpy(ix->stats + 2, &v, 8, hipMemcpyHostToDevice));
-        ix->rx_unchecked = true;
-
-    } else {
-        return fail(KMM_ERR_INVALID_ARG, "unknown parameter '%s'", name);
-    }
+    char why[256];
+    if (kmm_params::set_refused(row, name, value, why, sizeof why))
+        return fail(KMM_ERR_INVALID_ARG, "%s", why);
+    if (row->set)
+        return row->set(ix, *row, value);
+    kmm_params::store(*row, *ix, value);
     return KMM_OK;
 }
 
@@ -5447,258 +5060,15 @@ int kmm_get_param(kmm_index_t *ix, const char *name, int64_t *value)
 {
     if (!ix || !name || !value)
         return fail(KMM_ERR_INVALID_ARG, "NULL argument");
-    if (!strcmp(name, "path"))
-        *value = ix->path;
-    else if (!strcmp(name, "part_shift"))
-        *value = ix->rx_geo.w;
-    else if (!strcmp(name, "radix_min_units"))
-        *value = ix->rx_min_units;
-    else if (!strcmp(name, "radix_grid_per_cu"))
-        *value = ix->rx_grid_per_cu;
-    else if (!strcmp(name, "host_pack_threads"))
-        *value = ix->host_pack_threads;
-    else if (!strcmp(name, "host_pack_slice_kb"))
-        *value = ix->host_pack_slice_kb;
-    else if (!strcmp(name, "host_packed_calls")) // map calls whose flat reads crossed PCIe as 2-bit codes
-        *value = ix->host_packed_calls;
-    else if (!strcmp(name, "host_packed_record_calls")) // kmm_map_records calls whose sequence lines were packed on the host
-        *value = ix->host_packed_record_calls;
-    else if (!strcmp(name, "bgzf_prestaged_calls")) // kmm_map_bgzf calls that staged the chunk behind them under their own kernel
-        *value = ix->bgzf_prestaged_calls;
-    else if (!strcmp(name, "gzip_calls")) // kmm_map_gzip calls
-        *value = ix->gzip_calls;
-    else if (!strcmp(name, "gzip_members")) // gzip members whose CRC32 / ISIZE kmm_map_gzip checked
-        *value = ix->gzip_members;
-    else if (!strcmp(name, "gzip_chunks")) // speculative starts decoded by kmm_map_gzip (the first chunk of every call included)
-        *value = ix->gzip_chunks;
-    else if (!strcmp(name, "gzip_false_starts")) // starts rejected by the predecessor check
-        *value = ix->gzip_false_starts;
-    else if (!strcmp(name, "gzip_continuations")) // lanes re-run past a rejected start or a full output slot
-        *value = ix->gzip_continuations;
-    else if (!strcmp(name, "gzip_inflated_bytes")) // bytes kmm_map_gzip inflated (callers size their next window from it)
-        *value = ix->gzip_inflated;
-    else if (!strcmp(name, "debug_gzip_chunk_kb"))
-        *value = ix->dbg_gzip_chunk_kb;
-    else if (!strcmp(name, "min_base_quality"))
-        *value = ix->min_base_quality;
-    else if (!strcmp(name, "record_hits_min_base_quality"))
-        *value = ix->rh_min_base_quality;
-    else if (!strcmp(name, "use_record_qual"))
-        *value = ix->use_record_qual;
-    else if (!strcmp(name, "original_strand"))
-        *value = ix->original_strand;
-    else if (!strcmp(name, "debug_records_piece_kb"))
-        *value = ix->dbg_rec_piece_kb;
-    else if (!strcmp(name, "debug_records_grid"))
-        *value = ix->dbg_rec_grid;
-    else if (!strcmp(name, "record_hits"))
-        *value = ix->record_hits;
-    else if (!strcmp(name, "record_hits_pending")) // entries waiting for kmm_take_record_hits
-        *value = ix->rhq_pending;
-    else if (!strcmp(name, "record_hits_pending_mode")) // the mode the pending entries were appended in (2: they have windows)
-        *value = ix->rhq_mode;
-    else if (!strcmp(name, "record_names"))
-        *value = ix->record_names;
-    else if (!strcmp(name, "record_names_mate_suffix"))
-        *value = ix->record_names_mate_suffix;
-    else if (!strcmp(name, "record_bam"))
-        *value = ix->record_bam;
-    else if (!strcmp(name, "record_sam"))
-        *value = ix->record_sam;
-    else if (!strcmp(name, "record_bam_mates"))
-        *value = ix->record_bam_mates;
-    else if (!strcmp(name, "record_sam_mates"))
-        *value = ix->record_sam_mates;
-    else if (!strcmp(name, "record_sam_mate_waiting")) // (read-only) a selected SAM record waits for its mate
-        *value = ix->sam_mate_len > 0 ? 1 : 0;
-    else if (!strcmp(name, "record_keep"))
-        *value = ix->record_keep;
-    else if (!strcmp(name, "record_keep_min_hits"))
-        *value = ix->rk_min_hits;
-    else if (!strcmp(name, "record_keep_min_permille"))
-        *value = ix->rk_min_permille;
-    else if (!strcmp(name, "record_keep_invert"))
-        *value = ix->rk_invert;
-    else if (!strcmp(name, "record_names_pairs"))
-        *value = ix->record_names_pairs;
-    else if (!strcmp(name, "record_pairs"))
-        *value = ix->record_pairs;
-    else if (!strcmp(name, "record_pairs_rule"))
-        *value = ix->rk_pair_rule;
-    else if (!strcmp(name, "record_keep_pending_bytes") || !strcmp(name, "record_keep_pending_records") ||
-             !strcmp(name, "record_keep_pending_bytes_mate2") || !strcmp(name, "record_keep_pending_records_mate2")) {
-        // the true tail of the queue of kept records lives on the device: behind a synchronisation, as "quality_masked_bases"
-        HIPCHK(hipSetDevice(ix->device));
-        KMMCHK(drain(ix));
-        unsigned long long tail[2];
-        KMMCHK(rkq_tail(ix->rkq[strstr(name, "_mate2") ? 1 : 0], tail));
-        *value = (int64_t)tail[name[20] == 'b' ? 0 : 1];
-    } else if (!strcmp(name, "read_hits_calls")) // kmm_read_hits calls (a pure query: no other counter moves)
-        *value = ix->read_hits_calls;
-    else if (!strcmp(name, "bam_calls")) // kmm_map_bam calls that mapped their records (a window inside the header not counted)
-        *value = ix->bam_calls;
-    else if (!strcmp(name, "bam_records")) // BAM records mapped
-        *value = ix->bam_records;
-    else if (!strcmp(name, "bam_records_excluded")) // BAM records left out by "bam_exclude_flags"
-        *value = ix->bam_excluded;
-    else if (!strcmp(name, "bam_header_bytes")) // inflated bytes of the BAM headers read
-        *value = ix->bam_header_bytes;
-    else if (!strcmp(name, "bam_false_starts")) // speculative record starts found wrong by the link check
-        *value = ix->bam_false_starts;
-    else if (!strcmp(name, "bam_continuations")) // tiles walked again from the exit before them
-        *value = ix->bam_continuations;
-    else if (!strcmp(name, "bam_exclude_flags"))
-        *value = ix->bam_excl;
-    else if (!strcmp(name, "bam_include_flags"))
-        *value = ix->bam_incl;
-    else if (!strcmp(name, "bam_min_mapq"))
-        *value = ix->bam_min_mapq;
-    else if (!strcmp(name, "record_regions")) // intervals of kmm_set_record_regions after merging (by ref_id; by name where no id was given)
-        *value = (int64_t)(ix->sel_iv_id.empty() ? ix->sel_iv_name.size() : ix->sel_iv_id.size());
-    else if (!strcmp(name, "sam_calls")) // kmm_map_records calls (direct, or on the inflated bytes of kmm_map_bgzf / _gzip) on SAM
-        *value = ix->sam_calls;
-    else if (!strcmp(name, "sam_records")) // SAM records mapped
-        *value = ix->sam_records;
-    else if (!strcmp(name, "sam_records_excluded")) // SAM records left out by "bam_exclude_flags"
-        *value = ix->sam_excluded;
-    else if (!strcmp(name, "sam_header_lines")) // SAM lines starting with '@', skipped
-        *value = ix->sam_header_lines;
-    else if (!strcmp(name, "debug_bgzf_call_cap_kb"))
-        *value = ix->dbg_bgzf_call_cap_kb;
-    else if (!strcmp(name, "bam_n_ref"))
-        *value = ix->bam_n_ref_param;
-    else if (!strcmp(name, "debug_bam_resync_kb"))
-        *value = ix->dbg_bam_resync_kb;
-    else if (!strcmp(name, "flat_uniform_batches")) // flat reads of one length mapped by the uniform / packed front ends
-        *value = ix->flat_uniform_batches;
-    else if (!strcmp(name, "bgzf_members")) // BGZF members inflated on the GPU by kmm_map_bgzf
-        *value = ix->bgzf_members;
-    else if (!strcmp(name, "bgzf_carry_bytes")) // inflated bytes behind the last complete record, waiting for the next call
-        *value = ix->bgzf_carry_len;
-    else if (!strcmp(name, "host_cpu_budget")) // cores the process may keep busy (affinity mask, cgroup quota)
-        *value = kmm_hostpack::cpu_budget();
-    else if (!strcmp(name, "radix_sub_batch_kmers"))
-        *value = ix->rx_sub_cap;
-    else if (!strcmp(name, "radix_sub_batch_kmers_effective"))
-        *value = ix->rx_sub_cap_last;
-    else if (!strcmp(name, "comm_overlap_slices"))
-        *value = ix->comm_slices;
-    else if (!strcmp(name, "comm_sliced_reduces")) // kmm_comm_reduce_counts calls that issued one reduce per node range
-        *value = ix->comm_sliced_reduces;
-    else if (!strcmp(name, "debug_rx_t1_sum") || !strcmp(name, "debug_rx_start1_sum") || !strcmp(name, "debug_rx_items")) {
-        // diagnostics of the latest radix sub-batch (both streams drained first): the k-mers its directory accounts for —
-        // by coarse partition (T1), by pass-1 block (last entry of every start1 row) — and its items
-        HIPCHK(hipSetDevice(ix->device));
-        HIPCHK(hipStreamSynchronize(ix->copy_stream));
-        HIPCHK(hipStreamSynchronize(ix->stream));
-        if (!ix->dbg_T1)
-            return fail(KMM_ERR_INVALID_ARG, "no radix batch has run on this handle");
-        uint64_t sum = 0;
-        if (name[9] == 't') {
-            std::vector<uint32_t> t(ix->dbg_F1);
-            HIPCHK(hipMemcpy(t.data(), ix->dbg_T1, t.size() * 4, hipMemcpyDeviceToHost));
-            for (uint32_t v : t)
-                sum += v;
-        } else if (name[9] == 'i') {
-            uint32_t v = 0;
-            HIPCHK(hipMemcpy(&v, ix->dbg_item_base + ix->dbg_F1, 4, hipMemcpyDeviceToHost));
-            sum = v;
-        } else {
-            const size_t ld = (size_t)ix->dbg_F1 + 1;
-            std::vector<uint16_t> r((size_t)ix->dbg_NB * ld);
-            HIPCHK(hipMemcpy(r.data(), ix->dbg_start1, r.size() * 2, hipMemcpyDeviceToHost));
-            for (size_t b = 0; b < ix->dbg_NB; ++b)
-                sum += r[b * ld + ld - 1];
-        }
-        *value = (int64_t)sum;
-    }
-    else if (!strcmp(name, "radix_sorted_flush"))
-        *value = (ix->rx_flush_sorted && ix->rx_norder) ? 1 : 0;
-    else if (!strcmp(name, "radix_available"))
-        *value = ix->rx_ok ? 1 : 0;
-    else if (!strcmp(name, "radix_batches"))
-        *value = (int64_t)ix->n_radix_batches;
-    else if (!strcmp(name, "direct_batches"))
-        *value = (int64_t)ix->n_direct_batches;
-    else if (!strcmp(name, "radix_unavailable_reason")) // 0 available, 1 modulo >= 2^31, 2 slices, 3 memory, 4 overlapping buckets
-        *value = ix->rx_ok ? 0 : ix->rx_why_not;
-    else if (!strcmp(name, "direct_view_resident"))
-        *value = ix->buckets ? 1 : 0;
-    else if (!strcmp(name, "direct_view_bytes"))
-        *value = (int64_t)ix->direct_bytes;
-    else if (!strcmp(name, "radix_view_bytes"))
-        *value = ix->rx_pstart ? (int64_t)rx_view_bytes(ix->modulo, ix->rx_S, ix->rx_norder != nullptr) : 0;
-    else if (!strcmp(name, "radix_filter"))
-        *value = (ix->rx_ok && rx_filter_active(ix)) ? 1 : 0;
-    else if (!strcmp(name, "radix_p3_keys_in_lds")) // entries of a slice pass 3 keeps in LDS (the rest is walked in HBM)
-        *value = ix->rx_ok ? rx_p3_shape(rx_p3_variant(ix)).keys_in_lds : 0;
-    else if (!strcmp(name, "radix_filter_buckets_per_bit")) // 1, 2 or 4 (0: no filter)
-        *value = (ix->rx_ok && rx_filter_active(ix)) ? (1 << ix->rx_geo.occ_shift) : 0;
-    else if (!strcmp(name, "radix_filter_slots")) // 1: pass 2 filters with the slot filter
-        *value = (ix->rx_ok && rx_slots_active(ix)) ? 1 : 0;
-    else if (!strcmp(name, "radix_p3_fingerprints")) // 1: pass 3 probes through fingerprint bytes
-        *value = (ix->rx_ok && rx_p3_fp_active(ix)) ? 1 : 0;
-    else if (!strcmp(name, "radix_filter_bits_per_partition")) // filter bits of one coarse partition in LDS (0: no filter)
-        *value = !(ix->rx_ok && rx_filter_active(ix)) ? 0
-                 : rx_slots_active(ix)                ? (int64_t)P2F_SLOT_WORDS * 32
-                                                      : (int64_t)1 << (ix->rx_geo.w + ix->rx_geo.f2 - ix->rx_geo.occ_shift);
-    else if (!strcmp(name, "debug_p2f_round_slots"))
-        *value = ix->dbg_p2f_cap;
-    else if (!strcmp(name, "radix_packed_tiles"))
-        *value = ix->rx_packed ? 1 : 0;
-    else if (!strcmp(name, "n_fine_per_coarse"))
-        *value = ix->rx_ok ? ix->rx_geo.F2 : 0;
-    else if (!strcmp(name, "count_kmers"))
-        *value = ix->rx_ecnt_acc ? 1 : 0;
-    else if (!strcmp(name, "n_coarse_partitions"))
-        *value = ix->rx_ok ? ix->rx_geo.F1 : 0;
-    else if (!strcmp(name, "radix_p2_kmers") || !strcmp(name, "radix_p3_kmers") || !strcmp(name, "radix_p2_dropped") ||
-             !strcmp(name, "radix_p2_multi_round_items") || !strcmp(name, "quality_masked_bases") ||
-             !strcmp(name, "records_without_qual") || !strcmp(name, "records_reversed") || !strcmp(name, "record_name_bytes_replaced") ||
-             !strcmp(name, "debug_p3_key_reads") || !strncmp(name, "stats_slot_", 11)) {
-        // conservation check of the radix path: k-mers gathered by pass 2 / probed by pass 3 since the last
-        // kmm_get_stats(reset): both must equal the lookups pass 1 emitted
-        HIPCHK(hipSetDevice(ix->device));
-        KMMCHK(drain(ix));
-        std::vector<unsigned long long> st(KMM_STAT_BYTES / 8);
-        HIPCHK(hipMemcpy(st.data(), ix->stats, KMM_STAT_BYTES, hipMemcpyDeviceToHost));
-        // ("stats_slot_<n>": raw counter n of the statistics block; slots 4.. are only written by diagnostic builds)
-        // ("quality_masked_bases": FASTQ bases whose quality byte was below "min_base_quality", since the same reset)
-        // ("records_without_qual": SAM / BAM records with bases and no qualities that were mapped with a floor, since the same reset)
-        // ("records_reversed": SAM / BAM records with FLAG 0x10 and bases written in read orientation ("original_strand"), since the same reset)
-        // ("record_name_bytes_replaced": QNAME bytes outside '!' .. '~' written as '?' by the named BAM decode ("record_names"), since the same reset)
-        // ("debug_p3_key_reads": 8-byte key reads of pass 3's probes; counted by -DRX_P3_FP_STATS builds only, else 0)
-        const int slot = name[0] == 's' ? atoi(name + 11) : name[0] == 'q' ? KMM_STAT_QUAL_MASKED
-                                                          : !strcmp(name, "records_without_qual") ? KMM_STAT_REC_NO_QUAL
-                                                          : !strcmp(name, "records_reversed") ? KMM_STAT_REC_REVERSED
-                                                          : !strcmp(name, "record_name_bytes_replaced") ? KMM_STAT_REC_NAME_REPLACED
-                                                          : name[0] == 'd' ? KMM_STAT_RX_P3_KEYS
-                                                          : !strcmp(name, "radix_p2_dropped") ? KMM_STAT_RX_DROPPED
-                                                          : !strcmp(name, "radix_p2_multi_round_items") ? KMM_STAT_RX_MULTI
-                                                          : name[7] == '2' ? 2 : 3;
-        if (slot < 0 || slot >= KMM_STAT_STRIDE)
-            return fail(KMM_ERR_INVALID_ARG, "unknown parameter '%s'", name);
-        unsigned long long t = 0;
-        for (int i = 0; i < KMM_STAT_SHARDS; ++i)
-            t += st[(size_t)i * KMM_STAT_STRIDE + slot];
-        *value = (int64_t)t;
-    }
-    else if (!strcmp(name, "grid_per_cu"))
-        *value = ix->grid_per_cu;
-    else if (!strcmp(name, "dynamic_schedule"))
-        *value = ix->dynamic_schedule ? 1 : 0;
-    else if (!strcmp(name, "occupancy_filter"))
-        *value = (ix->use_occ && ix->occ) ? 1 : 0;
-    else if (!strcmp(name, "bloom_filter_bytes"))
-        *value = (ix->use_occ && ix->occ) ? (int64_t)ix->bloom_words * 4 : 0;
-    else if (!strcmp(name, "occupancy_bits_per_bucket"))
-        *value = (ix->use_occ && ix->occ && !ix->bloom_words) ? (1 << ix->occ_shift) : 0;
-    else if (!strcmp(name, "wide_buckets"))
-        *value = ix->wide ? 1 : 0;
-    else if (!strcmp(name, "n_partitions"))
-        *value = ix->rx_ok ? ix->rx_geo.PF : 0;
-    else
-        return fail(KMM_ERR_INVALID_ARG, "unknown parameter '%s'", name);
+    const kmm_params::Row *row = find_param(name);
+    if (!row && !strncmp(name, "stats_slot_", 11)) // raw counter <n> of the statistics block; slots 4.. are only written by diagnostic builds
+        return get_stat_slot(ix, atoi(name + 11), name, value);
+    char why[256];
+    if (kmm_params::get_refused(row, name, why, sizeof why))
+        return fail(KMM_ERR_INVALID_ARG, "%s", why);
+    if (row->get)
+        return row->get(ix, *row, value);
+    *value = kmm_params::load(*row, *ix, *ix);
     return KMM_OK;
 }
 

@@ -570,8 +570,8 @@ class DeviceIndex:
         return a.value, b.value
 
     def set_param(self, name, value):
-        """Tuning knobs of include/kmm.h: "path" (0 auto, 1 direct, 2 radix), "part_shift", "radix_min_units",
-        "count_kmers"."""
+        """kmm_set_param: the names, the values they take and what they do are documented in include/kmm.h (the list above
+        kmm_set_param, and the sections of the calls that read them)."""
         _lib.check(_lib.lib().kmm_set_param(self._h, name.encode(), int(value)))
 
     def set_record_regions(self, regions, keep_unplaced=False):
