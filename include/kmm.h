@@ -837,6 +837,49 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
                     uint16_t *frequencies_out);
 
 /*
+ * kmm_seq_index_build — a Kmer Index from sequences: the step in front of kmm_build_index that the callers of
+ * that function had to do themselves.  bases uint8 flat, seq_offsets int64[n_seqs + 1] (seq_offsets[0] == 0, non-decreasing),
+ * seq_nodes int32[n_seqs], all >= 0, or NULL: the node of sequence i is i.  lut as everywhere (NULL: the reference's table, N is
+ * A; 0xFF entries are KMM_ERR_INVALID_BASE; KMM_LUT_BREAK entries are breaks; k == 1 with a break table is
+ * KMM_ERR_INVALID_ARG, as in kmm_read_hits).  Every pointer may be host or device memory.
+ *   1. windows: all windows of k bases that lie inside one sequence and contain no break byte, in flat order; their packed
+ *      k-mers are what kmm_extract_kmers gives for break-free input.
+ *   2. pair list P: per window (k-mer, node of its sequence); with KMM_SEQIDX_BOTH_STRANDS directly followed by (reverse
+ *      complement of the k-mer, same node).
+ *   3. D: the distinct pairs of P in order of first occurrence in P.  A k-mer that occurs 10^6 times in one sequence is one
+ *      entry, the same k-mer under three nodes is three entries of frequency 3, a palindrome under both strands is one.
+ *   4. modulo: the caller's, or with modulo == 0 kmm_seq_index_modulo(|D|): the smallest prime >= max(2 |D| + 1, 3).  Limits as
+ *      in kmm_build_index (< 2^31).
+ *   5. the index: exactly what kmm_build_index(D.kmers, D.nodes, |D|, modulo) returns.
+ * The five arrays are a pure function of the input: two builds give the same bytes.  |D| == 0 (no sequences, all shorter than
+ * k) is KMM_OK: no entries, the two tables zeroed.  KMM_ERR_INVALID_ARG, the message naming the number: more than
+ * KMM_SEQIDX_MAX_PAIRS pairs in P, decreasing offsets, seq_offsets[0] != 0, a negative node, k outside [1, KMM_MAX_K], a flag
+ * bit not listed here, NULL where data is needed.  After an error *out is NULL, nothing stays allocated and the next call
+ * works.  Runs on a stream of its own, like kmm_build_index, and returns when the object is complete.  Device memory while it
+ * runs: about 40 bytes per pair of P beside the input.
+ *
+ * kmm_seq_index_info — the entries |D|, the modulo, the windows of step 1 and the pairs |P| (each pointer may be NULL).
+ * kmm_seq_index_fetch — copies the five arrays out: hashes_to_index int32[modulo], n_kmers int32[modulo], kmers
+ * uint64[n_entries], nodes int32[n_entries], frequencies uint16[n_entries], each host or device memory.  A NULL table, or a
+ * NULL per-entry array while n_entries > 0, is KMM_ERR_INVALID_ARG and nothing is copied.  May be called again.
+ * kmm_seq_index_destroy — frees the object (NULL: nothing).
+ * kmm_seq_index_modulo — pure, no device: what modulo == 0 chooses for n_entries entries.
+ */
+typedef struct kmm_seq_index kmm_seq_index_t;
+#define KMM_SEQIDX_BOTH_STRANDS 1
+#define KMM_SEQIDX_DEBUG_SHORT_ROUNDS 0x40000000 /* TEST ONLY: an emit round is two super-tiles (2 Mi bases) instead of 2^20
+                                                  * tiles, so that a 3 Mi-base input crosses a round seam; the result is the same */
+#define KMM_SEQIDX_MAX_PAIRS (1ll << 30)         /* pairs of P one call takes (the de-duplication table keeps 32-bit indices) */
+int kmm_seq_index_build(int device, const uint8_t *bases, const int64_t *seq_offsets, int64_t n_seqs,
+                        const int32_t *seq_nodes, int k, const uint8_t *lut, int flags, uint64_t modulo,
+                        kmm_seq_index_t **out);
+int kmm_seq_index_info(const kmm_seq_index_t *s, int64_t *n_entries, uint64_t *modulo, int64_t *n_windows, int64_t *n_pairs);
+int kmm_seq_index_fetch(kmm_seq_index_t *s, int32_t *hashes_to_index, int32_t *n_kmers, uint64_t *kmers, int32_t *nodes,
+                        uint16_t *frequencies);
+void kmm_seq_index_destroy(kmm_seq_index_t *s);
+uint64_t kmm_seq_index_modulo(int64_t n_entries);
+
+/*
  * Measurement hooks (the reference only logs perf_counter deltas,
  * command_line_interface.py:67-78).  With timing on, every launch of a hot-path kernel is
  * bracketed by HIP events on the handle's stream; kmm_get_timing drains the stream and returns,

@@ -24,7 +24,8 @@ KMM_ERR_INTERNAL = -7
 FORMAT_FASTA2, FORMAT_FASTQ = 2, 4
 FORMAT_FASTA, FORMAT_LAST_CHUNK, FORMAT_NEW_STREAM = 1, 0x100, 0x400      # multi-line FASTA (unwrapped on the GPU); flag: the chunk ends the file
 FORMAT_MID_STREAM = 0x200       # kmm_map_bam, with FORMAT_NEW_STREAM: the stream begins behind the header (a rank's share of a BAM file)
-FORMAT_SAM = 8                  # SAM text: the SEQ column extracted on the GPU (kmm_map_records / kmm_map_bgzf / kmm_map_gzip)
+SEQIDX_BOTH_STRANDS, SEQIDX_DEBUG_SHORT_ROUNDS, SEQIDX_MAX_PAIRS = 1, 0x40000000, 1 << 30     # kmm_seq_index_build (include/kmm.h)
+FORMAT_SAM = 8              # SAM text: the SEQ column extracted on the GPU (kmm_map_records / kmm_map_bgzf / kmm_map_gzip)
 
 # kernel ids of kmm_get_timing (include/kmm.h)
 (KERNEL_MAP_READS, KERNEL_MAP_KMERS, KERNEL_RX_P1, KERNEL_RX_SCAN, KERNEL_RX_P2, KERNEL_RX_P3,
@@ -76,6 +77,11 @@ SIGNATURES = {
     "kmm_map_packed": (_c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P, _c.c_int, _c.c_int, _c.c_int]),
     "kmm_extract_kmers": (_c.c_int, [_c.c_int, _P, _P, _c.c_int64, _c.c_int, _P, _P, _c.c_int64]),
     "kmm_build_index": (_c.c_int, [_c.c_int, _P, _P, _c.c_int64, _c.c_uint64, _P, _P, _P, _P, _P]),
+    "kmm_seq_index_build": (_c.c_int, [_c.c_int, _P, _P, _c.c_int64, _P, _c.c_int, _P, _c.c_int, _c.c_uint64, _P]),
+    "kmm_seq_index_info": (_c.c_int, [_P, _P, _P, _P, _P]),
+    "kmm_seq_index_fetch": (_c.c_int, [_P, _P, _P, _P, _P, _P]),
+    "kmm_seq_index_destroy": (None, [_P]),
+    "kmm_seq_index_modulo": (_c.c_uint64, [_c.c_int64]),
     "kmm_in_index": (_c.c_int, [_P, _P, _c.c_int64, _P]),
     "kmm_read_hits": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
     "kmm_take_record_hits": (_c.c_int, [_P, _P, _P, _c.c_int64, _P]),

@@ -1428,6 +1428,44 @@ def select_reads_file(args):
     return sink.seen, sink.kept
 
 
+def check_index_args(kmer_size, modulo, ambiguous_bases):
+    """The refusals of `kmer_mapper index` that need neither the file nor a device."""
+    if not 1 <= kmer_size <= 31:
+        raise ValueError("index: -k %d outside [1, 31]" % kmer_size)
+    if modulo != 0 and not 2 <= modulo <= 2 ** 31 - 1:
+        raise ValueError("index: --modulo %d outside [2, 2^31 - 1] (0, the default: the smallest prime >= 2 entries + 1)" % modulo)
+    if ambiguous_bases == "skip" and kmer_size < 2:
+        raise ValueError("--ambiguous-bases skip needs -k 2 or more")
+
+
+def index_file(args):
+    """`kmer_mapper index`: a Kmer Index (.npz) from the sequences of a FASTA file, built on the GPU: what
+    `map`, `read-hits` and `select-reads` take with -i.  Node i is the i-th sequence (--single-node: all are node 0)."""
+    from . import mapper
+    check_index_args(args.kmer_size, args.modulo, args.ambiguous_bases)
+    t0 = time.perf_counter()
+    index, names, info = mapper.index_from_fasta(args.fasta, k=args.kmer_size, both_strands=args.both_strands,
+                                                 single_node=args.single_node, modulo=args.modulo,
+                                                 ambiguous_bases=args.ambiguous_bases, device=args.device)
+    skipped = info["n_full_windows"] - info["n_windows"]
+    logging.info("index: %d sequences, %d bases, %d windows of %d bases (%d skipped at ambiguous bases: %.3f %%), %d pairs%s, "
+                 "%d entries, modulo %d, %.2f s", info["n_seqs"], info["n_bases"], info["n_windows"], args.kmer_size, skipped,
+                 100.0 * skipped / max(info["n_full_windows"], 1), info["n_pairs"], " (both strands)" if args.both_strands else "",
+                 info["n_entries"], info["modulo"], time.perf_counter() - t0)
+    if info["n_entries"] == 0:
+        raise ValueError("index: %s gives an index without entries (no sequence holds a window of %d bases clear of ambiguous "
+                         "bases): lower -k or check the file" % (args.fasta, args.kmer_size))
+    index.to_file(args.output_file)
+    if args.names_output:
+        with open(args.names_output, "w") as f:
+            for name in names:
+                f.write(name + "\n")
+        logging.info("index: %d names written to %s (line i names node i%s)", len(names), args.names_output,
+                     "; with --single-node every sequence is node 0" if args.single_node else "")
+    logging.info("index: written to %s", args.output_file if str(args.output_file).endswith(".npz") else str(args.output_file) + ".npz")
+    return index
+
+
 def build_argument_parser():
     parser = argparse.ArgumentParser(
         description='Kmer Mapper',
@@ -1657,6 +1695,27 @@ def build_argument_parser():
     sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
     sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
     sub.set_defaults(func=select_reads_file)
+
+    sub = subparsers.add_parser("index", help="Extension: build a kmer index from the sequences of a FASTA file, on the GPU")
+    sub.add_argument("-f", "--fasta", required=True, help="Sequences in FASTA format (.fa, .fa.gz; wrapped lines are fine). The "
+                     "file is read whole; FASTQ, SAM and BAM are refused.")
+    sub.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
+    sub.add_argument("-o", "--output-file", required=True, help="The kmer index (.npz) that map, read-hits and select-reads take with -i")
+    sub.add_argument("--both-strands", action="store_true",
+                     help="Also enter the reverse complement of every k-mer, under the same node: reads of either strand hit "
+                          "without -r.")
+    sub.add_argument("--single-node", action="store_true",
+                     help="Every sequence is node 0 (default: sequence i is node i): the smallest index, for select-reads.")
+    sub.add_argument("--modulo", default=0, type=int,
+                     help="The index's hash modulo, 2 .. 2^31 - 1. Default 0: the smallest prime >= 2 x entries + 1.")
+    sub.add_argument("--ambiguous-bases", choices=("skip", "a"), default="skip",
+                     help="skip (the default HERE): no k-mer over N or an IUPAC ambiguity letter enters the index, so an N run of "
+                          "a reference does not become a poly-A entry. a: N is A and every other letter is an error. Note that "
+                          "`map`, `read-hits` and `select-reads` default the other way (a), for the reference's sake.")
+    sub.add_argument("--names-output", required=False, help="Write the sequence names here, one per line: line i names node i.")
+    sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
+    sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
+    sub.set_defaults(func=index_file)
     return parser
 
 

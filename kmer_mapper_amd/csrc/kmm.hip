@@ -33,6 +33,7 @@
 #include "kmm.h"
 #include "kmm_radix_plan.hpp" // (plain C++ with standard headers of its own: before the namespace the kernels live in)
 #include "kmm_params.hpp"     // (the same: KmmKnobs, KmmCounters and the parameter table)
+#include "kmm_seqindex_plan.hpp" // (the same: the limits, the table size and the prime search of kmm_seq_index_build)
 
 namespace {
 
@@ -97,6 +98,7 @@ static double ms_since(std::chrono::steady_clock::time_point a)
 #include "kmm_record_keep.hpp"
 #include "kmm_radix.hpp"
 #include "kmm_build.hpp"
+#include "kmm_seqindex.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -483,6 +485,14 @@ struct kmm_index : IndexStreams, RxArrays, KmmKnobs, KmmCounters { // (the store
     int64_t launches[KMM_N_KERNELS] = {0};
 };
 
+// What kmm_seq_index_build returns: the five arrays in device memory, each in an owner of its own.
+struct kmm_seq_index {
+    int device = 0;
+    DevBuf h2i, nk, kmers, nodes, freqs;
+    int64_t n_entries = 0, n_windows = 0, n_pairs = 0;
+    uint64_t modulo = 0;
+};
+
 namespace {
 
 IndexView view_of(const kmm_index *ix)
@@ -780,6 +790,50 @@ int scan_exclusive(const uint32_t *in, uint32_t *out, uint64_t n, std::vector<De
     return KMM_OK;
 }
 
+// kmm_build_index on device arrays and a stream (kmm_build.hpp): kmers / nodes [n] -> the five arrays, all device memory, all
+// launches on `st`, nothing waited for.  Shared by kmm_build_index and kmm_seq_index_build (kmm_seqindex_host.hpp).
+struct BiScratch {
+    DevBuf cur, src, list, ksort;
+    std::vector<DevBuf> scan{2 * SCAN_MAX_LEVELS};
+};
+
+int bi_build_device(hipStream_t st, const uint64_t *kmers, const int32_t *nodes, int64_t n, uint64_t M, uint32_t *w_nk, uint32_t *w_h2i,
+                    uint64_t *w_ko, int32_t *w_no, uint16_t *w_fo, BiScratch &s)
+{
+    const uint64_t magic = magic_for(M);
+    KMMCHK(ensure(s.cur, (size_t)M * 4));
+    HIPCHK(hipMemsetAsync(w_nk, 0, (size_t)M * 4, st));
+    HIPCHK(hipMemsetAsync(s.cur.p, 0, (size_t)M * 4, st));
+    int64_t g = (n + 255) / 256;
+    if (g > 65536) g = 65536;
+    if (g < 1) g = 1;
+    uint64_t gm = (M + 255) / 256;
+    if (gm > 65536) gm = 65536;
+    if (n > 0)
+        hipLaunchKernelGGL(k_bi_hist, dim3((unsigned)g), dim3(256), 0, st, kmers, n, M, magic, w_nk);
+    KMMCHK(scan_exclusive(w_nk, w_h2i, M, s.scan, 0, st));
+    if (n > 0) {
+        KMMCHK(ensure(s.src, (size_t)n * 4));
+        hipLaunchKernelGGL(k_bi_scatter, dim3((unsigned)g), dim3(256), 0, st, kmers, n, M, magic, w_h2i, (uint32_t *)s.cur.p,
+                           (uint32_t *)s.src.p);
+        hipLaunchKernelGGL(k_bi_place, dim3((unsigned)g), dim3(256), 0, st, kmers, nodes, n, M, magic, w_h2i, w_nk,
+                           (const uint32_t *)s.src.p, w_ko, w_no, w_fo);
+        // buckets with more than BI_BIG entries: listed, then ordered by one workgroup each
+        const size_t list_cap = (size_t)n / BI_BIG + 2;
+        KMMCHK(ensure(s.list, (list_cap + 1) * 4));
+        KMMCHK(ensure(s.ksort, (size_t)n * 8));
+        uint32_t *d_count = (uint32_t *)s.list.p + list_cap;
+        HIPCHK(hipMemsetAsync(d_count, 0, 4, st));
+        hipLaunchKernelGGL(k_bi_list_big, dim3((unsigned)gm), dim3(256), 0, st, w_nk, M, (uint32_t *)s.list.p, d_count);
+        hipLaunchKernelGGL(k_bi_big, dim3(1024), dim3(1024), 0, st, kmers, nodes, w_h2i, w_nk, (const uint32_t *)s.list.p, d_count,
+                           (uint32_t *)s.src.p, (uint64_t *)s.ksort.p, w_ko, w_no, w_fo);
+    }
+    // the format leaves hashes_to_index = 0 for empty buckets (upstream fills only the used ones)
+    hipLaunchKernelGGL(k_bi_zero_empty, dim3((unsigned)gm), dim3(256), 0, st, w_h2i, w_nk, M);
+    HIPCHK(hipGetLastError());
+    return KMM_OK;
+}
+
 #include "kmm_radix_host.hpp"
 
 template <int MODE>
@@ -881,6 +935,8 @@ int check_k(int k)
         return fail(KMM_ERR_INVALID_ARG, "k=%d outside [1, %d]", k, KMM_MAX_K);
     return KMM_OK;
 }
+
+#include "kmm_seqindex_host.hpp" // kmm_seq_index_build behind bi_build_device and check_k
 
 template <int MODE>
 int launch_read_hits(kmm_index *ix, const ReadsView &rv, int k, int max_freq, int also_rc, const int64_t *tile_first_read,
@@ -4799,10 +4855,9 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
     }
     HIPCHK(hipSetDevice(device));
     const uint64_t M = modulo;
-    const uint64_t magic = magic_for(M);
     Stream st; // a stream of its own: other handles' work on this device is not stalled (destroyed after the buffers)
-    DevBuf d_km, d_nd, d_nk, d_h2i, d_cur, d_src, d_ko, d_no, d_fo, d_list, d_ksort;
-    std::vector<DevBuf> scratch(2 * SCAN_MAX_LEVELS);
+    DevBuf d_km, d_nd, d_nk, d_h2i, d_ko, d_no, d_fo;
+    BiScratch scratch;
     int rc = KMM_OK;
     hipError_t e = hipSuccess;
     HIPCHK(hipStreamCreateWithFlags(st.put(), hipStreamNonBlocking));
@@ -4835,55 +4890,24 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
         uint32_t *w_h2i = is_device_ptr(hashes_to_index) ? (uint32_t *)hashes_to_index : nullptr;
         if (!w_nk) { if ((rc = ensure(d_nk, (size_t)M * 4))) break; w_nk = (uint32_t *)d_nk.p; }
         if (!w_h2i) { if ((rc = ensure(d_h2i, (size_t)M * 4))) break; w_h2i = (uint32_t *)d_h2i.p; }
-        if ((rc = ensure(d_cur, (size_t)M * 4))) break;
-        if ((e = hipMemsetAsync(w_nk, 0, (size_t)M * 4, st))) break;
-        if ((e = hipMemsetAsync(d_cur.p, 0, (size_t)M * 4, st))) break;
-        int64_t g = (n + 255) / 256;
-        if (g > 65536) g = 65536;
-        if (g < 1) g = 1;
-        if (n > 0)
-            hipLaunchKernelGGL(k_bi_hist, dim3((unsigned)g), dim3(256), 0, st, (const uint64_t *)p_km, n, M, magic, w_nk);
-        if ((rc = scan_exclusive(w_nk, w_h2i, M, scratch, 0, st))) break;
+        uint64_t *w_ko = nullptr;
+        int32_t *w_no = nullptr;
+        uint16_t *w_fo = nullptr;
         if (n > 0) {
-            uint64_t *w_ko = is_device_ptr(kmers_out) ? kmers_out : nullptr;
-            int32_t *w_no = is_device_ptr(nodes_out) ? nodes_out : nullptr;
-            uint16_t *w_fo = is_device_ptr(frequencies_out) ? frequencies_out : nullptr;
+            w_ko = is_device_ptr(kmers_out) ? kmers_out : nullptr;
+            w_no = is_device_ptr(nodes_out) ? nodes_out : nullptr;
+            w_fo = is_device_ptr(frequencies_out) ? frequencies_out : nullptr;
             if (!w_ko) { if ((rc = ensure(d_ko, (size_t)n * 8))) break; w_ko = (uint64_t *)d_ko.p; }
             if (!w_no) { if ((rc = ensure(d_no, (size_t)n * 4))) break; w_no = (int32_t *)d_no.p; }
             if (!w_fo) { if ((rc = ensure(d_fo, (size_t)n * 2))) break; w_fo = (uint16_t *)d_fo.p; }
-            if ((rc = ensure(d_src, (size_t)n * 4))) break;
-            hipLaunchKernelGGL(k_bi_scatter, dim3((unsigned)g), dim3(256), 0, st, (const uint64_t *)p_km, n, M, magic,
-                               w_h2i, (uint32_t *)d_cur.p, (uint32_t *)d_src.p);
-            hipLaunchKernelGGL(k_bi_place, dim3((unsigned)g), dim3(256), 0, st, (const uint64_t *)p_km,
-                               (const int32_t *)p_nd, n, M, magic, w_h2i, w_nk, (const uint32_t *)d_src.p, w_ko,
-                               w_no, w_fo);
-            // buckets with more than BI_BIG entries: listed, then ordered by one workgroup each
-            const size_t list_cap = (size_t)n / BI_BIG + 2;
-            if ((rc = ensure(d_list, (list_cap + 1) * 4))) break;
-            if ((rc = ensure(d_ksort, (size_t)n * 8))) break;
-            uint32_t *d_count = (uint32_t *)d_list.p + list_cap;
-            if ((e = hipMemsetAsync(d_count, 0, 4, st))) break;
-            {
-                uint64_t gm = (M + 255) / 256;
-                if (gm > 65536) gm = 65536;
-                hipLaunchKernelGGL(k_bi_list_big, dim3((unsigned)gm), dim3(256), 0, st, w_nk, M, (uint32_t *)d_list.p, d_count);
-            }
-            hipLaunchKernelGGL(k_bi_big, dim3(1024), dim3(1024), 0, st, (const uint64_t *)p_km, (const int32_t *)p_nd, w_h2i,
-                               w_nk, (const uint32_t *)d_list.p, d_count, (uint32_t *)d_src.p, (uint64_t *)d_ksort.p, w_ko,
-                               w_no, w_fo);
-            if ((e = hipGetLastError())) break;
-            if ((e = hipStreamSynchronize(st))) break;
+        }
+        if ((rc = bi_build_device(st, (const uint64_t *)p_km, (const int32_t *)p_nd, n, M, w_nk, w_h2i, w_ko, w_no, w_fo, scratch))) break;
+        if ((e = hipStreamSynchronize(st))) break;
+        if (n > 0) {
             if (!down(kmers_out, w_ko, (size_t)n * 8)) break;
             if (!down(nodes_out, w_no, (size_t)n * 4)) break;
             if (!down(frequencies_out, w_fo, (size_t)n * 2)) break;
         }
-        {   // the format leaves hashes_to_index = 0 for empty buckets (upstream fills only the used ones)
-            uint64_t gm = (M + 255) / 256;
-            if (gm > 65536) gm = 65536;
-            hipLaunchKernelGGL(k_bi_zero_empty, dim3((unsigned)gm), dim3(256), 0, st, w_h2i, w_nk, M);
-        }
-        if ((e = hipGetLastError())) break;
-        if ((e = hipStreamSynchronize(st))) break;
         if (!down(n_kmers, w_nk, (size_t)M * 4)) break;
         if (!down(hashes_to_index, w_h2i, (size_t)M * 4)) break;
     } while (0);
@@ -4893,6 +4917,61 @@ int kmm_build_index(int device, const uint64_t *kmers, const int32_t *nodes, int
     if (e != hipSuccess)
         return fail(KMM_ERR_HIP, "kmm_build_index: %s", hipGetErrorString(e));
     return KMM_OK;
+}
+
+int kmm_seq_index_build(int device, const uint8_t *bases, const int64_t *seq_offsets, int64_t n_seqs, const int32_t *seq_nodes, int k,
+                        const uint8_t *lut, int flags, uint64_t modulo, kmm_seq_index_t **out)
+{
+    if (!out)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_seq_index_build: out is NULL");
+    *out = nullptr;
+    return guarded("kmm_seq_index_build", [&]() -> int {
+        std::unique_ptr<kmm_seq_index> s(new kmm_seq_index);
+        const int rc = seq_index_build_impl(device, bases, seq_offsets, n_seqs, seq_nodes, k, lut, flags, modulo, *s);
+        if (rc != KMM_OK) {
+            s.reset(); // (its arrays freed; hipFree leaves no error of ours behind)
+            (void)hipGetLastError();
+            return rc;
+        }
+        *out = s.release();
+        return KMM_OK;
+    });
+}
+
+int kmm_seq_index_info(const kmm_seq_index_t *s, int64_t *n_entries, uint64_t *modulo, int64_t *n_windows, int64_t *n_pairs)
+{
+    if (!s)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_seq_index_info: the object is NULL");
+    if (n_entries)
+        *n_entries = s->n_entries;
+    if (modulo)
+        *modulo = s->modulo;
+    if (n_windows)
+        *n_windows = s->n_windows;
+    if (n_pairs)
+        *n_pairs = s->n_pairs;
+    return KMM_OK;
+}
+
+int kmm_seq_index_fetch(kmm_seq_index_t *s, int32_t *hashes_to_index, int32_t *n_kmers, uint64_t *kmers, int32_t *nodes,
+                        uint16_t *frequencies)
+{
+    if (!s)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_seq_index_fetch: the object is NULL");
+    return seq_index_fetch_impl(*s, hashes_to_index, n_kmers, kmers, nodes, frequencies);
+}
+
+void kmm_seq_index_destroy(kmm_seq_index_t *s)
+{
+    if (!s)
+        return;
+    (void)hipSetDevice(s->device);
+    delete s;
+}
+
+uint64_t kmm_seq_index_modulo(int64_t n_entries)
+{
+    return si_modulo(n_entries);
 }
 
 int kmm_get_stats(kmm_index_t *ix, int reset, uint64_t *n_lookups, uint64_t *n_hits)

@@ -650,3 +650,64 @@ def build_index(kmers, nodes, modulo, device=0):
     p = lambda a: a.ctypes.data_as(_P)
     _lib.check(_lib.lib().kmm_build_index(int(device), p(km), p(nd), n, M, p(h2i), p(nk), p(ko), p(no), p(fo)))
     return h2i, nk, ko, no, fo
+
+
+def index_from_sequences(bases, seq_offsets, k=31, nodes=None, lut=None, both_strands=False, modulo=0, device=0, info=None,
+                         _flags=0):
+    """kmm_seq_index_build: sequences -> distinct (k-mer, node) pairs in order of first occurrence -> the five
+    index arrays, on the GPU.  bases uint8 flat, seq_offsets int64[n + 1]; nodes int32[n] or None (sequence i is node i);
+    modulo 0: the smallest prime >= 2 entries + 1.  Returns (hashes_to_index, n_kmers, kmers, nodes, frequencies, modulo) in
+    the order of build_index: numpy arrays for host input, torch tensors on the device of `bases` for a device tensor.
+    info: a dict that receives n_entries, modulo, n_windows and n_pairs."""
+    L = _lib.lib()
+    on_device = _is_torch_tensor(bases) and bases.is_cuda
+    b = _Arg(bases, np.uint8, "bases")
+    o = _Arg(seq_offsets if _is_torch_tensor(seq_offsets)
+             else np.ascontiguousarray(np.asarray(seq_offsets, dtype=np.int64)), np.int64, "seq_offsets")
+    if o.n < 1:
+        raise ValueError("seq_offsets needs n_seqs + 1 entries (got none)")
+    if nodes is not None and not _is_torch_tensor(nodes):
+        nd_in = np.asarray(nodes)
+        if nd_in.size and (nd_in.min() < -2 ** 31 or nd_in.max() > 2 ** 31 - 1):
+            raise ValueError("node ids must fit int32")
+        nodes = np.ascontiguousarray(nd_in, dtype=np.int32)
+    nd = _Arg(nodes, np.int32, "nodes")
+    if nodes is not None and nd.n != o.n - 1:
+        raise ValueError("nodes has %d entries for %d sequences" % (nd.n, o.n - 1))
+    t = _Arg(lut, np.uint8, "lut")
+    if lut is not None and t.n != 256:
+        raise ValueError("lut must have 256 entries")
+    flags = (_lib.SEQIDX_BOTH_STRANDS if both_strands else 0) | int(_flags)
+    h = _P()
+    _lib.check(L.kmm_seq_index_build(int(device), b.ptr, o.ptr, o.n - 1, nd.ptr, int(k), t.ptr, flags, int(modulo), ctypes.byref(h)))
+    try:
+        n, M, nw, npairs = ctypes.c_int64(0), ctypes.c_uint64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        _lib.check(L.kmm_seq_index_info(h, ctypes.byref(n), ctypes.byref(M), ctypes.byref(nw), ctypes.byref(npairs)))
+        n, M = n.value, M.value
+        if info is not None:
+            info.update(n_entries=n, modulo=M, n_windows=nw.value, n_pairs=npairs.value)
+        if on_device:
+            import torch
+            dev = bases.device
+            h2i = torch.empty(M, dtype=torch.int32, device=dev)
+            nk = torch.empty(M, dtype=torch.int32, device=dev)
+            ko = torch.empty(n, dtype=torch.int64, device=dev)
+            no = torch.empty(n, dtype=torch.int32, device=dev)
+            fo = torch.empty(n, dtype=torch.uint16, device=dev)
+            p = lambda x: _P(x.data_ptr()) if x.numel() else None
+        else:
+            h2i = np.empty(M, dtype=np.int32)
+            nk = np.empty(M, dtype=np.int32)
+            ko = np.empty(n, dtype=np.uint64)
+            no = np.empty(n, dtype=np.int32)
+            fo = np.empty(n, dtype=np.uint16)
+            p = lambda a: a.ctypes.data_as(_P) if a.size else None
+        _lib.check(L.kmm_seq_index_fetch(h, p(h2i), p(nk), p(ko), p(no), p(fo)))
+    finally:
+        L.kmm_seq_index_destroy(h)
+    return h2i, nk, ko, no, fo, M
+
+
+def seq_index_modulo(n_entries):
+    """What modulo=0 chooses for n_entries entries (kmm_seq_index_modulo: pure, needs no GPU)."""
+    return int(_lib.lib().kmm_seq_index_modulo(int(n_entries)))

@@ -67,6 +67,16 @@ class KmerIndex:
         return cls(h2i, nk, no, ko, int(modulo), fo)
 
     @classmethod
+    def from_sequences_gpu(cls, bases, seq_offsets, k=31, nodes=None, lut=None, both_strands=False, modulo=0, device=0,
+                           info=None):
+        """From sequences (kmm_seq_index_build): every window of k bases inside one sequence and clear of break bytes, as
+        distinct (k-mer, node) pairs in order of first occurrence; sequence i is node i unless `nodes` says otherwise."""
+        from .engine import index_from_sequences
+        h2i, nk, ko, no, fo, M = index_from_sequences(bases, seq_offsets, k=k, nodes=nodes, lut=lut, both_strands=both_strands,
+                                                      modulo=modulo, device=device, info=info)
+        return cls(h2i, nk, no, ko, M, fo)
+
+    @classmethod
     def from_flat_kmers(cls, kmers, nodes, modulo, ref_offsets=None):
         kmers = np.asarray(kmers, dtype=np.uint64)
         nodes = np.asarray(nodes)

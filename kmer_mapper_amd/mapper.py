@@ -375,3 +375,56 @@ def select_record_pairs(index, raw1, raw2=None, fmt="fastq", k=31, max_index_loo
         if not dev.get_param("record_hits_pending"):                                   # (a failing call appended nothing)
             dev.set_param("record_pairs", before[0])
     return text1, text2, hits, windows
+
+
+def index_from_fasta(path, k=31, both_strands=False, single_node=False, modulo=0, ambiguous_bases="skip", device=0):
+    """A Kmer Index from the sequences of a FASTA file (plain or .gz, wrapped or not): the file is read whole by the host reader,
+    the index is built on the GPU (engine.index_from_sequences).  Node i is the i-th sequence; single_node: every
+    sequence is node 0.  ambiguous_bases "skip" (the default HERE, unlike `map`): no k-mer over N or an IUPAC letter — an N run
+    of a reference must not become a poly-A entry; "a": the reference's table, N counted as A.
+    Returns (KmerIndex, names, info): names[i] names node i; info holds n_seqs, n_bases, n_windows, n_pairs, n_entries, modulo
+    and n_full_windows (the windows there would be without breaks)."""
+    from . import reads_io
+    from .kmer_index import KmerIndex
+    from .util import ambiguous_skip_lut
+    if ambiguous_bases not in ("skip", "a"):
+        raise ValueError("ambiguous_bases must be 'skip' or 'a'")
+    k = int(k)
+    lut = ambiguous_skip_lut() if ambiguous_bases == "skip" else None
+    if lut is not None and k < 2:
+        raise ValueError("--ambiguous-bases skip needs -k 2 or more")
+    probe = reads_io.probe_input(path)
+    if probe.fmt != "fasta":
+        raise ValueError("index: %s holds %s records, an index is built from FASTA sequences (convert it, e.g. "
+                         "`samtools fasta` / `seqtk seq -A`, or pass the reference the reads were aligned to)"
+                         % (path, probe.fmt.upper()))
+    with reads_io._open(path) as f:
+        parts = []
+        while True:
+            piece = f.read(1 << 26)
+            if not piece:
+                break
+            parts.append(bytes(piece))
+    buf = np.frombuffer(b"".join(parts), dtype=np.uint8)
+    batch, names = reads_io.parse_fasta_named(buf)
+    offsets = np.ascontiguousarray(batch.offsets, dtype=np.int64)
+    n_seqs = offsets.shape[0] - 1
+    full = int(np.maximum(np.diff(offsets) - k + 1, 0).sum())
+    from . import _lib
+    # (without breaks every window is a pair: refused before the file's bytes cross to the device; with breaks the library counts)
+    if full * (2 if both_strands else 1) > _lib.SEQIDX_MAX_PAIRS and lut is None:
+        raise ValueError("index: %s holds %d windows of %d bases%s, one build takes at most %d (k-mer, node) pairs: split the "
+                         "FASTA file and build one index per part" % (path, full, k, ", twice that on both strands" if both_strands
+                                                                      else "", _lib.SEQIDX_MAX_PAIRS))
+    nodes = np.zeros(n_seqs, dtype=np.int32) if single_node else None
+    info = {}
+    try:
+        index = KmerIndex.from_sequences_gpu(np.ascontiguousarray(batch.bases), offsets, k=k, nodes=nodes, lut=lut,
+                                             both_strands=both_strands, modulo=modulo, device=device, info=info)
+    except ValueError as exc:
+        if "KMM_SEQIDX_MAX_PAIRS" in str(exc):
+            raise ValueError("index: %s is above the limit of one build (%s): split the FASTA file and build one index per part"
+                             % (path, exc)) from None
+        raise
+    info.update(n_seqs=n_seqs, n_bases=int(offsets[-1]), n_full_windows=full)
+    return index, names, info

@@ -114,6 +114,26 @@ def parse_fasta_block(buf):
     return ReadBatch(bases, offsets)
 
 
+def parse_fasta_named(buf):
+    """parse_fasta_block plus the names: (ReadBatch, names).  A name is the header line up to the first blank, without the
+    '>' (and without a carriage return): what an aligner would call the sequence."""
+    buf = np.asarray(buf, dtype=np.uint8)
+    batch = parse_fasta_block(buf)
+    if buf.shape[0] == 0:
+        return batch, []
+    nl = np.flatnonzero(buf == _NL)
+    line_start = np.concatenate([np.zeros(1, dtype=np.int64), nl + 1])
+    line_start = line_start[line_start < buf.shape[0]]
+    line_end = np.concatenate([nl, np.array([buf.shape[0]], dtype=np.int64)])[:line_start.shape[0]]
+    is_header = buf[line_start] == ord(">")
+    raw = buf.tobytes()
+    names = []
+    for s, e in zip(line_start[is_header].tolist(), line_end[is_header].tolist()):
+        words = raw[s + 1:e].split(None, 1)
+        names.append(words[0].decode("utf-8", "replace") if words and not raw[s + 1:s + 2].isspace() else "")
+    return batch, names
+
+
 def _last_record_boundary(buf, fmt, at_eof):
     """Number of leading bytes of buf that form whole records."""
     if at_eof:
