@@ -507,6 +507,48 @@ int kmm_read_hits(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_of
                   uint32_t *windows);
 
 /*
+ * kmm_read_nodes — per read, the node that most of its k-mers map to.  Fused from read bytes to the answer:
+ * one walk of kmm_read_hits's kernel counts the votes of every read, a second adds each vote to the (read, node) cell of a
+ * hash table in device memory, and the cells are reduced to the per-read outputs.  No k-mer is written to memory.
+ * Reads (read_offsets / n_reads / read_len), bases, lut, host-or-device pointers, errors and synchronisation are exactly
+ * those of kmm_read_hits: ragged or uniform reads, KMM_LUT_BREAK entries are breaks, k == 1 with a break table is
+ * KMM_ERR_INVALID_ARG.
+ * Votes: votes[r][v] is what kmm_map_reads with the same k, max_index_lookup_frequency, also_revcomp and lut adds to
+ * node_counts[v] when it is given read r alone: one vote per entry l of bucket q % modulo with kmers[l] == q and
+ * frequencies[l] <= max_index_lookup_frequency (a k-mer under three nodes gives each node one vote; the filter applies
+ * per entry); with also_revcomp the same again for the reverse complement of q (a palindrome in the index votes twice, as
+ * map counts it twice); windows over a break give nothing.
+ * Outputs, each an array of n_reads entries in host or device memory (independently), written in full; all but best_node
+ * may be NULL:
+ *   - best_node[r] (int32): the node with the most votes, the smallest node id among equals, -1 when the read has no vote;
+ *   - best_votes[r]: that node's votes (0 with -1);
+ *   - second_votes[r]: the largest vote count among the other nodes, 0 if there is none (best_votes - second_votes is the
+ *     margin; 0: a tie);
+ *   - total_votes[r]: the sum over all nodes;
+ *   - n_nodes[r]: the number of distinct nodes with at least one vote.
+ * Counts are taken modulo 2^32.  The outputs do not depend on the order the GPU's threads ran in: the same call gives the
+ * same bytes.
+ * Rounds: the reads are served in rounds of whole reads (at least one), cut so that the votes of a round fit a table of
+ * table_bytes: 16 bytes per slot, two slots per vote.  table_bytes == 0: 4 GiB; values below 64 KiB count as 64 KiB; negative:
+ * KMM_ERR_INVALID_ARG.  The table is allocated at the size the round needs, never at the target; a single read whose
+ * votes need more than the target gets the table it needs (at most 2^31 - 1 votes: beyond, KMM_ERR_INVALID_ARG).  A table of
+ * up to 256 MiB stays with the handle for the next call; a larger one is freed when the call returns.  *n_rounds (may be
+ * NULL): the rounds the reads were cut into (0 when there was nothing to look up); rounds whose reads have no vote launch
+ * nothing and are counted all the same.  The answer does not depend on the rounds.
+ * A pure query like kmm_read_hits: node counts, per-k-mer counts, kmm_get_stats, the record-hits and keep queues, the
+ * compressed readers' stream state, every counter of kmm_get_param and any sticky error are left as they were.  Served by
+ * the direct view on every index ("radix_available" 0 included).
+ * Errors come from the call itself and are never left on the handle: a byte with table entry 0xFF is
+ * KMM_ERR_INVALID_BASE, the message naming its flat position; decreasing offsets, read_offsets[0] != 0, best_node == NULL
+ * with n_reads > 0, k out of range and negative table_bytes are KMM_ERR_INVALID_ARG.  After an error the outputs are
+ * unspecified.  n_reads == 0 or no bases at all is KMM_OK, the outputs that exist filled with -1 (best_node) and 0.
+ */
+int kmm_read_nodes(kmm_index_t *idx, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len,
+                   int k, int max_index_lookup_frequency, int also_revcomp, const uint8_t *lut, int64_t table_bytes,
+                   int32_t *best_node, uint32_t *best_votes, uint32_t *second_votes, uint32_t *total_votes,
+                   uint32_t *n_nodes, int64_t *n_rounds);
+
+/*
  * The record-hits mode: kmm_read_hits for reads that are still records.  kmm_set_param(idx, "record_hits", v):
  * 0 off (default), 1 hits, 2 hits and windows; any other value is KMM_ERR_INVALID_ARG; kmm_get_param returns it.  While the mode
  * is on:

@@ -84,6 +84,8 @@ SIGNATURES = {
     "kmm_seq_index_modulo": (_c.c_uint64, [_c.c_int64]),
     "kmm_in_index": (_c.c_int, [_P, _P, _c.c_int64, _P]),
     "kmm_read_hits": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
+    "kmm_read_nodes": (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_int64,
+                                  _P, _P, _P, _P, _P, _P]),
     "kmm_take_record_hits": (_c.c_int, [_P, _P, _P, _c.c_int64, _P]),
     "kmm_take_kept_records": (_c.c_int, [_P, _P, _c.c_int64, _P, _P]),
     "kmm_map_record_pairs": (_c.c_int, [_P, _P, _c.c_int64, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),

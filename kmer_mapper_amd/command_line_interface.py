@@ -964,6 +964,117 @@ def _save_read_hits(args, hits, wins):
     return (hits, wins) if args.windows else hits
 
 
+def check_assign_reads_input(fmt, world_size, k, ambiguous_bases, min_votes, min_margin):
+    """`kmer_mapper assign-reads` takes FASTA / FASTQ (plain or .gz) in one process; what it does not serve is refused before
+    the index is read, with what to do instead."""
+    if fmt in ("sam", "bam"):
+        raise ValueError("assign-reads does not read %s files: per-read node assignment is implemented for FASTA and FASTQ "
+                         "(plain or .gz) only; SAM and BAM input is out of scope (convert the reads to FASTQ first, e.g. with "
+                         "`kmer_mapper select-reads --bam-to-fastq`)" % fmt.upper())
+    if world_size > 1:
+        raise ValueError("assign-reads runs in one process: WORLD_SIZE=%d (torchrun) is out of scope, run it without torchrun"
+                         % world_size)
+    if ambiguous_bases == "skip" and k < 2:
+        raise ValueError("--ambiguous-bases skip needs -k 2 or more")
+    if min_votes < 0:
+        raise ValueError("--min-votes %d is negative: give 0 or more (1, the default, assigns every read with a vote)" % min_votes)
+    if min_margin < 0:
+        raise ValueError("--min-margin %d is negative: give 0 or more (0, the default, lets a tie go to the smallest node id)"
+                         % min_margin)
+
+
+def assign_rule(best_node, best_votes, second_votes, min_votes=1, min_margin=0):
+    """The node a read is assigned to: its best node, or -1 when best_votes < min_votes or best_votes - second_votes <
+    min_margin (a read without a vote has best_node -1 already) -> int32."""
+    best_votes, second_votes = np.asarray(best_votes, dtype=np.int64), np.asarray(second_votes, dtype=np.int64)
+    ok = (best_votes >= min_votes) & (best_votes - second_votes >= min_margin)
+    return np.where(ok, np.asarray(best_node, dtype=np.int32), np.int32(-1)).astype(np.int32)
+
+
+def read_node_names(path, n_nodes=None):
+    """Line i of `path` names node i (the file `kmer_mapper index --names-output` wrote); fewer lines than nodes are refused
+    (n_nodes None: the lines are read, check_node_names compares them once the node count is known)."""
+    with open(path) as f:
+        names = [line.rstrip("\n") for line in f]
+    return names if n_nodes is None else check_node_names(path, names, n_nodes)
+
+
+def check_node_names(path, names, n_nodes):
+    if len(names) < n_nodes:
+        raise ValueError("--names %s has %d lines and the index has %d nodes: line i names node i; give the file that "
+                         "`kmer_mapper index --names-output` wrote for this index" % (path, len(names), n_nodes))
+    return names
+
+
+def write_assign_summary(path, assigned, n_nodes, names=None):
+    """One line per node and one for the unassigned reads: node id, name, reads assigned, share of all reads."""
+    assigned = np.asarray(assigned)
+    counts = np.bincount(assigned[assigned >= 0], minlength=n_nodes)
+    n = max(assigned.shape[0], 1)
+    with open(path, "w") as f:
+        f.write("node\tname\treads\tshare\n")
+        for v in range(counts.shape[0]):
+            f.write("%d\t%s\t%d\t%.6f\n" % (v, names[v] if names is not None and v < len(names) else "", counts[v], counts[v] / n))
+        rest = int((assigned < 0).sum())
+        f.write("-1\tunassigned\t%d\t%.6f\n" % (rest, rest / n))
+
+
+def assign_reads_file(args):
+    """`kmer_mapper assign-reads`: per read of a FASTA / FASTQ file, in file order, the node most of its k-mers map to
+    (kmm_read_nodes) -> <out>.npy (int32, -1: unassigned), <out>.best_votes.npy, <out>.second_votes.npy, <out>.total_votes.npy
+    (uint32), and with --summary a table of reads per node.  The file is read through the host reader in chunks, as
+    `read-hits` without --device-parser reads it."""
+    k = args.kmer_size
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    probe = probe_input(args.reads)
+    check_assign_reads_input(probe.fmt, world, k, args.ambiguous_bases, args.min_votes, args.min_margin)
+    lut = None
+    if args.ambiguous_bases == "skip":
+        from .util import ambiguous_skip_lut
+        lut = ambiguous_skip_lut()
+    names = read_node_names(args.names) if args.names else None            # (read before the index: a missing file fails here)
+    kmer_index = _get_kmer_index_from_args(args)
+    max_node_id = kmer_index.max_node_id() if hasattr(kmer_index, "max_node_id") else int(np.max(kmer_index._nodes))
+    n_nodes = max_node_id + 1
+    if names is not None:                                                   # (the node count comes from the index: before the GPU)
+        check_node_names(args.names, names, n_nodes)
+    revcomp = bool(args.map_reverse_complements)
+    parts = [[], [], [], []]
+    dev = DeviceIndex.from_index(kmer_index, max_node_id, device=args.device)
+    try:
+        for chunk in prefetch(read_chunks(args.reads, min_chunk_size=args.chunk_size)):
+            L = chunk.uniform_length
+            if L is not None:
+                res = dev.read_nodes(chunk.bases, n_reads=len(chunk), read_len=L, k=k, max_index_lookup_frequency=args.max_hits_per_kmer,
+                                     also_revcomp=revcomp, lut=lut)
+            else:
+                res = dev.read_nodes(chunk.bases, chunk.offsets, k=k, max_index_lookup_frequency=args.max_hits_per_kmer,
+                                     also_revcomp=revcomp, lut=lut)
+            for part, got in zip(parts, (res.best_node, res.best_votes, res.second_votes, res.total_votes)):
+                part.append(got)
+    finally:
+        dev.close()
+    cat = lambda part, dt: np.concatenate(part) if part else np.zeros(0, dt)
+    best_node, best_votes, second_votes, total_votes = (cat(p, dt) for p, dt in zip(parts, (np.int32, np.uint32, np.uint32, np.uint32)))
+    assigned = assign_rule(best_node, best_votes, second_votes, args.min_votes, args.min_margin)
+    n_reads, n_assigned, n_none = assigned.shape[0], int((assigned >= 0).sum()), int((best_node < 0).sum())
+    n_margin = int(((best_votes.astype(np.int64) >= max(args.min_votes, 1)) &
+                    (best_votes.astype(np.int64) - second_votes < args.min_margin)).sum())
+    logging.info("%d reads; %d (%.2f %%) assigned to a node, %d ambiguous (margin below %d), %d without a vote", n_reads, n_assigned,
+                 100.0 * n_assigned / max(n_reads, 1), n_margin, args.min_margin, n_none)
+    if args.output_file is not None:
+        out = str(args.output_file)
+        np.save(out, assigned)
+        np.save(out + ".best_votes", best_votes)
+        np.save(out + ".second_votes", second_votes)
+        np.save(out + ".total_votes", total_votes)
+        logging.info("Saved per-read nodes to %s.npy (votes: .best_votes.npy, .second_votes.npy, .total_votes.npy)" % out)
+    if args.summary:
+        write_assign_summary(args.summary, assigned, n_nodes, names)
+        logging.info("Saved the per-node summary to %s" % args.summary)
+    return assigned
+
+
 class RecordKeepSink(RecordHitsSink):
     """The same hook for `select-reads`: open(dev) sets record-hits mode 2 and the keep rule, drain(dev) takes
     both queues after every map call — so both stay chunk-sized — and appends the kept records' bytes to `out`, a binary file
@@ -1588,6 +1699,35 @@ def build_argument_parser():
                      help="SAM and BAM input only, with --min-base-quality: decode every record's QUAL on the GPU and apply the "
                           "floor to it. Records that store no qualities pass unmasked and are counted in the log.")
     sub.set_defaults(func=read_hits_file)
+
+    sub = subparsers.add_parser("assign-reads", help="Extension: per read, the node (sequence) that most of its k-mers map to")
+    sub.add_argument("-i", "--kmer-index", required=False)
+    sub.add_argument("-b", "--index-bundle", required=False)
+    sub.add_argument("-f", "--reads", required=True, help="Reads in .fa, .fq, .fa.gz or .fq.gz format")
+    sub.add_argument("-k", "--kmer-size", required=False, default=31, type=int)
+    sub.add_argument("-c", "--chunk-size", required=False, type=int, default=2500000, help="N bytes to process in each chunk")
+    sub.add_argument("-o", "--output-file", required=True,
+                     help="<out>.npy: int32, one node id per read in file order, -1: unassigned; also <out>.best_votes.npy, "
+                          "<out>.second_votes.npy and <out>.total_votes.npy (uint32)")
+    sub.add_argument("-I", "--max-hits-per-kmer", required=False, default=1000, type=int,
+                     help="An index entry with a frequency above this gives no vote. Applied as given.")
+    sub.add_argument("-r", "--map-reverse-complements", default=False, type=bool,
+                     help="The reverse complement of every k-mer votes too, as `map -r True` counts it. Default False.")
+    sub.add_argument("--ambiguous-bases", choices=("a", "skip"), default="a",
+                     help="a (default): N is looked up as A and any other letter is an error. skip: no window that contains N "
+                          "or an IUPAC ambiguity letter votes.")
+    sub.add_argument("--min-votes", default=1, type=int, metavar="N",
+                     help="A read whose best node has fewer than N votes is unassigned (-1). Default 1.")
+    sub.add_argument("--min-margin", default=0, type=int, metavar="M",
+                     help="A read whose best node leads the runner-up by fewer than M votes is unassigned (-1). Default 0: a tie "
+                          "goes to the smallest node id.")
+    sub.add_argument("--names", default=None, metavar="FILE",
+                     help="Node names for --summary, line i names node i: the file `kmer_mapper index --names-output` wrote.")
+    sub.add_argument("--summary", default=None, metavar="TSV",
+                     help="Write one line per node and one for the unassigned reads: node id, name, reads assigned, share.")
+    sub.add_argument("--device", default=0, type=int, help="GPU ordinal.")
+    sub.add_argument("-d", "--debug", required=False, help="Set to True to print debug log")
+    sub.set_defaults(func=assign_reads_file)
 
     sub = subparsers.add_parser("select-reads", help="Extension: write the reads whose k-mers hit a kmer index back out")
     sub.add_argument("-i", "--kmer-index", required=False)

@@ -34,6 +34,7 @@
 #include "kmm_radix_plan.hpp" // (plain C++ with standard headers of its own: before the namespace the kernels live in)
 #include "kmm_params.hpp"     // (the same: KmmKnobs, KmmCounters and the parameter table)
 #include "kmm_seqindex_plan.hpp" // (the same: the limits, the table size and the prime search of kmm_seq_index_build)
+#include "kmm_read_nodes_plan.hpp" // (the same: keys, best words, table slots and round cuts of kmm_read_nodes)
 
 namespace {
 
@@ -99,6 +100,7 @@ static double ms_since(std::chrono::steady_clock::time_point a)
 #include "kmm_radix.hpp"
 #include "kmm_build.hpp"
 #include "kmm_seqindex.hpp"
+#include "kmm_read_nodes.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -411,6 +413,7 @@ struct kmm_index : IndexStreams, RxArrays, KmmKnobs, KmmCounters { // (the store
     int rhq_mode = 0;
     DevBuf rhq_hits, rhq_win;
     int64_t rhq_head = 0, rhq_pending = 0, rhq_cap = 0;
+    DevBuf rn_table; // kmm_read_nodes: a round's vote table, kept between calls up to RN_KEEP_TABLE_BYTES
     // the record-keep mode: with "record_keep" 1 the record calls also append the text of every record whose entry
     // passes the keep rule to rkq[0].  ctl (device): {bytes, records} of the queue's true tail, advanced by the kernels; the same
     // pair as a call found it (put back when the call fails); the kept bytes and records of the piece at work.  bound: what
@@ -953,19 +956,28 @@ int launch_read_hits(kmm_index *ix, const ReadsView &rv, int k, int max_freq, in
     return KMM_OK;
 }
 
+// Flat reads in front of k_read_hits's front end: what kmm_read_hits and kmm_read_nodes (kmm_read_nodes_host.hpp) share.
 // The ReadsView is prepared as map_reads_common prepares it (staging, lookup table, the uniform front end for reads of 16
 // bases and more without breaks, else the read-start bitset and k_mark_breaks), with two differences: the bad-byte and
 // bad-offset words are the call's own (in the stage's aux buffer, never ix->first_bad), and reads of one length that take
 // the ragged front end get no offsets array: their starts and their read ids are arithmetic.
-int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len, int k,
-                   int max_freq, int also_revcomp, const uint8_t *lut, uint32_t *hits, uint32_t *windows)
+struct FlatReads {
+    Stage *s = nullptr;
+    ReadsView rv;
+    bool uniform = false, uniform_kernel = false, has_break = false, staged = false;
+    int64_t total = 0, n_tiles = 0;
+    unsigned long long *d_bad = nullptr;  // aux [0, 256): the call's three error words
+    const int64_t *tile_first = nullptr;  // ragged reads: the first read of every tile (k_rh_tile_reads)
+};
+
+// The number of base bytes, and what is wrong with the arguments that say it.
+int flat_reads_total(const char *who, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len,
+                     int64_t *out)
 {
-    const bool uniform = read_offsets == nullptr;
-    HIPCHK(hipSetDevice(ix->device));
     int64_t total = 0;
-    if (uniform) {
+    if (!read_offsets) {
         if (read_len > 0 && n_reads > INT64_MAX / read_len)
-            return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: n_reads * read_len overflows");
+            return fail(KMM_ERR_INVALID_ARG, "%s: n_reads * read_len overflows", who);
         total = n_reads * read_len;
     } else {
         int64_t ends[2] = {0, 0};
@@ -977,13 +989,105 @@ int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offs
             ends[1] = read_offsets[n_reads];
         }
         if (ends[0] != 0)
-            return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: read_offsets[0] must be 0 (got %lld)", (long long)ends[0]);
+            return fail(KMM_ERR_INVALID_ARG, "%s: read_offsets[0] must be 0 (got %lld)", who, (long long)ends[0]);
         if (ends[1] < 0)
-            return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: read_offsets[n_reads] negative");
+            return fail(KMM_ERR_INVALID_ARG, "%s: read_offsets[n_reads] negative", who);
         total = ends[1];
     }
     if (total > 0 && !bases)
-        return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: bases is NULL");
+        return fail(KMM_ERR_INVALID_ARG, "%s: bases is NULL", who);
+    *out = total;
+    return KMM_OK;
+}
+
+// total > 0.  Takes the next stage, stages what lies in host memory, builds the view and makes room: aux holds the error words
+// and aux_bytes more behind them (at (uint8_t *)fr.d_bad + 256: the caller's).  On return the copies are ordered before the
+// handle's stream and the error words are NO_BAD there.
+int flat_reads_stage(kmm_index *ix, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len,
+                     int64_t total, const uint8_t *lut, size_t aux_bytes, FlatReads &fr)
+{
+    fr.uniform = read_offsets == nullptr;
+    fr.total = total;
+    KMMCHK(ensure_direct(ix));
+    Stage &s = next_stage(ix);
+    fr.s = &s;
+    KMMCHK(stage_acquire(ix, s));
+    ReadsView &rv = fr.rv;
+    memset(&rv, 0, sizeof rv);
+    KMMCHK(stage_in<uint8_t>(ix, s.bases, bases, (size_t)total, &rv.bases, &fr.staged));
+    KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &fr.staged, &fr.has_break));
+    if (!fr.uniform)
+        KMMCHK(stage_in<int64_t>(ix, s.offsets, read_offsets, (size_t)(n_reads + 1), &rv.offsets, &fr.staged));
+    rv.total = total;
+    rv.n_reads = n_reads;
+    if (fr.uniform) {
+        rv.read_len = (uint64_t)read_len;
+        rv.read_len_magic = magic_for((uint64_t)read_len);
+    }
+    fr.n_tiles = (total + TILE_T - 1) / TILE_T;
+    KMMCHK(ensure(s.aux, 256 + aux_bytes));
+    fr.d_bad = (unsigned long long *)s.aux.p;
+    rv.first_bad = fr.d_bad;
+    fr.uniform_kernel = fr.uniform && read_len >= 16 && !fr.has_break;
+    if (!fr.uniform_kernel) {
+        rv.n_start_words = total / 32 + 2;
+        KMMCHK(ensure(s.start_bits, (size_t)rv.n_start_words * 4));
+        rv.start_bits = (const uint32_t *)s.start_bits.p;
+    }
+    if (!fr.uniform) {
+        KMMCHK(ensure(s.tile_first, (size_t)(fr.n_tiles + 1) * 8));
+        fr.tile_first = (const int64_t *)s.tile_first.p;
+    }
+    KMMCHK(stage_copies_done(ix));
+    HIPCHK(hipMemsetAsync(fr.d_bad, 0xFF, 3 * sizeof(unsigned long long), ix->stream));
+    return KMM_OK;
+}
+
+// What the ragged front end reads (nothing for fr.uniform_kernel): read starts and break bytes into the bitset, the offsets
+// checked, the first read of every tile.
+int flat_reads_mark(kmm_index *ix, const FlatReads &fr)
+{
+    if (fr.uniform_kernel)
+        return KMM_OK;
+    const ReadsView &rv = fr.rv;
+    uint32_t *bits = (uint32_t *)fr.s->start_bits.p;
+    HIPCHK(hipMemsetAsync(bits, 0, (size_t)rv.n_start_words * 4, ix->stream));
+    if (fr.uniform)
+        hipLaunchKernelGGL(k_mark_uniform_starts, dim3(grid_for(ix, (rv.n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                           rv.n_reads, (int64_t)rv.read_len, bits);
+    else
+        hipLaunchKernelGGL(k_mark_starts, dim3(grid_for(ix, (rv.n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                           rv.offsets, rv.n_reads, fr.total, bits);
+    if (fr.has_break) // every break byte: a one-base read
+        hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (fr.total + 256 * 16 * MARK_U - 1) / (256 * 16 * MARK_U), 8)), dim3(256), 0,
+                           ix->stream, rv.bases, fr.total, rv.lut, bits);
+    if (!fr.uniform) {
+        hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(ix, (rv.n_reads + 255) / 256, 8)), dim3(256), 0, ix->stream,
+                           rv.offsets, rv.n_reads, fr.d_bad);
+        hipLaunchKernelGGL(k_rh_tile_reads, dim3(grid_for(ix, (fr.n_tiles + 256) / 256, 8)), dim3(256), 0, ix->stream,
+                           rv.offsets, rv.n_reads, fr.total, fr.n_tiles, (int64_t)TILE_T, (int64_t *)fr.s->tile_first.p);
+    }
+    HIPCHK(hipGetLastError());
+    return KMM_OK;
+}
+
+// errors of this call are this call's: nothing is left on the handle
+int flat_reads_errors(const char *who, const unsigned long long (&bad)[3])
+{
+    if (bad[2] != NO_BAD)
+        return fail(KMM_ERR_INVALID_ARG, "%s: read_offsets is not non-decreasing at read %llu", who, bad[2]);
+    if (bad[0] != NO_BAD)
+        return fail(KMM_ERR_INVALID_BASE, "%s: read byte at offset %llu is not a nucleotide under the lookup table "
+                    "(the reference's DNA encoder raises here)", who, bad[0]);
+    return KMM_OK;
+}
+
+int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len, int k,
+                   int max_freq, int also_revcomp, const uint8_t *lut, uint32_t *hits, uint32_t *windows)
+{
+    HIPCHK(hipSetDevice(ix->device));
+    int64_t total = 0;
+    KMMCHK(flat_reads_total("kmm_read_hits", bases, read_offsets, n_reads, read_len, &total));
     const bool hits_dev = is_device_ptr(hits), win_dev = windows && is_device_ptr(windows);
     const size_t out_bytes = (size_t)n_reads * 4;
     if (total == 0) { // nothing to look up: the outputs are written in full all the same
@@ -997,69 +1101,24 @@ int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offs
         ix->read_hits_calls++;
         return KMM_OK;
     }
-    KMMCHK(ensure_direct(ix));
-    Stage &s = next_stage(ix);
-    KMMCHK(stage_acquire(ix, s));
-    bool staged = false;
-    ReadsView rv;
-    memset(&rv, 0, sizeof rv);
-    KMMCHK(stage_in<uint8_t>(ix, s.bases, bases, (size_t)total, &rv.bases, &staged));
-    bool has_break = false;
-    KMMCHK(resolve_lut(ix, s, lut, &rv.lut, &staged, &has_break));
-    if (!uniform)
-        KMMCHK(stage_in<int64_t>(ix, s.offsets, read_offsets, (size_t)(n_reads + 1), &rv.offsets, &staged));
-    rv.total = total;
-    rv.n_reads = n_reads;
-    if (uniform) {
-        rv.read_len = (uint64_t)read_len;
-        rv.read_len_magic = magic_for((uint64_t)read_len);
-    }
-    const int64_t n_tiles = (total + TILE_T - 1) / TILE_T;
-    // aux: [0, 256) the call's three error words; then the outputs of a caller that gave host arrays
+    // aux behind the error words: the outputs of a caller that gave host arrays
     const size_t out_slot = (out_bytes + 255) & ~(size_t)255;
-    KMMCHK(ensure(s.aux, 256 + 2 * out_slot));
-    unsigned long long *d_bad = (unsigned long long *)s.aux.p;
-    uint32_t *d_hits = hits_dev ? hits : (uint32_t *)((uint8_t *)s.aux.p + 256);
-    uint32_t *d_win = !windows ? nullptr : (win_dev ? windows : (uint32_t *)((uint8_t *)s.aux.p + 256 + out_slot));
-    rv.first_bad = d_bad;
-    const bool uniform_kernel = uniform && read_len >= 16 && !has_break;
-    const int64_t n_words = total / 32 + 2;
-    if (!uniform_kernel)
-        KMMCHK(ensure(s.start_bits, (size_t)n_words * 4));
-    if (!uniform)
-        KMMCHK(ensure(s.tile_first, (size_t)(n_tiles + 1) * 8));
-    KMMCHK(stage_copies_done(ix));
-    HIPCHK(hipMemsetAsync(d_bad, 0xFF, 3 * sizeof(unsigned long long), ix->stream));
+    FlatReads fr;
+    KMMCHK(flat_reads_stage(ix, bases, read_offsets, n_reads, read_len, total, lut, 2 * out_slot, fr));
+    uint8_t *aux = (uint8_t *)fr.d_bad + 256;
+    uint32_t *d_hits = hits_dev ? hits : (uint32_t *)aux;
+    uint32_t *d_win = !windows ? nullptr : (win_dev ? windows : (uint32_t *)(aux + out_slot));
     HIPCHK(hipMemsetAsync(d_hits, 0, out_bytes, ix->stream));
     if (d_win)
         HIPCHK(hipMemsetAsync(d_win, 0, out_bytes, ix->stream));
     const int rc_flag = also_revcomp ? 1 : 0;
-    if (uniform_kernel) {
-        KMMCHK(launch_read_hits<MODE_UNIFORM>(ix, rv, k, max_freq, rc_flag, nullptr, d_hits, d_win));
-    } else {
-        rv.start_bits = (const uint32_t *)s.start_bits.p;
-        rv.n_start_words = n_words;
-        HIPCHK(hipMemsetAsync(s.start_bits.p, 0, (size_t)n_words * 4, ix->stream));
-        if (uniform)
-            hipLaunchKernelGGL(k_mark_uniform_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
-                               n_reads, read_len, (uint32_t *)s.start_bits.p);
-        else
-            hipLaunchKernelGGL(k_mark_starts, dim3(grid_for(ix, (n_reads + 256) / 256, 8)), dim3(256), 0, ix->stream,
-                               rv.offsets, n_reads, total, (uint32_t *)s.start_bits.p);
-        if (has_break) // every break byte: a one-base read
-            hipLaunchKernelGGL(k_mark_breaks, dim3(grid_for(ix, (total + 256 * 16 * MARK_U - 1) / (256 * 16 * MARK_U), 8)), dim3(256), 0,
-                               ix->stream, rv.bases, total, rv.lut, (uint32_t *)s.start_bits.p);
-        if (!uniform) {
-            hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(ix, (n_reads + 255) / 256, 8)), dim3(256), 0, ix->stream,
-                               rv.offsets, n_reads, d_bad);
-            hipLaunchKernelGGL(k_rh_tile_reads, dim3(grid_for(ix, (n_tiles + 256) / 256, 8)), dim3(256), 0, ix->stream,
-                               rv.offsets, n_reads, total, n_tiles, (int64_t)TILE_T, (int64_t *)s.tile_first.p);
-        }
-        HIPCHK(hipGetLastError());
-        KMMCHK(launch_read_hits<MODE_GENERAL>(ix, rv, k, max_freq, rc_flag, (const int64_t *)s.tile_first.p, d_hits, d_win));
-    }
+    KMMCHK(flat_reads_mark(ix, fr));
+    if (fr.uniform_kernel)
+        KMMCHK(launch_read_hits<MODE_UNIFORM>(ix, fr.rv, k, max_freq, rc_flag, nullptr, d_hits, d_win));
+    else
+        KMMCHK(launch_read_hits<MODE_GENERAL>(ix, fr.rv, k, max_freq, rc_flag, fr.tile_first, d_hits, d_win));
     unsigned long long bad[3] = {NO_BAD, NO_BAD, NO_BAD};
-    hipError_t e = hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ix->stream);
+    hipError_t e = hipMemcpyAsync(bad, fr.d_bad, sizeof bad, hipMemcpyDeviceToHost, ix->stream);
     if (e == hipSuccess && !hits_dev)
         e = hipMemcpyAsync(hits, d_hits, out_bytes, hipMemcpyDeviceToHost, ix->stream);
     if (e == hipSuccess && windows && !win_dev)
@@ -1068,16 +1127,13 @@ int read_hits_impl(kmm_index *ix, const uint8_t *bases, const int64_t *read_offs
         e = hipStreamSynchronize(ix->stream);
     if (e != hipSuccess)
         return fail(KMM_ERR_HIP, "kmm_read_hits: %s", hipGetErrorString(e));
-    KMMCHK(stage_release(ix, s, staged));
-    // errors of this call are this call's: nothing is left on the handle
-    if (bad[2] != NO_BAD)
-        return fail(KMM_ERR_INVALID_ARG, "kmm_read_hits: read_offsets is not non-decreasing at read %llu", bad[2]);
-    if (bad[0] != NO_BAD)
-        return fail(KMM_ERR_INVALID_BASE, "kmm_read_hits: read byte at offset %llu is not a nucleotide under the lookup table "
-                    "(the reference's DNA encoder raises here)", bad[0]);
+    KMMCHK(stage_release(ix, *fr.s, fr.staged));
+    KMMCHK(flat_reads_errors("kmm_read_hits", bad));
     ix->read_hits_calls++;
     return KMM_OK;
 }
+
+#include "kmm_read_nodes_host.hpp" // kmm_read_nodes behind the flat-reads helpers
 
 // ---- the record-hits queue
 // Room for n more entries behind the pending ones, zeroed on the handle's stream; *hits / *windows: the first new entry.  The
@@ -4473,6 +4529,30 @@ int kmm_read_hits(kmm_index_t *ix, const uint8_t *bases, const int64_t *read_off
     KMMCHK(check_k_lut(k, lut));
     return guarded("kmm_read_hits", [&] {
         return read_hits_impl(ix, bases, read_offsets, n_reads, read_len, k, max_freq, also_revcomp, lut, hits, windows);
+    });
+}
+
+int kmm_read_nodes(kmm_index_t *ix, const uint8_t *bases, const int64_t *read_offsets, int64_t n_reads, int64_t read_len, int k,
+                   int max_freq, int also_revcomp, const uint8_t *lut, int64_t table_bytes, int32_t *best_node, uint32_t *best_votes,
+                   uint32_t *second_votes, uint32_t *total_votes, uint32_t *n_nodes, int64_t *n_rounds)
+{
+    if (!ix)
+        return fail(KMM_ERR_INVALID_ARG, "idx is NULL");
+    KMMCHK(check_k(k));
+    if (n_reads < 0 || (!read_offsets && read_len < 0))
+        return fail(KMM_ERR_INVALID_ARG, "kmm_read_nodes: n_reads / read_len negative");
+    if (table_bytes < 0)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_read_nodes: table_bytes negative (0: the default, %lld)", (long long)RN_DEFAULT_TABLE_BYTES);
+    if (n_rounds)
+        *n_rounds = 0;
+    if (n_reads == 0)
+        return KMM_OK;
+    if (!best_node)
+        return fail(KMM_ERR_INVALID_ARG, "kmm_read_nodes: best_node is NULL");
+    KMMCHK(check_k_lut(k, lut));
+    return guarded("kmm_read_nodes", [&] {
+        const RnArgs a{k, max_freq, also_revcomp ? 1 : 0, n_reads, read_len, table_bytes, read_offsets, n_rounds};
+        return read_nodes_impl(ix, bases, lut, a, best_node, best_votes, second_votes, total_votes, n_nodes);
     });
 }
 

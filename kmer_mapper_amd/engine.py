@@ -5,12 +5,16 @@ map_cpu (kmer_mapper/command_line_interface.py:32-56) happens inside `map_reads`
 operator-level `map_kmers` is the drop-in for mapper.pyx:19-72.
 """
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 
 from . import _lib
 
 _P = ctypes.c_void_p
+
+# what DeviceIndex.read_nodes returns (kmm_read_nodes, include/kmm.h)
+ReadNodes = namedtuple("ReadNodes", "best_node best_votes second_votes total_votes n_nodes n_rounds")
 
 
 def _is_torch_tensor(x):
@@ -386,6 +390,46 @@ class DeviceIndex:
         _lib.check(_lib.lib().kmm_read_hits(self._h, b.ptr, optr, n, L, int(k), int(max_index_lookup_frequency),
                                             int(bool(also_revcomp)), t.ptr, hp, wp))
         return (hits, win) if windows else hits
+
+    def read_nodes(self, bases, read_offsets=None, n_reads=None, read_len=None, k=31, max_index_lookup_frequency=1000,
+                   also_revcomp=False, lut=None, table_bytes=0):
+        """kmm_read_nodes: per read, the node that most of its k-mers map to.  A vote is what map_reads would add to a node
+        count for the read alone (one per matching entry, both orientations with also_revcomp, entries above
+        max_index_lookup_frequency left out).  Reads as in read_hits.  Returns ReadNodes(best_node int32, best_votes,
+        second_votes, total_votes, n_nodes uint32, n_rounds int): best_node is the node with the most votes, the smallest id
+        among equals, -1 without a vote; second_votes the most votes among the other nodes.  table_bytes: the target size
+        of a round's vote table (0: the library's default); the answer does not depend on it.  A pure query.
+        numpy in -> numpy out; torch device tensors in -> torch device tensors out."""
+        b = _Arg(bases, np.uint8, "bases")
+        t = _Arg(lut, np.uint8, "lut")
+        if lut is not None and t.n != 256:
+            raise ValueError("lut must have 256 entries")
+        if read_offsets is not None:
+            o = _Arg(read_offsets, np.int64, "read_offsets")
+            if o.n < 1:
+                raise ValueError("read_offsets needs n_reads+1 entries")
+            n, L, optr = o.n - 1, 0, o.ptr
+        else:
+            if n_reads is None or read_len is None:
+                raise ValueError("read_nodes needs read_offsets, or n_reads and read_len")
+            n, L, optr = int(n_reads), int(read_len), None
+            if n < 0 or L < 0:
+                raise ValueError("n_reads / read_len negative")
+            if b.n < n * L:
+                raise ValueError("bases holds %d bytes, need n_reads*read_len=%d" % (b.n, n * L))
+        if _is_torch_tensor(bases) and bases.is_cuda:
+            import torch
+            dt = getattr(torch, "uint32", torch.int32)
+            outs = [torch.full((n,), -1, dtype=torch.int32, device=bases.device)]
+            outs += [torch.zeros(n, dtype=dt, device=bases.device) for _ in range(4)]
+            ptrs = [_P(x.data_ptr()) for x in outs]
+        else:
+            outs = [np.full(n, -1, dtype=np.int32)] + [np.zeros(n, dtype=np.uint32) for _ in range(4)]
+            ptrs = [x.ctypes.data_as(_P) for x in outs]
+        rounds = ctypes.c_int64(0)
+        _lib.check(_lib.lib().kmm_read_nodes(self._h, b.ptr, optr, n, L, int(k), int(max_index_lookup_frequency),
+                                             int(bool(also_revcomp)), t.ptr, int(table_bytes), *ptrs, ctypes.byref(rounds)))
+        return ReadNodes(*outs, rounds.value)
 
     def record_hits(self, on=True, windows=False, min_base_quality=0):
         """The record-hits mode (include/kmm.h): while it is on, map_records / map_bgzf / map_gzip / map_bam

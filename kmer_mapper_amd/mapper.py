@@ -120,6 +120,18 @@ def read_hits(index, reads, k=31, max_index_lookup_frequency=1000, also_revcomp=
                                                                also_revcomp=also_revcomp, lut=lut, windows=windows)
 
 
+def read_nodes(index, reads, k=31, max_index_lookup_frequency=1000, also_revcomp=False, lut=None, table_bytes=0, device=0):
+    """Extension: per read, the node that most of its k-mers map to -> engine.ReadNodes (best_node, best_votes, second_votes,
+    total_votes, n_nodes, n_rounds; DeviceIndex.read_nodes).  `reads`: what util.as_read_batch takes.  Opens a handle for the
+    call and closes it: nothing of the index stays on the device."""
+    from .util import as_read_batch
+    batch = as_read_batch(reads)
+    max_node_id = int(np.max(index._nodes)) if len(index._nodes) else 0
+    with DeviceIndex.from_index(index, max_node_id, device=device) as dev:
+        return dev.read_nodes(batch.bases, batch.offsets, k=k, max_index_lookup_frequency=max_index_lookup_frequency,
+                              also_revcomp=also_revcomp, lut=lut, table_bytes=table_bytes)
+
+
 def _floor_on(dev, windows, min_base_quality, use_record_qual):
     """The record-hits mode with its floor on a cached handle; returns what _floor_off puts back."""
     before = dev.get_param("use_record_qual")
